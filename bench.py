@@ -33,6 +33,8 @@ timing : `value` = the W warm-up + K timed steps behind --preheat-s seconds (def
          work of the process are reported beside it (`cold_start_window`: what rounds 1-5 printed), and `steady_state` (1000
          more steps) behind it.  roofline.frac is on the ALGORITHMIC bytes (2N + 5P); frac_actual / frac_of_achievable on the
          bytes the chip moved (counters) over 8 TB/s / over this board's plain streaming read.
+--full : a plain run sets up, preheats, warms up, times the K steps (writes --dump-outputs DIR) and prints the line; the rest
+         (cold_start_window, steady_state, gather_every, config5, the secondary lines, board, cpu_baseline, parity) needs --full.
 
 Prints ONE JSON line on rank 0.  The CPU oracle is used only as the checker / cpu_baseline leg.
 """
@@ -254,7 +256,16 @@ def parse():
     p.add_argument("--preheat-s", type=float, default=3.0,
                    help="seconds of the same step, untimed, in front of the W warm-up + K timed steps (the chip's clock ramp and "
                         "first heating: DESIGN.md section 8); 0: none -- the W + K steps are then the first GPU work of the process, "
-                        "as in rounds 1-5 (the default run reports that window too: cold_start_window)")
+                        "as in rounds 1-5 (--full reports that window too: cold_start_window)")
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline: cold_start_window, steady_state, gather_every, config5 / config5_per_gpu, "
+                        "pair_mode, regimes, two_streams_one_gpu, config3 / config4, host_path, board, cpu_baseline and the "
+                        "parity checks (the --no-* options above select among them).  Without it a run sets up, warms up, "
+                        "times the K steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the timed path handed its caller in its last step to DIR/<name>.npy (float64 / float32, "
+                        "a fixed seeded sample where the output is large): the same arguments give the same inputs, so two "
+                        "builds can be compared output for output")
     return p.parse_args()
 
 
@@ -507,6 +518,42 @@ def payload_digest(o, xs, df):
             int((df[:pn].to(torch.int64) * w).sum().item())]
 
 
+DUMP_SAMPLE = 1 << 20   # --dump-outputs: entries of the packed stream (and bytes of the state) kept when there are more
+DUMP_SEED = 20240607
+
+
+def dump_outputs(dirname, d_off, d_xs, d_df, state=None):
+    """--dump-outputs: what the timed path handed its caller in its last step, as DIR/<name>.npy (34 MB at most):
+    offsets     : the per-frame offsets into the packed stream, in full (float64)
+    xs_sum, diff_sum : per frame, the sums of the indices and of the differences over EVERY entry (float64, exact)
+    pos, xs, diff    : the entries at DUMP_SAMPLE positions of the packed stream drawn with DUMP_SEED (all of them when
+                       there are fewer): positions and indices float64, differences float32
+    state_pos, state : stream mode, the state carried into the next step at DUMP_SAMPLE seeded positions (float32)."""
+    os.makedirs(dirname, exist_ok=True)
+    dev = d_xs.device
+    off = d_off.cpu().numpy().view(np.uint32).astype(np.int64)
+    p = int(off[-1])
+    assert p <= d_xs.numel(), "output capacity too small for this stream"
+    rng = np.random.default_rng(DUMP_SEED)
+    pos = np.unique(rng.integers(0, p, DUMP_SAMPLE)) if p > DUMP_SAMPLE else np.arange(p, dtype=np.int64)
+    ends = torch.from_numpy(off).to(dev)
+
+    def per_frame_sums(v):
+        c = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(v[:p].to(torch.int64), 0)])
+        return (c[ends[1:]] - c[ends[:-1]]).cpu().numpy().astype(np.float64)
+
+    t_pos = torch.from_numpy(pos).to(dev)
+    arrays = {"offsets": off.astype(np.float64), "xs_sum": per_frame_sums(d_xs), "diff_sum": per_frame_sums(d_df),
+              "pos": pos.astype(np.float64), "xs": d_xs[t_pos].cpu().numpy().astype(np.float64),
+              "diff": d_df[t_pos].cpu().numpy().astype(np.float32)}
+    if state is not None:
+        spos = np.unique(rng.integers(0, state.size, DUMP_SAMPLE)) if state.size > DUMP_SAMPLE else np.arange(state.size)
+        arrays["state_pos"] = spos.astype(np.float64)
+        arrays["state"] = state[spos].astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 class Exchange:
     """The job's ONE exchange step: gather-v of every rank's (offsets, xs, diff) of a batch to rank 0 -- below the C-ABI
     (mi355_group_gather: RCCL all-gather of counts + point-to-point sends to the root, csrc/group.hip) when the group
@@ -659,7 +706,8 @@ def main():
     W, H, B, K = args.width, args.height, args.batch, args.steps
     n = 3 * W * H
     rr = args.shard == "roundrobin"
-    smi_before = smi_snapshot() if rank == 0 else None
+    full = args.full
+    smi_before = smi_snapshot() if rank == 0 and full else None
     if rr:   # local frame k is global frame rank + k*world; its predecessor travels with it
         mine = gx.roundrobin_frames(rank, world, B * world)
         base = synth.webcam_frame(-1, W, H, seed=21, device=dev)
@@ -679,7 +727,8 @@ def main():
     from cudavideostream_amd import lib as _L
     core_flags = _L.FLAG_OWN_QUEUES if (args.own_queues == "1" or (args.own_queues == "auto" and (world > 1 or "RANK" in os.environ))) else 0
     core = CUDACore(W, H, max_batch=B, device=local_rank, flags=core_flags)
-    core.set_state(base.cpu().numpy())
+    h_base = base.cpu().numpy()
+    core.set_state(h_base)
     torch.cuda.synchronize()   # the synthetic frames were made on torch's stream
 
     # The exchange step below the C-ABI (mi355_group_gather: RCCL all-gather of counts + point-to-point sends to
@@ -758,19 +807,25 @@ def main():
     # over 18 s: profiles/r05ao_* ... r05as_*).  W + K steps as the first GPU work of a process (W = 5, K = 20: 12 ms) measure
     # that ramp, not the path: they are kept as `cold_start_window` (what rounds 1-5 printed as `value`).  The line's
     # `value` is the same W + K steps behind --preheat-s seconds (default 3) of the same step, untimed: the state a stream
-    # that runs for longer than a few seconds is in.  (`steady_state`, 1000 more steps behind the timed ones, stays as well.)
+    # that runs for longer than a few seconds is in.  (`steady_state`, 1000 more steps behind the timed ones, stays as well,
+    # with --full like the cold window.)
     cold = None
     preheat_steps = 0
     if args.preheat_s > 0:
         for _ in range(args.warmup):
             plain_step()
-        cold = timed_window(K, plain_step)
+        if full:
+            cold = timed_window(K, plain_step)
         tp = time.perf_counter()
         while time.perf_counter() - tp < args.preheat_s:
             for _ in range(64):
                 plain_step()
             preheat_steps += 64
             core.synchronize()
+        # the stream starts again from its base frame: the preheat's length in steps follows the clock, and the outputs of
+        # the last timed step (--dump-outputs) must not
+        if not rr:
+            core.set_state(h_base)
 
     for i in range(args.warmup):
         step(i == args.warmup - 1)   # the last warm-up step also runs the exchange (RCCL sets up its peer channels on first use)
@@ -800,15 +855,17 @@ def main():
         gather_verified = xch.verify(d_off, d_xs, d_df)   # the ranks' digests of THIS batch, before any further step
     g_last = ({"ms": xch.ms, "calls": xch.calls, "bytes": xch.bytes, "ranks_seen": xch.ranks_seen} if xch is not None
               else {"ms": 0.0, "calls": 0, "bytes": 0, "ranks_seen": world if world > 1 else 1})
-    # What the path SUSTAINS: the same step `--steady-steps` times (default 1000: half a second), right behind the
+    if args.dump_outputs and rank == 0:   # the last timed step's outputs, before anything rewrites them
+        dump_outputs(args.dump_outputs, d_off, d_xs, d_df, None if rr else core.get_state())
+    # What the path SUSTAINS (--full): the same step `--steady-steps` times (default 1000: half a second), right behind the
     # timed region.
     steady = None
-    if args.steady_steps > 0:    # (every rank: the same steps between the same barriers, MAX over the ranks, no exchange)
+    if full and args.steady_steps > 0:    # (every rank: the same steps between the same barriers, MAX over the ranks, no exchange)
         steady = (args.steady_steps, timed_window(args.steady_steps, plain_step))
-    # secondary measurement (N > 1): the same job with the gather after EVERY batch -- the exchange at its worst
+    # secondary measurement (N > 1, --full): the same job with the gather after EVERY batch -- the exchange at its worst
     # (every byte of every rank funnelled to one GPU), so that the scaling curve shows what the gather costs
     g_every = None
-    if world > 1 and group is not None and args.gather_every_steps > 0:
+    if full and world > 1 and group is not None and args.gather_every_steps > 0:
         xch.reset()
         K2 = args.gather_every_steps
 
@@ -830,9 +887,9 @@ def main():
     p_total = int(off[-1])
     assert p_total <= cap, "output capacity too small for this stream"
 
-    # BASELINE configs[4] across the ranks of this job (whenever a launcher started it: N > 1, or N = 1 with real RCCL)
+    # BASELINE configs[4] across the ranks of this job (--full, whenever a launcher started it: N > 1, or N = 1 with real RCCL)
     c5 = None
-    if dist is not None and not args.no_config5 and not rr:
+    if full and dist is not None and not args.no_config5 and not rr:
         c5 = config5_across_ranks(args, dist, world, rank, local_rank, dev, cdev, rehearse)
 
     if rank == 0:
@@ -900,27 +957,29 @@ def main():
                           "note": "the same step, untimed, in front of the warm-up + timed steps whose rate is `value`: a chip that "
                                   "has been idle needs ~12 ms of load to reach its clocks and a second or two to settle "
                                   "(profiles/r05ao-r05as); --preheat-s 0: none"}
-        if world == 1 and not args.no_pair and not rr:
+        # the secondary lines, the board and the checks: --full only (a plain run prints what its headline needs)
+        if full and world == 1 and not args.no_pair and not rr:
             out["pair_mode"] = pair_mode(args, core, frames, d_off, d_xs, d_df, cap, n)
             out["regimes"] = regimes(args, dev)
-        if world == 1 and not args.no_pair and not rr:
+        if full and world == 1 and not args.no_pair and not rr:
             out["two_streams_one_gpu"] = two_streams(args, core, frames, base, d_off, d_xs, d_df, cap, dev)
-        if world == 1 and not args.no_filters and not rr:
+        if full and world == 1 and not args.no_filters and not rr:
             out.update(filter_configs(args, dev))
-        if world == 1 and not args.no_config5 and not rr and (W, H) == (1920, 1080):
+        if full and world == 1 and not args.no_config5 and not rr and (W, H) == (1920, 1080):
             out["config5_per_gpu"] = config5_per_gpu(args, dev)
-        if world == 1 and not args.no_host_path:
+        if full and world == 1 and not args.no_host_path:
             out["host_path"] = host_path(args, base, frames)
-        out["board"] = board_fingerprint(core, "right after the timed region")
-        out["board"]["rocm_smi_before"] = smi_before
-        out["board"]["rocm_smi_after"] = smi_snapshot()
-        stream_gbps = out["board"].get("hbm_stream_read_gbps")
-        if stream_gbps:
-            for blk in (out["roofline"], out.get("steady_state")):
-                if blk and blk.get("actual_gbps"):
-                    blk["frac_of_achievable"] = round(blk["actual_gbps"] / stream_gbps, 4)
+        if full:
+            out["board"] = board_fingerprint(core, "right after the timed region")
+            out["board"]["rocm_smi_before"] = smi_before
+            out["board"]["rocm_smi_after"] = smi_snapshot()
+            stream_gbps = out["board"].get("hbm_stream_read_gbps")
+            if stream_gbps:
+                for blk in (out["roofline"], out.get("steady_state")):
+                    if blk and blk.get("actual_gbps"):
+                        blk["frac_of_achievable"] = round(blk["actual_gbps"] / stream_gbps, 4)
         parity_failed = False
-        if world == 1 and not args.no_cpu and not rr:
+        if full and world == 1 and not args.no_cpu and not rr:
             out["cpu_baseline"], headline_ok = cpu_baseline(args, base, frames, dev)
             # parity next to every number of the line (product vs oracle, bit-exact, outside the timed regions)
             par = {"headline": headline_ok}

@@ -31,6 +31,19 @@ def save(name, **arrays):
     print(f"{name}: {os.path.getsize(path)} bytes")
 
 
+def ref_server_cpu_40x30():
+    """The random frames of tests/test_oracle.py::test_cpu_branch_matches_reference_live through oracle/_ref/server_cpu."""
+    rng = np.random.default_rng(7)
+    w, h = 40, 30
+    base = rng.integers(0, 256, 3 * w * h, dtype=np.uint8)
+    frames = rng.integers(0, 256, (8, 3 * w * h), dtype=np.uint8)
+    frames[3] //= 5
+    frames[5] = 255 - frames[5] // 7
+    with tempfile.TemporaryDirectory() as d:
+        out = po.run_ref_server_cpu(base, frames, w, h, d)
+    return dict(width=w, height=h, base=base, frames=frames, out=out)
+
+
 def main():
     po.build()
     rng = np.random.default_rng(20261003)
@@ -46,6 +59,7 @@ def main():
         with tempfile.TemporaryDirectory() as d:
             out = po.run_ref_server_cpu(base, frames, W, H, d)
         save("ref_server_cpu_64x48.npz", width=W, height=H, base=base, frames=frames, out=out)
+        save("ref_server_cpu_40x30.npz", **ref_server_cpu_40x30())
     else:
         print("oracle/_ref/server_cpu not built (no /root/reference): keeping the committed fixture")
 

@@ -14,7 +14,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MOCK = os.path.join(ROOT, "tests", "mock_rccl", "librccl_mock_ipc.so")
-SMALL = ["--width", "640", "--height", "360", "--batch", "8", "--steps", "3", "--warmup", "2", "--gather-every-steps", "2",
+SMALL = ["--full", "--width", "640", "--height", "360", "--batch", "8", "--steps", "3", "--warmup", "2", "--gather-every-steps", "2",
          "--no-cpu", "--no-pair", "--no-filters", "--no-host-path", "--preheat-s", "0.05", "--steady-steps", "20",
          # BASELINE configs[4] across the ranks of the job, at a size the oracle checks in a moment
          "--config5-size", "320", "180", "4", "--config5-steps", "2"]

@@ -9,11 +9,11 @@ say "== gpu suite"; timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/s
 say "== smoke"; timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1 >> $O/log.txt
 say "== soak 3000"; timeout -k 10 500 python tests/soak.py 3000 > $O/soak.txt 2>&1; tail -2 $O/soak.txt >> $O/log.txt
 say "== soak_chain 60"; timeout -k 10 400 python tests/soak_chain.py 60 9 > $O/soak_chain.txt 2>&1; tail -2 $O/soak_chain.txt >> $O/log.txt
-say "== bench.py default"; timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; say "rc=$?"
-say "== bench.py sequential"; MI355_PIPELINE=0 timeout -k 10 400 python bench.py --steps 20 --warmup 5 --no-cpu --no-host-path --no-config5 > $O/bench_sequential.json 2>/dev/null; say "rc=$?"
-say "== bench.py 4K stream"; timeout -k 10 400 python bench.py --steps 20 --warmup 5 --width 3840 --height 2160 --batch 64 --no-cpu --no-host-path --no-filters --no-pair > $O/bench_4k.json 2>/dev/null; say "rc=$?"
-say "== bench.py 4K round-robin pairs"; timeout -k 10 400 python bench.py --steps 20 --warmup 5 --width 3840 --height 2160 --batch 64 --shard roundrobin --no-cpu --no-host-path --no-filters --no-pair > $O/bench_4k_roundrobin.json 2>/dev/null; say "rc=$?"
-say "== bench.py rehearsal, 4 ranks on the one GPU (1080p, 64-frame batches)"; timeout -k 10 400 python bench.py --gpus 4 --rehearse-on-one-gpu --batch 64 --steps 5 --warmup 2 --gather-every-steps 6 --no-cpu > $O/bench_rehearsal4.json 2> $O/bench_rehearsal4.err; say "rc=$?"
+say "== bench.py default"; timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; say "rc=$?"
+say "== bench.py sequential"; MI355_PIPELINE=0 timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 --no-cpu --no-host-path --no-config5 > $O/bench_sequential.json 2>/dev/null; say "rc=$?"
+say "== bench.py 4K stream"; timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 --width 3840 --height 2160 --batch 64 --no-cpu --no-host-path --no-filters --no-pair > $O/bench_4k.json 2>/dev/null; say "rc=$?"
+say "== bench.py 4K round-robin pairs"; timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 --width 3840 --height 2160 --batch 64 --shard roundrobin --no-cpu --no-host-path --no-filters --no-pair > $O/bench_4k_roundrobin.json 2>/dev/null; say "rc=$?"
+say "== bench.py rehearsal, 4 ranks on the one GPU (1080p, 64-frame batches)"; timeout -k 10 400 python bench.py --full --gpus 4 --rehearse-on-one-gpu --batch 64 --steps 5 --warmup 2 --gather-every-steps 6 --no-cpu > $O/bench_rehearsal4.json 2> $O/bench_rehearsal4.err; say "rc=$?"
 say "== run_profile.sh r05"; bash profiles/run_profile.sh r05 5 > $O/run_profile.txt 2>&1; tail -25 $O/run_profile.txt >> $O/log.txt
 say "== filters"; bash profiles/run_profile_filters.sh r05 > $O/run_profile_filters.txt 2>&1; tail -25 $O/run_profile_filters.txt >> $O/log.txt
 say "== pair 1080p apart"; bash profiles/pmc_fw.sh pair1080apart --apart --batch 128 > $O/pmc_pair1080apart.txt 2>&1

@@ -3,7 +3,7 @@
 cd ${GRAFT_REPO_ROOT:-.}
 O=gpurun_out/r05al; mkdir -p $O
 T=$(date -u +%H%M%S)
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $O/bench_$T.json 2> $O/bench_$T.err; echo "rc=$?"
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_$T.json 2> $O/bench_$T.err; echo "rc=$?"
 python3 - $O/bench_$T.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 O=gpurun_out/r05d; mkdir -p $O
 {
 echo "=== rehearsal, direct (2 ranks on the one GPU)"
-timeout -k 10 240 python bench.py --gpus 2 --rehearse-on-one-gpu --width 640 --height 360 --batch 8 --steps 3 --warmup 2 --gather-every-steps 2 --no-cpu --no-pair --no-filters --no-host-path --no-config5 > $O/rehearse.json 2> $O/rehearse.err; echo "rc=$?"; tail -c 1500 $O/rehearse.err; head -c 600 $O/rehearse.json; echo
+timeout -k 10 240 python bench.py --full --gpus 2 --rehearse-on-one-gpu --width 640 --height 360 --batch 8 --steps 3 --warmup 2 --gather-every-steps 2 --no-cpu --no-pair --no-filters --no-host-path --no-config5 > $O/rehearse.json 2> $O/rehearse.err; echo "rc=$?"; tail -c 1500 $O/rehearse.err; head -c 600 $O/rehearse.json; echo
 echo "=== filters parity (conv: store fix, RTZ conversion)"; timeout -k 10 600 python -m pytest tests/test_filters_gpu.py tests/test_fuzz_gpu.py -x -q 2>&1 | tail -5
 for v in new quad new quad; do
   echo "--- filters $v"; LD_LIBRARY_PATH=build/ab/$v timeout -k 5 200 tools/diffbench --filters --batch 192 --steps 5 2>&1 | grep -E "conv3x3|config 4" | cut -c1-200

@@ -11,7 +11,7 @@ done
 done
 for rep in 1 2; do
 for v in fin note; do
-  echo -n "[$v bench] "; MI355DIFF_LIB=$PWD/build/ab/$v/libmi355diff.so timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu --no-host-path --no-config5 2>/dev/null | python3 -c "
+  echo -n "[$v bench] "; MI355DIFF_LIB=$PWD/build/ab/$v/libmi355diff.so timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu --no-host-path --no-config5 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['regimes']

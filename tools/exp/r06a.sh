@@ -8,7 +8,7 @@ O=$PWD/gpurun_out/r06a; mkdir -p $O
 timeout -k 10 600 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc $?" | tee -a $O/summary.txt
 tail -3 $O/pytest.log | tee -a $O/summary.txt
 for i in 1 2; do timeout -k 10 60 tools/compat_pipe 1920 1080 12 2>&1 | tail -1 | tee -a $O/summary.txt; done
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc $?" | tee -a $O/summary.txt
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc $?" | tee -a $O/summary.txt
 python3 - $O/bench.json <<'PY' | tee -a $O/summary.txt
 import json, sys
 try:

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 O=$PWD/gpurun_out/r06c; mkdir -p $O
 timeout -k 10 300 python -m pytest tests/test_filters_gpu.py -m gpu -x -q -k "config3 or binarize" > $O/pytest.log 2>&1; echo "pytest rc $?" | tee -a $O/summary.txt
 tail -15 $O/pytest.log | tee -a $O/summary.txt
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-pair --no-cpu --no-host-path --no-config5 --steady-steps 0 > $O/bench.json 2> $O/bench.err; echo "bench rc $?" | tee -a $O/summary.txt
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-pair --no-cpu --no-host-path --no-config5 --steady-steps 0 > $O/bench.json 2> $O/bench.err; echo "bench rc $?" | tee -a $O/summary.txt
 python3 - $O/bench.json <<'PY' | tee -a $O/summary.txt
 import json, sys
 try:

@@ -27,7 +27,7 @@ for tag, name in (("pmc_f", "FETCH_SIZE"), ("pmc_w", "WRITE_SIZE")):
     for k, v in sorted(acc.items(), key=lambda kv: -sum(kv[1])):
         print(tag, name, "%-90s launches %3d  mean per launch %.1f KB (x 1024 B; FETCH_SIZE: double it for bytes)" % (k, len(v), sum(v) / len(v)))
 PY
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu --no-host-path --no-config5 --steady-steps 0 --no-filters > $O/bench.json 2> $O/bench.err; echo "bench rc $?" | tee -a $O/summary.txt
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu --no-host-path --no-config5 --steady-steps 0 --no-filters > $O/bench.json 2> $O/bench.err; echo "bench rc $?" | tee -a $O/summary.txt
 python3 - $O/bench.json <<'PY' | tee -a $O/summary.txt
 import json, sys
 try:

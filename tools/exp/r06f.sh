@@ -13,7 +13,7 @@ for i in 1 2; do
   timeout -k 10 100 tools/diffbench --regime flip --batch 32 --steps 10 --warmup 30 > $O/flip_plain$i.json 2>/dev/null
   echo "P = N $i: lib-alloc $(grep -o '"kernels_us": [^]]*]' $O/flip_lib$i.json) ($(cat $O/flip_lib$i.err | tr '\n' ' '))  plain $(grep -o '"kernels_us": [^]]*]' $O/flip_plain$i.json)" | tee -a $O/summary.txt
 done
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu --no-host-path --no-config5 --steady-steps 0 --no-filters > $O/bench.json 2> $O/bench.err; echo "bench rc $?" | tee -a $O/summary.txt
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu --no-host-path --no-config5 --steady-steps 0 --no-filters > $O/bench.json 2> $O/bench.err; echo "bench rc $?" | tee -a $O/summary.txt
 python3 - $O/bench.json <<'PY' | tee -a $O/summary.txt
 import json, sys
 try:

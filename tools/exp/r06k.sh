@@ -15,8 +15,8 @@ PY
 }
 for q in default 8 16; do
   if [ $q = default ]; then unset GPU_MAX_HW_QUEUES; else export GPU_MAX_HW_QUEUES=$q; fi
-  timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr 127.0.0.1 --master-port 2953$((RANDOM % 10)) bench.py $A > $O/launcher_$q.json 2> $O/launcher_$q.err
+  timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr 127.0.0.1 --master-port 2953$((RANDOM % 10)) bench.py --full $A > $O/launcher_$q.json 2> $O/launcher_$q.err
   run "launcher GPU_MAX_HW_QUEUES=$q" $O/launcher_$q.json | tee -a $O/summary.txt
-  timeout -k 10 300 python bench.py $A > $O/plain_$q.json 2> $O/plain_$q.err
+  timeout -k 10 300 python bench.py --full $A > $O/plain_$q.json 2> $O/plain_$q.err
   run "plain    GPU_MAX_HW_QUEUES=$q" $O/plain_$q.json | tee -a $O/summary.txt
 done

@@ -15,8 +15,8 @@ PY
 }
 for v in product lowprio mixprio product lowprio; do
   if [ $v = product ]; then unset MI355DIFF_LIB; else export MI355DIFF_LIB=$PWD/build/ab/$v/libmi355diff.so; fi
-  timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr 127.0.0.1 --master-port 2954$((RANDOM % 10)) bench.py $A > $O/launcher_$v.json 2> $O/launcher_$v.err
+  timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr 127.0.0.1 --master-port 2954$((RANDOM % 10)) bench.py --full $A > $O/launcher_$v.json 2> $O/launcher_$v.err
   run "launcher $v" $O/launcher_$v.json | tee -a $O/summary.txt
-  timeout -k 10 300 python bench.py $A > $O/plain_$v.json 2> $O/plain_$v.err
+  timeout -k 10 300 python bench.py --full $A > $O/plain_$v.json 2> $O/plain_$v.err
   run "plain    $v" $O/plain_$v.json | tee -a $O/summary.txt
 done

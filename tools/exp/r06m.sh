@@ -16,8 +16,8 @@ except Exception as e:
 PY
 }
 for i in 1 2; do
-  timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr 127.0.0.1 --master-port 2955$i bench.py $A > $O/launcher_$i.json 2> $O/launcher_$i.err
+  timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr 127.0.0.1 --master-port 2955$i bench.py --full $A > $O/launcher_$i.json 2> $O/launcher_$i.err
   run "launcher $i" $O/launcher_$i.json | tee -a $O/summary.txt
-  timeout -k 10 300 python bench.py $A > $O/plain_$i.json 2> $O/plain_$i.err
+  timeout -k 10 300 python bench.py --full $A > $O/plain_$i.json 2> $O/plain_$i.err
   run "plain    $i" $O/plain_$i.json | tee -a $O/summary.txt
 done

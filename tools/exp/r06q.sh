@@ -3,7 +3,7 @@
 cd ${GRAFT_REPO_ROOT:-.}
 O=$PWD/gpurun_out/r06q; mkdir -p $O; : > $O/summary.txt
 for i in 1 2; do
-  timeout -k 10 300 python bench.py --steps 40000 --warmup 10 --preheat-s 0 --steady-steps 0 --no-cpu --no-pair --no-filters --no-host-path --no-config5 > $O/long$i.json 2> $O/long$i.err
+  timeout -k 10 300 python bench.py --full --steps 40000 --warmup 10 --preheat-s 0 --steady-steps 0 --no-cpu --no-pair --no-filters --no-host-path --no-config5 > $O/long$i.json 2> $O/long$i.err
   python3 -c "
 import json
 x=json.loads(open('$O/long$i.json').read().strip().splitlines()[-1]); r=x['roofline']

@@ -35,10 +35,10 @@ def main():
     def row(key, val, cmd, f):
         rows.append(f"| `{key}` | {val} | `{cmd}` | `profiles/{f}` |")
 
-    D = "python bench.py --steps 20 --warmup 5"
+    D = "python bench.py --full --steps 20 --warmup 5"
     F = f"{TAG}_bench.json"
     row("value, ms_per_step", f"**{k(b['value'])} frames/s, {b['ms_per_step']} ms per 256-frame step** (behind {b['preheat']['seconds']} s = "
-        f"{b['preheat']['steps']} untimed steps of the same load)", D + "  (the driver's command)", F)
+        f"{b['preheat']['steps']} untimed steps of the same load)", "python bench.py --steps 20 --warmup 5  (the driver's command; --full: the rest)", F)
     row("roofline.frac", f"**{r['frac']}** of 8 TB/s on the ALGORITHMIC 2N + 5P = {r['algorithmic_bytes_per_launch'] / 1e9:.4f} GB per launch "
         f"(not HBM utilisation: `frac_note`)", D, F)
     row("roofline.traffic, frac_actual, frac_of_achievable", f"{(r['traffic'] or 0) / 1e9:.4f} GB per launch by the counters "
@@ -53,7 +53,7 @@ def main():
     if di:
         row("the default invocation (100 timed steps, 10 warm-up; later in the call: a warm chip)", f"{k(di['value'])} frames/s, {di['ms_per_step']} ms, frac "
             f"{di['roofline']['frac']} / actual {di['roofline'].get('frac_actual')} / of achievable {di['roofline'].get('frac_of_achievable')}; steady_state {di['steady_state']['frac']}",
-            "python bench.py", f"{TAG}_bench_default_invocation.json")
+            "python bench.py --full", f"{TAG}_bench_default_invocation.json")
     try:
         runs = [ln for ln in open(os.path.join(P, "r06q_eighteen_seconds.txt")).read().splitlines() if ln.startswith("run ")]
         vals = [(float(ln.split()[2]), float(ln.split()[4]), float(ln.split()[7])) for ln in runs]
@@ -101,7 +101,7 @@ def main():
         f"index + value per lane {bd['hbm_narrow_write_gbps']:.0f} GB/s", D, F)
     if la:
         c = la["config5"]
-        L = "python -m torch.distributed.run --nproc-per-node=1 ... bench.py --gpus 1 --steps 20 --warmup 5 ..."
+        L = "python -m torch.distributed.run --nproc-per-node=1 ... bench.py --gpus 1 --full --steps 20 --warmup 5 ..."
         G = f"{TAG}_bench_launcher_1rank_rccl.json"
         row("N = 1 under the launcher, real RCCL: value", f"{k(la['value'])} frames/s, {la['ms_per_step']} ms (`config.core_flags`: MI355_FLAG_OWN_QUEUES; without the "
             "flag: 462 k)", L, G + "`; the finding: `profiles/r06k_streams_and_hardware_queues.txt")
@@ -113,7 +113,7 @@ def main():
         c = rh["config5"]
         row("N = 3 rehearsal on ONE GPU (NOT a measurement)", f"ranks_seen {rh['ranks_seen']}, gather_verified {rh['gather_verified']}, config5: parity {c['parity']}, "
             f"gather_verified {c['gather_verified']}, ranks_seen {c['ranks_seen']}, {c['gather_bytes']} B gathered",
-            "python bench.py --gpus 3 --rehearse-on-one-gpu --batch 64 ...", f"{TAG}_bench_rehearsal_3ranks_one_gpu.json")
+            "python bench.py --gpus 3 --rehearse-on-one-gpu --full --batch 64 ...", f"{TAG}_bench_rehearsal_3ranks_one_gpu.json")
     head = f"""# RESULTS — every key of the bench line, the command that prints it, the one file that holds it
 
 Generated by `tools/make_results.py` from the committed outputs of two `gpurun` calls, a 1×MI355X box each: `tools/exp/r06_final.sh`
@@ -137,7 +137,7 @@ do not.
 
 N > 1: `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N
 --steps K --warmup W` (the driver's command) prints the same keys with `n_gpus` N, `value` = all ranks' frames / MAX over the
-ranks of the K steps, `value_with_final_gather`, `gather_*`, `gather_every`, and the `config5` object (4K sequence dealt
+ranks of the K steps, `value_with_final_gather`, `gather_*`, and with `--full` `gather_every` and the `config5` object (4K sequence dealt
 round-robin over the N ranks + RCCL gather to rank 0, parity on rank 0's copy).  No 8-GPU node was available to the builder:
 the N = 3 line above is a rehearsal on one GPU, the N = 1 line runs the same code over real RCCL.
 """
