@@ -269,6 +269,23 @@ class CUDACore:
                                              _ptr(d_diff_all), _ptr(d_offsets), _ptr(d_xs), _ptr(d_diff),
                                              capacity))
 
+    # -- compact wire format (include/mi355diff.h): gap-coded indices, about 2/5 of the wire form's bytes ------------------
+    def cwire_encode_batch(self, d_offsets, d_xs, d_diff, entries_capacity, nframes, d_frame_pos, d_cwire, capacity_bytes):
+        """Packed stream (offsets, xs, diff) of nframes frames -> compact records in d_cwire; d_frame_pos: uint64[nframes + 1]
+        record positions (frame_pos[nframes] = the batch's bytes, or 2^64 - 1 if offsets[nframes] > entries_capacity)."""
+        self._hold(d_offsets, d_xs, d_diff, d_frame_pos, d_cwire)
+        _l.check(self._lib.mi355_cwire_encode_batch(self._h, _ptr(d_offsets), _ptr(d_xs), _ptr(d_diff), int(entries_capacity),
+                                                    int(nframes), _ptr(d_frame_pos), _ptr(d_cwire), int(capacity_bytes)))
+
+    def cwire_decode_batch(self, d_cwire, counts, escapes, nframes, d_offsets, d_xs, d_diff, capacity):
+        """Compact records -> packed stream; counts / escapes: the frames' headers (n, e) as the client read them."""
+        self._hold(d_cwire, d_offsets, d_xs, d_diff)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+        assert counts.size >= nframes and escapes.size >= nframes
+        _l.check(self._lib.mi355_cwire_decode_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
+                                                    int(nframes), _ptr(d_offsets), _ptr(d_xs), _ptr(d_diff), int(capacity)))
+
     def int_diff(self, d_cur, d_prev, d_out, n):
         self._hold(d_cur, d_prev, d_out)
         _l.check(self._lib.mi355_int_diff(self._h, _ptr(d_cur), _ptr(d_prev), _ptr(d_out), n))
@@ -366,3 +383,30 @@ class CUDACore:
         a, b, n = C.c_double(0), C.c_double(0), C.c_int(0)
         _l.check(self._lib.mi355_get_timing(self._h, C.byref(a), C.byref(b), C.byref(n)))
         return a.value, b.value, n.value
+
+
+# -- compact wire format, host side ---------------------------------------------------------------------------------------
+def cwire_frame_bytes(n, e):
+    """Bytes of one compact record: 8 + 2 * pad4(n) + 4 * e."""
+    return _l.load().mi355_cwire_frame_bytes(int(n), int(e))
+
+
+def cwire_bytes_max(frame_bytes, nframes):
+    """Largest compact stream of nframes frames of frame_bytes bytes: nframes * (8 + 2 * pad4(frame_bytes))."""
+    return _l.load().mi355_cwire_bytes_max(int(frame_bytes), int(nframes))
+
+
+def cwire_apply_host(state, buf, nframes):
+    """The client on the host (no GPU): applies nframes compact records of `buf` to `state` (uint8 numpy array, changed in
+    place) and returns the bytes consumed.  Malformed input raises lib.Mi355Error; its `consumed` attribute holds the bytes
+    of the frames before the bad one, which stay applied."""
+    L = _l.load()
+    assert isinstance(state, np.ndarray) and state.dtype == np.uint8 and state.flags.c_contiguous
+    buf = np.ascontiguousarray(np.frombuffer(buf, np.uint8) if isinstance(buf, (bytes, bytearray)) else buf, dtype=np.uint8)
+    consumed = C.c_size_t(0)
+    rc = L.mi355_cwire_apply_host(state.ctypes.data, state.size, buf.ctypes.data, buf.size, int(nframes), C.byref(consumed))
+    if rc != _l.OK:
+        err = _l.Mi355Error(rc, L.mi355_last_error().decode(errors="replace"))
+        err.consumed = consumed.value
+        raise err
+    return consumed.value

@@ -11,6 +11,7 @@
 //   meta      T*W*16       per (frame, tile): code position, record position, flagged bytes, candidates | multi << 16
 //   groff     T*ceil(W/64)*16 (a prefix per range of 16 tiles);  totals T*8 {total, epoch} + the ticket;  offsets (T+1)*4
 //   one_xs N*4, one_diff N exec(): packed output of a single frame before the D2H copies
+//   cw_cnt    32 KiB       the compact-wire encoder's escape counts per workgroup
 //   hist T*256*4, thr T*4 (per frame of a filter batch), k9 9*4, heat LUT 766*3, glyph atlas
 #include <cmath>
 #include <cstdio>
@@ -68,6 +69,7 @@ struct mi355_core {
     uint8_t *one_diff = nullptr;
     int32_t *hist = nullptr, *thr = nullptr;
     uint32_t *red_bounds = nullptr; // mi355_red_stream_batch (cleared form): entry ranges of the frame slices
+    uint32_t *cw_cnt = nullptr;     // mi355_cwire_encode_batch: escapes per workgroup of the emit kernel (kCwireSlots words)
     uint8_t *gray1 = nullptr;      // fused gray+binarize chain: one gray byte per pixel of a batch, made on first use
     size_t gray1_stride = 0;
     float *k9 = nullptr;
@@ -572,6 +574,7 @@ int mi355_create(const mi355_config *cfg, mi355_core **out) {
     if (!rc) rc = dev_alloc(c, &c->totals, 2 * T + 2);   // T x {total, epoch} + the scan kernel's ticket counter
     if (!rc) { e = hipMemsetAsync(c->totals, 0, (2 * T + 2) * sizeof(uint32_t), c->own_stream); if (e != hipSuccess) rc = fail(MI355_ERR_HIP, "hipMemset", e); }
     if (!rc) rc = dev_alloc(c, &c->offsets, T + 1);
+    if (!rc) rc = dev_alloc(c, &c->cw_cnt, (size_t)kCwireSlots);
     if (!rc) rc = dev_alloc(c, &c->one_xs, N + 4);
     if (!rc) rc = dev_alloc(c, &c->one_diff, N + 16);
     if (!rc) rc = dev_alloc(c, &c->hist, 256 * T);
@@ -617,7 +620,7 @@ void mi355_destroy(mi355_core *c) {
         if (c->h_tot) (void)hipHostFree(c->h_tot);
     }
     void *ptrs[] = {c->state, c->in, c->aux, c->vis, c->rec, c->codes, c->meta, c->groff, c->totals, c->offsets, c->one_xs, c->one_diff, c->hist, c->thr, c->k9,
-                    c->lut, c->glyphs, c->kxk, c->gray1, c->red_bounds};
+                    c->lut, c->glyphs, c->kxk, c->gray1, c->red_bounds, c->cw_cnt};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->h_count) (void)hipHostFree(c->h_count);
     for (auto &slot : c->ev) for (auto &ev : slot) if (ev) (void)hipEventDestroy(ev);
@@ -882,6 +885,127 @@ int mi355_merge_parts(mi355_core *c, int nparts, int nframes, const void *d_part
         a.xs_bias[p] = h_xs_bias[p];
     }
     HIP_TRY(launch_merge(a, (uint32_t *)d_offsets, c->stream));
+    return MI355_OK;
+}
+
+// ---- compact wire (include/mi355diff.h) ----------------------------------------------------------------------------
+static inline uint64_t pad4(uint64_t x) { return (x + 3) & ~3ull; }
+
+size_t mi355_cwire_frame_bytes(uint32_t n, uint32_t e) { return (size_t)(8 + 2 * pad4(n) + 4 * (uint64_t)e); }
+
+size_t mi355_cwire_bytes_max(size_t frame_bytes, int nframes) {
+    return nframes > 0 ? (size_t)nframes * (size_t)(8 + 2 * pad4(frame_bytes)) : 0;
+}
+
+int mi355_cwire_encode_batch(mi355_core *c, const void *d_offsets, const void *d_xs, const void *d_diff,
+                             size_t entries_capacity, int nframes, void *d_frame_pos, void *d_cwire, size_t capacity_bytes) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nframes < 0) return fail(MI355_ERR_INVALID, "nframes < 0");
+    if (nframes > kCwireSlots) return fail(MI355_ERR_INVALID, "nframes above 8192: encode the batch in parts");
+    if (!d_offsets || !d_frame_pos) return fail(MI355_ERR_INVALID, "null d_offsets / d_frame_pos");
+    if (entries_capacity > 0 && (!d_xs || !d_diff)) return fail(MI355_ERR_INVALID, "null stream pointer");
+    if (capacity_bytes > 0 && !d_cwire) return fail(MI355_ERR_INVALID, "null d_cwire");
+    if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_xs & 3u) || ((uintptr_t)d_frame_pos & 7u))
+        return fail(MI355_ERR_INVALID, "d_cwire, d_offsets and d_xs must be 4-byte aligned, d_frame_pos 8-byte aligned");
+    if (int rc = use_device(c)) return rc;
+    HIP_TRY(launch_cwire_encode((const uint32_t *)d_offsets, (const int32_t *)d_xs, (const uint8_t *)d_diff,
+                                (uint64_t)entries_capacity, nframes, c->cw_cnt, (uint64_t *)d_frame_pos, (uint8_t *)d_cwire,
+                                (uint64_t)capacity_bytes, c->stream));
+    return MI355_OK;
+}
+
+int mi355_cwire_decode_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
+                             int nframes, void *d_offsets, void *d_xs, void *d_diff, size_t capacity) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nframes < 0) return fail(MI355_ERR_INVALID, "nframes < 0");
+    if (nframes == 0) return MI355_OK;
+    if (!d_cwire || !h_counts || !h_escapes || !d_offsets) return fail(MI355_ERR_INVALID, "null argument");
+    if (capacity > 0 && (!d_xs || !d_diff)) return fail(MI355_ERR_INVALID, "null stream pointer");
+    if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_xs & 3u))
+        return fail(MI355_ERR_INVALID, "d_cwire, d_offsets and d_xs must be 4-byte aligned");
+    for (int t = 0; t < nframes; t++)
+        if (h_escapes[t] > h_counts[t]) return fail(MI355_ERR_INVALID, "frame header: more escapes than entries");
+    if (int rc = use_device(c)) return rc;
+    CwireDecodeArgs a{};
+    a.cwire = (const uint8_t *)d_cwire;
+    a.offsets = (uint32_t *)d_offsets;
+    a.xs = (int32_t *)d_xs;
+    a.diff = (uint8_t *)d_diff;
+    a.capacity = capacity;
+    uint64_t pos = 0;
+    uint32_t out = 0;   // uint32, like every offsets array of the library
+    for (int t0 = 0; t0 < nframes; t0 += kCwireDecodeFrames) {
+        const int nf = nframes - t0 < kCwireDecodeFrames ? nframes - t0 : kCwireDecodeFrames;
+        a.first_frame = t0;
+        for (int k = 0; k < nf; k++) {
+            const uint32_t n = h_counts[t0 + k], e = h_escapes[t0 + k];
+            a.frame[k] = CwireFrame{pos, n, e, out, 0};
+            pos += mi355_cwire_frame_bytes(n, e);
+            out += n;
+        }
+        HIP_TRY(launch_cwire_decode(a, nf, c->stream));
+    }
+    return MI355_OK;
+}
+
+// client/opencv.cpp:50-66 on the compact stream, on the host.  A frame is validated whole before any byte of the state
+// changes, so a malformed frame leaves the state as the frames before it made it.
+int mi355_cwire_apply_host(uint8_t *state, size_t frame_bytes, const void *cwire, size_t cwire_bytes, int nframes,
+                           size_t *consumed) {
+    if (consumed) *consumed = 0;
+    if (!state || !cwire || !consumed) return fail(MI355_ERR_INVALID, "null argument");
+    if (nframes < 0) return fail(MI355_ERR_INVALID, "nframes < 0");
+    const uint8_t *p = (const uint8_t *)cwire;
+    size_t at = 0;
+    char msg[160];
+    for (int t = 0; t < nframes; t++) {
+        if (cwire_bytes - at < 8) {
+            snprintf(msg, sizeof msg, "compact stream: frame %d: truncated header", t);
+            return fail(MI355_ERR_INVALID, msg);
+        }
+        uint32_t n, e;
+        memcpy(&n, p + at, 4);
+        memcpy(&e, p + at + 4, 4);
+        if (n > frame_bytes) {
+            snprintf(msg, sizeof msg, "compact stream: frame %d: %u entries > frame bytes", t, n);
+            return fail(MI355_ERR_INVALID, msg);
+        }
+        if (e > n) {
+            snprintf(msg, sizeof msg, "compact stream: frame %d: %u escapes > %u entries", t, e, n);
+            return fail(MI355_ERR_INVALID, msg);
+        }
+        const size_t rec = mi355_cwire_frame_bytes(n, e);
+        if (cwire_bytes - at < rec) {
+            snprintf(msg, sizeof msg, "compact stream: frame %d: truncated record", t);
+            return fail(MI355_ERR_INVALID, msg);
+        }
+        const uint8_t *code = p + at + 8, *escb = code + pad4(n), *diff = escb + 4 * (size_t)e;
+        uint32_t n255 = 0;
+        for (uint32_t k = 0; k < n; k++) n255 += code[k] == 255;
+        if (n255 != e) {
+            snprintf(msg, sizeof msg, "compact stream: frame %d: %u escape codes, header says %u", t, n255, e);
+            return fail(MI355_ERR_INVALID, msg);
+        }
+        uint64_t x = 0;   // running index + 1 (64-bit: escape values cannot wrap it)
+        for (uint32_t k = 0, r = 0; k < n; k++) {
+            uint32_t g = code[k];
+            if (g == 255) memcpy(&g, escb + 4 * (size_t)r++, 4);
+            x += (uint64_t)g + 1;
+            if (x > frame_bytes) {
+                snprintf(msg, sizeof msg, "compact stream: frame %d: entry %u decodes to an index >= frame bytes", t, k);
+                return fail(MI355_ERR_INVALID, msg);
+            }
+        }
+        x = 0;
+        for (uint32_t k = 0, r = 0; k < n; k++) {
+            uint32_t g = code[k];
+            if (g == 255) memcpy(&g, escb + 4 * (size_t)r++, 4);
+            x += (uint64_t)g + 1;
+            state[x - 1] = (uint8_t)(state[x - 1] + diff[k]);   // opencv.cpp:65
+        }
+        at += rec;
+        *consumed = at;
+    }
     return MI355_OK;
 }
 

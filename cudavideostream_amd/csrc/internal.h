@@ -97,6 +97,30 @@ hipError_t launch_apply_all(uint8_t *frame, uint32_t nbytes, const int32_t *xs, 
 hipError_t launch_export(const uint32_t *offsets, const int32_t *xs, const uint8_t *diff, int32_t *h_xs,
                          uint8_t *h_diff, uint32_t *h_count, hipStream_t s);
 hipError_t launch_merge(const MergeArgs &a, uint32_t *out_offsets, hipStream_t s);
+// compact wire (include/mi355diff.h): the encoder's per-workgroup escape counts live in kCwireSlots words of the core
+// (nframes * cwire_blocks_per_frame(nframes) <= kCwireSlots), so one encode takes at most kCwireSlots frames
+constexpr int kCwireSlots = 8192;
+int cwire_blocks_per_frame(int nframes);
+hipError_t launch_cwire_encode(const uint32_t *offsets, const int32_t *xs, const uint8_t *diff, uint64_t entries_capacity,
+                               int nframes, uint32_t *cnt /* kCwireSlots words */, uint64_t *frame_pos, uint8_t *out,
+                               uint64_t capacity_bytes, hipStream_t s);
+constexpr int kCwireDecodeFrames = 64;   // frames per decode launch (their descriptors travel as kernel arguments)
+struct CwireFrame {
+    uint64_t pos;   // byte position of the record in the compact stream
+    uint32_t n, e;  // its header, as the client read it
+    uint32_t out;   // entries of the frames before it (its first entry in xs / diff)
+    uint32_t pad;
+};
+struct CwireDecodeArgs {
+    const uint8_t *cwire;
+    uint32_t *offsets;
+    int32_t *xs;
+    uint8_t *diff;
+    uint64_t capacity;
+    int32_t first_frame;
+    CwireFrame frame[kCwireDecodeFrames];
+};
+hipError_t launch_cwire_decode(const CwireDecodeArgs &a, int nframes, hipStream_t s);
 
 // filters.hip -- every per-frame kernel takes a FrameBatch: frame f lives at base + f*stride
 struct FrameBatch {

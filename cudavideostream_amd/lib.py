@@ -71,6 +71,14 @@ SYMBOLS = {
     "mi355_apply_wire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "mi355_merge_parts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mi355_cwire_frame_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "mi355_cwire_bytes_max": (C.c_size_t, [C.c_size_t, C.c_int]),
+    "mi355_cwire_encode_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mi355_cwire_decode_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mi355_cwire_apply_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int,
+                                         C.POINTER(C.c_size_t)]),
     "mi355_int_diff": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "mi355_gray_avg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "mi355_gray_weighted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -127,7 +135,7 @@ SYMBOLS = {
     "mi355_group_synchronize": (C.c_int, [C.c_void_p]),
 }
 GROUP_ID_BYTES = 128   # MI355_GROUP_ID_BYTES
-ABI_VERSION = 6        # MI355_ABI_VERSION of the include/mi355diff.h these argument lists were written against
+ABI_VERSION = 7        # MI355_ABI_VERSION of the include/mi355diff.h these argument lists were written against
 
 _lib = None
 

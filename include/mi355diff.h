@@ -74,8 +74,10 @@ typedef struct mi355_config {
  *      gone and cfg.flags must be 0; the environment variables MI355_SPLIT, MI355_DENSE_PCT, MI355_CHAIN_HINT and the
  *      undocumented tuning variables are no longer read (options below); + MI355_OPT_MEDIAN_ROWS, mi355_probe_hbm_write
  *      (additions)
- *   6  round 6: + mi355_prepare, mi355_alloc_outputs, MI355_OPT_SCAN_EPOCH_LEFT, cfg.flags bit MI355_FLAG_OWN_QUEUES (additions only) */
-#define MI355_ABI_VERSION 6
+ *   6  round 6: + mi355_prepare, mi355_alloc_outputs, MI355_OPT_SCAN_EPOCH_LEFT, cfg.flags bit MI355_FLAG_OWN_QUEUES (additions only)
+ *   7  + the compact wire format: mi355_cwire_frame_bytes, mi355_cwire_bytes_max, mi355_cwire_encode_batch,
+ *      mi355_cwire_decode_batch, mi355_cwire_apply_host (additions only) */
+#define MI355_ABI_VERSION 7
 int mi355_abi_version(void);
 
 /* ---- life cycle: CUDACore::CUDACore (kernels.cu:377-428) without the uploads ------------------ */
@@ -181,8 +183,9 @@ int mi355_set_glyphs(mi355_core *core, const uint8_t *chars_px, int nglyphs, int
  * Asynchronous.  On the core's OWN stream consecutive batches are pipelined: the index and the expansion of a
  * batch run on a side stream beside the next batch's pack kernel.  A batch's outputs (d_offsets, d_xs, d_diff,
  * d_wire) are complete after mi355_synchronize and for every later call on this core that can consume them
- * (mi355_apply_*, mi355_red_stream_batch / _red_overlap, mi355_merge_parts, mi355_download, mi355_exec /
- * mi355_pipe_*, the group gather) -- these first wait for the last expansion.  The frame filters (mi355_filter_batch,
+ * (mi355_apply_*, mi355_red_stream_batch / _red_overlap, mi355_merge_parts, mi355_cwire_encode_batch /
+ * mi355_cwire_decode_batch, mi355_download, mi355_exec / mi355_pipe_*, the group gather) -- these first wait for the last
+ * expansion.  The frame filters (mi355_filter_batch,
  * mi355_gray_*, mi355_binarize_chain, mi355_heat_map, mi355_red_dense, mi355_conv*, mi355_median5x5,
  * mi355_int_diff) take frames, not packed streams, and are ordered on the core's stream only: they may run beside
  * the expansion of the batch before (visualiser of frame k + 1 beside the expansion of frame k).  With a caller's
@@ -244,6 +247,50 @@ int mi355_apply_wire_batch(mi355_core *core, const void *d_wire, const uint32_t 
 int mi355_merge_parts(mi355_core *core, int nparts, int nframes, const void *d_part_offsets,
                       const uint32_t *h_part_base, const int32_t *h_xs_bias, const void *d_xs_all,
                       const void *d_diff_all, void *d_offsets, void *d_xs, void *d_diff, size_t capacity);
+
+/* ---- compact wire format: the same stream as the wire form above in about 2/5 of the bytes ----------------------------
+ * Each index is coded as its gap from the previous one, which nearly always fits one byte.  One record per frame, records
+ * back to back, each 4-byte aligned from the start of the buffer; all integers little-endian; pad4(x) = x rounded up to a
+ * multiple of 4:
+ *     u32 n                 entries of the frame (h_pos; the same entries, in the same ascending order, as the packed stream)
+ *     u32 e                 escaped gaps
+ *     u8  code[n]           g_0 = xs[0], g_k = xs[k] - xs[k-1] - 1;  code[k] = g_k if g_k < 255, else 255 (escape)
+ *     u8  0[pad4(n) - n]
+ *     u32 esc[e]            g_k of every k with code[k] == 255, in k order
+ *     u8  diff[n]           (uint8)df, as diff[] of the wire form
+ *     u8  0[pad4(n) - n]
+ * A record is mi355_cwire_frame_bytes(n, e) = 8 + 2*pad4(n) + 4*e bytes.  An escape spans at least 256 indices, so e <= N/256
+ * and a frame never needs more than 8 + 2*pad4(N) bytes (mi355_cwire_bytes_max: nframes times that).  The encoding is
+ * canonical: one byte string per (xs, diff), pad bytes zero.  The reference's client cannot read it. */
+size_t mi355_cwire_frame_bytes(uint32_t n, uint32_t e);
+size_t mi355_cwire_bytes_max(size_t frame_bytes, int nframes);
+/* Encodes a packed stream of nframes frames -- of mi355_diff_stream_batch / _pairs_batch, mi355_merge_parts or a rank's
+ * segment of the group gather -- into records: frame t at byte d_frame_pos[t] (uint64[nframes + 1], exclusive scan of the
+ * record sizes; d_frame_pos[nframes] = the bytes of the whole batch).
+ *   Precondition: entries strictly ascending within each frame, as every entry point of this library emits them.
+ *   Frame t is written only if d_frame_pos[t + 1] <= capacity_bytes; a frame that does not fit is skipped whole (nothing of
+ *   it is written); d_frame_pos is exact regardless.
+ *   offsets[nframes] > entries_capacity (the diff batch dropped entries), or offsets that run backwards: nothing is read
+ *   from d_xs / d_diff, nothing is written but d_frame_pos[nframes] = UINT64_MAX.
+ *   d_cwire, d_offsets and d_xs 4-byte aligned, d_frame_pos 8-byte aligned; nframes <= 8192.  Asynchronous on the core's
+ *   stream; three kernel launches, the stores are dwords. */
+int mi355_cwire_encode_batch(mi355_core *core, const void *d_offsets, const void *d_xs, const void *d_diff,
+                             size_t entries_capacity, int nframes, void *d_frame_pos, void *d_cwire, size_t capacity_bytes);
+/* The inverse, into a packed stream (d_offsets uint32[nframes + 1], d_xs int32, d_diff uint8), for mi355_apply_batch.  The
+ * headers come from the host as the client read them from the socket: h_counts[t] = n, h_escapes[t] = e (the header words
+ * inside d_cwire are skipped, not trusted); the records are where those headers put them.  Entries beyond `capacity` are
+ * dropped, d_offsets stays exact.  Malformed content never makes it read outside a frame's record or write outside its
+ * outputs: an escape code ranked at or past e decodes to index 0xFFFFFFFF (mi355_apply_batch ignores it).  h_escapes[t] >
+ * h_counts[t] is refused.  Same alignment as the encoder.  Asynchronous on the core's stream. */
+int mi355_cwire_decode_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
+                             int nframes, void *d_offsets, void *d_xs, void *d_diff, size_t capacity);
+/* A client without a GPU: client/opencv.cpp:50-66 on the compact stream, state[xs] += diff for nframes records of host
+ * memory `cwire` (cwire_bytes bytes) on a host frame of frame_bytes bytes.  No core, no HIP call.  Every frame is validated
+ * before it is applied; MI355_ERR_INVALID (with the reason in mi355_last_error) for a truncated record, n > frame_bytes,
+ * e > n, a count of 255 codes other than e, a decoded index >= frame_bytes, a null pointer or nframes < 0.  The frames
+ * before a bad one stay applied and *consumed = their bytes (on success: all bytes of the nframes records). */
+int mi355_cwire_apply_host(uint8_t *state, size_t frame_bytes, const void *cwire, size_t cwire_bytes, int nframes,
+                           size_t *consumed);
 
 /* Integer difference of tests/algorithms_benchmarks.cu:24-30 (kernel1): d[i] = cur[i] - prev[i] on
  * int32 arrays of n elements, no threshold, no pack. */

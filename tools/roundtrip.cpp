@@ -8,7 +8,12 @@
 // second core.  The program checks that the client's frame equals the server's reconstructed state
 // after every batch and that every rebuilt byte is within the threshold of the frame that was sent.
 //
-//   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B]     exit status 0 = all checks passed
+// --compact: the same over the compact wire format (include/mi355diff.h): the server packs a batch and encodes it on the
+// GPU (mi355_diff_stream_batch, mi355_cwire_encode_batch), the records cross the same pipe, and the client -- with no
+// core and no GPU -- rebuilds every frame on the host with mi355_cwire_apply_host; each rebuilt frame is checked against
+// the frame that was sent, and the client's frame against the server's state after every batch.
+//
+//   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B] [--compact]   exit status 0 = all checks passed
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -64,8 +69,12 @@ static bool through_pipe(int wfd, int rfd, const uint8_t *src, uint8_t *dst, siz
 
 int main(int argc, char **argv) {
     int w = 320, h = 180, T = 24, B = 8;
+    bool compact = false;
+    for (int i = 1; i < argc; i++)
+        if (std::string(argv[i]) == "--compact") compact = true;
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string k = argv[i];
+        if (k == "--compact") { i--; continue; }
         const int v = atoi(argv[i + 1]);
         if (k == "--width") w = v; else if (k == "--height") h = v;
         else if (k == "--frames") T = v; else if (k == "--batch") B = v;
@@ -100,6 +109,66 @@ int main(int argc, char **argv) {
 
     size_t sent_bytes = 0, changed = 0;
     int max_err = 0;
+    if (compact) {
+        // ---- sender: pack + encode on the GPU; client: the host decoder on a host frame (no core)
+        void *d_xs = nullptr, *d_df = nullptr, *d_pos = nullptr, *d_cw = nullptr;
+        const size_t cap = (size_t)B * n, cw_cap = mi355_cwire_bytes_max(n, B);
+        OK(mi355_dev_alloc(server, &d_xs, cap * 4));
+        OK(mi355_dev_alloc(server, &d_df, cap));
+        OK(mi355_dev_alloc(server, &d_pos, sizeof(uint64_t) * (B + 1)));
+        OK(mi355_dev_alloc(server, &d_cw, cw_cap));
+        std::vector<uint8_t> cw_host(cw_cap), rx(cw_cap), c_frame(got_base);
+        for (int t0 = 0; t0 < T; t0 += B) {
+            const int nb = T - t0 < B ? T - t0 : B;
+            for (int k = 0; k < nb; k++) {
+                make_frame(frame, base, w, h, t0 + k);
+                memcpy(&frames[(size_t)k * n], frame.data(), n);
+            }
+            std::vector<uint32_t> off(nb + 1);
+            std::vector<uint64_t> pos(nb + 1);
+            OK(mi355_upload(server, d_frames, frames.data(), (size_t)nb * n));
+            OK(mi355_diff_stream_batch(server, d_frames, n, nb, d_off, d_xs, d_df, cap));
+            OK(mi355_cwire_encode_batch(server, d_off, d_xs, d_df, cap, nb, d_pos, d_cw, cw_cap));
+            OK(mi355_download(server, off.data(), d_off, sizeof(uint32_t) * (nb + 1)));
+            OK(mi355_download(server, pos.data(), d_pos, sizeof(uint64_t) * (nb + 1)));
+            if (pos[nb] > cw_cap) { fprintf(stderr, "compact stream larger than its bound\n"); return 1; }
+            const size_t cb = (size_t)pos[nb];
+            OK(mi355_download(server, cw_host.data(), d_cw, cb));
+            changed += off[nb];
+            if (!through_pipe(fds[1], fds[0], cw_host.data(), rx.data(), cb)) return 1;
+            sent_bytes += cb;
+            size_t at = 0;
+            for (int k = 0; k < nb; k++) {   // one frame at a time: what the client shows after each
+                size_t used = 0;
+                OK(mi355_cwire_apply_host(c_frame.data(), n, rx.data() + at, cb - at, 1, &used));
+                at += used;
+                for (size_t i = 0; i < n; i++) {
+                    const int e = abs((int)c_frame[i] - (int)frames[(size_t)k * n + i]);
+                    if (e > max_err) max_err = e;
+                }
+            }
+            if (at != cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
+            OK(mi355_get_state(server, s_state.data()));
+            if (memcmp(s_state.data(), c_frame.data(), n) != 0) { fprintf(stderr, "client frame != server state\n"); return 1; }
+        }
+        if (max_err > cfg.threshold) { fprintf(stderr, "rebuilt frame off by %d > threshold\n", max_err); return 1; }
+        OK(mi355_dev_free(server, d_xs));
+        OK(mi355_dev_free(server, d_df));
+        OK(mi355_dev_free(server, d_pos));
+        OK(mi355_dev_free(server, d_cw));
+        OK(mi355_dev_free(server, d_frames));
+        OK(mi355_dev_free(server, d_wire));
+        OK(mi355_dev_free(server, d_off));
+        OK(mi355_dev_free(client, d_cwire));
+        OK(mi355_dev_free(client, d_shown));
+        mi355_destroy(server);
+        mi355_destroy(client);
+        printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"width\": %d, \"height\": %d, \"frames\": %d, \"batch\": %d, "
+               "\"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, "
+               "\"max_abs_error\": %d}\n",
+               w, h, T, B, changed, sent_bytes, mi355_wire_bytes(T, changed), (size_t)T * n, max_err);
+        return 0;
+    }
     for (int t0 = 0; t0 < T; t0 += B) {
         const int nb = T - t0 < B ? T - t0 : B;
         for (int k = 0; k < nb; k++) {
