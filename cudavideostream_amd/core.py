@@ -146,7 +146,8 @@ class CUDACore:
         self._held = []
 
     def set_option(self, option, value):
-        """lib.OPT_*: the schedule of the own-stream batches (include/mi355diff.h, "Options"); never a result."""
+        """lib.OPT_*: OPT_PIPELINE switches the own-stream pipelining; OPT_MEDIAN_ROWS and OPT_SCAN_EPOCH_LEFT are seams
+        for the tests (include/mi355diff.h, "Options").  None of them changes a result."""
         _l.check(self._lib.mi355_set_option(self._h, int(option), int(value)))
         self._held = []   # (the call completed what was queued)
 

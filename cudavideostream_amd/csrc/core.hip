@@ -112,29 +112,25 @@ struct mi355_core {
     hipStream_t side = nullptr;
     hipEvent_t side_done = nullptr;   // == the `expanded` event of the last pipelined batch, or null: nothing pending
     bool pipeline_ok = true;          // false: MI355_PIPELINE=0 / MI355_OPT_PIPELINE 0, or the second set could not be allocated
-    int pack_blocks_opt = -1;         // MI355_OPT_PACK_BLOCKS (-1: the default, 4 workgroups per CU)
     int median_rows = 0;              // MI355_OPT_MEDIAN_ROWS (0: chosen per launch)
-    uint32_t k1_blocks = 0;           // pipelined batches: workgroups of the pack kernel (0 = one tile per wave)
-    uint32_t cu_count = 0;            // compute units of the device
-    // pipelined batches packed by TWO launches (tiles [0, split) on the core's stream, the rest on `main2`): the two chains
-    // of pack kernels drift apart, each one's kernel boundary (L2 write-back, event packets: 21-25 us) falls into the other's
-    // kernel.  split_pct = 0: one launch.
+    uint32_t cu_count = 0;            // compute units of the device (0: unknown)
+    // pipelined batches of 64 tiles or more are packed by TWO launches (tiles [0, cut) on the core's stream, the rest on
+    // `main2`): the two chains of pack kernels drift apart, each one's kernel boundary (L2 write-back, event packets:
+    // 21-25 us) falls into the other's kernel.
     // (three or four launches were measured: much slower, profiles/archive/r04ah)
-    int split_pct = 50;               // MI355_OPT_SPLIT_PCT
     hipStream_t main2 = nullptr;
     hipEvent_t packed2[kSets] = {};
     // Adaptive overlap: a batch whose expansion is longer than its pack kernel (dense input: a scene change, the synthetic
     // worst cases) loses by running beside the next batch's pack kernel (S0 pairs 0.313 ms one after the other, 0.35
     // overlapped).  The batch total (offsets[nframes]) of every own-stream batch is copied to pinned host memory behind its
     // expansion; the next calls look at the latest total that HAS ARRIVED (a word of pinned memory the index kernel stores, no
-    // waiting) and run one batch after the other while more than dense_pct per cent of the bytes changed.  Results never depend
-    // on it, only the schedule.
+    // waiting) and run one batch after the other while more than kDensePct per cent of the bytes changed.  Results never
+    // depend on it, only the schedule.
+    static constexpr uint32_t kDensePct = 40;
     uint64_t *h_tot = nullptr;        // pinned: {entries of the latest own-stream batch whose index has run, its frames << 32},
                                       // stored by that batch's index kernel itself (k_scan_groups, `note`)
-    int dense_pct = 40;               // MI355_OPT_DENSE_PCT (0: never switch)
     bool dense = false;               // what the latest total that has arrived said
     bool filter_since_batch = false;  // a frame filter ran on this core since the last batch (use_device_filter)
-    bool chain_hint = true;           // MI355_OPT_CHAIN_HINT 0: batches are overlapped regardless
     hipEvent_t fork[kSets] = {};          // recorded on the core's stream in front of a batch's first pack launch: the other parts wait for it
     int parts_pending = -1;           // log set of the last batch whose parts the core's stream has not waited for (-1: none)
 
@@ -206,9 +202,9 @@ int use_device(mi355_core *c, bool join = true, bool parts = true) {
 // filter in front of every diff: BASELINE configs 3 and 4) gains nothing from a batch's expansion running beside the next
 // filter -- both are bound by the memory system -- and loses the pipelined batch's smaller pack grid and stream hops:
 // 4.6 us per frame one after the other, 5.0-5.2 overlapped (config 3, profiles/archive/r04bd).  The next batch therefore runs one
-// kernel after the other on the core's stream (MI355_OPT_CHAIN_HINT 0: ignore the hint).
+// kernel after the other on the core's stream.
 int use_device_filter(mi355_core *c) {
-    c->filter_since_batch = c->chain_hint;
+    c->filter_since_batch = true;
     return use_device(c, false);
 }
 
@@ -289,14 +285,7 @@ int setup_pipeline(mi355_core *c) {
     // one tile per wave (6 per CU).  It is bound by the memory system and does not need its occupancy (profiles/README.md,
     // round 1), while the expansion of the batch before, which shares the chip with it, lives on the wave slots and
     // registers that are left: 0.503-0.507 -> 0.487-0.497 ms per batch on the faster boxes, +-1 % on the slower ones
-    // (profiles/archive/r04p, r04q, r04v).  MI355_OPT_PACK_BLOCKS overrides (0 = one tile per wave).
-    if (c->pack_blocks_opt >= 0) {
-        c->k1_blocks = (uint32_t)c->pack_blocks_opt;
-    } else {
-        hipDeviceProp_t prop{};
-        if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0)
-            c->k1_blocks = 4u * (uint32_t)prop.multiProcessorCount;
-    }
+    // (profiles/archive/r04p, r04q, r04v).  run_batch sizes the grid from cu_count.
     const size_t T = (size_t)c->cfg.max_batch, W = c->ntiles;
     mi355_core::LogSet &s0 = c->set[0], &s1 = c->set[1];
     s0.rec = c->rec; s0.codes = c->codes; s0.meta = c->meta; s0.groff = c->groff; s0.totals = c->totals;
@@ -366,10 +355,10 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
         if (int rc = setup_pipeline(c)) return rc;
         pipelined = c->pipeline_ok;
     }
-    if (pipelined && c->h_tot && c->dense_pct > 0 && c->dense_pct < 100) {
+    if (pipelined && c->h_tot) {
         // the latest batch total that has arrived: dense input -> this batch runs after the expansion of the one before
         const uint64_t note = __atomic_load_n(c->h_tot, __ATOMIC_RELAXED);   // one 64-bit word: never torn
-        if (note >> 32) c->dense = (note & 0xffffffffull) * 100u > (uint64_t)c->dense_pct * (note >> 32) * c->n;
+        if (note >> 32) c->dense = (note & 0xffffffffull) * 100u > (uint64_t)mi355_core::kDensePct * (note >> 32) * c->n;
         if (c->dense) pipelined = false;   // (no total has arrived yet: what the last one said still holds)
     }
     if (!pipelined)
@@ -428,17 +417,18 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
             if (k > -T && k < T && (d - k * st < 0 ? k * st - d : d - k * st) < (int64_t)c->n) shared = true;
         pair_once = !shared;
     }
-    const bool split = pipelined && c->split_pct && c->main2 && c->ntiles >= 64;
+    const uint32_t k1_blocks = 4u * c->cu_count;   // the pipelined pack grid (setup_pipeline; 0 = one tile per wave)
+    const bool split = pipelined && c->main2 && c->ntiles >= 64;
     if (split) {
         // tiles [0, cut) on the core's stream, the rest on a stream of its own (which also has to see the log set free
         // and everything the core's stream holds so far: a filter that is still writing the frames this batch reads,
         // the upload of the state); each part takes its share of the pipelined grid
-        const uint32_t cut = (uint32_t)((uint64_t)c->ntiles * (uint32_t)c->split_pct / 100u) & ~3u;
+        const uint32_t cut = (c->ntiles / 2) & ~3u;
         uint32_t blocks0 = 0, blocks1 = 0;
-        if (c->k1_blocks) {
-            blocks0 = (uint32_t)((uint64_t)c->k1_blocks * cut / c->ntiles);
+        if (k1_blocks) {
+            blocks0 = (uint32_t)((uint64_t)k1_blocks * cut / c->ntiles);
             if (blocks0 == 0) blocks0 = 1;
-            blocks1 = c->k1_blocks > blocks0 ? c->k1_blocks - blocks0 : 1u;
+            blocks1 = k1_blocks > blocks0 ? k1_blocks - blocks0 : 1u;
         }
         HIP_TRY(hipEventRecord(c->fork[c->flip], c->stream));
         PackArgs a0 = a, a1 = a;
@@ -453,7 +443,7 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
         if (tev) HIP_TRY(hipEventRecord(tev[5], c->main2));   // the pack "kernel" of a split batch ends when BOTH parts have
         c->parts_pending = c->flip;
     } else {
-        HIP_TRY(launch_diff_pack(a, pair, aligned, pair_once, pipelined ? c->k1_blocks : 0u, c->stream));
+        HIP_TRY(launch_diff_pack(a, pair, aligned, pair_once, pipelined ? k1_blocks : 0u, c->stream));
     }
     if (tev) {
         HIP_TRY(hipEventRecord(tev[1], c->stream));
@@ -476,7 +466,7 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
     }
     // (an own-stream batch leaves its total in pinned memory for the next calls' decisions -- stored by the index kernel
     // itself: a copy + an event behind every batch cost config 3's chain 4 %, the event's system-scope fence included)
-    uint64_t *const note = own && c->h_tot && c->pipeline_ok && c->dense_pct > 0 && c->dense_pct < 100 ? c->h_tot : nullptr;
+    uint64_t *const note = own && c->h_tot && c->pipeline_ok ? c->h_tot : nullptr;
     HIP_TRY(launch_scan(ls.meta, ls.groff, (uint64_t *)ls.totals, c->ntiles, nframes, (uint32_t *)d_offsets,
                         ls.totals + 2 * (size_t)c->cfg.max_batch, c->scan_epoch, note, tail));
     if (tev) HIP_TRY(hipEventRecord(tev[3], tail));
@@ -679,7 +669,8 @@ int mi355_synchronize(mi355_core *c) {
     return MI355_OK;
 }
 
-// Options: the schedule of the own-stream batches, never a result.  Changing one first completes what is queued.
+// Options: the pipelined mode of the own-stream batches and two seams for tests, never a result.  Changing one first
+// completes what is queued.
 int mi355_set_option(mi355_core *c, int option, int value) {
     if (!c) return fail(MI355_ERR_INVALID, "null core");
     if (int rc = use_device(c)) return rc;
@@ -690,33 +681,7 @@ int mi355_set_option(mi355_core *c, int option, int value) {
             // (a core whose second log set could not be allocated stays sequential: setup_pipeline says so by itself)
             c->pipeline_ok = value == 1;
             return MI355_OK;
-        case MI355_OPT_SPLIT_PCT:
-            if (value != 0 && (value < 5 || value > 95)) return fail(MI355_ERR_INVALID, "MI355_OPT_SPLIT_PCT: 0 or 5..95");
-            c->split_pct = value;
-            return MI355_OK;
-        case MI355_OPT_DENSE_PCT:
-            if (value < 0 || value > 100) return fail(MI355_ERR_INVALID, "MI355_OPT_DENSE_PCT: 0..100");
-            c->dense_pct = value;
-            c->dense = false;
-            return MI355_OK;
-        case MI355_OPT_CHAIN_HINT:
-            if (value != 0 && value != 1) return fail(MI355_ERR_INVALID, "MI355_OPT_CHAIN_HINT: 0 or 1");
-            c->chain_hint = value == 1;
-            c->filter_since_batch = false;
-            return MI355_OK;
-        case MI355_OPT_PACK_BLOCKS:
-            if (value < -1 || value > (1 << 20)) return fail(MI355_ERR_INVALID, "MI355_OPT_PACK_BLOCKS: -1 (default), 0 (one tile per wave) or a workgroup count");
-            c->pack_blocks_opt = value;
-            if (c->side) {   // the pipelined mode is already set up: takes effect with the next batch
-                if (value >= 0) c->k1_blocks = (uint32_t)value;
-                else {
-                    hipDeviceProp_t prop{};
-                    HIP_TRY(hipGetDeviceProperties(&prop, c->device));
-                    c->k1_blocks = 4u * (uint32_t)prop.multiProcessorCount;
-                }
-            }
-            return MI355_OK;
-        case MI355_OPT_MEDIAN_ROWS:
+        case MI355_OPT_MEDIAN_ROWS:   // tests: the median filter's band length, instead of the one chosen per launch
             if (value < 0 || value > 60 || value % 5) return fail(MI355_ERR_INVALID, "MI355_OPT_MEDIAN_ROWS: 0 (default) or 5, 10, .. 60");
             c->median_rows = value;
             return MI355_OK;
@@ -738,10 +703,6 @@ int mi355_get_option(mi355_core *c, int option, int *value) {
     if (!c || !value) return fail(MI355_ERR_INVALID, "null argument");
     switch (option) {
         case MI355_OPT_PIPELINE: *value = c->pipeline_ok ? 1 : 0; return MI355_OK;
-        case MI355_OPT_SPLIT_PCT: *value = c->split_pct; return MI355_OK;
-        case MI355_OPT_DENSE_PCT: *value = c->dense_pct; return MI355_OK;
-        case MI355_OPT_CHAIN_HINT: *value = c->chain_hint ? 1 : 0; return MI355_OK;
-        case MI355_OPT_PACK_BLOCKS: *value = c->pack_blocks_opt; return MI355_OK;
         case MI355_OPT_MEDIAN_ROWS: *value = c->median_rows; return MI355_OK;
         case MI355_OPT_SCAN_EPOCH_LEFT: {
             const uint64_t left = kEpochWrap - 1 - c->scan_epoch;

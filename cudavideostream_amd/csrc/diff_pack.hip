@@ -37,8 +37,6 @@
 
 namespace mi355 {
 
-// Laboratory builds (tools/ab_build.sh: -DMI355_LAB=1 -DMI355_ABLATE=n ..., never shipped) take parts of the kernels
-// out to price them; the shipped library has kAblate == kXAblate == kPad == 0 (lab.h) and none of that code.
 constexpr int kStreamPrefetch = 4;   // frames per register group of the stream kernel
 // Frames per register group (two groups per wave).  Stream mode: 4 (8 x 1 KiB in flight per wave, 58 VGPRs).  Pair
 // mode holds two operands per frame: with 4 it needed 89 VGPRs = 5 waves per SIMD, and the 6076 waves of a 1080p frame
@@ -87,7 +85,6 @@ __device__ __forceinline__ void compare_step(const uint4 c, uint4 &s, ThrConst t
     uint32_t fh[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        if (kAblate == 3) { sw[k] ^= cw[k]; dm[k] = 0; fh[k] = 0; continue; }   // lab: loads + a fold of the state only
         uint32_t x;
         fh[k] = dword_flags<HIGH>(cw[k], sw[k], tc, x);
         // 0xFF in every flagged byte: a v_perm selector byte of 0x80 yields the constant 0xFF, one of 0x00
@@ -99,12 +96,6 @@ __device__ __forceinline__ void compare_step(const uint4 c, uint4 &s, ThrConst t
         sw[k] = bitop3<(TA & TC) | (TB & ~TC)>(cw[k], sw[k], mask);
     }
     s = make_uint4(sw[0], sw[1], sw[2], sw[3]);
-    if (kPad > 0) {   // lab: what does an instruction cost?
-        uint32_t pad = cw[0];
-#pragma unroll
-        for (int i = 0; i < kPad; i++) asm volatile("v_add_u32 %0, %0, %1" : "+v"(pad) : "v"(cw[1]));
-        asm volatile("" :: "v"(pad));
-    }
     // flags are 0x80 per flagged byte: two v_dot4 chains weigh them into 128 * (map of 8 bytes)
     const uint32_t lo = __builtin_amdgcn_udot4(fh[1], tc.w1, __builtin_amdgcn_udot4(fh[0], tc.w0, 0u, false), false);
     const uint32_t hi = __builtin_amdgcn_udot4(fh[3], tc.w1, __builtin_amdgcn_udot4(fh[2], tc.w0, 0u, false), false);
@@ -137,7 +128,7 @@ __device__ __forceinline__ uint32_t emit_step(const uint32_t (&dm)[4], uint32_t 
     if (nm == 64u) {   // wave-uniform: a DENSE tile (all 64 lanes carry two or more flagged bytes) appends records only: a
                        // lane's record is record `lane`, and its map is the record's non-zero bytes (|df| > T >= 0 is never 0)
         const u32x4 v = {dm[0], dm[1], dm[2], dm[3]};
-        if (kAblate == 0) __builtin_amdgcn_raw_buffer_store_b128(v, lg.recs, pm + rankM * 16u, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(v, lg.recs, pm + rankM * 16u, 0, 0);
         lp.ptrM += 64u * 16u;
         lp.roomM -= 64u;
         return 64u | (64u << 16);
@@ -147,15 +138,11 @@ __device__ __forceinline__ uint32_t emit_step(const uint32_t (&dm)[4], uint32_t 
     // a lane with one flagged byte: the byte sum of its masked differences IS that byte
     const uint32_t one = __builtin_amdgcn_sad_u8((dm[0] | dm[1]) | (dm[2] | dm[3]), 0u, 0u);
     const uint32_t code = m16 | ((multi ? rankM : one) << 16) | lane24;
-    if (kAblate == 0) {
-        // plain (write-back) stores: the L2 is what merges a tile's 80-byte appends into whole lines (non-temporal log
-        // stores were measured 2-15 % slower, profiles/README.md r04)
-        __builtin_amdgcn_raw_buffer_store_b32(code, lg.codes, cand ? pc + rankC * 4u : kOOB, 0, 0);
-        const u32x4 v = {dm[0], dm[1], dm[2], dm[3]};
-        __builtin_amdgcn_raw_buffer_store_b128(v, lg.recs, multi ? pm + rankM * 16u : kOOB, 0, 0);
-    } else {
-        asm volatile("" ::"v"(dm[0]), "v"(dm[1]), "v"(dm[2]), "v"(dm[3]), "v"(rankC), "v"(rankM), "v"(code));
-    }
+    // plain (write-back) stores: the L2 is what merges a tile's 80-byte appends into whole lines (non-temporal log
+    // stores were measured 2-15 % slower, profiles/README.md r04)
+    __builtin_amdgcn_raw_buffer_store_b32(code, lg.codes, cand ? pc + rankC * 4u : kOOB, 0, 0);
+    const u32x4 v = {dm[0], dm[1], dm[2], dm[3]};
+    __builtin_amdgcn_raw_buffer_store_b128(v, lg.recs, multi ? pm + rankM * 16u : kOOB, 0, 0);
     lp.ptrC += nc * 4u;
     lp.roomC -= nc;
     lp.ptrM += nm * 16u;
@@ -250,11 +237,9 @@ __device__ __forceinline__ void pack_group(const PackArgs &a, const Group<PAIR, 
         write_lane(meta.z, tot >> 16, d + 1);
         write_lane(meta.w, c1, d + 1);
     }
-    if (kAblate < 2) {
-        const uint32_t moff = (__umul24((uint32_t)t0 + (uint32_t)lane, a.ntiles) + tile) * 16u;
-        const u32x4 mv = {meta.x, meta.y, meta.z, meta.w};
-        __builtin_amdgcn_raw_buffer_store_b128(mv, lg.meta, (lane < kPrefetch && t0 + lane < a.nframes) ? moff : kOOB, 0, 0);
-    }
+    const uint32_t moff = (__umul24((uint32_t)t0 + (uint32_t)lane, a.ntiles) + tile) * 16u;
+    const u32x4 mv = {meta.x, meta.y, meta.z, meta.w};
+    __builtin_amdgcn_raw_buffer_store_b128(mv, lg.meta, (lane < kPrefetch && t0 + lane < a.nframes) ? moff : kOOB, 0, 0);
 }
 
 template <bool PAIR, bool FAST, bool HIGH, bool ONCE>
@@ -574,16 +559,10 @@ typedef uint32_t u32a1 __attribute__((aligned(1)));
 template <bool BYTE_ALIGNED>
 __device__ __forceinline__ void store_out4(uint8_t *p, uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
     const u32x4 v = {x, y, z, w};
-    if (kXStore & 2) {   // lab: plain
-        if (BYTE_ALIGNED) *reinterpret_cast<u32x4a1 *>(p) = v;
-        else *reinterpret_cast<u32x4a4 *>(p) = v;
-        return;
-    }
     if (BYTE_ALIGNED) __builtin_nontemporal_store(v, reinterpret_cast<u32x4a1 *>(p));
     else __builtin_nontemporal_store(v, reinterpret_cast<u32x4a4 *>(p));
 }
 __device__ __forceinline__ void store_out1(uint8_t *p, uint32_t v) {   // any byte address
-    if (kXStore & 1) { *reinterpret_cast<u32a1 *>(p) = v; return; }   // lab: plain
     __builtin_nontemporal_store(v, reinterpret_cast<u32a1 *>(p));
 }
 
@@ -736,13 +715,6 @@ __device__ __forceinline__ void expand_group(const ExpandArgs &a, uint32_t mx, u
         }
         code[r] = __builtin_amdgcn_raw_buffer_load_b32(codes, lane < t ? lane4 + sel : kOOB, 0, 0);   // a lane without a candidate reads 0
     }
-    if (kXAblate == 2) {   // lab: prologue + code loads
-        uint32_t acc = 0;
-#pragma unroll
-        for (uint32_t r = 0; r < R; r++) acc ^= code[r];
-        if (acc == 0xfffffff0u) stage[0] = acc;
-        return;
-    }
     __builtin_amdgcn_sched_barrier(0);   // all requests leave before anything waits for the first
     // entry offsets of all rounds first: independent DPP scans in one block of straight code fill each other's
     // wait states (a scan alone is 7 dependent steps with 2 idle cycles between them)
@@ -791,7 +763,6 @@ __device__ __forceinline__ void expand_group(const ExpandArgs &a, uint32_t mx, u
         if (m16 != 0u && (m16 & (m16 - 1u)) == 0u)
             stage[e] = ((src16 + (uint32_t)__builtin_ctz(m16)) << 8) | ((c >> 16) & 0xffu);   // kernels.cu:314-315
     }
-    if (kXAblate == 3) return;   // lab: + rounds
     walk_records(lane < tail ? (w0.y & 0xffffu) : 0u, (w0.y >> 16) & 0x3ffu, ((w0.x >> 28) << 10) | ((w0.y >> 26) << 4),
                  make_uint4(q0.x, q0.y, q0.z, q0.w), stage, lane);
     for (uint32_t head = 64u; head < tail; head += 64u) {   // the rest, 64 at a time
@@ -879,24 +850,20 @@ __device__ __forceinline__ void expand_tiles(const ExpandArgs &a, const uint4 *t
 }
 
 template <bool WIRE>
-__global__ __launch_bounds__(64 * kXWaves) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_expand(const ExpandArgs a) {
-    // kXWaves (= 1) independent waves per workgroup, an item each (nothing is shared, no barrier).  The bare dispatch of the
-    // 97 280 single-wave workgroups of a 1080p batch takes 21 us, that of 24 320 four-wave workgroups 8 -- and the whole kernel
-    // is 5 % SLOWER with them (117-120 -> 124-127 us alone, 130 with eight waves; pipelined batch unchanged or worse): the
-    // dispatch runs beside the execution, it is not what the kernel waits for (profiles/r05i_expand_waves_per_workgroup.log)
-    __shared__ __attribute__((aligned(16))) uint2 s_lists[kXWaves][kFList];         // group path: the item's queued (multi-byte) lanes; tile path: the 16 tiles' facts
-    __shared__ __attribute__((aligned(16))) uint32_t s_stages[kXWaves][kWStage];    // (byte index relative to the item's first tile) << 8 | difference
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_expand(const ExpandArgs a) {
+    // One wave per workgroup, an item each (nothing is shared, no barrier).  The bare dispatch of the 97 280 single-wave
+    // workgroups of a 1080p batch takes 21 us, that of 24 320 four-wave workgroups 8 -- and the whole kernel is 5 % SLOWER
+    // with them (117-120 -> 124-127 us alone, 130 with eight waves; pipelined batch unchanged or worse): the dispatch runs
+    // beside the execution, it is not what the kernel waits for (profiles/r05i_expand_waves_per_workgroup.log)
+    __shared__ __attribute__((aligned(16))) uint2 s_list[kFList];         // group path: the item's queued (multi-byte) lanes; tile path: the 16 tiles' facts
+    __shared__ __attribute__((aligned(16))) uint32_t s_stage[kWStage];    // (byte index relative to the item's first tile) << 8 | difference
     // 5120 bytes of LDS per wave: 32 waves per CU
     // beside the next batch's pack kernel (pipelined batches) these short, latency-bound waves must not queue for
     // issue slots behind the older, issue-hungry pack waves
     __builtin_amdgcn_s_setprio(2);
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    uint2 *const s_list = s_lists[wave];
-    uint32_t *const s_stage = s_stages[wave];
-    if (kXAblate == 9) return;   // lab: nothing but the dispatch of the grid
     asm volatile("v_mov_b32 v63, 0" ::: "v63");   // 64 declared vector registers (above)
-    const uint32_t t = blockIdx.y, sub = blockIdx.x * kXWaves + wave;
+    const uint32_t t = blockIdx.y, sub = blockIdx.x;
     if (sub * kWTiles >= a.ntiles) return;   // the grid is padded (see launch_expand)
     const uint32_t ngroups = (a.ntiles + kXTiles - 1) / kXTiles;
     // lane L < 16: meta word of tile 16 sub + L = {code offset, record offset, flagged bytes, candidates | multi-byte
@@ -950,7 +917,6 @@ __global__ __launch_bounds__(64 * kXWaves) __attribute__((amdgpu_waves_per_eu(8,
         expand_tiles<WIRE>(a, s_tinfo, s_stage, lane, xs0, dst0, w_xs, w_df, w_room);
         return;
     }
-    if (kXAblate == 1) return;   // lab: prologue only
     // quads when every four neighbouring tiles fill at most the 64 lanes of a round (all items of a webcam-like frame away
     // from moving objects), pairs otherwise
     const uint32_t nc_q = nc_b + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(nc + nc_b), 0x102 /* row_shl:2 */, 0xf, 0xf, true);
@@ -958,7 +924,7 @@ __global__ __launch_bounds__(64 * kXWaves) __attribute__((amdgpu_waves_per_eu(8,
     if (quads) expand_group<4>(a, m.x, m.y, ((bincl - both) & 0xffffu) | (nc << 16), s_list, s_stage, lane);
     else expand_group<2>(a, m.x, m.y, ((bincl - both) & 0xffffu) | (nc << 16), s_list, s_stage, lane);
     lds_handoff();
-    if (kXAblate < 2) flush_entries<WIRE>(a, s_stage, 0u, nent, xs0, dst0, w_xs, w_df, w_room);
+    flush_entries<WIRE>(a, s_stage, 0u, nent, xs0, dst0, w_xs, w_df, w_room);
 }
 
 hipError_t launch_expand(const ExpandArgs &a, int nframes, hipStream_t s) {
@@ -968,12 +934,12 @@ hipError_t launch_expand(const ExpandArgs &a, int nframes, hipStream_t s) {
     // tile's code log holds the codes of two consecutive frames, a line of its record log those of two or three, and the
     // L2s of the XCDs do not share -- without the padding the expander's requests to memory rise by 78 % (TCC_EA0_RDREQ
     // 1.87 M -> 3.33 M per batch, L2 hit rate 55 % -> 38 %, profiles/archive/r04_tcc_grid_padding.txt).
-    const uint32_t gx = ((a.ntiles + kWTiles - 1) / kWTiles + kXWaves - 1) / kXWaves;   // workgroups per frame
+    const uint32_t gx = (a.ntiles + kWTiles - 1) / kWTiles;   // workgroups per frame
     const dim3 grid((gx + 7u) / 8u * 8u, nframes);
     if (a.wire)
-        hipLaunchKernelGGL(k_expand<true>, grid, dim3(64 * kXWaves), 0, s, a);
+        hipLaunchKernelGGL(k_expand<true>, grid, dim3(64), 0, s, a);
     else
-        hipLaunchKernelGGL(k_expand<false>, grid, dim3(64 * kXWaves), 0, s, a);
+        hipLaunchKernelGGL(k_expand<false>, grid, dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

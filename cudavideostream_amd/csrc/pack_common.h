@@ -4,7 +4,6 @@
 #define MI355_PACK_COMMON_H_
 
 #include "internal.h"
-#include "lab.h"
 
 namespace mi355 {
 

@@ -9,7 +9,7 @@ import os
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# MI355DIFF_LIB: another build of the same library (the laboratory builds of tools/ab_build.sh under build/ab/)
+# MI355DIFF_LIB: another build of the same library (tests/sanitize.sh loads its AddressSanitizer build through it)
 LIB_PATH = os.environ.get("MI355DIFF_LIB") or os.path.join(_HERE, "libmi355diff.so")
 
 OK = 0
@@ -21,8 +21,7 @@ VIS_NONE, VIS_HEAT, VIS_RED, VIS_RED_OVERLAP, VIS_GRAY, VIS_BINARIZE = range(6)
 (OP_GRAY_AVG, OP_GRAY_WEIGHTED, OP_BINARIZE, OP_GRAY_AVG_BINARIZE, OP_GRAY_WEIGHTED_BINARIZE, OP_HEAT_MAP,
  OP_RED_DENSE, OP_CONV3X3, OP_MEDIAN5X5) = range(1, 10)
 
-(OPT_PIPELINE, OPT_SPLIT_PCT, OPT_DENSE_PCT, OPT_CHAIN_HINT, OPT_PACK_BLOCKS, OPT_MEDIAN_ROWS,
- OPT_SCAN_EPOCH_LEFT) = range(1, 8)   # MI355_OPT_*
+OPT_PIPELINE, OPT_MEDIAN_ROWS, OPT_SCAN_EPOCH_LEFT = 1, 6, 7   # MI355_OPT_* (ids 2..5 are retired and refused)
 FLAG_OWN_QUEUES = 1   # MI355_FLAG_*
 PREPARE_BATCHES, PREPARE_GRAY_CHAIN, PREPARE_RED_CLEAR, PREPARE_CONV_KXK, PREPARE_EXEC, PREPARE_ALL = 1, 2, 4, 8, 16, 31   # MI355_PREPARE_*
 
@@ -135,7 +134,7 @@ SYMBOLS = {
     "mi355_group_synchronize": (C.c_int, [C.c_void_p]),
 }
 GROUP_ID_BYTES = 128   # MI355_GROUP_ID_BYTES
-ABI_VERSION = 7        # MI355_ABI_VERSION of the include/mi355diff.h these argument lists were written against
+ABI_VERSION = 8        # MI355_ABI_VERSION of the include/mi355diff.h these argument lists were written against
 
 _lib = None
 

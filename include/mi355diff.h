@@ -76,8 +76,11 @@ typedef struct mi355_config {
  *      (additions)
  *   6  round 6: + mi355_prepare, mi355_alloc_outputs, MI355_OPT_SCAN_EPOCH_LEFT, cfg.flags bit MI355_FLAG_OWN_QUEUES (additions only)
  *   7  + the compact wire format: mi355_cwire_frame_bytes, mi355_cwire_bytes_max, mi355_cwire_encode_batch,
- *      mi355_cwire_decode_batch, mi355_cwire_apply_host (additions only) */
-#define MI355_ABI_VERSION 7
+ *      mi355_cwire_decode_batch, mi355_cwire_apply_host (additions only)
+ *   8  the schedule options 2..5 (split share, dense threshold, filter/batch chain hint, pack grid) are gone: their ids
+ *      are refused (MI355_ERR_INVALID) and will not be reused; their defaults are the library's fixed schedule, unchanged
+ *      (mi355_diff_stream_batch) */
+#define MI355_ABI_VERSION 8
 int mi355_abi_version(void);
 
 /* ---- life cycle: CUDACore::CUDACore (kernels.cu:377-428) without the uploads ------------------ */
@@ -134,22 +137,16 @@ int mi355_synchronize(mi355_core *core);
  * then: on the core's own stream the library's kernels are not ordered against the framework's stream.
  * (cudavideostream_amd/core.py holds such references itself until synchronize().) */
 
-/* Options.  The schedule of the batches on the core's own stream can be tuned per core; RESULTS never depend on it.
- * Changing an option first waits for the work the core has queued.  Of the environment the library reads two variables
- * and nothing else: MI355_PIPELINE=0 makes MI355_OPT_PIPELINE default to 0 for every core of the process (a switch for
+/* Options.  The pipelining of the batches on the core's own stream can be switched off per core; two more options are
+ * seams for the tests.  RESULTS never depend on any of them.  Changing an option first waits for the work the core has
+ * queued; an unknown id (2..5 included: options of ABI version 7 and earlier) is refused with MI355_ERR_INVALID.
+ * Of the environment the library reads two variables and nothing else: MI355_PIPELINE=0 makes MI355_OPT_PIPELINE default to 0 for every core of the process (a switch for
  * the operator of an unmodified server binary); and, in the multi-GPU entry points only, MI355_RCCL_LIB=path names
  * another library with the ten RCCL entry points they bind instead of librccl.so.1 (the tests' stand-ins, which let
  * several ranks share the one GPU of a test box). */
 #define MI355_OPT_PIPELINE 1     /* 1 (default): own-stream batches are pipelined (below); 0: one kernel after the other */
-#define MI355_OPT_SPLIT_PCT 2    /* 50 (default): a pipelined batch is packed by two launches, this share of the tiles on
-                                  * the first; 5..95, or 0 = one launch */
-#define MI355_OPT_DENSE_PCT 3    /* 40 (default): batches in which more than this share of the bytes changed are not
-                                  * overlapped (adaptive overlap, below); 0 = always overlap, 100 = same */
-#define MI355_OPT_CHAIN_HINT 4   /* 1 (default): a batch that follows a frame filter on this core is not overlapped; 0: is */
-#define MI355_OPT_PACK_BLOCKS 5  /* -1 (default): the pipelined pack kernel runs on 4 workgroups per CU; 0: one tile per
-                                  * wave; n > 0: n workgroups */
-#define MI355_OPT_MEDIAN_ROWS 6  /* 0 (default): the 5x5 median's column-strip kernel walks bands of 5..60 rows, chosen per launch
-                                  * (from 20 rows up the length that wastes least of the frame's last pair of bands; shorter
+#define MI355_OPT_MEDIAN_ROWS 6  /* tests only: 0 (default): the 5x5 median's column-strip kernel walks bands of 5..60
+                                  * rows, chosen per launch (from 20 rows up the length that wastes least of the frame's last pair of bands; shorter
                                   * when that makes fewer than a few thousand waves); 5, 10, .. 60: this many */
 #define MI355_OPT_SCAN_EPOCH_LEFT 7 /* tests only: launches of the index kernel left before its 33-bit launch tag wraps (the
                                   * totals are then cleared behind a synchronisation and the tag restarts at 1); set: 1..2^30 */
@@ -190,13 +187,13 @@ int mi355_set_glyphs(mi355_core *core, const uint8_t *chars_px, int nglyphs, int
  * mi355_int_diff) take frames, not packed streams, and are ordered on the core's stream only: they may run beside
  * the expansion of the batch before (visualiser of frame k + 1 beside the expansion of frame k).  With a caller's
  * stream (mi355_set_stream) nothing is pipelined: every kernel runs on that stream, in call order.
- * MI355_OPT_PIPELINE 0 (or MI355_PIPELINE=0 in the environment) switches the pipelining off.  (A pipelined batch is packed
- * by two kernel launches on two streams of the core, half the tiles each; MI355_OPT_SPLIT_PCT 0 packs it with one.)
+ * MI355_OPT_PIPELINE 0 (or MI355_PIPELINE=0 in the environment) switches the pipelining off.  A pipelined batch is packed
+ * on 4 workgroups per CU; a frame of 64 tiles (64 KiB) or more is packed by two kernel launches on two streams of the
+ * core, the first half of the tiles (rounded down to a multiple of 4) and the rest, each with its share of that grid.
  * A batch that follows a frame filter on this core (the server's visualiser or noise filter in front of every diff) is not
- * overlapped either: one kernel after the other measured faster for such chains (MI355_OPT_CHAIN_HINT 0: overlap
- * regardless).
- * The overlap is adaptive: a batch in which more than 40 % of the bytes changed (a scene change; MI355_OPT_DENSE_PCT) has an
- * expansion longer than its pack kernel and loses by running beside the next batch.  The index kernel of every own-stream
+ * overlapped: one kernel after the other measured faster for such chains.
+ * The overlap is adaptive: a batch in which more than 40 % of the bytes changed (a scene change) has an expansion longer
+ * than its pack kernel and loses by running beside the next batch.  The index kernel of every own-stream
  * batch leaves the batch's total in a word of pinned host memory; the library, without ever waiting for it, runs batches
  * one after the other while the latest total that has arrived says "dense".  Only the schedule depends on it, never a result.
  * Cache policy: the frames of a stream are read, and every output (d_xs, d_diff, d_wire; the visualiser frames of the

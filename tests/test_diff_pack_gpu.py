@@ -635,37 +635,35 @@ def test_back_to_back_pair_batches_without_synchronisation(po):
         assert np.array_equal(outs[k][2][:tot].cpu().numpy(), edf), k
 
 
-def test_filter_then_diff_on_own_stream_orders_every_part(po):
+def test_split_batch_then_filter_orders_every_part(po):
     """Config 4's chain on the core's own stream with ONE scratch buffer and no synchronisation in between: the noise filter
-    writes `filt`, the batch's pack kernels -- two launches on two streams of the core -- read it, the next round's filter
-    rewrites it.  Every pack launch has to come behind the filter that made its input (the parts on other streams wait for
-    an event of the core's stream) and the next filter behind every part of the batch before.  Against the oracle, state
-    carried through the filtered frames."""
+    writes 2T frames of `filt`, batch A reads the first T and batch B the other T, the next round's filter rewrites all of
+    them.  A follows the filter and runs one kernel after the other; B follows a batch, so it is pipelined and its pack is
+    split into two launches on two streams of the core.  Every pack launch has to come behind the filter that made its
+    input (the parts on other streams wait for an event of the core's stream) and the next filter behind every part of
+    B, the batch right before it.  Against the oracle, state carried through the filtered frames."""
     w, h, T, K = 640, 360, 6, 4
     n = 3 * w * h
     k9 = po.gaussian_kernel(3, 1.5)
-    base, frames = synth.webcam_stream(T * K, w, h, seed=83)
+    base, frames = synth.webcam_stream(2 * T * K, w, h, seed=83)
     frames = np.ascontiguousarray(frames)
     filtered = np.stack([po.conv3x3(f, w, h, k9) for f in frames])
     eo, exs, edf, est = po.diff_stream(filtered, base)
     d_fr = to_dev(frames)
-    filt = torch.empty((T, n), dtype=torch.uint8, device=DEV)
+    filt = torch.empty((2 * T, n), dtype=torch.uint8, device=DEV)
     outs = [(torch.zeros(T + 1, dtype=torch.int32, device=DEV), torch.full((T * n,), -7, dtype=torch.int32, device=DEV),
-             torch.zeros(T * n, dtype=torch.uint8, device=DEV)) for _ in range(K)]
-    # (MI355_OPT_CHAIN_HINT 0: by default a batch that follows a frame filter is not overlapped at all -- this test is about
-    # the overlapped batch's ordering)
-    with CUDACore(w, h, k=k9, max_batch=T, sample_mat_data=base) as core:
-        core.set_option(lib.OPT_CHAIN_HINT, 0)
-        assert core.get_option(lib.OPT_CHAIN_HINT) == 0
+             torch.zeros(T * n, dtype=torch.uint8, device=DEV)) for _ in range(2 * K)]
+    with CUDACore(w, h, k=k9, max_batch=2 * T, sample_mat_data=base) as core:
         torch.cuda.synchronize()
         for k in range(K):
-            RawCore.filter_batch(core, lib.OP_CONV3X3, d_fr[k * T:(k + 1) * T], filt, T)
-            RawCore.diff_stream_batch(core, filt, T, *outs[k], T * n)
+            RawCore.filter_batch(core, lib.OP_CONV3X3, d_fr[2 * k * T:2 * (k + 1) * T], filt, 2 * T)
+            RawCore.diff_stream_batch(core, filt[:T], T, *outs[2 * k], T * n)       # A: after the filter, sequential
+            RawCore.diff_stream_batch(core, filt[T:], T, *outs[2 * k + 1], T * n)   # B: pipelined, split
         core.synchronize()
         assert np.array_equal(core.get_state(), est)
     per_frame = np.diff(eo.astype(np.int64))
     at = 0
-    for k in range(K):
+    for k in range(2 * K):
         cnt = per_frame[k * T:(k + 1) * T]
         off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.uint32)
         tot = int(off[-1])
@@ -688,7 +686,10 @@ def test_pipelined_1080p_batches_equal_the_sequential_path(po):
     """Full-size overlap: five batches of 65 (odd) 1080p frames queued back to back on the core's own stream -- the
     expansion of batch k runs beside the pack kernel of batch k + 1, two sets of logs in turn, the pack kernel on its
     pipelined grid --, the last two in the wire form; against the same sequence on a caller's stream (never pipelined),
-    byte for byte: offsets, indices, differences, wire bytes and the final state; batch 0 also against the oracle."""
+    byte for byte: offsets, indices, differences, wire bytes and the final state; batch 0 also against the oracle.
+    This is also the test of the pack kernel's grid-stride walk: the pipelined grid is 4 workgroups of 4 waves per CU,
+    shared by the two launches of a split batch, and a 1080p frame has 6075 tiles -- each launch's waves walk more than
+    one tile each (about 3036 tiles on 2044 waves on a 256-CU chip)."""
     w, h, T, K = 1920, 1080, 65, 5
     n = 3 * w * h
     base, frames = synth.webcam_stream(T * K, w, h, seed=77, device=DEV)
@@ -772,49 +773,70 @@ def test_pipelined_batches_then_other_entry_points(po):
         assert np.array_equal(core.get_state(), est)
 
 
-def test_options_change_the_schedule_never_the_result(po):
-    """mi355_set_option (include/mi355diff.h, "Options"): every combination of pipelining, split share, pack grid, dense
-    threshold and chain hint gives the oracle's stream for batches queued back to back on the core's own stream; values
-    outside an option's range, unknown options and non-zero cfg.flags are refused."""
-    w, h, T, K = 640, 360, 5, 3
-    n = 3 * w * h
-    base, frames = synth.webcam_stream(T * K, w, h, seed=91)
-    frames = np.ascontiguousarray(frames)
-    eo, exs, edf, est = po.diff_stream(frames, base)
-    d_fr = to_dev(frames)
-    combos = [{}, {lib.OPT_PIPELINE: 0}, {lib.OPT_SPLIT_PCT: 0}, {lib.OPT_SPLIT_PCT: 30}, {lib.OPT_SPLIT_PCT: 95},
-              {lib.OPT_PACK_BLOCKS: 0}, {lib.OPT_PACK_BLOCKS: 7}, {lib.OPT_PACK_BLOCKS: 4096, lib.OPT_SPLIT_PCT: 70},
-              {lib.OPT_DENSE_PCT: 0}, {lib.OPT_DENSE_PCT: 1}, {lib.OPT_CHAIN_HINT: 0, lib.OPT_DENSE_PCT: 100}]
-    per_frame = np.diff(eo.astype(np.int64))
-    for opts in combos:
+def test_every_schedule_gives_the_oracle_stream(po):
+    """Every schedule an own-stream batch can take (include/mi355diff.h, mi355_diff_stream_batch) gives the oracle's stream,
+    batches queued back to back on the core's own stream: pipelined with the pack split into two launches (640x360, 675
+    tiles); pipelined with one launch (160x120, 57 tiles: under 64); MI355_OPT_PIPELINE 0; the dense fallback and the
+    return from it (S0-like batches, 84 % changed, then webcam batches in the same core: a synchronisation after the first
+    of each kind makes its total arrive, so the batches behind it take the dense, then the overlapped schedule); and
+    batches that each follow a frame filter.  MI355_OPT_PIPELINE 2, unknown option ids -- the retired 2..5 among them --
+    and unknown cfg.flags bits are refused."""
+    T = 5
+
+    def run(w, h, base, frames, pipeline=1, filters=False, sync_after=()):
+        n = 3 * w * h
+        K = len(frames) // T
+        eo, exs, edf, est = po.diff_stream(frames, base)
+        d_fr = to_dev(frames)
+        scratch = torch.empty((T, n), dtype=torch.uint8, device=DEV)
+        outs = [(torch.zeros(T + 1, dtype=torch.int32, device=DEV), torch.full((T * n,), -7, dtype=torch.int32, device=DEV),
+                 torch.zeros(T * n, dtype=torch.uint8, device=DEV)) for _ in range(K)]
         with CUDACore(w, h, max_batch=T, sample_mat_data=base) as core:
-            for k, v in opts.items():
-                core.set_option(k, v)
-                assert core.get_option(k) == v
-            outs = [(torch.zeros(T + 1, dtype=torch.int32, device=DEV), torch.full((T * n,), -7, dtype=torch.int32, device=DEV),
-                     torch.zeros(T * n, dtype=torch.uint8, device=DEV)) for _ in range(K)]
+            if pipeline != 1:
+                core.set_option(lib.OPT_PIPELINE, pipeline)
+            assert core.get_option(lib.OPT_PIPELINE) == pipeline
             torch.cuda.synchronize()
-            for k in range(K):   # no synchronisation between the batches
+            for k in range(K):   # no synchronisation between the batches but the ones asked for
+                if filters:
+                    RawCore.filter_batch(core, lib.OP_GRAY_AVG, d_fr[k * T:(k + 1) * T], scratch, T)
                 RawCore.diff_stream_batch(core, d_fr[k * T:(k + 1) * T], T, *outs[k], T * n)
+                if k in sync_after:
+                    core.synchronize()
             core.synchronize()
-            assert np.array_equal(core.get_state(), est), opts
-            at = 0
-            for k in range(K):
-                cnt = per_frame[k * T:(k + 1) * T]
-                off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.uint32)
-                tot = int(off[-1])
-                assert np.array_equal(outs[k][0].cpu().numpy().view(np.uint32), off), (opts, k)
-                assert np.array_equal(outs[k][1][:tot].cpu().numpy(), exs[at:at + tot]), (opts, k)
-                assert np.array_equal(outs[k][2][:tot].cpu().numpy(), edf[at:at + tot]), (opts, k)
-                at += tot
+            assert np.array_equal(core.get_state(), est), (w, h, pipeline, filters)
+        per_frame = np.diff(eo.astype(np.int64))
+        at = 0
+        for k in range(K):
+            cnt = per_frame[k * T:(k + 1) * T]
+            off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.uint32)
+            tot = int(off[-1])
+            what = (w, h, pipeline, filters, k)
+            assert np.array_equal(outs[k][0].cpu().numpy().view(np.uint32), off), what
+            assert np.array_equal(outs[k][1][:tot].cpu().numpy(), exs[at:at + tot]), what
+            assert np.array_equal(outs[k][2][:tot].cpu().numpy(), edf[at:at + tot]), what
+            at += tot
+        return [per_frame[k * T:(k + 1) * T].sum() / (T * n) for k in range(K)]
+
+    w, h = 640, 360
+    base, frames = synth.webcam_stream(3 * T, w, h, seed=91)
+    frames = np.ascontiguousarray(frames)
+    run(w, h, base, frames)                      # pipelined, split
+    run(w, h, base, frames, pipeline=0)          # one kernel after the other
+    run(w, h, base, frames, filters=True)        # every batch follows a frame filter
+    small, small_frames = synth.webcam_stream(3 * T, 160, 120, seed=92)
+    run(160, 120, small, np.ascontiguousarray(small_frames))   # pipelined, one pack launch
+    dense = np.stack([synth.refrand_frame(3 * w * h, 300 + i) for i in range(3 * T)])
+    base, web = synth.webcam_stream(3 * T, w, h, seed=93)
+    share = run(w, h, base, np.ascontiguousarray(np.concatenate([dense, web])), sync_after=(0, 3))
+    assert min(share[:3]) > 0.4 and max(share[3:]) < 0.4, share   # both sides of the 40 % the library switches at
     with CUDACore(8, 8) as core:
-        assert core.get_option(lib.OPT_PIPELINE) == 1 and core.get_option(lib.OPT_SPLIT_PCT) == 50
-        assert core.get_option(lib.OPT_DENSE_PCT) == 40 and core.get_option(lib.OPT_CHAIN_HINT) == 1
-        assert core.get_option(lib.OPT_PACK_BLOCKS) == -1
-        for k, v in ((lib.OPT_PIPELINE, 2), (lib.OPT_SPLIT_PCT, 3), (lib.OPT_SPLIT_PCT, 96), (lib.OPT_DENSE_PCT, 101),
-                     (lib.OPT_CHAIN_HINT, -1), (lib.OPT_PACK_BLOCKS, -2), (99, 0), (0, 1)):
+        assert core.get_option(lib.OPT_PIPELINE) == 1
+        for k, v in ((lib.OPT_PIPELINE, 2), (lib.OPT_PIPELINE, -1), (2, 50), (3, 40), (4, 1), (5, -1), (99, 0), (0, 1)):
             with pytest.raises(lib.Mi355Error):
                 core.set_option(k, v)
+        for k in (2, 3, 4, 5, 99):
+            with pytest.raises(lib.Mi355Error):
+                core.get_option(k)
     import ctypes as C
     h_ = C.c_void_p()
     cfg = lib.Config(8, 8, 20, 1, -1, 0, 0, 2)   # an unknown flag bit (the experiment flags of rounds 2-4 are gone; bit 0 is MI355_FLAG_OWN_QUEUES)

@@ -7,19 +7,8 @@
 //
 //   diffbench [--width W] [--height H] [--batch B] [--steps K] [--warmup W] [--seed S]
 //             [--pairs] [--checksum T] [--cores C] [--digest]
-//             [--opt ID=VALUE ...]      mi355_set_option on every core (1 pipeline, 2 split per cent, 3 dense per cent,
-//                                       4 chain hint, 5 pack workgroups, 6 median band rows: include/mi355diff.h "Options")
 //             [--regime s0|flip|static] [--apart]   pairs of the dense / static regimes; pairs that share no frame
-//             [--skew-frames N] [--skew-xs N] [--skew-df N] [--print-ptrs]   the frames / the two output arrays displaced by N
-//                                       bytes inside a larger allocation
-//             [--reroll N]              pairs: after the run, N new pairs of output arrays, N new index arrays, N new value
-//                                       arrays, N new cores, N new copies of the frames -- the kernels' times after each
-//                                       (which buffer's placement decides the dense expansion's speed: profiles/README.md)
 //             [--lib-alloc]             the two output arrays from mi355_alloc_outputs (a pair placed for the dense expansion)
-//             [--place N]               pairs: the two output arrays inside ONE allocation, the value array at a sweep of
-//                                       distances behind the index array and the pair at a sweep of displacements; then N
-//                                       pairs of arrays from hipMalloc, from the HIP virtual-memory calls (hipMemCreate: one
-//                                       physical handle per array) and from mi355_dev_alloc -- the expansion's time for each
 //   diffbench --filters [--batch B] [--steps K]     the filter kernels and the BASELINE config 3 / 4 chains
 //                                                   (same lines as tools/bench_filters.py, for the --pmc passes)
 #include <hip/hip_runtime.h>
@@ -30,7 +19,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <utility>
 #include <vector>
 
 #include "../include/mi355diff.h"
@@ -98,72 +86,12 @@ __global__ __launch_bounds__(64) void k_corun_mem(const uint4 *buf, size_t nvec,
     if (acc == 0x12345u) out[0] = acc;
 }
 
-// --place probes: what distinguishes output arrays on which the dense expansion is fast from those on which it is slow?
-typedef uint32_t pv4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void k_probe_wide(pv4 *buf, size_t nvec) {   // streaming 16-byte non-temporal stores
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
-        const pv4 v = {(uint32_t)i, 1u, 2u, 3u};
-        __builtin_nontemporal_store(v, buf + i);
-    }
-}
-// the dense expansion's own shape: one wave per item, an item = a contiguous run of E entries: 16 bytes of indices and 4 of
-// values per lane and step, non-temporal
-__global__ __launch_bounds__(64) void k_probe_items(uint32_t *xs, uint8_t *df, uint32_t E, uint32_t items_per_frame) {
-    const size_t item = (size_t)blockIdx.y * items_per_frame + blockIdx.x;
-    uint32_t *x = xs + item * E;
-    uint8_t *d = df + item * E;
-    for (uint32_t e = threadIdx.x * 4u; e + 3u < E; e += 256u) {
-        const pv4 v = {e, e + 1u, e + 2u, e + 3u};
-        __builtin_nontemporal_store(v, reinterpret_cast<pv4 *>(x + e));
-        __builtin_nontemporal_store(e, reinterpret_cast<uint32_t *>(d + e));
-    }
-}
-// the same with the items dealt to the workgroups in a scattered order (item = w * step mod n): the waves that run at the same
-// time then write all over the arrays instead of inside one sliding window
-__global__ __launch_bounds__(64) void k_probe_items_perm(uint32_t *xs, uint8_t *df, uint32_t E, uint32_t nitems, uint32_t step) {
-    const size_t w = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-    if (w >= nitems) return;
-    const size_t item = (w * step) % nitems;
-    uint32_t *x = xs + item * E;
-    uint8_t *d = df + item * E;
-    for (uint32_t e = threadIdx.x * 4u; e + 3u < E; e += 256u) {
-        const pv4 v = {e, e + 1u, e + 2u, e + 3u};
-        __builtin_nontemporal_store(v, reinterpret_cast<pv4 *>(x + e));
-        __builtin_nontemporal_store(e, reinterpret_cast<uint32_t *>(d + e));
-    }
-}
-// only the value array / only the index array of the expansion's shape
-__global__ __launch_bounds__(64) void k_probe_items_one(uint32_t *xs, uint8_t *df, uint32_t E, uint32_t items_per_frame, int which) {
-    const size_t item = (size_t)blockIdx.y * items_per_frame + blockIdx.x;
-    uint32_t *x = xs + item * E;
-    uint8_t *d = df + item * E;
-    for (uint32_t e = threadIdx.x * 4u; e + 3u < E; e += 256u) {
-        const pv4 v = {e, e + 1u, e + 2u, e + 3u};
-        if (which == 0) __builtin_nontemporal_store(v, reinterpret_cast<pv4 *>(x + e));
-        else __builtin_nontemporal_store(e, reinterpret_cast<uint32_t *>(d + e));
-    }
-}
-// one random 64-byte line per lane and step: address translation (TLB reach: page-fragment size) and row misses, no streaming
-__global__ __launch_bounds__(256) void k_probe_rand(const pv4 *buf, size_t nlines, uint32_t *sink, int iters) {
-    uint32_t x = (blockIdx.x * 256u + threadIdx.x) * 2654435761u + 12345u, acc = 0;
-    for (int i = 0; i < iters; i++) {
-        x = x * 1664525u + 1013904223u;
-        const size_t line = ((size_t)x * 2654435761ull >> 7) % nlines;
-        acc += buf[line * 4].x;
-    }
-    if (acc == 0x12345u) sink[0] = acc;
-}
-
 int main(int argc, char **argv) {
     int W = 1920, H = 1080, B = 256, K = 20, WU = 3, checksum_t = -2, ncores = 1;
     uint32_t seed = 21;
-    bool pairs = false, filters = false, digest = false, apart = false, print_ptrs = false;
-    size_t skew_xs = 0, skew_df = 0, skew_frames = 0;
-    int reroll = 0, place = 0;
+    bool pairs = false, filters = false, digest = false, apart = false;
     bool lib_alloc = false;   // the two output arrays from mi355_alloc_outputs (a pair placed for the dense expansion)
     const char *corun = nullptr; int corun_blocks = 2048;
-    std::vector<std::pair<int, int>> opts;
     const char *regime = nullptr;   // --regime s0|flip|static: pairs of the dense / static regimes (tools/bench_regimes.py's inputs)
     for (int i = 1; i < argc; i++) {
         auto next = [&](int &v) { if (i + 1 < argc) v = atoi(argv[++i]); };
@@ -182,16 +110,8 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--corun") && i + 1 < argc) corun = argv[++i];
         else if (!strcmp(argv[i], "--regime") && i + 1 < argc) { regime = argv[++i]; pairs = true; }
         else if (!strcmp(argv[i], "--corun-blocks")) next(corun_blocks);
-        else if (!strcmp(argv[i], "--skew-xs") && i + 1 < argc) skew_xs = (size_t)atoll(argv[++i]) & ~(size_t)15;
-        else if (!strcmp(argv[i], "--skew-df") && i + 1 < argc) skew_df = (size_t)atoll(argv[++i]) & ~(size_t)15;
-        else if (!strcmp(argv[i], "--skew-frames") && i + 1 < argc) skew_frames = (size_t)atoll(argv[++i]) & ~(size_t)15;
-        else if (!strcmp(argv[i], "--print-ptrs")) print_ptrs = true;
-        else if (!strcmp(argv[i], "--reroll")) next(reroll);
-        else if (!strcmp(argv[i], "--place")) next(place);
         else if (!strcmp(argv[i], "--lib-alloc")) lib_alloc = true;
-        else if (!strcmp(argv[i], "--opt") && i + 1 < argc) { int id = 0, v = 0; if (sscanf(argv[++i], "%d=%d", &id, &v) == 2) opts.push_back({id, v}); }
     }
-    auto apply_opts = [&](mi355_core *c) { for (auto &o : opts) MI_OK(mi355_set_option(c, o.first, o.second)); };
     const size_t n = (size_t)3 * W * H;
     if (checksum_t >= -1) {  // print a checksum of one generated frame (generator cross-check)
         uint8_t *d; HIP_OK(hipMalloc((void **)&d, n));
@@ -217,7 +137,6 @@ int main(int argc, char **argv) {
         std::vector<uint8_t> h_base(n);
         for (int c = 0; c < ncores; c++) {
             MI_OK(mi355_create(&cfg, &cores[c]));
-            apply_opts(cores[c]);
             HIP_OK(hipMalloc((void **)&fr[c], n * (size_t)(B + 1)));
             for (int t = -1; t < B; t++)
                 hipLaunchKernelGGL(k_webcam_frame, g, b, 0, 0, fr[c] + (size_t)(t + 1) * n, t, W, H, seed + c);
@@ -247,7 +166,6 @@ int main(int argc, char **argv) {
     if (filters) {   // mi355_filter_batch per kernel, then the two chains; B frames resident, K repetitions each
         mi355_core *core = nullptr;
         MI_OK(mi355_create(&cfg, &core));
-        apply_opts(core);
         uint8_t *fr, *out, *filt; uint32_t *off; int32_t *xs; uint8_t *df;
         const size_t cap = (size_t)B * n / 4;
         HIP_OK(hipMalloc((void **)&fr, n * (size_t)(B + 1)));
@@ -300,12 +218,10 @@ int main(int argc, char **argv) {
     }
     mi355_core *core = nullptr;
     MI_OK(mi355_create(&cfg, &core));
-    apply_opts(core);
 
     uint8_t *d_frames = nullptr, *d_base = nullptr;
     const int nfr = apart ? 2 * B : B + 1;
-    HIP_OK(hipMalloc((void **)&d_frames, n * (size_t)nfr + skew_frames));
-    d_frames += skew_frames;
+    HIP_OK(hipMalloc((void **)&d_frames, n * (size_t)nfr));
     HIP_OK(hipMalloc((void **)&d_base, n));
     const dim3 g((unsigned)((n + 255) / 256)), b(256);
     hipLaunchKernelGGL(k_webcam_frame, g, b, 0, 0, d_base, -1, W, H, seed);
@@ -332,8 +248,6 @@ int main(int argc, char **argv) {
     const size_t cap = regime ? (size_t)B * n : ((size_t)B * n / 8 > (1u << 20) ? (size_t)B * n / 8 : (1u << 20));
     uint32_t *d_off; int32_t *d_xs; uint8_t *d_df;
     HIP_OK(hipMalloc((void **)&d_off, sizeof(uint32_t) * (B + 1)));
-    // --skew-xs / --skew-df BYTES (multiples of 16): the output arrays displaced inside a larger allocation -- does the
-    // expansion's time depend on WHERE its outputs lie (profiles/r05ae_*)?  --print-ptrs shows the addresses.
     if (lib_alloc) {
         void *a = nullptr, *b2 = nullptr; int draws = 0;
         const auto ta = std::chrono::high_resolution_clock::now();
@@ -341,12 +255,9 @@ int main(int argc, char **argv) {
         fprintf(stderr, "mi355_alloc_outputs: %d value array(s) drawn in %.1f ms\n", draws, std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - ta).count() * 1e3);
         d_xs = (int32_t *)a; d_df = (uint8_t *)b2;
     } else {
-    HIP_OK(hipMalloc((void **)&d_xs, sizeof(int32_t) * cap + skew_xs));
-    HIP_OK(hipMalloc((void **)&d_df, cap + skew_df));
+        HIP_OK(hipMalloc((void **)&d_xs, sizeof(int32_t) * cap));
+        HIP_OK(hipMalloc((void **)&d_df, cap));
     }
-    d_xs = reinterpret_cast<int32_t *>(reinterpret_cast<uint8_t *>(d_xs) + skew_xs);
-    d_df += skew_df;
-    if (print_ptrs) fprintf(stderr, "d_xs %p d_df %p d_off %p frames %p\n", (void *)d_xs, (void *)d_df, (void *)d_off, (void *)(pairs ? d_cur : d_frames));
 
     auto step = [&]() {
         if (pairs) MI_OK(mi355_diff_pairs_batch(core, d_cur, d_prev, apart ? 2 * n : n, B, d_off, d_xs, d_df, cap));
@@ -403,183 +314,6 @@ int main(int argc, char **argv) {
            pairs ? "pairs" : "stream", W, H, B, K, (double)B * K / sec, sec / K * 1e3, alg / (sec / K) / 8e12, pack_ms, ms_total / (launches ? launches : 1),
            k_pack / (kl ? kl : 1) * 1e3, k_scan / (kl ? kl : 1) * 1e3, k_exp / (kl ? kl : 1) * 1e3,
            p / B, alg / (pack_ms * 1e-3) / 1e9, mhz, hbm, mi355_workspace_bytes(core));
-    if (reroll > 0 && pairs) {
-        // Which buffers' placement decides the dense expansion's speed (profiles/README.md, "two speeds")?  In ONE process:
-        // new output arrays (the old ones stay allocated), then a new core = new logs (created before the old one is
-        // destroyed), then new copies of the input frames; the three kernels' times after every re-draw.
-        auto measure = [&](const char *what, int i) {
-            for (int w = 0; w < WU; w++) MI_OK(mi355_diff_pairs_batch(core, d_cur, d_prev, apart ? 2 * n : n, B, d_off, d_xs, d_df, cap));
-            MI_OK(mi355_synchronize(core));
-            MI_OK(mi355_set_timing(core, 1));
-            MI_OK(mi355_reset_timing(core));
-            for (int k = 0; k < K; k++) MI_OK(mi355_diff_pairs_batch(core, d_cur, d_prev, apart ? 2 * n : n, B, d_off, d_xs, d_df, cap));
-            MI_OK(mi355_synchronize(core));
-            double a = 0, b = 0, c = 0; int l = 0;
-            MI_OK(mi355_get_kernel_timing(core, &a, &b, &c, &l));
-            printf("reroll %s %d: kernels_us [%.1f, %.1f, %.1f]  xs %p df %p\n", what, i, a / l * 1e3, b / l * 1e3, c / l * 1e3, (void *)d_xs, (void *)d_df);
-        };
-        for (int i = 1; i <= reroll; i++) {
-            HIP_OK(hipMalloc((void **)&d_xs, sizeof(int32_t) * cap));
-            HIP_OK(hipMalloc((void **)&d_df, cap));
-            measure("outputs", i);
-        }
-        for (int i = 1; i <= reroll; i++) {   // the index array alone, then the value array alone
-            HIP_OK(hipMalloc((void **)&d_xs, sizeof(int32_t) * cap));
-            measure("xs-only", i);
-        }
-        for (int i = 1; i <= reroll; i++) {
-            HIP_OK(hipMalloc((void **)&d_df, cap));
-            measure("df-only", i);
-        }
-        for (int i = 1; i <= reroll; i++) {
-            mi355_core *fresh = nullptr;
-            MI_OK(mi355_create(&cfg, &fresh));
-            mi355_destroy(core);
-            core = fresh;
-            apply_opts(core);
-            measure("core", i);
-        }
-        for (int i = 1; i <= reroll; i++) {
-            const size_t bytes = (size_t)((regime || apart) ? 2 * B : B + 1) * n;
-            uint8_t *copy = nullptr;
-            HIP_OK(hipMalloc((void **)&copy, bytes));
-            HIP_OK(hipMemcpy(copy, d_prev, bytes, hipMemcpyDeviceToDevice));
-            d_cur = copy + (d_cur - d_prev);
-            d_prev = copy;
-            measure("frames", i);
-        }
-    }
-    if (place > 0 && pairs) {
-        // Where do the two output arrays have to lie for the dense expansion to run at its fast speed (profiles/README.md, r06)?
-        auto measure = [&](const char *what, long long a, long long b2) {
-            for (int w = 0; w < WU; w++) MI_OK(mi355_diff_pairs_batch(core, d_cur, d_prev, apart ? 2 * n : n, B, d_off, d_xs, d_df, cap));
-            MI_OK(mi355_synchronize(core));
-            MI_OK(mi355_set_timing(core, 1));
-            MI_OK(mi355_reset_timing(core));
-            for (int k = 0; k < K; k++) MI_OK(mi355_diff_pairs_batch(core, d_cur, d_prev, apart ? 2 * n : n, B, d_off, d_xs, d_df, cap));
-            MI_OK(mi355_synchronize(core));
-            double ta = 0, tb = 0, tc = 0; int l = 0;
-            MI_OK(mi355_get_kernel_timing(core, &ta, &tb, &tc, &l));
-            printf("place %s %lld %lld: expand_us %.1f pack_us %.1f  xs %p df %p\n", what, a, b2, tc / l * 1e3, ta / l * 1e3, (void *)d_xs, (void *)d_df);
-            fflush(stdout);
-        };
-        const size_t xs_bytes = sizeof(int32_t) * cap, df_bytes = cap, MiB2 = (size_t)2 << 20;
-        const size_t xs_span = (xs_bytes + MiB2 - 1) / MiB2 * MiB2;
-        uint8_t *block = nullptr;
-        HIP_OK(hipMalloc((void **)&block, xs_span + df_bytes + 64 * MiB2));
-        printf("place block %p (%zu bytes): xs %zu bytes, df %zu bytes\n", (void *)block, xs_span + df_bytes + 64 * MiB2, xs_bytes, df_bytes);
-        const long long rel[] = {0, 256, 1024, 4096, 16384, 65536, 262144, 1 << 20, 2 << 20, (2 << 20) + 4096, 3 << 20, 4 << 20, 8 << 20, 16 << 20, 32 << 20};
-        const bool sweeps = !getenv("DIFFBENCH_PLACE_NO_SWEEPS");
-        for (int rep = 0; rep < 2 && sweeps; rep++)
-            for (long long r : rel) {
-                d_xs = (int32_t *)block; d_df = block + xs_span + r;
-                measure("rel", r, rep);
-            }
-        const long long dis[] = {0, 4096, 65536, 1 << 20, 2 << 20, 5 << 20, 16 << 20};
-        for (long long d : dis) {
-            if (!sweeps) break;
-            d_xs = (int32_t *)(block + d); d_df = block + xs_span + (32 << 20) + d;
-            measure("both", d, 0);
-        }
-        // separate allocations, kept allocated: the expansion on each pair, then three probes on the same memory
-        hipEvent_t pe0, pe1; HIP_OK(hipEventCreate(&pe0)); HIP_OK(hipEventCreate(&pe1));
-        uint32_t *psink; HIP_OK(hipMalloc((void **)&psink, 64));
-        auto timed_us = [&](auto fn) {
-            float best = 1e30f;
-            for (int r = 0; r < 4; r++) {
-                HIP_OK(hipEventRecord(pe0, 0)); fn(); HIP_OK(hipEventRecord(pe1, 0)); HIP_OK(hipEventSynchronize(pe1));
-                float ms = 0; HIP_OK(hipEventElapsedTime(&ms, pe0, pe1));
-                if (r > 0 && ms < best) best = ms;
-            }
-            return best * 1e3;
-        };
-        const uint32_t items = (uint32_t)((n / 1024 + 15) / 16), E = (uint32_t)(cap / ((size_t)items * B)) & ~3u;
-        auto probes = [&](const char *what, int i) {
-            MI_OK(mi355_synchronize(core));
-            const double wide_xs = timed_us([&] { hipLaunchKernelGGL(k_probe_wide, dim3(2048), dim3(256), 0, 0, (pv4 *)d_xs, xs_bytes / 16); });
-            const double wide_df = timed_us([&] { hipLaunchKernelGGL(k_probe_wide, dim3(2048), dim3(256), 0, 0, (pv4 *)d_df, df_bytes / 16); });
-            const double it = timed_us([&] { hipLaunchKernelGGL(k_probe_items, dim3(items, B), dim3(64), 0, 0, (uint32_t *)d_xs, d_df, E, items); });
-            const double itp = timed_us([&] { hipLaunchKernelGGL(k_probe_items_perm, dim3(items, B), dim3(64), 0, 0, (uint32_t *)d_xs, d_df, E, items * B, 4099u); });
-            const double only_x = timed_us([&] { hipLaunchKernelGGL(k_probe_items_one, dim3(items, B), dim3(64), 0, 0, (uint32_t *)d_xs, d_df, E, items, 0); });
-            const double only_d = timed_us([&] { hipLaunchKernelGGL(k_probe_items_one, dim3(items, B), dim3(64), 0, 0, (uint32_t *)d_xs, d_df, E, items, 1); });
-            printf("probe2 %s %d: items_perm %.1f us  items_xs_only %.1f us  items_df_only %.1f us\n", what, i, itp, only_x, only_d);
-            const double rx = timed_us([&] { hipLaunchKernelGGL(k_probe_rand, dim3(2048), dim3(256), 0, 0, (const pv4 *)d_xs, xs_bytes / 64, psink, 64); });
-            const double rd = timed_us([&] { hipLaunchKernelGGL(k_probe_rand, dim3(2048), dim3(256), 0, 0, (const pv4 *)d_df, df_bytes / 64, psink, 64); });
-            printf("probe %s %d: wide_xs %.1f us (%.0f GB/s) wide_df %.1f us (%.0f GB/s) items %.1f us (%.0f GB/s) rand_xs %.1f us rand_df %.1f us\n", what, i,
-                   wide_xs, xs_bytes / wide_xs / 1e3, wide_df, df_bytes / wide_df / 1e3, it, 5.0 * E * items * B / it / 1e3, rx, rd);
-            fflush(stdout);
-        };
-        const int burn_gb = getenv("DIFFBENCH_BURN_GB") ? atoi(getenv("DIFFBENCH_BURN_GB")) : 0;
-        for (int g2 = 0; g2 < burn_gb; g2++) { void *b4 = nullptr; HIP_OK(hipMalloc(&b4, (size_t)1 << 30)); }
-        if (burn_gb) printf("place burned %d GiB\n", burn_gb);
-        std::vector<std::pair<int32_t *, uint8_t *>> kept;
-        for (int i = 0; i < place; i++) {
-            HIP_OK(hipMalloc((void **)&d_xs, xs_bytes));
-            HIP_OK(hipMalloc((void **)&d_df, df_bytes));
-            kept.push_back({d_xs, d_df});
-            measure("hipMalloc", i, 0);
-            probes("hipMalloc", i);
-        }
-        // the same arrays again in reverse order: is the speed a property of the MEMORY (it stays with the array)?
-        for (int i = place - 1; i >= 0; i -= 3) { d_xs = kept[i].first; d_df = kept[i].second; measure("again", i, 0); }
-        // mixed: index array of the last pair (the latest draw) with the value array of the first, and the other way round
-        if (place > 1) {
-            d_xs = kept[place - 1].first; d_df = kept[0].second; measure("mixed_xs_last_df_first", 0, 0);
-            d_xs = kept[0].first; d_df = kept[place - 1].second; measure("mixed_xs_first_df_last", 0, 0);
-        }
-        // free everything and draw again: does a fresh draw get the same memory back?
-        for (auto &kv : kept) { HIP_OK(hipFree(kv.first)); HIP_OK(hipFree(kv.second)); }
-        for (int i = 0; i < 3; i++) {
-            HIP_OK(hipMalloc((void **)&d_xs, xs_bytes));
-            HIP_OK(hipMalloc((void **)&d_df, df_bytes));
-            measure("after_free", i, 0);
-        }
-        // the value array put together from separately made physical pieces (HIP virtual-memory calls), mapped one after the
-        // other or in a shuffled order: is scattered memory the fast kind?
-        auto vmm_pieces = [&](size_t bytes, size_t piece, bool shuffle) -> void * {
-            hipMemAllocationProp prop{};
-            prop.type = hipMemAllocationTypePinned;
-            prop.location.type = hipMemLocationTypeDevice;
-            int dev = 0; HIP_OK(hipGetDevice(&dev));
-            prop.location.id = dev;
-            const size_t np = (bytes + piece - 1) / piece;
-            void *va = nullptr;
-            HIP_OK(hipMemAddressReserve(&va, np * piece, (size_t)2 << 20, nullptr, 0));
-            std::vector<hipMemGenericAllocationHandle_t> hs(np);
-            for (size_t k = 0; k < np; k++) HIP_OK(hipMemCreate(&hs[k], piece, &prop, 0));
-            std::vector<size_t> order(np);
-            for (size_t k = 0; k < np; k++) order[k] = k;
-            if (shuffle) { uint32_t r = 12345u; for (size_t k = np - 1; k > 0; k--) { r = r * 1664525u + 1013904223u; std::swap(order[k], order[(r >> 8) % (k + 1)]); } }
-            for (size_t k = 0; k < np; k++) HIP_OK(hipMemMap((char *)va + k * piece, piece, 0, hs[order[k]], 0));
-            hipMemAccessDesc acc{};
-            acc.location = prop.location;
-            acc.flags = hipMemAccessFlagsProtReadWrite;
-            HIP_OK(hipMemSetAccess(va, np * piece, &acc, 1));
-            return va;
-        };
-        HIP_OK(hipMalloc((void **)&d_xs, xs_bytes));
-        const size_t pieces[] = {(size_t)2 << 20, (size_t)256 << 10, (size_t)64 << 10};
-        for (size_t pc : pieces)
-            for (int sh = 0; sh < 2; sh++)
-                for (int i = 0; i < 2; i++) {
-                    const auto t0p = std::chrono::high_resolution_clock::now();
-                    d_df = (uint8_t *)vmm_pieces(df_bytes, pc, sh != 0);
-                    const double ms_make = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0p).count() * 1e3;
-                    char name[64]; snprintf(name, sizeof name, "vmm_%zuK_%s", pc >> 10, sh ? "shuffled" : "inorder");
-                    printf("place %s made in %.1f ms\n", name, ms_make);
-                    measure(name, i, 0);
-                    probes(name, i);
-                }
-        for (int i = 0; i < 3; i++) {   // physically contiguous allocations
-            void *a = nullptr, *b3 = nullptr;
-            if (hipExtMallocWithFlags(&a, xs_bytes, hipDeviceMallocContiguous) != hipSuccess || hipExtMallocWithFlags(&b3, df_bytes, hipDeviceMallocContiguous) != hipSuccess) {
-                printf("place contiguous: refused (%s)\n", hipGetErrorString(hipGetLastError())); break;
-            }
-            d_xs = (int32_t *)a; d_df = (uint8_t *)b3;
-            measure("contiguous", i, 0);
-            probes("contiguous", i);
-        }
-    }
     mi355_destroy(core);
     return 0;
 }
