@@ -240,6 +240,14 @@ class CUDACore:
         _l.check(self._lib.mi355_diff_stream_wire_batch(self._h, _ptr(d_frames), stride, nframes,
                                                         _ptr(d_offsets), _ptr(d_wire), capacity_bytes))
 
+    def diff_stream_cwire_batch(self, d_frames, nframes, d_offsets, d_frame_pos, d_cwire, capacity_bytes, stride=None):
+        """diff_stream_batch straight into compact records (include/mi355diff.h): d_frame_pos uint64[nframes + 1] record
+        positions; a frame whose record ends past capacity_bytes is skipped whole."""
+        self._hold(d_frames, d_offsets, d_frame_pos, d_cwire)
+        stride = self.total if stride is None else stride
+        _l.check(self._lib.mi355_diff_stream_cwire_batch(self._h, _ptr(d_frames), stride, int(nframes), _ptr(d_offsets),
+                                                         _ptr(d_frame_pos), _ptr(d_cwire), int(capacity_bytes)))
+
     def wire_bytes(self, nframes, entries):
         return self._lib.mi355_wire_bytes(nframes, entries)
 

@@ -12,6 +12,7 @@
 //   groff     T*ceil(W/64)*16 (a prefix per range of 16 tiles);  totals T*8 {total, epoch} + the ticket;  offsets (T+1)*4
 //   one_xs N*4, one_diff N exec(): packed output of a single frame before the D2H copies
 //   cw_cnt    32 KiB       the compact-wire encoder's escape counts per workgroup
+//   cw_items  T*ceil(W/16)*16 + T*4  mi355_diff_stream_cwire_batch: one word per item of the expansion, escapes per frame
 //   hist T*256*4, thr T*4 (per frame of a filter batch), k9 9*4, heat LUT 766*3, glyph atlas
 #include <cmath>
 #include <cstdio>
@@ -70,6 +71,8 @@ struct mi355_core {
     int32_t *hist = nullptr, *thr = nullptr;
     uint32_t *red_bounds = nullptr; // mi355_red_stream_batch (cleared form): entry ranges of the frame slices
     uint32_t *cw_cnt = nullptr;     // mi355_cwire_encode_batch: escapes per workgroup of the emit kernel (kCwireSlots words)
+    uint4 *cw_items = nullptr;      // mi355_diff_stream_cwire_batch: [T][ceil(W/16)] item words (diff_pack.hip, k_cwire_items)
+    uint32_t *cw_esc = nullptr;     // ... and [T] escapes per frame
     uint8_t *gray1 = nullptr;      // fused gray+binarize chain: one gray byte per pixel of a batch, made on first use
     size_t gray1_stride = 0;
     float *k9 = nullptr;
@@ -329,15 +332,35 @@ int setup_pipeline(mi355_core *c) {
     return MI355_OK;
 }
 
+// Outputs of mi355_diff_stream_cwire_batch: compact records instead of (d_xs, d_diff)
+struct CwireOut {
+    uint64_t *frame_pos;
+    uint8_t *cwire;
+    uint64_t capacity;   // bytes
+};
+
 // d_wire != nullptr: the expander writes the sender's byte stream (capacity in bytes) instead of d_xs/d_diff.
+// cw != nullptr: the log is expanded into compact records (launch_expand_cwire) instead.
 // pipelined: a public batch entry point on the core's OWN stream -- the index and the expansion run on the side
 // stream beside the next batch's pack kernel (which needs only the state, carried on the core's stream, and a free
 // set of logs); completion is what mi355_synchronize / any other entry point waits for (use_device joins).  With a
 // caller's stream (mi355_set_stream) everything stays on that stream, in order: a caller who enqueues its own
 // consumers there must find the batch complete.
+CwireDirectArgs cwire_args(mi355_core *c, const CwireOut *cw, const uint32_t *d_offsets, uint32_t ntiles) {
+    CwireDirectArgs x{};
+    x.x.offsets = d_offsets;
+    x.x.ntiles = ntiles;
+    x.items = c->cw_items;
+    x.esc = c->cw_esc;
+    x.frame_pos = cw->frame_pos;
+    x.cwire = cw->cwire;
+    x.capacity = cw->capacity;
+    return x;
+}
+
 int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, size_t stride,
               int nframes, void *d_offsets, void *d_xs, void *d_diff, size_t capacity,
-              void *d_wire = nullptr, bool pipelined = false) {
+              void *d_wire = nullptr, bool pipelined = false, const CwireOut *cw = nullptr) {
     if (!c) return fail(MI355_ERR_INVALID, "null core");
     if (nframes < 0 || nframes > c->cfg.max_batch)
         return fail(MI355_ERR_INVALID, "nframes outside [0, max_batch]");
@@ -345,7 +368,7 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
     if (nframes > 0 && c->n > 0 && (!d_cur || (pair && !d_prev)))
         return fail(MI355_ERR_INVALID, "null frame pointer");
     if (nframes > 0 && stride < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
-    if (capacity > 0 && !d_wire && (!d_xs || !d_diff)) return fail(MI355_ERR_INVALID, "null output pointer");
+    if (capacity > 0 && !d_wire && !cw && (!d_xs || !d_diff)) return fail(MI355_ERR_INVALID, "null output pointer");
     pipelined = pipelined && c->stream == c->own_stream && c->pipeline_ok && nframes > 0 && c->n > 0;
     const bool own = pipelined;   // an own-stream batch (its total is recorded for the next decisions)
     if (c->filter_since_batch) pipelined = false;   // a filter / batch chain: one kernel after the other (use_device_filter)
@@ -369,6 +392,7 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
             const size_t head = 4 * (size_t)nframes < capacity ? 4 * (size_t)nframes : capacity & ~(size_t)3;
             if (head) HIP_TRY(hipMemsetAsync(d_wire, 0, head, c->stream));
         }
+        if (cw) HIP_TRY(launch_expand_cwire(cwire_args(c, cw, (const uint32_t *)d_offsets, 0u), nframes, c->stream));
         return MI355_OK;
     }
     hipEvent_t *tev = nullptr;
@@ -483,7 +507,13 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
     g.out_diff = (uint8_t *)d_diff;
     g.wire = (uint8_t *)d_wire;
     g.capacity = capacity;
-    HIP_TRY(launch_expand(g, nframes, tail));
+    if (cw) {   // the same log into compact records (the kernels read only its fields and the offsets)
+        CwireDirectArgs x = cwire_args(c, cw, g.offsets, c->ntiles);
+        x.x = g;
+        HIP_TRY(launch_expand_cwire(x, nframes, tail));
+    } else {
+        HIP_TRY(launch_expand(g, nframes, tail));
+    }
     if (tev) {
         HIP_TRY(hipEventRecord(tev[4], tail));
         c->ev_count += 1;
@@ -565,6 +595,8 @@ int mi355_create(const mi355_config *cfg, mi355_core **out) {
     if (!rc) { e = hipMemsetAsync(c->totals, 0, (2 * T + 2) * sizeof(uint32_t), c->own_stream); if (e != hipSuccess) rc = fail(MI355_ERR_HIP, "hipMemset", e); }
     if (!rc) rc = dev_alloc(c, &c->offsets, T + 1);
     if (!rc) rc = dev_alloc(c, &c->cw_cnt, (size_t)kCwireSlots);
+    if (!rc) rc = dev_alloc(c, &c->cw_items, T * cwire_items_per_frame(c->ntiles));
+    if (!rc) rc = dev_alloc(c, &c->cw_esc, T);
     if (!rc) rc = dev_alloc(c, &c->one_xs, N + 4);
     if (!rc) rc = dev_alloc(c, &c->one_diff, N + 16);
     if (!rc) rc = dev_alloc(c, &c->hist, 256 * T);
@@ -610,7 +642,7 @@ void mi355_destroy(mi355_core *c) {
         if (c->h_tot) (void)hipHostFree(c->h_tot);
     }
     void *ptrs[] = {c->state, c->in, c->aux, c->vis, c->rec, c->codes, c->meta, c->groff, c->totals, c->offsets, c->one_xs, c->one_diff, c->hist, c->thr, c->k9,
-                    c->lut, c->glyphs, c->kxk, c->gray1, c->red_bounds, c->cw_cnt};
+                    c->lut, c->glyphs, c->kxk, c->gray1, c->red_bounds, c->cw_cnt, c->cw_items, c->cw_esc};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->h_count) (void)hipHostFree(c->h_count);
     for (auto &slot : c->ev) for (auto &ev : slot) if (ev) (void)hipEventDestroy(ev);
@@ -774,6 +806,18 @@ int mi355_diff_stream_wire_batch(mi355_core *c, const void *d_frames, size_t str
     if (!d_wire) return fail(MI355_ERR_INVALID, "null d_wire");
     return run_batch(c, false, d_frames, nullptr, stride_bytes, nframes, d_offsets, nullptr, nullptr,
                      capacity_bytes, d_wire, true);
+}
+
+int mi355_diff_stream_cwire_batch(mi355_core *c, const void *d_frames, size_t stride_bytes, int nframes,
+                                  void *d_offsets, void *d_frame_pos, void *d_cwire, size_t capacity_bytes) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nframes < 0 || nframes > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nframes outside [0, max_batch]");
+    if (!d_offsets || !d_frame_pos) return fail(MI355_ERR_INVALID, "null d_offsets / d_frame_pos");
+    if (capacity_bytes > 0 && !d_cwire) return fail(MI355_ERR_INVALID, "null d_cwire");
+    if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_frame_pos & 7u))
+        return fail(MI355_ERR_INVALID, "d_cwire and d_offsets must be 4-byte aligned, d_frame_pos 8-byte aligned");
+    const CwireOut cw{(uint64_t *)d_frame_pos, (uint8_t *)d_cwire, (uint64_t)capacity_bytes};
+    return run_batch(c, false, d_frames, nullptr, stride_bytes, nframes, d_offsets, nullptr, nullptr, 0, nullptr, true, &cw);
 }
 
 size_t mi355_wire_bytes(int nframes, uint64_t entries) { return 4 * (size_t)nframes + 5 * (size_t)entries; }

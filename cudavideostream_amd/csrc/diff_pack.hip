@@ -943,4 +943,306 @@ hipError_t launch_expand(const ExpandArgs &a, int nframes, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ---- compact-wire expansion: codes + records -> compact records (include/mi355diff.h, "compact wire format") -----------
+// mi355_diff_stream_cwire_batch reads the same log as k_expand and writes what mi355_cwire_encode_batch would write from
+// k_expand's (offsets, xs, diff), without the 5-bytes-per-entry arrays in between.  Four launches behind k_scan_groups:
+//   k_cwire_items  (grid as k_expand): per item (frame, 16 tiles) its first and last changed byte, its entries and the
+//                  escaped gaps between its own entries -- from the codes alone.  The entries of one pack lane lie within
+//                  16 bytes (never an escape between them): only the gap from one candidate lane's last byte to the next
+//                  one's first can reach 255.  A dense tile (64 multi-byte lanes, records only) has gaps below 32; its first
+//                  and last bytes come from the maps of its records 0 and 63.
+//   k_cwire_fscan  (grid T): per frame, the gaps between consecutive non-empty items (and from -1 to the first entry), each
+//                  item's escape rank and the frame's escapes e_t.  No workgroup looks at another's result.
+//   k_cwire_place  (one workgroup): frame_pos = exclusive scan of 8 + 2 pad4(n_t) + 4 e_t; the header {n, e} and the zero
+//                  pad bytes of every frame that fits.
+//   k_expand_cwire (grid as k_expand): the item's entries through the LDS stage as on the tile path of expand_tiles, then
+//                  its codes, escapes and differences at their places in the record (byte-aligned, non-temporal stores).
+// Item word (k_cwire_items -> k_cwire_fscan): {first byte, last byte, escapes inside the item, entries}; k_cwire_fscan
+// rewrites it for the expansion as {first byte, 1 + the frame's entry before the item (0: none), escapes of the frame before
+// the item's first entry, entries}.
+__host__ __device__ uint32_t cwire_items_per_frame(uint32_t ntiles) { return (ntiles + kWTiles - 1) / kWTiles; }
+
+__global__ __launch_bounds__(64) void k_cwire_items(const CwireDirectArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t t = blockIdx.y, sub = blockIdx.x, ntiles = a.x.ntiles;
+    if (sub * kWTiles >= ntiles) return;   // the grid is padded (as k_expand's)
+    const __amdgpu_buffer_rsrc_t metas = make_rsrc(a.x.meta + (size_t)t * ntiles, ntiles * 16u);
+    const u32x4 m = __builtin_amdgcn_raw_buffer_load_b128(metas, lane < kWTiles ? (sub * kWTiles + lane) * 16u : kOOB, 0, 0);
+    const __amdgpu_buffer_rsrc_t codes = make_rsrc(a.x.codes, a.x.codes_bytes), recs = make_rsrc(a.x.rec, a.x.rec_bytes);
+    // code `lane` of every tile of the item, all requested at once (a dense tile, and lanes past a tile's candidates, read 0)
+    uint32_t code[kWTiles];
+#pragma unroll
+    for (uint32_t i = 0; i < kWTiles; i++) {
+        const uint32_t cx = (uint32_t)__builtin_amdgcn_readlane((int)m.x, i), cw = (uint32_t)__builtin_amdgcn_readlane((int)m.w, i);
+        const bool load = (cw >> 16) != 64u && lane < (cw & 0xffffu);
+        code[i] = __builtin_amdgcn_raw_buffer_load_b32(codes, load ? cx + 4u * lane : kOOB, 0, 0);
+    }
+    uint32_t first = 0, end = 0, esc = 0, nent = 0;   // wave-uniform; end = 1 + the last changed byte so far (0: none yet)
+#pragma unroll
+    for (uint32_t i = 0; i < kWTiles; i++) {
+        const uint32_t cw = (uint32_t)__builtin_amdgcn_readlane((int)m.w, i), nc = cw & 0xffffu;
+        if (nc == 0u) continue;   // wave-uniform
+        nent += (uint32_t)__builtin_amdgcn_readlane((int)m.z, i);
+        const uint32_t base = (sub * kWTiles + i) * kTileBytes;   // the tile's first byte in the frame
+        uint32_t f, l;                                          // its first and last changed byte (wave-uniform)
+        if ((cw >> 16) == 64u) {
+            const uint32_t cy = (uint32_t)__builtin_amdgcn_readlane((int)m.y, i);
+            const u32x4 r = __builtin_amdgcn_raw_buffer_load_b128(recs, lane == 0u ? cy : (lane == 1u ? cy + 63u * 16u : kOOB), 0, 0);
+            const uint32_t map = record_map16(make_uint4(r.x, r.y, r.z, r.w));
+            f = base + (uint32_t)__builtin_ctz((uint32_t)__builtin_amdgcn_readlane((int)map, 0));
+            l = base + 63u * 16u + 31u - (uint32_t)__builtin_clz((uint32_t)__builtin_amdgcn_readlane((int)map, 1));
+            if (end != 0u && f - end >= 255u) esc++;
+        } else {
+            const uint32_t c = code[i], m16 = c & 0xffffu, at = base + ((c >> 20) & 0x3f0u);
+            const bool live = lane < nc;
+            const uint32_t fl = at + (uint32_t)__builtin_ctz(m16 | 0x10000u), ll = at + 31u - (uint32_t)__builtin_clz(m16 | 1u);
+            // 1 + the last byte of the candidate before: lane - 1's, or the item's so far for lane 0
+            const uint32_t up = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane - 1u) & 63u) << 2, (int)(ll + 1u));
+            const uint32_t pe = lane == 0u ? end : up;
+            esc += (uint32_t)__popcll(__ballot(live && pe != 0u && fl - pe >= 255u));
+            f = (uint32_t)__builtin_amdgcn_readlane((int)fl, 0);
+            l = (uint32_t)__builtin_amdgcn_readlane((int)ll, nc - 1u);
+        }
+        if (end == 0u) first = f;
+        end = l + 1u;
+    }
+    if (lane == 0u) a.items[(size_t)t * cwire_items_per_frame(ntiles) + sub] = make_uint4(first, end - 1u, esc, nent);
+}
+
+__global__ __launch_bounds__(256) void k_cwire_fscan(const CwireDirectArgs a) {
+    __shared__ uint32_t s_end[4], s_esc[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, t = blockIdx.x;
+    const uint32_t gx = cwire_items_per_frame(a.x.ntiles);
+    uint4 *it = a.items + (size_t)t * gx;
+    uint32_t carry_end = 0, carry_esc = 0;   // 1 + the frame's last entry before this round's items / escapes before them
+    for (uint32_t b0 = 0; b0 < gx; b0 += 256u) {
+        const uint32_t j = b0 + threadIdx.x;
+        const uint4 v = j < gx ? it[j] : make_uint4(0, 0, 0, 0);
+        const bool live = v.w != 0u;
+        // entries ascend over the items: the running maximum of (1 + last byte) is 1 + the last entry before an item
+        const uint32_t end = live ? v.y + 1u : 0u;
+        const uint32_t mx = wave_inclusive_max_scan(end);
+        const uint32_t mx_up = (uint32_t)__shfl_up((int)mx, 1, 64);
+        if (lane == 63u) s_end[wave] = mx;
+        __syncthreads();
+        uint32_t pe = carry_end;
+        for (uint32_t w = 0; w < wave; w++) pe = max(pe, s_end[w]);
+        if (lane != 0u) pe = max(pe, mx_up);
+        const uint32_t mine = live ? v.z + (v.x - pe >= 255u ? 1u : 0u) : 0u;   // g of the item's first entry = first - pe
+        const uint32_t incl = (uint32_t)wave_inclusive_scan((int)mine);
+        if (lane == 63u) s_esc[wave] = incl;
+        __syncthreads();
+        uint32_t rank = carry_esc + incl - mine;
+        for (uint32_t w = 0; w < wave; w++) rank += s_esc[w];
+        if (live) it[j] = make_uint4(v.x, pe, rank, v.w);
+        carry_end = max(max(carry_end, max(s_end[0], s_end[1])), max(s_end[2], s_end[3]));
+        carry_esc += s_esc[0] + s_esc[1] + s_esc[2] + s_esc[3];
+        __syncthreads();   // s_end / s_esc are rewritten by the next round
+    }
+    if (threadIdx.x == 0) a.esc[t] = carry_esc;
+}
+
+constexpr int kCwPlaceThreads = 1024;
+
+__device__ __forceinline__ void store_byte_nt(uint8_t *p, uint32_t v) { __builtin_nontemporal_store((uint8_t)v, p); }
+
+// esc == nullptr: every frame is empty (e = 0)
+__global__ __launch_bounds__(kCwPlaceThreads) void k_cwire_place(const uint32_t *offsets, const uint32_t *esc, int nframes,
+                                                                 uint64_t *frame_pos, uint8_t *out, uint64_t capacity) {
+    __shared__ uint64_t s_wave[kCwPlaceThreads / 64];
+    __shared__ uint64_t s_carry;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) s_carry = 0;
+    __syncthreads();
+    for (int t0 = 0; t0 < nframes; t0 += kCwPlaceThreads) {
+        const int t = t0 + tid;
+        uint64_t rec = 0, n = 0, e = 0;
+        if (t < nframes) {
+            n = offsets[t + 1] - offsets[t];
+            e = esc ? esc[t] : 0u;
+            rec = 8 + 2 * ((n + 3) & ~3ull) + 4 * e;
+        }
+        uint64_t incl = rec;   // inclusive scan of the record sizes over the wave, then over the waves
+#pragma unroll
+        for (int k = 1; k < 64; k <<= 1) {
+            const uint64_t v = __shfl_up(incl, k, 64);
+            if (lane >= k) incl += v;
+        }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        uint64_t before = s_carry;
+        for (int w = 0; w < wave; w++) before += s_wave[w];
+        const uint64_t pos = before + incl - rec;
+        if (t < nframes) {
+            frame_pos[t] = pos;
+            if (pos + rec <= capacity) {   // the frame fits: its header and pad bytes (k_expand_cwire writes the rest)
+                uint32_t *hdr = (uint32_t *)(out + pos);
+                __builtin_nontemporal_store((uint32_t)n, hdr);
+                __builtin_nontemporal_store((uint32_t)e, hdr + 1);
+                const uint64_t D = (n + 3) & ~3ull;
+                for (uint64_t k = n; k < D; k++) {
+                    store_byte_nt(out + pos + 8 + k, 0u);
+                    store_byte_nt(out + pos + 8 + D + 4 * e + k, 0u);
+                }
+            }
+        }
+        __syncthreads();
+        if (tid == kCwPlaceThreads - 1) s_carry = before + incl;
+        __syncthreads();
+    }
+    if (tid == 0) frame_pos[nframes] = s_carry;
+}
+
+// Where the entries of an item go in its frame's record (wave-uniform)
+struct CwireCursor {
+    uint8_t *code, *diff;   // the frame's code and difference sections
+    uint32_t *esc;          // its escapes
+    uint32_t n, e;          // its header
+    uint32_t entry;         // rank in the frame of the next entry to store
+    uint32_t end;           // 1 + the index of the entry before it (0: none), so that its gap is index - end
+    uint32_t erank;         // escapes of the frame before it
+};
+
+// Entries stage[0 .. count) (k_expand's stage format, indices relative to xs0) leave four to a lane: one unaligned dword of
+// codes and one of differences (bytes where the four do not all exist), escapes ranked by ballot as in k_cwire_emit.
+__device__ __forceinline__ void flush_cwire(const uint32_t *stage, uint32_t count, uint32_t xs0, CwireCursor &cur) {
+    if (count == 0u) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t lt = (1ull << lane) - 1ull;
+    for (uint32_t b0 = 0; b0 < count; b0 += 256u) {
+        const uint32_t i0 = b0 + 4u * lane;
+        const uint4 q = *reinterpret_cast<const uint4 *>(stage + (i0 < kWStage ? i0 : 0u));
+        const uint32_t v[4] = {q.x, q.y, q.z, q.w};
+        uint32_t pe = i0 == 0u ? cur.end : xs0 + (stage[(i0 - 1u) & (kWStage - 1u)] >> 8) + 1u;
+        uint32_t word = 0, dw = 0, g[4];
+        bool ok[4], fl[4];
+        uint32_t before = 0, wtot = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            ok[j] = i0 + j < count && cur.entry + i0 + j < cur.n;
+            const uint32_t x = xs0 + (v[j] >> 8);
+            g[j] = x - pe;
+            pe = x + 1u;
+            fl[j] = ok[j] && g[j] >= 255u;
+            word |= (fl[j] ? 255u : (g[j] & 255u)) << (8 * j);
+            dw |= (v[j] & 255u) << (8 * j);
+            const uint64_t mk = __ballot(fl[j]);
+            before += (uint32_t)__popcll(mk & lt);
+            wtot += (uint32_t)__popcll(mk);
+        }
+        const uint32_t r = cur.entry + i0;
+        if (ok[3]) {
+            store_out1(cur.code + r, word);
+            store_out1(cur.diff + r, dw);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 3; j++)
+                if (ok[j]) {
+                    store_byte_nt(cur.code + r + j, word >> (8 * j));
+                    store_byte_nt(cur.diff + r + j, dw >> (8 * j));
+                }
+        }
+        uint32_t rank = cur.erank + before;
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            if (fl[j]) {
+                if (rank < cur.e) __builtin_nontemporal_store(g[j], cur.esc + rank);
+                rank++;
+            }
+        cur.erank += wtot;
+    }
+    cur.entry += count;
+    cur.end = xs0 + (stage[count - 1u] >> 8) + 1u;
+}
+
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_expand_cwire(const CwireDirectArgs a) {
+    __shared__ __attribute__((aligned(16))) uint4 s_tinfo[kWTiles];
+    __shared__ __attribute__((aligned(16))) uint32_t s_stage[kWStage];
+    __builtin_amdgcn_s_setprio(2);   // as k_expand: beside the next batch's pack waves
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t t = blockIdx.y, sub = blockIdx.x, ntiles = a.x.ntiles;
+    if (sub * kWTiles >= ntiles) return;
+    const uint64_t p0 = a.frame_pos[t], p1 = a.frame_pos[t + 1];
+    if (p1 > a.capacity) return;   // the frame does not fit: skipped whole
+    const uint4 item = a.items[(size_t)t * cwire_items_per_frame(ntiles) + sub];
+    if (item.w == 0u) return;
+    const __amdgpu_buffer_rsrc_t metas = make_rsrc(a.x.meta + (size_t)t * ntiles, ntiles * 16u);
+    const u32x4 mq = __builtin_amdgcn_raw_buffer_load_b128(metas, lane < kWTiles ? (sub * kWTiles + lane) * 16u : kOOB, 0, 0);
+    const uint32_t ngroups = (ntiles + kXTiles - 1) / kXTiles;
+    const uint32_t off_t = a.x.offsets[t], n = a.x.offsets[t + 1] - off_t;
+    const uint64_t D = (n + 3u) & ~3u;
+    CwireCursor cur;
+    cur.n = n;
+    cur.e = (uint32_t)((p1 - p0 - 8 - 2 * D) / 4);
+    cur.code = a.cwire + p0 + 8;
+    cur.esc = (uint32_t *)(cur.code + D);
+    cur.diff = cur.code + D + 4 * (uint64_t)cur.e;
+    cur.entry = a.x.roff[(size_t)t * ngroups * 4u + sub];   // entries of the frame before the item
+    cur.end = item.y;
+    cur.erank = item.z;
+    if (lane < kWTiles) s_tinfo[lane] = make_uint4(mq.x, mq.y, mq.z, mq.w);
+    lds_handoff();
+    const uint32_t xs0 = sub * kWTiles * kTileBytes;
+    // the tile path of expand_tiles (a full tile, too, goes through the stage: every gap but its first is 0)
+    const __amdgpu_buffer_rsrc_t codes = make_rsrc(a.x.codes, a.x.codes_bytes), recs = make_rsrc(a.x.rec, a.x.rec_bytes);
+    auto load_code = [&](uint32_t i) {
+        const uint4 ti = s_tinfo[i & (kWTiles - 1u)];
+        const bool dense = (ti.w >> 16) == 64u;
+        return __builtin_amdgcn_raw_buffer_load_b32(codes, (i < kWTiles && !dense && lane < (ti.w & 0xffffu)) ? ti.x + 4u * lane : kOOB, 0, 0);
+    };
+    auto load_rec = [&](uint32_t i, uint32_t c) {
+        const uint4 ti = s_tinfo[i & (kWTiles - 1u)];
+        const uint32_t m16 = c & 0xffffu;
+        const bool dense = (ti.w >> 16) == 64u;
+        const uint32_t off = dense ? ti.y + 16u * lane : ((m16 & (m16 - 1u)) ? ti.y + 16u * ((c >> 16) & 0xffu) : kOOB);
+        return __builtin_amdgcn_raw_buffer_load_b128(recs, i < kWTiles ? off : kOOB, 0, 0);
+    };
+    uint32_t carry = 0, flushed = 0;   // entries of the item expanded so far / already stored (wave-uniform)
+    uint32_t c0 = load_code(0), c1 = load_code(1);
+    u32x4 r0 = load_rec(0, c0);
+#pragma unroll 1
+    for (uint32_t i = 0; i < kWTiles; i++) {
+        const uint32_t c2 = load_code(i + 2u);
+        const u32x4 r1 = load_rec(i + 1u, c1);
+        const uint4 ti = s_tinfo[i];
+        const uint32_t ncm = (uint32_t)__builtin_amdgcn_readfirstlane((int)ti.w), bytes = (uint32_t)__builtin_amdgcn_readfirstlane((int)ti.z);
+        const uint32_t nc = ncm & 0xffffu;
+        const bool dense = (ncm >> 16) == 64u;
+        if (nc != 0u) {
+            if (carry - flushed + bytes > kWStage) {
+                lds_handoff();
+                flush_cwire(s_stage, carry - flushed, xs0, cur);
+                lds_handoff();   // the stage is rewritten from its start
+                flushed = carry;
+            }
+            const uint4 r = make_uint4(r0.x, r0.y, r0.z, r0.w);
+            const uint32_t m16 = dense ? record_map16(r) : (c0 & 0xffffu);
+            const uint32_t cnt = (uint32_t)__builtin_popcount(m16);
+            const uint32_t e = carry - flushed + (uint32_t)wave_inclusive_scan((int)cnt) - cnt;
+            const uint32_t src16 = (i << 10) + (dense ? lane * 16u : ((c0 >> 20) & 0x3f0u));
+            if (cnt == 1u) s_stage[e] = ((src16 + (uint32_t)__builtin_ctz(m16)) << 8) | ((c0 >> 16) & 0xffu);
+            const bool multi = cnt > 1u;
+            if (__ballot(multi)) walk_records(multi ? m16 : 0u, e, src16, r, s_stage, lane);
+            carry += bytes;
+        }
+        c0 = c1; c1 = c2; r0 = r1;
+    }
+    lds_handoff();
+    flush_cwire(s_stage, carry - flushed, xs0, cur);
+}
+
+hipError_t launch_expand_cwire(const CwireDirectArgs &a, int nframes, hipStream_t s) {
+    const bool work = nframes > 0 && a.x.ntiles > 0;
+    const uint32_t gx = cwire_items_per_frame(a.x.ntiles);
+    const dim3 grid((gx + 7u) / 8u * 8u, nframes > 0 ? nframes : 1);   // padded as k_expand's (launch_expand)
+    if (work) {
+        hipLaunchKernelGGL(k_cwire_items, grid, dim3(64), 0, s, a);
+        hipLaunchKernelGGL(k_cwire_fscan, dim3(nframes), dim3(256), 0, s, a);
+    }
+    hipLaunchKernelGGL(k_cwire_place, dim3(1), dim3(kCwPlaceThreads), 0, s, a.x.offsets, work ? a.esc : nullptr, nframes,
+                       a.frame_pos, a.cwire, a.capacity);
+    if (work) hipLaunchKernelGGL(k_expand_cwire, grid, dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
 }  // namespace mi355

@@ -76,6 +76,18 @@ hipError_t launch_scan(const uint4 *meta, uint32_t *roff, uint64_t *totals /* [T
                        uint64_t epoch /* 1 .. kEpochWrap - 1, different from every tag `totals` still holds */,
                        uint64_t *note /* pinned host word for {batch total, frames << 32}, or nullptr */, hipStream_t s);
 hipError_t launch_expand(const ExpandArgs &a, int nframes, hipStream_t s);
+// The log straight into compact records (mi355_diff_stream_cwire_batch; diff_pack.hip, "compact-wire expansion").
+__host__ __device__ uint32_t cwire_items_per_frame(uint32_t ntiles);   // = items of k_expand: ceil(W / 16)
+struct CwireDirectArgs {
+    ExpandArgs x;             // the log and the batch's offsets (out_xs / out_diff / wire / capacity unused)
+    uint4 *items;             // [T][cwire_items_per_frame(W)] scratch of the core
+    uint32_t *esc;            // [T] escapes per frame, scratch of the core
+    uint64_t *frame_pos;      // [T+1] the caller's
+    uint8_t *cwire;           // the caller's records
+    uint64_t capacity;        // bytes of cwire
+};
+// nframes == 0 or ntiles == 0 (offsets already zero): only frame_pos and the empty records' headers are written
+hipError_t launch_expand_cwire(const CwireDirectArgs &a, int nframes, hipStream_t s);
 
 // stream_ops.hip
 constexpr int kMaxParts = 64;

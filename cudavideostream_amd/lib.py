@@ -64,6 +64,8 @@ SYMBOLS = {
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "mi355_diff_stream_wire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
                                                C.c_void_p, C.c_size_t]),
+    "mi355_diff_stream_cwire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_size_t]),
     "mi355_wire_bytes": (C.c_size_t, [C.c_int, C.c_uint64]),
     "mi355_apply_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                     C.c_size_t]),
@@ -134,7 +136,7 @@ SYMBOLS = {
     "mi355_group_synchronize": (C.c_int, [C.c_void_p]),
 }
 GROUP_ID_BYTES = 128   # MI355_GROUP_ID_BYTES
-ABI_VERSION = 8        # MI355_ABI_VERSION of the include/mi355diff.h these argument lists were written against
+ABI_VERSION = 9        # MI355_ABI_VERSION of the include/mi355diff.h these argument lists were written against
 
 _lib = None
 

@@ -79,8 +79,9 @@ typedef struct mi355_config {
  *      mi355_cwire_decode_batch, mi355_cwire_apply_host (additions only)
  *   8  the schedule options 2..5 (split share, dense threshold, filter/batch chain hint, pack grid) are gone: their ids
  *      are refused (MI355_ERR_INVALID) and will not be reused; their defaults are the library's fixed schedule, unchanged
- *      (mi355_diff_stream_batch) */
-#define MI355_ABI_VERSION 8
+ *      (mi355_diff_stream_batch)
+ *   9  + mi355_diff_stream_cwire_batch (additions only) */
+#define MI355_ABI_VERSION 9
 int mi355_abi_version(void);
 
 /* ---- life cycle: CUDACore::CUDACore (kernels.cu:377-428) without the uploads ------------------ */
@@ -223,6 +224,19 @@ int mi355_diff_pairs_batch(mi355_core *core, const void *d_cur, const void *d_pr
 int mi355_diff_stream_wire_batch(mi355_core *core, const void *d_frames, size_t stride_bytes, int nframes,
                                  void *d_offsets, void *d_wire, size_t capacity_bytes);
 size_t mi355_wire_bytes(int nframes, uint64_t entries);
+/* Compact form of the same batch (the record layout is under "compact wire format" below): the batch leaves as the records
+ * mi355_cwire_encode_batch would write from mi355_diff_stream_batch's (d_offsets, d_xs, d_diff), byte for byte, without those
+ * arrays.  Threshold, negative feedback and the state are those of mi355_diff_stream_batch on the same frames, and d_offsets
+ * (uint32[nframes + 1]) is the same.  Frame t's record is at byte d_frame_pos[t] (uint64[nframes + 1], exclusive scan of the
+ * record sizes, always exact); it is written only if d_frame_pos[t + 1] <= capacity_bytes, a frame that does not fit is
+ * skipped whole, header included.  mi355_cwire_bytes_max(N, nframes) always suffices.  nframes <= max_batch; d_cwire and
+ * d_offsets 4-byte aligned, d_frame_pos 8-byte aligned; anything else is refused (MI355_ERR_INVALID) before anything is
+ * written.  Ordering and pipelining are those of mi355_diff_stream_batch: outputs complete after mi355_synchronize and for
+ * every later consumer on this core.  The expansion runs four kernels on the batch's log (the stores are non-temporal); it
+ * adds max_batch * (16 * ceil(N / 16384) + 4) bytes of workspace, allocated with the core (about 1.6 MB at 1080p with
+ * max_batch 256). */
+int mi355_diff_stream_cwire_batch(mi355_core *core, const void *d_frames, size_t stride_bytes, int nframes,
+                                  void *d_offsets, void *d_frame_pos, void *d_cwire, size_t capacity_bytes);
 
 /* The client's side, client/opencv.cpp:50-66: for every frame in order, state[xs[i]] += diff[i] (uint8
  * wrap-around) on the core's state (a client core is a core whose state was set to the received base frame,

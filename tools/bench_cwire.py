@@ -3,7 +3,8 @@
 batches of S1 webcam frames resident in HBM: 1080p with B = 256 and 4K with B = 64.
 
 Prints one JSON line per size: microseconds per frame of diff_stream_batch alone, of the encoder alone, of the two
-back to back, and of the decoder; compact and reference-wire bytes per frame; and the encoder's achieved GB/s on its
+back to back, of diff_stream_cwire_batch (`direct`: the same records in one call, without the xs / diff arrays) and of
+the decoder; compact and reference-wire bytes per frame; and the encoder's achieved GB/s on its
 algorithmic bytes (per frame: read 4P + 5P, write 8 + 2 pad4(P) + 4e, P = changed bytes).  Not the headline metric
 (bench.py)."""
 import argparse
@@ -61,6 +62,13 @@ def run(W, H, B, reps):
             diff()
             encode()
 
+        q_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+        q_pos = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+        q_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
+
+        def direct():
+            core.diff_stream_cwire_batch(frames, B, q_off, q_pos, q_cw, cwcap)
+
         # the same batch over and over (the state carries over: its first frame is then diffed against its last one)
         us_diff = timed(diff, reps)
         core.set_state(base_h)
@@ -68,10 +76,16 @@ def run(W, H, B, reps):
         torch.cuda.synchronize()
         us_enc = timed(encode, reps)
         us_both = timed(both, reps)
+        us_direct = timed(direct, reps)
         core.set_state(base_h)
         diff()
         encode()
         torch.cuda.synchronize()
+        core.set_state(base_h)
+        direct()
+        torch.cuda.synchronize()
+        assert torch.equal(q_off, d_off) and torch.equal(q_pos, d_pos)   # the one-call form writes the same records
+        assert torch.equal(q_cw[:int(q_pos[-1])], d_cw[:int(d_pos[-1])])
         off = d_off.cpu().numpy().view(np.uint32).astype(np.int64)
         pos = d_pos.cpu().numpy().view(np.uint64).astype(np.int64)
         assert int(off[-1]) <= cap and int(pos[-1]) <= cwcap
@@ -99,6 +113,9 @@ def run(W, H, B, reps):
                           "diff_stream_us_per_frame": round(us_diff / B, 3),
                           "encode_us_per_frame": round(us_enc / B, 3),
                           "diff_plus_encode_us_per_frame": round(us_both / B, 3),
+                          "direct_us_per_frame": round(us_direct / B, 3),
+                          "direct_over_diff": round(us_direct / us_diff, 3),
+                          "direct_over_diff_plus_encode": round(us_direct / us_both, 3),
                           "encode_share_of_diff": round(us_enc / us_diff, 3),
                           "decode_us_per_frame": round(us_dec / B, 3),
                           "encode_algorithmic_bytes_per_frame": int(alg),

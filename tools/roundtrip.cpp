@@ -12,8 +12,9 @@
 // GPU (mi355_diff_stream_batch, mi355_cwire_encode_batch), the records cross the same pipe, and the client -- with no
 // core and no GPU -- rebuilds every frame on the host with mi355_cwire_apply_host; each rebuilt frame is checked against
 // the frame that was sent, and the client's frame against the server's state after every batch.
+// --compact --direct: the server makes the records in one call (mi355_diff_stream_cwire_batch), without the xs / diff arrays.
 //
-//   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B] [--compact]   exit status 0 = all checks passed
+//   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B] [--compact [--direct]]   exit status 0 = all checks passed
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -69,12 +70,15 @@ static bool through_pipe(int wfd, int rfd, const uint8_t *src, uint8_t *dst, siz
 
 int main(int argc, char **argv) {
     int w = 320, h = 180, T = 24, B = 8;
-    bool compact = false;
-    for (int i = 1; i < argc; i++)
+    bool compact = false, direct = false;
+    for (int i = 1; i < argc; i++) {
         if (std::string(argv[i]) == "--compact") compact = true;
+        if (std::string(argv[i]) == "--direct") direct = true;
+    }
+    if (direct && !compact) { fprintf(stderr, "--direct needs --compact\n"); return 2; }
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string k = argv[i];
-        if (k == "--compact") { i--; continue; }
+        if (k == "--compact" || k == "--direct") { i--; continue; }
         const int v = atoi(argv[i + 1]);
         if (k == "--width") w = v; else if (k == "--height") h = v;
         else if (k == "--frames") T = v; else if (k == "--batch") B = v;
@@ -113,8 +117,10 @@ int main(int argc, char **argv) {
         // ---- sender: pack + encode on the GPU; client: the host decoder on a host frame (no core)
         void *d_xs = nullptr, *d_df = nullptr, *d_pos = nullptr, *d_cw = nullptr;
         const size_t cap = (size_t)B * n, cw_cap = mi355_cwire_bytes_max(n, B);
-        OK(mi355_dev_alloc(server, &d_xs, cap * 4));
-        OK(mi355_dev_alloc(server, &d_df, cap));
+        if (!direct) {   // (the one-call form needs no arrays of 5 bytes per entry)
+            OK(mi355_dev_alloc(server, &d_xs, cap * 4));
+            OK(mi355_dev_alloc(server, &d_df, cap));
+        }
         OK(mi355_dev_alloc(server, &d_pos, sizeof(uint64_t) * (B + 1)));
         OK(mi355_dev_alloc(server, &d_cw, cw_cap));
         std::vector<uint8_t> cw_host(cw_cap), rx(cw_cap), c_frame(got_base);
@@ -127,8 +133,12 @@ int main(int argc, char **argv) {
             std::vector<uint32_t> off(nb + 1);
             std::vector<uint64_t> pos(nb + 1);
             OK(mi355_upload(server, d_frames, frames.data(), (size_t)nb * n));
-            OK(mi355_diff_stream_batch(server, d_frames, n, nb, d_off, d_xs, d_df, cap));
-            OK(mi355_cwire_encode_batch(server, d_off, d_xs, d_df, cap, nb, d_pos, d_cw, cw_cap));
+            if (direct) {
+                OK(mi355_diff_stream_cwire_batch(server, d_frames, n, nb, d_off, d_pos, d_cw, cw_cap));
+            } else {
+                OK(mi355_diff_stream_batch(server, d_frames, n, nb, d_off, d_xs, d_df, cap));
+                OK(mi355_cwire_encode_batch(server, d_off, d_xs, d_df, cap, nb, d_pos, d_cw, cw_cap));
+            }
             OK(mi355_download(server, off.data(), d_off, sizeof(uint32_t) * (nb + 1)));
             OK(mi355_download(server, pos.data(), d_pos, sizeof(uint64_t) * (nb + 1)));
             if (pos[nb] > cw_cap) { fprintf(stderr, "compact stream larger than its bound\n"); return 1; }
@@ -152,8 +162,10 @@ int main(int argc, char **argv) {
             if (memcmp(s_state.data(), c_frame.data(), n) != 0) { fprintf(stderr, "client frame != server state\n"); return 1; }
         }
         if (max_err > cfg.threshold) { fprintf(stderr, "rebuilt frame off by %d > threshold\n", max_err); return 1; }
-        OK(mi355_dev_free(server, d_xs));
-        OK(mi355_dev_free(server, d_df));
+        if (!direct) {
+            OK(mi355_dev_free(server, d_xs));
+            OK(mi355_dev_free(server, d_df));
+        }
         OK(mi355_dev_free(server, d_pos));
         OK(mi355_dev_free(server, d_cw));
         OK(mi355_dev_free(server, d_frames));
@@ -163,10 +175,10 @@ int main(int argc, char **argv) {
         OK(mi355_dev_free(client, d_shown));
         mi355_destroy(server);
         mi355_destroy(client);
-        printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"width\": %d, \"height\": %d, \"frames\": %d, \"batch\": %d, "
+        printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"direct\": %s, \"width\": %d, \"height\": %d, \"frames\": %d, \"batch\": %d, "
                "\"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, "
                "\"max_abs_error\": %d}\n",
-               w, h, T, B, changed, sent_bytes, mi355_wire_bytes(T, changed), (size_t)T * n, max_err);
+               direct ? "true" : "false", w, h, T, B, changed, sent_bytes, mi355_wire_bytes(T, changed), (size_t)T * n, max_err);
         return 0;
     }
     for (int t0 = 0; t0 < T; t0 += B) {
