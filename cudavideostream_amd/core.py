@@ -295,6 +295,17 @@ class CUDACore:
         _l.check(self._lib.mi355_cwire_decode_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
                                                     int(nframes), _ptr(d_offsets), _ptr(d_xs), _ptr(d_diff), int(capacity)))
 
+    def apply_cwire_batch(self, d_cwire, counts, escapes, nframes, d_frames_out=None, stride=None):
+        """client/opencv.cpp:50-66 straight from compact records on this core's state, in one call; counts / escapes: the
+        frames' headers (n, e) as the client read them.  d_frames_out: frame t is also written at t * stride."""
+        self._hold(d_cwire, d_frames_out)
+        stride = self.total if stride is None else stride
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+        assert counts.size >= nframes and escapes.size >= nframes
+        _l.check(self._lib.mi355_apply_cwire_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
+                                                   int(nframes), _ptr(d_frames_out), int(stride)))
+
     def int_diff(self, d_cur, d_prev, d_out, n):
         self._hold(d_cur, d_prev, d_out)
         _l.check(self._lib.mi355_int_diff(self._h, _ptr(d_cur), _ptr(d_prev), _ptr(d_out), n))

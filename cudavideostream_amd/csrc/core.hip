@@ -13,6 +13,7 @@
 //   one_xs N*4, one_diff N exec(): packed output of a single frame before the D2H copies
 //   cw_cnt    32 KiB       the compact-wire encoder's escape counts per workgroup
 //   cw_items  T*ceil(W/16)*16 + T*4  mi355_diff_stream_cwire_batch: one word per item of the expansion, escapes per frame
+//   cwa_*     T*24 + 2*T*ceil(N/4096)*16  mi355_apply_cwire_batch: frame table, chunk facts, tile directory
 //   hist T*256*4, thr T*4 (per frame of a filter batch), k9 9*4, heat LUT 766*3, glyph atlas
 #include <cmath>
 #include <cstdio>
@@ -20,6 +21,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "../../include/mi355diff.h"
 #include "internal.h"
@@ -73,6 +75,9 @@ struct mi355_core {
     uint32_t *cw_cnt = nullptr;     // mi355_cwire_encode_batch: escapes per workgroup of the emit kernel (kCwireSlots words)
     uint4 *cw_items = nullptr;      // mi355_diff_stream_cwire_batch: [T][ceil(W/16)] item words (diff_pack.hip, k_cwire_items)
     uint32_t *cw_esc = nullptr;     // ... and [T] escapes per frame
+    CwaFrame *cwa_ftab = nullptr;   // mi355_apply_cwire_batch (stream_ops.hip): [T] frame headers of a slice,
+    uint4 *cwa_chunk = nullptr;     // [T * cwa_chunks(N)] chunk facts,
+    uint4 *cwa_dir = nullptr;       // [T][cwa_tiles(N)] directory words
     uint8_t *gray1 = nullptr;      // fused gray+binarize chain: one gray byte per pixel of a batch, made on first use
     size_t gray1_stride = 0;
     float *k9 = nullptr;
@@ -597,6 +602,9 @@ int mi355_create(const mi355_config *cfg, mi355_core **out) {
     if (!rc) rc = dev_alloc(c, &c->cw_cnt, (size_t)kCwireSlots);
     if (!rc) rc = dev_alloc(c, &c->cw_items, T * cwire_items_per_frame(c->ntiles));
     if (!rc) rc = dev_alloc(c, &c->cw_esc, T);
+    if (!rc) rc = dev_alloc(c, &c->cwa_ftab, T);
+    if (!rc) rc = dev_alloc(c, &c->cwa_chunk, T * cwa_chunks(c->n));
+    if (!rc) rc = dev_alloc(c, &c->cwa_dir, T * cwa_tiles(c->n));
     if (!rc) rc = dev_alloc(c, &c->one_xs, N + 4);
     if (!rc) rc = dev_alloc(c, &c->one_diff, N + 16);
     if (!rc) rc = dev_alloc(c, &c->hist, 256 * T);
@@ -642,7 +650,8 @@ void mi355_destroy(mi355_core *c) {
         if (c->h_tot) (void)hipHostFree(c->h_tot);
     }
     void *ptrs[] = {c->state, c->in, c->aux, c->vis, c->rec, c->codes, c->meta, c->groff, c->totals, c->offsets, c->one_xs, c->one_diff, c->hist, c->thr, c->k9,
-                    c->lut, c->glyphs, c->kxk, c->gray1, c->red_bounds, c->cw_cnt, c->cw_items, c->cw_esc};
+                    c->lut, c->glyphs, c->kxk, c->gray1, c->red_bounds, c->cw_cnt, c->cw_items, c->cw_esc,
+                    c->cwa_ftab, c->cwa_chunk, c->cwa_dir};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->h_count) (void)hipHostFree(c->h_count);
     for (auto &slot : c->ev) for (auto &ev : slot) if (ev) (void)hipEventDestroy(ev);
@@ -949,6 +958,47 @@ int mi355_cwire_decode_batch(mi355_core *c, const void *d_cwire, const uint32_t 
             out += n;
         }
         HIP_TRY(launch_cwire_decode(a, nf, c->stream));
+    }
+    return MI355_OK;
+}
+
+int mi355_apply_cwire_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
+                            int nframes, void *d_frames_out, size_t stride_bytes) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nframes < 0) return fail(MI355_ERR_INVALID, "nframes < 0");
+    if (nframes == 0) return MI355_OK;
+    if (!d_cwire || !h_counts || !h_escapes) return fail(MI355_ERR_INVALID, "null argument");
+    if ((uintptr_t)d_cwire & 3u) return fail(MI355_ERR_INVALID, "d_cwire must be 4-byte aligned");
+    if (d_frames_out && stride_bytes < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
+    for (int t = 0; t < nframes; t++) {
+        if (h_escapes[t] > h_counts[t]) return fail(MI355_ERR_INVALID, "frame header: more escapes than entries");
+        if (h_counts[t] > c->n) return fail(MI355_ERR_INVALID, "frame header: more entries than frame bytes");
+    }
+    if (c->n == 0) return MI355_OK;   // (every count is 0)
+    if (int rc = use_device(c)) return rc;
+    CwaArgs a{};
+    a.cwire = (const uint8_t *)d_cwire;
+    a.ftab = c->cwa_ftab;
+    a.chunk = c->cwa_chunk;
+    a.dir = c->cwa_dir;
+    a.state = c->state;
+    a.stride = stride_bytes;
+    a.n = c->n;
+    a.ntiles = cwa_tiles(c->n);
+    const int T = c->cfg.max_batch;
+    std::vector<CwaFrame> fr((size_t)(nframes < T ? nframes : T));
+    uint64_t pos = 0;
+    for (int t0 = 0; t0 < nframes; t0 += T) {   // slices of at most max_batch frames: the scratch holds one
+        const int nf = nframes - t0 < T ? nframes - t0 : T;
+        uint32_t cbase = 0;
+        for (int k = 0; k < nf; k++) {
+            const uint32_t n = h_counts[t0 + k], e = h_escapes[t0 + k];
+            fr[k] = CwaFrame{pos, n, e, cbase, cwa_chunks(n)};
+            cbase += fr[k].nc;
+            pos += mi355_cwire_frame_bytes(n, e);
+        }
+        a.out = d_frames_out ? (uint8_t *)d_frames_out + (size_t)t0 * stride_bytes : nullptr;
+        HIP_TRY(launch_cwire_apply(a, fr.data(), nf, c->stream));
     }
     return MI355_OK;
 }

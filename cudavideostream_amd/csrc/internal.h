@@ -133,6 +133,34 @@ struct CwireDecodeArgs {
     CwireFrame frame[kCwireDecodeFrames];
 };
 hipError_t launch_cwire_decode(const CwireDecodeArgs &a, int nframes, hipStream_t s);
+// stream_ops.hip -- mi355_apply_cwire_batch: records straight onto the state, tile-major (one wave per kCwaTile bytes)
+constexpr uint32_t kCwaChunk = 4096;    // codes per workgroup of the directory kernels
+constexpr uint32_t kCwaTile = 4096;     // bytes of the state per workgroup of the apply kernel
+constexpr int kCwaTableFrames = 128;    // frame headers per k_cwa_table launch (kernel arguments)
+struct CwaFrame {
+    uint64_t pos;         // byte position of the record in the compact stream
+    uint32_t n, e;        // its header, as the client read it
+    uint32_t cbase, nc;   // its chunks: [cbase, cbase + nc) of the slice, nc = cwa_chunks(n)
+};
+struct CwaArgs {
+    const uint8_t *cwire;
+    CwaFrame *ftab;       // [T] scratch of the core
+    uint4 *chunk;         // [T * cwa_chunks(N)] scratch: {escape codes, first escape rank, running index, frame}
+    uint4 *dir;           // [T][ntiles] scratch: {first entry, its escape rank, running index before it, 0}
+    uint8_t *state;
+    uint8_t *out;         // frame t at out + t*stride, or nullptr
+    size_t stride;
+    uint32_t n;           // bytes per frame
+    uint32_t ntiles;      // cwa_tiles(n)
+};
+struct CwaTableArgs {
+    int32_t first;
+    CwaFrame frame[kCwaTableFrames];
+};
+uint32_t cwa_chunks(uint32_t n);        // chunks of a frame of n entries (1 for n = 0)
+uint32_t cwa_tiles(uint32_t nbytes);
+// frames[i].cbase / nc filled by the caller; nframes <= the scratch's T
+hipError_t launch_cwire_apply(const CwaArgs &a, const CwaFrame *frames, int nframes, hipStream_t s);
 
 // filters.hip -- every per-frame kernel takes a FrameBatch: frame f lives at base + f*stride
 struct FrameBatch {

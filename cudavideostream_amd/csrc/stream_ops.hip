@@ -5,7 +5,8 @@
 //   k_merge_parts         : concatenation of the streams of the row bands of ONE video stream that
 //                           several cores (GPUs) packed independently into
 //                           the single stream the sender would have produced;
-//   k_cwire_*             : the compact wire format's encoder (packed stream -> gap-coded records) and decoder.
+//   k_cwire_*             : the compact wire format's encoder (packed stream -> gap-coded records) and decoder;
+//   k_cwa_*               : the compact records applied straight to a client core's state (mi355_apply_cwire_batch).
 //
 // The first two are index-driven byte scatter/copy: HBM-latency work with 5 bytes of traffic per entry, no
 // arithmetic worth naming.
@@ -444,6 +445,361 @@ __global__ __launch_bounds__(256) void k_cwire_decode(const CwireDecodeArgs a) {
 
 hipError_t launch_cwire_decode(const CwireDecodeArgs &a, int nframes, hipStream_t s) {
     if (nframes > 0) hipLaunchKernelGGL(k_cwire_decode, dim3(nframes), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+
+// ---- mi355_apply_cwire_batch: compact records (include/mi355diff.h, "compact wire") applied straight to a
+// client core's state, client/opencv.cpp:50-66, without expanding them into (offsets, xs, diff) first.
+//
+// Tile-major.  The state is cut into byte tiles of kCwaTile bytes; one single-wave workgroup owns a tile for the whole
+// slice of frames: it keeps the tile in LDS, adds the tile's own entries of frame 0, 1, ... in order and stores the
+// tile to each output frame, then to the state once.  What a tile workgroup needs to start decoding frame t in the middle
+// of the record -- the first entry at or past the tile, the escape rank there and the running index before it -- is a
+// directory word dir[t][tile] that four small kernels make from the records beforehand:
+//   k_cwa_table  (grid: frames)  : the frames' headers (kernel arguments, host) -> ftab; chunk -> frame map
+//   k_cwa_facts  (grid: chunks)  : per chunk of kCwaChunk codes: escape codes, sum of g + 1 over the other codes
+//   k_cwa_scan   (grid: frames)  : exclusive scan over the frame's chunks (escape counts, then running sums)
+//   k_cwa_escsum (grid: chunks)  : adds the chunk's escaped gaps (esc[r] + 1 for its ranks r < e) to its sum
+//   k_cwa_dir    (grid: chunks)  : decodes the chunk once; entry k writes dir[t][tile] for every tile whose first byte
+//                                  lies in (x[k-1], x[k]]; the frame's last chunk writes k = n into the tiles past x[n-1]
+//   k_cwa_apply  (grid: tiles)   : the tile loop above
+// No workgroup waits on another; nothing but the state and the output frames' bytes is written outside the core's
+// scratch.  Decoding follows k_cwire_decode (stream_ops.hip): an escape ranked at or past e adds nothing to the running
+// index and changes nothing, indices outside the tile are not applied, reads stay inside [pos, pos + record bytes).
+typedef uint32_t cwa_u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ uint32_t cwa_wave_sum(uint32_t v) {
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) v += __shfl_xor(v, k, 64);
+    return v;
+}
+
+__device__ __forceinline__ uint32_t cwa_wave_incl(uint32_t v, int lane) {
+#pragma unroll
+    for (int k = 1; k < 64; k <<= 1) {
+        const uint32_t u = __shfl_up(v, k, 64);
+        if (lane >= k) v += u;
+    }
+    return v;
+}
+
+__device__ __forceinline__ uint64_t cwa_ceil_tile(uint32_t x) { return ((uint64_t)x + kCwaTile - 1) / kCwaTile; }
+
+__device__ __forceinline__ const uint32_t *cwa_codes(const CwaArgs &a, const CwaFrame &f) {
+    return (const uint32_t *)(a.cwire + f.pos + 8);
+}
+__device__ __forceinline__ const uint32_t *cwa_esc(const CwaArgs &a, const CwaFrame &f) {
+    return cwa_codes(a, f) + (f.n + 3u) / 4u;
+}
+__device__ __forceinline__ const uint32_t *cwa_dif(const CwaArgs &a, const CwaFrame &f) { return cwa_esc(a, f) + f.e; }
+
+// ---- headers -> ftab, chunk -> frame ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_cwa_table(const CwaArgs a, const CwaTableArgs h) {
+    const int i = blockIdx.x;
+    const CwaFrame f = h.frame[i];
+    if (threadIdx.x == 0) a.ftab[h.first + i] = f;
+    for (uint32_t j = threadIdx.x; j < f.nc; j += 256) a.chunk[f.cbase + j] = make_uint4(0u, 0u, 0u, (uint32_t)(h.first + i));
+}
+
+// ---- per chunk: escape codes (x) and sum of g + 1 over the non-escaped codes (z) --------------------------------------------
+__global__ __launch_bounds__(256) void k_cwa_facts(const CwaArgs a) {
+    __shared__ uint32_t s_cnt[4], s_sum[4];
+    const uint32_t c = blockIdx.x;
+    const uint32_t t = a.chunk[c].w;
+    const CwaFrame f = a.ftab[t];
+    const uint32_t k0 = (c - f.cbase) * kCwaChunk;
+    const uint32_t k1 = f.n - k0 < kCwaChunk ? f.n : k0 + kCwaChunk;
+    const uint32_t *code = cwa_codes(a, f);
+    uint32_t cnt = 0, sum = 0;
+#pragma unroll
+    for (int i = 0; i < (int)(kCwaChunk / 1024); i++) {
+        const uint32_t d = k0 / 4 + threadIdx.x + 256 * i;
+        if (4 * d < k1) {
+            const uint32_t w = code[d];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const uint32_t g = (w >> (8 * j)) & 255u;
+                if (4 * d + j < k1) {
+                    if (g == 255u) cnt++;
+                    else sum += g + 1u;
+                }
+            }
+        }
+    }
+    cnt = cwa_wave_sum(cnt);
+    sum = cwa_wave_sum(sum);
+    if ((threadIdx.x & 63) == 0) {
+        s_cnt[threadIdx.x >> 6] = cnt;
+        s_sum[threadIdx.x >> 6] = sum;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a.chunk[c].x = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+        a.chunk[c].z = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+    }
+}
+
+// ---- per frame: exclusive scan over its chunks; field 0: x (escape codes) -> y (first escape rank), field 1: z -> z ------
+__global__ __launch_bounds__(256) void k_cwa_scan(const CwaArgs a, int field) {
+    __shared__ uint32_t s_wave[2][4];
+    const CwaFrame f = a.ftab[blockIdx.x];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t carry = 0;
+    int buf = 0;
+    for (uint32_t i0 = 0; i0 < f.nc; i0 += 256, buf ^= 1) {
+        const uint32_t i = i0 + threadIdx.x;
+        uint4 *ch = a.chunk + f.cbase + i;
+        const uint32_t v = i < f.nc ? (field == 0 ? ch->x : ch->z) : 0u;
+        const uint32_t incl = cwa_wave_incl(v, lane);
+        if (lane == 63) s_wave[buf][wave] = incl;
+        __syncthreads();
+        uint32_t before = carry;
+        for (int w = 0; w < wave; w++) before += s_wave[buf][w];
+        if (i < f.nc) {
+            if (field == 0) ch->y = before + incl - v;
+            else ch->z = before + incl - v;
+        }
+        carry += s_wave[buf][0] + s_wave[buf][1] + s_wave[buf][2] + s_wave[buf][3];
+    }
+}
+
+// ---- per chunk: + sum of esc[r] + 1 over its escape ranks r in [y, y + x) below e ---------------------------------------
+__global__ __launch_bounds__(256) void k_cwa_escsum(const CwaArgs a) {
+    __shared__ uint32_t s_sum[4];
+    const uint32_t c = blockIdx.x;
+    const uint4 ch = a.chunk[c];
+    const CwaFrame f = a.ftab[ch.w];
+    const uint32_t r0 = ch.y < f.e ? ch.y : f.e;
+    const uint32_t r1 = f.e - r0 < ch.x ? f.e : r0 + ch.x;
+    const uint32_t *esc = cwa_esc(a, f);
+    uint32_t sum = 0;
+    for (uint32_t r = r0 + threadIdx.x; r < r1; r += 256) sum += esc[r] + 1u;
+    sum = cwa_wave_sum(sum);
+    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) a.chunk[c].z = ch.z + s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+}
+
+// ---- per chunk: the directory words of the tiles its entries open ---------------------------------------------------------
+__global__ __launch_bounds__(256) void k_cwa_dir(const CwaArgs a) {
+    __shared__ uint32_t s_esc[2][4], s_sum[2][4];
+    const uint32_t c = blockIdx.x;
+    const uint4 ch = a.chunk[c];
+    const uint32_t t = ch.w;
+    const CwaFrame f = a.ftab[t];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t cl = c - f.cbase;
+    const uint32_t k0 = cl * kCwaChunk;
+    const uint32_t k1 = f.n - k0 < kCwaChunk ? f.n : k0 + kCwaChunk;
+    const uint32_t *code = cwa_codes(a, f), *esc = cwa_esc(a, f);
+    uint4 *dir = a.dir + (size_t)t * a.ntiles;
+    const uint64_t lt = (1ull << lane) - 1ull;
+    uint32_t carry_e = ch.y, carry_x = ch.z;   // escape rank and running index (sum of g + 1) before the chunk
+    int buf = 0;
+    for (uint32_t base = k0; base < k1; base += 1024, buf ^= 1) {
+        const uint32_t d = base / 4 + threadIdx.x;
+        const bool live = 4 * d < k1;
+        const uint32_t word = live ? code[d] : 0u;
+        bool fl[4];
+        uint32_t before = 0, wtot = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            fl[j] = live && 4 * d + j < k1 && ((word >> (8 * j)) & 255u) == 255u;
+            const uint64_t m = __ballot(fl[j]);
+            before += (uint32_t)__popcll(m & lt);
+            wtot += (uint32_t)__popcll(m);
+        }
+        if (lane == 0) s_esc[buf][wave] = wtot;
+        __syncthreads();
+        uint32_t rank = carry_e + before;
+        for (int w = 0; w < wave; w++) rank += s_esc[buf][w];
+        uint32_t inc[4], rk[4], lsum = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            inc[j] = 0;
+            rk[j] = rank;
+            if (live && 4 * d + j < k1) {
+                uint32_t g = (word >> (8 * j)) & 255u;
+                bool bad = false;
+                if (fl[j]) {
+                    if (rank < f.e) g = esc[rank];
+                    else bad = true;
+                    rank++;
+                }
+                inc[j] = bad ? 0u : g + 1u;
+            }
+            lsum += inc[j];
+        }
+        const uint32_t incl = cwa_wave_incl(lsum, lane);
+        if (lane == 63) s_sum[buf][wave] = incl;
+        __syncthreads();
+        uint32_t x = carry_x + incl - lsum;
+        for (int w = 0; w < wave; w++) x += s_sum[buf][w];
+        carry_e += s_esc[buf][0] + s_esc[buf][1] + s_esc[buf][2] + s_esc[buf][3];
+        carry_x += s_sum[buf][0] + s_sum[buf][1] + s_sum[buf][2] + s_sum[buf][3];
+        if (live) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const uint32_t k = 4 * d + j;
+                if (k >= k1) break;
+                const uint32_t xn = x + inc[j];
+                // tiles whose first byte s has x <= s < xn, i.e. x[k-1] < s <= x[k] (none when the sum wrapped)
+                uint64_t lo = cwa_ceil_tile(x), hi = cwa_ceil_tile(xn);
+                if (hi > a.ntiles) hi = a.ntiles;
+                for (uint64_t tl = lo; tl < hi; tl++) dir[tl] = make_uint4(k, rk[j], x, 0u);
+                x = xn;
+            }
+        }
+    }
+    if (cl + 1 == f.nc)   // the tiles past the frame's last entry (all of them for n = 0)
+        for (uint64_t tl = cwa_ceil_tile(carry_x) + threadIdx.x; tl < a.ntiles; tl += 256)
+            dir[tl] = make_uint4(f.n, carry_e, carry_x, 0u);
+}
+
+// ---- per tile: the slice's frames in order, in LDS -------------------------------------------------------------------------
+// Bytes [lo, lo + len) of src -> LDS, or LDS -> dst: whole 16-byte words where the global address allows, bytes otherwise.
+__device__ __forceinline__ void cwa_tile_load(uint8_t *s, const uint8_t *src, uint32_t len, int lane) {
+    const uint32_t q = ((uintptr_t)src & 15u) ? 0u : len / 16u;
+    for (uint32_t i = lane; i < q; i += 64) ((cwa_u32x4 *)s)[i] = ((const cwa_u32x4 *)src)[i];
+    for (uint32_t i = 16 * q + lane; i < len; i += 64) s[i] = src[i];
+}
+
+__device__ __forceinline__ void cwa_tile_store(uint8_t *dst, const uint8_t *s, uint32_t len, int lane) {
+    const uint32_t q = ((uintptr_t)dst & 15u) ? 0u : len / 16u;
+    for (uint32_t i = lane; i < q; i += 64) __builtin_nontemporal_store(((const cwa_u32x4 *)s)[i], (cwa_u32x4 *)dst + i);
+    for (uint32_t i = 16 * q + lane; i < len; i += 64) __builtin_nontemporal_store(s[i], dst + i);
+}
+
+// The first block of a frame's entries for the tile: 256 entries from k & ~3, four per lane (code and diff dwords).
+struct CwaBlock {
+    uint32_t word, dw;
+};
+
+__device__ __forceinline__ CwaBlock cwa_block_load(const CwaArgs &a, const CwaFrame &f, uint32_t k, int lane) {
+    const uint32_t d = k / 4 + lane;
+    CwaBlock b{0u, 0u};
+    if (k < f.n && 4 * d < f.n) {
+        b.word = cwa_codes(a, f)[d];
+        b.dw = cwa_dif(a, f)[d];
+    }
+    return b;
+}
+
+__global__ __launch_bounds__(64) void k_cwa_apply(const CwaArgs a, int nframes) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
+    uint8_t *s = (uint8_t *)s_q;
+    const int lane = threadIdx.x;
+    const uint32_t tile = blockIdx.x;
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    const uint32_t hi = lo + len;
+    const uint64_t lt = (1ull << lane) - 1ull;
+    cwa_tile_load(s, a.state + lo, len, lane);
+    // while frame t is applied, frame t + 1's first block and frame t + 2's directory word are in flight
+    CwaFrame f1 = a.ftab[0], f2 = f1;
+    uint4 d1 = a.dir[tile], d2 = d1;
+    CwaBlock b1 = cwa_block_load(a, f1, d1.x, lane);
+    if (nframes > 1) {
+        f2 = a.ftab[1];
+        d2 = a.dir[(size_t)a.ntiles + tile];
+    }
+    __syncthreads();
+    for (int t = 0; t < nframes; t++) {
+        const CwaFrame f = f1;
+        const uint4 dr = d1;
+        CwaBlock b = b1;
+        if (t + 1 < nframes) {
+            f1 = f2;
+            d1 = d2;
+            b1 = cwa_block_load(a, f1, d1.x, lane);
+        }
+        if (t + 2 < nframes) {
+            f2 = a.ftab[t + 2];
+            d2 = a.dir[(size_t)(t + 2) * a.ntiles + tile];
+        }
+        const uint32_t *code = cwa_codes(a, f), *esc = cwa_esc(a, f), *dif = cwa_dif(a, f);
+        uint32_t k = dr.x, rank = dr.y, x = dr.z;
+        bool first = true;
+        while (k < f.n) {
+            const uint32_t ka = k & ~3u, d = ka / 4 + lane;
+            if (!first) {
+                b.word = 4 * d < f.n ? code[d] : 0u;
+                b.dw = 4 * d < f.n ? dif[d] : 0u;
+            }
+            first = false;
+            bool fl[4], in[4];
+            uint32_t before = 0, wtot = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const uint32_t kk = 4 * d + j;
+                in[j] = kk >= k && kk < f.n;
+                fl[j] = in[j] && ((b.word >> (8 * j)) & 255u) == 255u;
+                const uint64_t m = __ballot(fl[j]);
+                before += (uint32_t)__popcll(m & lt);
+                wtot += (uint32_t)__popcll(m);
+            }
+            uint32_t r = rank + before, inc[4], lsum = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                inc[j] = 0;
+                if (in[j]) {
+                    uint32_t g = (b.word >> (8 * j)) & 255u;
+                    bool bad = false;
+                    if (fl[j]) {
+                        if (r < f.e) g = esc[r];
+                        else bad = true;
+                        r++;
+                    }
+                    inc[j] = bad ? 0u : g + 1u;
+                }
+                lsum += inc[j];
+            }
+            const uint32_t incl = cwa_wave_incl(lsum, lane);
+            uint32_t xi = x + incl - lsum;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                xi += inc[j];
+                const uint32_t idx = xi - 1u;   // (inc 0: a bad escape or a masked entry, nothing to apply)
+                if (inc[j] && idx >= lo && idx < hi) s[idx - lo] = (uint8_t)(s[idx - lo] + (b.dw >> (8 * j)));
+            }
+            x += __shfl(incl, 63, 64);
+            rank += wtot;
+            k = ka + 256;
+            if (x >= hi) break;   // the next entry's index is at least x
+        }
+        __syncthreads();
+        if (a.out) cwa_tile_store(a.out + (size_t)t * a.stride + lo, s, len, lane);
+        __syncthreads();
+    }
+    const uint32_t q = len / 16u;   // the state is allocation aligned
+    for (uint32_t i = lane; i < q; i += 64) ((cwa_u32x4 *)(a.state + lo))[i] = s_q[i];
+    for (uint32_t i = 16 * q + lane; i < len; i += 64) a.state[lo + i] = s[i];
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+uint32_t cwa_chunks(uint32_t n) { return n ? (n + kCwaChunk - 1) / kCwaChunk : 1u; }
+uint32_t cwa_tiles(uint32_t nbytes) { return (nbytes + kCwaTile - 1) / kCwaTile; }
+
+hipError_t launch_cwire_apply(const CwaArgs &a, const CwaFrame *frames, int nframes, hipStream_t s) {
+    if (nframes <= 0 || a.ntiles == 0) return hipSuccess;
+    uint32_t nchunks = 0;
+    CwaTableArgs h{};
+    for (int i0 = 0; i0 < nframes; i0 += kCwaTableFrames) {
+        const int nf = nframes - i0 < kCwaTableFrames ? nframes - i0 : kCwaTableFrames;
+        h.first = i0;
+        for (int i = 0; i < nf; i++) {
+            h.frame[i] = frames[i0 + i];
+            nchunks = frames[i0 + i].cbase + frames[i0 + i].nc;
+        }
+        hipLaunchKernelGGL(k_cwa_table, dim3(nf), dim3(256), 0, s, a, h);
+    }
+    hipLaunchKernelGGL(k_cwa_facts, dim3(nchunks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_cwa_scan, dim3(nframes), dim3(256), 0, s, a, 0);
+    hipLaunchKernelGGL(k_cwa_escsum, dim3(nchunks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_cwa_scan, dim3(nframes), dim3(256), 0, s, a, 1);
+    hipLaunchKernelGGL(k_cwa_dir, dim3(nchunks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_cwa_apply, dim3(a.ntiles), dim3(64), 0, s, a, nframes);
     return hipGetLastError();
 }
 

@@ -78,6 +78,8 @@ SYMBOLS = {
                                            C.c_void_p, C.c_void_p, C.c_size_t]),
     "mi355_cwire_decode_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mi355_apply_cwire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_size_t]),
     "mi355_cwire_apply_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int,
                                          C.POINTER(C.c_size_t)]),
     "mi355_int_diff": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -136,7 +138,7 @@ SYMBOLS = {
     "mi355_group_synchronize": (C.c_int, [C.c_void_p]),
 }
 GROUP_ID_BYTES = 128   # MI355_GROUP_ID_BYTES
-ABI_VERSION = 9        # MI355_ABI_VERSION of the include/mi355diff.h these argument lists were written against
+ABI_VERSION = 10       # MI355_ABI_VERSION of the include/mi355diff.h these argument lists were written against
 
 _lib = None
 

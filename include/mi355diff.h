@@ -80,8 +80,9 @@ typedef struct mi355_config {
  *   8  the schedule options 2..5 (split share, dense threshold, filter/batch chain hint, pack grid) are gone: their ids
  *      are refused (MI355_ERR_INVALID) and will not be reused; their defaults are the library's fixed schedule, unchanged
  *      (mi355_diff_stream_batch)
- *   9  + mi355_diff_stream_cwire_batch (additions only) */
-#define MI355_ABI_VERSION 9
+ *   9  + mi355_diff_stream_cwire_batch (additions only)
+ *   10 + mi355_apply_cwire_batch (additions only) */
+#define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
 /* ---- life cycle: CUDACore::CUDACore (kernels.cu:377-428) without the uploads ------------------ */
@@ -182,7 +183,7 @@ int mi355_set_glyphs(mi355_core *core, const uint8_t *chars_px, int nglyphs, int
  * batch run on a side stream beside the next batch's pack kernel.  A batch's outputs (d_offsets, d_xs, d_diff,
  * d_wire) are complete after mi355_synchronize and for every later call on this core that can consume them
  * (mi355_apply_*, mi355_red_stream_batch / _red_overlap, mi355_merge_parts, mi355_cwire_encode_batch /
- * mi355_cwire_decode_batch, mi355_download, mi355_exec / mi355_pipe_*, the group gather) -- these first wait for the last
+ * mi355_cwire_decode_batch / mi355_apply_cwire_batch, mi355_download, mi355_exec / mi355_pipe_*, the group gather) -- these first wait for the last
  * expansion.  The frame filters (mi355_filter_batch,
  * mi355_gray_*, mi355_binarize_chain, mi355_heat_map, mi355_red_dense, mi355_conv*, mi355_median5x5,
  * mi355_int_diff) take frames, not packed streams, and are ordered on the core's stream only: they may run beside
@@ -295,6 +296,25 @@ int mi355_cwire_encode_batch(mi355_core *core, const void *d_offsets, const void
  * h_counts[t] is refused.  Same alignment as the encoder.  Asynchronous on the core's stream. */
 int mi355_cwire_decode_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
                              int nframes, void *d_offsets, void *d_xs, void *d_diff, size_t capacity);
+/* A GPU client in one call: client/opencv.cpp:50-66 straight from the records.  For each record t in order, state[x] += diff
+ * (uint8 wrap-around) on the core's state; d_frames_out != NULL: the reconstructed frame t is also written to
+ * d_frames_out + t*stride_bytes (whole 16-byte stores when d_frames_out and stride_bytes are multiples of 16, any
+ * alignment works); NULL: only the state advances.  The headers come from the host, as for mi355_cwire_decode_batch:
+ * h_counts[t] = n, h_escapes[t] = e; the records lie back to back where those headers put them and the header words inside
+ * d_cwire are skipped, not trusted.
+ *   Well-formed records: the state and every output frame are bit-identical to mi355_cwire_apply_host, and to
+ *   mi355_cwire_decode_batch followed by mi355_apply_batch (in both modes).
+ *   Malformed content (with consistent headers) stays memory-safe: nothing is read outside the records' span, nothing is
+ *   written outside the state and the nframes output frames (not into the stride gap either).  An escape ranked at or past
+ *   e and an index >= N change nothing; beyond that the bytes of a malformed frame's result are unspecified.
+ *   Refused with MI355_ERR_INVALID before anything is launched: nframes < 0; a null d_cwire, h_counts or h_escapes when
+ *   nframes > 0; h_escapes[t] > h_counts[t]; h_counts[t] > N; d_cwire not 4-byte aligned; stride_bytes < N with
+ *   d_frames_out set.
+ * nframes has no upper bound: longer batches are applied in slices of max_batch frames.  Scratch of the core, allocated with
+ * it and counted by mi355_workspace_bytes: max_batch * (24 + 32 * ceil(N / 4096)) bytes (12.5 MB at 1080p with max_batch
+ * 256).  Asynchronous on the core's stream; per slice six kernel launches and one more per 128 frames, no copies. */
+int mi355_apply_cwire_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
+                            int nframes, void *d_frames_out, size_t stride_bytes);
 /* A client without a GPU: client/opencv.cpp:50-66 on the compact stream, state[xs] += diff for nframes records of host
  * memory `cwire` (cwire_bytes bytes) on a host frame of frame_bytes bytes.  No core, no HIP call.  Every frame is validated
  * before it is applied; MI355_ERR_INVALID (with the reason in mi355_last_error) for a truncated record, n > frame_bytes,

@@ -5,8 +5,10 @@ batches of S1 webcam frames resident in HBM: 1080p with B = 256 and 4K with B = 
 Prints one JSON line per size: microseconds per frame of diff_stream_batch alone, of the encoder alone, of the two
 back to back, of diff_stream_cwire_batch (`direct`: the same records in one call, without the xs / diff arrays) and of
 the decoder; compact and reference-wire bytes per frame; and the encoder's achieved GB/s on its
-algorithmic bytes (per frame: read 4P + 5P, write 8 + 2 pad4(P) + 4e, P = changed bytes).  Not the headline metric
-(bench.py)."""
+algorithmic bytes (per frame: read 4P + 5P, write 8 + 2 pad4(P) + 4e, P = changed bytes).
+The GPU client: apply_cwire_batch (records straight onto a client core's state, one call) with the shown frames written
+out (`frames`) and state only (`state`), next to decode + apply_batch in the same two modes, measured in the same run;
+for the `frames` mode also the achieved write rate on N bytes per frame.  Not the headline metric (bench.py)."""
 import argparse
 import json
 import os
@@ -48,9 +50,11 @@ def run(W, H, B, reps):
     o_xs = torch.empty(cap, dtype=torch.int32, device=dev)
     o_df = torch.empty(cap, dtype=torch.uint8, device=dev)
     base_h = base.cpu().numpy()
-    with CUDACore(W, H, sample_mat_data=base_h, max_batch=B) as core, CUDACore(W, H, max_batch=1) as client:
+    with CUDACore(W, H, sample_mat_data=base_h, max_batch=B) as core, CUDACore(W, H, max_batch=1) as client, \
+            CUDACore(W, H, sample_mat_data=base_h, max_batch=B) as gclient:
         core.use_torch_stream()
         client.use_torch_stream()
+        gclient.use_torch_stream()
 
         def diff():
             core.diff_stream_batch(frames, B, d_off, d_xs, d_df, cap)
@@ -101,6 +105,37 @@ def run(W, H, B, reps):
         us_dec = timed(decode, reps)
         torch.cuda.synchronize()
         assert torch.equal(o_off, d_off)
+
+        # the GPU client: one call against decode + apply_batch, both modes
+        shown = torch.empty(B * n, dtype=torch.uint8, device=dev)
+        shown2 = torch.empty(B * n, dtype=torch.uint8, device=dev)
+
+        def apply_frames():
+            gclient.apply_cwire_batch(d_cw, counts, escapes, B, shown, n)
+
+        def apply_state():
+            gclient.apply_cwire_batch(d_cw, counts, escapes, B)
+
+        def two_frames():
+            client.cwire_decode_batch(d_cw, counts, escapes, B, o_off, o_xs, o_df, cap)
+            client.apply_batch(o_off, o_xs, o_df, B, shown2, n)
+
+        def two_state():
+            client.cwire_decode_batch(d_cw, counts, escapes, B, o_off, o_xs, o_df, cap)
+            client.apply_batch(o_off, o_xs, o_df, B)
+
+        us_af = timed(apply_frames, reps)
+        us_as = timed(apply_state, reps)
+        us_tf = timed(two_frames, reps)
+        us_ts = timed(two_state, reps)
+        gclient.set_state(base_h)
+        client.set_state(base_h)
+        apply_frames()
+        two_frames()
+        torch.cuda.synchronize()
+        assert torch.equal(shown, shown2)   # the one call shows the same frames
+        assert np.array_equal(gclient.get_state(), client.get_state())
+        del shown, shown2
         P = int(off[-1]) / B
         e = float(escapes.sum()) / B
         pad4 = float(np.sum((np.diff(off) + 3) // 4 * 4)) / B
@@ -119,7 +154,15 @@ def run(W, H, B, reps):
                           "encode_share_of_diff": round(us_enc / us_diff, 3),
                           "decode_us_per_frame": round(us_dec / B, 3),
                           "encode_algorithmic_bytes_per_frame": int(alg),
-                          "encode_achieved_gbps": round(alg * B / (us_enc * 1e-6) / 1e9, 1)}), flush=True)
+                          "encode_achieved_gbps": round(alg * B / (us_enc * 1e-6) / 1e9, 1),
+                          "apply_cwire_frames_us_per_frame": round(us_af / B, 3),
+                          "apply_cwire_state_us_per_frame": round(us_as / B, 3),
+                          "decode_apply_frames_us_per_frame": round(us_tf / B, 3),
+                          "decode_apply_state_us_per_frame": round(us_ts / B, 3),
+                          "apply_cwire_frames_speedup": round(us_tf / us_af, 2),
+                          "apply_cwire_state_speedup": round(us_ts / us_as, 2),
+                          "apply_cwire_state_over_direct": round(us_as / us_direct, 3),
+                          "apply_cwire_frames_write_tbps": round(n * B / (us_af * 1e-6) / 1e12, 2)}), flush=True)
 
 
 def main():

@@ -13,8 +13,12 @@
 // core and no GPU -- rebuilds every frame on the host with mi355_cwire_apply_host; each rebuilt frame is checked against
 // the frame that was sent, and the client's frame against the server's state after every batch.
 // --compact --direct: the server makes the records in one call (mi355_diff_stream_cwire_batch), without the xs / diff arrays.
+// --compact --gpu-client: the client core also uploads the received records and applies them in one call
+// (mi355_apply_cwire_batch) into its shown frames; every shown frame must equal the host client's frame after that record,
+// and the client core's state the server's state after every batch.
 //
-//   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B] [--compact [--direct]]   exit status 0 = all checks passed
+//   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B] [--compact [--direct] [--gpu-client]]
+//   exit status 0 = all checks passed
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -70,15 +74,17 @@ static bool through_pipe(int wfd, int rfd, const uint8_t *src, uint8_t *dst, siz
 
 int main(int argc, char **argv) {
     int w = 320, h = 180, T = 24, B = 8;
-    bool compact = false, direct = false;
+    bool compact = false, direct = false, gpu_client = false;
     for (int i = 1; i < argc; i++) {
         if (std::string(argv[i]) == "--compact") compact = true;
         if (std::string(argv[i]) == "--direct") direct = true;
+        if (std::string(argv[i]) == "--gpu-client") gpu_client = true;
     }
     if (direct && !compact) { fprintf(stderr, "--direct needs --compact\n"); return 2; }
+    if (gpu_client && !compact) { fprintf(stderr, "--gpu-client needs --compact\n"); return 2; }
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string k = argv[i];
-        if (k == "--compact" || k == "--direct") { i--; continue; }
+        if (k == "--compact" || k == "--direct" || k == "--gpu-client") { i--; continue; }
         const int v = atoi(argv[i + 1]);
         if (k == "--width") w = v; else if (k == "--height") h = v;
         else if (k == "--frames") T = v; else if (k == "--batch") B = v;
@@ -147,11 +153,28 @@ int main(int argc, char **argv) {
             changed += off[nb];
             if (!through_pipe(fds[1], fds[0], cw_host.data(), rx.data(), cb)) return 1;
             sent_bytes += cb;
+            std::vector<uint32_t> counts(nb), escapes(nb);
+            if (gpu_client) {   // the headers as the client reads them from the stream, then one call for the batch
+                size_t p = 0;
+                for (int k = 0; k < nb; k++) {
+                    memcpy(&counts[k], rx.data() + p, 4);
+                    memcpy(&escapes[k], rx.data() + p + 4, 4);
+                    p += mi355_cwire_frame_bytes(counts[k], escapes[k]);
+                }
+                if (p != cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
+                OK(mi355_upload(client, d_cwire, rx.data(), cb));
+                OK(mi355_apply_cwire_batch(client, d_cwire, counts.data(), escapes.data(), nb, d_shown, n));
+                OK(mi355_download(client, shown.data(), d_shown, (size_t)nb * n));
+            }
             size_t at = 0;
             for (int k = 0; k < nb; k++) {   // one frame at a time: what the client shows after each
                 size_t used = 0;
                 OK(mi355_cwire_apply_host(c_frame.data(), n, rx.data() + at, cb - at, 1, &used));
                 at += used;
+                if (gpu_client && memcmp(&shown[(size_t)k * n], c_frame.data(), n) != 0) {
+                    fprintf(stderr, "GPU client frame %d != host client frame\n", t0 + k);
+                    return 1;
+                }
                 for (size_t i = 0; i < n; i++) {
                     const int e = abs((int)c_frame[i] - (int)frames[(size_t)k * n + i]);
                     if (e > max_err) max_err = e;
@@ -160,6 +183,10 @@ int main(int argc, char **argv) {
             if (at != cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
             OK(mi355_get_state(server, s_state.data()));
             if (memcmp(s_state.data(), c_frame.data(), n) != 0) { fprintf(stderr, "client frame != server state\n"); return 1; }
+            if (gpu_client) {
+                OK(mi355_get_state(client, c_state.data()));
+                if (memcmp(s_state.data(), c_state.data(), n) != 0) { fprintf(stderr, "GPU client state != server state\n"); return 1; }
+            }
         }
         if (max_err > cfg.threshold) { fprintf(stderr, "rebuilt frame off by %d > threshold\n", max_err); return 1; }
         if (!direct) {
@@ -175,10 +202,10 @@ int main(int argc, char **argv) {
         OK(mi355_dev_free(client, d_shown));
         mi355_destroy(server);
         mi355_destroy(client);
-        printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"direct\": %s, \"width\": %d, \"height\": %d, \"frames\": %d, \"batch\": %d, "
+        printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"direct\": %s, \"gpu_client\": %s, \"width\": %d, \"height\": %d, \"frames\": %d, \"batch\": %d, "
                "\"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, "
                "\"max_abs_error\": %d}\n",
-               direct ? "true" : "false", w, h, T, B, changed, sent_bytes, mi355_wire_bytes(T, changed), (size_t)T * n, max_err);
+               direct ? "true" : "false", gpu_client ? "true" : "false", w, h, T, B, changed, sent_bytes, mi355_wire_bytes(T, changed), (size_t)T * n, max_err);
         return 0;
     }
     for (int t0 = 0; t0 < T; t0 += B) {
