@@ -24,7 +24,7 @@
 #include <vector>
 
 #include "../../include/mi355diff.h"
-#include "internal.h"
+#include "cwire_common.h"
 
 using namespace mi355;
 
@@ -903,13 +903,35 @@ int mi355_merge_parts(mi355_core *c, int nparts, int nframes, const void *d_part
 }
 
 // ---- compact wire (include/mi355diff.h) ----------------------------------------------------------------------------
-static inline uint64_t pad4(uint64_t x) { return (x + 3) & ~3ull; }
-
-size_t mi355_cwire_frame_bytes(uint32_t n, uint32_t e) { return (size_t)(8 + 2 * pad4(n) + 4 * (uint64_t)e); }
+size_t mi355_cwire_frame_bytes(uint32_t n, uint32_t e) { return (size_t)cwire_record_bytes(n, e); }
 
 size_t mi355_cwire_bytes_max(size_t frame_bytes, int nframes) {
-    return nframes > 0 ? (size_t)nframes * (size_t)(8 + 2 * pad4(frame_bytes)) : 0;
+    return nframes > 0 ? (size_t)nframes * (size_t)cwire_record_bytes(frame_bytes, 0) : 0;
 }
+
+// The frame headers of a compact stream as the client read them (decode and GPU client): check() before anything is
+// enqueued, then next() once per frame, in order, for the frame's place and header.
+struct CwireHeaders {
+    const uint32_t *counts, *escapes;
+    int nframes;
+    int t = 0;
+    uint64_t pos = 0;
+    // bounded: an entry count above frame_bytes is refused, too
+    int check(bool bounded, uint32_t frame_bytes) const {
+        for (int i = 0; i < nframes; i++) {
+            if (escapes[i] > counts[i]) return fail(MI355_ERR_INVALID, "frame header: more escapes than entries");
+            if (bounded && counts[i] > frame_bytes) return fail(MI355_ERR_INVALID, "frame header: more entries than frame bytes");
+        }
+        return MI355_OK;
+    }
+    struct Frame { uint64_t pos; uint32_t n, e; };
+    Frame next() {
+        const Frame f{pos, counts[t], escapes[t]};
+        pos += cwire_record_bytes(f.n, f.e);
+        t++;
+        return f;
+    }
+};
 
 int mi355_cwire_encode_batch(mi355_core *c, const void *d_offsets, const void *d_xs, const void *d_diff,
                              size_t entries_capacity, int nframes, void *d_frame_pos, void *d_cwire, size_t capacity_bytes) {
@@ -937,8 +959,8 @@ int mi355_cwire_decode_batch(mi355_core *c, const void *d_cwire, const uint32_t 
     if (capacity > 0 && (!d_xs || !d_diff)) return fail(MI355_ERR_INVALID, "null stream pointer");
     if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_xs & 3u))
         return fail(MI355_ERR_INVALID, "d_cwire, d_offsets and d_xs must be 4-byte aligned");
-    for (int t = 0; t < nframes; t++)
-        if (h_escapes[t] > h_counts[t]) return fail(MI355_ERR_INVALID, "frame header: more escapes than entries");
+    CwireHeaders hdr{h_counts, h_escapes, nframes};
+    if (int rc = hdr.check(false, 0)) return rc;
     if (int rc = use_device(c)) return rc;
     CwireDecodeArgs a{};
     a.cwire = (const uint8_t *)d_cwire;
@@ -946,16 +968,14 @@ int mi355_cwire_decode_batch(mi355_core *c, const void *d_cwire, const uint32_t 
     a.xs = (int32_t *)d_xs;
     a.diff = (uint8_t *)d_diff;
     a.capacity = capacity;
-    uint64_t pos = 0;
     uint32_t out = 0;   // uint32, like every offsets array of the library
     for (int t0 = 0; t0 < nframes; t0 += kCwireDecodeFrames) {
         const int nf = nframes - t0 < kCwireDecodeFrames ? nframes - t0 : kCwireDecodeFrames;
         a.first_frame = t0;
         for (int k = 0; k < nf; k++) {
-            const uint32_t n = h_counts[t0 + k], e = h_escapes[t0 + k];
-            a.frame[k] = CwireFrame{pos, n, e, out, 0};
-            pos += mi355_cwire_frame_bytes(n, e);
-            out += n;
+            const CwireHeaders::Frame f = hdr.next();
+            a.frame[k] = CwireFrame{f.pos, f.n, f.e, out, 0};
+            out += f.n;
         }
         HIP_TRY(launch_cwire_decode(a, nf, c->stream));
     }
@@ -970,10 +990,8 @@ int mi355_apply_cwire_batch(mi355_core *c, const void *d_cwire, const uint32_t *
     if (!d_cwire || !h_counts || !h_escapes) return fail(MI355_ERR_INVALID, "null argument");
     if ((uintptr_t)d_cwire & 3u) return fail(MI355_ERR_INVALID, "d_cwire must be 4-byte aligned");
     if (d_frames_out && stride_bytes < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
-    for (int t = 0; t < nframes; t++) {
-        if (h_escapes[t] > h_counts[t]) return fail(MI355_ERR_INVALID, "frame header: more escapes than entries");
-        if (h_counts[t] > c->n) return fail(MI355_ERR_INVALID, "frame header: more entries than frame bytes");
-    }
+    CwireHeaders hdr{h_counts, h_escapes, nframes};
+    if (int rc = hdr.check(true, c->n)) return rc;
     if (c->n == 0) return MI355_OK;   // (every count is 0)
     if (int rc = use_device(c)) return rc;
     CwaArgs a{};
@@ -987,15 +1005,13 @@ int mi355_apply_cwire_batch(mi355_core *c, const void *d_cwire, const uint32_t *
     a.ntiles = cwa_tiles(c->n);
     const int T = c->cfg.max_batch;
     std::vector<CwaFrame> fr((size_t)(nframes < T ? nframes : T));
-    uint64_t pos = 0;
     for (int t0 = 0; t0 < nframes; t0 += T) {   // slices of at most max_batch frames: the scratch holds one
         const int nf = nframes - t0 < T ? nframes - t0 : T;
         uint32_t cbase = 0;
         for (int k = 0; k < nf; k++) {
-            const uint32_t n = h_counts[t0 + k], e = h_escapes[t0 + k];
-            fr[k] = CwaFrame{pos, n, e, cbase, cwa_chunks(n)};
+            const CwireHeaders::Frame f = hdr.next();
+            fr[k] = CwaFrame{f.pos, f.n, f.e, cbase, cwa_chunks(f.n)};
             cbase += fr[k].nc;
-            pos += mi355_cwire_frame_bytes(n, e);
         }
         a.out = d_frames_out ? (uint8_t *)d_frames_out + (size_t)t0 * stride_bytes : nullptr;
         HIP_TRY(launch_cwire_apply(a, fr.data(), nf, c->stream));
@@ -1034,7 +1050,8 @@ int mi355_cwire_apply_host(uint8_t *state, size_t frame_bytes, const void *cwire
             snprintf(msg, sizeof msg, "compact stream: frame %d: truncated record", t);
             return fail(MI355_ERR_INVALID, msg);
         }
-        const uint8_t *code = p + at + 8, *escb = code + pad4(n), *diff = escb + 4 * (size_t)e;
+        const CwireSections<const uint8_t> sec(p, at, n, e);
+        const uint8_t *code = sec.code, *escb = sec.esc, *diff = sec.diff;
         uint32_t n255 = 0;
         for (uint32_t k = 0; k < n; k++) n255 += code[k] == 255;
         if (n255 != e) {

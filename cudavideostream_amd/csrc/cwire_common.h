@@ -1,0 +1,178 @@
+// cwire_common.h -- the compact wire format (include/mi355diff.h, "compact wire"), once, for host and device:
+// the record's arithmetic and sections, the encode / decode step of a lane's four entries, and the workgroup scans
+// of its kernels (stream_ops.hip: encoder, decoder, GPU client; diff_pack.hip: the log straight into records;
+// core.hip: sizes, header walk, host client).
+// Record of frame t, 4-aligned, at frame_pos[t]:  u32 n | u32 e | u8 code[pad4(n)] | u32 esc[e] | u8 diff[pad4(n)]
+// with g_0 = xs[0], g_k = xs[k] - xs[k-1] - 1, code[k] = min(g_k, 255) and esc[] the g_k of the codes 255, in order.
+#ifndef MI355_CWIRE_COMMON_H_
+#define MI355_CWIRE_COMMON_H_
+
+#include <type_traits>
+
+#include "internal.h"
+
+namespace mi355 {
+
+__host__ __device__ inline uint64_t cwire_pad4(uint64_t x) { return (x + 3) & ~3ull; }
+__host__ __device__ inline uint32_t cwire_dwords(uint32_t n) { return (n + 3u) / 4u; }   // code (or diff) dwords (32-bit, as the kernels always counted them)
+__host__ __device__ inline uint64_t cwire_record_bytes(uint64_t n, uint64_t e) { return 8 + 2 * cwire_pad4(n) + 4 * e; }
+// e of a record of `bytes` bytes with n entries
+__host__ __device__ inline uint32_t cwire_record_escapes(uint64_t bytes, uint32_t n) {
+    return (uint32_t)((bytes - 8 - 2 * cwire_pad4(n)) / 4);
+}
+
+// Where the sections of the record {n, e} at base + pos are.  Byte = uint8_t or const uint8_t.
+template <class Byte>
+struct CwireSections {
+    typedef typename std::conditional<std::is_const<Byte>::value, const uint32_t, uint32_t>::type Word;
+    Byte *code, *esc, *diff;   // pad4(n) codes, e escapes of 4 bytes, pad4(n) differences
+    __host__ __device__ CwireSections(Byte *base, uint64_t pos, uint32_t n, uint32_t e)
+        : code(base + pos + 8), esc(code + cwire_pad4(n)), diff(esc + 4 * (uint64_t)e) {}
+    // as dwords (the GPU entry points take a 4-aligned stream)
+    __host__ __device__ Word *code32() const { return (Word *)code; }
+    __host__ __device__ Word *esc32() const { return (Word *)esc; }
+    __host__ __device__ Word *diff32() const { return (Word *)diff; }
+};
+
+// ---- a lane's four entries ------------------------------------------------------------------------------------------
+// Encode: entry j (where ok[j]; they are the first of the four) has index x[j]; end = 1 + the index of the entry before
+// the four (0: none).  Returns the code dword (0 in the bytes of the entries that are not there); fl[j]: entry j is
+// there and escaped, g[j] its gap.
+__device__ __forceinline__ uint32_t cwire_encode4(const uint32_t x[4], const bool ok[4], uint32_t end, uint32_t g[4], bool fl[4]) {
+    uint32_t word = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        g[j] = x[j] - end;
+        end = x[j] + 1u;
+        fl[j] = ok[j] && g[j] >= 255u;
+        word |= (ok[j] ? (g[j] < 255u ? g[j] : 255u) : 0u) << (8 * j);
+    }
+    return word;
+}
+
+// Flags -> how many the lanes below this one hold (ballot + popcount); wtot: how many the wave holds
+__device__ __forceinline__ uint32_t cwire_rank4(const bool fl[4], uint32_t &wtot) {
+    const uint64_t lt = (1ull << (threadIdx.x & 63u)) - 1ull;
+    uint32_t before = 0;
+    wtot = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const uint64_t m = __ballot(fl[j]);
+        before += (uint32_t)__popcll(m & lt);
+        wtot += (uint32_t)__popcll(m);
+    }
+    return before;
+}
+
+// The escaped gaps of the four go to esc[rank], esc[rank + 1], ... (only input that changed between the launches of an
+// encoder breaks rank < e)
+template <bool NONTEMPORAL>
+__device__ __forceinline__ void cwire_store_escapes(uint32_t *esc, uint32_t e, uint32_t rank, const uint32_t g[4], const bool fl[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        if (fl[j]) {
+            if (rank < e) {
+                if (NONTEMPORAL) __builtin_nontemporal_store(g[j], esc + rank);
+                else esc[rank] = g[j];
+            }
+            rank++;
+        }
+}
+
+// Decode, first half: the escape codes (fl[j]) among the live entries (in[j]) of a code dword -> those of the lanes
+// below, and of the wave
+__device__ __forceinline__ uint32_t cwire_escapes_before(uint32_t word, const bool in[4], bool fl[4], uint32_t &wtot) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) fl[j] = in[j] && ((word >> (8 * j)) & 255u) == 255u;
+    return cwire_rank4(fl, wtot);
+}
+
+// Decode, second half: rank = escapes of the frame before the lane's.  inc[j] = g + 1 of the live entries, the running
+// index's increments; rk[j] the escape rank at entry j.  An escape ranked at or past e is BAD: it adds nothing (inc 0).
+// Returns the sum of the four increments.
+__device__ __forceinline__ uint32_t cwire_decode4(uint32_t word, const bool in[4], const bool fl[4], uint32_t rank, uint32_t e, const uint32_t *esc,
+                                                  uint32_t inc[4], bool bad[4], uint32_t rk[4]) {
+    uint32_t lsum = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        inc[j] = 0;
+        bad[j] = false;
+        rk[j] = rank;
+        if (in[j]) {
+            uint32_t g = (word >> (8 * j)) & 255u;
+            if (fl[j]) {
+                if (rank < e) g = esc[rank];
+                else bad[j] = true;
+                rank++;
+            }
+            inc[j] = bad[j] ? 0u : g + 1u;
+        }
+        lsum += inc[j];
+    }
+    return lsum;
+}
+
+// ---- workgroup scans (NW waves; T = uint32_t or uint64_t) -----------------------------------------------------------
+template <class T>
+__device__ __forceinline__ T wave_inclusive_scan_shfl(T v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 1; k < 64; k <<= 1) {
+        const T u = __shfl_up(v, k, 64);
+        if (lane >= k) v += u;
+    }
+    return v;
+}
+
+// carry + the totals of the waves below this one; carry += the totals of all waves.  Lane src_lane of a wave holds its
+// total in v.  s_wave: NW words of LDS that the caller owns and does not hand in again before another barrier (it
+// alternates two, or ends its round with one).  One barrier; a single wave needs neither the barrier nor s_wave.
+template <int NW, class T>
+__device__ __forceinline__ T block_waves_before(T v, int src_lane, T *s_wave, T &carry) {
+    T before = carry;
+    if (NW == 1) {
+        carry += (T)__shfl(v, src_lane, 64);
+        return before;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == src_lane) s_wave[wave] = v;
+    __syncthreads();
+    for (int w = 0; w < wave; w++) before += s_wave[w];
+#pragma unroll NW <= 4 ? NW : 1   // (sixteen 64-bit totals in flight at once cost a 1024-thread kernel a wave of occupancy)
+    for (int w = 0; w < NW; w++) carry += s_wave[w];
+    return before;
+}
+
+// carry + the values of the threads below this one; carry += all values
+template <int NW, class T>
+__device__ __forceinline__ T block_exclusive_scan(T v, T *s_wave, T &carry) {
+    const T incl = wave_inclusive_scan_shfl(v);
+    return block_waves_before<NW>(incl, 63, s_wave, carry) + incl - v;
+}
+
+// frame_pos[0 .. nframes] = exclusive scan of the record sizes, by ONE workgroup of THREADS threads.  header(t, n, e)
+// gives frame t's header, placed(t, pos, n, e) is told where it lies.  Each is called exactly once per frame, by one
+// thread, header first, and may have side effects (k_cwire_scan's turns the emit kernel's escape counts into their
+// prefix while it sums them); n and e enter header as 0.
+template <int THREADS, class Header, class Placed>
+__device__ __forceinline__ void cwire_scan_frame_pos(int nframes, uint64_t *frame_pos, Header header, Placed placed) {
+    __shared__ uint64_t s_wave[THREADS / 64];
+    const int tid = threadIdx.x;
+    uint64_t carry = 0;
+    for (int t0 = 0; t0 < nframes; t0 += THREADS) {
+        const int t = t0 + tid;
+        uint32_t n = 0, e = 0;
+        if (t < nframes) header(t, n, e);
+        const uint64_t rec = t < nframes ? cwire_record_bytes(n, e) : 0;
+        const uint64_t pos = block_exclusive_scan<THREADS / 64>(rec, s_wave, carry);
+        if (t < nframes) {
+            frame_pos[t] = pos;
+            placed(t, pos, n, e);
+        }
+        __syncthreads();   // s_wave is rewritten by the next round
+    }
+    if (tid == 0) frame_pos[nframes] = carry;
+}
+
+}  // namespace mi355
+#endif

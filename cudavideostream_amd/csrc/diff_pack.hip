@@ -33,6 +33,7 @@
 #include <cstdio>
 #include <vector>
 
+#include "cwire_common.h"
 #include "pack_common.h"
 
 namespace mi355 {
@@ -776,14 +777,45 @@ __device__ __forceinline__ void expand_group(const ExpandArgs &a, uint32_t mx, u
 }
 
 // The tile path.  tinfo[i] = {byte offset of the first code, of the first record, flagged bytes, candidates} of the
-// item's tile i; xs0 = byte index of the item's first byte, dst0 = entries of the batch before the item.
+// item's tile i; xs0 = byte index of the item's first byte.
 // A tile needs two dependent loads (its codes, then the records its codes name); the loop keeps the codes two tiles
 // ahead and the records one tile ahead of the tile it expands, so a wave waits for memory once per item, not twice per
 // tile (an item of a dense region is 16 such tiles: without the look-ahead it took ~50 us, and a scene change late in
 // a batch held the whole grid up).
+// Where the entries go is the SINK's business:
+//   sink.flush(stage, first, count, xs0)   entries [first, first + count) of the item, staged at stage[0 .. count), leave;
+//   Sink::kFullTileDirect                  a tile with every byte flagged bypasses the stage (the stage is emptied first):
+//   sink.full_tile_fits(carry) / sink.store_full_tile(i, carry, xs0, lane, r0)   its 1024 entries from item entry `carry` on.
+// The arrays and the sender's stream: what k_expand's WIRE branch prepared (flush_entries)
 template <bool WIRE>
+struct EntrySink {
+    static constexpr bool kFullTileDirect = true;
+    const ExpandArgs &a;
+    uint32_t dst0;        // entries of the batch before the item
+    uint8_t *w_xs, *w_df;
+    size_t w_room;
+    __device__ __forceinline__ void flush(const uint32_t *stage, uint32_t first, uint32_t count, uint32_t xs0) {
+        flush_entries<WIRE>(a, stage, first, count, xs0, dst0, w_xs, w_df, w_room);
+    }
+    __device__ __forceinline__ bool full_tile_fits(uint32_t carry) const {
+        return WIRE ? w_room != 0 : (size_t)dst0 + carry + kTileBytes <= a.capacity;
+    }
+    // all 64 lanes carry 16 bytes: record `lane` of the tile holds the differences of its bytes 16 lane .. 16 lane + 15
+    // (one wave-contiguous KiB); the 1024 indices are consecutive and leave as four wave-contiguous KiB
+    __device__ __forceinline__ void store_full_tile(uint32_t i, uint32_t carry, uint32_t xs0, uint32_t lane, u32x4 r0) {
+        uint8_t *xsp = WIRE ? w_xs + 4 * (size_t)carry : (uint8_t *)(a.out_xs + (size_t)dst0 + carry);
+        uint8_t *dfp = WIRE ? w_df + carry : a.out_diff + (size_t)dst0 + carry;
+        const uint32_t x = xs0 + (i << 10) + 4u * lane;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++)
+            store_out4<true>(xsp + 1024 * k + 16 * lane, x + 256 * k, x + 256 * k + 1, x + 256 * k + 2, x + 256 * k + 3);
+        store_out4<true>(dfp + 16 * lane, r0.x, r0.y, r0.z, r0.w);
+    }
+};
+
+template <class Sink>
 __device__ __forceinline__ void expand_tiles(const ExpandArgs &a, const uint4 *tinfo, uint32_t *stage, uint32_t lane, uint32_t xs0,
-                                             uint32_t dst0, uint8_t *w_xs, uint8_t *w_df, size_t w_room) {
+                                             Sink sink) {
     const __amdgpu_buffer_rsrc_t codes = make_rsrc(a.codes, a.codes_bytes), recs = make_rsrc(a.rec, a.rec_bytes);
     // loads beyond the item (i >= 16) or without a candidate carry an offset outside the buffer: they return 0 and read nothing
     // tinfo[i].w = candidates | multi-byte lanes << 16.  A DENSE tile (64 multi-byte lanes) has records only (k_diff_pack,
@@ -813,23 +845,20 @@ __device__ __forceinline__ void expand_tiles(const ExpandArgs &a, const uint4 *t
         const uint32_t nc = ncm & 0xffffu;
         const bool dense = (ncm >> 16) == 64u;   // records only, no codes
         if (nc != 0u) {
-            const bool full = bytes == kTileBytes;   // every byte of the tile flagged: its 64 records are the difference bytes
+            // every byte of the tile flagged: its 64 records are the difference bytes
+            const bool full = Sink::kFullTileDirect && bytes == kTileBytes;
             if (full || carry - flushed + bytes > kWStage) {   // make room (a full tile goes straight out: empty the stage first)
                 lds_handoff();
-                flush_entries<WIRE>(a, stage, flushed, carry - flushed, xs0, dst0, w_xs, w_df, w_room);
+                sink.flush(stage, flushed, carry - flushed, xs0);
                 lds_handoff();   // the stage is rewritten from its start
                 flushed = carry;
             }
-            if (full && (WIRE ? w_room != 0 : (size_t)dst0 + carry + kTileBytes <= a.capacity)) {
-                // all 64 lanes carry 16 bytes: record `lane` of the tile holds the differences of its bytes 16 lane .. 16 lane + 15
-                // (one wave-contiguous KiB); the 1024 indices are consecutive and leave as four wave-contiguous KiB
-                uint8_t *xsp = WIRE ? w_xs + 4 * (size_t)carry : (uint8_t *)(a.out_xs + (size_t)dst0 + carry);
-                uint8_t *dfp = WIRE ? w_df + carry : a.out_diff + (size_t)dst0 + carry;
-                const uint32_t x = xs0 + (i << 10) + 4u * lane;
-#pragma unroll
-                for (uint32_t k = 0; k < 4; k++)
-                    store_out4<true>(xsp + 1024 * k + 16 * lane, x + 256 * k, x + 256 * k + 1, x + 256 * k + 2, x + 256 * k + 3);
-                store_out4<true>(dfp + 16 * lane, r0.x, r0.y, r0.z, r0.w);
+            bool direct = false;
+            if constexpr (Sink::kFullTileDirect) {
+                direct = full && sink.full_tile_fits(carry);
+                if (direct) sink.store_full_tile(i, carry, xs0, lane, r0);
+            }
+            if (direct) {
                 flushed = carry + kTileBytes;
             } else {
                 const uint4 r = make_uint4(r0.x, r0.y, r0.z, r0.w);
@@ -846,7 +875,7 @@ __device__ __forceinline__ void expand_tiles(const ExpandArgs &a, const uint4 *t
         c0 = c1; c1 = c2; r0 = r1;
     }
     lds_handoff();
-    flush_entries<WIRE>(a, stage, flushed, carry - flushed, xs0, dst0, w_xs, w_df, w_room);
+    sink.flush(stage, flushed, carry - flushed, xs0);
 }
 
 template <bool WIRE>
@@ -914,7 +943,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         uint4 *const s_tinfo = reinterpret_cast<uint4 *>(s_list);
         if (lane < kWTiles) s_tinfo[lane] = make_uint4(m.x, m.y, m.z, m.w);   // .w = candidates | multi-byte lanes << 16
         lds_handoff();
-        expand_tiles<WIRE>(a, s_tinfo, s_stage, lane, xs0, dst0, w_xs, w_df, w_room);
+        EntrySink<WIRE> sink{a, dst0, w_xs, w_df, w_room};
+        expand_tiles(a, s_tinfo, s_stage, lane, xs0, sink);
         return;
     }
     // quads when every four neighbouring tiles fill at most the 64 lanes of a round (all items of a webcam-like frame away
@@ -953,9 +983,10 @@ hipError_t launch_expand(const ExpandArgs &a, int nframes, hipStream_t s) {
 //                  and last bytes come from the maps of its records 0 and 63.
 //   k_cwire_fscan  (grid T): per frame, the gaps between consecutive non-empty items (and from -1 to the first entry), each
 //                  item's escape rank and the frame's escapes e_t.  No workgroup looks at another's result.
-//   k_cwire_place  (one workgroup): frame_pos = exclusive scan of 8 + 2 pad4(n_t) + 4 e_t; the header {n, e} and the zero
+//   k_cwire_place  (one workgroup): frame_pos = exclusive scan of the record sizes (cwire_common.h); the header {n, e} and the zero
 //                  pad bytes of every frame that fits.
-//   k_expand_cwire (grid as k_expand): the item's entries through the LDS stage as on the tile path of expand_tiles, then
+//   k_expand_cwire (grid as k_expand): the item's entries through the LDS stage by expand_tiles (every item: there is no
+//                  group path here), then
 //                  its codes, escapes and differences at their places in the record (byte-aligned, non-temporal stores).
 // Item word (k_cwire_items -> k_cwire_fscan): {first byte, last byte, escapes inside the item, entries}; k_cwire_fscan
 // rewrites it for the expansion as {first byte, 1 + the frame's entry before the item (0: none), escapes of the frame before
@@ -1049,54 +1080,29 @@ __device__ __forceinline__ void store_byte_nt(uint8_t *p, uint32_t v) { __builti
 // esc == nullptr: every frame is empty (e = 0)
 __global__ __launch_bounds__(kCwPlaceThreads) void k_cwire_place(const uint32_t *offsets, const uint32_t *esc, int nframes,
                                                                  uint64_t *frame_pos, uint8_t *out, uint64_t capacity) {
-    __shared__ uint64_t s_wave[kCwPlaceThreads / 64];
-    __shared__ uint64_t s_carry;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (int t0 = 0; t0 < nframes; t0 += kCwPlaceThreads) {
-        const int t = t0 + tid;
-        uint64_t rec = 0, n = 0, e = 0;
-        if (t < nframes) {
+    cwire_scan_frame_pos<kCwPlaceThreads>(
+        nframes, frame_pos,
+        [&](int t, uint32_t &n, uint32_t &e) {
             n = offsets[t + 1] - offsets[t];
             e = esc ? esc[t] : 0u;
-            rec = 8 + 2 * ((n + 3) & ~3ull) + 4 * e;
-        }
-        uint64_t incl = rec;   // inclusive scan of the record sizes over the wave, then over the waves
-#pragma unroll
-        for (int k = 1; k < 64; k <<= 1) {
-            const uint64_t v = __shfl_up(incl, k, 64);
-            if (lane >= k) incl += v;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        uint64_t before = s_carry;
-        for (int w = 0; w < wave; w++) before += s_wave[w];
-        const uint64_t pos = before + incl - rec;
-        if (t < nframes) {
-            frame_pos[t] = pos;
-            if (pos + rec <= capacity) {   // the frame fits: its header and pad bytes (k_expand_cwire writes the rest)
-                uint32_t *hdr = (uint32_t *)(out + pos);
-                __builtin_nontemporal_store((uint32_t)n, hdr);
-                __builtin_nontemporal_store((uint32_t)e, hdr + 1);
-                const uint64_t D = (n + 3) & ~3ull;
-                for (uint64_t k = n; k < D; k++) {
-                    store_byte_nt(out + pos + 8 + k, 0u);
-                    store_byte_nt(out + pos + 8 + D + 4 * e + k, 0u);
-                }
+        },
+        [&](int, uint64_t pos, uint32_t n, uint32_t e) {
+            if (pos + cwire_record_bytes(n, e) > capacity) return;
+            // the frame fits: its header and pad bytes (k_expand_cwire writes the rest)
+            uint32_t *hdr = (uint32_t *)(out + pos);
+            __builtin_nontemporal_store(n, hdr);
+            __builtin_nontemporal_store(e, hdr + 1);
+            const CwireSections<uint8_t> sec(out, pos, n, e);
+            for (uint64_t k = n; k < cwire_pad4(n); k++) {
+                store_byte_nt(sec.code + k, 0u);
+                store_byte_nt(sec.diff + k, 0u);
             }
-        }
-        __syncthreads();
-        if (tid == kCwPlaceThreads - 1) s_carry = before + incl;
-        __syncthreads();
-    }
-    if (tid == 0) frame_pos[nframes] = s_carry;
+        });
 }
 
 // Where the entries of an item go in its frame's record (wave-uniform)
 struct CwireCursor {
-    uint8_t *code, *diff;   // the frame's code and difference sections
-    uint32_t *esc;          // its escapes
+    CwireSections<uint8_t> sec;   // the frame's record
     uint32_t n, e;          // its header
     uint32_t entry;         // rank in the frame of the next entry to store
     uint32_t end;           // 1 + the index of the entry before it (0: none), so that its gap is index - end
@@ -1108,52 +1114,46 @@ struct CwireCursor {
 __device__ __forceinline__ void flush_cwire(const uint32_t *stage, uint32_t count, uint32_t xs0, CwireCursor &cur) {
     if (count == 0u) return;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t lt = (1ull << lane) - 1ull;
     for (uint32_t b0 = 0; b0 < count; b0 += 256u) {
         const uint32_t i0 = b0 + 4u * lane;
         const uint4 q = *reinterpret_cast<const uint4 *>(stage + (i0 < kWStage ? i0 : 0u));
         const uint32_t v[4] = {q.x, q.y, q.z, q.w};
-        uint32_t pe = i0 == 0u ? cur.end : xs0 + (stage[(i0 - 1u) & (kWStage - 1u)] >> 8) + 1u;
-        uint32_t word = 0, dw = 0, g[4];
+        uint32_t x[4], g[4], dw = 0;
         bool ok[4], fl[4];
-        uint32_t before = 0, wtot = 0;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             ok[j] = i0 + j < count && cur.entry + i0 + j < cur.n;
-            const uint32_t x = xs0 + (v[j] >> 8);
-            g[j] = x - pe;
-            pe = x + 1u;
-            fl[j] = ok[j] && g[j] >= 255u;
-            word |= (fl[j] ? 255u : (g[j] & 255u)) << (8 * j);
+            x[j] = xs0 + (v[j] >> 8);
             dw |= (v[j] & 255u) << (8 * j);
-            const uint64_t mk = __ballot(fl[j]);
-            before += (uint32_t)__popcll(mk & lt);
-            wtot += (uint32_t)__popcll(mk);
         }
+        const uint32_t word = cwire_encode4(x, ok, i0 == 0u ? cur.end : xs0 + (stage[(i0 - 1u) & (kWStage - 1u)] >> 8) + 1u, g, fl);
+        uint32_t wtot;
+        const uint32_t before = cwire_rank4(fl, wtot);
         const uint32_t r = cur.entry + i0;
         if (ok[3]) {
-            store_out1(cur.code + r, word);
-            store_out1(cur.diff + r, dw);
+            store_out1(cur.sec.code + r, word);
+            store_out1(cur.sec.diff + r, dw);
         } else {
 #pragma unroll
             for (int j = 0; j < 3; j++)
                 if (ok[j]) {
-                    store_byte_nt(cur.code + r + j, word >> (8 * j));
-                    store_byte_nt(cur.diff + r + j, dw >> (8 * j));
+                    store_byte_nt(cur.sec.code + r + j, word >> (8 * j));
+                    store_byte_nt(cur.sec.diff + r + j, dw >> (8 * j));
                 }
         }
-        uint32_t rank = cur.erank + before;
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            if (fl[j]) {
-                if (rank < cur.e) __builtin_nontemporal_store(g[j], cur.esc + rank);
-                rank++;
-            }
+        cwire_store_escapes<true>(cur.sec.esc32(), cur.e, cur.erank + before, g, fl);
         cur.erank += wtot;
     }
     cur.entry += count;
     cur.end = xs0 + (stage[count - 1u] >> 8) + 1u;
 }
+
+// expand_tiles' sink: a full tile, too, goes through the stage (every gap but its first is 0)
+struct CwireSink {
+    static constexpr bool kFullTileDirect = false;
+    CwireCursor &cur;
+    __device__ __forceinline__ void flush(const uint32_t *stage, uint32_t, uint32_t count, uint32_t xs0) { flush_cwire(stage, count, xs0, cur); }
+};
 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_expand_cwire(const CwireDirectArgs a) {
     __shared__ __attribute__((aligned(16))) uint4 s_tinfo[kWTiles];
@@ -1170,65 +1170,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     const u32x4 mq = __builtin_amdgcn_raw_buffer_load_b128(metas, lane < kWTiles ? (sub * kWTiles + lane) * 16u : kOOB, 0, 0);
     const uint32_t ngroups = (ntiles + kXTiles - 1) / kXTiles;
     const uint32_t off_t = a.x.offsets[t], n = a.x.offsets[t + 1] - off_t;
-    const uint64_t D = (n + 3u) & ~3u;
-    CwireCursor cur;
-    cur.n = n;
-    cur.e = (uint32_t)((p1 - p0 - 8 - 2 * D) / 4);
-    cur.code = a.cwire + p0 + 8;
-    cur.esc = (uint32_t *)(cur.code + D);
-    cur.diff = cur.code + D + 4 * (uint64_t)cur.e;
+    const uint32_t e = cwire_record_escapes(p1 - p0, n);
+    CwireCursor cur{CwireSections<uint8_t>(a.cwire, p0, n, e), n, e, 0u, 0u, 0u};
     cur.entry = a.x.roff[(size_t)t * ngroups * 4u + sub];   // entries of the frame before the item
     cur.end = item.y;
     cur.erank = item.z;
     if (lane < kWTiles) s_tinfo[lane] = make_uint4(mq.x, mq.y, mq.z, mq.w);
     lds_handoff();
     const uint32_t xs0 = sub * kWTiles * kTileBytes;
-    // the tile path of expand_tiles (a full tile, too, goes through the stage: every gap but its first is 0)
-    const __amdgpu_buffer_rsrc_t codes = make_rsrc(a.x.codes, a.x.codes_bytes), recs = make_rsrc(a.x.rec, a.x.rec_bytes);
-    auto load_code = [&](uint32_t i) {
-        const uint4 ti = s_tinfo[i & (kWTiles - 1u)];
-        const bool dense = (ti.w >> 16) == 64u;
-        return __builtin_amdgcn_raw_buffer_load_b32(codes, (i < kWTiles && !dense && lane < (ti.w & 0xffffu)) ? ti.x + 4u * lane : kOOB, 0, 0);
-    };
-    auto load_rec = [&](uint32_t i, uint32_t c) {
-        const uint4 ti = s_tinfo[i & (kWTiles - 1u)];
-        const uint32_t m16 = c & 0xffffu;
-        const bool dense = (ti.w >> 16) == 64u;
-        const uint32_t off = dense ? ti.y + 16u * lane : ((m16 & (m16 - 1u)) ? ti.y + 16u * ((c >> 16) & 0xffu) : kOOB);
-        return __builtin_amdgcn_raw_buffer_load_b128(recs, i < kWTiles ? off : kOOB, 0, 0);
-    };
-    uint32_t carry = 0, flushed = 0;   // entries of the item expanded so far / already stored (wave-uniform)
-    uint32_t c0 = load_code(0), c1 = load_code(1);
-    u32x4 r0 = load_rec(0, c0);
-#pragma unroll 1
-    for (uint32_t i = 0; i < kWTiles; i++) {
-        const uint32_t c2 = load_code(i + 2u);
-        const u32x4 r1 = load_rec(i + 1u, c1);
-        const uint4 ti = s_tinfo[i];
-        const uint32_t ncm = (uint32_t)__builtin_amdgcn_readfirstlane((int)ti.w), bytes = (uint32_t)__builtin_amdgcn_readfirstlane((int)ti.z);
-        const uint32_t nc = ncm & 0xffffu;
-        const bool dense = (ncm >> 16) == 64u;
-        if (nc != 0u) {
-            if (carry - flushed + bytes > kWStage) {
-                lds_handoff();
-                flush_cwire(s_stage, carry - flushed, xs0, cur);
-                lds_handoff();   // the stage is rewritten from its start
-                flushed = carry;
-            }
-            const uint4 r = make_uint4(r0.x, r0.y, r0.z, r0.w);
-            const uint32_t m16 = dense ? record_map16(r) : (c0 & 0xffffu);
-            const uint32_t cnt = (uint32_t)__builtin_popcount(m16);
-            const uint32_t e = carry - flushed + (uint32_t)wave_inclusive_scan((int)cnt) - cnt;
-            const uint32_t src16 = (i << 10) + (dense ? lane * 16u : ((c0 >> 20) & 0x3f0u));
-            if (cnt == 1u) s_stage[e] = ((src16 + (uint32_t)__builtin_ctz(m16)) << 8) | ((c0 >> 16) & 0xffu);
-            const bool multi = cnt > 1u;
-            if (__ballot(multi)) walk_records(multi ? m16 : 0u, e, src16, r, s_stage, lane);
-            carry += bytes;
-        }
-        c0 = c1; c1 = c2; r0 = r1;
-    }
-    lds_handoff();
-    flush_cwire(s_stage, carry - flushed, xs0, cur);
+    CwireSink sink{cur};
+    expand_tiles(a.x, s_tinfo, s_stage, lane, xs0, sink);
 }
 
 hipError_t launch_expand_cwire(const CwireDirectArgs &a, int nframes, hipStream_t s) {

@@ -10,7 +10,7 @@
 //
 // The first two are index-driven byte scatter/copy: HBM-latency work with 5 bytes of traffic per entry, no
 // arithmetic worth naming.
-#include "internal.h"
+#include "cwire_common.h"
 
 namespace mi355 {
 
@@ -158,8 +158,7 @@ hipError_t launch_merge(const MergeArgs &a, uint32_t *out_offsets, hipStream_t s
 
 
 // ---- compact wire format (include/mi355diff.h, "compact wire"): encoder and decoder ------------------------------
-// Record of frame t, 4-aligned, at frame_pos[t]:  u32 n | u32 e | u8 code[pad4(n)] | u32 esc[e] | u8 diff[pad4(n)]
-// with g_0 = xs[0], g_k = xs[k] - xs[k-1] - 1, code[k] = min(g_k, 255) and esc[] the g_k of the codes 255, in order.
+// The record, its arithmetic and the steps all of these kernels share: cwire_common.h.
 // The encoder is three launches, none of which waits on another workgroup:
 //   k_cwire_count (grid (bpf, T)): workgroup (b, t) owns a contiguous range of frame t's code dwords and counts its
 //                                  escapes into cnt[t*bpf + b];
@@ -178,23 +177,15 @@ __device__ __forceinline__ bool cwire_frame_ok(const uint32_t *off, int t, uint6
 
 // the escape flags and codes of the (up to) 4 entries of code dword d of a frame whose entries start at xs
 __device__ __forceinline__ uint32_t cwire_codes(const int32_t *xs, uint32_t n, uint32_t d, uint32_t g[4], bool esc[4]) {
-    uint32_t word = 0;
     const uint32_t i0 = 4 * d;
-    uint32_t prev = i0 ? (uint32_t)xs[i0 - 1] : 0;
+    uint32_t x[4];
+    bool ok[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        const uint32_t i = i0 + j;
-        g[j] = 0;
-        esc[j] = false;
-        if (i < n) {
-            const uint32_t x = (uint32_t)xs[i];
-            g[j] = i ? x - prev - 1u : x;
-            prev = x;
-            esc[j] = g[j] >= 255u;
-            word |= (esc[j] ? 255u : g[j]) << (8 * j);
-        }
+        ok[j] = i0 + j < n;
+        x[j] = ok[j] ? (uint32_t)xs[i0 + j] : 0u;
     }
-    return word;
+    return cwire_encode4(x, ok, i0 ? (uint32_t)xs[i0 - 1] + 1u : 0u, g, esc);
 }
 
 __global__ __launch_bounds__(256) void k_cwire_count(const uint32_t *offsets, const int32_t *xs, uint64_t entries_capacity,
@@ -204,7 +195,7 @@ __global__ __launch_bounds__(256) void k_cwire_count(const uint32_t *offsets, co
     const uint64_t total = offsets[nframes];
     uint32_t lo, n;
     if (total > entries_capacity || !cwire_frame_ok(offsets, t, total, &lo, &n)) return;
-    const uint64_t D = (n + 3u) / 4u;
+    const uint64_t D = cwire_dwords(n);
     const uint32_t d0 = (uint32_t)(D * b / bpf), d1 = (uint32_t)(D * (b + 1) / bpf);
     uint32_t mine = 0;   // wave-uniform
     for (uint32_t base = d0; base < d1; base += 256) {
@@ -225,10 +216,8 @@ constexpr int kCwScanThreads = 1024;
 __global__ __launch_bounds__(kCwScanThreads) void k_cwire_scan(const uint32_t *offsets, uint64_t entries_capacity, int nframes,
                                                                int bpf, uint32_t *cnt, uint64_t *frame_pos) {
     extern __shared__ uint32_t s_cnt[];   // nframes * bpf
-    __shared__ uint64_t s_wave[kCwScanThreads / 64];
-    __shared__ uint64_t s_carry;
     __shared__ int s_bad;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const uint64_t total = offsets[nframes];
     if (tid == 0) s_bad = total > entries_capacity;
     __syncthreads();
@@ -242,41 +231,22 @@ __global__ __launch_bounds__(kCwScanThreads) void k_cwire_scan(const uint32_t *o
     }
     const int ncnt = nframes * bpf;
     for (int i = tid; i < ncnt; i += kCwScanThreads) s_cnt[i] = cnt[i];
-    if (tid == 0) s_carry = 0;
     __syncthreads();
     if (s_bad) {
         if (tid == 0) frame_pos[nframes] = ~0ull;
         return;
     }
-    for (int t0 = 0; t0 < nframes; t0 += kCwScanThreads) {
-        const int t = t0 + tid;
-        uint64_t rec = 0;
-        if (t < nframes) {
-            uint32_t e = 0;
+    cwire_scan_frame_pos<kCwScanThreads>(
+        nframes, frame_pos,
+        [&](int t, uint32_t &n, uint32_t &e) {
             for (int b = 0; b < bpf; b++) {   // exclusive prefix of the frame's escapes per workgroup of the emit kernel
                 const uint32_t c = s_cnt[t * bpf + b];
                 cnt[(size_t)t * bpf + b] = e;
                 e += c;
             }
-            const uint64_t n = offsets[t + 1] - offsets[t];
-            rec = 8 + 2 * ((n + 3) & ~3ull) + 4 * (uint64_t)e;
-        }
-        uint64_t incl = rec;   // inclusive scan of the record sizes over the wave, then over the waves
-#pragma unroll
-        for (int k = 1; k < 64; k <<= 1) {
-            const uint64_t v = __shfl_up(incl, k, 64);
-            if (lane >= k) incl += v;
-        }
-        if (lane == 63) s_wave[wave] = incl;
-        __syncthreads();
-        uint64_t before = s_carry;
-        for (int w = 0; w < wave; w++) before += s_wave[w];
-        if (t < nframes) frame_pos[t] = before + incl - rec;
-        __syncthreads();
-        if (tid == kCwScanThreads - 1) s_carry = before + incl;
-        __syncthreads();
-    }
-    if (tid == 0) frame_pos[nframes] = s_carry;
+            n = offsets[t + 1] - offsets[t];
+        },
+        [](int, uint64_t, uint32_t, uint32_t) {});
 }
 
 __global__ __launch_bounds__(256) void k_cwire_emit(const uint32_t *offsets, const int32_t *xs, const uint8_t *diff,
@@ -284,17 +254,16 @@ __global__ __launch_bounds__(256) void k_cwire_emit(const uint32_t *offsets, con
                                                     const uint64_t *frame_pos, uint8_t *out, uint64_t capacity_bytes) {
     __shared__ uint32_t s_wave[2][4];
     const int t = blockIdx.y, b = blockIdx.x, bpf = gridDim.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t total = offsets[nframes];
     uint32_t lo, n;
     if (total > entries_capacity || frame_pos[nframes] == ~0ull || !cwire_frame_ok(offsets, t, total, &lo, &n)) return;
     const uint64_t fp0 = frame_pos[t], fp1 = frame_pos[t + 1];
     if (fp1 > capacity_bytes) return;   // the frame does not fit: skipped whole
-    const uint64_t D = (n + 3u) / 4u;
-    const uint64_t ebytes = fp1 - fp0 - 8 - 8 * D;   // 4 e
-    const uint32_t e = (uint32_t)(ebytes / 4);
+    const uint64_t D = cwire_dwords(n);
+    const uint32_t e = cwire_record_escapes(fp1 - fp0, n);
     uint32_t *hdr = (uint32_t *)(out + fp0);
-    uint32_t *code = hdr + 2, *esc = code + D, *dif = esc + e;
+    const CwireSections<uint8_t> sec(out, fp0, n, e);
+    uint32_t *code = sec.code32(), *esc = sec.esc32(), *dif = sec.diff32();
     if (b == 0 && threadIdx.x == 0) {
         hdr[0] = n;
         hdr[1] = e;
@@ -302,7 +271,6 @@ __global__ __launch_bounds__(256) void k_cwire_emit(const uint32_t *offsets, con
     const int32_t *fx = xs + lo;
     const uint8_t *fd = diff + lo;
     const uint32_t d0 = (uint32_t)(D * b / bpf), d1 = (uint32_t)(D * (b + 1) / bpf);
-    const uint64_t lt = (1ull << lane) - 1ull;
     uint32_t carry = cnt[(size_t)t * bpf + b];   // escapes of the frame before this workgroup's range
     int buf = 0;
     for (uint32_t base = d0; base < d1; base += 256, buf ^= 1) {
@@ -317,28 +285,13 @@ __global__ __launch_bounds__(256) void k_cwire_emit(const uint32_t *offsets, con
             for (int j = 0; j < 4; j++)
                 if (4 * d + j < n) dw |= (uint32_t)fd[4 * d + j] << (8 * j);
         }
-        uint32_t before = 0, wtot = 0;   // escapes of the lanes below this one in the wave, and of the whole wave
-        uint64_t m[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            m[j] = __ballot(fl[j]);
-            before += (uint32_t)__popcll(m[j] & lt);
-            wtot += (uint32_t)__popcll(m[j]);
-        }
-        if (lane == 0) s_wave[buf][wave] = wtot;
-        __syncthreads();
-        uint32_t rank = carry + before;
-        for (int w = 0; w < wave; w++) rank += s_wave[buf][w];
-        carry += s_wave[buf][0] + s_wave[buf][1] + s_wave[buf][2] + s_wave[buf][3];
+        uint32_t wtot;   // escapes of the lanes below this one in the wave, and of the whole wave
+        const uint32_t before = cwire_rank4(fl, wtot);
+        const uint32_t rank = block_waves_before<4>(wtot, 0, s_wave[buf], carry) + before;
         if (live) {
             code[d] = word;
             dif[d] = dw;
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                if (fl[j]) {
-                    if (rank < e) esc[rank] = g[j];   // (only input that changed between the launches breaks rank < e)
-                    rank++;
-                }
+            cwire_store_escapes<false>(esc, e, rank, g, fl);
         }
     }
 }
@@ -365,68 +318,34 @@ hipError_t launch_cwire_encode(const uint32_t *offsets, const int32_t *xs, const
 
 // Decoder: one workgroup per frame, frames described by the host (positions follow from the headers the client read).
 // The frame's entries are scanned in tiles of 1024 (4 per lane): escape rank = escapes before the entry (ballot), index =
-// running sum of g + 1, minus 1.  Reads stay inside [pos, pos + 8 + 2 pad4(n) + 4 e); an escape ranked at or past e
+// running sum of g + 1, minus 1.  Reads stay inside the record [pos, pos + cwire_record_bytes(n, e)); an escape ranked at or past e
 // decodes to 0xFFFFFFFF (and adds nothing to the running sum); entries at or past `capacity` are not written.
 __global__ __launch_bounds__(256) void k_cwire_decode(const CwireDecodeArgs a) {
     __shared__ uint32_t s_esc[2][4], s_sum[2][4];
     const CwireFrame f = a.frame[blockIdx.x];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (threadIdx.x == 0) {
         if (a.first_frame + blockIdx.x == 0) a.offsets[0] = 0;
         a.offsets[a.first_frame + blockIdx.x + 1] = f.out + f.n;
     }
-    const uint32_t D = (f.n + 3u) / 4u;
-    const uint32_t *code = (const uint32_t *)(a.cwire + f.pos + 8);
-    const uint32_t *esc = code + D, *dif = esc + f.e;
-    const uint64_t lt = (1ull << lane) - 1ull;
+    const uint32_t D = cwire_dwords(f.n);
+    const CwireSections<const uint8_t> sec(a.cwire, f.pos, f.n, f.e);
+    const uint32_t *code = sec.code32(), *esc = sec.esc32(), *dif = sec.diff32();
     uint32_t carry_e = 0, carry_x = 0;
     int buf = 0;
     for (uint32_t base = 0; base < D; base += 256, buf ^= 1) {
         const uint32_t d = base + threadIdx.x;
         const bool live = d < D;
-        uint32_t word = live ? code[d] : 0u, dw = live ? dif[d] : 0u;
-        bool fl[4];
-        uint32_t before = 0, wtot = 0;
+        const uint32_t word = live ? code[d] : 0u, dw = live ? dif[d] : 0u;
+        bool in[4], fl[4];
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            fl[j] = live && 4 * d + j < f.n && ((word >> (8 * j)) & 255u) == 255u;
-            const uint64_t m = __ballot(fl[j]);
-            before += (uint32_t)__popcll(m & lt);
-            wtot += (uint32_t)__popcll(m);
-        }
-        if (lane == 0) s_esc[buf][wave] = wtot;
-        __syncthreads();
-        uint32_t rank = carry_e + before;
-        for (int w = 0; w < wave; w++) rank += s_esc[buf][w];
-        uint32_t inc[4], lsum = 0;
+        for (int j = 0; j < 4; j++) in[j] = live && 4 * d + j < f.n;
+        uint32_t wtot;
+        const uint32_t before = cwire_escapes_before(word, in, fl, wtot);
+        const uint32_t rank = block_waves_before<4>(wtot, 0, s_esc[buf], carry_e) + before;
+        uint32_t inc[4], rk[4];
         bool bad[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            inc[j] = 0;
-            bad[j] = false;
-            if (live && 4 * d + j < f.n) {
-                uint32_t g = (word >> (8 * j)) & 255u;
-                if (fl[j]) {
-                    if (rank < f.e) g = esc[rank];
-                    else bad[j] = true;
-                    rank++;
-                }
-                inc[j] = bad[j] ? 0u : g + 1u;
-            }
-            lsum += inc[j];
-        }
-        uint32_t incl = lsum;   // inclusive scan of the lanes' sums over the wave, then over the waves
-#pragma unroll
-        for (int k = 1; k < 64; k <<= 1) {
-            const uint32_t v = __shfl_up(incl, k, 64);
-            if (lane >= k) incl += v;
-        }
-        if (lane == 63) s_sum[buf][wave] = incl;
-        __syncthreads();
-        uint32_t x = carry_x + incl - lsum;
-        for (int w = 0; w < wave; w++) x += s_sum[buf][w];
-        carry_e += s_esc[buf][0] + s_esc[buf][1] + s_esc[buf][2] + s_esc[buf][3];
-        carry_x += s_sum[buf][0] + s_sum[buf][1] + s_sum[buf][2] + s_sum[buf][3];
+        const uint32_t lsum = cwire_decode4(word, in, fl, rank, f.e, esc, inc, bad, rk);
+        uint32_t x = block_exclusive_scan<4>(lsum, s_sum[buf], carry_x);
         if (live) {
 #pragma unroll
             for (int j = 0; j < 4; j++) {
@@ -475,24 +394,11 @@ __device__ __forceinline__ uint32_t cwa_wave_sum(uint32_t v) {
     return v;
 }
 
-__device__ __forceinline__ uint32_t cwa_wave_incl(uint32_t v, int lane) {
-#pragma unroll
-    for (int k = 1; k < 64; k <<= 1) {
-        const uint32_t u = __shfl_up(v, k, 64);
-        if (lane >= k) v += u;
-    }
-    return v;
-}
-
 __device__ __forceinline__ uint64_t cwa_ceil_tile(uint32_t x) { return ((uint64_t)x + kCwaTile - 1) / kCwaTile; }
 
-__device__ __forceinline__ const uint32_t *cwa_codes(const CwaArgs &a, const CwaFrame &f) {
-    return (const uint32_t *)(a.cwire + f.pos + 8);
+__device__ __forceinline__ CwireSections<const uint8_t> cwa_sections(const CwaArgs &a, const CwaFrame &f) {
+    return CwireSections<const uint8_t>(a.cwire, f.pos, f.n, f.e);
 }
-__device__ __forceinline__ const uint32_t *cwa_esc(const CwaArgs &a, const CwaFrame &f) {
-    return cwa_codes(a, f) + (f.n + 3u) / 4u;
-}
-__device__ __forceinline__ const uint32_t *cwa_dif(const CwaArgs &a, const CwaFrame &f) { return cwa_esc(a, f) + f.e; }
 
 // ---- headers -> ftab, chunk -> frame ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_cwa_table(const CwaArgs a, const CwaTableArgs h) {
@@ -510,7 +416,7 @@ __global__ __launch_bounds__(256) void k_cwa_facts(const CwaArgs a) {
     const CwaFrame f = a.ftab[t];
     const uint32_t k0 = (c - f.cbase) * kCwaChunk;
     const uint32_t k1 = f.n - k0 < kCwaChunk ? f.n : k0 + kCwaChunk;
-    const uint32_t *code = cwa_codes(a, f);
+    const uint32_t *code = cwa_sections(a, f).code32();
     uint32_t cnt = 0, sum = 0;
 #pragma unroll
     for (int i = 0; i < (int)(kCwaChunk / 1024); i++) {
@@ -544,23 +450,17 @@ __global__ __launch_bounds__(256) void k_cwa_facts(const CwaArgs a) {
 __global__ __launch_bounds__(256) void k_cwa_scan(const CwaArgs a, int field) {
     __shared__ uint32_t s_wave[2][4];
     const CwaFrame f = a.ftab[blockIdx.x];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint32_t carry = 0;
     int buf = 0;
     for (uint32_t i0 = 0; i0 < f.nc; i0 += 256, buf ^= 1) {
         const uint32_t i = i0 + threadIdx.x;
         uint4 *ch = a.chunk + f.cbase + i;
         const uint32_t v = i < f.nc ? (field == 0 ? ch->x : ch->z) : 0u;
-        const uint32_t incl = cwa_wave_incl(v, lane);
-        if (lane == 63) s_wave[buf][wave] = incl;
-        __syncthreads();
-        uint32_t before = carry;
-        for (int w = 0; w < wave; w++) before += s_wave[buf][w];
+        const uint32_t before = block_exclusive_scan<4>(v, s_wave[buf], carry);
         if (i < f.nc) {
-            if (field == 0) ch->y = before + incl - v;
-            else ch->z = before + incl - v;
+            if (field == 0) ch->y = before;
+            else ch->z = before;
         }
-        carry += s_wave[buf][0] + s_wave[buf][1] + s_wave[buf][2] + s_wave[buf][3];
     }
 }
 
@@ -572,7 +472,7 @@ __global__ __launch_bounds__(256) void k_cwa_escsum(const CwaArgs a) {
     const CwaFrame f = a.ftab[ch.w];
     const uint32_t r0 = ch.y < f.e ? ch.y : f.e;
     const uint32_t r1 = f.e - r0 < ch.x ? f.e : r0 + ch.x;
-    const uint32_t *esc = cwa_esc(a, f);
+    const uint32_t *esc = cwa_sections(a, f).esc32();
     uint32_t sum = 0;
     for (uint32_t r = r0 + threadIdx.x; r < r1; r += 256) sum += esc[r] + 1u;
     sum = cwa_wave_sum(sum);
@@ -588,56 +488,28 @@ __global__ __launch_bounds__(256) void k_cwa_dir(const CwaArgs a) {
     const uint4 ch = a.chunk[c];
     const uint32_t t = ch.w;
     const CwaFrame f = a.ftab[t];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t cl = c - f.cbase;
     const uint32_t k0 = cl * kCwaChunk;
     const uint32_t k1 = f.n - k0 < kCwaChunk ? f.n : k0 + kCwaChunk;
-    const uint32_t *code = cwa_codes(a, f), *esc = cwa_esc(a, f);
+    const CwireSections<const uint8_t> sec = cwa_sections(a, f);
+    const uint32_t *code = sec.code32(), *esc = sec.esc32();
     uint4 *dir = a.dir + (size_t)t * a.ntiles;
-    const uint64_t lt = (1ull << lane) - 1ull;
     uint32_t carry_e = ch.y, carry_x = ch.z;   // escape rank and running index (sum of g + 1) before the chunk
     int buf = 0;
     for (uint32_t base = k0; base < k1; base += 1024, buf ^= 1) {
         const uint32_t d = base / 4 + threadIdx.x;
         const bool live = 4 * d < k1;
         const uint32_t word = live ? code[d] : 0u;
-        bool fl[4];
-        uint32_t before = 0, wtot = 0;
+        bool in[4], fl[4];
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            fl[j] = live && 4 * d + j < k1 && ((word >> (8 * j)) & 255u) == 255u;
-            const uint64_t m = __ballot(fl[j]);
-            before += (uint32_t)__popcll(m & lt);
-            wtot += (uint32_t)__popcll(m);
-        }
-        if (lane == 0) s_esc[buf][wave] = wtot;
-        __syncthreads();
-        uint32_t rank = carry_e + before;
-        for (int w = 0; w < wave; w++) rank += s_esc[buf][w];
-        uint32_t inc[4], rk[4], lsum = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            inc[j] = 0;
-            rk[j] = rank;
-            if (live && 4 * d + j < k1) {
-                uint32_t g = (word >> (8 * j)) & 255u;
-                bool bad = false;
-                if (fl[j]) {
-                    if (rank < f.e) g = esc[rank];
-                    else bad = true;
-                    rank++;
-                }
-                inc[j] = bad ? 0u : g + 1u;
-            }
-            lsum += inc[j];
-        }
-        const uint32_t incl = cwa_wave_incl(lsum, lane);
-        if (lane == 63) s_sum[buf][wave] = incl;
-        __syncthreads();
-        uint32_t x = carry_x + incl - lsum;
-        for (int w = 0; w < wave; w++) x += s_sum[buf][w];
-        carry_e += s_esc[buf][0] + s_esc[buf][1] + s_esc[buf][2] + s_esc[buf][3];
-        carry_x += s_sum[buf][0] + s_sum[buf][1] + s_sum[buf][2] + s_sum[buf][3];
+        for (int j = 0; j < 4; j++) in[j] = live && 4 * d + j < k1;
+        uint32_t wtot;
+        const uint32_t before = cwire_escapes_before(word, in, fl, wtot);
+        const uint32_t rank = block_waves_before<4>(wtot, 0, s_esc[buf], carry_e) + before;
+        uint32_t inc[4], rk[4];
+        bool bad[4];
+        const uint32_t lsum = cwire_decode4(word, in, fl, rank, f.e, esc, inc, bad, rk);
+        uint32_t x = block_exclusive_scan<4>(lsum, s_sum[buf], carry_x);
         if (live) {
 #pragma unroll
             for (int j = 0; j < 4; j++) {
@@ -680,8 +552,9 @@ __device__ __forceinline__ CwaBlock cwa_block_load(const CwaArgs &a, const CwaFr
     const uint32_t d = k / 4 + lane;
     CwaBlock b{0u, 0u};
     if (k < f.n && 4 * d < f.n) {
-        b.word = cwa_codes(a, f)[d];
-        b.dw = cwa_dif(a, f)[d];
+        const CwireSections<const uint8_t> sec = cwa_sections(a, f);
+        b.word = sec.code32()[d];
+        b.dw = sec.diff32()[d];
     }
     return b;
 }
@@ -694,7 +567,6 @@ __global__ __launch_bounds__(64) void k_cwa_apply(const CwaArgs a, int nframes) 
     const uint32_t lo = tile * kCwaTile;
     const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
     const uint32_t hi = lo + len;
-    const uint64_t lt = (1ull << lane) - 1ull;
     cwa_tile_load(s, a.state + lo, len, lane);
     // while frame t is applied, frame t + 1's first block and frame t + 2's directory word are in flight
     CwaFrame f1 = a.ftab[0], f2 = f1;
@@ -718,7 +590,8 @@ __global__ __launch_bounds__(64) void k_cwa_apply(const CwaArgs a, int nframes) 
             f2 = a.ftab[t + 2];
             d2 = a.dir[(size_t)(t + 2) * a.ntiles + tile];
         }
-        const uint32_t *code = cwa_codes(a, f), *esc = cwa_esc(a, f), *dif = cwa_dif(a, f);
+        const CwireSections<const uint8_t> sec = cwa_sections(a, f);
+        const uint32_t *code = sec.code32(), *esc = sec.esc32(), *dif = sec.diff32();
         uint32_t k = dr.x, rank = dr.y, x = dr.z;
         bool first = true;
         while (k < f.n) {
@@ -728,43 +601,22 @@ __global__ __launch_bounds__(64) void k_cwa_apply(const CwaArgs a, int nframes) 
                 b.dw = 4 * d < f.n ? dif[d] : 0u;
             }
             first = false;
-            bool fl[4], in[4];
-            uint32_t before = 0, wtot = 0;
+            bool in[4], fl[4];
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const uint32_t kk = 4 * d + j;
-                in[j] = kk >= k && kk < f.n;
-                fl[j] = in[j] && ((b.word >> (8 * j)) & 255u) == 255u;
-                const uint64_t m = __ballot(fl[j]);
-                before += (uint32_t)__popcll(m & lt);
-                wtot += (uint32_t)__popcll(m);
-            }
-            uint32_t r = rank + before, inc[4], lsum = 0;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                inc[j] = 0;
-                if (in[j]) {
-                    uint32_t g = (b.word >> (8 * j)) & 255u;
-                    bool bad = false;
-                    if (fl[j]) {
-                        if (r < f.e) g = esc[r];
-                        else bad = true;
-                        r++;
-                    }
-                    inc[j] = bad ? 0u : g + 1u;
-                }
-                lsum += inc[j];
-            }
-            const uint32_t incl = cwa_wave_incl(lsum, lane);
-            uint32_t xi = x + incl - lsum;
+            for (int j = 0; j < 4; j++) in[j] = 4 * d + j >= k && 4 * d + j < f.n;
+            uint32_t wtot;
+            const uint32_t before = cwire_escapes_before(b.word, in, fl, wtot);
+            uint32_t inc[4], rk[4];
+            bool bad[4];
+            const uint32_t lsum = cwire_decode4(b.word, in, fl, rank + before, f.e, esc, inc, bad, rk);
+            rank += wtot;
+            uint32_t xi = block_exclusive_scan<1>(lsum, (uint32_t *)nullptr, x);   // a single wave: no LDS, no barrier
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 xi += inc[j];
                 const uint32_t idx = xi - 1u;   // (inc 0: a bad escape or a masked entry, nothing to apply)
                 if (inc[j] && idx >= lo && idx < hi) s[idx - lo] = (uint8_t)(s[idx - lo] + (b.dw >> (8 * j)));
             }
-            x += __shfl(incl, 63, 64);
-            rank += wtot;
             k = ka + 256;
             if (x >= hi) break;   // the next entry's index is at least x
         }
