@@ -48,6 +48,12 @@ public:
     long long exec_submit(uint8_t *frameData, uint8_t *showReadyNData, std::string &text, int *h_xs);
     void exec_wait(long long ticket, unsigned int *h_pos);
     void pipe_close();
+    // One tick of nstreams cameras in one call (include/mi355diff.h, mi355_diff_multi_batch): camera s has its new frame at
+    // d_frames + s*stride and its reconstructed-frame state at d_states + s*stride, both in DEVICE memory of the caller
+    // (mi355_dev_alloc / hipMalloc); segment s of (d_offsets, d_xs, d_diff) is its packed frame.  Blocking, like exec_core.
+    // nstreams <= MI355_MAX_BATCH of the environment when the object was made (default 1: the reference's one stream).
+    void exec_multi(const void *d_frames, void *d_states, size_t stride, int nstreams, void *d_offsets, void *d_xs,
+                    void *d_diff, size_t capacity);
 };
 
 static_assert(sizeof(CUDACore) == 160, "must match the reference's object size (LP64)");

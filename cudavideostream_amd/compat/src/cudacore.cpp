@@ -44,7 +44,8 @@ CUDACore::CUDACore(uint8_t *charsPx, matsz &charsSz, float *k, int total, uint8_
     cfg.width = frameSz.width;
     cfg.height = frameSz.height;
     cfg.threshold = LR_THRESHOLDS;
-    cfg.max_batch = 1;
+    cfg.max_batch = env_int("MI355_MAX_BATCH", 1);   // exec_multi: the most cameras per tick (the logs grow with it)
+    if (cfg.max_batch < 1) cfg.max_batch = 1;
     cfg.device = 0;  // kernels.cu:385 uses device 0
 #ifdef NOISE_FILTER
     cfg.noise_filter = 1;
@@ -88,6 +89,12 @@ void CUDACore::exec_wait(long long ticket, unsigned int *h_pos) {
     uint32_t pos = 0;
     MI355_CHECK(mi355_pipe_wait(core_, ticket, &pos));
     *h_pos = pos;
+}
+
+void CUDACore::exec_multi(const void *d_frames, void *d_states, size_t stride, int nstreams, void *d_offsets, void *d_xs,
+                          void *d_diff, size_t capacity) {
+    MI355_CHECK(mi355_diff_multi_batch(core_, d_frames, d_states, stride, nstreams, d_offsets, d_xs, d_diff, capacity));
+    MI355_CHECK(mi355_synchronize(core_));
 }
 
 size_t CUDACore::chunkt_size() { return 32; }  // sizeof(long4), kernels.cu:27,527-529

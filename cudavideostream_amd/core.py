@@ -248,6 +248,31 @@ class CUDACore:
         _l.check(self._lib.mi355_diff_stream_cwire_batch(self._h, _ptr(d_frames), stride, int(nframes), _ptr(d_offsets),
                                                          _ptr(d_frame_pos), _ptr(d_cwire), int(capacity_bytes)))
 
+    # -- many streams, one frame each: the states live in the caller's memory (include/mi355diff.h) --------------------
+    def diff_multi_batch(self, d_frames, d_states, nstreams, d_offsets, d_xs, d_diff, capacity, stride=None):
+        """One tick of nstreams streams: stream s diffs d_frames[s] against d_states[s], which takes the negative feedback;
+        segment s of (d_offsets, d_xs, d_diff) is that stream's packed frame.  The core's own state is not involved."""
+        self._hold(d_frames, d_states, d_offsets, d_xs, d_diff)
+        stride = self.total if stride is None else stride
+        _l.check(self._lib.mi355_diff_multi_batch(self._h, _ptr(d_frames), _ptr(d_states), int(stride), int(nstreams),
+                                                  _ptr(d_offsets), _ptr(d_xs), _ptr(d_diff), int(capacity)))
+
+    def diff_multi_wire_batch(self, d_frames, d_states, nstreams, d_offsets, d_wire, capacity_bytes, stride=None):
+        """diff_multi_batch into the sender's byte stream: {u32 n, i32 xs[n], u8 diff[n]} per stream."""
+        self._hold(d_frames, d_states, d_offsets, d_wire)
+        stride = self.total if stride is None else stride
+        _l.check(self._lib.mi355_diff_multi_wire_batch(self._h, _ptr(d_frames), _ptr(d_states), int(stride), int(nstreams),
+                                                       _ptr(d_offsets), _ptr(d_wire), int(capacity_bytes)))
+
+    def diff_multi_cwire_batch(self, d_frames, d_states, nstreams, d_offsets, d_frame_pos, d_cwire, capacity_bytes,
+                               stride=None):
+        """diff_multi_batch into compact records: stream s's record at d_frame_pos[s] (uint64[nstreams + 1])."""
+        self._hold(d_frames, d_states, d_offsets, d_frame_pos, d_cwire)
+        stride = self.total if stride is None else stride
+        _l.check(self._lib.mi355_diff_multi_cwire_batch(self._h, _ptr(d_frames), _ptr(d_states), int(stride), int(nstreams),
+                                                        _ptr(d_offsets), _ptr(d_frame_pos), _ptr(d_cwire),
+                                                        int(capacity_bytes)))
+
     def wire_bytes(self, nframes, entries):
         return self._lib.mi355_wire_bytes(nframes, entries)
 

@@ -141,6 +141,13 @@ struct mi355_core {
     bool filter_since_batch = false;  // a frame filter ran on this core since the last batch (use_device_filter)
     hipEvent_t fork[kSets] = {};          // recorded on the core's stream in front of a batch's first pack launch: the other parts wait for it
     int parts_pending = -1;           // log set of the last batch whose parts the core's stream has not waited for (-1: none)
+    // Feedback pairs (mi355_diff_multi_*) write the CALLER's states, half of every state on `main2` when the pack is split.
+    // Tick k + 1 on the same states needs no wait: a tile's bytes are read and written by the launches of one stream only,
+    // tick after tick, as the core's own state is.  Any other batch that follows may read those states at other tile
+    // positions (mi355_diff_pairs_batch with the states as an operand, other states that overlap these), so it first lets
+    // the core's stream wait for the parts (run_batch).
+    const void *fb_states = nullptr;  // states and stride of the last split feedback batch the core's stream has not
+    size_t fb_stride = 0;             // waited for (nullptr: none)
 
     // timing: ring of event sets {before pack, after pack, before scan, after scan, after expand, after the second pack
     // launch of a split batch}, harvested lazily so that timed batches still queue back to back
@@ -346,6 +353,8 @@ struct CwireOut {
 
 // d_wire != nullptr: the expander writes the sender's byte stream (capacity in bytes) instead of d_xs/d_diff.
 // cw != nullptr: the log is expanded into compact records (launch_expand_cwire) instead.
+// feedback (pair mode): d_prev are the caller's states, one per batch index, and take the fed-back state of their frame
+// (mi355_diff_multi_*); the operands do not overlap (the entry points refuse that).
 // pipelined: a public batch entry point on the core's OWN stream -- the index and the expansion run on the side
 // stream beside the next batch's pack kernel (which needs only the state, carried on the core's stream, and a free
 // set of logs); completion is what mi355_synchronize / any other entry point waits for (use_device joins).  With a
@@ -365,7 +374,7 @@ CwireDirectArgs cwire_args(mi355_core *c, const CwireOut *cw, const uint32_t *d_
 
 int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, size_t stride,
               int nframes, void *d_offsets, void *d_xs, void *d_diff, size_t capacity,
-              void *d_wire = nullptr, bool pipelined = false, const CwireOut *cw = nullptr) {
+              void *d_wire = nullptr, bool pipelined = false, const CwireOut *cw = nullptr, bool feedback = false) {
     if (!c) return fail(MI355_ERR_INVALID, "null core");
     if (nframes < 0 || nframes > c->cfg.max_batch)
         return fail(MI355_ERR_INVALID, "nframes outside [0, max_batch]");
@@ -379,7 +388,11 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
     if (c->filter_since_batch) pipelined = false;   // a filter / batch chain: one kernel after the other (use_device_filter)
     c->filter_since_batch = false;
     if (pipelined) {
-        if (int rc = use_device(c, false, false)) return rc;
+        // the parts of the last batch: a tick on the states of the tick before may queue up behind them unseen (every tile
+        // stays on its stream); any other tick must not write what a part elsewhere still reads, and no other batch may
+        // read what a tick's part elsewhere still writes
+        const bool same_states = feedback && c->fb_states == d_prev && c->fb_stride == stride;
+        if (int rc = use_device(c, false, !same_states && (feedback || c->fb_states))) return rc;
         if (int rc = setup_pipeline(c)) return rc;
         pipelined = c->pipeline_ok;
     }
@@ -391,6 +404,7 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
     }
     if (!pipelined)
         if (int rc = use_device(c)) return rc;
+    c->fb_states = nullptr;   // (whatever was pending has been waited for above, or is these very states)
     if (nframes == 0 || c->n == 0) {
         HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(uint32_t) * ((size_t)nframes + 1), c->stream));
         if (d_wire) {   // empty frames still have their headers {n = 0}
@@ -463,16 +477,17 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
         PackArgs a0 = a, a1 = a;
         a0.tile_end = cut;
         a1.tile_begin = cut;
-        HIP_TRY(launch_diff_pack(a0, pair, aligned, pair_once, blocks0, c->stream));
+        HIP_TRY(launch_diff_pack(a0, pair, aligned, pair_once, blocks0, c->stream, feedback));
         HIP_TRY(hipStreamWaitEvent(c->main2, c->fork[c->flip], 0));
         if (ls.in_use) HIP_TRY(hipStreamWaitEvent(c->main2, ls.expanded, 0));
-        HIP_TRY(launch_diff_pack(a1, pair, aligned, pair_once, blocks1, c->main2));
+        HIP_TRY(launch_diff_pack(a1, pair, aligned, pair_once, blocks1, c->main2, feedback));
         HIP_TRY(hipEventRecord(c->packed2[c->flip], c->main2));
         HIP_TRY(hipStreamWaitEvent(tail, c->packed2[c->flip], 0));
         if (tev) HIP_TRY(hipEventRecord(tev[5], c->main2));   // the pack "kernel" of a split batch ends when BOTH parts have
         c->parts_pending = c->flip;
+        if (feedback) { c->fb_states = d_prev; c->fb_stride = stride; }
     } else {
-        HIP_TRY(launch_diff_pack(a, pair, aligned, pair_once, pipelined ? k1_blocks : 0u, c->stream));
+        HIP_TRY(launch_diff_pack(a, pair, aligned, pair_once, pipelined ? k1_blocks : 0u, c->stream, feedback));
     }
     if (tev) {
         HIP_TRY(hipEventRecord(tev[1], c->stream));
@@ -827,6 +842,46 @@ int mi355_diff_stream_cwire_batch(mi355_core *c, const void *d_frames, size_t st
         return fail(MI355_ERR_INVALID, "d_cwire and d_offsets must be 4-byte aligned, d_frame_pos 8-byte aligned");
     const CwireOut cw{(uint64_t *)d_frame_pos, (uint8_t *)d_cwire, (uint64_t)capacity_bytes};
     return run_batch(c, false, d_frames, nullptr, stride_bytes, nframes, d_offsets, nullptr, nullptr, 0, nullptr, true, &cw);
+}
+
+// mi355_diff_multi_*: what the three forms refuse alike, before anything is launched
+static int check_multi(mi355_core *c, const void *d_frames, const void *d_states, size_t stride, int nstreams) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nstreams < 0 || nstreams > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams outside [0, max_batch]");
+    if (nstreams == 0) return MI355_OK;
+    if (!d_frames || !d_states) return fail(MI355_ERR_INVALID, "null d_frames / d_states");
+    if (stride < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
+    const uintptr_t f = (uintptr_t)d_frames, s = (uintptr_t)d_states;
+    const uintptr_t span = (uintptr_t)(nstreams - 1) * stride + c->n;   // bytes from the first frame to the end of the last
+    if (f < s + span && s < f + span) return fail(MI355_ERR_INVALID, "the states overlap the frames");
+    return MI355_OK;
+}
+
+int mi355_diff_multi_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
+                           void *d_offsets, void *d_xs, void *d_diff, size_t capacity) {
+    if (int rc = check_multi(c, d_frames, d_states, stride_bytes, nstreams)) return rc;
+    return run_batch(c, true, d_frames, d_states, stride_bytes, nstreams, d_offsets, d_xs, d_diff, capacity, nullptr, true,
+                     nullptr, true);
+}
+
+int mi355_diff_multi_wire_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
+                                void *d_offsets, void *d_wire, size_t capacity_bytes) {
+    if (int rc = check_multi(c, d_frames, d_states, stride_bytes, nstreams)) return rc;
+    if (!d_wire) return fail(MI355_ERR_INVALID, "null d_wire");
+    return run_batch(c, true, d_frames, d_states, stride_bytes, nstreams, d_offsets, nullptr, nullptr, capacity_bytes,
+                     d_wire, true, nullptr, true);
+}
+
+int mi355_diff_multi_cwire_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
+                                 void *d_offsets, void *d_frame_pos, void *d_cwire, size_t capacity_bytes) {
+    if (int rc = check_multi(c, d_frames, d_states, stride_bytes, nstreams)) return rc;
+    if (!d_offsets || !d_frame_pos) return fail(MI355_ERR_INVALID, "null d_offsets / d_frame_pos");
+    if (capacity_bytes > 0 && !d_cwire) return fail(MI355_ERR_INVALID, "null d_cwire");
+    if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_frame_pos & 7u))
+        return fail(MI355_ERR_INVALID, "d_cwire and d_offsets must be 4-byte aligned, d_frame_pos 8-byte aligned");
+    const CwireOut cw{(uint64_t *)d_frame_pos, (uint8_t *)d_cwire, (uint64_t)capacity_bytes};
+    return run_batch(c, true, d_frames, d_states, stride_bytes, nstreams, d_offsets, nullptr, nullptr, 0, nullptr, true, &cw,
+                     true);
 }
 
 size_t mi355_wire_bytes(int nframes, uint64_t entries) { return 4 * (size_t)nframes + 5 * (size_t)entries; }

@@ -77,6 +77,12 @@ struct LogOut {
     __amdgpu_buffer_rsrc_t codes, recs, meta;
 };
 
+// Cache policy of the states of feedback pairs (auxiliary bits of the buffer instructions: 0 plain, 2 non-temporal).
+// Plain loads, non-temporal stores, measured against the three other combinations at S * N = 50 MB and 1.6 GB (DESIGN.md,
+// "K1 with caller-owned states": 5 % faster than plain / plain at the small size, equal at the large one; non-temporal
+// LOADS lose at both: a state is read again one tick later).  The new frames are read once: non-temporal.
+constexpr int kStateLoadAux = 0, kStateStoreAux = 2;
+
 // One frame of one tile, arithmetic only: compare, feed back.  dm = the 16 masked difference bytes,
 // m16 = map of the flagged bytes.
 template <bool HIGH>
@@ -169,14 +175,15 @@ struct Group {
     // (round-robin shards: pairs (f - 1, f) of every 8th f): non-temporal loads, +7 % for such pairs (0.355 -> 0.332 ms per
     // 128 pairs of 1080p, 4K 0.60 -> 0.63 of the roofline); pairs of CONSECUTIVE frames, where cur of one pair is prev of
     // the next, keep the plain policy (the second read hits): non-temporal loads cost them 6 % (profiles/archive/r04av).
-    template <bool ONCE>
+    // FB: feedback pairs -- the states (prev) take their own policy (kStateLoadAux).
+    template <bool ONCE, bool FB = false>
     __device__ __forceinline__ void load_desc(__amdgpu_buffer_rsrc_t cur, __amdgpu_buffer_rsrc_t prev, const uint32_t (&voff)[kPrefetch]) {
 #pragma unroll
         for (int d = 0; d < kPrefetch; d++) {
             const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(cur, voff[d], 0, ONCE ? 2 : 0);
             c[d] = make_uint4(v.x, v.y, v.z, v.w);
             if (PAIR) {
-                const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(prev, voff[d], 0, ONCE ? 2 : 0);
+                const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(prev, voff[d], 0, FB ? kStateLoadAux : (ONCE ? 2 : 0));
                 p[d] = make_uint4(w.x, w.y, w.z, w.w);
             }
         }
@@ -200,9 +207,32 @@ struct Group {
     }
 };
 
-template <bool PAIR, bool FAST, bool HIGH>
+// Feedback pairs (mi355_diff_multi_*: batch index = stream, `prev` = the caller's states, writable): where a group's
+// states go back.  Aligned tiles: the descriptor the group's states were loaded through (frame d of the group at voff[d]);
+// ragged tiles: the lane's address in the group's first state, the others `stride` apart.
+struct StateOut {
+    __amdgpu_buffer_rsrc_t desc;
+    const uint32_t *voff;
+    uint8_t *base;
+};
+
+// The state of frame d of the group goes back where it came from.  Only a lane that holds a flagged byte (m16 != 0) has
+// anything new: the others' stores carry an offset beyond the descriptor and are dropped (no branch, no traffic), so the
+// write-back follows the changed lanes, not N.
+template <bool FAST>
+__device__ __forceinline__ void store_state(const PackArgs &a, const StateOut &so, int d, uint4 st, uint32_t m16, int valid) {
+    if (FAST) {
+        const u32x4 v = {st.x, st.y, st.z, st.w};
+        __builtin_amdgcn_raw_buffer_store_b128(v, so.desc, m16 != 0u ? so.voff[d] : kOOB, 0, kStateStoreAux);
+    } else {
+        store16_bytes(so.base + (size_t)d * a.stride, st, m16 != 0u ? valid : 0);
+    }
+}
+
+template <bool PAIR, bool FAST, bool HIGH, bool FB = false>
 __device__ __forceinline__ void pack_group(const PackArgs &a, const Group<PAIR, FAST> &g, int t0, uint4 &st,
-                                           LogPos &lp, uint32_t tile, ThrConst tc, int lane, const LogOut &lg) {
+                                           LogPos &lp, uint32_t tile, ThrConst tc, int lane, const LogOut &lg,
+                                           const StateOut *so = nullptr, int valid = 16) {
     // The group's kPrefetch meta words are assembled in lanes 0..kPrefetch-1 and leave with ONE store.
     constexpr int kPrefetch = PrefetchOf<PAIR>::value;
     uint4 meta = make_uint4(0, 0, 0, 0);
@@ -216,12 +246,14 @@ __device__ __forceinline__ void pack_group(const PackArgs &a, const Group<PAIR, 
         uint32_t dm0[4], m0, m1 = 0, pc0, pm0, pc1 = 0, pm1 = 0;
         if (PAIR) st = g.p[d];
         compare_step<HIGH>(g.c[d], st, tc, dm0, m0);
+        if (FB) store_state<FAST>(a, *so, d, st, m0, valid);
         const uint32_t c0 = emit_step(dm0, m0, lg, lp, jump, lane24, pc0, pm0);
         uint32_t c1 = 0;
         if (two) {
             if (PAIR) st = g.p[d + 1];
             uint32_t dm1[4];
             compare_step<HIGH>(g.c[d + 1], st, tc, dm1, m1);
+            if (FB) store_state<FAST>(a, *so, d + 1, st, m1, valid);
             c1 = emit_step(dm1, m1, lg, lp, jump, lane24, pc1, pm1);
         }
         // flagged bytes of the two frames: one register (16-bit fields, a tile holds at most 1024) and one
@@ -243,7 +275,7 @@ __device__ __forceinline__ void pack_group(const PackArgs &a, const Group<PAIR, 
     __builtin_amdgcn_raw_buffer_store_b128(mv, lg.meta, (lane < kPrefetch && t0 + lane < a.nframes) ? moff : kOOB, 0, 0);
 }
 
-template <bool PAIR, bool FAST, bool HIGH, bool ONCE>
+template <bool PAIR, bool FAST, bool HIGH, bool ONCE, bool FB = false>
 __device__ __forceinline__ void pack_tile(const PackArgs &a, uint32_t tile, uint32_t byte_off,
                                           int valid, int lane) {
     const int T = a.nframes;
@@ -270,6 +302,25 @@ __device__ __forceinline__ void pack_tile(const PackArgs &a, uint32_t tile, uint
             const uint32_t bytes = left <= 0 ? 0u : (left > 0xffffffffll ? 0xffffffffu : (uint32_t)left);
             return make_rsrc(base, bytes);
         };
+        if (FB) {   // the same loop; each group's states go back through the descriptor they came through
+            StateOut sa{desc(pb), voff, nullptr}, sb = sa;
+            ga.template load_desc<ONCE, true>(desc(cb), sa.desc, voff);
+            for (int t0 = 0;;) {
+                cb += gstep; pb += gstep; left -= (int64_t)gstep;
+                sb.desc = desc(pb);
+                gb.template load_desc<ONCE, true>(desc(cb), sb.desc, voff);
+                pack_group<PAIR, FAST, HIGH, true>(a, ga, t0, st, lp, tile, tc, lane, lg, &sa);
+                t0 += kPrefetch;
+                if (t0 >= T) break;
+                cb += gstep; pb += gstep; left -= (int64_t)gstep;
+                sa.desc = desc(pb);
+                ga.template load_desc<ONCE, true>(desc(cb), sa.desc, voff);
+                pack_group<PAIR, FAST, HIGH, true>(a, gb, t0, st, lp, tile, tc, lane, lg, &sb);
+                t0 += kPrefetch;
+                if (t0 >= T) break;
+            }
+            return;
+        }
         ga.template load_desc<ONCE>(desc(cb), desc(pb), voff);
         for (int t0 = 0;;) {
             cb += gstep; if (PAIR) pb += gstep; left -= (int64_t)gstep;
@@ -288,6 +339,25 @@ __device__ __forceinline__ void pack_tile(const PackArgs &a, uint32_t tile, uint
     }
     const uint8_t *cur_last = a.cur + (size_t)(T - 1) * a.stride, *prev_last = PAIR ? a.prev + (size_t)(T - 1) * a.stride : nullptr;
     const uint8_t *cp = a.cur, *pp = a.prev;   // frame t0 + kPrefetch, the next group to request
+    if (FB) {   // the same loop; the lane's bytes of each group's states go back where they were read
+        StateOut sa{lg.meta, nullptr, const_cast<uint8_t *>(pp) + byte_off}, sb = sa;
+        ga.load(a, byte_off, 0, valid, cp, pp, cur_last, prev_last);
+        for (int t0 = 0;;) {
+            cp += gstep; pp += gstep;
+            sb.base = const_cast<uint8_t *>(pp) + byte_off;
+            gb.load(a, byte_off, t0 + kPrefetch, valid, cp, pp, cur_last, prev_last);
+            pack_group<PAIR, FAST, HIGH, true>(a, ga, t0, st, lp, tile, tc, lane, lg, &sa, valid);
+            t0 += kPrefetch;
+            if (t0 >= T) break;
+            cp += gstep; pp += gstep;
+            sa.base = const_cast<uint8_t *>(pp) + byte_off;
+            ga.load(a, byte_off, t0 + kPrefetch, valid, cp, pp, cur_last, prev_last);
+            pack_group<PAIR, FAST, HIGH, true>(a, gb, t0, st, lp, tile, tc, lane, lg, &sb, valid);
+            t0 += kPrefetch;
+            if (t0 >= T) break;
+        }
+        return;
+    }
     ga.load(a, byte_off, 0, valid, cp, pp, cur_last, prev_last);
     for (int t0 = 0;;) {
         cp += gstep; if (PAIR) pp += gstep;
@@ -308,8 +378,10 @@ __device__ __forceinline__ void pack_tile(const PackArgs &a, uint32_t tile, uint
     }
 }
 
-template <bool PAIR, bool ALIGNED, bool HIGH, bool ONCE = !PAIR>
+// FB (pair mode only): feedback pairs -- frame t's state, as compare_step leaves it, goes back to prev + t * stride.
+template <bool PAIR, bool ALIGNED, bool HIGH, bool ONCE = !PAIR, bool FB = false>
 __global__ __launch_bounds__(256) void k_diff_pack(const PackArgs a) {
+    static_assert(!FB || PAIR, "feedback write-back is a form of pair mode");
     const int lane = threadIdx.x & 63;
     // one tile per wave when the grid covers the frame (the default); a smaller grid walks the tiles with its stride
     // (pipelined batches leave wave slots to the expansion of the batch before, core.hip)
@@ -322,15 +394,16 @@ __global__ __launch_bounds__(256) void k_diff_pack(const PackArgs a) {
         const uint32_t byte_off = tile_off + (uint32_t)lane * 16u;
         // wave-uniform choice: every lane of a full, aligned tile takes the vector path
         if (ALIGNED && tile_off + kTileBytes <= a.n) {
-            pack_tile<PAIR, true, HIGH, ONCE>(a, tile, byte_off, 16, lane);
+            pack_tile<PAIR, true, HIGH, ONCE, FB>(a, tile, byte_off, 16, lane);
         } else {
             const int valid = byte_off < a.n ? (int)min(16u, a.n - byte_off) : 0;
-            pack_tile<PAIR, false, HIGH, ONCE>(a, tile, byte_off, valid, lane);
+            pack_tile<PAIR, false, HIGH, ONCE, FB>(a, tile, byte_off, valid, lane);
         }
     }
 }
 
-hipError_t launch_diff_pack(const PackArgs &a, bool pair, bool aligned, bool pair_once, uint32_t max_blocks, hipStream_t s) {
+hipError_t launch_diff_pack(const PackArgs &a, bool pair, bool aligned, bool pair_once, uint32_t max_blocks, hipStream_t s,
+                            bool feedback) {
     const dim3 block(64 * kWavesPerBlock);
     uint32_t blocks = (a.tile_end - a.tile_begin + kWavesPerBlock - 1) / kWavesPerBlock;
     if (max_blocks && max_blocks < blocks) blocks = max_blocks;
@@ -344,7 +417,15 @@ hipError_t launch_diff_pack(const PackArgs &a, bool pair, bool aligned, bool pai
         if (high) hipLaunchKernelGGL((k_diff_pack<P, A, true>), grid, block, 0, s, a);                 \
         else hipLaunchKernelGGL((k_diff_pack<P, A, false>), grid, block, 0, s, a);                     \
     } while (0)
-    if (pair) {
+    if (pair && feedback) {   // a.prev = the caller's states (core.hip, run_batch); the frames are read once
+        if (aligned) {
+            if (high) hipLaunchKernelGGL((k_diff_pack<true, true, true, true, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((k_diff_pack<true, true, false, true, true>), grid, block, 0, s, a);
+        } else {
+            if (high) hipLaunchKernelGGL((k_diff_pack<true, false, true, true, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((k_diff_pack<true, false, false, true, true>), grid, block, 0, s, a);
+        }
+    } else if (pair) {
         if (aligned && pair_once) {   // operands that share no frame (core.hip, run_batch)
             if (high) hipLaunchKernelGGL((k_diff_pack<true, true, true, true>), grid, block, 0, s, a);
             else hipLaunchKernelGGL((k_diff_pack<true, true, false, true>), grid, block, 0, s, a);

@@ -57,7 +57,8 @@ int core_device(const ::mi355_core *c);
 
 // diff_pack.hip
 hipError_t launch_diff_pack(const PackArgs &a, bool pair, bool aligned, bool pair_once /* pair mode: no frame is an operand twice */,
-                            uint32_t max_blocks /* 0: one tile per wave */, hipStream_t s);
+                            uint32_t max_blocks /* 0: one tile per wave */, hipStream_t s,
+                            bool feedback = false /* pair mode: prev + t * stride is writable and takes frame t's fed-back state */);
 uint32_t expand_groups(uint32_t ntiles);
 // A frame total travels as ONE 64-bit word {total: 31 bits (a frame is below 2 GiB), tag of the launch: 33 bits}
 // (diff_pack.hip, publish_total).  The tag counts the launches of a core and is never 0 (0 = never written); when it

@@ -81,7 +81,8 @@ typedef struct mi355_config {
  *      are refused (MI355_ERR_INVALID) and will not be reused; their defaults are the library's fixed schedule, unchanged
  *      (mi355_diff_stream_batch)
  *   9  + mi355_diff_stream_cwire_batch (additions only)
- *   10 + mi355_apply_cwire_batch (additions only) */
+ *   10 + mi355_apply_cwire_batch (additions only); + mi355_diff_multi_batch, mi355_diff_multi_wire_batch,
+ *      mi355_diff_multi_cwire_batch (additions only: no existing argument list changed, so the number stays) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -238,6 +239,38 @@ size_t mi355_wire_bytes(int nframes, uint64_t entries);
  * max_batch 256). */
 int mi355_diff_stream_cwire_batch(mi355_core *core, const void *d_frames, size_t stride_bytes, int nframes,
                                   void *d_offsets, void *d_frame_pos, void *d_cwire, size_t capacity_bytes);
+
+/* ---- many streams, one frame each ("many cameras per GPU") ---------------------------
+ * One tick of nstreams independent streams in ONE call: stream s (0 <= s < nstreams <= max_batch) has its new frame at
+ * d_frames + s*stride_bytes and its state -- the frame its clients have reconstructed, kept in the CALLER's memory -- at
+ * d_states + s*stride_bytes.  For every s and every byte i (ascending) exactly what mi355_diff_stream_batch(nframes = 1)
+ * does on a core whose state is states[s]: df = frame[s][i] - state[s][i]; if |df| > threshold emit (i, (uint8)df) into
+ * segment s and set state[s][i] = frame[s][i].  The core's own state is neither read nor written.
+ * The outputs are those of the single-stream forms with "frame t" read as "stream s": d_offsets is uint32[nstreams + 1];
+ * the wire form holds {u32 n, i32 xs[n], u8 diff[n]} per stream, stream s at byte 4*s + 5*offsets[s]; the compact form one
+ * record per stream at d_frame_pos[s].  Capacity, drop and alignment rules and mi355_cwire_bytes_max(N, nstreams) are
+ * unchanged; when the outputs overflow the states still advance completely.  A per-stream consumer slices segment s out
+ * for that camera's socket; a late joiner is served with mi355_download of states[s] as its base frame.
+ * Refused (MI355_ERR_INVALID) before anything is launched or written: a null d_frames or d_states with nstreams > 0,
+ * nstreams outside [0, max_batch], stride_bytes < N, states [d_states, d_states + (nstreams-1)*stride_bytes + N) that overlap
+ * the frames' region of the same shape, and whatever the single-stream form refuses.  nstreams == 0 writes offsets[0] = 0
+ * (and frame_pos[0] = 0).  The fast path needs d_frames, d_states and stride_bytes to be multiples of 16; anything else
+ * goes the byte path.  Bytes of the states' region outside the N bytes of each state are never written.
+ * The pack kernel is the pair form with a write-back: a lane stores its 16 state bytes only if one of them changed, so
+ * the write traffic follows the changes, not N.  The frames are read with non-temporal loads, the states with plain loads
+ * (they are read again one tick later) and written with non-temporal stores.
+ * Ordering is that of mi355_diff_stream_batch with the caller's states in the place of the core's: asynchronous; on the
+ * core's own stream ticks are pipelined and the next tick on the same (d_states, stride_bytes) sees every state byte the
+ * tick before wrote, split launches included; every later entry point of this core that reads the states (mi355_download,
+ * a frame filter, mi355_diff_pairs_batch, a tick on other states) finds them complete; with a caller's stream everything
+ * runs on it in call order.  Work of the CALLER on another stream (the upload of the next frames, a copy of a state) is
+ * ordered by the caller: mi355_synchronize first. */
+int mi355_diff_multi_batch(mi355_core *core, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
+                           void *d_offsets, void *d_xs, void *d_diff, size_t capacity);
+int mi355_diff_multi_wire_batch(mi355_core *core, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
+                                void *d_offsets, void *d_wire, size_t capacity_bytes);
+int mi355_diff_multi_cwire_batch(mi355_core *core, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
+                                 void *d_offsets, void *d_frame_pos, void *d_cwire, size_t capacity_bytes);
 
 /* The client's side, client/opencv.cpp:50-66: for every frame in order, state[xs[i]] += diff[i] (uint8
  * wrap-around) on the core's state (a client core is a core whose state was set to the received base frame,

@@ -1,0 +1,181 @@
+#!/usr/bin/env python3
+"""Secondary benchmark: one frame of each of S camera streams per tick (mi355_diff_multi_*, include/mi355diff.h), 1080p,
+S = 8, 64, 256, S1 webcam-like input resident in HBM.  Not the headline metric (bench.py).
+
+Three legs, each in microseconds per frame (wall clock around `ticks` ticks on the cores' own streams, then a
+synchronisation -- what a server sees), alternating within every round; the line carries median, minimum and maximum of
+the rounds:
+  multi       the arrays call and the compact call: one call per tick, the S states in the caller's memory;
+  cores_loop  S cores, each diff_stream_batch(nframes = 1) per tick -- the only way before these entry points;
+  pairs       mi355_diff_pairs_batch on the same operands: the same kernel without the write-back, a floor for the pack.
+`cores_loop` and `pairs` use old entry points only: against a library without the new symbols (MI355DIFF_LIB names
+another build) the script runs them alone, which is how their numbers on the parent commit are taken.
+
+What `pairs` is and is not: it diffs frames 1 .. S against a constant copy of the initial states every tick (nothing is
+fed back, so walking the frames would let the differences grow), i.e. one webcam step per stream like every tick of
+`multi`, but the SAME 2 S N bytes each time.  At S = 8 those 100 MB stay in the 256 MB last-level cache, while `multi`
+walks through (S + K) N bytes of frames: there `multi_over_pairs` compares a streaming run with a cache-resident floor.
+At S = 64 and 256 neither fits and the ratio is the write-back's cost.
+Where the time goes (a run of its own; tracing slows the host, so no timing is taken from it):
+  rocprofv3 --kernel-trace --stats --output-format csv -d trace -- python tools/bench_multi.py --legs multi,pairs --streams 64 --rounds 1
+and compare k_diff_pack<true, true, false, true, true> (multi) with k_diff_pack<true, true, false, true, false> (pairs) in
+*_kernel_stats.csv; counters (--pmc) go in yet another run.
+
+Input: ONE webcam stream of S + K + 1 frames; stream s shows frame s + j at step j, so every tick of every stream is the
+step between two consecutive webcam frames, and a tick's S frames are one contiguous region.  j walks 1 .. K and back."""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from cudavideostream_amd import lib, synth  # noqa: E402
+
+MULTI = ("mi355_diff_multi_batch", "mi355_diff_multi_wire_batch", "mi355_diff_multi_cwire_batch")
+
+
+def load_library():
+    """True if the library has the many-streams entry points; a build without them is bound without them."""
+    probe = ctypes.CDLL(lib.LIB_PATH)
+    have = all(hasattr(probe, n) for n in MULTI)
+    if not have:
+        for n in MULTI:
+            lib.SYMBOLS.pop(n, None)
+    lib.load()
+    return have
+
+
+def walk(K, ticks):
+    """Steps 1, 2, .. K, K - 1, .. 2, 1, 2, ..: consecutive ticks are consecutive frames, for ever."""
+    j, d, out = 1, 1, []
+    for _ in range(ticks):
+        out.append(j)
+        if K > 1:
+            if j + d > K or j + d < 1:
+                d = -d
+            j += d
+    return out
+
+
+def stats(us):
+    return {"median": round(statistics.median(us), 3), "min": round(min(us), 3), "max": round(max(us), 3)}
+
+
+def run(W, H, S, K, rounds, legs, have_multi):
+    from cudavideostream_amd import CUDACore, cwire_bytes_max
+    dev = torch.device("cuda", 0)
+    n = 3 * W * H
+    ticks = max(16, min(2048, 16384 // S))             # ~16 k frames per timed window: tens of milliseconds
+    steps = walk(K, ticks)
+    _, frames = synth.webcam_stream(S + K + 1, W, H, device=dev)
+    frames = frames.reshape(S + K + 1, n)
+    states0 = frames[:S].clone()
+    states = states0.clone()
+    cap = S * n // 8                                   # S1 changes ~2 % of the bytes
+    d_off = torch.zeros(S + 1, dtype=torch.int32, device=dev)
+    d_xs = torch.empty(cap, dtype=torch.int32, device=dev)
+    d_df = torch.empty(cap, dtype=torch.uint8, device=dev)
+    cwcap = cwire_bytes_max(n, S)
+    d_pos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
+    d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
+    result = {"size": f"{W}x{H}", "streams": S, "ticks": ticks, "rounds": rounds, "has_multi": have_multi}
+    times = {}
+    core = CUDACore(W, H, max_batch=S)
+    core.prepare(lib.PREPARE_BATCHES)
+    cores, outs = [], []
+    if "cores_loop" in legs:
+        one = n // 8
+        for s in range(S):
+            c = CUDACore(W, H, max_batch=1)
+            c.prepare(lib.PREPARE_BATCHES)
+            cores.append(c)
+            outs.append((torch.zeros(2, dtype=torch.int32, device=dev), torch.empty(one, dtype=torch.int32, device=dev),
+                         torch.empty(one, dtype=torch.uint8, device=dev)))
+    torch.cuda.synchronize()
+
+    host0 = states0.cpu().numpy() if cores else None
+
+    def reset(name):
+        states.copy_(states0)
+        if name == "cores_loop":
+            for s, c in enumerate(cores):
+                c.set_state(host0[s])
+        torch.cuda.synchronize()
+
+    def leg_multi():
+        for j in steps:
+            core.diff_multi_batch(frames[j:j + S], states, S, d_off, d_xs, d_df, cap)
+        core.synchronize()
+
+    def leg_multi_cwire():
+        for j in steps:
+            core.diff_multi_cwire_batch(frames[j:j + S], states, S, d_off, d_pos, d_cw, cwcap)
+        core.synchronize()
+
+    def leg_pairs():
+        for _ in steps:
+            core.diff_pairs_batch(frames[1:1 + S], states0, S, d_off, d_xs, d_df, cap)
+        core.synchronize()
+
+    def leg_cores():
+        one = n // 8
+        for j in steps:
+            for s, c in enumerate(cores):
+                c.diff_stream_batch(frames[j + s], 1, outs[s][0], outs[s][1], outs[s][2], one)
+        for c in cores:
+            c.synchronize()
+
+    table = {"multi": leg_multi, "multi_cwire": leg_multi_cwire, "pairs": leg_pairs, "cores_loop": leg_cores}
+    active = [k for k in table if ("multi" if k.startswith("multi") else k) in legs and (have_multi or not k.startswith("multi"))]
+    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
+        for name in active:
+            reset(name)
+            t0 = time.perf_counter()
+            table[name]()
+            dt = time.perf_counter() - t0
+            if r:
+                times.setdefault(name, []).append(dt * 1e6 / (ticks * S))
+    if "multi" in active:
+        reset("multi")
+        core.diff_multi_batch(frames[1:1 + S], states, S, d_off, d_xs, d_df, cap)
+        core.synchronize()
+        total = int(d_off.cpu()[-1])
+        assert 0 < total <= cap
+        result["changed_bytes_per_frame"] = round(total / S, 1)
+    for name in active:
+        result[name + "_us_per_frame"] = stats(times[name])
+    if "multi" in times and "cores_loop" in times:
+        result["cores_loop_over_multi"] = round(statistics.median(times["cores_loop"]) / statistics.median(times["multi"]), 2)
+    if "multi" in times and "pairs" in times:
+        result["multi_over_pairs"] = round(statistics.median(times["multi"]) / statistics.median(times["pairs"]), 3)
+    if "write_probe" in legs:                          # the board's streaming-write rate (wide stores), for the write-back's bound
+        result["hbm_write_gbps"] = round(core.probe_hbm_write(1024, narrow=False), 1)
+    print(json.dumps(result), flush=True)
+    for c in cores:
+        c.close()
+    core.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", default="1920x1080")
+    ap.add_argument("--streams", default="8,64,256")
+    ap.add_argument("--steps", type=int, default=8, help="K: webcam frames a stream walks through")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--legs", default="multi,cores_loop,pairs", help="of multi, cores_loop, pairs, write_probe")
+    a = ap.parse_args()
+    have = load_library()
+    W, H = (int(v) for v in a.size.split("x"))
+    for S in (int(v) for v in a.streams.split(",")):
+        run(W, H, S, a.steps, a.rounds, set(a.legs.split(",")), have)
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
