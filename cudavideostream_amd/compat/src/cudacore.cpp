@@ -97,6 +97,12 @@ void CUDACore::exec_multi(const void *d_frames, void *d_states, size_t stride, i
     MI355_CHECK(mi355_synchronize(core_));
 }
 
+void CUDACore::apply_multi(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, int nstreams, void *d_states,
+                           size_t stride) {
+    MI355_CHECK(mi355_apply_multi_cwire_batch(core_, d_cwire, counts, escapes, nstreams, d_states, stride));
+    MI355_CHECK(mi355_synchronize(core_));
+}
+
 size_t CUDACore::chunkt_size() { return 32; }  // sizeof(long4), kernels.cu:27,527-529
 
 void CUDACore::alloc_arrays(uint8_t **h_frame, uint8_t **n_frame, uint8_t **o_frame, int **h_xs, int r,

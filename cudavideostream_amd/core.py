@@ -273,6 +273,35 @@ class CUDACore:
                                                         _ptr(d_offsets), _ptr(d_frame_pos), _ptr(d_cwire),
                                                         int(capacity_bytes)))
 
+    # ... and their receiving end: segment / record s onto d_states[s], the frame to show
+    def apply_multi_batch(self, d_offsets, d_xs, d_diff, nstreams, d_states, stride=None):
+        """client/opencv.cpp:64-66 for one tick of nstreams streams: segment s of (d_offsets, d_xs, d_diff) is added to
+        d_states[s].  The core's own state is not involved."""
+        self._hold(d_offsets, d_xs, d_diff, d_states)
+        stride = self.total if stride is None else stride
+        _l.check(self._lib.mi355_apply_multi_batch(self._h, _ptr(d_offsets), _ptr(d_xs), _ptr(d_diff), int(nstreams),
+                                                   _ptr(d_states), int(stride)))
+
+    def apply_multi_wire_batch(self, d_wire, counts, nstreams, d_states, stride=None):
+        """apply_multi_batch from the wire bytes; counts: the streams' headers as read from the sockets."""
+        self._hold(d_wire, d_states)
+        stride = self.total if stride is None else stride
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        assert counts.size >= nstreams
+        _l.check(self._lib.mi355_apply_multi_wire_batch(self._h, _ptr(d_wire), counts.ctypes.data, int(nstreams),
+                                                        _ptr(d_states), int(stride)))
+
+    def apply_multi_cwire_batch(self, d_cwire, counts, escapes, nstreams, d_states, stride=None):
+        """apply_multi_batch straight from compact records, one per stream, back to back where the headers (counts,
+        escapes) put them; only the tiles of a state that its record touches are read and written."""
+        self._hold(d_cwire, d_states)
+        stride = self.total if stride is None else stride
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+        assert counts.size >= nstreams and escapes.size >= nstreams
+        _l.check(self._lib.mi355_apply_multi_cwire_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
+                                                         int(nstreams), _ptr(d_states), int(stride)))
+
     def wire_bytes(self, nframes, entries):
         return self._lib.mi355_wire_bytes(nframes, entries)
 

@@ -1074,6 +1074,103 @@ int mi355_apply_cwire_batch(mi355_core *c, const void *d_cwire, const uint32_t *
     return MI355_OK;
 }
 
+// ---- mi355_apply_multi_*: one segment / record of each of nstreams streams onto the caller's states -----------------------
+// What the three forms refuse alike, before anything is launched; *run = there is something to do
+static int check_apply_multi(mi355_core *c, bool inputs, int nstreams, const void *d_states, size_t stride, bool *run) {
+    *run = false;
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nstreams < 0 || nstreams > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams outside [0, max_batch]");
+    if (nstreams == 0) return MI355_OK;
+    if (!inputs) return fail(MI355_ERR_INVALID, "null stream pointer");
+    if (!d_states) return fail(MI355_ERR_INVALID, "null d_states");
+    if (stride < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
+    *run = c->n > 0;
+    return MI355_OK;
+}
+
+// An input of `bytes` bytes (known from the host's headers) against the states' region: check_multi's test
+static int check_apply_multi_overlap(const mi355_core *c, const void *d_in, uint64_t bytes, const void *d_states, size_t stride,
+                                     int nstreams) {
+    const uintptr_t in = (uintptr_t)d_in, s = (uintptr_t)d_states;
+    const uintptr_t span = (uintptr_t)(nstreams - 1) * stride + c->n;
+    if (in < s + span && s < in + (uintptr_t)bytes) return fail(MI355_ERR_INVALID, "the states overlap the input stream");
+    return MI355_OK;
+}
+
+int mi355_apply_multi_batch(mi355_core *c, const void *d_offsets, const void *d_xs, const void *d_diff, int nstreams,
+                            void *d_states, size_t stride_bytes) {
+    bool run;
+    if (int rc = check_apply_multi(c, d_offsets && d_xs && d_diff, nstreams, d_states, stride_bytes, &run)) return rc;
+    if (nstreams > 0 && (((uintptr_t)d_offsets | (uintptr_t)d_xs) & 3u))
+        return fail(MI355_ERR_INVALID, "d_offsets and d_xs must be 4-byte aligned");
+    if (!run) return MI355_OK;
+    if (int rc = use_device(c)) return rc;
+    HIP_TRY(launch_apply_multi((uint8_t *)d_states, stride_bytes, c->n, (const uint32_t *)d_offsets, (const int32_t *)d_xs,
+                               (const uint8_t *)d_diff, nstreams, c->stream));
+    return MI355_OK;
+}
+
+int mi355_apply_multi_wire_batch(mi355_core *c, const void *d_wire, const uint32_t *h_counts, int nstreams, void *d_states,
+                                 size_t stride_bytes) {
+    bool run;
+    if (int rc = check_apply_multi(c, d_wire && h_counts, nstreams, d_states, stride_bytes, &run)) return rc;
+    uint64_t entries = 0;
+    for (int s = 0; s < nstreams; s++) {
+        if (h_counts[s] > c->n) return fail(MI355_ERR_INVALID, "frame count larger than the frame");
+        entries += h_counts[s];
+    }
+    if (nstreams > 0)
+        if (int rc = check_apply_multi_overlap(c, d_wire, mi355_wire_bytes(nstreams, entries), d_states, stride_bytes, nstreams))
+            return rc;
+    if (!run) return MI355_OK;
+    if (int rc = use_device(c)) return rc;
+    ApplyMultiWireArgs h{};
+    uint64_t pos = 0;
+    for (int s0 = 0; s0 < nstreams; s0 += kApplyMultiWireStreams) {
+        h.first = s0;
+        h.count = nstreams - s0 < kApplyMultiWireStreams ? nstreams - s0 : kApplyMultiWireStreams;
+        h.cum[0] = 0;
+        for (int j = 0; j < h.count; j++) {
+            h.pos[j] = pos;
+            h.cum[j + 1] = h.cum[j] + h_counts[s0 + j];
+            pos += mi355_wire_bytes(1, h_counts[s0 + j]);
+        }
+        HIP_TRY(launch_apply_multi_wire((uint8_t *)d_states, stride_bytes, c->n, (const uint8_t *)d_wire, h, c->stream));
+    }
+    return MI355_OK;
+}
+
+int mi355_apply_multi_cwire_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
+                                  int nstreams, void *d_states, size_t stride_bytes) {
+    bool run;
+    if (int rc = check_apply_multi(c, d_cwire && h_counts && h_escapes, nstreams, d_states, stride_bytes, &run)) return rc;
+    if (nstreams == 0) return MI355_OK;
+    if ((uintptr_t)d_cwire & 3u) return fail(MI355_ERR_INVALID, "d_cwire must be 4-byte aligned");
+    CwireHeaders hdr{h_counts, h_escapes, nstreams};
+    if (int rc = hdr.check(true, c->n)) return rc;
+    std::vector<CwaFrame> fr((size_t)nstreams);   // nstreams <= max_batch: the scratch of the one-stream client holds them
+    uint32_t cbase = 0;
+    for (int s = 0; s < nstreams; s++) {
+        const CwireHeaders::Frame f = hdr.next();
+        fr[s] = CwaFrame{f.pos, f.n, f.e, cbase, cwa_chunks(f.n)};
+        cbase += fr[s].nc;
+    }
+    if (int rc = check_apply_multi_overlap(c, d_cwire, hdr.pos, d_states, stride_bytes, nstreams)) return rc;
+    if (!run) return MI355_OK;
+    if (int rc = use_device(c)) return rc;
+    CwaArgs a{};
+    a.cwire = (const uint8_t *)d_cwire;
+    a.ftab = c->cwa_ftab;
+    a.chunk = c->cwa_chunk;
+    a.dir = c->cwa_dir;
+    a.state = (uint8_t *)d_states;
+    a.stride = stride_bytes;
+    a.n = c->n;
+    a.ntiles = cwa_tiles(c->n);
+    HIP_TRY(launch_cwire_apply_multi(a, fr.data(), nstreams, c->stream));
+    return MI355_OK;
+}
+
 // client/opencv.cpp:50-66 on the compact stream, on the host.  A frame is validated whole before any byte of the state
 // changes, so a malformed frame leaves the state as the frames before it made it.
 int mi355_cwire_apply_host(uint8_t *state, size_t frame_bytes, const void *cwire, size_t cwire_bytes, int nframes,

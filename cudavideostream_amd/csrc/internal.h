@@ -107,6 +107,17 @@ hipError_t launch_apply(uint8_t *frame, uint32_t nbytes, const void *xs, const v
                         const uint32_t *d_offsets, int t, uint32_t host_count, hipStream_t s);
 hipError_t launch_apply_all(uint8_t *frame, uint32_t nbytes, const int32_t *xs, const uint8_t *diff,
                             const uint32_t *d_offsets, int nframes, hipStream_t s);
+// mi355_apply_multi_*: segment s of a packed stream onto states + s*stride
+hipError_t launch_apply_multi(uint8_t *states, size_t stride, uint32_t nbytes, const uint32_t *d_offsets, const int32_t *xs,
+                              const uint8_t *diff, int nstreams, hipStream_t s);
+constexpr int kApplyMultiWireStreams = 128;   // streams per k_apply_multi_wire launch (their places travel as kernel arguments)
+struct ApplyMultiWireArgs {
+    int32_t first, count;                       // streams [first, first + count)
+    uint64_t pos[kApplyMultiWireStreams];       // byte position of stream first + j's {n, xs, diff} in the wire stream
+    uint64_t cum[kApplyMultiWireStreams + 1];   // entries of this launch's streams before j (cum[count]: all of them)
+};
+hipError_t launch_apply_multi_wire(uint8_t *states, size_t stride, uint32_t nbytes, const uint8_t *wire,
+                                   const ApplyMultiWireArgs &h, hipStream_t s);
 hipError_t launch_export(const uint32_t *offsets, const int32_t *xs, const uint8_t *diff, int32_t *h_xs,
                          uint8_t *h_diff, uint32_t *h_count, hipStream_t s);
 hipError_t launch_merge(const MergeArgs &a, uint32_t *out_offsets, hipStream_t s);
@@ -162,6 +173,8 @@ uint32_t cwa_chunks(uint32_t n);        // chunks of a frame of n entries (1 for
 uint32_t cwa_tiles(uint32_t nbytes);
 // frames[i].cbase / nc filled by the caller; nframes <= the scratch's T
 hipError_t launch_cwire_apply(const CwaArgs &a, const CwaFrame *frames, int nframes, hipStream_t s);
+// mi355_apply_multi_cwire_batch: record s onto a.state + s*a.stride (the caller's states; a.out unused), tiles x streams
+hipError_t launch_cwire_apply_multi(const CwaArgs &a, const CwaFrame *records, int nstreams, hipStream_t s);
 
 // filters.hip -- every per-frame kernel takes a FrameBatch: frame f lives at base + f*stride
 struct FrameBatch {

@@ -2,11 +2,13 @@
 //
 //   k_apply / k_apply_all : the client's reconstruction, client/opencv.cpp:64-66
 //                           (`frame2.data[xs[i]] += buffer[i]` for the pos entries of a frame);
+//   k_apply_multi(_wire)  : the same for one segment of each of many streams, onto the caller's states;
 //   k_merge_parts         : concatenation of the streams of the row bands of ONE video stream that
 //                           several cores (GPUs) packed independently into
 //                           the single stream the sender would have produced;
 //   k_cwire_*             : the compact wire format's encoder (packed stream -> gap-coded records) and decoder;
-//   k_cwa_*               : the compact records applied straight to a client core's state (mi355_apply_cwire_batch).
+//   k_cwa_*               : the compact records applied straight to a client core's state (mi355_apply_cwire_batch) or,
+//                           one record per stream, to the caller's states (mi355_apply_multi_cwire_batch).
 //
 // The first two are index-driven byte scatter/copy: HBM-latency work with 5 bytes of traffic per entry, no
 // arithmetic worth naming.
@@ -77,6 +79,89 @@ hipError_t launch_apply(uint8_t *frame, uint32_t nbytes, const void *xs, const v
 hipError_t launch_apply_all(uint8_t *frame, uint32_t nbytes, const int32_t *xs, const uint8_t *diff,
                             const uint32_t *d_offsets, int nframes, hipStream_t s) {
     hipLaunchKernelGGL(k_apply_all, dim3(4096), dim3(256), 0, s, frame, nbytes, xs, diff, d_offsets, nframes);
+    return hipGetLastError();
+}
+
+// ---- mi355_apply_multi_batch / _wire_batch: segment s onto the caller's state s --------------------------------------------
+// One launch strides over the entries of all segments; a lane finds its segment by binary search in the segments' first
+// entries, which the workgroup keeps in LDS.  Indices of a segment are distinct and segments go to different states, so
+// plain byte read-modify-writes do not race -- and a byte store cannot touch the neighbouring state, which a dword
+// compare-and-swap at the edge of two states stride == N apart would.
+// off[0 .. nseg] ascending, off[0] <= i < off[nseg]: the segment s with off[s] <= i < off[s + 1] (the last such)
+template <class T>
+__device__ __forceinline__ uint32_t apply_multi_segment(const T *off, uint32_t nseg, T i) {
+    uint32_t lo = 0, hi = nseg;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) / 2;
+        if (off[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// lds != 0: the nstreams + 1 offsets fit the launch's dynamic LDS
+__global__ __launch_bounds__(256) void k_apply_multi(uint8_t *states, size_t stride, uint32_t nbytes, const uint32_t *offsets,
+                                                     const int32_t *xs, const uint8_t *diff, uint32_t nstreams, int lds) {
+    extern __shared__ uint32_t s_off[];
+    const uint32_t *off = offsets;
+    if (lds) {
+        for (uint32_t j = threadIdx.x; j <= nstreams; j += 256) s_off[j] = offsets[j];
+        __syncthreads();
+        off = s_off;
+    }
+    const uint32_t first = off[0], end = off[nstreams];
+    const uint32_t step = gridDim.x * 256u;
+    for (uint64_t i64 = (uint64_t)first + blockIdx.x * 256u + threadIdx.x; i64 < end; i64 += step) {
+        const uint32_t i = (uint32_t)i64;
+        const uint32_t x = (uint32_t)xs[i];
+        if (x >= nbytes) continue;
+        uint8_t *p = states + (size_t)apply_multi_segment(off, nstreams, i) * stride + x;
+        *p = (uint8_t)(*p + diff[i]);   // opencv.cpp:65
+    }
+}
+
+// The wire form: segment j of this launch is stream h.first + j, {u32 n, i32 xs[n], u8 diff[n]} at wire + h.pos[j], with
+// h.cum[j] entries in the segments before it (the host's headers; the header words in the buffer are not read).  xs is
+// read with byte alignment, as k_apply does.
+__global__ __launch_bounds__(256) void k_apply_multi_wire(uint8_t *states, size_t stride, uint32_t nbytes, const uint8_t *wire,
+                                                          const ApplyMultiWireArgs h) {
+    __shared__ uint64_t s_cum[kApplyMultiWireStreams + 1], s_pos[kApplyMultiWireStreams];
+    const uint32_t nseg = (uint32_t)h.count;
+    for (uint32_t j = threadIdx.x; j <= nseg; j += 256) {
+        s_cum[j] = h.cum[j];
+        if (j < nseg) s_pos[j] = h.pos[j];
+    }
+    __syncthreads();
+    const uint64_t end = s_cum[nseg];
+    const uint32_t step = gridDim.x * 256u;
+    for (uint64_t i = blockIdx.x * 256u + threadIdx.x; i < end; i += step) {
+        const uint32_t seg = apply_multi_segment(s_cum, nseg, i);
+        const uint64_t j = i - s_cum[seg], cnt = s_cum[seg + 1] - s_cum[seg];
+        const uint8_t *rec_xs = wire + s_pos[seg] + 4, *rec_diff = rec_xs + 4 * cnt;   // opencv.cpp:52-62
+        const uint32_t x = load_u32_unaligned(rec_xs + 4 * j);
+        if (x >= nbytes) continue;
+        uint8_t *p = states + (size_t)(h.first + seg) * stride + x;
+        *p = (uint8_t)(*p + rec_diff[j]);
+    }
+}
+
+hipError_t launch_apply_multi(uint8_t *states, size_t stride, uint32_t nbytes, const uint32_t *d_offsets, const int32_t *xs,
+                              const uint8_t *diff, int nstreams, hipStream_t s) {
+    // device-side counts: a fixed grid strides over whatever the segments hold
+    const size_t words = (size_t)nstreams + 1;
+    const bool lds = words <= 8192;   // 32 KiB; more streams than that search the offsets where they are
+    hipLaunchKernelGGL(k_apply_multi, dim3(1024), dim3(256), lds ? words * sizeof(uint32_t) : 0, s, states, stride, nbytes,
+                       d_offsets, xs, diff, (uint32_t)nstreams, lds ? 1 : 0);
+    return hipGetLastError();
+}
+
+hipError_t launch_apply_multi_wire(uint8_t *states, size_t stride, uint32_t nbytes, const uint8_t *wire,
+                                   const ApplyMultiWireArgs &h, hipStream_t s) {
+    const uint64_t total = h.cum[h.count];
+    if (total == 0) return hipSuccess;
+    const uint64_t blocks = (total + 255u) / 256u;
+    hipLaunchKernelGGL(k_apply_multi_wire, dim3((uint32_t)(blocks > 2048u ? 2048u : blocks)), dim3(256), 0, s, states, stride,
+                       nbytes, wire, h);
     return hipGetLastError();
 }
 
@@ -559,6 +644,43 @@ __device__ __forceinline__ CwaBlock cwa_block_load(const CwaArgs &a, const CwaFr
     return b;
 }
 
+// Record f's entries from directory word dr = {first entry, its escape rank, running index before it} on, added to the tile
+// [lo, hi) in LDS (s[0] is byte lo).  b: the first block (cwa_block_load at dr.x).  One wave.  The decode loop of the GPU
+// clients, once: k_cwa_apply runs it per frame of a slice, k_cwa_apply_multi per stream.
+__device__ __forceinline__ void cwa_apply_record(uint8_t *s, const CwaArgs &a, const CwaFrame &f, const uint4 dr, CwaBlock b,
+                                                 uint32_t lo, uint32_t hi, int lane) {
+    const CwireSections<const uint8_t> sec = cwa_sections(a, f);
+    const uint32_t *code = sec.code32(), *esc = sec.esc32(), *dif = sec.diff32();
+    uint32_t k = dr.x, rank = dr.y, x = dr.z;
+    bool first = true;
+    while (k < f.n) {
+        const uint32_t ka = k & ~3u, d = ka / 4 + lane;
+        if (!first) {
+            b.word = 4 * d < f.n ? code[d] : 0u;
+            b.dw = 4 * d < f.n ? dif[d] : 0u;
+        }
+        first = false;
+        bool in[4], fl[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) in[j] = 4 * d + j >= k && 4 * d + j < f.n;
+        uint32_t wtot;
+        const uint32_t before = cwire_escapes_before(b.word, in, fl, wtot);
+        uint32_t inc[4], rk[4];
+        bool bad[4];
+        const uint32_t lsum = cwire_decode4(b.word, in, fl, rank + before, f.e, esc, inc, bad, rk);
+        rank += wtot;
+        uint32_t xi = block_exclusive_scan<1>(lsum, (uint32_t *)nullptr, x);   // a single wave: no LDS, no barrier
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            xi += inc[j];
+            const uint32_t idx = xi - 1u;   // (inc 0: a bad escape or a masked entry, nothing to apply)
+            if (inc[j] && idx >= lo && idx < hi) s[idx - lo] = (uint8_t)(s[idx - lo] + (b.dw >> (8 * j)));
+        }
+        k = ka + 256;
+        if (x >= hi) break;   // the next entry's index is at least x
+    }
+}
+
 __global__ __launch_bounds__(64) void k_cwa_apply(const CwaArgs a, int nframes) {
     __shared__ cwa_u32x4 s_q[kCwaTile / 16];
     uint8_t *s = (uint8_t *)s_q;
@@ -580,7 +702,7 @@ __global__ __launch_bounds__(64) void k_cwa_apply(const CwaArgs a, int nframes) 
     for (int t = 0; t < nframes; t++) {
         const CwaFrame f = f1;
         const uint4 dr = d1;
-        CwaBlock b = b1;
+        const CwaBlock b = b1;
         if (t + 1 < nframes) {
             f1 = f2;
             d1 = d2;
@@ -590,36 +712,7 @@ __global__ __launch_bounds__(64) void k_cwa_apply(const CwaArgs a, int nframes) 
             f2 = a.ftab[t + 2];
             d2 = a.dir[(size_t)(t + 2) * a.ntiles + tile];
         }
-        const CwireSections<const uint8_t> sec = cwa_sections(a, f);
-        const uint32_t *code = sec.code32(), *esc = sec.esc32(), *dif = sec.diff32();
-        uint32_t k = dr.x, rank = dr.y, x = dr.z;
-        bool first = true;
-        while (k < f.n) {
-            const uint32_t ka = k & ~3u, d = ka / 4 + lane;
-            if (!first) {
-                b.word = 4 * d < f.n ? code[d] : 0u;
-                b.dw = 4 * d < f.n ? dif[d] : 0u;
-            }
-            first = false;
-            bool in[4], fl[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) in[j] = 4 * d + j >= k && 4 * d + j < f.n;
-            uint32_t wtot;
-            const uint32_t before = cwire_escapes_before(b.word, in, fl, wtot);
-            uint32_t inc[4], rk[4];
-            bool bad[4];
-            const uint32_t lsum = cwire_decode4(b.word, in, fl, rank + before, f.e, esc, inc, bad, rk);
-            rank += wtot;
-            uint32_t xi = block_exclusive_scan<1>(lsum, (uint32_t *)nullptr, x);   // a single wave: no LDS, no barrier
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                xi += inc[j];
-                const uint32_t idx = xi - 1u;   // (inc 0: a bad escape or a masked entry, nothing to apply)
-                if (inc[j] && idx >= lo && idx < hi) s[idx - lo] = (uint8_t)(s[idx - lo] + (b.dw >> (8 * j)));
-            }
-            k = ka + 256;
-            if (x >= hi) break;   // the next entry's index is at least x
-        }
+        cwa_apply_record(s, a, f, dr, b, lo, hi, lane);
         __syncthreads();
         if (a.out) cwa_tile_store(a.out + (size_t)t * a.stride + lo, s, len, lane);
         __syncthreads();
@@ -629,12 +722,40 @@ __global__ __launch_bounds__(64) void k_cwa_apply(const CwaArgs a, int nframes) 
     for (uint32_t i = 16 * q + lane; i < len; i += 64) a.state[lo + i] = s[i];
 }
 
+// ---- mi355_apply_multi_cwire_batch: record s onto the caller's state s, one record each ------------------------------------
+// Grid of tiles x streams (workgroup w: stream w / ntiles, tile w % ntiles); a.state / a.stride are the caller's states.  The
+// directory says which entries of record s land in the tile -- [dir[s][tile].x, dir[s][tile + 1].x), the last tile's up to
+// n -- before a state byte is touched: a workgroup with none returns, so the traffic follows the changes and not N.  The
+// others load the tile, run the decode loop above once and store the tile back, non-temporal: whole 16-byte words when
+// the tile's address allows it (states and stride multiples of 16), bytes otherwise.  No store leaves the tile's own
+// [lo, hi) of states[s], so neighbouring states (stride == N, N odd) and the stride gap are never touched.
+__global__ __launch_bounds__(64) void k_cwa_apply_multi(const CwaArgs a) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
+    uint8_t *s = (uint8_t *)s_q;
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
+    const CwaFrame f = a.ftab[st];
+    const uint4 *dir = a.dir + (size_t)st * a.ntiles + tile;
+    const uint4 dr = dir[0];
+    const uint32_t kend = tile + 1 < a.ntiles ? dir[1].x : f.n;
+    if (dr.x >= kend || dr.x >= f.n) return;
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    uint8_t *tile_bytes = a.state + (size_t)st * a.stride + lo;
+    const CwaBlock b = cwa_block_load(a, f, dr.x, lane);
+    cwa_tile_load(s, tile_bytes, len, lane);
+    __syncthreads();
+    cwa_apply_record(s, a, f, dr, b, lo, lo + len, lane);
+    __syncthreads();
+    cwa_tile_store(tile_bytes, s, len, lane);
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 uint32_t cwa_chunks(uint32_t n) { return n ? (n + kCwaChunk - 1) / kCwaChunk : 1u; }
 uint32_t cwa_tiles(uint32_t nbytes) { return (nbytes + kCwaTile - 1) / kCwaTile; }
 
-hipError_t launch_cwire_apply(const CwaArgs &a, const CwaFrame *frames, int nframes, hipStream_t s) {
-    if (nframes <= 0 || a.ntiles == 0) return hipSuccess;
+// the directory of nframes records (k_cwa_table .. k_cwa_dir)
+static void launch_cwa_directory(const CwaArgs &a, const CwaFrame *frames, int nframes, hipStream_t s) {
     uint32_t nchunks = 0;
     CwaTableArgs h{};
     for (int i0 = 0; i0 < nframes; i0 += kCwaTableFrames) {
@@ -651,7 +772,19 @@ hipError_t launch_cwire_apply(const CwaArgs &a, const CwaFrame *frames, int nfra
     hipLaunchKernelGGL(k_cwa_escsum, dim3(nchunks), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_cwa_scan, dim3(nframes), dim3(256), 0, s, a, 1);
     hipLaunchKernelGGL(k_cwa_dir, dim3(nchunks), dim3(256), 0, s, a);
+}
+
+hipError_t launch_cwire_apply(const CwaArgs &a, const CwaFrame *frames, int nframes, hipStream_t s) {
+    if (nframes <= 0 || a.ntiles == 0) return hipSuccess;
+    launch_cwa_directory(a, frames, nframes, s);
     hipLaunchKernelGGL(k_cwa_apply, dim3(a.ntiles), dim3(64), 0, s, a, nframes);
+    return hipGetLastError();
+}
+
+hipError_t launch_cwire_apply_multi(const CwaArgs &a, const CwaFrame *records, int nstreams, hipStream_t s) {
+    if (nstreams <= 0 || a.ntiles == 0) return hipSuccess;
+    launch_cwa_directory(a, records, nstreams, s);
+    hipLaunchKernelGGL(k_cwa_apply_multi, dim3(a.ntiles * (uint32_t)nstreams), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

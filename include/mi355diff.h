@@ -82,7 +82,8 @@ typedef struct mi355_config {
  *      (mi355_diff_stream_batch)
  *   9  + mi355_diff_stream_cwire_batch (additions only)
  *   10 + mi355_apply_cwire_batch (additions only); + mi355_diff_multi_batch, mi355_diff_multi_wire_batch,
- *      mi355_diff_multi_cwire_batch (additions only: no existing argument list changed, so the number stays) */
+ *      mi355_diff_multi_cwire_batch (additions only: no existing argument list changed, so the number stays);
+ *      + mi355_apply_multi_batch, mi355_apply_multi_wire_batch, mi355_apply_multi_cwire_batch (additions only) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -271,6 +272,54 @@ int mi355_diff_multi_wire_batch(mi355_core *core, const void *d_frames, void *d_
                                 void *d_offsets, void *d_wire, size_t capacity_bytes);
 int mi355_diff_multi_cwire_batch(mi355_core *core, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
                                  void *d_offsets, void *d_frame_pos, void *d_cwire, size_t capacity_bytes);
+/* The receiving end of such a tick, client/opencv.cpp:50-66 for nstreams cameras in ONE call: segment or record s
+ * (0 <= s < nstreams <= max_batch) is applied to the N bytes at d_states + s*stride_bytes -- for each of its entries
+ * state[s][x] += diff (uint8 wrap-around) -- exactly what mi355_apply_batch / _wire_batch / _cwire_batch with nframes = 1 does
+ * on a client core whose state is states[s].  The core's own state is neither read nor written, and there is no
+ * d_frames_out: the caller's state is the frame to show.
+ * The inputs have the layout of the outputs of mi355_diff_multi_*: d_offsets is uint32[nstreams + 1] over (d_xs, d_diff); the
+ * wire form holds stream s at byte 4*s + 5*sum(h_counts[0..s)); the compact records lie back to back where h_counts[s] = n
+ * and h_escapes[s] = e put them.  The headers come from the host, as the client read them from the sockets; the header
+ * words in the buffer are skipped, not trusted.  A receiver that reads nstreams sockets stages the records back to back
+ * itself; a camera that sent nothing this tick is an n = 0 record (8 bytes compact, 4 bytes wire) whose contents are
+ * never read.
+ *   Written bytes: bytes of the states' region outside the N bytes of each state are never written, the stride gap
+ *   included, and record s never changes a byte of states[r], r != s -- also with stride_bytes == N and N no multiple of
+ *   4: every read-modify-write is of single bytes, or of a tile that lies within its state.
+ *   d_states and stride_bytes may have any alignment; the compact form moves whole 16-byte words when both are multiples
+ *   of 16, bytes otherwise.
+ *   Well-formed records: every state is bit-identical to mi355_cwire_apply_host on that stream's record, and to the
+ *   one-stream GPU forms on a core that holds that state.
+ *   Malformed compact content under consistent headers: the guarantees of mi355_apply_cwire_batch -- nothing is read
+ *   outside the records' span, nothing is written outside the nstreams states, an escape ranked at or past e and an index
+ *   >= N change nothing; beyond that only the malformed stream's own state is unspecified.
+ *   Refused with MI355_ERR_INVALID before anything is launched or written: a null core; nstreams outside [0, max_batch];
+ *   with nstreams > 0 a null input pointer, a null d_states or stride_bytes < N; h_escapes[s] > h_counts[s]; h_counts[s]
+ *   > N; d_cwire (arrays form: d_offsets or d_xs) not 4-byte aligned; wire and compact forms: an input span, known from
+ *   the host's headers, that overlaps the states' region [d_states, d_states + (nstreams-1)*stride_bytes + N).
+ *   nstreams == 0 does nothing and returns MI355_OK.
+ * Asynchronous on the core's stream.  Like every other consumer of a packed stream the call first waits for the last
+ * expansion of this core: mi355_diff_multi_cwire_batch followed by mi355_apply_multi_cwire_batch on the same core (a relay
+ * that checks what it forwards) needs no synchronisation in between.  Every later entry point of this core that reads
+ * the states finds them complete; with a caller's stream everything runs on it in call order.
+ * The compact form runs the directory kernels of mi355_apply_cwire_batch on the nstreams records and then ONE kernel on a
+ * grid of 4096-byte tiles x streams: a tile that no entry of its record lands in -- the directory says so before a state
+ * byte is touched -- is neither read nor written, the others are loaded, updated and stored back with non-temporal
+ * stores.  Traffic on the states is 2 * 4096 bytes per touched tile, not 2N per stream.  Six launches and one more per
+ * 128 streams, whatever nstreams; the arrays form is one launch (a lane finds its segment by binary search in the
+ * offsets), the wire form one per 128 streams.  No workspace beyond the scratch of mi355_apply_cwire_batch, which is sized
+ * for max_batch records.
+ * Measured (profiles/multi_client.json: 1080p, webcam-like input, microseconds per stream and tick, S = 4 / 16 / 64): the
+ * compact form 7.537 / 3.544 / 2.972 against 22.841 / 22.355 / 22.863 for S client cores calling
+ * mi355_apply_cwire_batch(nframes = 1) each.  That input touches all 1519 tiles of every state (its changes are sensor noise
+ * over the whole picture), so there the states still move 2N per stream; the tile skip pays on local changes. */
+int mi355_apply_multi_batch(mi355_core *core, const void *d_offsets, const void *d_xs, const void *d_diff,
+                            int nstreams, void *d_states, size_t stride_bytes);
+int mi355_apply_multi_wire_batch(mi355_core *core, const void *d_wire, const uint32_t *h_counts,
+                                 int nstreams, void *d_states, size_t stride_bytes);
+int mi355_apply_multi_cwire_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts,
+                                  const uint32_t *h_escapes, int nstreams, void *d_states,
+                                  size_t stride_bytes);
 
 /* The client's side, client/opencv.cpp:50-66: for every frame in order, state[xs[i]] += diff[i] (uint8
  * wrap-around) on the core's state (a client core is a core whose state was set to the received base frame,

@@ -21,6 +21,15 @@ Where the time goes (a run of its own; tracing slows the host, so no timing is t
 and compare k_diff_pack<true, true, false, true, true> (multi) with k_diff_pack<true, true, false, true, false> (pairs) in
 *_kernel_stats.csv; counters (--pmc) go in yet another run.
 
+The client leg (--legs client, a run of its own: `--legs client --streams 4,16,64` is how profiles/multi_client.json was
+taken) measures the receiving end of such ticks, in microseconds per stream and tick, ONE JSON line for all S:
+  multi_client   mi355_apply_multi_cwire_batch: one call per tick onto the S states in the caller's memory;
+  cores_client   S client cores, each apply_cwire_batch(nframes = 1) on its own record -- the only way before;
+  decode_arrays  cwire_decode_batch + mi355_apply_multi_batch: two calls per tick through the (offsets, xs, diff) arrays;
+and the bytes of the states the compact form moves per stream and tick: touched 4096-byte tiles x 2 x 4096, counted from
+the decoded indices.  The records are K ticks of a server core (diff_multi_cwire_batch on the same input), applied round
+and round: adding a record to a state is the same work whatever the state holds.
+
 Input: ONE webcam stream of S + K + 1 frames; stream s shows frame s + j at step j, so every tick of every stream is the
 step between two consecutive webcam frames, and a tick's S frames are one contiguous region.  j walks 1 .. K and back."""
 import argparse
@@ -162,16 +171,118 @@ def run(W, H, S, K, rounds, legs, have_multi):
     core.close()
 
 
+def run_client(W, H, S, K, rounds):
+    """The client leg for one S -> its dictionary."""
+    import numpy as np
+    from cudavideostream_amd import CUDACore, cwire_bytes_max
+    dev = torch.device("cuda", 0)
+    n = 3 * W * H
+    ticks = max(16, min(512, 4096 // S))
+    _, frames = synth.webcam_stream(S + K + 1, W, H, device=dev)
+    frames = frames.reshape(S + K + 1, n)
+    states0 = frames[:S].clone()
+    states = states0.clone()
+    cwcap = cwire_bytes_max(n, S)
+    d_off = torch.zeros(S + 1, dtype=torch.int32, device=dev)
+    d_pos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
+    d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
+    recs = []                                          # per recorded tick: (records, counts, escapes, positions)
+    with CUDACore(W, H, max_batch=S) as server:
+        for j in range(1, K + 1):
+            server.diff_multi_cwire_batch(frames[j:j + S], states, S, d_off, d_pos, d_cw, cwcap)
+            server.synchronize()
+            pos = d_pos.cpu().numpy().astype(np.int64)
+            counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
+            pad = (counts.astype(np.int64) + 3) & ~3
+            escapes = ((np.diff(pos) - 8 - 2 * pad) // 4).astype(np.uint32)
+            recs.append((d_cw[:int(pos[S])].clone(), counts, escapes, pos))
+    cap = max(int(r[1].sum()) for r in recs) + 16
+    d_xs = torch.empty(cap, dtype=torch.int32, device=dev)
+    d_df = torch.empty(cap, dtype=torch.uint8, device=dev)
+    client = CUDACore(W, H, max_batch=S)
+    cores = [CUDACore(W, H, max_batch=1) for _ in range(S)]
+    own = [[r[0][int(r[3][s]):int(r[3][s + 1])] for s in range(S)] for r in recs]   # camera s's record of tick k
+    hdr = [[(r[1][s:s + 1], r[2][s:s + 1]) for s in range(S)] for r in recs]
+    host0 = states0.cpu().numpy()
+    # touched tiles, from the decoded indices
+    touched = []
+    for r in recs:
+        client.cwire_decode_batch(r[0], r[1], r[2], S, d_off, d_xs, d_df, cap)
+        client.synchronize()
+        tot = int(r[1].sum())
+        seg = torch.repeat_interleave(torch.arange(S, device=dev), torch.from_numpy(r[1].astype(np.int64)).to(dev))
+        key = seg * ((n + 4095) // 4096) + d_xs[:tot].to(torch.int64) // 4096
+        touched.append(int(torch.unique(key).numel()))
+    torch.cuda.synchronize()
+
+    def leg_multi_client():
+        for t in range(ticks):
+            r = recs[t % K]
+            client.apply_multi_cwire_batch(r[0], r[1], r[2], S, states)
+        client.synchronize()
+
+    def leg_cores_client():
+        for t in range(ticks):
+            k = t % K
+            for s, c in enumerate(cores):
+                c.apply_cwire_batch(own[k][s], hdr[k][s][0], hdr[k][s][1], 1)
+        for c in cores:
+            c.synchronize()
+
+    def leg_decode_arrays():
+        for t in range(ticks):
+            r = recs[t % K]
+            client.cwire_decode_batch(r[0], r[1], r[2], S, d_off, d_xs, d_df, cap)
+            client.apply_multi_batch(d_off, d_xs, d_df, S, states)
+        client.synchronize()
+
+    table = {"multi_client": leg_multi_client, "cores_client": leg_cores_client, "decode_arrays": leg_decode_arrays}
+    times = {}
+    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
+        for name, leg in table.items():
+            states.copy_(states0)
+            if name == "cores_client":
+                for s, c in enumerate(cores):
+                    c.set_state(host0[s])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            leg()
+            dt = time.perf_counter() - t0
+            if r:
+                times.setdefault(name, []).append(dt * 1e6 / (ticks * S))
+    out = {"streams": S, "ticks": ticks, "changed_bytes_per_stream": round(sum(int(r[1].sum()) for r in recs) / (K * S), 1),
+           "record_bytes_per_stream": round(sum(int(r[3][S]) for r in recs) / (K * S), 1),
+           "touched_tiles_per_stream": round(sum(touched) / (K * S), 1), "tiles_per_state": (n + 4095) // 4096,
+           "state_bytes_moved_per_stream": round(sum(touched) * 2 * 4096 / (K * S), 1), "state_bytes_2N": 2 * n}
+    for name in table:
+        out[name + "_us_per_stream"] = stats(times[name])
+    med = {k: statistics.median(v) for k, v in times.items()}
+    out["cores_client_over_multi_client"] = round(med["cores_client"] / med["multi_client"], 2)
+    out["decode_arrays_over_multi_client"] = round(med["decode_arrays"] / med["multi_client"], 2)
+    for c in cores:
+        c.close()
+    client.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", default="1920x1080")
     ap.add_argument("--streams", default="8,64,256")
     ap.add_argument("--steps", type=int, default=8, help="K: webcam frames a stream walks through")
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--legs", default="multi,cores_loop,pairs", help="of multi, cores_loop, pairs, write_probe")
+    ap.add_argument("--legs", default="multi,cores_loop,pairs", help="of multi, cores_loop, pairs, write_probe; or client alone")
     a = ap.parse_args()
     have = load_library()
     W, H = (int(v) for v in a.size.split("x"))
+    if a.legs == "client":
+        per = []
+        for S in (int(v) for v in a.streams.split(",")):
+            per.append(run_client(W, H, S, a.steps, a.rounds))
+            torch.cuda.empty_cache()
+        print(json.dumps({"bench": "multi_client", "size": f"{W}x{H}", "input": "synth.webcam_stream", "rounds": a.rounds,
+                          "steps": a.steps, "client": per}), flush=True)
+        return
     for S in (int(v) for v in a.streams.split(",")):
         run(W, H, S, a.steps, a.rounds, set(a.legs.split(",")), have)
         torch.cuda.empty_cache()

@@ -16,8 +16,12 @@
 // --compact --gpu-client: the client core also uploads the received records and applies them in one call
 // (mi355_apply_cwire_batch) into its shown frames; every shown frame must equal the host client's frame after that record,
 // and the client core's state the server's state after every batch.
+// --compact --multi S: many cameras per GPU, both ends.  A server core runs T ticks of S synthetic cameras through
+// mi355_diff_multi_cwire_batch; each tick's records (headers included) cross the pipe; a client core uploads them and applies
+// them in one call (mi355_apply_multi_cwire_batch) onto S states of its own.  After every tick the client's states must equal
+// the server's, byte for byte, and after the last tick the frames a host client (mi355_cwire_apply_host) rebuilt per camera.
 //
-//   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B] [--compact [--direct] [--gpu-client]]
+//   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B] [--compact [--direct] [--gpu-client] [--multi S]]
 //   exit status 0 = all checks passed
 #include <cstdint>
 #include <cstdio>
@@ -72,8 +76,100 @@ static bool through_pipe(int wfd, int rfd, const uint8_t *src, uint8_t *dst, siz
     return true;
 }
 
+// --compact --multi S (see the head of the file)
+static int run_multi(int w, int h, int T, int S) {
+    const size_t n = (size_t)3 * w * h;
+    mi355_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.width = w; cfg.height = h; cfg.threshold = 20; cfg.max_batch = S; cfg.device = -1;
+    mi355_core *server = nullptr, *client = nullptr;
+    OK(mi355_create(&cfg, &server));
+    OK(mi355_create(&cfg, &client));
+    const size_t cw_cap = mi355_cwire_bytes_max(n, S);
+    void *d_frames = nullptr, *d_sstates = nullptr, *d_off = nullptr, *d_pos = nullptr, *d_cw = nullptr;   // server
+    void *d_rx = nullptr, *d_cstates = nullptr;                                                              // client
+    OK(mi355_dev_alloc(server, &d_frames, (size_t)S * n));
+    OK(mi355_dev_alloc(server, &d_sstates, (size_t)S * n));
+    OK(mi355_dev_alloc(server, &d_off, sizeof(uint32_t) * (S + 1)));
+    OK(mi355_dev_alloc(server, &d_pos, sizeof(uint64_t) * (S + 1)));
+    OK(mi355_dev_alloc(server, &d_cw, cw_cap));
+    OK(mi355_dev_alloc(client, &d_rx, cw_cap));
+    OK(mi355_dev_alloc(client, &d_cstates, (size_t)S * n));
+    int fds[2];
+    if (pipe(fds) != 0) return 1;
+    // every camera's base frame: the server's states, and through the pipe the client's (opencv.cpp:38-46 per camera)
+    std::vector<uint8_t> bases((size_t)S * n), host_frames((size_t)S * n), frames((size_t)S * n), s_states((size_t)S * n),
+        c_states((size_t)S * n), cw_host(cw_cap), rx(cw_cap);
+    for (int s = 0; s < S; s++)
+        for (size_t i = 0; i < n; i++) bases[(size_t)s * n + i] = (uint8_t)(40 + (i * 7 + (size_t)s * 31) % 150);
+    OK(mi355_upload(server, d_sstates, bases.data(), bases.size()));
+    if (!through_pipe(fds[1], fds[0], bases.data(), host_frames.data(), bases.size())) return 1;
+    OK(mi355_upload(client, d_cstates, host_frames.data(), host_frames.size()));
+    std::vector<uint8_t> base(n), frame(n);
+    std::vector<uint32_t> off(S + 1), counts(S), escapes(S);
+    std::vector<uint64_t> pos(S + 1);
+    size_t sent_bytes = 0, changed = 0;
+    int max_err = 0;
+    for (int t = 0; t < T; t++) {
+        for (int s = 0; s < S; s++) {   // camera s: its own base, its block a few steps ahead of its neighbour's
+            memcpy(base.data(), &bases[(size_t)s * n], n);
+            make_frame(frame, base, w, h, t + 5 * s);
+            memcpy(&frames[(size_t)s * n], frame.data(), n);
+        }
+        // ---- server: one tick -> S records
+        OK(mi355_upload(server, d_frames, frames.data(), frames.size()));
+        OK(mi355_diff_multi_cwire_batch(server, d_frames, d_sstates, n, S, d_off, d_pos, d_cw, cw_cap));
+        OK(mi355_download(server, off.data(), d_off, sizeof(uint32_t) * (S + 1)));
+        OK(mi355_download(server, pos.data(), d_pos, sizeof(uint64_t) * (S + 1)));
+        if (pos[S] > cw_cap) { fprintf(stderr, "compact stream larger than its bound\n"); return 1; }
+        const size_t cb = (size_t)pos[S];
+        OK(mi355_download(server, cw_host.data(), d_cw, cb));
+        changed += off[S];
+        // ---- the sockets (one pipe here: the receiver stages the cameras' records back to back)
+        if (!through_pipe(fds[1], fds[0], cw_host.data(), rx.data(), cb)) return 1;
+        sent_bytes += cb;
+        // ---- client: the headers as read from the stream, one upload, one call
+        size_t p = 0;
+        for (int s = 0; s < S; s++) {
+            if (p + 8 > cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
+            memcpy(&counts[s], rx.data() + p, 4);
+            memcpy(&escapes[s], rx.data() + p + 4, 4);
+            size_t used = 0;   // ... and the host client of camera s beside it
+            OK(mi355_cwire_apply_host(&host_frames[(size_t)s * n], n, rx.data() + p, cb - p, 1, &used));
+            if (used != mi355_cwire_frame_bytes(counts[s], escapes[s])) { fprintf(stderr, "stream framing broken\n"); return 1; }
+            p += used;
+        }
+        if (p != cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
+        OK(mi355_upload(client, d_rx, rx.data(), cb));
+        OK(mi355_apply_multi_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, d_cstates, n));
+        // ---- checks
+        OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
+        OK(mi355_download(server, s_states.data(), d_sstates, s_states.size()));
+        if (memcmp(s_states.data(), c_states.data(), s_states.size()) != 0) {
+            fprintf(stderr, "tick %d: client states != server states\n", t);
+            return 1;
+        }
+        for (size_t i = 0; i < c_states.size(); i++) {
+            const int e = abs((int)c_states[i] - (int)frames[i]);
+            if (e > max_err) max_err = e;
+        }
+    }
+    if (memcmp(host_frames.data(), c_states.data(), c_states.size()) != 0) { fprintf(stderr, "client states != host client frames\n"); return 1; }
+    if (max_err > cfg.threshold) { fprintf(stderr, "rebuilt frame off by %d > threshold\n", max_err); return 1; }
+    void *srv[] = {d_frames, d_sstates, d_off, d_pos, d_cw};
+    for (void *q : srv) OK(mi355_dev_free(server, q));
+    OK(mi355_dev_free(client, d_rx));
+    OK(mi355_dev_free(client, d_cstates));
+    mi355_destroy(server);
+    mi355_destroy(client);
+    printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"width\": %d, \"height\": %d, \"ticks\": %d, "
+           "\"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d}\n",
+           S, w, h, T, changed, sent_bytes, mi355_wire_bytes(T * S, changed), (size_t)T * S * n, max_err);
+    return 0;
+}
+
 int main(int argc, char **argv) {
-    int w = 320, h = 180, T = 24, B = 8;
+    int w = 320, h = 180, T = 24, B = 8, multi = 0;
     bool compact = false, direct = false, gpu_client = false;
     for (int i = 1; i < argc; i++) {
         if (std::string(argv[i]) == "--compact") compact = true;
@@ -88,6 +184,11 @@ int main(int argc, char **argv) {
         const int v = atoi(argv[i + 1]);
         if (k == "--width") w = v; else if (k == "--height") h = v;
         else if (k == "--frames") T = v; else if (k == "--batch") B = v;
+        else if (k == "--multi") multi = v;
+    }
+    if (multi) {
+        if (!compact || direct || gpu_client || multi < 0) { fprintf(stderr, "--multi S needs --compact alone and S >= 1\n"); return 2; }
+        return run_multi(w, h, T, multi);
     }
     const size_t n = (size_t)3 * w * h;
     mi355_config cfg;
