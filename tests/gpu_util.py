@@ -41,6 +41,70 @@ def to_dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
 
 
+GUARD = 0x5C
+PAD = 256            # guard elements before and behind every guarded buffer
+_FILL = {torch.uint8: GUARD, torch.int32: -7, torch.int64: -3}
+
+
+class Guarded:
+    """`count` elements of `dtype` with PAD guard elements before and behind them, the first of them `skew` elements behind
+    an aligned address.  Everything starts as the guard value of its type; get() asserts that the guards still hold it.
+    Hand `ptr` to the library (the view `t` is empty for count == 0)."""
+
+    def __init__(self, count, dtype=torch.uint8, skew=0, data=None):
+        self.count, self.lo, self.fill = int(count), PAD + skew, _FILL[dtype]
+        self.buf = torch.full((self.lo + self.count + PAD,), self.fill, dtype=dtype, device=DEV)
+        self.t = self.buf[self.lo:self.lo + self.count]
+        self.ptr = self.buf.data_ptr() + self.lo * self.buf.element_size()
+        if data is not None and self.count:
+            self.t.copy_(to_dev(data))
+
+    def get(self, written=None):
+        """The count elements (numpy); only the first `written` of them may have been written."""
+        h = self.buf.cpu().numpy()
+        assert (h[:self.lo] == self.fill).all(), "written before the buffer"
+        assert (h[self.lo + self.count:] == self.fill).all(), "written behind the buffer"
+        body = h[self.lo:self.lo + self.count]
+        if written is not None:
+            assert (body[written:] == self.fill).all(), "written behind the part that was to be written"
+        return body
+
+
+class Region:
+    """S frames of n bytes, `stride` apart, in a guarded device buffer, the first `skew` bytes behind an aligned address.
+    Every byte outside the S frames -- before, behind, and in the stride gaps -- holds GUARD; get() asserts that it still
+    does."""
+
+    def __init__(self, S, n, stride=None, skew=0):
+        self.S, self.n, self.stride, self.skew = S, n, n if stride is None else stride, skew
+        self.lo = PAD + skew
+        self.buf = torch.full((self.lo + max(S, 1) * self.stride + PAD,), GUARD, dtype=torch.uint8, device=DEV)
+        self.t = self.buf[self.lo:]
+        self.ptr = self.t.data_ptr()
+        assert self.buf.data_ptr() % 16 == 0 and self.ptr % 16 == skew % 16
+
+    def put(self, rows):
+        h = np.full(self.buf.numel(), GUARD, np.uint8)
+        for s, row in enumerate(rows):
+            h[self.lo + s * self.stride:self.lo + s * self.stride + self.n] = row
+        self.buf.copy_(to_dev(h))
+        return self
+
+    def get(self):
+        """(rows as numpy [S, n]); asserts the guard bytes."""
+        h = self.buf.cpu().numpy()
+        keep = np.zeros(h.size, bool)
+        for s in range(self.S):
+            keep[self.lo + s * self.stride:self.lo + s * self.stride + self.n] = True
+        assert (h[~keep] == GUARD).all(), "bytes outside the frames were written"
+        return h[keep].reshape(self.S, self.n)
+
+    def clone(self):
+        r = Region(self.S, self.n, self.stride, self.skew)
+        r.buf.copy_(self.buf)
+        return r
+
+
 def run_stream(core, frames, capacity=None, stride=None, pair_prev=None):
     """frames: (T, N) uint8 numpy or cuda tensor.  Returns (offsets, xs, diff) as numpy, with xs/diff
     cut to min(total, capacity)."""
