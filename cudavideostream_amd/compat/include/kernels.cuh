@@ -54,6 +54,11 @@ public:
     // nstreams <= MI355_MAX_BATCH of the environment when the object was made (default 1: the reference's one stream).
     void exec_multi(const void *d_frames, void *d_states, size_t stride, int nstreams, void *d_offsets, void *d_xs,
                     void *d_diff, size_t capacity);
+    // nframes frames of each of nstreams cameras in one call (include/mi355diff.h, mi355_diff_multi_stream_batch): frame t of
+    // camera s at d_frames + (s*nframes + t)*stride, its state at d_states + s*stride; segments s*nframes .. (s+1)*nframes - 1
+    // of (d_offsets, d_xs, d_diff) are its packed frames.  Blocking, like exec_multi; nstreams*nframes <= MI355_MAX_BATCH.
+    void exec_multi_stream(const void *d_frames, void *d_states, size_t stride, int nstreams, int nframes, void *d_offsets,
+                           void *d_xs, void *d_diff, size_t capacity);
     // The receiving end of such a tick (include/mi355diff.h, mi355_apply_multi_cwire_batch): the compact record of camera s
     // -- records back to back in DEVICE memory, headers counts[s] / escapes[s] as read from the sockets -- is applied to the
     // frame at d_states + s*stride, which is then the frame to show.  Blocking, like exec_multi; the same nstreams bound.

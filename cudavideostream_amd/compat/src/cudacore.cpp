@@ -97,6 +97,13 @@ void CUDACore::exec_multi(const void *d_frames, void *d_states, size_t stride, i
     MI355_CHECK(mi355_synchronize(core_));
 }
 
+void CUDACore::exec_multi_stream(const void *d_frames, void *d_states, size_t stride, int nstreams, int nframes,
+                                 void *d_offsets, void *d_xs, void *d_diff, size_t capacity) {
+    MI355_CHECK(mi355_diff_multi_stream_batch(core_, d_frames, d_states, stride, nstreams, nframes, d_offsets, d_xs, d_diff,
+                                              capacity));
+    MI355_CHECK(mi355_synchronize(core_));
+}
+
 void CUDACore::apply_multi(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, int nstreams, void *d_states,
                            size_t stride) {
     MI355_CHECK(mi355_apply_multi_cwire_batch(core_, d_cwire, counts, escapes, nstreams, d_states, stride));

@@ -273,6 +273,36 @@ class CUDACore:
                                                         _ptr(d_offsets), _ptr(d_frame_pos), _ptr(d_cwire),
                                                         int(capacity_bytes)))
 
+    # -- many streams, many frames each: frame t of stream s at d_frames[s * nframes + t], batch index s * nframes + t ---------
+    def diff_multi_stream_batch(self, d_frames, d_states, nstreams, nframes, d_offsets, d_xs, d_diff, capacity, stride=None):
+        """nframes frames of each of nstreams streams: what diff_stream_batch(nframes) does on a core whose state is
+        d_states[s], for every s; segments s * nframes .. (s + 1) * nframes - 1 of (d_offsets, d_xs, d_diff) are stream s's
+        packed frames.  The core's own state is not involved."""
+        self._hold(d_frames, d_states, d_offsets, d_xs, d_diff)
+        stride = self.total if stride is None else stride
+        _l.check(self._lib.mi355_diff_multi_stream_batch(self._h, _ptr(d_frames), _ptr(d_states), int(stride), int(nstreams),
+                                                         int(nframes), _ptr(d_offsets), _ptr(d_xs), _ptr(d_diff),
+                                                         int(capacity)))
+
+    def diff_multi_stream_wire_batch(self, d_frames, d_states, nstreams, nframes, d_offsets, d_wire, capacity_bytes,
+                                     stride=None):
+        """diff_multi_stream_batch into the sender's byte stream: {u32 n, i32 xs[n], u8 diff[n]} per batch index."""
+        self._hold(d_frames, d_states, d_offsets, d_wire)
+        stride = self.total if stride is None else stride
+        _l.check(self._lib.mi355_diff_multi_stream_wire_batch(self._h, _ptr(d_frames), _ptr(d_states), int(stride),
+                                                              int(nstreams), int(nframes), _ptr(d_offsets), _ptr(d_wire),
+                                                              int(capacity_bytes)))
+
+    def diff_multi_stream_cwire_batch(self, d_frames, d_states, nstreams, nframes, d_offsets, d_frame_pos, d_cwire,
+                                      capacity_bytes, stride=None):
+        """diff_multi_stream_batch into compact records: batch index b's record at d_frame_pos[b]
+        (uint64[nstreams * nframes + 1])."""
+        self._hold(d_frames, d_states, d_offsets, d_frame_pos, d_cwire)
+        stride = self.total if stride is None else stride
+        _l.check(self._lib.mi355_diff_multi_stream_cwire_batch(self._h, _ptr(d_frames), _ptr(d_states), int(stride),
+                                                               int(nstreams), int(nframes), _ptr(d_offsets),
+                                                               _ptr(d_frame_pos), _ptr(d_cwire), int(capacity_bytes)))
+
     # ... and their receiving end: segment / record s onto d_states[s], the frame to show
     def apply_multi_batch(self, d_offsets, d_xs, d_diff, nstreams, d_states, stride=None):
         """client/opencv.cpp:64-66 for one tick of nstreams streams: segment s of (d_offsets, d_xs, d_diff) is added to

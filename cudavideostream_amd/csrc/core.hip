@@ -355,6 +355,10 @@ struct CwireOut {
 // cw != nullptr: the log is expanded into compact records (launch_expand_cwire) instead.
 // feedback (pair mode): d_prev are the caller's states, one per batch index, and take the fed-back state of their frame
 // (mi355_diff_multi_*); the operands do not overlap (the entry points refuse that).
+// seg > 0 (stream mode, feedback): nframes / seg streams of seg frames each, batch index s * seg + t; d_prev are the caller's
+// states, one per STREAM (mi355_diff_multi_stream_*).  A tile of a state is read and written by the launches of one stream only,
+// exactly as with feedback pairs (the cut depends on the frame size alone), so the two forms share the fb_states bookkeeping
+// and may alternate on the same states.
 // pipelined: a public batch entry point on the core's OWN stream -- the index and the expansion run on the side
 // stream beside the next batch's pack kernel (which needs only the state, carried on the core's stream, and a free
 // set of logs); completion is what mi355_synchronize / any other entry point waits for (use_device joins).  With a
@@ -374,7 +378,8 @@ CwireDirectArgs cwire_args(mi355_core *c, const CwireOut *cw, const uint32_t *d_
 
 int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, size_t stride,
               int nframes, void *d_offsets, void *d_xs, void *d_diff, size_t capacity,
-              void *d_wire = nullptr, bool pipelined = false, const CwireOut *cw = nullptr, bool feedback = false) {
+              void *d_wire = nullptr, bool pipelined = false, const CwireOut *cw = nullptr, bool feedback = false,
+              int seg = 0) {
     if (!c) return fail(MI355_ERR_INVALID, "null core");
     if (nframes < 0 || nframes > c->cfg.max_batch)
         return fail(MI355_ERR_INVALID, "nframes outside [0, max_batch]");
@@ -429,8 +434,10 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
     if (tev) HIP_TRY(hipEventRecord(tev[0], c->stream));
     PackArgs a{};
     a.cur = (const uint8_t *)d_cur;
-    a.prev = (const uint8_t *)d_prev;
+    a.prev = seg ? nullptr : (const uint8_t *)d_prev;
     a.state = c->state;
+    a.seg = seg;
+    if (seg) a.states = (uint8_t *)const_cast<void *>(d_prev);
     a.stride = stride;
     a.n = c->n;
     a.nframes = nframes;
@@ -882,6 +889,47 @@ int mi355_diff_multi_cwire_batch(mi355_core *c, const void *d_frames, void *d_st
     const CwireOut cw{(uint64_t *)d_frame_pos, (uint8_t *)d_cwire, (uint64_t)capacity_bytes};
     return run_batch(c, true, d_frames, d_states, stride_bytes, nstreams, d_offsets, nullptr, nullptr, 0, nullptr, true, &cw,
                      true);
+}
+
+// mi355_diff_multi_stream_*: what the three forms refuse alike, before anything is launched
+static int check_multi_stream(mi355_core *c, const void *d_frames, const void *d_states, size_t stride, int nstreams, int nframes) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nstreams < 0 || nframes < 0) return fail(MI355_ERR_INVALID, "negative nstreams / nframes");
+    if ((int64_t)nstreams * nframes > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams * nframes above max_batch");
+    if (nstreams == 0 || nframes == 0) return MI355_OK;
+    if (!d_frames || !d_states) return fail(MI355_ERR_INVALID, "null d_frames / d_states");
+    if (stride < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
+    const uintptr_t f = (uintptr_t)d_frames, s = (uintptr_t)d_states;
+    const uintptr_t fspan = (uintptr_t)((int64_t)nstreams * nframes - 1) * stride + c->n, sspan = (uintptr_t)(nstreams - 1) * stride + c->n;
+    if (f < s + sspan && s < f + fspan) return fail(MI355_ERR_INVALID, "the states overlap the frames");
+    return MI355_OK;
+}
+
+int mi355_diff_multi_stream_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
+                                  int nframes, void *d_offsets, void *d_xs, void *d_diff, size_t capacity) {
+    if (int rc = check_multi_stream(c, d_frames, d_states, stride_bytes, nstreams, nframes)) return rc;
+    return run_batch(c, false, d_frames, d_states, stride_bytes, nstreams * nframes, d_offsets, d_xs, d_diff, capacity, nullptr, true,
+                     nullptr, true, nframes);
+}
+
+int mi355_diff_multi_stream_wire_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
+                                       int nframes, void *d_offsets, void *d_wire, size_t capacity_bytes) {
+    if (int rc = check_multi_stream(c, d_frames, d_states, stride_bytes, nstreams, nframes)) return rc;
+    if (!d_wire) return fail(MI355_ERR_INVALID, "null d_wire");
+    return run_batch(c, false, d_frames, d_states, stride_bytes, nstreams * nframes, d_offsets, nullptr, nullptr, capacity_bytes,
+                     d_wire, true, nullptr, true, nframes);
+}
+
+int mi355_diff_multi_stream_cwire_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
+                                        int nframes, void *d_offsets, void *d_frame_pos, void *d_cwire, size_t capacity_bytes) {
+    if (int rc = check_multi_stream(c, d_frames, d_states, stride_bytes, nstreams, nframes)) return rc;
+    if (!d_offsets || !d_frame_pos) return fail(MI355_ERR_INVALID, "null d_offsets / d_frame_pos");
+    if (capacity_bytes > 0 && !d_cwire) return fail(MI355_ERR_INVALID, "null d_cwire");
+    if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_frame_pos & 7u))
+        return fail(MI355_ERR_INVALID, "d_cwire and d_offsets must be 4-byte aligned, d_frame_pos 8-byte aligned");
+    const CwireOut cw{(uint64_t *)d_frame_pos, (uint8_t *)d_cwire, (uint64_t)capacity_bytes};
+    return run_batch(c, false, d_frames, d_states, stride_bytes, nstreams * nframes, d_offsets, nullptr, nullptr, 0, nullptr, true,
+                     &cw, true, nframes);
 }
 
 size_t mi355_wire_bytes(int nframes, uint64_t entries) { return 4 * (size_t)nframes + 5 * (size_t)entries; }

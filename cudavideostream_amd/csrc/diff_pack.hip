@@ -229,10 +229,59 @@ __device__ __forceinline__ void store_state(const PackArgs &a, const StateOut &s
     }
 }
 
-template <bool PAIR, bool FAST, bool HIGH, bool FB = false>
+// Segmented stream mode (mi355_diff_multi_stream_*: batch index b = s * a.seg + t, the caller's states): the wave walks all
+// the batch's frames as in stream mode and EXCHANGES the state it holds in front of every frame b with b % a.seg == 0 --
+// the state of the segment that ended goes back to states[b / seg - 1], the one of the segment that begins is taken.  The
+// exchange is a wave-uniform step between two frames of a register group; the frame loads, the log and the meta words do not
+// know of it.
+struct Seg {
+    int32_t left;    // frames until the next exchange (0: in front of the next frame); wave-uniform
+    int32_t next;    // the stream whose state is taken then; wave-uniform
+    uint32_t chg;    // per lane: not 0 once one of the lane's 16 bytes was flagged since the last exchange
+    uint32_t byte_off;
+};
+
+// The lane's 16 bytes of stream k's state.  Always issued (want == false: an offset beyond the descriptor, nothing is read),
+// for the reason Group's loads are.
+template <bool FAST>
+__device__ __forceinline__ uint4 load_seg_state(const PackArgs &a, int32_t k, uint32_t byte_off, int valid, bool want) {
+    const uint8_t *base = uniform_ptr(a.states + (size_t)k * a.stride);
+    if (FAST) {
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(make_rsrc(base, a.n), want ? byte_off : kOOB, 0, kStateLoadAux);
+        return make_uint4(v.x, v.y, v.z, v.w);
+    }
+    return load16_bytes(base + byte_off, want ? valid : 0);
+}
+
+// ... and back: only a lane that has seen a flagged byte during the segment holds anything new (store_state)
+template <bool FAST>
+__device__ __forceinline__ void store_seg_state(const PackArgs &a, int32_t k, const Seg &sg, uint4 st, int valid) {
+    uint8_t *base = const_cast<uint8_t *>(uniform_ptr(a.states + (size_t)k * a.stride));
+    if (FAST) {
+        const u32x4 v = {st.x, st.y, st.z, st.w};
+        __builtin_amdgcn_raw_buffer_store_b128(v, make_rsrc(base, a.n), sg.chg != 0u ? sg.byte_off : kOOB, 0, kStateStoreAux);
+    } else {
+        store16_bytes(base + sg.byte_off, st, sg.chg != 0u ? valid : 0);
+    }
+}
+
+// ns: the state the group's loads brought along -- that of the FIRST exchange inside the group (with a.seg >= kPrefetch the
+// only one); a further one (segments shorter than a group) waits for its load
+template <bool FAST>
+__device__ __forceinline__ void exchange_state(const PackArgs &a, Seg &sg, uint4 &st, const uint4 &ns, bool first, int valid) {
+    if (sg.next > 0) store_seg_state<FAST>(a, sg.next - 1, sg, st, valid);
+    st = first ? ns : load_seg_state<FAST>(a, sg.next, sg.byte_off, valid, true);
+    sg.next += 1;
+    sg.left = a.seg;
+    sg.chg = 0u;
+}
+
+template <bool PAIR, bool FAST, bool HIGH, bool FB = false, bool SEG = false>
 __device__ __forceinline__ void pack_group(const PackArgs &a, const Group<PAIR, FAST> &g, int t0, uint4 &st,
                                            LogPos &lp, uint32_t tile, ThrConst tc, int lane, const LogOut &lg,
-                                           const StateOut *so = nullptr, int valid = 16) {
+                                           const StateOut *so = nullptr, int valid = 16, Seg *sg = nullptr,
+                                           const uint4 *ns = nullptr) {
+    bool first = true;   // SEG: no exchange inside this group yet
     // The group's kPrefetch meta words are assembled in lanes 0..kPrefetch-1 and leave with ONE store.
     constexpr int kPrefetch = PrefetchOf<PAIR>::value;
     uint4 meta = make_uint4(0, 0, 0, 0);
@@ -245,14 +294,24 @@ __device__ __forceinline__ void pack_group(const PackArgs &a, const Group<PAIR, 
         const bool two = t + 1 < a.nframes;
         uint32_t dm0[4], m0, m1 = 0, pc0, pm0, pc1 = 0, pm1 = 0;
         if (PAIR) st = g.p[d];
+        if (SEG) {
+            if (sg->left == 0) { exchange_state<FAST>(a, *sg, st, *ns, first, valid); first = false; }   // wave-uniform
+            sg->left -= 1;
+        }
         compare_step<HIGH>(g.c[d], st, tc, dm0, m0);
+        if (SEG) sg->chg |= m0;
         if (FB) store_state<FAST>(a, *so, d, st, m0, valid);
         const uint32_t c0 = emit_step(dm0, m0, lg, lp, jump, lane24, pc0, pm0);
         uint32_t c1 = 0;
         if (two) {
             if (PAIR) st = g.p[d + 1];
+            if (SEG) {
+                if (sg->left == 0) { exchange_state<FAST>(a, *sg, st, *ns, first, valid); first = false; }
+                sg->left -= 1;
+            }
             uint32_t dm1[4];
             compare_step<HIGH>(g.c[d + 1], st, tc, dm1, m1);
+            if (SEG) sg->chg |= m1;
             if (FB) store_state<FAST>(a, *so, d + 1, st, m1, valid);
             c1 = emit_step(dm1, m1, lg, lp, jump, lane24, pc1, pm1);
         }
@@ -275,7 +334,7 @@ __device__ __forceinline__ void pack_group(const PackArgs &a, const Group<PAIR, 
     __builtin_amdgcn_raw_buffer_store_b128(mv, lg.meta, (lane < kPrefetch && t0 + lane < a.nframes) ? moff : kOOB, 0, 0);
 }
 
-template <bool PAIR, bool FAST, bool HIGH, bool ONCE, bool FB = false>
+template <bool PAIR, bool FAST, bool HIGH, bool ONCE, bool FB = false, bool SEG = false>
 __device__ __forceinline__ void pack_tile(const PackArgs &a, uint32_t tile, uint32_t byte_off,
                                           int valid, int lane) {
     const int T = a.nframes;
@@ -284,7 +343,7 @@ __device__ __forceinline__ void pack_tile(const PackArgs &a, uint32_t tile, uint
     const LogOut lg{make_rsrc(a.codes, a.codes_bytes), make_rsrc(a.rec, a.rec_bytes), make_rsrc(a.meta, a.meta_bytes)};
 
     uint4 st = make_uint4(0, 0, 0, 0);
-    if (!PAIR) st = load16<FAST>(a.state + byte_off, valid);
+    if (!PAIR && !SEG) st = load16<FAST>(a.state + byte_off, valid);
 
     // Two register groups: while one is processed (its stores are issued), the other's loads are in
     // flight.
@@ -292,6 +351,17 @@ __device__ __forceinline__ void pack_tile(const PackArgs &a, uint32_t tile, uint
     LogPos lp{tile * 1024u, 256u, tile * 1024u, 64u};   // codes / records this tile has appended to its logs so far
     constexpr int kPrefetch = PrefetchOf<PAIR>::value;
     const size_t gstep = (size_t)kPrefetch * a.stride;
+    // SEG: the first exchange (in front of frame 0) takes states[0] and stores nothing.  A group's loads bring the state of
+    // the first exchange inside the group along (pk: the next stream whose state nobody has asked for, pf: its first frame),
+    // so that its latency is hidden behind the group before, like the frames'.
+    Seg sg{0, 0, 0u, byte_off};
+    int32_t pk = 0, pf = 0;
+    uint4 na = st, nb = st;
+    auto prefetch_state = [&](int t0) {
+        const uint4 v = load_seg_state<FAST>(a, pk, byte_off, valid, pf < t0 + kPrefetch && pf < T);
+        while (pf < t0 + kPrefetch) { pf += a.seg; pk += 1; }   // (once, or not at all, unless a.seg < kPrefetch)
+        return v;
+    };
     if (FAST) {
         uint32_t voff[kPrefetch];
 #pragma unroll
@@ -319,6 +389,26 @@ __device__ __forceinline__ void pack_tile(const PackArgs &a, uint32_t tile, uint
                 t0 += kPrefetch;
                 if (t0 >= T) break;
             }
+            return;
+        }
+        if (SEG) {   // the same loop; frames through the one descriptor, states on their own
+            na = prefetch_state(0);
+            ga.template load_desc<ONCE>(desc(cb), desc(cb), voff);
+            for (int t0 = 0;;) {
+                cb += gstep; left -= (int64_t)gstep;
+                nb = prefetch_state(t0 + kPrefetch);
+                gb.template load_desc<ONCE>(desc(cb), desc(cb), voff);
+                pack_group<PAIR, FAST, HIGH, false, true>(a, ga, t0, st, lp, tile, tc, lane, lg, nullptr, valid, &sg, &na);
+                t0 += kPrefetch;
+                if (t0 >= T) break;
+                cb += gstep; left -= (int64_t)gstep;
+                na = prefetch_state(t0 + kPrefetch);
+                ga.template load_desc<ONCE>(desc(cb), desc(cb), voff);
+                pack_group<PAIR, FAST, HIGH, false, true>(a, gb, t0, st, lp, tile, tc, lane, lg, nullptr, valid, &sg, &nb);
+                t0 += kPrefetch;
+                if (t0 >= T) break;
+            }
+            store_seg_state<FAST>(a, sg.next - 1, sg, st, valid);   // the last segment's
             return;
         }
         ga.template load_desc<ONCE>(desc(cb), desc(pb), voff);
@@ -358,6 +448,26 @@ __device__ __forceinline__ void pack_tile(const PackArgs &a, uint32_t tile, uint
         }
         return;
     }
+    if (SEG) {
+        na = prefetch_state(0);
+        ga.load(a, byte_off, 0, valid, cp, pp, cur_last, prev_last);
+        for (int t0 = 0;;) {
+            cp += gstep;
+            nb = prefetch_state(t0 + kPrefetch);
+            gb.load(a, byte_off, t0 + kPrefetch, valid, cp, pp, cur_last, prev_last);
+            pack_group<PAIR, FAST, HIGH, false, true>(a, ga, t0, st, lp, tile, tc, lane, lg, nullptr, valid, &sg, &na);
+            t0 += kPrefetch;
+            if (t0 >= T) break;
+            cp += gstep;
+            na = prefetch_state(t0 + kPrefetch);
+            ga.load(a, byte_off, t0 + kPrefetch, valid, cp, pp, cur_last, prev_last);
+            pack_group<PAIR, FAST, HIGH, false, true>(a, gb, t0, st, lp, tile, tc, lane, lg, nullptr, valid, &sg, &nb);
+            t0 += kPrefetch;
+            if (t0 >= T) break;
+        }
+        store_seg_state<FAST>(a, sg.next - 1, sg, st, valid);
+        return;
+    }
     ga.load(a, byte_off, 0, valid, cp, pp, cur_last, prev_last);
     for (int t0 = 0;;) {
         cp += gstep; if (PAIR) pp += gstep;
@@ -379,9 +489,11 @@ __device__ __forceinline__ void pack_tile(const PackArgs &a, uint32_t tile, uint
 }
 
 // FB (pair mode only): feedback pairs -- frame t's state, as compare_step leaves it, goes back to prev + t * stride.
-template <bool PAIR, bool ALIGNED, bool HIGH, bool ONCE = !PAIR, bool FB = false>
+// SEG (stream mode only): the batch is a.nframes / a.seg segments of a.seg frames, each on its own state in a.states (Seg).
+template <bool PAIR, bool ALIGNED, bool HIGH, bool ONCE = !PAIR, bool FB = false, bool SEG = false>
 __global__ __launch_bounds__(256) void k_diff_pack(const PackArgs a) {
     static_assert(!FB || PAIR, "feedback write-back is a form of pair mode");
+    static_assert(!SEG || !PAIR, "segments are a form of stream mode");
     const int lane = threadIdx.x & 63;
     // one tile per wave when the grid covers the frame (the default); a smaller grid walks the tiles with its stride
     // (pipelined batches leave wave slots to the expansion of the batch before, core.hip)
@@ -394,10 +506,10 @@ __global__ __launch_bounds__(256) void k_diff_pack(const PackArgs a) {
         const uint32_t byte_off = tile_off + (uint32_t)lane * 16u;
         // wave-uniform choice: every lane of a full, aligned tile takes the vector path
         if (ALIGNED && tile_off + kTileBytes <= a.n) {
-            pack_tile<PAIR, true, HIGH, ONCE, FB>(a, tile, byte_off, 16, lane);
+            pack_tile<PAIR, true, HIGH, ONCE, FB, SEG>(a, tile, byte_off, 16, lane);
         } else {
             const int valid = byte_off < a.n ? (int)min(16u, a.n - byte_off) : 0;
-            pack_tile<PAIR, false, HIGH, ONCE, FB>(a, tile, byte_off, valid, lane);
+            pack_tile<PAIR, false, HIGH, ONCE, FB, SEG>(a, tile, byte_off, valid, lane);
         }
     }
 }
@@ -417,7 +529,15 @@ hipError_t launch_diff_pack(const PackArgs &a, bool pair, bool aligned, bool pai
         if (high) hipLaunchKernelGGL((k_diff_pack<P, A, true>), grid, block, 0, s, a);                 \
         else hipLaunchKernelGGL((k_diff_pack<P, A, false>), grid, block, 0, s, a);                     \
     } while (0)
-    if (pair && feedback) {   // a.prev = the caller's states (core.hip, run_batch); the frames are read once
+    if (!pair && a.seg > 0) {   // a.states = the caller's states, one per segment of a.seg frames (core.hip, run_batch)
+        if (aligned) {
+            if (high) hipLaunchKernelGGL((k_diff_pack<false, true, true, true, false, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((k_diff_pack<false, true, false, true, false, true>), grid, block, 0, s, a);
+        } else {
+            if (high) hipLaunchKernelGGL((k_diff_pack<false, false, true, true, false, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((k_diff_pack<false, false, false, true, false, true>), grid, block, 0, s, a);
+        }
+    } else if (pair && feedback) {   // a.prev = the caller's states (core.hip, run_batch); the frames are read once
         if (aligned) {
             if (high) hipLaunchKernelGGL((k_diff_pack<true, true, true, true, true>), grid, block, 0, s, a);
             else hipLaunchKernelGGL((k_diff_pack<true, true, false, true, true>), grid, block, 0, s, a);

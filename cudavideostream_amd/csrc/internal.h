@@ -16,7 +16,10 @@ constexpr uint32_t kWavesPerBlock = 4;
 struct PackArgs {
     const uint8_t *cur;    // frame t at cur + t*stride
     const uint8_t *prev;   // pair mode: prev frame t at prev + t*stride; stream mode: unused
-    uint8_t *state;        // stream mode: N bytes, read at start and written back at the end
+    union {
+        uint8_t *state;    // stream mode: N bytes, read at start and written back at the end
+        uint8_t *states;   // segmented stream mode (seg > 0): stream s's state at states + s*stride, read when its segment
+    };                     // begins and written back when it ends
     size_t stride;         // bytes between frames
     uint32_t n;            // bytes per frame
     int32_t nframes;       // T
@@ -30,7 +33,12 @@ struct PackArgs {
     uint32_t codes_bytes;  // sizes of the logs (buffer descriptors; all < 2^32)
     uint32_t rec_bytes;
     uint32_t meta_bytes;
+    // segmented stream mode (mi355_diff_multi_stream_*): batch index b = s * seg + t is frame t of stream s
+    int32_t seg;           // frames per stream (0: not segmented); nframes = streams * seg
 };
+// (seg fills the struct's tail padding and states shares state's place: the kernel arguments keep their size, and with it the
+// existing instantiations of k_diff_pack their code down to the offset of the implicit arguments)
+static_assert(sizeof(PackArgs) == 96, "see above");
 
 struct ExpandArgs {
     const uint32_t *codes;
@@ -56,6 +64,7 @@ hipStream_t core_stream(::mi355_core *c);   // the stream the core currently enq
 int core_device(const ::mi355_core *c);
 
 // diff_pack.hip
+// a.seg > 0 (stream mode only): the segmented form, a.states instead of a.state
 hipError_t launch_diff_pack(const PackArgs &a, bool pair, bool aligned, bool pair_once /* pair mode: no frame is an operand twice */,
                             uint32_t max_blocks /* 0: one tile per wave */, hipStream_t s,
                             bool feedback = false /* pair mode: prev + t * stride is writable and takes frame t's fed-back state */);

@@ -72,6 +72,12 @@ SYMBOLS = {
                                               C.c_void_p, C.c_size_t]),
     "mi355_diff_multi_cwire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mi355_diff_multi_stream_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mi355_diff_multi_stream_wire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                                     C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mi355_diff_multi_stream_cwire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "mi355_apply_multi_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                           C.c_size_t]),
     "mi355_apply_multi_wire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),

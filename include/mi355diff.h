@@ -83,7 +83,9 @@ typedef struct mi355_config {
  *   9  + mi355_diff_stream_cwire_batch (additions only)
  *   10 + mi355_apply_cwire_batch (additions only); + mi355_diff_multi_batch, mi355_diff_multi_wire_batch,
  *      mi355_diff_multi_cwire_batch (additions only: no existing argument list changed, so the number stays);
- *      + mi355_apply_multi_batch, mi355_apply_multi_wire_batch, mi355_apply_multi_cwire_batch (additions only) */
+ *      + mi355_apply_multi_batch, mi355_apply_multi_wire_batch, mi355_apply_multi_cwire_batch (additions only);
+ *      + mi355_diff_multi_stream_batch, mi355_diff_multi_stream_wire_batch, mi355_diff_multi_stream_cwire_batch (additions
+ *      only) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -272,6 +274,49 @@ int mi355_diff_multi_wire_batch(mi355_core *core, const void *d_frames, void *d_
                                 void *d_offsets, void *d_wire, size_t capacity_bytes);
 int mi355_diff_multi_cwire_batch(mi355_core *core, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
                                  void *d_offsets, void *d_frame_pos, void *d_cwire, size_t capacity_bytes);
+/* ---- many streams, many frames each (recorded streams, buffered ticks, a camera that catches up) ----------------------
+ * nframes frames of each of nstreams independent streams in ONE call: frame t of stream s is at
+ * d_frames + (s*nframes + t)*stride_bytes (stream-major), stream s's state -- in the CALLER's memory -- at
+ * d_states + s*stride_bytes.  For every s the frames t = 0 .. nframes - 1 are processed in order, and the result is exactly
+ * what mi355_diff_stream_batch(nframes) leaves on a core whose state is states[s]: threshold, negative feedback, ascending
+ * indices; afterwards states[s] is that core's state.  The core's own state is neither read nor written.  With
+ * nstreams == 1 this is the stream form on a caller-held state, with nframes == 1 it is mi355_diff_multi_*.
+ * The outputs are those of the single-stream forms with batch index b = s*nframes + t in the place of "frame t":
+ * d_offsets is uint32[nstreams*nframes + 1]; the wire form holds {u32 n, i32 xs[n], u8 diff[n]} of batch index b at byte
+ * 4*b + 5*offsets[b]; the compact form its record at d_frame_pos[b] (uint64[nstreams*nframes + 1]).  The nframes frames of
+ * a stream are therefore ONE contiguous slice of every output: one write() per socket.  Capacity, drop and alignment rules
+ * are unchanged and mi355_cwire_bytes_max(N, nstreams*nframes) always suffices; when the outputs overflow the states still
+ * advance completely.
+ * Refused (MI355_ERR_INVALID) before anything is launched or written: a null core, a negative nstreams or nframes,
+ * nstreams*nframes > max_batch, a null d_frames or d_states with nstreams*nframes > 0, stride_bytes < N, states
+ * [d_states, d_states + (nstreams-1)*stride_bytes + N) that overlap the frames
+ * [d_frames, d_frames + (nstreams*nframes-1)*stride_bytes + N), and whatever the single-stream form of the same output
+ * refuses.  nstreams*nframes == 0 writes offsets[0] = 0 (and frame_pos[0] = 0) and nothing else.  Bytes of the states'
+ * region outside the N bytes of each state are never written, the gap of the stride included; the frames are only read.
+ * The fast path needs d_frames, d_states and stride_bytes to be multiples of 16; anything else goes the byte path with
+ * identical results.
+ * The pack kernel is the STREAM form (one wave keeps its tile's state in registers and reads N bytes per frame, not 2N) with
+ * the register-held state exchanged every nframes frames: states[s] is read once (plain loads, prefetched with the frames
+ * of the register group the exchange falls into) and written once per call (non-temporal stores, only by lanes whose 16
+ * bytes changed during the stream's frames).  Per frame it reads N + N/nframes bytes where nframes calls of
+ * mi355_diff_multi_* read 2N, and it is one launch sequence instead of nframes.  No workspace beyond the core's; nothing
+ * is allocated inside the call.
+ * Ordering is that of mi355_diff_multi_batch: asynchronous; pipelined on the core's own stream, split launches included; the
+ * next call on the same (d_states, stride_bytes) -- of this form or of mi355_diff_multi_*, the two may alternate without a
+ * synchronisation -- sees every state byte this one wrote; every later entry point of the core that reads the states finds
+ * them complete; with a caller's stream everything runs on it in call order.
+ * Measured (profiles/multi_stream.json: 1080p, webcam-like input, compact form, microseconds per frame, median of five
+ * rounds; T calls of mi355_diff_multi_cwire_batch on the same frames / S cores with mi355_diff_stream_cwire_batch(T) in
+ * brackets): S = 4: T = 4 5.50 (25.4 / 12.8), T = 16 3.79 (25.4 / 4.12), T = 64 3.41 (25.5 / 3.00); S = 16: T = 4 3.99
+ * (8.82 / 12.8), T = 16 3.33 (8.83 / 4.84), T = 64 3.51 in two calls (8.93 / 3.04).  DESIGN.md section 4, "K1, segmented
+ * stream form". */
+int mi355_diff_multi_stream_batch(mi355_core *core, const void *d_frames, void *d_states, size_t stride_bytes,
+                                  int nstreams, int nframes, void *d_offsets, void *d_xs, void *d_diff, size_t capacity);
+int mi355_diff_multi_stream_wire_batch(mi355_core *core, const void *d_frames, void *d_states, size_t stride_bytes,
+                                       int nstreams, int nframes, void *d_offsets, void *d_wire, size_t capacity_bytes);
+int mi355_diff_multi_stream_cwire_batch(mi355_core *core, const void *d_frames, void *d_states, size_t stride_bytes,
+                                        int nstreams, int nframes, void *d_offsets, void *d_frame_pos, void *d_cwire,
+                                        size_t capacity_bytes);
 /* The receiving end of such a tick, client/opencv.cpp:50-66 for nstreams cameras in ONE call: segment or record s
  * (0 <= s < nstreams <= max_batch) is applied to the N bytes at d_states + s*stride_bytes -- for each of its entries
  * state[s][x] += diff (uint8 wrap-around) -- exactly what mi355_apply_batch / _wire_batch / _cwire_batch with nframes = 1 does

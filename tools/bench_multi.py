@@ -30,7 +30,19 @@ and the bytes of the states the compact form moves per stream and tick: touched 
 the decoded indices.  The records are K ticks of a server core (diff_multi_cwire_batch on the same input), applied round
 and round: adding a record to a state is the same work whatever the state holds.
 
-Input: ONE webcam stream of S + K + 1 frames; stream s shows frame s + j at step j, so every tick of every stream is the
+The burst leg (--legs burst, a run of its own: `--legs burst --streams 4,16 --frames 4,16,64` is how
+profiles/multi_stream.json was taken) measures T frames of each of S streams, in microseconds per frame, ONE JSON line for
+all (S, T), the three ways a sender can make the S * T compact records:
+  burst_cwire    mi355_diff_multi_stream_cwire_batch: one call, the S states in the caller's memory;
+  multi_ticks    T calls of mi355_diff_multi_cwire_batch on the same frames arranged tick-major ([T][S][N]), on the same states;
+  cores_stream   S cores, each mi355_diff_stream_cwire_batch(T) on its own state (a workspace sized for T per camera).
+Its input is ONE webcam stream of S * T + 1 frames cut into S pieces: stream s starts from frame s * T as its state and
+takes the T frames behind it.  A timed window runs the pieces forwards, then backwards (frames T - 1 .. 0 of each piece),
+and so on, so that every step of every window is the step between two neighbouring webcam frames.  A core takes
+max_batch * N < 2^32 bytes per call (682 frames of 1080p): where S * T is more, burst_cwire makes the fewest calls that fit,
+each with as many whole streams as it can hold (`calls_per_burst` in the line).
+
+Input of the other legs: ONE webcam stream of S + K + 1 frames; stream s shows frame s + j at step j, so every tick of every stream is the
 step between two consecutive webcam frames, and a tick's S frames are one contiguous region.  j walks 1 .. K and back."""
 import argparse
 import ctypes
@@ -265,13 +277,101 @@ def run_client(W, H, S, K, rounds):
     return out
 
 
+def run_burst(W, H, S, T, rounds):
+    """The burst leg for one (S, T) -> its dictionary."""
+    from cudavideostream_amd import CUDACore, cwire_bytes_max
+    dev = torch.device("cuda", 0)
+    n, B = 3 * W * H, S * T
+    passes = 2 * max(1, 1024 // B)                     # forwards and backwards in turn: ~2 k frames per timed window
+    _, web = synth.webcam_stream(B + 1, W, H, device=dev)
+    web = web.reshape(B + 1, n)
+    states0 = web[0:B:T].clone()                                        # [S][n]: frame s * T
+    fwd = web[1:].reshape(S, T, n)                                      # stream-major, a view
+    bwd = web[:B].reshape(S, T, n).flip(1).contiguous()                 # frames T - 1 .. 0 of each piece
+    sets = [(fwd, fwd.transpose(0, 1).contiguous()), (bwd, bwd.transpose(0, 1).contiguous())]   # (stream-major, tick-major)
+    states = states0.clone()
+    cwcap = min(cwire_bytes_max(n, B), max(B * n // 4, 1 << 16))        # the input changes ~2 % of the bytes
+    d_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+    d_pos = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+    d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
+    per_call = min(S, max(1, ((1 << 32) - 1) // n // T))             # whole streams per call: max_batch * N < 2^32
+    chunks = [(s0, min(per_call, S - s0)) for s0 in range(0, S, per_call)]
+    burst = CUDACore(W, H, max_batch=per_call * T)
+    ticks = CUDACore(W, H, max_batch=S)
+    cores = [CUDACore(W, H, max_batch=T) for _ in range(S)]
+    one = cwcap // S
+    outs = [(torch.zeros(T + 1, dtype=torch.int32, device=dev), torch.zeros(T + 1, dtype=torch.int64, device=dev),
+             torch.empty(one, dtype=torch.uint8, device=dev)) for _ in range(S)]
+    for c in [burst, ticks] + cores:
+        c.prepare(lib.PREPARE_BATCHES)
+    host0 = states0.cpu().numpy()
+    torch.cuda.synchronize()
+
+    def leg_burst():
+        for p in range(passes):
+            for s0, ns in chunks:
+                burst.diff_multi_stream_cwire_batch(sets[p & 1][0][s0], states[s0], ns, T, d_off, d_pos, d_cw, cwcap)
+        burst.synchronize()
+
+    def leg_ticks():
+        for p in range(passes):
+            tm = sets[p & 1][1]
+            for t in range(T):
+                ticks.diff_multi_cwire_batch(tm[t], states, S, d_off, d_pos, d_cw, cwcap)
+        ticks.synchronize()
+
+    def leg_cores():
+        for p in range(passes):
+            sm = sets[p & 1][0]
+            for s, c in enumerate(cores):
+                c.diff_stream_cwire_batch(sm[s], T, outs[s][0], outs[s][1], outs[s][2], one)
+        for c in cores:
+            c.synchronize()
+
+    table = {"burst_cwire": leg_burst, "multi_ticks": leg_ticks, "cores_stream": leg_cores}
+    times = {}
+    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
+        for name, leg in table.items():
+            states.copy_(states0)
+            if name == "cores_stream":
+                for s, c in enumerate(cores):
+                    c.set_state(host0[s])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            leg()
+            dt = time.perf_counter() - t0
+            if r:
+                times.setdefault(name, []).append(dt * 1e6 / (passes * B))
+    states.copy_(states0)
+    torch.cuda.synchronize()
+    total = nbytes = 0
+    for s0, ns in chunks:
+        burst.diff_multi_stream_cwire_batch(fwd[s0], states[s0], ns, T, d_off, d_pos, d_cw, cwcap)
+        burst.synchronize()
+        total, nbytes = total + int(d_off.cpu()[ns * T]), nbytes + int(d_pos.cpu()[ns * T])
+        assert int(d_pos.cpu()[ns * T]) <= cwcap                                               # nothing was dropped
+    assert 0 < total and all(int(o[1].cpu()[-1]) <= one for o in outs)
+    out = {"streams": S, "frames": T, "passes": passes, "calls_per_burst": len(chunks), "changed_bytes_per_frame": round(total / B, 1),
+           "record_bytes_per_frame": round(nbytes / B, 1)}
+    for name in table:
+        out[name + "_us_per_frame"] = stats(times[name])
+    med = {k: statistics.median(v) for k, v in times.items()}
+    out["multi_ticks_over_burst"] = round(med["multi_ticks"] / med["burst_cwire"], 3)
+    out["cores_stream_over_burst"] = round(med["cores_stream"] / med["burst_cwire"], 3)
+    for c in [burst, ticks] + cores:
+        c.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", default="1920x1080")
     ap.add_argument("--streams", default="8,64,256")
     ap.add_argument("--steps", type=int, default=8, help="K: webcam frames a stream walks through")
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--legs", default="multi,cores_loop,pairs", help="of multi, cores_loop, pairs, write_probe; or client alone")
+    ap.add_argument("--legs", default="multi,cores_loop,pairs",
+                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone")
+    ap.add_argument("--frames", default="4,16,64", help="burst leg: T, frames per stream and call")
     a = ap.parse_args()
     have = load_library()
     W, H = (int(v) for v in a.size.split("x"))
@@ -282,6 +382,15 @@ def main():
             torch.cuda.empty_cache()
         print(json.dumps({"bench": "multi_client", "size": f"{W}x{H}", "input": "synth.webcam_stream", "rounds": a.rounds,
                           "steps": a.steps, "client": per}), flush=True)
+        return
+    if a.legs == "burst":
+        per = []
+        for S in (int(v) for v in a.streams.split(",")):
+            for T in (int(v) for v in a.frames.split(",")):
+                per.append(run_burst(W, H, S, T, a.rounds))
+                torch.cuda.empty_cache()
+        print(json.dumps({"bench": "multi_stream", "size": f"{W}x{H}", "input": "synth.webcam_stream", "rounds": a.rounds,
+                          "burst": per}), flush=True)
         return
     for S in (int(v) for v in a.streams.split(",")):
         run(W, H, S, a.steps, a.rounds, set(a.legs.split(",")), have)

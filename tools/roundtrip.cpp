@@ -20,8 +20,12 @@
 // mi355_diff_multi_cwire_batch; each tick's records (headers included) cross the pipe; a client core uploads them and applies
 // them in one call (mi355_apply_multi_cwire_batch) onto S states of its own.  After every tick the client's states must equal
 // the server's, byte for byte, and after the last tick the frames a host client (mi355_cwire_apply_host) rebuilt per camera.
+// --compact --multi S --burst K: the sender buffers K ticks per camera (a recorder, a camera that catches up) and makes their
+// S * K records in ONE call, mi355_diff_multi_stream_cwire_batch: camera s's K records are one contiguous slice, one write()
+// per socket.  The receiver stages record (s, t) of every s back to back for tick t and applies the ticks with the same
+// mi355_apply_multi_cwire_batch; after every burst the states at both ends must be equal.
 //
-//   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B] [--compact [--direct] [--gpu-client] [--multi S]]
+//   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B] [--compact [--direct] [--gpu-client] [--multi S [--burst K]]]
 //   exit status 0 = all checks passed
 #include <cstdint>
 #include <cstdio>
@@ -168,8 +172,128 @@ static int run_multi(int w, int h, int T, int S) {
     return 0;
 }
 
+// --compact --multi S --burst K (see the head of the file)
+static int run_multi_burst(int w, int h, int T, int S, int K) {
+    const size_t n = (size_t)3 * w * h;
+    mi355_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.width = w; cfg.height = h; cfg.threshold = 20; cfg.max_batch = S * K; cfg.device = -1;
+    mi355_core *server = nullptr, *client = nullptr;
+    OK(mi355_create(&cfg, &server));
+    cfg.max_batch = S;
+    OK(mi355_create(&cfg, &client));
+    const int B = S * K;
+    const size_t cw_cap = mi355_cwire_bytes_max(n, B), tick_cap = mi355_cwire_bytes_max(n, S);
+    void *d_frames = nullptr, *d_sstates = nullptr, *d_off = nullptr, *d_pos = nullptr, *d_cw = nullptr;   // server
+    void *d_rx = nullptr, *d_cstates = nullptr;                                                              // client
+    OK(mi355_dev_alloc(server, &d_frames, (size_t)B * n));
+    OK(mi355_dev_alloc(server, &d_sstates, (size_t)S * n));
+    OK(mi355_dev_alloc(server, &d_off, sizeof(uint32_t) * (B + 1)));
+    OK(mi355_dev_alloc(server, &d_pos, sizeof(uint64_t) * (B + 1)));
+    OK(mi355_dev_alloc(server, &d_cw, cw_cap));
+    OK(mi355_dev_alloc(client, &d_rx, tick_cap));
+    OK(mi355_dev_alloc(client, &d_cstates, (size_t)S * n));
+    int fds[2];
+    if (pipe(fds) != 0) return 1;
+    std::vector<uint8_t> bases((size_t)S * n), host_frames((size_t)S * n), frames((size_t)B * n), s_states((size_t)S * n),
+        c_states((size_t)S * n), cw_host(cw_cap), rx(cw_cap), stage(tick_cap);
+    for (int s = 0; s < S; s++)
+        for (size_t i = 0; i < n; i++) bases[(size_t)s * n + i] = (uint8_t)(40 + (i * 7 + (size_t)s * 31) % 150);
+    OK(mi355_upload(server, d_sstates, bases.data(), bases.size()));
+    if (!through_pipe(fds[1], fds[0], bases.data(), host_frames.data(), bases.size())) return 1;
+    OK(mi355_upload(client, d_cstates, host_frames.data(), host_frames.size()));
+    std::vector<uint8_t> base(n), frame(n);
+    std::vector<uint32_t> off(B + 1), counts(S), escapes(S);
+    std::vector<uint64_t> pos(B + 1);
+    std::vector<size_t> at(B), len(B);   // where record (s, t) lies in the received bytes, as the receiver found it
+    size_t sent_bytes = 0, changed = 0;
+    int max_err = 0, calls = 0;
+    for (int t0 = 0; t0 < T; t0 += K) {
+        const int nb = T - t0 < K ? T - t0 : K, nrec = S * nb;
+        for (int s = 0; s < S; s++) {   // camera s's nb frames, one behind the other
+            memcpy(base.data(), &bases[(size_t)s * n], n);
+            for (int k = 0; k < nb; k++) {
+                make_frame(frame, base, w, h, t0 + k + 5 * s);
+                memcpy(&frames[((size_t)s * nb + k) * n], frame.data(), n);
+            }
+        }
+        // ---- server: nb ticks of S cameras -> S * nb records in one call
+        OK(mi355_upload(server, d_frames, frames.data(), (size_t)nrec * n));
+        OK(mi355_diff_multi_stream_cwire_batch(server, d_frames, d_sstates, n, S, nb, d_off, d_pos, d_cw, cw_cap));
+        calls++;
+        OK(mi355_download(server, off.data(), d_off, sizeof(uint32_t) * (nrec + 1)));
+        OK(mi355_download(server, pos.data(), d_pos, sizeof(uint64_t) * (nrec + 1)));
+        if (pos[nrec] > cw_cap) { fprintf(stderr, "compact stream larger than its bound\n"); return 1; }
+        const size_t cb = (size_t)pos[nrec];
+        OK(mi355_download(server, cw_host.data(), d_cw, cb));
+        changed += off[nrec];
+        // ---- the sockets: camera s's slice [pos[s * nb], pos[(s + 1) * nb]) is one write
+        for (int s = 0; s < S; s++) {
+            const size_t a = (size_t)pos[(size_t)s * nb], b = (size_t)pos[(size_t)(s + 1) * nb];
+            if (!through_pipe(fds[1], fds[0], cw_host.data() + a, rx.data() + a, b - a)) return 1;
+        }
+        sent_bytes += cb;
+        // ---- receiver: the records of every socket, found from their headers
+        size_t p = 0;
+        for (int r = 0; r < nrec; r++) {
+            if (p + 8 > cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
+            uint32_t c, e;
+            memcpy(&c, rx.data() + p, 4);
+            memcpy(&e, rx.data() + p + 4, 4);
+            at[r] = p;
+            len[r] = mi355_cwire_frame_bytes(c, e);
+            p += len[r];
+        }
+        if (p != cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
+        // ---- client: tick k = record (s, k) of every s back to back, one upload, one call
+        for (int k = 0; k < nb; k++) {
+            size_t q = 0;
+            for (int s = 0; s < S; s++) {
+                const int r = s * nb + k;
+                memcpy(stage.data() + q, rx.data() + at[r], len[r]);
+                memcpy(&counts[s], stage.data() + q, 4);
+                memcpy(&escapes[s], stage.data() + q + 4, 4);
+                size_t used = 0;   // ... and the host client of camera s beside it
+                OK(mi355_cwire_apply_host(&host_frames[(size_t)s * n], n, stage.data() + q, len[r], 1, &used));
+                if (used != len[r]) { fprintf(stderr, "stream framing broken\n"); return 1; }
+                q += len[r];
+            }
+            OK(mi355_upload(client, d_rx, stage.data(), q));
+            OK(mi355_apply_multi_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, d_cstates, n));
+            OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
+            if (memcmp(host_frames.data(), c_states.data(), c_states.size()) != 0) {
+                fprintf(stderr, "tick %d: client states != host client frames\n", t0 + k);
+                return 1;
+            }
+            for (int s = 0; s < S; s++)
+                for (size_t i = 0; i < n; i++) {
+                    const int e = abs((int)c_states[(size_t)s * n + i] - (int)frames[((size_t)s * nb + k) * n + i]);
+                    if (e > max_err) max_err = e;
+                }
+        }
+        // ---- the states at both ends
+        OK(mi355_download(server, s_states.data(), d_sstates, s_states.size()));
+        if (memcmp(s_states.data(), c_states.data(), s_states.size()) != 0) {
+            fprintf(stderr, "burst at tick %d: client states != server states\n", t0);
+            return 1;
+        }
+    }
+    if (max_err > cfg.threshold) { fprintf(stderr, "rebuilt frame off by %d > threshold\n", max_err); return 1; }
+    void *srv[] = {d_frames, d_sstates, d_off, d_pos, d_cw};
+    for (void *q : srv) OK(mi355_dev_free(server, q));
+    OK(mi355_dev_free(client, d_rx));
+    OK(mi355_dev_free(client, d_cstates));
+    mi355_destroy(server);
+    mi355_destroy(client);
+    printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"burst\": %d, \"sender_calls\": %d, \"width\": %d, \"height\": %d, "
+           "\"ticks\": %d, \"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, "
+           "\"max_abs_error\": %d}\n",
+           S, K, calls, w, h, T, changed, sent_bytes, mi355_wire_bytes(T * S, changed), (size_t)T * S * n, max_err);
+    return 0;
+}
+
 int main(int argc, char **argv) {
-    int w = 320, h = 180, T = 24, B = 8, multi = 0;
+    int w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0;
     bool compact = false, direct = false, gpu_client = false;
     for (int i = 1; i < argc; i++) {
         if (std::string(argv[i]) == "--compact") compact = true;
@@ -185,10 +309,12 @@ int main(int argc, char **argv) {
         if (k == "--width") w = v; else if (k == "--height") h = v;
         else if (k == "--frames") T = v; else if (k == "--batch") B = v;
         else if (k == "--multi") multi = v;
+        else if (k == "--burst") burst = v;
     }
+    if (burst && (!multi || burst < 0)) { fprintf(stderr, "--burst K needs --multi S and K >= 1\n"); return 2; }
     if (multi) {
         if (!compact || direct || gpu_client || multi < 0) { fprintf(stderr, "--multi S needs --compact alone and S >= 1\n"); return 2; }
-        return run_multi(w, h, T, multi);
+        return burst ? run_multi_burst(w, h, T, multi, burst) : run_multi(w, h, T, multi);
     }
     const size_t n = (size_t)3 * w * h;
     mi355_config cfg;
