@@ -112,6 +112,21 @@ static inline dim3 px16_grid(uint32_t npix) {
 
 static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
+// The frame is a grid dimension (y or z) of every batched kernel of this file, and those dimensions are bounded: 65535 is
+// what every HIP platform accepts.  A longer batch (mi355_create allows a max_batch in the millions for small frames)
+// goes out as several grids of at most kGridFrames frames: launch(first frame, frames) advances the launcher's per-frame
+// pointers by the frames already issued.  One grid, as before, for every batch up to 65535 frames.
+constexpr int kGridFrames = 65535;
+template <class Launch>
+static hipError_t for_frame_grids(int nframes, Launch launch) {
+    for (int64_t t0 = 0; t0 < nframes; t0 += kGridFrames) {   // (64 bits: nframes may be close to INT_MAX)
+        launch((size_t)t0, (unsigned)(nframes - t0 < kGridFrames ? nframes - t0 : kGridFrames));
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 // ---- integer difference: tests/algorithms_benchmarks.cu:24-30 (kernel1) ------------------------------
 __global__ __launch_bounds__(256) void k_int_diff(const int32_t *cur, const int32_t *prev, int32_t *out,
                                                   size_t n) {
@@ -237,17 +252,20 @@ hipError_t launch_gray(const uint8_t *in, uint8_t *out, uint32_t npix, bool weig
                        hipStream_t s) {
     if (npix == 0 || fb.nframes <= 0) return hipSuccess;
     const bool fast = aligned16(in) && aligned16(out) && fb.stride % 16 == 0;
-    dim3 g = px16_grid(npix);
-    g.y = (unsigned)fb.nframes;
     const dim3 b(256);
-    if (weighted) {
-        if (fast) hipLaunchKernelGGL((k_gray<true, true>), g, b, 0, s, in, out, npix, fb.stride);
-        else hipLaunchKernelGGL((k_gray<true, false>), g, b, 0, s, in, out, npix, fb.stride);
-    } else {
-        if (fast) hipLaunchKernelGGL((k_gray<false, true>), g, b, 0, s, in, out, npix, fb.stride);
-        else hipLaunchKernelGGL((k_gray<false, false>), g, b, 0, s, in, out, npix, fb.stride);
-    }
-    return hipGetLastError();
+    return for_frame_grids(fb.nframes, [&](size_t t0, unsigned cnt) {
+        dim3 g = px16_grid(npix);
+        g.y = cnt;
+        const uint8_t *i = in + t0 * fb.stride;
+        uint8_t *o = out + t0 * fb.stride;
+        if (weighted) {
+            if (fast) hipLaunchKernelGGL((k_gray<true, true>), g, b, 0, s, i, o, npix, fb.stride);
+            else hipLaunchKernelGGL((k_gray<true, false>), g, b, 0, s, i, o, npix, fb.stride);
+        } else {
+            if (fast) hipLaunchKernelGGL((k_gray<false, true>), g, b, 0, s, i, o, npix, fb.stride);
+            else hipLaunchKernelGGL((k_gray<false, false>), g, b, 0, s, i, o, npix, fb.stride);
+        }
+    });
 }
 
 // ---- binarize chain: kernels.cu:138-241, CPU semantics server/src/server.cpp:103-135 -----------------
@@ -485,17 +503,23 @@ static hipError_t launch_hist_thr(const uint8_t *img, uint32_t npix, int mode, i
     if (e != hipSuccess) return e;
     if (npix) {
         const uint32_t px_per_block = 256 * 16 * kHistBlocks;
-        const dim3 g((npix + px_per_block - 1) / px_per_block, (unsigned)fb.nframes);
         const bool fast = aligned16(img) && fb.stride % 16 == 0;
 #define MI355_HIST(M)                                                                                   \
     do {                                                                                                \
-        if (fast) hipLaunchKernelGGL((k_histogram<M, true>), g, dim3(256), 0, s, img, npix, hist, fb.stride, gray1, gray1_stride); \
-        else hipLaunchKernelGGL((k_histogram<M, false>), g, dim3(256), 0, s, img, npix, hist, fb.stride, gray1, gray1_stride);     \
+        if (fast) hipLaunchKernelGGL((k_histogram<M, true>), g, dim3(256), 0, s, im, npix, hi, fb.stride, g1, gray1_stride); \
+        else hipLaunchKernelGGL((k_histogram<M, false>), g, dim3(256), 0, s, im, npix, hi, fb.stride, g1, gray1_stride);     \
     } while (0)
-        if (mode == 0) MI355_HIST(0);
-        else if (mode == 1) MI355_HIST(1);
-        else MI355_HIST(2);
+        e = for_frame_grids(fb.nframes, [&](size_t t0, unsigned cnt) {
+            const dim3 g((npix + px_per_block - 1) / px_per_block, cnt);
+            const uint8_t *im = img + t0 * fb.stride;
+            int32_t *hi = hist + t0 * 256;
+            uint8_t *g1 = gray1 ? gray1 + t0 * gray1_stride : nullptr;
+            if (mode == 0) MI355_HIST(0);
+            else if (mode == 1) MI355_HIST(1);
+            else MI355_HIST(2);
+        });
 #undef MI355_HIST
+        if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(k_two_max_threshold, dim3(fb.nframes), dim3(64), 0, s, hist, thr);
     return hipGetLastError();
@@ -508,8 +532,11 @@ hipError_t launch_binarize_chain(const uint8_t *gray, uint8_t *out, uint32_t nby
     if (e != hipSuccess) return e;
     if (nbytes) {
         const uint32_t lanes = (nbytes + 15) / 16;
-        hipLaunchKernelGGL(k_binarize, dim3((lanes + 255) / 256, (unsigned)fb.nframes), dim3(256), 0, s, gray,
-                           out, nbytes, thr, aligned16(gray) && aligned16(out) && fb.stride % 16 == 0, fb.stride);
+        const bool fast = aligned16(gray) && aligned16(out) && fb.stride % 16 == 0;
+        return for_frame_grids(fb.nframes, [&](size_t t0, unsigned cnt) {
+            hipLaunchKernelGGL(k_binarize, dim3((lanes + 255) / 256, cnt), dim3(256), 0, s, gray + t0 * fb.stride,
+                               out + t0 * fb.stride, nbytes, thr + t0, fast, fb.stride);
+        });
     }
     return hipGetLastError();
 }
@@ -525,23 +552,26 @@ hipError_t launch_gray_binarize_fused(const uint8_t *color, uint8_t *out, uint32
     hipError_t e = launch_hist_thr(color, npix, weighted ? 2 : 1, hist, thr, fb, s, gray1, gray1_stride);
     if (e != hipSuccess || npix == 0) return e;
     const bool fast = aligned16(color) && aligned16(out) && fb.stride % 16 == 0;
-    dim3 g = px16_grid(npix);
-    g.y = (unsigned)fb.nframes;
-    if (gray1) {
-        if (aligned16(out) && fb.stride % 16 == 0)
-            hipLaunchKernelGGL((k_binarize_gray1<true>), g, dim3(256), 0, s, gray1, gray1_stride, out, npix, thr, fb.stride);
-        else
-            hipLaunchKernelGGL((k_binarize_gray1<false>), g, dim3(256), 0, s, gray1, gray1_stride, out, npix, thr, fb.stride);
-        return hipGetLastError();
-    }
-    if (weighted) {
-        if (fast) hipLaunchKernelGGL((k_gray_binarize<true, true>), g, dim3(256), 0, s, color, out, npix, thr, fb.stride);
-        else hipLaunchKernelGGL((k_gray_binarize<true, false>), g, dim3(256), 0, s, color, out, npix, thr, fb.stride);
-    } else {
-        if (fast) hipLaunchKernelGGL((k_gray_binarize<false, true>), g, dim3(256), 0, s, color, out, npix, thr, fb.stride);
-        else hipLaunchKernelGGL((k_gray_binarize<false, false>), g, dim3(256), 0, s, color, out, npix, thr, fb.stride);
-    }
-    return hipGetLastError();
+    return for_frame_grids(fb.nframes, [&](size_t t0, unsigned cnt) {
+        dim3 g = px16_grid(npix);
+        g.y = cnt;
+        const uint8_t *c = color + t0 * fb.stride;
+        uint8_t *o = out + t0 * fb.stride;
+        const int32_t *th = thr + t0;
+        if (gray1) {
+            const uint8_t *g1 = gray1 + t0 * gray1_stride;
+            if (aligned16(out) && fb.stride % 16 == 0)
+                hipLaunchKernelGGL((k_binarize_gray1<true>), g, dim3(256), 0, s, g1, gray1_stride, o, npix, th, fb.stride);
+            else
+                hipLaunchKernelGGL((k_binarize_gray1<false>), g, dim3(256), 0, s, g1, gray1_stride, o, npix, th, fb.stride);
+        } else if (weighted) {
+            if (fast) hipLaunchKernelGGL((k_gray_binarize<true, true>), g, dim3(256), 0, s, c, o, npix, th, fb.stride);
+            else hipLaunchKernelGGL((k_gray_binarize<true, false>), g, dim3(256), 0, s, c, o, npix, th, fb.stride);
+        } else {
+            if (fast) hipLaunchKernelGGL((k_gray_binarize<false, true>), g, dim3(256), 0, s, c, o, npix, th, fb.stride);
+            else hipLaunchKernelGGL((k_gray_binarize<false, false>), g, dim3(256), 0, s, c, o, npix, th, fb.stride);
+        }
+    });
 }
 
 // ---- heat map: kernels.cu:243-270, CPU tests/heat_map_benchmark/cpu.cu:19-27,54-66 -----------------
@@ -587,11 +617,13 @@ hipError_t launch_heat_map(const uint8_t *cur, const uint8_t *prev, uint8_t *out
                            const uint8_t *lut, FrameBatch fb, hipStream_t s) {
     if (npix == 0 || fb.nframes <= 0) return hipSuccess;
     const bool fast = aligned16(cur) && aligned16(prev) && aligned16(out) && fb.stride % 16 == 0;
-    dim3 g = px16_grid(npix);
-    g.y = (unsigned)fb.nframes;
-    if (fast) hipLaunchKernelGGL((k_heat_map<true>), g, dim3(256), 0, s, cur, prev, out, npix, lut, fb.stride);
-    else hipLaunchKernelGGL((k_heat_map<false>), g, dim3(256), 0, s, cur, prev, out, npix, lut, fb.stride);
-    return hipGetLastError();
+    return for_frame_grids(fb.nframes, [&](size_t t0, unsigned cnt) {
+        dim3 g = px16_grid(npix);
+        g.y = cnt;
+        const size_t at = t0 * fb.stride;
+        if (fast) hipLaunchKernelGGL((k_heat_map<true>), g, dim3(256), 0, s, cur + at, prev + at, out + at, npix, lut, fb.stride);
+        else hipLaunchKernelGGL((k_heat_map<false>), g, dim3(256), 0, s, cur + at, prev + at, out + at, npix, lut, fb.stride);
+    });
 }
 
 // ---- red motion map, dense: tests/heat_map_red_benchmark/cpu.cu:38-55 (test.cu:142-168) -----------
@@ -631,11 +663,13 @@ hipError_t launch_red_dense(const uint8_t *cur, const uint8_t *prev, uint8_t *ou
                             int thr, FrameBatch fb, hipStream_t s) {
     if (npix == 0 || fb.nframes <= 0) return hipSuccess;
     const bool fast = aligned16(cur) && aligned16(prev) && aligned16(out) && fb.stride % 16 == 0;
-    dim3 g = px16_grid(npix);
-    g.y = (unsigned)fb.nframes;
-    if (fast) hipLaunchKernelGGL((k_red_dense<true>), g, dim3(256), 0, s, cur, prev, out, npix, thr, fb.stride);
-    else hipLaunchKernelGGL((k_red_dense<false>), g, dim3(256), 0, s, cur, prev, out, npix, thr, fb.stride);
-    return hipGetLastError();
+    return for_frame_grids(fb.nframes, [&](size_t t0, unsigned cnt) {
+        dim3 g = px16_grid(npix);
+        g.y = cnt;
+        const size_t at = t0 * fb.stride;
+        if (fast) hipLaunchKernelGGL((k_red_dense<true>), g, dim3(256), 0, s, cur + at, prev + at, out + at, npix, thr, fb.stride);
+        else hipLaunchKernelGGL((k_red_dense<false>), g, dim3(256), 0, s, cur + at, prev + at, out + at, npix, thr, fb.stride);
+    });
 }
 
 // ---- red overlap: kernels.cu:273-281 (all entries; the h_pos/nMaxThreads truncation of :514 is not
@@ -749,11 +783,12 @@ hipError_t launch_red_stream(uint8_t *out, const uint32_t *offsets, const int32_
     if (fb.nframes <= 0 || nbytes == 0) return hipSuccess;
     if (clear && bounds_scratch && aligned16(out) && fb.stride % 16 == 0) {
         const uint32_t nb = red_bounds_per_frame(nbytes), nslices = nb - 1u;
-        hipLaunchKernelGGL(k_red_bounds, dim3((nb + 255u) / 256u, (unsigned)fb.nframes), dim3(256), 0, s, offsets, xs, nbytes,
-                           nb, bounds_scratch);
-        hipLaunchKernelGGL(k_red_stream_clear, dim3((nslices + 3u) / 4u, (unsigned)fb.nframes), dim3(256), 0, s, out,
-                           fb.stride, offsets, xs, nbytes, bounds_scratch, nslices);
-        return hipGetLastError();
+        return for_frame_grids(fb.nframes, [&](size_t t0, unsigned cnt) {   // (offsets[t] index xs as a whole: xs stays)
+            hipLaunchKernelGGL(k_red_bounds, dim3((nb + 255u) / 256u, cnt), dim3(256), 0, s, offsets + t0, xs, nbytes, nb,
+                               bounds_scratch + t0 * nb);
+            hipLaunchKernelGGL(k_red_stream_clear, dim3((nslices + 3u) / 4u, cnt), dim3(256), 0, s, out + t0 * fb.stride,
+                               fb.stride, offsets + t0, xs, nbytes, bounds_scratch + t0 * nb, nslices);
+        });
     }
     if (clear) {
         hipError_t e = fb.stride == nbytes
@@ -761,8 +796,9 @@ hipError_t launch_red_stream(uint8_t *out, const uint32_t *offsets, const int32_
                            : hipMemset2DAsync(out, fb.stride, 0, nbytes, (size_t)fb.nframes, s);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_red_stream, dim3(64, (unsigned)fb.nframes), dim3(256), 0, s, out, fb.stride, offsets, xs, nbytes);
-    return hipGetLastError();
+    return for_frame_grids(fb.nframes, [&](size_t t0, unsigned cnt) {
+        hipLaunchKernelGGL(k_red_stream, dim3(64, cnt), dim3(256), 0, s, out + t0 * fb.stride, fb.stride, offsets + t0, xs, nbytes);
+    });
 }
 
 // ---- 3x3 noise filter: kernels.cu:97-136 --------------------------------------------------------------
@@ -1100,9 +1136,10 @@ hipError_t launch_conv_kxk(const uint8_t *in, uint8_t *out, int w, int h, const 
                            hipStream_t s) {
     if (w <= 0 || h <= 0 || fb.nframes <= 0) return hipSuccess;
     const int rowbytes = 3 * w;
-    hipLaunchKernelGGL(k_conv_kxk, dim3((rowbytes + 255) / 256, (h + 3) / 4, (unsigned)fb.nframes), dim3(256), 0, s, in, out,
-                       rowbytes, h, kk, K, fb.stride);
-    return hipGetLastError();
+    return for_frame_grids(fb.nframes, [&](size_t t0, unsigned cnt) {
+        hipLaunchKernelGGL(k_conv_kxk, dim3((rowbytes + 255) / 256, (h + 3) / 4, cnt), dim3(256), 0, s, in + t0 * fb.stride,
+                           out + t0 * fb.stride, rowbytes, h, kk, K, fb.stride);
+    });
 }
 
 hipError_t launch_conv3x3(const uint8_t *in, uint8_t *out, int w, int h, const float *k9, bool k9_symmetric,
@@ -1110,18 +1147,22 @@ hipError_t launch_conv3x3(const uint8_t *in, uint8_t *out, int w, int h, const f
     if (w <= 0 || h <= 0 || fb.nframes <= 0) return hipSuccess;
     const int rowbytes = 3 * w;
     // (the strip kernel keeps lanes without work at an offset of 2^31 plus up to 40 rows: rows below 2^31 / 40 bytes)
-    if (rowbytes % 16 == 0 && aligned16(in) && aligned16(out) && fb.stride % 16 == 0 && rowbytes < (1 << 25)) {
-        const unsigned lanes = (unsigned)(rowbytes / 16) * (unsigned)((h + kStripRows - 1) / kStripRows);   // (band, strip) pairs
-        const dim3 grid((lanes + 63u) / 64u, 1, (unsigned)fb.nframes);
-        if (k9_symmetric)
-            hipLaunchKernelGGL((k_conv3x3_strip<true>), grid, dim3(64), 0, s, in, out, rowbytes, h, k9, fb.stride);
-        else
-            hipLaunchKernelGGL((k_conv3x3_strip<false>), grid, dim3(64), 0, s, in, out, rowbytes, h, k9, fb.stride);
-    } else {
-        const dim3 grid((w + kConvTW - 1) / kConvTW, (h + kConvRows - 1) / kConvRows, (unsigned)fb.nframes);
-        hipLaunchKernelGGL(k_conv3x3_any, grid, dim3(256), 0, s, in, out, w, h, k9, fb.stride);
-    }
-    return hipGetLastError();
+    const bool strip = rowbytes % 16 == 0 && aligned16(in) && aligned16(out) && fb.stride % 16 == 0 && rowbytes < (1 << 25);
+    return for_frame_grids(fb.nframes, [&](size_t t0, unsigned cnt) {
+        const uint8_t *i = in + t0 * fb.stride;
+        uint8_t *o = out + t0 * fb.stride;
+        if (strip) {
+            const unsigned lanes = (unsigned)(rowbytes / 16) * (unsigned)((h + kStripRows - 1) / kStripRows);   // (band, strip) pairs
+            const dim3 grid((lanes + 63u) / 64u, 1, cnt);
+            if (k9_symmetric)
+                hipLaunchKernelGGL((k_conv3x3_strip<true>), grid, dim3(64), 0, s, i, o, rowbytes, h, k9, fb.stride);
+            else
+                hipLaunchKernelGGL((k_conv3x3_strip<false>), grid, dim3(64), 0, s, i, o, rowbytes, h, k9, fb.stride);
+        } else {
+            const dim3 grid((w + kConvTW - 1) / kConvTW, (h + kConvRows - 1) / kConvRows, cnt);
+            hipLaunchKernelGGL(k_conv3x3_any, grid, dim3(256), 0, s, i, o, w, h, k9, fb.stride);
+        }
+    });
 }
 
 // ---- 5x5 median: tests/noise_filter_benchmark/v3.cu:32-90 ----------------------------------------------
@@ -1377,13 +1418,16 @@ hipError_t launch_median5x5(const uint8_t *in, uint8_t *out, int w, int h, int r
         const int strips = (int)(rowbytes / 8);
         const int bandrows = rows_per_band > 0 ? rows_per_band : median_bandrows(h, strips, fb.nframes);
         const int pairs = (h + 2 * bandrows - 1) / (2 * bandrows);
-        const dim3 grid((unsigned)(((long)pairs * (strips + 2) + kMedStripLanes - 1) / kMedStripLanes), 1, (unsigned)fb.nframes);
-        hipLaunchKernelGGL(k_median5x5_strip, grid, dim3(64), 0, s, in, out, (int)rowbytes, h, bandrows, pairs, fb.stride);
-        return hipGetLastError();
+        return for_frame_grids(fb.nframes, [&](size_t t0, unsigned cnt) {
+            const dim3 grid((unsigned)(((long)pairs * (strips + 2) + kMedStripLanes - 1) / kMedStripLanes), 1, cnt);
+            hipLaunchKernelGGL(k_median5x5_strip, grid, dim3(64), 0, s, in + t0 * fb.stride, out + t0 * fb.stride, (int)rowbytes, h,
+                               bandrows, pairs, fb.stride);
+        });
     }
-    const dim3 grid((w + kMedTW - 1) / kMedTW, (h + kMedTR - 1) / kMedTR, (unsigned)fb.nframes);
-    hipLaunchKernelGGL(k_median5x5, grid, dim3(256), 0, s, in, out, w, h, fb.stride);
-    return hipGetLastError();
+    return for_frame_grids(fb.nframes, [&](size_t t0, unsigned cnt) {
+        const dim3 grid((w + kMedTW - 1) / kMedTW, (h + kMedTR - 1) / kMedTR, cnt);
+        hipLaunchKernelGGL(k_median5x5, grid, dim3(256), 0, s, in + t0 * fb.stride, out + t0 * fb.stride, w, h, fb.stride);
+    });
 }
 
 // ---- text overlay: kernel2_char, kernels.cu:351-375 (row-exact blit, no 32-byte straddle) ---------

@@ -476,7 +476,9 @@ int mi355_red_overlap(mi355_core *core, void *d_img, const void *d_xs, const voi
  * clear != 0 builds every frame from its entries in ONE write-only pass and needs them ASCENDING within the
  * frame -- as every diff entry point of this library produces them (the pass finds a slice's entries by
  * binary search; entries out of order would be dropped without an error) -- and nframes <= max_batch.
- * clear == 0 is a plain scatter: any order, any nframes. */
+ * clear == 0 is a plain scatter: any order, any nframes.
+ * Either form takes frame counts beyond 65535 (the frame is a grid dimension of its kernels): such a batch is issued
+ * as several grids of at most 65535 frames each, with the same result as one. */
 int mi355_red_stream_batch(mi355_core *core, const void *d_offsets, const void *d_xs, int nframes,
                            void *d_frames, size_t stride_bytes, int clear);
 /* kernels.cu:97-136: 3x3 convolution with the kernel of mi355_set_conv_kernel; not in-place.  fp32, taps in
@@ -497,7 +499,12 @@ int mi355_median5x5(mi355_core *core, const void *d_in, void *d_out);
  * for the two-input filters) -> d_out + t*stride_bytes, one launch per kernel for the whole batch.
  * The *_BINARIZE ops compute one histogram and one two-max threshold per frame; the fused forms read the colour
  * frame ONCE: pass 1 converts it and keeps one gray byte per pixel in a scratch of the core (max_batch * N/3 bytes,
- * allocated at the first such call) beside the histogram, pass 2 binarizes from that scratch (BASELINE config 3). */
+ * allocated at the first such call) beside the histogram, pass 2 binarizes from that scratch (BASELINE config 3).
+ * Every nframes in [0, max_batch] is accepted, whatever max_batch mi355_create allowed: up to 65535 frames are one launch
+ * per kernel; a longer batch is issued as several grids of at most 65535 frames each (the frame is a grid dimension),
+ * every slice with its own frames, histograms and thresholds, and computes what one launch would.  An argument the call
+ * refuses (MI355_ERR_INVALID) is refused before anything is written; any other error (MI355_ERR_HIP from an allocation or a
+ * launch, MI355_ERR_STATE) may leave the output frames, and the core's histograms and thresholds, partly written. */
 #define MI355_OP_GRAY_AVG 1                /* kernels.cu:31-43                         */
 #define MI355_OP_GRAY_WEIGHTED 2           /* kernels.cu:67-95                         */
 #define MI355_OP_BINARIZE 3                /* gray3 in: kernels.cu:138-241             */

@@ -83,21 +83,29 @@ class Region:
         self.ptr = self.t.data_ptr()
         assert self.buf.data_ptr() % 16 == 0 and self.ptr % 16 == skew % 16
 
+    def _frames(self, h):
+        """The [S, stride] view of a host copy of the buffer: columns [:n] are the frames, [n:] the stride gaps."""
+        return h[self.lo:self.lo + self.S * self.stride].reshape(self.S, self.stride)
+
     def put(self, rows):
+        """rows: up to S rows of n bytes (one [S, n] array is copied in one piece, whatever S is)."""
         h = np.full(self.buf.numel(), GUARD, np.uint8)
-        for s, row in enumerate(rows):
-            h[self.lo + s * self.stride:self.lo + s * self.stride + self.n] = row
+        if isinstance(rows, np.ndarray) and rows.shape == (self.S, self.n):
+            self._frames(h)[:, :self.n] = rows
+        else:
+            for s, row in enumerate(rows):
+                h[self.lo + s * self.stride:self.lo + s * self.stride + self.n] = row
         self.buf.copy_(to_dev(h))
         return self
 
     def get(self):
         """(rows as numpy [S, n]); asserts the guard bytes."""
         h = self.buf.cpu().numpy()
-        keep = np.zeros(h.size, bool)
-        for s in range(self.S):
-            keep[self.lo + s * self.stride:self.lo + s * self.stride + self.n] = True
-        assert (h[~keep] == GUARD).all(), "bytes outside the frames were written"
-        return h[keep].reshape(self.S, self.n)
+        body = self._frames(h)
+        assert (h[:self.lo] == GUARD).all(), "bytes in front of the frames were written"
+        assert (h[self.lo + self.S * self.stride:] == GUARD).all(), "bytes behind the frames were written"
+        assert (body[:, self.n:] == GUARD).all(), "bytes in the stride gaps were written"
+        return body[:, :self.n].copy()
 
     def clone(self):
         r = Region(self.S, self.n, self.stride, self.skew)
