@@ -64,6 +64,13 @@ public:
     // frame at d_states + s*stride, which is then the frame to show.  Blocking, like exec_multi; the same nstreams bound.
     void apply_multi(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, int nstreams, void *d_states,
                      size_t stride);
+    // The receiving end of a burst (include/mi355diff.h, mi355_apply_multi_stream_cwire_batch): the nframes records of camera s
+    // -- records back to back in DEVICE memory, camera-major as exec_multi_stream's sender made them, headers counts[s*nframes
+    // + t] / escapes[...] as read from the sockets -- are applied in order to the frame at d_states + s*stride; d_frames_out !=
+    // nullptr: the frame after record t also goes to d_frames_out + (s*nframes + t)*out_stride.  Blocking, like apply_multi;
+    // nstreams*nframes <= MI355_MAX_BATCH.
+    void apply_multi_stream(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, int nstreams, int nframes,
+                            void *d_states, size_t stride, void *d_frames_out, size_t out_stride);
 };
 
 static_assert(sizeof(CUDACore) == 160, "must match the reference's object size (LP64)");

@@ -110,6 +110,13 @@ void CUDACore::apply_multi(const void *d_cwire, const uint32_t *counts, const ui
     MI355_CHECK(mi355_synchronize(core_));
 }
 
+void CUDACore::apply_multi_stream(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, int nstreams, int nframes,
+                                  void *d_states, size_t stride, void *d_frames_out, size_t out_stride) {
+    MI355_CHECK(mi355_apply_multi_stream_cwire_batch(core_, d_cwire, counts, escapes, nstreams, nframes, d_states, stride,
+                                                     d_frames_out, out_stride));
+    MI355_CHECK(mi355_synchronize(core_));
+}
+
 size_t CUDACore::chunkt_size() { return 32; }  // sizeof(long4), kernels.cu:27,527-529
 
 void CUDACore::alloc_arrays(uint8_t **h_frame, uint8_t **n_frame, uint8_t **o_frame, int **h_xs, int r,

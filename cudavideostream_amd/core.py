@@ -332,6 +332,45 @@ class CUDACore:
         _l.check(self._lib.mi355_apply_multi_cwire_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
                                                          int(nstreams), _ptr(d_states), int(stride)))
 
+    # ... and of a burst: segments / records s * nframes + t, t in order, onto d_states[s]; the frames in between on request
+    def apply_multi_stream_batch(self, d_offsets, d_xs, d_diff, nstreams, nframes, d_states, stride=None, d_frames_out=None,
+                                 out_stride=None):
+        """client/opencv.cpp:64-66 for nframes ticks of nstreams streams, stream-major as diff_multi_stream_batch makes them:
+        segments s * nframes .. (s + 1) * nframes - 1 are added to d_states[s] in order.  d_frames_out: the frame of stream s
+        after segment t is also written at (s * nframes + t) * out_stride.  The core's own state is not involved."""
+        self._hold(d_offsets, d_xs, d_diff, d_states, d_frames_out)
+        stride = self.total if stride is None else stride
+        out_stride = self.total if out_stride is None else out_stride
+        _l.check(self._lib.mi355_apply_multi_stream_batch(self._h, _ptr(d_offsets), _ptr(d_xs), _ptr(d_diff), int(nstreams),
+                                                          int(nframes), _ptr(d_states), int(stride), _ptr(d_frames_out),
+                                                          int(out_stride)))
+
+    def apply_multi_stream_wire_batch(self, d_wire, counts, nstreams, nframes, d_states, stride=None, d_frames_out=None,
+                                      out_stride=None):
+        """apply_multi_stream_batch from the wire bytes; counts[s * nframes + t]: the headers as read from the sockets."""
+        self._hold(d_wire, d_states, d_frames_out)
+        stride = self.total if stride is None else stride
+        out_stride = self.total if out_stride is None else out_stride
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        assert counts.size >= nstreams * nframes
+        _l.check(self._lib.mi355_apply_multi_stream_wire_batch(self._h, _ptr(d_wire), counts.ctypes.data, int(nstreams),
+                                                               int(nframes), _ptr(d_states), int(stride), _ptr(d_frames_out),
+                                                               int(out_stride)))
+
+    def apply_multi_stream_cwire_batch(self, d_cwire, counts, escapes, nstreams, nframes, d_states, stride=None,
+                                       d_frames_out=None, out_stride=None):
+        """apply_multi_stream_batch straight from compact records, back to back in s * nframes + t order where the headers
+        (counts, escapes) put them; a tile of a state is loaded and stored once per call, and only if a record touches it."""
+        self._hold(d_cwire, d_states, d_frames_out)
+        stride = self.total if stride is None else stride
+        out_stride = self.total if out_stride is None else out_stride
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+        assert counts.size >= nstreams * nframes and escapes.size >= nstreams * nframes
+        _l.check(self._lib.mi355_apply_multi_stream_cwire_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
+                                                                int(nstreams), int(nframes), _ptr(d_states), int(stride),
+                                                                _ptr(d_frames_out), int(out_stride)))
+
     def wire_bytes(self, nframes, entries):
         return self._lib.mi355_wire_bytes(nframes, entries)
 

@@ -1219,6 +1219,137 @@ int mi355_apply_multi_cwire_batch(mi355_core *c, const void *d_cwire, const uint
     return MI355_OK;
 }
 
+// ---- mi355_apply_multi_stream_*: nframes segments / records of each of nstreams streams, batch index b = s*nframes + t -------
+// What the three forms refuse alike, before anything is launched; *run = there is something to do
+static int check_apply_multi_stream(mi355_core *c, bool inputs, int nstreams, int nframes, const void *d_states, size_t stride,
+                                    const void *d_out, size_t out_stride, bool *run) {
+    *run = false;
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nstreams < 0 || nframes < 0) return fail(MI355_ERR_INVALID, "nstreams or nframes < 0");
+    const int64_t B = (int64_t)nstreams * nframes;
+    if (B > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams * nframes above max_batch");
+    if (B == 0) return MI355_OK;
+    if (!inputs) return fail(MI355_ERR_INVALID, "null stream pointer");
+    if (!d_states) return fail(MI355_ERR_INVALID, "null d_states");
+    if (stride < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
+    if (d_out) {
+        if (out_stride < c->n) return fail(MI355_ERR_INVALID, "out_stride_bytes < frame bytes");
+        const uintptr_t s = (uintptr_t)d_states, o = (uintptr_t)d_out;
+        const uintptr_t sspan = (uintptr_t)(nstreams - 1) * stride + c->n, ospan = (uintptr_t)(B - 1) * out_stride + c->n;
+        if (s < o + ospan && o < s + sspan) return fail(MI355_ERR_INVALID, "the states overlap the output frames");
+    }
+    *run = c->n > 0;
+    return MI355_OK;
+}
+
+// An input of `bytes` bytes (known from the host's headers) against the states and the output frames
+static int check_apply_multi_stream_overlap(const mi355_core *c, const void *d_in, uint64_t bytes, int nstreams, int nframes,
+                                            const void *d_states, size_t stride, const void *d_out, size_t out_stride) {
+    if (int rc = check_apply_multi_overlap(c, d_in, bytes, d_states, stride, nstreams)) return rc;
+    if (!d_out) return MI355_OK;
+    const uintptr_t in = (uintptr_t)d_in, o = (uintptr_t)d_out;
+    const uintptr_t ospan = (uintptr_t)((int64_t)nstreams * nframes - 1) * out_stride + c->n;
+    if (in < o + ospan && o < in + (uintptr_t)bytes) return fail(MI355_ERR_INVALID, "the output frames overlap the input stream");
+    return MI355_OK;
+}
+
+int mi355_apply_multi_stream_batch(mi355_core *c, const void *d_offsets, const void *d_xs, const void *d_diff, int nstreams,
+                                   int nframes, void *d_states, size_t stride_bytes, void *d_frames_out, size_t out_stride_bytes) {
+    bool run;
+    if (int rc = check_apply_multi_stream(c, d_offsets && d_xs && d_diff, nstreams, nframes, d_states, stride_bytes, d_frames_out,
+                                          out_stride_bytes, &run))
+        return rc;
+    if (nstreams > 0 && nframes > 0 && (((uintptr_t)d_offsets | (uintptr_t)d_xs) & 3u))
+        return fail(MI355_ERR_INVALID, "d_offsets and d_xs must be 4-byte aligned");
+    if (!run) return MI355_OK;
+    if (int rc = use_device(c)) return rc;
+    for (int t = 0; t < nframes; t++) {   // records of one stream may hit the same byte: one launch per t (stream_ops.hip)
+        HIP_TRY(launch_apply_multi_strided((uint8_t *)d_states, stride_bytes, c->n, (const uint32_t *)d_offsets,
+                                           (const int32_t *)d_xs, (const uint8_t *)d_diff, nstreams, nframes, t, c->stream));
+        if (d_frames_out)
+            HIP_TRY(launch_apply_multi_show((const uint8_t *)d_states, stride_bytes, c->n, (uint8_t *)d_frames_out, out_stride_bytes,
+                                            nstreams, nframes, t, c->stream));
+    }
+    return MI355_OK;
+}
+
+int mi355_apply_multi_stream_wire_batch(mi355_core *c, const void *d_wire, const uint32_t *h_counts, int nstreams, int nframes,
+                                        void *d_states, size_t stride_bytes, void *d_frames_out, size_t out_stride_bytes) {
+    bool run;
+    if (int rc = check_apply_multi_stream(c, d_wire && h_counts, nstreams, nframes, d_states, stride_bytes, d_frames_out,
+                                          out_stride_bytes, &run))
+        return rc;
+    const int B = nstreams > 0 && nframes > 0 ? nstreams * nframes : 0;   // (<= max_batch)
+    if (B == 0) return MI355_OK;
+    std::vector<uint64_t> pos((size_t)B + 1);   // pos[b]: byte position of {n, xs, diff} of batch index b
+    pos[0] = 0;
+    for (int b = 0; b < B; b++) {
+        if (h_counts[b] > c->n) return fail(MI355_ERR_INVALID, "frame count larger than the frame");
+        pos[b + 1] = pos[b] + mi355_wire_bytes(1, h_counts[b]);
+    }
+    if (int rc = check_apply_multi_stream_overlap(c, d_wire, pos[B], nstreams, nframes, d_states, stride_bytes, d_frames_out,
+                                                  out_stride_bytes))
+        return rc;
+    if (!run) return MI355_OK;
+    if (int rc = use_device(c)) return rc;
+    ApplyMultiWireArgs h{};
+    for (int t = 0; t < nframes; t++) {   // launch t: record s*nframes + t of every stream s, 128 streams per launch
+        for (int s0 = 0; s0 < nstreams; s0 += kApplyMultiWireStreams) {
+            h.first = s0;
+            h.count = nstreams - s0 < kApplyMultiWireStreams ? nstreams - s0 : kApplyMultiWireStreams;
+            h.cum[0] = 0;
+            for (int j = 0; j < h.count; j++) {
+                const size_t b = (size_t)(s0 + j) * nframes + t;
+                h.pos[j] = pos[b];
+                h.cum[j + 1] = h.cum[j] + h_counts[b];
+            }
+            HIP_TRY(launch_apply_multi_wire((uint8_t *)d_states, stride_bytes, c->n, (const uint8_t *)d_wire, h, c->stream));
+        }
+        if (d_frames_out)
+            HIP_TRY(launch_apply_multi_show((const uint8_t *)d_states, stride_bytes, c->n, (uint8_t *)d_frames_out, out_stride_bytes,
+                                            nstreams, nframes, t, c->stream));
+    }
+    return MI355_OK;
+}
+
+int mi355_apply_multi_stream_cwire_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
+                                         int nstreams, int nframes, void *d_states, size_t stride_bytes, void *d_frames_out,
+                                         size_t out_stride_bytes) {
+    bool run;
+    if (int rc = check_apply_multi_stream(c, d_cwire && h_counts && h_escapes, nstreams, nframes, d_states, stride_bytes,
+                                          d_frames_out, out_stride_bytes, &run))
+        return rc;
+    const int B = nstreams > 0 && nframes > 0 ? nstreams * nframes : 0;   // (<= max_batch)
+    if (B == 0) return MI355_OK;
+    if ((uintptr_t)d_cwire & 3u) return fail(MI355_ERR_INVALID, "d_cwire must be 4-byte aligned");
+    CwireHeaders hdr{h_counts, h_escapes, B};
+    if (int rc = hdr.check(true, c->n)) return rc;
+    std::vector<CwaFrame> fr((size_t)B);   // B <= max_batch: the scratch of the one-stream client holds them
+    uint32_t cbase = 0;
+    for (int b = 0; b < B; b++) {
+        const CwireHeaders::Frame f = hdr.next();
+        fr[b] = CwaFrame{f.pos, f.n, f.e, cbase, cwa_chunks(f.n)};
+        cbase += fr[b].nc;
+    }
+    if (int rc = check_apply_multi_stream_overlap(c, d_cwire, hdr.pos, nstreams, nframes, d_states, stride_bytes, d_frames_out,
+                                                  out_stride_bytes))
+        return rc;
+    if (!run) return MI355_OK;
+    if (int rc = use_device(c)) return rc;
+    CwaArgs a{};
+    a.cwire = (const uint8_t *)d_cwire;
+    a.ftab = c->cwa_ftab;
+    a.chunk = c->cwa_chunk;
+    a.dir = c->cwa_dir;
+    a.state = (uint8_t *)d_states;
+    a.out = (uint8_t *)d_frames_out;
+    a.stride = stride_bytes;
+    a.n = c->n;
+    a.ntiles = cwa_tiles(c->n);
+    HIP_TRY(launch_cwire_apply_multi_stream(a, fr.data(), nstreams, nframes, out_stride_bytes, c->stream));
+    return MI355_OK;
+}
+
 // client/opencv.cpp:50-66 on the compact stream, on the host.  A frame is validated whole before any byte of the state
 // changes, so a malformed frame leaves the state as the frames before it made it.
 int mi355_cwire_apply_host(uint8_t *state, size_t frame_bytes, const void *cwire, size_t cwire_bytes, int nframes,

@@ -127,6 +127,12 @@ struct ApplyMultiWireArgs {
 };
 hipError_t launch_apply_multi_wire(uint8_t *states, size_t stride, uint32_t nbytes, const uint8_t *wire,
                                    const ApplyMultiWireArgs &h, hipStream_t s);
+// mi355_apply_multi_stream_*: launch t of a burst takes segment s*nframes + t of every stream s; ..._show copies the states
+// to the output frames s*nframes + t (out + b*out_stride) afterwards
+hipError_t launch_apply_multi_strided(uint8_t *states, size_t stride, uint32_t nbytes, const uint32_t *d_offsets, const int32_t *xs,
+                                      const uint8_t *diff, int nstreams, int nframes, int t, hipStream_t s);
+hipError_t launch_apply_multi_show(const uint8_t *states, size_t stride, uint32_t nbytes, uint8_t *out, size_t out_stride,
+                                   int nstreams, int nframes, int t, hipStream_t s);
 hipError_t launch_export(const uint32_t *offsets, const int32_t *xs, const uint8_t *diff, int32_t *h_xs,
                          uint8_t *h_diff, uint32_t *h_count, hipStream_t s);
 hipError_t launch_merge(const MergeArgs &a, uint32_t *out_offsets, hipStream_t s);
@@ -184,6 +190,10 @@ uint32_t cwa_tiles(uint32_t nbytes);
 hipError_t launch_cwire_apply(const CwaArgs &a, const CwaFrame *frames, int nframes, hipStream_t s);
 // mi355_apply_multi_cwire_batch: record s onto a.state + s*a.stride (the caller's states; a.out unused), tiles x streams
 hipError_t launch_cwire_apply_multi(const CwaArgs &a, const CwaFrame *records, int nstreams, hipStream_t s);
+// mi355_apply_multi_stream_cwire_batch: records s*nframes + t, t in order, onto a.state + s*a.stride; a.out != nullptr: the frame
+// after record b = s*nframes + t also to a.out + b*out_stride (a.stride is the states')
+hipError_t launch_cwire_apply_multi_stream(const CwaArgs &a, const CwaFrame *records, int nstreams, int nframes, size_t out_stride,
+                                           hipStream_t s);
 
 // filters.hip -- every per-frame kernel takes a FrameBatch: frame f lives at base + f*stride
 struct FrameBatch {

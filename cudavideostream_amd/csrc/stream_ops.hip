@@ -2,13 +2,15 @@
 //
 //   k_apply / k_apply_all : the client's reconstruction, client/opencv.cpp:64-66
 //                           (`frame2.data[xs[i]] += buffer[i]` for the pos entries of a frame);
-//   k_apply_multi(_wire)  : the same for one segment of each of many streams, onto the caller's states;
+//   k_apply_multi(_wire)  : the same for one segment of each of many streams, onto the caller's states
+//                           (k_apply_multi_strided: segment s*T + t of each, one launch per t of a burst);
 //   k_merge_parts         : concatenation of the streams of the row bands of ONE video stream that
 //                           several cores (GPUs) packed independently into
 //                           the single stream the sender would have produced;
 //   k_cwire_*             : the compact wire format's encoder (packed stream -> gap-coded records) and decoder;
 //   k_cwa_*               : the compact records applied straight to a client core's state (mi355_apply_cwire_batch) or,
-//                           one record per stream, to the caller's states (mi355_apply_multi_cwire_batch).
+//                           one record per stream, to the caller's states (mi355_apply_multi_cwire_batch), or a burst of
+//                           records per stream, with the frames in between (mi355_apply_multi_stream_cwire_batch).
 //
 // The first two are index-driven byte scatter/copy: HBM-latency work with 5 bytes of traffic per entry, no
 // arithmetic worth naming.
@@ -162,6 +164,63 @@ hipError_t launch_apply_multi_wire(uint8_t *states, size_t stride, uint32_t nbyt
     const uint64_t blocks = (total + 255u) / 256u;
     hipLaunchKernelGGL(k_apply_multi_wire, dim3((uint32_t)(blocks > 2048u ? 2048u : blocks)), dim3(256), 0, s, states, stride,
                        nbytes, wire, h);
+    return hipGetLastError();
+}
+
+// ---- mi355_apply_multi_stream_batch / _wire_batch: nframes records of each stream, batch index b = s*nframes + t -------------
+// Records of ONE stream may hit the same byte, so the argument above does not reach across t: the host issues one launch per
+// t, and launch t takes the segments s*nframes + t of all streams -- one per state, race-free as above.  The segments of a
+// launch are not neighbours in the offsets, so the grid is (x, streams) and a workgroup strides over its stream's segment;
+// the wire form keeps k_apply_multi_wire (its segments' places are kernel arguments anyway).
+__global__ __launch_bounds__(256) void k_apply_multi_strided(uint8_t *states, size_t stride, uint32_t nbytes, const uint32_t *offsets,
+                                                             const int32_t *xs, const uint8_t *diff, uint32_t nstreams,
+                                                             uint32_t nframes, uint32_t t) {
+    const uint32_t step = gridDim.x * 256u;
+    for (uint32_t s = blockIdx.y; s < nstreams; s += gridDim.y) {
+        const size_t b = (size_t)s * nframes + t;
+        const uint32_t first = offsets[b], end = offsets[b + 1];
+        uint8_t *state = states + (size_t)s * stride;
+        for (uint64_t i = (uint64_t)first + blockIdx.x * 256u + threadIdx.x; i < end; i += step) {
+            const uint32_t x = (uint32_t)xs[i];
+            if (x >= nbytes) continue;
+            state[x] = (uint8_t)(state[x] + diff[i]);   // opencv.cpp:65
+        }
+    }
+}
+
+// State s -> output frame s*nframes + t (what the client shows after record t): the N bytes and nothing else; 16-byte words
+// when both addresses allow.
+__global__ __launch_bounds__(256) void k_apply_multi_show(const uint8_t *states, size_t stride, uint32_t nbytes, uint8_t *out,
+                                                          size_t out_stride, uint32_t nstreams, uint32_t nframes, uint32_t t) {
+    const uint32_t gid = blockIdx.x * 256u + threadIdx.x, step = gridDim.x * 256u;
+    for (uint32_t s = blockIdx.y; s < nstreams; s += gridDim.y) {
+        const uint8_t *src = states + (size_t)s * stride;
+        uint8_t *dst = out + ((size_t)s * nframes + t) * out_stride;
+        const uint32_t q = (((uintptr_t)src | (uintptr_t)dst) & 15u) ? 0u : nbytes / 16u;
+        for (uint32_t i = gid; i < q; i += step) ((uint4 *)dst)[i] = ((const uint4 *)src)[i];
+        for (uint32_t i = 16 * q + gid; i < nbytes; i += step) dst[i] = src[i];
+    }
+}
+
+// a grid of (x, streams) workgroups, about 1024 in all, no more along x than the frame has 256-byte pieces
+static dim3 apply_multi_strided_grid(uint32_t nbytes, int nstreams) {
+    const uint32_t y = nstreams < 65535 ? (uint32_t)nstreams : 65535u;
+    uint32_t x = 1024u / y, most = (nbytes + 255u) / 256u;
+    if (x > most) x = most;
+    return dim3(x ? x : 1u, y);
+}
+
+hipError_t launch_apply_multi_strided(uint8_t *states, size_t stride, uint32_t nbytes, const uint32_t *d_offsets, const int32_t *xs,
+                                      const uint8_t *diff, int nstreams, int nframes, int t, hipStream_t s) {
+    hipLaunchKernelGGL(k_apply_multi_strided, apply_multi_strided_grid(nbytes, nstreams), dim3(256), 0, s, states, stride, nbytes,
+                       d_offsets, xs, diff, (uint32_t)nstreams, (uint32_t)nframes, (uint32_t)t);
+    return hipGetLastError();
+}
+
+hipError_t launch_apply_multi_show(const uint8_t *states, size_t stride, uint32_t nbytes, uint8_t *out, size_t out_stride,
+                                   int nstreams, int nframes, int t, hipStream_t s) {
+    hipLaunchKernelGGL(k_apply_multi_show, apply_multi_strided_grid(nbytes, nstreams), dim3(256), 0, s, states, stride, nbytes, out,
+                       out_stride, (uint32_t)nstreams, (uint32_t)nframes, (uint32_t)t);
     return hipGetLastError();
 }
 
@@ -750,6 +809,81 @@ __global__ __launch_bounds__(64) void k_cwa_apply_multi(const CwaArgs a) {
     cwa_tile_store(tile_bytes, s, len, lane);
 }
 
+// ---- mi355_apply_multi_stream_cwire_batch: records s*nframes .. (s + 1)*nframes - 1 onto the caller's state s, in order ----
+// Grid of tiles x streams as above.  Lane j asks the directory whether record t = j of its stream (passes of 64 records) has
+// an entry in the tile, and a ballot gives the pass's set of records that do.  The tile is loaded from states[s] once, when
+// the first pass with a record for it comes (at once when frames go out), and stored back once, non-temporal, if a record
+// touched it: a tile that none of the stream's records lands in is neither read nor written when no frames go out.  The
+// walk over t runs cwa_apply_record for the records of the set only -- the others cost neither a directory word nor a code
+// load -- with the next such record's header, directory word and first block in flight, and with output frames stores the
+// tile to frame s*nframes + t after every t.  No store leaves the tile's own [lo, hi) of its state or of its output frame;
+// the states are the caller's (any alignment), so the write-back is cwa_tile_store, not k_cwa_apply's aligned epilogue.
+__global__ __launch_bounds__(64) void k_cwa_apply_multi_stream(const CwaArgs a, int nframes, size_t out_stride) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
+    uint8_t *s = (uint8_t *)s_q;
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    const uint32_t hi = lo + len;
+    const size_t b0 = (size_t)st * nframes;   // the stream's first batch index
+    uint8_t *tile_bytes = a.state + (size_t)st * a.stride + lo;
+    bool loaded = false, dirty = false;
+    for (int base = 0; base < nframes; base += 64) {
+        bool touch = false;
+        if (base + lane < nframes) {
+            const size_t b = b0 + base + lane;
+            const uint32_t fn = a.ftab[b].n;
+            const uint4 *dir = a.dir + b * a.ntiles + tile;
+            const uint32_t k0 = dir[0].x, kend = tile + 1 < a.ntiles ? dir[1].x : fn;
+            touch = k0 < kend && k0 < fn;
+        }
+        const uint64_t set = __ballot(touch);
+        if (!set && !a.out) continue;
+        if (!loaded) {
+            cwa_tile_load(s, tile_bytes, len, lane);
+            loaded = true;
+        }
+        const int cnt = nframes - base < 64 ? nframes - base : 64;
+        // while record j is applied, the header, directory word and first block of the set's next record are in flight
+        CwaFrame f1{};
+        uint4 d1{};
+        CwaBlock b1{};
+        int j = a.out ? 0 : __ffsll((unsigned long long)set) - 1, jn = set ? __ffsll((unsigned long long)set) - 1 : cnt;
+        if (jn < cnt) {
+            f1 = a.ftab[b0 + base + jn];
+            d1 = a.dir[(b0 + base + jn) * a.ntiles + tile];
+            b1 = cwa_block_load(a, f1, d1.x, lane);
+        }
+        __syncthreads();
+        while (j < cnt) {
+            if (j == jn) {
+                const CwaFrame f = f1;
+                const uint4 dr = d1;
+                const CwaBlock b = b1;
+                const uint64_t rest = set & ~((2ull << j) - 1ull);   // (j = 63: 2 << 63 is 0, rest = 0)
+                jn = rest ? __ffsll((unsigned long long)rest) - 1 : cnt;
+                if (jn < cnt) {
+                    f1 = a.ftab[b0 + base + jn];
+                    d1 = a.dir[(b0 + base + jn) * a.ntiles + tile];
+                    b1 = cwa_block_load(a, f1, d1.x, lane);
+                }
+                cwa_apply_record(s, a, f, dr, b, lo, hi, lane);
+                dirty = true;
+                __syncthreads();
+            }
+            if (a.out) {
+                cwa_tile_store(a.out + (b0 + base + j) * out_stride + lo, s, len, lane);
+                __syncthreads();
+                j++;
+            } else {
+                j = jn;
+            }
+        }
+    }
+    if (dirty) cwa_tile_store(tile_bytes, s, len, lane);
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 uint32_t cwa_chunks(uint32_t n) { return n ? (n + kCwaChunk - 1) / kCwaChunk : 1u; }
 uint32_t cwa_tiles(uint32_t nbytes) { return (nbytes + kCwaTile - 1) / kCwaTile; }
@@ -785,6 +919,14 @@ hipError_t launch_cwire_apply_multi(const CwaArgs &a, const CwaFrame *records, i
     if (nstreams <= 0 || a.ntiles == 0) return hipSuccess;
     launch_cwa_directory(a, records, nstreams, s);
     hipLaunchKernelGGL(k_cwa_apply_multi, dim3(a.ntiles * (uint32_t)nstreams), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_cwire_apply_multi_stream(const CwaArgs &a, const CwaFrame *records, int nstreams, int nframes, size_t out_stride,
+                                           hipStream_t s) {
+    if (nstreams <= 0 || nframes <= 0 || a.ntiles == 0) return hipSuccess;
+    launch_cwa_directory(a, records, nstreams * nframes, s);
+    hipLaunchKernelGGL(k_cwa_apply_multi_stream, dim3(a.ntiles * (uint32_t)nstreams), dim3(64), 0, s, a, nframes, out_stride);
     return hipGetLastError();
 }
 

@@ -85,7 +85,8 @@ typedef struct mi355_config {
  *      mi355_diff_multi_cwire_batch (additions only: no existing argument list changed, so the number stays);
  *      + mi355_apply_multi_batch, mi355_apply_multi_wire_batch, mi355_apply_multi_cwire_batch (additions only);
  *      + mi355_diff_multi_stream_batch, mi355_diff_multi_stream_wire_batch, mi355_diff_multi_stream_cwire_batch (additions
- *      only) */
+ *      only); + mi355_apply_multi_stream_batch, mi355_apply_multi_stream_wire_batch, mi355_apply_multi_stream_cwire_batch
+ *      (additions only) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -365,6 +366,69 @@ int mi355_apply_multi_wire_batch(mi355_core *core, const void *d_wire, const uin
 int mi355_apply_multi_cwire_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts,
                                   const uint32_t *h_escapes, int nstreams, void *d_states,
                                   size_t stride_bytes);
+/* The receiving end of a burst, the counterpart of mi355_diff_multi_stream_*: nframes segments or records of each of nstreams
+ * streams are applied to nstreams states in the CALLER's memory in ONE call, straight from the stream-major layout the
+ * sockets delivered.  The batch index is b = s*nframes + t and the inputs have exactly the layout of the outputs of
+ * mi355_diff_multi_stream_*: d_offsets is uint32[nstreams*nframes + 1] over (d_xs, d_diff); the wire form holds
+ * {u32 n, i32 xs[n], u8 diff[n]} of index b at byte 4*b + 5*sum(h_counts[0..b)); the compact records lie back to back in b
+ * order where h_counts[b] = n and h_escapes[b] = e put them.  The headers come from the host; the header words in the buffer
+ * are skipped, not trusted, as in mi355_apply_multi_*.
+ * For every s the records t = 0 .. nframes - 1 are applied in order to the N bytes at d_states + s*stride_bytes (state[x] +=
+ * diff, uint8 wrap-around): bit-identical to mi355_apply_batch / _wire_batch / _cwire_batch(nframes) on a client core whose
+ * state is states[s], to mi355_cwire_apply_host on that stream's slice, and to nframes ticks of mi355_apply_multi_* on
+ * re-staged records.  With nframes == 1 it is mi355_apply_multi_*, with nstreams == 1 the one-stream client on a caller-held
+ * state.  The core's own state is neither read nor written.
+ * d_frames_out != NULL: the frame of stream s after record t is also written to d_frames_out + b*out_stride_bytes (N bytes
+ * each, the gap of the stride is never written; any alignment works, whole 16-byte stores when the pointer and the stride
+ * are multiples of 16) -- what a video wall or a recorder shows between the ends of a burst.  NULL: only the states advance
+ * and out_stride_bytes is ignored.
+ *   Written bytes: nothing outside the N bytes of each state and of each output frame; record (s, t) never changes a byte
+ *   of states[r], r != s -- also with stride_bytes == N and N no multiple of 4 or 16.
+ *   Malformed compact content under consistent headers: the guarantees of mi355_apply_multi_cwire_batch -- nothing is read
+ *   outside the records' span, nothing is written outside the states and the output frames, an escape ranked at or past e
+ *   and an index >= N change nothing; beyond that only the malformed stream's own state and frames are unspecified.
+ *   Refused with MI355_ERR_INVALID before anything is launched or written: a null core; a negative nstreams or nframes;
+ *   nstreams*nframes > max_batch (the directory scratch of mi355_apply_cwire_batch holds max_batch records); with
+ *   nstreams*nframes > 0 a null input pointer, a null d_states or stride_bytes < N; out_stride_bytes < N with d_frames_out
+ *   set; h_escapes[b] > h_counts[b]; h_counts[b] > N; d_cwire (arrays form: d_offsets or d_xs) not 4-byte aligned; any
+ *   overlap between two of the states' region [d_states, d_states + (nstreams-1)*stride_bytes + N), the output frames
+ *   [d_frames_out, d_frames_out + (nstreams*nframes-1)*out_stride_bytes + N) and -- wire and compact forms -- the input span
+ *   known from the host's headers.  nstreams*nframes == 0 does nothing and returns MI355_OK.
+ * Ordering is that of mi355_apply_multi_*: asynchronous on the core's stream, behind the last expansion of this core, so
+ * mi355_diff_multi_stream_cwire_batch followed by this call on one core needs no synchronisation; every later entry point
+ * of the core that reads the states or the output frames finds them complete; with a caller's stream everything runs on it
+ * in call order.  Nothing is allocated inside the call.
+ * The compact form runs the directory kernels of mi355_apply_cwire_batch on the nstreams*nframes records and then ONE
+ * kernel on a grid of 4096-byte tiles x streams: a wave finds the records of its stream that have an entry in its tile
+ * (one lane per record, one ballot per 64 records) before a state byte is touched; with no output frames a tile that no
+ * record lands in is neither read nor written; the others are loaded once, the records that touch them are applied in
+ * order in LDS, and the tile is stored back once, non-temporal.  State traffic per touched tile is 2 * 4096 bytes per
+ * CALL, not per tick, plus nframes * 4096 written when frames go out.  Six launches and one more per 128 records.
+ * The arrays and wire forms are not tuned: records of one stream may hit the same byte, so they issue one launch per t
+ * (the wire form one per 128 streams and t), each followed by a copy kernel when frames go out.
+ * Measured once on one MI355X (profiles/multi_stream_client.json: 1080p, compact form, microseconds per record, median of five
+ * rounds whose spread -- max minus min over the median -- is at most 4.0 % for this call, 1.3 % for the ticks and 7.6 % for the
+ * cores; without / with output frames, and in brackets T calls of mi355_apply_multi_cwire_batch on records re-staged
+ * beforehand / S client cores with mi355_apply_cwire_batch(T) each, both without frames, same run, same board).
+ * Webcam-like input, every tile touched by every record: S = 4: T = 4 2.628 / 3.212 (7.299 / 5.339), T = 16 1.28 / 1.841
+ * (7.344 / 1.891), T = 64 0.989 / 1.582 (7.529 / 1.37); S = 16: T = 4 1.549 / 2.309 (3.521 / 5.056), T = 16 1.021 / 1.737
+ * (3.573 / 1.494), T = 64 0.987 / 1.965 (3.688 / 1.205).
+ * Local input (a block moving on a still background, 367 of 1519 tiles touched): S = 4: T = 4 3.118 / 3.935 (10.55 / 6.081),
+ * T = 16 1.127 / 2.068 (10.612 / 2.316), T = 64 0.703 / 1.643 (10.757 / 1.391); S = 16: T = 4 1.083 / 2.001 (3.108 / 5.055),
+ * T = 16 0.427 / 1.473 (3.127 / 1.631), T = 64 0.453 / 1.423 (3.174 / 1.06).
+ * Without frames the call is ahead of the pre-staged ticks and of the S cores by more than the spread at every point on both
+ * inputs; with frames it is still ahead of the ticks everywhere, but behind S cores that write none at T = 64 (and at S = 16,
+ * T = 16 on the webcam-like input).  The time does not fall T-fold as the state traffic does: the records are still read
+ * twice and decoded once each.  DESIGN.md section 4, "The receiving end of a burst". */
+int mi355_apply_multi_stream_batch(mi355_core *core, const void *d_offsets, const void *d_xs, const void *d_diff,
+                                   int nstreams, int nframes, void *d_states, size_t stride_bytes,
+                                   void *d_frames_out, size_t out_stride_bytes);
+int mi355_apply_multi_stream_wire_batch(mi355_core *core, const void *d_wire, const uint32_t *h_counts,
+                                        int nstreams, int nframes, void *d_states, size_t stride_bytes,
+                                        void *d_frames_out, size_t out_stride_bytes);
+int mi355_apply_multi_stream_cwire_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts,
+                                         const uint32_t *h_escapes, int nstreams, int nframes, void *d_states,
+                                         size_t stride_bytes, void *d_frames_out, size_t out_stride_bytes);
 
 /* The client's side, client/opencv.cpp:50-66: for every frame in order, state[xs[i]] += diff[i] (uint8
  * wrap-around) on the core's state (a client core is a core whose state was set to the received base frame,

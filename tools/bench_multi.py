@@ -42,6 +42,19 @@ and so on, so that every step of every window is the step between two neighbouri
 max_batch * N < 2^32 bytes per call (682 frames of 1080p): where S * T is more, burst_cwire makes the fewest calls that fit,
 each with as many whole streams as it can hold (`calls_per_burst` in the line).
 
+The burst-client leg (--legs burst_client, a run of its own: `--legs burst_client --streams 4,16 --frames 4,16,64` is how
+profiles/multi_stream_client.json was taken) measures the receiving end of such bursts, in microseconds per record, ONE JSON
+line for all (S, T) and both inputs, the ways a receiver can apply the S * T compact records of a burst:
+  burst_apply         mi355_apply_multi_stream_cwire_batch without output frames: one call, straight from the stream-major records;
+  burst_apply_frames  the same with every frame in between written out;
+  multi_ticks         T calls of mi355_apply_multi_cwire_batch on records re-staged tick-major BEFOREHAND (the staging is not
+                      timed, which flatters this baseline);
+  cores_client        S client cores, each mi355_apply_cwire_batch(T) on its camera's slice.
+Inputs: `webcam`, the burst leg's (every tile of every state is touched every tick), and `local`, a static background with
+the moving block of tools/roundtrip's make_frame without the noise (few tiles are touched).  The records are one burst of a
+server core, applied round and round: adding a record to a state is the same work whatever the state holds.  The line also
+carries the touched 4096-byte tiles per record and per stream and call, counted from the decoded indices.
+
 Input of the other legs: ONE webcam stream of S + K + 1 frames; stream s shows frame s + j at step j, so every tick of every stream is the
 step between two consecutive webcam frames, and a tick's S frames are one contiguous region.  j walks 1 .. K and back."""
 import argparse
@@ -363,6 +376,147 @@ def run_burst(W, H, S, T, rounds):
     return out
 
 
+def local_streams(S, T, W, H, dev):
+    """The local input: a static background with a block that moves 3 pixels per frame, as tools/roundtrip's make_frame
+    draws it, without the noise -> (states0 [S][n], frames [S][T][n])."""
+    n = 3 * W * H
+    i = torch.arange(n, device=dev, dtype=torch.int64)
+    bw, bh, y0 = W // 4 + 1, H // 4 + 1, H // 3
+    colour = torch.tensor([200, 210, 220], dtype=torch.uint8, device=dev)
+    frames = torch.empty(S, T + 1, n, dtype=torch.uint8, device=dev)
+    for s in range(S):
+        base = (40 + (i * 7 + s * 31) % 150).to(torch.uint8)
+        for t in range(T + 1):
+            f = frames[s, t]
+            f.copy_(base)
+            x0 = ((t + 5 * s) * 3) % (W - bw + 1)
+            f.view(H, W, 3)[y0:y0 + bh, x0:x0 + bw] = colour
+    return frames[:, 0].contiguous(), frames[:, 1:].contiguous()
+
+
+def run_burst_client(W, H, S, T, rounds, kind):
+    """The burst-client leg for one (S, T) and one input -> its dictionary."""
+    import numpy as np
+    from cudavideostream_amd import CUDACore, cwire_bytes_max
+    dev = torch.device("cuda", 0)
+    n, B = 3 * W * H, S * T
+    ntiles = (n + 4095) // 4096
+    passes = 2 * max(1, 1024 // B)                     # ~2 k records per timed window
+    if kind == "webcam":                                # run_burst's input: one stream cut into S pieces
+        _, web = synth.webcam_stream(B + 1, W, H, device=dev)
+        web = web.reshape(B + 1, n)
+        states0, fwd = web[0:B:T].clone(), web[1:].reshape(S, T, n)
+    else:
+        states0, fwd = local_streams(S, T, W, H, dev)
+    per_call = min(S, max(1, ((1 << 32) - 1) // n // T))             # whole streams per call: max_batch * N < 2^32
+    chunks = [(s0, min(per_call, S - s0)) for s0 in range(0, S, per_call)]
+    # ---- the records, as a sender's mi355_diff_multi_stream_cwire_batch makes them: per chunk (records, counts, escapes, positions)
+    recs = []
+    srv_states = states0.clone()
+    with CUDACore(W, H, max_batch=per_call * T) as server:
+        for s0, ns in chunks:
+            nb = ns * T
+            cwcap = cwire_bytes_max(n, nb)
+            d_off = torch.zeros(nb + 1, dtype=torch.int32, device=dev)
+            d_pos = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
+            d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()
+            server.diff_multi_stream_cwire_batch(fwd[s0], srv_states[s0], ns, T, d_off, d_pos, d_cw, cwcap)
+            server.synchronize()
+            pos = d_pos.cpu().numpy().astype(np.int64)
+            counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
+            pad = (counts.astype(np.int64) + 3) & ~3
+            escapes = ((np.diff(pos) - 8 - 2 * pad) // 4).astype(np.uint32)
+            recs.append((d_cw[:int(pos[nb])].clone(), counts, escapes, pos))
+            del d_cw
+    # re-staged tick-major for baseline (3): tick t = record (s, t) of every s back to back
+    flat = [(recs[c][0], recs[c][3], j * T, recs[c][1], recs[c][2]) for c, (s0, ns) in enumerate(chunks) for j in range(ns)]
+    staged = []
+    for t in range(T):
+        parts = [r[int(p[b0 + t]):int(p[b0 + t + 1])] for r, p, b0, _, _ in flat]
+        staged.append((torch.cat(parts), np.array([c[b0 + t] for _, _, b0, c, _ in flat], np.uint32),
+                       np.array([e[b0 + t] for _, _, b0, _, e in flat], np.uint32)))
+    # camera s's slice for baseline (4)
+    own = [(r[int(p[b0]):int(p[b0 + T])], c[b0:b0 + T], e[b0:b0 + T]) for r, p, b0, c, e in flat]
+    states = states0.clone()
+    d_out = torch.empty(B, n, dtype=torch.uint8, device=dev)
+    client = CUDACore(W, H, max_batch=per_call * T)
+    ticks = CUDACore(W, H, max_batch=S)
+    cores = [CUDACore(W, H, max_batch=T) for _ in range(S)]
+    host0 = states0.cpu().numpy()
+    # touched tiles, from the decoded indices: per record, and per stream and call (what the new call loads and stores)
+    entries = sum(int(r[1].sum()) for r in recs)
+    tiles_rec = tiles_call = 0
+    for (s0, ns), r in zip(chunks, recs):
+        tot, nb = int(r[1].sum()), ns * T
+        d_off = torch.zeros(nb + 1, dtype=torch.int32, device=dev)
+        d_xs = torch.empty(tot + 16, dtype=torch.int32, device=dev)
+        d_df = torch.empty(tot + 16, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        client.cwire_decode_batch(r[0], r[1], r[2], nb, d_off, d_xs, d_df, tot + 16)
+        client.synchronize()
+        b = torch.repeat_interleave(torch.arange(nb, device=dev), torch.from_numpy(r[1].astype(np.int64)).to(dev))
+        tile = d_xs[:tot].to(torch.int64) // 4096
+        tiles_rec += int(torch.unique(b * ntiles + tile).numel())
+        tiles_call += int(torch.unique((b // T) * ntiles + tile).numel())
+        del d_xs, d_df, b, tile
+    torch.cuda.synchronize()
+
+    def leg_burst(out):
+        for _ in range(passes):
+            for (s0, ns), r in zip(chunks, recs):
+                client.apply_multi_stream_cwire_batch(r[0], r[1], r[2], ns, T, states[s0], d_frames_out=out[s0 * T] if out is not None else None)
+        client.synchronize()
+
+    def leg_ticks():
+        for _ in range(passes):
+            for r, c, e in staged:
+                ticks.apply_multi_cwire_batch(r, c, e, S, states)
+        ticks.synchronize()
+
+    def leg_cores():
+        for _ in range(passes):
+            for s, c in enumerate(cores):
+                c.apply_cwire_batch(own[s][0], own[s][1], own[s][2], T)
+        for c in cores:
+            c.synchronize()
+
+    table = {"burst_apply": lambda: leg_burst(None), "burst_apply_frames": lambda: leg_burst(d_out), "multi_ticks": leg_ticks,
+             "cores_client": leg_cores}
+    times = {}
+    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
+        for name, leg in table.items():
+            states.copy_(states0)
+            if name == "cores_client":
+                for s, c in enumerate(cores):
+                    c.set_state(host0[s])
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            leg()
+            dt = time.perf_counter() - t0
+            if r:
+                times.setdefault(name, []).append(dt * 1e6 / (passes * B))
+    # one burst from the base states is what the sender's states became, by every way
+    states.copy_(states0)
+    torch.cuda.synchronize()
+    for (s0, ns), r in zip(chunks, recs):
+        client.apply_multi_stream_cwire_batch(r[0], r[1], r[2], ns, T, states[s0], d_frames_out=d_out[s0 * T])
+    client.synchronize()
+    assert torch.equal(states, srv_states) and torch.equal(d_out[T - 1::T], srv_states)
+    out = {"input": kind, "streams": S, "frames": T, "passes": passes, "calls_per_burst": len(chunks),
+           "changed_bytes_per_record": round(entries / B, 1), "record_bytes_per_record": round(sum(int(r[3][-1]) for r in recs) / B, 1),
+           "tiles_per_state": ntiles, "touched_tiles_per_record": round(tiles_rec / B, 1),
+           "touched_tiles_per_stream_and_call": round(tiles_call / S, 1)}
+    for name in table:
+        out[name + "_us_per_record"] = stats(times[name])
+    med = {k: statistics.median(v) for k, v in times.items()}
+    out["multi_ticks_over_burst_apply"] = round(med["multi_ticks"] / med["burst_apply"], 3)
+    out["cores_client_over_burst_apply"] = round(med["cores_client"] / med["burst_apply"], 3)
+    for c in [client, ticks] + cores:
+        c.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", default="1920x1080")
@@ -370,8 +524,8 @@ def main():
     ap.add_argument("--steps", type=int, default=8, help="K: webcam frames a stream walks through")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--legs", default="multi,cores_loop,pairs",
-                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone")
-    ap.add_argument("--frames", default="4,16,64", help="burst leg: T, frames per stream and call")
+                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone")
+    ap.add_argument("--frames", default="4,16,64", help="burst and burst_client legs: T, frames per stream and call")
     a = ap.parse_args()
     have = load_library()
     W, H = (int(v) for v in a.size.split("x"))
@@ -391,6 +545,15 @@ def main():
                 torch.cuda.empty_cache()
         print(json.dumps({"bench": "multi_stream", "size": f"{W}x{H}", "input": "synth.webcam_stream", "rounds": a.rounds,
                           "burst": per}), flush=True)
+        return
+    if a.legs == "burst_client":
+        per = []
+        for S in (int(v) for v in a.streams.split(",")):
+            for T in (int(v) for v in a.frames.split(",")):
+                for kind in ("webcam", "local"):
+                    per.append(run_burst_client(W, H, S, T, a.rounds, kind))
+                    torch.cuda.empty_cache()
+        print(json.dumps({"bench": "multi_stream_client", "size": f"{W}x{H}", "rounds": a.rounds, "burst_client": per}), flush=True)
         return
     for S in (int(v) for v in a.streams.split(",")):
         run(W, H, S, a.steps, a.rounds, set(a.legs.split(",")), have)
