@@ -71,6 +71,13 @@ public:
     // nstreams*nframes <= MI355_MAX_BATCH.
     void apply_multi_stream(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, int nstreams, int nframes,
                             void *d_states, size_t stride, void *d_frames_out, size_t out_stride);
+    // A relay between the two (include/mi355diff.h, mi355_cwire_coalesce_cwire_batch): the nframes records of camera s, laid
+    // out and described as for apply_multi_stream, become ONE record per camera -- the sum of the burst's differences per byte,
+    // bytes that went back to where they were dropped -- at d_cwire_out + d_frame_pos[s] (uint64[nstreams + 1]), entry counts
+    // scanned in d_offsets (uint32[nstreams + 1]); all in DEVICE memory.  No state is involved.  Blocking, like
+    // apply_multi_stream; nstreams*nframes <= MI355_MAX_BATCH.
+    void coalesce_multi_stream(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, int nstreams, int nframes,
+                               void *d_offsets, void *d_frame_pos, void *d_cwire_out, size_t capacity_bytes);
 };
 
 static_assert(sizeof(CUDACore) == 160, "must match the reference's object size (LP64)");

@@ -117,6 +117,13 @@ void CUDACore::apply_multi_stream(const void *d_cwire, const uint32_t *counts, c
     MI355_CHECK(mi355_synchronize(core_));
 }
 
+void CUDACore::coalesce_multi_stream(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, int nstreams, int nframes,
+                                     void *d_offsets, void *d_frame_pos, void *d_cwire_out, size_t capacity_bytes) {
+    MI355_CHECK(mi355_cwire_coalesce_cwire_batch(core_, d_cwire, counts, escapes, nstreams, nframes, d_offsets, d_frame_pos,
+                                                 d_cwire_out, capacity_bytes));
+    MI355_CHECK(mi355_synchronize(core_));
+}
+
 size_t CUDACore::chunkt_size() { return 32; }  // sizeof(long4), kernels.cu:27,527-529
 
 void CUDACore::alloc_arrays(uint8_t **h_frame, uint8_t **n_frame, uint8_t **o_frame, int **h_xs, int r,

@@ -371,6 +371,31 @@ class CUDACore:
                                                                 int(nstreams), int(nframes), _ptr(d_states), int(stride),
                                                                 _ptr(d_frames_out), int(out_stride)))
 
+    # ... and a relay between the two: a burst of records per stream -> one record per stream, no state involved
+    def cwire_coalesce_batch(self, d_cwire, counts, escapes, nstreams, nframes, d_offsets, d_xs, d_diff, capacity):
+        """nframes compact records of each of nstreams streams (s * nframes + t order, headers counts / escapes) -> segment s
+        of (d_offsets, d_xs, d_diff): the sums (mod 256) of the stream's differences per byte index that are not 0, ascending.
+        Applying segment s equals applying the stream's records in order."""
+        self._hold(d_cwire, d_offsets, d_xs, d_diff)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+        assert counts.size >= nstreams * nframes and escapes.size >= nstreams * nframes
+        _l.check(self._lib.mi355_cwire_coalesce_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
+                                                      int(nstreams), int(nframes), _ptr(d_offsets), _ptr(d_xs), _ptr(d_diff),
+                                                      int(capacity)))
+
+    def cwire_coalesce_cwire_batch(self, d_cwire, counts, escapes, nstreams, nframes, d_offsets, d_frame_pos, d_cwire_out,
+                                   capacity_bytes):
+        """cwire_coalesce_batch into compact records: stream s's ONE record at d_frame_pos[s] (uint64[nstreams + 1]), the
+        canonical encoding of its segment."""
+        self._hold(d_cwire, d_offsets, d_frame_pos, d_cwire_out)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+        assert counts.size >= nstreams * nframes and escapes.size >= nstreams * nframes
+        _l.check(self._lib.mi355_cwire_coalesce_cwire_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
+                                                            int(nstreams), int(nframes), _ptr(d_offsets), _ptr(d_frame_pos),
+                                                            _ptr(d_cwire_out), int(capacity_bytes)))
+
     def wire_bytes(self, nframes, entries):
         return self._lib.mi355_wire_bytes(nframes, entries)
 

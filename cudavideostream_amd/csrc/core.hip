@@ -1350,6 +1350,88 @@ int mi355_apply_multi_stream_cwire_batch(mi355_core *c, const void *d_cwire, con
     return MI355_OK;
 }
 
+// ---- mi355_cwire_coalesce_(cwire_)batch: nframes records of each of nstreams streams -> ONE segment / record per stream -------
+// Both forms: everything is refused here, before anything is launched; the core's state is not touched.
+namespace {
+struct CoalesceRegion {
+    const void *p;
+    uint64_t bytes;
+    const char *what;
+};
+}  // namespace
+
+static int coalesce(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams,
+                    int nframes, bool cwire, void *d_offsets, void *d_frame_pos, void *d_cwire_out, void *d_xs, void *d_diff,
+                    size_t capacity) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nstreams < 0 || nframes < 0) return fail(MI355_ERR_INVALID, "nstreams or nframes < 0");
+    const int64_t B64 = (int64_t)nstreams * nframes;
+    if (B64 > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams * nframes above max_batch");
+    const int B = (int)B64;
+    if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_cwire_out & 3u) || ((uintptr_t)d_xs & 3u))
+        return fail(MI355_ERR_INVALID, "d_cwire, d_cwire_out, d_offsets and d_xs must be 4-byte aligned");
+    if ((uintptr_t)d_frame_pos & 7u) return fail(MI355_ERR_INVALID, "d_frame_pos must be 8-byte aligned");
+    if (B == 0) {   // offsets[0] = 0 (and frame_pos[0] = 0) and nothing else
+        if (!d_offsets && !d_frame_pos) return MI355_OK;
+        if (int rc = use_device(c)) return rc;
+        if (d_offsets) HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(uint32_t), c->stream));
+        if (d_frame_pos) HIP_TRY(hipMemsetAsync(d_frame_pos, 0, sizeof(uint64_t), c->stream));
+        return MI355_OK;
+    }
+    if (!d_cwire || !h_counts || !h_escapes) return fail(MI355_ERR_INVALID, "null stream pointer");
+    if (!d_offsets || (cwire ? !d_frame_pos || !d_cwire_out : !d_xs || !d_diff)) return fail(MI355_ERR_INVALID, "null output pointer");
+    CwireHeaders hdr{h_counts, h_escapes, B};
+    if (int rc = hdr.check(true, c->n)) return rc;
+    std::vector<CwaFrame> fr((size_t)B);   // B <= max_batch: the scratch of the one-stream client holds them
+    uint32_t cbase = 0;
+    for (int b = 0; b < B; b++) {
+        const CwireHeaders::Frame f = hdr.next();
+        fr[b] = CwaFrame{f.pos, f.n, f.e, cbase, cwa_chunks(f.n)};
+        cbase += fr[b].nc;
+    }
+    const CoalesceRegion out[] = {
+        {d_offsets, ((uint64_t)nstreams + 1) * sizeof(uint32_t), "d_offsets overlaps the input stream"},
+        {cwire ? d_frame_pos : nullptr, ((uint64_t)nstreams + 1) * sizeof(uint64_t), "d_frame_pos overlaps the input stream"},
+        {cwire ? d_cwire_out : nullptr, capacity, "d_cwire_out overlaps the input stream"},
+        {cwire ? nullptr : d_xs, 4 * (uint64_t)capacity, "d_xs overlaps the input stream"},
+        {cwire ? nullptr : d_diff, capacity, "d_diff overlaps the input stream"},
+    };
+    const uintptr_t in = (uintptr_t)d_cwire;
+    for (const CoalesceRegion &r : out) {
+        const uintptr_t o = (uintptr_t)r.p;
+        if (r.p && in < o + (uintptr_t)r.bytes && o < in + (uintptr_t)hdr.pos) return fail(MI355_ERR_INVALID, r.what);
+    }
+    if (int rc = use_device(c)) return rc;
+    CwaArgs a{};
+    a.cwire = (const uint8_t *)d_cwire;
+    a.ftab = c->cwa_ftab;
+    a.chunk = c->cwa_chunk;   // chunk facts for the directory, then one fact word per (stream, tile): nstreams <= max_batch
+    a.dir = c->cwa_dir;
+    a.n = c->n;
+    a.ntiles = cwa_tiles(c->n);
+    CwcOut o{};
+    o.offsets = (uint32_t *)d_offsets;
+    o.frame_pos = (uint64_t *)d_frame_pos;
+    o.cwire = (uint8_t *)d_cwire_out;
+    o.xs = (int32_t *)d_xs;
+    o.diff = (uint8_t *)d_diff;
+    o.capacity = capacity;
+    HIP_TRY(launch_cwire_coalesce(a, fr.data(), nstreams, nframes, o, cwire, c->stream));
+    return MI355_OK;
+}
+
+int mi355_cwire_coalesce_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
+                               int nstreams, int nframes, void *d_offsets, void *d_xs, void *d_diff, size_t capacity) {
+    return coalesce(c, d_cwire, h_counts, h_escapes, nstreams, nframes, false, d_offsets, nullptr, nullptr, d_xs, d_diff, capacity);
+}
+
+int mi355_cwire_coalesce_cwire_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
+                                     int nstreams, int nframes, void *d_offsets, void *d_frame_pos, void *d_cwire_out,
+                                     size_t capacity_bytes) {
+    return coalesce(c, d_cwire, h_counts, h_escapes, nstreams, nframes, true, d_offsets, d_frame_pos, d_cwire_out, nullptr, nullptr,
+                    capacity_bytes);
+}
+
 // client/opencv.cpp:50-66 on the compact stream, on the host.  A frame is validated whole before any byte of the state
 // changes, so a malformed frame leaves the state as the frames before it made it.
 int mi355_cwire_apply_host(uint8_t *state, size_t frame_bytes, const void *cwire, size_t cwire_bytes, int nframes,

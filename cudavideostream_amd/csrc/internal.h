@@ -194,6 +194,18 @@ hipError_t launch_cwire_apply_multi(const CwaArgs &a, const CwaFrame *records, i
 // after record b = s*nframes + t also to a.out + b*out_stride (a.stride is the states')
 hipError_t launch_cwire_apply_multi_stream(const CwaArgs &a, const CwaFrame *records, int nstreams, int nframes, size_t out_stride,
                                            hipStream_t s);
+// mi355_cwire_coalesce_(cwire_)batch: records s*nframes + t of each stream summed (mod 256) into ONE record / segment per stream;
+// a.state / a.out / a.stride unused, a.chunk doubles as the per-(stream, tile) facts once the directory is made
+struct CwcOut {
+    uint32_t *offsets;     // [nstreams + 1]
+    uint64_t *frame_pos;   // [nstreams + 1], compact form
+    uint8_t *cwire;        // compact form: the records
+    int32_t *xs;           // arrays form
+    uint8_t *diff;
+    uint64_t capacity;     // bytes of cwire, or entries of xs / diff
+};
+hipError_t launch_cwire_coalesce(const CwaArgs &a, const CwaFrame *records, int nstreams, int nframes, const CwcOut &o, bool cwire,
+                                 hipStream_t s);
 
 // filters.hip -- every per-frame kernel takes a FrameBatch: frame f lives at base + f*stride
 struct FrameBatch {

@@ -10,7 +10,9 @@
 //   k_cwire_*             : the compact wire format's encoder (packed stream -> gap-coded records) and decoder;
 //   k_cwa_*               : the compact records applied straight to a client core's state (mi355_apply_cwire_batch) or,
 //                           one record per stream, to the caller's states (mi355_apply_multi_cwire_batch), or a burst of
-//                           records per stream, with the frames in between (mi355_apply_multi_stream_cwire_batch).
+//                           records per stream, with the frames in between (mi355_apply_multi_stream_cwire_batch);
+//   k_cwc_*               : a burst of compact records per stream summed into ONE record / segment per stream, from the records
+//                           alone (mi355_cwire_coalesce_batch / _cwire_batch).
 //
 // The first two are index-driven byte scatter/copy: HBM-latency work with 5 bytes of traffic per entry, no
 // arithmetic worth naming.
@@ -884,6 +886,304 @@ __global__ __launch_bounds__(64) void k_cwa_apply_multi_stream(const CwaArgs a, 
     if (dirty) cwa_tile_store(tile_bytes, s, len, lane);
 }
 
+// ---- mi355_cwire_coalesce_(cwire_)batch: records s*nframes .. (s + 1)*nframes - 1 -> ONE record / segment per stream ---------
+// The sum (mod 256) of a stream's differences at every byte index, the indices whose sum is not 0 in ascending order.  Nothing
+// but the records is read: the tile machinery above applied to a ZEROED tile in LDS gives the sums, and the tile is encoded
+// from LDS.  Behind the directory of the nstreams*nframes records:
+//   k_cwc_sum   (grid: tiles x streams, one wave) : the summed tile -> one fact word per (stream, tile) in the chunk scratch
+//                                                   (free once k_cwa_dir has run: the tile kernels read ftab and dir only):
+//                                                   {nonzero bytes, index of the first, index of the last, gaps >= 255
+//                                                   between consecutive nonzero bytes inside the tile}; a tile no record
+//                                                   lands in writes an all-zero word (the scratch holds stale data) and returns
+//   k_cwc_scan  (grid: streams)                   : over the stream's tiles: fact word -> {nonzero bytes, entries before the
+//                                                   tile, escapes before it, 1 + the last index before it (0: none)}; the
+//                                                   stream's n to offsets[s + 1], its e to frame_pos[s + 1] (unscanned)
+//   k_cwc_place (one workgroup)                   : offsets, frame_pos scanned in place; the records' headers and pad bytes
+//   k_cwc_emit  (grid: tiles x streams, one wave) : a tile with no nonzero byte returns before it touches anything; the others
+//                                                   build the summed tile again (record bytes, not N) and write their entries
+// A lane owns 64 consecutive bytes of the tile: only its first nonzero byte can be an escape (the others' gaps are below 64).
+// No workgroup waits on another.  The entries of a tile are compacted in LDS at the alignment of their place in the output and
+// stored as dwords inside, bytes at the ragged edges: neighbouring workgroups share dwords of the code and diff sections and
+// never read-modify-write one.  Malformed content: both tile kernels compute the same tile from the same bytes, so the facts
+// and the record agree whatever the records held.
+// The stream's summed tile [lo, hi) in LDS (s: kCwaTile bytes; s[0] is byte lo); false: no record has an entry in the tile
+// and s was not touched.  The ballot passes and the walk of k_cwa_apply_multi_stream without a state and output frames.
+__device__ __forceinline__ bool cwc_sum_tile(uint8_t *s, const CwaArgs &a, int nframes, uint32_t st, uint32_t tile, uint32_t lo,
+                                             uint32_t hi, int lane) {
+    const size_t b0 = (size_t)st * nframes;   // the stream's first batch index
+    bool any = false;
+    for (int base = 0; base < nframes; base += 64) {
+        bool touch = false;
+        if (base + lane < nframes) {
+            const size_t b = b0 + base + lane;
+            const uint32_t fn = a.ftab[b].n;
+            const uint4 *dir = a.dir + b * a.ntiles + tile;
+            const uint32_t k0 = dir[0].x, kend = tile + 1 < a.ntiles ? dir[1].x : fn;
+            touch = k0 < kend && k0 < fn;
+        }
+        const uint64_t set = __ballot(touch);
+        if (!set) continue;
+        if (!any) {
+            for (uint32_t i = lane; i < kCwaTile / 16; i += 64) ((cwa_u32x4 *)s)[i] = cwa_u32x4{0u, 0u, 0u, 0u};
+            any = true;
+        }
+        const int cnt = nframes - base < 64 ? nframes - base : 64;
+        // while record j is applied, the header, directory word and first block of the set's next record are in flight
+        int jn = __ffsll((unsigned long long)set) - 1;
+        CwaFrame f1 = a.ftab[b0 + base + jn];
+        uint4 d1 = a.dir[(b0 + base + jn) * a.ntiles + tile];
+        CwaBlock b1 = cwa_block_load(a, f1, d1.x, lane);
+        __syncthreads();
+        while (jn < cnt) {
+            const int j = jn;
+            const CwaFrame f = f1;
+            const uint4 dr = d1;
+            const CwaBlock b = b1;
+            const uint64_t rest = set & ~((2ull << j) - 1ull);   // (j = 63: 2 << 63 is 0, rest = 0)
+            jn = rest ? __ffsll((unsigned long long)rest) - 1 : cnt;
+            if (jn < cnt) {
+                f1 = a.ftab[b0 + base + jn];
+                d1 = a.dir[(b0 + base + jn) * a.ntiles + tile];
+                b1 = cwa_block_load(a, f1, d1.x, lane);
+            }
+            cwa_apply_record(s, a, f, dr, b, lo, hi, lane);
+            __syncthreads();
+        }
+    }
+    return any;
+}
+
+// What a lane's 64 bytes of the summed tile hold: bit i of the mask = byte 64*lane + i is not 0
+__device__ __forceinline__ uint64_t cwc_lane_mask(const uint8_t *s, int lane) {
+    const uint32_t *w = (const uint32_t *)s + 16 * lane;
+    uint64_t m = 0;
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const uint32_t v = w[i];
+        const uint32_t nz = ((v & 0xffu) ? 1u : 0u) | ((v & 0xff00u) ? 2u : 0u) | ((v & 0xff0000u) ? 4u : 0u) | ((v & 0xff000000u) ? 8u : 0u);
+        m |= (uint64_t)nz << (4 * i);
+    }
+    return m;
+}
+
+// 1 + the tile-relative position of the last nonzero byte of the lanes below this one that hold any (0: none does);
+// lanes: the ballot of the lanes that hold one
+__device__ __forceinline__ uint32_t cwc_end_before(uint64_t m, uint64_t lanes, int lane) {
+    const uint32_t my_end = m ? 64u * lane + 64u - (uint32_t)__builtin_clzll(m) : 0u;
+    const uint64_t below = lanes & ((1ull << lane) - 1ull);
+    const int src = below ? 63 - __builtin_clzll(below) : 0;
+    const uint32_t end = (uint32_t)__shfl((int)my_end, src, 64);
+    return below ? end : 0u;
+}
+
+__global__ __launch_bounds__(64) void k_cwc_sum(const CwaArgs a, int nframes) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
+    uint8_t *s = (uint8_t *)s_q;
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    uint4 *fact = a.chunk + (size_t)st * a.ntiles + tile;
+    if (!cwc_sum_tile(s, a, nframes, st, tile, lo, lo + len, lane)) {
+        if (lane == 0) *fact = make_uint4(0u, 0u, 0u, 0u);
+        return;
+    }
+    const uint64_t m = cwc_lane_mask(s, lane);
+    const uint64_t lanes = __ballot(m != 0);
+    const uint32_t count = cwa_wave_sum((uint32_t)__popcll(m));
+    const uint32_t end = cwc_end_before(m, lanes, lane);
+    // the gap in front of a lane's first nonzero byte, where a lane below holds one (the tile's first has no gap inside the tile)
+    const bool wide = m && end && 64u * lane + (uint32_t)__builtin_ctzll(m) - end >= 255u;
+    const uint32_t gaps = (uint32_t)__popcll(__ballot(wide));
+    uint32_t first = 0, last = 0;
+    if (lanes) {
+        const int l0 = __ffsll((unsigned long long)lanes) - 1, l1 = 63 - __builtin_clzll(lanes);
+        const uint32_t my_first = m ? 64u * lane + (uint32_t)__builtin_ctzll(m) : 0u;
+        const uint32_t my_last = m ? 64u * lane + 63u - (uint32_t)__builtin_clzll(m) : 0u;
+        first = lo + (uint32_t)__shfl((int)my_first, l0, 64);
+        last = lo + (uint32_t)__shfl((int)my_last, l1, 64);
+    }
+    if (lane == 0) *fact = make_uint4(count, first, last, gaps);
+}
+
+// carry = max(carry, every value); returns the max of carry and the values of the threads below this one.  One barrier
+// (none for a single wave); s_wave as block_waves_before.
+template <int NW>
+__device__ __forceinline__ uint32_t cwc_block_exclusive_max(uint32_t v, uint32_t *s_wave, uint32_t &carry) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t incl = v;
+#pragma unroll
+    for (int k = 1; k < 64; k <<= 1) {
+        const uint32_t u = (uint32_t)__shfl_up((int)incl, k, 64);
+        if (lane >= k && u > incl) incl = u;
+    }
+    uint32_t before = (uint32_t)__shfl_up((int)incl, 1, 64);
+    if (lane == 0) before = 0;
+    if (before < carry) before = carry;
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    for (int w = 0; w < NW; w++) {
+        const uint32_t u = s_wave[w];
+        if (w < wave && u > before) before = u;
+        if (u > carry) carry = u;
+    }
+    return before;
+}
+
+template <bool CWIRE>
+__global__ __launch_bounds__(256) void k_cwc_scan(const CwaArgs a, const CwcOut o) {
+    __shared__ uint32_t s_n[2][4], s_e[2][4], s_end[2][4];
+    const uint32_t st = blockIdx.x;
+    uint4 *facts = a.chunk + (size_t)st * a.ntiles;
+    uint32_t n = 0, e = 0, end = 0;   // entries, escapes and 1 + the last index of the tiles before the round
+    int buf = 0;
+    for (uint32_t i0 = 0; i0 < a.ntiles; i0 += 256, buf ^= 1) {
+        const uint32_t i = i0 + threadIdx.x;
+        const uint4 f = i < a.ntiles ? facts[i] : make_uint4(0u, 0u, 0u, 0u);
+        const uint32_t nbefore = block_exclusive_scan<4>(f.x, s_n[buf], n);
+        const uint32_t prev_end = cwc_block_exclusive_max<4>(f.x ? f.z + 1u : 0u, s_end[buf], end);
+        // the tile's first entry: g_0 = xs[0] for the stream's first, else the gap across the tile edge (and any empty tiles)
+        const uint32_t esc = f.x ? f.w + (f.y - prev_end >= 255u ? 1u : 0u) : 0u;
+        const uint32_t ebefore = block_exclusive_scan<4>(esc, s_e[buf], e);
+        if (i < a.ntiles) facts[i] = make_uint4(f.x, nbefore, ebefore, prev_end);
+    }
+    if (threadIdx.x == 0) {
+        o.offsets[st + 1] = n;
+        if (CWIRE) o.frame_pos[st + 1] = e;
+    }
+}
+
+constexpr int kCwcPlaceThreads = 1024;
+
+// offsets[s + 1] = n_s, frame_pos[s + 1] = e_s -> the exclusive scans, in place (a thread reads its stream's two words before
+// the round's barrier and writes behind it); compact form: header and zero pad bytes of every record that fits
+template <bool CWIRE>
+__global__ __launch_bounds__(kCwcPlaceThreads) void k_cwc_place(const CwcOut o, int nstreams) {
+    __shared__ uint32_t s_n[kCwcPlaceThreads / 64];
+    __shared__ uint64_t s_pos[kCwcPlaceThreads / 64];
+    const int tid = threadIdx.x;
+    uint32_t first = 0;
+    uint64_t pos = 0;
+    for (int s0 = 0; s0 < nstreams; s0 += kCwcPlaceThreads) {
+        const int s = s0 + tid;
+        const bool live = s < nstreams;
+        const uint32_t n = live ? o.offsets[s + 1] : 0u;
+        const uint32_t e = live && CWIRE ? (uint32_t)o.frame_pos[s + 1] : 0u;
+        const uint64_t rec = live && CWIRE ? cwire_record_bytes(n, e) : 0;
+        const uint32_t my_first = block_exclusive_scan<kCwcPlaceThreads / 64>(n, s_n, first);
+        uint64_t my_pos = 0;
+        if (CWIRE) my_pos = block_exclusive_scan<kCwcPlaceThreads / 64>(rec, s_pos, pos);
+        if (live) {
+            o.offsets[s] = my_first;
+            if (CWIRE) {
+                o.frame_pos[s] = my_pos;
+                if (my_pos + rec <= o.capacity) {
+                    uint32_t *hdr = (uint32_t *)(o.cwire + my_pos);
+                    hdr[0] = n;
+                    hdr[1] = e;
+                    const CwireSections<uint8_t> sec(o.cwire, my_pos, n, e);
+                    for (uint32_t k = n; k < (uint32_t)cwire_pad4(n); k++) {
+                        sec.code[k] = 0;
+                        sec.diff[k] = 0;
+                    }
+                }
+            }
+        }
+        __syncthreads();   // the scans' LDS words are rewritten by the next round
+    }
+    if (tid == 0) {
+        o.offsets[nstreams] = first;
+        if (CWIRE) o.frame_pos[nstreams] = pos;
+    }
+}
+
+// cnt bytes of LDS at s + sh -> g, where sh = g & 3: bytes up to g's first dword, whole dwords, bytes behind the last
+__device__ __forceinline__ void cwc_store_bytes(uint8_t *g, const uint8_t *s, uint32_t sh, uint32_t cnt, int lane) {
+    const uint32_t head = (4u - sh) & 3u;
+    if (cnt <= head) {
+        if ((uint32_t)lane < cnt) __builtin_nontemporal_store(s[sh + lane], g + lane);
+        return;
+    }
+    const uint32_t q = (cnt - head) / 4u, tail = head + 4u * q;
+    if ((uint32_t)lane < head) __builtin_nontemporal_store(s[sh + lane], g + lane);
+    const uint32_t *sw = (const uint32_t *)(s + sh + head);   // sh + head is 0 or 4
+    uint32_t *gw = (uint32_t *)(g + head);
+    for (uint32_t i = lane; i < q; i += 64) __builtin_nontemporal_store(sw[i], gw + i);
+    if ((uint32_t)lane < cnt - tail) __builtin_nontemporal_store(s[sh + tail + lane], g + tail + lane);
+}
+
+template <bool CWIRE>
+__global__ __launch_bounds__(64) void k_cwc_emit(const CwaArgs a, const CwcOut o, int nframes) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
+    __shared__ uint32_t s_code32[CWIRE ? kCwaTile / 4 + 2 : 1], s_diff32[kCwaTile / 4 + 2];
+    uint8_t *s = (uint8_t *)s_q, *s_code = (uint8_t *)s_code32, *s_diff = (uint8_t *)s_diff32;
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
+    const uint4 fact = a.chunk[(size_t)st * a.ntiles + tile];   // {nonzero bytes, entries before, escapes before, end before}
+    if (fact.x == 0) return;
+    const uint32_t seg = o.offsets[st], n = o.offsets[st + 1] - seg;
+    uint64_t fp0 = 0;
+    uint32_t e = 0;
+    if (CWIRE) {
+        fp0 = o.frame_pos[st];
+        const uint64_t fp1 = o.frame_pos[st + 1];
+        if (fp1 > o.capacity) return;   // the record does not fit: skipped whole, by every workgroup alike
+        e = cwire_record_escapes(fp1 - fp0, n);
+    }
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    if (!cwc_sum_tile(s, a, nframes, st, tile, lo, lo + len, lane)) return;   // (the facts say otherwise)
+    const uint64_t m = cwc_lane_mask(s, lane);
+    const uint64_t lanes = __ballot(m != 0);
+    uint32_t zero = 0;
+    const uint32_t r0 = block_exclusive_scan<1>((uint32_t)__popcll(m), (uint32_t *)nullptr, zero);   // tile-relative rank
+    const uint32_t before = cwc_end_before(m, lanes, lane);
+    uint32_t end = before ? lo + before : fact.w;   // 1 + the index of the entry before the lane's first
+    // where the tile's entries go, and the alignment of that place
+    uint8_t *g_code = nullptr, *g_diff;
+    uint32_t *g_esc = nullptr;
+    uint64_t room = fact.x;   // entries of the tile that are written
+    if (CWIRE) {
+        const CwireSections<uint8_t> sec(o.cwire, fp0, n, e);
+        g_code = sec.code + fact.y;
+        g_diff = sec.diff + fact.y;
+        g_esc = sec.esc32();
+    } else {
+        const uint64_t at = (uint64_t)seg + fact.y;
+        room = at < o.capacity ? (o.capacity - at < room ? o.capacity - at : room) : 0;
+        g_diff = o.diff + at;
+    }
+    const uint32_t sh_code = (uint32_t)((uintptr_t)g_code & 3u), sh_diff = (uint32_t)((uintptr_t)g_diff & 3u);
+    const uint32_t first_gap = m ? lo + 64u * lane + (uint32_t)__builtin_ctzll(m) - end : 0u;
+    const bool escaped = CWIRE && m && first_gap >= 255u;
+    const uint32_t erank = fact.z + (uint32_t)__popcll(__ballot(escaped) & ((1ull << lane) - 1ull));
+    if (escaped && erank < e) __builtin_nontemporal_store(first_gap, g_esc + erank);
+    uint32_t r = r0;
+    const uint32_t *w = (const uint32_t *)s + 16 * lane;
+    for (int i = 0; i < 16 && m; i++) {
+        const uint32_t v = w[i];
+        if (!v) continue;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint32_t d = (v >> (8 * j)) & 255u;
+            if (!d) continue;
+            const uint32_t x = lo + 64u * lane + 4u * i + j;
+            if (CWIRE) {
+                const uint32_t g = x - end;
+                s_code[sh_code + r] = (uint8_t)(g < 255u ? g : 255u);
+            } else if (r < room) {
+                __builtin_nontemporal_store((int32_t)x, o.xs + (uint64_t)seg + fact.y + r);
+            }
+            s_diff[sh_diff + r] = (uint8_t)d;
+            end = x + 1u;
+            r++;
+        }
+    }
+    __syncthreads();
+    if (CWIRE) cwc_store_bytes(g_code, s_code, sh_code, (uint32_t)room, lane);
+    cwc_store_bytes(g_diff, s_diff, sh_diff, (uint32_t)room, lane);
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 uint32_t cwa_chunks(uint32_t n) { return n ? (n + kCwaChunk - 1) / kCwaChunk : 1u; }
 uint32_t cwa_tiles(uint32_t nbytes) { return (nbytes + kCwaTile - 1) / kCwaTile; }
@@ -927,6 +1227,24 @@ hipError_t launch_cwire_apply_multi_stream(const CwaArgs &a, const CwaFrame *rec
     if (nstreams <= 0 || nframes <= 0 || a.ntiles == 0) return hipSuccess;
     launch_cwa_directory(a, records, nstreams * nframes, s);
     hipLaunchKernelGGL(k_cwa_apply_multi_stream, dim3(a.ntiles * (uint32_t)nstreams), dim3(64), 0, s, a, nframes, out_stride);
+    return hipGetLastError();
+}
+
+template <bool CWIRE>
+static void launch_cwc(const CwaArgs &a, const CwcOut &o, int nstreams, int nframes, hipStream_t s) {
+    const dim3 tiles(a.ntiles * (uint32_t)nstreams);
+    if (a.ntiles) hipLaunchKernelGGL(k_cwc_sum, tiles, dim3(64), 0, s, a, nframes);
+    hipLaunchKernelGGL(k_cwc_scan<CWIRE>, dim3(nstreams), dim3(256), 0, s, a, o);
+    hipLaunchKernelGGL(k_cwc_place<CWIRE>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, nstreams);
+    if (a.ntiles) hipLaunchKernelGGL(k_cwc_emit<CWIRE>, tiles, dim3(64), 0, s, a, o, nframes);
+}
+
+hipError_t launch_cwire_coalesce(const CwaArgs &a, const CwaFrame *records, int nstreams, int nframes, const CwcOut &o, bool cwire,
+                                 hipStream_t s) {
+    if (nstreams <= 0 || nframes <= 0) return hipSuccess;
+    if (a.ntiles) launch_cwa_directory(a, records, nstreams * nframes, s);
+    if (cwire) launch_cwc<true>(a, o, nstreams, nframes, s);
+    else launch_cwc<false>(a, o, nstreams, nframes, s);
     return hipGetLastError();
 }
 

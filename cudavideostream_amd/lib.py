@@ -89,6 +89,10 @@ SYMBOLS = {
                                                       C.c_size_t, C.c_void_p, C.c_size_t]),
     "mi355_apply_multi_stream_cwire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "mi355_cwire_coalesce_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mi355_cwire_coalesce_cwire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "mi355_wire_bytes": (C.c_size_t, [C.c_int, C.c_uint64]),
     "mi355_apply_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                     C.c_size_t]),

@@ -86,7 +86,7 @@ typedef struct mi355_config {
  *      + mi355_apply_multi_batch, mi355_apply_multi_wire_batch, mi355_apply_multi_cwire_batch (additions only);
  *      + mi355_diff_multi_stream_batch, mi355_diff_multi_stream_wire_batch, mi355_diff_multi_stream_cwire_batch (additions
  *      only); + mi355_apply_multi_stream_batch, mi355_apply_multi_stream_wire_batch, mi355_apply_multi_stream_cwire_batch
- *      (additions only) */
+ *      (additions only); + mi355_cwire_coalesce_batch, mi355_cwire_coalesce_cwire_batch (additions only) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -429,6 +429,52 @@ int mi355_apply_multi_stream_wire_batch(mi355_core *core, const void *d_wire, co
 int mi355_apply_multi_stream_cwire_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts,
                                          const uint32_t *h_escapes, int nstreams, int nframes, void *d_states,
                                          size_t stride_bytes, void *d_frames_out, size_t out_stride_bytes);
+
+/* A burst coalesced: nframes compact records of each of nstreams streams (batch index b = s*nframes + t, the layout of
+ * mi355_diff_multi_stream_cwire_batch's output; the headers h_counts[b] / h_escapes[b] from the host as in
+ * mi355_apply_multi_stream_cwire_batch) -> ONE segment / record per stream, the one that takes a client from the frame
+ * before the burst to the frame after it.  For a relay that is nframes ticks behind, a recorder that keeps every
+ * nframes-th picture, a wall that shows its cameras at a fraction of their rate: none of them holds a state.
+ *   Result: for stream s, sum[x] = the sum over t of the difference record (s, t) holds at index x, in uint8 wrap-around
+ *   (0 where no record has an entry).  Segment s holds the entries (x, sum[x]) with sum[x] != 0 in ascending x -- an index
+ *   whose differences cancel drops out.  d_offsets: uint32[nstreams + 1], the exclusive scan of the segments' counts.
+ *   Compact form: record s is the canonical encoding of segment s -- the bytes mi355_cwire_encode_batch would write from it,
+ *   pad bytes zero, headers {n, e} written -- at d_cwire_out + d_frame_pos[s]; d_frame_pos: uint64[nstreams + 1], always
+ *   exact.  Record s is written only if d_frame_pos[s + 1] <= capacity_bytes; one that does not fit is skipped whole and the
+ *   records behind it that fit are still written.  mi355_cwire_bytes_max(N, nstreams) always suffices.
+ *   Arrays form: entries at or past `capacity` are dropped, the offsets stay exact.
+ *   Applying output record s to any N-byte state equals applying the stream's nframes records in order (mi355_cwire_apply_host,
+ *   mi355_apply_multi_cwire_batch, and mi355_apply_multi_batch for the arrays form).  With nframes == 1 a record this library
+ *   made comes back byte for byte.  A stream whose records cancel completely yields an n = 0 record of 8 bytes.
+ *   Malformed compact content under consistent headers: nothing is read outside the input span, nothing is written outside the
+ *   outputs; an escape ranked at or past e and an index >= N contribute nothing (the guarantees of
+ *   mi355_apply_multi_stream_cwire_batch).  The output is still one well-formed canonical record per stream -- it is encoded
+ *   from the accumulated sums -- and d_offsets / d_frame_pos agree with it; only the malformed stream's own record is
+ *   otherwise unspecified.
+ *   Refused with MI355_ERR_INVALID before anything is launched or written: a null core; a negative nstreams or nframes;
+ *   nstreams*nframes > max_batch; with nstreams*nframes > 0 a null input or output pointer; h_escapes[b] > h_counts[b];
+ *   h_counts[b] > N; d_cwire, d_cwire_out, d_offsets or d_xs not 4-byte aligned; d_frame_pos not 8-byte aligned; the input
+ *   span (known from the host's headers) overlapping an output region: [d_cwire_out, + capacity_bytes), d_xs / d_diff over
+ *   `capacity` entries, the offsets or frame_pos array.  nstreams*nframes == 0 writes offsets[0] = 0 (and frame_pos[0] = 0)
+ *   and nothing else.
+ * Asynchronous on the core's stream, behind the last expansion of this core as every consumer of a packed stream is, so
+ * mi355_diff_multi_stream_cwire_batch followed by this call on one core needs no synchronisation; with a caller's stream
+ * everything runs on it in call order.  Nothing is allocated inside the call; the core's state is neither read nor written
+ * (the call uses the directory scratch of mi355_apply_cwire_batch and nothing else of the core).
+ * The directory kernels of mi355_apply_cwire_batch on the nstreams*nframes records, then four launches: a grid of 4096-byte
+ * tiles x streams sums the records that land in a tile into a ZEROED tile in LDS and leaves four facts of it (nonzero bytes,
+ * first, last, gaps >= 255 inside); one workgroup per stream scans the tiles; one workgroup places the streams and writes
+ * headers and pad bytes; the tile grid runs again, a tile without a nonzero byte returns on its fact word, the others rebuild
+ * their sums from the records and store their entries.  The records are read about three times; no N-byte buffer exists.
+ * Not measured yet: tools/bench_multi.py --legs coalesce writes profiles/multi_coalesce.json (microseconds per input record
+ * against mi355_apply_multi_stream_cwire_batch onto relay-held states + mi355_diff_multi_cwire_batch of a threshold-0 core, same
+ * run, same board).  The expectation to test -- no slower than that route at S = 16, T = 16 on either input, by more than
+ * the rounds' spread -- is neither met nor missed until that file exists.  DESIGN.md section 4, "Coalescing a burst". */
+int mi355_cwire_coalesce_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
+                               int nstreams, int nframes, void *d_offsets, void *d_xs, void *d_diff, size_t capacity);
+int mi355_cwire_coalesce_cwire_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts,
+                                     const uint32_t *h_escapes, int nstreams, int nframes, void *d_offsets,
+                                     void *d_frame_pos, void *d_cwire_out, size_t capacity_bytes);
 
 /* The client's side, client/opencv.cpp:50-66: for every frame in order, state[xs[i]] += diff[i] (uint8
  * wrap-around) on the core's state (a client core is a core whose state was set to the received base frame,

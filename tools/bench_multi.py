@@ -517,6 +517,109 @@ def run_burst_client(W, H, S, T, rounds, kind):
     return out
 
 
+def run_coalesce(W, H, S, T, rounds, kind):
+    """The coalesce leg for one (S, T) and one input -> its dictionary.  coalesce: mi355_cwire_coalesce_cwire_batch on the
+    burst's records, nothing else.  state_route: what a relay did before -- mi355_apply_multi_stream_cwire_batch onto states it
+    holds, then mi355_diff_multi_cwire_batch of a threshold-0 core between the new states and the saved ones (which the call
+    advances), both on one core, no synchronisation in between."""
+    import numpy as np
+    from cudavideostream_amd import CUDACore, cwire_bytes_max
+    dev = torch.device("cuda", 0)
+    n, B = 3 * W * H, S * T
+    passes = 2 * max(1, 1024 // B)                     # ~2 k records per timed window
+    if kind == "webcam":                                # run_burst's input: one stream cut into S pieces
+        _, web = synth.webcam_stream(B + 1, W, H, device=dev)
+        web = web.reshape(B + 1, n)
+        states0, fwd = web[0:B:T].clone(), web[1:].reshape(S, T, n)
+    else:
+        states0, fwd = local_streams(S, T, W, H, dev)
+    per_call = min(S, max(1, ((1 << 32) - 1) // n // T))             # whole streams per call: max_batch * N < 2^32
+    chunks = [(s0, min(per_call, S - s0)) for s0 in range(0, S, per_call)]
+    recs = []                                           # per chunk: (records, counts, escapes, bytes)
+    srv_states = states0.clone()
+    with CUDACore(W, H, max_batch=per_call * T) as server:
+        for s0, ns in chunks:
+            nb = ns * T
+            cwcap = cwire_bytes_max(n, nb)
+            d_off = torch.zeros(nb + 1, dtype=torch.int32, device=dev)
+            d_pos = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
+            d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()
+            server.diff_multi_stream_cwire_batch(fwd[s0], srv_states[s0], ns, T, d_off, d_pos, d_cw, cwcap)
+            server.synchronize()
+            pos = d_pos.cpu().numpy().astype(np.int64)
+            counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
+            pad = (counts.astype(np.int64) + 3) & ~3
+            escapes = ((np.diff(pos) - 8 - 2 * pad) // 4).astype(np.uint32)
+            recs.append((d_cw[:int(pos[nb])].clone(), counts, escapes, int(pos[nb])))
+            del d_cw
+    ocap = cwire_bytes_max(n, per_call)
+    d_ooff = torch.zeros(per_call + 1, dtype=torch.int32, device=dev)
+    d_opos = torch.zeros(per_call + 1, dtype=torch.int64, device=dev)
+    d_out = torch.empty(ocap, dtype=torch.uint8, device=dev)
+    d_roff, d_rpos, d_rout = torch.zeros_like(d_ooff), torch.zeros_like(d_opos), torch.empty_like(d_out)
+    states, saved = states0.clone(), states0.clone()
+    relay = CUDACore(W, H, max_batch=per_call * T)
+    route = CUDACore(W, H, max_batch=per_call * T, threshold=0)
+    torch.cuda.synchronize()
+
+    def leg_coalesce():
+        for _ in range(passes):
+            for (s0, ns), r in zip(chunks, recs):
+                relay.cwire_coalesce_cwire_batch(r[0], r[1], r[2], ns, T, d_ooff, d_opos, d_out, ocap)
+        relay.synchronize()
+
+    def leg_route():
+        for _ in range(passes):
+            for (s0, ns), r in zip(chunks, recs):
+                route.apply_multi_stream_cwire_batch(r[0], r[1], r[2], ns, T, states[s0])
+                route.diff_multi_cwire_batch(states[s0], saved[s0], ns, d_roff, d_rpos, d_rout, ocap)
+        route.synchronize()
+
+    table = {"coalesce": leg_coalesce, "state_route": leg_route}
+    times = {}
+    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
+        for name, leg in table.items():
+            states.copy_(states0)
+            saved.copy_(states0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            leg()
+            dt = time.perf_counter() - t0
+            if r:
+                times.setdefault(name, []).append(dt * 1e6 / (passes * B))
+    # one burst from the base states: both ways make the same records, and they lead to the sender's states
+    states.copy_(states0)
+    saved.copy_(states0)
+    out_bytes = out_entries = 0
+    torch.cuda.synchronize()
+    for (s0, ns), r in zip(chunks, recs):
+        relay.cwire_coalesce_cwire_batch(r[0], r[1], r[2], ns, T, d_ooff, d_opos, d_out, ocap)
+        route.apply_multi_stream_cwire_batch(r[0], r[1], r[2], ns, T, states[s0])
+        route.diff_multi_cwire_batch(states[s0], saved[s0], ns, d_roff, d_rpos, d_rout, ocap)
+        relay.synchronize()
+        route.synchronize()
+        nbytes = int(d_opos[ns].item())
+        assert torch.equal(d_opos[:ns + 1], d_rpos[:ns + 1]) and torch.equal(d_out[:nbytes], d_rout[:nbytes])
+        out_bytes += nbytes
+        out_entries += int(d_ooff[ns].item())
+    assert torch.equal(states, srv_states) and torch.equal(saved, srv_states)
+    in_bytes = sum(r[3] for r in recs)
+    out = {"input": kind, "streams": S, "frames": T, "passes": passes, "calls_per_burst": len(chunks),
+           "input_entries_per_stream": round(sum(int(r[1].sum()) for r in recs) / S, 1), "output_entries_per_stream": round(out_entries / S, 1),
+           "input_bytes_per_stream": round(in_bytes / S, 1), "output_bytes_per_stream": round(out_bytes / S, 1),
+           "output_over_input_bytes": round(out_bytes / in_bytes, 4)}
+    for name in table:
+        st = stats(times[name])
+        st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
+        out[name + "_us_per_input_record"] = st
+    med = {k: statistics.median(v) for k, v in times.items()}
+    out["state_route_over_coalesce"] = round(med["state_route"] / med["coalesce"], 3)
+    relay.close()
+    route.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", default="1920x1080")
@@ -524,8 +627,8 @@ def main():
     ap.add_argument("--steps", type=int, default=8, help="K: webcam frames a stream walks through")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--legs", default="multi,cores_loop,pairs",
-                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone")
-    ap.add_argument("--frames", default="4,16,64", help="burst and burst_client legs: T, frames per stream and call")
+                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone")
+    ap.add_argument("--frames", default="4,16,64", help="burst, burst_client and coalesce legs: T, frames per stream and call")
     a = ap.parse_args()
     have = load_library()
     W, H = (int(v) for v in a.size.split("x"))
@@ -554,6 +657,16 @@ def main():
                     per.append(run_burst_client(W, H, S, T, a.rounds, kind))
                     torch.cuda.empty_cache()
         print(json.dumps({"bench": "multi_stream_client", "size": f"{W}x{H}", "rounds": a.rounds, "burst_client": per}), flush=True)
+        return
+    if a.legs == "coalesce":
+        per = []
+        for S in (int(v) for v in a.streams.split(",")):
+            for T in (int(v) for v in a.frames.split(",")):
+                for kind in ("webcam", "local"):
+                    per.append(run_coalesce(W, H, S, T, a.rounds, kind))
+                    print(f"coalesce S={S} T={T} {kind}: done", file=sys.stderr, flush=True)
+                    torch.cuda.empty_cache()
+        print(json.dumps({"bench": "multi_coalesce", "size": f"{W}x{H}", "rounds": a.rounds, "coalesce": per}), flush=True)
         return
     for S in (int(v) for v in a.streams.split(",")):
         run(W, H, S, a.steps, a.rounds, set(a.legs.split(",")), have)

@@ -28,9 +28,15 @@
 // and not re-staged, and applies the whole burst with ONE mi355_apply_multi_stream_cwire_batch into output frames.  After every
 // burst the states at both ends must be equal, and every output frame the frame a host client (mi355_cwire_apply_host) rebuilt
 // for that camera and tick.
+// --compact --multi S --burst K --coalesce: a relay between the two ends that forwards at 1/K of the rate (a slow link, a
+// time-lapse recorder, a video wall).  It holds no frame: it uploads every camera's slice as it came off its socket, makes
+// ONE record per camera of the burst with mi355_cwire_coalesce_cwire_batch, and forwards those S records; the receiver applies
+// them with one mi355_apply_multi_cwire_batch.  After every burst each camera's state at the receiver must equal the frame of
+// a host client (mi355_cwire_apply_host) that applied all K original records, and the sender's state.  The line also says how
+// many bytes the relay received and how many it forwarded.
 //
 //   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B]
-//                   [--compact [--direct] [--gpu-client] [--multi S [--burst K [--burst-client]]]]
+//                   [--compact [--direct] [--gpu-client] [--multi S [--burst K [--burst-client | --coalesce]]]]
 //   exit status 0 = all checks passed
 #include <cstdint>
 #include <cstdio>
@@ -406,20 +412,158 @@ static int run_multi_burst_client(int w, int h, int T, int S, int K) {
     return 0;
 }
 
+// --compact --multi S --burst K --coalesce (see the head of the file)
+static int run_multi_burst_coalesce(int w, int h, int T, int S, int K) {
+    const size_t n = (size_t)3 * w * h;
+    mi355_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.width = w; cfg.height = h; cfg.threshold = 20; cfg.max_batch = S * K; cfg.device = -1;
+    mi355_core *server = nullptr, *relay = nullptr, *client = nullptr;
+    OK(mi355_create(&cfg, &server));
+    OK(mi355_create(&cfg, &relay));
+    cfg.max_batch = S;
+    OK(mi355_create(&cfg, &client));
+    const int B = S * K;
+    const size_t cw_cap = mi355_cwire_bytes_max(n, B), one_cap = mi355_cwire_bytes_max(n, S);
+    void *d_frames = nullptr, *d_sstates = nullptr, *d_off = nullptr, *d_pos = nullptr, *d_cw = nullptr;   // server
+    void *d_in = nullptr, *d_roff = nullptr, *d_rpos = nullptr, *d_fwd = nullptr;                           // relay
+    void *d_rx = nullptr, *d_cstates = nullptr;                                                              // client
+    OK(mi355_dev_alloc(server, &d_frames, (size_t)B * n));
+    OK(mi355_dev_alloc(server, &d_sstates, (size_t)S * n));
+    OK(mi355_dev_alloc(server, &d_off, sizeof(uint32_t) * (B + 1)));
+    OK(mi355_dev_alloc(server, &d_pos, sizeof(uint64_t) * (B + 1)));
+    OK(mi355_dev_alloc(server, &d_cw, cw_cap));
+    OK(mi355_dev_alloc(relay, &d_in, cw_cap));
+    OK(mi355_dev_alloc(relay, &d_roff, sizeof(uint32_t) * (S + 1)));
+    OK(mi355_dev_alloc(relay, &d_rpos, sizeof(uint64_t) * (S + 1)));
+    OK(mi355_dev_alloc(relay, &d_fwd, one_cap));
+    OK(mi355_dev_alloc(client, &d_rx, one_cap));
+    OK(mi355_dev_alloc(client, &d_cstates, (size_t)S * n));
+    int fds[2];
+    if (pipe(fds) != 0) return 1;
+    std::vector<uint8_t> bases((size_t)S * n), host_frames((size_t)S * n), frames((size_t)B * n), s_states((size_t)S * n),
+        c_states((size_t)S * n), cw_host(cw_cap), relay_rx(cw_cap), fwd(one_cap), rx(one_cap);
+    for (int s = 0; s < S; s++)
+        for (size_t i = 0; i < n; i++) bases[(size_t)s * n + i] = (uint8_t)(40 + (i * 7 + (size_t)s * 31) % 150);
+    OK(mi355_upload(server, d_sstates, bases.data(), bases.size()));
+    if (!through_pipe(fds[1], fds[0], bases.data(), host_frames.data(), bases.size())) return 1;
+    OK(mi355_upload(client, d_cstates, host_frames.data(), host_frames.size()));
+    std::vector<uint8_t> base(n), frame(n);
+    std::vector<uint32_t> off(B + 1), counts(B), escapes(B), roff(S + 1), ocounts(S), oescapes(S);
+    std::vector<uint64_t> pos(B + 1), rpos(S + 1);
+    size_t received = 0, forwarded = 0, changed = 0, kept = 0;
+    int max_err = 0, calls = 0;
+    for (int t0 = 0; t0 < T; t0 += K) {
+        const int nb = T - t0 < K ? T - t0 : K, nrec = S * nb;
+        for (int s = 0; s < S; s++) {   // camera s's nb frames, one behind the other
+            memcpy(base.data(), &bases[(size_t)s * n], n);
+            for (int k = 0; k < nb; k++) {
+                make_frame(frame, base, w, h, t0 + k + 5 * s);
+                memcpy(&frames[((size_t)s * nb + k) * n], frame.data(), n);
+            }
+        }
+        // ---- server: nb ticks of S cameras -> S * nb records in one call
+        OK(mi355_upload(server, d_frames, frames.data(), (size_t)nrec * n));
+        OK(mi355_diff_multi_stream_cwire_batch(server, d_frames, d_sstates, n, S, nb, d_off, d_pos, d_cw, cw_cap));
+        OK(mi355_download(server, off.data(), d_off, sizeof(uint32_t) * (nrec + 1)));
+        OK(mi355_download(server, pos.data(), d_pos, sizeof(uint64_t) * (nrec + 1)));
+        if (pos[nrec] > cw_cap) { fprintf(stderr, "compact stream larger than its bound\n"); return 1; }
+        const size_t cb = (size_t)pos[nrec];
+        OK(mi355_download(server, cw_host.data(), d_cw, cb));
+        changed += off[nrec];
+        // ---- the sockets into the relay: camera s's slice is one write; the relay reads the headers, uploads the slice as it
+        // came; a host client beside it applies all nb original records of the camera
+        size_t p = 0;
+        for (int s = 0; s < S; s++) {
+            const size_t a = (size_t)pos[(size_t)s * nb], b = (size_t)pos[(size_t)(s + 1) * nb];
+            if (a != p) { fprintf(stderr, "stream framing broken\n"); return 1; }
+            if (!through_pipe(fds[1], fds[0], cw_host.data() + a, relay_rx.data() + a, b - a)) return 1;
+            for (int k = 0; k < nb; k++) {
+                const int r = s * nb + k;
+                if (p + 8 > b) { fprintf(stderr, "stream framing broken\n"); return 1; }
+                memcpy(&counts[r], relay_rx.data() + p, 4);
+                memcpy(&escapes[r], relay_rx.data() + p + 4, 4);
+                size_t used = 0;
+                OK(mi355_cwire_apply_host(&host_frames[(size_t)s * n], n, relay_rx.data() + p, b - p, 1, &used));
+                if (used != mi355_cwire_frame_bytes(counts[r], escapes[r])) { fprintf(stderr, "stream framing broken\n"); return 1; }
+                p += used;
+            }
+            if (p != b) { fprintf(stderr, "stream framing broken\n"); return 1; }
+            if (b > a) OK(mi355_upload(relay, (uint8_t *)d_in + a, relay_rx.data() + a, b - a));
+        }
+        received += cb;
+        // ---- relay: the burst -> one record per camera, in one call; no frame exists here
+        OK(mi355_cwire_coalesce_cwire_batch(relay, d_in, counts.data(), escapes.data(), S, nb, d_roff, d_rpos, d_fwd, one_cap));
+        calls++;
+        OK(mi355_download(relay, roff.data(), d_roff, sizeof(uint32_t) * (S + 1)));
+        OK(mi355_download(relay, rpos.data(), d_rpos, sizeof(uint64_t) * (S + 1)));
+        if (rpos[S] > one_cap) { fprintf(stderr, "coalesced stream larger than its bound\n"); return 1; }
+        const size_t fb = (size_t)rpos[S];
+        OK(mi355_download(relay, fwd.data(), d_fwd, fb));
+        kept += roff[S];
+        // ---- the sockets out of the relay, one record per camera; the receiver finds them from their headers
+        if (!through_pipe(fds[1], fds[0], fwd.data(), rx.data(), fb)) return 1;
+        forwarded += fb;
+        p = 0;
+        for (int s = 0; s < S; s++) {
+            if (p + 8 > fb) { fprintf(stderr, "forwarded framing broken\n"); return 1; }
+            memcpy(&ocounts[s], rx.data() + p, 4);
+            memcpy(&oescapes[s], rx.data() + p + 4, 4);
+            p += mi355_cwire_frame_bytes(ocounts[s], oescapes[s]);
+        }
+        if (p != fb) { fprintf(stderr, "forwarded framing broken\n"); return 1; }
+        // ---- receiver: one call per burst
+        OK(mi355_upload(client, d_rx, rx.data(), fb));
+        OK(mi355_apply_multi_cwire_batch(client, d_rx, ocounts.data(), oescapes.data(), S, d_cstates, n));
+        OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
+        OK(mi355_download(server, s_states.data(), d_sstates, s_states.size()));
+        for (int s = 0; s < S; s++)
+            if (memcmp(&host_frames[(size_t)s * n], &c_states[(size_t)s * n], n) != 0) {
+                fprintf(stderr, "burst at tick %d: camera %d: receiver state != host client that applied all %d records\n", t0, s, nb);
+                return 1;
+            }
+        if (memcmp(s_states.data(), c_states.data(), s_states.size()) != 0) {
+            fprintf(stderr, "burst at tick %d: receiver states != server states\n", t0);
+            return 1;
+        }
+        for (int s = 0; s < S; s++)
+            for (size_t i = 0; i < n; i++) {
+                const int e = abs((int)c_states[(size_t)s * n + i] - (int)frames[((size_t)s * nb + nb - 1) * n + i]);
+                if (e > max_err) max_err = e;
+            }
+    }
+    if (max_err > cfg.threshold) { fprintf(stderr, "rebuilt frame off by %d > threshold\n", max_err); return 1; }
+    void *srv[] = {d_frames, d_sstates, d_off, d_pos, d_cw};
+    for (void *q : srv) OK(mi355_dev_free(server, q));
+    void *rel[] = {d_in, d_roff, d_rpos, d_fwd};
+    for (void *q : rel) OK(mi355_dev_free(relay, q));
+    OK(mi355_dev_free(client, d_rx));
+    OK(mi355_dev_free(client, d_cstates));
+    mi355_destroy(server);
+    mi355_destroy(relay);
+    mi355_destroy(client);
+    printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"burst\": %d, \"coalesce\": true, \"relay_calls\": %d, "
+           "\"width\": %d, \"height\": %d, \"ticks\": %d, \"changed_bytes\": %zu, \"coalesced_entries\": %zu, "
+           "\"relay_received_bytes\": %zu, \"relay_forwarded_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d}\n",
+           S, K, calls, w, h, T, changed, kept, received, forwarded, (size_t)T * S * n, max_err);
+    return 0;
+}
+
 int main(int argc, char **argv) {
     int w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0;
-    bool compact = false, direct = false, gpu_client = false, burst_client = false;
+    bool compact = false, direct = false, gpu_client = false, burst_client = false, coalesce = false;
     for (int i = 1; i < argc; i++) {
         if (std::string(argv[i]) == "--compact") compact = true;
         if (std::string(argv[i]) == "--direct") direct = true;
         if (std::string(argv[i]) == "--gpu-client") gpu_client = true;
         if (std::string(argv[i]) == "--burst-client") burst_client = true;
+        if (std::string(argv[i]) == "--coalesce") coalesce = true;
     }
     if (direct && !compact) { fprintf(stderr, "--direct needs --compact\n"); return 2; }
     if (gpu_client && !compact) { fprintf(stderr, "--gpu-client needs --compact\n"); return 2; }
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string k = argv[i];
-        if (k == "--compact" || k == "--direct" || k == "--gpu-client" || k == "--burst-client") { i--; continue; }
+        if (k == "--compact" || k == "--direct" || k == "--gpu-client" || k == "--burst-client" || k == "--coalesce") { i--; continue; }
         const int v = atoi(argv[i + 1]);
         if (k == "--width") w = v; else if (k == "--height") h = v;
         else if (k == "--frames") T = v; else if (k == "--batch") B = v;
@@ -428,9 +572,14 @@ int main(int argc, char **argv) {
     }
     if (burst && (!multi || burst < 0)) { fprintf(stderr, "--burst K needs --multi S and K >= 1\n"); return 2; }
     if (burst_client && (!compact || !multi || !burst)) { fprintf(stderr, "--burst-client needs --compact --multi S --burst K\n"); return 2; }
+    if (coalesce && (!compact || !multi || !burst || burst_client)) {
+        fprintf(stderr, "--coalesce needs --compact --multi S --burst K, without --burst-client\n");
+        return 2;
+    }
     if (multi) {
         if (!compact || direct || gpu_client || multi < 0) { fprintf(stderr, "--multi S needs --compact alone and S >= 1\n"); return 2; }
         if (burst_client) return run_multi_burst_client(w, h, T, multi, burst);
+        if (coalesce) return run_multi_burst_coalesce(w, h, T, multi, burst);
         return burst ? run_multi_burst(w, h, T, multi, burst) : run_multi(w, h, T, multi);
     }
     const size_t n = (size_t)3 * w * h;
