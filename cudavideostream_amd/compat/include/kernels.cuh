@@ -48,6 +48,16 @@ public:
     long long exec_submit(uint8_t *frameData, uint8_t *showReadyNData, std::string &text, int *h_xs);
     void exec_wait(long long ticket, unsigned int *h_pos);
     void pipe_close();
+    // The same three with the frame's changes as ONE compact record in host memory, ready for one write() (include/
+    // mi355diff.h, mi355_exec_cwire / mi355_pipe_submit_cwire / mi355_pipe_wait_cwire): frameData is only read, h_record
+    // (alloc_record: pinned, record_capacity bytes) takes the record, *h_bytes its length, *h_pos / *h_escapes its header.
+    // Plain and compact calls may alternate on one object.
+    static void alloc_record(void **h_record, size_t *record_capacity, int r, int c);
+    void exec_core_compact(const uint8_t *frameData, uint8_t *showReadyNData, std::string &text, void *h_record,
+                           size_t record_capacity, unsigned int *h_pos, unsigned int *h_escapes, size_t *h_bytes);
+    long long exec_submit_compact(const uint8_t *frameData, uint8_t *showReadyNData, std::string &text, void *h_record,
+                                  size_t record_capacity);
+    void exec_wait_compact(long long ticket, unsigned int *h_pos, unsigned int *h_escapes, size_t *h_bytes);
     // One tick of nstreams cameras in one call (include/mi355diff.h, mi355_diff_multi_batch): camera s has its new frame at
     // d_frames + s*stride and its reconstructed-frame state at d_states + s*stride, both in DEVICE memory of the caller
     // (mi355_dev_alloc / hipMalloc); segment s of (d_offsets, d_xs, d_diff) is its packed frame.  Blocking, like exec_core.

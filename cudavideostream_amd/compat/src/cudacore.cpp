@@ -91,6 +91,35 @@ void CUDACore::exec_wait(long long ticket, unsigned int *h_pos) {
     *h_pos = pos;
 }
 
+void CUDACore::alloc_record(void **h_record, size_t *record_capacity, int r, int c) {
+    *record_capacity = mi355_cwire_bytes_max((size_t)3 * r * c, 1);
+    MI355_CHECK(mi355_host_alloc(h_record, *record_capacity));
+}
+
+void CUDACore::exec_core_compact(const uint8_t *frameData, uint8_t *showReadyNData, std::string &text, void *h_record,
+                                 size_t record_capacity, unsigned int *h_pos, unsigned int *h_escapes, size_t *h_bytes) {
+    uint32_t pos = 0, esc = 0;
+    MI355_CHECK(mi355_exec_cwire(core_, frameData, showReadyNData, text.empty() ? nullptr : text.c_str(), h_record,
+                                 record_capacity, &pos, &esc, h_bytes));
+    *h_pos = pos;
+    *h_escapes = esc;
+}
+
+long long CUDACore::exec_submit_compact(const uint8_t *frameData, uint8_t *showReadyNData, std::string &text, void *h_record,
+                                        size_t record_capacity) {
+    int64_t ticket = -1;
+    MI355_CHECK(mi355_pipe_submit_cwire(core_, frameData, showReadyNData, text.empty() ? nullptr : text.c_str(), h_record,
+                                        record_capacity, &ticket));
+    return ticket;
+}
+
+void CUDACore::exec_wait_compact(long long ticket, unsigned int *h_pos, unsigned int *h_escapes, size_t *h_bytes) {
+    uint32_t pos = 0, esc = 0;
+    MI355_CHECK(mi355_pipe_wait_cwire(core_, ticket, &pos, &esc, h_bytes));
+    *h_pos = pos;
+    *h_escapes = esc;
+}
+
 void CUDACore::exec_multi(const void *d_frames, void *d_states, size_t stride, int nstreams, void *d_offsets, void *d_xs,
                           void *d_diff, size_t capacity) {
     MI355_CHECK(mi355_diff_multi_batch(core_, d_frames, d_states, stride, nstreams, d_offsets, d_xs, d_diff, capacity));

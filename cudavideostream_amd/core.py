@@ -205,6 +205,40 @@ class CUDACore:
         _l.check(self._lib.mi355_pipe_wait(self._h, ticket, C.byref(pos)))
         return pos.value
 
+    # -- exec_core into ONE compact record per frame (include/mi355diff.h) -------------------------------
+    @staticmethod
+    def alloc_record(r, c):
+        """A pinned buffer for one frame's compact record: cwire_bytes_max(3rc, 1) bytes, the capacity the compact calls ask for."""
+        return PinnedArray(cwire_bytes_max(3 * r * c, 1))
+
+    @staticmethod
+    def _record_capacity(h_record, capacity):
+        return int(capacity) if capacity is not None else int(h_record.nbytes)
+
+    def exec_core_compact(self, frame_data, show_ready_n_data, text, h_record, capacity=None):
+        """exec_core with the frame's changes as one compact record in h_record (uint8, 4-byte aligned, capacity -- by
+        default its size -- at least cwire_bytes_max(N, 1)); frame_data is only read.  Returns (h_pos, escapes, bytes): the
+        record is h_record[:bytes]."""
+        n, e, b = C.c_uint32(0), C.c_uint32(0), C.c_size_t(0)
+        t = text.encode() if text else None
+        _l.check(self._lib.mi355_exec_cwire(self._h, _ptr(frame_data), _ptr(show_ready_n_data), t, _ptr(h_record),
+                                            self._record_capacity(h_record, capacity), C.byref(n), C.byref(e), C.byref(b)))
+        return n.value, e.value, b.value
+
+    def exec_submit_compact(self, frame_data, show_ready_n_data, text, h_record, capacity=None):
+        """Arguments of exec_core_compact (pinned buffers); returns a ticket for exec_wait_compact (or exec_wait)."""
+        ticket = C.c_int64(-1)
+        t = text.encode() if text else None
+        _l.check(self._lib.mi355_pipe_submit_cwire(self._h, _ptr(frame_data), _ptr(show_ready_n_data), t, _ptr(h_record),
+                                                   self._record_capacity(h_record, capacity), C.byref(ticket)))
+        return ticket.value
+
+    def exec_wait_compact(self, ticket):
+        """Blocks until the frame's record is in its buffer; returns (h_pos, escapes, bytes)."""
+        n, e, b = C.c_uint32(0), C.c_uint32(0), C.c_size_t(0)
+        _l.check(self._lib.mi355_pipe_wait_cwire(self._h, ticket, C.byref(n), C.byref(e), C.byref(b)))
+        return n.value, e.value, b.value
+
     # -- state ------------------------------------------------------------------------------------
     def set_state(self, frame):
         frame = np.ascontiguousarray(frame, dtype=np.uint8).reshape(-1)

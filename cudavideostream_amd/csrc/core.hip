@@ -12,6 +12,8 @@
 //   groff     T*ceil(W/64)*16 (a prefix per range of 16 tiles);  totals T*8 {total, epoch} + the ticket;  offsets (T+1)*4
 //   one_xs N*4, one_diff N exec(): packed output of a single frame before the D2H copies
 //   cw_cnt    32 KiB       the compact-wire encoder's escape counts per workgroup
+//   cw_rec    8 + 2*pad4(N) (rounded up to 16) + 16  mi355_exec_cwire / mi355_pipe_submit_cwire: the frame's record before its
+//                          export and its frame_pos[2]; made by the first such call (or MI355_PREPARE_EXEC_CWIRE)
 //   cw_items  T*ceil(W/16)*16 + T*4  mi355_diff_stream_cwire_batch: one word per item of the expansion, escapes per frame
 //   cwa_*     T*24 + 2*T*ceil(N/4096)*16  mi355_apply_cwire_batch: frame table, chunk facts, tile directory
 //   hist T*256*4, thr T*4 (per frame of a filter batch), k9 9*4, heat LUT 766*3, glyph atlas
@@ -73,6 +75,17 @@ struct mi355_core {
     int32_t *hist = nullptr, *thr = nullptr;
     uint32_t *red_bounds = nullptr; // mi355_red_stream_batch (cleared form): entry ranges of the frame slices
     uint32_t *cw_cnt = nullptr;     // mi355_cwire_encode_batch: escapes per workgroup of the emit kernel (kCwireSlots words)
+    // mi355_exec_cwire / mi355_pipe_submit_cwire (made on first use, need_exec_cwire): the frame's record on the device
+    // (cw_rec_bytes = mi355_cwire_bytes_max(N, 1); the allocation is that rounded up to 16) and its frame_pos[2].  One buffer
+    // serves every slot of the ring, as one_xs does: encode and export of a frame run back to back on the core's stream.
+    uint8_t *cw_rec = nullptr;
+    uint64_t *cw_rec_pos = nullptr;
+    uint64_t cw_rec_bytes = 0;
+    // ... and what k_export_record reports, pinned: kRecWords words {n, e, bytes low, bytes high} per slot of the ring, then
+    // those of the blocking form, then 16 bytes of scratch (the warm pass's record; the pageable form's read-back)
+    static constexpr int kRecWords = 4;
+    uint32_t *h_rec = nullptr;
+    bool cw_warm = false;             // the warm pass of the encode and export kernels has run and gave the empty record
     uint4 *cw_items = nullptr;      // mi355_diff_stream_cwire_batch: [T][ceil(W/16)] item words (diff_pack.hip, k_cwire_items)
     uint32_t *cw_esc = nullptr;     // ... and [T] escapes per frame
     CwaFrame *cwa_ftab = nullptr;   // mi355_apply_cwire_batch (stream_ops.hip): [T] frame headers of a slice,
@@ -98,6 +111,7 @@ struct mi355_core {
         uint32_t *h_count = nullptr;                   // pinned, written by k_export
         hipEvent_t uploaded = nullptr, painted = nullptr, packed = nullptr, shown = nullptr;
         bool has_vis = false;
+        bool compact = false;                          // submitted by mi355_pipe_submit_cwire: the results are in h_rec
         int64_t ticket = -1;                           // frame in flight in this slot, -1 = free
     };
     Slot slots[kMaxSlots];
@@ -673,19 +687,21 @@ void mi355_destroy(mi355_core *c) {
     }
     void *ptrs[] = {c->state, c->in, c->aux, c->vis, c->rec, c->codes, c->meta, c->groff, c->totals, c->offsets, c->one_xs, c->one_diff, c->hist, c->thr, c->k9,
                     c->lut, c->glyphs, c->kxk, c->gray1, c->red_bounds, c->cw_cnt, c->cw_items, c->cw_esc,
-                    c->cwa_ftab, c->cwa_chunk, c->cwa_dir};
+                    c->cwa_ftab, c->cwa_chunk, c->cwa_dir, c->cw_rec, c->cw_rec_pos};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->h_count) (void)hipHostFree(c->h_count);
+    if (c->h_rec) (void)hipHostFree(c->h_rec);
     for (auto &slot : c->ev) for (auto &ev : slot) if (ev) (void)hipEventDestroy(ev);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
 }
 
 static int warm_exec(mi355_core *c);   // below, beside mi355_exec
+static int need_exec_cwire(mi355_core *c);   // below, beside mi355_exec_cwire
 
 int mi355_prepare(mi355_core *c, unsigned what) {
     if (!c) return fail(MI355_ERR_INVALID, "null core");
-    if (what & ~MI355_PREPARE_ALL) return fail(MI355_ERR_INVALID, "mi355_prepare: unknown bit in `what`");
+    if (what & ~(MI355_PREPARE_ALL | MI355_PREPARE_EXEC_CWIRE)) return fail(MI355_ERR_INVALID, "mi355_prepare: unknown bit in `what`");
     if (int rc = use_device(c)) return rc;
     if ((what & MI355_PREPARE_BATCHES) && c->n > 0) {
         if (int rc = setup_pipeline(c)) return rc;   // (a core that cannot have its second set stays sequential: not an error)
@@ -698,6 +714,8 @@ int mi355_prepare(mi355_core *c, unsigned what) {
         if (int rc = dev_alloc(c, &c->kxk, 81)) return rc;
     if ((what & MI355_PREPARE_EXEC) && c->n > 0 && c->nslots == 0)
         if (int rc = warm_exec(c)) return rc;
+    if (what & MI355_PREPARE_EXEC_CWIRE)
+        if (int rc = need_exec_cwire(c)) return rc;
     HIP_TRY(hipDeviceSynchronize());   // the memsets of the new buffers
     return MI355_OK;
 }
@@ -1710,13 +1728,10 @@ static int warm_exec(mi355_core *c) {
     return MI355_OK;
 }
 
-int mi355_exec(mi355_core *c, uint8_t *frame_data, uint8_t *show_ready, const char *text,
-               uint32_t *h_pos, int32_t *h_xs) {
-    if (!h_pos) return fail(MI355_ERR_INVALID, "null argument");
-    if (int rc = check_exec_args(c, frame_data, show_ready, h_xs)) return rc;
-    if (c->nslots) return fail(MI355_ERR_STATE, "pipe open: use mi355_pipe_submit");
+// A frame of mi355_exec / mi355_exec_cwire up to its packed entries in one_xs / one_diff (the caller has made the device
+// current): upload, noise filter, overlay, the visualisers that look at the frame before the diff, the diff with feedback.
+static int exec_frame(mi355_core *c, const uint8_t *frame_data, uint8_t *show_ready, const char *text) {
     const int vis = c->cfg.visualizer;
-    if (int rc = use_device(c)) return rc;
     hipStream_t s = c->stream;
     const uint32_t N = c->n;
     const FrameBatch one{N, 1};
@@ -1733,7 +1748,19 @@ int mi355_exec(mi355_core *c, uint8_t *frame_data, uint8_t *show_ready, const ch
         HIP_TRY(hipMemcpyAsync(show_ready, c->vis, N, hipMemcpyDeviceToHost, s));
 
     // kernels.cu:505  kernel2
-    if (int rc = run_batch(c, false, c->in, nullptr, N, 1, c->offsets, c->one_xs, c->one_diff, N)) return rc;
+    return run_batch(c, false, c->in, nullptr, N, 1, c->offsets, c->one_xs, c->one_diff, N);
+}
+
+int mi355_exec(mi355_core *c, uint8_t *frame_data, uint8_t *show_ready, const char *text,
+               uint32_t *h_pos, int32_t *h_xs) {
+    if (!h_pos) return fail(MI355_ERR_INVALID, "null argument");
+    if (int rc = check_exec_args(c, frame_data, show_ready, h_xs)) return rc;
+    if (c->nslots) return fail(MI355_ERR_STATE, "pipe open: use mi355_pipe_submit");
+    const int vis = c->cfg.visualizer;
+    if (int rc = use_device(c)) return rc;
+    hipStream_t s = c->stream;
+    const uint32_t N = c->n;
+    if (int rc = exec_frame(c, frame_data, show_ready, text)) return rc;
     if (is_pinned(frame_data) && is_pinned(h_xs)) {
         // Pinned buffers (alloc_arrays): the count stays on the device, the red maps take it from there and
         // k_export stores count/diff/xs through the mapped pointers -- one synchronisation instead of the
@@ -1816,19 +1843,12 @@ int mi355_pipe_open(mi355_core *c, int depth) {
     return MI355_OK;
 }
 
-int mi355_pipe_submit(mi355_core *c, uint8_t *frame_data, uint8_t *show_ready, const char *text, int32_t *h_xs,
-                      int64_t *ticket) {
-    if (!ticket) return fail(MI355_ERR_INVALID, "null argument");
-    if (int rc = check_exec_args(c, frame_data, show_ready, h_xs)) return rc;
-    if (!c->nslots) return fail(MI355_ERR_STATE, "pipe not open");
-    if (int rc = use_device(c)) return rc;
-    // the kernels store through these pointers: pageable memory would fault on the device
-    if (!is_pinned(frame_data) || !is_pinned(h_xs) || (show_ready && !is_pinned(show_ready)))
-        return fail(MI355_ERR_INVALID, "pipe buffers must be pinned host memory (mi355_host_alloc)");
+// A frame of mi355_pipe_submit / mi355_pipe_submit_cwire up to its export, into the ring's next slot: upload, noise filter,
+// overlay, visualiser, diff with feedback into one_xs / one_diff, red maps, the visualisation frame's way back.
+static int pipe_frame(mi355_core *c, const uint8_t *frame_data, uint8_t *show_ready, const char *text, mi355_core::Slot &sl) {
     const int vis = c->cfg.visualizer;
     const uint32_t N = c->n;
     const FrameBatch one{N, 1};
-    mi355_core::Slot &sl = c->slots[c->next_ticket % c->nslots];
     hipStream_t s = c->stream;
     if (sl.ticket >= 0) {   // ring full: the slot's previous frame was never waited for; finish it first
         HIP_TRY(hipEventSynchronize(sl.packed));
@@ -1856,25 +1876,183 @@ int mi355_pipe_submit(mi355_core *c, uint8_t *frame_data, uint8_t *show_ready, c
         HIP_TRY(hipMemcpyAsync(show_ready, sl.d_vis, N, hipMemcpyDeviceToHost, c->down_stream));
         HIP_TRY(hipEventRecord(sl.shown, c->down_stream));
     }
+    return MI355_OK;
+}
+
+int mi355_pipe_submit(mi355_core *c, uint8_t *frame_data, uint8_t *show_ready, const char *text, int32_t *h_xs,
+                      int64_t *ticket) {
+    if (!ticket) return fail(MI355_ERR_INVALID, "null argument");
+    if (int rc = check_exec_args(c, frame_data, show_ready, h_xs)) return rc;
+    if (!c->nslots) return fail(MI355_ERR_STATE, "pipe not open");
+    if (int rc = use_device(c)) return rc;
+    // the kernels store through these pointers: pageable memory would fault on the device
+    if (!is_pinned(frame_data) || !is_pinned(h_xs) || (show_ready && !is_pinned(show_ready)))
+        return fail(MI355_ERR_INVALID, "pipe buffers must be pinned host memory (mi355_host_alloc)");
+    mi355_core::Slot &sl = c->slots[c->next_ticket % c->nslots];
+    if (int rc = pipe_frame(c, frame_data, show_ready, text, sl)) return rc;
     // count, indices and differences leave through the mapped pointers: no host round trip for the count
-    HIP_TRY(launch_export(c->offsets, c->one_xs, c->one_diff, h_xs, frame_data, sl.h_count, s));
-    HIP_TRY(hipEventRecord(sl.packed, s));
+    HIP_TRY(launch_export(c->offsets, c->one_xs, c->one_diff, h_xs, frame_data, sl.h_count, c->stream));
+    HIP_TRY(hipEventRecord(sl.packed, c->stream));
+    sl.compact = false;
     sl.ticket = c->next_ticket;
     *ticket = c->next_ticket++;
     return MI355_OK;
 }
 
-int mi355_pipe_wait(mi355_core *c, int64_t ticket, uint32_t *h_pos) {
-    if (!c || !h_pos) return fail(MI355_ERR_INVALID, "null argument");
+// Finds the frame of `ticket` complete in its slot, or says why not.
+static int pipe_wait_slot(mi355_core *c, int64_t ticket, bool compact_only, mi355_core::Slot **out) {
     if (!c->nslots) return fail(MI355_ERR_STATE, "pipe not open");
     if (ticket < 0 || ticket >= c->next_ticket) return fail(MI355_ERR_INVALID, "unknown ticket");
     mi355_core::Slot &sl = c->slots[ticket % c->nslots];
     if (sl.ticket != ticket) return fail(MI355_ERR_STATE, "ticket already waited for or overwritten");
+    if (compact_only && !sl.compact)   // (the ticket stays waitable)
+        return fail(MI355_ERR_STATE, "ticket of mi355_pipe_submit: it has no compact record, use mi355_pipe_wait");
     if (int rc = use_device(c)) return rc;
     HIP_TRY(hipEventSynchronize(sl.packed));
     if (sl.has_vis) HIP_TRY(hipEventSynchronize(sl.shown));
-    *h_pos = *sl.h_count;
-    sl.ticket = -1;
+    *out = &sl;
+    return MI355_OK;
+}
+
+int mi355_pipe_wait(mi355_core *c, int64_t ticket, uint32_t *h_pos) {
+    if (!c || !h_pos) return fail(MI355_ERR_INVALID, "null argument");
+    mi355_core::Slot *sl = nullptr;
+    if (int rc = pipe_wait_slot(c, ticket, false, &sl)) return rc;
+    *h_pos = sl->compact ? c->h_rec[(sl - c->slots) * mi355_core::kRecWords] : *sl->h_count;
+    sl->ticket = -1;
+    return MI355_OK;
+}
+
+// ---- the per-frame path into ONE compact record (include/mi355diff.h, "compact form of the per-frame entry points") ----
+namespace {
+
+constexpr int kRecBlocking = mi355_core::kMaxSlots;        // h_rec: the words of mi355_exec_cwire
+constexpr int kRecScratch = mi355_core::kMaxSlots + 1;     // ... and the 16 bytes of scratch
+
+// one_xs / one_diff of the frame run_batch has just packed -> its record in cw_rec, the record's size in cw_rec_pos[1]
+int encode_record(mi355_core *c) {
+    HIP_TRY(launch_cwire_encode(c->offsets, c->one_xs, c->one_diff, c->n, 1, c->cw_cnt, c->cw_rec_pos, c->cw_rec, c->cw_rec_bytes,
+                                c->stream));
+    return MI355_OK;
+}
+
+int check_exec_cwire_args(mi355_core *c, const void *frame_data, const void *show_ready, const void *h_record, size_t record_capacity) {
+    if (int rc = check_exec_args(c, frame_data, show_ready, h_record)) return rc;
+    if ((uintptr_t)h_record & 3u) return fail(MI355_ERR_INVALID, "h_record must be 4-byte aligned");
+    // a record that did not fit would lose a frame whose state has already advanced: the worst case is demanded up front
+    if (record_capacity < mi355_cwire_bytes_max(c->n, 1))
+        return fail(MI355_ERR_INVALID, "record_capacity below mi355_cwire_bytes_max(frame bytes, 1)");
+    return MI355_OK;
+}
+
+// h_record is pinned up to the last byte the export kernel could ever store (the worst-case record)
+bool record_is_pinned(const mi355_core *c, const void *h_record) {
+    return is_pinned(h_record) && is_pinned((const uint8_t *)h_record + mi355_cwire_bytes_max(c->n, 1) - 1);
+}
+
+void read_rec_words(const uint32_t *w, uint32_t *h_pos, uint32_t *h_escapes, size_t *h_bytes) {
+    *h_pos = w[0];
+    *h_escapes = w[1];
+    *h_bytes = (size_t)(w[2] | (uint64_t)w[3] << 32);
+}
+
+}  // namespace
+
+// The record buffer, its frame_pos and the pinned result words; then the encode and export kernels once, on an empty frame
+// (the offsets of a frame without entries), so that the first real frame does not pay for their first use.
+static int need_exec_cwire(mi355_core *c) {
+    if (c->cw_warm) return MI355_OK;   // (a warm pass that failed is run again, on the buffers that exist)
+    c->cw_rec_bytes = (uint64_t)mi355_cwire_bytes_max(c->n, 1);
+    if (!c->cw_rec)
+        if (int rc = dev_alloc(c, &c->cw_rec, (size_t)((c->cw_rec_bytes + 15) & ~15ull))) return rc;
+    if (!c->cw_rec_pos)
+        if (int rc = dev_alloc(c, &c->cw_rec_pos, 2)) return rc;
+    if (!c->h_rec) {
+        HIP_TRY(hipHostMalloc((void **)&c->h_rec, (size_t)(kRecScratch + 1) * mi355_core::kRecWords * sizeof(uint32_t), hipHostMallocDefault));
+        memset(c->h_rec, 0xff, (size_t)(kRecScratch + 1) * mi355_core::kRecWords * sizeof(uint32_t));
+    }
+    // (c->offsets: every frame queued so far has read its own, in stream order; the next frame writes them again)
+    HIP_TRY(hipMemsetAsync(c->offsets, 0, 2 * sizeof(uint32_t), c->stream));
+    if (int rc = encode_record(c)) return rc;
+    uint32_t *const words = c->h_rec + kRecBlocking * mi355_core::kRecWords, *const scratch = c->h_rec + kRecScratch * mi355_core::kRecWords;
+    HIP_TRY(launch_export_record(c->cw_rec_pos, c->cw_rec, c->cw_rec_bytes, scratch, words, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (words[0] != 0 || words[1] != 0 || words[2] != 8 || words[3] != 0 || scratch[0] != 0 || scratch[1] != 0)
+        return fail(MI355_ERR_STATE, "MI355_PREPARE_EXEC_CWIRE: the warm pass did not give the empty record");
+    c->cw_warm = true;
+    return MI355_OK;
+}
+
+int mi355_exec_cwire(mi355_core *c, const uint8_t *frame_data, uint8_t *show_ready, const char *text, void *h_record,
+                     size_t record_capacity, uint32_t *h_pos, uint32_t *h_escapes, size_t *h_bytes) {
+    if (!h_pos || !h_escapes || !h_bytes) return fail(MI355_ERR_INVALID, "null argument");
+    if (int rc = check_exec_cwire_args(c, frame_data, show_ready, h_record, record_capacity)) return rc;
+    if (c->nslots) return fail(MI355_ERR_STATE, "pipe open: use mi355_pipe_submit_cwire");
+    const int vis = c->cfg.visualizer;
+    if (int rc = use_device(c)) return rc;
+    if (int rc = need_exec_cwire(c)) return rc;
+    hipStream_t s = c->stream;
+    const uint32_t N = c->n;
+    if (int rc = exec_frame(c, frame_data, show_ready, text)) return rc;
+    // the red maps take the count from the device in either form (the indices stay in one_xs)
+    if (vis == MI355_VIS_RED || vis == MI355_VIS_RED_OVERLAP) {
+        HIP_TRY(launch_red_overlap(c->vis, c->one_xs, c->offsets + 1, 0, N, s));
+        HIP_TRY(hipMemcpyAsync(show_ready, c->vis, N, hipMemcpyDeviceToHost, s));
+    }
+    if (int rc = encode_record(c)) return rc;
+    if (record_is_pinned(c, h_record)) {
+        // pinned: the record's size stays on the device, k_export_record stores exactly that many bytes through the mapped
+        // pointer -- one synchronisation
+        uint32_t *const words = c->h_rec + kRecBlocking * mi355_core::kRecWords;
+        HIP_TRY(launch_export_record(c->cw_rec_pos, c->cw_rec, c->cw_rec_bytes, (uint32_t *)h_record, words, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        read_rec_words(words, h_pos, h_escapes, h_bytes);
+        return MI355_OK;
+    }
+    // pageable: the header and the size come back first, then a copy of exactly that many bytes
+    uint32_t *const scratch = c->h_rec + kRecScratch * mi355_core::kRecWords;
+    HIP_TRY(hipMemcpyAsync(scratch, c->cw_rec, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(scratch + 2, c->cw_rec_pos + 1, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint64_t bytes = scratch[2] | (uint64_t)scratch[3] << 32;
+    if (bytes > c->cw_rec_bytes || scratch[0] > N || scratch[1] > scratch[0] || bytes != cwire_record_bytes(scratch[0], scratch[1]))
+        return fail(MI355_ERR_STATE, "mi355_exec_cwire: the encoder left an inconsistent record");
+    HIP_TRY(hipMemcpyAsync(h_record, c->cw_rec, (size_t)bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *h_pos = scratch[0];
+    *h_escapes = scratch[1];
+    *h_bytes = (size_t)bytes;
+    return MI355_OK;
+}
+
+int mi355_pipe_submit_cwire(mi355_core *c, const uint8_t *frame_data, uint8_t *show_ready, const char *text, void *h_record,
+                            size_t record_capacity, int64_t *ticket) {
+    if (!ticket) return fail(MI355_ERR_INVALID, "null argument");
+    if (int rc = check_exec_cwire_args(c, frame_data, show_ready, h_record, record_capacity)) return rc;
+    if (!c->nslots) return fail(MI355_ERR_STATE, "pipe not open");
+    if (int rc = use_device(c)) return rc;
+    // the export kernel stores through h_record, and only a pinned frame crosses PCIe beside the frame before it
+    if (!is_pinned(frame_data) || !record_is_pinned(c, h_record) || (show_ready && !is_pinned(show_ready)))
+        return fail(MI355_ERR_INVALID, "pipe buffers must be pinned host memory (mi355_host_alloc)");
+    if (int rc = need_exec_cwire(c)) return rc;
+    mi355_core::Slot &sl = c->slots[c->next_ticket % c->nslots];
+    if (int rc = pipe_frame(c, frame_data, show_ready, text, sl)) return rc;
+    if (int rc = encode_record(c)) return rc;
+    HIP_TRY(launch_export_record(c->cw_rec_pos, c->cw_rec, c->cw_rec_bytes, (uint32_t *)h_record,
+                                 c->h_rec + (&sl - c->slots) * mi355_core::kRecWords, c->stream));
+    HIP_TRY(hipEventRecord(sl.packed, c->stream));
+    sl.compact = true;
+    sl.ticket = c->next_ticket;
+    *ticket = c->next_ticket++;
+    return MI355_OK;
+}
+
+int mi355_pipe_wait_cwire(mi355_core *c, int64_t ticket, uint32_t *h_pos, uint32_t *h_escapes, size_t *h_bytes) {
+    if (!c || !h_pos || !h_escapes || !h_bytes) return fail(MI355_ERR_INVALID, "null argument");
+    mi355_core::Slot *sl = nullptr;
+    if (int rc = pipe_wait_slot(c, ticket, true, &sl)) return rc;
+    read_rec_words(c->h_rec + (sl - c->slots) * mi355_core::kRecWords, h_pos, h_escapes, h_bytes);
+    sl->ticket = -1;
     return MI355_OK;
 }
 

@@ -135,6 +135,9 @@ hipError_t launch_apply_multi_show(const uint8_t *states, size_t stride, uint32_
                                    int nstreams, int nframes, int t, hipStream_t s);
 hipError_t launch_export(const uint32_t *offsets, const int32_t *xs, const uint8_t *diff, int32_t *h_xs,
                          uint8_t *h_diff, uint32_t *h_count, hipStream_t s);
+// one compact record (rec[0 .. frame_pos[1]), at most rec_bytes) to the mapped h_record, {n, e, bytes low, bytes high} to h_words
+hipError_t launch_export_record(const uint64_t *frame_pos, const uint8_t *rec, uint64_t rec_bytes, uint32_t *h_record,
+                                uint32_t *h_words, hipStream_t s);
 hipError_t launch_merge(const MergeArgs &a, uint32_t *out_offsets, hipStream_t s);
 // compact wire (include/mi355diff.h): the encoder's per-workgroup escape counts live in kCwireSlots words of the core
 // (nframes * cwire_blocks_per_frame(nframes) <= kCwireSlots), so one encode takes at most kCwireSlots frames

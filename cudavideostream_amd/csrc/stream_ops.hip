@@ -259,6 +259,39 @@ hipError_t launch_export(const uint32_t *offsets, const int32_t *xs, const uint8
     return hipGetLastError();
 }
 
+// The same for ONE compact record (mi355_exec_cwire / mi355_pipe_submit_cwire): the record the encoder has just written at
+// rec[0 .. frame_pos[1]) of the core's record buffer goes to the mapped host pointer, its {n, e, bytes low, bytes high} to
+// four pinned words.  The size is read from the device word -- no host round trip -- and clamped to rec_bytes, the
+// size both buffers are known to have (the caller's capacity was checked against it), so that a wrong word could never run
+// past either.  Whole 16-byte stores when the host pointer allows (rec is allocation aligned and padded to 16), dwords
+// otherwise and for the tail; no byte at or past the record's end is written.
+__global__ __launch_bounds__(256) void k_export_record(const uint64_t *frame_pos, const uint32_t *rec, uint64_t rec_bytes,
+                                                       uint32_t *h_record, uint32_t *h_words) {
+    uint64_t bytes = frame_pos[1];
+    if (bytes > rec_bytes) bytes = rec_bytes;
+    const uint64_t dwords = bytes / 4;   // (a record is a whole number of dwords)
+    const uint64_t gid = blockIdx.x * 256u + threadIdx.x, step = (uint64_t)gridDim.x * 256u;
+    if (gid == 0) {
+        h_words[0] = dwords >= 2 ? rec[0] : 0u;
+        h_words[1] = dwords >= 2 ? rec[1] : 0u;
+        h_words[2] = (uint32_t)(4 * dwords);
+        h_words[3] = (uint32_t)((4 * dwords) >> 32);
+    }
+    if (((uintptr_t)h_record & 15u) == 0) {
+        const uint64_t q = dwords / 4;
+        for (uint64_t i = gid; i < q; i += step) ((uint4 *)h_record)[i] = ((const uint4 *)rec)[i];
+        for (uint64_t i = 4 * q + gid; i < dwords; i += step) h_record[i] = rec[i];
+    } else {
+        for (uint64_t i = gid; i < dwords; i += step) h_record[i] = rec[i];
+    }
+}
+
+hipError_t launch_export_record(const uint64_t *frame_pos, const uint8_t *rec, uint64_t rec_bytes, uint32_t *h_record,
+                                uint32_t *h_words, hipStream_t s) {
+    hipLaunchKernelGGL(k_export_record, dim3(256), dim3(256), 0, s, frame_pos, (const uint32_t *)rec, rec_bytes, h_record, h_words);
+    return hipGetLastError();
+}
+
 // ---- merge of row-band streams -------------------------------------------------------------------------
 // Part p (a row band, bands ordered top to bottom) holds its own packed stream of the same T frames:
 // index part_off[p][0..T], entries at xs_all/diff_all[part_base[p] + ...], byte indices relative to

@@ -24,6 +24,7 @@ VIS_NONE, VIS_HEAT, VIS_RED, VIS_RED_OVERLAP, VIS_GRAY, VIS_BINARIZE = range(6)
 OPT_PIPELINE, OPT_MEDIAN_ROWS, OPT_SCAN_EPOCH_LEFT = 1, 6, 7   # MI355_OPT_* (ids 2..5 are retired and refused)
 FLAG_OWN_QUEUES = 1   # MI355_FLAG_*
 PREPARE_BATCHES, PREPARE_GRAY_CHAIN, PREPARE_RED_CLEAR, PREPARE_CONV_KXK, PREPARE_EXEC, PREPARE_ALL = 1, 2, 4, 8, 16, 31   # MI355_PREPARE_*
+PREPARE_EXEC_CWIRE = 32   # (not part of PREPARE_ALL)
 
 
 class Config(C.Structure):
@@ -128,6 +129,12 @@ SYMBOLS = {
                                     C.POINTER(C.c_int64)]),
     "mi355_pipe_wait": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_uint32)]),
     "mi355_pipe_close": (C.c_int, [C.c_void_p]),
+    "mi355_exec_cwire": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t,
+                                   C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]),
+    "mi355_pipe_submit_cwire": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t,
+                                          C.POINTER(C.c_int64)]),
+    "mi355_pipe_wait_cwire": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_size_t)]),
     "mi355_host_alloc": (C.c_int, [C.POINTER(C.c_void_p), C.c_size_t]),
     "mi355_host_free": (C.c_int, [C.c_void_p]),
     "mi355_dev_alloc": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]),

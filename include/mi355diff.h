@@ -86,7 +86,8 @@ typedef struct mi355_config {
  *      + mi355_apply_multi_batch, mi355_apply_multi_wire_batch, mi355_apply_multi_cwire_batch (additions only);
  *      + mi355_diff_multi_stream_batch, mi355_diff_multi_stream_wire_batch, mi355_diff_multi_stream_cwire_batch (additions
  *      only); + mi355_apply_multi_stream_batch, mi355_apply_multi_stream_wire_batch, mi355_apply_multi_stream_cwire_batch
- *      (additions only); + mi355_cwire_coalesce_batch, mi355_cwire_coalesce_cwire_batch (additions only) */
+ *      (additions only); + mi355_cwire_coalesce_batch, mi355_cwire_coalesce_cwire_batch (additions only);
+ *      + mi355_exec_cwire, mi355_pipe_submit_cwire, mi355_pipe_wait_cwire, MI355_PREPARE_EXEC_CWIRE (additions only) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -114,15 +115,21 @@ size_t mi355_workspace_bytes(const mi355_core *core);
  *                              the state and the caller's buffers stay as they are -- so that the first real frame does
  *                              not pay for the first use of each kernel (measured: the first exec_core of a fresh core
  *                              1.4 ms, the later ones 0.16).  The C++ drop-in's constructor calls it.
+ *   MI355_PREPARE_EXEC_CWIRE   the record buffer (mi355_cwire_bytes_max(N, 1) bytes) and the pinned result words of
+ *                              mi355_exec_cwire / mi355_pipe_submit_cwire, and one pass of their encode and export kernels on
+ *                              an empty frame.  Not part of MI355_PREPARE_ALL: only a caller of the compact per-frame form
+ *                              wants it, and asks for it by name.
  * mi355_create already makes the one a per-frame server needs (MI355_VIS_BINARIZE's gray bytes).  Blocking; idempotent;
  * mi355_workspace_bytes grows by what was made.  After mi355_prepare(core, MI355_PREPARE_ALL) no entry point of the core
- * allocates (mi355_pipe_open and mi355_set_glyphs, which say so, excepted). */
+ * allocates (mi355_pipe_open and mi355_set_glyphs, which say so, excepted -- and the first mi355_exec_cwire /
+ * mi355_pipe_submit_cwire, unless MI355_PREPARE_EXEC_CWIRE, which MI355_PREPARE_ALL does not contain, was asked for too). */
 #define MI355_PREPARE_BATCHES 1u
 #define MI355_PREPARE_GRAY_CHAIN 2u
 #define MI355_PREPARE_RED_CLEAR 4u
 #define MI355_PREPARE_CONV_KXK 8u
 #define MI355_PREPARE_EXEC 16u
 #define MI355_PREPARE_ALL 31u
+#define MI355_PREPARE_EXEC_CWIRE 32u
 int mi355_prepare(mi355_core *core, unsigned what);
 
 /* Streams.  A core starts on a stream of its own, created hipStreamNonBlocking: it is NOT ordered against the
@@ -655,6 +662,37 @@ int mi355_pipe_submit(mi355_core *core, uint8_t *frame_data, uint8_t *show_ready
                       int32_t *h_xs, int64_t *ticket);
 int mi355_pipe_wait(mi355_core *core, int64_t ticket, uint32_t *h_pos);
 int mi355_pipe_close(mi355_core *core);
+
+/* ---- compact form of the per-frame entry points: the frame's changes as ONE compact record in host memory -----------
+ * Each frame gets exactly what mi355_exec / mi355_pipe_submit do to it, in the same order, on the same state: upload, noise
+ * filter when configured, text overlay, visualiser into show_ready (the red maps included), diff with negative feedback.
+ * The packed entries do not go to h_xs / frame_data: h_record receives the frame's compact record, byte for byte what
+ * mi355_cwire_encode_batch writes for those entries (header {n, e} included, pad bytes zero), *h_bytes =
+ * mi355_cwire_frame_bytes(n, e) bytes long, ready for one write(); *h_pos = n, *h_escapes = e.
+ *   - frame_data is only read (the one difference from mi355_exec); no byte of h_record at or past *h_bytes is written;
+ *     nothing but h_record and show_ready is written on the host.
+ *   - Refused before anything is launched (MI355_ERR_INVALID, or MI355_ERR_STATE for the open / closed pipe): whatever
+ *     mi355_exec refuses; a null h_record, h_pos, h_escapes, h_bytes or ticket; an h_record that is not 4-byte aligned;
+ *     record_capacity < mi355_cwire_bytes_max(N, 1) -- a record that did not fit would lose a frame whose state has already
+ *     advanced, so the worst case is demanded up front; mi355_exec_cwire while a pipe is open, the submit / wait forms while
+ *     none is; pageable buffers handed to mi355_pipe_submit_cwire.
+ *   - mi355_exec_cwire takes pinned or pageable buffers, as mi355_exec does.  A pinned h_record is written by a device
+ *     kernel through the mapped pointer (the size never visits the host; whole 16-byte stores when h_record is 16-byte
+ *     aligned); for a pageable one the size is read back and exactly that many bytes are copied.
+ *   - Plain and compact submits may alternate on one open pipe, mi355_exec and mi355_exec_cwire on one core: they share the
+ *     state and the ticket counter.  mi355_pipe_wait on a compact ticket is valid and returns n; mi355_pipe_wait_cwire on a
+ *     plain ticket is MI355_ERR_STATE and leaves the ticket waitable.  Ring overrun and "already waited" as above.
+ *   - The first compact call of a core allocates (a device record buffer of mi355_cwire_bytes_max(N, 1) bytes, counted by
+ *     mi355_workspace_bytes, and a few pinned words) and synchronises once, unless
+ *     mi355_prepare(core, MI355_PREPARE_EXEC_CWIRE) did.  mi355_pipe_open allocates nothing for it.
+ * On the device the frame is packed as for mi355_exec, then encoded (three launches) and exported (one).  Speed of
+ * mi355_pipe_submit_cwire against mi355_pipe_submit on the same frames: not yet measured (tools/bench_cwire.py host
+ * is the run, and writes profiles/host_cwire.json). */
+int mi355_exec_cwire(mi355_core *core, const uint8_t *frame_data, uint8_t *show_ready, const char *text, void *h_record,
+                     size_t record_capacity, uint32_t *h_pos, uint32_t *h_escapes, size_t *h_bytes);
+int mi355_pipe_submit_cwire(mi355_core *core, const uint8_t *frame_data, uint8_t *show_ready, const char *text, void *h_record,
+                            size_t record_capacity, int64_t *ticket);
+int mi355_pipe_wait_cwire(mi355_core *core, int64_t ticket, uint32_t *h_pos, uint32_t *h_escapes, size_t *h_bytes);
 
 /* ---- pinned host memory: CUDACore::alloc_arrays (kernels.cu:531-536) ---------------------------- */
 int mi355_host_alloc(void **out, size_t bytes);

@@ -34,15 +34,25 @@
 // them with one mi355_apply_multi_cwire_batch.  After every burst each camera's state at the receiver must equal the frame of
 // a host client (mi355_cwire_apply_host) that applied all K original records, and the sender's state.  The line also says how
 // many bytes the relay received and how many it forwarded.
+// --compact --per-frame: the per-frame server, one host frame per call and no device pointer in sight.  The sender feeds
+// host frames through mi355_pipe_submit_cwire, four in flight, and writes each frame's record to the pipe with ONE write()
+// from the pinned buffer it arrived in; the receiver -- a thread with no core -- reads header and body, applies the record
+// with mi355_cwire_apply_host and compares its frame, frame by frame, with that of a host client of the plain path
+// (mi355_exec on a second core: frame[xs[i]] += diff[i], client/opencv.cpp:64-66).
 //
 //   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B]
-//                   [--compact [--direct] [--gpu-client] [--multi S [--burst K [--burst-client | --coalesce]]]]
+//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--burst K [--burst-client | --coalesce]]]]
 //   exit status 0 = all checks passed
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <condition_variable>
+#include <csignal>
+#include <deque>
+#include <mutex>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include <unistd.h>
@@ -549,21 +559,183 @@ static int run_multi_burst_coalesce(int w, int h, int T, int S, int K) {
     return 0;
 }
 
+// --compact --per-frame (see the head of the file)
+namespace {
+struct Expected {   // the plain path's client frames, in order, from the sender to the receiver thread
+    std::mutex m;
+    std::condition_variable cv;
+    std::deque<std::vector<uint8_t> > q;
+    void push(const std::vector<uint8_t> &f) {
+        { std::lock_guard<std::mutex> l(m); q.push_back(f); }
+        cv.notify_one();
+    }
+    std::vector<uint8_t> pop() {
+        std::unique_lock<std::mutex> l(m);
+        cv.wait(l, [this] { return !q.empty(); });
+        std::vector<uint8_t> f = std::move(q.front());
+        q.pop_front();
+        return f;
+    }
+};
+struct Receiver {
+    int fd, frames;
+    size_t n;
+    Expected *expected;
+    int equal = 0;
+    size_t bytes = 0;
+    std::string error;
+    void run() {
+        receive();
+        if (!error.empty()) close(fd);   // the sender's next write then fails instead of waiting for a reader that has left
+    }
+    void receive() {   // opencv.cpp:38-66 over the compact stream: the base frame, then header + body per frame
+        std::vector<uint8_t> frame(n), rec;
+        if (!read_all(fd, frame.data(), n)) { error = "base frame: short read"; return; }
+        for (int t = 0; t < frames; t++) {
+            uint32_t hdr[2];
+            if (!read_all(fd, hdr, 8)) { error = "record header: short read"; return; }
+            const size_t len = mi355_cwire_frame_bytes(hdr[0], hdr[1]);
+            rec.resize(len);
+            memcpy(rec.data(), hdr, 8);
+            if (!read_all(fd, rec.data() + 8, len - 8)) { error = "record body: short read"; return; }
+            size_t used = 0;
+            if (mi355_cwire_apply_host(frame.data(), n, rec.data(), len, 1, &used) != MI355_OK || used != len) {
+                error = std::string("mi355_cwire_apply_host: ") + mi355_last_error();
+                return;
+            }
+            bytes += len;
+            const std::vector<uint8_t> want = expected->pop();
+            if (want.size() != n || memcmp(want.data(), frame.data(), n) != 0) {
+                error = "frame " + std::to_string(t) + ": compact client frame != plain client frame";
+                return;
+            }
+            equal++;
+        }
+    }
+};
+}  // namespace
+
+static int run_per_frame(int w, int h, int T) {
+    const size_t n = (size_t)3 * w * h;
+    const int depth = 4;
+    mi355_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.width = w; cfg.height = h; cfg.threshold = 20; cfg.max_batch = 1; cfg.device = -1;
+    mi355_core *server = nullptr, *plain = nullptr;
+    OK(mi355_create(&cfg, &server));
+    OK(mi355_create(&cfg, &plain));
+    std::vector<uint8_t> base(n), frame(n), p_frame(n), s_state(n);
+    for (size_t i = 0; i < n; i++) base[i] = (uint8_t)(40 + (i * 7) % 150);
+    OK(mi355_set_state(server, base.data()));
+    OK(mi355_set_state(plain, base.data()));
+    OK(mi355_prepare(server, MI355_PREPARE_EXEC_CWIRE));
+    p_frame = base;
+    const size_t cap = mi355_cwire_bytes_max(n, 1);
+    void *h_frame[depth], *h_rec[depth], *p_in = nullptr, *p_xs = nullptr;
+    for (int i = 0; i < depth; i++) {
+        OK(mi355_host_alloc(&h_frame[i], n));
+        OK(mi355_host_alloc(&h_rec[i], cap));
+    }
+    OK(mi355_host_alloc(&p_in, n));
+    OK(mi355_host_alloc(&p_xs, n * sizeof(int32_t)));
+    int fds[2];
+    if (pipe(fds) != 0) return 1;
+    OK(mi355_pipe_open(server, depth));
+    // (from here to receiver.join() an error ends the loop, not the function: the thread is joined first)
+    Expected expected;
+    Receiver rx;
+    rx.fd = fds[0]; rx.frames = T; rx.n = n; rx.expected = &expected;
+    signal(SIGPIPE, SIG_IGN);   // (a write to a pipe the receiver has closed returns an error)
+    std::thread receiver(&Receiver::run, &rx);
+    bool ok = true;
+    auto send = [&](const void *p, size_t len) {   // ONE write per record; the loop only serves a short write
+        const uint8_t *b = (const uint8_t *)p;
+        while (len) {
+            const ssize_t k = write(fds[1], b, len);
+            if (k <= 0) return false;
+            b += k;
+            len -= (size_t)k;
+        }
+        return true;
+    };
+    ok = send(base.data(), n);   // threads.cpp:220
+    int64_t tickets[depth];
+    size_t changed = 0, sent_bytes = 0;
+    int rc = 0;
+    auto finish = [&](int t) -> int {   // the sender thread's part: wait for frame t, one write
+        uint32_t pos = 0, esc = 0;
+        size_t len = 0;
+        OK(mi355_pipe_wait_cwire(server, tickets[t % depth], &pos, &esc, &len));
+        if (len != mi355_cwire_frame_bytes(pos, esc) || len > cap) { fprintf(stderr, "frame %d: record size\n", t); return 1; }
+        changed += pos;
+        sent_bytes += len;
+        if (!send(h_rec[t % depth], len)) { fprintf(stderr, "write failed\n"); return 1; }
+        return 0;
+    };
+    for (int t = 0; t < T && ok && !rc; t++) {
+        if (t >= depth) rc = finish(t - depth);
+        if (rc) break;
+        make_frame(frame, base, w, h, t);
+        // the plain path beside it: mi355_exec on its own core, and its host client
+        memcpy(p_in, frame.data(), n);
+        uint32_t pos = 0;
+        if (mi355_exec(plain, (uint8_t *)p_in, nullptr, nullptr, &pos, (int32_t *)p_xs) != MI355_OK) {
+            fprintf(stderr, "mi355_exec failed: %s\n", mi355_last_error());
+            rc = 1;
+            break;
+        }
+        for (uint32_t i = 0; i < pos; i++) p_frame[((const int32_t *)p_xs)[i]] += ((const uint8_t *)p_in)[i];
+        expected.push(p_frame);
+        // the elaboration loop: one host frame in, a ticket out
+        memcpy(h_frame[t % depth], frame.data(), n);
+        if (mi355_pipe_submit_cwire(server, (const uint8_t *)h_frame[t % depth], nullptr, nullptr, h_rec[t % depth], cap,
+                                    &tickets[t % depth]) != MI355_OK) {
+            fprintf(stderr, "mi355_pipe_submit_cwire failed: %s\n", mi355_last_error());
+            rc = 1;
+            break;
+        }
+    }
+    for (int t = T > depth ? T - depth : 0; t < T && ok && !rc; t++) rc = finish(t);
+    close(fds[1]);   // (a receiver that still waits for bytes sees the end of the stream)
+    if (rc || !ok)
+        for (int t = 0; t < T; t++) expected.push(std::vector<uint8_t>());   // ... and one that waits for a frame gets a wrong one
+    receiver.join();
+    if (rc || !ok) return 1;
+    if (!rx.error.empty()) { fprintf(stderr, "%s\n", rx.error.c_str()); return 1; }
+    OK(mi355_pipe_close(server));
+    OK(mi355_get_state(server, s_state.data()));
+    if (memcmp(s_state.data(), p_frame.data(), n) != 0) { fprintf(stderr, "server state != plain client frame\n"); return 1; }
+    for (int i = 0; i < depth; i++) {
+        OK(mi355_host_free(h_frame[i]));
+        OK(mi355_host_free(h_rec[i]));
+    }
+    OK(mi355_host_free(p_in));
+    OK(mi355_host_free(p_xs));
+    mi355_destroy(server);
+    mi355_destroy(plain);
+    printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"per_frame\": true, \"depth\": %d, \"width\": %d, \"height\": %d, "
+           "\"frames\": %d, \"frames_equal\": %d, \"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, "
+           "\"raw_bytes\": %zu}\n",
+           depth, w, h, T, rx.equal, changed, sent_bytes, mi355_wire_bytes(T, changed), (size_t)T * n);
+    return rx.equal == T ? 0 : 1;
+}
+
 int main(int argc, char **argv) {
     int w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0;
-    bool compact = false, direct = false, gpu_client = false, burst_client = false, coalesce = false;
+    bool compact = false, direct = false, gpu_client = false, burst_client = false, coalesce = false, per_frame = false;
     for (int i = 1; i < argc; i++) {
         if (std::string(argv[i]) == "--compact") compact = true;
         if (std::string(argv[i]) == "--direct") direct = true;
         if (std::string(argv[i]) == "--gpu-client") gpu_client = true;
         if (std::string(argv[i]) == "--burst-client") burst_client = true;
         if (std::string(argv[i]) == "--coalesce") coalesce = true;
+        if (std::string(argv[i]) == "--per-frame") per_frame = true;
     }
     if (direct && !compact) { fprintf(stderr, "--direct needs --compact\n"); return 2; }
     if (gpu_client && !compact) { fprintf(stderr, "--gpu-client needs --compact\n"); return 2; }
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string k = argv[i];
-        if (k == "--compact" || k == "--direct" || k == "--gpu-client" || k == "--burst-client" || k == "--coalesce") { i--; continue; }
+        if (k == "--compact" || k == "--direct" || k == "--gpu-client" || k == "--burst-client" || k == "--coalesce" || k == "--per-frame") { i--; continue; }
         const int v = atoi(argv[i + 1]);
         if (k == "--width") w = v; else if (k == "--height") h = v;
         else if (k == "--frames") T = v; else if (k == "--batch") B = v;
@@ -575,6 +747,10 @@ int main(int argc, char **argv) {
     if (coalesce && (!compact || !multi || !burst || burst_client)) {
         fprintf(stderr, "--coalesce needs --compact --multi S --burst K, without --burst-client\n");
         return 2;
+    }
+    if (per_frame) {
+        if (!compact || direct || gpu_client || multi) { fprintf(stderr, "--per-frame needs --compact alone\n"); return 2; }
+        return run_per_frame(w, h, T);
     }
     if (multi) {
         if (!compact || direct || gpu_client || multi < 0) { fprintf(stderr, "--multi S needs --compact alone and S >= 1\n"); return 2; }
