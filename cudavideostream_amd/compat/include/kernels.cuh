@@ -88,6 +88,14 @@ public:
     // apply_multi_stream; nstreams*nframes <= MI355_MAX_BATCH.
     void coalesce_multi_stream(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, int nstreams, int nframes,
                                void *d_offsets, void *d_frame_pos, void *d_cwire_out, size_t capacity_bytes);
+    // The sender's rate control behind exec_multi's compact form (include/mi355diff.h, mi355_cwire_budget_cwire_batch): record s
+    // of the tick just diffed keeps at most budgets[s] entries (mi355_cwire_budget_entries turns a byte budget into one;
+    // UINT32_MAX: no limit), the largest changes first: the thinned records go to d_cwire_out + d_frame_pos[s], the threshold that
+    // was needed to d_thresholds[s] (uint32[nstreams]), and d_states + s*stride is taken back to the previous value where an entry
+    // was dropped, so the change stays pending for a later tick.  All but counts / escapes / budgets in DEVICE memory.  Blocking.
+    void budget_multi(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, void *d_states, size_t stride,
+                      int nstreams, const uint32_t *budgets, void *d_thresholds, void *d_offsets, void *d_frame_pos,
+                      void *d_cwire_out, size_t capacity_bytes);
 };
 
 static_assert(sizeof(CUDACore) == 160, "must match the reference's object size (LP64)");

@@ -153,6 +153,14 @@ void CUDACore::coalesce_multi_stream(const void *d_cwire, const uint32_t *counts
     MI355_CHECK(mi355_synchronize(core_));
 }
 
+void CUDACore::budget_multi(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, void *d_states, size_t stride,
+                            int nstreams, const uint32_t *budgets, void *d_thresholds, void *d_offsets, void *d_frame_pos,
+                            void *d_cwire_out, size_t capacity_bytes) {
+    MI355_CHECK(mi355_cwire_budget_cwire_batch(core_, d_cwire, counts, escapes, d_states, stride, nstreams, budgets, d_thresholds,
+                                               d_offsets, d_frame_pos, d_cwire_out, capacity_bytes));
+    MI355_CHECK(mi355_synchronize(core_));
+}
+
 size_t CUDACore::chunkt_size() { return 32; }  // sizeof(long4), kernels.cu:27,527-529
 
 void CUDACore::alloc_arrays(uint8_t **h_frame, uint8_t **n_frame, uint8_t **o_frame, int **h_xs, int r,

@@ -430,6 +430,24 @@ class CUDACore:
                                                             int(nstreams), int(nframes), _ptr(d_offsets), _ptr(d_frame_pos),
                                                             _ptr(d_cwire_out), int(capacity_bytes)))
 
+    # ... and the sender's rate control: the records of one tick held to an entry budget each
+    def cwire_budget_cwire_batch(self, d_cwire, counts, escapes, d_states, nstreams, budgets, d_thresholds, d_offsets,
+                                 d_frame_pos, d_cwire_out, capacity_bytes, stride=None):
+        """The records diff_multi_cwire_batch just made (headers counts / escapes), thinned: stream s keeps at most budgets[s]
+        entries (0xFFFFFFFF: no limit) -- those above the least threshold T_s >= the core's that allows it, written to
+        d_thresholds[s] (uint32[nstreams]).  The thinned record s goes to d_cwire_out + d_frame_pos[s], and d_states[s] takes the
+        previous value at every dropped entry: records and states are those of a tick diffed at T_s."""
+        self._hold(d_cwire, d_states, d_thresholds, d_offsets, d_frame_pos, d_cwire_out)
+        stride = self.total if stride is None else stride
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+        budgets = np.ascontiguousarray(budgets, dtype=np.uint32)
+        assert counts.size >= nstreams and escapes.size >= nstreams and budgets.size >= nstreams
+        _l.check(self._lib.mi355_cwire_budget_cwire_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
+                                                          _ptr(d_states), int(stride), int(nstreams), budgets.ctypes.data,
+                                                          _ptr(d_thresholds), _ptr(d_offsets), _ptr(d_frame_pos),
+                                                          _ptr(d_cwire_out), int(capacity_bytes)))
+
     def wire_bytes(self, nframes, entries):
         return self._lib.mi355_wire_bytes(nframes, entries)
 
@@ -596,6 +614,12 @@ def cwire_frame_bytes(n, e):
 def cwire_bytes_max(frame_bytes, nframes):
     """Largest compact stream of nframes frames of frame_bytes bytes: nframes * (8 + 2 * pad4(frame_bytes))."""
     return _l.load().mi355_cwire_bytes_max(int(frame_bytes), int(nframes))
+
+
+def cwire_budget_entries(frame_bytes, record_bytes):
+    """The most entries a record of a frame of frame_bytes bytes may hold so that it fits record_bytes whatever its escapes:
+    a sender's per-socket byte budget as a budget of cwire_budget_cwire_batch."""
+    return _l.load().mi355_cwire_budget_entries(int(frame_bytes), int(record_bytes))
 
 
 def cwire_apply_host(state, buf, nframes):

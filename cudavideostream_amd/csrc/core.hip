@@ -91,6 +91,7 @@ struct mi355_core {
     CwaFrame *cwa_ftab = nullptr;   // mi355_apply_cwire_batch (stream_ops.hip): [T] frame headers of a slice,
     uint4 *cwa_chunk = nullptr;     // [T * cwa_chunks(N)] chunk facts,
     uint4 *cwa_dir = nullptr;       // [T][cwa_tiles(N)] directory words
+    uint32_t *cwb_hist = nullptr;   // mi355_cwire_budget_cwire_batch: [T][kCwbWords] bins of |cur - prev|, budget and threshold per stream
     uint8_t *gray1 = nullptr;      // fused gray+binarize chain: one gray byte per pixel of a batch, made on first use
     size_t gray1_stride = 0;
     float *k9 = nullptr;
@@ -641,6 +642,7 @@ int mi355_create(const mi355_config *cfg, mi355_core **out) {
     if (!rc) rc = dev_alloc(c, &c->cwa_ftab, T);
     if (!rc) rc = dev_alloc(c, &c->cwa_chunk, T * cwa_chunks(c->n));
     if (!rc) rc = dev_alloc(c, &c->cwa_dir, T * cwa_tiles(c->n));
+    if (!rc) rc = dev_alloc(c, &c->cwb_hist, T * kCwbWords);
     if (!rc) rc = dev_alloc(c, &c->one_xs, N + 4);
     if (!rc) rc = dev_alloc(c, &c->one_diff, N + 16);
     if (!rc) rc = dev_alloc(c, &c->hist, 256 * T);
@@ -687,7 +689,7 @@ void mi355_destroy(mi355_core *c) {
     }
     void *ptrs[] = {c->state, c->in, c->aux, c->vis, c->rec, c->codes, c->meta, c->groff, c->totals, c->offsets, c->one_xs, c->one_diff, c->hist, c->thr, c->k9,
                     c->lut, c->glyphs, c->kxk, c->gray1, c->red_bounds, c->cw_cnt, c->cw_items, c->cw_esc,
-                    c->cwa_ftab, c->cwa_chunk, c->cwa_dir, c->cw_rec, c->cw_rec_pos};
+                    c->cwa_ftab, c->cwa_chunk, c->cwa_dir, c->cwb_hist, c->cw_rec, c->cw_rec_pos};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->h_count) (void)hipHostFree(c->h_count);
     if (c->h_rec) (void)hipHostFree(c->h_rec);
@@ -1448,6 +1450,88 @@ int mi355_cwire_coalesce_cwire_batch(mi355_core *c, const void *d_cwire, const u
                                      size_t capacity_bytes) {
     return coalesce(c, d_cwire, h_counts, h_escapes, nstreams, nframes, true, d_offsets, d_frame_pos, d_cwire_out, nullptr, nullptr,
                     capacity_bytes);
+}
+
+// ---- mi355_cwire_budget_cwire_batch: the records of one tick held to an entry budget each ------------------------------------
+size_t mi355_cwire_budget_entries(size_t frame_bytes, size_t record_bytes) {
+    // the largest n <= frame_bytes whose worst record (e = min(n, frame_bytes / 256) escapes) fits; the size rises with n
+    const uint64_t most_e = frame_bytes / 256;
+    uint64_t lo = 0, hi = frame_bytes;   // lo fits (or nothing does), hi + 1 does not
+    if (record_bytes < 8) return 0;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (cwire_record_bytes(mid, mid < most_e ? mid : most_e) <= (uint64_t)record_bytes) lo = mid;
+        else hi = mid - 1;
+    }
+    return (size_t)lo;
+}
+
+int mi355_cwire_budget_cwire_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
+                                   void *d_states, size_t stride_bytes, int nstreams, const uint32_t *h_budget, void *d_thresholds,
+                                   void *d_offsets, void *d_frame_pos, void *d_cwire_out, size_t capacity_bytes) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nstreams < 0 || nstreams > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams outside [0, max_batch]");
+    if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_cwire_out & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_thresholds & 3u))
+        return fail(MI355_ERR_INVALID, "d_cwire, d_cwire_out, d_offsets and d_thresholds must be 4-byte aligned");
+    if ((uintptr_t)d_frame_pos & 7u) return fail(MI355_ERR_INVALID, "d_frame_pos must be 8-byte aligned");
+    if (nstreams == 0) {   // offsets[0] = 0 and frame_pos[0] = 0 and nothing else
+        if (!d_offsets && !d_frame_pos) return MI355_OK;
+        if (int rc = use_device(c)) return rc;
+        if (d_offsets) HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(uint32_t), c->stream));
+        if (d_frame_pos) HIP_TRY(hipMemsetAsync(d_frame_pos, 0, sizeof(uint64_t), c->stream));
+        return MI355_OK;
+    }
+    if (!d_cwire || !h_counts || !h_escapes || !d_states || !h_budget) return fail(MI355_ERR_INVALID, "null input pointer");
+    if (!d_thresholds || !d_offsets || !d_frame_pos || !d_cwire_out) return fail(MI355_ERR_INVALID, "null output pointer");
+    if (stride_bytes < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
+    CwireHeaders hdr{h_counts, h_escapes, nstreams};
+    if (int rc = hdr.check(true, c->n)) return rc;
+    std::vector<CwaFrame> fr((size_t)nstreams);   // nstreams <= max_batch: the scratch of the one-stream client holds them
+    uint32_t cbase = 0;
+    for (int s = 0; s < nstreams; s++) {
+        const CwireHeaders::Frame f = hdr.next();
+        fr[s] = CwaFrame{f.pos, f.n, f.e, cbase, cwa_chunks(f.n)};
+        cbase += fr[s].nc;
+    }
+    const CoalesceRegion out[] = {
+        {d_offsets, ((uint64_t)nstreams + 1) * sizeof(uint32_t), "d_offsets"},
+        {d_thresholds, (uint64_t)nstreams * sizeof(uint32_t), "d_thresholds"},
+        {d_frame_pos, ((uint64_t)nstreams + 1) * sizeof(uint64_t), "d_frame_pos"},
+        {d_cwire_out, capacity_bytes, "d_cwire_out"},
+    };
+    const uintptr_t in = (uintptr_t)d_cwire, st = (uintptr_t)d_states;
+    const uintptr_t span = (uintptr_t)(nstreams - 1) * stride_bytes + c->n;
+    if (in < st + span && st < in + (uintptr_t)hdr.pos) return fail(MI355_ERR_INVALID, "the states overlap the input stream");
+    for (const CoalesceRegion &r : out) {
+        const uintptr_t o = (uintptr_t)r.p;
+        char msg[96];
+        if (in < o + (uintptr_t)r.bytes && o < in + (uintptr_t)hdr.pos) {
+            snprintf(msg, sizeof msg, "%s overlaps the input stream", r.what);
+            return fail(MI355_ERR_INVALID, msg);
+        }
+        if (st < o + (uintptr_t)r.bytes && o < st + span) {
+            snprintf(msg, sizeof msg, "%s overlaps the states", r.what);
+            return fail(MI355_ERR_INVALID, msg);
+        }
+    }
+    if (int rc = use_device(c)) return rc;
+    CwaArgs a{};
+    a.cwire = (const uint8_t *)d_cwire;
+    a.ftab = c->cwa_ftab;
+    a.chunk = c->cwa_chunk;   // chunk facts for the directory, then one fact word per (stream, tile)
+    a.dir = c->cwa_dir;
+    a.state = (uint8_t *)d_states;
+    a.stride = stride_bytes;
+    a.n = c->n;
+    a.ntiles = cwa_tiles(c->n);
+    CwcOut o{};
+    o.offsets = (uint32_t *)d_offsets;
+    o.frame_pos = (uint64_t *)d_frame_pos;
+    o.cwire = (uint8_t *)d_cwire_out;
+    o.capacity = capacity_bytes;
+    HIP_TRY(launch_cwire_budget(a, fr.data(), nstreams, h_budget, (uint32_t)c->cfg.threshold, c->cwb_hist, (uint32_t *)d_thresholds, o,
+                                c->stream));
+    return MI355_OK;
 }
 
 // client/opencv.cpp:50-66 on the compact stream, on the host.  A frame is validated whole before any byte of the state

@@ -209,6 +209,18 @@ struct CwcOut {
 };
 hipError_t launch_cwire_coalesce(const CwaArgs &a, const CwaFrame *records, int nstreams, int nframes, const CwcOut &o, bool cwire,
                                  hipStream_t s);
+// mi355_cwire_budget_cwire_batch: record s thinned to budget[s] entries (host array) at the least threshold >= thr0 that allows it,
+// a.state + s*a.stride reverted at the dropped entries; hist: kCwbWords words per stream (scratch of the core), thresholds and o:
+// the caller's.  a.out unused, a.chunk doubles as the facts as above.
+constexpr int kCwbInitStreams = 128;                         // budgets per k_cwb_init launch (kernel arguments)
+constexpr uint32_t kCwbBudget = 256, kCwbThr = 257, kCwbWords = 258;   // a stream's row: 256 bins of |cur - prev|, its budget, its T
+struct CwbInitArgs {
+    int32_t first;
+    uint32_t thr0;
+    uint32_t budget[kCwbInitStreams];
+};
+hipError_t launch_cwire_budget(const CwaArgs &a, const CwaFrame *records, int nstreams, const uint32_t *budget, uint32_t thr0,
+                               uint32_t *hist, uint32_t *thresholds, const CwcOut &o, hipStream_t s);
 
 // filters.hip -- every per-frame kernel takes a FrameBatch: frame f lives at base + f*stride
 struct FrameBatch {

@@ -12,7 +12,9 @@
 //                           one record per stream, to the caller's states (mi355_apply_multi_cwire_batch), or a burst of
 //                           records per stream, with the frames in between (mi355_apply_multi_stream_cwire_batch);
 //   k_cwc_*               : a burst of compact records per stream summed into ONE record / segment per stream, from the records
-//                           alone (mi355_cwire_coalesce_batch / _cwire_batch).
+//                           alone (mi355_cwire_coalesce_batch / _cwire_batch);
+//   k_cwb_*               : one record per stream thinned to an entry budget, the caller's states reverted where entries are
+//                           dropped (mi355_cwire_budget_cwire_batch).
 //
 // The first two are index-driven byte scatter/copy: HBM-latency work with 5 bytes of traffic per entry, no
 // arithmetic worth naming.
@@ -1009,18 +1011,8 @@ __device__ __forceinline__ uint32_t cwc_end_before(uint64_t m, uint64_t lanes, i
     return below ? end : 0u;
 }
 
-__global__ __launch_bounds__(64) void k_cwc_sum(const CwaArgs a, int nframes) {
-    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
-    uint8_t *s = (uint8_t *)s_q;
-    const int lane = threadIdx.x;
-    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
-    const uint32_t lo = tile * kCwaTile;
-    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
-    uint4 *fact = a.chunk + (size_t)st * a.ntiles + tile;
-    if (!cwc_sum_tile(s, a, nframes, st, tile, lo, lo + len, lane)) {
-        if (lane == 0) *fact = make_uint4(0u, 0u, 0u, 0u);
-        return;
-    }
+// The four facts of the tile in LDS (s[0] is byte lo): {nonzero bytes, index of the first, index of the last, gaps >= 255 inside}
+__device__ __forceinline__ uint4 cwc_tile_facts(const uint8_t *s, uint32_t lo, int lane) {
     const uint64_t m = cwc_lane_mask(s, lane);
     const uint64_t lanes = __ballot(m != 0);
     const uint32_t count = cwa_wave_sum((uint32_t)__popcll(m));
@@ -1036,7 +1028,23 @@ __global__ __launch_bounds__(64) void k_cwc_sum(const CwaArgs a, int nframes) {
         first = lo + (uint32_t)__shfl((int)my_first, l0, 64);
         last = lo + (uint32_t)__shfl((int)my_last, l1, 64);
     }
-    if (lane == 0) *fact = make_uint4(count, first, last, gaps);
+    return make_uint4(count, first, last, gaps);
+}
+
+__global__ __launch_bounds__(64) void k_cwc_sum(const CwaArgs a, int nframes) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
+    uint8_t *s = (uint8_t *)s_q;
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    uint4 *fact = a.chunk + (size_t)st * a.ntiles + tile;
+    if (!cwc_sum_tile(s, a, nframes, st, tile, lo, lo + len, lane)) {
+        if (lane == 0) *fact = make_uint4(0u, 0u, 0u, 0u);
+        return;
+    }
+    const uint4 f = cwc_tile_facts(s, lo, lane);
+    if (lane == 0) *fact = f;
 }
 
 // carry = max(carry, every value); returns the max of carry and the values of the threads below this one.  One barrier
@@ -1145,27 +1153,12 @@ __device__ __forceinline__ void cwc_store_bytes(uint8_t *g, const uint8_t *s, ui
     if ((uint32_t)lane < cnt - tail) __builtin_nontemporal_store(s[sh + tail + lane], g + tail + lane);
 }
 
+// The entries of the tile in LDS (s[0] is byte lo; fact: its scanned word {nonzero bytes, entries before, escapes before, end
+// before}) to their place in stream st's record {n, e} at fp0 (compact form) or segment at `seg` (arrays form).  s_code / s_diff:
+// kCwaTile + 8 bytes of LDS each (s_code unused in the arrays form).  One wave.
 template <bool CWIRE>
-__global__ __launch_bounds__(64) void k_cwc_emit(const CwaArgs a, const CwcOut o, int nframes) {
-    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
-    __shared__ uint32_t s_code32[CWIRE ? kCwaTile / 4 + 2 : 1], s_diff32[kCwaTile / 4 + 2];
-    uint8_t *s = (uint8_t *)s_q, *s_code = (uint8_t *)s_code32, *s_diff = (uint8_t *)s_diff32;
-    const int lane = threadIdx.x;
-    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
-    const uint4 fact = a.chunk[(size_t)st * a.ntiles + tile];   // {nonzero bytes, entries before, escapes before, end before}
-    if (fact.x == 0) return;
-    const uint32_t seg = o.offsets[st], n = o.offsets[st + 1] - seg;
-    uint64_t fp0 = 0;
-    uint32_t e = 0;
-    if (CWIRE) {
-        fp0 = o.frame_pos[st];
-        const uint64_t fp1 = o.frame_pos[st + 1];
-        if (fp1 > o.capacity) return;   // the record does not fit: skipped whole, by every workgroup alike
-        e = cwire_record_escapes(fp1 - fp0, n);
-    }
-    const uint32_t lo = tile * kCwaTile;
-    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
-    if (!cwc_sum_tile(s, a, nframes, st, tile, lo, lo + len, lane)) return;   // (the facts say otherwise)
+__device__ __forceinline__ void cwc_emit_tile(const uint8_t *s, uint8_t *s_code, uint8_t *s_diff, const uint4 fact, const CwcOut &o,
+                                              uint32_t seg, uint32_t n, uint64_t fp0, uint32_t e, uint32_t lo, int lane) {
     const uint64_t m = cwc_lane_mask(s, lane);
     const uint64_t lanes = __ballot(m != 0);
     uint32_t zero = 0;
@@ -1215,6 +1208,174 @@ __global__ __launch_bounds__(64) void k_cwc_emit(const CwaArgs a, const CwcOut o
     __syncthreads();
     if (CWIRE) cwc_store_bytes(g_code, s_code, sh_code, (uint32_t)room, lane);
     cwc_store_bytes(g_diff, s_diff, sh_diff, (uint32_t)room, lane);
+}
+
+template <bool CWIRE>
+__global__ __launch_bounds__(64) void k_cwc_emit(const CwaArgs a, const CwcOut o, int nframes) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
+    __shared__ uint32_t s_code32[CWIRE ? kCwaTile / 4 + 2 : 1], s_diff32[kCwaTile / 4 + 2];
+    uint8_t *s = (uint8_t *)s_q;
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
+    const uint4 fact = a.chunk[(size_t)st * a.ntiles + tile];   // {nonzero bytes, entries before, escapes before, end before}
+    if (fact.x == 0) return;
+    const uint32_t seg = o.offsets[st], n = o.offsets[st + 1] - seg;
+    uint64_t fp0 = 0;
+    uint32_t e = 0;
+    if (CWIRE) {
+        fp0 = o.frame_pos[st];
+        const uint64_t fp1 = o.frame_pos[st + 1];
+        if (fp1 > o.capacity) return;   // the record does not fit: skipped whole, by every workgroup alike
+        e = cwire_record_escapes(fp1 - fp0, n);
+    }
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    if (!cwc_sum_tile(s, a, nframes, st, tile, lo, lo + len, lane)) return;   // (the facts say otherwise)
+    cwc_emit_tile<CWIRE>(s, (uint8_t *)s_code32, (uint8_t *)s_diff32, fact, o, seg, n, fp0, e, lo, lane);
+}
+
+// ---- mi355_cwire_budget_cwire_batch: record s of a tick thinned to h_budget[s] entries, the caller's state s reverted where ----
+// an entry is dropped.  An entry (x, d) of stream s changed state[s][x] from prev = cur - d to cur; its magnitude a = |cur -
+// prev| (as integers: the diff byte alone does not give it) is above the threshold T0 that made the record.  The entries with
+// a > T are the record of the same tick at threshold T >= T0, and the state of that tick holds prev at the others.  Behind the
+// directory of the nstreams records (hist: [nstreams][kCwbWords] words of the core, zeroed and given the budgets by k_cwb_init):
+//   k_cwb_hist  (grid: tiles x streams, one wave) : streams over their budget only; the tile of differences in LDS (cwc_sum_tile,
+//                                                   one record), the same tile of the state, a per bin of a 256-bin histogram in LDS,
+//                                                   then ONE global atomic per nonzero bin
+//   k_cwb_thr   (grid: streams)                   : T_s = the least T in [T0, 255] with at most `budget` entries of a > T
+//   k_cwb_facts (grid: tiles x streams, one wave) : k_cwc_sum on the tile with the entries of a <= T_s zeroed
+//   k_cwc_scan, k_cwc_place                       : the coalescer's, unchanged
+//   k_cwb_emit  (grid: tiles x streams, one wave) : the filtered tile again, from the same bytes: the state is read by all three
+//                                                   tile passes and written by this, the last one, alone -- prev at the dropped
+//                                                   entries, single byte stores by the lanes that own them, also where the record
+//                                                   is skipped for lack of room; then k_cwc_emit's tile
+// A stream with T_s == T0 is not filtered (every entry of a record made at T0 has a > T0): its state is not even read.
+// The lane's 64 bytes of the tile of differences s against the same bytes of the state sv: HIST: hist[a]++ per entry; else the
+// entries with a <= thr are zeroed in s and, REVERT, state[x] = prev is stored to g (the tile's place in the state).
+template <bool HIST, bool REVERT>
+__device__ __forceinline__ void cwb_lane_bytes(uint8_t *s, const uint8_t *sv, uint32_t thr, uint32_t *hist, uint8_t *g, int lane) {
+    uint32_t *w = (uint32_t *)s + 16 * lane;
+    const uint32_t *wv = (const uint32_t *)sv + 16 * lane;
+    for (int i = 0; i < 16; i++) {
+        const uint32_t v = w[i];
+        if (!v) continue;
+        const uint32_t cv = wv[i];
+        uint32_t keep = v;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint32_t d = (v >> (8 * j)) & 255u;
+            if (!d) continue;
+            const uint32_t cur = (cv >> (8 * j)) & 255u, prev = (cur - d) & 255u;
+            const uint32_t mag = cur > prev ? cur - prev : prev - cur;   // 1 .. 255
+            if (HIST) {
+                atomicAdd(hist + mag, 1u);
+            } else if (mag <= thr) {
+                keep &= ~(255u << (8 * j));
+                if (REVERT) g[64 * lane + 4 * i + j] = (uint8_t)prev;
+            }
+        }
+        if (!HIST) w[i] = keep;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_cwb_init(uint32_t *hist, const CwbInitArgs h) {
+    uint32_t *row = hist + (size_t)(h.first + blockIdx.x) * kCwbWords;
+    row[threadIdx.x] = 0u;
+    if (threadIdx.x == 0) {
+        row[kCwbBudget] = h.budget[blockIdx.x];
+        row[kCwbThr] = h.thr0;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_cwb_hist(const CwaArgs a, uint32_t *hist) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16], s_v[kCwaTile / 16];
+    __shared__ uint32_t s_hist[256];
+    uint8_t *s = (uint8_t *)s_q, *sv = (uint8_t *)s_v;
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
+    uint32_t *row = hist + (size_t)st * kCwbWords;
+    if (row[kCwbBudget] >= a.ftab[st].n) return;   // within its budget whatever the magnitudes are
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    if (!cwc_sum_tile(s, a, 1, st, tile, lo, lo + len, lane)) return;
+    for (int i = lane; i < 256; i += 64) s_hist[i] = 0u;
+    cwa_tile_load(sv, a.state + (size_t)st * a.stride + lo, len, lane);
+    __syncthreads();
+    cwb_lane_bytes<true, false>(s, sv, 0u, s_hist, nullptr, lane);
+    __syncthreads();
+    for (int i = lane; i < 256; i += 64) {
+        const uint32_t v = s_hist[i];
+        if (v) atomicAdd(row + i, v);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_cwb_thr(uint32_t *hist, uint32_t thr0, uint32_t *thresholds) {
+    __shared__ uint32_t s_bin[256];
+    uint32_t *row = hist + (size_t)blockIdx.x * kCwbWords;
+    const uint32_t T = threadIdx.x, budget = row[kCwbBudget];
+    s_bin[T] = row[T];
+    __syncthreads();
+    uint32_t above = 0;   // entries with a > T
+    for (uint32_t k = T + 1; k < 256; k++) above += s_bin[k];
+    // `above` falls with T: the T in [thr0, 255) that are over the budget are the first ones
+    const int over = __syncthreads_count(T >= thr0 && T < 255u && above > budget);
+    if (T == 0) {
+        row[kCwbThr] = thr0 + (uint32_t)over;
+        thresholds[blockIdx.x] = thr0 + (uint32_t)over;
+    }
+}
+
+// The tile of stream st in LDS, filtered where `filter` says so; false: no entry of the record lands in the tile (s untouched).
+// REVERT: the dropped entries' state bytes are stored.
+template <bool REVERT>
+__device__ __forceinline__ bool cwb_tile(uint8_t *s, uint8_t *sv, const CwaArgs &a, uint32_t thr, bool filter, uint32_t st, uint32_t tile,
+                                         uint32_t lo, uint32_t len, int lane) {
+    if (!cwc_sum_tile(s, a, 1, st, tile, lo, lo + len, lane)) return false;
+    if (filter) {
+        uint8_t *g = a.state + (size_t)st * a.stride + lo;
+        cwa_tile_load(sv, g, len, lane);
+        __syncthreads();
+        cwb_lane_bytes<false, REVERT>(s, sv, thr, nullptr, g, lane);
+        __syncthreads();
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(64) void k_cwb_facts(const CwaArgs a, const uint32_t *hist, uint32_t thr0) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16], s_v[kCwaTile / 16];
+    uint8_t *s = (uint8_t *)s_q;
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
+    const uint32_t thr = hist[(size_t)st * kCwbWords + kCwbThr];
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    uint4 *fact = a.chunk + (size_t)st * a.ntiles + tile;
+    if (!cwb_tile<false>(s, (uint8_t *)s_v, a, thr, thr > thr0, st, tile, lo, len, lane)) {
+        if (lane == 0) *fact = make_uint4(0u, 0u, 0u, 0u);
+        return;
+    }
+    const uint4 f = cwc_tile_facts(s, lo, lane);
+    if (lane == 0) *fact = f;
+}
+
+__global__ __launch_bounds__(64) void k_cwb_emit(const CwaArgs a, const CwcOut o, const uint32_t *hist, uint32_t thr0) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16], s_v[kCwaTile / 16];
+    __shared__ uint32_t s_code32[kCwaTile / 4 + 2], s_diff32[kCwaTile / 4 + 2];
+    uint8_t *s = (uint8_t *)s_q;
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
+    const uint32_t thr = hist[(size_t)st * kCwbWords + kCwbThr];
+    const bool filter = thr > thr0;
+    const uint4 fact = a.chunk[(size_t)st * a.ntiles + tile];   // {kept bytes, entries before, escapes before, end before}
+    const uint32_t seg = o.offsets[st], n = o.offsets[st + 1] - seg;
+    const uint64_t fp0 = o.frame_pos[st], fp1 = o.frame_pos[st + 1];
+    const bool write = fact.x != 0 && fp1 <= o.capacity;   // (a record that does not fit is skipped whole, by every workgroup alike)
+    if (!write && !filter) return;
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    if (!cwb_tile<true>(s, (uint8_t *)s_v, a, thr, filter, st, tile, lo, len, lane)) return;
+    if (!write) return;
+    cwc_emit_tile<true>(s, (uint8_t *)s_code32, (uint8_t *)s_diff32, fact, o, seg, n, fp0, cwire_record_escapes(fp1 - fp0, n), lo, lane);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
@@ -1278,6 +1439,30 @@ hipError_t launch_cwire_coalesce(const CwaArgs &a, const CwaFrame *records, int 
     if (a.ntiles) launch_cwa_directory(a, records, nstreams * nframes, s);
     if (cwire) launch_cwc<true>(a, o, nstreams, nframes, s);
     else launch_cwc<false>(a, o, nstreams, nframes, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_cwire_budget(const CwaArgs &a, const CwaFrame *records, int nstreams, const uint32_t *budget, uint32_t thr0,
+                               uint32_t *hist, uint32_t *thresholds, const CwcOut &o, hipStream_t s) {
+    if (nstreams <= 0) return hipSuccess;
+    CwbInitArgs h{};
+    h.thr0 = thr0;
+    for (int s0 = 0; s0 < nstreams; s0 += kCwbInitStreams) {
+        h.first = s0;
+        const int ns = nstreams - s0 < kCwbInitStreams ? nstreams - s0 : kCwbInitStreams;
+        for (int j = 0; j < ns; j++) h.budget[j] = budget[s0 + j];
+        hipLaunchKernelGGL(k_cwb_init, dim3(ns), dim3(256), 0, s, hist, h);
+    }
+    const dim3 tiles(a.ntiles * (uint32_t)nstreams);
+    if (a.ntiles) {
+        launch_cwa_directory(a, records, nstreams, s);
+        hipLaunchKernelGGL(k_cwb_hist, tiles, dim3(64), 0, s, a, hist);
+    }
+    hipLaunchKernelGGL(k_cwb_thr, dim3(nstreams), dim3(256), 0, s, hist, thr0, thresholds);
+    if (a.ntiles) hipLaunchKernelGGL(k_cwb_facts, tiles, dim3(64), 0, s, a, (const uint32_t *)hist, thr0);
+    hipLaunchKernelGGL(k_cwc_scan<true>, dim3(nstreams), dim3(256), 0, s, a, o);
+    hipLaunchKernelGGL(k_cwc_place<true>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, nstreams);
+    if (a.ntiles) hipLaunchKernelGGL(k_cwb_emit, tiles, dim3(64), 0, s, a, o, (const uint32_t *)hist, thr0);
     return hipGetLastError();
 }
 

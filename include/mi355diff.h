@@ -87,7 +87,8 @@ typedef struct mi355_config {
  *      + mi355_diff_multi_stream_batch, mi355_diff_multi_stream_wire_batch, mi355_diff_multi_stream_cwire_batch (additions
  *      only); + mi355_apply_multi_stream_batch, mi355_apply_multi_stream_wire_batch, mi355_apply_multi_stream_cwire_batch
  *      (additions only); + mi355_cwire_coalesce_batch, mi355_cwire_coalesce_cwire_batch (additions only);
- *      + mi355_exec_cwire, mi355_pipe_submit_cwire, mi355_pipe_wait_cwire, MI355_PREPARE_EXEC_CWIRE (additions only) */
+ *      + mi355_exec_cwire, mi355_pipe_submit_cwire, mi355_pipe_wait_cwire, MI355_PREPARE_EXEC_CWIRE (additions only);
+ *      + mi355_cwire_budget_cwire_batch, mi355_cwire_budget_entries (additions only) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -482,6 +483,67 @@ int mi355_cwire_coalesce_batch(mi355_core *core, const void *d_cwire, const uint
 int mi355_cwire_coalesce_cwire_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts,
                                      const uint32_t *h_escapes, int nstreams, int nframes, void *d_offsets,
                                      void *d_frame_pos, void *d_cwire_out, size_t capacity_bytes);
+
+/* A tick held to a budget: the sender's rate control.  The nstreams compact records mi355_diff_multi_cwire_batch just wrote
+ * (back to back where h_counts[s] / h_escapes[s] put them; the headers come from the host and are not trusted in the buffer, as
+ * in mi355_apply_multi_cwire_batch) and the caller's states as that tick left them (stream s at d_states + s*stride_bytes) ->
+ * records of at most h_budget[s] entries each (UINT32_MAX: no limit), the largest changes kept.  What is not sent is not lost:
+ * the state goes back to the previous value there, so the change stays pending and is sent on a later tick if it persists --
+ * the negative feedback of the diff itself, with the threshold raised for one camera for one tick.
+ *   Semantics: T0 = the core's threshold.  For an entry (x, d) of stream s let cur = state[s][x], prev = (uint8)(cur - d) and
+ *   a = |cur - prev| as integers, 1 .. 255 -- taken from the STATE: (uint8)df is the same byte for df and df +- 256, the diff
+ *   byte alone does not give the magnitude.  T_s = the least T in [T0, 255] such that at most h_budget[s] entries have a > T
+ *   (T = 255 keeps nothing, so T_s exists).  Entries of equal magnitude cannot be told apart: when more than h_budget[s] of them
+ *   share the largest magnitude, T_s passes all of them and this tick sends none of them (they stay pending).
+ *   Outputs: d_thresholds, uint32[nstreams], receives T_s.  Record s at d_cwire_out + d_frame_pos[s] is the canonical encoding
+ *   (ascending indices, pad bytes zero, headers written) of the entries with a > T_s; d_offsets, uint32[nstreams + 1], is the
+ *   exclusive scan of the kept counts; d_frame_pos, uint64[nstreams + 1], is always exact.  state[s][x] = prev at every dropped
+ *   entry.
+ *   Guarantees: records, offsets, frame positions and states are byte for byte what mi355_diff_multi_cwire_batch of a core with
+ *   threshold T_s would have left from the same frames and the same states before the tick (the entries of a tick at T' >= T
+ *   are a subset of those at T, and the states differ exactly at the dropped ones).  A stream within its budget comes back
+ *   byte for byte and its state is not written (not even read).  Capacity rule of the family: a record with d_frame_pos[s + 1]
+ *   > capacity_bytes is skipped whole and the ones behind it that fit are written; the states are thinned completely
+ *   regardless; mi355_cwire_bytes_max(N, nstreams) always suffices.  Bytes of the states' region outside the N bytes of each
+ *   state are never written, the stride gap included (every state store is a single byte).
+ *   Malformed content under consistent headers: the guarantees of mi355_cwire_coalesce_cwire_batch -- nothing is read outside
+ *   the input span or the states, nothing is written outside the outputs and the N bytes of each state, an index >= N and an
+ *   escape ranked at or past e contribute nothing; that stream's own result is otherwise unspecified.
+ *   Refused with MI355_ERR_INVALID before anything is launched or written: a null core; nstreams outside [0, max_batch]; with
+ *   nstreams > 0 a null pointer among the arguments; h_escapes[s] > h_counts[s]; h_counts[s] > N; stride_bytes < N; d_cwire,
+ *   d_cwire_out, d_offsets or d_thresholds not 4-byte aligned; d_frame_pos not 8-byte aligned; the input span (known from the
+ *   host's headers) overlapping an output region or the states' region [d_states, d_states + (nstreams-1)*stride_bytes + N); an
+ *   output region (offsets, thresholds, frame_pos, [d_cwire_out, + capacity_bytes)) overlapping the states' region.
+ *   nstreams == 0 writes offsets[0] = 0 and frame_pos[0] = 0 and nothing else.
+ * Asynchronous on the core's stream, behind the last expansion of this core as every consumer of a packed stream is, so it may
+ * follow mi355_diff_multi_cwire_batch on one core without a synchronisation of the device work (the host still needs the
+ * headers); a later tick on the same states sees every byte this call wrote; with a caller's stream everything runs on it in
+ * call order.  Nothing is allocated inside the call: the 258 words per stream it needs beyond the directory scratch of
+ * mi355_apply_cwire_batch (256 bins, budget, threshold) are made with the core, max_batch of them, and counted by
+ * mi355_workspace_bytes.
+ * The directory kernels of mi355_apply_cwire_batch on the nstreams records, then a grid of 4096-byte tiles x streams three
+ * times, one wave per tile, a tile no entry lands in returning on its directory word: (1) streams over their budget only: the
+ * tile of differences rebuilt in LDS, the same tile of the state beside it, a per entry into a 256-bin histogram in LDS, one
+ * global atomic per nonzero bin; one workgroup per stream then sums the bins from the top for T_s; (2) the tile again with the
+ * entries of a <= T_s zeroed -> the coalescer's facts, its scan and its placement; (3) the same filtered tile from the same
+ * bytes, the dropped entries' state bytes stored (the only pass that writes the state is the last that reads it; a tile of a
+ * record that is skipped for lack of room still reverts), the kept entries written as the coalescer writes them.  A stream
+ * with T_s == T0 skips the state in every pass.  The cost follows the entries and their tiles, not N.
+ * Out of scope: the stream forms (nframes frames chained through one state: frame t + 1 depends on how frame t was thinned);
+ * the per-frame host path (mi355_exec_cwire, mi355_pipe_submit_cwire); an arrays or plain-wire output form.
+ * Not measured yet: tools/bench_multi.py --legs budget writes profiles/multi_budget.json (microseconds per stream of this call
+ * with budgets at half of each stream's count, against a second mi355_diff_multi_cwire_batch over the same frames -- the
+ * cheapest re-diff a caller has without it, and one that still lacks the threshold choice; 1080p, webcam-like input, S = 4, 16,
+ * 64, median of five rounds, same run, same board).  The expectation to test -- cheaper than that second diff at every S -- is
+ * neither met nor missed until that file exists.  DESIGN.md section 4, "Holding a tick to a budget". */
+int mi355_cwire_budget_cwire_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
+                                   void *d_states, size_t stride_bytes, int nstreams, const uint32_t *h_budget,
+                                   void *d_thresholds, void *d_offsets, void *d_frame_pos, void *d_cwire_out,
+                                   size_t capacity_bytes);
+/* Host only, no core: the largest n such that EVERY record of n entries of a frame of frame_bytes bytes fits in record_bytes --
+ * the largest n <= frame_bytes with 8 + 2*pad4(n) + 4*min(n, frame_bytes/256) <= record_bytes (an escape spans at least 256
+ * bytes of the frame), 0 when record_bytes < 8.  A sender turns its per-socket byte budget into h_budget[s] with it. */
+size_t mi355_cwire_budget_entries(size_t frame_bytes, size_t record_bytes);
 
 /* The client's side, client/opencv.cpp:50-66: for every frame in order, state[xs[i]] += diff[i] (uint8
  * wrap-around) on the core's state (a client core is a core whose state was set to the received base frame,

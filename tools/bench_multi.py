@@ -55,6 +55,13 @@ the moving block of tools/roundtrip's make_frame without the noise (few tiles ar
 server core, applied round and round: adding a record to a state is the same work whatever the state holds.  The line also
 carries the touched 4096-byte tiles per record and per stream and call, counted from the decoded indices.
 
+The budget leg (--legs budget, a run of its own: `--legs budget --streams 4,16,64 > profiles/multi_budget.json`) measures the
+sender's rate control, in microseconds per stream, ONE JSON line for all S:
+  budget       mi355_cwire_budget_cwire_batch on the records of one tick, every stream's budget at half of its count;
+  second_diff  a second mi355_diff_multi_cwire_batch over the same S frames from the states before the tick: the cheapest
+               re-diff a caller has without the call -- and it still lacks the threshold choice.
+Every pass of a timed window works on its own copy of the S states (restored outside the window).
+
 Input of the other legs: ONE webcam stream of S + K + 1 frames; stream s shows frame s + j at step j, so every tick of every stream is the
 step between two consecutive webcam frames, and a tick's S frames are one contiguous region.  j walks 1 .. K and back."""
 import argparse
@@ -620,6 +627,74 @@ def run_coalesce(W, H, S, T, rounds, kind):
     return out
 
 
+def run_budget(W, H, S, rounds):
+    """The budget leg for one S -> its dictionary.  budget: mi355_cwire_budget_cwire_batch on the records of one tick with every
+    stream's budget at half of its count, on the states as the tick left them.  second_diff: mi355_diff_multi_cwire_batch over the
+    same S frames from the states before the tick -- the cheapest re-diff a caller has without the call (and one that still lacks
+    the threshold choice).  Both on a core's own stream; every pass of a timed window has its own copy of the states, restored
+    outside the window, so no pass sees what another one wrote."""
+    import numpy as np
+    from cudavideostream_amd import CUDACore, cwire_bytes_max
+    dev = torch.device("cuda", 0)
+    n = 3 * W * H
+    passes = max(2, min(16, 128 // S))
+    _, web = synth.webcam_stream(S + 1, W, H, device=dev)
+    web = web.reshape(S + 1, n)
+    pre, frames = web[:S].clone(), web[1:].clone()      # stream s: webcam frame s -> s + 1
+    cwcap = cwire_bytes_max(n, S)
+    d_off = torch.zeros(S + 1, dtype=torch.int32, device=dev)
+    d_pos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
+    d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
+    d_thr = torch.zeros(S, dtype=torch.int32, device=dev)
+    d_ooff, d_opos, d_out = torch.zeros_like(d_off), torch.zeros_like(d_pos), torch.empty_like(d_cw)
+    d_roff, d_rpos, d_rcw = torch.zeros_like(d_off), torch.zeros_like(d_pos), torch.empty_like(d_cw)
+    post = pre.clone()
+    core = CUDACore(W, H, max_batch=S)
+    torch.cuda.synchronize()
+    core.diff_multi_cwire_batch(frames, post, S, d_off, d_pos, d_cw, cwcap)
+    core.synchronize()
+    pos = d_pos.cpu().numpy().astype(np.int64)
+    counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
+    escapes = ((np.diff(pos) - 8 - 2 * ((counts.astype(np.int64) + 3) & ~3)) // 4).astype(np.uint32)
+    budgets = (counts // 2).astype(np.uint32)
+    work = torch.empty(passes, S, n, dtype=torch.uint8, device=dev)
+
+    def leg_budget():
+        for p in range(passes):
+            core.cwire_budget_cwire_batch(d_cw, counts, escapes, work[p], S, budgets, d_thr, d_ooff, d_opos, d_out, cwcap)
+        core.synchronize()
+
+    def leg_diff():
+        for p in range(passes):
+            core.diff_multi_cwire_batch(frames, work[p], S, d_roff, d_rpos, d_rcw, cwcap)
+        core.synchronize()
+
+    table = {"budget": (leg_budget, post), "second_diff": (leg_diff, pre)}
+    times = {}
+    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
+        for name, (leg, start) in table.items():
+            work.copy_(start.unsqueeze(0).expand(passes, S, n))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            leg()
+            dt = time.perf_counter() - t0
+            if r:
+                times.setdefault(name, []).append(dt * 1e6 / (passes * S))
+    kept = np.diff(d_ooff.cpu().numpy().view(np.uint32).astype(np.int64))
+    thr = d_thr.cpu().numpy().view(np.uint32)
+    assert (kept <= budgets).all() and (thr >= 20).all() and torch.equal(d_rpos, d_pos)
+    out = {"streams": S, "passes": passes, "entries_per_stream": round(float(counts.mean()), 1),
+           "kept_entries_per_stream": round(float(kept.mean()), 1), "record_bytes_per_stream": round(int(pos[S]) / S, 1),
+           "kept_bytes_per_stream": round(int(d_opos[S].item()) / S, 1), "threshold_min": int(thr.min()), "threshold_max": int(thr.max())}
+    for name in table:
+        st = stats(times[name])
+        st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
+        out[name + "_us_per_stream"] = st
+    out["second_diff_over_budget"] = round(statistics.median(times["second_diff"]) / statistics.median(times["budget"]), 3)
+    core.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", default="1920x1080")
@@ -627,7 +702,7 @@ def main():
     ap.add_argument("--steps", type=int, default=8, help="K: webcam frames a stream walks through")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--legs", default="multi,cores_loop,pairs",
-                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone")
+                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or budget alone")
     ap.add_argument("--frames", default="4,16,64", help="burst, burst_client and coalesce legs: T, frames per stream and call")
     a = ap.parse_args()
     have = load_library()
@@ -667,6 +742,15 @@ def main():
                     print(f"coalesce S={S} T={T} {kind}: done", file=sys.stderr, flush=True)
                     torch.cuda.empty_cache()
         print(json.dumps({"bench": "multi_coalesce", "size": f"{W}x{H}", "rounds": a.rounds, "coalesce": per}), flush=True)
+        return
+    if a.legs == "budget":
+        per = []
+        for S in (int(v) for v in a.streams.split(",")):
+            per.append(run_budget(W, H, S, a.rounds))
+            print(f"budget S={S}: done", file=sys.stderr, flush=True)
+            torch.cuda.empty_cache()
+        print(json.dumps({"bench": "multi_budget", "size": f"{W}x{H}", "input": "synth.webcam_stream", "rounds": a.rounds,
+                          "budget": per}), flush=True)
         return
     for S in (int(v) for v in a.streams.split(",")):
         run(W, H, S, a.steps, a.rounds, set(a.legs.split(",")), have)

@@ -20,6 +20,11 @@
 // mi355_diff_multi_cwire_batch; each tick's records (headers included) cross the pipe; a client core uploads them and applies
 // them in one call (mi355_apply_multi_cwire_batch) onto S states of its own.  After every tick the client's states must equal
 // the server's, byte for byte, and after the last tick the frames a host client (mi355_cwire_apply_host) rebuilt per camera.
+// --compact --multi S --budget BYTES: the sender holds every camera's record of a tick to BYTES bytes (a socket's share of the
+// link): the records larger than that are thinned to mi355_cwire_budget_entries(N, BYTES) entries by
+// mi355_cwire_budget_cwire_batch, which takes the sender's states back where it drops an entry.  Checked: every record written is
+// at most BYTES; each client's frame equals the sender's state after every tick; and once the input has stood still for enough
+// ticks every client's frame is within the threshold of the camera's frame at every byte -- what was postponed arrives.
 // --compact --multi S --burst K: the sender buffers K ticks per camera (a recorder, a camera that catches up) and makes their
 // S * K records in ONE call, mi355_diff_multi_stream_cwire_batch: camera s's K records are one contiguous slice, one write()
 // per socket.  The receiver stages record (s, t) of every s back to back for tick t and applies the ticks with the same
@@ -41,7 +46,7 @@
 // (mi355_exec on a second core: frame[xs[i]] += diff[i], client/opencv.cpp:64-66).
 //
 //   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B]
-//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--burst K [--burst-client | --coalesce]]]]
+//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]]]]
 //   exit status 0 = all checks passed
 #include <cstdint>
 #include <cstdio>
@@ -190,6 +195,131 @@ static int run_multi(int w, int h, int T, int S) {
     printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"width\": %d, \"height\": %d, \"ticks\": %d, "
            "\"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d}\n",
            S, w, h, T, changed, sent_bytes, mi355_wire_bytes(T * S, changed), (size_t)T * S * n, max_err);
+    return 0;
+}
+
+// --compact --multi S --budget BYTES (see the head of the file)
+static int run_multi_budget(int w, int h, int T, int S, long bytes) {
+    const size_t n = (size_t)3 * w * h;
+    const size_t most = bytes >= 0 ? mi355_cwire_budget_entries(n, (size_t)bytes) : 0;
+    if (most == 0) { fprintf(stderr, "--budget %ld holds no entry of a %dx%d frame\n", bytes, w, h); return 2; }
+    mi355_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.width = w; cfg.height = h; cfg.threshold = 20; cfg.max_batch = S; cfg.device = -1;
+    mi355_core *server = nullptr, *client = nullptr;
+    OK(mi355_create(&cfg, &server));
+    OK(mi355_create(&cfg, &client));
+    const size_t cw_cap = mi355_cwire_bytes_max(n, S);
+    void *d_frames = nullptr, *d_sstates = nullptr, *d_off = nullptr, *d_pos = nullptr, *d_cw = nullptr;   // server
+    void *d_thr = nullptr, *d_ooff = nullptr, *d_opos = nullptr, *d_out = nullptr;
+    void *d_rx = nullptr, *d_cstates = nullptr;                                                              // client
+    OK(mi355_dev_alloc(server, &d_frames, (size_t)S * n));
+    OK(mi355_dev_alloc(server, &d_sstates, (size_t)S * n));
+    OK(mi355_dev_alloc(server, &d_off, sizeof(uint32_t) * (S + 1)));
+    OK(mi355_dev_alloc(server, &d_pos, sizeof(uint64_t) * (S + 1)));
+    OK(mi355_dev_alloc(server, &d_cw, cw_cap));
+    OK(mi355_dev_alloc(server, &d_thr, sizeof(uint32_t) * S));
+    OK(mi355_dev_alloc(server, &d_ooff, sizeof(uint32_t) * (S + 1)));
+    OK(mi355_dev_alloc(server, &d_opos, sizeof(uint64_t) * (S + 1)));
+    OK(mi355_dev_alloc(server, &d_out, cw_cap));
+    OK(mi355_dev_alloc(client, &d_rx, cw_cap));
+    OK(mi355_dev_alloc(client, &d_cstates, (size_t)S * n));
+    int fds[2];
+    if (pipe(fds) != 0) return 1;
+    std::vector<uint8_t> bases((size_t)S * n), frames((size_t)S * n), s_states((size_t)S * n), c_states((size_t)S * n), cw_host(cw_cap),
+        rx(cw_cap);
+    for (int s = 0; s < S; s++)
+        for (size_t i = 0; i < n; i++) bases[(size_t)s * n + i] = (uint8_t)(40 + (i * 7 + (size_t)s * 31) % 150);
+    OK(mi355_upload(server, d_sstates, bases.data(), bases.size()));
+    if (!through_pipe(fds[1], fds[0], bases.data(), c_states.data(), bases.size())) return 1;
+    OK(mi355_upload(client, d_cstates, c_states.data(), c_states.size()));
+    std::vector<uint8_t> base(n), frame(n);
+    std::vector<uint32_t> counts(S), escapes(S), budget(S), thr(S);
+    std::vector<uint64_t> pos(S + 1);
+    size_t sent_bytes = 0, largest = 0;
+    int thinned = 0, max_thr = cfg.threshold, max_err = 0, still = 0;
+    // T ticks of moving input, then the last frames again and again until nothing is held back any more: what a budget
+    // postponed must arrive.  A tick sends up to `most` of a camera's pending entries, so N / most still ticks suffice -- unless
+    // more than `most` of them share one magnitude (then no threshold separates them; the synthetic input has no such group).
+    const int still_limit = (int)(2 * ((n + most - 1) / most)) + 2;
+    for (int t = 0;; t++) {
+        if (t < T) {
+            for (int s = 0; s < S; s++) {   // camera s: its own base, its block a few steps ahead of its neighbour's
+                memcpy(base.data(), &bases[(size_t)s * n], n);
+                make_frame(frame, base, w, h, t + 5 * s);
+                memcpy(&frames[(size_t)s * n], frame.data(), n);
+            }
+            OK(mi355_upload(server, d_frames, frames.data(), frames.size()));
+        }
+        // ---- server: one tick -> S records, their headers, the records above the budget thinned
+        OK(mi355_diff_multi_cwire_batch(server, d_frames, d_sstates, n, S, d_off, d_pos, d_cw, cw_cap));
+        OK(mi355_download(server, pos.data(), d_pos, sizeof(uint64_t) * (S + 1)));
+        if (pos[S] > cw_cap) { fprintf(stderr, "compact stream larger than its bound\n"); return 1; }
+        bool over = false;
+        for (int s = 0; s < S; s++) {
+            uint32_t hdr[2];
+            OK(mi355_download(server, hdr, (const uint8_t *)d_cw + pos[s], sizeof hdr));
+            counts[s] = hdr[0];
+            escapes[s] = hdr[1];
+            budget[s] = pos[s + 1] - pos[s] > (uint64_t)bytes ? (uint32_t)most : UINT32_MAX;
+            if (budget[s] != UINT32_MAX) { over = true; thinned++; }
+        }
+        OK(mi355_cwire_budget_cwire_batch(server, d_cw, counts.data(), escapes.data(), d_sstates, n, S, budget.data(), d_thr, d_ooff,
+                                          d_opos, d_out, cw_cap));
+        OK(mi355_download(server, pos.data(), d_opos, sizeof(uint64_t) * (S + 1)));
+        OK(mi355_download(server, thr.data(), d_thr, sizeof(uint32_t) * S));
+        if (pos[S] > cw_cap) { fprintf(stderr, "thinned stream larger than its bound\n"); return 1; }
+        for (int s = 0; s < S; s++) {   // check 1: every record that is written fits the socket's budget
+            const size_t rb = (size_t)(pos[s + 1] - pos[s]);
+            if (rb > (size_t)bytes) { fprintf(stderr, "tick %d: camera %d's record has %zu bytes > %ld\n", t, s, rb, bytes); return 1; }
+            if (rb > largest) largest = rb;
+            if ((int)thr[s] > max_thr) max_thr = (int)thr[s];
+            if ((budget[s] == UINT32_MAX) != ((int)thr[s] == cfg.threshold)) { fprintf(stderr, "tick %d: camera %d: threshold %u\n", t, s, thr[s]); return 1; }
+        }
+        const size_t cb = (size_t)pos[S];
+        OK(mi355_download(server, cw_host.data(), d_out, cb));
+        if (!through_pipe(fds[1], fds[0], cw_host.data(), rx.data(), cb)) return 1;
+        sent_bytes += cb;
+        // ---- client: the headers as read from the stream, one upload, one call
+        size_t p = 0;
+        for (int s = 0; s < S; s++) {
+            if (p + 8 > cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
+            memcpy(&counts[s], rx.data() + p, 4);
+            memcpy(&escapes[s], rx.data() + p + 4, 4);
+            p += mi355_cwire_frame_bytes(counts[s], escapes[s]);
+        }
+        if (p != cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
+        OK(mi355_upload(client, d_rx, rx.data(), cb));
+        OK(mi355_apply_multi_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, d_cstates, n));
+        // ---- check 2: each client's frame equals the sender's state after every tick
+        OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
+        OK(mi355_download(server, s_states.data(), d_sstates, s_states.size()));
+        if (memcmp(s_states.data(), c_states.data(), s_states.size()) != 0) {
+            fprintf(stderr, "tick %d: client states != server states\n", t);
+            return 1;
+        }
+        if (t + 1 < T) continue;
+        // ---- check 3, once the input stands still: every client's frame within the threshold of the camera's, at every byte
+        max_err = 0;
+        for (size_t i = 0; i < c_states.size(); i++) {
+            const int e = abs((int)c_states[i] - (int)frames[i]);
+            if (e > max_err) max_err = e;
+        }
+        if (t >= T && !over && max_err <= cfg.threshold) break;
+        if (t >= T) still++;
+        if (still > still_limit) { fprintf(stderr, "held still for %d ticks and still off by %d > threshold\n", still, max_err); return 1; }
+    }
+    void *srv[] = {d_frames, d_sstates, d_off, d_pos, d_cw, d_thr, d_ooff, d_opos, d_out};
+    for (void *q : srv) OK(mi355_dev_free(server, q));
+    OK(mi355_dev_free(client, d_rx));
+    OK(mi355_dev_free(client, d_cstates));
+    mi355_destroy(server);
+    mi355_destroy(client);
+    printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"budget_bytes\": %ld, \"budget_entries\": %zu, \"width\": %d, "
+           "\"height\": %d, \"ticks\": %d, \"still_ticks\": %d, \"thinned_records\": %d, \"largest_record_bytes\": %zu, "
+           "\"largest_threshold\": %d, \"records_within_budget\": true, \"states_equal_every_tick\": true, "
+           "\"max_abs_error_when_still\": %d, \"wire_bytes\": %zu}\n",
+           S, bytes, most, w, h, T, still + 1, thinned, largest, max_thr, max_err, sent_bytes);
     return 0;
 }
 
@@ -722,6 +852,7 @@ static int run_per_frame(int w, int h, int T) {
 
 int main(int argc, char **argv) {
     int w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0;
+    long budget = -1;
     bool compact = false, direct = false, gpu_client = false, burst_client = false, coalesce = false, per_frame = false;
     for (int i = 1; i < argc; i++) {
         if (std::string(argv[i]) == "--compact") compact = true;
@@ -741,11 +872,16 @@ int main(int argc, char **argv) {
         else if (k == "--frames") T = v; else if (k == "--batch") B = v;
         else if (k == "--multi") multi = v;
         else if (k == "--burst") burst = v;
+        else if (k == "--budget") budget = atol(argv[i + 1]) < 0 ? 0 : atol(argv[i + 1]);
     }
     if (burst && (!multi || burst < 0)) { fprintf(stderr, "--burst K needs --multi S and K >= 1\n"); return 2; }
     if (burst_client && (!compact || !multi || !burst)) { fprintf(stderr, "--burst-client needs --compact --multi S --burst K\n"); return 2; }
     if (coalesce && (!compact || !multi || !burst || burst_client)) {
         fprintf(stderr, "--coalesce needs --compact --multi S --burst K, without --burst-client\n");
+        return 2;
+    }
+    if (budget >= 0 && (!compact || !multi || burst || direct || gpu_client || per_frame)) {
+        fprintf(stderr, "--budget BYTES needs --compact --multi S alone\n");
         return 2;
     }
     if (per_frame) {
@@ -756,6 +892,7 @@ int main(int argc, char **argv) {
         if (!compact || direct || gpu_client || multi < 0) { fprintf(stderr, "--multi S needs --compact alone and S >= 1\n"); return 2; }
         if (burst_client) return run_multi_burst_client(w, h, T, multi, burst);
         if (coalesce) return run_multi_burst_coalesce(w, h, T, multi, burst);
+        if (budget >= 0) return run_multi_budget(w, h, T, multi, budget);
         return burst ? run_multi_burst(w, h, T, multi, burst) : run_multi(w, h, T, multi);
     }
     const size_t n = (size_t)3 * w * h;
