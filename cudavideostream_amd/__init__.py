@@ -7,5 +7,5 @@ path of MatteoBattilana/CUDAVideoStream behind the reference's own CUDACore call
   synth.py   deterministic synthetic frames
 """
 from .core import CHARS_STR, LR_THRESHOLDS, CUDACore, PinnedArray  # noqa: F401
-from .core import cwire_apply_host, cwire_budget_entries, cwire_bytes_max, cwire_frame_bytes  # noqa: F401
+from .core import activity_cells, cwire_apply_host, cwire_budget_entries, cwire_bytes_max, cwire_frame_bytes  # noqa: F401
 from . import lib  # noqa: F401

@@ -96,6 +96,13 @@ public:
     void budget_multi(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, void *d_states, size_t stride,
                       int nstreams, const uint32_t *budgets, void *d_thresholds, void *d_offsets, void *d_frame_pos,
                       void *d_cwire_out, size_t capacity_bytes);
+    // Where the cameras move (include/mi355diff.h, mi355_cwire_activity_batch): from the nframes records of camera s, laid out
+    // and described as for apply_multi_stream, a grid of changed bytes per cell of cell_w x cell_h pixels at d_cells
+    // (uint32[nstreams][mi355_activity_cells(...)]) and eight words at d_summary (uint32[nstreams][8]): entries, box x0, y0, x1,
+    // y1, cells of at least min_count, peak count, peak cell.  accumulate != 0 adds onto what the two hold.  Both in DEVICE
+    // memory; no state is involved.  Blocking, like budget_multi; nstreams*nframes <= MI355_MAX_BATCH.
+    void activity_multi(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, int nstreams, int nframes, int cell_w,
+                        int cell_h, uint32_t min_count, int accumulate, void *d_cells, void *d_summary);
 };
 
 static_assert(sizeof(CUDACore) == 160, "must match the reference's object size (LP64)");

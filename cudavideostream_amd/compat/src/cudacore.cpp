@@ -161,6 +161,13 @@ void CUDACore::budget_multi(const void *d_cwire, const uint32_t *counts, const u
     MI355_CHECK(mi355_synchronize(core_));
 }
 
+void CUDACore::activity_multi(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, int nstreams, int nframes,
+                              int cell_w, int cell_h, uint32_t min_count, int accumulate, void *d_cells, void *d_summary) {
+    MI355_CHECK(mi355_cwire_activity_batch(core_, d_cwire, counts, escapes, nstreams, nframes, cell_w, cell_h, min_count, accumulate,
+                                           d_cells, d_summary));
+    MI355_CHECK(mi355_synchronize(core_));
+}
+
 size_t CUDACore::chunkt_size() { return 32; }  // sizeof(long4), kernels.cu:27,527-529
 
 void CUDACore::alloc_arrays(uint8_t **h_frame, uint8_t **n_frame, uint8_t **o_frame, int **h_xs, int r,

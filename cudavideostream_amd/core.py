@@ -448,6 +448,29 @@ class CUDACore:
                                                           _ptr(d_thresholds), _ptr(d_offsets), _ptr(d_frame_pos),
                                                           _ptr(d_cwire_out), int(capacity_bytes)))
 
+    # ... and what any of these nodes can ask about a camera: is it moving, and where
+    def activity_batch(self, d_offsets, d_xs, nstreams, nframes, cell_w, cell_h, d_cells, d_summary, min_count=1,
+                       accumulate=False):
+        """The segments diff_multi_batch / diff_multi_stream_batch wrote (s * nframes + t order) -> per stream a grid of
+        changed bytes per cell of cell_w x cell_h pixels (d_cells, uint32[nstreams][activity_cells(...)[0]]) and
+        d_summary, uint32[nstreams][8]: entries, box x0, y0, x1, y1, cells of at least min_count, peak, peak cell.
+        accumulate: add onto what the two buffers hold instead of clearing them first."""
+        self._hold(d_offsets, d_xs, d_cells, d_summary)
+        _l.check(self._lib.mi355_activity_batch(self._h, _ptr(d_offsets), _ptr(d_xs), int(nstreams), int(nframes), int(cell_w),
+                                                int(cell_h), int(min_count), int(bool(accumulate)), _ptr(d_cells),
+                                                _ptr(d_summary)))
+
+    def cwire_activity_batch(self, d_cwire, counts, escapes, nstreams, nframes, cell_w, cell_h, d_cells, d_summary,
+                             min_count=1, accumulate=False):
+        """activity_batch straight from compact records (headers counts / escapes, s * nframes + t order)."""
+        self._hold(d_cwire, d_cells, d_summary)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+        assert counts.size >= nstreams * nframes and escapes.size >= nstreams * nframes
+        _l.check(self._lib.mi355_cwire_activity_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
+                                                      int(nstreams), int(nframes), int(cell_w), int(cell_h), int(min_count),
+                                                      int(bool(accumulate)), _ptr(d_cells), _ptr(d_summary)))
+
     def wire_bytes(self, nframes, entries):
         return self._lib.mi355_wire_bytes(nframes, entries)
 
@@ -620,6 +643,14 @@ def cwire_budget_entries(frame_bytes, record_bytes):
     """The most entries a record of a frame of frame_bytes bytes may hold so that it fits record_bytes whatever its escapes:
     a sender's per-socket byte budget as a budget of cwire_budget_cwire_batch."""
     return _l.load().mi355_cwire_budget_entries(int(frame_bytes), int(record_bytes))
+
+
+def activity_cells(width, height, cell_w, cell_h):
+    """(cells, grid_w, grid_h) of the motion grid of activity_batch / cwire_activity_batch: ceil(width / cell_w) columns,
+    ceil(height / cell_h) rows; all 0 for an argument below 1."""
+    gw, gh = C.c_int(0), C.c_int(0)
+    cells = _l.load().mi355_activity_cells(int(width), int(height), int(cell_w), int(cell_h), C.byref(gw), C.byref(gh))
+    return cells, gw.value, gh.value
 
 
 def cwire_apply_host(state, buf, nframes):

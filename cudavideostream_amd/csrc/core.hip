@@ -1534,6 +1534,93 @@ int mi355_cwire_budget_cwire_batch(mi355_core *c, const void *d_cwire, const uin
     return MI355_OK;
 }
 
+// ---- mi355_(cwire_)activity_batch: per stream, where the entries of its records land (stream_ops.hip, k_act_*) ----------------
+size_t mi355_activity_cells(int width, int height, int cell_w, int cell_h, int *grid_w, int *grid_h) {
+    const bool ok = width >= 1 && height >= 1 && cell_w >= 1 && cell_h >= 1;
+    const int gw = ok ? (int)(((int64_t)width + cell_w - 1) / cell_w) : 0, gh = ok ? (int)(((int64_t)height + cell_h - 1) / cell_h) : 0;
+    if (grid_w) *grid_w = gw;
+    if (grid_h) *grid_h = gh;
+    return (size_t)gw * (size_t)gh;
+}
+
+// What both forms refuse alike, before anything is launched; *B = nstreams * nframes (0: nothing to do).  in0 / in1: the form's
+// two device inputs, in_ok: none of its inputs is null.
+static int check_activity(mi355_core *c, const void *in0, const void *in1, bool in_ok, int nstreams, int nframes, int cell_w, int cell_h,
+                          uint32_t min_count, const void *d_cells, const void *d_summary, int *B, ActGeom *g) {
+    *B = 0;
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nstreams < 0 || nframes < 0) return fail(MI355_ERR_INVALID, "nstreams or nframes < 0");
+    if ((int64_t)nstreams * nframes > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams * nframes above max_batch");
+    if (cell_w < 1 || cell_h < 1) return fail(MI355_ERR_INVALID, "cell_w or cell_h < 1");
+    if (min_count < 1) return fail(MI355_ERR_INVALID, "min_count < 1");
+    if (((uintptr_t)in0 | (uintptr_t)in1 | (uintptr_t)d_cells | (uintptr_t)d_summary) & 3u)
+        return fail(MI355_ERR_INVALID, "the device pointers must be 4-byte aligned");
+    if (nstreams * nframes == 0) return MI355_OK;
+    if (!in_ok) return fail(MI355_ERR_INVALID, "null stream pointer");
+    if (!d_cells || !d_summary) return fail(MI355_ERR_INVALID, "null output pointer");
+    int gw = 0;
+    g->n = c->n;
+    g->width = act_divisor((uint32_t)c->cfg.width);
+    g->cell_w = act_divisor((uint32_t)cell_w);
+    g->cell_h = act_divisor((uint32_t)cell_h);
+    g->cells = (uint32_t)mi355_activity_cells(c->cfg.width, c->cfg.height, cell_w, cell_h, &gw, nullptr);
+    g->grid_w = (uint32_t)gw;
+    g->min_count = min_count;
+    *B = nstreams * nframes;
+    return MI355_OK;
+}
+
+int mi355_activity_batch(mi355_core *c, const void *d_offsets, const void *d_xs, int nstreams, int nframes, int cell_w, int cell_h,
+                         uint32_t min_count, int accumulate, void *d_cells, void *d_summary) {
+    int B;
+    ActGeom g{};
+    if (int rc = check_activity(c, d_offsets, d_xs, d_offsets && d_xs, nstreams, nframes, cell_w, cell_h, min_count, d_cells, d_summary, &B, &g))
+        return rc;
+    if (B == 0) return MI355_OK;
+    if (int rc = use_device(c)) return rc;
+    HIP_TRY(launch_activity((const uint32_t *)d_offsets, (const int32_t *)d_xs, nstreams, nframes, g, accumulate != 0, (uint32_t *)d_cells,
+                            (uint32_t *)d_summary, c->stream));
+    return MI355_OK;
+}
+
+int mi355_cwire_activity_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams,
+                               int nframes, int cell_w, int cell_h, uint32_t min_count, int accumulate, void *d_cells, void *d_summary) {
+    int B;
+    ActGeom g{};
+    if (int rc = check_activity(c, d_cwire, nullptr, d_cwire && h_counts && h_escapes, nstreams, nframes, cell_w, cell_h, min_count, d_cells,
+                                d_summary, &B, &g))
+        return rc;
+    if (B == 0) return MI355_OK;
+    CwireHeaders hdr{h_counts, h_escapes, B};
+    if (int rc = hdr.check(true, c->n)) return rc;
+    std::vector<CwaFrame> fr((size_t)B);   // B <= max_batch: the scratch of the one-stream client holds them
+    uint32_t cbase = 0;
+    for (int b = 0; b < B; b++) {
+        const CwireHeaders::Frame f = hdr.next();
+        fr[b] = CwaFrame{f.pos, f.n, f.e, cbase, cwa_chunks(f.n)};
+        cbase += fr[b].nc;
+    }
+    const CoalesceRegion out[] = {
+        {d_cells, 4 * (uint64_t)nstreams * g.cells, "d_cells overlaps the input stream"},
+        {d_summary, 32 * (uint64_t)nstreams, "d_summary overlaps the input stream"},
+    };
+    const uintptr_t in = (uintptr_t)d_cwire;
+    for (const CoalesceRegion &r : out) {
+        const uintptr_t o = (uintptr_t)r.p;
+        if (in < o + (uintptr_t)r.bytes && o < in + (uintptr_t)hdr.pos) return fail(MI355_ERR_INVALID, r.what);
+    }
+    if (int rc = use_device(c)) return rc;
+    CwaArgs a{};
+    a.cwire = (const uint8_t *)d_cwire;
+    a.ftab = c->cwa_ftab;
+    a.chunk = c->cwa_chunk;
+    a.dir = c->cwa_dir;
+    a.n = c->n;
+    a.ntiles = cwa_tiles(c->n);
+    HIP_TRY(launch_cwire_activity(a, fr.data(), nstreams, nframes, g, accumulate != 0, (uint32_t *)d_cells, (uint32_t *)d_summary, c->stream));
+    return MI355_OK;
+}
+
 // client/opencv.cpp:50-66 on the compact stream, on the host.  A frame is validated whole before any byte of the state
 // changes, so a malformed frame leaves the state as the frames before it made it.
 int mi355_cwire_apply_host(uint8_t *state, size_t frame_bytes, const void *cwire, size_t cwire_bytes, int nframes,

@@ -221,6 +221,23 @@ struct CwbInitArgs {
 };
 hipError_t launch_cwire_budget(const CwaArgs &a, const CwaFrame *records, int nstreams, const uint32_t *budget, uint32_t thr0,
                                uint32_t *hist, uint32_t *thresholds, const CwcOut &o, hipStream_t s);
+// mi355_(cwire_)activity_batch: per stream, a grid of counts of the entries of its nframes records (batch index s*nframes + t)
+// per cell of cell_w x cell_h pixels, and 8 summary words (include/mi355diff.h).  Divisors travel with floor(2^32 / d).
+struct ActDiv {
+    uint32_t d, m;   // m = floor(2^32 / d), 2^32 - 1 for d = 1
+};
+ActDiv act_divisor(uint32_t d);   // d >= 1
+struct ActGeom {
+    uint32_t n;                      // bytes per frame
+    ActDiv width, cell_w, cell_h;    // pixels
+    uint32_t grid_w, cells;          // cells per row of the grid, cells per stream
+    uint32_t min_count;
+};
+// compact form: a.state / a.out / a.stride unused; accumulate == false: grids and summaries are cleared first
+hipError_t launch_cwire_activity(const CwaArgs &a, const CwaFrame *records, int nstreams, int nframes, const ActGeom &g, bool accumulate,
+                                 uint32_t *cells, uint32_t *summary, hipStream_t s);
+hipError_t launch_activity(const uint32_t *d_offsets, const int32_t *xs, int nstreams, int nframes, const ActGeom &g, bool accumulate,
+                           uint32_t *cells, uint32_t *summary, hipStream_t s);
 
 // filters.hip -- every per-frame kernel takes a FrameBatch: frame f lives at base + f*stride
 struct FrameBatch {

@@ -14,7 +14,9 @@
 //   k_cwc_*               : a burst of compact records per stream summed into ONE record / segment per stream, from the records
 //                           alone (mi355_cwire_coalesce_batch / _cwire_batch);
 //   k_cwb_*               : one record per stream thinned to an entry budget, the caller's states reverted where entries are
-//                           dropped (mi355_cwire_budget_cwire_batch).
+//                           dropped (mi355_cwire_budget_cwire_batch);
+//   k_act_*               : where the entries of each stream's records land: a grid of counts per cell, a bounding box and the
+//                           peak cell per stream (mi355_cwire_activity_batch; mi355_activity_batch from the arrays).
 //
 // The first two are index-driven byte scatter/copy: HBM-latency work with 5 bytes of traffic per entry, no
 // arithmetic worth naming.
@@ -729,22 +731,26 @@ struct CwaBlock {
     uint32_t word, dw;
 };
 
+// DIFF == false: the codes only (dw stays 0), for the walks that do not look at the differences (k_act_tile).
+template <bool DIFF = true>
 __device__ __forceinline__ CwaBlock cwa_block_load(const CwaArgs &a, const CwaFrame &f, uint32_t k, int lane) {
     const uint32_t d = k / 4 + lane;
     CwaBlock b{0u, 0u};
     if (k < f.n && 4 * d < f.n) {
         const CwireSections<const uint8_t> sec = cwa_sections(a, f);
         b.word = sec.code32()[d];
-        b.dw = sec.diff32()[d];
+        if (DIFF) b.dw = sec.diff32()[d];
     }
     return b;
 }
 
-// Record f's entries from directory word dr = {first entry, its escape rank, running index before it} on, added to the tile
-// [lo, hi) in LDS (s[0] is byte lo).  b: the first block (cwa_block_load at dr.x).  One wave.  The decode loop of the GPU
-// clients, once: k_cwa_apply runs it per frame of a slice, k_cwa_apply_multi per stream.
-__device__ __forceinline__ void cwa_apply_record(uint8_t *s, const CwaArgs &a, const CwaFrame &f, const uint4 dr, CwaBlock b,
-                                                 uint32_t lo, uint32_t hi, int lane) {
+// Record f's entries from directory word dr = {first entry, its escape rank, running index before it} on: op(idx, diff byte)
+// for every entry with lo <= idx < hi.  b: the first block (cwa_block_load at dr.x).  One wave.  The decode loop of the GPU
+// clients, once: k_cwa_apply runs it per frame of a slice, k_cwa_apply_multi per stream, the coalescer, the budget and the
+// motion grid per record of a tile.  DIFF == false: the differences are not loaded and op gets 0.
+template <bool DIFF, class Op>
+__device__ __forceinline__ void cwa_walk_record(const CwaArgs &a, const CwaFrame &f, const uint4 dr, CwaBlock b, uint32_t lo,
+                                                uint32_t hi, int lane, Op op) {
     const CwireSections<const uint8_t> sec = cwa_sections(a, f);
     const uint32_t *code = sec.code32(), *esc = sec.esc32(), *dif = sec.diff32();
     uint32_t k = dr.x, rank = dr.y, x = dr.z;
@@ -753,7 +759,7 @@ __device__ __forceinline__ void cwa_apply_record(uint8_t *s, const CwaArgs &a, c
         const uint32_t ka = k & ~3u, d = ka / 4 + lane;
         if (!first) {
             b.word = 4 * d < f.n ? code[d] : 0u;
-            b.dw = 4 * d < f.n ? dif[d] : 0u;
+            if (DIFF) b.dw = 4 * d < f.n ? dif[d] : 0u;
         }
         first = false;
         bool in[4], fl[4];
@@ -770,11 +776,17 @@ __device__ __forceinline__ void cwa_apply_record(uint8_t *s, const CwaArgs &a, c
         for (int j = 0; j < 4; j++) {
             xi += inc[j];
             const uint32_t idx = xi - 1u;   // (inc 0: a bad escape or a masked entry, nothing to apply)
-            if (inc[j] && idx >= lo && idx < hi) s[idx - lo] = (uint8_t)(s[idx - lo] + (b.dw >> (8 * j)));
+            if (inc[j] && idx >= lo && idx < hi) op(idx, (uint8_t)(b.dw >> (8 * j)));
         }
         k = ka + 256;
         if (x >= hi) break;   // the next entry's index is at least x
     }
+}
+
+// ... added to the tile [lo, hi) in LDS (s[0] is byte lo)
+__device__ __forceinline__ void cwa_apply_record(uint8_t *s, const CwaArgs &a, const CwaFrame &f, const uint4 dr, CwaBlock b,
+                                                 uint32_t lo, uint32_t hi, int lane) {
+    cwa_walk_record<true>(a, f, dr, b, lo, hi, lane, [=](uint32_t idx, uint8_t d) { s[idx - lo] = (uint8_t)(s[idx - lo] + d); });
 }
 
 __global__ __launch_bounds__(64) void k_cwa_apply(const CwaArgs a, int nframes) {
@@ -941,10 +953,13 @@ __global__ __launch_bounds__(64) void k_cwa_apply_multi_stream(const CwaArgs a, 
 // stored as dwords inside, bytes at the ragged edges: neighbouring workgroups share dwords of the code and diff sections and
 // never read-modify-write one.  Malformed content: both tile kernels compute the same tile from the same bytes, so the facts
 // and the record agree whatever the records held.
-// The stream's summed tile [lo, hi) in LDS (s: kCwaTile bytes; s[0] is byte lo); false: no record has an entry in the tile
-// and s was not touched.  The ballot passes and the walk of k_cwa_apply_multi_stream without a state and output frames.
-__device__ __forceinline__ bool cwc_sum_tile(uint8_t *s, const CwaArgs &a, int nframes, uint32_t st, uint32_t tile, uint32_t lo,
-                                             uint32_t hi, int lane) {
+// The records of stream st that have an entry in the tile, in order: the ballot passes and the walk of
+// k_cwa_apply_multi_stream without a state and output frames.  clear() runs once, before the first such record, and
+// record(f, dr, b) per record (the caller's LDS: a barrier follows clear and every record); false: no record has an entry in
+// the tile and neither ran.  DIFF: cwa_block_load's.
+template <bool DIFF, class Clear, class Record>
+__device__ __forceinline__ bool cwa_tile_records(const CwaArgs &a, int nframes, uint32_t st, uint32_t tile, int lane, Clear clear,
+                                                 Record record) {
     const size_t b0 = (size_t)st * nframes;   // the stream's first batch index
     bool any = false;
     for (int base = 0; base < nframes; base += 64) {
@@ -959,7 +974,7 @@ __device__ __forceinline__ bool cwc_sum_tile(uint8_t *s, const CwaArgs &a, int n
         const uint64_t set = __ballot(touch);
         if (!set) continue;
         if (!any) {
-            for (uint32_t i = lane; i < kCwaTile / 16; i += 64) ((cwa_u32x4 *)s)[i] = cwa_u32x4{0u, 0u, 0u, 0u};
+            clear();
             any = true;
         }
         const int cnt = nframes - base < 64 ? nframes - base : 64;
@@ -967,7 +982,7 @@ __device__ __forceinline__ bool cwc_sum_tile(uint8_t *s, const CwaArgs &a, int n
         int jn = __ffsll((unsigned long long)set) - 1;
         CwaFrame f1 = a.ftab[b0 + base + jn];
         uint4 d1 = a.dir[(b0 + base + jn) * a.ntiles + tile];
-        CwaBlock b1 = cwa_block_load(a, f1, d1.x, lane);
+        CwaBlock b1 = cwa_block_load<DIFF>(a, f1, d1.x, lane);
         __syncthreads();
         while (jn < cnt) {
             const int j = jn;
@@ -979,13 +994,25 @@ __device__ __forceinline__ bool cwc_sum_tile(uint8_t *s, const CwaArgs &a, int n
             if (jn < cnt) {
                 f1 = a.ftab[b0 + base + jn];
                 d1 = a.dir[(b0 + base + jn) * a.ntiles + tile];
-                b1 = cwa_block_load(a, f1, d1.x, lane);
+                b1 = cwa_block_load<DIFF>(a, f1, d1.x, lane);
             }
-            cwa_apply_record(s, a, f, dr, b, lo, hi, lane);
+            record(f, dr, b);
             __syncthreads();
         }
     }
     return any;
+}
+
+// The stream's summed tile [lo, hi) in LDS (s: kCwaTile bytes; s[0] is byte lo); false: no record has an entry in the tile
+// and s was not touched.
+__device__ __forceinline__ bool cwc_sum_tile(uint8_t *s, const CwaArgs &a, int nframes, uint32_t st, uint32_t tile, uint32_t lo,
+                                             uint32_t hi, int lane) {
+    return cwa_tile_records<true>(
+        a, nframes, st, tile, lane,
+        [=]() {
+            for (uint32_t i = lane; i < kCwaTile / 16; i += 64) ((cwa_u32x4 *)s)[i] = cwa_u32x4{0u, 0u, 0u, 0u};
+        },
+        [&](const CwaFrame &f, const uint4 dr, const CwaBlock b) { cwa_apply_record(s, a, f, dr, b, lo, hi, lane); });
 }
 
 // What a lane's 64 bytes of the summed tile hold: bit i of the mask = byte 64*lane + i is not 0
@@ -1378,6 +1405,203 @@ __global__ __launch_bounds__(64) void k_cwb_emit(const CwaArgs a, const CwcOut o
     cwc_emit_tile<true>(s, (uint8_t *)s_code32, (uint8_t *)s_diff32, fact, o, seg, n, fp0, cwire_record_escapes(fp1 - fp0, n), lo, lane);
 }
 
+// ---- mi355_(cwire_)activity_batch: where the entries of a stream's records land, as a grid of counts and a box ----------------
+// An entry with byte index x < N is a changed byte of pixel p = x / 3, column p % width, row p / width; it counts 1 in cell
+// (row / cell_h) * grid_w + column / cell_w of its stream's grid.  Nothing but the records is read.  Behind the directory of the
+// nstreams*nframes records:
+//   k_act_clear   (skipped when the call accumulates)  : the grids to 0, the summaries to the empty values
+//   k_act_tile    (grid: tiles x streams, one wave)    : a tile no record lands in returns on its directory words; the others
+//                                                        count their entries per PIXEL in LDS (a tile holds at most 1366 pixels;
+//                                                        an LDS atomic per entry, no global one), then fold the pixels to cells:
+//                                                        64 consecutive pixels a round, the runs of one cell summed with a scan
+//                                                        (indices ascend, so the cells along a row form runs) and ONE global
+//                                                        atomic per run; entries and box: a wave reduction, then one atomic per
+//                                                        word and tile
+//   k_act_summary (grid: streams)                      : active cells, peak and its least index from the finished grid
+// The arrays form (k_act_entries) replaces the tile kernel: a lane per entry, its segment by binary search in the offsets as in
+// k_apply_multi, equal neighbouring cells merged by the same scan.  It is not tuned further.
+// All divisors are uniform across a launch: ActDiv holds floor(2^32 / d), the quotient estimate mulhi(n, m) is at most 1 short
+// (n * m / 2^32 > n / d - 1 for every n < 2^32), and one comparison mends it -- exact for every width and cell size.
+__device__ __forceinline__ uint32_t act_div(uint32_t n, const ActDiv dv) {
+    const uint32_t q = __umulhi(n, dv.m);
+    return n - q * dv.d >= dv.d ? q + 1u : q;
+}
+
+// The cell of pixel p, and its column and row
+__device__ __forceinline__ uint32_t act_cell(uint32_t p, const ActGeom &g, uint32_t &px, uint32_t &py) {
+    py = act_div(p, g.width);
+    px = p - py * g.width.d;
+    return act_div(py, g.cell_h) * g.grid_w + act_div(px, g.cell_w);
+}
+
+// c is added to *dst, the lanes of a wave that follow each other with the same dst (a run) by ONE atomic of the run's first lane.
+// Every lane of the wave calls; dst == nullptr with c == 0 for a lane that has nothing.
+__device__ __forceinline__ void act_add_runs(uint32_t *dst, uint32_t c, int lane) {
+    const uint64_t prev = __shfl_up((unsigned long long)(uintptr_t)dst, 1, 64);
+    const bool head = lane == 0 || prev != (uint64_t)(uintptr_t)dst;
+    const uint64_t heads = __ballot(head);
+    const uint32_t incl = wave_inclusive_scan_shfl(c);
+    const uint64_t above = lane == 63 ? 0ull : heads & ~((2ull << lane) - 1ull);   // the heads of the runs behind this lane's
+    const int last = above ? __ffsll((unsigned long long)above) - 2 : 63;          // the run's last lane
+    const uint32_t run = (uint32_t)__shfl((int)incl, last, 64) - incl + c;
+    if (head && run) atomicAdd(dst, run);
+}
+
+// What a lane saw -> the stream's summary words 0 .. 4, one atomic per word by lane 0 (nothing when the wave counted nothing)
+struct ActBox {
+    uint32_t total = 0, x0 = ~0u, y0 = ~0u, x1 = 0, y1 = 0;
+    __device__ __forceinline__ void add(uint32_t c, uint32_t px, uint32_t py) {
+        total += c;
+        x0 = px < x0 ? px : x0;
+        y0 = py < y0 ? py : y0;
+        x1 = px > x1 ? px : x1;
+        y1 = py > y1 ? py : y1;
+    }
+    __device__ __forceinline__ void flush(uint32_t *sum, int lane) {
+#pragma unroll
+        for (int k = 32; k >= 1; k >>= 1) {
+            const uint32_t ox0 = __shfl_xor(x0, k, 64), oy0 = __shfl_xor(y0, k, 64), ox1 = __shfl_xor(x1, k, 64), oy1 = __shfl_xor(y1, k, 64);
+            total += __shfl_xor(total, k, 64);
+            x0 = ox0 < x0 ? ox0 : x0;
+            y0 = oy0 < y0 ? oy0 : y0;
+            x1 = ox1 > x1 ? ox1 : x1;
+            y1 = oy1 > y1 ? oy1 : y1;
+        }
+        if (lane == 0 && total) {
+            atomicAdd(sum + 0, total);
+            atomicMin(sum + 1, x0);
+            atomicMin(sum + 2, y0);
+            atomicMax(sum + 3, x1);
+            atomicMax(sum + 4, y1);
+        }
+    }
+};
+
+__global__ __launch_bounds__(256) void k_act_clear(uint32_t *cells, uint32_t *summary, size_t ncells /* of all streams */, uint32_t nstreams) {
+    const size_t gid = (size_t)blockIdx.x * 256u + threadIdx.x, step = (size_t)gridDim.x * 256u;
+    for (size_t i = gid; i < ncells; i += step) cells[i] = 0u;
+    for (size_t i = gid; i < 8 * (size_t)nstreams; i += step) summary[i] = (i & 7u) == 1u || (i & 7u) == 2u ? ~0u : 0u;
+}
+
+constexpr uint32_t kActPixels = (kCwaTile + 2) / 3 + 1;   // pixels a tile can touch: byte 4096*t is channel t % 3 of its pixel
+
+__global__ __launch_bounds__(64) void k_act_tile(const CwaArgs a, int nframes, const ActGeom g, uint32_t *cells, uint32_t *summary) {
+    __shared__ uint32_t s_cnt[kActPixels];
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    const uint32_t hi = lo + len;
+    const uint32_t p0 = lo / 3u, np = (hi - 1u) / 3u - p0 + 1u;   // the tile's pixels: p0 .. p0 + np - 1, np <= kActPixels
+    const bool any = cwa_tile_records<false>(
+        a, nframes, st, tile, lane,
+        [&]() {
+            for (uint32_t i = lane; i < kActPixels; i += 64) s_cnt[i] = 0u;
+        },
+        [&](const CwaFrame &f, const uint4 dr, const CwaBlock b) {
+            cwa_walk_record<false>(a, f, dr, b, lo, hi, lane, [&](uint32_t idx, uint8_t) { atomicAdd(&s_cnt[idx / 3u - p0], 1u); });
+        });
+    if (!any) return;
+    uint32_t *grid = cells + (size_t)st * g.cells;
+    ActBox box;
+    for (uint32_t q0 = 0; q0 < np; q0 += 64) {
+        const uint32_t q = q0 + lane;
+        const uint32_t c = q < np ? s_cnt[q] : 0u;
+        if (!__ballot(c != 0u)) continue;
+        uint32_t *dst = nullptr;
+        if (q < np) {   // (p < N / 3 = width * height: a cell of the grid, also where c is 0)
+            uint32_t px, py;
+            dst = grid + act_cell(p0 + q, g, px, py);
+            if (c) box.add(c, px, py);
+        }
+        act_add_runs(dst, c, lane);
+    }
+    box.flush(summary + 8 * (size_t)st, lane);
+}
+
+// lds != 0: the nseg + 1 offsets fit the launch's dynamic LDS (k_apply_multi's rule)
+__global__ __launch_bounds__(256) void k_act_entries(const uint32_t *offsets, const int32_t *xs, uint32_t nseg, const ActDiv nframes,
+                                                     const ActGeom g, uint32_t *cells, uint32_t *summary, int lds) {
+    extern __shared__ uint32_t s_off[];
+    const uint32_t *off = offsets;
+    if (lds) {
+        for (uint32_t j = threadIdx.x; j <= nseg; j += 256) s_off[j] = offsets[j];
+        __syncthreads();
+        off = s_off;
+    }
+    const int lane = threadIdx.x & 63;
+    const uint32_t first = off[0], end = off[nseg];
+    const uint32_t step = gridDim.x * 256u;
+    // a wave takes 64 consecutive entries a round, all of its lanes every round (the merge below is a wave operation)
+    for (uint64_t base = (uint64_t)first + blockIdx.x * 256u + (threadIdx.x & ~63u); base < end; base += step) {
+        const uint64_t i = base + lane;
+        const uint32_t x = i < end ? (uint32_t)xs[i] : ~0u;
+        const bool live = i < end && x < g.n;
+        uint32_t st = 0, px = 0, py = 0;
+        uint32_t *dst = nullptr;
+        if (live) {
+            st = act_div(apply_multi_segment(off, nseg, (uint32_t)i), nframes);
+            dst = cells + (size_t)st * g.cells + act_cell(x / 3u, g, px, py);
+        }
+        act_add_runs(dst, live ? 1u : 0u, lane);
+        // entries and box: one set of atomics for the wave when its entries are of one stream, else one per lane
+        const uint64_t lives = __ballot(live);
+        if (!lives) continue;
+        const uint32_t st0 = (uint32_t)__shfl((int)st, __ffsll((unsigned long long)lives) - 1, 64);
+        ActBox box;
+        if (live) box.add(1u, px, py);
+        if (__ballot(live && st != st0)) {
+            if (live) {
+                uint32_t *sum = summary + 8 * (size_t)st;
+                atomicAdd(sum + 0, 1u);
+                atomicMin(sum + 1, px);
+                atomicMin(sum + 2, py);
+                atomicMax(sum + 3, px);
+                atomicMax(sum + 4, py);
+            }
+        } else {
+            box.flush(summary + 8 * (size_t)st0, lane);
+        }
+    }
+}
+
+// Words 5 .. 7 of the stream's summary from its grid: cells of at least min_count, the largest count and the least index that has it
+__global__ __launch_bounds__(256) void k_act_summary(const uint32_t *cells, uint32_t *summary, uint32_t ncells /* of a stream */,
+                                                     uint32_t min_count) {
+    __shared__ uint32_t s_active[4];
+    __shared__ uint64_t s_best[4];
+    const uint32_t *grid = cells + (size_t)blockIdx.x * ncells;
+    uint32_t active = 0;
+    uint64_t best = 0;   // {count, ~index}: the greatest is the largest count at the least index; 0: no cell counts anything
+    for (uint32_t i = threadIdx.x; i < ncells; i += 256) {
+        const uint32_t v = grid[i];
+        active += v >= min_count ? 1u : 0u;
+        const uint64_t key = ((uint64_t)v << 32) | (uint32_t)~i;
+        if (v && key > best) best = key;
+    }
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) {
+        active += __shfl_xor(active, k, 64);
+        const uint64_t o = __shfl_xor((unsigned long long)best, k, 64);
+        if (o > best) best = o;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_active[threadIdx.x >> 6] = active;
+        s_best[threadIdx.x >> 6] = best;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++) {
+            active += s_active[w];
+            if (s_best[w] > best) best = s_best[w];
+        }
+        uint32_t *sum = summary + 8 * (size_t)blockIdx.x;
+        sum[5] = active;
+        sum[6] = (uint32_t)(best >> 32);
+        sum[7] = best ? ~(uint32_t)best : 0u;
+    }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 uint32_t cwa_chunks(uint32_t n) { return n ? (n + kCwaChunk - 1) / kCwaChunk : 1u; }
 uint32_t cwa_tiles(uint32_t nbytes) { return (nbytes + kCwaTile - 1) / kCwaTile; }
@@ -1463,6 +1687,38 @@ hipError_t launch_cwire_budget(const CwaArgs &a, const CwaFrame *records, int ns
     hipLaunchKernelGGL(k_cwc_scan<true>, dim3(nstreams), dim3(256), 0, s, a, o);
     hipLaunchKernelGGL(k_cwc_place<true>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, nstreams);
     if (a.ntiles) hipLaunchKernelGGL(k_cwb_emit, tiles, dim3(64), 0, s, a, o, (const uint32_t *)hist, thr0);
+    return hipGetLastError();
+}
+
+ActDiv act_divisor(uint32_t d) { return ActDiv{d, d > 1u ? (uint32_t)(0x100000000ull / d) : ~0u}; }
+
+static void launch_act_clear(const ActGeom &g, int nstreams, uint32_t *cells, uint32_t *summary, hipStream_t s) {
+    const size_t ncells = (size_t)nstreams * g.cells;
+    const size_t blocks = ((ncells > 8 * (size_t)nstreams ? ncells : 8 * (size_t)nstreams) + 255u) / 256u;
+    hipLaunchKernelGGL(k_act_clear, dim3((uint32_t)(blocks > 2048u ? 2048u : blocks)), dim3(256), 0, s, cells, summary, ncells,
+                       (uint32_t)nstreams);
+}
+
+hipError_t launch_cwire_activity(const CwaArgs &a, const CwaFrame *records, int nstreams, int nframes, const ActGeom &g, bool accumulate,
+                                 uint32_t *cells, uint32_t *summary, hipStream_t s) {
+    if (nstreams <= 0 || nframes <= 0) return hipSuccess;
+    if (a.ntiles) launch_cwa_directory(a, records, nstreams * nframes, s);
+    if (!accumulate) launch_act_clear(g, nstreams, cells, summary, s);
+    if (a.ntiles) hipLaunchKernelGGL(k_act_tile, dim3(a.ntiles * (uint32_t)nstreams), dim3(64), 0, s, a, nframes, g, cells, summary);
+    hipLaunchKernelGGL(k_act_summary, dim3(nstreams), dim3(256), 0, s, (const uint32_t *)cells, summary, g.cells, g.min_count);
+    return hipGetLastError();
+}
+
+hipError_t launch_activity(const uint32_t *d_offsets, const int32_t *xs, int nstreams, int nframes, const ActGeom &g, bool accumulate,
+                           uint32_t *cells, uint32_t *summary, hipStream_t s) {
+    if (nstreams <= 0 || nframes <= 0) return hipSuccess;
+    if (!accumulate) launch_act_clear(g, nstreams, cells, summary, s);
+    // device-side counts: a fixed grid strides over whatever the segments hold
+    const size_t words = (size_t)nstreams * nframes + 1;
+    const bool lds = words <= 8192;   // 32 KiB; more segments than that search the offsets where they are
+    hipLaunchKernelGGL(k_act_entries, dim3(1024), dim3(256), lds ? words * sizeof(uint32_t) : 0, s, d_offsets, xs, (uint32_t)(words - 1),
+                       act_divisor((uint32_t)nframes), g, cells, summary, lds ? 1 : 0);
+    hipLaunchKernelGGL(k_act_summary, dim3(nstreams), dim3(256), 0, s, (const uint32_t *)cells, summary, g.cells, g.min_count);
     return hipGetLastError();
 }
 

@@ -97,6 +97,11 @@ SYMBOLS = {
     "mi355_cwire_budget_cwire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "mi355_cwire_budget_entries": (C.c_size_t, [C.c_size_t, C.c_size_t]),
+    "mi355_activity_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int,
+                                       C.c_void_p, C.c_void_p]),
+    "mi355_cwire_activity_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]),
+    "mi355_activity_cells": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mi355_wire_bytes": (C.c_size_t, [C.c_int, C.c_uint64]),
     "mi355_apply_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                     C.c_size_t]),

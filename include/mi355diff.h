@@ -88,7 +88,8 @@ typedef struct mi355_config {
  *      only); + mi355_apply_multi_stream_batch, mi355_apply_multi_stream_wire_batch, mi355_apply_multi_stream_cwire_batch
  *      (additions only); + mi355_cwire_coalesce_batch, mi355_cwire_coalesce_cwire_batch (additions only);
  *      + mi355_exec_cwire, mi355_pipe_submit_cwire, mi355_pipe_wait_cwire, MI355_PREPARE_EXEC_CWIRE (additions only);
- *      + mi355_cwire_budget_cwire_batch, mi355_cwire_budget_entries (additions only) */
+ *      + mi355_cwire_budget_cwire_batch, mi355_cwire_budget_entries (additions only);
+ *      + mi355_activity_batch, mi355_cwire_activity_batch, mi355_activity_cells (additions only) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -544,6 +545,71 @@ int mi355_cwire_budget_cwire_batch(mi355_core *core, const void *d_cwire, const 
  * the largest n <= frame_bytes with 8 + 2*pad4(n) + 4*min(n, frame_bytes/256) <= record_bytes (an escape spans at least 256
  * bytes of the frame), 0 when record_bytes < 8.  A sender turns its per-socket byte budget into h_budget[s] with it. */
 size_t mi355_cwire_budget_entries(size_t frame_bytes, size_t record_bytes);
+
+/* Where a camera moves: per stream, a grid of counts of its records' entries and a bounding box, made on the GPU from the records
+ * a node already holds -- a recorder that keeps footage only while something moves, a wall that frames the active cameras, a
+ * sender that hands its socket budget to the cameras with motion download 32 bytes per camera instead of 4n bytes of indices.
+ * Inputs, batch index b = s*nframes + t (nframes == 1: one tick of nstreams cameras; nstreams == 1: one stream's batch):
+ *   mi355_activity_batch        d_offsets, uint32[nstreams*nframes + 1], over d_xs -- what mi355_diff_multi_batch /
+ *                               mi355_diff_multi_stream_batch wrote (d_diff is not needed); d_xs is read as uint32
+ *   mi355_cwire_activity_batch  compact records back to back where h_counts[b] / h_escapes[b] put them; the header words in the
+ *                               buffer are skipped, not trusted, as in mi355_apply_multi_stream_cwire_batch
+ *   Semantics: an entry with byte index x < N is a changed byte of pixel p = x / 3, column px = p % width, row py = p / width, and
+ *   counts 1 in cell (py / cell_h) * grid_w + px / cell_w (mi355_activity_cells gives grid_w and the cells per stream).  An index
+ *   >= N contributes nothing.  Counts are of changed BYTES, the unit of h_pos and n: a pixel whose three channels changed counts
+ *   3, an index present in two records of a burst counts twice.
+ *   Outputs, per stream s: d_cells, uint32[nstreams][grid_w*grid_h], the entries of the stream's nframes records per cell;
+ *   d_summary, uint32[nstreams][8]:
+ *     0     entries counted (x < N)
+ *     1, 2  x0, y0: least column and row of a counted entry, in pixels; UINT32_MAX when word 0 is 0
+ *     3, 4  x1, y1: greatest column and row, inclusive; 0 when word 0 is 0
+ *     5     active cells: cells whose count is >= min_count
+ *     6     peak: the largest cell count
+ *     7     index of the peak cell, the lowest among equals; 0 when word 6 is 0
+ *   accumulate == 0: the nstreams grids are cleared and the summaries set to the empty values first.  accumulate != 0: the call
+ *   adds onto what d_cells and d_summary hold -- from an earlier call with the same geometry and nstreams, or the empty values:
+ *   counts and word 0 add (uint32 wrap-around), the box widens, words 5 to 7 are recomputed from the accumulated grids.  A burst
+ *   in one call equals its records fed one tick at a time with accumulate set; a running motion picture over a time window is a
+ *   sequence of accumulating calls.
+ *   Guarantees: nothing is written outside d_cells (4 * nstreams * cells bytes) and d_summary (32 * nstreams bytes); the core's
+ *   state is neither read nor written.  Malformed compact content under consistent headers: the guarantees of
+ *   mi355_apply_multi_stream_cwire_batch -- nothing is read outside the input span, an escape ranked at or past e and an index
+ *   >= N contribute nothing; only that stream's own grid and summary are otherwise unspecified.
+ *   Refused with MI355_ERR_INVALID before anything is launched or written: a null core; nstreams or nframes < 0; nstreams*nframes
+ *   > max_batch; cell_w < 1, cell_h < 1 or min_count < 1; d_cwire, d_offsets, d_xs, d_cells or d_summary not 4-byte aligned; with
+ *   nstreams*nframes > 0 a null pointer among the arguments, h_escapes[b] > h_counts[b], h_counts[b] > N, or (compact form) the
+ *   input span known from the host's headers overlapping either output region.  nstreams*nframes == 0 does nothing.  A cell larger
+ *   than the frame is valid: a grid of one cell.
+ * Asynchronous on the core's stream, behind the last expansion of this core as every consumer of a packed stream is:
+ * mi355_diff_multi_batch followed by mi355_activity_batch on one core needs no synchronisation in between; with a caller's stream
+ * everything runs on it in call order.  Nothing is allocated inside the call; the compact form uses the directory scratch of
+ * mi355_apply_cwire_batch and nothing else of the core.
+ * Compact form: the directory kernels of mi355_apply_cwire_batch on the nstreams*nframes records, a clear launch (skipped when
+ * accumulating), then a grid of 4096-byte tiles x streams, one wave per tile: the wave finds the records of its stream that have
+ * an entry in the tile (a lane per record, a ballot per 64) and returns if there are none -- no state byte moves, the cost follows
+ * the changes; else it walks those entries with the decode loop of the apply calls, counts them per pixel in LDS (a tile holds at
+ * most 1366 pixels; no global atomic per entry), folds the pixels to cells 64 at a time -- indices ascend, so the cells along a row
+ * form runs, and a scan sums each run -- with one global atomic per run, and reduces entries and box in the wave to one atomic per
+ * word.  One workgroup per stream then reduces the finished grid to words 5 to 7.  Row, column and cell come from exact divisions
+ * by multipliers the host prepares, for every width and cell size.
+ * Arrays form: the clear and summary launches around ONE launch in which a lane takes an entry, finds its segment by binary search
+ * in the offsets (as mi355_apply_multi_batch does) and a wave merges equal neighbouring cells before its atomics.  This form is
+ * not tuned further.
+ * Not measured yet: tools/bench_multi.py --legs activity --streams 4,16,64 writes profiles/multi_activity.json (microseconds per
+ * record of the compact form, 16x16 cells, 1080p, median of five rounds with the spread, webcam-like input and a block moving on
+ * a still background, S = 4, 16, 64 with T = 1 and S = 16 with T = 16, against mi355_apply_multi_stream_cwire_batch without output
+ * frames on the same records in the same run on the same board -- the same directory kernels and entry walk, plus the state
+ * tiles it moves).  The expectation to test -- no slower than that apply at any point by more than the rounds' spread -- is
+ * neither met nor missed until that file exists.
+ * DESIGN.md section 4, "Where a record lands: motion grids". */
+int mi355_activity_batch(mi355_core *core, const void *d_offsets, const void *d_xs, int nstreams, int nframes, int cell_w,
+                         int cell_h, uint32_t min_count, int accumulate, void *d_cells, void *d_summary);
+int mi355_cwire_activity_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
+                               int nstreams, int nframes, int cell_w, int cell_h, uint32_t min_count, int accumulate,
+                               void *d_cells, void *d_summary);
+/* Host only, no core: cells of the grid; *grid_w = ceil(width / cell_w), *grid_h = ceil(height / cell_h) (either may be NULL);
+ * returns grid_w * grid_h, 0 (and 0 in both) for width, height, cell_w or cell_h < 1. */
+size_t mi355_activity_cells(int width, int height, int cell_w, int cell_h, int *grid_w, int *grid_h);
 
 /* The client's side, client/opencv.cpp:50-66: for every frame in order, state[xs[i]] += diff[i] (uint8
  * wrap-around) on the core's state (a client core is a core whose state was set to the received base frame,

@@ -62,6 +62,14 @@ sender's rate control, in microseconds per stream, ONE JSON line for all S:
                re-diff a caller has without the call -- and it still lacks the threshold choice.
 Every pass of a timed window works on its own copy of the S states (restored outside the window).
 
+The activity leg (--legs activity, a run of its own: `--legs activity --streams 4,16,64 > profiles/multi_activity.json`) measures
+the motion grids, in microseconds per record, ONE JSON line: S = 4, 16, 64 (--streams) with T = 1 and S = 16 with T = 16, on both
+inputs of the burst-client leg:
+  activity     mi355_cwire_activity_batch, 16x16 cells, the grids cleared by every call;
+  burst_apply  mi355_apply_multi_stream_cwire_batch without output frames on the same records: the same directory kernels and
+               the same entry walk, plus the state tiles it moves.
+The expectation to test: `activity` no slower than `burst_apply` at any point by more than the rounds' spread (`verdict`).
+
 Input of the other legs: ONE webcam stream of S + K + 1 frames; stream s shows frame s + j at step j, so every tick of every stream is the
 step between two consecutive webcam frames, and a tick's S frames are one contiguous region.  j walks 1 .. K and back."""
 import argparse
@@ -524,6 +532,79 @@ def run_burst_client(W, H, S, T, rounds, kind):
     return out
 
 
+def run_activity(W, H, S, T, rounds, kind, cell=16):
+    """The activity leg for one (S, T) and one input -> its dictionary."""
+    import numpy as np
+    from cudavideostream_amd import CUDACore, activity_cells, cwire_bytes_max
+    dev = torch.device("cuda", 0)
+    n, B = 3 * W * H, S * T
+    passes = 2 * max(1, 1024 // B)                     # ~2 k records per timed window
+    if kind == "webcam":                                # run_burst's input: one stream cut into S pieces
+        _, web = synth.webcam_stream(B + 1, W, H, device=dev)
+        web = web.reshape(B + 1, n)
+        states0, fwd = web[0:B:T].clone(), web[1:].reshape(S, T, n)
+    else:
+        states0, fwd = local_streams(S, T, W, H, dev)
+    # ---- the records, as a sender's mi355_diff_multi_stream_cwire_batch makes them
+    cwcap = cwire_bytes_max(n, B)
+    d_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+    d_pos = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+    d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
+    srv_states = states0.clone()
+    with CUDACore(W, H, max_batch=B) as server:
+        torch.cuda.synchronize()
+        server.diff_multi_stream_cwire_batch(fwd, srv_states, S, T, d_off, d_pos, d_cw, cwcap)
+        server.synchronize()
+    pos = d_pos.cpu().numpy().astype(np.int64)
+    off = d_off.cpu().numpy().view(np.uint32).astype(np.int64)
+    counts = np.diff(off).astype(np.uint32)
+    escapes = ((np.diff(pos) - 8 - 2 * ((counts.astype(np.int64) + 3) & ~3)) // 4).astype(np.uint32)
+    recs = d_cw[:int(pos[B])].clone()
+    del d_cw, fwd
+    ncells = activity_cells(W, H, cell, cell)[0]
+    d_cells = torch.empty(S * ncells, dtype=torch.int32, device=dev)
+    d_sum = torch.empty(S * 8, dtype=torch.int32, device=dev)
+    states = states0.clone()
+    core = CUDACore(W, H, max_batch=B)
+    torch.cuda.synchronize()
+
+    def leg_activity():
+        for _ in range(passes):
+            core.cwire_activity_batch(recs, counts, escapes, S, T, cell, cell, d_cells, d_sum)
+        core.synchronize()
+
+    def leg_apply():
+        for _ in range(passes):
+            core.apply_multi_stream_cwire_batch(recs, counts, escapes, S, T, states)
+        core.synchronize()
+
+    table = {"activity": leg_activity, "burst_apply": leg_apply}
+    times = {}
+    for r in range(rounds + 1):                        # round 0 warms both legs up and is dropped
+        for name, leg in table.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            leg()
+            dt = time.perf_counter() - t0
+            if r:
+                times.setdefault(name, []).append(dt * 1e6 / (passes * B))
+    # every counted entry is in the grids, and every stream's count is its records'
+    summ = d_sum.cpu().numpy().view(np.uint32).reshape(S, 8)
+    per_stream = counts.astype(np.int64).reshape(S, T).sum(axis=1)
+    assert (summ[:, 0] == per_stream).all()
+    assert (d_cells.cpu().numpy().view(np.uint32).astype(np.int64).reshape(S, ncells).sum(axis=1) == per_stream).all()
+    out = {"input": kind, "streams": S, "frames": T, "passes": passes, "cell": cell, "cells_per_stream": ncells,
+           "changed_bytes_per_record": round(int(counts.sum()) / B, 1), "active_cells_per_stream": round(float(summ[:, 5].mean()), 1)}
+    for name in table:
+        out[name + "_us_per_record"] = stats(times[name])
+    med = {k: statistics.median(v) for k, v in times.items()}
+    spread = max(max(v) - min(v) for v in times.values())
+    out["activity_over_burst_apply"] = round(med["activity"] / med["burst_apply"], 3)
+    out["no_slower_than_burst_apply"] = bool(med["activity"] <= med["burst_apply"] + spread)
+    core.close()
+    return out
+
+
 def run_coalesce(W, H, S, T, rounds, kind):
     """The coalesce leg for one (S, T) and one input -> its dictionary.  coalesce: mi355_cwire_coalesce_cwire_batch on the
     burst's records, nothing else.  state_route: what a relay did before -- mi355_apply_multi_stream_cwire_batch onto states it
@@ -702,7 +783,7 @@ def main():
     ap.add_argument("--steps", type=int, default=8, help="K: webcam frames a stream walks through")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--legs", default="multi,cores_loop,pairs",
-                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or budget alone")
+                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or budget alone; or activity alone")
     ap.add_argument("--frames", default="4,16,64", help="burst, burst_client and coalesce legs: T, frames per stream and call")
     a = ap.parse_args()
     have = load_library()
@@ -751,6 +832,18 @@ def main():
             torch.cuda.empty_cache()
         print(json.dumps({"bench": "multi_budget", "size": f"{W}x{H}", "input": "synth.webcam_stream", "rounds": a.rounds,
                           "budget": per}), flush=True)
+        return
+    if a.legs == "activity":
+        points = [(S, 1) for S in (int(v) for v in a.streams.split(","))] + [(16, 16)]
+        per = []
+        for S, T in points:
+            for kind in ("webcam", "local"):
+                per.append(run_activity(W, H, S, T, a.rounds, kind))
+                print(f"activity S={S} T={T} {kind}: done", file=sys.stderr, flush=True)
+                torch.cuda.empty_cache()
+        print(json.dumps({"bench": "multi_activity", "size": f"{W}x{H}", "rounds": a.rounds, "activity": per,
+                          "verdict": "no slower than burst_apply at every point" if all(p["no_slower_than_burst_apply"] for p in per)
+                          else "slower than burst_apply at some point"}), flush=True)
         return
     for S in (int(v) for v in a.streams.split(",")):
         run(W, H, S, a.steps, a.rounds, set(a.legs.split(",")), have)

@@ -39,6 +39,10 @@
 // them with one mi355_apply_multi_cwire_batch.  After every burst each camera's state at the receiver must equal the frame of
 // a host client (mi355_cwire_apply_host) that applied all K original records, and the sender's state.  The line also says how
 // many bytes the relay received and how many it forwarded.
+// --compact --multi S --activity CELL [--burst K --burst-client]: after every tick (or burst) the receiver also asks where its
+// cameras move: mi355_cwire_activity_batch on the records it is about to apply, square cells of CELL pixels -> a grid of changed
+// bytes per cell and eight summary words per camera.  Checked against a plain C++ count over records decoded here; the box and the
+// active cells of every camera's last tick (or burst) are printed.
 // --compact --per-frame: the per-frame server, one host frame per call and no device pointer in sight.  The sender feeds
 // host frames through mi355_pipe_submit_cwire, four in flight, and writes each frame's record to the pipe with ONE write()
 // from the pinned buffer it arrived in; the receiver -- a thread with no core -- reads header and body, applies the record
@@ -46,8 +50,9 @@
 // (mi355_exec on a second core: frame[xs[i]] += diff[i], client/opencv.cpp:64-66).
 //
 //   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B]
-//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]]]]
+//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL]]]
 //   exit status 0 = all checks passed
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -106,8 +111,92 @@ static bool through_pipe(int wfd, int rfd, const uint8_t *src, uint8_t *dst, siz
     return true;
 }
 
+// --activity CELL (see the head of the file): the receiver's motion grids of the records in rx, against a count made here
+struct ActivityCheck {
+    mi355_core *core = nullptr;
+    int w = 0, h = 0, cell = 0, S = 0, gw = 0, gh = 0, calls = 0;
+    size_t cells = 0;
+    void *d_cells = nullptr, *d_summary = nullptr;
+    std::vector<uint32_t> got_cells, got_sum, want_cells, want_sum;
+
+    int open(mi355_core *c, int w_, int h_, int cell_, int S_) {
+        core = c; w = w_; h = h_; cell = cell_; S = S_;
+        cells = mi355_activity_cells(w, h, cell, cell, &gw, &gh);
+        if (!cells) { fprintf(stderr, "--activity CELL needs CELL >= 1\n"); return 2; }
+        OK(mi355_dev_alloc(core, &d_cells, sizeof(uint32_t) * cells * S));
+        OK(mi355_dev_alloc(core, &d_summary, sizeof(uint32_t) * 8 * S));
+        got_cells.resize(cells * S); want_cells.resize(cells * S);
+        got_sum.resize((size_t)8 * S); want_sum.resize((size_t)8 * S);
+        return 0;
+    }
+    // the nb records of each of the S cameras: back to back in rx (and uploaded to d_rx), headers counts / escapes
+    int run(const void *d_rx, const uint8_t *rx, const uint32_t *counts, const uint32_t *escapes, int nb, int t) {
+        if (!cell) return 0;
+        OK(mi355_cwire_activity_batch(core, d_rx, counts, escapes, S, nb, cell, cell, 1, 0, d_cells, d_summary));
+        OK(mi355_download(core, got_cells.data(), d_cells, sizeof(uint32_t) * got_cells.size()));
+        OK(mi355_download(core, got_sum.data(), d_summary, sizeof(uint32_t) * got_sum.size()));
+        calls++;
+        const uint64_t n = (uint64_t)3 * w * h;
+        std::fill(want_cells.begin(), want_cells.end(), 0u);
+        size_t p = 0;
+        for (int s = 0; s < S; s++) {
+            uint32_t *grid = &want_cells[cells * s], *sum = &want_sum[(size_t)8 * s];
+            uint32_t total = 0, x0 = UINT32_MAX, y0 = UINT32_MAX, x1 = 0, y1 = 0;
+            for (int k = 0; k < nb; k++) {
+                const uint32_t cnt = counts[s * nb + k], esc = escapes[s * nb + k];
+                const uint8_t *code = rx + p + 8, *escb = code + ((cnt + 3u) & ~3u);
+                uint64_t x = 0;   // running index + 1
+                for (uint32_t i = 0, r = 0; i < cnt; i++) {
+                    uint32_t g = code[i];
+                    if (g == 255) memcpy(&g, escb + 4 * (size_t)r++, 4);
+                    x += (uint64_t)g + 1;
+                    if (x > n) continue;
+                    const uint32_t px = (uint32_t)(((x - 1) / 3) % w), py = (uint32_t)(((x - 1) / 3) / w);
+                    grid[(size_t)(py / cell) * gw + px / cell]++;
+                    total++;
+                    if (px < x0) x0 = px;
+                    if (py < y0) y0 = py;
+                    if (px > x1) x1 = px;
+                    if (py > y1) y1 = py;
+                }
+                p += mi355_cwire_frame_bytes(cnt, esc);
+            }
+            uint32_t active = 0, peak = 0, at = 0;
+            for (size_t i = 0; i < cells; i++) {
+                if (grid[i] >= 1) active++;
+                if (grid[i] > peak) { peak = grid[i]; at = (uint32_t)i; }
+            }
+            const uint32_t want[8] = {total, x0, y0, x1, y1, active, peak, at};
+            memcpy(sum, want, sizeof want);
+        }
+        if (got_cells != want_cells) { fprintf(stderr, "tick %d: motion grids != the count over the decoded records\n", t); return 1; }
+        if (got_sum != want_sum) { fprintf(stderr, "tick %d: motion summaries != the count over the decoded records\n", t); return 1; }
+        return 0;
+    }
+    // ", "activity": {...}" for the result line: box and active cells of every camera's last tick (or burst)
+    std::string json() const {
+        if (!cell) return "";
+        std::string o = ", \"activity\": {\"cell\": " + std::to_string(cell) + ", \"grid\": [" + std::to_string(gw) + ", " + std::to_string(gh) +
+                        "], \"checked_calls\": " + std::to_string(calls) + ", \"cameras\": [";
+        for (int s = 0; s < S; s++) {
+            const uint32_t *m = &got_sum[(size_t)8 * s];
+            o += std::string(s ? ", " : "") + "{\"entries\": " + std::to_string(m[0]) + ", \"box\": ";
+            if (m[0]) o += "[" + std::to_string(m[1]) + ", " + std::to_string(m[2]) + ", " + std::to_string(m[3]) + ", " + std::to_string(m[4]) + "]";
+            else o += "null";
+            o += ", \"active_cells\": " + std::to_string(m[5]) + "}";
+        }
+        return o + "]}";
+    }
+    int close() {
+        if (!cell) return 0;
+        OK(mi355_dev_free(core, d_cells));
+        OK(mi355_dev_free(core, d_summary));
+        return 0;
+    }
+};
+
 // --compact --multi S (see the head of the file)
-static int run_multi(int w, int h, int T, int S) {
+static int run_multi(int w, int h, int T, int S, int activity) {
     const size_t n = (size_t)3 * w * h;
     mi355_config cfg;
     memset(&cfg, 0, sizeof cfg);
@@ -125,6 +214,9 @@ static int run_multi(int w, int h, int T, int S) {
     OK(mi355_dev_alloc(server, &d_cw, cw_cap));
     OK(mi355_dev_alloc(client, &d_rx, cw_cap));
     OK(mi355_dev_alloc(client, &d_cstates, (size_t)S * n));
+    ActivityCheck act;
+    if (activity)
+        if (int rc = act.open(client, w, h, activity, S)) return rc;
     int fds[2];
     if (pipe(fds) != 0) return 1;
     // every camera's base frame: the server's states, and through the pipe the client's (opencv.cpp:38-46 per camera)
@@ -171,6 +263,7 @@ static int run_multi(int w, int h, int T, int S) {
         }
         if (p != cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
         OK(mi355_upload(client, d_rx, rx.data(), cb));
+        if (int rc = act.run(d_rx, rx.data(), counts.data(), escapes.data(), 1, t)) return rc;
         OK(mi355_apply_multi_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, d_cstates, n));
         // ---- checks
         OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
@@ -190,11 +283,12 @@ static int run_multi(int w, int h, int T, int S) {
     for (void *q : srv) OK(mi355_dev_free(server, q));
     OK(mi355_dev_free(client, d_rx));
     OK(mi355_dev_free(client, d_cstates));
+    if (int rc = act.close()) return rc;
     mi355_destroy(server);
     mi355_destroy(client);
     printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"width\": %d, \"height\": %d, \"ticks\": %d, "
-           "\"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d}\n",
-           S, w, h, T, changed, sent_bytes, mi355_wire_bytes(T * S, changed), (size_t)T * S * n, max_err);
+           "\"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d%s}\n",
+           S, w, h, T, changed, sent_bytes, mi355_wire_bytes(T * S, changed), (size_t)T * S * n, max_err, act.json().c_str());
     return 0;
 }
 
@@ -444,7 +538,7 @@ static int run_multi_burst(int w, int h, int T, int S, int K) {
 }
 
 // --compact --multi S --burst K --burst-client (see the head of the file)
-static int run_multi_burst_client(int w, int h, int T, int S, int K) {
+static int run_multi_burst_client(int w, int h, int T, int S, int K, int activity) {
     const size_t n = (size_t)3 * w * h;
     mi355_config cfg;
     memset(&cfg, 0, sizeof cfg);
@@ -464,6 +558,9 @@ static int run_multi_burst_client(int w, int h, int T, int S, int K) {
     OK(mi355_dev_alloc(client, &d_rx, cw_cap));
     OK(mi355_dev_alloc(client, &d_cstates, (size_t)S * n));
     OK(mi355_dev_alloc(client, &d_shown, (size_t)B * n));
+    ActivityCheck act;
+    if (activity)
+        if (int rc = act.open(client, w, h, activity, S)) return rc;
     int fds[2];
     if (pipe(fds) != 0) return 1;
     std::vector<uint8_t> bases((size_t)S * n), host_frames((size_t)S * n), frames((size_t)B * n), s_states((size_t)S * n),
@@ -519,6 +616,7 @@ static int run_multi_burst_client(int w, int h, int T, int S, int K) {
             if (b > a) OK(mi355_upload(client, (uint8_t *)d_rx + a, rx.data() + a, b - a));
         }
         sent_bytes += cb;
+        if (int rc = act.run(d_rx, rx.data(), counts.data(), escapes.data(), nb, t0)) return rc;
         // ---- client: the whole burst in one call, every frame in between into d_shown
         OK(mi355_apply_multi_stream_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, nb, d_cstates, n, d_shown, n));
         OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
@@ -543,12 +641,14 @@ static int run_multi_burst_client(int w, int h, int T, int S, int K) {
     for (void *q : srv) OK(mi355_dev_free(server, q));
     void *cli[] = {d_rx, d_cstates, d_shown};
     for (void *q : cli) OK(mi355_dev_free(client, q));
+    if (int rc = act.close()) return rc;
     mi355_destroy(server);
     mi355_destroy(client);
     printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"burst\": %d, \"burst_client\": true, \"sender_calls\": %d, "
            "\"receiver_calls\": %d, \"width\": %d, \"height\": %d, \"ticks\": %d, \"changed_bytes\": %zu, \"wire_bytes\": %zu, "
-           "\"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d}\n",
-           S, K, calls, calls, w, h, T, changed, sent_bytes, mi355_wire_bytes(T * S, changed), (size_t)T * S * n, max_err);
+           "\"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d%s}\n",
+           S, K, calls, calls, w, h, T, changed, sent_bytes, mi355_wire_bytes(T * S, changed), (size_t)T * S * n, max_err,
+           act.json().c_str());
     return 0;
 }
 
@@ -851,7 +951,7 @@ static int run_per_frame(int w, int h, int T) {
 }
 
 int main(int argc, char **argv) {
-    int w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0;
+    int w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0, activity = -1;
     long budget = -1;
     bool compact = false, direct = false, gpu_client = false, burst_client = false, coalesce = false, per_frame = false;
     for (int i = 1; i < argc; i++) {
@@ -872,6 +972,7 @@ int main(int argc, char **argv) {
         else if (k == "--frames") T = v; else if (k == "--batch") B = v;
         else if (k == "--multi") multi = v;
         else if (k == "--burst") burst = v;
+        else if (k == "--activity") activity = v < 0 ? 0 : v;
         else if (k == "--budget") budget = atol(argv[i + 1]) < 0 ? 0 : atol(argv[i + 1]);
     }
     if (burst && (!multi || burst < 0)) { fprintf(stderr, "--burst K needs --multi S and K >= 1\n"); return 2; }
@@ -884,16 +985,21 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--budget BYTES needs --compact --multi S alone\n");
         return 2;
     }
+    if (activity >= 0 && (activity == 0 || !compact || !multi || budget >= 0 || coalesce || (burst && !burst_client))) {
+        fprintf(stderr, "--activity CELL needs CELL >= 1 and --compact --multi S, alone or with --burst K --burst-client\n");
+        return 2;
+    }
+    if (activity < 0) activity = 0;
     if (per_frame) {
         if (!compact || direct || gpu_client || multi) { fprintf(stderr, "--per-frame needs --compact alone\n"); return 2; }
         return run_per_frame(w, h, T);
     }
     if (multi) {
         if (!compact || direct || gpu_client || multi < 0) { fprintf(stderr, "--multi S needs --compact alone and S >= 1\n"); return 2; }
-        if (burst_client) return run_multi_burst_client(w, h, T, multi, burst);
+        if (burst_client) return run_multi_burst_client(w, h, T, multi, burst, activity);
         if (coalesce) return run_multi_burst_coalesce(w, h, T, multi, burst);
         if (budget >= 0) return run_multi_budget(w, h, T, multi, budget);
-        return burst ? run_multi_burst(w, h, T, multi, burst) : run_multi(w, h, T, multi);
+        return burst ? run_multi_burst(w, h, T, multi, burst) : run_multi(w, h, T, multi, activity);
     }
     const size_t n = (size_t)3 * w * h;
     mi355_config cfg;
