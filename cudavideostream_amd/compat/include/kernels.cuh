@@ -103,6 +103,11 @@ public:
     // memory; no state is involved.  Blocking, like budget_multi; nstreams*nframes <= MI355_MAX_BATCH.
     void activity_multi(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, int nstreams, int nframes, int cell_w,
                         int cell_h, uint32_t min_count, int accumulate, void *d_cells, void *d_summary);
+    // Before any of the calls above trusts what arrived (include/mi355diff.h, mi355_cwire_check_batch): one verdict of four words
+    // per record at d_verdicts (uint32[nrecords][4], DEVICE memory) -- {MI355_CWIRE_BAD_* flags, 0: well-formed and canonical;
+    // 255 codes; first entry at or past the frame's end, n: none; 1 + the last index, saturated} -- from the records alone, laid
+    // out and described as for apply_multi.  No state is involved.  Blocking; nrecords <= MI355_MAX_BATCH.
+    void check_multi(const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nrecords, void *d_verdicts);
 };
 
 static_assert(sizeof(CUDACore) == 160, "must match the reference's object size (LP64)");

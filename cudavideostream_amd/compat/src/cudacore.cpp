@@ -168,6 +168,11 @@ void CUDACore::activity_multi(const void *d_cwire, const uint32_t *counts, const
     MI355_CHECK(mi355_synchronize(core_));
 }
 
+void CUDACore::check_multi(const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nrecords, void *d_verdicts) {
+    MI355_CHECK(mi355_cwire_check_batch(core_, d_cwire, h_counts, h_escapes, nrecords, d_verdicts));
+    MI355_CHECK(mi355_synchronize(core_));
+}
+
 size_t CUDACore::chunkt_size() { return 32; }  // sizeof(long4), kernels.cu:27,527-529
 
 void CUDACore::alloc_arrays(uint8_t **h_frame, uint8_t **n_frame, uint8_t **o_frame, int **h_xs, int r,

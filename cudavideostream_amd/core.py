@@ -471,6 +471,18 @@ class CUDACore:
                                                       int(nstreams), int(nframes), int(cell_w), int(cell_h), int(min_count),
                                                       int(bool(accumulate)), _ptr(d_cells), _ptr(d_summary)))
 
+    # ... and, before any of them trusts what arrived: is every record well-formed and canonical
+    def cwire_check_batch(self, d_cwire, counts, escapes, nrecords, d_verdicts):
+        """One verdict per compact record (headers counts / escapes, back to back) into d_verdicts, uint32[nrecords][4]:
+        {lib.CWIRE_BAD_* flags (0: well-formed and canonical), 255 codes, first entry at or past the frame's end (n: none),
+        1 + the last decoded index, saturated}.  No state is read or written; cwire_check_host is the same on the host."""
+        self._hold(d_cwire, d_verdicts)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+        assert counts.size >= nrecords and escapes.size >= nrecords
+        _l.check(self._lib.mi355_cwire_check_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
+                                                   int(nrecords), _ptr(d_verdicts)))
+
     def wire_bytes(self, nframes, entries):
         return self._lib.mi355_wire_bytes(nframes, entries)
 
@@ -667,3 +679,18 @@ def cwire_apply_host(state, buf, nframes):
         err.consumed = consumed.value
         raise err
     return consumed.value
+
+
+def cwire_check_host(buf, counts, escapes, frame_bytes):
+    """The verdicts of cwire_check_batch computed on the host (no GPU, no core): uint32[nrecords, 4] for the records of `buf`
+    that the headers counts / escapes describe, on a frame of frame_bytes bytes.  Headers that cannot be followed (more escapes
+    than entries, more entries than frame bytes, records past the end of buf) raise lib.Mi355Error."""
+    L = _l.load()
+    buf = np.ascontiguousarray(np.frombuffer(buf, np.uint8) if isinstance(buf, (bytes, bytearray)) else buf, dtype=np.uint8)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+    assert counts.size == escapes.size
+    verdicts = np.zeros((counts.size, 4), np.uint32)
+    _l.check(L.mi355_cwire_check_host(int(frame_bytes), buf.ctypes.data, buf.size, counts.ctypes.data, escapes.ctypes.data,
+                                      counts.size, verdicts.ctypes.data))
+    return verdicts

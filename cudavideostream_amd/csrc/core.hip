@@ -1683,6 +1683,87 @@ int mi355_cwire_apply_host(uint8_t *state, size_t frame_bytes, const void *cwire
     return MI355_OK;
 }
 
+// ---- mi355_cwire_check_host / _batch: one verdict of four words per record (include/mi355diff.h) ---------------------------
+// The definition: the decode rule of the GPU clients with a running total that cannot wrap (frame_bytes < 2^32 - 1 and every
+// step adds at most 2^32, so a total that has passed 2^33 is frozen: it stays above frame_bytes and above the saturation point).
+int mi355_cwire_check_host(size_t frame_bytes, const void *cwire, size_t cwire_bytes, const uint32_t *h_counts,
+                           const uint32_t *h_escapes, int nrecords, uint32_t *verdicts) {
+    if (nrecords < 0) return fail(MI355_ERR_INVALID, "nrecords < 0");
+    if (frame_bytes >= 0xFFFFFFFFull) return fail(MI355_ERR_INVALID, "frame_bytes must be below 2^32 - 1");
+    if (nrecords == 0) return MI355_OK;
+    if (!cwire || !h_counts || !h_escapes || !verdicts) return fail(MI355_ERR_INVALID, "null argument");
+    uint64_t end = 0;
+    for (int b = 0; b < nrecords; b++) {
+        if (h_escapes[b] > h_counts[b]) return fail(MI355_ERR_INVALID, "frame header: more escapes than entries");
+        if (h_counts[b] > frame_bytes) return fail(MI355_ERR_INVALID, "frame header: more entries than frame bytes");
+        end += cwire_record_bytes(h_counts[b], h_escapes[b]);
+        if (end > cwire_bytes) return fail(MI355_ERR_INVALID, "the records end past cwire_bytes");
+    }
+    const uint8_t *p = (const uint8_t *)cwire;
+    uint64_t pos = 0;
+    for (int b = 0; b < nrecords; b++) {
+        const uint32_t n = h_counts[b], e = h_escapes[b];
+        const CwireSections<const uint8_t> sec(p, pos, n, e);
+        uint32_t hn, he, flags = 0, r = 0, first = n;
+        memcpy(&hn, p + pos, 4);
+        memcpy(&he, p + pos + 4, 4);
+        if (hn != n || he != e) flags |= MI355_CWIRE_BAD_HEADER;
+        uint64_t x = 0;
+        for (uint32_t k = 0; k < n; k++) {
+            uint64_t g = sec.code[k];
+            if (g == 255) {
+                if (r++ >= e) continue;   // a bad escape: the total stays
+                uint32_t v;
+                memcpy(&v, sec.esc + 4 * (size_t)(r - 1), 4);
+                if (v < 255) flags |= MI355_CWIRE_BAD_ESCAPE;
+                g = v;
+            }
+            if (x < (1ull << 33)) x += g + 1;
+            if (x > frame_bytes && first == n) first = k;
+        }
+        for (uint64_t k = n; k < cwire_pad4(n); k++)
+            if (sec.code[k] | sec.diff[k]) flags |= MI355_CWIRE_BAD_PAD;
+        if (r != e) flags |= MI355_CWIRE_BAD_CODES;
+        if (first < n) flags |= MI355_CWIRE_BAD_RANGE;
+        uint32_t *v = verdicts + 4 * (size_t)b;
+        v[0] = flags;
+        v[1] = r;
+        v[2] = first;
+        v[3] = x > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)x;
+        pos += cwire_record_bytes(n, e);
+    }
+    return MI355_OK;
+}
+
+int mi355_cwire_check_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nrecords,
+                            void *d_verdicts) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nrecords < 0 || nrecords > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nrecords outside [0, max_batch]");
+    if (nrecords == 0) return MI355_OK;
+    if (!d_cwire || !h_counts || !h_escapes || !d_verdicts) return fail(MI355_ERR_INVALID, "null argument");
+    if (((uintptr_t)d_cwire | (uintptr_t)d_verdicts) & 3u) return fail(MI355_ERR_INVALID, "d_cwire and d_verdicts must be 4-byte aligned");
+    CwireHeaders hdr{h_counts, h_escapes, nrecords};
+    if (int rc = hdr.check(true, c->n)) return rc;
+    std::vector<CwaFrame> fr((size_t)nrecords);   // nrecords <= max_batch: the scratch of the one-stream client holds them
+    uint32_t cbase = 0;
+    for (int b = 0; b < nrecords; b++) {
+        const CwireHeaders::Frame f = hdr.next();
+        fr[b] = CwaFrame{f.pos, f.n, f.e, cbase, cwa_chunks(f.n)};
+        cbase += fr[b].nc;
+    }
+    const uintptr_t in = (uintptr_t)d_cwire, o = (uintptr_t)d_verdicts;
+    if (in < o + 16 * (uintptr_t)nrecords && o < in + (uintptr_t)hdr.pos)
+        return fail(MI355_ERR_INVALID, "d_verdicts overlaps the input stream");
+    if (int rc = use_device(c)) return rc;
+    CwaArgs a{};
+    a.cwire = (const uint8_t *)d_cwire;
+    a.ftab = c->cwa_ftab;
+    a.chunk = c->cwa_chunk;
+    a.n = c->n;
+    HIP_TRY(launch_cwire_check(a, fr.data(), nrecords, (uint32_t *)d_verdicts, c->stream));
+    return MI355_OK;
+}
+
 int mi355_int_diff(mi355_core *c, const void *d_cur, const void *d_prev, void *d_out, size_t n) {
     if (!c || (n && (!d_cur || !d_prev || !d_out))) return fail(MI355_ERR_INVALID, "null argument");
     if (int rc = use_device_filter(c)) return rc;

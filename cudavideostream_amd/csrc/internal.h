@@ -238,6 +238,9 @@ hipError_t launch_cwire_activity(const CwaArgs &a, const CwaFrame *records, int 
                                  uint32_t *cells, uint32_t *summary, hipStream_t s);
 hipError_t launch_activity(const uint32_t *d_offsets, const int32_t *xs, int nstreams, int nframes, const ActGeom &g, bool accumulate,
                            uint32_t *cells, uint32_t *summary, hipStream_t s);
+// mi355_cwire_check_batch: verdicts[b][0 .. 4) of record b (include/mi355diff.h); a.ftab and a.chunk are the scratch it uses, a.n the
+// frame bytes; a.dir / a.state / a.out / a.stride / a.ntiles unused
+hipError_t launch_cwire_check(const CwaArgs &a, const CwaFrame *records, int nrecords, uint32_t *verdicts, hipStream_t s);
 
 // filters.hip -- every per-frame kernel takes a FrameBatch: frame f lives at base + f*stride
 struct FrameBatch {

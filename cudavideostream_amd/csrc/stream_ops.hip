@@ -17,6 +17,8 @@
 //                           dropped (mi355_cwire_budget_cwire_batch);
 //   k_act_*               : where the entries of each stream's records land: a grid of counts per cell, a bounding box and the
 //                           peak cell per stream (mi355_cwire_activity_batch; mi355_activity_batch from the arrays).
+//   k_cwk_*               : one verdict of four words per compact record -- is it well-formed and canonical, and where not --
+//                           from the records alone, with sums that cannot wrap (mi355_cwire_check_batch).
 //
 // The first two are index-driven byte scatter/copy: HBM-latency work with 5 bytes of traffic per entry, no
 // arithmetic worth naming.
@@ -1602,9 +1604,173 @@ __global__ __launch_bounds__(256) void k_act_summary(const uint32_t *cells, uint
     }
 }
 
+// ---- mi355_cwire_check_batch: one verdict of four words per record, from the records alone (include/mi355diff.h) ---------------
+// The chunk table of the directory (k_cwa_table, k_cwa_facts, k_cwa_scan field 0: per chunk of kCwaChunk codes the 255 codes, the
+// sum of g + 1 over the others -- at most 4096 * 255, it cannot wrap -- and the chunk's first escape rank), then two kernels of
+// its own, in which NO sum wraps: everything that can reach 2^32 is added in 64 bits and travels through the 32-bit chunk word
+// clamped to 0xFFFFFFFF.  Clamped addition of non-negative values is associative, so a prefix of clamped chunk sums, clamped,
+// is the clamped true prefix: exact below 2^32, stuck at the top above it -- all that a comparison with N < 2^32 - 1 needs.
+//   k_cwk_escsum (grid: chunks)  : + esc[r] + 1 for the chunk's ranks r < e, clamped; a used escape value < 255 and, in the
+//                                  record's last chunk, a nonzero pad byte of either section are noted in bits 16, 17 of chunk.x
+//   k_cwk_finish (grid: records) : scans the record's chunk sums (64-bit), which gives the total and the one chunk whose inclusive
+//                                  prefix is the first above N; walks that chunk with the decode step of the GPU clients for the
+//                                  least such entry; compares the header words; lane 0 stores the four words
+// No workgroup waits on another; nothing is written but the core's chunk scratch and the verdicts; reads stay inside
+// [pos, pos + record bytes) of every record: code dwords below pad4(n) / 4, escape words below e, the two header words.
+constexpr uint32_t kCwkPadBit = 1u << 16, kCwkLowBit = 1u << 17;   // beside the chunk's count of 255 codes (<= 4096) in chunk.x
+// the verdict's flags (MI355_CWIRE_BAD_* of include/mi355diff.h)
+constexpr uint32_t kCwkBadCodes = 1u, kCwkBadRange = 2u, kCwkBadPad = 4u, kCwkBadEscape = 8u, kCwkBadHeader = 16u;
+
+__global__ __launch_bounds__(256) void k_cwk_escsum(const CwaArgs a) {
+    __shared__ uint64_t s_sum[4];
+    __shared__ uint32_t s_low[4];
+    const uint32_t c = blockIdx.x;
+    const uint4 ch = a.chunk[c];
+    const CwaFrame f = a.ftab[ch.w];
+    const uint32_t r0 = ch.y < f.e ? ch.y : f.e;
+    const uint32_t r1 = f.e - r0 < ch.x ? f.e : r0 + ch.x;
+    const CwireSections<const uint8_t> sec = cwa_sections(a, f);
+    const uint32_t *esc = sec.esc32();
+    uint64_t sum = 0;
+    bool low = false;
+    for (uint32_t r = r0 + threadIdx.x; r < r1; r += 256) {
+        const uint32_t g = esc[r];
+        sum += (uint64_t)g + 1u;
+        low = low || g < 255u;
+    }
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1) sum += __shfl_xor((unsigned long long)sum, k, 64);
+    const uint64_t lows = __ballot(low);
+    if ((threadIdx.x & 63) == 0) {
+        s_sum[threadIdx.x >> 6] = sum;
+        s_low[threadIdx.x >> 6] = lows ? 1u : 0u;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint64_t total = (uint64_t)ch.z + s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];   // <= 4096 * 2^32
+        uint32_t bits = (s_low[0] | s_low[1] | s_low[2] | s_low[3]) ? kCwkLowBit : 0u;
+        if (c - f.cbase + 1 == f.nc && (f.n & 3u)) {   // the pad bytes: the top of the last dword of either section
+            const uint32_t d = f.n / 4u, used = 8u * (f.n & 3u);
+            if ((sec.code32()[d] | sec.diff32()[d]) >> used) bits |= kCwkPadBit;
+        }
+        a.chunk[c].x = ch.x | bits;
+        a.chunk[c].z = total > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)total;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_cwk_finish(const CwaArgs a, uint32_t *verdicts) {
+    __shared__ uint64_t s_pre[2][4], s_sum[2][4], s_before;
+    __shared__ uint32_t s_esc[2][4], s_chunk, s_rank, s_bits, s_cnt, s_k;
+    const uint32_t b = blockIdx.x;
+    const CwaFrame f = a.ftab[b];
+    if (threadIdx.x == 0) {
+        s_chunk = ~0u;
+        s_bits = 0u;
+        s_cnt = 0u;
+        s_k = f.n;
+    }
+    __syncthreads();
+    // the record's chunks: 255 codes, flag bits, and the prefix of the clamped sums
+    uint64_t total = 0;
+    uint32_t bits = 0, cnt = 0;
+    int buf = 0;
+    for (uint32_t i0 = 0; i0 < f.nc; i0 += 256, buf ^= 1) {
+        const uint32_t i = i0 + threadIdx.x;
+        const uint4 ch = i < f.nc ? a.chunk[f.cbase + i] : make_uint4(0u, 0u, 0u, 0u);
+        const uint64_t before = block_exclusive_scan<4>((uint64_t)ch.z, s_pre[buf], total);
+        bits |= ch.x >> 16;
+        cnt += ch.x & 0xffffu;
+        // prefixes only grow: at most one chunk starts at or below N and ends above it
+        if (i < f.nc && before <= a.n && before + ch.z > a.n) {
+            s_chunk = i;
+            s_before = before;
+            s_rank = ch.y;
+        }
+    }
+    if (bits) atomicOr(&s_bits, bits);
+    if (cnt) atomicAdd(&s_cnt, cnt);
+    __syncthreads();
+    const uint32_t ci = s_chunk;
+    if (ci != ~0u) {   // that chunk once more, for the least k with X_k > N
+        const uint32_t k0 = ci * kCwaChunk;
+        const uint32_t k1 = f.n - k0 < kCwaChunk ? f.n : k0 + kCwaChunk;
+        const CwireSections<const uint8_t> sec = cwa_sections(a, f);
+        const uint32_t *code = sec.code32(), *esc = sec.esc32();
+        uint32_t carry_e = s_rank;
+        uint64_t carry_x = s_before;
+        for (uint32_t base = k0; base < k1; base += 1024, buf ^= 1) {
+            const uint32_t d = base / 4 + threadIdx.x;
+            const bool live = 4 * d < k1;
+            const uint32_t word = live ? code[d] : 0u;
+            bool in[4], fl[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) in[j] = live && 4 * d + j < k1;
+            uint32_t wtot;
+            const uint32_t before = cwire_escapes_before(word, in, fl, wtot);
+            const uint32_t rank = block_waves_before<4>(wtot, 0, s_esc[buf], carry_e) + before;
+            uint32_t inc[4], rk[4];
+            bool bad[4];
+            cwire_decode4(word, in, fl, rank, f.e, esc, inc, bad, rk);
+            // a live entry that is not a bad escape adds g + 1 >= 1: an increment of 0 is 0xFFFFFFFF + 1 wrapped
+            uint64_t inc64[4], lsum = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                inc64[j] = in[j] && !bad[j] && inc[j] == 0u ? 0x100000000ull : inc[j];
+                lsum += inc64[j];
+            }
+            uint64_t x = block_exclusive_scan<4>(lsum, s_sum[buf], carry_x);
+            uint32_t mine = ~0u;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                x += inc64[j];
+                if (in[j] && x > a.n && mine == ~0u) mine = 4 * d + j;
+            }
+            if (mine != ~0u) atomicMin(&s_k, mine);
+            if (carry_x > a.n) break;   // (the same for every thread) the entry is in this round
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const uint32_t *hdr = (const uint32_t *)(a.cwire + f.pos);
+        const uint32_t n255 = s_cnt, k = s_k, sb = s_bits;
+        uint32_t w0 = 0;
+        if (n255 != f.e) w0 |= kCwkBadCodes;
+        if (k < f.n) w0 |= kCwkBadRange;
+        if (sb & (kCwkPadBit >> 16)) w0 |= kCwkBadPad;
+        if (sb & (kCwkLowBit >> 16)) w0 |= kCwkBadEscape;
+        if (hdr[0] != f.n || hdr[1] != f.e) w0 |= kCwkBadHeader;
+        uint32_t *v = verdicts + 4 * (size_t)b;
+        v[0] = w0;
+        v[1] = n255;
+        v[2] = k;
+        v[3] = total > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)total;
+    }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 uint32_t cwa_chunks(uint32_t n) { return n ? (n + kCwaChunk - 1) / kCwaChunk : 1u; }
 uint32_t cwa_tiles(uint32_t nbytes) { return (nbytes + kCwaTile - 1) / kCwaTile; }
+
+// mi355_cwire_check_batch: the chunk table and its first two passes are the directory's
+hipError_t launch_cwire_check(const CwaArgs &a, const CwaFrame *records, int nrecords, uint32_t *verdicts, hipStream_t s) {
+    if (nrecords <= 0) return hipSuccess;
+    uint32_t nchunks = 0;   // >= nrecords: a record of no entries has one (empty) chunk
+    CwaTableArgs h{};
+    for (int i0 = 0; i0 < nrecords; i0 += kCwaTableFrames) {
+        const int nf = nrecords - i0 < kCwaTableFrames ? nrecords - i0 : kCwaTableFrames;
+        h.first = i0;
+        for (int i = 0; i < nf; i++) {
+            h.frame[i] = records[i0 + i];
+            nchunks = records[i0 + i].cbase + records[i0 + i].nc;
+        }
+        hipLaunchKernelGGL(k_cwa_table, dim3(nf), dim3(256), 0, s, a, h);
+    }
+    hipLaunchKernelGGL(k_cwa_facts, dim3(nchunks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_cwa_scan, dim3(nrecords), dim3(256), 0, s, a, 0);
+    hipLaunchKernelGGL(k_cwk_escsum, dim3(nchunks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_cwk_finish, dim3(nrecords), dim3(256), 0, s, a, verdicts);
+    return hipGetLastError();
+}
 
 // the directory of nframes records (k_cwa_table .. k_cwa_dir)
 static void launch_cwa_directory(const CwaArgs &a, const CwaFrame *frames, int nframes, hipStream_t s) {

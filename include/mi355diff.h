@@ -89,7 +89,8 @@ typedef struct mi355_config {
  *      (additions only); + mi355_cwire_coalesce_batch, mi355_cwire_coalesce_cwire_batch (additions only);
  *      + mi355_exec_cwire, mi355_pipe_submit_cwire, mi355_pipe_wait_cwire, MI355_PREPARE_EXEC_CWIRE (additions only);
  *      + mi355_cwire_budget_cwire_batch, mi355_cwire_budget_entries (additions only);
- *      + mi355_activity_batch, mi355_cwire_activity_batch, mi355_activity_cells (additions only) */
+ *      + mi355_activity_batch, mi355_cwire_activity_batch, mi355_activity_cells (additions only);
+ *      + mi355_cwire_check_host, mi355_cwire_check_batch, MI355_CWIRE_BAD_* (additions only) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -694,6 +695,62 @@ int mi355_apply_cwire_batch(mi355_core *core, const void *d_cwire, const uint32_
  * before a bad one stay applied and *consumed = their bytes (on success: all bytes of the nframes records). */
 int mi355_cwire_apply_host(uint8_t *state, size_t frame_bytes, const void *cwire, size_t cwire_bytes, int nframes,
                            size_t *consumed);
+
+/* Checking records before they are used: one verdict of four words per record, from the record's bytes alone -- no state, so a
+ * relay that coalesces bursts, a recorder that keeps every T-th picture or a wall that asks for motion grids can tell a good
+ * record from a damaged one before it forwards, counts or applies it.  The GPU consumers of compact records promise memory
+ * safety under malformed content and nothing more; the directory kernels of mi355_apply_cwire_batch keep the running index in
+ * 32 bits, so a record whose escape values sum past 2^32 wraps to a small index and is applied somewhere inside the frame.  The
+ * check cannot wrap.
+ * The records lie back to back where h_counts[b] = n and h_escapes[b] = e put them, as in every other call of the family; the
+ * header words in the buffer are compared (BAD_HEADER) and never used to find anything.
+ *   Decode rule (that of the GPU clients), with unbounded integers: walk k = 0 .. n-1 with escape rank r = 0 and running total
+ *   X = 0; c = code[k]; c < 255: X += c + 1; else if r < e: X += esc[r] + 1, r++; else r++ and X stays (a bad escape).  X_k is X
+ *   after step k; entry k has index X_k - 1.
+ *   Verdict of record b, uint32[4]:
+ *     0  the flags below, or'ed; 0: well-formed and canonical
+ *     1  the number of 255 codes among the n codes (the final r)
+ *     2  the least k with X_k > N; n when there is none
+ *     3  min(X_{n-1}, 0xFFFFFFFF): 1 + the last decoded index, saturated; 0 for n = 0
+ *   BAD_CODES: word 1 != e.  BAD_RANGE: word 2 < n.  BAD_ESCAPE: some esc[r] < 255 with r < min(e, word 1).  BAD_PAD: one of the
+ *   2 * (pad4(n) - n) pad bytes is not zero.  BAD_HEADER: the {n, e} words in the buffer differ from h_counts[b] / h_escapes[b].
+ *   Properties: a record whose BAD_HEADER bit is clear is accepted by mi355_cwire_apply_host on a frame of N bytes exactly when
+ *   BAD_CODES and BAD_RANGE are clear.  Word 0 == 0 exactly when the record's bytes equal the canonical encoding of what it
+ *   decodes to -- what mi355_cwire_encode_batch would write.  No sum wraps: a total of 2^32 or more is BAD_RANGE, whatever it
+ *   is modulo 2^32 (N < 2^32 - 1).
+ * mi355_cwire_check_host is the definition: host memory, no alignment, no core, no HIP call.  Refused with MI355_ERR_INVALID,
+ * the verdicts untouched: a null pointer with nrecords > 0; nrecords < 0; h_escapes[b] > h_counts[b]; h_counts[b] > frame_bytes;
+ * frame_bytes >= 2^32 - 1; records that, by the headers, end past cwire_bytes.
+ * mi355_cwire_check_batch is the same on the GPU, N the core's frame bytes, d_verdicts uint32[nrecords][4], bit-identical to the
+ * host form.  Refused with MI355_ERR_INVALID before anything is launched or written: a null core; nrecords outside
+ * [0, max_batch]; with nrecords > 0 a null pointer among the arguments, h_escapes[b] > h_counts[b], h_counts[b] > N, d_cwire
+ * or d_verdicts not 4-byte aligned, or the input span known from the headers overlapping the 16 * nrecords verdict bytes.
+ * nrecords == 0 does nothing.
+ *   Guarantees: nothing is read outside the span that the host's headers give, nothing is written outside the verdicts, the
+ *   core's state is neither read nor written, nothing is allocated inside the call (the chunk table of mi355_apply_cwire_batch's
+ *   directory scratch is reused, sized for max_batch records).  Asynchronous on the core's stream, behind the last expansion of
+ *   this core: mi355_diff_multi_cwire_batch followed by the check on one core needs no synchronisation in between.
+ *   Kernels: the chunk table and the first two passes of the directory (per chunk of 4096 codes: its 255 codes and the sum of
+ *   the other codes' g + 1; per record: each chunk's first escape rank), then per chunk the escaped gaps of its ranks below e
+ *   added in 64 bits and clamped to 0xFFFFFFFF (clamped addition is associative: exact below 2^32, stuck at the top above),
+ *   with the escape values < 255 and the last chunk's pad bytes noted; then one workgroup per record scans the chunk sums, walks
+ *   the one chunk whose prefix is the first above N for word 2 with the decode step of the GPU clients, compares the header and
+ *   stores the verdict.  Four launches and one more per 128 records; the records are read about twice, no state tile moves.
+ * Not measured yet: tools/bench_multi.py --legs check --streams 4,16,64 writes profiles/multi_check.json (microseconds per record,
+ * 1080p, median of five rounds with the spread, webcam-like input and a block moving on a still background, S = 4, 16, 64 with
+ * T = 1 and S = 16 with T = 16, against mi355_apply_multi_stream_cwire_batch without output frames on the same records in the
+ * same run on the same board).  The expectation to test -- no slower than that apply at any point by more than the rounds'
+ * spread -- is neither met nor missed until that file exists.
+ * DESIGN.md section 4, "Checking records before they are used". */
+#define MI355_CWIRE_BAD_CODES   1u  /* the number of 255 codes among the n codes is not e                 */
+#define MI355_CWIRE_BAD_RANGE   2u  /* an entry decodes to an index >= N                                  */
+#define MI355_CWIRE_BAD_PAD     4u  /* a pad byte behind code[n) or diff[n) is not zero                   */
+#define MI355_CWIRE_BAD_ESCAPE  8u  /* a used escape value is < 255 (it should have been a code)          */
+#define MI355_CWIRE_BAD_HEADER 16u  /* the {n, e} words in the buffer differ from h_counts / h_escapes    */
+int mi355_cwire_check_host(size_t frame_bytes, const void *cwire, size_t cwire_bytes, const uint32_t *h_counts,
+                           const uint32_t *h_escapes, int nrecords, uint32_t *verdicts /* [nrecords][4] */);
+int mi355_cwire_check_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
+                            int nrecords, void *d_verdicts /* uint32[nrecords][4] */);
 
 /* Integer difference of tests/algorithms_benchmarks.cu:24-30 (kernel1): d[i] = cur[i] - prev[i] on
  * int32 arrays of n elements, no threshold, no pack. */

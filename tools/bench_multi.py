@@ -70,6 +70,13 @@ inputs of the burst-client leg:
                the same entry walk, plus the state tiles it moves.
 The expectation to test: `activity` no slower than `burst_apply` at any point by more than the rounds' spread (`verdict`).
 
+The check leg (--legs check, a run of its own: `--legs check --streams 4,16,64 > profiles/multi_check.json`) measures the record
+check, in microseconds per record, ONE JSON line, at the points and on the inputs of the activity leg:
+  check        mi355_cwire_check_batch: a verdict per record, no state;
+  burst_apply  mi355_apply_multi_stream_cwire_batch without output frames on the same records.
+The expectation to test: `check` no slower than `burst_apply` at any point by more than the rounds' spread (`verdict`): the check
+reads the records about twice and moves no state tile.
+
 Input of the other legs: ONE webcam stream of S + K + 1 frames; stream s shows frame s + j at step j, so every tick of every stream is the
 step between two consecutive webcam frames, and a tick's S frames are one contiguous region.  j walks 1 .. K and back."""
 import argparse
@@ -605,6 +612,76 @@ def run_activity(W, H, S, T, rounds, kind, cell=16):
     return out
 
 
+def run_check(W, H, S, T, rounds, kind):
+    """The check leg for one (S, T) and one input -> its dictionary."""
+    import numpy as np
+    from cudavideostream_amd import CUDACore, cwire_bytes_max, cwire_check_host
+    dev = torch.device("cuda", 0)
+    n, B = 3 * W * H, S * T
+    passes = 2 * max(1, 1024 // B)                     # ~2 k records per timed window
+    if kind == "webcam":                                # run_burst's input: one stream cut into S pieces
+        _, web = synth.webcam_stream(B + 1, W, H, device=dev)
+        web = web.reshape(B + 1, n)
+        states0, fwd = web[0:B:T].clone(), web[1:].reshape(S, T, n)
+    else:
+        states0, fwd = local_streams(S, T, W, H, dev)
+    # ---- the records, as a sender's mi355_diff_multi_stream_cwire_batch makes them
+    cwcap = cwire_bytes_max(n, B)
+    d_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+    d_pos = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+    d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
+    srv_states = states0.clone()
+    with CUDACore(W, H, max_batch=B) as server:
+        torch.cuda.synchronize()
+        server.diff_multi_stream_cwire_batch(fwd, srv_states, S, T, d_off, d_pos, d_cw, cwcap)
+        server.synchronize()
+    pos = d_pos.cpu().numpy().astype(np.int64)
+    off = d_off.cpu().numpy().view(np.uint32).astype(np.int64)
+    counts = np.diff(off).astype(np.uint32)
+    escapes = ((np.diff(pos) - 8 - 2 * ((counts.astype(np.int64) + 3) & ~3)) // 4).astype(np.uint32)
+    recs = d_cw[:int(pos[B])].clone()
+    del d_cw, fwd
+    d_verdicts = torch.empty(B * 4, dtype=torch.int32, device=dev)
+    states = states0.clone()
+    core = CUDACore(W, H, max_batch=B)
+    torch.cuda.synchronize()
+
+    def leg_check():
+        for _ in range(passes):
+            core.cwire_check_batch(recs, counts, escapes, B, d_verdicts)
+        core.synchronize()
+
+    def leg_apply():
+        for _ in range(passes):
+            core.apply_multi_stream_cwire_batch(recs, counts, escapes, S, T, states)
+        core.synchronize()
+
+    table = {"check": leg_check, "burst_apply": leg_apply}
+    times = {}
+    for r in range(rounds + 1):                        # round 0 warms both legs up and is dropped
+        for name, leg in table.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            leg()
+            dt = time.perf_counter() - t0
+            if r:
+                times.setdefault(name, []).append(dt * 1e6 / (passes * B))
+    # a sender's records are clean, and the device's verdicts are the host's
+    got = d_verdicts.cpu().numpy().view(np.uint32).reshape(B, 4)
+    assert not got[:, 0].any() and (got[:, 1] == escapes).all() and (got[:, 2] == counts).all()
+    assert np.array_equal(got, cwire_check_host(recs.cpu().numpy(), counts, escapes, n))
+    out = {"input": kind, "streams": S, "frames": T, "passes": passes, "changed_bytes_per_record": round(int(counts.sum()) / B, 1),
+           "record_bytes_per_record": round(int(pos[B]) / B, 1)}
+    for name in table:
+        out[name + "_us_per_record"] = stats(times[name])
+    med = {k: statistics.median(v) for k, v in times.items()}
+    spread = max(max(v) - min(v) for v in times.values())
+    out["check_over_burst_apply"] = round(med["check"] / med["burst_apply"], 3)
+    out["no_slower_than_burst_apply"] = bool(med["check"] <= med["burst_apply"] + spread)
+    core.close()
+    return out
+
+
 def run_coalesce(W, H, S, T, rounds, kind):
     """The coalesce leg for one (S, T) and one input -> its dictionary.  coalesce: mi355_cwire_coalesce_cwire_batch on the
     burst's records, nothing else.  state_route: what a relay did before -- mi355_apply_multi_stream_cwire_batch onto states it
@@ -783,7 +860,7 @@ def main():
     ap.add_argument("--steps", type=int, default=8, help="K: webcam frames a stream walks through")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--legs", default="multi,cores_loop,pairs",
-                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or budget alone; or activity alone")
+                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or budget alone; or activity alone; or check alone")
     ap.add_argument("--frames", default="4,16,64", help="burst, burst_client and coalesce legs: T, frames per stream and call")
     a = ap.parse_args()
     have = load_library()
@@ -842,6 +919,18 @@ def main():
                 print(f"activity S={S} T={T} {kind}: done", file=sys.stderr, flush=True)
                 torch.cuda.empty_cache()
         print(json.dumps({"bench": "multi_activity", "size": f"{W}x{H}", "rounds": a.rounds, "activity": per,
+                          "verdict": "no slower than burst_apply at every point" if all(p["no_slower_than_burst_apply"] for p in per)
+                          else "slower than burst_apply at some point"}), flush=True)
+        return
+    if a.legs == "check":
+        points = [(S, 1) for S in (int(v) for v in a.streams.split(","))] + [(16, 16)]
+        per = []
+        for S, T in points:
+            for kind in ("webcam", "local"):
+                per.append(run_check(W, H, S, T, a.rounds, kind))
+                print(f"check S={S} T={T} {kind}: done", file=sys.stderr, flush=True)
+                torch.cuda.empty_cache()
+        print(json.dumps({"bench": "multi_check", "size": f"{W}x{H}", "rounds": a.rounds, "check": per,
                           "verdict": "no slower than burst_apply at every point" if all(p["no_slower_than_burst_apply"] for p in per)
                           else "slower than burst_apply at some point"}), flush=True)
         return

@@ -43,6 +43,11 @@
 // cameras move: mi355_cwire_activity_batch on the records it is about to apply, square cells of CELL pixels -> a grid of changed
 // bytes per cell and eight summary words per camera.  Checked against a plain C++ count over records decoded here; the box and the
 // active cells of every camera's last tick (or burst) are printed.
+// --compact --multi S --check [--burst K --burst-client]: the receiver trusts nothing it has not checked: before it applies a tick
+// (or burst) it asks mi355_cwire_check_batch for a verdict per record and requires every record well-formed and canonical (word
+// 0 == 0), the verdicts equal to mi355_cwire_check_host's on the received bytes, and word 3 of every record equal to 1 + the
+// last byte index that the apply then changes.  Once per run it also checks a damaged copy of the first non-empty record -- one
+// code byte set to 255 -- and requires MI355_CWIRE_BAD_CODES.
 // --compact --per-frame: the per-frame server, one host frame per call and no device pointer in sight.  The sender feeds
 // host frames through mi355_pipe_submit_cwire, four in flight, and writes each frame's record to the pipe with ONE write()
 // from the pinned buffer it arrived in; the receiver -- a thread with no core -- reads header and body, applies the record
@@ -50,7 +55,7 @@
 // (mi355_exec on a second core: frame[xs[i]] += diff[i], client/opencv.cpp:64-66).
 //
 //   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B]
-//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL]]]
+//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check]]]
 //   exit status 0 = all checks passed
 #include <algorithm>
 #include <cstdint>
@@ -195,8 +200,81 @@ struct ActivityCheck {
     }
 };
 
+// --check (see the head of the file): the verdicts of the records in rx before they are applied, and what the apply then changed
+struct RecordCheck {
+    mi355_core *core = nullptr;
+    bool on = false, damaged_done = false;
+    size_t n = 0;
+    int records = 0;
+    void *d_verdicts = nullptr, *d_damaged = nullptr;
+    std::vector<uint32_t> got, want;
+
+    int open(mi355_core *c, size_t n_, int most) {
+        core = c; n = n_; on = true;
+        OK(mi355_dev_alloc(core, &d_verdicts, sizeof(uint32_t) * 4 * most));
+        OK(mi355_dev_alloc(core, &d_damaged, mi355_cwire_bytes_max(n, 1)));
+        got.resize((size_t)4 * most); want.resize((size_t)4 * most);
+        return 0;
+    }
+    // the nrec records back to back in rx (cb bytes, uploaded to d_rx), headers counts / escapes
+    int run(const void *d_rx, const uint8_t *rx, size_t cb, const uint32_t *counts, const uint32_t *escapes, int nrec, int t) {
+        if (!on) return 0;
+        OK(mi355_cwire_check_batch(core, d_rx, counts, escapes, nrec, d_verdicts));
+        OK(mi355_download(core, got.data(), d_verdicts, sizeof(uint32_t) * 4 * nrec));
+        OK(mi355_cwire_check_host(n, rx, cb, counts, escapes, nrec, want.data()));
+        if (memcmp(got.data(), want.data(), sizeof(uint32_t) * 4 * nrec) != 0) { fprintf(stderr, "tick %d: device verdicts != host verdicts\n", t); return 1; }
+        size_t p = 0;
+        for (int r = 0; r < nrec; r++) {
+            if (got[(size_t)4 * r] != 0) { fprintf(stderr, "tick %d: record %d: verdict flags %u\n", t, r, got[(size_t)4 * r]); return 1; }
+            const size_t size = mi355_cwire_frame_bytes(counts[r], escapes[r]);
+            if (!damaged_done && counts[r] > 0) {   // a copy of this record with its first plain code turned into an escape code
+                std::vector<uint8_t> copy(rx + p, rx + p + size);
+                uint32_t k = 0;
+                while (k < counts[r] && copy[8 + k] == 255) k++;
+                if (k < counts[r]) {
+                    copy[8 + k] = 255;
+                    uint32_t v[4] = {0, 0, 0, 0};
+                    OK(mi355_upload(core, d_damaged, copy.data(), size));
+                    OK(mi355_cwire_check_batch(core, d_damaged, counts + r, escapes + r, 1, d_verdicts));
+                    OK(mi355_download(core, v, d_verdicts, sizeof v));
+                    if (!(v[0] & MI355_CWIRE_BAD_CODES) || v[1] != escapes[r] + 1) {
+                        fprintf(stderr, "tick %d: the damaged copy of record %d got verdict {%u, %u, %u, %u}\n", t, r, v[0], v[1], v[2], v[3]);
+                        return 1;
+                    }
+                    damaged_done = true;
+                }
+            }
+            p += size;
+        }
+        records += nrec;
+        return 0;
+    }
+    // after the apply: record r (of the last run) turned frame `before` into `after`
+    int applied(int r, const uint8_t *before, const uint8_t *after, int t) const {
+        if (!on) return 0;
+        size_t last = n;
+        while (last > 0 && before[last - 1] == after[last - 1]) last--;
+        if (got[(size_t)4 * r + 3] != last) {
+            fprintf(stderr, "tick %d: record %d: verdict word 3 is %u, the last byte applied is %zu - 1\n", t, r, got[(size_t)4 * r + 3], last);
+            return 1;
+        }
+        return 0;
+    }
+    std::string json() const {
+        if (!on) return "";
+        return ", \"check\": {\"records\": " + std::to_string(records) + ", \"damaged_copy\": " + (damaged_done ? "\"bad_codes\"" : "null") + "}";
+    }
+    int close() {
+        if (!on) return 0;
+        if (!damaged_done) { fprintf(stderr, "--check: no record had an entry to damage\n"); return 1; }
+        OK(mi355_dev_free(core, d_verdicts));
+        OK(mi355_dev_free(core, d_damaged));
+        return 0;
+    }
+};
+
 // --compact --multi S (see the head of the file)
-static int run_multi(int w, int h, int T, int S, int activity) {
+static int run_multi(int w, int h, int T, int S, int activity, bool check) {
     const size_t n = (size_t)3 * w * h;
     mi355_config cfg;
     memset(&cfg, 0, sizeof cfg);
@@ -217,6 +295,9 @@ static int run_multi(int w, int h, int T, int S, int activity) {
     ActivityCheck act;
     if (activity)
         if (int rc = act.open(client, w, h, activity, S)) return rc;
+    RecordCheck chk;
+    if (check)
+        if (int rc = chk.open(client, n, S)) return rc;
     int fds[2];
     if (pipe(fds) != 0) return 1;
     // every camera's base frame: the server's states, and through the pipe the client's (opencv.cpp:38-46 per camera)
@@ -227,7 +308,7 @@ static int run_multi(int w, int h, int T, int S, int activity) {
     OK(mi355_upload(server, d_sstates, bases.data(), bases.size()));
     if (!through_pipe(fds[1], fds[0], bases.data(), host_frames.data(), bases.size())) return 1;
     OK(mi355_upload(client, d_cstates, host_frames.data(), host_frames.size()));
-    std::vector<uint8_t> base(n), frame(n);
+    std::vector<uint8_t> base(n), frame(n), before(check ? host_frames : std::vector<uint8_t>());   // (before: the states a tick finds)
     std::vector<uint32_t> off(S + 1), counts(S), escapes(S);
     std::vector<uint64_t> pos(S + 1);
     size_t sent_bytes = 0, changed = 0;
@@ -264,9 +345,13 @@ static int run_multi(int w, int h, int T, int S, int activity) {
         if (p != cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
         OK(mi355_upload(client, d_rx, rx.data(), cb));
         if (int rc = act.run(d_rx, rx.data(), counts.data(), escapes.data(), 1, t)) return rc;
+        if (int rc = chk.run(d_rx, rx.data(), cb, counts.data(), escapes.data(), S, t)) return rc;
         OK(mi355_apply_multi_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, d_cstates, n));
         // ---- checks
         OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
+        for (int s = 0; s < S && check; s++)
+            if (int rc = chk.applied(s, &before[(size_t)s * n], &c_states[(size_t)s * n], t)) return rc;
+        if (check) before = c_states;
         OK(mi355_download(server, s_states.data(), d_sstates, s_states.size()));
         if (memcmp(s_states.data(), c_states.data(), s_states.size()) != 0) {
             fprintf(stderr, "tick %d: client states != server states\n", t);
@@ -284,11 +369,13 @@ static int run_multi(int w, int h, int T, int S, int activity) {
     OK(mi355_dev_free(client, d_rx));
     OK(mi355_dev_free(client, d_cstates));
     if (int rc = act.close()) return rc;
+    if (int rc = chk.close()) return rc;
     mi355_destroy(server);
     mi355_destroy(client);
     printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"width\": %d, \"height\": %d, \"ticks\": %d, "
-           "\"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d%s}\n",
-           S, w, h, T, changed, sent_bytes, mi355_wire_bytes(T * S, changed), (size_t)T * S * n, max_err, act.json().c_str());
+           "\"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d%s%s}\n",
+           S, w, h, T, changed, sent_bytes, mi355_wire_bytes(T * S, changed), (size_t)T * S * n, max_err, act.json().c_str(),
+           chk.json().c_str());
     return 0;
 }
 
@@ -538,7 +625,7 @@ static int run_multi_burst(int w, int h, int T, int S, int K) {
 }
 
 // --compact --multi S --burst K --burst-client (see the head of the file)
-static int run_multi_burst_client(int w, int h, int T, int S, int K, int activity) {
+static int run_multi_burst_client(int w, int h, int T, int S, int K, int activity, bool check) {
     const size_t n = (size_t)3 * w * h;
     mi355_config cfg;
     memset(&cfg, 0, sizeof cfg);
@@ -561,6 +648,9 @@ static int run_multi_burst_client(int w, int h, int T, int S, int K, int activit
     ActivityCheck act;
     if (activity)
         if (int rc = act.open(client, w, h, activity, S)) return rc;
+    RecordCheck chk;
+    if (check)
+        if (int rc = chk.open(client, n, B)) return rc;
     int fds[2];
     if (pipe(fds) != 0) return 1;
     std::vector<uint8_t> bases((size_t)S * n), host_frames((size_t)S * n), frames((size_t)B * n), s_states((size_t)S * n),
@@ -570,7 +660,7 @@ static int run_multi_burst_client(int w, int h, int T, int S, int K, int activit
     OK(mi355_upload(server, d_sstates, bases.data(), bases.size()));
     if (!through_pipe(fds[1], fds[0], bases.data(), host_frames.data(), bases.size())) return 1;
     OK(mi355_upload(client, d_cstates, host_frames.data(), host_frames.size()));
-    std::vector<uint8_t> base(n), frame(n);
+    std::vector<uint8_t> base(n), frame(n), before(check ? host_frames : std::vector<uint8_t>());   // (before: the states a burst finds)
     std::vector<uint32_t> off(B + 1), counts(B), escapes(B);
     std::vector<uint64_t> pos(B + 1);
     size_t sent_bytes = 0, changed = 0;
@@ -617,10 +707,14 @@ static int run_multi_burst_client(int w, int h, int T, int S, int K, int activit
         }
         sent_bytes += cb;
         if (int rc = act.run(d_rx, rx.data(), counts.data(), escapes.data(), nb, t0)) return rc;
+        if (int rc = chk.run(d_rx, rx.data(), cb, counts.data(), escapes.data(), nrec, t0)) return rc;
         // ---- client: the whole burst in one call, every frame in between into d_shown
         OK(mi355_apply_multi_stream_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, nb, d_cstates, n, d_shown, n));
         OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
         OK(mi355_download(client, shown.data(), d_shown, (size_t)nrec * n));
+        for (int r = 0; r < nrec && check; r++)   // record (s, k) turned the frame after record (s, k - 1) into its own
+            if (int rc = chk.applied(r, r % nb ? &shown[(size_t)(r - 1) * n] : &before[(size_t)(r / nb) * n], &shown[(size_t)r * n], t0)) return rc;
+        if (check) before = c_states;
         OK(mi355_download(server, s_states.data(), d_sstates, s_states.size()));
         if (memcmp(s_states.data(), c_states.data(), s_states.size()) != 0) {
             fprintf(stderr, "burst at tick %d: client states != server states\n", t0);
@@ -642,13 +736,14 @@ static int run_multi_burst_client(int w, int h, int T, int S, int K, int activit
     void *cli[] = {d_rx, d_cstates, d_shown};
     for (void *q : cli) OK(mi355_dev_free(client, q));
     if (int rc = act.close()) return rc;
+    if (int rc = chk.close()) return rc;
     mi355_destroy(server);
     mi355_destroy(client);
     printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"burst\": %d, \"burst_client\": true, \"sender_calls\": %d, "
            "\"receiver_calls\": %d, \"width\": %d, \"height\": %d, \"ticks\": %d, \"changed_bytes\": %zu, \"wire_bytes\": %zu, "
-           "\"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d%s}\n",
+           "\"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d%s%s}\n",
            S, K, calls, calls, w, h, T, changed, sent_bytes, mi355_wire_bytes(T * S, changed), (size_t)T * S * n, max_err,
-           act.json().c_str());
+           act.json().c_str(), chk.json().c_str());
     return 0;
 }
 
@@ -953,7 +1048,7 @@ static int run_per_frame(int w, int h, int T) {
 int main(int argc, char **argv) {
     int w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0, activity = -1;
     long budget = -1;
-    bool compact = false, direct = false, gpu_client = false, burst_client = false, coalesce = false, per_frame = false;
+    bool compact = false, direct = false, gpu_client = false, burst_client = false, coalesce = false, per_frame = false, check = false;
     for (int i = 1; i < argc; i++) {
         if (std::string(argv[i]) == "--compact") compact = true;
         if (std::string(argv[i]) == "--direct") direct = true;
@@ -961,12 +1056,13 @@ int main(int argc, char **argv) {
         if (std::string(argv[i]) == "--burst-client") burst_client = true;
         if (std::string(argv[i]) == "--coalesce") coalesce = true;
         if (std::string(argv[i]) == "--per-frame") per_frame = true;
+        if (std::string(argv[i]) == "--check") check = true;
     }
     if (direct && !compact) { fprintf(stderr, "--direct needs --compact\n"); return 2; }
     if (gpu_client && !compact) { fprintf(stderr, "--gpu-client needs --compact\n"); return 2; }
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string k = argv[i];
-        if (k == "--compact" || k == "--direct" || k == "--gpu-client" || k == "--burst-client" || k == "--coalesce" || k == "--per-frame") { i--; continue; }
+        if (k == "--compact" || k == "--direct" || k == "--gpu-client" || k == "--burst-client" || k == "--coalesce" || k == "--per-frame" || k == "--check") { i--; continue; }
         const int v = atoi(argv[i + 1]);
         if (k == "--width") w = v; else if (k == "--height") h = v;
         else if (k == "--frames") T = v; else if (k == "--batch") B = v;
@@ -990,16 +1086,20 @@ int main(int argc, char **argv) {
         return 2;
     }
     if (activity < 0) activity = 0;
+    if (check && (!compact || !multi || budget >= 0 || coalesce || per_frame || (burst && !burst_client))) {
+        fprintf(stderr, "--check needs --compact --multi S, alone or with --burst K --burst-client\n");
+        return 2;
+    }
     if (per_frame) {
         if (!compact || direct || gpu_client || multi) { fprintf(stderr, "--per-frame needs --compact alone\n"); return 2; }
         return run_per_frame(w, h, T);
     }
     if (multi) {
         if (!compact || direct || gpu_client || multi < 0) { fprintf(stderr, "--multi S needs --compact alone and S >= 1\n"); return 2; }
-        if (burst_client) return run_multi_burst_client(w, h, T, multi, burst, activity);
+        if (burst_client) return run_multi_burst_client(w, h, T, multi, burst, activity, check);
         if (coalesce) return run_multi_burst_coalesce(w, h, T, multi, burst);
         if (budget >= 0) return run_multi_budget(w, h, T, multi, budget);
-        return burst ? run_multi_burst(w, h, T, multi, burst) : run_multi(w, h, T, multi, activity);
+        return burst ? run_multi_burst(w, h, T, multi, burst) : run_multi(w, h, T, multi, activity, check);
     }
     const size_t n = (size_t)3 * w * h;
     mi355_config cfg;
