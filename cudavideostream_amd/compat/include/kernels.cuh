@@ -108,6 +108,16 @@ public:
     // 255 codes; first entry at or past the frame's end, n: none; 1 + the last index, saturated} -- from the records alone, laid
     // out and described as for apply_multi.  No state is involved.  Blocking; nrecords <= MI355_MAX_BATCH.
     void check_multi(const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nrecords, void *d_verdicts);
+    // Resynchronising a receiver (include/mi355diff.h, "Resynchronising a receiver"), all on DEVICE memory, states laid out as for
+    // apply_multi.  digest_multi: the receiver's two words per tile of 4096 bytes, uint32[nstreams][tiles][2] (mi355_state_tiles).
+    // refresh_multi, the sender: the tiles whose digest differs from d_peer_digests (NULL: every tile) as a mask
+    // (uint32[nstreams][ceil(tiles / 32)]) and one ordinary compact record per stream that holds their nonzero bytes, laid out
+    // and bounded as coalesce_multi_stream's.  clear_tiles_multi, the receiver again: zeroes the masked tiles; apply_multi of
+    // the refresh records then makes them the sender's.  Blocking; nstreams <= MI355_MAX_BATCH.
+    void digest_multi(const void *d_states, size_t stride, int nstreams, void *d_digests);
+    void refresh_multi(const void *d_states, size_t stride, int nstreams, const void *d_peer_digests, void *d_tile_mask,
+                       void *d_offsets, void *d_frame_pos, void *d_cwire_out, size_t capacity_bytes);
+    void clear_tiles_multi(void *d_states, size_t stride, int nstreams, const void *d_tile_mask);
 };
 
 static_assert(sizeof(CUDACore) == 160, "must match the reference's object size (LP64)");

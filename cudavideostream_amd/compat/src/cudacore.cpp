@@ -173,6 +173,23 @@ void CUDACore::check_multi(const void *d_cwire, const uint32_t *h_counts, const 
     MI355_CHECK(mi355_synchronize(core_));
 }
 
+void CUDACore::digest_multi(const void *d_states, size_t stride, int nstreams, void *d_digests) {
+    MI355_CHECK(mi355_state_digest_batch(core_, d_states, stride, nstreams, d_digests));
+    MI355_CHECK(mi355_synchronize(core_));
+}
+
+void CUDACore::refresh_multi(const void *d_states, size_t stride, int nstreams, const void *d_peer_digests, void *d_tile_mask,
+                             void *d_offsets, void *d_frame_pos, void *d_cwire_out, size_t capacity_bytes) {
+    MI355_CHECK(mi355_refresh_cwire_batch(core_, d_states, stride, nstreams, d_peer_digests, d_tile_mask, d_offsets, d_frame_pos,
+                                          d_cwire_out, capacity_bytes));
+    MI355_CHECK(mi355_synchronize(core_));
+}
+
+void CUDACore::clear_tiles_multi(void *d_states, size_t stride, int nstreams, const void *d_tile_mask) {
+    MI355_CHECK(mi355_state_clear_tiles_batch(core_, d_states, stride, nstreams, d_tile_mask));
+    MI355_CHECK(mi355_synchronize(core_));
+}
+
 size_t CUDACore::chunkt_size() { return 32; }  // sizeof(long4), kernels.cu:27,527-529
 
 void CUDACore::alloc_arrays(uint8_t **h_frame, uint8_t **n_frame, uint8_t **o_frame, int **h_xs, int r,

@@ -483,6 +483,34 @@ class CUDACore:
         _l.check(self._lib.mi355_cwire_check_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
                                                    int(nrecords), _ptr(d_verdicts)))
 
+    # ... and when a record was refused or lost after all: the receiver's digests, the sender's refresh, the receiver's clear
+    def state_digest_batch(self, d_states, nstreams, d_digests, stride=None):
+        """Two words per tile of 4096 bytes of each of nstreams states (stream s at d_states + s*stride, any alignment) into
+        d_digests, uint32[nstreams][state_tiles(N)][2]; state_digest_host is the same on the host and the definition."""
+        self._hold(d_states, d_digests)
+        stride = self.total if stride is None else stride
+        _l.check(self._lib.mi355_state_digest_batch(self._h, _ptr(d_states), int(stride), int(nstreams), _ptr(d_digests)))
+
+    def refresh_cwire_batch(self, d_states, nstreams, d_peer_digests, d_tile_mask, d_offsets, d_frame_pos, d_cwire_out,
+                            capacity_bytes, stride=None):
+        """The sender's answer to a receiver's digests (None: every tile, a key frame): d_tile_mask,
+        uint32[nstreams][ceil(tiles / 32)], has the bits of the tiles whose digest differs from the sender's, and stream s's ONE
+        record at d_frame_pos[s] holds (x, state[s][x]) for the nonzero bytes of those tiles -- an ordinary compact record that
+        makes a state with those tiles cleared (state_clear_tiles_batch) equal to the sender's there.  Offsets, frame positions
+        and capacity as for cwire_coalesce_cwire_batch; the states are only read."""
+        self._hold(d_states, d_peer_digests, d_tile_mask, d_offsets, d_frame_pos, d_cwire_out)
+        stride = self.total if stride is None else stride
+        _l.check(self._lib.mi355_refresh_cwire_batch(self._h, _ptr(d_states), int(stride), int(nstreams), _ptr(d_peer_digests),
+                                                     _ptr(d_tile_mask), _ptr(d_offsets), _ptr(d_frame_pos), _ptr(d_cwire_out),
+                                                     int(capacity_bytes)))
+
+    def state_clear_tiles_batch(self, d_states, nstreams, d_tile_mask, stride=None):
+        """Zeroes the tiles of each state whose bit of d_tile_mask (refresh_cwire_batch's) is set, inside the state's N bytes
+        only; apply_multi_cwire_batch of the refresh records follows on the same stream."""
+        self._hold(d_states, d_tile_mask)
+        stride = self.total if stride is None else stride
+        _l.check(self._lib.mi355_state_clear_tiles_batch(self._h, _ptr(d_states), int(stride), int(nstreams), _ptr(d_tile_mask)))
+
     def wire_bytes(self, nframes, entries):
         return self._lib.mi355_wire_bytes(nframes, entries)
 
@@ -694,3 +722,19 @@ def cwire_check_host(buf, counts, escapes, frame_bytes):
     _l.check(L.mi355_cwire_check_host(int(frame_bytes), buf.ctypes.data, buf.size, counts.ctypes.data, escapes.ctypes.data,
                                       counts.size, verdicts.ctypes.data))
     return verdicts
+
+
+def state_tiles(frame_bytes):
+    """Tiles of 4096 bytes of a state of frame_bytes bytes (the last may be ragged): the rows of a digest array."""
+    return _l.load().mi355_state_tiles(int(frame_bytes))
+
+
+def state_digest_host(state):
+    """The digests of state_digest_batch computed on the host (no GPU, no core) and their definition: uint32[tiles, 2] for the
+    uint8 array `state` -- per tile of 4096 bytes, zero-extended, the sum of its little-endian words and the sum of their
+    position-keyed mixes, both mod 2^32."""
+    L = _l.load()
+    state = np.ascontiguousarray(np.frombuffer(state, np.uint8) if isinstance(state, (bytes, bytearray)) else state, dtype=np.uint8)
+    digests = np.zeros((L.mi355_state_tiles(state.size), 2), np.uint32)
+    _l.check(L.mi355_state_digest_host(state.ctypes.data, state.size, digests.ctypes.data))
+    return digests

@@ -1764,6 +1764,135 @@ int mi355_cwire_check_batch(mi355_core *c, const void *d_cwire, const uint32_t *
     return MI355_OK;
 }
 
+// ---- resynchronising a receiver: tile digests, refresh records, tile clears (stream_ops.hip, k_state_digest, k_rf_*) ----------
+size_t mi355_state_tiles(size_t frame_bytes) { return frame_bytes / kCwaTile + (frame_bytes % kCwaTile ? 1 : 0); }
+
+// The definition of the digest; the device forms compute the same two words per tile.
+int mi355_state_digest_host(const uint8_t *state, size_t frame_bytes, uint32_t *digests) {
+    if (frame_bytes && (!state || !digests)) return fail(MI355_ERR_INVALID, "null argument");
+    const size_t tiles = mi355_state_tiles(frame_bytes);
+    for (size_t t = 0; t < tiles; t++) {
+        const size_t lo = t * kCwaTile, len = frame_bytes - lo < kCwaTile ? frame_bytes - lo : kCwaTile;
+        uint32_t sum = 0, mix = 0;
+        for (uint32_t i = 0; i < kCwaTile / 4; i++) {
+            uint32_t w = 0;   // little-endian, the bytes past the tile's end zero
+            for (uint32_t j = 0; j < 4 && 4 * (size_t)i + j < len; j++) w |= (uint32_t)state[lo + 4 * i + j] << (8 * j);
+            uint32_t v = w ^ (0x9E3779B9u * (i + 1u));
+            v ^= v >> 16;
+            v *= 0x85EBCA6Bu;
+            v ^= v >> 13;
+            v *= 0xC2B2AE35u;
+            v ^= v >> 16;
+            sum += w;
+            mix += v;
+        }
+        const uint32_t d[2] = {sum, mix};
+        memcpy((uint8_t *)digests + 8 * t, d, 8);   // (no alignment asked of digests)
+    }
+    return MI355_OK;
+}
+
+namespace {
+// [p, p + bytes) of a resync call, for its overlap tests; an empty region overlaps nothing
+struct ResyncRegion {
+    const void *p;
+    uint64_t bytes;
+    const char *what;
+};
+bool resync_overlap(const ResyncRegion &a, const ResyncRegion &b) {
+    const uintptr_t pa = (uintptr_t)a.p, pb = (uintptr_t)b.p;
+    return a.bytes && b.bytes && pa < pb + (uintptr_t)b.bytes && pb < pa + (uintptr_t)a.bytes;
+}
+int resync_overlap_fail(const ResyncRegion &a, const ResyncRegion &b) {
+    char msg[96];
+    snprintf(msg, sizeof msg, "%s overlaps %s", a.what, b.what);
+    return fail(MI355_ERR_INVALID, msg);
+}
+ResyncRegion resync_states(const mi355_core *c, const void *d_states, size_t stride, int nstreams) {
+    return ResyncRegion{d_states, c->n ? (uint64_t)(nstreams - 1) * stride + c->n : 0, "the states"};
+}
+}  // namespace
+
+int mi355_state_digest_batch(mi355_core *c, const void *d_states, size_t stride_bytes, int nstreams, void *d_digests) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nstreams < 0 || nstreams > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams outside [0, max_batch]");
+    if (nstreams == 0) return MI355_OK;
+    if (!d_states || !d_digests) return fail(MI355_ERR_INVALID, "null argument");
+    if (stride_bytes < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
+    if ((uintptr_t)d_digests & 3u) return fail(MI355_ERR_INVALID, "d_digests must be 4-byte aligned");
+    const ResyncRegion st = resync_states(c, d_states, stride_bytes, nstreams);
+    const ResyncRegion dg{d_digests, 8 * (uint64_t)nstreams * cwa_tiles(c->n), "d_digests"};
+    if (resync_overlap(dg, st)) return resync_overlap_fail(dg, st);
+    if (int rc = use_device(c)) return rc;
+    HIP_TRY(launch_state_digest((const uint8_t *)d_states, stride_bytes, c->n, nstreams, (uint32_t *)d_digests, c->stream));
+    return MI355_OK;
+}
+
+int mi355_refresh_cwire_batch(mi355_core *c, const void *d_states, size_t stride_bytes, int nstreams, const void *d_peer_digests,
+                              void *d_tile_mask, void *d_offsets, void *d_frame_pos, void *d_cwire_out, size_t capacity_bytes) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nstreams < 0 || nstreams > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams outside [0, max_batch]");
+    if (((uintptr_t)d_peer_digests & 3u) || ((uintptr_t)d_tile_mask & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_cwire_out & 3u))
+        return fail(MI355_ERR_INVALID, "d_peer_digests, d_tile_mask, d_offsets and d_cwire_out must be 4-byte aligned");
+    if ((uintptr_t)d_frame_pos & 7u) return fail(MI355_ERR_INVALID, "d_frame_pos must be 8-byte aligned");
+    if (nstreams == 0) {   // offsets[0] = 0 and frame_pos[0] = 0 and nothing else
+        if (!d_offsets && !d_frame_pos) return MI355_OK;
+        if (int rc = use_device(c)) return rc;
+        if (d_offsets) HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(uint32_t), c->stream));
+        if (d_frame_pos) HIP_TRY(hipMemsetAsync(d_frame_pos, 0, sizeof(uint64_t), c->stream));
+        return MI355_OK;
+    }
+    if (!d_states) return fail(MI355_ERR_INVALID, "null d_states");
+    if (!d_tile_mask || !d_offsets || !d_frame_pos || !d_cwire_out) return fail(MI355_ERR_INVALID, "null output pointer");
+    if (stride_bytes < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
+    const uint32_t ntiles = cwa_tiles(c->n);
+    const ResyncRegion in[] = {
+        resync_states(c, d_states, stride_bytes, nstreams),
+        {d_peer_digests, d_peer_digests ? 8 * (uint64_t)nstreams * ntiles : 0, "the peer digests"},
+    };
+    const ResyncRegion out[] = {
+        {d_tile_mask, 4 * (uint64_t)nstreams * ((ntiles + 31u) / 32u), "d_tile_mask"},
+        {d_offsets, ((uint64_t)nstreams + 1) * sizeof(uint32_t), "d_offsets"},
+        {d_frame_pos, ((uint64_t)nstreams + 1) * sizeof(uint64_t), "d_frame_pos"},
+        {d_cwire_out, capacity_bytes, "d_cwire_out"},
+    };
+    for (size_t i = 0; i < sizeof out / sizeof out[0]; i++) {
+        for (const ResyncRegion &r : in)
+            if (resync_overlap(out[i], r)) return resync_overlap_fail(out[i], r);
+        for (size_t j = i + 1; j < sizeof out / sizeof out[0]; j++)
+            if (resync_overlap(out[i], out[j])) return resync_overlap_fail(out[i], out[j]);
+    }
+    if (int rc = use_device(c)) return rc;
+    CwaArgs a{};
+    a.chunk = c->cwa_chunk;   // one fact word per (stream, tile): nstreams <= max_batch
+    a.state = (uint8_t *)d_states;   // (only read)
+    a.stride = stride_bytes;
+    a.n = c->n;
+    a.ntiles = ntiles;
+    CwcOut o{};
+    o.offsets = (uint32_t *)d_offsets;
+    o.frame_pos = (uint64_t *)d_frame_pos;
+    o.cwire = (uint8_t *)d_cwire_out;
+    o.capacity = capacity_bytes;
+    HIP_TRY(launch_refresh(a, nstreams, (const uint32_t *)d_peer_digests, (uint32_t *)d_tile_mask, o, c->stream));
+    return MI355_OK;
+}
+
+int mi355_state_clear_tiles_batch(mi355_core *c, void *d_states, size_t stride_bytes, int nstreams, const void *d_tile_mask) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nstreams < 0 || nstreams > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams outside [0, max_batch]");
+    if (nstreams == 0) return MI355_OK;
+    if (!d_states || !d_tile_mask) return fail(MI355_ERR_INVALID, "null argument");
+    if (stride_bytes < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
+    if ((uintptr_t)d_tile_mask & 3u) return fail(MI355_ERR_INVALID, "d_tile_mask must be 4-byte aligned");
+    const ResyncRegion st = resync_states(c, d_states, stride_bytes, nstreams);
+    const ResyncRegion mk{d_tile_mask, 4 * (uint64_t)nstreams * ((cwa_tiles(c->n) + 31u) / 32u), "d_tile_mask"};
+    if (resync_overlap(mk, st)) return resync_overlap_fail(mk, st);
+    if (int rc = use_device(c)) return rc;
+    HIP_TRY(launch_state_clear_tiles((uint8_t *)d_states, stride_bytes, c->n, nstreams, (const uint32_t *)d_tile_mask, c->stream));
+    return MI355_OK;
+}
+
 int mi355_int_diff(mi355_core *c, const void *d_cur, const void *d_prev, void *d_out, size_t n) {
     if (!c || (n && (!d_cur || !d_prev || !d_out))) return fail(MI355_ERR_INVALID, "null argument");
     if (int rc = use_device_filter(c)) return rc;

@@ -241,6 +241,14 @@ hipError_t launch_activity(const uint32_t *d_offsets, const int32_t *xs, int nst
 // mi355_cwire_check_batch: verdicts[b][0 .. 4) of record b (include/mi355diff.h); a.ftab and a.chunk are the scratch it uses, a.n the
 // frame bytes; a.dir / a.state / a.out / a.stride / a.ntiles unused
 hipError_t launch_cwire_check(const CwaArgs &a, const CwaFrame *records, int nrecords, uint32_t *verdicts, hipStream_t s);
+// Resynchronising a receiver (include/mi355diff.h).  mi355_state_digest_batch: digests[s][tile][0 .. 2) of the n bytes at
+// states + s*stride
+hipError_t launch_state_digest(const uint8_t *states, size_t stride, uint32_t n, int nstreams, uint32_t *digests, hipStream_t s);
+// mi355_refresh_cwire_batch: a.state / a.stride / a.n / a.ntiles the sender's states (only read), a.chunk the per-(stream, tile)
+// facts; peer: the receiver's digests or nullptr (every tile); mask: [nstreams][ceil(ntiles / 32)]; o as for the coalescer
+hipError_t launch_refresh(const CwaArgs &a, int nstreams, const uint32_t *peer, uint32_t *mask, const CwcOut &o, hipStream_t s);
+// mi355_state_clear_tiles_batch: the tiles of states + s*stride whose bit of mask[s] is set -> 0
+hipError_t launch_state_clear_tiles(uint8_t *states, size_t stride, uint32_t n, int nstreams, const uint32_t *mask, hipStream_t s);
 
 // filters.hip -- every per-frame kernel takes a FrameBatch: frame f lives at base + f*stride
 struct FrameBatch {

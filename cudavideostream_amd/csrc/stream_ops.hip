@@ -1747,6 +1747,145 @@ __global__ __launch_bounds__(256) void k_cwk_finish(const CwaArgs a, uint32_t *v
     }
 }
 
+// ---- mi355_state_digest_batch, mi355_refresh_cwire_batch, mi355_state_clear_tiles_batch: resynchronising a receiver ------------
+// The digest of a tile (include/mi355diff.h, mi355_state_digest_host, is the definition): the tile extended with zero bytes to
+// kCwaTile bytes, read as 1024 little-endian words w_i: {sum of w_i, sum of rf_mix(w_i ^ kRfGolden * (i + 1))}, both mod 2^32.
+// Both sums commute, so a lane folds whichever words it holds and the wave adds the lanes.
+//   k_state_digest      (grid: tiles x streams, one wave) : a whole tile at a 16-byte aligned address: four 16-byte loads per lane
+//                                                           (quad 64*i + lane: each load of the wave is 1 KiB in one piece);
+//                                                           any other tile through LDS (cwa_tile_load, the rest zeroed)
+//   k_rf_facts          (grid: tiles x streams, one wave) : the sender's tile in LDS, its digest against the peer's (no peer: every
+//                                                           tile is selected); a selected tile: its mask bit (one atomic OR
+//                                                           into words cleared on the same stream) and cwc_tile_facts of its
+//                                                           bytes, any other the all-zero fact -- an empty tile to what follows
+//   k_cwc_scan<true>, k_cwc_place<true>                   : the coalescer's, unchanged
+//   k_rf_emit           (grid: tiles x streams, one wave) : k_cwc_emit with the tile loaded from the state again
+//   k_state_clear_tiles (grid: tiles x streams, one wave) : zeroes the tiles whose mask bit is set: bytes up to the first 16-byte
+//                                                           boundary, whole 16-byte stores, bytes behind the last
+// The refresh record of a stream holds (x, state[x]) for the nonzero bytes of its selected tiles: applied to a state whose
+// selected tiles are zero it makes them the sender's, whichever client applies it.
+constexpr uint32_t kRfGolden = 0x9E3779B9u;
+
+__device__ __forceinline__ uint32_t rf_mix(uint32_t v) {
+    v ^= v >> 16;
+    v *= 0x85EBCA6Bu;
+    v ^= v >> 13;
+    v *= 0xC2B2AE35u;
+    v ^= v >> 16;
+    return v;
+}
+
+// quad q of a tile (its words 4q .. 4q + 3) added to a lane's two sums
+__device__ __forceinline__ void rf_fold(const cwa_u32x4 v, uint32_t q, uint32_t &sum, uint32_t &mix) {
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) {
+        sum += v[j];
+        mix += rf_mix(v[j] ^ (kRfGolden * (4u * q + j + 1u)));
+    }
+}
+
+// The digest of the kCwaTile bytes at s (LDS), in every lane.  One wave.
+__device__ __forceinline__ uint2 rf_digest_lds(const uint8_t *s, int lane) {
+    uint32_t sum = 0, mix = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < kCwaTile / 1024; i++) rf_fold(((const cwa_u32x4 *)s)[64 * i + lane], 64 * i + lane, sum, mix);
+    return make_uint2(cwa_wave_sum(sum), cwa_wave_sum(mix));
+}
+
+// len bytes at src -> s (LDS, kCwaTile bytes), the bytes past len zero: LDS holds whatever the previous workgroup left there.
+// One wave; the tile is complete for every lane on return.
+__device__ __forceinline__ void rf_tile_load(uint8_t *s, const uint8_t *src, uint32_t len, int lane) {
+    if (len < kCwaTile) {
+        for (uint32_t i = lane; i < kCwaTile / 16; i += 64) ((cwa_u32x4 *)s)[i] = cwa_u32x4{0u, 0u, 0u, 0u};
+        __syncthreads();
+    }
+    cwa_tile_load(s, src, len, lane);
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(64) void k_state_digest(const uint8_t *states, size_t stride, uint32_t n, uint32_t ntiles,
+                                                     uint32_t *digests) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / ntiles, tile = blockIdx.x % ntiles;
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = n - lo < kCwaTile ? n - lo : kCwaTile;
+    const uint8_t *src = states + (size_t)st * stride + lo;
+    uint2 d;
+    if (len == kCwaTile && !((uintptr_t)src & 15u)) {   // (the same for every lane)
+        cwa_u32x4 v[kCwaTile / 1024];
+#pragma unroll
+        for (uint32_t i = 0; i < kCwaTile / 1024; i++) v[i] = __builtin_nontemporal_load((const cwa_u32x4 *)src + 64 * i + lane);
+        uint32_t sum = 0, mix = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < kCwaTile / 1024; i++) rf_fold(v[i], 64 * i + lane, sum, mix);
+        d = make_uint2(cwa_wave_sum(sum), cwa_wave_sum(mix));
+    } else {
+        rf_tile_load((uint8_t *)s_q, src, len, lane);
+        d = rf_digest_lds((const uint8_t *)s_q, lane);
+    }
+    if (lane == 0) {
+        uint32_t *out = digests + 2 * ((size_t)st * ntiles + tile);   // (4-byte aligned, no more)
+        out[0] = d.x;
+        out[1] = d.y;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_rf_facts(const CwaArgs a, const uint32_t *peer, uint32_t *mask, uint32_t mask_words) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
+    uint8_t *s = (uint8_t *)s_q;
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    const size_t t = (size_t)st * a.ntiles + tile;
+    rf_tile_load(s, a.state + (size_t)st * a.stride + lo, len, lane);
+    bool selected = true;   // (the same for every lane)
+    if (peer) {
+        const uint2 d = rf_digest_lds(s, lane);
+        selected = peer[2 * t] != d.x || peer[2 * t + 1] != d.y;
+    }
+    uint4 f = make_uint4(0u, 0u, 0u, 0u);
+    if (selected) {
+        f = cwc_tile_facts(s, lo, lane);
+        if (lane == 0) atomicOr(mask + (size_t)st * mask_words + (tile >> 5), 1u << (tile & 31u));
+    }
+    if (lane == 0) a.chunk[t] = f;
+}
+
+__global__ __launch_bounds__(64) void k_rf_emit(const CwaArgs a, const CwcOut o) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
+    __shared__ uint32_t s_code32[kCwaTile / 4 + 2], s_diff32[kCwaTile / 4 + 2];
+    uint8_t *s = (uint8_t *)s_q;
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
+    const uint4 fact = a.chunk[(size_t)st * a.ntiles + tile];   // {nonzero bytes, entries before, escapes before, end before}
+    if (fact.x == 0) return;   // not selected, or no nonzero byte
+    const uint32_t seg = o.offsets[st], n = o.offsets[st + 1] - seg;
+    const uint64_t fp0 = o.frame_pos[st], fp1 = o.frame_pos[st + 1];
+    if (fp1 > o.capacity) return;   // the record does not fit: skipped whole, by every workgroup alike
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    rf_tile_load(s, a.state + (size_t)st * a.stride + lo, len, lane);
+    cwc_emit_tile<true>(s, (uint8_t *)s_code32, (uint8_t *)s_diff32, fact, o, seg, n, fp0, cwire_record_escapes(fp1 - fp0, n), lo, lane);
+}
+
+__global__ __launch_bounds__(64) void k_state_clear_tiles(uint8_t *states, size_t stride, uint32_t n, uint32_t ntiles,
+                                                          const uint32_t *mask, uint32_t mask_words) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / ntiles, tile = blockIdx.x % ntiles;
+    if (!((mask[(size_t)st * mask_words + (tile >> 5)] >> (tile & 31u)) & 1u)) return;
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = n - lo < kCwaTile ? n - lo : kCwaTile;
+    uint8_t *dst = states + (size_t)st * stride + lo;
+    const uint32_t to16 = (16u - (uint32_t)((uintptr_t)dst & 15u)) & 15u;
+    const uint32_t head = to16 < len ? to16 : len;
+    const uint32_t q = (len - head) / 16u, tail = head + 16u * q;   // len - tail < 16
+    if (lane < head) dst[lane] = 0;
+    for (uint32_t i = lane; i < q; i += 64) ((cwa_u32x4 *)(dst + head))[i] = cwa_u32x4{0u, 0u, 0u, 0u};
+    if (lane < len - tail) dst[tail + lane] = 0;
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 uint32_t cwa_chunks(uint32_t n) { return n ? (n + kCwaChunk - 1) / kCwaChunk : 1u; }
 uint32_t cwa_tiles(uint32_t nbytes) { return (nbytes + kCwaTile - 1) / kCwaTile; }
@@ -1853,6 +1992,36 @@ hipError_t launch_cwire_budget(const CwaArgs &a, const CwaFrame *records, int ns
     hipLaunchKernelGGL(k_cwc_scan<true>, dim3(nstreams), dim3(256), 0, s, a, o);
     hipLaunchKernelGGL(k_cwc_place<true>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, nstreams);
     if (a.ntiles) hipLaunchKernelGGL(k_cwb_emit, tiles, dim3(64), 0, s, a, o, (const uint32_t *)hist, thr0);
+    return hipGetLastError();
+}
+
+hipError_t launch_state_digest(const uint8_t *states, size_t stride, uint32_t n, int nstreams, uint32_t *digests, hipStream_t s) {
+    const uint32_t ntiles = cwa_tiles(n);
+    if (nstreams <= 0 || ntiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_state_digest, dim3(ntiles * (uint32_t)nstreams), dim3(64), 0, s, states, stride, n, ntiles, digests);
+    return hipGetLastError();
+}
+
+hipError_t launch_refresh(const CwaArgs &a, int nstreams, const uint32_t *peer, uint32_t *mask, const CwcOut &o, hipStream_t s) {
+    if (nstreams <= 0) return hipSuccess;
+    const uint32_t mask_words = (a.ntiles + 31u) / 32u;
+    const dim3 tiles(a.ntiles * (uint32_t)nstreams);
+    if (a.ntiles) {
+        const hipError_t e = hipMemsetAsync(mask, 0, (size_t)nstreams * mask_words * sizeof(uint32_t), s);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_rf_facts, tiles, dim3(64), 0, s, a, peer, mask, mask_words);
+    }
+    hipLaunchKernelGGL(k_cwc_scan<true>, dim3(nstreams), dim3(256), 0, s, a, o);
+    hipLaunchKernelGGL(k_cwc_place<true>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, nstreams);
+    if (a.ntiles) hipLaunchKernelGGL(k_rf_emit, tiles, dim3(64), 0, s, a, o);
+    return hipGetLastError();
+}
+
+hipError_t launch_state_clear_tiles(uint8_t *states, size_t stride, uint32_t n, int nstreams, const uint32_t *mask, hipStream_t s) {
+    const uint32_t ntiles = cwa_tiles(n);
+    if (nstreams <= 0 || ntiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_state_clear_tiles, dim3(ntiles * (uint32_t)nstreams), dim3(64), 0, s, states, stride, n, ntiles, mask,
+                       (ntiles + 31u) / 32u);
     return hipGetLastError();
 }
 

@@ -90,7 +90,9 @@ typedef struct mi355_config {
  *      + mi355_exec_cwire, mi355_pipe_submit_cwire, mi355_pipe_wait_cwire, MI355_PREPARE_EXEC_CWIRE (additions only);
  *      + mi355_cwire_budget_cwire_batch, mi355_cwire_budget_entries (additions only);
  *      + mi355_activity_batch, mi355_cwire_activity_batch, mi355_activity_cells (additions only);
- *      + mi355_cwire_check_host, mi355_cwire_check_batch, MI355_CWIRE_BAD_* (additions only) */
+ *      + mi355_cwire_check_host, mi355_cwire_check_batch, MI355_CWIRE_BAD_* (additions only);
+ *      + mi355_state_tiles, mi355_state_digest_host, mi355_state_digest_batch, mi355_refresh_cwire_batch,
+ *      mi355_state_clear_tiles_batch (additions only) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -751,6 +753,91 @@ int mi355_cwire_check_host(size_t frame_bytes, const void *cwire, size_t cwire_b
                            const uint32_t *h_escapes, int nrecords, uint32_t *verdicts /* [nrecords][4] */);
 int mi355_cwire_check_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
                             int nrecords, void *d_verdicts /* uint32[nrecords][4] */);
+
+/* ---- Resynchronising a receiver: tile digests, refresh records, tile clears ------------------------------------------------
+ * Compact records are additive (state[x] += diff, mod 256): a receiver is right only while it applies every record of a camera
+ * exactly once.  After a record it refused (mi355_cwire_check_batch), lost, or never saw because it joined late, every later
+ * record lands on a wrong state and the error never decays.  These calls let it find out and let the sender repair it with
+ * ordinary records, tile by tile.
+ *   tiles = ceil(N / 4096); tile t of a state is its bytes [4096 t, min(N, 4096 (t + 1))) -- the grid of the apply kernels;
+ *   mask_words = ceil(tiles / 32).
+ * The protocol, in the order of the socket:
+ *   up    the receiver's digests, uint32[S][tiles][2] (mi355_state_digest_batch on its states; 8 bytes per 4096 of a state);
+ *   down  behind the sender's latest tick: the tile mask, uint32[S][mask_words], and one refresh record per camera
+ *         (mi355_refresh_cwire_batch on the sender's states and the receiver's digests);
+ *   then  the receiver clears the masked tiles (mi355_state_clear_tiles_batch) and applies the refresh records
+ *         (mi355_apply_multi_cwire_batch) on one stream with no synchronisation in between, after every tick that came before
+ *         them on the socket.  A host client clears the tiles itself and calls mi355_cwire_apply_host.
+ * The digests describe the receiver's state of some earlier tick: the tiles that the ticks in flight since then changed differ
+ * from the sender's too and are selected as well.  That is wasteful, never wrong: a selected tile is cleared and rewritten whole.
+ *
+ * The digest of a tile: extend it with zero bytes to 4096 bytes, read them as little-endian words w_i, i = 0 .. 1023;
+ *   word 0 = sum of w_i                                       mod 2^32
+ *   word 1 = sum of h(w_i ^ (0x9E3779B9 * (i + 1) mod 2^32))  mod 2^32
+ *   h(v): v ^= v >> 16; v *= 0x85EBCA6B; v ^= v >> 13; v *= 0xC2B2AE35; v ^= v >> 16   (mod 2^32; a bijection)
+ * Properties: a change confined to one 4-byte word always changes word 0.  Word 1 depends on position: words that moved or were
+ * swapped show there (for nearly every pair of unequal words), where word 0 stays.  The digest is NOT cryptographic: it guards
+ * against loss and damage, not against an adversary.
+ * mi355_state_tiles(frame_bytes) is tiles (0 for 0).  mi355_state_digest_host is the definition: host memory, no alignment, no
+ * core, no HIP call; digests[tiles][2].  Refused with MI355_ERR_INVALID, the output untouched: a null pointer with
+ * frame_bytes > 0.
+ * mi355_state_digest_batch: stream s is the N bytes at d_states + s*stride_bytes (any alignment of base and stride, as for the
+ * apply calls; stride_bytes == N with N odd included), d_digests uint32[nstreams][tiles][2], bit-identical to the host form.
+ * Asynchronous on the core's stream, ordered like every other consumer of the states; nothing is allocated; the core's own state
+ * is untouched.  Refused before anything is launched or written: a null core; nstreams outside [0, max_batch]; with
+ * nstreams > 0 a null pointer, stride_bytes < N, d_digests not 4-byte aligned, or the digests overlapping the states' region
+ * [d_states, + (nstreams - 1)*stride_bytes + N).  nstreams == 0 does nothing.
+ *   Kernel: tiles x streams single-wave workgroups.  A whole tile at a 16-byte aligned address is four 16-byte loads per lane,
+ *   each load of the wave 1 KiB in one piece; any other tile goes through LDS with the unaligned tile load of the apply kernels,
+ *   the bytes past N zeroed there.  Both sums are folded per lane and added across the wave; lane 0 stores the 8 bytes.
+ * mi355_refresh_cwire_batch, the sender's answer: tile t of stream s is SELECTED when either word of d_peer_digests[s][t] differs
+ * from the digest of the sender's tile, computed inside the call; d_peer_digests == NULL selects every tile (a key frame, for a
+ * receiver that joins late).  d_tile_mask[s][t >> 5] has bit t & 31 set exactly for the selected tiles (bits at or past tiles
+ * are zero).  Record s, at d_cwire_out + d_frame_pos[s], is the canonical compact encoding of the entries (x, state[s][x]) for
+ * every x in a selected tile with state[s][x] != 0, ascending: headers {n, e} written, pad bytes zero, byte for byte what
+ * mi355_cwire_encode_batch would write from those entries.  d_offsets uint32[nstreams + 1] is the exclusive scan of the counts,
+ * d_frame_pos uint64[nstreams + 1] is always exact.
+ *   The guarantee: let R be any N-byte state whose selected tiles are zero.  Record s applied to R -- by mi355_cwire_apply_host,
+ *   mi355_apply_multi_cwire_batch, or the coalescer in front of either -- makes the selected tiles equal to the sender's and
+ *   leaves the others as they were.  A selected tile that the sender holds all zero has no entry but its mask bit is set: the
+ *   receiver clears it.  A stream with no selected tile yields the 8-byte n = 0 record.  The records are ordinary records:
+ *   mi355_cwire_check_batch gives word 0 == 0 for each, and activity, coalesce and budget take them.
+ *   Capacity, as in the family: a record with d_frame_pos[s + 1] > capacity_bytes is skipped whole, the records behind it that
+ *   fit are written; mask, offsets and frame positions are exact regardless.  mi355_cwire_bytes_max(N, nstreams) always suffices.
+ *   Refused before anything is launched or written: a null core; nstreams outside [0, max_batch]; with nstreams > 0 a null
+ *   pointer other than d_peer_digests, stride_bytes < N; d_peer_digests, d_tile_mask, d_offsets or d_cwire_out not 4-byte
+ *   aligned; d_frame_pos not 8-byte aligned; an output region overlapping the states' region, the peer digests or another output
+ *   region.  nstreams == 0 writes offsets[0] = 0 and frame_pos[0] = 0 and nothing else; as in the coalescer, either of the
+ *   two may be null there and is then skipped, the alignment rules still hold, and no other argument is looked at.  The states
+ *   are only read; nothing is
+ *   allocated (one fact word per (stream, tile) lives in the directory scratch of mi355_apply_cwire_batch, as in the coalescer).
+ *   Kernels: the mask words are cleared on the core's stream; k_rf_facts (tiles x streams, one wave) loads the tile into LDS,
+ *   digests it there, compares, and stores the coalescer's tile facts for a selected tile (and ORs its mask bit in, one atomic)
+ *   or the all-zero fact; the coalescer's scan and place kernels follow unchanged; k_rf_emit loads the selected tiles that hold
+ *   a nonzero byte again and encodes them from LDS with the coalescer's emit step.  The states are read about twice.
+ * mi355_state_clear_tiles_batch, the receiver's first step: zeroes the tiles of state s whose bit of d_tile_mask[s] is set, inside
+ * the N bytes of the state only -- never the stride gap, never a byte of an unselected tile; byte stores at the ragged ends of an
+ * unaligned tile, 16-byte stores inside.  Mask bits at or past tiles are ignored.  Refused as for the digest call, and for a mask
+ * that is not 4-byte aligned or overlaps the states.
+ * Not measured: tools/bench_multi.py --legs refresh --streams 4,16,64 writes profiles/multi_refresh.json (microseconds per stream,
+ * 1080p, webcam-like input, median of five rounds with the spread: the digest call, the refresh with 1 %, 10 % and all tiles
+ * selected, the clear, against mi355_diff_multi_cwire_batch on the same streams in the same run on the same board -- the call the
+ * sender pays every tick, which reads 2N per stream where the digest reads N).  The expectation to test -- the digest call no
+ * slower than that diff at any S by more than the rounds' spread -- is neither met nor missed until that file exists; the other
+ * figures are reported, not judged.  The expectation is about streams at 16-byte aligned addresses: a stream at any other
+ * address (stride_bytes == N with N no multiple of 16: every stream but the first) sends every tile through the byte loads of
+ * the unaligned tile load, as in the apply calls, and is expected to be several times slower; the leg reports that layout too
+ * (digest_skewed: base + 1, stride N) without judging it.
+ * DESIGN.md section 4, "Resynchronising a receiver". */
+size_t mi355_state_tiles(size_t frame_bytes);
+int mi355_state_digest_host(const uint8_t *state, size_t frame_bytes, uint32_t *digests /* [tiles][2] */);
+int mi355_state_digest_batch(mi355_core *core, const void *d_states, size_t stride_bytes, int nstreams,
+                             void *d_digests /* uint32[nstreams][tiles][2] */);
+int mi355_refresh_cwire_batch(mi355_core *core, const void *d_states, size_t stride_bytes, int nstreams,
+                              const void *d_peer_digests /* uint32[nstreams][tiles][2], or NULL: every tile */,
+                              void *d_tile_mask /* uint32[nstreams][mask_words] */, void *d_offsets /* uint32[nstreams + 1] */,
+                              void *d_frame_pos /* uint64[nstreams + 1] */, void *d_cwire_out, size_t capacity_bytes);
+int mi355_state_clear_tiles_batch(mi355_core *core, void *d_states, size_t stride_bytes, int nstreams, const void *d_tile_mask);
 
 /* Integer difference of tests/algorithms_benchmarks.cu:24-30 (kernel1): d[i] = cur[i] - prev[i] on
  * int32 arrays of n elements, no threshold, no pack. */

@@ -77,6 +77,20 @@ check, in microseconds per record, ONE JSON line, at the points and on the input
 The expectation to test: `check` no slower than `burst_apply` at any point by more than the rounds' spread (`verdict`): the check
 reads the records about twice and moves no state tile.
 
+The refresh leg (--legs refresh, a run of its own: `--legs refresh --streams 4,16,64 > profiles/multi_refresh.json`) measures the
+calls that resynchronise a receiver, in microseconds per stream, ONE JSON line for all S, on webcam-like states:
+  digest        mi355_state_digest_batch: two words per 4096-byte tile of every state;
+  digest_skewed the same on a copy of the states one byte behind an aligned address, stride N: every tile takes the unaligned
+                tile load (reported, not judged);
+  refresh_1pct, refresh_10pct, refresh_all
+                mi355_refresh_cwire_batch with the peer's digests differing in 1 % and in 10 % of the tiles (one byte changed
+                in each, evenly spread) and with no peer digests (every tile: a key frame);
+  clear_10pct   mi355_state_clear_tiles_batch with the 10 % mask;
+  diff          mi355_diff_multi_cwire_batch on the same streams: the call the sender pays every tick anyway; it reads 2N per
+                stream where the digest reads N.
+The expectation to test: `digest` no slower than `diff` at any S by more than the rounds' spread (`verdict`).  The other figures
+are reported, not judged.
+
 Input of the other legs: ONE webcam stream of S + K + 1 frames; stream s shows frame s + j at step j, so every tick of every stream is the
 step between two consecutive webcam frames, and a tick's S frames are one contiguous region.  j walks 1 .. K and back."""
 import argparse
@@ -682,6 +696,109 @@ def run_check(W, H, S, T, rounds, kind):
     return out
 
 
+def run_refresh(W, H, S, rounds):
+    """The refresh leg for one S -> its dictionary.  All legs on one core's own stream, alternating within every round; the diff
+    leg has its own copy of the states per pass, restored outside the window (it is the only leg that writes states it reads)."""
+    import numpy as np
+    from cudavideostream_amd import CUDACore, cwire_bytes_max, state_tiles
+    dev = torch.device("cuda", 0)
+    n = 3 * W * H
+    tiles = state_tiles(n)
+    mask_words = (tiles + 31) // 32
+    passes = max(2, min(16, 128 // S))
+    _, web = synth.webcam_stream(S + 1, W, H, device=dev)
+    web = web.reshape(S + 1, n)
+    sender, frames = web[:S].clone(), web[1:].clone()   # stream s: webcam frame s, and the tick s -> s + 1 for the diff leg
+    cwcap = cwire_bytes_max(n, S)
+    d_off = torch.zeros(S + 1, dtype=torch.int32, device=dev)
+    d_pos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
+    d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
+    d_mask = torch.zeros(S * mask_words, dtype=torch.int32, device=dev)
+    d_dig = torch.zeros(S * tiles * 2, dtype=torch.int32, device=dev)
+    core = CUDACore(W, H, max_batch=S)
+    torch.cuda.synchronize()
+    peers, masks, selected = {}, {}, {}
+    for name, every in (("1pct", 100), ("10pct", 10)):   # the receiver: the sender's states with a byte changed in every k-th tile
+        recv = sender.clone()
+        hit = torch.arange(every // 2, tiles, every, device=dev) * 4096 + 1234
+        hit = hit[hit < n]
+        recv[:, hit] ^= 0x5A
+        peers[name] = torch.zeros_like(d_dig)
+        torch.cuda.synchronize()
+        core.state_digest_batch(recv, S, peers[name])
+        core.refresh_cwire_batch(sender, S, peers[name], d_mask, d_off, d_pos, d_cw, cwcap)
+        core.synchronize()
+        masks[name] = d_mask.clone()
+        selected[name] = int(sum(bin(int(v) & 0xFFFFFFFF).count("1") for v in d_mask.cpu().numpy()))
+        assert selected[name] == S * int(hit.numel()), "the refresh did not select exactly the changed tiles"
+        del recv
+    work = torch.empty(passes, S, n, dtype=torch.uint8, device=dev)
+    scratch = sender.clone()                             # the clear leg's states
+    skew_buf = torch.empty(S * n + 16, dtype=torch.uint8, device=dev)
+    skewed = skew_buf[1:1 + S * n]                       # 1080p: N is a multiple of 16, so every stream is one byte off
+    skewed.copy_(sender.reshape(-1))
+    assert skewed.data_ptr() % 16 == 1
+    rec_bytes = {}
+
+    def leg_digest():
+        for _ in range(passes):
+            core.state_digest_batch(sender, S, d_dig)
+        core.synchronize()
+
+    def leg_digest_skewed():
+        for _ in range(passes):
+            core.state_digest_batch(skewed, S, d_dig)
+        core.synchronize()
+
+    def leg_refresh(peer):
+        def leg():
+            for _ in range(passes):
+                core.refresh_cwire_batch(sender, S, peer, d_mask, d_off, d_pos, d_cw, cwcap)
+            core.synchronize()
+        return leg
+
+    def leg_clear():
+        for _ in range(passes):
+            core.state_clear_tiles_batch(scratch, S, masks["10pct"])
+        core.synchronize()
+
+    def leg_diff():
+        for p in range(passes):
+            core.diff_multi_cwire_batch(frames, work[p], S, d_off, d_pos, d_cw, cwcap)
+        core.synchronize()
+
+    table = {"digest": leg_digest, "digest_skewed": leg_digest_skewed, "refresh_1pct": leg_refresh(peers["1pct"]), "refresh_10pct": leg_refresh(peers["10pct"]),
+             "refresh_all": leg_refresh(None), "clear_10pct": leg_clear, "diff": leg_diff}
+    times = {}
+    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
+        for name, leg in table.items():
+            if name == "diff":
+                work.copy_(sender.unsqueeze(0).expand(passes, S, n))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            leg()
+            dt = time.perf_counter() - t0
+            if r:
+                times.setdefault(name, []).append(dt * 1e6 / (passes * S))
+            if name.startswith("refresh"):
+                rec_bytes[name] = int(d_pos[S].item())
+    out = {"streams": S, "passes": passes, "tiles": tiles, "state_bytes": n}
+    for name in table:
+        st = stats(times[name])
+        st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
+        out[name + "_us_per_stream"] = st
+    for name in ("1pct", "10pct"):
+        out["refresh_" + name + "_tiles_per_stream"] = selected[name] // S
+    for name, b in rec_bytes.items():
+        out[name + "_bytes_per_stream"] = round(b / S, 1)
+    med = {k: statistics.median(v) for k, v in times.items()}
+    spread = max(max(times[k]) - min(times[k]) for k in ("digest", "diff"))
+    out["digest_over_diff"] = round(med["digest"] / med["diff"], 3)
+    out["digest_no_slower_than_diff"] = bool(med["digest"] <= med["diff"] + spread)
+    core.close()
+    return out
+
+
 def run_coalesce(W, H, S, T, rounds, kind):
     """The coalesce leg for one (S, T) and one input -> its dictionary.  coalesce: mi355_cwire_coalesce_cwire_batch on the
     burst's records, nothing else.  state_route: what a relay did before -- mi355_apply_multi_stream_cwire_batch onto states it
@@ -860,7 +977,7 @@ def main():
     ap.add_argument("--steps", type=int, default=8, help="K: webcam frames a stream walks through")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--legs", default="multi,cores_loop,pairs",
-                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or budget alone; or activity alone; or check alone")
+                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or budget alone; or activity alone; or check alone; or refresh alone")
     ap.add_argument("--frames", default="4,16,64", help="burst, burst_client and coalesce legs: T, frames per stream and call")
     a = ap.parse_args()
     have = load_library()
@@ -933,6 +1050,16 @@ def main():
         print(json.dumps({"bench": "multi_check", "size": f"{W}x{H}", "rounds": a.rounds, "check": per,
                           "verdict": "no slower than burst_apply at every point" if all(p["no_slower_than_burst_apply"] for p in per)
                           else "slower than burst_apply at some point"}), flush=True)
+        return
+    if a.legs == "refresh":
+        per = []
+        for S in (int(v) for v in a.streams.split(",")):
+            per.append(run_refresh(W, H, S, a.rounds))
+            print(f"refresh S={S}: done", file=sys.stderr, flush=True)
+            torch.cuda.empty_cache()
+        print(json.dumps({"bench": "multi_refresh", "size": f"{W}x{H}", "rounds": a.rounds, "refresh": per,
+                          "verdict": "digest no slower than diff at every S" if all(p["digest_no_slower_than_diff"] for p in per)
+                          else "digest slower than diff at some S"}), flush=True)
         return
     for S in (int(v) for v in a.streams.split(",")):
         run(W, H, S, a.steps, a.rounds, set(a.legs.split(",")), have)

@@ -48,6 +48,16 @@
 // 0 == 0), the verdicts equal to mi355_cwire_check_host's on the received bytes, and word 3 of every record equal to 1 + the
 // last byte index that the apply then changes.  Once per run it also checks a damaged copy of the first non-empty record -- one
 // code byte set to 255 -- and requires MI355_CWIRE_BAD_CODES.
+// --compact --multi S --resync K [--burst B]: a receiver that lost a record finds its way back.  At tick K the receiver drops one
+// camera's record (it applies an empty record in its place), so that camera's frame is wrong from then on.  After tick K + 1 it
+// digests its states (mi355_state_digest_batch, checked against mi355_state_digest_host) and sends the digests up; the sender
+// answers behind its latest tick -- with --burst B the end of the burst it has already made -- with a tile mask and one refresh
+// record per camera (mi355_refresh_cwire_batch); the receiver applies the ticks that were in flight, clears the masked tiles
+// (mi355_state_clear_tiles_batch) and applies the refresh records like any others.  Checked: the dropped camera's frame differs
+// from the sender's at every tick between the loss and the refresh, and every other frame of every tick -- all of them from the
+// refresh on -- equals the sender's; the dropped camera has mask bits and, unless ticks were in flight, only that camera (the
+// others get the 8-byte record); a host client that
+// clears the tiles itself and calls mi355_cwire_apply_host ends at the same frames.
 // --compact --per-frame: the per-frame server, one host frame per call and no device pointer in sight.  The sender feeds
 // host frames through mi355_pipe_submit_cwire, four in flight, and writes each frame's record to the pipe with ONE write()
 // from the pinned buffer it arrived in; the receiver -- a thread with no core -- reads header and body, applies the record
@@ -55,7 +65,7 @@
 // (mi355_exec on a second core: frame[xs[i]] += diff[i], client/opencv.cpp:64-66).
 //
 //   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B]
-//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check]]]
+//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check] | --resync K [--burst B]]]
 //   exit status 0 = all checks passed
 #include <algorithm>
 #include <cstdint>
@@ -1045,8 +1055,211 @@ static int run_per_frame(int w, int h, int T) {
     return rx.equal == T ? 0 : 1;
 }
 
+// --compact --multi S --resync R [--burst K] (see the head of the file)
+static int run_multi_resync(int w, int h, int T, int S, int R, int K) {
+    const size_t n = (size_t)3 * w * h;
+    if (R < 0 || R + 1 >= T) { fprintf(stderr, "--resync K needs 0 <= K and K + 1 < --frames\n"); return 2; }
+    if (K < 1) K = 1;
+    mi355_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.width = w; cfg.height = h; cfg.threshold = 20; cfg.max_batch = S * K; cfg.device = -1;
+    mi355_core *server = nullptr, *client = nullptr;
+    OK(mi355_create(&cfg, &server));
+    cfg.max_batch = S;
+    OK(mi355_create(&cfg, &client));
+    const int B = S * K, victim = R % S;
+    const size_t cw_cap = mi355_cwire_bytes_max(n, B), tick_cap = mi355_cwire_bytes_max(n, S);
+    const size_t tiles = mi355_state_tiles(n), mask_words = (tiles + 31) / 32;
+    const size_t dig_bytes = 8 * (size_t)S * tiles, mask_bytes = 4 * (size_t)S * mask_words;
+    void *d_frames = nullptr, *d_sstates = nullptr, *d_off = nullptr, *d_pos = nullptr, *d_cw = nullptr;   // server
+    void *d_peer = nullptr, *d_smask = nullptr, *d_roff = nullptr, *d_rpos = nullptr, *d_rcw = nullptr;    // ... its refresh
+    void *d_rx = nullptr, *d_cstates = nullptr, *d_dig = nullptr, *d_cmask = nullptr;                      // client
+    OK(mi355_dev_alloc(server, &d_frames, (size_t)B * n));
+    OK(mi355_dev_alloc(server, &d_sstates, (size_t)S * n));
+    OK(mi355_dev_alloc(server, &d_off, sizeof(uint32_t) * (B + 1)));
+    OK(mi355_dev_alloc(server, &d_pos, sizeof(uint64_t) * (B + 1)));
+    OK(mi355_dev_alloc(server, &d_cw, cw_cap));
+    OK(mi355_dev_alloc(server, &d_peer, dig_bytes));
+    OK(mi355_dev_alloc(server, &d_smask, mask_bytes));
+    OK(mi355_dev_alloc(server, &d_roff, sizeof(uint32_t) * (S + 1)));
+    OK(mi355_dev_alloc(server, &d_rpos, sizeof(uint64_t) * (S + 1)));
+    OK(mi355_dev_alloc(server, &d_rcw, tick_cap));
+    OK(mi355_dev_alloc(client, &d_rx, tick_cap));
+    OK(mi355_dev_alloc(client, &d_cstates, (size_t)S * n));
+    OK(mi355_dev_alloc(client, &d_dig, dig_bytes));
+    OK(mi355_dev_alloc(client, &d_cmask, mask_bytes));
+    int fds[2];
+    if (pipe(fds) != 0) return 1;
+    // truth: a host client per camera that applies EVERY record -- the sender's state after every tick
+    std::vector<uint8_t> bases((size_t)S * n), truth((size_t)S * n), frames((size_t)B * n), s_states((size_t)S * n),
+        c_states((size_t)S * n), cw_host(cw_cap), rx(cw_cap), stage(tick_cap), host_client;
+    for (int s = 0; s < S; s++)
+        for (size_t i = 0; i < n; i++) bases[(size_t)s * n + i] = (uint8_t)(40 + (i * 7 + (size_t)s * 31) % 150);
+    OK(mi355_upload(server, d_sstates, bases.data(), bases.size()));
+    if (!through_pipe(fds[1], fds[0], bases.data(), truth.data(), bases.size())) return 1;
+    OK(mi355_upload(client, d_cstates, truth.data(), truth.size()));
+    std::vector<uint8_t> base(n), frame(n);
+    std::vector<uint32_t> off(B + 1), counts(S), escapes(S), dig(2 * (size_t)S * tiles), dig_up(dig.size()), dig_host(2 * tiles),
+        mask(S * mask_words), mask_rx(mask.size());
+    std::vector<uint64_t> pos(B + 1), rpos(S + 1);
+    std::vector<size_t> at(B), len(B);
+    size_t sent_bytes = 0, refresh_bytes = 0, lost_entries = 0, tiles_selected = 0;
+    int wrong_ticks = 0, right_ticks_after = 0;
+    bool lost = false, refreshed = false;
+    // the receiver's frames of tick t against the truth: while the record is lost the victim's differs and only the victim's
+    auto compare = [&](int t) -> int {
+        for (int s = 0; s < S; s++) {
+            const bool same = memcmp(&truth[(size_t)s * n], &c_states[(size_t)s * n], n) == 0;
+            const bool wrong = lost && !refreshed && s == victim;
+            if (same == wrong) {
+                fprintf(stderr, "tick %d: camera %d: the receiver's frame %s the sender's\n", t, s, same ? "equals" : "differs from");
+                return 1;
+            }
+        }
+        if (lost && !refreshed) wrong_ticks++;
+        if (refreshed) right_ticks_after++;
+        return 0;
+    };
+    for (int t0 = 0; t0 < T; t0 += K) {
+        const int nb = T - t0 < K ? T - t0 : K, nrec = S * nb;
+        for (int s = 0; s < S; s++) {   // camera s's nb frames, one behind the other
+            memcpy(base.data(), &bases[(size_t)s * n], n);
+            for (int k = 0; k < nb; k++) {
+                make_frame(frame, base, w, h, t0 + k + 5 * s);
+                memcpy(&frames[((size_t)s * nb + k) * n], frame.data(), n);
+            }
+        }
+        // ---- server: nb ticks of S cameras
+        OK(mi355_upload(server, d_frames, frames.data(), (size_t)nrec * n));
+        if (K == 1) OK(mi355_diff_multi_cwire_batch(server, d_frames, d_sstates, n, S, d_off, d_pos, d_cw, cw_cap));
+        else OK(mi355_diff_multi_stream_cwire_batch(server, d_frames, d_sstates, n, S, nb, d_off, d_pos, d_cw, cw_cap));
+        OK(mi355_download(server, pos.data(), d_pos, sizeof(uint64_t) * (nrec + 1)));
+        if (pos[nrec] > cw_cap) { fprintf(stderr, "compact stream larger than its bound\n"); return 1; }
+        const size_t cb = (size_t)pos[nrec];
+        OK(mi355_download(server, cw_host.data(), d_cw, cb));
+        if (!through_pipe(fds[1], fds[0], cw_host.data(), rx.data(), cb)) return 1;
+        sent_bytes += cb;
+        size_t p = 0;
+        for (int r = 0; r < nrec; r++) {   // the records of every socket, found from their headers
+            if (p + 8 > cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
+            uint32_t c, e;
+            memcpy(&c, rx.data() + p, 4);
+            memcpy(&e, rx.data() + p + 4, 4);
+            at[r] = p;
+            len[r] = mi355_cwire_frame_bytes(c, e);
+            p += len[r];
+        }
+        if (p != cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
+        // ---- client: tick k = record (s, k) of every s back to back, one upload, one call
+        bool asked = false;
+        for (int k = 0; k < nb; k++) {
+            const int t = t0 + k;
+            size_t q = 0;
+            for (int s = 0; s < S; s++) {
+                const int r = s * nb + k;
+                size_t used = 0;
+                OK(mi355_cwire_apply_host(&truth[(size_t)s * n], n, rx.data() + at[r], len[r], 1, &used));
+                if (used != len[r]) { fprintf(stderr, "stream framing broken\n"); return 1; }
+                if (t == R && s == victim) {   // the loss: the receiver has nothing to apply for this camera
+                    memcpy(&lost_entries, rx.data() + at[r], 4);
+                    if (lost_entries == 0) { fprintf(stderr, "--resync: the record to drop holds no entry\n"); return 1; }
+                    memset(stage.data() + q, 0, 8);
+                    counts[s] = escapes[s] = 0;
+                    q += 8;
+                    lost = true;
+                    continue;
+                }
+                memcpy(stage.data() + q, rx.data() + at[r], len[r]);
+                memcpy(&counts[s], stage.data() + q, 4);
+                memcpy(&escapes[s], stage.data() + q + 4, 4);
+                q += len[r];
+            }
+            OK(mi355_upload(client, d_rx, stage.data(), q));
+            OK(mi355_apply_multi_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, d_cstates, n));
+            if (t == R + 1) {   // the receiver asks: its digests go up
+                OK(mi355_state_digest_batch(client, d_cstates, n, S, d_dig));
+                OK(mi355_download(client, dig.data(), d_dig, dig_bytes));
+                asked = true;
+            }
+            OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
+            if (asked && t == R + 1)
+                for (int s = 0; s < S; s++) {
+                    OK(mi355_state_digest_host(&c_states[(size_t)s * n], n, dig_host.data()));
+                    if (memcmp(dig_host.data(), &dig[2 * (size_t)s * tiles], 8 * tiles) != 0) {
+                        fprintf(stderr, "tick %d: camera %d: device digests != host digests\n", t, s);
+                        return 1;
+                    }
+                }
+            if (int rc = compare(t)) return rc;
+        }
+        // ---- the states at both ends of the burst: the truth is the sender's
+        OK(mi355_download(server, s_states.data(), d_sstates, s_states.size()));
+        if (memcmp(s_states.data(), truth.data(), s_states.size()) != 0) { fprintf(stderr, "tick %d: host frames != server states\n", t0); return 1; }
+        if (!asked) continue;
+        const bool in_flight = t0 + nb - 1 > R + 1;
+        // ---- server: the answer, behind its latest tick
+        if (!through_pipe(fds[1], fds[0], (const uint8_t *)dig.data(), (uint8_t *)dig_up.data(), dig_bytes)) return 1;
+        OK(mi355_upload(server, d_peer, dig_up.data(), dig_bytes));
+        OK(mi355_refresh_cwire_batch(server, d_sstates, n, S, d_peer, d_smask, d_roff, d_rpos, d_rcw, tick_cap));
+        OK(mi355_download(server, rpos.data(), d_rpos, sizeof(uint64_t) * (S + 1)));
+        OK(mi355_download(server, mask.data(), d_smask, mask_bytes));
+        refresh_bytes = (size_t)rpos[S];
+        if (refresh_bytes > tick_cap) { fprintf(stderr, "refresh records larger than their bound\n"); return 1; }
+        OK(mi355_download(server, cw_host.data(), d_rcw, refresh_bytes));
+        if (!through_pipe(fds[1], fds[0], (const uint8_t *)mask.data(), (uint8_t *)mask_rx.data(), mask_bytes)) return 1;
+        if (!through_pipe(fds[1], fds[0], cw_host.data(), stage.data(), refresh_bytes)) return 1;
+        // ---- client: clear, then apply like any other records; a host client does the same beside it
+        host_client = c_states;
+        p = 0;
+        for (int s = 0; s < S; s++) {
+            if (p + 8 > refresh_bytes) { fprintf(stderr, "refresh framing broken\n"); return 1; }
+            memcpy(&counts[s], stage.data() + p, 4);
+            memcpy(&escapes[s], stage.data() + p + 4, 4);
+            size_t bits = 0;
+            for (size_t tl = 0; tl < tiles; tl++)
+                if (mask_rx[s * mask_words + (tl >> 5)] >> (tl & 31) & 1u) {
+                    bits++;
+                    const size_t lo = tl * 4096, hi = lo + 4096 < n ? lo + 4096 : n;
+                    memset(&host_client[(size_t)s * n + lo], 0, hi - lo);
+                }
+            // (ticks in flight behind the digests changed tiles of every camera: those are selected too, wasteful and never wrong)
+            if (s == victim ? bits == 0 : !in_flight && (bits != 0 || counts[s] != 0)) {
+                fprintf(stderr, "refresh: camera %d: %zu tiles selected, %u entries\n", s, bits, counts[s]);
+                return 1;
+            }
+            tiles_selected += bits;
+            size_t used = 0;
+            OK(mi355_cwire_apply_host(&host_client[(size_t)s * n], n, stage.data() + p, refresh_bytes - p, 1, &used));
+            p += used;
+        }
+        if (p != refresh_bytes) { fprintf(stderr, "refresh framing broken\n"); return 1; }
+        OK(mi355_upload(client, d_cmask, mask_rx.data(), mask_bytes));
+        OK(mi355_upload(client, d_rx, stage.data(), refresh_bytes));
+        OK(mi355_state_clear_tiles_batch(client, d_cstates, n, S, d_cmask));
+        OK(mi355_apply_multi_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, d_cstates, n));
+        OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
+        refreshed = true;
+        if (memcmp(c_states.data(), host_client.data(), c_states.size()) != 0) { fprintf(stderr, "refresh: client states != host client frames\n"); return 1; }
+        if (memcmp(c_states.data(), s_states.data(), c_states.size()) != 0) { fprintf(stderr, "refresh: client states != server states\n"); return 1; }
+    }
+    if (!refreshed || wrong_ticks < 1) { fprintf(stderr, "--resync: no refresh happened\n"); return 1; }
+    void *srv[] = {d_frames, d_sstates, d_off, d_pos, d_cw, d_peer, d_smask, d_roff, d_rpos, d_rcw};
+    for (void *q : srv) OK(mi355_dev_free(server, q));
+    void *cli[] = {d_rx, d_cstates, d_dig, d_cmask};
+    for (void *q : cli) OK(mi355_dev_free(client, q));
+    mi355_destroy(server);
+    mi355_destroy(client);
+    printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"burst\": %d, \"resync\": %d, \"width\": %d, \"height\": %d, "
+           "\"ticks\": %d, \"dropped_camera\": %d, \"dropped_entries\": %zu, \"wrong_ticks\": %d, \"ticks_equal_after_refresh\": %d, "
+           "\"tiles\": %zu, \"tiles_selected\": %zu, \"digest_bytes\": %zu, \"mask_bytes\": %zu, \"refresh_bytes\": %zu, "
+           "\"key_frame_bytes\": %zu, \"wire_bytes\": %zu}\n",
+           S, K, R, w, h, T, victim, lost_entries, wrong_ticks, right_ticks_after, tiles, tiles_selected, dig_bytes, mask_bytes,
+           refresh_bytes, (size_t)S * n, sent_bytes);
+    return 0;
+}
+
 int main(int argc, char **argv) {
-    int w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0, activity = -1;
+    int w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0, activity = -1, resync = -1;
     long budget = -1;
     bool compact = false, direct = false, gpu_client = false, burst_client = false, coalesce = false, per_frame = false, check = false;
     for (int i = 1; i < argc; i++) {
@@ -1069,6 +1282,7 @@ int main(int argc, char **argv) {
         else if (k == "--multi") multi = v;
         else if (k == "--burst") burst = v;
         else if (k == "--activity") activity = v < 0 ? 0 : v;
+        else if (k == "--resync") resync = v < 0 ? 0 : v;
         else if (k == "--budget") budget = atol(argv[i + 1]) < 0 ? 0 : atol(argv[i + 1]);
     }
     if (burst && (!multi || burst < 0)) { fprintf(stderr, "--burst K needs --multi S and K >= 1\n"); return 2; }
@@ -1090,12 +1304,17 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--check needs --compact --multi S, alone or with --burst K --burst-client\n");
         return 2;
     }
+    if (resync >= 0 && (!compact || !multi || budget >= 0 || coalesce || per_frame || burst_client || activity || check)) {
+        fprintf(stderr, "--resync K needs --compact --multi S, alone or with --burst B\n");
+        return 2;
+    }
     if (per_frame) {
         if (!compact || direct || gpu_client || multi) { fprintf(stderr, "--per-frame needs --compact alone\n"); return 2; }
         return run_per_frame(w, h, T);
     }
     if (multi) {
         if (!compact || direct || gpu_client || multi < 0) { fprintf(stderr, "--multi S needs --compact alone and S >= 1\n"); return 2; }
+        if (resync >= 0) return run_multi_resync(w, h, T, multi, resync, burst);
         if (burst_client) return run_multi_burst_client(w, h, T, multi, burst, activity, check);
         if (coalesce) return run_multi_burst_coalesce(w, h, T, multi, burst);
         if (budget >= 0) return run_multi_budget(w, h, T, multi, budget);
