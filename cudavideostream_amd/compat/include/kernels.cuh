@@ -118,6 +118,16 @@ public:
     void refresh_multi(const void *d_states, size_t stride, int nstreams, const void *d_peer_digests, void *d_tile_mask,
                        void *d_offsets, void *d_frame_pos, void *d_cwire_out, size_t capacity_bytes);
     void clear_tiles_multi(void *d_states, size_t stride, int nstreams, const void *d_tile_mask);
+    // A wall of many cameras (include/mi355diff.h, "A wall of many cameras"), all on DEVICE memory but h_place.
+    // wall_compose_multi: the box-downscaled thumbnail of each state (laid out as for apply_multi) at scale h_place[s][2]
+    // (1 .. 16; 0: not shown) to (h_place[s][0], h_place[s][1]) of the BGR24 wall; d_tile_mask (refresh_multi's or
+    // touched_tiles_multi's) limits the repaint to where a selected tile lands, NULL repaints all.  touched_tiles_multi: that mask
+    // from the records of a tick or burst, described as for apply_multi_stream; accumulate ORs onto what the mask holds.
+    // Blocking; nstreams (* nframes) <= MI355_MAX_BATCH.
+    void wall_compose_multi(const void *d_states, size_t stride, int nstreams, const int32_t *h_place, const void *d_tile_mask,
+                            void *d_wall, int wall_w, int wall_h, size_t wall_pitch);
+    void touched_tiles_multi(const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams, int nframes,
+                             bool accumulate, void *d_tile_mask);
 };
 
 static_assert(sizeof(CUDACore) == 160, "must match the reference's object size (LP64)");

@@ -190,6 +190,18 @@ void CUDACore::clear_tiles_multi(void *d_states, size_t stride, int nstreams, co
     MI355_CHECK(mi355_synchronize(core_));
 }
 
+void CUDACore::wall_compose_multi(const void *d_states, size_t stride, int nstreams, const int32_t *h_place, const void *d_tile_mask,
+                                  void *d_wall, int wall_w, int wall_h, size_t wall_pitch) {
+    MI355_CHECK(mi355_wall_compose_batch(core_, d_states, stride, nstreams, h_place, d_tile_mask, d_wall, wall_w, wall_h, wall_pitch));
+    MI355_CHECK(mi355_synchronize(core_));
+}
+
+void CUDACore::touched_tiles_multi(const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams, int nframes,
+                                   bool accumulate, void *d_tile_mask) {
+    MI355_CHECK(mi355_cwire_touched_tiles_batch(core_, d_cwire, h_counts, h_escapes, nstreams, nframes, accumulate ? 1 : 0, d_tile_mask));
+    MI355_CHECK(mi355_synchronize(core_));
+}
+
 size_t CUDACore::chunkt_size() { return 32; }  // sizeof(long4), kernels.cu:27,527-529
 
 void CUDACore::alloc_arrays(uint8_t **h_frame, uint8_t **n_frame, uint8_t **o_frame, int **h_xs, int r,

@@ -511,6 +511,31 @@ class CUDACore:
         stride = self.total if stride is None else stride
         _l.check(self._lib.mi355_state_clear_tiles_batch(self._h, _ptr(d_states), int(stride), int(nstreams), _ptr(d_tile_mask)))
 
+    # ... and the wall that shows its cameras: thumbnails of the states in one frame, repainted where records landed
+    def wall_compose_batch(self, d_states, nstreams, place, d_wall, wall_w, wall_h, wall_pitch=None, d_tile_mask=None, stride=None):
+        """Box-downscaled thumbnails of nstreams states (stream s at d_states + s*stride, any alignment) into the BGR24 wall of
+        wall_w x wall_h pixels at d_wall (pixel (X, Y) at Y*wall_pitch + 3*X).  place is int32[nstreams][3] = {x, y, k}: the
+        thumbnail at scale k (1 .. 16; wall_thumb_size) goes to (x, y), k == 0 hides the stream.  d_tile_mask
+        (refresh_cwire_batch's or cwire_touched_tiles_batch's) limits the repaint to where a selected tile lands; None: all."""
+        self._hold(d_states, d_tile_mask, d_wall)
+        stride = self.total if stride is None else stride
+        wall_pitch = 3 * int(wall_w) if wall_pitch is None else wall_pitch
+        place = np.ascontiguousarray(place, dtype=np.int32)
+        assert place.size >= 3 * nstreams
+        _l.check(self._lib.mi355_wall_compose_batch(self._h, _ptr(d_states), int(stride), int(nstreams), place.ctypes.data,
+                                                    _ptr(d_tile_mask), _ptr(d_wall), int(wall_w), int(wall_h), int(wall_pitch)))
+
+    def cwire_touched_tiles_batch(self, d_cwire, counts, escapes, nstreams, nframes, d_tile_mask, accumulate=False):
+        """The tiles of 4096 bytes that the compact records of each stream (headers counts / escapes, s * nframes + t order) have
+        an entry in, as the tile mask of refresh_cwire_batch: uint32[nstreams][ceil(tiles / 32)], overwritten or, with
+        accumulate, ORed onto."""
+        self._hold(d_cwire, d_tile_mask)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+        assert counts.size >= nstreams * nframes and escapes.size >= nstreams * nframes
+        _l.check(self._lib.mi355_cwire_touched_tiles_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
+                                                           int(nstreams), int(nframes), int(bool(accumulate)), _ptr(d_tile_mask)))
+
     def wire_bytes(self, nframes, entries):
         return self._lib.mi355_wire_bytes(nframes, entries)
 
@@ -691,6 +716,14 @@ def activity_cells(width, height, cell_w, cell_h):
     gw, gh = C.c_int(0), C.c_int(0)
     cells = _l.load().mi355_activity_cells(int(width), int(height), int(cell_w), int(cell_h), C.byref(gw), C.byref(gh))
     return cells, gw.value, gh.value
+
+
+def wall_thumb_size(width, height, k):
+    """(pixels, tw, th) of the thumbnail of a width x height state at scale k of wall_compose_batch: ceil(width / k) by
+    ceil(height / k); all 0 for a width or height below 1 or a k outside 1 .. 16."""
+    tw, th = C.c_int(0), C.c_int(0)
+    pixels = _l.load().mi355_wall_thumb_size(int(width), int(height), int(k), C.byref(tw), C.byref(th))
+    return pixels, tw.value, th.value
 
 
 def cwire_apply_host(state, buf, nframes):

@@ -1893,6 +1893,80 @@ int mi355_state_clear_tiles_batch(mi355_core *c, void *d_states, size_t stride_b
     return MI355_OK;
 }
 
+// ---- a wall of many cameras: thumbnails of the states in one frame, touched-tile masks (stream_ops.hip, k_wall_compose) -------
+size_t mi355_wall_thumb_size(int width, int height, int k, int *tw, int *th) {
+    const bool ok = width >= 1 && height >= 1 && k >= 1 && k <= 16;
+    const int w = ok ? (int)(((int64_t)width + k - 1) / k) : 0, h = ok ? (int)(((int64_t)height + k - 1) / k) : 0;
+    if (tw) *tw = w;
+    if (th) *th = h;
+    return (size_t)w * (size_t)h;
+}
+
+int mi355_wall_compose_batch(mi355_core *c, const void *d_states, size_t stride_bytes, int nstreams, const int32_t *h_place,
+                             const void *d_tile_mask, void *d_wall, int wall_w, int wall_h, size_t wall_pitch) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nstreams < 0 || nstreams > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams outside [0, max_batch]");
+    if (nstreams == 0) return MI355_OK;
+    if (!d_states || !h_place || !d_wall) return fail(MI355_ERR_INVALID, "null argument");
+    if (stride_bytes < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
+    if (wall_w < 1 || wall_h < 1) return fail(MI355_ERR_INVALID, "wall_w or wall_h < 1");
+    if (wall_pitch < 3 * (size_t)wall_w) return fail(MI355_ERR_INVALID, "wall_pitch < 3 * wall_w");
+    if ((uintptr_t)d_tile_mask & 3u) return fail(MI355_ERR_INVALID, "d_tile_mask must be 4-byte aligned");
+    for (int s = 0; s < nstreams; s++) {
+        const int32_t x = h_place[3 * s], y = h_place[3 * s + 1], k = h_place[3 * s + 2];
+        if (k < 0 || k > 16) return fail(MI355_ERR_INVALID, "h_place: a scale outside [0, 16]");
+        if (k == 0) continue;
+        int tw, th;
+        mi355_wall_thumb_size(c->cfg.width, c->cfg.height, k, &tw, &th);
+        if (x < 0 || y < 0 || (int64_t)x + tw > wall_w || (int64_t)y + th > wall_h)
+            return fail(MI355_ERR_INVALID, "h_place: a thumbnail does not lie inside the wall");
+    }
+    const ResyncRegion st = resync_states(c, d_states, stride_bytes, nstreams);
+    const ResyncRegion wl{d_wall, (uint64_t)(wall_h - 1) * wall_pitch + 3 * (uint64_t)wall_w, "the wall"};
+    const ResyncRegion mk{d_tile_mask, d_tile_mask ? 4 * (uint64_t)nstreams * ((cwa_tiles(c->n) + 31u) / 32u) : 0, "d_tile_mask"};
+    if (resync_overlap(wl, st)) return resync_overlap_fail(wl, st);
+    if (resync_overlap(mk, st)) return resync_overlap_fail(mk, st);
+    if (resync_overlap(wl, mk)) return resync_overlap_fail(wl, mk);
+    if (int rc = use_device(c)) return rc;
+    HIP_TRY(launch_wall_compose((const uint8_t *)d_states, stride_bytes, (uint32_t)c->cfg.width, (uint32_t)c->cfg.height, nstreams, h_place,
+                                (const uint32_t *)d_tile_mask, (uint8_t *)d_wall, wall_pitch, c->stream));
+    return MI355_OK;
+}
+
+int mi355_cwire_touched_tiles_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams,
+                                    int nframes, int accumulate, void *d_tile_mask) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nstreams < 0 || nframes < 0) return fail(MI355_ERR_INVALID, "nstreams or nframes < 0");
+    if ((int64_t)nstreams * nframes > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams * nframes above max_batch");
+    if (((uintptr_t)d_cwire | (uintptr_t)d_tile_mask) & 3u) return fail(MI355_ERR_INVALID, "the device pointers must be 4-byte aligned");
+    const int B = nstreams * nframes;
+    if (B == 0) return MI355_OK;
+    if (!d_cwire || !h_counts || !h_escapes) return fail(MI355_ERR_INVALID, "null stream pointer");
+    if (!d_tile_mask) return fail(MI355_ERR_INVALID, "null output pointer");
+    CwireHeaders hdr{h_counts, h_escapes, B};
+    if (int rc = hdr.check(true, c->n)) return rc;
+    std::vector<CwaFrame> fr((size_t)B);   // B <= max_batch: the scratch of the one-stream client holds them
+    uint32_t cbase = 0;
+    for (int b = 0; b < B; b++) {
+        const CwireHeaders::Frame f = hdr.next();
+        fr[b] = CwaFrame{f.pos, f.n, f.e, cbase, cwa_chunks(f.n)};
+        cbase += fr[b].nc;
+    }
+    const ResyncRegion in{d_cwire, hdr.pos, "the input stream"};
+    const ResyncRegion mk{d_tile_mask, 4 * (uint64_t)nstreams * ((cwa_tiles(c->n) + 31u) / 32u), "d_tile_mask"};
+    if (resync_overlap(mk, in)) return resync_overlap_fail(mk, in);
+    if (int rc = use_device(c)) return rc;
+    CwaArgs a{};
+    a.cwire = (const uint8_t *)d_cwire;
+    a.ftab = c->cwa_ftab;
+    a.chunk = c->cwa_chunk;
+    a.dir = c->cwa_dir;
+    a.n = c->n;
+    a.ntiles = cwa_tiles(c->n);
+    HIP_TRY(launch_cwire_touched(a, fr.data(), nstreams, nframes, accumulate != 0, (uint32_t *)d_tile_mask, c->stream));
+    return MI355_OK;
+}
+
 int mi355_int_diff(mi355_core *c, const void *d_cur, const void *d_prev, void *d_out, size_t n) {
     if (!c || (n && (!d_cur || !d_prev || !d_out))) return fail(MI355_ERR_INVALID, "null argument");
     if (int rc = use_device_filter(c)) return rc;

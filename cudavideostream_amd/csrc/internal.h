@@ -249,6 +249,28 @@ hipError_t launch_state_digest(const uint8_t *states, size_t stride, uint32_t n,
 hipError_t launch_refresh(const CwaArgs &a, int nstreams, const uint32_t *peer, uint32_t *mask, const CwcOut &o, hipStream_t s);
 // mi355_state_clear_tiles_batch: the tiles of states + s*stride whose bit of mask[s] is set -> 0
 hipError_t launch_state_clear_tiles(uint8_t *states, size_t stride, uint32_t n, int nstreams, const uint32_t *mask, hipStream_t s);
+// A wall of many cameras (include/mi355diff.h).  mi355_wall_compose_batch: the thumbnail of the width x height state at
+// states + s*stride, scale place[s][2] (0: not shown), to (place[s][0], place[s][1]) of the wall; mask: the tile mask above or
+// nullptr (every tile).  The placements travel as kernel arguments, kWallPlaceStreams streams per launch.
+constexpr int kWallPlaceStreams = 128;
+struct WallPlaceArgs {
+    int32_t first;
+    int32_t x[kWallPlaceStreams], y[kWallPlaceStreams], k[kWallPlaceStreams];
+};
+// Thumbnail pixels per workgroup of k_wall_compose: a row's tw pixels in even chunks of a multiple of 16 pixels (a chunk's
+// first source byte, 3*k*u0, keeps its row's 16-byte alignment) whose 3*k*pixels source bytes per row fit the workgroup's 4096
+__host__ __device__ inline uint32_t wall_chunk_pixels(uint32_t tw, uint32_t k) {
+    const uint32_t most = (4096u / (3u * k)) & ~15u;   // 1360 (k = 1) .. 80 (k = 16)
+    const uint32_t nch = (tw + most - 1u) / most;
+    return ((tw + nch - 1u) / nch + 15u) & ~15u;       // <= most
+}
+hipError_t launch_wall_compose(const uint8_t *states, size_t stride, uint32_t width, uint32_t height, int nstreams,
+                               const int32_t *place /* host, [nstreams][3] */, const uint32_t *mask, uint8_t *wall, size_t wall_pitch,
+                               hipStream_t s);
+// mi355_cwire_touched_tiles_batch: behind the directory of the nstreams*nframes records, mask[s] (ceil(a.ntiles / 32) words) = or
+// |= the tiles that a record of stream s has an entry in; a.state / a.out / a.stride unused
+hipError_t launch_cwire_touched(const CwaArgs &a, const CwaFrame *records, int nstreams, int nframes, bool accumulate, uint32_t *mask,
+                                hipStream_t s);
 
 // filters.hip -- every per-frame kernel takes a FrameBatch: frame f lives at base + f*stride
 struct FrameBatch {

@@ -1886,6 +1886,131 @@ __global__ __launch_bounds__(64) void k_state_clear_tiles(uint8_t *states, size_
     if (lane < len - tail) dst[tail + lane] = 0;
 }
 
+// ---- mi355_wall_compose_batch, mi355_cwire_touched_tiles_batch: a wall of many cameras ------------------------------------------
+// The thumbnail of a state at scale k (include/mi355diff.h is the definition): pixel (u, v), channel c is the rounded mean
+// floor((sum + floor(a / 2)) / a) of the a <= k*k source bytes of its block, the blocks at the right and bottom edges smaller.
+//   k_wall_compose (grid: (rows x column chunks, streams of the launch), 256 threads) : a workgroup owns up to wall_chunk_pixels(k)
+//       pixels of ONE thumbnail row: a band of kh <= k source rows, each a contiguous range of at most kWallBytes bytes of the state.
+//       With a mask it first asks whether a tile that one of those ranges meets is selected and returns if none is -- no state
+//       byte moves for a still camera, and a selected tile repaints whole chunks, which the call is allowed to.  Thread j
+//       then owns bytes [16j, 16j + 16) of every range: one 16-byte load per row where the row's address allows it (bytes
+//       otherwise, and at the ragged end), added vertically as 16-bit sums packed two to a register (16 * 255 < 2^16), the
+//       sums to LDS.  Output byte o = 3u + c of the chunk is then the sum of kw LDS entries at a 3-entry pitch; consecutive
+//       threads take consecutive o, so the 16-bit LDS reads of a wave's step lie k entries apart on average (not 4k, as with
+//       four bytes per thread) and its 64 one-byte stores are one 64-byte piece of the wall row.  One integer division per
+//       output byte.
+//   k_cw_touched   (grid: ceil(tiles / 64) x streams, one wave) : behind the directory; lane = tile, the touch test of
+//       k_cwa_apply_multi_stream ORed over the stream's nframes records, a ballot, two mask words per wave stored by lane 0
+//       (ORed onto what is there when accumulating: one wave owns the two words)
+constexpr uint32_t kWallBytes = 4096;   // source bytes of one row per workgroup: 256 threads x 16
+
+struct WallBand {
+    const uint8_t *src;   // byte 0 of the band's first row inside the chunk
+    uint32_t pitch;       // bytes between the band's rows (3 * width)
+    uint32_t kh, cb;      // rows of the band, bytes per row of the chunk
+};
+
+// true: a selected tile of mask (the stream's row) meets one of the band's ranges; off: the band's first byte in the state
+__device__ __forceinline__ bool wall_band_selected(const uint32_t *mask, uint32_t off, const WallBand &b) {
+    bool any = false;
+    for (uint32_t r = 0; r < b.kh; r++) {
+        const uint32_t lo = off + r * b.pitch;
+        for (uint32_t t = lo / kCwaTile; t <= (lo + b.cb - 1u) / kCwaTile; t++) any |= (mask[t >> 5] >> (t & 31u)) & 1u;
+    }
+    return any;
+}
+
+__global__ __launch_bounds__(256) void k_wall_compose(const uint8_t *states, size_t stride, uint32_t width, uint32_t height,
+                                                      const uint32_t *mask, uint32_t mask_words, uint8_t *wall, size_t wall_pitch,
+                                                      const WallPlaceArgs h) {
+    __shared__ cwa_u32x4 s_sum32[kWallBytes / 8];   // 16-bit column sums, eight to a quad
+    const uint32_t j = blockIdx.y, tid = threadIdx.x;
+    const uint32_t k = (uint32_t)h.k[j];
+    if (k == 0) return;
+    const uint32_t tw = (width + k - 1u) / k, th = (height + k - 1u) / k;
+    const uint32_t cp = wall_chunk_pixels(tw, k), nch = (tw + cp - 1u) / cp;
+    if (blockIdx.x >= th * nch) return;
+    const uint32_t v = blockIdx.x / nch, u0 = (blockIdx.x % nch) * cp;
+    const uint32_t cw = tw - u0 < cp ? tw - u0 : cp;                          // thumbnail pixels of the chunk
+    const uint32_t x1 = (u0 + cw) * k < width ? (u0 + cw) * k : width;       // its source columns [u0 * k, x1)
+    const uint32_t st = (uint32_t)h.first + j;
+    WallBand b;
+    b.pitch = 3u * width;
+    b.kh = height - v * k < k ? height - v * k : k;
+    b.cb = 3u * (x1 - u0 * k);
+    const uint32_t off = v * k * b.pitch + 3u * u0 * k;
+    b.src = states + (size_t)st * stride + off;
+    if (mask && !wall_band_selected(mask + (size_t)st * mask_words, off, b)) return;   // (the same for every thread)
+
+    // vertical sums of the thread's 16 bytes: ev[d] holds bytes 0 and 2 of dword d, od[d] bytes 1 and 3
+    uint32_t ev[4] = {0u, 0u, 0u, 0u}, od[4] = {0u, 0u, 0u, 0u};
+    const uint32_t c0 = 16u * tid;
+    if (c0 < b.cb) {
+        const uint32_t mine = b.cb - c0 < 16u ? b.cb - c0 : 16u;
+        for (uint32_t r = 0; r < b.kh; r++) {
+            const uint8_t *row = b.src + (size_t)r * b.pitch;
+            cwa_u32x4 q = {0u, 0u, 0u, 0u};
+            if (mine == 16u && !((uintptr_t)row & 15u)) {
+                q = *(const cwa_u32x4 *)(row + c0);
+            } else {
+#pragma unroll
+                for (uint32_t i = 0; i < 16u; i++)
+                    if (i < mine) q[i / 4u] |= (uint32_t)row[c0 + i] << (8u * (i % 4u));
+            }
+#pragma unroll
+            for (uint32_t d = 0; d < 4u; d++) {
+                ev[d] += q[d] & 0x00FF00FFu;
+                od[d] += (q[d] >> 8) & 0x00FF00FFu;
+            }
+        }
+    }
+    cwa_u32x4 w0, w1;   // sums of bytes 0 .. 7 and 8 .. 15, in byte order
+#pragma unroll
+    for (uint32_t d = 0; d < 2u; d++) {
+        w0[2u * d] = (ev[d] & 0xFFFFu) | (od[d] << 16);
+        w0[2u * d + 1u] = (ev[d] >> 16) | (od[d] & 0xFFFF0000u);
+        w1[2u * d] = (ev[d + 2u] & 0xFFFFu) | (od[d + 2u] << 16);
+        w1[2u * d + 1u] = (ev[d + 2u] >> 16) | (od[d + 2u] & 0xFFFF0000u);
+    }
+    s_sum32[2u * tid] = w0;
+    s_sum32[2u * tid + 1u] = w1;
+    __syncthreads();
+
+    const uint16_t *s_sum = (const uint16_t *)s_sum32;
+    uint8_t *out = wall + (size_t)((uint32_t)h.y[j] + v) * wall_pitch + 3u * ((size_t)(uint32_t)h.x[j] + u0);
+    for (uint32_t o = tid; o < 3u * cw; o += 256u) {
+        const uint32_t u = o / 3u, c = o - 3u * u;
+        const uint32_t left = width - (u0 + u) * k, kw = left < k ? left : k;
+        const uint32_t a = kw * b.kh;
+        uint32_t sum = 0;
+        for (uint32_t i = 0; i < kw; i++) sum += s_sum[3u * (u * k + i) + c];
+        out[o] = (uint8_t)(a == 1u ? sum : (sum + a / 2u) / a);
+    }
+}
+
+__global__ __launch_bounds__(64) void k_cw_touched(const CwaArgs a, int nframes, int accumulate, uint32_t *mask, uint32_t mask_words) {
+    const uint32_t lane = threadIdx.x, waves = (a.ntiles + 63u) / 64u;   // workgroup w: stream w / waves, tiles 64 (w % waves) ..
+    const uint32_t st = blockIdx.x / waves, wv = blockIdx.x % waves;
+    const uint32_t tile = 64u * wv + lane;
+    const size_t b0 = (size_t)st * nframes;   // the stream's first batch index
+    bool touch = false;
+    if (tile < a.ntiles) {
+        for (int t = 0; t < nframes; t++) {
+            const uint32_t fn = a.ftab[b0 + t].n;
+            const uint4 *dir = a.dir + (b0 + t) * a.ntiles + tile;
+            const uint32_t k0 = dir[0].x, kend = tile + 1 < a.ntiles ? dir[1].x : fn;
+            touch |= k0 < kend && k0 < fn;
+        }
+    }
+    const uint64_t set = __ballot(touch);
+    if (lane == 0) {
+        uint32_t *row = mask + (size_t)st * mask_words;
+        const uint32_t w = 2u * wv;   // (< mask_words: the wave has a tile)
+        row[w] = (accumulate ? row[w] : 0u) | (uint32_t)set;
+        if (w + 1u < mask_words) row[w + 1u] = (accumulate ? row[w + 1u] : 0u) | (uint32_t)(set >> 32);
+    }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 uint32_t cwa_chunks(uint32_t n) { return n ? (n + kCwaChunk - 1) / kCwaChunk : 1u; }
 uint32_t cwa_tiles(uint32_t nbytes) { return (nbytes + kCwaTile - 1) / kCwaTile; }
@@ -2022,6 +2147,40 @@ hipError_t launch_state_clear_tiles(uint8_t *states, size_t stride, uint32_t n, 
     if (nstreams <= 0 || ntiles == 0) return hipSuccess;
     hipLaunchKernelGGL(k_state_clear_tiles, dim3(ntiles * (uint32_t)nstreams), dim3(64), 0, s, states, stride, n, ntiles, mask,
                        (ntiles + 31u) / 32u);
+    return hipGetLastError();
+}
+
+hipError_t launch_wall_compose(const uint8_t *states, size_t stride, uint32_t width, uint32_t height, int nstreams,
+                               const int32_t *place, const uint32_t *mask, uint8_t *wall, size_t wall_pitch, hipStream_t s) {
+    const uint32_t mask_words = (cwa_tiles(3u * width * height) + 31u) / 32u;
+    WallPlaceArgs h{};
+    for (int s0 = 0; s0 < nstreams; s0 += kWallPlaceStreams) {
+        h.first = s0;
+        const int ns = nstreams - s0 < kWallPlaceStreams ? nstreams - s0 : kWallPlaceStreams;
+        uint32_t blocks = 0;   // of the launch's stream that has the most
+        for (int j = 0; j < ns; j++) {
+            const int32_t *p = place + 3 * (size_t)(s0 + j);
+            h.x[j] = p[0];
+            h.y[j] = p[1];
+            h.k[j] = p[2];
+            if (p[2] < 1) continue;
+            const uint32_t k = (uint32_t)p[2], tw = (width + k - 1u) / k, th = (height + k - 1u) / k;
+            const uint32_t cp = wall_chunk_pixels(tw, k), b = th * ((tw + cp - 1u) / cp);
+            blocks = b > blocks ? b : blocks;
+        }
+        if (blocks)
+            hipLaunchKernelGGL(k_wall_compose, dim3(blocks, (uint32_t)ns), dim3(256), 0, s, states, stride, width, height, mask, mask_words,
+                               wall, wall_pitch, h);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_cwire_touched(const CwaArgs &a, const CwaFrame *records, int nstreams, int nframes, bool accumulate, uint32_t *mask,
+                                hipStream_t s) {
+    if (nstreams <= 0 || nframes <= 0 || a.ntiles == 0) return hipSuccess;
+    launch_cwa_directory(a, records, nstreams * nframes, s);
+    hipLaunchKernelGGL(k_cw_touched, dim3((a.ntiles + 63u) / 64u * (uint32_t)nstreams), dim3(64), 0, s, a, nframes, accumulate ? 1 : 0, mask,
+                       (a.ntiles + 31u) / 32u);
     return hipGetLastError();
 }
 

@@ -92,7 +92,8 @@ typedef struct mi355_config {
  *      + mi355_activity_batch, mi355_cwire_activity_batch, mi355_activity_cells (additions only);
  *      + mi355_cwire_check_host, mi355_cwire_check_batch, MI355_CWIRE_BAD_* (additions only);
  *      + mi355_state_tiles, mi355_state_digest_host, mi355_state_digest_batch, mi355_refresh_cwire_batch,
- *      mi355_state_clear_tiles_batch (additions only) */
+ *      mi355_state_clear_tiles_batch (additions only);
+ *      + mi355_wall_thumb_size, mi355_wall_compose_batch, mi355_cwire_touched_tiles_batch (additions only) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -838,6 +839,84 @@ int mi355_refresh_cwire_batch(mi355_core *core, const void *d_states, size_t str
                               void *d_tile_mask /* uint32[nstreams][mask_words] */, void *d_offsets /* uint32[nstreams + 1] */,
                               void *d_frame_pos /* uint64[nstreams + 1] */, void *d_cwire_out, size_t capacity_bytes);
 int mi355_state_clear_tiles_batch(mi355_core *core, void *d_states, size_t stride_bytes, int nstreams, const void *d_tile_mask);
+
+/* ---- A wall of many cameras: thumbnails of many states in one frame, repainted where records landed ---------------------------
+ * The third node of the compact wire, next to the relay and the recorder: a receiver that holds S camera states
+ * (mi355_apply_multi_stream_cwire_batch) and shows them side by side.  mi355_wall_compose_batch box-downscales the states into
+ * thumbnails placed in ONE wall frame; mi355_cwire_touched_tiles_batch says which tiles the records of a tick or burst land in, as
+ * the tile mask of mi355_refresh_cwire_batch (uint32[S][mask_words], tiles and mask_words as defined there), and with that mask
+ * the compose moves state bytes only where something changed.  All integers, every comparison exact.
+ *   The thumbnail of a state (width x height BGR24, N = 3*width*height) at scale k in 1 .. 16 is tw x th pixels,
+ *   tw = ceil(width / k), th = ceil(height / k) (mi355_wall_thumb_size: host only, returns tw*th and the two through the pointers
+ *   that are not null; 0 and zeros for width or height < 1 or k outside 1 .. 16).  Pixel (u, v), channel c: its block is the
+ *   source pixels x in [u*k, min(width, (u + 1)*k)), y in [v*k, min(height, (v + 1)*k)), a their number (the blocks at the right
+ *   and bottom edges are smaller when k does not divide the frame), and
+ *     value = floor((sum of the block's channel-c bytes + floor(a / 2)) / a).
+ *   k = 1 is a copy; a k above the width or the height gives a thumbnail one pixel wide or high.
+ *   The wall is BGR24, wall_w x wall_h pixels, pixel (X, Y) at d_wall + Y*wall_pitch + 3*X, wall_pitch >= 3*wall_w; d_wall and
+ *   the pitch may have any alignment.  h_place is a HOST array int32[nstreams][3] = {x, y, k}: the thumbnail of stream s (the N
+ *   bytes at d_states + s*stride_bytes, any alignment, as for the apply calls) occupies [x, x + tw) x [y, y + th) of the wall;
+ *   k == 0: the stream is not shown and nothing of it is read or written.
+ * mi355_wall_compose_batch with d_tile_mask == NULL writes every pixel of every shown thumbnail from the current states.  With a
+ * mask, a thumbnail pixel of stream s is REQUIRED when its block contains a source pixel p whose bytes [3p, 3p + 3) meet a tile
+ * whose bit of d_tile_mask[s] is set (a pixel that straddles a tile edge belongs to both tiles).  Every required pixel is
+ * rewritten from the current states; the call may also rewrite any other pixel of the same stream's thumbnail, with that pixel's
+ * correct value; a stream with no selected tile has no pixel written; mask bits at or past tiles are ignored.
+ *   Both forms: nothing is ever written outside the shown thumbnails' rectangles -- the pitch gap, the wall between the
+ *   rectangles and the memory around the wall stay untouched.  The states are only read, the core's own state is untouched,
+ *   nothing is allocated.  Asynchronous on the core's stream, in call order behind an apply or a clear on the same core with no
+ *   synchronisation in between.  h_place may be reused as soon as the call returns: it travels as kernel arguments, 128 streams
+ *   per launch.  Rectangles that overlap each other are not checked: their shared pixels are unspecified among the overlapping
+ *   thumbnails' values.
+ *   Refused with MI355_ERR_INVALID before anything is launched or written: a null core; nstreams outside [0, max_batch]; with
+ *   nstreams > 0 a null d_states, h_place or d_wall, stride_bytes < N, wall_w or wall_h < 1, wall_pitch < 3*wall_w, a k outside
+ *   [0, 16], a shown rectangle not inside the wall, a mask that is not 4-byte aligned, the wall's region
+ *   [d_wall, + (wall_h - 1)*wall_pitch + 3*wall_w) or the mask overlapping the states' region, or overlapping each other.
+ *   nstreams == 0 does nothing.
+ *   The property that ties the calls together: if the wall equals the full composition of the states before a tick, then
+ *   apply (mi355_apply_multi_stream_cwire_batch), mi355_cwire_touched_tiles_batch of the same records and the masked compose,
+ *   with no wait between the three, make it the full composition of the states after the tick.  The same holds for a resync:
+ *   mi355_state_clear_tiles_batch, the apply of the refresh records, and the masked compose with the refresh call's own mask.
+ *   The masks are one object: a tick's mask and a refresh's mask OR together (accumulate below).
+ *   Kernel: k_wall_compose, one for both forms.  A workgroup of 256 threads owns a chunk of one thumbnail row of one stream: a
+ *   band of up to k source rows, each a contiguous range of at most 4096 bytes of the state (chunks are multiples of 16 pixels,
+ *   so a chunk starts at the alignment of its row).  With a mask it first tests the bits of the tiles those ranges meet and
+ *   returns if none is set, before a state byte moves -- which is why correct rewrites beyond the required set are allowed.
+ *   Otherwise thread j loads bytes [16j, 16j + 16) of every row of the band (one 16-byte load where the row's address allows
+ *   it, bytes otherwise and at the ragged end), adds them vertically in registers as 16-bit sums and puts the sums into LDS; the
+ *   threads then produce the chunk's output bytes, consecutive threads consecutive bytes: the sum of up to k LDS entries at a
+ *   3-entry pitch, the rounding term, one integer division, one byte store.
+ * mi355_cwire_touched_tiles_batch: the records lie back to back where the host's headers put them, batch index
+ * b = s*nframes + t, described as for mi355_cwire_activity_batch (the header words in the buffer are skipped, not trusted).  Bit
+ * t & 31 of d_tile_mask[s][t >> 5] is set exactly when some record of stream s has an entry whose decoded index x lies in tile t,
+ * 4096 t <= x < min(N, 4096 (t + 1)); bits at or past tiles are zero.  accumulate == 0 overwrites the nstreams rows;
+ * accumulate != 0 ORs onto what they hold (a refresh mask, the mask of earlier ticks).  It uses the directory kernels of
+ * mi355_apply_cwire_batch and nothing else of the core; no state is touched, nothing is allocated; asynchronous on the core's
+ * stream.  Malformed content under consistent headers gets the memory-safety guarantees of mi355_cwire_activity_batch: only that
+ * stream's own mask words below tiles are unspecified.  Refused before anything is launched or written: a null core; negative
+ * counts; nstreams*nframes > max_batch; d_cwire or the mask not 4-byte aligned; with nstreams*nframes > 0 a null pointer,
+ * h_escapes[b] > h_counts[b], h_counts[b] > N, or the input span overlapping the mask.  nstreams*nframes == 0 does nothing (no
+ * row is written).
+ *   Kernel: k_cw_touched behind the directory, a lane per tile (a wave per 64 tiles of a stream).  Each lane walks the stream's
+ *   nframes records reading dir[b][tile] and dir[b][tile + 1] -- the touch test of the multi-stream apply; neighbouring lanes read
+ *   neighbouring words -- and ORs over t; a ballot gives the wave's two mask words and lane 0 stores them, after a plain load and
+ *   OR when accumulating (one wave owns those words).  No atomics.
+ * Measured: profiles/multi_wall.json (tools/bench_multi.py --legs wall --streams 4,16,64; microseconds per stream, 1080p,
+ * k = 2, 4, 8, median of five rounds, spreads below 3 %, one run on one board).  Both expectations were MISSED.  The full compose
+ * at k = 8 takes 2.13 / 1.40 / 1.42 us per stream at S = 4 / 16 / 64 against 1.60 / 1.10 / 1.04 for mi355_state_digest_batch
+ * on the same aligned states (1.28 to 1.37 times slower; k = 4: 2.58 / 1.71 / 1.77, k = 2: 4.47 / 3.46 / 3.38).  Touched tiles
+ * plus the masked compose on the moving-block tick (367 of 1519 tiles touched) take 12.2 / 3.8 / 1.6 us per stream at k = 8:
+ * cheaper than the full compose only at S = 64 with k = 2 (0.80 times), dearer everywhere else (1.08 to 5.7 times), because the
+ * touched-tiles call pays the directory's six launches again, 40 to 75 us per call whatever S is; a mask that comes for free (the
+ * refresh's) was not measured alone.  The skewed layout (base + 1, stride N: byte loads) takes 8.4 / 6.8 / 7.1 at k = 4, reported
+ * and not judged.  DESIGN.md says what bounds both.
+ * DESIGN.md section 4, "A wall of many cameras". */
+size_t mi355_wall_thumb_size(int width, int height, int k, int *tw, int *th);
+int mi355_wall_compose_batch(mi355_core *core, const void *d_states, size_t stride_bytes, int nstreams,
+                             const int32_t *h_place /* [nstreams][3] */, const void *d_tile_mask /* or NULL: every tile */,
+                             void *d_wall, int wall_w, int wall_h, size_t wall_pitch);
+int mi355_cwire_touched_tiles_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
+                                    int nstreams, int nframes, int accumulate, void *d_tile_mask /* uint32[nstreams][mask_words] */);
 
 /* Integer difference of tests/algorithms_benchmarks.cu:24-30 (kernel1): d[i] = cur[i] - prev[i] on
  * int32 arrays of n elements, no threshold, no pack. */

@@ -91,6 +91,20 @@ calls that resynchronise a receiver, in microseconds per stream, ONE JSON line f
 The expectation to test: `digest` no slower than `diff` at any S by more than the rounds' spread (`verdict`).  The other figures
 are reported, not judged.
 
+The wall leg (--legs wall, a run of its own: `--legs wall --streams 4,16,64 > profiles/multi_wall.json`) measures the calls of a
+wall that shows its cameras, in microseconds per stream, ONE JSON line for all S, at the scales k = 2, 4 and 8, the wall a grid
+of ceil(sqrt(S)) columns:
+  digest             mi355_state_digest_batch on the same 16-byte aligned states: like the full compose it reads N per stream once;
+  full_k2, full_k4, full_k8
+                     mi355_wall_compose_batch without a mask: every thumbnail from the states;
+  full_skewed_k4     the same on a copy of the states one byte behind an aligned address, stride N: every row takes the byte
+                     loads (reported, not judged);
+  masked_webcam_k*, masked_local_k*
+                     mi355_cwire_touched_tiles_batch plus the masked compose on the records of ONE tick: a webcam-like tick
+                     (noise everywhere: nearly every tile is touched) and a block moving over a still background.
+The expectations to test: `masked_local` cheaper than `full` at every k and S by more than the rounds' spread, and `full_k8` no
+slower than `digest` by more than the spread (`verdict`).  The other figures are reported, not judged.
+
 Input of the other legs: ONE webcam stream of S + K + 1 frames; stream s shows frame s + j at step j, so every tick of every stream is the
 step between two consecutive webcam frames, and a tick's S frames are one contiguous region.  j walks 1 .. K and back."""
 import argparse
@@ -799,6 +813,117 @@ def run_refresh(W, H, S, rounds):
     return out
 
 
+def run_wall(W, H, S, rounds, scales=(2, 4, 8)):
+    """The wall leg for one S -> its dictionary.  All legs on one core's own stream, alternating within every round."""
+    import numpy as np
+    from cudavideostream_amd import CUDACore, cwire_bytes_max, state_tiles, wall_thumb_size
+    dev = torch.device("cuda", 0)
+    n = 3 * W * H
+    tiles = state_tiles(n)
+    mask_words = (tiles + 31) // 32
+    passes = max(2, min(16, 128 // S))
+    cols = int(np.ceil(np.sqrt(S)))
+    cwcap = cwire_bytes_max(n, S)
+    d_off = torch.zeros(S + 1, dtype=torch.int32, device=dev)
+    d_pos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
+    d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
+    d_mask = torch.zeros(S * mask_words, dtype=torch.int32, device=dev)
+    d_dig = torch.zeros(S * tiles * 2, dtype=torch.int32, device=dev)
+    core = CUDACore(W, H, max_batch=S)
+    # ---- one tick of every input: the states after it and its records
+    ticks = {}
+    for kind in ("webcam", "local"):
+        if kind == "webcam":
+            _, web = synth.webcam_stream(S + 1, W, H, device=dev)
+            web = web.reshape(S + 1, n)
+            before, frames = web[:S].clone(), web[1:].clone()
+        else:
+            before, fwd = local_streams(S, 1, W, H, dev)
+            frames = fwd[:, 0].contiguous()
+        states = before.clone()
+        torch.cuda.synchronize()
+        core.diff_multi_cwire_batch(frames, states, S, d_off, d_pos, d_cw, cwcap)
+        core.synchronize()
+        pos = d_pos.cpu().numpy().astype(np.int64)
+        counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
+        escapes = ((np.diff(pos) - 8 - 2 * ((counts.astype(np.int64) + 3) & ~3)) // 4).astype(np.uint32)
+        core.cwire_touched_tiles_batch(d_cw, counts, escapes, S, 1, d_mask)
+        core.synchronize()
+        touched = int(sum(bin(int(v) & 0xFFFFFFFF).count("1") for v in d_mask.cpu().numpy()))
+        ticks[kind] = (states, d_cw[:int(pos[S])].clone(), counts, escapes, touched)
+        del before, frames
+    aligned = ticks["webcam"][0]
+    assert aligned.data_ptr() % 16 == 0
+    skew_buf = torch.empty(S * n + 16, dtype=torch.uint8, device=dev)
+    skewed = skew_buf[1:1 + S * n]                       # 1080p: N is a multiple of 16, so every stream is one byte off
+    skewed.copy_(aligned.reshape(-1))
+    walls = {}
+    for k in scales:
+        _, tw, th = wall_thumb_size(W, H, k)
+        place = np.array([((s % cols) * tw, (s // cols) * th, k) for s in range(S)], np.int32)
+        wall_w, wall_h = cols * tw, ((S + cols - 1) // cols) * th
+        walls[k] = (place, torch.zeros(wall_h * wall_w * 3, dtype=torch.uint8, device=dev), wall_w, wall_h)
+    torch.cuda.synchronize()
+
+    def leg_digest():
+        for _ in range(passes):
+            core.state_digest_batch(aligned, S, d_dig)
+        core.synchronize()
+
+    def leg_full(k, states):
+        place, d_wall, wall_w, wall_h = walls[k]
+
+        def leg():
+            for _ in range(passes):
+                core.wall_compose_batch(states, S, place, d_wall, wall_w, wall_h)
+            core.synchronize()
+        return leg
+
+    def leg_masked(k, kind):
+        place, d_wall, wall_w, wall_h = walls[k]
+        states, recs, counts, escapes, _ = ticks[kind]
+
+        def leg():
+            for _ in range(passes):
+                core.cwire_touched_tiles_batch(recs, counts, escapes, S, 1, d_mask)
+                core.wall_compose_batch(states, S, place, d_wall, wall_w, wall_h, d_tile_mask=d_mask)
+            core.synchronize()
+        return leg
+
+    table = {"digest": leg_digest, "full_skewed_k4": leg_full(4, skewed)}
+    for k in scales:
+        table[f"full_k{k}"] = leg_full(k, aligned)
+        table[f"masked_webcam_k{k}"] = leg_masked(k, "webcam")
+        table[f"masked_local_k{k}"] = leg_masked(k, "local")
+    times = {}
+    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
+        for name, leg in table.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            leg()
+            dt = time.perf_counter() - t0
+            if r:
+                times.setdefault(name, []).append(dt * 1e6 / (passes * S))
+    out = {"streams": S, "passes": passes, "tiles": tiles, "state_bytes": n, "columns": cols,
+           "touched_tiles_per_stream": {kind: round(ticks[kind][4] / S, 1) for kind in ticks}}
+    for name in table:
+        st = stats(times[name])
+        st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
+        out[name + "_us_per_stream"] = st
+    med = {k: statistics.median(v) for k, v in times.items()}
+
+    def spread(*names):
+        return max(max(times[k]) - min(times[k]) for k in names)
+
+    out["masked_local_over_full"] = {f"k{k}": round(med[f"masked_local_k{k}"] / med[f"full_k{k}"], 3) for k in scales}
+    out["masked_local_cheaper_than_full"] = bool(all(
+        med[f"masked_local_k{k}"] + spread(f"masked_local_k{k}", f"full_k{k}") < med[f"full_k{k}"] for k in scales))
+    out["full_k8_over_digest"] = round(med["full_k8"] / med["digest"], 3)
+    out["full_k8_no_slower_than_digest"] = bool(med["full_k8"] <= med["digest"] + spread("full_k8", "digest"))
+    core.close()
+    return out
+
+
 def run_coalesce(W, H, S, T, rounds, kind):
     """The coalesce leg for one (S, T) and one input -> its dictionary.  coalesce: mi355_cwire_coalesce_cwire_batch on the
     burst's records, nothing else.  state_route: what a relay did before -- mi355_apply_multi_stream_cwire_batch onto states it
@@ -977,7 +1102,7 @@ def main():
     ap.add_argument("--steps", type=int, default=8, help="K: webcam frames a stream walks through")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--legs", default="multi,cores_loop,pairs",
-                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or budget alone; or activity alone; or check alone; or refresh alone")
+                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or budget alone; or activity alone; or check alone; or refresh alone; or wall alone")
     ap.add_argument("--frames", default="4,16,64", help="burst, burst_client and coalesce legs: T, frames per stream and call")
     a = ap.parse_args()
     have = load_library()
@@ -1060,6 +1185,19 @@ def main():
         print(json.dumps({"bench": "multi_refresh", "size": f"{W}x{H}", "rounds": a.rounds, "refresh": per,
                           "verdict": "digest no slower than diff at every S" if all(p["digest_no_slower_than_diff"] for p in per)
                           else "digest slower than diff at some S"}), flush=True)
+        return
+    if a.legs == "wall":
+        per = []
+        for S in (int(v) for v in a.streams.split(",")):
+            per.append(run_wall(W, H, S, a.rounds))
+            print(f"wall S={S}: done", file=sys.stderr, flush=True)
+            torch.cuda.empty_cache()
+        ok_mask, ok_full = all(p["masked_local_cheaper_than_full"] for p in per), all(p["full_k8_no_slower_than_digest"] for p in per)
+        print(json.dumps({"bench": "multi_wall", "size": f"{W}x{H}", "rounds": a.rounds, "wall": per,
+                          "verdict": ("masked update on the moving block cheaper than the full compose at every k and S"
+                                      if ok_mask else "masked update on the moving block not cheaper than the full compose at some k or S")
+                          + "; " + ("full compose at k = 8 no slower than digest at every S" if ok_full
+                                    else "full compose at k = 8 slower than digest at some S")}), flush=True)
         return
     for S in (int(v) for v in a.streams.split(",")):
         run(W, H, S, a.steps, a.rounds, set(a.legs.split(",")), have)

@@ -58,6 +58,13 @@
 // refresh on -- equals the sender's; the dropped camera has mask bits and, unless ticks were in flight, only that camera (the
 // others get the 8-byte record); a host client that
 // clears the tiles itself and calls mi355_cwire_apply_host ends at the same frames.
+// --compact --multi S --wall K [--burst B --burst-client | --resync R [--burst B]]: the receiver is a wall that shows its cameras.  It
+// keeps ONE wall frame of ceil(sqrt(S)) columns of thumbnails at scale K, composed fully once (mi355_wall_compose_batch without
+// a mask).  After every tick's apply -- with --burst B --burst-client after every burst's -- it asks which tiles the records it just
+// applied land in (mi355_cwire_touched_tiles_batch) and repaints the wall there (mi355_wall_compose_batch with that mask), the
+// three calls with no wait in between.  With --resync R the refresh's own mask goes through the same masked compose behind the
+// clear and the apply.  After every tick or burst, and after the refresh, the wall must equal a plain C++ box average of the
+// receiver's states, and the wall's bytes outside the thumbnails the pattern they started as.
 // --compact --per-frame: the per-frame server, one host frame per call and no device pointer in sight.  The sender feeds
 // host frames through mi355_pipe_submit_cwire, four in flight, and writes each frame's record to the pipe with ONE write()
 // from the pinned buffer it arrived in; the receiver -- a thread with no core -- reads header and body, applies the record
@@ -65,7 +72,7 @@
 // (mi355_exec on a second core: frame[xs[i]] += diff[i], client/opencv.cpp:64-66).
 //
 //   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B]
-//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check] | --resync K [--burst B]]]
+//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check] | --resync K [--burst B]] [--wall K]]
 //   exit status 0 = all checks passed
 #include <algorithm>
 #include <cstdint>
@@ -283,8 +290,97 @@ struct RecordCheck {
     }
 };
 
+// --wall K (see the head of the file): the receiver's wall of thumbnails, kept current where records land, against a box average
+// made here
+struct WallCheck {
+    mi355_core *core = nullptr;
+    int w = 0, h = 0, k = 0, S = 0, tw = 0, th = 0, cols = 0, wall_w = 0, wall_h = 0, composes = 0, compared = 0;
+    size_t pitch = 0, mask_bytes = 0;
+    void *d_wall = nullptr, *d_mask = nullptr;
+    std::vector<int32_t> place;
+    std::vector<uint8_t> got, want;
+    enum : uint8_t { kPattern = 0x5C };     // what the wall holds outside the thumbnails (and in its pitch gap), from start to end
+
+    int open(mi355_core *c, int w_, int h_, int k_, int S_) {
+        if (!mi355_wall_thumb_size(w_, h_, k_, &tw, &th)) { fprintf(stderr, "--wall K needs 1 <= K <= 16\n"); return 2; }
+        core = c; w = w_; h = h_; k = k_; S = S_;
+        while (cols * cols < S) cols++;
+        const int rows = (S + cols - 1) / cols;
+        wall_w = cols * (tw + 1) + 1;   // a pixel of the pattern around every thumbnail
+        wall_h = rows * (th + 1) + 1;
+        pitch = (size_t)3 * wall_w + 5;
+        place.resize((size_t)3 * S);
+        for (int s = 0; s < S; s++) {
+            place[3 * s] = 1 + (s % cols) * (tw + 1);
+            place[3 * s + 1] = 1 + (s / cols) * (th + 1);
+            place[3 * s + 2] = k;
+        }
+        mask_bytes = 4 * (size_t)S * ((mi355_state_tiles((size_t)3 * w * h) + 31) / 32);
+        got.assign(pitch * wall_h, kPattern);
+        want = got;
+        OK(mi355_dev_alloc(core, &d_wall, got.size()));
+        OK(mi355_dev_alloc(core, &d_mask, mask_bytes));
+        OK(mi355_upload(core, d_wall, got.data(), got.size()));
+        return 0;
+    }
+    // every thumbnail from the states as they are
+    int full(const void *d_states) {
+        if (!k) return 0;
+        OK(mi355_wall_compose_batch(core, d_states, (size_t)3 * w * h, S, place.data(), nullptr, d_wall, wall_w, wall_h, pitch));
+        composes++;
+        return 0;
+    }
+    // behind the apply of the nb records of each camera at d_rx (headers counts / escapes): their tiles, repainted
+    int update(const void *d_rx, const uint32_t *counts, const uint32_t *escapes, int nb, const void *d_states) {
+        if (!k) return 0;
+        OK(mi355_cwire_touched_tiles_batch(core, d_rx, counts, escapes, S, nb, 0, d_mask));
+        return masked(d_mask, d_states);
+    }
+    int masked(const void *d_tile_mask, const void *d_states) {
+        if (!k) return 0;
+        OK(mi355_wall_compose_batch(core, d_states, (size_t)3 * w * h, S, place.data(), d_tile_mask, d_wall, wall_w, wall_h, pitch));
+        composes++;
+        return 0;
+    }
+    // the wall against the box average of `states` (the receiver's, S frames back to back)
+    int compare(const uint8_t *states, int t) {
+        if (!k) return 0;
+        OK(mi355_download(core, got.data(), d_wall, got.size()));
+        for (int s = 0; s < S; s++) {
+            const uint8_t *st = states + (size_t)s * 3 * w * h;
+            for (int v = 0; v < th; v++)
+                for (int u = 0; u < tw; u++) {
+                    const int x0 = u * k, x1 = std::min(w, x0 + k), y0 = v * k, y1 = std::min(h, y0 + k);
+                    const uint32_t a = (uint32_t)((x1 - x0) * (y1 - y0));
+                    uint32_t sum[3] = {0, 0, 0};
+                    for (int y = y0; y < y1; y++)
+                        for (int x = x0; x < x1; x++)
+                            for (int c = 0; c < 3; c++) sum[c] += st[3 * ((size_t)y * w + x) + c];
+                    uint8_t *o = &want[(size_t)(place[3 * s + 1] + v) * pitch + 3 * (size_t)(place[3 * s] + u)];
+                    for (int c = 0; c < 3; c++) o[c] = (uint8_t)((sum[c] + a / 2) / a);
+                }
+        }
+        if (got != want) { fprintf(stderr, "tick %d: the wall != the box average of the receiver's states\n", t); return 1; }
+        compared++;
+        return 0;
+    }
+    std::string json() const {
+        if (!k) return "";
+        return ", \"wall\": {\"scale\": " + std::to_string(k) + ", \"size\": [" + std::to_string(wall_w) + ", " + std::to_string(wall_h) +
+               "], \"thumb\": [" + std::to_string(tw) + ", " + std::to_string(th) + "], \"composes\": " + std::to_string(composes) +
+               ", \"walls_equal\": " + std::to_string(compared) + "}";
+    }
+    int close() {
+        if (!k) return 0;
+        if (!compared) { fprintf(stderr, "--wall: no wall was compared\n"); return 1; }
+        OK(mi355_dev_free(core, d_wall));
+        OK(mi355_dev_free(core, d_mask));
+        return 0;
+    }
+};
+
 // --compact --multi S (see the head of the file)
-static int run_multi(int w, int h, int T, int S, int activity, bool check) {
+static int run_multi(int w, int h, int T, int S, int activity, bool check, int wall_k) {
     const size_t n = (size_t)3 * w * h;
     mi355_config cfg;
     memset(&cfg, 0, sizeof cfg);
@@ -308,6 +404,9 @@ static int run_multi(int w, int h, int T, int S, int activity, bool check) {
     RecordCheck chk;
     if (check)
         if (int rc = chk.open(client, n, S)) return rc;
+    WallCheck wall;
+    if (wall_k)
+        if (int rc = wall.open(client, w, h, wall_k, S)) return rc;
     int fds[2];
     if (pipe(fds) != 0) return 1;
     // every camera's base frame: the server's states, and through the pipe the client's (opencv.cpp:38-46 per camera)
@@ -318,6 +417,7 @@ static int run_multi(int w, int h, int T, int S, int activity, bool check) {
     OK(mi355_upload(server, d_sstates, bases.data(), bases.size()));
     if (!through_pipe(fds[1], fds[0], bases.data(), host_frames.data(), bases.size())) return 1;
     OK(mi355_upload(client, d_cstates, host_frames.data(), host_frames.size()));
+    if (int rc = wall.full(d_cstates)) return rc;
     std::vector<uint8_t> base(n), frame(n), before(check ? host_frames : std::vector<uint8_t>());   // (before: the states a tick finds)
     std::vector<uint32_t> off(S + 1), counts(S), escapes(S);
     std::vector<uint64_t> pos(S + 1);
@@ -357,8 +457,10 @@ static int run_multi(int w, int h, int T, int S, int activity, bool check) {
         if (int rc = act.run(d_rx, rx.data(), counts.data(), escapes.data(), 1, t)) return rc;
         if (int rc = chk.run(d_rx, rx.data(), cb, counts.data(), escapes.data(), S, t)) return rc;
         OK(mi355_apply_multi_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, d_cstates, n));
+        if (int rc = wall.update(d_rx, counts.data(), escapes.data(), 1, d_cstates)) return rc;
         // ---- checks
         OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
+        if (int rc = wall.compare(c_states.data(), t)) return rc;
         for (int s = 0; s < S && check; s++)
             if (int rc = chk.applied(s, &before[(size_t)s * n], &c_states[(size_t)s * n], t)) return rc;
         if (check) before = c_states;
@@ -380,12 +482,13 @@ static int run_multi(int w, int h, int T, int S, int activity, bool check) {
     OK(mi355_dev_free(client, d_cstates));
     if (int rc = act.close()) return rc;
     if (int rc = chk.close()) return rc;
+    if (int rc = wall.close()) return rc;
     mi355_destroy(server);
     mi355_destroy(client);
     printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"width\": %d, \"height\": %d, \"ticks\": %d, "
-           "\"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d%s%s}\n",
+           "\"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d%s%s%s}\n",
            S, w, h, T, changed, sent_bytes, mi355_wire_bytes(T * S, changed), (size_t)T * S * n, max_err, act.json().c_str(),
-           chk.json().c_str());
+           chk.json().c_str(), wall.json().c_str());
     return 0;
 }
 
@@ -635,7 +738,7 @@ static int run_multi_burst(int w, int h, int T, int S, int K) {
 }
 
 // --compact --multi S --burst K --burst-client (see the head of the file)
-static int run_multi_burst_client(int w, int h, int T, int S, int K, int activity, bool check) {
+static int run_multi_burst_client(int w, int h, int T, int S, int K, int activity, bool check, int wall_k) {
     const size_t n = (size_t)3 * w * h;
     mi355_config cfg;
     memset(&cfg, 0, sizeof cfg);
@@ -661,6 +764,9 @@ static int run_multi_burst_client(int w, int h, int T, int S, int K, int activit
     RecordCheck chk;
     if (check)
         if (int rc = chk.open(client, n, B)) return rc;
+    WallCheck wall;
+    if (wall_k)
+        if (int rc = wall.open(client, w, h, wall_k, S)) return rc;
     int fds[2];
     if (pipe(fds) != 0) return 1;
     std::vector<uint8_t> bases((size_t)S * n), host_frames((size_t)S * n), frames((size_t)B * n), s_states((size_t)S * n),
@@ -670,6 +776,7 @@ static int run_multi_burst_client(int w, int h, int T, int S, int K, int activit
     OK(mi355_upload(server, d_sstates, bases.data(), bases.size()));
     if (!through_pipe(fds[1], fds[0], bases.data(), host_frames.data(), bases.size())) return 1;
     OK(mi355_upload(client, d_cstates, host_frames.data(), host_frames.size()));
+    if (int rc = wall.full(d_cstates)) return rc;
     std::vector<uint8_t> base(n), frame(n), before(check ? host_frames : std::vector<uint8_t>());   // (before: the states a burst finds)
     std::vector<uint32_t> off(B + 1), counts(B), escapes(B);
     std::vector<uint64_t> pos(B + 1);
@@ -720,7 +827,9 @@ static int run_multi_burst_client(int w, int h, int T, int S, int K, int activit
         if (int rc = chk.run(d_rx, rx.data(), cb, counts.data(), escapes.data(), nrec, t0)) return rc;
         // ---- client: the whole burst in one call, every frame in between into d_shown
         OK(mi355_apply_multi_stream_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, nb, d_cstates, n, d_shown, n));
+        if (int rc = wall.update(d_rx, counts.data(), escapes.data(), nb, d_cstates)) return rc;
         OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
+        if (int rc = wall.compare(c_states.data(), t0 + nb - 1)) return rc;
         OK(mi355_download(client, shown.data(), d_shown, (size_t)nrec * n));
         for (int r = 0; r < nrec && check; r++)   // record (s, k) turned the frame after record (s, k - 1) into its own
             if (int rc = chk.applied(r, r % nb ? &shown[(size_t)(r - 1) * n] : &before[(size_t)(r / nb) * n], &shown[(size_t)r * n], t0)) return rc;
@@ -747,13 +856,14 @@ static int run_multi_burst_client(int w, int h, int T, int S, int K, int activit
     for (void *q : cli) OK(mi355_dev_free(client, q));
     if (int rc = act.close()) return rc;
     if (int rc = chk.close()) return rc;
+    if (int rc = wall.close()) return rc;
     mi355_destroy(server);
     mi355_destroy(client);
     printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"burst\": %d, \"burst_client\": true, \"sender_calls\": %d, "
            "\"receiver_calls\": %d, \"width\": %d, \"height\": %d, \"ticks\": %d, \"changed_bytes\": %zu, \"wire_bytes\": %zu, "
-           "\"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d%s%s}\n",
+           "\"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d%s%s%s}\n",
            S, K, calls, calls, w, h, T, changed, sent_bytes, mi355_wire_bytes(T * S, changed), (size_t)T * S * n, max_err,
-           act.json().c_str(), chk.json().c_str());
+           act.json().c_str(), chk.json().c_str(), wall.json().c_str());
     return 0;
 }
 
@@ -1056,7 +1166,7 @@ static int run_per_frame(int w, int h, int T) {
 }
 
 // --compact --multi S --resync R [--burst K] (see the head of the file)
-static int run_multi_resync(int w, int h, int T, int S, int R, int K) {
+static int run_multi_resync(int w, int h, int T, int S, int R, int K, int wall_k) {
     const size_t n = (size_t)3 * w * h;
     if (R < 0 || R + 1 >= T) { fprintf(stderr, "--resync K needs 0 <= K and K + 1 < --frames\n"); return 2; }
     if (K < 1) K = 1;
@@ -1088,6 +1198,9 @@ static int run_multi_resync(int w, int h, int T, int S, int R, int K) {
     OK(mi355_dev_alloc(client, &d_cstates, (size_t)S * n));
     OK(mi355_dev_alloc(client, &d_dig, dig_bytes));
     OK(mi355_dev_alloc(client, &d_cmask, mask_bytes));
+    WallCheck wall;
+    if (wall_k)
+        if (int rc = wall.open(client, w, h, wall_k, S)) return rc;
     int fds[2];
     if (pipe(fds) != 0) return 1;
     // truth: a host client per camera that applies EVERY record -- the sender's state after every tick
@@ -1098,6 +1211,7 @@ static int run_multi_resync(int w, int h, int T, int S, int R, int K) {
     OK(mi355_upload(server, d_sstates, bases.data(), bases.size()));
     if (!through_pipe(fds[1], fds[0], bases.data(), truth.data(), bases.size())) return 1;
     OK(mi355_upload(client, d_cstates, truth.data(), truth.size()));
+    if (int rc = wall.full(d_cstates)) return rc;
     std::vector<uint8_t> base(n), frame(n);
     std::vector<uint32_t> off(B + 1), counts(S), escapes(S), dig(2 * (size_t)S * tiles), dig_up(dig.size()), dig_host(2 * tiles),
         mask(S * mask_words), mask_rx(mask.size());
@@ -1176,6 +1290,7 @@ static int run_multi_resync(int w, int h, int T, int S, int R, int K) {
             }
             OK(mi355_upload(client, d_rx, stage.data(), q));
             OK(mi355_apply_multi_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, d_cstates, n));
+            if (int rc = wall.update(d_rx, counts.data(), escapes.data(), 1, d_cstates)) return rc;   // (the wall shows what it holds)
             if (t == R + 1) {   // the receiver asks: its digests go up
                 OK(mi355_state_digest_batch(client, d_cstates, n, S, d_dig));
                 OK(mi355_download(client, dig.data(), d_dig, dig_bytes));
@@ -1191,6 +1306,7 @@ static int run_multi_resync(int w, int h, int T, int S, int R, int K) {
                     }
                 }
             if (int rc = compare(t)) return rc;
+            if (int rc = wall.compare(c_states.data(), t)) return rc;
         }
         // ---- the states at both ends of the burst: the truth is the sender's
         OK(mi355_download(server, s_states.data(), d_sstates, s_states.size()));
@@ -1237,7 +1353,9 @@ static int run_multi_resync(int w, int h, int T, int S, int R, int K) {
         OK(mi355_upload(client, d_rx, stage.data(), refresh_bytes));
         OK(mi355_state_clear_tiles_batch(client, d_cstates, n, S, d_cmask));
         OK(mi355_apply_multi_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, d_cstates, n));
+        if (int rc = wall.masked(d_cmask, d_cstates)) return rc;   // the refresh's own mask: what was cleared and refilled is repainted
         OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
+        if (int rc = wall.compare(c_states.data(), t0 + nb - 1)) return rc;
         refreshed = true;
         if (memcmp(c_states.data(), host_client.data(), c_states.size()) != 0) { fprintf(stderr, "refresh: client states != host client frames\n"); return 1; }
         if (memcmp(c_states.data(), s_states.data(), c_states.size()) != 0) { fprintf(stderr, "refresh: client states != server states\n"); return 1; }
@@ -1247,19 +1365,20 @@ static int run_multi_resync(int w, int h, int T, int S, int R, int K) {
     for (void *q : srv) OK(mi355_dev_free(server, q));
     void *cli[] = {d_rx, d_cstates, d_dig, d_cmask};
     for (void *q : cli) OK(mi355_dev_free(client, q));
+    if (int rc = wall.close()) return rc;
     mi355_destroy(server);
     mi355_destroy(client);
     printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"burst\": %d, \"resync\": %d, \"width\": %d, \"height\": %d, "
            "\"ticks\": %d, \"dropped_camera\": %d, \"dropped_entries\": %zu, \"wrong_ticks\": %d, \"ticks_equal_after_refresh\": %d, "
            "\"tiles\": %zu, \"tiles_selected\": %zu, \"digest_bytes\": %zu, \"mask_bytes\": %zu, \"refresh_bytes\": %zu, "
-           "\"key_frame_bytes\": %zu, \"wire_bytes\": %zu}\n",
+           "\"key_frame_bytes\": %zu, \"wire_bytes\": %zu%s}\n",
            S, K, R, w, h, T, victim, lost_entries, wrong_ticks, right_ticks_after, tiles, tiles_selected, dig_bytes, mask_bytes,
-           refresh_bytes, (size_t)S * n, sent_bytes);
+           refresh_bytes, (size_t)S * n, sent_bytes, wall.json().c_str());
     return 0;
 }
 
 int main(int argc, char **argv) {
-    int w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0, activity = -1, resync = -1;
+    int w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0, activity = -1, resync = -1, wall = 0;
     long budget = -1;
     bool compact = false, direct = false, gpu_client = false, burst_client = false, coalesce = false, per_frame = false, check = false;
     for (int i = 1; i < argc; i++) {
@@ -1283,6 +1402,7 @@ int main(int argc, char **argv) {
         else if (k == "--burst") burst = v;
         else if (k == "--activity") activity = v < 0 ? 0 : v;
         else if (k == "--resync") resync = v < 0 ? 0 : v;
+        else if (k == "--wall") wall = v < 1 ? -1 : v;
         else if (k == "--budget") budget = atol(argv[i + 1]) < 0 ? 0 : atol(argv[i + 1]);
     }
     if (burst && (!multi || burst < 0)) { fprintf(stderr, "--burst K needs --multi S and K >= 1\n"); return 2; }
@@ -1308,17 +1428,21 @@ int main(int argc, char **argv) {
         fprintf(stderr, "--resync K needs --compact --multi S, alone or with --burst B\n");
         return 2;
     }
+    if (wall && (wall < 0 || wall > 16 || !compact || !multi || budget >= 0 || coalesce || per_frame || (burst && !burst_client && resync < 0))) {
+        fprintf(stderr, "--wall K needs 1 <= K <= 16 and --compact --multi S, alone, with --burst B --burst-client or with --resync R\n");
+        return 2;
+    }
     if (per_frame) {
         if (!compact || direct || gpu_client || multi) { fprintf(stderr, "--per-frame needs --compact alone\n"); return 2; }
         return run_per_frame(w, h, T);
     }
     if (multi) {
         if (!compact || direct || gpu_client || multi < 0) { fprintf(stderr, "--multi S needs --compact alone and S >= 1\n"); return 2; }
-        if (resync >= 0) return run_multi_resync(w, h, T, multi, resync, burst);
-        if (burst_client) return run_multi_burst_client(w, h, T, multi, burst, activity, check);
+        if (resync >= 0) return run_multi_resync(w, h, T, multi, resync, burst, wall);
+        if (burst_client) return run_multi_burst_client(w, h, T, multi, burst, activity, check, wall);
         if (coalesce) return run_multi_burst_coalesce(w, h, T, multi, burst);
         if (budget >= 0) return run_multi_budget(w, h, T, multi, budget);
-        return burst ? run_multi_burst(w, h, T, multi, burst) : run_multi(w, h, T, multi, activity, check);
+        return burst ? run_multi_burst(w, h, T, multi, burst) : run_multi(w, h, T, multi, activity, check, wall);
     }
     const size_t n = (size_t)3 * w * h;
     mi355_config cfg;
