@@ -193,6 +193,17 @@ int mi355_set_glyphs(mi355_core *core, const uint8_t *chars_px, int nglyphs, int
  * not the reference kernel's atomicInc order.
  *   d_frames : nframes frames, frame t at d_frames + t*stride_bytes (stride_bytes >= N; the fast
  *              path needs d_frames and stride_bytes to be multiples of 16)
+ *              Strides and pitches -- every stride_bytes, out_stride_bytes and wall_pitch of this
+ *              header -- are bounded from below only (>= N; the wall pitch >= 3*wall_w); from above
+ *              only the address space bounds them: every index * stride is a 64-bit product, and
+ *              tests/test_far_strides_gpu.py runs every strided entry point (the mi355_group_diff_*
+ *              calls excepted: the same kernels) on windows 4 GiB and more apart, one slab per
+ *              camera.  One speed cliff: the pack kernel's vector path reads a group of frames
+ *              through one 32-bit window and needs 3*stride_bytes + N < 2^32; a larger stride takes
+ *              the byte path (the one unaligned operands take), with identical results and slower.
+ *              By how much has not been measured.  Untested: RECORD buffers past 4 GiB --
+ *              d_frame_pos is 64-bit, but records lie back to back, so a position reaches 2^32 only
+ *              behind 4 GiB of real record bytes.
  *   d_offsets: uint32[nframes+1], exclusive scan of the per-frame counts (offsets[0] = 0)
  *   d_xs     : int32[capacity]  byte indices, frame t's entries at [offsets[t], offsets[t+1])
  *   d_diff   : uint8[capacity]  (uint8)df of the same entries

@@ -113,6 +113,68 @@ class Region:
         return r
 
 
+class FarRegion:
+    """Region's interface for strides of many MiB or GiB: S windows of n bytes, `stride` apart, in ONE device allocation of
+    PAD + skew + (S - 1) * stride + n + PAD bytes that never crosses to the host.  The allocation is filled with GUARD on the
+    device; put() uploads the S x n rows and scatters them there; get() gathers the S windows there, downloads those, and
+    asserts on the device, in pieces of at most 1 GiB, that every other byte -- the front pad, every stride gap in full, the
+    tail pad -- still holds GUARD.  (S * n bytes cross the bus each way, whatever the stride.)"""
+
+    PIECE = 1 << 30
+
+    def __init__(self, S, n, stride, skew=0, device=DEV):
+        assert S >= 1 and stride >= n
+        self.S, self.n, self.stride, self.skew, self.lo = S, n, stride, skew, PAD + skew
+        self.buf = torch.full((self.bytes_needed(S, n, stride, skew),), GUARD, dtype=torch.uint8, device=device)
+        self.ptr = self.buf.data_ptr() + self.lo
+        assert self.buf.data_ptr() % 16 == 0 and self.ptr % 16 == skew % 16
+
+    @staticmethod
+    def bytes_needed(S, n, stride, skew=0):
+        return PAD + skew + (S - 1) * stride + n + PAD
+
+    def window(self, s):
+        """The view of window s (a slice of the allocation: its offset is 64-bit host arithmetic)."""
+        at = self.lo + s * self.stride
+        return self.buf[at:at + self.n]
+
+    def put(self, rows):
+        """rows: S rows of n bytes (an [S, n] array or a list of rows)."""
+        rows = np.ascontiguousarray(np.stack([np.asarray(r, np.uint8) for r in rows]) if not isinstance(rows, np.ndarray) else rows)
+        assert rows.shape == (self.S, self.n) and rows.dtype == np.uint8
+        d = torch.from_numpy(rows).to(self.buf.device)
+        for s in range(self.S):
+            self.window(s).copy_(d[s])
+        return self
+
+    def gaps(self):
+        """[(first byte, end, name)] of everything outside the windows, in address order."""
+        out = [(0, self.lo, "the front pad")]
+        for s in range(self.S - 1):
+            out.append((self.lo + s * self.stride + self.n, self.lo + (s + 1) * self.stride, f"the gap behind window {s}"))
+        end = self.lo + (self.S - 1) * self.stride + self.n
+        out.append((end, self.buf.numel(), "the tail pad"))
+        return [g for g in out if g[1] > g[0]]
+
+    def get(self):
+        """(rows as numpy [S, n]); asserts every guard byte, on the device."""
+        if self.buf.is_cuda:
+            torch.cuda.synchronize()
+        rows = torch.stack([self.window(s) for s in range(self.S)]).cpu().numpy()
+        pieces = [(a, min(a + self.PIECE, hi), name) for lo, hi, name in self.gaps() for a in range(lo, hi, self.PIECE)]
+        bad = torch.stack([(self.buf[a:b] != GUARD).any() for a, b, _ in pieces]).cpu().numpy()
+        for (a, b, name), hit in zip(pieces, bad):
+            if hit:
+                first = a + int(torch.argmax((self.buf[a:b] != GUARD).to(torch.uint8)))   # (the first of the maxima)
+                where = first - self.lo
+                raise AssertionError(f"byte {first} of the allocation (window base {where:+d}, that is {where // self.stride} "
+                                     f"strides and {where % self.stride} bytes) was written: it lies in {name}")
+        return rows
+
+    def free(self):
+        self.buf = None
+
+
 def run_stream(core, frames, capacity=None, stride=None, pair_prev=None):
     """frames: (T, N) uint8 numpy or cuda tensor.  Returns (offsets, xs, diff) as numpy, with xs/diff
     cut to min(total, capacity)."""
