@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -871,47 +872,60 @@ int mi355_diff_stream_cwire_batch(mi355_core *c, const void *d_frames, size_t st
     return run_batch(c, false, d_frames, nullptr, stride_bytes, nframes, d_offsets, nullptr, nullptr, 0, nullptr, true, &cw);
 }
 
-// mi355_diff_multi_*: what the three forms refuse alike, before anything is launched
-static int check_multi(mi355_core *c, const void *d_frames, const void *d_states, size_t stride, int nstreams) {
-    if (!c) return fail(MI355_ERR_INVALID, "null core");
-    if (nstreams < 0 || nstreams > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams outside [0, max_batch]");
-    if (nstreams == 0) return MI355_OK;
-    if (!d_frames || !d_states) return fail(MI355_ERR_INVALID, "null d_frames / d_states");
-    if (stride < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
-    const uintptr_t f = (uintptr_t)d_frames, s = (uintptr_t)d_states;
-    const uintptr_t span = (uintptr_t)(nstreams - 1) * stride + c->n;   // bytes from the first frame to the end of the last
-    if (f < s + span && s < f + span) return fail(MI355_ERR_INVALID, "the states overlap the frames");
+// ---- the caller's regions of device memory, for the overlap tests of the entry points below ---------------------------------
+namespace {
+// [p, p + bytes) and its name in an error text
+struct Region {
+    const void *p;
+    uint64_t bytes;
+    const char *what;
+};
+// Plain intervals: an empty region that lies strictly inside another one overlaps it, {nullptr, 0} overlaps nothing (p = 0 and
+// bytes = 0 never satisfy the second comparison).  The calls that let an empty region lie anywhere hand theirs through nowhere().
+bool overlap(const Region &a, const Region &b) {
+    const uintptr_t pa = (uintptr_t)a.p, pb = (uintptr_t)b.p;
+    return pa < pb + (uintptr_t)b.bytes && pb < pa + (uintptr_t)a.bytes;
+}
+int overlap_fail(const Region &a, const Region &b) {
+    char msg[96];
+    snprintf(msg, sizeof msg, "%s and %s overlap", a.what, b.what);
+    return fail(MI355_ERR_INVALID, msg);
+}
+Region nowhere(Region r) {
+    if (r.bytes == 0) r.p = nullptr;
+    return r;
+}
+// count >= 1 windows of the core's frame bytes, stride apart: from the first byte of the first to the end of the last
+Region windows(const mi355_core *c, const void *p, int64_t count, size_t stride, const char *what) {
+    return Region{p, (uint64_t)(count - 1) * stride + c->n, what};
+}
+Region states_region(const mi355_core *c, const void *d_states, size_t stride, int nstreams) {
+    return windows(c, d_states, nstreams, stride, "the states");
+}
+Region out_frames_region(const mi355_core *c, const void *d_out, size_t out_stride, int64_t nframes) {
+    return windows(c, d_out, nframes, out_stride, "the output frames");
+}
+Region input_region(const void *d_in, uint64_t bytes) { return Region{d_in, bytes, "the input stream"}; }
+Region offsets_region(const void *d_offsets, int nstreams) { return Region{d_offsets, ((uint64_t)nstreams + 1) * sizeof(uint32_t), "d_offsets"}; }
+Region frame_pos_region(const void *d_frame_pos, int nstreams) {
+    return Region{d_frame_pos, ((uint64_t)nstreams + 1) * sizeof(uint64_t), "d_frame_pos"};
+}
+Region tile_mask_region(const mi355_core *c, const void *d_tile_mask, int nstreams) {
+    return Region{d_tile_mask, 4 * (uint64_t)nstreams * cwa_mask_words(c->n), "d_tile_mask"};
+}
+// Refuses an output that overlaps an input, output by output in their order; among_outputs: and one that overlaps a later output
+int check_regions(std::initializer_list<Region> in, std::initializer_list<Region> out, bool among_outputs = false) {
+    for (const Region *o = out.begin(); o != out.end(); o++) {
+        for (const Region &i : in)
+            if (overlap(*o, i)) return overlap_fail(*o, i);
+        for (const Region *later = o + 1; among_outputs && later != out.end(); later++)
+            if (overlap(*o, *later)) return overlap_fail(*o, *later);
+    }
     return MI355_OK;
 }
+}  // namespace
 
-int mi355_diff_multi_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
-                           void *d_offsets, void *d_xs, void *d_diff, size_t capacity) {
-    if (int rc = check_multi(c, d_frames, d_states, stride_bytes, nstreams)) return rc;
-    return run_batch(c, true, d_frames, d_states, stride_bytes, nstreams, d_offsets, d_xs, d_diff, capacity, nullptr, true,
-                     nullptr, true);
-}
-
-int mi355_diff_multi_wire_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
-                                void *d_offsets, void *d_wire, size_t capacity_bytes) {
-    if (int rc = check_multi(c, d_frames, d_states, stride_bytes, nstreams)) return rc;
-    if (!d_wire) return fail(MI355_ERR_INVALID, "null d_wire");
-    return run_batch(c, true, d_frames, d_states, stride_bytes, nstreams, d_offsets, nullptr, nullptr, capacity_bytes,
-                     d_wire, true, nullptr, true);
-}
-
-int mi355_diff_multi_cwire_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
-                                 void *d_offsets, void *d_frame_pos, void *d_cwire, size_t capacity_bytes) {
-    if (int rc = check_multi(c, d_frames, d_states, stride_bytes, nstreams)) return rc;
-    if (!d_offsets || !d_frame_pos) return fail(MI355_ERR_INVALID, "null d_offsets / d_frame_pos");
-    if (capacity_bytes > 0 && !d_cwire) return fail(MI355_ERR_INVALID, "null d_cwire");
-    if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_frame_pos & 7u))
-        return fail(MI355_ERR_INVALID, "d_cwire and d_offsets must be 4-byte aligned, d_frame_pos 8-byte aligned");
-    const CwireOut cw{(uint64_t *)d_frame_pos, (uint8_t *)d_cwire, (uint64_t)capacity_bytes};
-    return run_batch(c, true, d_frames, d_states, stride_bytes, nstreams, d_offsets, nullptr, nullptr, 0, nullptr, true, &cw,
-                     true);
-}
-
-// mi355_diff_multi_stream_*: what the three forms refuse alike, before anything is launched
+// mi355_diff_multi(_stream)_*: what the six forms refuse alike, before anything is launched (mi355_diff_multi_*: nframes = 1)
 static int check_multi_stream(mi355_core *c, const void *d_frames, const void *d_states, size_t stride, int nstreams, int nframes) {
     if (!c) return fail(MI355_ERR_INVALID, "null core");
     if (nstreams < 0 || nframes < 0) return fail(MI355_ERR_INVALID, "negative nstreams / nframes");
@@ -919,10 +933,37 @@ static int check_multi_stream(mi355_core *c, const void *d_frames, const void *d
     if (nstreams == 0 || nframes == 0) return MI355_OK;
     if (!d_frames || !d_states) return fail(MI355_ERR_INVALID, "null d_frames / d_states");
     if (stride < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
-    const uintptr_t f = (uintptr_t)d_frames, s = (uintptr_t)d_states;
-    const uintptr_t fspan = (uintptr_t)((int64_t)nstreams * nframes - 1) * stride + c->n, sspan = (uintptr_t)(nstreams - 1) * stride + c->n;
-    if (f < s + sspan && s < f + fspan) return fail(MI355_ERR_INVALID, "the states overlap the frames");
+    const Region st = states_region(c, d_states, stride, nstreams);
+    const Region fr = windows(c, d_frames, (int64_t)nstreams * nframes, stride, "the frames");
+    if (overlap(st, fr)) return overlap_fail(st, fr);
     return MI355_OK;
+}
+
+int mi355_diff_multi_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
+                           void *d_offsets, void *d_xs, void *d_diff, size_t capacity) {
+    if (int rc = check_multi_stream(c, d_frames, d_states, stride_bytes, nstreams, 1)) return rc;
+    return run_batch(c, true, d_frames, d_states, stride_bytes, nstreams, d_offsets, d_xs, d_diff, capacity, nullptr, true,
+                     nullptr, true);
+}
+
+int mi355_diff_multi_wire_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
+                                void *d_offsets, void *d_wire, size_t capacity_bytes) {
+    if (int rc = check_multi_stream(c, d_frames, d_states, stride_bytes, nstreams, 1)) return rc;
+    if (!d_wire) return fail(MI355_ERR_INVALID, "null d_wire");
+    return run_batch(c, true, d_frames, d_states, stride_bytes, nstreams, d_offsets, nullptr, nullptr, capacity_bytes,
+                     d_wire, true, nullptr, true);
+}
+
+int mi355_diff_multi_cwire_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
+                                 void *d_offsets, void *d_frame_pos, void *d_cwire, size_t capacity_bytes) {
+    if (int rc = check_multi_stream(c, d_frames, d_states, stride_bytes, nstreams, 1)) return rc;
+    if (!d_offsets || !d_frame_pos) return fail(MI355_ERR_INVALID, "null d_offsets / d_frame_pos");
+    if (capacity_bytes > 0 && !d_cwire) return fail(MI355_ERR_INVALID, "null d_cwire");
+    if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_frame_pos & 7u))
+        return fail(MI355_ERR_INVALID, "d_cwire and d_offsets must be 4-byte aligned, d_frame_pos 8-byte aligned");
+    const CwireOut cw{(uint64_t *)d_frame_pos, (uint8_t *)d_cwire, (uint64_t)capacity_bytes};
+    return run_batch(c, true, d_frames, d_states, stride_bytes, nstreams, d_offsets, nullptr, nullptr, 0, nullptr, true, &cw,
+                     true);
 }
 
 int mi355_diff_multi_stream_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
@@ -1056,6 +1097,51 @@ struct CwireHeaders {
     }
 };
 
+// The record table of the GPU clients: the headers checked, then place, header and chunks of every record.  The chunk bases
+// begin again every max_batch records: the scratch of the one-stream client holds one such slice (only mi355_apply_cwire_batch
+// takes more records than that).
+struct CwaTable {
+    std::vector<CwaFrame> fr;
+    uint64_t bytes = 0;   // of all the records
+};
+static int cwa_table(const mi355_core *c, const uint32_t *h_counts, const uint32_t *h_escapes, int nrecords, CwaTable *tab) {
+    CwireHeaders hdr{h_counts, h_escapes, nrecords};
+    if (int rc = hdr.check(true, c->n)) return rc;
+    tab->fr.resize((size_t)nrecords);
+    uint32_t cbase = 0;
+    for (int k = 0; k < nrecords; k++) {
+        if (k % c->cfg.max_batch == 0) cbase = 0;
+        const CwireHeaders::Frame f = hdr.next();
+        tab->fr[k] = CwaFrame{f.pos, f.n, f.e, cbase, cwa_chunks(f.n)};
+        cbase += tab->fr[k].nc;
+    }
+    tab->bytes = hdr.pos;
+    return MI355_OK;
+}
+
+// The core's scratch and frame size for a launch on the records at d_cwire; state / out / stride are the call's own.  Every
+// field is filled for every call: the kernels of mi355_cwire_check_batch never read dir or ntiles, those of
+// mi355_refresh_cwire_batch (d_cwire = nullptr) never read cwire, ftab or dir.
+static CwaArgs cwa_args(const mi355_core *c, const void *d_cwire) {
+    CwaArgs a{};
+    a.cwire = (const uint8_t *)d_cwire;
+    a.ftab = c->cwa_ftab;
+    a.chunk = c->cwa_chunk;   // chunk facts for the directory, then one fact word per (stream, tile) where a call keeps such
+    a.dir = c->cwa_dir;
+    a.n = c->n;
+    a.ntiles = cwa_tiles(c->n);
+    return a;
+}
+
+// offsets[0] = 0 and frame_pos[0] = 0, where given, and nothing else: what an empty batch leaves
+static int write_empty_heads(mi355_core *c, void *d_offsets, void *d_frame_pos) {
+    if (!d_offsets && !d_frame_pos) return MI355_OK;
+    if (int rc = use_device(c)) return rc;
+    if (d_offsets) HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(uint32_t), c->stream));
+    if (d_frame_pos) HIP_TRY(hipMemsetAsync(d_frame_pos, 0, sizeof(uint64_t), c->stream));
+    return MI355_OK;
+}
+
 int mi355_cwire_encode_batch(mi355_core *c, const void *d_offsets, const void *d_xs, const void *d_diff,
                              size_t entries_capacity, int nframes, void *d_frame_pos, void *d_cwire, size_t capacity_bytes) {
     if (!c) return fail(MI355_ERR_INVALID, "null core");
@@ -1113,134 +1199,24 @@ int mi355_apply_cwire_batch(mi355_core *c, const void *d_cwire, const uint32_t *
     if (!d_cwire || !h_counts || !h_escapes) return fail(MI355_ERR_INVALID, "null argument");
     if ((uintptr_t)d_cwire & 3u) return fail(MI355_ERR_INVALID, "d_cwire must be 4-byte aligned");
     if (d_frames_out && stride_bytes < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
-    CwireHeaders hdr{h_counts, h_escapes, nframes};
-    if (int rc = hdr.check(true, c->n)) return rc;
+    CwaTable tab;
+    if (int rc = cwa_table(c, h_counts, h_escapes, nframes, &tab)) return rc;
     if (c->n == 0) return MI355_OK;   // (every count is 0)
     if (int rc = use_device(c)) return rc;
-    CwaArgs a{};
-    a.cwire = (const uint8_t *)d_cwire;
-    a.ftab = c->cwa_ftab;
-    a.chunk = c->cwa_chunk;
-    a.dir = c->cwa_dir;
+    CwaArgs a = cwa_args(c, d_cwire);
     a.state = c->state;
     a.stride = stride_bytes;
-    a.n = c->n;
-    a.ntiles = cwa_tiles(c->n);
     const int T = c->cfg.max_batch;
-    std::vector<CwaFrame> fr((size_t)(nframes < T ? nframes : T));
     for (int t0 = 0; t0 < nframes; t0 += T) {   // slices of at most max_batch frames: the scratch holds one
-        const int nf = nframes - t0 < T ? nframes - t0 : T;
-        uint32_t cbase = 0;
-        for (int k = 0; k < nf; k++) {
-            const CwireHeaders::Frame f = hdr.next();
-            fr[k] = CwaFrame{f.pos, f.n, f.e, cbase, cwa_chunks(f.n)};
-            cbase += fr[k].nc;
-        }
         a.out = d_frames_out ? (uint8_t *)d_frames_out + (size_t)t0 * stride_bytes : nullptr;
-        HIP_TRY(launch_cwire_apply(a, fr.data(), nf, c->stream));
+        HIP_TRY(launch_cwire_apply(a, tab.fr.data() + t0, nframes - t0 < T ? nframes - t0 : T, c->stream));
     }
     return MI355_OK;
 }
 
-// ---- mi355_apply_multi_*: one segment / record of each of nstreams streams onto the caller's states -----------------------
-// What the three forms refuse alike, before anything is launched; *run = there is something to do
-static int check_apply_multi(mi355_core *c, bool inputs, int nstreams, const void *d_states, size_t stride, bool *run) {
-    *run = false;
-    if (!c) return fail(MI355_ERR_INVALID, "null core");
-    if (nstreams < 0 || nstreams > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams outside [0, max_batch]");
-    if (nstreams == 0) return MI355_OK;
-    if (!inputs) return fail(MI355_ERR_INVALID, "null stream pointer");
-    if (!d_states) return fail(MI355_ERR_INVALID, "null d_states");
-    if (stride < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
-    *run = c->n > 0;
-    return MI355_OK;
-}
-
-// An input of `bytes` bytes (known from the host's headers) against the states' region: check_multi's test
-static int check_apply_multi_overlap(const mi355_core *c, const void *d_in, uint64_t bytes, const void *d_states, size_t stride,
-                                     int nstreams) {
-    const uintptr_t in = (uintptr_t)d_in, s = (uintptr_t)d_states;
-    const uintptr_t span = (uintptr_t)(nstreams - 1) * stride + c->n;
-    if (in < s + span && s < in + (uintptr_t)bytes) return fail(MI355_ERR_INVALID, "the states overlap the input stream");
-    return MI355_OK;
-}
-
-int mi355_apply_multi_batch(mi355_core *c, const void *d_offsets, const void *d_xs, const void *d_diff, int nstreams,
-                            void *d_states, size_t stride_bytes) {
-    bool run;
-    if (int rc = check_apply_multi(c, d_offsets && d_xs && d_diff, nstreams, d_states, stride_bytes, &run)) return rc;
-    if (nstreams > 0 && (((uintptr_t)d_offsets | (uintptr_t)d_xs) & 3u))
-        return fail(MI355_ERR_INVALID, "d_offsets and d_xs must be 4-byte aligned");
-    if (!run) return MI355_OK;
-    if (int rc = use_device(c)) return rc;
-    HIP_TRY(launch_apply_multi((uint8_t *)d_states, stride_bytes, c->n, (const uint32_t *)d_offsets, (const int32_t *)d_xs,
-                               (const uint8_t *)d_diff, nstreams, c->stream));
-    return MI355_OK;
-}
-
-int mi355_apply_multi_wire_batch(mi355_core *c, const void *d_wire, const uint32_t *h_counts, int nstreams, void *d_states,
-                                 size_t stride_bytes) {
-    bool run;
-    if (int rc = check_apply_multi(c, d_wire && h_counts, nstreams, d_states, stride_bytes, &run)) return rc;
-    uint64_t entries = 0;
-    for (int s = 0; s < nstreams; s++) {
-        if (h_counts[s] > c->n) return fail(MI355_ERR_INVALID, "frame count larger than the frame");
-        entries += h_counts[s];
-    }
-    if (nstreams > 0)
-        if (int rc = check_apply_multi_overlap(c, d_wire, mi355_wire_bytes(nstreams, entries), d_states, stride_bytes, nstreams))
-            return rc;
-    if (!run) return MI355_OK;
-    if (int rc = use_device(c)) return rc;
-    ApplyMultiWireArgs h{};
-    uint64_t pos = 0;
-    for (int s0 = 0; s0 < nstreams; s0 += kApplyMultiWireStreams) {
-        h.first = s0;
-        h.count = nstreams - s0 < kApplyMultiWireStreams ? nstreams - s0 : kApplyMultiWireStreams;
-        h.cum[0] = 0;
-        for (int j = 0; j < h.count; j++) {
-            h.pos[j] = pos;
-            h.cum[j + 1] = h.cum[j] + h_counts[s0 + j];
-            pos += mi355_wire_bytes(1, h_counts[s0 + j]);
-        }
-        HIP_TRY(launch_apply_multi_wire((uint8_t *)d_states, stride_bytes, c->n, (const uint8_t *)d_wire, h, c->stream));
-    }
-    return MI355_OK;
-}
-
-int mi355_apply_multi_cwire_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
-                                  int nstreams, void *d_states, size_t stride_bytes) {
-    bool run;
-    if (int rc = check_apply_multi(c, d_cwire && h_counts && h_escapes, nstreams, d_states, stride_bytes, &run)) return rc;
-    if (nstreams == 0) return MI355_OK;
-    if ((uintptr_t)d_cwire & 3u) return fail(MI355_ERR_INVALID, "d_cwire must be 4-byte aligned");
-    CwireHeaders hdr{h_counts, h_escapes, nstreams};
-    if (int rc = hdr.check(true, c->n)) return rc;
-    std::vector<CwaFrame> fr((size_t)nstreams);   // nstreams <= max_batch: the scratch of the one-stream client holds them
-    uint32_t cbase = 0;
-    for (int s = 0; s < nstreams; s++) {
-        const CwireHeaders::Frame f = hdr.next();
-        fr[s] = CwaFrame{f.pos, f.n, f.e, cbase, cwa_chunks(f.n)};
-        cbase += fr[s].nc;
-    }
-    if (int rc = check_apply_multi_overlap(c, d_cwire, hdr.pos, d_states, stride_bytes, nstreams)) return rc;
-    if (!run) return MI355_OK;
-    if (int rc = use_device(c)) return rc;
-    CwaArgs a{};
-    a.cwire = (const uint8_t *)d_cwire;
-    a.ftab = c->cwa_ftab;
-    a.chunk = c->cwa_chunk;
-    a.dir = c->cwa_dir;
-    a.state = (uint8_t *)d_states;
-    a.stride = stride_bytes;
-    a.n = c->n;
-    a.ntiles = cwa_tiles(c->n);
-    HIP_TRY(launch_cwire_apply_multi(a, fr.data(), nstreams, c->stream));
-    return MI355_OK;
-}
-
-// ---- mi355_apply_multi_stream_*: nframes segments / records of each of nstreams streams, batch index b = s*nframes + t -------
-// What the three forms refuse alike, before anything is launched; *run = there is something to do
+// ---- mi355_apply_multi(_stream)_*: nframes segments / records of each of nstreams streams onto the caller's states, batch index
+// b = s*nframes + t (mi355_apply_multi_*: nframes = 1, no output frames) ---------------------------------------------------------
+// What the six forms refuse alike, before anything is launched; *run = there is something to do
 static int check_apply_multi_stream(mi355_core *c, bool inputs, int nstreams, int nframes, const void *d_states, size_t stride,
                                     const void *d_out, size_t out_stride, bool *run) {
     *run = false;
@@ -1254,22 +1230,90 @@ static int check_apply_multi_stream(mi355_core *c, bool inputs, int nstreams, in
     if (stride < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
     if (d_out) {
         if (out_stride < c->n) return fail(MI355_ERR_INVALID, "out_stride_bytes < frame bytes");
-        const uintptr_t s = (uintptr_t)d_states, o = (uintptr_t)d_out;
-        const uintptr_t sspan = (uintptr_t)(nstreams - 1) * stride + c->n, ospan = (uintptr_t)(B - 1) * out_stride + c->n;
-        if (s < o + ospan && o < s + sspan) return fail(MI355_ERR_INVALID, "the states overlap the output frames");
+        if (int rc = check_regions({out_frames_region(c, d_out, out_stride, B)}, {states_region(c, d_states, stride, nstreams)})) return rc;
     }
     *run = c->n > 0;
     return MI355_OK;
 }
 
-// An input of `bytes` bytes (known from the host's headers) against the states and the output frames
-static int check_apply_multi_stream_overlap(const mi355_core *c, const void *d_in, uint64_t bytes, int nstreams, int nframes,
-                                            const void *d_states, size_t stride, const void *d_out, size_t out_stride) {
-    if (int rc = check_apply_multi_overlap(c, d_in, bytes, d_states, stride, nstreams)) return rc;
-    if (!d_out) return MI355_OK;
-    const uintptr_t in = (uintptr_t)d_in, o = (uintptr_t)d_out;
-    const uintptr_t ospan = (uintptr_t)((int64_t)nstreams * nframes - 1) * out_stride + c->n;
-    if (in < o + ospan && o < in + (uintptr_t)bytes) return fail(MI355_ERR_INVALID, "the output frames overlap the input stream");
+// An input of `bytes` bytes (known from the host's headers) against the states and, where there are any, the output frames
+static int check_apply_multi_input(const mi355_core *c, const void *d_in, uint64_t bytes, int nstreams, int nframes, const void *d_states,
+                                   size_t stride, const void *d_out, size_t out_stride) {
+    return check_regions({input_region(d_in, bytes)},
+                         {states_region(c, d_states, stride, nstreams),
+                          d_out ? out_frames_region(c, d_out, out_stride, (int64_t)nstreams * nframes) : Region{}});
+}
+
+// One launch's streams [s0, s0 + h->count) of a wire stream, record t of each: batch index b = s*nframes + t, pos[b] its place
+static void fill_apply_multi_wire(ApplyMultiWireArgs *h, int s0, int nstreams, int nframes, int t, const uint64_t *pos,
+                                  const uint32_t *h_counts) {
+    h->first = s0;
+    h->count = nstreams - s0 < kApplyMultiWireStreams ? nstreams - s0 : kApplyMultiWireStreams;
+    h->cum[0] = 0;
+    for (int j = 0; j < h->count; j++) {
+        const size_t b = (size_t)(s0 + j) * nframes + t;
+        h->pos[j] = pos[b];
+        h->cum[j + 1] = h->cum[j] + h_counts[b];
+    }
+}
+
+// pos[b]: byte position of {n, xs, diff} of batch index b of a wire stream, pos[B] its length; refuses a count above the frame
+static int wire_positions(const mi355_core *c, const uint32_t *h_counts, int B, std::vector<uint64_t> *pos) {
+    pos->assign((size_t)B + 1, 0);
+    for (int b = 0; b < B; b++) {
+        if (h_counts[b] > c->n) return fail(MI355_ERR_INVALID, "frame count larger than the frame");
+        (*pos)[b + 1] = (*pos)[b] + mi355_wire_bytes(1, h_counts[b]);
+    }
+    return MI355_OK;
+}
+
+int mi355_apply_multi_batch(mi355_core *c, const void *d_offsets, const void *d_xs, const void *d_diff, int nstreams,
+                            void *d_states, size_t stride_bytes) {
+    bool run;
+    if (int rc = check_apply_multi_stream(c, d_offsets && d_xs && d_diff, nstreams, 1, d_states, stride_bytes, nullptr, 0, &run)) return rc;
+    if (nstreams > 0 && (((uintptr_t)d_offsets | (uintptr_t)d_xs) & 3u))
+        return fail(MI355_ERR_INVALID, "d_offsets and d_xs must be 4-byte aligned");
+    if (!run) return MI355_OK;
+    if (int rc = use_device(c)) return rc;
+    HIP_TRY(launch_apply_multi((uint8_t *)d_states, stride_bytes, c->n, (const uint32_t *)d_offsets, (const int32_t *)d_xs,
+                               (const uint8_t *)d_diff, nstreams, c->stream));
+    return MI355_OK;
+}
+
+int mi355_apply_multi_wire_batch(mi355_core *c, const void *d_wire, const uint32_t *h_counts, int nstreams, void *d_states,
+                                 size_t stride_bytes) {
+    bool run;
+    if (int rc = check_apply_multi_stream(c, d_wire && h_counts, nstreams, 1, d_states, stride_bytes, nullptr, 0, &run)) return rc;
+    if (nstreams == 0) return MI355_OK;
+    std::vector<uint64_t> pos;
+    if (int rc = wire_positions(c, h_counts, nstreams, &pos)) return rc;
+    if (int rc = check_apply_multi_input(c, d_wire, pos[nstreams], nstreams, 1, d_states, stride_bytes, nullptr, 0)) return rc;
+    if (!run) return MI355_OK;
+    if (int rc = use_device(c)) return rc;
+    ApplyMultiWireArgs h{};
+    for (int s0 = 0; s0 < nstreams; s0 += kApplyMultiWireStreams) {
+        fill_apply_multi_wire(&h, s0, nstreams, 1, 0, pos.data(), h_counts);
+        HIP_TRY(launch_apply_multi_wire((uint8_t *)d_states, stride_bytes, c->n, (const uint8_t *)d_wire, h, c->stream));
+    }
+    return MI355_OK;
+}
+
+int mi355_apply_multi_cwire_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
+                                  int nstreams, void *d_states, size_t stride_bytes) {
+    bool run;
+    if (int rc = check_apply_multi_stream(c, d_cwire && h_counts && h_escapes, nstreams, 1, d_states, stride_bytes, nullptr, 0, &run))
+        return rc;
+    if (nstreams == 0) return MI355_OK;
+    if ((uintptr_t)d_cwire & 3u) return fail(MI355_ERR_INVALID, "d_cwire must be 4-byte aligned");
+    CwaTable tab;
+    if (int rc = cwa_table(c, h_counts, h_escapes, nstreams, &tab)) return rc;
+    if (int rc = check_apply_multi_input(c, d_cwire, tab.bytes, nstreams, 1, d_states, stride_bytes, nullptr, 0)) return rc;
+    if (!run) return MI355_OK;
+    if (int rc = use_device(c)) return rc;
+    CwaArgs a = cwa_args(c, d_cwire);
+    a.state = (uint8_t *)d_states;
+    a.stride = stride_bytes;
+    HIP_TRY(launch_cwire_apply_multi(a, tab.fr.data(), nstreams, c->stream));
     return MI355_OK;
 }
 
@@ -1301,28 +1345,16 @@ int mi355_apply_multi_stream_wire_batch(mi355_core *c, const void *d_wire, const
         return rc;
     const int B = nstreams > 0 && nframes > 0 ? nstreams * nframes : 0;   // (<= max_batch)
     if (B == 0) return MI355_OK;
-    std::vector<uint64_t> pos((size_t)B + 1);   // pos[b]: byte position of {n, xs, diff} of batch index b
-    pos[0] = 0;
-    for (int b = 0; b < B; b++) {
-        if (h_counts[b] > c->n) return fail(MI355_ERR_INVALID, "frame count larger than the frame");
-        pos[b + 1] = pos[b] + mi355_wire_bytes(1, h_counts[b]);
-    }
-    if (int rc = check_apply_multi_stream_overlap(c, d_wire, pos[B], nstreams, nframes, d_states, stride_bytes, d_frames_out,
-                                                  out_stride_bytes))
+    std::vector<uint64_t> pos;
+    if (int rc = wire_positions(c, h_counts, B, &pos)) return rc;
+    if (int rc = check_apply_multi_input(c, d_wire, pos[B], nstreams, nframes, d_states, stride_bytes, d_frames_out, out_stride_bytes))
         return rc;
     if (!run) return MI355_OK;
     if (int rc = use_device(c)) return rc;
     ApplyMultiWireArgs h{};
     for (int t = 0; t < nframes; t++) {   // launch t: record s*nframes + t of every stream s, 128 streams per launch
         for (int s0 = 0; s0 < nstreams; s0 += kApplyMultiWireStreams) {
-            h.first = s0;
-            h.count = nstreams - s0 < kApplyMultiWireStreams ? nstreams - s0 : kApplyMultiWireStreams;
-            h.cum[0] = 0;
-            for (int j = 0; j < h.count; j++) {
-                const size_t b = (size_t)(s0 + j) * nframes + t;
-                h.pos[j] = pos[b];
-                h.cum[j + 1] = h.cum[j] + h_counts[b];
-            }
+            fill_apply_multi_wire(&h, s0, nstreams, nframes, t, pos.data(), h_counts);
             HIP_TRY(launch_apply_multi_wire((uint8_t *)d_states, stride_bytes, c->n, (const uint8_t *)d_wire, h, c->stream));
         }
         if (d_frames_out)
@@ -1342,44 +1374,22 @@ int mi355_apply_multi_stream_cwire_batch(mi355_core *c, const void *d_cwire, con
     const int B = nstreams > 0 && nframes > 0 ? nstreams * nframes : 0;   // (<= max_batch)
     if (B == 0) return MI355_OK;
     if ((uintptr_t)d_cwire & 3u) return fail(MI355_ERR_INVALID, "d_cwire must be 4-byte aligned");
-    CwireHeaders hdr{h_counts, h_escapes, B};
-    if (int rc = hdr.check(true, c->n)) return rc;
-    std::vector<CwaFrame> fr((size_t)B);   // B <= max_batch: the scratch of the one-stream client holds them
-    uint32_t cbase = 0;
-    for (int b = 0; b < B; b++) {
-        const CwireHeaders::Frame f = hdr.next();
-        fr[b] = CwaFrame{f.pos, f.n, f.e, cbase, cwa_chunks(f.n)};
-        cbase += fr[b].nc;
-    }
-    if (int rc = check_apply_multi_stream_overlap(c, d_cwire, hdr.pos, nstreams, nframes, d_states, stride_bytes, d_frames_out,
-                                                  out_stride_bytes))
+    CwaTable tab;
+    if (int rc = cwa_table(c, h_counts, h_escapes, B, &tab)) return rc;
+    if (int rc = check_apply_multi_input(c, d_cwire, tab.bytes, nstreams, nframes, d_states, stride_bytes, d_frames_out, out_stride_bytes))
         return rc;
     if (!run) return MI355_OK;
     if (int rc = use_device(c)) return rc;
-    CwaArgs a{};
-    a.cwire = (const uint8_t *)d_cwire;
-    a.ftab = c->cwa_ftab;
-    a.chunk = c->cwa_chunk;
-    a.dir = c->cwa_dir;
+    CwaArgs a = cwa_args(c, d_cwire);
     a.state = (uint8_t *)d_states;
     a.out = (uint8_t *)d_frames_out;
     a.stride = stride_bytes;
-    a.n = c->n;
-    a.ntiles = cwa_tiles(c->n);
-    HIP_TRY(launch_cwire_apply_multi_stream(a, fr.data(), nstreams, nframes, out_stride_bytes, c->stream));
+    HIP_TRY(launch_cwire_apply_multi_stream(a, tab.fr.data(), nstreams, nframes, out_stride_bytes, c->stream));
     return MI355_OK;
 }
 
 // ---- mi355_cwire_coalesce_(cwire_)batch: nframes records of each of nstreams streams -> ONE segment / record per stream -------
 // Both forms: everything is refused here, before anything is launched; the core's state is not touched.
-namespace {
-struct CoalesceRegion {
-    const void *p;
-    uint64_t bytes;
-    const char *what;
-};
-}  // namespace
-
 static int coalesce(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams,
                     int nframes, bool cwire, void *d_offsets, void *d_frame_pos, void *d_cwire_out, void *d_xs, void *d_diff,
                     size_t capacity) {
@@ -1391,44 +1401,19 @@ static int coalesce(mi355_core *c, const void *d_cwire, const uint32_t *h_counts
     if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_cwire_out & 3u) || ((uintptr_t)d_xs & 3u))
         return fail(MI355_ERR_INVALID, "d_cwire, d_cwire_out, d_offsets and d_xs must be 4-byte aligned");
     if ((uintptr_t)d_frame_pos & 7u) return fail(MI355_ERR_INVALID, "d_frame_pos must be 8-byte aligned");
-    if (B == 0) {   // offsets[0] = 0 (and frame_pos[0] = 0) and nothing else
-        if (!d_offsets && !d_frame_pos) return MI355_OK;
-        if (int rc = use_device(c)) return rc;
-        if (d_offsets) HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(uint32_t), c->stream));
-        if (d_frame_pos) HIP_TRY(hipMemsetAsync(d_frame_pos, 0, sizeof(uint64_t), c->stream));
-        return MI355_OK;
-    }
+    if (B == 0) return write_empty_heads(c, d_offsets, d_frame_pos);
     if (!d_cwire || !h_counts || !h_escapes) return fail(MI355_ERR_INVALID, "null stream pointer");
     if (!d_offsets || (cwire ? !d_frame_pos || !d_cwire_out : !d_xs || !d_diff)) return fail(MI355_ERR_INVALID, "null output pointer");
-    CwireHeaders hdr{h_counts, h_escapes, B};
-    if (int rc = hdr.check(true, c->n)) return rc;
-    std::vector<CwaFrame> fr((size_t)B);   // B <= max_batch: the scratch of the one-stream client holds them
-    uint32_t cbase = 0;
-    for (int b = 0; b < B; b++) {
-        const CwireHeaders::Frame f = hdr.next();
-        fr[b] = CwaFrame{f.pos, f.n, f.e, cbase, cwa_chunks(f.n)};
-        cbase += fr[b].nc;
-    }
-    const CoalesceRegion out[] = {
-        {d_offsets, ((uint64_t)nstreams + 1) * sizeof(uint32_t), "d_offsets overlaps the input stream"},
-        {cwire ? d_frame_pos : nullptr, ((uint64_t)nstreams + 1) * sizeof(uint64_t), "d_frame_pos overlaps the input stream"},
-        {cwire ? d_cwire_out : nullptr, capacity, "d_cwire_out overlaps the input stream"},
-        {cwire ? nullptr : d_xs, 4 * (uint64_t)capacity, "d_xs overlaps the input stream"},
-        {cwire ? nullptr : d_diff, capacity, "d_diff overlaps the input stream"},
-    };
-    const uintptr_t in = (uintptr_t)d_cwire;
-    for (const CoalesceRegion &r : out) {
-        const uintptr_t o = (uintptr_t)r.p;
-        if (r.p && in < o + (uintptr_t)r.bytes && o < in + (uintptr_t)hdr.pos) return fail(MI355_ERR_INVALID, r.what);
-    }
+    CwaTable tab;
+    if (int rc = cwa_table(c, h_counts, h_escapes, B, &tab)) return rc;
+    if (int rc = check_regions({input_region(d_cwire, tab.bytes)},   // (the outputs of the other form: nowhere)
+                               {offsets_region(d_offsets, nstreams), cwire ? frame_pos_region(d_frame_pos, nstreams) : Region{},
+                                cwire ? Region{d_cwire_out, capacity, "d_cwire_out"} : Region{},
+                                cwire ? Region{} : Region{d_xs, 4 * (uint64_t)capacity, "d_xs"},
+                                cwire ? Region{} : Region{d_diff, capacity, "d_diff"}}))
+        return rc;
     if (int rc = use_device(c)) return rc;
-    CwaArgs a{};
-    a.cwire = (const uint8_t *)d_cwire;
-    a.ftab = c->cwa_ftab;
-    a.chunk = c->cwa_chunk;   // chunk facts for the directory, then one fact word per (stream, tile): nstreams <= max_batch
-    a.dir = c->cwa_dir;
-    a.n = c->n;
-    a.ntiles = cwa_tiles(c->n);
+    const CwaArgs a = cwa_args(c, d_cwire);
     CwcOut o{};
     o.offsets = (uint32_t *)d_offsets;
     o.frame_pos = (uint64_t *)d_frame_pos;
@@ -1436,7 +1421,7 @@ static int coalesce(mi355_core *c, const void *d_cwire, const uint32_t *h_counts
     o.xs = (int32_t *)d_xs;
     o.diff = (uint8_t *)d_diff;
     o.capacity = capacity;
-    HIP_TRY(launch_cwire_coalesce(a, fr.data(), nstreams, nframes, o, cwire, c->stream));
+    HIP_TRY(launch_cwire_coalesce(a, tab.fr.data(), nstreams, nframes, o, cwire, c->stream));
     return MI355_OK;
 }
 
@@ -1474,62 +1459,27 @@ int mi355_cwire_budget_cwire_batch(mi355_core *c, const void *d_cwire, const uin
     if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_cwire_out & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_thresholds & 3u))
         return fail(MI355_ERR_INVALID, "d_cwire, d_cwire_out, d_offsets and d_thresholds must be 4-byte aligned");
     if ((uintptr_t)d_frame_pos & 7u) return fail(MI355_ERR_INVALID, "d_frame_pos must be 8-byte aligned");
-    if (nstreams == 0) {   // offsets[0] = 0 and frame_pos[0] = 0 and nothing else
-        if (!d_offsets && !d_frame_pos) return MI355_OK;
-        if (int rc = use_device(c)) return rc;
-        if (d_offsets) HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(uint32_t), c->stream));
-        if (d_frame_pos) HIP_TRY(hipMemsetAsync(d_frame_pos, 0, sizeof(uint64_t), c->stream));
-        return MI355_OK;
-    }
+    if (nstreams == 0) return write_empty_heads(c, d_offsets, d_frame_pos);
     if (!d_cwire || !h_counts || !h_escapes || !d_states || !h_budget) return fail(MI355_ERR_INVALID, "null input pointer");
     if (!d_thresholds || !d_offsets || !d_frame_pos || !d_cwire_out) return fail(MI355_ERR_INVALID, "null output pointer");
     if (stride_bytes < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
-    CwireHeaders hdr{h_counts, h_escapes, nstreams};
-    if (int rc = hdr.check(true, c->n)) return rc;
-    std::vector<CwaFrame> fr((size_t)nstreams);   // nstreams <= max_batch: the scratch of the one-stream client holds them
-    uint32_t cbase = 0;
-    for (int s = 0; s < nstreams; s++) {
-        const CwireHeaders::Frame f = hdr.next();
-        fr[s] = CwaFrame{f.pos, f.n, f.e, cbase, cwa_chunks(f.n)};
-        cbase += fr[s].nc;
-    }
-    const CoalesceRegion out[] = {
-        {d_offsets, ((uint64_t)nstreams + 1) * sizeof(uint32_t), "d_offsets"},
-        {d_thresholds, (uint64_t)nstreams * sizeof(uint32_t), "d_thresholds"},
-        {d_frame_pos, ((uint64_t)nstreams + 1) * sizeof(uint64_t), "d_frame_pos"},
-        {d_cwire_out, capacity_bytes, "d_cwire_out"},
-    };
-    const uintptr_t in = (uintptr_t)d_cwire, st = (uintptr_t)d_states;
-    const uintptr_t span = (uintptr_t)(nstreams - 1) * stride_bytes + c->n;
-    if (in < st + span && st < in + (uintptr_t)hdr.pos) return fail(MI355_ERR_INVALID, "the states overlap the input stream");
-    for (const CoalesceRegion &r : out) {
-        const uintptr_t o = (uintptr_t)r.p;
-        char msg[96];
-        if (in < o + (uintptr_t)r.bytes && o < in + (uintptr_t)hdr.pos) {
-            snprintf(msg, sizeof msg, "%s overlaps the input stream", r.what);
-            return fail(MI355_ERR_INVALID, msg);
-        }
-        if (st < o + (uintptr_t)r.bytes && o < st + span) {
-            snprintf(msg, sizeof msg, "%s overlaps the states", r.what);
-            return fail(MI355_ERR_INVALID, msg);
-        }
-    }
+    CwaTable tab;
+    if (int rc = cwa_table(c, h_counts, h_escapes, nstreams, &tab)) return rc;
+    const Region in = input_region(d_cwire, tab.bytes), st = states_region(c, d_states, stride_bytes, nstreams);
+    if (overlap(st, in)) return overlap_fail(st, in);
+    if (int rc = check_regions({in, st}, {offsets_region(d_offsets, nstreams), Region{d_thresholds, (uint64_t)nstreams * sizeof(uint32_t), "d_thresholds"},
+                                          frame_pos_region(d_frame_pos, nstreams), Region{d_cwire_out, capacity_bytes, "d_cwire_out"}}))
+        return rc;
     if (int rc = use_device(c)) return rc;
-    CwaArgs a{};
-    a.cwire = (const uint8_t *)d_cwire;
-    a.ftab = c->cwa_ftab;
-    a.chunk = c->cwa_chunk;   // chunk facts for the directory, then one fact word per (stream, tile)
-    a.dir = c->cwa_dir;
+    CwaArgs a = cwa_args(c, d_cwire);
     a.state = (uint8_t *)d_states;
     a.stride = stride_bytes;
-    a.n = c->n;
-    a.ntiles = cwa_tiles(c->n);
     CwcOut o{};
     o.offsets = (uint32_t *)d_offsets;
     o.frame_pos = (uint64_t *)d_frame_pos;
     o.cwire = (uint8_t *)d_cwire_out;
     o.capacity = capacity_bytes;
-    HIP_TRY(launch_cwire_budget(a, fr.data(), nstreams, h_budget, (uint32_t)c->cfg.threshold, c->cwb_hist, (uint32_t *)d_thresholds, o,
+    HIP_TRY(launch_cwire_budget(a, tab.fr.data(), nstreams, h_budget, (uint32_t)c->cfg.threshold, c->cwb_hist, (uint32_t *)d_thresholds, o,
                                 c->stream));
     return MI355_OK;
 }
@@ -1591,33 +1541,14 @@ int mi355_cwire_activity_batch(mi355_core *c, const void *d_cwire, const uint32_
                                 d_summary, &B, &g))
         return rc;
     if (B == 0) return MI355_OK;
-    CwireHeaders hdr{h_counts, h_escapes, B};
-    if (int rc = hdr.check(true, c->n)) return rc;
-    std::vector<CwaFrame> fr((size_t)B);   // B <= max_batch: the scratch of the one-stream client holds them
-    uint32_t cbase = 0;
-    for (int b = 0; b < B; b++) {
-        const CwireHeaders::Frame f = hdr.next();
-        fr[b] = CwaFrame{f.pos, f.n, f.e, cbase, cwa_chunks(f.n)};
-        cbase += fr[b].nc;
-    }
-    const CoalesceRegion out[] = {
-        {d_cells, 4 * (uint64_t)nstreams * g.cells, "d_cells overlaps the input stream"},
-        {d_summary, 32 * (uint64_t)nstreams, "d_summary overlaps the input stream"},
-    };
-    const uintptr_t in = (uintptr_t)d_cwire;
-    for (const CoalesceRegion &r : out) {
-        const uintptr_t o = (uintptr_t)r.p;
-        if (in < o + (uintptr_t)r.bytes && o < in + (uintptr_t)hdr.pos) return fail(MI355_ERR_INVALID, r.what);
-    }
+    CwaTable tab;
+    if (int rc = cwa_table(c, h_counts, h_escapes, B, &tab)) return rc;
+    if (int rc = check_regions({input_region(d_cwire, tab.bytes)}, {Region{d_cells, 4 * (uint64_t)nstreams * g.cells, "d_cells"},
+                                                                    Region{d_summary, 32 * (uint64_t)nstreams, "d_summary"}}))
+        return rc;
     if (int rc = use_device(c)) return rc;
-    CwaArgs a{};
-    a.cwire = (const uint8_t *)d_cwire;
-    a.ftab = c->cwa_ftab;
-    a.chunk = c->cwa_chunk;
-    a.dir = c->cwa_dir;
-    a.n = c->n;
-    a.ntiles = cwa_tiles(c->n);
-    HIP_TRY(launch_cwire_activity(a, fr.data(), nstreams, nframes, g, accumulate != 0, (uint32_t *)d_cells, (uint32_t *)d_summary, c->stream));
+    const CwaArgs a = cwa_args(c, d_cwire);
+    HIP_TRY(launch_cwire_activity(a, tab.fr.data(), nstreams, nframes, g, accumulate != 0, (uint32_t *)d_cells, (uint32_t *)d_summary, c->stream));
     return MI355_OK;
 }
 
@@ -1742,25 +1673,12 @@ int mi355_cwire_check_batch(mi355_core *c, const void *d_cwire, const uint32_t *
     if (nrecords == 0) return MI355_OK;
     if (!d_cwire || !h_counts || !h_escapes || !d_verdicts) return fail(MI355_ERR_INVALID, "null argument");
     if (((uintptr_t)d_cwire | (uintptr_t)d_verdicts) & 3u) return fail(MI355_ERR_INVALID, "d_cwire and d_verdicts must be 4-byte aligned");
-    CwireHeaders hdr{h_counts, h_escapes, nrecords};
-    if (int rc = hdr.check(true, c->n)) return rc;
-    std::vector<CwaFrame> fr((size_t)nrecords);   // nrecords <= max_batch: the scratch of the one-stream client holds them
-    uint32_t cbase = 0;
-    for (int b = 0; b < nrecords; b++) {
-        const CwireHeaders::Frame f = hdr.next();
-        fr[b] = CwaFrame{f.pos, f.n, f.e, cbase, cwa_chunks(f.n)};
-        cbase += fr[b].nc;
-    }
-    const uintptr_t in = (uintptr_t)d_cwire, o = (uintptr_t)d_verdicts;
-    if (in < o + 16 * (uintptr_t)nrecords && o < in + (uintptr_t)hdr.pos)
-        return fail(MI355_ERR_INVALID, "d_verdicts overlaps the input stream");
+    CwaTable tab;
+    if (int rc = cwa_table(c, h_counts, h_escapes, nrecords, &tab)) return rc;
+    if (int rc = check_regions({input_region(d_cwire, tab.bytes)}, {Region{d_verdicts, 16 * (uint64_t)nrecords, "d_verdicts"}})) return rc;
     if (int rc = use_device(c)) return rc;
-    CwaArgs a{};
-    a.cwire = (const uint8_t *)d_cwire;
-    a.ftab = c->cwa_ftab;
-    a.chunk = c->cwa_chunk;
-    a.n = c->n;
-    HIP_TRY(launch_cwire_check(a, fr.data(), nrecords, (uint32_t *)d_verdicts, c->stream));
+    const CwaArgs a = cwa_args(c, d_cwire);
+    HIP_TRY(launch_cwire_check(a, tab.fr.data(), nrecords, (uint32_t *)d_verdicts, c->stream));
     return MI355_OK;
 }
 
@@ -1792,26 +1710,11 @@ int mi355_state_digest_host(const uint8_t *state, size_t frame_bytes, uint32_t *
     return MI355_OK;
 }
 
-namespace {
-// [p, p + bytes) of a resync call, for its overlap tests; an empty region overlaps nothing
-struct ResyncRegion {
-    const void *p;
-    uint64_t bytes;
-    const char *what;
-};
-bool resync_overlap(const ResyncRegion &a, const ResyncRegion &b) {
-    const uintptr_t pa = (uintptr_t)a.p, pb = (uintptr_t)b.p;
-    return a.bytes && b.bytes && pa < pb + (uintptr_t)b.bytes && pb < pa + (uintptr_t)a.bytes;
+// In these calls and in the wall's an empty region overlaps nothing, wherever it lies: every region goes through nowhere().
+// The states of zero-byte frames are empty whatever the stride.
+static Region resync_states(const mi355_core *c, const void *d_states, size_t stride, int nstreams) {
+    return c->n ? states_region(c, d_states, stride, nstreams) : Region{nullptr, 0, "the states"};
 }
-int resync_overlap_fail(const ResyncRegion &a, const ResyncRegion &b) {
-    char msg[96];
-    snprintf(msg, sizeof msg, "%s overlaps %s", a.what, b.what);
-    return fail(MI355_ERR_INVALID, msg);
-}
-ResyncRegion resync_states(const mi355_core *c, const void *d_states, size_t stride, int nstreams) {
-    return ResyncRegion{d_states, c->n ? (uint64_t)(nstreams - 1) * stride + c->n : 0, "the states"};
-}
-}  // namespace
 
 int mi355_state_digest_batch(mi355_core *c, const void *d_states, size_t stride_bytes, int nstreams, void *d_digests) {
     if (!c) return fail(MI355_ERR_INVALID, "null core");
@@ -1820,9 +1723,9 @@ int mi355_state_digest_batch(mi355_core *c, const void *d_states, size_t stride_
     if (!d_states || !d_digests) return fail(MI355_ERR_INVALID, "null argument");
     if (stride_bytes < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
     if ((uintptr_t)d_digests & 3u) return fail(MI355_ERR_INVALID, "d_digests must be 4-byte aligned");
-    const ResyncRegion st = resync_states(c, d_states, stride_bytes, nstreams);
-    const ResyncRegion dg{d_digests, 8 * (uint64_t)nstreams * cwa_tiles(c->n), "d_digests"};
-    if (resync_overlap(dg, st)) return resync_overlap_fail(dg, st);
+    if (int rc = check_regions({resync_states(c, d_states, stride_bytes, nstreams)},
+                               {nowhere(Region{d_digests, 8 * (uint64_t)nstreams * cwa_tiles(c->n), "d_digests"})}))
+        return rc;
     if (int rc = use_device(c)) return rc;
     HIP_TRY(launch_state_digest((const uint8_t *)d_states, stride_bytes, c->n, nstreams, (uint32_t *)d_digests, c->stream));
     return MI355_OK;
@@ -1835,40 +1738,20 @@ int mi355_refresh_cwire_batch(mi355_core *c, const void *d_states, size_t stride
     if (((uintptr_t)d_peer_digests & 3u) || ((uintptr_t)d_tile_mask & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_cwire_out & 3u))
         return fail(MI355_ERR_INVALID, "d_peer_digests, d_tile_mask, d_offsets and d_cwire_out must be 4-byte aligned");
     if ((uintptr_t)d_frame_pos & 7u) return fail(MI355_ERR_INVALID, "d_frame_pos must be 8-byte aligned");
-    if (nstreams == 0) {   // offsets[0] = 0 and frame_pos[0] = 0 and nothing else
-        if (!d_offsets && !d_frame_pos) return MI355_OK;
-        if (int rc = use_device(c)) return rc;
-        if (d_offsets) HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(uint32_t), c->stream));
-        if (d_frame_pos) HIP_TRY(hipMemsetAsync(d_frame_pos, 0, sizeof(uint64_t), c->stream));
-        return MI355_OK;
-    }
+    if (nstreams == 0) return write_empty_heads(c, d_offsets, d_frame_pos);
     if (!d_states) return fail(MI355_ERR_INVALID, "null d_states");
     if (!d_tile_mask || !d_offsets || !d_frame_pos || !d_cwire_out) return fail(MI355_ERR_INVALID, "null output pointer");
     if (stride_bytes < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
-    const uint32_t ntiles = cwa_tiles(c->n);
-    const ResyncRegion in[] = {
-        resync_states(c, d_states, stride_bytes, nstreams),
-        {d_peer_digests, d_peer_digests ? 8 * (uint64_t)nstreams * ntiles : 0, "the peer digests"},
-    };
-    const ResyncRegion out[] = {
-        {d_tile_mask, 4 * (uint64_t)nstreams * ((ntiles + 31u) / 32u), "d_tile_mask"},
-        {d_offsets, ((uint64_t)nstreams + 1) * sizeof(uint32_t), "d_offsets"},
-        {d_frame_pos, ((uint64_t)nstreams + 1) * sizeof(uint64_t), "d_frame_pos"},
-        {d_cwire_out, capacity_bytes, "d_cwire_out"},
-    };
-    for (size_t i = 0; i < sizeof out / sizeof out[0]; i++) {
-        for (const ResyncRegion &r : in)
-            if (resync_overlap(out[i], r)) return resync_overlap_fail(out[i], r);
-        for (size_t j = i + 1; j < sizeof out / sizeof out[0]; j++)
-            if (resync_overlap(out[i], out[j])) return resync_overlap_fail(out[i], out[j]);
-    }
+    if (int rc = check_regions({resync_states(c, d_states, stride_bytes, nstreams),
+                                d_peer_digests ? nowhere(Region{d_peer_digests, 8 * (uint64_t)nstreams * cwa_tiles(c->n), "the peer digests"}) : Region{}},
+                               {nowhere(tile_mask_region(c, d_tile_mask, nstreams)), offsets_region(d_offsets, nstreams),
+                                frame_pos_region(d_frame_pos, nstreams), nowhere(Region{d_cwire_out, capacity_bytes, "d_cwire_out"})},
+                               true))
+        return rc;
     if (int rc = use_device(c)) return rc;
-    CwaArgs a{};
-    a.chunk = c->cwa_chunk;   // one fact word per (stream, tile): nstreams <= max_batch
-    a.state = (uint8_t *)d_states;   // (only read)
+    CwaArgs a = cwa_args(c, nullptr);   // (chunk: one fact word per (stream, tile), nstreams <= max_batch)
+    a.state = (uint8_t *)d_states;      // (only read)
     a.stride = stride_bytes;
-    a.n = c->n;
-    a.ntiles = ntiles;
     CwcOut o{};
     o.offsets = (uint32_t *)d_offsets;
     o.frame_pos = (uint64_t *)d_frame_pos;
@@ -1885,9 +1768,8 @@ int mi355_state_clear_tiles_batch(mi355_core *c, void *d_states, size_t stride_b
     if (!d_states || !d_tile_mask) return fail(MI355_ERR_INVALID, "null argument");
     if (stride_bytes < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
     if ((uintptr_t)d_tile_mask & 3u) return fail(MI355_ERR_INVALID, "d_tile_mask must be 4-byte aligned");
-    const ResyncRegion st = resync_states(c, d_states, stride_bytes, nstreams);
-    const ResyncRegion mk{d_tile_mask, 4 * (uint64_t)nstreams * ((cwa_tiles(c->n) + 31u) / 32u), "d_tile_mask"};
-    if (resync_overlap(mk, st)) return resync_overlap_fail(mk, st);
+    if (int rc = check_regions({resync_states(c, d_states, stride_bytes, nstreams)}, {nowhere(tile_mask_region(c, d_tile_mask, nstreams))}))
+        return rc;
     if (int rc = use_device(c)) return rc;
     HIP_TRY(launch_state_clear_tiles((uint8_t *)d_states, stride_bytes, c->n, nstreams, (const uint32_t *)d_tile_mask, c->stream));
     return MI355_OK;
@@ -1921,12 +1803,12 @@ int mi355_wall_compose_batch(mi355_core *c, const void *d_states, size_t stride_
         if (x < 0 || y < 0 || (int64_t)x + tw > wall_w || (int64_t)y + th > wall_h)
             return fail(MI355_ERR_INVALID, "h_place: a thumbnail does not lie inside the wall");
     }
-    const ResyncRegion st = resync_states(c, d_states, stride_bytes, nstreams);
-    const ResyncRegion wl{d_wall, (uint64_t)(wall_h - 1) * wall_pitch + 3 * (uint64_t)wall_w, "the wall"};
-    const ResyncRegion mk{d_tile_mask, d_tile_mask ? 4 * (uint64_t)nstreams * ((cwa_tiles(c->n) + 31u) / 32u) : 0, "d_tile_mask"};
-    if (resync_overlap(wl, st)) return resync_overlap_fail(wl, st);
-    if (resync_overlap(mk, st)) return resync_overlap_fail(mk, st);
-    if (resync_overlap(wl, mk)) return resync_overlap_fail(wl, mk);
+    const Region st = resync_states(c, d_states, stride_bytes, nstreams);
+    const Region wl{d_wall, (uint64_t)(wall_h - 1) * wall_pitch + 3 * (uint64_t)wall_w, "the wall"};
+    const Region mk = d_tile_mask ? nowhere(tile_mask_region(c, d_tile_mask, nstreams)) : Region{nullptr, 0, "d_tile_mask"};
+    if (overlap(wl, st)) return overlap_fail(wl, st);
+    if (overlap(mk, st)) return overlap_fail(mk, st);
+    if (overlap(wl, mk)) return overlap_fail(wl, mk);
     if (int rc = use_device(c)) return rc;
     HIP_TRY(launch_wall_compose((const uint8_t *)d_states, stride_bytes, (uint32_t)c->cfg.width, (uint32_t)c->cfg.height, nstreams, h_place,
                                 (const uint32_t *)d_tile_mask, (uint8_t *)d_wall, wall_pitch, c->stream));
@@ -1943,27 +1825,12 @@ int mi355_cwire_touched_tiles_batch(mi355_core *c, const void *d_cwire, const ui
     if (B == 0) return MI355_OK;
     if (!d_cwire || !h_counts || !h_escapes) return fail(MI355_ERR_INVALID, "null stream pointer");
     if (!d_tile_mask) return fail(MI355_ERR_INVALID, "null output pointer");
-    CwireHeaders hdr{h_counts, h_escapes, B};
-    if (int rc = hdr.check(true, c->n)) return rc;
-    std::vector<CwaFrame> fr((size_t)B);   // B <= max_batch: the scratch of the one-stream client holds them
-    uint32_t cbase = 0;
-    for (int b = 0; b < B; b++) {
-        const CwireHeaders::Frame f = hdr.next();
-        fr[b] = CwaFrame{f.pos, f.n, f.e, cbase, cwa_chunks(f.n)};
-        cbase += fr[b].nc;
-    }
-    const ResyncRegion in{d_cwire, hdr.pos, "the input stream"};
-    const ResyncRegion mk{d_tile_mask, 4 * (uint64_t)nstreams * ((cwa_tiles(c->n) + 31u) / 32u), "d_tile_mask"};
-    if (resync_overlap(mk, in)) return resync_overlap_fail(mk, in);
+    CwaTable tab;
+    if (int rc = cwa_table(c, h_counts, h_escapes, B, &tab)) return rc;
+    if (int rc = check_regions({input_region(d_cwire, tab.bytes)}, {nowhere(tile_mask_region(c, d_tile_mask, nstreams))})) return rc;
     if (int rc = use_device(c)) return rc;
-    CwaArgs a{};
-    a.cwire = (const uint8_t *)d_cwire;
-    a.ftab = c->cwa_ftab;
-    a.chunk = c->cwa_chunk;
-    a.dir = c->cwa_dir;
-    a.n = c->n;
-    a.ntiles = cwa_tiles(c->n);
-    HIP_TRY(launch_cwire_touched(a, fr.data(), nstreams, nframes, accumulate != 0, (uint32_t *)d_tile_mask, c->stream));
+    const CwaArgs a = cwa_args(c, d_cwire);
+    HIP_TRY(launch_cwire_touched(a, tab.fr.data(), nstreams, nframes, accumulate != 0, (uint32_t *)d_tile_mask, c->stream));
     return MI355_OK;
 }
 

@@ -189,6 +189,7 @@ struct CwaTableArgs {
 };
 uint32_t cwa_chunks(uint32_t n);        // chunks of a frame of n entries (1 for n = 0)
 uint32_t cwa_tiles(uint32_t nbytes);
+uint32_t cwa_mask_words(uint32_t nbytes);   // 32-bit words of a stream's tile mask
 // frames[i].cbase / nc filled by the caller; nframes <= the scratch's T
 hipError_t launch_cwire_apply(const CwaArgs &a, const CwaFrame *frames, int nframes, hipStream_t s);
 // mi355_apply_multi_cwire_batch: record s onto a.state + s*a.stride (the caller's states; a.out unused), tiles x streams

@@ -2014,21 +2014,25 @@ __global__ __launch_bounds__(64) void k_cw_touched(const CwaArgs a, int nframes,
 // ---- host side ---------------------------------------------------------------------------------------------------------
 uint32_t cwa_chunks(uint32_t n) { return n ? (n + kCwaChunk - 1) / kCwaChunk : 1u; }
 uint32_t cwa_tiles(uint32_t nbytes) { return (nbytes + kCwaTile - 1) / kCwaTile; }
+uint32_t cwa_mask_words(uint32_t nbytes) { return (cwa_tiles(nbytes) + 31u) / 32u; }
+
+// the n >= 1 records to the core's table (k_cwa_table, kCwaTableFrames per launch) -> their chunks (>= n: a record of no entries
+// has one empty chunk)
+static uint32_t launch_cwa_table(const CwaArgs &a, const CwaFrame *records, int n, hipStream_t s) {
+    CwaTableArgs h{};
+    for (int i0 = 0; i0 < n; i0 += kCwaTableFrames) {
+        const int nf = n - i0 < kCwaTableFrames ? n - i0 : kCwaTableFrames;
+        h.first = i0;
+        for (int i = 0; i < nf; i++) h.frame[i] = records[i0 + i];
+        hipLaunchKernelGGL(k_cwa_table, dim3(nf), dim3(256), 0, s, a, h);
+    }
+    return records[n - 1].cbase + records[n - 1].nc;
+}
 
 // mi355_cwire_check_batch: the chunk table and its first two passes are the directory's
 hipError_t launch_cwire_check(const CwaArgs &a, const CwaFrame *records, int nrecords, uint32_t *verdicts, hipStream_t s) {
     if (nrecords <= 0) return hipSuccess;
-    uint32_t nchunks = 0;   // >= nrecords: a record of no entries has one (empty) chunk
-    CwaTableArgs h{};
-    for (int i0 = 0; i0 < nrecords; i0 += kCwaTableFrames) {
-        const int nf = nrecords - i0 < kCwaTableFrames ? nrecords - i0 : kCwaTableFrames;
-        h.first = i0;
-        for (int i = 0; i < nf; i++) {
-            h.frame[i] = records[i0 + i];
-            nchunks = records[i0 + i].cbase + records[i0 + i].nc;
-        }
-        hipLaunchKernelGGL(k_cwa_table, dim3(nf), dim3(256), 0, s, a, h);
-    }
+    const uint32_t nchunks = launch_cwa_table(a, records, nrecords, s);
     hipLaunchKernelGGL(k_cwa_facts, dim3(nchunks), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_cwa_scan, dim3(nrecords), dim3(256), 0, s, a, 0);
     hipLaunchKernelGGL(k_cwk_escsum, dim3(nchunks), dim3(256), 0, s, a);
@@ -2036,19 +2040,9 @@ hipError_t launch_cwire_check(const CwaArgs &a, const CwaFrame *records, int nre
     return hipGetLastError();
 }
 
-// the directory of nframes records (k_cwa_table .. k_cwa_dir)
+// the directory of nframes >= 1 records (k_cwa_table .. k_cwa_dir)
 static void launch_cwa_directory(const CwaArgs &a, const CwaFrame *frames, int nframes, hipStream_t s) {
-    uint32_t nchunks = 0;
-    CwaTableArgs h{};
-    for (int i0 = 0; i0 < nframes; i0 += kCwaTableFrames) {
-        const int nf = nframes - i0 < kCwaTableFrames ? nframes - i0 : kCwaTableFrames;
-        h.first = i0;
-        for (int i = 0; i < nf; i++) {
-            h.frame[i] = frames[i0 + i];
-            nchunks = frames[i0 + i].cbase + frames[i0 + i].nc;
-        }
-        hipLaunchKernelGGL(k_cwa_table, dim3(nf), dim3(256), 0, s, a, h);
-    }
+    const uint32_t nchunks = launch_cwa_table(a, frames, nframes, s);
     hipLaunchKernelGGL(k_cwa_facts, dim3(nchunks), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_cwa_scan, dim3(nframes), dim3(256), 0, s, a, 0);
     hipLaunchKernelGGL(k_cwa_escsum, dim3(nchunks), dim3(256), 0, s, a);
@@ -2129,7 +2123,7 @@ hipError_t launch_state_digest(const uint8_t *states, size_t stride, uint32_t n,
 
 hipError_t launch_refresh(const CwaArgs &a, int nstreams, const uint32_t *peer, uint32_t *mask, const CwcOut &o, hipStream_t s) {
     if (nstreams <= 0) return hipSuccess;
-    const uint32_t mask_words = (a.ntiles + 31u) / 32u;
+    const uint32_t mask_words = cwa_mask_words(a.n);
     const dim3 tiles(a.ntiles * (uint32_t)nstreams);
     if (a.ntiles) {
         const hipError_t e = hipMemsetAsync(mask, 0, (size_t)nstreams * mask_words * sizeof(uint32_t), s);
@@ -2146,13 +2140,13 @@ hipError_t launch_state_clear_tiles(uint8_t *states, size_t stride, uint32_t n, 
     const uint32_t ntiles = cwa_tiles(n);
     if (nstreams <= 0 || ntiles == 0) return hipSuccess;
     hipLaunchKernelGGL(k_state_clear_tiles, dim3(ntiles * (uint32_t)nstreams), dim3(64), 0, s, states, stride, n, ntiles, mask,
-                       (ntiles + 31u) / 32u);
+                       cwa_mask_words(n));
     return hipGetLastError();
 }
 
 hipError_t launch_wall_compose(const uint8_t *states, size_t stride, uint32_t width, uint32_t height, int nstreams,
                                const int32_t *place, const uint32_t *mask, uint8_t *wall, size_t wall_pitch, hipStream_t s) {
-    const uint32_t mask_words = (cwa_tiles(3u * width * height) + 31u) / 32u;
+    const uint32_t mask_words = cwa_mask_words(3u * width * height);
     WallPlaceArgs h{};
     for (int s0 = 0; s0 < nstreams; s0 += kWallPlaceStreams) {
         h.first = s0;
@@ -2180,7 +2174,7 @@ hipError_t launch_cwire_touched(const CwaArgs &a, const CwaFrame *records, int n
     if (nstreams <= 0 || nframes <= 0 || a.ntiles == 0) return hipSuccess;
     launch_cwa_directory(a, records, nstreams * nframes, s);
     hipLaunchKernelGGL(k_cw_touched, dim3((a.ntiles + 63u) / 64u * (uint32_t)nstreams), dim3(64), 0, s, a, nframes, accumulate ? 1 : 0, mask,
-                       (a.ntiles + 31u) / 32u);
+                       cwa_mask_words(a.n));
     return hipGetLastError();
 }
 
