@@ -7,69 +7,8 @@
 // (read the base frame, then pos, pos indices, pos differences per frame) and rebuilds the frames on a
 // second core.  The program checks that the client's frame equals the server's reconstructed state
 // after every batch and that every rebuilt byte is within the threshold of the frame that was sent.
-//
-// --compact: the same over the compact wire format (include/mi355diff.h): the server packs a batch and encodes it on the
-// GPU (mi355_diff_stream_batch, mi355_cwire_encode_batch), the records cross the same pipe, and the client -- with no
-// core and no GPU -- rebuilds every frame on the host with mi355_cwire_apply_host; each rebuilt frame is checked against
-// the frame that was sent, and the client's frame against the server's state after every batch.
-// --compact --direct: the server makes the records in one call (mi355_diff_stream_cwire_batch), without the xs / diff arrays.
-// --compact --gpu-client: the client core also uploads the received records and applies them in one call
-// (mi355_apply_cwire_batch) into its shown frames; every shown frame must equal the host client's frame after that record,
-// and the client core's state the server's state after every batch.
-// --compact --multi S: many cameras per GPU, both ends.  A server core runs T ticks of S synthetic cameras through
-// mi355_diff_multi_cwire_batch; each tick's records (headers included) cross the pipe; a client core uploads them and applies
-// them in one call (mi355_apply_multi_cwire_batch) onto S states of its own.  After every tick the client's states must equal
-// the server's, byte for byte, and after the last tick the frames a host client (mi355_cwire_apply_host) rebuilt per camera.
-// --compact --multi S --budget BYTES: the sender holds every camera's record of a tick to BYTES bytes (a socket's share of the
-// link): the records larger than that are thinned to mi355_cwire_budget_entries(N, BYTES) entries by
-// mi355_cwire_budget_cwire_batch, which takes the sender's states back where it drops an entry.  Checked: every record written is
-// at most BYTES; each client's frame equals the sender's state after every tick; and once the input has stood still for enough
-// ticks every client's frame is within the threshold of the camera's frame at every byte -- what was postponed arrives.
-// --compact --multi S --burst K: the sender buffers K ticks per camera (a recorder, a camera that catches up) and makes their
-// S * K records in ONE call, mi355_diff_multi_stream_cwire_batch: camera s's K records are one contiguous slice, one write()
-// per socket.  The receiver stages record (s, t) of every s back to back for tick t and applies the ticks with the same
-// mi355_apply_multi_cwire_batch; after every burst the states at both ends must be equal.
-// --compact --multi S --burst K --burst-client: the receiver uploads every camera's slice as it came off its socket, stream-major
-// and not re-staged, and applies the whole burst with ONE mi355_apply_multi_stream_cwire_batch into output frames.  After every
-// burst the states at both ends must be equal, and every output frame the frame a host client (mi355_cwire_apply_host) rebuilt
-// for that camera and tick.
-// --compact --multi S --burst K --coalesce: a relay between the two ends that forwards at 1/K of the rate (a slow link, a
-// time-lapse recorder, a video wall).  It holds no frame: it uploads every camera's slice as it came off its socket, makes
-// ONE record per camera of the burst with mi355_cwire_coalesce_cwire_batch, and forwards those S records; the receiver applies
-// them with one mi355_apply_multi_cwire_batch.  After every burst each camera's state at the receiver must equal the frame of
-// a host client (mi355_cwire_apply_host) that applied all K original records, and the sender's state.  The line also says how
-// many bytes the relay received and how many it forwarded.
-// --compact --multi S --activity CELL [--burst K --burst-client]: after every tick (or burst) the receiver also asks where its
-// cameras move: mi355_cwire_activity_batch on the records it is about to apply, square cells of CELL pixels -> a grid of changed
-// bytes per cell and eight summary words per camera.  Checked against a plain C++ count over records decoded here; the box and the
-// active cells of every camera's last tick (or burst) are printed.
-// --compact --multi S --check [--burst K --burst-client]: the receiver trusts nothing it has not checked: before it applies a tick
-// (or burst) it asks mi355_cwire_check_batch for a verdict per record and requires every record well-formed and canonical (word
-// 0 == 0), the verdicts equal to mi355_cwire_check_host's on the received bytes, and word 3 of every record equal to 1 + the
-// last byte index that the apply then changes.  Once per run it also checks a damaged copy of the first non-empty record -- one
-// code byte set to 255 -- and requires MI355_CWIRE_BAD_CODES.
-// --compact --multi S --resync K [--burst B]: a receiver that lost a record finds its way back.  At tick K the receiver drops one
-// camera's record (it applies an empty record in its place), so that camera's frame is wrong from then on.  After tick K + 1 it
-// digests its states (mi355_state_digest_batch, checked against mi355_state_digest_host) and sends the digests up; the sender
-// answers behind its latest tick -- with --burst B the end of the burst it has already made -- with a tile mask and one refresh
-// record per camera (mi355_refresh_cwire_batch); the receiver applies the ticks that were in flight, clears the masked tiles
-// (mi355_state_clear_tiles_batch) and applies the refresh records like any others.  Checked: the dropped camera's frame differs
-// from the sender's at every tick between the loss and the refresh, and every other frame of every tick -- all of them from the
-// refresh on -- equals the sender's; the dropped camera has mask bits and, unless ticks were in flight, only that camera (the
-// others get the 8-byte record); a host client that
-// clears the tiles itself and calls mi355_cwire_apply_host ends at the same frames.
-// --compact --multi S --wall K [--burst B --burst-client | --resync R [--burst B]]: the receiver is a wall that shows its cameras.  It
-// keeps ONE wall frame of ceil(sqrt(S)) columns of thumbnails at scale K, composed fully once (mi355_wall_compose_batch without
-// a mask).  After every tick's apply -- with --burst B --burst-client after every burst's -- it asks which tiles the records it just
-// applied land in (mi355_cwire_touched_tiles_batch) and repaints the wall there (mi355_wall_compose_batch with that mask), the
-// three calls with no wait in between.  With --resync R the refresh's own mask goes through the same masked compose behind the
-// clear and the apply.  After every tick or burst, and after the refresh, the wall must equal a plain C++ box average of the
-// receiver's states, and the wall's bytes outside the thumbnails the pattern they started as.
-// --compact --per-frame: the per-frame server, one host frame per call and no device pointer in sight.  The sender feeds
-// host frames through mi355_pipe_submit_cwire, four in flight, and writes each frame's record to the pipe with ONE write()
-// from the pinned buffer it arrived in; the receiver -- a thread with no core -- reads header and body, applies the record
-// with mi355_cwire_apply_host and compares its frame, frame by frame, with that of a host client of the plain path
-// (mi355_exec on a second core: frame[xs[i]] += diff[i], client/opencv.cpp:64-66).
+// Every other mode is described at the head of the run_* function, or of the check a mode hands its records to
+// (ActivityCheck, RecordCheck, WallCheck), that is that mode.
 //
 //   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B]
 //                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check] | --resync K [--burst B]] [--wall K]]
@@ -122,18 +61,274 @@ static bool read_all(int fd, void *p, size_t n) {   // the client's read loops, 
     return true;
 }
 
-// "send" n bytes and "receive" them: written in pieces that fit the pipe buffer, read back in between
-static bool through_pipe(int wfd, int rfd, const uint8_t *src, uint8_t *dst, size_t n) {
-    for (size_t at = 0; at < n;) {
-        const size_t piece = n - at < 32768 ? n - at : 32768;
-        if (write(wfd, src + at, piece) != (ssize_t)piece) return false;
-        if (!read_all(rfd, dst + at, piece)) return false;
-        at += piece;
-    }
-    return true;
+static mi355_config make_config(int w, int h, int max_batch) {
+    mi355_config cfg;
+    memset(&cfg, 0, sizeof cfg);
+    cfg.width = w; cfg.height = h; cfg.threshold = 20; cfg.max_batch = max_batch; cfg.device = -1;
+    return cfg;
 }
 
-// --activity CELL (see the head of the file): the receiver's motion grids of the records in rx, against a count made here
+// What one run holds: its cores, its pipe and every allocation it handed out.  A failure is printed where it happens and
+// remembered: everything after it hands out nullptr, so a mode asks ok() once behind its set-up.  close() is for the success
+// path; after an error the function returns and the process ends.
+struct Session {
+    int w, h, threshold, fds[2];
+    size_t n;   // bytes of a frame
+    bool failed = false;
+    std::vector<mi355_core *> cores;
+    struct Dev { mi355_core *core; void *p; };
+    std::vector<Dev> devs;
+    std::vector<void *> pins;
+
+    Session(int w_, int h_) : w(w_), h(h_), threshold(make_config(w_, h_, 1).threshold), n((size_t)3 * w_ * h_) {
+        if (pipe(fds) != 0) failed = true;
+    }
+    bool ok() const { return !failed; }
+    void *fail(const char *what) {
+        if (!failed) fprintf(stderr, "%s failed: %s\n", what, mi355_last_error());
+        failed = true;
+        return nullptr;
+    }
+    mi355_core *core(int max_batch) {
+        const mi355_config cfg = make_config(w, h, max_batch);
+        mi355_core *c = nullptr;
+        if (failed || mi355_create(&cfg, &c) != MI355_OK) return (mi355_core *)fail("mi355_create");
+        cores.push_back(c);
+        return c;
+    }
+    void *dev(mi355_core *c, size_t bytes) {
+        void *p = nullptr;
+        if (failed || mi355_dev_alloc(c, &p, bytes) != MI355_OK) return fail("mi355_dev_alloc");
+        devs.push_back(Dev{c, p});
+        return p;
+    }
+    void *pinned(size_t bytes) {
+        void *p = nullptr;
+        if (failed || mi355_host_alloc(&p, bytes) != MI355_OK) return fail("mi355_host_alloc");
+        pins.push_back(p);
+        return p;
+    }
+    // "send" bytes and "receive" them: written in pieces that fit the pipe buffer, read back in between
+    bool send(const void *src, void *dst, size_t bytes) {
+        for (size_t at = 0; at < bytes;) {
+            const size_t piece = bytes - at < 32768 ? bytes - at : 32768;
+            if (write(fds[1], (const uint8_t *)src + at, piece) != (ssize_t)piece) return false;
+            if (!read_all(fds[0], (uint8_t *)dst + at, piece)) return false;
+            at += piece;
+        }
+        return true;
+    }
+    int close() {
+        for (size_t i = 0; i < devs.size(); i++) OK(mi355_dev_free(devs[i].core, devs[i].p));
+        for (size_t i = 0; i < pins.size(); i++) OK(mi355_host_free(pins[i]));
+        for (size_t i = 0; i < cores.size(); i++) mi355_destroy(cores[i]);
+        return 0;
+    }
+};
+
+// ---- checks every mode makes
+static int max_abs_error(const uint8_t *a, const uint8_t *b, size_t bytes) {
+    int max_err = 0;
+    for (size_t i = 0; i < bytes; i++) {
+        const int e = abs((int)a[i] - (int)b[i]);
+        if (e > max_err) max_err = e;
+    }
+    return max_err;
+}
+
+static int within_threshold(int max_err, const Session &ss) {
+    if (max_err > ss.threshold) { fprintf(stderr, "rebuilt frame off by %d > threshold\n", max_err); return 1; }
+    return 0;
+}
+
+// the two buffers are equal, or: "tick t: what" (t < 0: no tick to name)
+static int same(const void *a, const void *b, size_t bytes, const char *what, int t = -1) {
+    if (memcmp(a, b, bytes) == 0) return 0;
+    if (t >= 0) fprintf(stderr, "tick %d: ", t);
+    fprintf(stderr, "%s\n", what);
+    return 1;
+}
+
+// The receiver's header walk: nrec records back to back in rx[p, end), found from their headers as they are read from a
+// socket -> counts[r], escapes[r] and, if asked for, where each lies: at[r] .. at[r + 1]
+static int walk_records(const uint8_t *rx, size_t p, size_t end, int nrec, uint32_t *counts, uint32_t *escapes, size_t *at) {
+    int r = 0;
+    for (; r < nrec && p + 8 <= end; r++) {
+        memcpy(&counts[r], rx + p, 4);
+        memcpy(&escapes[r], rx + p + 4, 4);
+        if (at) at[r] = p;
+        p += mi355_cwire_frame_bytes(counts[r], escapes[r]);
+    }
+    if (at) at[r] = p;
+    if (r == nrec && p == end) return 0;
+    fprintf(stderr, "stream framing broken\n");
+    return 1;
+}
+
+// a host client beside a receiver: record r of a walk (rx, at) onto its frame; it must use the bytes the header said it has
+static int host_apply(uint8_t *frame, size_t n, const uint8_t *rx, const size_t *at, int r) {
+    size_t used = 0;
+    OK(mi355_cwire_apply_host(frame, n, rx + at[r], at[r + 1] - at[r], 1, &used));
+    if (used != at[r + 1] - at[r]) { fprintf(stderr, "stream framing broken\n"); return 1; }
+    return 0;
+}
+
+// ---- the two ends of the many-camera modes
+// The sender: S camera states on a core of its own, and one step of the loop -- upload the frames of nb ticks, diff them
+// into records (one call), download offsets and positions, refuse a stream larger than its bound, download the bytes.
+struct Sender {
+    mi355_core *core = nullptr;
+    int S = 0;
+    size_t n = 0, cap = 0, cb = 0, changed = 0;   // cb: the bytes of the last step; changed: entries so far
+    void *d_frames = nullptr, *d_states = nullptr, *d_off = nullptr, *d_pos = nullptr, *d_cw = nullptr;
+    std::vector<uint8_t> frames, bytes, states;   // stream-major frames of a step, its records, the states (get_states)
+    std::vector<uint32_t> off;
+    std::vector<uint64_t> pos;
+
+    int open(Session &ss, int S_, int K) {   // K: the most ticks in one step
+        const int B = S_ * K;
+        S = S_; n = ss.n; cap = mi355_cwire_bytes_max(n, B);
+        core = ss.core(B);
+        d_frames = ss.dev(core, (size_t)B * n);
+        d_states = ss.dev(core, (size_t)S * n);
+        d_off = ss.dev(core, sizeof(uint32_t) * (B + 1));
+        d_pos = ss.dev(core, sizeof(uint64_t) * (B + 1));
+        d_cw = ss.dev(core, cap);
+        frames.resize((size_t)B * n); bytes.resize(cap); states.resize((size_t)S * n);
+        off.resize(B + 1); pos.resize(B + 1);
+        return ss.ok() ? 0 : 1;
+    }
+    // one tick (mi355_diff_multi_cwire_batch), or a burst of nb ticks, camera s's nb records one contiguous slice
+    int step(int nb, bool burst) {
+        const int nrec = S * nb;
+        OK(mi355_upload(core, d_frames, frames.data(), (size_t)nrec * n));
+        if (!burst) OK(mi355_diff_multi_cwire_batch(core, d_frames, d_states, n, S, d_off, d_pos, d_cw, cap));
+        else OK(mi355_diff_multi_stream_cwire_batch(core, d_frames, d_states, n, S, nb, d_off, d_pos, d_cw, cap));
+        OK(mi355_download(core, off.data(), d_off, sizeof(uint32_t) * (nrec + 1)));
+        OK(mi355_download(core, pos.data(), d_pos, sizeof(uint64_t) * (nrec + 1)));
+        if (pos[nrec] > cap) { fprintf(stderr, "compact stream larger than its bound\n"); return 1; }
+        cb = (size_t)pos[nrec];
+        OK(mi355_download(core, bytes.data(), d_cw, cb));
+        changed += off[nrec];
+        return 0;
+    }
+    int get_states() {
+        OK(mi355_download(core, states.data(), d_states, states.size()));
+        return 0;
+    }
+};
+
+// A node that receives records: a core, the bytes as they came (rx, and d_rx for their upload), the headers its walk found
+// and, unless it is a relay that holds no frame, S camera states.
+struct Receiver {
+    mi355_core *core = nullptr;
+    int S = 0;
+    size_t n = 0, cap = 0;
+    void *d_rx = nullptr, *d_states = nullptr;
+    std::vector<uint8_t> rx, states;
+    std::vector<uint32_t> counts, escapes;
+    std::vector<size_t> at;
+
+    int open(Session &ss, int S_, int max_batch, int most, bool holds_states = true) {   // most: records in one upload
+        S = S_; n = ss.n; cap = mi355_cwire_bytes_max(n, most);
+        core = ss.core(max_batch);
+        d_rx = ss.dev(core, cap);
+        if (holds_states) d_states = ss.dev(core, (size_t)S * n);
+        rx.resize(cap); states.resize(holds_states ? (size_t)S * n : 0);
+        counts.resize(most); escapes.resize(most); at.resize(most + 1);
+        return ss.ok() ? 0 : 1;
+    }
+    // records first .. first + nrec - 1 lie in rx[from, to)
+    int walk(size_t from, size_t to, int first, int nrec) {
+        return walk_records(rx.data(), from, to, nrec, &counts[first], &escapes[first], &at[first]);
+    }
+    // Tick k of a burst of nb that was received stream-major (burst, b_at): record (s, k) of every camera s back to back in rx,
+    // walked.  drop >= 0: that camera's record is lost, an empty record stands in its place.  Returns the bytes staged.
+    size_t stage(const uint8_t *burst, const size_t *b_at, int nb, int k, int drop) {
+        size_t q = 0;
+        for (int s = 0; s < S; s++) {
+            const int r = s * nb + k;
+            const size_t len = s == drop ? 8 : b_at[r + 1] - b_at[r];
+            if (s == drop) memset(rx.data() + q, 0, 8);
+            else memcpy(rx.data() + q, burst + b_at[r], len);
+            memcpy(&counts[s], rx.data() + q, 4);
+            memcpy(&escapes[s], rx.data() + q + 4, 4);
+            at[s] = q;
+            q += len;
+        }
+        at[S] = q;
+        return q;
+    }
+    // one tick's S records, uploaded to d_rx, onto the states: one call
+    int apply_tick() {
+        OK(mi355_apply_multi_cwire_batch(core, d_rx, counts.data(), escapes.data(), S, d_states, n));
+        return 0;
+    }
+    int get_states() {
+        OK(mi355_download(core, states.data(), d_states, states.size()));
+        return 0;
+    }
+};
+
+// the states at both ends (the receiver's as get_states() left them) are equal
+static int states_equal(Sender &tx, const Receiver &rcv, int t) {
+    if (tx.get_states()) return 1;
+    return same(tx.states.data(), rcv.states.data(), tx.states.size(), "receiver states != sender states", t);
+}
+
+// S synthetic cameras: their base frames and, tick by tick, their frames
+struct Cameras {
+    int S, w, h;
+    size_t n;
+    std::vector<uint8_t> bases, base, frame;
+
+    Cameras(int S_, int w_, int h_) : S(S_), w(w_), h(h_), n((size_t)3 * w_ * h_), bases((size_t)S_ * n), base(n), frame(n) {
+        for (int s = 0; s < S; s++)
+            for (size_t i = 0; i < n; i++) bases[(size_t)s * n + i] = (uint8_t)(40 + (i * 7 + (size_t)s * 31) % 150);
+    }
+    // the frames of ticks t0 .. t0 + nb - 1, stream-major: camera s's nb frames one behind the other, its own base, its block a
+    // few steps ahead of its neighbour's
+    void fill(uint8_t *frames, int t0, int nb) {
+        for (int s = 0; s < S; s++) {
+            memcpy(base.data(), &bases[(size_t)s * n], n);
+            for (int k = 0; k < nb; k++) {
+                make_frame(frame, base, w, h, t0 + k + 5 * s);
+                memcpy(frames + ((size_t)s * nb + k) * n, frame.data(), n);
+            }
+        }
+    }
+    // every camera's base frame: the sender's states, and through the pipe the receiver's (opencv.cpp:38-46 per camera)
+    int start(Session &ss, Sender &tx, Receiver &rcv, uint8_t *host_copy) {
+        OK(mi355_upload(tx.core, tx.d_states, bases.data(), bases.size()));
+        if (!ss.send(bases.data(), host_copy, bases.size())) return 1;
+        OK(mi355_upload(rcv.core, rcv.d_states, host_copy, bases.size()));
+        return 0;
+    }
+};
+
+// The sockets of a burst into a node that keeps the slices as they came (a burst client, a relay): camera s's nb records,
+// [pos[s * nb], pos[(s + 1) * nb]), are one write; the node reads their headers behind those of camera s - 1 and uploads the
+// slice where it lies, stream-major, nothing re-staged.  A host client of camera s beside it applies the records one by one
+// (host_shown, if given: the frame it shows after each).
+static int slices_to_node(Session &ss, const Sender &tx, Receiver &node, int nb, uint8_t *host_frames, uint8_t *host_shown) {
+    const size_t n = tx.n;
+    for (int s = 0; s < tx.S; s++) {
+        const size_t a = (size_t)tx.pos[(size_t)s * nb], b = (size_t)tx.pos[(size_t)(s + 1) * nb];
+        if (!ss.send(tx.bytes.data() + a, node.rx.data() + a, b - a)) return 1;
+        if (node.walk(a, b, s * nb, nb)) return 1;
+        for (int r = s * nb; r < (s + 1) * nb; r++) {
+            if (host_apply(host_frames + (size_t)s * n, n, node.rx.data(), node.at.data(), r)) return 1;
+            if (host_shown) memcpy(host_shown + (size_t)r * n, host_frames + (size_t)s * n, n);
+        }
+        if (b > a) OK(mi355_upload(node.core, (uint8_t *)node.d_rx + a, node.rx.data() + a, b - a));
+    }
+    return 0;
+}
+
+// --compact --multi S --activity CELL [--burst K --burst-client]: after every tick (or burst) the receiver also asks where its
+// cameras move: mi355_cwire_activity_batch on the records it is about to apply, square cells of CELL pixels -> a grid of changed
+// bytes per cell and eight summary words per camera.  Checked against a plain C++ count over records decoded here; the box and the
+// active cells of every camera's last tick (or burst) are printed.
 struct ActivityCheck {
     mi355_core *core = nullptr;
     int w = 0, h = 0, cell = 0, S = 0, gw = 0, gh = 0, calls = 0;
@@ -141,12 +336,14 @@ struct ActivityCheck {
     void *d_cells = nullptr, *d_summary = nullptr;
     std::vector<uint32_t> got_cells, got_sum, want_cells, want_sum;
 
-    int open(mi355_core *c, int w_, int h_, int cell_, int S_) {
-        core = c; w = w_; h = h_; cell = cell_; S = S_;
+    int open(Session &ss, mi355_core *c, int cell_, int S_) {   // cell_ == 0: not asked for
+        if (!cell_) return 0;
+        core = c; w = ss.w; h = ss.h; cell = cell_; S = S_;
         cells = mi355_activity_cells(w, h, cell, cell, &gw, &gh);
         if (!cells) { fprintf(stderr, "--activity CELL needs CELL >= 1\n"); return 2; }
-        OK(mi355_dev_alloc(core, &d_cells, sizeof(uint32_t) * cells * S));
-        OK(mi355_dev_alloc(core, &d_summary, sizeof(uint32_t) * 8 * S));
+        d_cells = ss.dev(core, sizeof(uint32_t) * cells * S);
+        d_summary = ss.dev(core, sizeof(uint32_t) * 8 * S);
+        if (!ss.ok()) return 1;
         got_cells.resize(cells * S); want_cells.resize(cells * S);
         got_sum.resize((size_t)8 * S); want_sum.resize((size_t)8 * S);
         return 0;
@@ -209,15 +406,13 @@ struct ActivityCheck {
         }
         return o + "]}";
     }
-    int close() {
-        if (!cell) return 0;
-        OK(mi355_dev_free(core, d_cells));
-        OK(mi355_dev_free(core, d_summary));
-        return 0;
-    }
 };
 
-// --check (see the head of the file): the verdicts of the records in rx before they are applied, and what the apply then changed
+// --compact --multi S --check [--burst K --burst-client]: the receiver trusts nothing it has not checked: before it applies a tick
+// (or burst) it asks mi355_cwire_check_batch for a verdict per record and requires every record well-formed and canonical (word
+// 0 == 0), the verdicts equal to mi355_cwire_check_host's on the received bytes, and word 3 of every record equal to 1 + the
+// last byte index that the apply then changes.  Once per run it also checks a damaged copy of the first non-empty record -- one
+// code byte set to 255 -- and requires MI355_CWIRE_BAD_CODES.
 struct RecordCheck {
     mi355_core *core = nullptr;
     bool on = false, damaged_done = false;
@@ -226,10 +421,12 @@ struct RecordCheck {
     void *d_verdicts = nullptr, *d_damaged = nullptr;
     std::vector<uint32_t> got, want;
 
-    int open(mi355_core *c, size_t n_, int most) {
-        core = c; n = n_; on = true;
-        OK(mi355_dev_alloc(core, &d_verdicts, sizeof(uint32_t) * 4 * most));
-        OK(mi355_dev_alloc(core, &d_damaged, mi355_cwire_bytes_max(n, 1)));
+    int open(Session &ss, mi355_core *c, bool on_, int most) {
+        if (!on_) return 0;
+        core = c; n = ss.n; on = true;
+        d_verdicts = ss.dev(core, sizeof(uint32_t) * 4 * most);
+        d_damaged = ss.dev(core, mi355_cwire_bytes_max(n, 1));
+        if (!ss.ok()) return 1;
         got.resize((size_t)4 * most); want.resize((size_t)4 * most);
         return 0;
     }
@@ -284,14 +481,17 @@ struct RecordCheck {
     int close() {
         if (!on) return 0;
         if (!damaged_done) { fprintf(stderr, "--check: no record had an entry to damage\n"); return 1; }
-        OK(mi355_dev_free(core, d_verdicts));
-        OK(mi355_dev_free(core, d_damaged));
         return 0;
     }
 };
 
-// --wall K (see the head of the file): the receiver's wall of thumbnails, kept current where records land, against a box average
-// made here
+// --compact --multi S --wall K [--burst B --burst-client | --resync R [--burst B]]: the receiver is a wall that shows its cameras.  It
+// keeps ONE wall frame of ceil(sqrt(S)) columns of thumbnails at scale K, composed fully once (mi355_wall_compose_batch without
+// a mask).  After every tick's apply -- with --burst B --burst-client after every burst's -- it asks which tiles the records it just
+// applied land in (mi355_cwire_touched_tiles_batch) and repaints the wall there (mi355_wall_compose_batch with that mask), the
+// three calls with no wait in between.  With --resync R the refresh's own mask goes through the same masked compose behind the
+// clear and the apply.  After every tick or burst, and after the refresh, the wall must equal a plain C++ box average of the
+// receiver's states, and the wall's bytes outside the thumbnails the pattern they started as.
 struct WallCheck {
     mi355_core *core = nullptr;
     int w = 0, h = 0, k = 0, S = 0, tw = 0, th = 0, cols = 0, wall_w = 0, wall_h = 0, composes = 0, compared = 0;
@@ -301,9 +501,10 @@ struct WallCheck {
     std::vector<uint8_t> got, want;
     enum : uint8_t { kPattern = 0x5C };     // what the wall holds outside the thumbnails (and in its pitch gap), from start to end
 
-    int open(mi355_core *c, int w_, int h_, int k_, int S_) {
-        if (!mi355_wall_thumb_size(w_, h_, k_, &tw, &th)) { fprintf(stderr, "--wall K needs 1 <= K <= 16\n"); return 2; }
-        core = c; w = w_; h = h_; k = k_; S = S_;
+    int open(Session &ss, mi355_core *c, int k_, int S_) {   // k_ == 0: not asked for
+        if (!k_) return 0;
+        if (!mi355_wall_thumb_size(ss.w, ss.h, k_, &tw, &th)) { fprintf(stderr, "--wall K needs 1 <= K <= 16\n"); return 2; }
+        core = c; w = ss.w; h = ss.h; k = k_; S = S_;
         while (cols * cols < S) cols++;
         const int rows = (S + cols - 1) / cols;
         wall_w = cols * (tw + 1) + 1;   // a pixel of the pattern around every thumbnail
@@ -318,8 +519,9 @@ struct WallCheck {
         mask_bytes = 4 * (size_t)S * ((mi355_state_tiles((size_t)3 * w * h) + 31) / 32);
         got.assign(pitch * wall_h, kPattern);
         want = got;
-        OK(mi355_dev_alloc(core, &d_wall, got.size()));
-        OK(mi355_dev_alloc(core, &d_mask, mask_bytes));
+        d_wall = ss.dev(core, got.size());
+        d_mask = ss.dev(core, mask_bytes);
+        if (!ss.ok()) return 1;
         OK(mi355_upload(core, d_wall, got.data(), got.size()));
         return 0;
     }
@@ -373,242 +575,169 @@ struct WallCheck {
     int close() {
         if (!k) return 0;
         if (!compared) { fprintf(stderr, "--wall: no wall was compared\n"); return 1; }
-        OK(mi355_dev_free(core, d_wall));
-        OK(mi355_dev_free(core, d_mask));
         return 0;
     }
 };
 
-// --compact --multi S (see the head of the file)
-static int run_multi(int w, int h, int T, int S, int activity, bool check, int wall_k) {
-    const size_t n = (size_t)3 * w * h;
-    mi355_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.width = w; cfg.height = h; cfg.threshold = 20; cfg.max_batch = S; cfg.device = -1;
-    mi355_core *server = nullptr, *client = nullptr;
-    OK(mi355_create(&cfg, &server));
-    OK(mi355_create(&cfg, &client));
-    const size_t cw_cap = mi355_cwire_bytes_max(n, S);
-    void *d_frames = nullptr, *d_sstates = nullptr, *d_off = nullptr, *d_pos = nullptr, *d_cw = nullptr;   // server
-    void *d_rx = nullptr, *d_cstates = nullptr;                                                              // client
-    OK(mi355_dev_alloc(server, &d_frames, (size_t)S * n));
-    OK(mi355_dev_alloc(server, &d_sstates, (size_t)S * n));
-    OK(mi355_dev_alloc(server, &d_off, sizeof(uint32_t) * (S + 1)));
-    OK(mi355_dev_alloc(server, &d_pos, sizeof(uint64_t) * (S + 1)));
-    OK(mi355_dev_alloc(server, &d_cw, cw_cap));
-    OK(mi355_dev_alloc(client, &d_rx, cw_cap));
-    OK(mi355_dev_alloc(client, &d_cstates, (size_t)S * n));
+// --compact --multi S: many cameras per GPU, both ends.  A server core runs T ticks of S synthetic cameras through
+// mi355_diff_multi_cwire_batch; each tick's records (headers included) cross the pipe; a client core uploads them and applies
+// them in one call (mi355_apply_multi_cwire_batch) onto S states of its own.  After every tick the client's states must equal
+// the server's, byte for byte, and the frames a host client (mi355_cwire_apply_host) rebuilt per camera.
+// --compact --multi S --burst K --burst-client (K > 0 here): the sender makes the S * K records of K ticks in ONE call
+// (run_multi_burst says how); the receiver uploads every camera's slice as it came off its socket, stream-major and not
+// re-staged, and applies the whole burst with ONE mi355_apply_multi_stream_cwire_batch into output frames.  After every burst
+// the states at both ends must be equal, and every output frame the frame a host client rebuilt for that camera and tick.
+static int run_multi(int w, int h, int T, int S, int K, int activity, bool check, int wall_k) {
+    const bool burst = K > 0;
+    if (!burst) K = 1;
+    Session ss(w, h);
+    const size_t n = ss.n;
+    const int B = S * K;
+    Cameras cams(S, w, h);
+    Sender tx;
+    Receiver rcv;
     ActivityCheck act;
-    if (activity)
-        if (int rc = act.open(client, w, h, activity, S)) return rc;
     RecordCheck chk;
-    if (check)
-        if (int rc = chk.open(client, n, S)) return rc;
     WallCheck wall;
-    if (wall_k)
-        if (int rc = wall.open(client, w, h, wall_k, S)) return rc;
-    int fds[2];
-    if (pipe(fds) != 0) return 1;
-    // every camera's base frame: the server's states, and through the pipe the client's (opencv.cpp:38-46 per camera)
-    std::vector<uint8_t> bases((size_t)S * n), host_frames((size_t)S * n), frames((size_t)S * n), s_states((size_t)S * n),
-        c_states((size_t)S * n), cw_host(cw_cap), rx(cw_cap);
-    for (int s = 0; s < S; s++)
-        for (size_t i = 0; i < n; i++) bases[(size_t)s * n + i] = (uint8_t)(40 + (i * 7 + (size_t)s * 31) % 150);
-    OK(mi355_upload(server, d_sstates, bases.data(), bases.size()));
-    if (!through_pipe(fds[1], fds[0], bases.data(), host_frames.data(), bases.size())) return 1;
-    OK(mi355_upload(client, d_cstates, host_frames.data(), host_frames.size()));
-    if (int rc = wall.full(d_cstates)) return rc;
-    std::vector<uint8_t> base(n), frame(n), before(check ? host_frames : std::vector<uint8_t>());   // (before: the states a tick finds)
-    std::vector<uint32_t> off(S + 1), counts(S), escapes(S);
-    std::vector<uint64_t> pos(S + 1);
-    size_t sent_bytes = 0, changed = 0;
-    int max_err = 0;
-    for (int t = 0; t < T; t++) {
-        for (int s = 0; s < S; s++) {   // camera s: its own base, its block a few steps ahead of its neighbour's
-            memcpy(base.data(), &bases[(size_t)s * n], n);
-            make_frame(frame, base, w, h, t + 5 * s);
-            memcpy(&frames[(size_t)s * n], frame.data(), n);
+    if (tx.open(ss, S, K) || rcv.open(ss, S, B, B)) return 1;
+    void *d_shown = burst ? ss.dev(rcv.core, (size_t)B * n) : nullptr;
+    if (!ss.ok()) return 1;
+    if (int rc = act.open(ss, rcv.core, activity, S)) return rc;
+    if (int rc = chk.open(ss, rcv.core, check, B)) return rc;
+    if (int rc = wall.open(ss, rcv.core, wall_k, S)) return rc;
+    // a host client per camera beside the receiver, and what it shows after every record of a burst
+    std::vector<uint8_t> host_frames((size_t)S * n), host_shown((size_t)B * n), shown(burst ? (size_t)B * n : 0);
+    if (cams.start(ss, tx, rcv, host_frames.data())) return 1;
+    if (int rc = wall.full(rcv.d_states)) return rc;
+    std::vector<uint8_t> before(check ? host_frames : std::vector<uint8_t>());   // (the states a tick or burst finds)
+    const uint32_t *counts = rcv.counts.data(), *escapes = rcv.escapes.data();
+    size_t sent_bytes = 0;
+    int max_err = 0, calls = 0;
+    for (int t0 = 0; t0 < T; t0 += K) {
+        const int nb = T - t0 < K ? T - t0 : K, nrec = S * nb, t = t0 + nb - 1;
+        cams.fill(tx.frames.data(), t0, nb);
+        // ---- server: one tick -> S records, or nb ticks -> S * nb records, in one call
+        if (tx.step(nb, burst)) return 1;
+        calls++;
+        // ---- the sockets, the headers as read from the stream, the upload; the host clients beside it.  A tick: one pipe here,
+        // the receiver stages the cameras' records back to back.  A burst: a slice per camera.
+        if (burst) {
+            if (slices_to_node(ss, tx, rcv, nb, host_frames.data(), host_shown.data())) return 1;
+        } else {
+            if (!ss.send(tx.bytes.data(), rcv.rx.data(), tx.cb) || rcv.walk(0, tx.cb, 0, S)) return 1;
+            for (int s = 0; s < S; s++)
+                if (host_apply(&host_frames[(size_t)s * n], n, rcv.rx.data(), rcv.at.data(), s)) return 1;
+            host_shown = host_frames;
+            OK(mi355_upload(rcv.core, rcv.d_rx, rcv.rx.data(), tx.cb));
         }
-        // ---- server: one tick -> S records
-        OK(mi355_upload(server, d_frames, frames.data(), frames.size()));
-        OK(mi355_diff_multi_cwire_batch(server, d_frames, d_sstates, n, S, d_off, d_pos, d_cw, cw_cap));
-        OK(mi355_download(server, off.data(), d_off, sizeof(uint32_t) * (S + 1)));
-        OK(mi355_download(server, pos.data(), d_pos, sizeof(uint64_t) * (S + 1)));
-        if (pos[S] > cw_cap) { fprintf(stderr, "compact stream larger than its bound\n"); return 1; }
-        const size_t cb = (size_t)pos[S];
-        OK(mi355_download(server, cw_host.data(), d_cw, cb));
-        changed += off[S];
-        // ---- the sockets (one pipe here: the receiver stages the cameras' records back to back)
-        if (!through_pipe(fds[1], fds[0], cw_host.data(), rx.data(), cb)) return 1;
-        sent_bytes += cb;
-        // ---- client: the headers as read from the stream, one upload, one call
-        size_t p = 0;
-        for (int s = 0; s < S; s++) {
-            if (p + 8 > cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
-            memcpy(&counts[s], rx.data() + p, 4);
-            memcpy(&escapes[s], rx.data() + p + 4, 4);
-            size_t used = 0;   // ... and the host client of camera s beside it
-            OK(mi355_cwire_apply_host(&host_frames[(size_t)s * n], n, rx.data() + p, cb - p, 1, &used));
-            if (used != mi355_cwire_frame_bytes(counts[s], escapes[s])) { fprintf(stderr, "stream framing broken\n"); return 1; }
-            p += used;
-        }
-        if (p != cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
-        OK(mi355_upload(client, d_rx, rx.data(), cb));
-        if (int rc = act.run(d_rx, rx.data(), counts.data(), escapes.data(), 1, t)) return rc;
-        if (int rc = chk.run(d_rx, rx.data(), cb, counts.data(), escapes.data(), S, t)) return rc;
-        OK(mi355_apply_multi_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, d_cstates, n));
-        if (int rc = wall.update(d_rx, counts.data(), escapes.data(), 1, d_cstates)) return rc;
-        // ---- checks
-        OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
-        if (int rc = wall.compare(c_states.data(), t)) return rc;
-        for (int s = 0; s < S && check; s++)
-            if (int rc = chk.applied(s, &before[(size_t)s * n], &c_states[(size_t)s * n], t)) return rc;
-        if (check) before = c_states;
-        OK(mi355_download(server, s_states.data(), d_sstates, s_states.size()));
-        if (memcmp(s_states.data(), c_states.data(), s_states.size()) != 0) {
-            fprintf(stderr, "tick %d: client states != server states\n", t);
-            return 1;
-        }
-        for (size_t i = 0; i < c_states.size(); i++) {
-            const int e = abs((int)c_states[i] - (int)frames[i]);
-            if (e > max_err) max_err = e;
-        }
+        sent_bytes += tx.cb;
+        if (int rc = act.run(rcv.d_rx, rcv.rx.data(), counts, escapes, nb, t0)) return rc;
+        if (int rc = chk.run(rcv.d_rx, rcv.rx.data(), tx.cb, counts, escapes, nrec, t0)) return rc;
+        // ---- client: one call; of a burst, every frame in between into d_shown
+        if (burst) OK(mi355_apply_multi_stream_cwire_batch(rcv.core, rcv.d_rx, counts, escapes, S, nb, rcv.d_states, n, d_shown, n));
+        else if (rcv.apply_tick()) return 1;
+        if (int rc = wall.update(rcv.d_rx, counts, escapes, nb, rcv.d_states)) return rc;
+        // ---- checks; `after`: the frame behind every record (of a tick, the states themselves)
+        if (rcv.get_states()) return 1;
+        if (int rc = wall.compare(rcv.states.data(), t)) return rc;
+        if (burst) OK(mi355_download(rcv.core, shown.data(), d_shown, (size_t)nrec * n));
+        const uint8_t *after = burst ? shown.data() : rcv.states.data();
+        for (int r = 0; r < nrec && check; r++)   // record (s, k) turned the frame after record (s, k - 1) into its own
+            if (int rc = chk.applied(r, r % nb ? after + (size_t)(r - 1) * n : &before[(size_t)(r / nb) * n], after + (size_t)r * n, t0)) return rc;
+        if (check) before = rcv.states;
+        if (states_equal(tx, rcv, t0)) return 1;
+        for (int r = 0; r < nrec; r++)
+            if (memcmp(after + (size_t)r * n, &host_shown[(size_t)r * n], n) != 0) {
+                fprintf(stderr, "tick %d: camera %d: GPU client frame != host client frame\n", t0 + r % nb, r / nb);
+                return 1;
+            }
+        max_err = std::max(max_err, max_abs_error(after, tx.frames.data(), (size_t)nrec * n));
     }
-    if (memcmp(host_frames.data(), c_states.data(), c_states.size()) != 0) { fprintf(stderr, "client states != host client frames\n"); return 1; }
-    if (max_err > cfg.threshold) { fprintf(stderr, "rebuilt frame off by %d > threshold\n", max_err); return 1; }
-    void *srv[] = {d_frames, d_sstates, d_off, d_pos, d_cw};
-    for (void *q : srv) OK(mi355_dev_free(server, q));
-    OK(mi355_dev_free(client, d_rx));
-    OK(mi355_dev_free(client, d_cstates));
-    if (int rc = act.close()) return rc;
+    if (within_threshold(max_err, ss)) return 1;
     if (int rc = chk.close()) return rc;
     if (int rc = wall.close()) return rc;
-    mi355_destroy(server);
-    mi355_destroy(client);
-    printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"width\": %d, \"height\": %d, \"ticks\": %d, "
-           "\"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d%s%s%s}\n",
-           S, w, h, T, changed, sent_bytes, mi355_wire_bytes(T * S, changed), (size_t)T * S * n, max_err, act.json().c_str(),
-           chk.json().c_str(), wall.json().c_str());
+    if (ss.close()) return 1;
+    const size_t changed = tx.changed, ref_bytes = mi355_wire_bytes(T * S, changed), raw = (size_t)T * S * n;
+    const std::string checks = act.json() + chk.json() + wall.json();
+    if (burst)
+        printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"burst\": %d, \"burst_client\": true, \"sender_calls\": %d, "
+               "\"receiver_calls\": %d, \"width\": %d, \"height\": %d, \"ticks\": %d, \"changed_bytes\": %zu, \"wire_bytes\": %zu, "
+               "\"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d%s}\n",
+               S, K, calls, calls, w, h, T, changed, sent_bytes, ref_bytes, raw, max_err, checks.c_str());
+    else
+        printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"width\": %d, \"height\": %d, \"ticks\": %d, "
+               "\"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d%s}\n",
+               S, w, h, T, changed, sent_bytes, ref_bytes, raw, max_err, checks.c_str());
     return 0;
 }
 
-// --compact --multi S --budget BYTES (see the head of the file)
+// --compact --multi S --budget BYTES: the sender holds every camera's record of a tick to BYTES bytes (a socket's share of the
+// link): the records larger than that are thinned to mi355_cwire_budget_entries(N, BYTES) entries by
+// mi355_cwire_budget_cwire_batch, which takes the sender's states back where it drops an entry.  Checked: every record written is
+// at most BYTES; each client's frame equals the sender's state after every tick; and once the input has stood still for enough
+// ticks every client's frame is within the threshold of the camera's frame at every byte -- what was postponed arrives.
 static int run_multi_budget(int w, int h, int T, int S, long bytes) {
     const size_t n = (size_t)3 * w * h;
     const size_t most = bytes >= 0 ? mi355_cwire_budget_entries(n, (size_t)bytes) : 0;
     if (most == 0) { fprintf(stderr, "--budget %ld holds no entry of a %dx%d frame\n", bytes, w, h); return 2; }
-    mi355_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.width = w; cfg.height = h; cfg.threshold = 20; cfg.max_batch = S; cfg.device = -1;
-    mi355_core *server = nullptr, *client = nullptr;
-    OK(mi355_create(&cfg, &server));
-    OK(mi355_create(&cfg, &client));
-    const size_t cw_cap = mi355_cwire_bytes_max(n, S);
-    void *d_frames = nullptr, *d_sstates = nullptr, *d_off = nullptr, *d_pos = nullptr, *d_cw = nullptr;   // server
-    void *d_thr = nullptr, *d_ooff = nullptr, *d_opos = nullptr, *d_out = nullptr;
-    void *d_rx = nullptr, *d_cstates = nullptr;                                                              // client
-    OK(mi355_dev_alloc(server, &d_frames, (size_t)S * n));
-    OK(mi355_dev_alloc(server, &d_sstates, (size_t)S * n));
-    OK(mi355_dev_alloc(server, &d_off, sizeof(uint32_t) * (S + 1)));
-    OK(mi355_dev_alloc(server, &d_pos, sizeof(uint64_t) * (S + 1)));
-    OK(mi355_dev_alloc(server, &d_cw, cw_cap));
-    OK(mi355_dev_alloc(server, &d_thr, sizeof(uint32_t) * S));
-    OK(mi355_dev_alloc(server, &d_ooff, sizeof(uint32_t) * (S + 1)));
-    OK(mi355_dev_alloc(server, &d_opos, sizeof(uint64_t) * (S + 1)));
-    OK(mi355_dev_alloc(server, &d_out, cw_cap));
-    OK(mi355_dev_alloc(client, &d_rx, cw_cap));
-    OK(mi355_dev_alloc(client, &d_cstates, (size_t)S * n));
-    int fds[2];
-    if (pipe(fds) != 0) return 1;
-    std::vector<uint8_t> bases((size_t)S * n), frames((size_t)S * n), s_states((size_t)S * n), c_states((size_t)S * n), cw_host(cw_cap),
-        rx(cw_cap);
-    for (int s = 0; s < S; s++)
-        for (size_t i = 0; i < n; i++) bases[(size_t)s * n + i] = (uint8_t)(40 + (i * 7 + (size_t)s * 31) % 150);
-    OK(mi355_upload(server, d_sstates, bases.data(), bases.size()));
-    if (!through_pipe(fds[1], fds[0], bases.data(), c_states.data(), bases.size())) return 1;
-    OK(mi355_upload(client, d_cstates, c_states.data(), c_states.size()));
-    std::vector<uint8_t> base(n), frame(n);
+    Session ss(w, h);
+    Cameras cams(S, w, h);
+    Sender tx;
+    Receiver rcv;
+    if (tx.open(ss, S, 1) || rcv.open(ss, S, S, S)) return 1;
+    void *d_thr = ss.dev(tx.core, sizeof(uint32_t) * S), *d_ooff = ss.dev(tx.core, sizeof(uint32_t) * (S + 1));
+    void *d_opos = ss.dev(tx.core, sizeof(uint64_t) * (S + 1)), *d_out = ss.dev(tx.core, tx.cap);
+    if (!ss.ok()) return 1;
+    if (cams.start(ss, tx, rcv, rcv.states.data())) return 1;
     std::vector<uint32_t> counts(S), escapes(S), budget(S), thr(S);
     std::vector<uint64_t> pos(S + 1);
     size_t sent_bytes = 0, largest = 0;
-    int thinned = 0, max_thr = cfg.threshold, max_err = 0, still = 0;
+    int thinned = 0, max_thr = ss.threshold, max_err = 0, still = 0;
     // T ticks of moving input, then the last frames again and again until nothing is held back any more: what a budget
     // postponed must arrive.  A tick sends up to `most` of a camera's pending entries, so N / most still ticks suffice -- unless
     // more than `most` of them share one magnitude (then no threshold separates them; the synthetic input has no such group).
     const int still_limit = (int)(2 * ((n + most - 1) / most)) + 2;
     for (int t = 0;; t++) {
-        if (t < T) {
-            for (int s = 0; s < S; s++) {   // camera s: its own base, its block a few steps ahead of its neighbour's
-                memcpy(base.data(), &bases[(size_t)s * n], n);
-                make_frame(frame, base, w, h, t + 5 * s);
-                memcpy(&frames[(size_t)s * n], frame.data(), n);
-            }
-            OK(mi355_upload(server, d_frames, frames.data(), frames.size()));
-        }
+        if (t < T) cams.fill(tx.frames.data(), t, 1);
         // ---- server: one tick -> S records, their headers, the records above the budget thinned
-        OK(mi355_diff_multi_cwire_batch(server, d_frames, d_sstates, n, S, d_off, d_pos, d_cw, cw_cap));
-        OK(mi355_download(server, pos.data(), d_pos, sizeof(uint64_t) * (S + 1)));
-        if (pos[S] > cw_cap) { fprintf(stderr, "compact stream larger than its bound\n"); return 1; }
+        if (tx.step(1, false)) return 1;
         bool over = false;
         for (int s = 0; s < S; s++) {
-            uint32_t hdr[2];
-            OK(mi355_download(server, hdr, (const uint8_t *)d_cw + pos[s], sizeof hdr));
-            counts[s] = hdr[0];
-            escapes[s] = hdr[1];
-            budget[s] = pos[s + 1] - pos[s] > (uint64_t)bytes ? (uint32_t)most : UINT32_MAX;
+            memcpy(&counts[s], &tx.bytes[tx.pos[s]], 4);
+            memcpy(&escapes[s], &tx.bytes[tx.pos[s] + 4], 4);
+            budget[s] = tx.pos[s + 1] - tx.pos[s] > (uint64_t)bytes ? (uint32_t)most : UINT32_MAX;
             if (budget[s] != UINT32_MAX) { over = true; thinned++; }
         }
-        OK(mi355_cwire_budget_cwire_batch(server, d_cw, counts.data(), escapes.data(), d_sstates, n, S, budget.data(), d_thr, d_ooff,
-                                          d_opos, d_out, cw_cap));
-        OK(mi355_download(server, pos.data(), d_opos, sizeof(uint64_t) * (S + 1)));
-        OK(mi355_download(server, thr.data(), d_thr, sizeof(uint32_t) * S));
-        if (pos[S] > cw_cap) { fprintf(stderr, "thinned stream larger than its bound\n"); return 1; }
+        OK(mi355_cwire_budget_cwire_batch(tx.core, tx.d_cw, counts.data(), escapes.data(), tx.d_states, n, S, budget.data(), d_thr, d_ooff,
+                                          d_opos, d_out, tx.cap));
+        OK(mi355_download(tx.core, pos.data(), d_opos, sizeof(uint64_t) * (S + 1)));
+        OK(mi355_download(tx.core, thr.data(), d_thr, sizeof(uint32_t) * S));
+        if (pos[S] > tx.cap) { fprintf(stderr, "thinned stream larger than its bound\n"); return 1; }
         for (int s = 0; s < S; s++) {   // check 1: every record that is written fits the socket's budget
             const size_t rb = (size_t)(pos[s + 1] - pos[s]);
             if (rb > (size_t)bytes) { fprintf(stderr, "tick %d: camera %d's record has %zu bytes > %ld\n", t, s, rb, bytes); return 1; }
             if (rb > largest) largest = rb;
             if ((int)thr[s] > max_thr) max_thr = (int)thr[s];
-            if ((budget[s] == UINT32_MAX) != ((int)thr[s] == cfg.threshold)) { fprintf(stderr, "tick %d: camera %d: threshold %u\n", t, s, thr[s]); return 1; }
+            if ((budget[s] == UINT32_MAX) != ((int)thr[s] == ss.threshold)) { fprintf(stderr, "tick %d: camera %d: threshold %u\n", t, s, thr[s]); return 1; }
         }
         const size_t cb = (size_t)pos[S];
-        OK(mi355_download(server, cw_host.data(), d_out, cb));
-        if (!through_pipe(fds[1], fds[0], cw_host.data(), rx.data(), cb)) return 1;
+        OK(mi355_download(tx.core, tx.bytes.data(), d_out, cb));
+        if (!ss.send(tx.bytes.data(), rcv.rx.data(), cb)) return 1;
         sent_bytes += cb;
         // ---- client: the headers as read from the stream, one upload, one call
-        size_t p = 0;
-        for (int s = 0; s < S; s++) {
-            if (p + 8 > cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
-            memcpy(&counts[s], rx.data() + p, 4);
-            memcpy(&escapes[s], rx.data() + p + 4, 4);
-            p += mi355_cwire_frame_bytes(counts[s], escapes[s]);
-        }
-        if (p != cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
-        OK(mi355_upload(client, d_rx, rx.data(), cb));
-        OK(mi355_apply_multi_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, d_cstates, n));
+        if (rcv.walk(0, cb, 0, S)) return 1;
+        OK(mi355_upload(rcv.core, rcv.d_rx, rcv.rx.data(), cb));
+        if (rcv.apply_tick()) return 1;
         // ---- check 2: each client's frame equals the sender's state after every tick
-        OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
-        OK(mi355_download(server, s_states.data(), d_sstates, s_states.size()));
-        if (memcmp(s_states.data(), c_states.data(), s_states.size()) != 0) {
-            fprintf(stderr, "tick %d: client states != server states\n", t);
-            return 1;
-        }
+        if (rcv.get_states() || states_equal(tx, rcv, t)) return 1;
         if (t + 1 < T) continue;
         // ---- check 3, once the input stands still: every client's frame within the threshold of the camera's, at every byte
-        max_err = 0;
-        for (size_t i = 0; i < c_states.size(); i++) {
-            const int e = abs((int)c_states[i] - (int)frames[i]);
-            if (e > max_err) max_err = e;
-        }
-        if (t >= T && !over && max_err <= cfg.threshold) break;
+        max_err = max_abs_error(rcv.states.data(), tx.frames.data(), (size_t)S * n);
+        if (t >= T && !over && max_err <= ss.threshold) break;
         if (t >= T) still++;
         if (still > still_limit) { fprintf(stderr, "held still for %d ticks and still off by %d > threshold\n", still, max_err); return 1; }
     }
-    void *srv[] = {d_frames, d_sstates, d_off, d_pos, d_cw, d_thr, d_ooff, d_opos, d_out};
-    for (void *q : srv) OK(mi355_dev_free(server, q));
-    OK(mi355_dev_free(client, d_rx));
-    OK(mi355_dev_free(client, d_cstates));
-    mi355_destroy(server);
-    mi355_destroy(client);
+    if (ss.close()) return 1;
     printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"budget_bytes\": %ld, \"budget_entries\": %zu, \"width\": %d, "
            "\"height\": %d, \"ticks\": %d, \"still_ticks\": %d, \"thinned_records\": %d, \"largest_record_bytes\": %zu, "
            "\"largest_threshold\": %d, \"records_within_budget\": true, \"states_equal_every_tick\": true, "
@@ -617,394 +746,124 @@ static int run_multi_budget(int w, int h, int T, int S, long bytes) {
     return 0;
 }
 
-// --compact --multi S --burst K (see the head of the file)
+// --compact --multi S --burst K: the sender buffers K ticks per camera (a recorder, a camera that catches up) and makes their
+// S * K records in ONE call, mi355_diff_multi_stream_cwire_batch: camera s's K records are one contiguous slice, one write()
+// per socket.  The receiver stages record (s, t) of every s back to back for tick t and applies the ticks with the same
+// mi355_apply_multi_cwire_batch; after every burst the states at both ends must be equal.
 static int run_multi_burst(int w, int h, int T, int S, int K) {
-    const size_t n = (size_t)3 * w * h;
-    mi355_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.width = w; cfg.height = h; cfg.threshold = 20; cfg.max_batch = S * K; cfg.device = -1;
-    mi355_core *server = nullptr, *client = nullptr;
-    OK(mi355_create(&cfg, &server));
-    cfg.max_batch = S;
-    OK(mi355_create(&cfg, &client));
-    const int B = S * K;
-    const size_t cw_cap = mi355_cwire_bytes_max(n, B), tick_cap = mi355_cwire_bytes_max(n, S);
-    void *d_frames = nullptr, *d_sstates = nullptr, *d_off = nullptr, *d_pos = nullptr, *d_cw = nullptr;   // server
-    void *d_rx = nullptr, *d_cstates = nullptr;                                                              // client
-    OK(mi355_dev_alloc(server, &d_frames, (size_t)B * n));
-    OK(mi355_dev_alloc(server, &d_sstates, (size_t)S * n));
-    OK(mi355_dev_alloc(server, &d_off, sizeof(uint32_t) * (B + 1)));
-    OK(mi355_dev_alloc(server, &d_pos, sizeof(uint64_t) * (B + 1)));
-    OK(mi355_dev_alloc(server, &d_cw, cw_cap));
-    OK(mi355_dev_alloc(client, &d_rx, tick_cap));
-    OK(mi355_dev_alloc(client, &d_cstates, (size_t)S * n));
-    int fds[2];
-    if (pipe(fds) != 0) return 1;
-    std::vector<uint8_t> bases((size_t)S * n), host_frames((size_t)S * n), frames((size_t)B * n), s_states((size_t)S * n),
-        c_states((size_t)S * n), cw_host(cw_cap), rx(cw_cap), stage(tick_cap);
-    for (int s = 0; s < S; s++)
-        for (size_t i = 0; i < n; i++) bases[(size_t)s * n + i] = (uint8_t)(40 + (i * 7 + (size_t)s * 31) % 150);
-    OK(mi355_upload(server, d_sstates, bases.data(), bases.size()));
-    if (!through_pipe(fds[1], fds[0], bases.data(), host_frames.data(), bases.size())) return 1;
-    OK(mi355_upload(client, d_cstates, host_frames.data(), host_frames.size()));
-    std::vector<uint8_t> base(n), frame(n);
-    std::vector<uint32_t> off(B + 1), counts(S), escapes(S);
-    std::vector<uint64_t> pos(B + 1);
-    std::vector<size_t> at(B), len(B);   // where record (s, t) lies in the received bytes, as the receiver found it
-    size_t sent_bytes = 0, changed = 0;
+    Session ss(w, h);
+    const size_t n = ss.n;
+    Cameras cams(S, w, h);
+    Sender tx;
+    Receiver rcv;
+    if (tx.open(ss, S, K) || rcv.open(ss, S, S, S)) return 1;
+    std::vector<uint8_t> host_frames((size_t)S * n), burst(tx.cap);   // a host client per camera; the bytes as the sockets gave them
+    std::vector<uint32_t> b_counts(S * K), b_escapes(S * K);
+    std::vector<size_t> b_at(S * K + 1);   // where record (s, t) lies in them, as the receiver found it
+    if (cams.start(ss, tx, rcv, host_frames.data())) return 1;
+    size_t sent_bytes = 0;
     int max_err = 0, calls = 0;
     for (int t0 = 0; t0 < T; t0 += K) {
-        const int nb = T - t0 < K ? T - t0 : K, nrec = S * nb;
-        for (int s = 0; s < S; s++) {   // camera s's nb frames, one behind the other
-            memcpy(base.data(), &bases[(size_t)s * n], n);
-            for (int k = 0; k < nb; k++) {
-                make_frame(frame, base, w, h, t0 + k + 5 * s);
-                memcpy(&frames[((size_t)s * nb + k) * n], frame.data(), n);
-            }
-        }
+        const int nb = T - t0 < K ? T - t0 : K;
+        cams.fill(tx.frames.data(), t0, nb);
         // ---- server: nb ticks of S cameras -> S * nb records in one call
-        OK(mi355_upload(server, d_frames, frames.data(), (size_t)nrec * n));
-        OK(mi355_diff_multi_stream_cwire_batch(server, d_frames, d_sstates, n, S, nb, d_off, d_pos, d_cw, cw_cap));
+        if (tx.step(nb, true)) return 1;
         calls++;
-        OK(mi355_download(server, off.data(), d_off, sizeof(uint32_t) * (nrec + 1)));
-        OK(mi355_download(server, pos.data(), d_pos, sizeof(uint64_t) * (nrec + 1)));
-        if (pos[nrec] > cw_cap) { fprintf(stderr, "compact stream larger than its bound\n"); return 1; }
-        const size_t cb = (size_t)pos[nrec];
-        OK(mi355_download(server, cw_host.data(), d_cw, cb));
-        changed += off[nrec];
         // ---- the sockets: camera s's slice [pos[s * nb], pos[(s + 1) * nb]) is one write
         for (int s = 0; s < S; s++) {
-            const size_t a = (size_t)pos[(size_t)s * nb], b = (size_t)pos[(size_t)(s + 1) * nb];
-            if (!through_pipe(fds[1], fds[0], cw_host.data() + a, rx.data() + a, b - a)) return 1;
+            const size_t a = (size_t)tx.pos[(size_t)s * nb], b = (size_t)tx.pos[(size_t)(s + 1) * nb];
+            if (!ss.send(tx.bytes.data() + a, burst.data() + a, b - a)) return 1;
         }
-        sent_bytes += cb;
+        sent_bytes += tx.cb;
         // ---- receiver: the records of every socket, found from their headers
-        size_t p = 0;
-        for (int r = 0; r < nrec; r++) {
-            if (p + 8 > cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
-            uint32_t c, e;
-            memcpy(&c, rx.data() + p, 4);
-            memcpy(&e, rx.data() + p + 4, 4);
-            at[r] = p;
-            len[r] = mi355_cwire_frame_bytes(c, e);
-            p += len[r];
-        }
-        if (p != cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
-        // ---- client: tick k = record (s, k) of every s back to back, one upload, one call
+        if (walk_records(burst.data(), 0, tx.cb, S * nb, b_counts.data(), b_escapes.data(), b_at.data())) return 1;
+        // ---- client: tick k = record (s, k) of every s back to back (the host client of camera s beside it), one upload, one call
         for (int k = 0; k < nb; k++) {
-            size_t q = 0;
-            for (int s = 0; s < S; s++) {
-                const int r = s * nb + k;
-                memcpy(stage.data() + q, rx.data() + at[r], len[r]);
-                memcpy(&counts[s], stage.data() + q, 4);
-                memcpy(&escapes[s], stage.data() + q + 4, 4);
-                size_t used = 0;   // ... and the host client of camera s beside it
-                OK(mi355_cwire_apply_host(&host_frames[(size_t)s * n], n, stage.data() + q, len[r], 1, &used));
-                if (used != len[r]) { fprintf(stderr, "stream framing broken\n"); return 1; }
-                q += len[r];
-            }
-            OK(mi355_upload(client, d_rx, stage.data(), q));
-            OK(mi355_apply_multi_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, d_cstates, n));
-            OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
-            if (memcmp(host_frames.data(), c_states.data(), c_states.size()) != 0) {
-                fprintf(stderr, "tick %d: client states != host client frames\n", t0 + k);
-                return 1;
-            }
+            const size_t q = rcv.stage(burst.data(), b_at.data(), nb, k, -1);
             for (int s = 0; s < S; s++)
-                for (size_t i = 0; i < n; i++) {
-                    const int e = abs((int)c_states[(size_t)s * n + i] - (int)frames[((size_t)s * nb + k) * n + i]);
-                    if (e > max_err) max_err = e;
-                }
+                if (host_apply(&host_frames[(size_t)s * n], n, rcv.rx.data(), rcv.at.data(), s)) return 1;
+            OK(mi355_upload(rcv.core, rcv.d_rx, rcv.rx.data(), q));
+            if (rcv.apply_tick() || rcv.get_states()) return 1;
+            if (same(host_frames.data(), rcv.states.data(), rcv.states.size(), "receiver states != host client frames", t0 + k)) return 1;
+            for (int s = 0; s < S; s++)
+                max_err = std::max(max_err, max_abs_error(&rcv.states[(size_t)s * n], &tx.frames[((size_t)s * nb + k) * n], n));
         }
         // ---- the states at both ends
-        OK(mi355_download(server, s_states.data(), d_sstates, s_states.size()));
-        if (memcmp(s_states.data(), c_states.data(), s_states.size()) != 0) {
-            fprintf(stderr, "burst at tick %d: client states != server states\n", t0);
-            return 1;
-        }
+        if (states_equal(tx, rcv, t0)) return 1;
     }
-    if (max_err > cfg.threshold) { fprintf(stderr, "rebuilt frame off by %d > threshold\n", max_err); return 1; }
-    void *srv[] = {d_frames, d_sstates, d_off, d_pos, d_cw};
-    for (void *q : srv) OK(mi355_dev_free(server, q));
-    OK(mi355_dev_free(client, d_rx));
-    OK(mi355_dev_free(client, d_cstates));
-    mi355_destroy(server);
-    mi355_destroy(client);
+    if (within_threshold(max_err, ss) || ss.close()) return 1;
     printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"burst\": %d, \"sender_calls\": %d, \"width\": %d, \"height\": %d, "
            "\"ticks\": %d, \"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, "
            "\"max_abs_error\": %d}\n",
-           S, K, calls, w, h, T, changed, sent_bytes, mi355_wire_bytes(T * S, changed), (size_t)T * S * n, max_err);
+           S, K, calls, w, h, T, tx.changed, sent_bytes, mi355_wire_bytes(T * S, tx.changed), (size_t)T * S * n, max_err);
     return 0;
 }
 
-// --compact --multi S --burst K --burst-client (see the head of the file)
-static int run_multi_burst_client(int w, int h, int T, int S, int K, int activity, bool check, int wall_k) {
-    const size_t n = (size_t)3 * w * h;
-    mi355_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.width = w; cfg.height = h; cfg.threshold = 20; cfg.max_batch = S * K; cfg.device = -1;
-    mi355_core *server = nullptr, *client = nullptr;
-    OK(mi355_create(&cfg, &server));
-    OK(mi355_create(&cfg, &client));
-    const int B = S * K;
-    const size_t cw_cap = mi355_cwire_bytes_max(n, B);
-    void *d_frames = nullptr, *d_sstates = nullptr, *d_off = nullptr, *d_pos = nullptr, *d_cw = nullptr;   // server
-    void *d_rx = nullptr, *d_cstates = nullptr, *d_shown = nullptr;                                         // client
-    OK(mi355_dev_alloc(server, &d_frames, (size_t)B * n));
-    OK(mi355_dev_alloc(server, &d_sstates, (size_t)S * n));
-    OK(mi355_dev_alloc(server, &d_off, sizeof(uint32_t) * (B + 1)));
-    OK(mi355_dev_alloc(server, &d_pos, sizeof(uint64_t) * (B + 1)));
-    OK(mi355_dev_alloc(server, &d_cw, cw_cap));
-    OK(mi355_dev_alloc(client, &d_rx, cw_cap));
-    OK(mi355_dev_alloc(client, &d_cstates, (size_t)S * n));
-    OK(mi355_dev_alloc(client, &d_shown, (size_t)B * n));
-    ActivityCheck act;
-    if (activity)
-        if (int rc = act.open(client, w, h, activity, S)) return rc;
-    RecordCheck chk;
-    if (check)
-        if (int rc = chk.open(client, n, B)) return rc;
-    WallCheck wall;
-    if (wall_k)
-        if (int rc = wall.open(client, w, h, wall_k, S)) return rc;
-    int fds[2];
-    if (pipe(fds) != 0) return 1;
-    std::vector<uint8_t> bases((size_t)S * n), host_frames((size_t)S * n), frames((size_t)B * n), s_states((size_t)S * n),
-        c_states((size_t)S * n), shown((size_t)B * n), host_shown((size_t)B * n), cw_host(cw_cap), rx(cw_cap);
-    for (int s = 0; s < S; s++)
-        for (size_t i = 0; i < n; i++) bases[(size_t)s * n + i] = (uint8_t)(40 + (i * 7 + (size_t)s * 31) % 150);
-    OK(mi355_upload(server, d_sstates, bases.data(), bases.size()));
-    if (!through_pipe(fds[1], fds[0], bases.data(), host_frames.data(), bases.size())) return 1;
-    OK(mi355_upload(client, d_cstates, host_frames.data(), host_frames.size()));
-    if (int rc = wall.full(d_cstates)) return rc;
-    std::vector<uint8_t> base(n), frame(n), before(check ? host_frames : std::vector<uint8_t>());   // (before: the states a burst finds)
-    std::vector<uint32_t> off(B + 1), counts(B), escapes(B);
-    std::vector<uint64_t> pos(B + 1);
-    size_t sent_bytes = 0, changed = 0;
-    int max_err = 0, calls = 0;
-    for (int t0 = 0; t0 < T; t0 += K) {
-        const int nb = T - t0 < K ? T - t0 : K, nrec = S * nb;
-        for (int s = 0; s < S; s++) {   // camera s's nb frames, one behind the other
-            memcpy(base.data(), &bases[(size_t)s * n], n);
-            for (int k = 0; k < nb; k++) {
-                make_frame(frame, base, w, h, t0 + k + 5 * s);
-                memcpy(&frames[((size_t)s * nb + k) * n], frame.data(), n);
-            }
-        }
-        // ---- server: nb ticks of S cameras -> S * nb records in one call
-        OK(mi355_upload(server, d_frames, frames.data(), (size_t)nrec * n));
-        OK(mi355_diff_multi_stream_cwire_batch(server, d_frames, d_sstates, n, S, nb, d_off, d_pos, d_cw, cw_cap));
-        calls++;
-        OK(mi355_download(server, off.data(), d_off, sizeof(uint32_t) * (nrec + 1)));
-        OK(mi355_download(server, pos.data(), d_pos, sizeof(uint64_t) * (nrec + 1)));
-        if (pos[nrec] > cw_cap) { fprintf(stderr, "compact stream larger than its bound\n"); return 1; }
-        const size_t cb = (size_t)pos[nrec];
-        OK(mi355_download(server, cw_host.data(), d_cw, cb));
-        changed += off[nrec];
-        // ---- the sockets: camera s's slice is one write; the receiver reads its nb records (header, then the rest) behind
-        // the slice of camera s - 1 and uploads the slice as it came, stream-major, nothing re-staged
-        size_t p = 0;
-        for (int s = 0; s < S; s++) {
-            const size_t a = (size_t)pos[(size_t)s * nb], b = (size_t)pos[(size_t)(s + 1) * nb];
-            if (a != p) { fprintf(stderr, "stream framing broken\n"); return 1; }
-            if (!through_pipe(fds[1], fds[0], cw_host.data() + a, rx.data() + a, b - a)) return 1;
-            for (int k = 0; k < nb; k++) {
-                const int r = s * nb + k;
-                if (p + 8 > b) { fprintf(stderr, "stream framing broken\n"); return 1; }
-                memcpy(&counts[r], rx.data() + p, 4);
-                memcpy(&escapes[r], rx.data() + p + 4, 4);
-                size_t used = 0;   // the host client of camera s beside it: the frame it shows after tick k
-                OK(mi355_cwire_apply_host(&host_frames[(size_t)s * n], n, rx.data() + p, b - p, 1, &used));
-                if (used != mi355_cwire_frame_bytes(counts[r], escapes[r])) { fprintf(stderr, "stream framing broken\n"); return 1; }
-                memcpy(&host_shown[(size_t)r * n], &host_frames[(size_t)s * n], n);
-                p += used;
-            }
-            if (p != b) { fprintf(stderr, "stream framing broken\n"); return 1; }
-            if (b > a) OK(mi355_upload(client, (uint8_t *)d_rx + a, rx.data() + a, b - a));
-        }
-        sent_bytes += cb;
-        if (int rc = act.run(d_rx, rx.data(), counts.data(), escapes.data(), nb, t0)) return rc;
-        if (int rc = chk.run(d_rx, rx.data(), cb, counts.data(), escapes.data(), nrec, t0)) return rc;
-        // ---- client: the whole burst in one call, every frame in between into d_shown
-        OK(mi355_apply_multi_stream_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, nb, d_cstates, n, d_shown, n));
-        if (int rc = wall.update(d_rx, counts.data(), escapes.data(), nb, d_cstates)) return rc;
-        OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
-        if (int rc = wall.compare(c_states.data(), t0 + nb - 1)) return rc;
-        OK(mi355_download(client, shown.data(), d_shown, (size_t)nrec * n));
-        for (int r = 0; r < nrec && check; r++)   // record (s, k) turned the frame after record (s, k - 1) into its own
-            if (int rc = chk.applied(r, r % nb ? &shown[(size_t)(r - 1) * n] : &before[(size_t)(r / nb) * n], &shown[(size_t)r * n], t0)) return rc;
-        if (check) before = c_states;
-        OK(mi355_download(server, s_states.data(), d_sstates, s_states.size()));
-        if (memcmp(s_states.data(), c_states.data(), s_states.size()) != 0) {
-            fprintf(stderr, "burst at tick %d: client states != server states\n", t0);
-            return 1;
-        }
-        for (int r = 0; r < nrec; r++)
-            if (memcmp(&shown[(size_t)r * n], &host_shown[(size_t)r * n], n) != 0) {
-                fprintf(stderr, "burst at tick %d: camera %d, tick %d: GPU client frame != host client frame\n", t0, r / nb, t0 + r % nb);
-                return 1;
-            }
-        for (size_t i = 0; i < (size_t)nrec * n; i++) {
-            const int e = abs((int)shown[i] - (int)frames[i]);
-            if (e > max_err) max_err = e;
-        }
-    }
-    if (max_err > cfg.threshold) { fprintf(stderr, "rebuilt frame off by %d > threshold\n", max_err); return 1; }
-    void *srv[] = {d_frames, d_sstates, d_off, d_pos, d_cw};
-    for (void *q : srv) OK(mi355_dev_free(server, q));
-    void *cli[] = {d_rx, d_cstates, d_shown};
-    for (void *q : cli) OK(mi355_dev_free(client, q));
-    if (int rc = act.close()) return rc;
-    if (int rc = chk.close()) return rc;
-    if (int rc = wall.close()) return rc;
-    mi355_destroy(server);
-    mi355_destroy(client);
-    printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"burst\": %d, \"burst_client\": true, \"sender_calls\": %d, "
-           "\"receiver_calls\": %d, \"width\": %d, \"height\": %d, \"ticks\": %d, \"changed_bytes\": %zu, \"wire_bytes\": %zu, "
-           "\"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d%s%s%s}\n",
-           S, K, calls, calls, w, h, T, changed, sent_bytes, mi355_wire_bytes(T * S, changed), (size_t)T * S * n, max_err,
-           act.json().c_str(), chk.json().c_str(), wall.json().c_str());
-    return 0;
-}
-
-// --compact --multi S --burst K --coalesce (see the head of the file)
+// --compact --multi S --burst K --coalesce: a relay between the two ends that forwards at 1/K of the rate (a slow link, a
+// time-lapse recorder, a video wall).  It holds no frame: it uploads every camera's slice as it came off its socket, makes
+// ONE record per camera of the burst with mi355_cwire_coalesce_cwire_batch, and forwards those S records; the receiver applies
+// them with one mi355_apply_multi_cwire_batch.  After every burst each camera's state at the receiver must equal the frame of
+// a host client (mi355_cwire_apply_host) that applied all K original records, and the sender's state.  The line also says how
+// many bytes the relay received and how many it forwarded.
 static int run_multi_burst_coalesce(int w, int h, int T, int S, int K) {
-    const size_t n = (size_t)3 * w * h;
-    mi355_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.width = w; cfg.height = h; cfg.threshold = 20; cfg.max_batch = S * K; cfg.device = -1;
-    mi355_core *server = nullptr, *relay = nullptr, *client = nullptr;
-    OK(mi355_create(&cfg, &server));
-    OK(mi355_create(&cfg, &relay));
-    cfg.max_batch = S;
-    OK(mi355_create(&cfg, &client));
-    const int B = S * K;
-    const size_t cw_cap = mi355_cwire_bytes_max(n, B), one_cap = mi355_cwire_bytes_max(n, S);
-    void *d_frames = nullptr, *d_sstates = nullptr, *d_off = nullptr, *d_pos = nullptr, *d_cw = nullptr;   // server
-    void *d_in = nullptr, *d_roff = nullptr, *d_rpos = nullptr, *d_fwd = nullptr;                           // relay
-    void *d_rx = nullptr, *d_cstates = nullptr;                                                              // client
-    OK(mi355_dev_alloc(server, &d_frames, (size_t)B * n));
-    OK(mi355_dev_alloc(server, &d_sstates, (size_t)S * n));
-    OK(mi355_dev_alloc(server, &d_off, sizeof(uint32_t) * (B + 1)));
-    OK(mi355_dev_alloc(server, &d_pos, sizeof(uint64_t) * (B + 1)));
-    OK(mi355_dev_alloc(server, &d_cw, cw_cap));
-    OK(mi355_dev_alloc(relay, &d_in, cw_cap));
-    OK(mi355_dev_alloc(relay, &d_roff, sizeof(uint32_t) * (S + 1)));
-    OK(mi355_dev_alloc(relay, &d_rpos, sizeof(uint64_t) * (S + 1)));
-    OK(mi355_dev_alloc(relay, &d_fwd, one_cap));
-    OK(mi355_dev_alloc(client, &d_rx, one_cap));
-    OK(mi355_dev_alloc(client, &d_cstates, (size_t)S * n));
-    int fds[2];
-    if (pipe(fds) != 0) return 1;
-    std::vector<uint8_t> bases((size_t)S * n), host_frames((size_t)S * n), frames((size_t)B * n), s_states((size_t)S * n),
-        c_states((size_t)S * n), cw_host(cw_cap), relay_rx(cw_cap), fwd(one_cap), rx(one_cap);
-    for (int s = 0; s < S; s++)
-        for (size_t i = 0; i < n; i++) bases[(size_t)s * n + i] = (uint8_t)(40 + (i * 7 + (size_t)s * 31) % 150);
-    OK(mi355_upload(server, d_sstates, bases.data(), bases.size()));
-    if (!through_pipe(fds[1], fds[0], bases.data(), host_frames.data(), bases.size())) return 1;
-    OK(mi355_upload(client, d_cstates, host_frames.data(), host_frames.size()));
-    std::vector<uint8_t> base(n), frame(n);
-    std::vector<uint32_t> off(B + 1), counts(B), escapes(B), roff(S + 1), ocounts(S), oescapes(S);
-    std::vector<uint64_t> pos(B + 1), rpos(S + 1);
-    size_t received = 0, forwarded = 0, changed = 0, kept = 0;
+    Session ss(w, h);
+    const size_t n = ss.n;
+    Cameras cams(S, w, h);
+    Sender tx;
+    Receiver relay, rcv;
+    if (tx.open(ss, S, K) || relay.open(ss, S, S * K, S * K, false) || rcv.open(ss, S, S, S)) return 1;
+    void *d_roff = ss.dev(relay.core, sizeof(uint32_t) * (S + 1)), *d_rpos = ss.dev(relay.core, sizeof(uint64_t) * (S + 1));
+    void *d_fwd = ss.dev(relay.core, rcv.cap);
+    if (!ss.ok()) return 1;
+    std::vector<uint8_t> host_frames((size_t)S * n), fwd(rcv.cap);
+    std::vector<uint32_t> roff(S + 1);
+    std::vector<uint64_t> rpos(S + 1);
+    if (cams.start(ss, tx, rcv, host_frames.data())) return 1;
+    size_t received = 0, forwarded = 0, kept = 0;
     int max_err = 0, calls = 0;
     for (int t0 = 0; t0 < T; t0 += K) {
-        const int nb = T - t0 < K ? T - t0 : K, nrec = S * nb;
-        for (int s = 0; s < S; s++) {   // camera s's nb frames, one behind the other
-            memcpy(base.data(), &bases[(size_t)s * n], n);
-            for (int k = 0; k < nb; k++) {
-                make_frame(frame, base, w, h, t0 + k + 5 * s);
-                memcpy(&frames[((size_t)s * nb + k) * n], frame.data(), n);
-            }
-        }
+        const int nb = T - t0 < K ? T - t0 : K;
+        cams.fill(tx.frames.data(), t0, nb);
         // ---- server: nb ticks of S cameras -> S * nb records in one call
-        OK(mi355_upload(server, d_frames, frames.data(), (size_t)nrec * n));
-        OK(mi355_diff_multi_stream_cwire_batch(server, d_frames, d_sstates, n, S, nb, d_off, d_pos, d_cw, cw_cap));
-        OK(mi355_download(server, off.data(), d_off, sizeof(uint32_t) * (nrec + 1)));
-        OK(mi355_download(server, pos.data(), d_pos, sizeof(uint64_t) * (nrec + 1)));
-        if (pos[nrec] > cw_cap) { fprintf(stderr, "compact stream larger than its bound\n"); return 1; }
-        const size_t cb = (size_t)pos[nrec];
-        OK(mi355_download(server, cw_host.data(), d_cw, cb));
-        changed += off[nrec];
-        // ---- the sockets into the relay: camera s's slice is one write; the relay reads the headers, uploads the slice as it
-        // came; a host client beside it applies all nb original records of the camera
-        size_t p = 0;
-        for (int s = 0; s < S; s++) {
-            const size_t a = (size_t)pos[(size_t)s * nb], b = (size_t)pos[(size_t)(s + 1) * nb];
-            if (a != p) { fprintf(stderr, "stream framing broken\n"); return 1; }
-            if (!through_pipe(fds[1], fds[0], cw_host.data() + a, relay_rx.data() + a, b - a)) return 1;
-            for (int k = 0; k < nb; k++) {
-                const int r = s * nb + k;
-                if (p + 8 > b) { fprintf(stderr, "stream framing broken\n"); return 1; }
-                memcpy(&counts[r], relay_rx.data() + p, 4);
-                memcpy(&escapes[r], relay_rx.data() + p + 4, 4);
-                size_t used = 0;
-                OK(mi355_cwire_apply_host(&host_frames[(size_t)s * n], n, relay_rx.data() + p, b - p, 1, &used));
-                if (used != mi355_cwire_frame_bytes(counts[r], escapes[r])) { fprintf(stderr, "stream framing broken\n"); return 1; }
-                p += used;
-            }
-            if (p != b) { fprintf(stderr, "stream framing broken\n"); return 1; }
-            if (b > a) OK(mi355_upload(relay, (uint8_t *)d_in + a, relay_rx.data() + a, b - a));
-        }
-        received += cb;
+        if (tx.step(nb, true)) return 1;
+        // ---- the sockets into the relay; a host client beside it applies all nb original records of every camera
+        if (slices_to_node(ss, tx, relay, nb, host_frames.data(), nullptr)) return 1;
+        received += tx.cb;
         // ---- relay: the burst -> one record per camera, in one call; no frame exists here
-        OK(mi355_cwire_coalesce_cwire_batch(relay, d_in, counts.data(), escapes.data(), S, nb, d_roff, d_rpos, d_fwd, one_cap));
+        OK(mi355_cwire_coalesce_cwire_batch(relay.core, relay.d_rx, relay.counts.data(), relay.escapes.data(), S, nb, d_roff, d_rpos,
+                                            d_fwd, rcv.cap));
         calls++;
-        OK(mi355_download(relay, roff.data(), d_roff, sizeof(uint32_t) * (S + 1)));
-        OK(mi355_download(relay, rpos.data(), d_rpos, sizeof(uint64_t) * (S + 1)));
-        if (rpos[S] > one_cap) { fprintf(stderr, "coalesced stream larger than its bound\n"); return 1; }
+        OK(mi355_download(relay.core, roff.data(), d_roff, sizeof(uint32_t) * (S + 1)));
+        OK(mi355_download(relay.core, rpos.data(), d_rpos, sizeof(uint64_t) * (S + 1)));
+        if (rpos[S] > rcv.cap) { fprintf(stderr, "coalesced stream larger than its bound\n"); return 1; }
         const size_t fb = (size_t)rpos[S];
-        OK(mi355_download(relay, fwd.data(), d_fwd, fb));
+        OK(mi355_download(relay.core, fwd.data(), d_fwd, fb));
         kept += roff[S];
         // ---- the sockets out of the relay, one record per camera; the receiver finds them from their headers
-        if (!through_pipe(fds[1], fds[0], fwd.data(), rx.data(), fb)) return 1;
+        if (!ss.send(fwd.data(), rcv.rx.data(), fb)) return 1;
         forwarded += fb;
-        p = 0;
-        for (int s = 0; s < S; s++) {
-            if (p + 8 > fb) { fprintf(stderr, "forwarded framing broken\n"); return 1; }
-            memcpy(&ocounts[s], rx.data() + p, 4);
-            memcpy(&oescapes[s], rx.data() + p + 4, 4);
-            p += mi355_cwire_frame_bytes(ocounts[s], oescapes[s]);
-        }
-        if (p != fb) { fprintf(stderr, "forwarded framing broken\n"); return 1; }
+        if (rcv.walk(0, fb, 0, S)) return 1;
         // ---- receiver: one call per burst
-        OK(mi355_upload(client, d_rx, rx.data(), fb));
-        OK(mi355_apply_multi_cwire_batch(client, d_rx, ocounts.data(), oescapes.data(), S, d_cstates, n));
-        OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
-        OK(mi355_download(server, s_states.data(), d_sstates, s_states.size()));
+        OK(mi355_upload(rcv.core, rcv.d_rx, rcv.rx.data(), fb));
+        if (rcv.apply_tick() || rcv.get_states()) return 1;
+        // ---- checks
         for (int s = 0; s < S; s++)
-            if (memcmp(&host_frames[(size_t)s * n], &c_states[(size_t)s * n], n) != 0) {
-                fprintf(stderr, "burst at tick %d: camera %d: receiver state != host client that applied all %d records\n", t0, s, nb);
+            if (memcmp(&host_frames[(size_t)s * n], &rcv.states[(size_t)s * n], n) != 0) {
+                fprintf(stderr, "tick %d: camera %d: receiver state != host client that applied all %d records\n", t0, s, nb);
                 return 1;
             }
-        if (memcmp(s_states.data(), c_states.data(), s_states.size()) != 0) {
-            fprintf(stderr, "burst at tick %d: receiver states != server states\n", t0);
-            return 1;
-        }
+        if (states_equal(tx, rcv, t0)) return 1;
         for (int s = 0; s < S; s++)
-            for (size_t i = 0; i < n; i++) {
-                const int e = abs((int)c_states[(size_t)s * n + i] - (int)frames[((size_t)s * nb + nb - 1) * n + i]);
-                if (e > max_err) max_err = e;
-            }
+            max_err = std::max(max_err, max_abs_error(&rcv.states[(size_t)s * n], &tx.frames[((size_t)s * nb + nb - 1) * n], n));
     }
-    if (max_err > cfg.threshold) { fprintf(stderr, "rebuilt frame off by %d > threshold\n", max_err); return 1; }
-    void *srv[] = {d_frames, d_sstates, d_off, d_pos, d_cw};
-    for (void *q : srv) OK(mi355_dev_free(server, q));
-    void *rel[] = {d_in, d_roff, d_rpos, d_fwd};
-    for (void *q : rel) OK(mi355_dev_free(relay, q));
-    OK(mi355_dev_free(client, d_rx));
-    OK(mi355_dev_free(client, d_cstates));
-    mi355_destroy(server);
-    mi355_destroy(relay);
-    mi355_destroy(client);
+    if (within_threshold(max_err, ss) || ss.close()) return 1;
     printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"burst\": %d, \"coalesce\": true, \"relay_calls\": %d, "
            "\"width\": %d, \"height\": %d, \"ticks\": %d, \"changed_bytes\": %zu, \"coalesced_entries\": %zu, "
            "\"relay_received_bytes\": %zu, \"relay_forwarded_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d}\n",
-           S, K, calls, w, h, T, changed, kept, received, forwarded, (size_t)T * S * n, max_err);
+           S, K, calls, w, h, T, tx.changed, kept, received, forwarded, (size_t)T * S * n, max_err);
     return 0;
 }
 
-// --compact --per-frame (see the head of the file)
 namespace {
 struct Expected {   // the plain path's client frames, in order, from the sender to the receiver thread
     std::mutex m;
@@ -1022,7 +881,7 @@ struct Expected {   // the plain path's client frames, in order, from the sender
         return f;
     }
 };
-struct Receiver {
+struct FrameReceiver {
     int fd, frames;
     size_t n;
     Expected *expected;
@@ -1060,50 +919,47 @@ struct Receiver {
 };
 }  // namespace
 
+// --compact --per-frame: the per-frame server, one host frame per call and no device pointer in sight.  The sender feeds
+// host frames through mi355_pipe_submit_cwire, four in flight, and writes each frame's record to the pipe with ONE write()
+// from the pinned buffer it arrived in; the receiver -- a thread with no core -- reads header and body, applies the record
+// with mi355_cwire_apply_host and compares its frame, frame by frame, with that of a host client of the plain path
+// (mi355_exec on a second core: frame[xs[i]] += diff[i], client/opencv.cpp:64-66).
 static int run_per_frame(int w, int h, int T) {
-    const size_t n = (size_t)3 * w * h;
     const int depth = 4;
-    mi355_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.width = w; cfg.height = h; cfg.threshold = 20; cfg.max_batch = 1; cfg.device = -1;
-    mi355_core *server = nullptr, *plain = nullptr;
-    OK(mi355_create(&cfg, &server));
-    OK(mi355_create(&cfg, &plain));
-    std::vector<uint8_t> base(n), frame(n), p_frame(n), s_state(n);
-    for (size_t i = 0; i < n; i++) base[i] = (uint8_t)(40 + (i * 7) % 150);
-    OK(mi355_set_state(server, base.data()));
-    OK(mi355_set_state(plain, base.data()));
+    Session ss(w, h);
+    const size_t n = ss.n, cap = mi355_cwire_bytes_max(n, 1);
+    Cameras cam(1, w, h);
+    mi355_core *server = ss.core(1), *plain = ss.core(1);
+    if (!ss.ok()) return 1;
+    std::vector<uint8_t> frame(n), p_frame(cam.bases), s_state(n);
+    OK(mi355_set_state(server, cam.bases.data()));
+    OK(mi355_set_state(plain, cam.bases.data()));
     OK(mi355_prepare(server, MI355_PREPARE_EXEC_CWIRE));
-    p_frame = base;
-    const size_t cap = mi355_cwire_bytes_max(n, 1);
-    void *h_frame[depth], *h_rec[depth], *p_in = nullptr, *p_xs = nullptr;
+    void *h_frame[depth], *h_rec[depth];
     for (int i = 0; i < depth; i++) {
-        OK(mi355_host_alloc(&h_frame[i], n));
-        OK(mi355_host_alloc(&h_rec[i], cap));
+        h_frame[i] = ss.pinned(n);
+        h_rec[i] = ss.pinned(cap);
     }
-    OK(mi355_host_alloc(&p_in, n));
-    OK(mi355_host_alloc(&p_xs, n * sizeof(int32_t)));
-    int fds[2];
-    if (pipe(fds) != 0) return 1;
+    void *p_in = ss.pinned(n), *p_xs = ss.pinned(n * sizeof(int32_t));
+    if (!ss.ok()) return 1;
     OK(mi355_pipe_open(server, depth));
     // (from here to receiver.join() an error ends the loop, not the function: the thread is joined first)
     Expected expected;
-    Receiver rx;
-    rx.fd = fds[0]; rx.frames = T; rx.n = n; rx.expected = &expected;
+    FrameReceiver rx;
+    rx.fd = ss.fds[0]; rx.frames = T; rx.n = n; rx.expected = &expected;
     signal(SIGPIPE, SIG_IGN);   // (a write to a pipe the receiver has closed returns an error)
-    std::thread receiver(&Receiver::run, &rx);
-    bool ok = true;
+    std::thread receiver(&FrameReceiver::run, &rx);
     auto send = [&](const void *p, size_t len) {   // ONE write per record; the loop only serves a short write
         const uint8_t *b = (const uint8_t *)p;
         while (len) {
-            const ssize_t k = write(fds[1], b, len);
+            const ssize_t k = write(ss.fds[1], b, len);
             if (k <= 0) return false;
             b += k;
             len -= (size_t)k;
         }
         return true;
     };
-    ok = send(base.data(), n);   // threads.cpp:220
+    const bool ok = send(cam.bases.data(), n);   // threads.cpp:220
     int64_t tickets[depth];
     size_t changed = 0, sent_bytes = 0;
     int rc = 0;
@@ -1117,31 +973,25 @@ static int run_per_frame(int w, int h, int T) {
         if (!send(h_rec[t % depth], len)) { fprintf(stderr, "write failed\n"); return 1; }
         return 0;
     };
-    for (int t = 0; t < T && ok && !rc; t++) {
-        if (t >= depth) rc = finish(t - depth);
-        if (rc) break;
-        make_frame(frame, base, w, h, t);
+    auto submit = [&](int t) -> int {
+        cam.fill(frame.data(), t, 1);
         // the plain path beside it: mi355_exec on its own core, and its host client
         memcpy(p_in, frame.data(), n);
         uint32_t pos = 0;
-        if (mi355_exec(plain, (uint8_t *)p_in, nullptr, nullptr, &pos, (int32_t *)p_xs) != MI355_OK) {
-            fprintf(stderr, "mi355_exec failed: %s\n", mi355_last_error());
-            rc = 1;
-            break;
-        }
+        OK(mi355_exec(plain, (uint8_t *)p_in, nullptr, nullptr, &pos, (int32_t *)p_xs));
         for (uint32_t i = 0; i < pos; i++) p_frame[((const int32_t *)p_xs)[i]] += ((const uint8_t *)p_in)[i];
         expected.push(p_frame);
         // the elaboration loop: one host frame in, a ticket out
         memcpy(h_frame[t % depth], frame.data(), n);
-        if (mi355_pipe_submit_cwire(server, (const uint8_t *)h_frame[t % depth], nullptr, nullptr, h_rec[t % depth], cap,
-                                    &tickets[t % depth]) != MI355_OK) {
-            fprintf(stderr, "mi355_pipe_submit_cwire failed: %s\n", mi355_last_error());
-            rc = 1;
-            break;
-        }
+        OK(mi355_pipe_submit_cwire(server, (const uint8_t *)h_frame[t % depth], nullptr, nullptr, h_rec[t % depth], cap, &tickets[t % depth]));
+        return 0;
+    };
+    for (int t = 0; t < T && ok && !rc; t++) {
+        if (t >= depth) rc = finish(t - depth);
+        if (!rc) rc = submit(t);
     }
     for (int t = T > depth ? T - depth : 0; t < T && ok && !rc; t++) rc = finish(t);
-    close(fds[1]);   // (a receiver that still waits for bytes sees the end of the stream)
+    close(ss.fds[1]);   // (a receiver that still waits for bytes sees the end of the stream)
     if (rc || !ok)
         for (int t = 0; t < T; t++) expected.push(std::vector<uint8_t>());   // ... and one that waits for a frame gets a wrong one
     receiver.join();
@@ -1149,15 +999,7 @@ static int run_per_frame(int w, int h, int T) {
     if (!rx.error.empty()) { fprintf(stderr, "%s\n", rx.error.c_str()); return 1; }
     OK(mi355_pipe_close(server));
     OK(mi355_get_state(server, s_state.data()));
-    if (memcmp(s_state.data(), p_frame.data(), n) != 0) { fprintf(stderr, "server state != plain client frame\n"); return 1; }
-    for (int i = 0; i < depth; i++) {
-        OK(mi355_host_free(h_frame[i]));
-        OK(mi355_host_free(h_rec[i]));
-    }
-    OK(mi355_host_free(p_in));
-    OK(mi355_host_free(p_xs));
-    mi355_destroy(server);
-    mi355_destroy(plain);
+    if (same(s_state.data(), p_frame.data(), n, "server state != plain client frame") || ss.close()) return 1;
     printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"per_frame\": true, \"depth\": %d, \"width\": %d, \"height\": %d, "
            "\"frames\": %d, \"frames_equal\": %d, \"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, "
            "\"raw_bytes\": %zu}\n",
@@ -1165,68 +1007,53 @@ static int run_per_frame(int w, int h, int T) {
     return rx.equal == T ? 0 : 1;
 }
 
-// --compact --multi S --resync R [--burst K] (see the head of the file)
+// --compact --multi S --resync R [--burst K]: a receiver that lost a record finds its way back.  At tick R the receiver drops one
+// camera's record (it applies an empty record in its place), so that camera's frame is wrong from then on.  After tick R + 1 it
+// digests its states (mi355_state_digest_batch, checked against mi355_state_digest_host) and sends the digests up; the sender
+// answers behind its latest tick -- with --burst K the end of the burst it has already made -- with a tile mask and one refresh
+// record per camera (mi355_refresh_cwire_batch); the receiver applies the ticks that were in flight, clears the masked tiles
+// (mi355_state_clear_tiles_batch) and applies the refresh records like any others.  Checked: the dropped camera's frame differs
+// from the sender's at every tick between the loss and the refresh, and every other frame of every tick -- all of them from the
+// refresh on -- equals the sender's; the dropped camera has mask bits and, unless ticks were in flight, only that camera (the
+// others get the 8-byte record); a host client that clears the tiles itself and calls mi355_cwire_apply_host ends at the same
+// frames.
 static int run_multi_resync(int w, int h, int T, int S, int R, int K, int wall_k) {
-    const size_t n = (size_t)3 * w * h;
     if (R < 0 || R + 1 >= T) { fprintf(stderr, "--resync K needs 0 <= K and K + 1 < --frames\n"); return 2; }
     if (K < 1) K = 1;
-    mi355_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.width = w; cfg.height = h; cfg.threshold = 20; cfg.max_batch = S * K; cfg.device = -1;
-    mi355_core *server = nullptr, *client = nullptr;
-    OK(mi355_create(&cfg, &server));
-    cfg.max_batch = S;
-    OK(mi355_create(&cfg, &client));
+    Session ss(w, h);
+    const size_t n = ss.n;
     const int B = S * K, victim = R % S;
-    const size_t cw_cap = mi355_cwire_bytes_max(n, B), tick_cap = mi355_cwire_bytes_max(n, S);
     const size_t tiles = mi355_state_tiles(n), mask_words = (tiles + 31) / 32;
     const size_t dig_bytes = 8 * (size_t)S * tiles, mask_bytes = 4 * (size_t)S * mask_words;
-    void *d_frames = nullptr, *d_sstates = nullptr, *d_off = nullptr, *d_pos = nullptr, *d_cw = nullptr;   // server
-    void *d_peer = nullptr, *d_smask = nullptr, *d_roff = nullptr, *d_rpos = nullptr, *d_rcw = nullptr;    // ... its refresh
-    void *d_rx = nullptr, *d_cstates = nullptr, *d_dig = nullptr, *d_cmask = nullptr;                      // client
-    OK(mi355_dev_alloc(server, &d_frames, (size_t)B * n));
-    OK(mi355_dev_alloc(server, &d_sstates, (size_t)S * n));
-    OK(mi355_dev_alloc(server, &d_off, sizeof(uint32_t) * (B + 1)));
-    OK(mi355_dev_alloc(server, &d_pos, sizeof(uint64_t) * (B + 1)));
-    OK(mi355_dev_alloc(server, &d_cw, cw_cap));
-    OK(mi355_dev_alloc(server, &d_peer, dig_bytes));
-    OK(mi355_dev_alloc(server, &d_smask, mask_bytes));
-    OK(mi355_dev_alloc(server, &d_roff, sizeof(uint32_t) * (S + 1)));
-    OK(mi355_dev_alloc(server, &d_rpos, sizeof(uint64_t) * (S + 1)));
-    OK(mi355_dev_alloc(server, &d_rcw, tick_cap));
-    OK(mi355_dev_alloc(client, &d_rx, tick_cap));
-    OK(mi355_dev_alloc(client, &d_cstates, (size_t)S * n));
-    OK(mi355_dev_alloc(client, &d_dig, dig_bytes));
-    OK(mi355_dev_alloc(client, &d_cmask, mask_bytes));
+    Cameras cams(S, w, h);
+    Sender tx;
+    Receiver rcv;
     WallCheck wall;
-    if (wall_k)
-        if (int rc = wall.open(client, w, h, wall_k, S)) return rc;
-    int fds[2];
-    if (pipe(fds) != 0) return 1;
+    if (tx.open(ss, S, K) || rcv.open(ss, S, S, S)) return 1;
+    void *d_peer = ss.dev(tx.core, dig_bytes), *d_smask = ss.dev(tx.core, mask_bytes);   // the sender's refresh
+    void *d_roff = ss.dev(tx.core, sizeof(uint32_t) * (S + 1)), *d_rpos = ss.dev(tx.core, sizeof(uint64_t) * (S + 1));
+    void *d_rcw = ss.dev(tx.core, rcv.cap);
+    void *d_dig = ss.dev(rcv.core, dig_bytes), *d_cmask = ss.dev(rcv.core, mask_bytes);   // the receiver's question, its clear
+    if (!ss.ok()) return 1;
+    if (int rc = wall.open(ss, rcv.core, wall_k, S)) return rc;
     // truth: a host client per camera that applies EVERY record -- the sender's state after every tick
-    std::vector<uint8_t> bases((size_t)S * n), truth((size_t)S * n), frames((size_t)B * n), s_states((size_t)S * n),
-        c_states((size_t)S * n), cw_host(cw_cap), rx(cw_cap), stage(tick_cap), host_client;
-    for (int s = 0; s < S; s++)
-        for (size_t i = 0; i < n; i++) bases[(size_t)s * n + i] = (uint8_t)(40 + (i * 7 + (size_t)s * 31) % 150);
-    OK(mi355_upload(server, d_sstates, bases.data(), bases.size()));
-    if (!through_pipe(fds[1], fds[0], bases.data(), truth.data(), bases.size())) return 1;
-    OK(mi355_upload(client, d_cstates, truth.data(), truth.size()));
-    if (int rc = wall.full(d_cstates)) return rc;
-    std::vector<uint8_t> base(n), frame(n);
-    std::vector<uint32_t> off(B + 1), counts(S), escapes(S), dig(2 * (size_t)S * tiles), dig_up(dig.size()), dig_host(2 * tiles),
+    std::vector<uint8_t> truth((size_t)S * n), burst(tx.cap), host_client;
+    if (cams.start(ss, tx, rcv, truth.data())) return 1;
+    if (int rc = wall.full(rcv.d_states)) return rc;
+    std::vector<uint32_t> b_counts(B), b_escapes(B), dig(2 * (size_t)S * tiles), dig_up(dig.size()), dig_host(2 * tiles),
         mask(S * mask_words), mask_rx(mask.size());
-    std::vector<uint64_t> pos(B + 1), rpos(S + 1);
-    std::vector<size_t> at(B), len(B);
+    std::vector<uint64_t> rpos(S + 1);
+    std::vector<size_t> b_at(B + 1);
     size_t sent_bytes = 0, refresh_bytes = 0, lost_entries = 0, tiles_selected = 0;
     int wrong_ticks = 0, right_ticks_after = 0;
     bool lost = false, refreshed = false;
     // the receiver's frames of tick t against the truth: while the record is lost the victim's differs and only the victim's
     auto compare = [&](int t) -> int {
         for (int s = 0; s < S; s++) {
-            const bool same = memcmp(&truth[(size_t)s * n], &c_states[(size_t)s * n], n) == 0;
+            const bool same_frame = memcmp(&truth[(size_t)s * n], &rcv.states[(size_t)s * n], n) == 0;
             const bool wrong = lost && !refreshed && s == victim;
-            if (same == wrong) {
-                fprintf(stderr, "tick %d: camera %d: the receiver's frame %s the sender's\n", t, s, same ? "equals" : "differs from");
+            if (same_frame == wrong) {
+                fprintf(stderr, "tick %d: camera %d: the receiver's frame %s the sender's\n", t, s, same_frame ? "equals" : "differs from");
                 return 1;
             }
         }
@@ -1235,102 +1062,63 @@ static int run_multi_resync(int w, int h, int T, int S, int R, int K, int wall_k
         return 0;
     };
     for (int t0 = 0; t0 < T; t0 += K) {
-        const int nb = T - t0 < K ? T - t0 : K, nrec = S * nb;
-        for (int s = 0; s < S; s++) {   // camera s's nb frames, one behind the other
-            memcpy(base.data(), &bases[(size_t)s * n], n);
-            for (int k = 0; k < nb; k++) {
-                make_frame(frame, base, w, h, t0 + k + 5 * s);
-                memcpy(&frames[((size_t)s * nb + k) * n], frame.data(), n);
-            }
-        }
-        // ---- server: nb ticks of S cameras
-        OK(mi355_upload(server, d_frames, frames.data(), (size_t)nrec * n));
-        if (K == 1) OK(mi355_diff_multi_cwire_batch(server, d_frames, d_sstates, n, S, d_off, d_pos, d_cw, cw_cap));
-        else OK(mi355_diff_multi_stream_cwire_batch(server, d_frames, d_sstates, n, S, nb, d_off, d_pos, d_cw, cw_cap));
-        OK(mi355_download(server, pos.data(), d_pos, sizeof(uint64_t) * (nrec + 1)));
-        if (pos[nrec] > cw_cap) { fprintf(stderr, "compact stream larger than its bound\n"); return 1; }
-        const size_t cb = (size_t)pos[nrec];
-        OK(mi355_download(server, cw_host.data(), d_cw, cb));
-        if (!through_pipe(fds[1], fds[0], cw_host.data(), rx.data(), cb)) return 1;
-        sent_bytes += cb;
-        size_t p = 0;
-        for (int r = 0; r < nrec; r++) {   // the records of every socket, found from their headers
-            if (p + 8 > cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
-            uint32_t c, e;
-            memcpy(&c, rx.data() + p, 4);
-            memcpy(&e, rx.data() + p + 4, 4);
-            at[r] = p;
-            len[r] = mi355_cwire_frame_bytes(c, e);
-            p += len[r];
-        }
-        if (p != cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
+        const int nb = T - t0 < K ? T - t0 : K;
+        cams.fill(tx.frames.data(), t0, nb);
+        // ---- server: nb ticks of S cameras; the sockets; the records of every socket, found from their headers
+        if (tx.step(nb, K != 1)) return 1;
+        if (!ss.send(tx.bytes.data(), burst.data(), tx.cb)) return 1;
+        sent_bytes += tx.cb;
+        if (walk_records(burst.data(), 0, tx.cb, S * nb, b_counts.data(), b_escapes.data(), b_at.data())) return 1;
         // ---- client: tick k = record (s, k) of every s back to back, one upload, one call
         bool asked = false;
         for (int k = 0; k < nb; k++) {
             const int t = t0 + k;
-            size_t q = 0;
-            for (int s = 0; s < S; s++) {
-                const int r = s * nb + k;
-                size_t used = 0;
-                OK(mi355_cwire_apply_host(&truth[(size_t)s * n], n, rx.data() + at[r], len[r], 1, &used));
-                if (used != len[r]) { fprintf(stderr, "stream framing broken\n"); return 1; }
-                if (t == R && s == victim) {   // the loss: the receiver has nothing to apply for this camera
-                    memcpy(&lost_entries, rx.data() + at[r], 4);
-                    if (lost_entries == 0) { fprintf(stderr, "--resync: the record to drop holds no entry\n"); return 1; }
-                    memset(stage.data() + q, 0, 8);
-                    counts[s] = escapes[s] = 0;
-                    q += 8;
-                    lost = true;
-                    continue;
-                }
-                memcpy(stage.data() + q, rx.data() + at[r], len[r]);
-                memcpy(&counts[s], stage.data() + q, 4);
-                memcpy(&escapes[s], stage.data() + q + 4, 4);
-                q += len[r];
+            for (int s = 0; s < S; s++)
+                if (host_apply(&truth[(size_t)s * n], n, burst.data(), b_at.data(), s * nb + k)) return 1;
+            if (t == R) {   // the loss: the receiver has nothing to apply for this camera
+                lost_entries = b_counts[victim * nb + k];
+                if (lost_entries == 0) { fprintf(stderr, "--resync: the record to drop holds no entry\n"); return 1; }
+                lost = true;
             }
-            OK(mi355_upload(client, d_rx, stage.data(), q));
-            OK(mi355_apply_multi_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, d_cstates, n));
-            if (int rc = wall.update(d_rx, counts.data(), escapes.data(), 1, d_cstates)) return rc;   // (the wall shows what it holds)
+            const size_t q = rcv.stage(burst.data(), b_at.data(), nb, k, t == R ? victim : -1);
+            OK(mi355_upload(rcv.core, rcv.d_rx, rcv.rx.data(), q));
+            if (rcv.apply_tick()) return 1;
+            if (int rc = wall.update(rcv.d_rx, rcv.counts.data(), rcv.escapes.data(), 1, rcv.d_states)) return rc;   // (the wall shows what it holds)
             if (t == R + 1) {   // the receiver asks: its digests go up
-                OK(mi355_state_digest_batch(client, d_cstates, n, S, d_dig));
-                OK(mi355_download(client, dig.data(), d_dig, dig_bytes));
+                OK(mi355_state_digest_batch(rcv.core, rcv.d_states, n, S, d_dig));
+                OK(mi355_download(rcv.core, dig.data(), d_dig, dig_bytes));
                 asked = true;
             }
-            OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
-            if (asked && t == R + 1)
-                for (int s = 0; s < S; s++) {
-                    OK(mi355_state_digest_host(&c_states[(size_t)s * n], n, dig_host.data()));
-                    if (memcmp(dig_host.data(), &dig[2 * (size_t)s * tiles], 8 * tiles) != 0) {
-                        fprintf(stderr, "tick %d: camera %d: device digests != host digests\n", t, s);
-                        return 1;
-                    }
+            if (rcv.get_states()) return 1;
+            for (int s = 0; s < S && t == R + 1; s++) {
+                OK(mi355_state_digest_host(&rcv.states[(size_t)s * n], n, dig_host.data()));
+                if (memcmp(dig_host.data(), &dig[2 * (size_t)s * tiles], 8 * tiles) != 0) {
+                    fprintf(stderr, "tick %d: camera %d: device digests != host digests\n", t, s);
+                    return 1;
                 }
+            }
             if (int rc = compare(t)) return rc;
-            if (int rc = wall.compare(c_states.data(), t)) return rc;
+            if (int rc = wall.compare(rcv.states.data(), t)) return rc;
         }
         // ---- the states at both ends of the burst: the truth is the sender's
-        OK(mi355_download(server, s_states.data(), d_sstates, s_states.size()));
-        if (memcmp(s_states.data(), truth.data(), s_states.size()) != 0) { fprintf(stderr, "tick %d: host frames != server states\n", t0); return 1; }
+        if (tx.get_states() || same(tx.states.data(), truth.data(), truth.size(), "host client frames != sender states", t0)) return 1;
         if (!asked) continue;
         const bool in_flight = t0 + nb - 1 > R + 1;
         // ---- server: the answer, behind its latest tick
-        if (!through_pipe(fds[1], fds[0], (const uint8_t *)dig.data(), (uint8_t *)dig_up.data(), dig_bytes)) return 1;
-        OK(mi355_upload(server, d_peer, dig_up.data(), dig_bytes));
-        OK(mi355_refresh_cwire_batch(server, d_sstates, n, S, d_peer, d_smask, d_roff, d_rpos, d_rcw, tick_cap));
-        OK(mi355_download(server, rpos.data(), d_rpos, sizeof(uint64_t) * (S + 1)));
-        OK(mi355_download(server, mask.data(), d_smask, mask_bytes));
+        if (!ss.send(dig.data(), dig_up.data(), dig_bytes)) return 1;
+        OK(mi355_upload(tx.core, d_peer, dig_up.data(), dig_bytes));
+        OK(mi355_refresh_cwire_batch(tx.core, tx.d_states, n, S, d_peer, d_smask, d_roff, d_rpos, d_rcw, rcv.cap));
+        OK(mi355_download(tx.core, rpos.data(), d_rpos, sizeof(uint64_t) * (S + 1)));
+        OK(mi355_download(tx.core, mask.data(), d_smask, mask_bytes));
         refresh_bytes = (size_t)rpos[S];
-        if (refresh_bytes > tick_cap) { fprintf(stderr, "refresh records larger than their bound\n"); return 1; }
-        OK(mi355_download(server, cw_host.data(), d_rcw, refresh_bytes));
-        if (!through_pipe(fds[1], fds[0], (const uint8_t *)mask.data(), (uint8_t *)mask_rx.data(), mask_bytes)) return 1;
-        if (!through_pipe(fds[1], fds[0], cw_host.data(), stage.data(), refresh_bytes)) return 1;
+        if (refresh_bytes > rcv.cap) { fprintf(stderr, "refresh stream larger than its bound\n"); return 1; }
+        OK(mi355_download(tx.core, tx.bytes.data(), d_rcw, refresh_bytes));
+        if (!ss.send(mask.data(), mask_rx.data(), mask_bytes)) return 1;
+        if (!ss.send(tx.bytes.data(), rcv.rx.data(), refresh_bytes)) return 1;
         // ---- client: clear, then apply like any other records; a host client does the same beside it
-        host_client = c_states;
-        p = 0;
+        if (rcv.walk(0, refresh_bytes, 0, S)) return 1;
+        host_client = rcv.states;
         for (int s = 0; s < S; s++) {
-            if (p + 8 > refresh_bytes) { fprintf(stderr, "refresh framing broken\n"); return 1; }
-            memcpy(&counts[s], stage.data() + p, 4);
-            memcpy(&escapes[s], stage.data() + p + 4, 4);
             size_t bits = 0;
             for (size_t tl = 0; tl < tiles; tl++)
                 if (mask_rx[s * mask_words + (tl >> 5)] >> (tl & 31) & 1u) {
@@ -1339,35 +1127,27 @@ static int run_multi_resync(int w, int h, int T, int S, int R, int K, int wall_k
                     memset(&host_client[(size_t)s * n + lo], 0, hi - lo);
                 }
             // (ticks in flight behind the digests changed tiles of every camera: those are selected too, wasteful and never wrong)
-            if (s == victim ? bits == 0 : !in_flight && (bits != 0 || counts[s] != 0)) {
-                fprintf(stderr, "refresh: camera %d: %zu tiles selected, %u entries\n", s, bits, counts[s]);
+            if (s == victim ? bits == 0 : !in_flight && (bits != 0 || rcv.counts[s] != 0)) {
+                fprintf(stderr, "refresh: camera %d: %zu tiles selected, %u entries\n", s, bits, rcv.counts[s]);
                 return 1;
             }
             tiles_selected += bits;
-            size_t used = 0;
-            OK(mi355_cwire_apply_host(&host_client[(size_t)s * n], n, stage.data() + p, refresh_bytes - p, 1, &used));
-            p += used;
+            if (host_apply(&host_client[(size_t)s * n], n, rcv.rx.data(), rcv.at.data(), s)) return 1;
         }
-        if (p != refresh_bytes) { fprintf(stderr, "refresh framing broken\n"); return 1; }
-        OK(mi355_upload(client, d_cmask, mask_rx.data(), mask_bytes));
-        OK(mi355_upload(client, d_rx, stage.data(), refresh_bytes));
-        OK(mi355_state_clear_tiles_batch(client, d_cstates, n, S, d_cmask));
-        OK(mi355_apply_multi_cwire_batch(client, d_rx, counts.data(), escapes.data(), S, d_cstates, n));
-        if (int rc = wall.masked(d_cmask, d_cstates)) return rc;   // the refresh's own mask: what was cleared and refilled is repainted
-        OK(mi355_download(client, c_states.data(), d_cstates, c_states.size()));
-        if (int rc = wall.compare(c_states.data(), t0 + nb - 1)) return rc;
+        OK(mi355_upload(rcv.core, d_cmask, mask_rx.data(), mask_bytes));
+        OK(mi355_upload(rcv.core, rcv.d_rx, rcv.rx.data(), refresh_bytes));
+        OK(mi355_state_clear_tiles_batch(rcv.core, rcv.d_states, n, S, d_cmask));
+        if (rcv.apply_tick()) return 1;
+        if (int rc = wall.masked(d_cmask, rcv.d_states)) return rc;   // the refresh's own mask: what was cleared and refilled is repainted
+        if (rcv.get_states()) return 1;
+        if (int rc = wall.compare(rcv.states.data(), t0 + nb - 1)) return rc;
         refreshed = true;
-        if (memcmp(c_states.data(), host_client.data(), c_states.size()) != 0) { fprintf(stderr, "refresh: client states != host client frames\n"); return 1; }
-        if (memcmp(c_states.data(), s_states.data(), c_states.size()) != 0) { fprintf(stderr, "refresh: client states != server states\n"); return 1; }
+        if (same(rcv.states.data(), host_client.data(), host_client.size(), "refresh: receiver states != host client frames")) return 1;
+        if (same(rcv.states.data(), tx.states.data(), tx.states.size(), "refresh: receiver states != sender states")) return 1;
     }
     if (!refreshed || wrong_ticks < 1) { fprintf(stderr, "--resync: no refresh happened\n"); return 1; }
-    void *srv[] = {d_frames, d_sstates, d_off, d_pos, d_cw, d_peer, d_smask, d_roff, d_rpos, d_rcw};
-    for (void *q : srv) OK(mi355_dev_free(server, q));
-    void *cli[] = {d_rx, d_cstates, d_dig, d_cmask};
-    for (void *q : cli) OK(mi355_dev_free(client, q));
     if (int rc = wall.close()) return rc;
-    mi355_destroy(server);
-    mi355_destroy(client);
+    if (ss.close()) return 1;
     printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"burst\": %d, \"resync\": %d, \"width\": %d, \"height\": %d, "
            "\"ticks\": %d, \"dropped_camera\": %d, \"dropped_entries\": %zu, \"wrong_ticks\": %d, \"ticks_equal_after_refresh\": %d, "
            "\"tiles\": %zu, \"tiles_selected\": %zu, \"digest_bytes\": %zu, \"mask_bytes\": %zu, \"refresh_bytes\": %zu, "
@@ -1377,243 +1157,205 @@ static int run_multi_resync(int w, int h, int T, int S, int R, int K, int wall_k
     return 0;
 }
 
-int main(int argc, char **argv) {
-    int w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0, activity = -1, resync = -1, wall = 0;
-    long budget = -1;
-    bool compact = false, direct = false, gpu_client = false, burst_client = false, coalesce = false, per_frame = false, check = false;
-    for (int i = 1; i < argc; i++) {
-        if (std::string(argv[i]) == "--compact") compact = true;
-        if (std::string(argv[i]) == "--direct") direct = true;
-        if (std::string(argv[i]) == "--gpu-client") gpu_client = true;
-        if (std::string(argv[i]) == "--burst-client") burst_client = true;
-        if (std::string(argv[i]) == "--coalesce") coalesce = true;
-        if (std::string(argv[i]) == "--per-frame") per_frame = true;
-        if (std::string(argv[i]) == "--check") check = true;
-    }
-    if (direct && !compact) { fprintf(stderr, "--direct needs --compact\n"); return 2; }
-    if (gpu_client && !compact) { fprintf(stderr, "--gpu-client needs --compact\n"); return 2; }
-    for (int i = 1; i + 1 < argc; i += 2) {
-        const std::string k = argv[i];
-        if (k == "--compact" || k == "--direct" || k == "--gpu-client" || k == "--burst-client" || k == "--coalesce" || k == "--per-frame" || k == "--check") { i--; continue; }
-        const int v = atoi(argv[i + 1]);
-        if (k == "--width") w = v; else if (k == "--height") h = v;
-        else if (k == "--frames") T = v; else if (k == "--batch") B = v;
-        else if (k == "--multi") multi = v;
-        else if (k == "--burst") burst = v;
-        else if (k == "--activity") activity = v < 0 ? 0 : v;
-        else if (k == "--resync") resync = v < 0 ? 0 : v;
-        else if (k == "--wall") wall = v < 1 ? -1 : v;
-        else if (k == "--budget") budget = atol(argv[i + 1]) < 0 ? 0 : atol(argv[i + 1]);
-    }
-    if (burst && (!multi || burst < 0)) { fprintf(stderr, "--burst K needs --multi S and K >= 1\n"); return 2; }
-    if (burst_client && (!compact || !multi || !burst)) { fprintf(stderr, "--burst-client needs --compact --multi S --burst K\n"); return 2; }
-    if (coalesce && (!compact || !multi || !burst || burst_client)) {
-        fprintf(stderr, "--coalesce needs --compact --multi S --burst K, without --burst-client\n");
-        return 2;
-    }
-    if (budget >= 0 && (!compact || !multi || burst || direct || gpu_client || per_frame)) {
-        fprintf(stderr, "--budget BYTES needs --compact --multi S alone\n");
-        return 2;
-    }
-    if (activity >= 0 && (activity == 0 || !compact || !multi || budget >= 0 || coalesce || (burst && !burst_client))) {
-        fprintf(stderr, "--activity CELL needs CELL >= 1 and --compact --multi S, alone or with --burst K --burst-client\n");
-        return 2;
-    }
-    if (activity < 0) activity = 0;
-    if (check && (!compact || !multi || budget >= 0 || coalesce || per_frame || (burst && !burst_client))) {
-        fprintf(stderr, "--check needs --compact --multi S, alone or with --burst K --burst-client\n");
-        return 2;
-    }
-    if (resync >= 0 && (!compact || !multi || budget >= 0 || coalesce || per_frame || burst_client || activity || check)) {
-        fprintf(stderr, "--resync K needs --compact --multi S, alone or with --burst B\n");
-        return 2;
-    }
-    if (wall && (wall < 0 || wall > 16 || !compact || !multi || budget >= 0 || coalesce || per_frame || (burst && !burst_client && resync < 0))) {
-        fprintf(stderr, "--wall K needs 1 <= K <= 16 and --compact --multi S, alone, with --burst B --burst-client or with --resync R\n");
-        return 2;
-    }
-    if (per_frame) {
-        if (!compact || direct || gpu_client || multi) { fprintf(stderr, "--per-frame needs --compact alone\n"); return 2; }
-        return run_per_frame(w, h, T);
-    }
-    if (multi) {
-        if (!compact || direct || gpu_client || multi < 0) { fprintf(stderr, "--multi S needs --compact alone and S >= 1\n"); return 2; }
-        if (resync >= 0) return run_multi_resync(w, h, T, multi, resync, burst, wall);
-        if (burst_client) return run_multi_burst_client(w, h, T, multi, burst, activity, check, wall);
-        if (coalesce) return run_multi_burst_coalesce(w, h, T, multi, burst);
-        if (budget >= 0) return run_multi_budget(w, h, T, multi, budget);
-        return burst ? run_multi_burst(w, h, T, multi, burst) : run_multi(w, h, T, multi, activity, check, wall);
-    }
-    const size_t n = (size_t)3 * w * h;
-    mi355_config cfg;
-    memset(&cfg, 0, sizeof cfg);
-    cfg.width = w; cfg.height = h; cfg.threshold = 20; cfg.max_batch = B; cfg.device = -1;
+// One camera, the state inside the cores (mi355_set_state / mi355_get_state): the start both single-camera modes share
+struct Single {
+    int B;
+    Session ss;
+    Cameras cam;
     mi355_core *server = nullptr, *client = nullptr;
-    OK(mi355_create(&cfg, &server));
-    OK(mi355_create(&cfg, &client));
+    void *d_frames = nullptr, *d_off = nullptr;
+    std::vector<uint8_t> frames, got_base, s_state, c_state;
+    std::vector<uint32_t> off, counts, escapes;
 
-    std::vector<uint8_t> base(n), frame(n), frames((size_t)B * n), shown((size_t)B * n), s_state(n), c_state(n);
-    for (size_t i = 0; i < n; i++) base[i] = (uint8_t)(40 + (i * 7) % 150);
-    OK(mi355_set_state(server, base.data()));                  // kernels.cu:406
-
-    int fds[2];
-    if (pipe(fds) != 0) return 1;
-    // ---- sender side: the base frame first (threads.cpp:220)
-    std::vector<uint8_t> wire_host(mi355_wire_bytes(B, (uint64_t)B * n));
-    void *d_frames = nullptr, *d_wire = nullptr, *d_off = nullptr, *d_cwire = nullptr, *d_shown = nullptr;
-    OK(mi355_dev_alloc(server, &d_frames, (size_t)B * n));
-    OK(mi355_dev_alloc(server, &d_wire, wire_host.size()));
-    OK(mi355_dev_alloc(server, &d_off, sizeof(uint32_t) * (B + 1)));
-    OK(mi355_dev_alloc(client, &d_cwire, wire_host.size()));
-    OK(mi355_dev_alloc(client, &d_shown, (size_t)B * n));
-
-    // ---- client start-up: read the base frame (opencv.cpp:38-46)
-    std::vector<uint8_t> got_base(n);
-    if (!through_pipe(fds[1], fds[0], base.data(), got_base.data(), n)) return 1;
-    OK(mi355_set_state(client, got_base.data()));
-
-    size_t sent_bytes = 0, changed = 0;
-    int max_err = 0;
-    if (compact) {
-        // ---- sender: pack + encode on the GPU; client: the host decoder on a host frame (no core)
-        void *d_xs = nullptr, *d_df = nullptr, *d_pos = nullptr, *d_cw = nullptr;
-        const size_t cap = (size_t)B * n, cw_cap = mi355_cwire_bytes_max(n, B);
-        if (!direct) {   // (the one-call form needs no arrays of 5 bytes per entry)
-            OK(mi355_dev_alloc(server, &d_xs, cap * 4));
-            OK(mi355_dev_alloc(server, &d_df, cap));
-        }
-        OK(mi355_dev_alloc(server, &d_pos, sizeof(uint64_t) * (B + 1)));
-        OK(mi355_dev_alloc(server, &d_cw, cw_cap));
-        std::vector<uint8_t> cw_host(cw_cap), rx(cw_cap), c_frame(got_base);
-        for (int t0 = 0; t0 < T; t0 += B) {
-            const int nb = T - t0 < B ? T - t0 : B;
-            for (int k = 0; k < nb; k++) {
-                make_frame(frame, base, w, h, t0 + k);
-                memcpy(&frames[(size_t)k * n], frame.data(), n);
-            }
-            std::vector<uint32_t> off(nb + 1);
-            std::vector<uint64_t> pos(nb + 1);
-            OK(mi355_upload(server, d_frames, frames.data(), (size_t)nb * n));
-            if (direct) {
-                OK(mi355_diff_stream_cwire_batch(server, d_frames, n, nb, d_off, d_pos, d_cw, cw_cap));
-            } else {
-                OK(mi355_diff_stream_batch(server, d_frames, n, nb, d_off, d_xs, d_df, cap));
-                OK(mi355_cwire_encode_batch(server, d_off, d_xs, d_df, cap, nb, d_pos, d_cw, cw_cap));
-            }
-            OK(mi355_download(server, off.data(), d_off, sizeof(uint32_t) * (nb + 1)));
-            OK(mi355_download(server, pos.data(), d_pos, sizeof(uint64_t) * (nb + 1)));
-            if (pos[nb] > cw_cap) { fprintf(stderr, "compact stream larger than its bound\n"); return 1; }
-            const size_t cb = (size_t)pos[nb];
-            OK(mi355_download(server, cw_host.data(), d_cw, cb));
-            changed += off[nb];
-            if (!through_pipe(fds[1], fds[0], cw_host.data(), rx.data(), cb)) return 1;
-            sent_bytes += cb;
-            std::vector<uint32_t> counts(nb), escapes(nb);
-            if (gpu_client) {   // the headers as the client reads them from the stream, then one call for the batch
-                size_t p = 0;
-                for (int k = 0; k < nb; k++) {
-                    memcpy(&counts[k], rx.data() + p, 4);
-                    memcpy(&escapes[k], rx.data() + p + 4, 4);
-                    p += mi355_cwire_frame_bytes(counts[k], escapes[k]);
-                }
-                if (p != cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
-                OK(mi355_upload(client, d_cwire, rx.data(), cb));
-                OK(mi355_apply_cwire_batch(client, d_cwire, counts.data(), escapes.data(), nb, d_shown, n));
-                OK(mi355_download(client, shown.data(), d_shown, (size_t)nb * n));
-            }
-            size_t at = 0;
-            for (int k = 0; k < nb; k++) {   // one frame at a time: what the client shows after each
-                size_t used = 0;
-                OK(mi355_cwire_apply_host(c_frame.data(), n, rx.data() + at, cb - at, 1, &used));
-                at += used;
-                if (gpu_client && memcmp(&shown[(size_t)k * n], c_frame.data(), n) != 0) {
-                    fprintf(stderr, "GPU client frame %d != host client frame\n", t0 + k);
-                    return 1;
-                }
-                for (size_t i = 0; i < n; i++) {
-                    const int e = abs((int)c_frame[i] - (int)frames[(size_t)k * n + i]);
-                    if (e > max_err) max_err = e;
-                }
-            }
-            if (at != cb) { fprintf(stderr, "stream framing broken\n"); return 1; }
-            OK(mi355_get_state(server, s_state.data()));
-            if (memcmp(s_state.data(), c_frame.data(), n) != 0) { fprintf(stderr, "client frame != server state\n"); return 1; }
-            if (gpu_client) {
-                OK(mi355_get_state(client, c_state.data()));
-                if (memcmp(s_state.data(), c_state.data(), n) != 0) { fprintf(stderr, "GPU client state != server state\n"); return 1; }
-            }
-        }
-        if (max_err > cfg.threshold) { fprintf(stderr, "rebuilt frame off by %d > threshold\n", max_err); return 1; }
-        if (!direct) {
-            OK(mi355_dev_free(server, d_xs));
-            OK(mi355_dev_free(server, d_df));
-        }
-        OK(mi355_dev_free(server, d_pos));
-        OK(mi355_dev_free(server, d_cw));
-        OK(mi355_dev_free(server, d_frames));
-        OK(mi355_dev_free(server, d_wire));
-        OK(mi355_dev_free(server, d_off));
-        OK(mi355_dev_free(client, d_cwire));
-        OK(mi355_dev_free(client, d_shown));
-        mi355_destroy(server);
-        mi355_destroy(client);
-        printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"direct\": %s, \"gpu_client\": %s, \"width\": %d, \"height\": %d, \"frames\": %d, \"batch\": %d, "
-               "\"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, "
-               "\"max_abs_error\": %d}\n",
-               direct ? "true" : "false", gpu_client ? "true" : "false", w, h, T, B, changed, sent_bytes, mi355_wire_bytes(T, changed), (size_t)T * n, max_err);
+    Single(int w, int h, int B_) : B(B_), ss(w, h), cam(1, w, h), frames((size_t)B * ss.n), got_base(ss.n), s_state(ss.n), c_state(ss.n), off(B + 1),
+                                  counts(B), escapes(B) {}
+    int start() {
+        server = ss.core(B);
+        client = ss.core(B);
+        d_frames = ss.dev(server, (size_t)B * ss.n);
+        d_off = ss.dev(server, sizeof(uint32_t) * (B + 1));
+        if (!ss.ok()) return 1;
+        OK(mi355_set_state(server, cam.bases.data()));                  // kernels.cu:406
+        // the base frame first (threads.cpp:220); the client's start-up reads it (opencv.cpp:38-46)
+        if (!ss.send(cam.bases.data(), got_base.data(), ss.n)) return 1;
+        OK(mi355_set_state(client, got_base.data()));
         return 0;
     }
+};
+
+// (no option): the plain wire format, as the head of the file says
+static int run_single_wire(int w, int h, int T, int B) {
+    Single one(w, h, B);
+    Session &ss = one.ss;
+    const size_t n = ss.n, wire_cap = mi355_wire_bytes(B, (uint64_t)B * n);
+    if (one.start()) return 1;
+    mi355_core *server = one.server, *client = one.client;
+    void *d_wire = ss.dev(server, wire_cap), *d_rx = ss.dev(client, wire_cap), *d_shown = ss.dev(client, (size_t)B * n);
+    if (!ss.ok()) return 1;
+    std::vector<uint8_t> wire_host(wire_cap), rx(wire_cap), shown((size_t)B * n);
+    size_t sent_bytes = 0, changed = 0;
+    int max_err = 0;
     for (int t0 = 0; t0 < T; t0 += B) {
         const int nb = T - t0 < B ? T - t0 : B;
-        for (int k = 0; k < nb; k++) {
-            make_frame(frame, base, w, h, t0 + k);
-            memcpy(&frames[(size_t)k * n], frame.data(), n);
-        }
+        one.cam.fill(one.frames.data(), t0, nb);
         // ---- server: one batch -> the socket bytes of nb frames
-        std::vector<uint32_t> off(nb + 1);
-        OK(mi355_upload(server, d_frames, frames.data(), (size_t)nb * n));
-        OK(mi355_diff_stream_wire_batch(server, d_frames, n, nb, d_off, d_wire, wire_host.size()));
-        OK(mi355_download(server, off.data(), d_off, sizeof(uint32_t) * (nb + 1)));
-        const size_t wb = mi355_wire_bytes(nb, off[nb]);
+        OK(mi355_upload(server, one.d_frames, one.frames.data(), (size_t)nb * n));
+        OK(mi355_diff_stream_wire_batch(server, one.d_frames, n, nb, one.d_off, d_wire, wire_cap));
+        OK(mi355_download(server, one.off.data(), one.d_off, sizeof(uint32_t) * (nb + 1)));
+        const size_t wb = mi355_wire_bytes(nb, one.off[nb]);
         OK(mi355_download(server, wire_host.data(), d_wire, wb));
-        changed += off[nb];
+        changed += one.off[nb];
         // ---- the socket (a pipe here)
-        std::vector<uint8_t> rx(wb);
-        if (!through_pipe(fds[1], fds[0], wire_host.data(), rx.data(), wb)) return 1;
+        if (!ss.send(wire_host.data(), rx.data(), wb)) return 1;
         sent_bytes += wb;
         // ---- client: parse the headers as opencv.cpp:52 does, hand the bytes to the device
-        std::vector<uint32_t> counts(nb);
         size_t at = 0;
         for (int k = 0; k < nb; k++) {
-            uint32_t pos;
-            memcpy(&pos, &rx[at], 4);
-            counts[k] = pos;
-            at += 4 + (size_t)5 * pos;
+            memcpy(&one.counts[k], &rx[at], 4);
+            at += 4 + (size_t)5 * one.counts[k];
         }
         if (at != wb) { fprintf(stderr, "stream framing broken\n"); return 1; }
-        OK(mi355_upload(client, d_cwire, rx.data(), wb));
-        OK(mi355_apply_wire_batch(client, d_cwire, counts.data(), nb, d_shown, n));
+        OK(mi355_upload(client, d_rx, rx.data(), wb));
+        OK(mi355_apply_wire_batch(client, d_rx, one.counts.data(), nb, d_shown, n));
         OK(mi355_download(client, shown.data(), d_shown, (size_t)nb * n));
         // ---- checks
-        OK(mi355_get_state(server, s_state.data()));
-        OK(mi355_get_state(client, c_state.data()));
-        if (memcmp(s_state.data(), c_state.data(), n) != 0) { fprintf(stderr, "client state != server state\n"); return 1; }
-        if (memcmp(&shown[(size_t)(nb - 1) * n], c_state.data(), n) != 0) { fprintf(stderr, "last shown frame != state\n"); return 1; }
-        for (size_t i = 0; i < (size_t)nb * n; i++) {
-            const int e = abs((int)shown[i] - (int)frames[i]);
-            if (e > max_err) max_err = e;
-        }
+        OK(mi355_get_state(server, one.s_state.data()));
+        OK(mi355_get_state(client, one.c_state.data()));
+        if (same(one.s_state.data(), one.c_state.data(), n, "client state != server state")) return 1;
+        if (same(&shown[(size_t)(nb - 1) * n], one.c_state.data(), n, "last shown frame != state")) return 1;
+        max_err = std::max(max_err, max_abs_error(shown.data(), one.frames.data(), (size_t)nb * n));
     }
-    if (max_err > cfg.threshold) { fprintf(stderr, "rebuilt frame off by %d > threshold\n", max_err); return 1; }
-    OK(mi355_dev_free(server, d_frames));
-    OK(mi355_dev_free(server, d_wire));
-    OK(mi355_dev_free(server, d_off));
-    OK(mi355_dev_free(client, d_cwire));
-    OK(mi355_dev_free(client, d_shown));
-    mi355_destroy(server);
-    mi355_destroy(client);
+    if (within_threshold(max_err, ss) || ss.close()) return 1;
     printf("{\"roundtrip\": \"ok\", \"width\": %d, \"height\": %d, \"frames\": %d, \"batch\": %d, "
            "\"changed_bytes\": %zu, \"wire_bytes\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d}\n",
            w, h, T, B, changed, sent_bytes, (size_t)T * n, max_err);
     return 0;
+}
+
+// --compact: the same over the compact wire format (include/mi355diff.h): the server packs a batch and encodes it on the
+// GPU (mi355_diff_stream_batch, mi355_cwire_encode_batch), the records cross the same pipe, and the client -- with no
+// core and no GPU -- rebuilds every frame on the host with mi355_cwire_apply_host; each rebuilt frame is checked against
+// the frame that was sent, and the client's frame against the server's state after every batch.
+// --compact --direct: the server makes the records in one call (mi355_diff_stream_cwire_batch), without the xs / diff arrays.
+// --compact --gpu-client: the client core also uploads the received records and applies them in one call
+// (mi355_apply_cwire_batch) into its shown frames; every shown frame must equal the host client's frame after that record,
+// and the client core's state the server's state after every batch.
+static int run_single_compact(int w, int h, int T, int B, bool direct, bool gpu_client) {
+    Single one(w, h, B);
+    Session &ss = one.ss;
+    const size_t n = ss.n, cap = (size_t)B * n, cw_cap = mi355_cwire_bytes_max(n, B);
+    if (one.start()) return 1;
+    mi355_core *server = one.server, *client = one.client;
+    // (the one-call form needs no arrays of 5 bytes per entry; only the GPU client needs device buffers at the receiving end)
+    void *d_xs = direct ? nullptr : ss.dev(server, cap * 4), *d_df = direct ? nullptr : ss.dev(server, cap);
+    void *d_pos = ss.dev(server, sizeof(uint64_t) * (B + 1)), *d_cw = ss.dev(server, cw_cap);
+    void *d_rx = gpu_client ? ss.dev(client, cw_cap) : nullptr, *d_shown = gpu_client ? ss.dev(client, (size_t)B * n) : nullptr;
+    if (!ss.ok()) return 1;
+    std::vector<uint8_t> cw_host(cw_cap), rx(cw_cap), c_frame(one.got_base), shown(gpu_client ? (size_t)B * n : 0);
+    std::vector<uint64_t> pos(B + 1);
+    std::vector<size_t> at(B + 1);
+    size_t sent_bytes = 0, changed = 0;
+    int max_err = 0;
+    for (int t0 = 0; t0 < T; t0 += B) {
+        const int nb = T - t0 < B ? T - t0 : B;
+        one.cam.fill(one.frames.data(), t0, nb);
+        // ---- sender: pack + encode on the GPU, or both in one call
+        OK(mi355_upload(server, one.d_frames, one.frames.data(), (size_t)nb * n));
+        if (direct) {
+            OK(mi355_diff_stream_cwire_batch(server, one.d_frames, n, nb, one.d_off, d_pos, d_cw, cw_cap));
+        } else {
+            OK(mi355_diff_stream_batch(server, one.d_frames, n, nb, one.d_off, d_xs, d_df, cap));
+            OK(mi355_cwire_encode_batch(server, one.d_off, d_xs, d_df, cap, nb, d_pos, d_cw, cw_cap));
+        }
+        OK(mi355_download(server, one.off.data(), one.d_off, sizeof(uint32_t) * (nb + 1)));
+        OK(mi355_download(server, pos.data(), d_pos, sizeof(uint64_t) * (nb + 1)));
+        if (pos[nb] > cw_cap) { fprintf(stderr, "compact stream larger than its bound\n"); return 1; }
+        const size_t cb = (size_t)pos[nb];
+        OK(mi355_download(server, cw_host.data(), d_cw, cb));
+        changed += one.off[nb];
+        if (!ss.send(cw_host.data(), rx.data(), cb)) return 1;
+        sent_bytes += cb;
+        // ---- client: the headers as it reads them from the stream; the GPU client: one upload, one call for the batch
+        if (walk_records(rx.data(), 0, cb, nb, one.counts.data(), one.escapes.data(), at.data())) return 1;
+        if (gpu_client) {
+            OK(mi355_upload(client, d_rx, rx.data(), cb));
+            OK(mi355_apply_cwire_batch(client, d_rx, one.counts.data(), one.escapes.data(), nb, d_shown, n));
+            OK(mi355_download(client, shown.data(), d_shown, (size_t)nb * n));
+        }
+        for (int k = 0; k < nb; k++) {   // the host client, one frame at a time: what the client shows after each
+            if (host_apply(c_frame.data(), n, rx.data(), at.data(), k)) return 1;
+            if (gpu_client && same(&shown[(size_t)k * n], c_frame.data(), n, "GPU client frame != host client frame", t0 + k)) return 1;
+            max_err = std::max(max_err, max_abs_error(c_frame.data(), &one.frames[(size_t)k * n], n));
+        }
+        OK(mi355_get_state(server, one.s_state.data()));
+        if (same(one.s_state.data(), c_frame.data(), n, "client frame != server state")) return 1;
+        if (gpu_client) {
+            OK(mi355_get_state(client, one.c_state.data()));
+            if (same(one.s_state.data(), one.c_state.data(), n, "GPU client state != server state")) return 1;
+        }
+    }
+    if (within_threshold(max_err, ss) || ss.close()) return 1;
+    printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"direct\": %s, \"gpu_client\": %s, \"width\": %d, \"height\": %d, \"frames\": %d, \"batch\": %d, "
+           "\"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, "
+           "\"max_abs_error\": %d}\n",
+           direct ? "true" : "false", gpu_client ? "true" : "false", w, h, T, B, changed, sent_bytes, mi355_wire_bytes(T, changed), (size_t)T * n, max_err);
+    return 0;
+}
+
+static int run_single(int w, int h, int T, int B, bool compact, bool direct, bool gpu_client) {
+    return compact ? run_single_compact(w, h, T, B, direct, gpu_client) : run_single_wire(w, h, T, B);
+}
+
+static int usage(const char *text) {
+    fprintf(stderr, "%s\n", text);
+    return 2;
+}
+
+int main(int argc, char **argv) {
+    long w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0, activity = -1, resync = -1, wall = 0, budget = -1;
+    bool compact = false, direct = false, gpu_client = false, burst_client = false, coalesce = false, per_frame = false, check = false;
+    const struct { const char *name; bool *on; } flags[] = {
+        {"--compact", &compact}, {"--direct", &direct}, {"--gpu-client", &gpu_client}, {"--burst-client", &burst_client},
+        {"--coalesce", &coalesce}, {"--per-frame", &per_frame}, {"--check", &check}};
+    const long any = INT32_MIN;   // (no least value)
+    const struct { const char *name; long *value, least, below; } valued[] = {   // a value below `least` is taken as `below`
+        {"--width", &w, any, 0}, {"--height", &h, any, 0}, {"--frames", &T, any, 0}, {"--batch", &B, any, 0}, {"--multi", &multi, any, 0},
+        {"--burst", &burst, any, 0}, {"--activity", &activity, 0, 0}, {"--resync", &resync, 0, 0}, {"--wall", &wall, 1, -1},
+        {"--budget", &budget, 0, 0}};
+    for (int i = 1; i < argc; i++) {   // (an option the tool does not know is ignored)
+        for (const auto &f : flags)
+            if (!strcmp(argv[i], f.name)) *f.on = true;
+        for (const auto &v : valued)
+            if (!strcmp(argv[i], v.name) && i + 1 < argc) {
+                const long x = atol(argv[++i]);
+                *v.value = x < v.least ? v.below : x;
+                break;
+            }
+    }
+    if (direct && !compact) return usage("--direct needs --compact");
+    if (gpu_client && !compact) return usage("--gpu-client needs --compact");
+    if (burst && (!multi || burst < 0)) return usage("--burst K needs --multi S and K >= 1");
+    if (burst_client && (!compact || !multi || !burst)) return usage("--burst-client needs --compact --multi S --burst K");
+    if (coalesce && (!compact || !multi || !burst || burst_client)) return usage("--coalesce needs --compact --multi S --burst K, without --burst-client");
+    if (budget >= 0 && (!compact || !multi || burst || direct || gpu_client || per_frame)) return usage("--budget BYTES needs --compact --multi S alone");
+    if (activity >= 0 && (activity == 0 || !compact || !multi || budget >= 0 || coalesce || (burst && !burst_client)))
+        return usage("--activity CELL needs CELL >= 1 and --compact --multi S, alone or with --burst K --burst-client");
+    if (activity < 0) activity = 0;
+    if (check && (!compact || !multi || budget >= 0 || coalesce || per_frame || (burst && !burst_client)))
+        return usage("--check needs --compact --multi S, alone or with --burst K --burst-client");
+    if (resync >= 0 && (!compact || !multi || budget >= 0 || coalesce || per_frame || burst_client || activity || check))
+        return usage("--resync K needs --compact --multi S, alone or with --burst B");
+    if (wall && (wall < 0 || wall > 16 || !compact || !multi || budget >= 0 || coalesce || per_frame || (burst && !burst_client && resync < 0)))
+        return usage("--wall K needs 1 <= K <= 16 and --compact --multi S, alone, with --burst B --burst-client or with --resync R");
+    if (per_frame) {
+        if (!compact || direct || gpu_client || multi) return usage("--per-frame needs --compact alone");
+        return run_per_frame(w, h, T);
+    }
+    if (!multi) return run_single(w, h, T, B, compact, direct, gpu_client);
+    if (!compact || direct || gpu_client || multi < 0) return usage("--multi S needs --compact alone and S >= 1");
+    if (resync >= 0) return run_multi_resync(w, h, T, multi, resync, burst, wall);
+    if (coalesce) return run_multi_burst_coalesce(w, h, T, multi, burst);
+    if (budget >= 0) return run_multi_budget(w, h, T, multi, budget);
+    if (burst && !burst_client) return run_multi_burst(w, h, T, multi, burst);
+    return run_multi(w, h, T, multi, burst, activity, check, wall);   // (burst == 0: tick by tick)
 }
