@@ -88,6 +88,13 @@ public:
     // apply_multi_stream; nstreams*nframes <= MI355_MAX_BATCH.
     void coalesce_multi_stream(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, int nstreams, int nframes,
                                void *d_offsets, void *d_frame_pos, void *d_cwire_out, size_t capacity_bytes);
+    // The same relay for a viewer that zooms into a camera (include/mi355diff.h, mi355_cwire_crop_cwire_batch): the burst of
+    // camera s cut to the rectangle h_rects[s] = {x0, y0, w, h} in pixels and written with the byte indices of the rectangle's own
+    // w x h frame (flags = MI355_CROP_KEEP_INDEX: of the full frame), so the viewer holds a w x h frame.  Outputs as
+    // coalesce_multi_stream's.  Blocking; nstreams*nframes <= MI355_MAX_BATCH.
+    void crop_multi_stream(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, int nstreams, int nframes,
+                           const int32_t *h_rects, unsigned flags, void *d_offsets, void *d_frame_pos, void *d_cwire_out,
+                           size_t capacity_bytes);
     // The sender's rate control behind exec_multi's compact form (include/mi355diff.h, mi355_cwire_budget_cwire_batch): record s
     // of the tick just diffed keeps at most budgets[s] entries (mi355_cwire_budget_entries turns a byte budget into one;
     // UINT32_MAX: no limit), the largest changes first: the thinned records go to d_cwire_out + d_frame_pos[s], the threshold that

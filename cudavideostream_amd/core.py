@@ -430,6 +430,34 @@ class CUDACore:
                                                             int(nstreams), int(nframes), _ptr(d_offsets), _ptr(d_frame_pos),
                                                             _ptr(d_cwire_out), int(capacity_bytes)))
 
+    # ... and a relay for a viewer that zooms into a camera: the coalesced records cut to a rectangle per stream
+    def cwire_crop_batch(self, d_cwire, counts, escapes, nstreams, nframes, rects, d_offsets, d_xs, d_diff, capacity, flags=0):
+        """cwire_coalesce_batch with stream s's sums cut to rects[s] = (x0, y0, w, h) in pixels and written with the byte index
+        of the rectangle's own w x h frame (flags = lib.CROP_KEEP_INDEX: with the full frame's index).  Applying segment s to
+        the crop of a state equals the crop of applying the stream's records to the state."""
+        self._hold(d_cwire, d_offsets, d_xs, d_diff)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+        rects = np.ascontiguousarray(rects, dtype=np.int32)
+        assert counts.size >= nstreams * nframes and escapes.size >= nstreams * nframes and rects.size >= 4 * nstreams
+        _l.check(self._lib.mi355_cwire_crop_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data, int(nstreams),
+                                                  int(nframes), rects.ctypes.data, int(flags), _ptr(d_offsets), _ptr(d_xs),
+                                                  _ptr(d_diff), int(capacity)))
+
+    def cwire_crop_cwire_batch(self, d_cwire, counts, escapes, nstreams, nframes, rects, d_offsets, d_frame_pos, d_cwire_out,
+                               capacity_bytes, flags=0):
+        """cwire_crop_batch into compact records: stream s's ONE record at d_frame_pos[s] (uint64[nstreams + 1]), the
+        canonical encoding of its segment."""
+        self._hold(d_cwire, d_offsets, d_frame_pos, d_cwire_out)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+        rects = np.ascontiguousarray(rects, dtype=np.int32)
+        assert counts.size >= nstreams * nframes and escapes.size >= nstreams * nframes and rects.size >= 4 * nstreams
+        _l.check(self._lib.mi355_cwire_crop_cwire_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
+                                                        int(nstreams), int(nframes), rects.ctypes.data, int(flags),
+                                                        _ptr(d_offsets), _ptr(d_frame_pos), _ptr(d_cwire_out),
+                                                        int(capacity_bytes)))
+
     # ... and the sender's rate control: the records of one tick held to an entry budget each
     def cwire_budget_cwire_batch(self, d_cwire, counts, escapes, d_states, nstreams, budgets, d_thresholds, d_offsets,
                                  d_frame_pos, d_cwire_out, capacity_bytes, stride=None):

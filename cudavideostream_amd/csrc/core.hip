@@ -1437,6 +1437,67 @@ int mi355_cwire_coalesce_cwire_batch(mi355_core *c, const void *d_cwire, const u
                     capacity_bytes);
 }
 
+// ---- mi355_cwire_crop_(cwire_)batch: coalesce(...) with every stream's sums cut to its rectangle -----------------------------
+// Both forms: everything is refused here, before anything is launched; the core's state is not touched.  The per-stream words
+// are the budget call's (c->cwb_hist, max_batch rows): both calls are ordered on the core's stream.
+static int crop(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams, int nframes,
+                const int32_t *h_rects, unsigned flags, bool cwire, void *d_offsets, void *d_frame_pos, void *d_cwire_out, void *d_xs,
+                void *d_diff, size_t capacity) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nstreams < 0 || nframes < 0) return fail(MI355_ERR_INVALID, "nstreams or nframes < 0");
+    const int64_t B64 = (int64_t)nstreams * nframes;
+    if (B64 > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams * nframes above max_batch");
+    const int B = (int)B64;
+    if (flags & ~MI355_CROP_KEEP_INDEX) return fail(MI355_ERR_INVALID, "unknown flag bit (MI355_CROP_KEEP_INDEX is the only one)");
+    if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_cwire_out & 3u) || ((uintptr_t)d_xs & 3u))
+        return fail(MI355_ERR_INVALID, "d_cwire, d_cwire_out, d_offsets and d_xs must be 4-byte aligned");
+    if ((uintptr_t)d_frame_pos & 7u) return fail(MI355_ERR_INVALID, "d_frame_pos must be 8-byte aligned");
+    if (B == 0) return write_empty_heads(c, d_offsets, d_frame_pos);
+    if (!d_cwire || !h_counts || !h_escapes) return fail(MI355_ERR_INVALID, "null stream pointer");
+    if (!h_rects) return fail(MI355_ERR_INVALID, "null h_rects");
+    if (!d_offsets || (cwire ? !d_frame_pos || !d_cwire_out : !d_xs || !d_diff)) return fail(MI355_ERR_INVALID, "null output pointer");
+    for (int s = 0; s < nstreams; s++) {
+        const int32_t *r = h_rects + 4 * (size_t)s;
+        if (r[0] < 0 || r[1] < 0 || r[2] < 0 || r[3] < 0) return fail(MI355_ERR_INVALID, "rectangle with a negative member");
+        if ((int64_t)r[0] + r[2] > c->cfg.width || (int64_t)r[1] + r[3] > c->cfg.height)
+            return fail(MI355_ERR_INVALID, "rectangle outside the frame");
+    }
+    CwaTable tab;
+    if (int rc = cwa_table(c, h_counts, h_escapes, B, &tab)) return rc;
+    if (int rc = check_regions({input_region(d_cwire, tab.bytes)},   // (the outputs of the other form: nowhere)
+                               {offsets_region(d_offsets, nstreams), cwire ? frame_pos_region(d_frame_pos, nstreams) : Region{},
+                                cwire ? Region{d_cwire_out, capacity, "d_cwire_out"} : Region{},
+                                cwire ? Region{} : Region{d_xs, 4 * (uint64_t)capacity, "d_xs"},
+                                cwire ? Region{} : Region{d_diff, capacity, "d_diff"}}))
+        return rc;
+    if (int rc = use_device(c)) return rc;
+    const CwaArgs a = cwa_args(c, d_cwire);
+    CwcOut o{};
+    o.offsets = (uint32_t *)d_offsets;
+    o.frame_pos = (uint64_t *)d_frame_pos;
+    o.cwire = (uint8_t *)d_cwire_out;
+    o.xs = (int32_t *)d_xs;
+    o.diff = (uint8_t *)d_diff;
+    o.capacity = capacity;
+    HIP_TRY(launch_cwire_crop(a, tab.fr.data(), nstreams, nframes, h_rects, (uint32_t)c->cfg.width, (flags & MI355_CROP_KEEP_INDEX) != 0,
+                              c->cwb_hist, o, cwire, c->stream));
+    return MI355_OK;
+}
+
+int mi355_cwire_crop_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams,
+                           int nframes, const int32_t *h_rects, unsigned flags, void *d_offsets, void *d_xs, void *d_diff,
+                           size_t capacity) {
+    return crop(c, d_cwire, h_counts, h_escapes, nstreams, nframes, h_rects, flags, false, d_offsets, nullptr, nullptr, d_xs, d_diff,
+                capacity);
+}
+
+int mi355_cwire_crop_cwire_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams,
+                                 int nframes, const int32_t *h_rects, unsigned flags, void *d_offsets, void *d_frame_pos,
+                                 void *d_cwire_out, size_t capacity_bytes) {
+    return crop(c, d_cwire, h_counts, h_escapes, nstreams, nframes, h_rects, flags, true, d_offsets, d_frame_pos, d_cwire_out, nullptr,
+                nullptr, capacity_bytes);
+}
+
 // ---- mi355_cwire_budget_cwire_batch: the records of one tick held to an entry budget each ------------------------------------
 size_t mi355_cwire_budget_entries(size_t frame_bytes, size_t record_bytes) {
     // the largest n <= frame_bytes whose worst record (e = min(n, frame_bytes / 256) escapes) fits; the size rises with n

@@ -239,6 +239,19 @@ hipError_t launch_cwire_activity(const CwaArgs &a, const CwaFrame *records, int 
                                  uint32_t *cells, uint32_t *summary, hipStream_t s);
 hipError_t launch_activity(const uint32_t *d_offsets, const int32_t *xs, int nstreams, int nframes, const ActGeom &g, bool accumulate,
                            uint32_t *cells, uint32_t *summary, hipStream_t s);
+// mi355_cwire_crop_(cwire_)batch: the coalescer with every stream's sums cut to its rectangle rects[s] = {x0, y0, w, h} (host array,
+// checked by the caller against width x height) and, unless keep_index, re-indexed to the rectangle's w x h frame.  words: the budget
+// call's per-stream rows (kCwbWords words apart), of which a stream's first six are written (its rows, its column bytes and the
+// map's two constants: CropWords); a and o as for the coalescer.
+constexpr int kCropStreams = 128;   // rectangles per k_crop_facts launch (kernel arguments)
+struct CropArgs {
+    int32_t first;        // the launch's first stream
+    uint32_t row_bytes;   // 3W
+    int32_t keep_index;
+    int32_t rect[kCropStreams][4];
+};
+hipError_t launch_cwire_crop(const CwaArgs &a, const CwaFrame *records, int nstreams, int nframes, const int32_t *rects, uint32_t width,
+                             bool keep_index, uint32_t *words, const CwcOut &o, bool cwire, hipStream_t s);
 // mi355_cwire_check_batch: verdicts[b][0 .. 4) of record b (include/mi355diff.h); a.ftab and a.chunk are the scratch it uses, a.n the
 // frame bytes; a.dir / a.state / a.out / a.stride / a.ntiles unused
 hipError_t launch_cwire_check(const CwaArgs &a, const CwaFrame *records, int nrecords, uint32_t *verdicts, hipStream_t s);

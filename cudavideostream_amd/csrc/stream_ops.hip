@@ -15,6 +15,8 @@
 //                           alone (mi355_cwire_coalesce_batch / _cwire_batch);
 //   k_cwb_*               : one record per stream thinned to an entry budget, the caller's states reverted where entries are
 //                           dropped (mi355_cwire_budget_cwire_batch);
+//   k_crop_*              : a stream's coalesced records cut to a rectangle and re-indexed to the rectangle's frame
+//                           (mi355_cwire_crop_batch / _cwire_batch);
 //   k_act_*               : where the entries of each stream's records land: a grid of counts per cell, a bounding box and the
 //                           peak cell per stream (mi355_cwire_activity_batch; mi355_activity_batch from the arrays).
 //   k_cwk_*               : one verdict of four words per compact record -- is it well-formed and canonical, and where not --
@@ -1030,32 +1032,42 @@ __device__ __forceinline__ uint64_t cwc_lane_mask(const uint8_t *s, int lane) {
     return m;
 }
 
-// 1 + the tile-relative position of the last nonzero byte of the lanes below this one that hold any (0: none does);
-// lanes: the ballot of the lanes that hold one
-__device__ __forceinline__ uint32_t cwc_end_before(uint64_t m, uint64_t lanes, int lane) {
-    const uint32_t my_end = m ? 64u * lane + 64u - (uint32_t)__builtin_clzll(m) : 0u;
+// The index an entry of the tile is written with: its byte index x itself (the crop call maps x into its rectangle's frame:
+// any map that ascends with x and never widens the distance of two kept bytes can stand here, so that a gap >= 255 still opens
+// between lanes only)
+struct CwcIdentity {
+    __device__ __forceinline__ uint32_t operator()(uint32_t x) const { return x; }
+};
+
+// 1 + the written index of the last nonzero byte of the lanes below this one that hold any (0: none does); lanes: the ballot
+// of the lanes that hold one
+template <class Map>
+__device__ __forceinline__ uint32_t cwc_end_before(uint64_t m, uint64_t lanes, int lane, uint32_t lo, const Map &map) {
+    const uint32_t my_end = m ? map(lo + 64u * lane + 63u - (uint32_t)__builtin_clzll(m)) + 1u : 0u;
     const uint64_t below = lanes & ((1ull << lane) - 1ull);
     const int src = below ? 63 - __builtin_clzll(below) : 0;
     const uint32_t end = (uint32_t)__shfl((int)my_end, src, 64);
     return below ? end : 0u;
 }
 
-// The four facts of the tile in LDS (s[0] is byte lo): {nonzero bytes, index of the first, index of the last, gaps >= 255 inside}
-__device__ __forceinline__ uint4 cwc_tile_facts(const uint8_t *s, uint32_t lo, int lane) {
+// The four facts of the tile in LDS (s[0] is byte lo): {nonzero bytes, index of the first, index of the last, gaps >= 255 inside},
+// indices and gaps as `map` writes them
+template <class Map = CwcIdentity>
+__device__ __forceinline__ uint4 cwc_tile_facts(const uint8_t *s, uint32_t lo, int lane, const Map map = Map()) {
     const uint64_t m = cwc_lane_mask(s, lane);
     const uint64_t lanes = __ballot(m != 0);
     const uint32_t count = cwa_wave_sum((uint32_t)__popcll(m));
-    const uint32_t end = cwc_end_before(m, lanes, lane);
+    const uint32_t end = cwc_end_before(m, lanes, lane, lo, map);
+    const uint32_t my_first = m ? map(lo + 64u * lane + (uint32_t)__builtin_ctzll(m)) : 0u;
     // the gap in front of a lane's first nonzero byte, where a lane below holds one (the tile's first has no gap inside the tile)
-    const bool wide = m && end && 64u * lane + (uint32_t)__builtin_ctzll(m) - end >= 255u;
+    const bool wide = m && end && my_first - end >= 255u;
     const uint32_t gaps = (uint32_t)__popcll(__ballot(wide));
     uint32_t first = 0, last = 0;
     if (lanes) {
         const int l0 = __ffsll((unsigned long long)lanes) - 1, l1 = 63 - __builtin_clzll(lanes);
-        const uint32_t my_first = m ? 64u * lane + (uint32_t)__builtin_ctzll(m) : 0u;
-        const uint32_t my_last = m ? 64u * lane + 63u - (uint32_t)__builtin_clzll(m) : 0u;
-        first = lo + (uint32_t)__shfl((int)my_first, l0, 64);
-        last = lo + (uint32_t)__shfl((int)my_last, l1, 64);
+        const uint32_t my_last = m ? map(lo + 64u * lane + 63u - (uint32_t)__builtin_clzll(m)) : 0u;
+        first = (uint32_t)__shfl((int)my_first, l0, 64);
+        last = (uint32_t)__shfl((int)my_last, l1, 64);
     }
     return make_uint4(count, first, last, gaps);
 }
@@ -1184,16 +1196,17 @@ __device__ __forceinline__ void cwc_store_bytes(uint8_t *g, const uint8_t *s, ui
 
 // The entries of the tile in LDS (s[0] is byte lo; fact: its scanned word {nonzero bytes, entries before, escapes before, end
 // before}) to their place in stream st's record {n, e} at fp0 (compact form) or segment at `seg` (arrays form).  s_code / s_diff:
-// kCwaTile + 8 bytes of LDS each (s_code unused in the arrays form).  One wave.
-template <bool CWIRE>
+// kCwaTile + 8 bytes of LDS each (s_code unused in the arrays form).  One wave.  map: the facts' (end before included).
+template <bool CWIRE, class Map = CwcIdentity>
 __device__ __forceinline__ void cwc_emit_tile(const uint8_t *s, uint8_t *s_code, uint8_t *s_diff, const uint4 fact, const CwcOut &o,
-                                              uint32_t seg, uint32_t n, uint64_t fp0, uint32_t e, uint32_t lo, int lane) {
+                                              uint32_t seg, uint32_t n, uint64_t fp0, uint32_t e, uint32_t lo, int lane,
+                                              const Map map = Map()) {
     const uint64_t m = cwc_lane_mask(s, lane);
     const uint64_t lanes = __ballot(m != 0);
     uint32_t zero = 0;
     const uint32_t r0 = block_exclusive_scan<1>((uint32_t)__popcll(m), (uint32_t *)nullptr, zero);   // tile-relative rank
-    const uint32_t before = cwc_end_before(m, lanes, lane);
-    uint32_t end = before ? lo + before : fact.w;   // 1 + the index of the entry before the lane's first
+    const uint32_t before = cwc_end_before(m, lanes, lane, lo, map);
+    uint32_t end = before ? before : fact.w;   // 1 + the index of the entry before the lane's first
     // where the tile's entries go, and the alignment of that place
     uint8_t *g_code = nullptr, *g_diff;
     uint32_t *g_esc = nullptr;
@@ -1209,7 +1222,7 @@ __device__ __forceinline__ void cwc_emit_tile(const uint8_t *s, uint8_t *s_code,
         g_diff = o.diff + at;
     }
     const uint32_t sh_code = (uint32_t)((uintptr_t)g_code & 3u), sh_diff = (uint32_t)((uintptr_t)g_diff & 3u);
-    const uint32_t first_gap = m ? lo + 64u * lane + (uint32_t)__builtin_ctzll(m) - end : 0u;
+    const uint32_t first_gap = m ? map(lo + 64u * lane + (uint32_t)__builtin_ctzll(m)) - end : 0u;
     const bool escaped = CWIRE && m && first_gap >= 255u;
     const uint32_t erank = fact.z + (uint32_t)__popcll(__ballot(escaped) & ((1ull << lane) - 1ull));
     if (escaped && erank < e) __builtin_nontemporal_store(first_gap, g_esc + erank);
@@ -1222,7 +1235,7 @@ __device__ __forceinline__ void cwc_emit_tile(const uint8_t *s, uint8_t *s_code,
         for (int j = 0; j < 4; j++) {
             const uint32_t d = (v >> (8 * j)) & 255u;
             if (!d) continue;
-            const uint32_t x = lo + 64u * lane + 4u * i + j;
+            const uint32_t x = map(lo + 64u * lane + 4u * i + j);
             if (CWIRE) {
                 const uint32_t g = x - end;
                 s_code[sh_code + r] = (uint8_t)(g < 255u ? g : 255u);
@@ -1602,6 +1615,140 @@ __global__ __launch_bounds__(256) void k_act_summary(const uint32_t *cells, uint
         sum[6] = (uint32_t)(best >> 32);
         sum[7] = best ? ~(uint32_t)best : 0u;
     }
+}
+
+// ---- mi355_cwire_crop_(cwire_)batch: the coalesced records of stream s cut to its rectangle, re-indexed to the rectangle's frame -----
+// The coalescer with a filter on the tile, as the budget call is: behind the directory of the nstreams*nframes records
+//   k_crop_facts (grid: tiles x streams, one wave) : the rectangles {x0, y0, w, h} of its streams are kernel arguments (kCropStreams
+//                                                    per launch); a stream's first tile leaves the six words made of them
+//                                                    in the budget call's per-stream rows (the two calls are ordered on one
+//                                                    stream) for k_crop_emit.  A tile whose bytes miss the rectangle's rows stores
+//                                                    the all-zero fact and reads no record byte; the others sum their records in
+//                                                    LDS (cwc_sum_tile), zero the bytes outside the rectangle and take the four
+//                                                    facts in MAPPED indices
+//   k_cwc_scan, k_cwc_place                        : the coalescer's, unchanged (they see indices, whatever frame they are of)
+//   k_crop_emit  (grid: tiles x streams, one wave) : the same tile from the same bytes, its entries written with mapped indices
+// The map: byte x of row r = x / 3W, column byte x - r*3W, is byte (r - y0)*3w + column byte - 3*x0 of the rectangle's frame
+// = x - r*(3W - 3w) - (y0*3w + 3*x0).  It ascends with x over the kept bytes and never widens a distance, so the lane-local
+// reasoning of the coalescer's tile functions holds (CwcIdentity above).  MI355_CROP_KEEP_INDEX: skip = base = 0; a rectangle
+// as wide as the frame has skip = 0 too, and no division is made.  Otherwise a lane divides once, for its first byte, and again
+// only for a byte of a later row.
+struct CropWords {
+    uint32_t row0, row1;   // rows [row0, row1) (row0 == row1: nothing is kept)
+    uint32_t col0, col1;   // column bytes [col0, col1) of a row
+    uint32_t skip, base;   // 3W - 3w, y0*3w + 3*x0
+};
+
+__device__ __forceinline__ CropWords crop_words(const CropArgs &h, uint32_t j) {
+    const uint32_t x0 = (uint32_t)h.rect[j][0], y0 = (uint32_t)h.rect[j][1], w = (uint32_t)h.rect[j][2], ht = (uint32_t)h.rect[j][3];
+    CropWords c;
+    c.row0 = y0;
+    c.row1 = w ? y0 + ht : y0;   // (no column: no row either, and every tile returns on its rows)
+    c.col0 = 3u * x0;
+    c.col1 = 3u * (x0 + w);
+    c.skip = h.keep_index ? 0u : h.row_bytes - 3u * w;
+    c.base = h.keep_index ? 0u : y0 * 3u * w + 3u * x0;
+    return c;
+}
+
+struct CropMap {
+    ActDiv row;            // bytes of a full row, 3W
+    uint32_t skip, base;
+    uint32_t shift0, next;   // of the row r0 of the lane's first byte: r0*skip + base, and the first byte of the row behind it
+    __device__ __forceinline__ CropMap(const ActDiv row_, const CropWords &c, uint32_t r0)
+        : row(row_), skip(c.skip), base(c.base), shift0(r0 * c.skip + c.base), next((r0 + 1u) * row_.d) {}
+    // x: a byte of the lane, so never before its first
+    __device__ __forceinline__ uint32_t operator()(uint32_t x) const {
+        if (skip == 0u) return x - base;   // (uniform)
+        return x < next ? x - shift0 : x - act_div(x, row) * skip - base;
+    }
+};
+
+// Stream st's summed tile [lo, lo + len) in LDS with the bytes outside its rectangle zeroed; false: the tile misses the
+// rectangle's rows (no record byte was read) or no record has an entry in it, and s was not touched.  r0: the row of the lane's
+// first byte, lo + 64*lane.
+__device__ __forceinline__ bool crop_tile(uint8_t *s, const CwaArgs &a, int nframes, const CropWords &c, uint32_t rb, uint32_t r0,
+                                          uint32_t st, uint32_t tile, uint32_t lo, uint32_t len, int lane) {
+    // rows [row0, row1) are bytes [rb*row0, rb*row1) of the frame, at most N < 2^32
+    const uint32_t last = lo + (len - 1u);
+    if (c.row0 >= c.row1 || last < rb * c.row0 || lo >= rb * c.row1) return false;
+    if (!cwc_sum_tile(s, a, nframes, st, tile, lo, lo + len, lane)) return false;
+    if (c.col0 == 0u && c.col1 == rb && lo >= rb * c.row0 && last < rb * c.row1) return true;   // every byte of the tile is kept
+    // the lane's 64 bytes, row by row (several rows when 3W < 64, a part of one when 3W > 64): bit p of keep = byte p stays.
+    // Bytes past the frame's end are 0 already, whatever the mask says of them.
+    uint32_t r = r0, col = lo + 64u * lane - r0 * rb;   // col < rb
+    uint64_t keep = 0;
+    for (uint32_t p = 0; p < 64u; r++, col = 0u) {
+        const uint32_t seg = rb - col < 64u - p ? rb - col : 64u - p;   // >= 1
+        if (r >= c.row0 && r < c.row1) {
+            const uint32_t k0 = col > c.col0 ? col : c.col0, k1 = col + seg < c.col1 ? col + seg : c.col1;
+            if (k0 < k1) {
+                const uint32_t cnt = k1 - k0;   // <= 64
+                keep |= (cnt == 64u ? ~0ull : (1ull << cnt) - 1ull) << (p + k0 - col);
+            }
+        }
+        p += seg;
+    }
+    if (keep != ~0ull) {
+        uint32_t *w = (uint32_t *)s + 16 * lane;
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const uint32_t nib = (uint32_t)(keep >> (4 * i)) & 15u;
+            if (nib == 15u) continue;
+            w[i] &= ((nib & 1u) ? 0xffu : 0u) | ((nib & 2u) ? 0xff00u : 0u) | ((nib & 4u) ? 0xff0000u : 0u) | ((nib & 8u) ? 0xff000000u : 0u);
+        }
+    }
+    __syncthreads();
+    return true;
+}
+
+__global__ __launch_bounds__(64) void k_crop_facts(const CwaArgs a, int nframes, uint32_t *words, const CropArgs h, const ActDiv row) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
+    uint8_t *s = (uint8_t *)s_q;
+    const int lane = threadIdx.x;
+    const uint32_t j = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles, st = (uint32_t)h.first + j;
+    const CropWords c = crop_words(h, j);
+    if (tile == 0 && lane == 0) {
+        uint32_t *rw = words + (size_t)st * kCwbWords;
+        rw[0] = c.row0, rw[1] = c.row1, rw[2] = c.col0, rw[3] = c.col1, rw[4] = c.skip, rw[5] = c.base;
+    }
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    const uint32_t r0 = act_div(lo + 64u * lane, row);
+    uint4 *fact = a.chunk + (size_t)st * a.ntiles + tile;
+    if (!crop_tile(s, a, nframes, c, row.d, r0, st, tile, lo, len, lane)) {
+        if (lane == 0) *fact = make_uint4(0u, 0u, 0u, 0u);
+        return;
+    }
+    const uint4 f = cwc_tile_facts(s, lo, lane, CropMap(row, c, r0));
+    if (lane == 0) *fact = f;
+}
+
+template <bool CWIRE>
+__global__ __launch_bounds__(64) void k_crop_emit(const CwaArgs a, const CwcOut o, int nframes, const uint32_t *words, const ActDiv row) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
+    __shared__ uint32_t s_code32[CWIRE ? kCwaTile / 4 + 2 : 1], s_diff32[kCwaTile / 4 + 2];
+    uint8_t *s = (uint8_t *)s_q;
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
+    const uint4 fact = a.chunk[(size_t)st * a.ntiles + tile];   // {kept bytes, entries before, escapes before, mapped end before}
+    const uint32_t *rw = words + (size_t)st * kCwbWords;         // (loaded beside the fact, not behind it)
+    const CropWords c{rw[0], rw[1], rw[2], rw[3], rw[4], rw[5]};
+    if (fact.x == 0) return;
+    const uint32_t seg = o.offsets[st], n = o.offsets[st + 1] - seg;
+    uint64_t fp0 = 0;
+    uint32_t e = 0;
+    if (CWIRE) {
+        fp0 = o.frame_pos[st];
+        const uint64_t fp1 = o.frame_pos[st + 1];
+        if (fp1 > o.capacity) return;   // the record does not fit: skipped whole, by every workgroup alike
+        e = cwire_record_escapes(fp1 - fp0, n);
+    }
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    const uint32_t r0 = act_div(lo + 64u * lane, row);
+    if (!crop_tile(s, a, nframes, c, row.d, r0, st, tile, lo, len, lane)) return;   // (the facts say otherwise)
+    cwc_emit_tile<CWIRE>(s, (uint8_t *)s_code32, (uint8_t *)s_diff32, fact, o, seg, n, fp0, e, lo, lane, CropMap(row, c, r0));
 }
 
 // ---- mi355_cwire_check_batch: one verdict of four words per record, from the records alone (include/mi355diff.h) ---------------
@@ -2111,6 +2258,36 @@ hipError_t launch_cwire_budget(const CwaArgs &a, const CwaFrame *records, int ns
     hipLaunchKernelGGL(k_cwc_scan<true>, dim3(nstreams), dim3(256), 0, s, a, o);
     hipLaunchKernelGGL(k_cwc_place<true>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, nstreams);
     if (a.ntiles) hipLaunchKernelGGL(k_cwb_emit, tiles, dim3(64), 0, s, a, o, (const uint32_t *)hist, thr0);
+    return hipGetLastError();
+}
+
+hipError_t launch_cwire_crop(const CwaArgs &a, const CwaFrame *records, int nstreams, int nframes, const int32_t *rects, uint32_t width,
+                             bool keep_index, uint32_t *words, const CwcOut &o, bool cwire, hipStream_t s) {
+    if (nstreams <= 0 || nframes <= 0) return hipSuccess;
+    const ActDiv row = act_divisor(a.ntiles ? 3u * width : 1u);
+    if (a.ntiles) {
+        launch_cwa_directory(a, records, nstreams * nframes, s);
+        CropArgs h{};
+        h.row_bytes = 3u * width;
+        h.keep_index = keep_index ? 1 : 0;
+        for (int s0 = 0; s0 < nstreams; s0 += kCropStreams) {
+            h.first = s0;
+            const int ns = nstreams - s0 < kCropStreams ? nstreams - s0 : kCropStreams;
+            for (int j = 0; j < ns; j++)
+                for (int k = 0; k < 4; k++) h.rect[j][k] = rects[4 * (size_t)(s0 + j) + k];
+            hipLaunchKernelGGL(k_crop_facts, dim3(a.ntiles * (uint32_t)ns), dim3(64), 0, s, a, nframes, words, h, row);
+        }
+    }
+    const dim3 tiles(a.ntiles * (uint32_t)nstreams);
+    if (cwire) {
+        hipLaunchKernelGGL(k_cwc_scan<true>, dim3(nstreams), dim3(256), 0, s, a, o);
+        hipLaunchKernelGGL(k_cwc_place<true>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, nstreams);
+        if (a.ntiles) hipLaunchKernelGGL(k_crop_emit<true>, tiles, dim3(64), 0, s, a, o, nframes, (const uint32_t *)words, row);
+    } else {
+        hipLaunchKernelGGL(k_cwc_scan<false>, dim3(nstreams), dim3(256), 0, s, a, o);
+        hipLaunchKernelGGL(k_cwc_place<false>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, nstreams);
+        if (a.ntiles) hipLaunchKernelGGL(k_crop_emit<false>, tiles, dim3(64), 0, s, a, o, nframes, (const uint32_t *)words, row);
+    }
     return hipGetLastError();
 }
 

@@ -25,6 +25,7 @@ OPT_PIPELINE, OPT_MEDIAN_ROWS, OPT_SCAN_EPOCH_LEFT = 1, 6, 7   # MI355_OPT_* (id
 FLAG_OWN_QUEUES = 1   # MI355_FLAG_*
 PREPARE_BATCHES, PREPARE_GRAY_CHAIN, PREPARE_RED_CLEAR, PREPARE_CONV_KXK, PREPARE_EXEC, PREPARE_ALL = 1, 2, 4, 8, 16, 31   # MI355_PREPARE_*
 PREPARE_EXEC_CWIRE = 32   # (not part of PREPARE_ALL)
+CROP_KEEP_INDEX = 1   # MI355_CROP_*
 CWIRE_BAD_CODES, CWIRE_BAD_RANGE, CWIRE_BAD_PAD, CWIRE_BAD_ESCAPE, CWIRE_BAD_HEADER = 1, 2, 4, 8, 16   # MI355_CWIRE_BAD_*
 
 
@@ -95,6 +96,10 @@ SYMBOLS = {
                                              C.c_void_p, C.c_void_p, C.c_size_t]),
     "mi355_cwire_coalesce_cwire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mi355_cwire_crop_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mi355_cwire_crop_cwire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                               C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "mi355_cwire_budget_cwire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "mi355_cwire_budget_entries": (C.c_size_t, [C.c_size_t, C.c_size_t]),

@@ -93,7 +93,8 @@ typedef struct mi355_config {
  *      + mi355_cwire_check_host, mi355_cwire_check_batch, MI355_CWIRE_BAD_* (additions only);
  *      + mi355_state_tiles, mi355_state_digest_host, mi355_state_digest_batch, mi355_refresh_cwire_batch,
  *      mi355_state_clear_tiles_batch (additions only);
- *      + mi355_wall_thumb_size, mi355_wall_compose_batch, mi355_cwire_touched_tiles_batch (additions only) */
+ *      + mi355_wall_thumb_size, mi355_wall_compose_batch, mi355_cwire_touched_tiles_batch (additions only);
+ *      + mi355_cwire_crop_batch, mi355_cwire_crop_cwire_batch, MI355_CROP_KEEP_INDEX (additions only) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -499,6 +500,66 @@ int mi355_cwire_coalesce_batch(mi355_core *core, const void *d_cwire, const uint
 int mi355_cwire_coalesce_cwire_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts,
                                      const uint32_t *h_escapes, int nstreams, int nframes, void *d_offsets,
                                      void *d_frame_pos, void *d_cwire_out, size_t capacity_bytes);
+
+/* A camera cropped: the records of mi355_cwire_coalesce_* (same input, same batch index b = s*nframes + t, the headers
+ * h_counts[b] / h_escapes[b] from the host, the header words in the buffer not trusted) cut to one rectangle per stream,
+ * h_rects[s] = {x0, y0, w, h} in pixels of the core's W x H frame, and re-indexed to the rectangle's own w x h frame.  For a
+ * viewer that zooms into a part of one camera of a wall and a relay that thins a camera's traffic to the region somebody looks
+ * at: the client holds a w x h state, not a full one.  Cropping commutes with the client's state[x] += diff, so it is exact and
+ * needs no state.
+ *   Sums and selection: sum_s[x] = the uint8 wrap-around sum of stream s's differences at byte index x < N, as in the coalescer.
+ *   An entry (x, sum_s[x]) with sum_s[x] != 0 is kept if its pixel lies inside the rectangle: row = x / (3*W) in [y0, y0 + h) and
+ *   column byte = x % (3*W) in [3*x0, 3*(x0 + w)).
+ *   Index map: a kept entry is written with index (row - y0)*3*w + column byte - 3*x0, its byte index in the w x h BGR24 frame of
+ *   the rectangle (N'_s = 3*w*h bytes).  The map is monotone: the kept entries stay in ascending order.  With flags =
+ *   MI355_CROP_KEEP_INDEX the entry is written with x unchanged instead: the record then updates only the rectangle of a
+ *   full-size state.  w == 0 or h == 0 selects nothing and yields an n = 0 record of 8 bytes.  With nframes > 1 the result is
+ *   the crop of the coalesced burst; with nframes == 1, the full-frame rectangle and a record this library made, the input
+ *   comes back byte for byte.
+ *   Outputs: those of the coalescer -- d_offsets, uint32[nstreams + 1]; compact form: record s, the canonical encoding of
+ *   segment s (pad bytes zero, headers written), at d_cwire_out + d_frame_pos[s], d_frame_pos uint64[nstreams + 1] and always
+ *   exact; a record is written only if it fits, one that does not is skipped whole and the ones behind it that fit are still
+ *   written; arrays form: entries at or past `capacity` are dropped, the offsets stay exact.  mi355_cwire_bytes_max(N, nstreams)
+ *   always suffices as capacity, and without MI355_CROP_KEEP_INDEX so does the sum over s of mi355_cwire_bytes_max(3*w_s*h_s, 1).
+ *   Law: for any N-byte state A let crop(A) be the rectangle of A as a w x h frame.  Applying output record s to crop(A) equals
+ *   the crop of applying the stream's nframes records to A.  With MI355_CROP_KEEP_INDEX, applying it to A changes exactly the
+ *   rectangle, in the same way.
+ *   Malformed content under consistent headers: the coalescer's guarantees -- nothing is read outside the input span, nothing is
+ *   written outside the outputs, an escape ranked at or past e and an index >= N contribute nothing.  Output record s is still
+ *   well-formed and canonical: mi355_cwire_check_host(N'_s, ...) gives verdict 0 (against N with MI355_CROP_KEEP_INDEX).
+ *   Refused with MI355_ERR_INVALID before anything is launched or written: whatever mi355_cwire_coalesce_* refuses; a null
+ *   h_rects when nstreams*nframes > 0; a flag bit other than MI355_CROP_KEEP_INDEX; a rectangle with a negative member; a
+ *   rectangle with x0 + w > W or y0 + h > H (computed in 64 bits).  nstreams*nframes == 0 writes offsets[0] = 0 (and
+ *   frame_pos[0] = 0) and nothing else.
+ * Asynchronous on the core's stream, behind the last expansion of this core as every consumer of a packed stream is; with a
+ * caller's stream everything runs on it in call order.  Nothing is allocated inside the call and nothing is copied to the
+ * device: the rectangles travel as kernel arguments of the first tile pass, which leaves six words per stream in the per-stream
+ * words of mi355_cwire_budget_cwire_batch for the second (the two calls are ordered on one stream).  The core's state is neither
+ * read nor written.
+ * The directory kernels on the nstreams*nframes records, then the coalescer's four launches with a filter on the tile: a
+ * 4096-byte tile whose byte range misses the rectangle's rows [3W*y0, 3W*(y0 + h)) stores the all-zero fact and reads no record
+ * byte; the others sum their records in LDS, zero the bytes outside the rectangle (a lane's 64 bytes may span several rows when
+ * 3W < 64; a tile may sit inside one row when 3W > 4096) and take the four facts in mapped indices; the coalescer's scan and
+ * placement follow unchanged; the tile grid runs again and writes the entries with mapped indices.  The row of a byte comes from
+ * an exact multiply-and-correct division by 3W, once per lane and again only where a lane's bytes reach a later row.
+ * Measured (profiles/multi_crop.json: tools/bench_multi.py --legs crop; the compact form at 1080p, T = 1, median of five rounds,
+ * spread of the rounds 0.1 - 1.0 %, against mi355_cwire_coalesce_cwire_batch on the same records in the same run), us per stream
+ * at S = 4 / 16 / 64: webcam-like input (137 k entries per stream, 37 k in the quarter picture) coalesce 15.9 / 8.1 / 6.2, the
+ * quarter-picture crop 15.5 / 6.8 / 4.6, the full-frame crop 16.6 / 8.6 / 6.7; local input (a block moving over a still
+ * background, 4.8 k entries) coalesce 16.6 / 5.4 / 2.4, quarter 17.8 / 5.7 / 2.6, full 16.9 / 5.5 / 2.5.  The expectation --
+ * the quarter-picture crop no slower than that coalesce call by more than the rounds' spread -- is met on the webcam-like input
+ * (0.97 / 0.83 / 0.74 of it) and MISSED on the local input (1.07 / 1.06 / 1.10: there nearly every tile is empty in both calls
+ * and the kept ones pay the mask and the map); the full-frame crop is 2 - 8 % slower than the coalesce call (1 to 30 us per call),
+ * more than the spread, with no table launch left to blame.  An earlier attempt at this call was
+ * not merged; this one rests on the budget call's filtered tile and on the one record table and region test of core.hip.
+ * DESIGN.md section 4, "Cropping records". */
+#define MI355_CROP_KEEP_INDEX 1u
+int mi355_cwire_crop_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
+                           int nstreams, int nframes, const int32_t *h_rects, unsigned flags, void *d_offsets, void *d_xs,
+                           void *d_diff, size_t capacity);
+int mi355_cwire_crop_cwire_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
+                                 int nstreams, int nframes, const int32_t *h_rects, unsigned flags, void *d_offsets,
+                                 void *d_frame_pos, void *d_cwire_out, size_t capacity_bytes);
 
 /* A tick held to a budget: the sender's rate control.  The nstreams compact records mi355_diff_multi_cwire_batch just wrote
  * (back to back where h_counts[s] / h_escapes[s] put them; the headers come from the host and are not trusted in the buffer, as

@@ -62,6 +62,14 @@ sender's rate control, in microseconds per stream, ONE JSON line for all S:
                re-diff a caller has without the call -- and it still lacks the threshold choice.
 Every pass of a timed window works on its own copy of the S states (restored outside the window).
 
+The crop leg (--legs crop, a run of its own: `--legs crop --streams 4,16,64 > profiles/multi_crop.json`) measures the crop call on
+the records of one tick (T = 1), in microseconds per stream, ONE JSON line for all S, on the webcam-like and the local input:
+  coalesce       mi355_cwire_coalesce_cwire_batch on the same records: the nearest route a relay has without the crop call;
+  crop_quarter   mi355_cwire_crop_cwire_batch with the rectangle (W/4, H/4, W/2, H/2) for every stream;
+  crop_full      the same call with the full frame: the coalescer's work plus the rectangle table's launch.
+The expectations to test: `crop_quarter` no slower than `coalesce` by more than the rounds' spread
+(`quarter_no_slower_than_coalesce`), and `crop_full` within the spread plus the one table launch (`full_minus_coalesce_us_per_call`).
+
 The activity leg (--legs activity, a run of its own: `--legs activity --streams 4,16,64 > profiles/multi_activity.json`) measures
 the motion grids, in microseconds per record, ONE JSON line: S = 4, 16, 64 (--streams) with T = 1 and S = 16 with T = 16, on both
 inputs of the burst-client leg:
@@ -1027,6 +1035,110 @@ def run_coalesce(W, H, S, T, rounds, kind):
     return out
 
 
+def run_crop(W, H, S, rounds, kind):
+    """The crop leg for one S and one input, T = 1 -> its dictionary.  coalesce: mi355_cwire_coalesce_cwire_batch on the records of
+    one tick, the nearest route without the crop call.  crop_quarter / crop_full: mi355_cwire_crop_cwire_batch on the same records
+    with the rectangle (W/4, H/4, W/2, H/2) for every stream, and with the full frame.  All on one core's own stream, alternating
+    within every round."""
+    import numpy as np
+    from cudavideostream_amd import CUDACore, cwire_bytes_max
+    dev = torch.device("cuda", 0)
+    n, T = 3 * W * H, 1
+    passes = 2 * max(1, 1024 // S)                     # ~2 k records per timed window
+    if kind == "webcam":                                # run_burst's input: one stream cut into S pieces
+        _, web = synth.webcam_stream(S + 1, W, H, device=dev)
+        web = web.reshape(S + 1, n)
+        states0, fwd = web[0:S].clone(), web[1:].reshape(S, T, n)
+    else:
+        states0, fwd = local_streams(S, T, W, H, dev)
+    per_call = min(S, max(1, ((1 << 32) - 1) // n))                  # streams per call: max_batch * N < 2^32
+    chunks = [(s0, min(per_call, S - s0)) for s0 in range(0, S, per_call)]
+    recs = []                                           # per chunk: (records, counts, escapes, bytes)
+    srv_states = states0.clone()
+    with CUDACore(W, H, max_batch=per_call) as server:
+        for s0, ns in chunks:
+            cwcap = cwire_bytes_max(n, ns)
+            d_off = torch.zeros(ns + 1, dtype=torch.int32, device=dev)
+            d_pos = torch.zeros(ns + 1, dtype=torch.int64, device=dev)
+            d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()
+            server.diff_multi_stream_cwire_batch(fwd[s0], srv_states[s0], ns, T, d_off, d_pos, d_cw, cwcap)
+            server.synchronize()
+            pos = d_pos.cpu().numpy().astype(np.int64)
+            counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
+            pad = (counts.astype(np.int64) + 3) & ~3
+            escapes = ((np.diff(pos) - 8 - 2 * pad) // 4).astype(np.uint32)
+            recs.append((d_cw[:int(pos[ns])].clone(), counts, escapes, int(pos[ns])))
+            del d_cw
+    ocap = cwire_bytes_max(n, per_call)
+    d_ooff = torch.zeros(per_call + 1, dtype=torch.int32, device=dev)
+    d_opos = torch.zeros(per_call + 1, dtype=torch.int64, device=dev)
+    d_out = torch.empty(ocap, dtype=torch.uint8, device=dev)
+    d_coff, d_cpos, d_cout = torch.zeros_like(d_ooff), torch.zeros_like(d_opos), torch.empty_like(d_out)
+    quarter = np.tile(np.array([W // 4, H // 4, W // 2, H // 2], np.int32), (per_call, 1))
+    full = np.tile(np.array([0, 0, W, H], np.int32), (per_call, 1))
+    relay = CUDACore(W, H, max_batch=per_call)
+    torch.cuda.synchronize()
+
+    def leg_coalesce():
+        for _ in range(passes):
+            for (s0, ns), r in zip(chunks, recs):
+                relay.cwire_coalesce_cwire_batch(r[0], r[1], r[2], ns, T, d_ooff, d_opos, d_out, ocap)
+        relay.synchronize()
+
+    def leg_crop(rects):
+        def leg():
+            for _ in range(passes):
+                for (s0, ns), r in zip(chunks, recs):
+                    relay.cwire_crop_cwire_batch(r[0], r[1], r[2], ns, T, rects, d_ooff, d_opos, d_out, ocap)
+            relay.synchronize()
+        return leg
+
+    table = {"coalesce": leg_coalesce, "crop_quarter": leg_crop(quarter), "crop_full": leg_crop(full)}
+    times = {}
+    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
+        for name, leg in table.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            leg()
+            dt = time.perf_counter() - t0
+            if r:
+                times.setdefault(name, []).append(dt * 1e6 / (passes * S))
+    # the full-frame crop of one record per stream is the coalescer's output (and the input); the quarter holds fewer entries
+    in_entries = quarter_entries = quarter_bytes = 0
+    for (s0, ns), r in zip(chunks, recs):
+        relay.cwire_coalesce_cwire_batch(r[0], r[1], r[2], ns, T, d_coff, d_cpos, d_cout, ocap)
+        relay.cwire_crop_cwire_batch(r[0], r[1], r[2], ns, T, full, d_ooff, d_opos, d_out, ocap)
+        relay.synchronize()
+        nbytes = int(d_cpos[ns].item())
+        assert nbytes == r[3] and torch.equal(d_opos[:ns + 1], d_cpos[:ns + 1]) and torch.equal(d_out[:nbytes], d_cout[:nbytes])
+        assert torch.equal(d_out[:nbytes], r[0])
+        in_entries += int(d_coff[ns].item())
+        relay.cwire_crop_cwire_batch(r[0], r[1], r[2], ns, T, quarter, d_ooff, d_opos, d_out, ocap)
+        relay.synchronize()
+        quarter_entries += int(d_ooff[ns].item())
+        quarter_bytes += int(d_opos[ns].item())
+    assert quarter_entries <= in_entries
+    in_bytes = sum(r[3] for r in recs)
+    out = {"input": kind, "streams": S, "frames": T, "passes": passes, "calls_per_tick": len(chunks),
+           "rectangle": [int(v) for v in quarter[0]],
+           "input_entries_per_stream": round(in_entries / S, 1), "quarter_entries_per_stream": round(quarter_entries / S, 1),
+           "input_bytes_per_stream": round(in_bytes / S, 1), "quarter_bytes_per_stream": round(quarter_bytes / S, 1)}
+    med, spread = {}, {}
+    for name in table:
+        st = stats(times[name])
+        st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
+        out[name + "_us_per_stream"] = st
+        med[name], spread[name] = st["median"], st["max"] - st["min"]
+    out["crop_quarter_over_coalesce"] = round(med["crop_quarter"] / med["coalesce"], 3)
+    out["crop_full_over_coalesce"] = round(med["crop_full"] / med["coalesce"], 3)
+    # the expectation: the quarter no slower than the coalescer by more than the rounds' spread (of either leg)
+    out["quarter_no_slower_than_coalesce"] = bool(med["crop_quarter"] <= med["coalesce"] + max(spread["crop_quarter"], spread["coalesce"]))
+    out["full_minus_coalesce_us_per_call"] = round((med["crop_full"] - med["coalesce"]) * S / len(chunks), 3)
+    relay.close()
+    return out
+
+
 def run_budget(W, H, S, rounds):
     """The budget leg for one S -> its dictionary.  budget: mi355_cwire_budget_cwire_batch on the records of one tick with every
     stream's budget at half of its count, on the states as the tick left them.  second_diff: mi355_diff_multi_cwire_batch over the
@@ -1102,7 +1214,7 @@ def main():
     ap.add_argument("--steps", type=int, default=8, help="K: webcam frames a stream walks through")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--legs", default="multi,cores_loop,pairs",
-                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or budget alone; or activity alone; or check alone; or refresh alone; or wall alone")
+                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or crop alone; or budget alone; or activity alone; or check alone; or refresh alone; or wall alone")
     ap.add_argument("--frames", default="4,16,64", help="burst, burst_client and coalesce legs: T, frames per stream and call")
     a = ap.parse_args()
     have = load_library()
@@ -1142,6 +1254,15 @@ def main():
                     print(f"coalesce S={S} T={T} {kind}: done", file=sys.stderr, flush=True)
                     torch.cuda.empty_cache()
         print(json.dumps({"bench": "multi_coalesce", "size": f"{W}x{H}", "rounds": a.rounds, "coalesce": per}), flush=True)
+        return
+    if a.legs == "crop":
+        per = []
+        for S in (int(v) for v in a.streams.split(",")):
+            for kind in ("webcam", "local"):
+                per.append(run_crop(W, H, S, a.rounds, kind))
+                print(f"crop S={S} {kind}: done", file=sys.stderr, flush=True)
+                torch.cuda.empty_cache()
+        print(json.dumps({"bench": "multi_crop", "size": f"{W}x{H}", "rounds": a.rounds, "crop": per}), flush=True)
         return
     if a.legs == "budget":
         per = []

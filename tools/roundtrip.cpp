@@ -11,7 +11,7 @@
 // (ActivityCheck, RecordCheck, WallCheck), that is that mode.
 //
 //   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B]
-//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check] | --resync K [--burst B]] [--wall K]]
+//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check] | --resync K [--burst B] | --crop X,Y,W,H [--burst K]] [--wall K]]
 //   exit status 0 = all checks passed
 #include <algorithm>
 #include <cstdint>
@@ -864,6 +864,83 @@ static int run_multi_burst_coalesce(int w, int h, int T, int S, int K) {
     return 0;
 }
 
+// --compact --multi S --crop X,Y,W,H [--burst K]: a relay for viewers that zoomed into their cameras.  It holds no frame: it
+// uploads every camera's records as they came off its socket (one tick, or a burst of K), cuts them to the rectangle with ONE
+// mi355_cwire_crop_cwire_batch -- of a burst, the crop of the coalesced burst -- and forwards those S records, indexed in the
+// rectangle's own W x H frame.  The receiver is a core of W x H pixels: its states are seeded from the crops of the base frames
+// and take the records with one mi355_apply_multi_cwire_batch.  After every tick or burst each of its states must equal the
+// crop of the sender's state and of a full-size host client (mi355_cwire_apply_host) that applied the original records.
+static void crop_frame(uint8_t *dst, const uint8_t *src, int w, const int32_t *r) {
+    for (int y = 0; y < r[3]; y++) memcpy(dst + (size_t)y * 3 * r[2], src + ((size_t)(r[1] + y) * w + r[0]) * 3, (size_t)3 * r[2]);
+}
+
+static int run_multi_crop(int w, int h, int T, int S, int K, const int32_t *rect) {
+    const bool burst = K > 0;
+    if (!burst) K = 1;
+    Session ss(w, h), view(rect[2], rect[3]);
+    const size_t n = ss.n, m = view.n;
+    Cameras cams(S, w, h);
+    Sender tx;
+    Receiver relay, rcv;
+    if (tx.open(ss, S, K) || relay.open(ss, S, S * K, S * K, false) || rcv.open(view, S, S, S)) return 1;
+    void *d_roff = ss.dev(relay.core, sizeof(uint32_t) * (S + 1)), *d_rpos = ss.dev(relay.core, sizeof(uint64_t) * (S + 1));
+    void *d_fwd = ss.dev(relay.core, rcv.cap);   // S records of a W x H frame at most: the sum of the rectangles' bounds
+    if (!ss.ok() || !view.ok()) return 1;
+    std::vector<uint8_t> host_frames((size_t)S * n), fwd(rcv.cap), cropped((size_t)S * m), seed((size_t)S * m);
+    std::vector<int32_t> rects((size_t)4 * S);
+    for (int s = 0; s < S; s++) memcpy(&rects[(size_t)4 * s], rect, 4 * sizeof(int32_t));
+    std::vector<uint32_t> roff(S + 1);
+    std::vector<uint64_t> rpos(S + 1);
+    // the sender's states and the full-size host clients from the base frames; the receiver's from their crops, through the pipe
+    OK(mi355_upload(tx.core, tx.d_states, cams.bases.data(), cams.bases.size()));
+    memcpy(host_frames.data(), cams.bases.data(), cams.bases.size());
+    for (int s = 0; s < S; s++) crop_frame(&cropped[(size_t)s * m], &cams.bases[(size_t)s * n], w, rect);
+    if (!ss.send(cropped.data(), seed.data(), seed.size())) return 1;
+    OK(mi355_upload(rcv.core, rcv.d_states, seed.data(), seed.size()));
+    size_t received = 0, forwarded = 0, kept = 0;
+    int calls = 0;
+    for (int t0 = 0; t0 < T; t0 += K) {
+        const int nb = T - t0 < K ? T - t0 : K;
+        cams.fill(tx.frames.data(), t0, nb);
+        // ---- server: nb ticks of S cameras -> S * nb records in one call
+        if (tx.step(nb, burst)) return 1;
+        // ---- the sockets into the relay; a full-size host client beside it applies every original record
+        if (slices_to_node(ss, tx, relay, nb, host_frames.data(), nullptr)) return 1;
+        received += tx.cb;
+        // ---- relay: the records -> one cropped record per camera, in one call; no frame exists here
+        OK(mi355_cwire_crop_cwire_batch(relay.core, relay.d_rx, relay.counts.data(), relay.escapes.data(), S, nb, rects.data(), 0u, d_roff,
+                                        d_rpos, d_fwd, rcv.cap));
+        calls++;
+        OK(mi355_download(relay.core, roff.data(), d_roff, sizeof(uint32_t) * (S + 1)));
+        OK(mi355_download(relay.core, rpos.data(), d_rpos, sizeof(uint64_t) * (S + 1)));
+        if (rpos[S] > rcv.cap) { fprintf(stderr, "cropped stream larger than its bound\n"); return 1; }
+        const size_t fb = (size_t)rpos[S];
+        OK(mi355_download(relay.core, fwd.data(), d_fwd, fb));
+        kept += roff[S];
+        // ---- the sockets out of the relay, one record per camera; the receiver finds them from their headers
+        if (!ss.send(fwd.data(), rcv.rx.data(), fb)) return 1;
+        forwarded += fb;
+        if (rcv.walk(0, fb, 0, S)) return 1;
+        // ---- receiver: one call per tick or burst, on W x H states
+        OK(mi355_upload(rcv.core, rcv.d_rx, rcv.rx.data(), fb));
+        if (rcv.apply_tick() || rcv.get_states() || tx.get_states()) return 1;
+        // ---- checks: the crop of the sender's states, and of the host clients that applied all the original records
+        for (int s = 0; s < S; s++) {
+            crop_frame(&cropped[(size_t)s * m], &tx.states[(size_t)s * n], w, rect);
+            if (same(&cropped[(size_t)s * m], &rcv.states[(size_t)s * m], m, "receiver state != crop of the sender's state", t0)) return 1;
+            crop_frame(&cropped[(size_t)s * m], &host_frames[(size_t)s * n], w, rect);
+            if (same(&cropped[(size_t)s * m], &rcv.states[(size_t)s * m], m, "receiver state != crop of the host client's frame", t0)) return 1;
+        }
+    }
+    if (kept == 0) { fprintf(stderr, "no entry fell into the rectangle: nothing was checked\n"); return 1; }
+    if (ss.close() || view.close()) return 1;
+    printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"burst\": %d, \"crop\": [%d, %d, %d, %d], \"relay_calls\": %d, "
+           "\"width\": %d, \"height\": %d, \"ticks\": %d, \"changed_bytes\": %zu, \"cropped_entries\": %zu, "
+           "\"relay_received_bytes\": %zu, \"relay_forwarded_bytes\": %zu, \"cropped_states_equal_every_step\": true}\n",
+           S, burst ? K : 0, rect[0], rect[1], rect[2], rect[3], calls, w, h, T, tx.changed, kept, received, forwarded);
+    return 0;
+}
+
 namespace {
 struct Expected {   // the plain path's client frames, in order, from the sender to the receiver thread
     std::mutex m;
@@ -1322,7 +1399,15 @@ int main(int argc, char **argv) {
         {"--width", &w, any, 0}, {"--height", &h, any, 0}, {"--frames", &T, any, 0}, {"--batch", &B, any, 0}, {"--multi", &multi, any, 0},
         {"--burst", &burst, any, 0}, {"--activity", &activity, 0, 0}, {"--resync", &resync, 0, 0}, {"--wall", &wall, 1, -1},
         {"--budget", &budget, 0, 0}};
+    int32_t crop[4] = {0, 0, 0, 0};
+    bool cropped = false, crop_ok = true;
     for (int i = 1; i < argc; i++) {   // (an option the tool does not know is ignored)
+        if (!strcmp(argv[i], "--crop") && i + 1 < argc) {
+            char tail = 0;
+            cropped = true;
+            crop_ok = sscanf(argv[++i], "%d,%d,%d,%d%c", &crop[0], &crop[1], &crop[2], &crop[3], &tail) == 4;
+            continue;
+        }
         for (const auto &f : flags)
             if (!strcmp(argv[i], f.name)) *f.on = true;
         for (const auto &v : valued)
@@ -1347,6 +1432,12 @@ int main(int argc, char **argv) {
         return usage("--resync K needs --compact --multi S, alone or with --burst B");
     if (wall && (wall < 0 || wall > 16 || !compact || !multi || budget >= 0 || coalesce || per_frame || (burst && !burst_client && resync < 0)))
         return usage("--wall K needs 1 <= K <= 16 and --compact --multi S, alone, with --burst B --burst-client or with --resync R");
+    if (cropped) {
+        if (!compact || !multi || budget >= 0 || coalesce || per_frame || burst_client || activity || check || resync >= 0 || wall)
+            return usage("--crop X,Y,W,H needs --compact --multi S, alone or with --burst K");
+        if (!crop_ok || crop[0] < 0 || crop[1] < 0 || crop[2] < 1 || crop[3] < 1 || (long)crop[0] + crop[2] > w || (long)crop[1] + crop[3] > h)
+            return usage("--crop X,Y,W,H needs a rectangle of at least one pixel inside the frame");
+    }
     if (per_frame) {
         if (!compact || direct || gpu_client || multi) return usage("--per-frame needs --compact alone");
         return run_per_frame(w, h, T);
@@ -1354,6 +1445,7 @@ int main(int argc, char **argv) {
     if (!multi) return run_single(w, h, T, B, compact, direct, gpu_client);
     if (!compact || direct || gpu_client || multi < 0) return usage("--multi S needs --compact alone and S >= 1");
     if (resync >= 0) return run_multi_resync(w, h, T, multi, resync, burst, wall);
+    if (cropped) return run_multi_crop(w, h, T, multi, burst, crop);
     if (coalesce) return run_multi_burst_coalesce(w, h, T, multi, burst);
     if (budget >= 0) return run_multi_budget(w, h, T, multi, budget);
     if (burst && !burst_client) return run_multi_burst(w, h, T, multi, burst);
