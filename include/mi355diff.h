@@ -202,9 +202,15 @@ int mi355_set_glyphs(mi355_core *core, const uint8_t *chars_px, int nglyphs, int
  *              camera.  One speed cliff: the pack kernel's vector path reads a group of frames
  *              through one 32-bit window and needs 3*stride_bytes + N < 2^32; a larger stride takes
  *              the byte path (the one unaligned operands take), with identical results and slower.
- *              By how much has not been measured.  Untested: RECORD buffers past 4 GiB --
- *              d_frame_pos is 64-bit, but records lie back to back, so a position reaches 2^32 only
- *              behind 4 GiB of real record bytes.
+ *              By how much has not been measured.
+ *              The top of the range mi355_create accepts is tested in tests/test_top_of_range_gpu.py:
+ *              diff batches of 65535, 65536, 65537 and 131073 frames or streams (the expansion kernels
+ *              take the whole batch as one grid dimension, above 65535 too); log offsets from 2^31
+ *              to 9216 bytes below 2^32 (1000x700 at max_batch 1100 and 2045, the largest accepted);
+ *              batch totals of 2^31 entries and more with d_xs past 8 GiB, plain-wire positions and
+ *              RECORD positions (d_frame_pos) past 2^32 -- 4.6 GB of records written by
+ *              mi355_diff_stream_cwire_batch and read by the apply, check, decode, multi-stream apply,
+ *              coalesce, crop, activity and touched-tiles calls.
  *   d_offsets: uint32[nframes+1], exclusive scan of the per-frame counts (offsets[0] = 0)
  *   d_xs     : int32[capacity]  byte indices, frame t's entries at [offsets[t], offsets[t+1])
  *   d_diff   : uint8[capacity]  (uint8)df of the same entries

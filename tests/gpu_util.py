@@ -203,3 +203,49 @@ def oracle_pairs(po, cur, prev, thr=20):
         offs.append(offs[-1] + c); xs.append(x); df.append(d)
     return (np.array(offs, np.uint32), np.concatenate(xs) if xs else np.empty(0, np.int32),
             np.concatenate(df) if df else np.empty(0, np.uint8))
+
+
+class BigGuarded:
+    """Guarded's interface for outputs of many GiB that never cross to the host: `count` elements of `dtype` with PAD guard
+    elements before and behind them, everything filled with the guard value of its type on the device.  check() asserts on the
+    device, in pieces of at most PIECE bytes, that both pads -- and the body from element `written` on -- still hold it."""
+
+    PIECE = 1 << 30
+
+    def __init__(self, count, dtype=torch.uint8, device=DEV):
+        self.count, self.fill = int(count), _FILL[dtype]
+        self.buf = torch.full((self.bytes_needed(count, dtype) // torch.empty(0, dtype=dtype).element_size(),), self.fill,
+                              dtype=dtype, device=device)
+        self.t = self.buf[PAD:PAD + self.count]
+        self.ptr = self.buf.data_ptr() + PAD * self.buf.element_size()
+
+    @staticmethod
+    def bytes_needed(count, dtype=torch.uint8):
+        return (PAD + int(count) + PAD) * torch.empty(0, dtype=dtype).element_size()
+
+    def check(self, written=None):
+        step = self.PIECE // self.buf.element_size()
+        spans = [(0, PAD, "before the buffer"), (PAD + self.count, self.buf.numel(), "behind the buffer")]
+        if written is not None:
+            spans.insert(1, (PAD + int(written), PAD + self.count, "behind the part that was to be written"))
+        for lo, hi, name in spans:
+            for a in range(lo, hi, step):
+                piece = self.buf[a:min(a + step, hi)]
+                if bool((piece != self.fill).any()):
+                    first = a + int(torch.argmax((piece != self.fill).to(torch.uint8))) - PAD
+                    raise AssertionError(f"element {first} of the buffer's {self.count} was written: it lies {name}")
+
+    def free(self):
+        self.buf = self.t = None
+
+
+def assert_same_on_device(got, want, what, piece=1 << 30):
+    """Two device tensors of one shape and type, compared where they lie in slices of at most `piece` bytes; the message names
+    the first element that differs and both values."""
+    assert got.shape == want.shape and got.dtype == want.dtype and got.dim() == 1, (what, got.shape, want.shape)
+    step = max(1, piece // got.element_size())
+    for a in range(0, got.numel(), step):
+        g, w = got[a:a + step], want[a:a + step]
+        if not torch.equal(g, w):
+            first = a + int(torch.argmax((g != w).to(torch.uint8)))
+            raise AssertionError(f"{what}: element {first} is {got[first].item()}, the reference's {want[first].item()}")
