@@ -95,6 +95,13 @@ public:
     void crop_multi_stream(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, int nstreams, int nframes,
                            const int32_t *h_rects, unsigned flags, void *d_offsets, void *d_frame_pos, void *d_cwire_out,
                            size_t capacity_bytes);
+    // A multiview relay (include/mi355diff.h, mi355_cwire_mosaic_cwire_batch): the bursts of all the cameras placed side by side
+    // into ONE record of a canvas_w x canvas_h canvas, h_place[s] = {sx, sy, w, h, dx, dy} in pixels; the client holds one canvas
+    // state and reads one socket.  d_offsets uint32[2], d_frame_pos uint64[2].  Blocking; nstreams*nframes <= MI355_MAX_BATCH, and
+    // the canvas may have at most MI355_MAX_BATCH frames' worth of 4096-byte tiles.
+    void mosaic_multi_stream(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, int nstreams, int nframes,
+                             const int32_t *h_place, int canvas_w, int canvas_h, void *d_offsets, void *d_frame_pos,
+                             void *d_cwire_out, size_t capacity_bytes);
     // The sender's rate control behind exec_multi's compact form (include/mi355diff.h, mi355_cwire_budget_cwire_batch): record s
     // of the tick just diffed keeps at most budgets[s] entries (mi355_cwire_budget_entries turns a byte budget into one;
     // UINT32_MAX: no limit), the largest changes first: the thinned records go to d_cwire_out + d_frame_pos[s], the threshold that

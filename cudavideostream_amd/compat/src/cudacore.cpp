@@ -161,6 +161,14 @@ void CUDACore::crop_multi_stream(const void *d_cwire, const uint32_t *counts, co
     MI355_CHECK(mi355_synchronize(core_));
 }
 
+void CUDACore::mosaic_multi_stream(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, int nstreams, int nframes,
+                                   const int32_t *h_place, int canvas_w, int canvas_h, void *d_offsets, void *d_frame_pos,
+                                   void *d_cwire_out, size_t capacity_bytes) {
+    MI355_CHECK(mi355_cwire_mosaic_cwire_batch(core_, d_cwire, counts, escapes, nstreams, nframes, h_place, canvas_w, canvas_h,
+                                               d_offsets, d_frame_pos, d_cwire_out, capacity_bytes));
+    MI355_CHECK(mi355_synchronize(core_));
+}
+
 void CUDACore::budget_multi(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, void *d_states, size_t stride,
                             int nstreams, const uint32_t *budgets, void *d_thresholds, void *d_offsets, void *d_frame_pos,
                             void *d_cwire_out, size_t capacity_bytes) {

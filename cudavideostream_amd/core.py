@@ -458,6 +458,35 @@ class CUDACore:
                                                         _ptr(d_offsets), _ptr(d_frame_pos), _ptr(d_cwire_out),
                                                         int(capacity_bytes)))
 
+    # ... and a multiview relay: the coalesced records of many cameras placed on one canvas, ONE record out
+    def cwire_mosaic_batch(self, d_cwire, counts, escapes, nstreams, nframes, place, canvas_w, canvas_h, d_offsets, d_xs, d_diff,
+                           capacity):
+        """cwire_coalesce_batch of all the streams into ONE segment of a canvas_w x canvas_h BGR24 canvas: place[s] = (sx, sy, w,
+        h, dx, dy) in pixels puts that rectangle of camera s at (dx, dy); overlapping destinations add.  d_offsets: uint32[2].
+        Applying the segment to a canvas state equals placing what the streams' records make of the cameras' states."""
+        self._hold(d_cwire, d_offsets, d_xs, d_diff)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+        place = np.ascontiguousarray(place, dtype=np.int32)
+        assert counts.size >= nstreams * nframes and escapes.size >= nstreams * nframes and place.size >= 6 * nstreams
+        _l.check(self._lib.mi355_cwire_mosaic_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data, int(nstreams),
+                                                    int(nframes), place.ctypes.data, int(canvas_w), int(canvas_h), _ptr(d_offsets),
+                                                    _ptr(d_xs), _ptr(d_diff), int(capacity)))
+
+    def cwire_mosaic_cwire_batch(self, d_cwire, counts, escapes, nstreams, nframes, place, canvas_w, canvas_h, d_offsets,
+                                 d_frame_pos, d_cwire_out, capacity_bytes):
+        """cwire_mosaic_batch into ONE compact record at d_cwire_out, the canonical encoding of the segment; d_frame_pos
+        (uint64[2]) = {0, record bytes}."""
+        self._hold(d_cwire, d_offsets, d_frame_pos, d_cwire_out)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+        place = np.ascontiguousarray(place, dtype=np.int32)
+        assert counts.size >= nstreams * nframes and escapes.size >= nstreams * nframes and place.size >= 6 * nstreams
+        _l.check(self._lib.mi355_cwire_mosaic_cwire_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
+                                                          int(nstreams), int(nframes), place.ctypes.data, int(canvas_w),
+                                                          int(canvas_h), _ptr(d_offsets), _ptr(d_frame_pos), _ptr(d_cwire_out),
+                                                          int(capacity_bytes)))
+
     # ... and the sender's rate control: the records of one tick held to an entry budget each
     def cwire_budget_cwire_batch(self, d_cwire, counts, escapes, d_states, nstreams, budgets, d_thresholds, d_offsets,
                                  d_frame_pos, d_cwire_out, capacity_bytes, stride=None):

@@ -1498,6 +1498,75 @@ int mi355_cwire_crop_cwire_batch(mi355_core *c, const void *d_cwire, const uint3
                 nullptr, capacity_bytes);
 }
 
+// ---- mi355_cwire_mosaic_(cwire_)batch: the streams' coalesced records placed on a canvas, ONE segment / record out --------------
+// Both forms: everything is refused here, before anything is launched; the core's state is not touched.  The per-stream words
+// are the budget call's, as for the crop; the facts of the canvas' tiles take the chunk scratch, which holds max_batch *
+// cwa_chunks(N) words and is not grown here.
+static int mosaic(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams, int nframes,
+                  const int32_t *h_place, int canvas_w, int canvas_h, bool cwire, void *d_offsets, void *d_frame_pos, void *d_cwire_out,
+                  void *d_xs, void *d_diff, size_t capacity) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nstreams < 0 || nframes < 0) return fail(MI355_ERR_INVALID, "nstreams or nframes < 0");
+    const int64_t B64 = (int64_t)nstreams * nframes;
+    if (B64 > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams * nframes above max_batch");
+    const int B = (int)B64;
+    if (canvas_w < 1 || canvas_h < 1) return fail(MI355_ERR_INVALID, "canvas_w or canvas_h < 1");
+    const uint64_t nc = 3ull * (uint64_t)canvas_w * (uint64_t)canvas_h;
+    if (nc >= (1ull << 31)) return fail(MI355_ERR_INVALID, "canvas of 2^31 bytes or more");
+    if ((uint64_t)mi355_state_tiles((size_t)nc) > (uint64_t)c->cfg.max_batch * mi355_state_tiles(c->n))
+        return fail(MI355_ERR_INVALID, "canvas of more 4096-byte tiles than max_batch frames hold: create the core with a larger max_batch");
+    if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_cwire_out & 3u) || ((uintptr_t)d_xs & 3u))
+        return fail(MI355_ERR_INVALID, "d_cwire, d_cwire_out, d_offsets and d_xs must be 4-byte aligned");
+    if ((uintptr_t)d_frame_pos & 7u) return fail(MI355_ERR_INVALID, "d_frame_pos must be 8-byte aligned");
+    if (B == 0) return write_empty_heads(c, d_offsets, d_frame_pos);
+    if (!d_cwire || !h_counts || !h_escapes) return fail(MI355_ERR_INVALID, "null stream pointer");
+    if (!h_place) return fail(MI355_ERR_INVALID, "null h_place");
+    if (!d_offsets || (cwire ? !d_frame_pos || !d_cwire_out : !d_xs || !d_diff)) return fail(MI355_ERR_INVALID, "null output pointer");
+    for (int s = 0; s < nstreams; s++) {
+        const int32_t *p = h_place + 6 * (size_t)s;
+        for (int k = 0; k < 6; k++)
+            if (p[k] < 0) return fail(MI355_ERR_INVALID, "placement with a negative member");
+        if ((int64_t)p[0] + p[2] > c->cfg.width || (int64_t)p[1] + p[3] > c->cfg.height)
+            return fail(MI355_ERR_INVALID, "source rectangle outside the frame");
+        if ((int64_t)p[4] + p[2] > canvas_w || (int64_t)p[5] + p[3] > canvas_h)
+            return fail(MI355_ERR_INVALID, "destination rectangle outside the canvas");
+    }
+    CwaTable tab;
+    if (int rc = cwa_table(c, h_counts, h_escapes, B, &tab)) return rc;
+    if (int rc = check_regions({input_region(d_cwire, tab.bytes)},   // (the outputs of the other form: nowhere)
+                               {offsets_region(d_offsets, 1), cwire ? frame_pos_region(d_frame_pos, 1) : Region{},
+                                cwire ? Region{d_cwire_out, capacity, "d_cwire_out"} : Region{},
+                                cwire ? Region{} : Region{d_xs, 4 * (uint64_t)capacity, "d_xs"},
+                                cwire ? Region{} : Region{d_diff, capacity, "d_diff"}}))
+        return rc;
+    if (int rc = use_device(c)) return rc;
+    const CwaArgs a = cwa_args(c, d_cwire);
+    CwcOut o{};
+    o.offsets = (uint32_t *)d_offsets;
+    o.frame_pos = (uint64_t *)d_frame_pos;
+    o.cwire = (uint8_t *)d_cwire_out;
+    o.xs = (int32_t *)d_xs;
+    o.diff = (uint8_t *)d_diff;
+    o.capacity = capacity;
+    HIP_TRY(launch_cwire_mosaic(a, tab.fr.data(), nstreams, nframes, h_place, (uint32_t)c->cfg.width, (uint32_t)canvas_w, (uint32_t)nc,
+                                c->cwb_hist, o, cwire, c->stream));
+    return MI355_OK;
+}
+
+int mi355_cwire_mosaic_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams,
+                             int nframes, const int32_t *h_place, int canvas_w, int canvas_h, void *d_offsets, void *d_xs, void *d_diff,
+                             size_t capacity) {
+    return mosaic(c, d_cwire, h_counts, h_escapes, nstreams, nframes, h_place, canvas_w, canvas_h, false, d_offsets, nullptr, nullptr,
+                  d_xs, d_diff, capacity);
+}
+
+int mi355_cwire_mosaic_cwire_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams,
+                                   int nframes, const int32_t *h_place, int canvas_w, int canvas_h, void *d_offsets, void *d_frame_pos,
+                                   void *d_cwire_out, size_t capacity_bytes) {
+    return mosaic(c, d_cwire, h_counts, h_escapes, nstreams, nframes, h_place, canvas_w, canvas_h, true, d_offsets, d_frame_pos,
+                  d_cwire_out, nullptr, nullptr, capacity_bytes);
+}
+
 // ---- mi355_cwire_budget_cwire_batch: the records of one tick held to an entry budget each ------------------------------------
 size_t mi355_cwire_budget_entries(size_t frame_bytes, size_t record_bytes) {
     // the largest n <= frame_bytes whose worst record (e = min(n, frame_bytes / 256) escapes) fits; the size rises with n

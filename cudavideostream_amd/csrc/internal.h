@@ -252,6 +252,18 @@ struct CropArgs {
 };
 hipError_t launch_cwire_crop(const CwaArgs &a, const CwaFrame *records, int nstreams, int nframes, const int32_t *rects, uint32_t width,
                              bool keep_index, uint32_t *words, const CwcOut &o, bool cwire, hipStream_t s);
+// mi355_cwire_mosaic_(cwire_)batch: the coalesced records of the streams placed on a BGR24 canvas of canvas_bytes = 3 * canvas_w *
+// canvas_h bytes, place[s] = {sx, sy, w, h, dx, dy} (host array, checked by the caller against the frame and the canvas), ONE
+// segment / record out (o.offsets uint32[2], o.frame_pos uint64[2]).  words: the budget call's per-stream rows, of which a stream's
+// first six are written (MosaicWords); a.chunk holds one fact word per CANVAS tile, so cwa_tiles(canvas_bytes) must not exceed the
+// scratch (the caller refuses a larger canvas); a as for the coalescer, of the source frames.
+constexpr int kMosaicStreams = 128;   // placements per k_mosaic_table launch (kernel arguments)
+struct MosaicArgs {
+    int32_t first, count;   // the launch's first stream and its streams
+    int32_t place[kMosaicStreams][6];
+};
+hipError_t launch_cwire_mosaic(const CwaArgs &a, const CwaFrame *records, int nstreams, int nframes, const int32_t *place, uint32_t width,
+                               uint32_t canvas_w, uint32_t canvas_bytes, uint32_t *words, const CwcOut &o, bool cwire, hipStream_t s);
 // mi355_cwire_check_batch: verdicts[b][0 .. 4) of record b (include/mi355diff.h); a.ftab and a.chunk are the scratch it uses, a.n the
 // frame bytes; a.dir / a.state / a.out / a.stride / a.ntiles unused
 hipError_t launch_cwire_check(const CwaArgs &a, const CwaFrame *records, int nrecords, uint32_t *verdicts, hipStream_t s);

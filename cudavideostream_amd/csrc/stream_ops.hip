@@ -17,6 +17,8 @@
 //                           dropped (mi355_cwire_budget_cwire_batch);
 //   k_crop_*              : a stream's coalesced records cut to a rectangle and re-indexed to the rectangle's frame
 //                           (mi355_cwire_crop_batch / _cwire_batch);
+//   k_mosaic_*            : the coalesced records of many streams placed side by side into ONE record of a canvas frame
+//                           (mi355_cwire_mosaic_batch / _cwire_batch);
 //   k_act_*               : where the entries of each stream's records land: a grid of counts per cell, a bounding box and the
 //                           peak cell per stream (mi355_cwire_activity_batch; mi355_activity_batch from the arrays).
 //   k_cwk_*               : one verdict of four words per compact record -- is it well-formed and canonical, and where not --
@@ -1751,6 +1753,177 @@ __global__ __launch_bounds__(64) void k_crop_emit(const CwaArgs a, const CwcOut 
     cwc_emit_tile<CWIRE>(s, (uint8_t *)s_code32, (uint8_t *)s_diff32, fact, o, seg, n, fp0, e, lo, lane, CropMap(row, c, r0));
 }
 
+// ---- mi355_cwire_mosaic_(cwire_)batch: the coalesced records of nstreams cameras placed on a canvas, ONE record out ------------
+// The opposite of the crop: the tile grid runs over the CANVAS (Nc = 3 * canvas_w * canvas_h bytes, cwa_tiles(Nc) tiles) and a tile
+// gathers from every stream whose destination it meets.  Behind the directory of the nstreams*nframes records:
+//   k_mosaic_table (one workgroup per launch)        : the placements {sx, sy, w, h, dx, dy} are kernel arguments (kMosaicStreams
+//                                                      per launch) and become six words per stream in the budget call's per-stream
+//                                                      rows (the two calls are ordered on one stream): the destination's rows and
+//                                                      column bytes on the canvas, the source's first row and column byte
+//   k_mosaic_facts (grid: canvas tiles, one wave)    : lanes test 64 streams a round -- do the tile's rows meet the destination's,
+//                                                      and does the tile hold a byte of its columns -- and take the source byte
+//                                                      range [slo, shi) the tile's bytes come from; per hit, lanes test 64 records
+//                                                      a round on the directory words of the source tiles that range meets; per
+//                                                      record with an entry there, ONE walk (cwa_walk_record from the first source
+//                                                      tile's directory word) whose op keeps the entries of the source rectangle
+//                                                      and adds them at their canvas byte into a ZEROED tile in LDS.  A barrier
+//                                                      stands between walks: two streams (or two records) may hit one byte, the
+//                                                      entries of one record never do.  A tile nothing lands in stores the
+//                                                      all-zero fact, the others cwc_tile_facts: the tile is in canvas indices
+//                                                      already, so the map is the identity
+//   k_cwc_scan, k_cwc_place                          : the coalescer's, unchanged, for ONE stream of cwa_tiles(Nc) tiles
+//   k_mosaic_emit  (grid: canvas tiles, one wave)    : the same tile from the same bytes, its entries written by cwc_emit_tile
+// The facts live where the coalescer's do (the chunk scratch, max_batch * cwa_chunks(N) words: the caller refuses a canvas of more
+// tiles).  Source byte x of row r = x / 3W, column byte c = x - r*3W, is canvas byte (r - sy + dy) * 3*canvas_w + c - 3*sx + 3*dx:
+// the row comes from the exact multiply-and-correct division of the motion grid (act_div), once per kept entry of a walk.  The walk
+// range is exact in its first and last row and spans whole source rows between them, so a canvas narrower than the source frame
+// walks over entries it drops; the op decides.  Malformed content: the walk's own guarantees (nothing read outside the record,
+// no index at or past N), and both tile kernels build the same tile from the same bytes, so facts and record agree.
+struct MosaicWords {
+    uint32_t drow0, drow1;   // canvas rows [drow0, drow1) (drow0 == drow1: nothing is placed)
+    uint32_t dcol0, dcol1;   // canvas column bytes [dcol0, dcol1) of a row
+    uint32_t srow0, scol0;   // the source's first row and column byte
+};
+
+__global__ __launch_bounds__(kMosaicStreams) void k_mosaic_table(uint32_t *words, const MosaicArgs h) {
+    const int j = threadIdx.x;
+    if (j >= h.count) return;
+    const uint32_t sx = (uint32_t)h.place[j][0], sy = (uint32_t)h.place[j][1], w = (uint32_t)h.place[j][2], ht = (uint32_t)h.place[j][3];
+    const uint32_t dx = (uint32_t)h.place[j][4], dy = (uint32_t)h.place[j][5];
+    uint32_t *rw = words + (size_t)(h.first + j) * kCwbWords;
+    rw[0] = dy, rw[1] = w ? dy + ht : dy;   // (no column: no row either)
+    rw[2] = 3u * dx, rw[3] = 3u * (dx + w);
+    rw[4] = sy, rw[5] = 3u * sx;
+}
+
+// The canvas tile [lo, lo + len) in LDS (s: kCwaTile bytes; s[0] is canvas byte lo): the sum over the streams that cover a byte of
+// their summed differences there.  false: nothing lands in the tile and s was not touched.  rs: 3W, rc: 3 * canvas_w.
+__device__ __forceinline__ bool mosaic_tile(uint8_t *s, const CwaArgs &a, int nstreams, int nframes, const uint32_t *words,
+                                            const ActDiv rs, const ActDiv rc, uint32_t lo, uint32_t len, int lane) {
+    const uint32_t last = lo + (len - 1u);
+    const uint32_t R0 = act_div(lo, rc), R1 = act_div(last, rc);     // the tile's first and last canvas row
+    const uint32_t q0 = lo - R0 * rc.d, q1 = last - R1 * rc.d;       // column bytes of its first and last byte
+    bool any = false;
+    for (int sb = 0; sb < nstreams; sb += 64) {
+        // the source bytes [slo, shi) that the tile's bytes of stream sb + lane come from (empty: the tile misses its destination)
+        uint32_t slo = 0, shi = 0;
+        if (sb + lane < nstreams) {
+            const uint32_t *rw = words + (size_t)(sb + lane) * kCwbWords;
+            const MosaicWords p{rw[0], rw[1], rw[2], rw[3], rw[4], rw[5]};
+            uint32_t ra = R0 > p.drow0 ? R0 : p.drow0, rb = R1 + 1u < p.drow1 ? R1 + 1u : p.drow1;   // rows [ra, rb)
+            // the tile's bytes of its first row may all lie behind the columns, those of its last row all before them
+            if (ra < rb && ra == R0 && q0 >= p.dcol1) ra++;
+            if (ra < rb && rb - 1u == R1 && q1 < p.dcol0) rb--;
+            if (ra < rb && p.dcol0 < p.dcol1) {
+                const uint32_t c0 = ra == R0 && q0 > p.dcol0 ? q0 : p.dcol0;
+                const uint32_t c1 = rb - 1u == R1 && q1 + 1u < p.dcol1 ? q1 + 1u : p.dcol1;
+                slo = (p.srow0 + (ra - p.drow0)) * rs.d + p.scol0 + (c0 - p.dcol0);
+                shi = (p.srow0 + (rb - 1u - p.drow0)) * rs.d + p.scol0 + (c1 - p.dcol0);
+            }
+        }
+        uint64_t hits = __ballot(slo < shi);
+        for (; hits; hits &= hits - 1ull) {
+            const int js = __ffsll((unsigned long long)hits) - 1;
+            const uint32_t st = (uint32_t)(sb + js);
+            const uint32_t ulo = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)slo, js, 64));
+            const uint32_t uhi = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)shi, js, 64));
+            const uint32_t *rw = words + (size_t)st * kCwbWords;
+            const MosaicWords p{rw[0], rw[1], rw[2], rw[3], rw[4], rw[5]};
+            const uint32_t ft = ulo / kCwaTile, lt = (uhi - 1u) / kCwaTile;   // the source tiles the range meets
+            const size_t b0 = (size_t)st * nframes;                           // the stream's first batch index
+            for (int base = 0; base < nframes; base += 64) {
+                bool touch = false;
+                if (base + lane < nframes) {
+                    const size_t b = b0 + base + lane;
+                    const uint32_t fn = a.ftab[b].n;
+                    const uint4 *dir = a.dir + b * a.ntiles;
+                    const uint32_t k0 = dir[ft].x, kend = lt + 1u < a.ntiles ? dir[lt + 1u].x : fn;
+                    touch = k0 < kend && k0 < fn;
+                }
+                const uint64_t set = __ballot(touch);
+                if (!set) continue;
+                if (!any) {
+                    for (uint32_t i = lane; i < kCwaTile / 16; i += 64) ((cwa_u32x4 *)s)[i] = cwa_u32x4{0u, 0u, 0u, 0u};
+                    any = true;
+                }
+                const int cnt = nframes - base < 64 ? nframes - base : 64;
+                // while record j is walked, the header, directory word and first block of the set's next record are in flight
+                int jn = __ffsll((unsigned long long)set) - 1;
+                CwaFrame f1 = a.ftab[b0 + base + jn];
+                uint4 d1 = a.dir[(b0 + base + jn) * a.ntiles + ft];
+                CwaBlock b1 = cwa_block_load(a, f1, d1.x, lane);
+                __syncthreads();
+                while (jn < cnt) {
+                    const int j = jn;
+                    const CwaFrame f = f1;
+                    const uint4 dr = d1;
+                    const CwaBlock blk = b1;
+                    const uint64_t rest = set & ~((2ull << j) - 1ull);   // (j = 63: 2 << 63 is 0, rest = 0)
+                    jn = rest ? __ffsll((unsigned long long)rest) - 1 : cnt;
+                    if (jn < cnt) {
+                        f1 = a.ftab[b0 + base + jn];
+                        d1 = a.dir[(b0 + base + jn) * a.ntiles + ft];
+                        b1 = cwa_block_load(a, f1, d1.x, lane);
+                    }
+                    cwa_walk_record<true>(a, f, dr, blk, ulo, uhi, lane, [=](uint32_t idx, uint8_t d) {
+                        const uint32_t r = act_div(idx, rs), col = idx - r * rs.d;
+                        if (r < p.srow0 || col < p.scol0) return;
+                        const uint32_t R = r - p.srow0 + p.drow0, q = col - p.scol0 + p.dcol0;
+                        if (R >= p.drow1 || q >= p.dcol1) return;
+                        const uint32_t y = R * rc.d + q;   // < Nc
+                        if (y < lo || y - lo >= len) return;
+                        s[y - lo] = (uint8_t)(s[y - lo] + d);
+                    });
+                    __syncthreads();
+                }
+            }
+        }
+    }
+    return any;
+}
+
+__global__ __launch_bounds__(64) void k_mosaic_facts(const CwaArgs a, int nstreams, int nframes, const uint32_t *words, const ActDiv rs,
+                                                     const ActDiv rc, uint32_t nc) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
+    uint8_t *s = (uint8_t *)s_q;
+    const int lane = threadIdx.x;
+    const uint32_t tile = blockIdx.x;
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = nc - lo < kCwaTile ? nc - lo : kCwaTile;
+    uint4 *fact = a.chunk + tile;
+    if (!mosaic_tile(s, a, nstreams, nframes, words, rs, rc, lo, len, lane)) {
+        if (lane == 0) *fact = make_uint4(0u, 0u, 0u, 0u);
+        return;
+    }
+    const uint4 f = cwc_tile_facts(s, lo, lane);
+    if (lane == 0) *fact = f;
+}
+
+template <bool CWIRE>
+__global__ __launch_bounds__(64) void k_mosaic_emit(const CwaArgs a, const CwcOut o, int nstreams, int nframes, const uint32_t *words,
+                                                    const ActDiv rs, const ActDiv rc, uint32_t nc) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
+    __shared__ uint32_t s_code32[CWIRE ? kCwaTile / 4 + 2 : 1], s_diff32[kCwaTile / 4 + 2];
+    uint8_t *s = (uint8_t *)s_q;
+    const int lane = threadIdx.x;
+    const uint32_t tile = blockIdx.x;
+    const uint4 fact = a.chunk[tile];   // {nonzero bytes, entries before, escapes before, end before}
+    if (fact.x == 0) return;
+    const uint32_t seg = o.offsets[0], n = o.offsets[1] - seg;
+    uint64_t fp0 = 0;
+    uint32_t e = 0;
+    if (CWIRE) {
+        fp0 = o.frame_pos[0];
+        const uint64_t fp1 = o.frame_pos[1];
+        if (fp1 > o.capacity) return;   // the record does not fit: skipped whole, by every workgroup alike
+        e = cwire_record_escapes(fp1 - fp0, n);
+    }
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = nc - lo < kCwaTile ? nc - lo : kCwaTile;
+    if (!mosaic_tile(s, a, nstreams, nframes, words, rs, rc, lo, len, lane)) return;   // (the facts say otherwise)
+    cwc_emit_tile<CWIRE>(s, (uint8_t *)s_code32, (uint8_t *)s_diff32, fact, o, seg, n, fp0, e, lo, lane);
+}
+
 // ---- mi355_cwire_check_batch: one verdict of four words per record, from the records alone (include/mi355diff.h) ---------------
 // The chunk table of the directory (k_cwa_table, k_cwa_facts, k_cwa_scan field 0: per chunk of kCwaChunk codes the 255 codes, the
 // sum of g + 1 over the others -- at most 4096 * 255, it cannot wrap -- and the chunk's first escape rank), then two kernels of
@@ -2287,6 +2460,39 @@ hipError_t launch_cwire_crop(const CwaArgs &a, const CwaFrame *records, int nstr
         hipLaunchKernelGGL(k_cwc_scan<false>, dim3(nstreams), dim3(256), 0, s, a, o);
         hipLaunchKernelGGL(k_cwc_place<false>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, nstreams);
         if (a.ntiles) hipLaunchKernelGGL(k_crop_emit<false>, tiles, dim3(64), 0, s, a, o, nframes, (const uint32_t *)words, row);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_cwire_mosaic(const CwaArgs &a, const CwaFrame *records, int nstreams, int nframes, const int32_t *place, uint32_t width,
+                               uint32_t canvas_w, uint32_t canvas_bytes, uint32_t *words, const CwcOut &o, bool cwire, hipStream_t s) {
+    if (nstreams <= 0 || nframes <= 0) return hipSuccess;
+    const ActDiv rs = act_divisor(3u * width), rc = act_divisor(3u * canvas_w);
+    const int ns = a.ntiles ? nstreams : 0;   // (frames of no bytes: nothing lands anywhere)
+    if (ns) {
+        launch_cwa_directory(a, records, nstreams * nframes, s);
+        MosaicArgs h{};
+        for (int s0 = 0; s0 < nstreams; s0 += kMosaicStreams) {
+            h.first = s0;
+            h.count = nstreams - s0 < kMosaicStreams ? nstreams - s0 : kMosaicStreams;
+            for (int j = 0; j < h.count; j++)
+                for (int k = 0; k < 6; k++) h.place[j][k] = place[6 * (size_t)(s0 + j) + k];
+            hipLaunchKernelGGL(k_mosaic_table, dim3(1), dim3(kMosaicStreams), 0, s, words, h);
+        }
+    }
+    CwaArgs ac = a;   // the coalescer's scan sees ONE stream of the canvas' tiles
+    ac.n = canvas_bytes;
+    ac.ntiles = cwa_tiles(canvas_bytes);
+    const dim3 canvas_tiles(ac.ntiles);   // (the canvas' size alone: no count of frames, streams or records sizes this grid)
+    hipLaunchKernelGGL(k_mosaic_facts, canvas_tiles, dim3(64), 0, s, a, ns, nframes, (const uint32_t *)words, rs, rc, canvas_bytes);
+    if (cwire) {
+        hipLaunchKernelGGL(k_cwc_scan<true>, dim3(1), dim3(256), 0, s, ac, o);
+        hipLaunchKernelGGL(k_cwc_place<true>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, 1);
+        hipLaunchKernelGGL(k_mosaic_emit<true>, canvas_tiles, dim3(64), 0, s, a, o, ns, nframes, (const uint32_t *)words, rs, rc, canvas_bytes);
+    } else {
+        hipLaunchKernelGGL(k_cwc_scan<false>, dim3(1), dim3(256), 0, s, ac, o);
+        hipLaunchKernelGGL(k_cwc_place<false>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, 1);
+        hipLaunchKernelGGL(k_mosaic_emit<false>, canvas_tiles, dim3(64), 0, s, a, o, ns, nframes, (const uint32_t *)words, rs, rc, canvas_bytes);
     }
     return hipGetLastError();
 }

@@ -94,7 +94,8 @@ typedef struct mi355_config {
  *      + mi355_state_tiles, mi355_state_digest_host, mi355_state_digest_batch, mi355_refresh_cwire_batch,
  *      mi355_state_clear_tiles_batch (additions only);
  *      + mi355_wall_thumb_size, mi355_wall_compose_batch, mi355_cwire_touched_tiles_batch (additions only);
- *      + mi355_cwire_crop_batch, mi355_cwire_crop_cwire_batch, MI355_CROP_KEEP_INDEX (additions only) */
+ *      + mi355_cwire_crop_batch, mi355_cwire_crop_cwire_batch, MI355_CROP_KEEP_INDEX (additions only);
+ *      + mi355_cwire_mosaic_batch, mi355_cwire_mosaic_cwire_batch (additions only) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -566,6 +567,78 @@ int mi355_cwire_crop_batch(mi355_core *core, const void *d_cwire, const uint32_t
 int mi355_cwire_crop_cwire_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
                                  int nstreams, int nframes, const int32_t *h_rects, unsigned flags, void *d_offsets,
                                  void *d_frame_pos, void *d_cwire_out, size_t capacity_bytes);
+
+/* Many cameras on one canvas: the opposite direction of the crop.  The records of mi355_cwire_coalesce_* / mi355_cwire_crop_*
+ * (same input, same batch index b = s*nframes + t, the headers h_counts[b] / h_escapes[b] from the host, the header words in the
+ * buffer not trusted, frames of the core's W x H, N bytes) -> ONE segment / record for a BGR24 canvas of canvas_w x canvas_h
+ * pixels, Nc = 3*canvas_w*canvas_h bytes, that shows the cameras side by side at full resolution.  For a multiview relay (four
+ * 1080p cameras in a 4K canvas, one record per tick for a client that holds one canvas state and reads one socket), a recorder
+ * that keeps one stream per wall, and row-band sharding: the compact records of several cores that each own a band of one
+ * picture merged into the whole picture's record (mi355_merge_parts does that for the arrays form only).  Placing commutes with
+ * the client's state[x] += diff, exactly as cropping does, so it is exact and needs no state.
+ *   Placement: h_place[s] = {sx, sy, w, h, dx, dy} in pixels: the rectangle [sx, sx + w) x [sy, sy + h) of camera s goes to
+ *   [dx, dx + w) x [dy, dy + h) of the canvas.  w == 0 or h == 0 places nothing.
+ *   Sums: sum_s[x] = the uint8 wrap-around sum of stream s's differences at byte index x < N, as in the coalescer.  Canvas byte
+ *   y lies in row R = y / (3*canvas_w) at column byte q = y % (3*canvas_w); stream s covers y when dy <= R < dy + h and
+ *   3*dx <= q < 3*(dx + w), and its source byte is then (sy + R - dy)*3*W + 3*sx + (q - 3*dx).  C[y] = the uint8 sum of
+ *   sum_s[source byte] over the streams that cover y.  Destination rectangles that overlap are not refused: their differences
+ *   add, which is well defined and spares an S^2 host check.
+ *   Outputs: the ONE segment holds the entries (y, C[y]) with C[y] != 0 in ascending y; d_offsets = {0, n} (uint32[2]).  The
+ *   compact form writes its canonical record (headers written, pad bytes zero, byte for byte what mi355_cwire_encode_batch would
+ *   write) at d_cwire_out, d_frame_pos = {0, record bytes} (uint64[2]), both always exact; the record is written only if it
+ *   fits, otherwise nothing of it is written.  Arrays form: entries at or past `capacity` are dropped.
+ *   mi355_cwire_bytes_max(Nc, 1) always suffices.  A canvas no camera lands on yields the 8-byte n = 0 record.
+ *   Laws: (a) apply -- applying the output to an Nc-byte canvas state K changes exactly the covered bytes; with disjoint
+ *   destinations the rectangle of K at (dx, dy, w, h) becomes what stream s's records make of it through the crop law.
+ *   (b) inverse of the crop -- with disjoint destinations, mi355_cwire_crop_cwire_batch of the output, on a core of the canvas'
+ *   geometry with rectangle (dx, dy, w, h), equals mi355_cwire_crop_cwire_batch of stream s's input with (sx, sy, w, h), byte
+ *   for byte.  (c) special cases -- one stream with {0, 0, W, H, 0, 0} on a W x H canvas is the coalescer's output byte for
+ *   byte; one stream with {x0, y0, w, h, 0, 0} on a w x h canvas is the crop call's.  (d) bands -- {0, 0, W, H, 0, s*H} on a
+ *   W x S*H canvas is the bands' coalesced records concatenated with index bias s*N.
+ *   Malformed content under consistent headers: the family's memory safety -- nothing is read outside the input span, nothing
+ *   is written outside the outputs; an index >= N and an escape ranked at or past e contribute nothing.  The output is still
+ *   one canonical record: mi355_cwire_check_host(Nc, ...) gives word 0 == 0.  Only canvas bytes inside the malformed stream's
+ *   destination are otherwise unspecified.
+ *   Refused with MI355_ERR_INVALID before anything is launched or written: whatever mi355_cwire_coalesce_* refuses; a null
+ *   h_place when nstreams*nframes > 0; a negative member of a placement; sx + w > W or sy + h > H; dx + w > canvas_w or
+ *   dy + h > canvas_h (all computed in 64 bits); canvas_w or canvas_h < 1; Nc >= 2^31, the bound mi355_create puts on a frame;
+ *   the input span overlapping an output region; and a canvas of more 4096-byte tiles than the fact scratch holds, that is
+ *   mi355_state_tiles(Nc) > max_batch * mi355_state_tiles(N).  Nothing is allocated inside the call: the per-tile facts take
+ *   the scratch the core made for max_batch records, so a canvas needs a core whose max_batch covers it -- four 1080p
+ *   cameras in a 3840 x 2160 canvas: mi355_state_tiles(N) = 1519, max_batch 4 gives 6076 words for the canvas' 6075 tiles.
+ *   nstreams*nframes == 0 writes offsets[0] = 0 (and frame_pos[0] = 0) and nothing else.
+ * Asynchronous on the core's stream, behind the last expansion of this core as every consumer of a packed stream is; with a
+ * caller's stream everything runs on it in call order.  Nothing is copied to the device: the placements travel as kernel
+ * arguments of a small table kernel (128 streams per launch), which leaves six words per stream in the per-stream words of
+ * mi355_cwire_budget_cwire_batch (the two calls are ordered on one stream).  The core's state is neither read nor written.
+ * The directory kernels on the nstreams*nframes records, the table kernel, then a tile grid over the CANVAS: a 4096-byte canvas
+ * tile tests 64 streams a round (do its rows meet the destination's, does it hold a byte of its columns), per hit 64 records a
+ * round on the directory words of the source tiles its bytes come from, and per record with an entry there walks the record
+ * once from the first of those tiles, adding the entries of the source rectangle at their canvas byte into a zeroed tile in
+ * LDS.  The coalescer's scan and placement follow unchanged, for one stream of mi355_state_tiles(Nc) tiles; the tile grid runs
+ * again and writes the entries.  The row of a source byte comes from an exact multiply-and-correct division by 3W, once per
+ * kept entry; while a record is walked, the header, directory word and first block of the next are in flight.  A first form:
+ * a walk begins at the first source tile's edge, not at the first byte the canvas tile needs, and a canvas narrower than the
+ * source frames walks over source rows it then drops.
+ * Measured (profiles/multi_mosaic.json: tools/bench_multi.py --legs mosaic --streams 4,16; the compact form at 1080p, whole
+ * frames in a 2x2 grid of a 3840 x 2160 canvas and a 4x4 grid of a 7680 x 4320 canvas, median of five rounds, spread of the rounds
+ * 0.2 - 9 %), us per input record, the call / the route a caller has without it in the same run
+ * (mi355_apply_multi_stream_cwire_batch onto relay-held states, mi355_wall_compose_batch at k = 1 into a canvas, a synchronize,
+ * mi355_diff_stream_cwire_batch(nframes = 1) on a threshold-0 core of the canvas' geometry; its record equals the call's byte
+ * for byte at every point).  Webcam-like input (137 k entries per record): S = 4, T = 1 26.09 / 36.33, T = 16 4.96 / 3.22; S = 16,
+ * T = 1 19.16 / 17.18, T = 16 4.08 / 2.23.  Local input (a block moving over a still background, 4.8 k entries): S = 4, T = 1
+ * 25.43 / 35.81, T = 16 3.19 / 2.84; S = 16, T = 1 14.12 / 15.92, T = 16 1.73 / 1.45.  The expectation -- no slower than that route at
+ * any point, by more than the rounds' spread -- is met at T = 1 for S = 4 on both inputs and for S = 16 on the local input (0.71 -
+ * 0.89 of the route) and MISSED at T = 1 for S = 16 webcam-like cameras (1.12) and at T = 16 everywhere (1.12 - 1.83): the route
+ * pays per state and canvas byte once per call whatever T is, the call per record entry, in both tile passes.  Not profiled per
+ * kernel, not tuned in this change.  DESIGN.md section 4, "Placing cameras on a canvas". */
+int mi355_cwire_mosaic_batch(mi355_core *core, const void *d_cwire_in, const uint32_t *h_counts, const uint32_t *h_escapes,
+                             int nstreams, int nframes, const int32_t *h_place /* [nstreams][6] */, int canvas_w, int canvas_h,
+                             void *d_offsets /* uint32[2] */, void *d_xs, void *d_diff, size_t capacity);
+int mi355_cwire_mosaic_cwire_batch(mi355_core *core, const void *d_cwire_in, const uint32_t *h_counts, const uint32_t *h_escapes,
+                                   int nstreams, int nframes, const int32_t *h_place, int canvas_w, int canvas_h,
+                                   void *d_offsets /* uint32[2] */, void *d_frame_pos /* uint64[2] */, void *d_cwire_out,
+                                   size_t capacity_bytes);
 
 /* A tick held to a budget: the sender's rate control.  The nstreams compact records mi355_diff_multi_cwire_batch just wrote
  * (back to back where h_counts[s] / h_escapes[s] put them; the headers come from the host and are not trusted in the buffer, as

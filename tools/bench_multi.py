@@ -70,6 +70,15 @@ the records of one tick (T = 1), in microseconds per stream, ONE JSON line for a
 The expectations to test: `crop_quarter` no slower than `coalesce` by more than the rounds' spread
 (`quarter_no_slower_than_coalesce`), and `crop_full` within the spread plus the one table launch (`full_minus_coalesce_us_per_call`).
 
+The mosaic leg (--legs mosaic, a run of its own: `--legs mosaic --streams 4,16 > profiles/multi_mosaic.json`) measures the call that
+places S cameras side by side on one canvas (a C x C grid of whole frames, C = ceil(sqrt(S)): 2x2 into 3840x2160 and 4x4 into
+7680x4320 at 1080p), in microseconds per input record, ONE JSON line: T = 1 and T = 16, on the webcam-like and the local input:
+  mosaic         mi355_cwire_mosaic_cwire_batch on the S*T records: ONE canvas record, no state;
+  state_route    the route a caller has without the call: mi355_apply_multi_stream_cwire_batch onto relay-held states,
+                 mi355_wall_compose_batch at k = 1 into a canvas, then (behind a synchronize: another core)
+                 mi355_diff_stream_cwire_batch(nframes = 1) on a threshold-0 core of the canvas' geometry.
+The expectation to test: `mosaic` no slower than `state_route` by more than the rounds' spread (`mosaic_no_slower_than_route`).
+
 The activity leg (--legs activity, a run of its own: `--legs activity --streams 4,16,64 > profiles/multi_activity.json`) measures
 the motion grids, in microseconds per record, ONE JSON line: S = 4, 16, 64 (--streams) with T = 1 and S = 16 with T = 16, on both
 inputs of the burst-client leg:
@@ -1139,6 +1148,111 @@ def run_crop(W, H, S, rounds, kind):
     return out
 
 
+def run_mosaic(W, H, S, T, rounds, kind):
+    """The mosaic leg for one (S, T) and one input -> its dictionary.  mosaic: mi355_cwire_mosaic_cwire_batch on the burst's
+    records, whole frames in a C x R grid.  state_route: mi355_apply_multi_stream_cwire_batch onto states the relay holds,
+    mi355_wall_compose_batch at k = 1 into a canvas, a synchronize, mi355_diff_stream_cwire_batch(nframes = 1) on a threshold-0
+    core of the canvas' geometry.  Alternating within every round."""
+    import math
+    import numpy as np
+    from cudavideostream_amd import CUDACore, cwire_bytes_max
+    dev = torch.device("cuda", 0)
+    n, B = 3 * W * H, S * T
+    C = math.isqrt(S - 1) + 1
+    R = (S + C - 1) // C
+    cw, ch = C * W, R * H
+    nc = 3 * cw * ch
+    assert B * n < (1 << 32) and nc < (1 << 31), "the leg runs in one call: max_batch * N < 2^32 and a canvas below 2^31 bytes"
+    passes = 2 * max(1, 256 // B)
+    if kind == "webcam":                                # run_burst's input: one stream cut into S pieces
+        _, web = synth.webcam_stream(B + 1, W, H, device=dev)
+        web = web.reshape(B + 1, n)
+        states0, fwd = web[0:B:T].clone(), web[1:].reshape(S, T, n)
+    else:
+        states0, fwd = local_streams(S, T, W, H, dev)
+    cwcap = cwire_bytes_max(n, B)
+    d_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
+    d_pos = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+    d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
+    srv_states = states0.clone()
+    with CUDACore(W, H, max_batch=B) as server:
+        torch.cuda.synchronize()
+        server.diff_multi_stream_cwire_batch(fwd, srv_states, S, T, d_off, d_pos, d_cw, cwcap)
+        server.synchronize()
+    pos = d_pos.cpu().numpy().astype(np.int64)
+    counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
+    pad = (counts.astype(np.int64) + 3) & ~3
+    escapes = ((np.diff(pos) - 8 - 2 * pad) // 4).astype(np.uint32)
+    recs, in_bytes = d_cw[:int(pos[B])].clone(), int(pos[B])
+    del d_cw, fwd, srv_states
+    ocap = cwire_bytes_max(nc, 1)
+    d_ooff = torch.zeros(2, dtype=torch.int32, device=dev)
+    d_opos = torch.zeros(2, dtype=torch.int64, device=dev)
+    d_out = torch.empty(ocap, dtype=torch.uint8, device=dev)
+    d_roff, d_rpos, d_rout = torch.zeros_like(d_ooff), torch.zeros_like(d_opos), torch.empty_like(d_out)
+    place = np.array([[0, 0, W, H, (s % C) * W, (s // C) * H] for s in range(S)], np.int32)
+    wall_place = np.array([[(s % C) * W, (s // C) * H, 1] for s in range(S)], np.int32)
+    states = states0.clone()
+    d_canvas = torch.zeros(nc, dtype=torch.uint8, device=dev)
+    relay = CUDACore(W, H, max_batch=max(B, C * R))    # one fact word per canvas tile where max_batch frames keep theirs
+    route = CUDACore(W, H, max_batch=B)
+    canvas = CUDACore(cw, ch, max_batch=1, threshold=0)
+    torch.cuda.synchronize()
+
+    def route_pass():
+        route.apply_multi_stream_cwire_batch(recs, counts, escapes, S, T, states)
+        route.wall_compose_batch(states, S, wall_place, d_canvas, cw, ch)
+        route.synchronize()
+        canvas.diff_stream_cwire_batch(d_canvas, 1, d_roff, d_rpos, d_rout, ocap)
+
+    # the route's record of the first burst, from a canvas core primed with the tiling of the base states, is the call's record
+    route.wall_compose_batch(states, S, wall_place, d_canvas, cw, ch)
+    route.synchronize()
+    canvas.diff_stream_cwire_batch(d_canvas, 1, d_roff, d_rpos, d_rout, ocap)
+    canvas.synchronize()
+    route_pass()
+    canvas.synchronize()
+    relay.cwire_mosaic_cwire_batch(recs, counts, escapes, S, T, place, cw, ch, d_ooff, d_opos, d_out, ocap)
+    relay.synchronize()
+    out_entries, out_bytes = int(d_ooff[1].item()), int(d_opos[1].item())
+    equal = bool(int(d_rpos[1].item()) == out_bytes and torch.equal(d_rout[:out_bytes], d_out[:out_bytes]))
+
+    def leg_mosaic():
+        for _ in range(passes):
+            relay.cwire_mosaic_cwire_batch(recs, counts, escapes, S, T, place, cw, ch, d_ooff, d_opos, d_out, ocap)
+        relay.synchronize()
+
+    def leg_route():
+        for _ in range(passes):
+            route_pass()
+        canvas.synchronize()
+
+    table = {"mosaic": leg_mosaic, "state_route": leg_route}
+    times = {}
+    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
+        for name, leg in table.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            leg()
+            dt = time.perf_counter() - t0
+            if r:
+                times.setdefault(name, []).append(dt * 1e6 / (passes * B))
+    out = {"input": kind, "streams": S, "frames": T, "passes": passes, "grid": [C, R], "canvas": [cw, ch],
+           "input_entries_per_record": round(float(counts.sum()) / B, 1), "input_bytes_per_record": round(in_bytes / B, 1),
+           "canvas_entries": out_entries, "canvas_record_bytes": out_bytes, "route_record_equals_mosaic": equal}
+    med, spread = {}, {}
+    for name in table:
+        st = stats(times[name])
+        st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
+        out[name + "_us_per_record"] = st
+        med[name], spread[name] = st["median"], st["max"] - st["min"]
+    out["mosaic_over_route"] = round(med["mosaic"] / med["state_route"], 3)
+    out["mosaic_no_slower_than_route"] = bool(med["mosaic"] <= med["state_route"] + max(spread["mosaic"], spread["state_route"]))
+    for c in (relay, route, canvas):
+        c.close()
+    return out
+
+
 def run_budget(W, H, S, rounds):
     """The budget leg for one S -> its dictionary.  budget: mi355_cwire_budget_cwire_batch on the records of one tick with every
     stream's budget at half of its count, on the states as the tick left them.  second_diff: mi355_diff_multi_cwire_batch over the
@@ -1214,7 +1328,7 @@ def main():
     ap.add_argument("--steps", type=int, default=8, help="K: webcam frames a stream walks through")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--legs", default="multi,cores_loop,pairs",
-                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or crop alone; or budget alone; or activity alone; or check alone; or refresh alone; or wall alone")
+                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or crop alone; or mosaic alone; or budget alone; or activity alone; or check alone; or refresh alone; or wall alone")
     ap.add_argument("--frames", default="4,16,64", help="burst, burst_client and coalesce legs: T, frames per stream and call")
     a = ap.parse_args()
     have = load_library()
@@ -1263,6 +1377,16 @@ def main():
                 print(f"crop S={S} {kind}: done", file=sys.stderr, flush=True)
                 torch.cuda.empty_cache()
         print(json.dumps({"bench": "multi_crop", "size": f"{W}x{H}", "rounds": a.rounds, "crop": per}), flush=True)
+        return
+    if a.legs == "mosaic":
+        per = []
+        for S in (int(v) for v in a.streams.split(",")):
+            for T in (1, 16):
+                for kind in ("webcam", "local"):
+                    per.append(run_mosaic(W, H, S, T, a.rounds, kind))
+                    print(f"mosaic S={S} T={T} {kind}: done", file=sys.stderr, flush=True)
+                    torch.cuda.empty_cache()
+        print(json.dumps({"bench": "multi_mosaic", "size": f"{W}x{H}", "rounds": a.rounds, "mosaic": per}), flush=True)
         return
     if a.legs == "budget":
         per = []

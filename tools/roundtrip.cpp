@@ -11,7 +11,7 @@
 // (ActivityCheck, RecordCheck, WallCheck), that is that mode.
 //
 //   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B]
-//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check] | --resync K [--burst B] | --crop X,Y,W,H [--burst K]] [--wall K]]
+//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check] | --resync K [--burst B] | --crop X,Y,W,H [--burst K] | --mosaic CxR [--burst K]] [--wall K]]
 //   exit status 0 = all checks passed
 #include <algorithm>
 #include <cstdint>
@@ -941,6 +941,90 @@ static int run_multi_crop(int w, int h, int T, int S, int K, const int32_t *rect
     return 0;
 }
 
+// --compact --multi S --mosaic CxR [--burst K]: a multiview relay.  It holds no frame: it uploads every camera's records as they
+// came off its socket (one tick, or a burst of K) and makes ONE record of a canvas of C x R cells with ONE
+// mi355_cwire_mosaic_cwire_batch, camera s whole in cell (s % C, s / C); S <= C*R, the cells behind the last camera stay empty.
+// The receiver is a viewer that holds one C*W x R*H host state, seeded with the tiling of the base frames, reads one socket and
+// applies the record with mi355_cwire_apply_host.  After every tick or burst its canvas must equal the tiling of the sender's
+// states and of full-size host clients that applied the original records.
+static void tile_frames(uint8_t *canvas, const uint8_t *frames, int S, int w, int h, int C) {
+    const size_t n = (size_t)3 * w * h, row = (size_t)3 * w, crow = row * C;
+    for (int s = 0; s < S; s++)
+        for (int y = 0; y < h; y++)
+            memcpy(canvas + ((size_t)(s / C) * h + y) * crow + (size_t)(s % C) * row, frames + (size_t)s * n + (size_t)y * row, row);
+}
+
+static int run_multi_mosaic(int w, int h, int T, int S, int K, int C, int R) {
+    const bool burst = K > 0;
+    if (!burst) K = 1;
+    Session ss(w, h);
+    const size_t n = ss.n, nc = n * C * R;
+    const int cw = C * w, ch = R * h;
+    Cameras cams(S, w, h);
+    Sender tx;
+    Receiver relay;
+    // the relay's core keeps one fact word per 4096-byte tile of the canvas where it keeps those of max_batch frames: C*R suffice
+    if (tx.open(ss, S, K) || relay.open(ss, S, S * K > C * R ? S * K : C * R, S * K, false)) return 1;
+    const size_t cap = mi355_cwire_bytes_max(nc, 1);
+    void *d_roff = ss.dev(relay.core, sizeof(uint32_t) * 2), *d_rpos = ss.dev(relay.core, sizeof(uint64_t) * 2);
+    void *d_fwd = ss.dev(relay.core, cap);
+    if (!ss.ok()) return 1;
+    std::vector<uint8_t> host_frames((size_t)S * n), fwd(cap), rx(cap), tiled(nc, 0), canvas(nc, 0);
+    std::vector<int32_t> place((size_t)6 * S);
+    for (int s = 0; s < S; s++) {
+        const int32_t p[6] = {0, 0, w, h, (s % C) * w, (s / C) * h};
+        memcpy(&place[(size_t)6 * s], p, sizeof p);
+    }
+    uint32_t roff[2];
+    uint64_t rpos[2];
+    // the sender's states and the full-size host clients from the base frames; the viewer's canvas from their tiling, through the pipe
+    OK(mi355_upload(tx.core, tx.d_states, cams.bases.data(), cams.bases.size()));
+    memcpy(host_frames.data(), cams.bases.data(), cams.bases.size());
+    tile_frames(tiled.data(), cams.bases.data(), S, w, h, C);
+    if (!ss.send(tiled.data(), canvas.data(), nc)) return 1;
+    size_t received = 0, forwarded = 0, kept = 0;
+    int calls = 0;
+    for (int t0 = 0; t0 < T; t0 += K) {
+        const int nb = T - t0 < K ? T - t0 : K;
+        cams.fill(tx.frames.data(), t0, nb);
+        // ---- server: nb ticks of S cameras -> S * nb records in one call
+        if (tx.step(nb, burst)) return 1;
+        // ---- the sockets into the relay; a full-size host client beside it applies every original record
+        if (slices_to_node(ss, tx, relay, nb, host_frames.data(), nullptr)) return 1;
+        received += tx.cb;
+        // ---- relay: the records -> ONE record of the canvas, in one call; no frame exists here
+        OK(mi355_cwire_mosaic_cwire_batch(relay.core, relay.d_rx, relay.counts.data(), relay.escapes.data(), S, nb, place.data(), cw, ch,
+                                          d_roff, d_rpos, d_fwd, cap));
+        calls++;
+        OK(mi355_download(relay.core, roff, d_roff, sizeof roff));
+        OK(mi355_download(relay.core, rpos, d_rpos, sizeof rpos));
+        if (roff[0] != 0 || rpos[0] != 0 || rpos[1] > cap) { fprintf(stderr, "canvas record larger than its bound\n"); return 1; }
+        const size_t fb = (size_t)rpos[1];
+        OK(mi355_download(relay.core, fwd.data(), d_fwd, fb));
+        kept += roff[1];
+        // ---- the ONE socket out of the relay; the viewer reads the header and applies the record to its canvas
+        if (!ss.send(fwd.data(), rx.data(), fb)) return 1;
+        forwarded += fb;
+        uint32_t cnt, esc;
+        size_t at[2];
+        if (walk_records(rx.data(), 0, fb, 1, &cnt, &esc, at) || cnt != roff[1]) { fprintf(stderr, "canvas record framing broken\n"); return 1; }
+        if (host_apply(canvas.data(), nc, rx.data(), at, 0)) return 1;
+        // ---- checks: the tiling of the sender's states, and of the host clients that applied all the original records
+        if (tx.get_states()) return 1;
+        tile_frames(tiled.data(), tx.states.data(), S, w, h, C);
+        if (same(tiled.data(), canvas.data(), nc, "viewer's canvas != tiling of the sender's states", t0)) return 1;
+        tile_frames(tiled.data(), host_frames.data(), S, w, h, C);
+        if (same(tiled.data(), canvas.data(), nc, "viewer's canvas != tiling of the host clients' frames", t0)) return 1;
+    }
+    if (kept == 0) { fprintf(stderr, "no entry reached the canvas: nothing was checked\n"); return 1; }
+    if (ss.close()) return 1;
+    printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"burst\": %d, \"mosaic\": [%d, %d], \"relay_calls\": %d, "
+           "\"width\": %d, \"height\": %d, \"canvas\": [%d, %d], \"ticks\": %d, \"changed_bytes\": %zu, \"canvas_entries\": %zu, "
+           "\"relay_received_bytes\": %zu, \"relay_forwarded_bytes\": %zu, \"canvases_equal_every_step\": true}\n",
+           S, burst ? K : 0, C, R, calls, w, h, cw, ch, T, tx.changed, kept, received, forwarded);
+    return 0;
+}
+
 namespace {
 struct Expected {   // the plain path's client frames, in order, from the sender to the receiver thread
     std::mutex m;
@@ -1401,11 +1485,19 @@ int main(int argc, char **argv) {
         {"--budget", &budget, 0, 0}};
     int32_t crop[4] = {0, 0, 0, 0};
     bool cropped = false, crop_ok = true;
+    int grid[2] = {0, 0};
+    bool mosaic = false, mosaic_ok = true;
     for (int i = 1; i < argc; i++) {   // (an option the tool does not know is ignored)
         if (!strcmp(argv[i], "--crop") && i + 1 < argc) {
             char tail = 0;
             cropped = true;
             crop_ok = sscanf(argv[++i], "%d,%d,%d,%d%c", &crop[0], &crop[1], &crop[2], &crop[3], &tail) == 4;
+            continue;
+        }
+        if (!strcmp(argv[i], "--mosaic") && i + 1 < argc) {
+            char tail = 0;
+            mosaic = true;
+            mosaic_ok = sscanf(argv[++i], "%dx%d%c", &grid[0], &grid[1], &tail) == 2;
             continue;
         }
         for (const auto &f : flags)
@@ -1438,6 +1530,13 @@ int main(int argc, char **argv) {
         if (!crop_ok || crop[0] < 0 || crop[1] < 0 || crop[2] < 1 || crop[3] < 1 || (long)crop[0] + crop[2] > w || (long)crop[1] + crop[3] > h)
             return usage("--crop X,Y,W,H needs a rectangle of at least one pixel inside the frame");
     }
+    if (mosaic) {
+        if (!compact || !multi || cropped || budget >= 0 || coalesce || per_frame || burst_client || activity || check || resync >= 0 || wall)
+            return usage("--mosaic CxR needs --compact --multi S, alone or with --burst K");
+        if (!mosaic_ok || grid[0] < 1 || grid[1] < 1 || (long)grid[0] * grid[1] < multi || (long)grid[0] * grid[1] > 4096 ||
+            3.0 * w * h * grid[0] * grid[1] >= 2147483648.0)
+            return usage("--mosaic CxR needs C, R >= 1, S <= C*R <= 4096 cells and a canvas below 2^31 bytes");
+    }
     if (per_frame) {
         if (!compact || direct || gpu_client || multi) return usage("--per-frame needs --compact alone");
         return run_per_frame(w, h, T);
@@ -1446,6 +1545,7 @@ int main(int argc, char **argv) {
     if (!compact || direct || gpu_client || multi < 0) return usage("--multi S needs --compact alone and S >= 1");
     if (resync >= 0) return run_multi_resync(w, h, T, multi, resync, burst, wall);
     if (cropped) return run_multi_crop(w, h, T, multi, burst, crop);
+    if (mosaic) return run_multi_mosaic(w, h, T, multi, burst, grid[0], grid[1]);
     if (coalesce) return run_multi_burst_coalesce(w, h, T, multi, burst);
     if (budget >= 0) return run_multi_budget(w, h, T, multi, budget);
     if (burst && !burst_client) return run_multi_burst(w, h, T, multi, burst);
