@@ -266,6 +266,14 @@ class CUDACore:
         _l.check(self._lib.mi355_diff_pairs_batch(self._h, _ptr(d_cur), _ptr(d_prev), stride, nframes,
                                                   _ptr(d_offsets), _ptr(d_xs), _ptr(d_diff), capacity))
 
+    def diff_consecutive_batch(self, d_first_prev, d_frames, nframes, d_offsets, d_xs, d_diff, capacity, stride=None):
+        """Frame 0 against the one frame at d_first_prev, frame t against frame t - 1 of d_frames; no feedback, every frame
+        read once.  The core's state is not involved (include/mi355diff.h)."""
+        self._hold(d_first_prev, d_frames, d_offsets, d_xs, d_diff)
+        stride = self.total if stride is None else stride
+        _l.check(self._lib.mi355_diff_consecutive_batch(self._h, _ptr(d_first_prev), _ptr(d_frames), stride, nframes,
+                                                        _ptr(d_offsets), _ptr(d_xs), _ptr(d_diff), capacity))
+
     # -- the stream either side of the path (wire format, client, row-band merge) -------------------
     def diff_stream_wire_batch(self, d_frames, nframes, d_offsets, d_wire, capacity_bytes, stride=None):
         """threads.cpp:227-229 byte stream of the batch: {u32 n, i32 xs[n], u8 diff[n]} per frame."""

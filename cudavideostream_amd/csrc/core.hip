@@ -375,6 +375,9 @@ struct CwireOut {
 // states, one per STREAM (mi355_diff_multi_stream_*).  A tile of a state is read and written by the launches of one stream only,
 // exactly as with feedback pairs (the cut depends on the frame size alone), so the two forms share the fb_states bookkeeping
 // and may alternate on the same states.
+// consecutive (stream mode, no feedback): d_prev is ONE frame, the predecessor of frame 0; frame t is compared with frame t - 1
+// (mi355_diff_consecutive_batch).  The core's state takes no part.  d_prev may be the core's state or a caller's states: like a
+// pair batch's operand it is read tile by tile by the launch that packs the tile, on the stream that wrote that tile.
 // pipelined: a public batch entry point on the core's OWN stream -- the index and the expansion run on the side
 // stream beside the next batch's pack kernel (which needs only the state, carried on the core's stream, and a free
 // set of logs); completion is what mi355_synchronize / any other entry point waits for (use_device joins).  With a
@@ -395,12 +398,12 @@ CwireDirectArgs cwire_args(mi355_core *c, const CwireOut *cw, const uint32_t *d_
 int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, size_t stride,
               int nframes, void *d_offsets, void *d_xs, void *d_diff, size_t capacity,
               void *d_wire = nullptr, bool pipelined = false, const CwireOut *cw = nullptr, bool feedback = false,
-              int seg = 0) {
+              int seg = 0, bool consecutive = false) {
     if (!c) return fail(MI355_ERR_INVALID, "null core");
     if (nframes < 0 || nframes > c->cfg.max_batch)
         return fail(MI355_ERR_INVALID, "nframes outside [0, max_batch]");
     if (!d_offsets) return fail(MI355_ERR_INVALID, "null d_offsets");
-    if (nframes > 0 && c->n > 0 && (!d_cur || (pair && !d_prev)))
+    if (nframes > 0 && c->n > 0 && (!d_cur || ((pair || consecutive) && !d_prev)))
         return fail(MI355_ERR_INVALID, "null frame pointer");
     if (nframes > 0 && stride < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
     if (capacity > 0 && !d_wire && !cw && (!d_xs || !d_diff)) return fail(MI355_ERR_INVALID, "null output pointer");
@@ -468,7 +471,8 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
     a.rec_bytes = (uint32_t)((size_t)c->cfg.max_batch * c->ntiles * 1024u);
     a.meta_bytes = (uint32_t)((size_t)c->cfg.max_batch * c->ntiles * 16u);
     // the vector path of the pack kernel: 16-byte aligned operands, and a group of four frames within reach of one
-    // buffer descriptor's 32-bit offsets (diff_pack.hip, Group::load_desc)
+    // buffer descriptor's 32-bit offsets (diff_pack.hip, Group::load_desc); d_prev: the pairs' second operand, or the one
+    // predecessor of consecutive frames (nullptr otherwise)
     const bool aligned = (((uintptr_t)d_cur | (uintptr_t)d_prev | stride) & 15u) == 0 && 3 * (uint64_t)stride + c->n < (1ull << 32);
     // Pair mode: do the two operands share a frame (or part of one), i.e. does prev + j * stride come within a frame of
     // cur + i * stride for some i, j < T?  Pairs of consecutive frames do (cur of one pair is prev of the next: the second
@@ -500,17 +504,17 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
         PackArgs a0 = a, a1 = a;
         a0.tile_end = cut;
         a1.tile_begin = cut;
-        HIP_TRY(launch_diff_pack(a0, pair, aligned, pair_once, blocks0, c->stream, feedback));
+        HIP_TRY(launch_diff_pack(a0, pair, aligned, pair_once, blocks0, c->stream, feedback, consecutive));
         HIP_TRY(hipStreamWaitEvent(c->main2, c->fork[c->flip], 0));
         if (ls.in_use) HIP_TRY(hipStreamWaitEvent(c->main2, ls.expanded, 0));
-        HIP_TRY(launch_diff_pack(a1, pair, aligned, pair_once, blocks1, c->main2, feedback));
+        HIP_TRY(launch_diff_pack(a1, pair, aligned, pair_once, blocks1, c->main2, feedback, consecutive));
         HIP_TRY(hipEventRecord(c->packed2[c->flip], c->main2));
         HIP_TRY(hipStreamWaitEvent(tail, c->packed2[c->flip], 0));
         if (tev) HIP_TRY(hipEventRecord(tev[5], c->main2));   // the pack "kernel" of a split batch ends when BOTH parts have
         c->parts_pending = c->flip;
         if (feedback) { c->fb_states = d_prev; c->fb_stride = stride; }
     } else {
-        HIP_TRY(launch_diff_pack(a, pair, aligned, pair_once, pipelined ? k1_blocks : 0u, c->stream, feedback));
+        HIP_TRY(launch_diff_pack(a, pair, aligned, pair_once, pipelined ? k1_blocks : 0u, c->stream, feedback, consecutive));
     }
     if (tev) {
         HIP_TRY(hipEventRecord(tev[1], c->stream));
@@ -937,6 +941,12 @@ static int check_multi_stream(mi355_core *c, const void *d_frames, const void *d
     const Region fr = windows(c, d_frames, (int64_t)nstreams * nframes, stride, "the frames");
     if (overlap(st, fr)) return overlap_fail(st, fr);
     return MI355_OK;
+}
+
+int mi355_diff_consecutive_batch(mi355_core *c, const void *d_first_prev, const void *d_frames, size_t frame_step_bytes, int nframes,
+                                 void *d_offsets, void *d_xs, void *d_diff, size_t capacity) {
+    return run_batch(c, false, d_frames, d_first_prev, frame_step_bytes, nframes, d_offsets, d_xs, d_diff, capacity, nullptr, true,
+                     nullptr, false, 0, true);
 }
 
 int mi355_diff_multi_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,

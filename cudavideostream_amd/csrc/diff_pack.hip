@@ -22,6 +22,10 @@
 //                 it appends a 4-byte code {map, the byte's difference, lane} to the tile's code log; a lane
 //                 with two or more flagged bytes also appends its 16 masked difference bytes to the record
 //                 log (see "the log" below).  Per (frame, tile) one 16-byte meta word.
+//                 Forms of the kernel (template flags): pairs (both operands from memory), feedback pairs (FB), segmented
+//                 streams (SEG), and consecutive frames without feedback (SEQ: stream mode whose register-held comparand
+//                 is the frame just compared -- pairs of consecutive frames with every frame loaded once, not twice;
+//                 DESIGN.md, K1, says what that is worth: the pair form's second load of a frame hits in the L2).
 //   k_scan_groups: per frame, flagged bytes before every range of 16 tiles; its last workgroup scans the
 //               frame totals into offsets[0..T].
 //   k_expand    : one wave per (frame, 16 tiles): turns codes and records into the caller's packed,
@@ -276,11 +280,14 @@ __device__ __forceinline__ void exchange_state(const PackArgs &a, Seg &sg, uint4
     sg.chg = 0u;
 }
 
-template <bool PAIR, bool FAST, bool HIGH, bool FB = false, bool SEG = false>
+// SEQ (stream mode, no feedback): the comparand of the next frame is the frame just compared, whatever was flagged -- the
+// select at the end of compare_step is overwritten at once and the compiler drops it.
+template <bool PAIR, bool FAST, bool HIGH, bool FB = false, bool SEG = false, bool SEQ = false>
 __device__ __forceinline__ void pack_group(const PackArgs &a, const Group<PAIR, FAST> &g, int t0, uint4 &st,
                                            LogPos &lp, uint32_t tile, ThrConst tc, int lane, const LogOut &lg,
                                            const StateOut *so = nullptr, int valid = 16, Seg *sg = nullptr,
                                            const uint4 *ns = nullptr) {
+    static_assert(!SEQ || (!PAIR && !FB && !SEG), "consecutive frames are a form of plain stream mode");
     bool first = true;   // SEG: no exchange inside this group yet
     // The group's kPrefetch meta words are assembled in lanes 0..kPrefetch-1 and leave with ONE store.
     constexpr int kPrefetch = PrefetchOf<PAIR>::value;
@@ -299,6 +306,7 @@ __device__ __forceinline__ void pack_group(const PackArgs &a, const Group<PAIR, 
             sg->left -= 1;
         }
         compare_step<HIGH>(g.c[d], st, tc, dm0, m0);
+        if (SEQ) st = g.c[d];
         if (SEG) sg->chg |= m0;
         if (FB) store_state<FAST>(a, *so, d, st, m0, valid);
         const uint32_t c0 = emit_step(dm0, m0, lg, lp, jump, lane24, pc0, pm0);
@@ -311,6 +319,7 @@ __device__ __forceinline__ void pack_group(const PackArgs &a, const Group<PAIR, 
             }
             uint32_t dm1[4];
             compare_step<HIGH>(g.c[d + 1], st, tc, dm1, m1);
+            if (SEQ) st = g.c[d + 1];
             if (SEG) sg->chg |= m1;
             if (FB) store_state<FAST>(a, *so, d + 1, st, m1, valid);
             c1 = emit_step(dm1, m1, lg, lp, jump, lane24, pc1, pm1);
@@ -334,7 +343,7 @@ __device__ __forceinline__ void pack_group(const PackArgs &a, const Group<PAIR, 
     __builtin_amdgcn_raw_buffer_store_b128(mv, lg.meta, (lane < kPrefetch && t0 + lane < a.nframes) ? moff : kOOB, 0, 0);
 }
 
-template <bool PAIR, bool FAST, bool HIGH, bool ONCE, bool FB = false, bool SEG = false>
+template <bool PAIR, bool FAST, bool HIGH, bool ONCE, bool FB = false, bool SEG = false, bool SEQ = false>
 __device__ __forceinline__ void pack_tile(const PackArgs &a, uint32_t tile, uint32_t byte_off,
                                           int valid, int lane) {
     const int T = a.nframes;
@@ -343,7 +352,8 @@ __device__ __forceinline__ void pack_tile(const PackArgs &a, uint32_t tile, uint
     const LogOut lg{make_rsrc(a.codes, a.codes_bytes), make_rsrc(a.rec, a.rec_bytes), make_rsrc(a.meta, a.meta_bytes)};
 
     uint4 st = make_uint4(0, 0, 0, 0);
-    if (!PAIR && !SEG) st = load16<FAST>(a.state + byte_off, valid);
+    if (SEQ) st = load16<FAST>(a.prev + byte_off, valid);   // the first frame's predecessor; the core's state takes no part
+    else if (!PAIR && !SEG) st = load16<FAST>(a.state + byte_off, valid);
 
     // Two register groups: while one is processed (its stores are issued), the other's loads are in
     // flight.
@@ -415,16 +425,16 @@ __device__ __forceinline__ void pack_tile(const PackArgs &a, uint32_t tile, uint
         for (int t0 = 0;;) {
             cb += gstep; if (PAIR) pb += gstep; left -= (int64_t)gstep;
             gb.template load_desc<ONCE>(desc(cb), desc(pb), voff);
-            pack_group<PAIR, FAST, HIGH>(a, ga, t0, st, lp, tile, tc, lane, lg);
+            pack_group<PAIR, FAST, HIGH, false, false, SEQ>(a, ga, t0, st, lp, tile, tc, lane, lg);
             t0 += kPrefetch;
             if (t0 >= T) break;
             cb += gstep; if (PAIR) pb += gstep; left -= (int64_t)gstep;
             ga.template load_desc<ONCE>(desc(cb), desc(pb), voff);
-            pack_group<PAIR, FAST, HIGH>(a, gb, t0, st, lp, tile, tc, lane, lg);
+            pack_group<PAIR, FAST, HIGH, false, false, SEQ>(a, gb, t0, st, lp, tile, tc, lane, lg);
             t0 += kPrefetch;
             if (t0 >= T) break;
         }
-        if (!PAIR) *reinterpret_cast<uint4 *>(a.state + byte_off) = st;
+        if (!PAIR && !SEQ) *reinterpret_cast<uint4 *>(a.state + byte_off) = st;
         return;
     }
     const uint8_t *cur_last = a.cur + (size_t)(T - 1) * a.stride, *prev_last = PAIR ? a.prev + (size_t)(T - 1) * a.stride : nullptr;
@@ -472,17 +482,17 @@ __device__ __forceinline__ void pack_tile(const PackArgs &a, uint32_t tile, uint
     for (int t0 = 0;;) {
         cp += gstep; if (PAIR) pp += gstep;
         gb.load(a, byte_off, t0 + kPrefetch, valid, cp, pp, cur_last, prev_last);
-        pack_group<PAIR, FAST, HIGH>(a, ga, t0, st, lp, tile, tc, lane, lg);
+        pack_group<PAIR, FAST, HIGH, false, false, SEQ>(a, ga, t0, st, lp, tile, tc, lane, lg);
         t0 += kPrefetch;
         if (t0 >= T) break;
         cp += gstep; if (PAIR) pp += gstep;
         ga.load(a, byte_off, t0 + kPrefetch, valid, cp, pp, cur_last, prev_last);
-        pack_group<PAIR, FAST, HIGH>(a, gb, t0, st, lp, tile, tc, lane, lg);
+        pack_group<PAIR, FAST, HIGH, false, false, SEQ>(a, gb, t0, st, lp, tile, tc, lane, lg);
         t0 += kPrefetch;
         if (t0 >= T) break;
     }
 
-    if (!PAIR) {
+    if (!PAIR && !SEQ) {
         if (FAST) *reinterpret_cast<uint4 *>(a.state + byte_off) = st;
         else store16_bytes(a.state + byte_off, st, valid);
     }
@@ -490,8 +500,11 @@ __device__ __forceinline__ void pack_tile(const PackArgs &a, uint32_t tile, uint
 
 // FB (pair mode only): feedback pairs -- frame t's state, as compare_step leaves it, goes back to prev + t * stride.
 // SEG (stream mode only): the batch is a.nframes / a.seg segments of a.seg frames, each on its own state in a.states (Seg).
-template <bool PAIR, bool ALIGNED, bool HIGH, bool ONCE = !PAIR, bool FB = false, bool SEG = false>
+// SEQ (plain stream mode only): consecutive frames without feedback -- frame 0 against a.prev (one frame), frame t against
+// frame t - 1, which the wave still holds in registers; a.state is neither read nor written.
+template <bool PAIR, bool ALIGNED, bool HIGH, bool ONCE = !PAIR, bool FB = false, bool SEG = false, bool SEQ = false>
 __global__ __launch_bounds__(256) void k_diff_pack(const PackArgs a) {
+    static_assert(!SEQ || (!PAIR && !FB && !SEG), "consecutive frames are a form of plain stream mode");
     static_assert(!FB || PAIR, "feedback write-back is a form of pair mode");
     static_assert(!SEG || !PAIR, "segments are a form of stream mode");
     const int lane = threadIdx.x & 63;
@@ -506,16 +519,16 @@ __global__ __launch_bounds__(256) void k_diff_pack(const PackArgs a) {
         const uint32_t byte_off = tile_off + (uint32_t)lane * 16u;
         // wave-uniform choice: every lane of a full, aligned tile takes the vector path
         if (ALIGNED && tile_off + kTileBytes <= a.n) {
-            pack_tile<PAIR, true, HIGH, ONCE, FB, SEG>(a, tile, byte_off, 16, lane);
+            pack_tile<PAIR, true, HIGH, ONCE, FB, SEG, SEQ>(a, tile, byte_off, 16, lane);
         } else {
             const int valid = byte_off < a.n ? (int)min(16u, a.n - byte_off) : 0;
-            pack_tile<PAIR, false, HIGH, ONCE, FB, SEG>(a, tile, byte_off, valid, lane);
+            pack_tile<PAIR, false, HIGH, ONCE, FB, SEG, SEQ>(a, tile, byte_off, valid, lane);
         }
     }
 }
 
 hipError_t launch_diff_pack(const PackArgs &a, bool pair, bool aligned, bool pair_once, uint32_t max_blocks, hipStream_t s,
-                            bool feedback) {
+                            bool feedback, bool consecutive) {
     const dim3 block(64 * kWavesPerBlock);
     uint32_t blocks = (a.tile_end - a.tile_begin + kWavesPerBlock - 1) / kWavesPerBlock;
     if (max_blocks && max_blocks < blocks) blocks = max_blocks;
@@ -529,7 +542,15 @@ hipError_t launch_diff_pack(const PackArgs &a, bool pair, bool aligned, bool pai
         if (high) hipLaunchKernelGGL((k_diff_pack<P, A, true>), grid, block, 0, s, a);                 \
         else hipLaunchKernelGGL((k_diff_pack<P, A, false>), grid, block, 0, s, a);                     \
     } while (0)
-    if (!pair && a.seg > 0) {   // a.states = the caller's states, one per segment of a.seg frames (core.hip, run_batch)
+    if (consecutive) {   // a.prev = the ONE predecessor of frame 0 (core.hip, run_batch); every frame is read once
+        if (aligned) {
+            if (high) hipLaunchKernelGGL((k_diff_pack<false, true, true, true, false, false, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((k_diff_pack<false, true, false, true, false, false, true>), grid, block, 0, s, a);
+        } else {
+            if (high) hipLaunchKernelGGL((k_diff_pack<false, false, true, true, false, false, true>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((k_diff_pack<false, false, false, true, false, false, true>), grid, block, 0, s, a);
+        }
+    } else if (!pair && a.seg > 0) {   // a.states = the caller's states, one per segment of a.seg frames (core.hip, run_batch)
         if (aligned) {
             if (high) hipLaunchKernelGGL((k_diff_pack<false, true, true, true, false, true>), grid, block, 0, s, a);
             else hipLaunchKernelGGL((k_diff_pack<false, true, false, true, false, true>), grid, block, 0, s, a);

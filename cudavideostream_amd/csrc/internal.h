@@ -15,7 +15,7 @@ constexpr uint32_t kWavesPerBlock = 4;
 
 struct PackArgs {
     const uint8_t *cur;    // frame t at cur + t*stride
-    const uint8_t *prev;   // pair mode: prev frame t at prev + t*stride; stream mode: unused
+    const uint8_t *prev;   // pair mode: prev frame t at prev + t*stride; consecutive frames: frame 0's predecessor; stream mode: unused
     union {
         uint8_t *state;    // stream mode: N bytes, read at start and written back at the end
         uint8_t *states;   // segmented stream mode (seg > 0): stream s's state at states + s*stride, read when its segment
@@ -67,7 +67,9 @@ int core_device(const ::mi355_core *c);
 // a.seg > 0 (stream mode only): the segmented form, a.states instead of a.state
 hipError_t launch_diff_pack(const PackArgs &a, bool pair, bool aligned, bool pair_once /* pair mode: no frame is an operand twice */,
                             uint32_t max_blocks /* 0: one tile per wave */, hipStream_t s,
-                            bool feedback = false /* pair mode: prev + t * stride is writable and takes frame t's fed-back state */);
+                            bool feedback = false /* pair mode: prev + t * stride is writable and takes frame t's fed-back state */,
+                            bool consecutive = false /* stream mode without feedback: frame t against frame t - 1, frame 0
+                                                        against the one frame at a.prev; a.state unused */);
 uint32_t expand_groups(uint32_t ntiles);
 // A frame total travels as ONE 64-bit word {total: 31 bits (a frame is below 2 GiB), tag of the launch: 33 bits}
 // (diff_pack.hip, publish_total).  The tag counts the launches of a core and is never 0 (0 = never written); when it

@@ -65,6 +65,8 @@ SYMBOLS = {
                                           C.c_void_p, C.c_void_p, C.c_size_t]),
     "mi355_diff_pairs_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mi355_diff_consecutive_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "mi355_diff_stream_wire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
                                                C.c_void_p, C.c_size_t]),
     "mi355_diff_stream_cwire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,

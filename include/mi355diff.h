@@ -95,7 +95,8 @@ typedef struct mi355_config {
  *      mi355_state_clear_tiles_batch (additions only);
  *      + mi355_wall_thumb_size, mi355_wall_compose_batch, mi355_cwire_touched_tiles_batch (additions only);
  *      + mi355_cwire_crop_batch, mi355_cwire_crop_cwire_batch, MI355_CROP_KEEP_INDEX (additions only);
- *      + mi355_cwire_mosaic_batch, mi355_cwire_mosaic_cwire_batch (additions only) */
+ *      + mi355_cwire_mosaic_batch, mi355_cwire_mosaic_cwire_batch (additions only);
+ *      + mi355_diff_consecutive_batch (additions only) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -250,6 +251,32 @@ int mi355_diff_stream_batch(mi355_core *core, const void *d_frames, size_t strid
 int mi355_diff_pairs_batch(mi355_core *core, const void *d_cur, const void *d_prev,
                            size_t stride_bytes, int nframes, void *d_offsets, void *d_xs,
                            void *d_diff, size_t capacity);
+
+/* Consecutive frames, stateless, every frame read ONCE: frame 0 is compared with the one frame at d_first_prev,
+ * frame t >= 1 with frame t-1 of d_frames (d_frames + (t-1)*frame_step_bytes; frame_step_bytes is the distance between two
+ * frames in bytes, with the rules of every stride_bytes of this header: >= the frame's bytes, bounded above by the address
+ * space alone, a multiple of 16 for the fast path).  No feedback: the comparand of frame t+1 is
+ * frame t itself, not a reconstructed state (the reference's stateless benchmark, tests/algorithms_benchmarks.cu:24-40,
+ * run over a recorded sequence; the reference keeps the previous frame resident and swaps, server/src/kernels.cu:451 --
+ * here a wave keeps the previous frame of its tile in registers, as the stream kernel keeps the state).  For every t in
+ * order and every byte i ascending: df = frame[t][i] - prev[t][i]; |df| > threshold emits (i, (uint8)df).
+ * The output is bit for bit that of mi355_diff_pairs_batch(d_cur = d_frames, prev = {d_first_prev, d_frames,
+ * d_frames + frame_step_bytes, ...}) if such a prev could be expressed; with d_first_prev == d_frames - frame_step_bytes it IS
+ * mi355_diff_pairs_batch(core, d_frames, d_frames - frame_step_bytes, ...), d_offsets included, with every frame loaded
+ * once instead of twice (measured 14 to 19 % faster per pair at 4K and 1080p, profiles/pair_consecutive.json; the bytes
+ * fetched from memory drop by 4 % only, the pair form's second load of a frame hits in the L2).
+ * The core's state is neither read nor written, and nothing at d_first_prev or in d_frames is written.  d_first_prev may
+ * lie anywhere readable: inside the frames' buffer (a ring), in another buffer (the last frame of the block before, for a
+ * rank that takes frames [rB, (r+1)B) of a sequence plus one predecessor), or be mi355_state_device_ptr(core).
+ * Capacity, drop, alignment (d_first_prev counts as an operand: off 16 bytes it sends the batch down the byte path) and
+ * d_offsets rules, the ordering and pipelining on the core's own stream (the two launches at 64 tiles and more included)
+ * and the behaviour on a caller's stream are those of mi355_diff_pairs_batch.  MI355_ERR_INVALID, before anything is
+ * launched or written: a null d_first_prev or d_frames with nframes > 0 and a frame of more than 0 bytes; nframes outside
+ * [0, max_batch]; frame_step_bytes < frame bytes; null outputs where mi355_diff_pairs_batch refuses them.  nframes == 0
+ * writes offsets[0] = 0.  mi355_diff_pairs_batch does not route itself here, whatever its operands. */
+int mi355_diff_consecutive_batch(mi355_core *core, const void *d_first_prev, const void *d_frames,
+                                 size_t frame_step_bytes, int nframes,
+                                 void *d_offsets, void *d_xs, void *d_diff, size_t capacity);
 
 /* ---- the stream either side of the path ---------------------------------------
  * Wire form of mi355_diff_stream_batch: instead of separate (xs, diff) arrays the batch leaves as the exact

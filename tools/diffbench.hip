@@ -9,6 +9,9 @@
 //             [--pairs] [--checksum T] [--cores C] [--digest]
 //             [--regime s0|flip|static] [--apart]   pairs of the dense / static regimes; pairs that share no frame
 //             [--lib-alloc]             the two output arrays from mi355_alloc_outputs (a pair placed for the dense expansion)
+//   diffbench --consecutive [--width W] [--height H] [--batch B] [--steps K]   mi355_diff_consecutive_batch on one buffer of
+//                                                   B + 1 frames, then mi355_diff_pairs_batch on the same views: us per pair
+//                                                   of both, and whether offsets and entries are equal (exit 5 if not)
 //   diffbench --filters [--batch B] [--steps K]     the filter kernels and the BASELINE config 3 / 4 chains
 //                                                   (same lines as tools/bench_filters.py, for the --pmc passes)
 #include <hip/hip_runtime.h>
@@ -89,7 +92,7 @@ __global__ __launch_bounds__(64) void k_corun_mem(const uint4 *buf, size_t nvec,
 int main(int argc, char **argv) {
     int W = 1920, H = 1080, B = 256, K = 20, WU = 3, checksum_t = -2, ncores = 1;
     uint32_t seed = 21;
-    bool pairs = false, filters = false, digest = false, apart = false;
+    bool pairs = false, filters = false, digest = false, apart = false, consecutive = false;
     bool lib_alloc = false;   // the two output arrays from mi355_alloc_outputs (a pair placed for the dense expansion)
     const char *corun = nullptr; int corun_blocks = 2048;
     const char *regime = nullptr;   // --regime s0|flip|static: pairs of the dense / static regimes (tools/bench_regimes.py's inputs)
@@ -106,6 +109,7 @@ int main(int argc, char **argv) {
         else if (!strcmp(argv[i], "--apart")) { pairs = true; apart = true; }   // pairs (0,1), (2,3), ...: no frame is an operand twice (round-robin sharding)
         else if (!strcmp(argv[i], "--cores")) next(ncores);
         else if (!strcmp(argv[i], "--filters")) filters = true;
+        else if (!strcmp(argv[i], "--consecutive")) consecutive = true;
         else if (!strcmp(argv[i], "--digest")) digest = true;
         else if (!strcmp(argv[i], "--corun") && i + 1 < argc) corun = argv[++i];
         else if (!strcmp(argv[i], "--regime") && i + 1 < argc) { regime = argv[++i]; pairs = true; }
@@ -215,6 +219,59 @@ int main(int argc, char **argv) {
         printf("{\"note\": \"chains: algorithmic bytes above exclude the 5P of the packed stream\", \"last_chain_changed_bytes_per_frame\": %.1f}\n", (double)h_tot / B);
         mi355_destroy(core);
         return 0;
+    }
+    if (consecutive) {   // ONE buffer of B + 1 frames; frame t against frame t - 1: the new call, then the pair form on the same views
+        mi355_core *core = nullptr;
+        MI_OK(mi355_create(&cfg, &core));
+        uint8_t *buf = nullptr;
+        HIP_OK(hipMalloc((void **)&buf, n * (size_t)(B + 1)));
+        const dim3 g((unsigned)((n + 255) / 256)), b(256);
+        for (int t = 0; t <= B; t++) hipLaunchKernelGGL(k_webcam_frame, g, b, 0, 0, buf + (size_t)t * n, t - 1, W, H, seed);
+        HIP_OK(hipDeviceSynchronize());
+        const size_t cap = (size_t)B * n / 8 > (1u << 20) ? (size_t)B * n / 8 : (1u << 20);
+        uint32_t *d_off[2]; int32_t *d_xs[2]; uint8_t *d_df[2];
+        for (int k = 0; k < 2; k++) {
+            HIP_OK(hipMalloc((void **)&d_off[k], sizeof(uint32_t) * (B + 1)));
+            HIP_OK(hipMalloc((void **)&d_xs[k], sizeof(int32_t) * cap));
+            HIP_OK(hipMalloc((void **)&d_df[k], cap));
+            HIP_OK(hipMemset(d_off[k], 0xEE, sizeof(uint32_t) * (B + 1)));
+        }
+        const uint8_t *first_prev = buf, *frames = buf + n;
+        auto step = [&](int k) {
+            if (k == 0) MI_OK(mi355_diff_consecutive_batch(core, first_prev, frames, n, B, d_off[0], d_xs[0], d_df[0], cap));
+            else MI_OK(mi355_diff_pairs_batch(core, frames, first_prev, n, B, d_off[1], d_xs[1], d_df[1], cap));
+        };
+        double us[2] = {0, 0};
+        for (int k = 0; k < 2; k++) {
+            for (int i = 0; i < WU; i++) step(k);
+            MI_OK(mi355_synchronize(core));
+            const auto t0 = std::chrono::high_resolution_clock::now();
+            for (int i = 0; i < K; i++) step(k);
+            MI_OK(mi355_synchronize(core));
+            us[k] = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count() * 1e6 / ((double)K * B);
+        }
+        std::vector<uint32_t> off[2];
+        bool equal = true;
+        for (int k = 0; k < 2; k++) {
+            off[k].resize(B + 1);
+            HIP_OK(hipMemcpy(off[k].data(), d_off[k], sizeof(uint32_t) * (B + 1), hipMemcpyDeviceToHost));
+        }
+        equal = off[0] == off[1] && off[0][0] == 0;
+        const size_t p = equal ? (off[0][B] < cap ? off[0][B] : cap) : 0;
+        if (equal) {
+            std::vector<int32_t> hx[2]; std::vector<uint8_t> hd[2];
+            for (int k = 0; k < 2; k++) {
+                hx[k].resize(p); hd[k].resize(p);
+                HIP_OK(hipMemcpy(hx[k].data(), d_xs[k], sizeof(int32_t) * p, hipMemcpyDeviceToHost));
+                HIP_OK(hipMemcpy(hd[k].data(), d_df[k], p, hipMemcpyDeviceToHost));
+            }
+            equal = hx[0] == hx[1] && hd[0] == hd[1];
+        }
+        printf("{\"harness\": \"diffbench\", \"mode\": \"consecutive\", \"width\": %d, \"height\": %d, \"batch\": %d, \"steps\": %d, "
+               "\"consecutive_us_per_pair\": %.3f, \"pairs_us_per_pair\": %.3f, \"changed_bytes_per_frame\": %.1f, \"outputs\": \"%s\"}\n",
+               W, H, B, K, us[0], us[1], (double)off[0][B] / B, equal ? "equal" : "DIFFERENT");
+        mi355_destroy(core);
+        return equal ? 0 : 5;
     }
     mi355_core *core = nullptr;
     MI_OK(mi355_create(&cfg, &core));
