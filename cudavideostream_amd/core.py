@@ -548,6 +548,21 @@ class CUDACore:
         _l.check(self._lib.mi355_cwire_check_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
                                                    int(nrecords), _ptr(d_verdicts)))
 
+    # ... and a sender on a datagram socket: every record cut into pieces that are records themselves
+    def cwire_split_cwire_batch(self, d_cwire, counts, escapes, nrecords, max_bytes, d_piece_first, d_piece_pos, piece_capacity,
+                                d_cwire_out, capacity_bytes):
+        """Every compact record (headers counts / escapes, back to back) cut into pieces of at most max_bytes bytes (a multiple of
+        4 in [64, 65536]), each a record of the same frame: piece p at d_cwire_out + d_piece_pos[p] (uint64[piece_capacity + 1]),
+        record r's pieces are d_piece_first[r] .. d_piece_first[r + 1] (uint32[nrecords + 1]).  cwire_split_host is the same on
+        the host and the definition; cwire_split_pieces_max / cwire_split_bytes_max give sufficient capacities."""
+        self._hold(d_cwire, d_piece_first, d_piece_pos, d_cwire_out)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+        assert counts.size >= nrecords and escapes.size >= nrecords
+        _l.check(self._lib.mi355_cwire_split_cwire_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
+                                                         int(nrecords), int(max_bytes), _ptr(d_piece_first), _ptr(d_piece_pos),
+                                                         int(piece_capacity), _ptr(d_cwire_out), int(capacity_bytes)))
+
     # ... and when a record was refused or lost after all: the receiver's digests, the sender's refresh, the receiver's clear
     def state_digest_batch(self, d_states, nstreams, d_digests, stride=None):
         """Two words per tile of 4096 bytes of each of nstreams states (stream s at d_states + s*stride, any alignment) into
@@ -820,6 +835,39 @@ def cwire_check_host(buf, counts, escapes, frame_bytes):
     _l.check(L.mi355_cwire_check_host(int(frame_bytes), buf.ctypes.data, buf.size, counts.ctypes.data, escapes.ctypes.data,
                                       counts.size, verdicts.ctypes.data))
     return verdicts
+
+
+def cwire_split_pieces_max(n, e, max_bytes):
+    """A sufficient piece count for a record of n entries and e escapes split at max_bytes (0 for a max_bytes outside
+    [64, 65536])."""
+    return _l.load().mi355_cwire_split_pieces_max(int(n), int(e), int(max_bytes))
+
+
+def cwire_split_bytes_max(n, e, max_bytes):
+    """A sufficient byte count for the pieces of a record of n entries and e escapes split at max_bytes."""
+    return _l.load().mi355_cwire_split_bytes_max(int(n), int(e), int(max_bytes))
+
+
+def cwire_split_host(buf, counts, escapes, frame_bytes, max_bytes, piece_capacity=None, capacity_bytes=None):
+    """cwire_split_cwire_batch computed on the host (no GPU, no core) and its definition: (piece_first uint32[nrecords + 1],
+    piece_pos uint64[piece_capacity + 1], out uint8[capacity_bytes]) for the records of `buf` that the headers counts / escapes
+    describe.  The capacities default to the helpers' sums, which always suffice."""
+    L = _l.load()
+    buf = np.ascontiguousarray(np.frombuffer(buf, np.uint8) if isinstance(buf, (bytes, bytearray)) else buf, dtype=np.uint8)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+    assert counts.size == escapes.size
+    if piece_capacity is None:
+        piece_capacity = sum(L.mi355_cwire_split_pieces_max(int(n), int(e), int(max_bytes)) for n, e in zip(counts, escapes))
+    if capacity_bytes is None:
+        capacity_bytes = sum(L.mi355_cwire_split_bytes_max(int(n), int(e), int(max_bytes)) for n, e in zip(counts, escapes))
+    piece_first = np.zeros(counts.size + 1, np.uint32)
+    piece_pos = np.zeros(int(piece_capacity) + 1, np.uint64)
+    out = np.zeros(max(int(capacity_bytes), 1), np.uint8)
+    _l.check(L.mi355_cwire_split_host(int(frame_bytes), buf.ctypes.data, buf.size, counts.ctypes.data, escapes.ctypes.data,
+                                      counts.size, int(max_bytes), piece_first.ctypes.data, piece_pos.ctypes.data,
+                                      int(piece_capacity), out.ctypes.data, int(capacity_bytes)))
+    return piece_first, piece_pos, out[:int(capacity_bytes)]
 
 
 def state_tiles(frame_bytes):

@@ -16,6 +16,7 @@
 //                          export and its frame_pos[2]; made by the first such call (or MI355_PREPARE_EXEC_CWIRE)
 //   cw_items  T*ceil(W/16)*16 + T*4  mi355_diff_stream_cwire_batch: one word per item of the expansion, escapes per frame
 //   cwa_*     T*24 + 2*T*ceil(N/4096)*16  mi355_apply_cwire_batch: frame table, chunk facts, tile directory
+//   cws_*     2*T*max(1, ceil(N/65536))*16  mi355_cwire_split_cwire_batch: per block of 65536 entries its pieces and bytes, their bases
 //   hist T*256*4, thr T*4 (per frame of a filter batch), k9 9*4, heat LUT 766*3, glyph atlas
 #include <cmath>
 #include <cstdio>
@@ -92,6 +93,8 @@ struct mi355_core {
     CwaFrame *cwa_ftab = nullptr;   // mi355_apply_cwire_batch (stream_ops.hip): [T] frame headers of a slice,
     uint4 *cwa_chunk = nullptr;     // [T * cwa_chunks(N)] chunk facts,
     uint4 *cwa_dir = nullptr;       // [T][cwa_tiles(N)] directory words
+    uint4 *cws_blk = nullptr;       // mi355_cwire_split_cwire_batch (stream_ops.hip): [T * cws_blocks(N)] block words
+    ulonglong2 *cws_base = nullptr; // ... and the pieces and bytes before each block
     uint32_t *cwb_hist = nullptr;   // mi355_cwire_budget_cwire_batch: [T][kCwbWords] bins of |cur - prev|, budget and threshold per stream
     uint8_t *gray1 = nullptr;      // fused gray+binarize chain: one gray byte per pixel of a batch, made on first use
     size_t gray1_stride = 0;
@@ -648,6 +651,8 @@ int mi355_create(const mi355_config *cfg, mi355_core **out) {
     if (!rc) rc = dev_alloc(c, &c->cwa_chunk, T * cwa_chunks(c->n));
     if (!rc) rc = dev_alloc(c, &c->cwa_dir, T * cwa_tiles(c->n));
     if (!rc) rc = dev_alloc(c, &c->cwb_hist, T * kCwbWords);
+    if (!rc) rc = dev_alloc(c, &c->cws_blk, T * cws_blocks(c->n));
+    if (!rc) rc = dev_alloc(c, &c->cws_base, T * cws_blocks(c->n));
     if (!rc) rc = dev_alloc(c, &c->one_xs, N + 4);
     if (!rc) rc = dev_alloc(c, &c->one_diff, N + 16);
     if (!rc) rc = dev_alloc(c, &c->hist, 256 * T);
@@ -694,7 +699,7 @@ void mi355_destroy(mi355_core *c) {
     }
     void *ptrs[] = {c->state, c->in, c->aux, c->vis, c->rec, c->codes, c->meta, c->groff, c->totals, c->offsets, c->one_xs, c->one_diff, c->hist, c->thr, c->k9,
                     c->lut, c->glyphs, c->kxk, c->gray1, c->red_bounds, c->cw_cnt, c->cw_items, c->cw_esc,
-                    c->cwa_ftab, c->cwa_chunk, c->cwa_dir, c->cwb_hist, c->cw_rec, c->cw_rec_pos};
+                    c->cwa_ftab, c->cwa_chunk, c->cwa_dir, c->cwb_hist, c->cws_blk, c->cws_base, c->cw_rec, c->cw_rec_pos};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->h_count) (void)hipHostFree(c->h_count);
     if (c->h_rec) (void)hipHostFree(c->h_rec);
@@ -1819,6 +1824,144 @@ int mi355_cwire_check_batch(mi355_core *c, const void *d_cwire, const uint32_t *
     if (int rc = use_device(c)) return rc;
     const CwaArgs a = cwa_args(c, d_cwire);
     HIP_TRY(launch_cwire_check(a, tab.fr.data(), nrecords, (uint32_t *)d_verdicts, c->stream));
+    return MI355_OK;
+}
+
+// ---- mi355_cwire_split_host / _cwire_batch: records cut into pieces of at most max_bytes (include/mi355diff.h, "the piece rule") ----
+static uint64_t split_content_pieces(uint64_t n, uint64_t e, uint64_t M) { return (2 * cwire_pad4(n) + 4 * e) / (M - 35); }
+
+size_t mi355_cwire_split_pieces_max(uint32_t n, uint32_t e, size_t max_bytes) {
+    if (max_bytes < 64 || max_bytes > kCwsBlock) return 0;
+    return (size_t)(((uint64_t)n + kCwsBlock - 1) / kCwsBlock + split_content_pieces(n, e, max_bytes));
+}
+
+size_t mi355_cwire_split_bytes_max(uint32_t n, uint32_t e, size_t max_bytes) {
+    if (max_bytes < 64 || max_bytes > kCwsBlock) return 0;
+    return (size_t)cwire_record_bytes(n, e) + 12 * mi355_cwire_split_pieces_max(n, e, max_bytes);
+}
+
+static int split_check_limit(size_t max_bytes) {
+    if (max_bytes < 64 || max_bytes > kCwsBlock || (max_bytes & 3u))
+        return fail(MI355_ERR_INVALID, "max_bytes must be a multiple of 4 in [64, 65536]");
+    return MI355_OK;
+}
+
+// The definition.  The decode rule of the GPU clients (an escape ranked at or past e adds nothing, the running index wraps at
+// 2^32), so that the piece sizes of malformed content are the device form's, too.
+int mi355_cwire_split_host(size_t frame_bytes, const void *cwire, size_t cwire_bytes, const uint32_t *h_counts,
+                           const uint32_t *h_escapes, int nrecords, size_t max_bytes, uint32_t *piece_first, uint64_t *piece_pos,
+                           size_t piece_capacity, void *out, size_t capacity_bytes) {
+    if (nrecords < 0) return fail(MI355_ERR_INVALID, "nrecords < 0");
+    if (frame_bytes >= 0xFFFFFFFFull) return fail(MI355_ERR_INVALID, "frame_bytes must be below 2^32 - 1");
+    if (int rc = split_check_limit(max_bytes)) return rc;
+    if (nrecords == 0) {
+        if (piece_first) piece_first[0] = 0;
+        if (piece_pos) piece_pos[0] = 0;
+        return MI355_OK;
+    }
+    if (!cwire || !h_counts || !h_escapes) return fail(MI355_ERR_INVALID, "null stream pointer");
+    if (!piece_first || !piece_pos || !out) return fail(MI355_ERR_INVALID, "null output pointer");
+    uint64_t span = 0;
+    for (int r = 0; r < nrecords; r++) {
+        if (h_escapes[r] > h_counts[r]) return fail(MI355_ERR_INVALID, "frame header: more escapes than entries");
+        if (h_counts[r] > frame_bytes) return fail(MI355_ERR_INVALID, "frame header: more entries than frame bytes");
+        span += cwire_record_bytes(h_counts[r], h_escapes[r]);
+        if (span > cwire_bytes) return fail(MI355_ERR_INVALID, "the records end past cwire_bytes");
+    }
+    if (int rc = check_regions({input_region(cwire, span)},
+                               {Region{piece_first, 4 * ((uint64_t)nrecords + 1), "piece_first"},
+                                Region{piece_pos, 8 * ((uint64_t)piece_capacity + 1), "piece_pos"}, Region{out, capacity_bytes, "out"}}))
+        return rc;
+    const uint8_t *p = (const uint8_t *)cwire;
+    uint8_t *dst = (uint8_t *)out;
+    const uint32_t M = (uint32_t)max_bytes;
+    std::vector<uint32_t> xs, rk;   // per entry: its index, and the 255 codes before it
+    uint64_t pos = 0, pieces = 0, at = 0;
+    piece_pos[0] = 0;
+    for (int r = 0; r < nrecords; r++) {
+        const uint32_t n = h_counts[r], e = h_escapes[r];
+        const CwireSections<const uint8_t> sec(p, pos, n, e);
+        piece_first[r] = (uint32_t)pieces;
+        xs.resize(n);
+        rk.resize((size_t)n + 1);
+        uint32_t X = 0, rank = 0;
+        for (uint32_t k = 0; k < n; k++) {
+            rk[k] = rank;
+            uint32_t g = sec.code[k];
+            bool bad = false;
+            if (g == 255) {
+                if (rank < e) memcpy(&g, sec.esc + 4 * (size_t)rank, 4);
+                else bad = true;
+                rank++;
+            }
+            if (!bad) X += g + 1u;
+            xs[k] = X - 1u;
+        }
+        rk[n] = rank;
+        for (uint32_t k0 = 0; k0 < n; k0 += kCwsBlock) {
+            const uint32_t B = n - k0 < kCwsBlock ? n : k0 + kCwsBlock;
+            for (uint32_t a = k0; a < B;) {
+                const uint32_t F = xs[a] >= 255u ? 1u : 0u;
+                uint32_t cost = 8 + 4 * F, b = a;
+                while (b < B) {   // four more entries, or the block's rest
+                    const uint32_t nb = B - b < 4 ? B : b + 4, from = b == a ? a + 1 : b;
+                    const uint32_t c = 8 + 4 * (rk[nb] - rk[from]);
+                    if (cost + c > M) break;
+                    cost += c;
+                    b = nb;
+                }
+                const uint32_t len = b - a, E = (cost - 8 - 2 * (uint32_t)cwire_pad4(len)) / 4;
+                if (pieces + 1 <= piece_capacity) piece_pos[pieces + 1] = at + cost;
+                if (pieces < piece_capacity && at + cost <= capacity_bytes) {
+                    uint8_t *q = dst + at;
+                    memset(q, 0, cost);
+                    memcpy(q, &len, 4);
+                    memcpy(q + 4, &E, 4);
+                    const CwireSections<uint8_t> o(dst, at, len, E);
+                    memcpy(o.code, sec.code + a, len);
+                    o.code[0] = (uint8_t)(xs[a] < 255u ? xs[a] : 255u);
+                    if (F) memcpy(o.esc, &xs[a], 4);
+                    for (uint32_t i = 0; i < E - F; i++) {
+                        const uint32_t rr = rk[a + 1] + i;
+                        if (rr < e) memcpy(o.esc + 4 * (size_t)(F + i), sec.esc + 4 * (size_t)rr, 4);
+                    }
+                    memcpy(o.diff, sec.diff + a, len);
+                }
+                pieces++;
+                at += cost;
+                a = b;
+            }
+        }
+        pos += cwire_record_bytes(n, e);
+    }
+    piece_first[nrecords] = (uint32_t)pieces;
+    return MI355_OK;
+}
+
+int mi355_cwire_split_cwire_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nrecords,
+                                  size_t max_bytes, void *d_piece_first, void *d_piece_pos, size_t piece_capacity, void *d_cwire_out,
+                                  size_t capacity_bytes) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nrecords < 0 || nrecords > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nrecords outside [0, max_batch]");
+    if (int rc = split_check_limit(max_bytes)) return rc;
+    if (((uintptr_t)d_cwire | (uintptr_t)d_cwire_out | (uintptr_t)d_piece_first) & 3u)
+        return fail(MI355_ERR_INVALID, "d_cwire, d_cwire_out and d_piece_first must be 4-byte aligned");
+    if ((uintptr_t)d_piece_pos & 7u) return fail(MI355_ERR_INVALID, "d_piece_pos must be 8-byte aligned");
+    if (nrecords == 0) return write_empty_heads(c, d_piece_first, d_piece_pos);
+    if (!d_cwire || !h_counts || !h_escapes) return fail(MI355_ERR_INVALID, "null stream pointer");
+    if (!d_piece_first || !d_piece_pos || !d_cwire_out) return fail(MI355_ERR_INVALID, "null output pointer");
+    CwaTable tab;
+    if (int rc = cwa_table(c, h_counts, h_escapes, nrecords, &tab)) return rc;
+    if (int rc = check_regions({input_region(d_cwire, tab.bytes)},
+                               {Region{d_piece_first, 4 * ((uint64_t)nrecords + 1), "d_piece_first"},
+                                Region{d_piece_pos, 8 * ((uint64_t)piece_capacity + 1), "d_piece_pos"},
+                                Region{d_cwire_out, capacity_bytes, "d_cwire_out"}}))
+        return rc;
+    if (int rc = use_device(c)) return rc;
+    const CwaArgs a = cwa_args(c, d_cwire);
+    const CwsOut o{(uint32_t *)d_piece_first, (uint64_t *)d_piece_pos, (uint64_t)piece_capacity, (uint8_t *)d_cwire_out,
+                   (uint64_t)capacity_bytes};
+    HIP_TRY(launch_cwire_split(a, tab.fr.data(), nrecords, (uint32_t)max_bytes, c->cws_blk, c->cws_base, o, c->stream));
     return MI355_OK;
 }
 

@@ -299,6 +299,27 @@ hipError_t launch_wall_compose(const uint8_t *states, size_t stride, uint32_t wi
 // |= the tiles that a record of stream s has an entry in; a.state / a.out / a.stride unused
 hipError_t launch_cwire_touched(const CwaArgs &a, const CwaFrame *records, int nstreams, int nframes, bool accumulate, uint32_t *mask,
                                 hipStream_t s);
+// mi355_cwire_split_cwire_batch: every record cut into pieces of at most max_bytes bytes (include/mi355diff.h, "the piece rule").
+// A block is kCwsBlock entries of one record, kCwsBlock / kCwaChunk chunks of the chunk table; a record of no entries has one
+// empty block, as it has one empty chunk.  blk / base: one word each per block of the call (scratch of the core, cws_blocks(N) per
+// record of max_batch): blk = {record, block of the record, pieces, bytes}, base = {pieces, bytes} of the blocks before it.
+constexpr uint32_t kCwsBlock = 65536;
+constexpr int kCwsTableRecords = 128;   // first blocks per k_cws_table launch (kernel arguments)
+struct CwsTableArgs {
+    int32_t first;
+    uint32_t bbase[kCwsTableRecords];
+};
+struct CwsOut {
+    uint32_t *piece_first;   // [nrecords + 1]
+    uint64_t *piece_pos;     // [piece_capacity + 1]
+    uint64_t piece_capacity;
+    uint8_t *cwire;
+    uint64_t capacity;       // bytes of cwire
+};
+uint32_t cws_blocks(uint32_t n);   // blocks of a record of n entries (1 for n = 0)
+// a.ftab and a.chunk are the scratch it shares with the other calls; a.dir / a.state / a.out / a.stride / a.ntiles unused
+hipError_t launch_cwire_split(const CwaArgs &a, const CwaFrame *records, int nrecords, uint32_t max_bytes, uint4 *blk, ulonglong2 *base,
+                              const CwsOut &o, hipStream_t s);
 
 // filters.hip -- every per-frame kernel takes a FrameBatch: frame f lives at base + f*stride
 struct FrameBatch {

@@ -23,6 +23,8 @@
 //                           peak cell per stream (mi355_cwire_activity_batch; mi355_activity_batch from the arrays).
 //   k_cwk_*               : one verdict of four words per compact record -- is it well-formed and canonical, and where not --
 //                           from the records alone, with sums that cannot wrap (mi355_cwire_check_batch).
+//   k_cws_*               : every compact record cut into pieces of at most a datagram's bytes, each a record of the same frame
+//                           (mi355_cwire_split_cwire_batch).
 //
 // The first two are index-driven byte scatter/copy: HBM-latency work with 5 bytes of traffic per entry, no
 // arithmetic worth naming.
@@ -2331,6 +2333,198 @@ __global__ __launch_bounds__(64) void k_cw_touched(const CwaArgs a, int nframes,
     }
 }
 
+// ---- mi355_cwire_split_cwire_batch: every record cut into pieces of at most max_bytes bytes (include/mi355diff.h) -----------------
+// The chunk table of the directory through its running sums (k_cwa_table, k_cwa_facts, k_cwa_scan 0, k_cwa_escsum, k_cwa_scan 1),
+// then, over the blocks of kCwsBlock entries of all records (a block is kCwsBlock / kCwaChunk chunks, so the escape rank and the
+// running index at its start are the words of its first chunk):
+//   k_cws_table (grid: records)  : blk[b] = {record, block of the record, 0, 0}; the records' first blocks are kernel arguments
+//   k_cws_count (grid: blocks)   : walks the block and leaves its pieces and their bytes in blk[b]
+//   k_cws_scan  (one workgroup)  : exclusive scan of both in 64 bits -> base[b]; piece_first[r] at a record's first block,
+//                                  piece_first[nrecords], piece_pos[0]
+//   k_cws_emit  (grid: blocks)   : the same walk; every piece it closes is written, with piece_pos[p + 1], if it fits
+// The walk (cws_walk): rounds of 4096 entries, a code dword per thread, the next round's dword loaded before this one is cut.  With r(d) the 255 codes of the block before dword d, a
+// piece from dword a to dword q costs 8 + V(q) - V(a) - 4*[code[4a] == 255] + 4*F(a) with V(d) = 8d + 4r(d): the cost needs no
+// scan of its own beside the escape rank and the running index of the decode step.  Wave 0 holds the open piece and finds the
+// round's cuts one after the other -- the first dword the open piece cannot take, by a ballot over 64 of the round's V in LDS at
+// a time -- and lists the pieces it closes; in the emit pass the sixteen waves then copy a listed piece each, whole dwords of the input's code and
+// diff sections (the first code byte and the pad bytes of a record's last dword rewritten), the piece's own first escape and the
+// input's escape words of its other 255 codes.  A cut needs two dwords before it (eight entries cost at most 56 bytes), so a round
+// closes at most 512 pieces and the block's last.  No workgroup waits on another; every loop is bounded by the block's own entries;
+// reads stay inside the record (code and diff dwords below pad4(n) / 4, escape words below e); a piece that does not fit is not
+// begun.
+constexpr int kCwsThreads = 1024, kCwsWaves = kCwsThreads / 64;   // a round: kCwsThreads dwords, one chunk of the table
+constexpr int kCwsList = kCwsThreads / 2 + 4;
+
+struct CwsPiece {
+    uint32_t d, len, x, rank;       // first dword (of the block), entries, x_a, the input's escape rank of its first inner 255 code
+    uint32_t F, bytes, off, idx;    // F(a), size, bytes and pieces of the block before it
+};
+
+__device__ __forceinline__ uint32_t cws_block_count(uint32_t n) { return n ? (n + kCwsBlock - 1) / kCwsBlock : 1u; }
+
+__global__ __launch_bounds__(64) void k_cws_table(const CwaArgs a, uint4 *blk, const CwsTableArgs h) {
+    const uint32_t rec = (uint32_t)h.first + blockIdx.x;
+    const uint32_t nb = cws_block_count(a.ftab[rec].n);
+    for (uint32_t j = threadIdx.x; j < nb; j += 64) blk[h.bbase[blockIdx.x] + j] = make_uint4(rec, j, 0u, 0u);
+}
+
+// One listed piece, by one wave; p0 / b0: pieces and bytes before the block
+__device__ __forceinline__ void cws_write_piece(const CwaArgs &a, const CwaFrame &f, uint32_t d0, const CwsPiece &pc, uint64_t p0,
+                                                uint64_t b0, const CwsOut &o, int lane) {
+    const uint64_t p = p0 + pc.idx, pos = b0 + pc.off, end = pos + pc.bytes;
+    if (lane == 0 && p + 1 <= o.piece_capacity) o.piece_pos[p + 1] = end;
+    if (p >= o.piece_capacity || end > o.capacity) return;
+    const CwireSections<const uint8_t> sec = cwa_sections(a, f);
+    const uint32_t *code = sec.code32() + d0 + pc.d, *dif = sec.diff32() + d0 + pc.d, *esc = sec.esc32();
+    const uint32_t ndw = cwire_dwords(pc.len), E = (pc.bytes - 8u - 8u * ndw) / 4u;
+    const uint32_t last = (pc.len & 3u) ? 0xFFFFFFFFu >> (32u - 8u * (pc.len & 3u)) : 0xFFFFFFFFu;   // the last dword's entries
+    uint32_t *out = (uint32_t *)(o.cwire + pos);
+    if (lane == 0) {
+        __builtin_nontemporal_store(pc.len, out);
+        __builtin_nontemporal_store(E, out + 1);
+    }
+    uint32_t *oc = out + 2, *oe = oc + ndw, *od = oe + E;
+    for (uint32_t i = lane; i < ndw; i += 64) {
+        uint32_t w = code[i], v = dif[i];
+        if (i == 0) w = (w & ~255u) | (pc.x < 255u ? pc.x : 255u);
+        if (i + 1 == ndw) {
+            w &= last;
+            v &= last;
+        }
+        __builtin_nontemporal_store(w, oc + i);
+        __builtin_nontemporal_store(v, od + i);
+    }
+    if (pc.F && lane == 0) __builtin_nontemporal_store(pc.x, oe);
+    for (uint32_t i = lane; i < E - pc.F; i += 64) {
+        const uint32_t r = pc.rank + i;
+        __builtin_nontemporal_store(r < f.e ? esc[r] : 0u, oe + pc.F + i);   // (an escape ranked at or past e has no word)
+    }
+}
+
+template <bool EMIT>
+__device__ __forceinline__ void cws_walk(const CwaArgs &a, uint4 *blk, const ulonglong2 *base, uint32_t M, const CwsOut &o) {
+    __shared__ uint32_t s_esc[2][kCwsWaves], s_sum[2][kCwsWaves];
+    __shared__ uint32_t s_v[kCwsThreads], s_vn[kCwsThreads], s_xa[kCwsThreads], s_fl[kCwsThreads];
+    __shared__ CwsPiece s_list[EMIT ? kCwsList : 1];
+    __shared__ uint32_t s_nlist;
+    const uint32_t b = blockIdx.x, tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const uint4 bw = blk[b];
+    const CwaFrame f = a.ftab[bw.x];
+    const uint32_t k0 = bw.y * kCwsBlock;
+    const uint32_t k1 = f.n - k0 < kCwsBlock ? f.n : k0 + kCwsBlock;
+    const uint4 ch = a.chunk[f.cbase + bw.y * (kCwsBlock / kCwaChunk)];
+    const CwireSections<const uint8_t> sec = cwa_sections(a, f);
+    const uint32_t *code = sec.code32(), *esc = sec.esc32();
+    const uint32_t d0 = k0 / 4, dend = k0 < k1 ? cwire_dwords(k1 - k0) : 0u;   // the block's dwords: d0 + [0, dend)
+    uint64_t p0 = 0, b0 = 0;
+    if (EMIT) {
+        const ulonglong2 bs = base[b];
+        p0 = bs.x;
+        b0 = bs.y;
+    }
+    uint32_t carry_e = ch.y, carry_x = ch.z;   // escape rank and running index before the round
+    // the open piece and the block's totals so far (wave 0, the same in every lane)
+    uint32_t o_d = 0, o_base = 0, o_x = 0, o_rank = 0, o_F = 0, pieces = 0, bytes = 0;
+    int buf = 0;
+    uint32_t ahead = tid < dend ? code[d0 + tid] : 0u;   // the next round's code dword: in flight while this round is cut
+    for (uint32_t r0 = 0; r0 < dend; r0 += kCwsThreads, buf ^= 1) {
+        const uint32_t dl = r0 + tid, d = d0 + dl;
+        const bool live = dl < dend;
+        const uint32_t word = ahead;
+        ahead = dl + kCwsThreads < dend ? code[d + kCwsThreads] : 0u;
+        bool in[4], fl[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) in[j] = live && 4 * d + j < k1;
+        uint32_t wtot;
+        const uint32_t before = cwire_escapes_before(word, in, fl, wtot);
+        const uint32_t rank = block_waves_before<kCwsWaves>(wtot, 0, s_esc[buf], carry_e) + before;
+        uint32_t inc[4], rk[4];
+        bool bad[4];
+        const uint32_t lsum = cwire_decode4(word, in, fl, rank, f.e, esc, inc, bad, rk);
+        const uint32_t x = block_exclusive_scan<kCwsWaves>(lsum, s_sum[buf], carry_x);
+        const uint32_t n255 = (uint32_t)fl[0] + fl[1] + fl[2] + fl[3];
+        const uint32_t v = 8u * dl + 4u * (rank - ch.y), xa = x + inc[0] - 1u;
+        s_v[tid] = v;
+        s_vn[tid] = live ? v + 8u + 4u * n255 : v;
+        s_xa[tid] = xa;
+        s_fl[tid] = (fl[0] ? 1u : 0u) | (xa >= 255u ? 2u : 0u);
+        __syncthreads();
+        if (wave == 0) {
+            const uint32_t nd = dend - r0 < (uint32_t)kCwsThreads ? dend - r0 : (uint32_t)kCwsThreads;
+            uint32_t nlist = 0, lo = 0;   // lo: the first dword of the round not yet known to fit the open piece
+            bool open = r0 != 0;          // (the block's first piece opens at its first dword)
+            for (;;) {
+                uint32_t q = open ? nd : 0u;   // the dword of the round the next piece opens at; nd: none
+                for (; open && lo < nd; lo += 64) {   // 64 dwords a step: the cost grows with the dword, the first over the limit cuts
+                    const uint32_t i = lo + lane;
+                    const uint64_t m = __ballot(i < nd && s_vn[i] - o_base > M);
+                    if (m) {
+                        q = lo + (uint32_t)__ffsll((unsigned long long)m) - 1u;
+                        break;
+                    }
+                }
+                const bool fin = q == nd && r0 + nd == dend;   // the block's last piece ends with the block
+                if (open && (q < nd || fin)) {                 // the open piece closes: dwords [o_d, r0 + q)
+                    const uint32_t size = (q < nd ? s_v[q] : s_vn[nd - 1]) - o_base;
+                    if (EMIT && lane == 0 && nlist < (uint32_t)kCwsList)
+                        s_list[nlist] = CwsPiece{o_d, (fin ? k1 - k0 : 4u * (r0 + q)) - 4u * o_d, o_x, o_rank, o_F, size, bytes, pieces};
+                    nlist++;
+                    pieces++;
+                    bytes += size;
+                }
+                if (q == nd) break;
+                const uint32_t fw = s_fl[q];
+                o_d = r0 + q;
+                o_F = fw >> 1;
+                o_x = s_xa[q];
+                o_base = s_v[q] + 4u * (fw & 1u) - 4u * o_F - 8u;
+                o_rank = ch.y + (s_v[q] - 8u * o_d) / 4u + (fw & 1u);
+                open = true;
+                lo = q + 1u;   // (its first dword always fits)
+            }
+            if (EMIT && lane == 0) s_nlist = nlist < (uint32_t)kCwsList ? nlist : (uint32_t)kCwsList;
+        }
+        if (EMIT) {
+            __syncthreads();
+            const uint32_t nlist = s_nlist;
+            for (uint32_t i = wave; i < nlist; i += kCwsWaves) cws_write_piece(a, f, d0, s_list[i], p0, b0, o, lane);
+        }
+    }
+    if (!EMIT && tid == 0) {
+        blk[b].z = pieces;
+        blk[b].w = bytes;
+    }
+}
+
+__global__ __launch_bounds__(kCwsThreads) void k_cws_count(const CwaArgs a, uint4 *blk, uint32_t M) {
+    cws_walk<false>(a, blk, nullptr, M, CwsOut{});
+}
+
+__global__ __launch_bounds__(kCwsThreads) void k_cws_emit(const CwaArgs a, uint4 *blk, const ulonglong2 *base, uint32_t M, const CwsOut o) {
+    cws_walk<true>(a, blk, base, M, o);
+}
+
+__global__ __launch_bounds__(256) void k_cws_scan(const uint4 *blk, ulonglong2 *base, uint32_t nblocks, int nrecords, const CwsOut o) {
+    __shared__ uint64_t s_p[2][4], s_b[2][4];
+    uint64_t pieces = 0, bytes = 0;
+    int buf = 0;
+    for (uint32_t i0 = 0; i0 < nblocks; i0 += 256, buf ^= 1) {
+        const uint32_t i = i0 + threadIdx.x;
+        const uint4 w = i < nblocks ? blk[i] : make_uint4(0u, 1u, 0u, 0u);
+        const uint64_t pb = block_exclusive_scan<4>((uint64_t)w.z, s_p[buf], pieces);
+        const uint64_t bb = block_exclusive_scan<4>((uint64_t)w.w, s_b[buf], bytes);
+        if (i < nblocks) {
+            base[i] = make_ulonglong2(pb, bb);
+            if (w.y == 0) o.piece_first[w.x] = (uint32_t)pb;
+        }
+    }
+    if (threadIdx.x == 0) {
+        o.piece_first[nrecords] = (uint32_t)pieces;
+        o.piece_pos[0] = 0;
+    }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 uint32_t cwa_chunks(uint32_t n) { return n ? (n + kCwaChunk - 1) / kCwaChunk : 1u; }
 uint32_t cwa_tiles(uint32_t nbytes) { return (nbytes + kCwaTile - 1) / kCwaTile; }
@@ -2357,6 +2551,34 @@ hipError_t launch_cwire_check(const CwaArgs &a, const CwaFrame *records, int nre
     hipLaunchKernelGGL(k_cwa_scan, dim3(nrecords), dim3(256), 0, s, a, 0);
     hipLaunchKernelGGL(k_cwk_escsum, dim3(nchunks), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_cwk_finish, dim3(nrecords), dim3(256), 0, s, a, verdicts);
+    return hipGetLastError();
+}
+
+uint32_t cws_blocks(uint32_t n) { return n ? (n + kCwsBlock - 1) / kCwsBlock : 1u; }
+
+// mi355_cwire_split_cwire_batch: the chunk table through its running sums, then the block table, count, scan and emit
+hipError_t launch_cwire_split(const CwaArgs &a, const CwaFrame *records, int nrecords, uint32_t max_bytes, uint4 *blk, ulonglong2 *base,
+                              const CwsOut &o, hipStream_t s) {
+    if (nrecords <= 0) return hipSuccess;
+    const uint32_t nchunks = launch_cwa_table(a, records, nrecords, s);
+    hipLaunchKernelGGL(k_cwa_facts, dim3(nchunks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_cwa_scan, dim3(nrecords), dim3(256), 0, s, a, 0);
+    hipLaunchKernelGGL(k_cwa_escsum, dim3(nchunks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_cwa_scan, dim3(nrecords), dim3(256), 0, s, a, 1);
+    CwsTableArgs h{};
+    uint32_t nblocks = 0;
+    for (int i0 = 0; i0 < nrecords; i0 += kCwsTableRecords) {
+        const int nr = nrecords - i0 < kCwsTableRecords ? nrecords - i0 : kCwsTableRecords;
+        h.first = i0;
+        for (int i = 0; i < nr; i++) {
+            h.bbase[i] = nblocks;
+            nblocks += cws_blocks(records[i0 + i].n);
+        }
+        hipLaunchKernelGGL(k_cws_table, dim3(nr), dim3(64), 0, s, a, blk, h);
+    }
+    hipLaunchKernelGGL(k_cws_count, dim3(nblocks), dim3(kCwsThreads), 0, s, a, blk, max_bytes);
+    hipLaunchKernelGGL(k_cws_scan, dim3(1), dim3(256), 0, s, blk, base, nblocks, nrecords, o);
+    hipLaunchKernelGGL(k_cws_emit, dim3(nblocks), dim3(kCwsThreads), 0, s, a, blk, base, max_bytes, o);
     return hipGetLastError();
 }
 

@@ -26,6 +26,7 @@ FLAG_OWN_QUEUES = 1   # MI355_FLAG_*
 PREPARE_BATCHES, PREPARE_GRAY_CHAIN, PREPARE_RED_CLEAR, PREPARE_CONV_KXK, PREPARE_EXEC, PREPARE_ALL = 1, 2, 4, 8, 16, 31   # MI355_PREPARE_*
 PREPARE_EXEC_CWIRE = 32   # (not part of PREPARE_ALL)
 CROP_KEEP_INDEX = 1   # MI355_CROP_*
+CWIRE_SPLIT_BLOCK = 65536   # MI355_CWIRE_SPLIT_BLOCK
 CWIRE_BAD_CODES, CWIRE_BAD_RANGE, CWIRE_BAD_PAD, CWIRE_BAD_ESCAPE, CWIRE_BAD_HEADER = 1, 2, 4, 8, 16   # MI355_CWIRE_BAD_*
 
 
@@ -132,6 +133,12 @@ SYMBOLS = {
                                          C.POINTER(C.c_size_t)]),
     "mi355_cwire_check_host": (C.c_int, [C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "mi355_cwire_check_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "mi355_cwire_split_host": (C.c_int, [C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t,
+                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "mi355_cwire_split_cwire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p,
+                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "mi355_cwire_split_pieces_max": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_size_t]),
+    "mi355_cwire_split_bytes_max": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_size_t]),
     "mi355_state_tiles": (C.c_size_t, [C.c_size_t]),
     "mi355_state_digest_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "mi355_state_digest_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),

@@ -96,7 +96,9 @@ typedef struct mi355_config {
  *      + mi355_wall_thumb_size, mi355_wall_compose_batch, mi355_cwire_touched_tiles_batch (additions only);
  *      + mi355_cwire_crop_batch, mi355_cwire_crop_cwire_batch, MI355_CROP_KEEP_INDEX (additions only);
  *      + mi355_cwire_mosaic_batch, mi355_cwire_mosaic_cwire_batch (additions only);
- *      + mi355_diff_consecutive_batch (additions only) */
+ *      + mi355_diff_consecutive_batch (additions only);
+ *      + mi355_cwire_split_host, mi355_cwire_split_cwire_batch, mi355_cwire_split_pieces_max, mi355_cwire_split_bytes_max,
+ *      MI355_CWIRE_SPLIT_BLOCK (additions only) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -666,6 +668,71 @@ int mi355_cwire_mosaic_cwire_batch(mi355_core *core, const void *d_cwire_in, con
                                    int nstreams, int nframes, const int32_t *h_place, int canvas_w, int canvas_h,
                                    void *d_offsets /* uint32[2] */, void *d_frame_pos /* uint64[2] */, void *d_cwire_out,
                                    size_t capacity_bytes);
+
+/* Records for a datagram socket: every compact record (back to back where h_counts[r] / h_escapes[r] put them, as in
+ * mi355_cwire_check_batch; the header words in the buffer are not trusted) cut into pieces of at most max_bytes bytes each.  A
+ * record is additive over ascending, disjoint indices, so any run of its entries is a record of the same frame: a piece IS a
+ * record, the receiver needs nothing new, pieces may be applied in any order and a lost piece costs its own entries only (which
+ * the resync calls -- mi355_state_digest_batch, mi355_refresh_cwire_batch, mi355_state_clear_tiles_batch -- then repair).
+ *   The piece rule (mi355_cwire_split_host is the definition; entry k of a record has index x_k by the decode rule of
+ *   mi355_cwire_check_*):  the entries are cut at every multiple of MI355_CWIRE_SPLIT_BLOCK and no piece crosses such a cut.  A
+ *   piece [a, b) costs bytes(a, b) = 8 + 2*pad4(b - a) + 4*(F(a) + #{k in (a, b): code[k] == 255}) with F(a) = 1 if x_a >= 255, else
+ *   0.  From a (always a multiple of 4) with B = min(n, the end of a's block) the piece ends at the largest b <= B with
+ *   bytes(a, b) <= max_bytes where b == B or (b - a) % 4 == 0; the next piece starts at b.  max_bytes is a multiple of 4 in
+ *   [64, 65536]: four escaped entries cost 32 bytes, so a piece always exists.  A record with n == 0 yields no piece.
+ *   Piece contents: header {b - a, its escapes}; code[a .. b) and diff[a .. b) copied, pad bytes zero; the first code is
+ *   min(x_a, 255); escape section: x_a first if F(a), then the input's escape values of the 255 codes in (a, b), in order.  Every
+ *   piece's code and diff sections are whole dwords of the input.
+ *   Laws: a piece of a canonical record is canonical (mi355_cwire_check_host gives word 0 == 0 against N); decoding a record's
+ *   pieces back to back gives the record's (xs, diff); applying any permutation of the pieces gives the state the record gives;
+ *   applying any subset changes exactly that subset's indices; a record that fits max_bytes comes back as one piece, byte for byte
+ *   the input when x_0 < 255 or code[0] was already 255 (both always hold for canonical input).
+ *   Outputs: piece_first, uint32[nrecords + 1], the exclusive scan of the pieces per record, always exact.  piece_pos,
+ *   uint64[piece_capacity + 1], the exclusive scan of the piece sizes: entries 0 .. min(total, piece_capacity) are written and
+ *   exact.  Piece p is written whole, at out + piece_pos[p], iff p < piece_capacity and piece_pos[p + 1] <= capacity_bytes; one
+ *   that does not fit is skipped whole and later ones that fit are still written.  Pieces lie in record order, then entry order.
+ *   Capacity helpers (host only, never below what the rule produces): mi355_cwire_split_pieces_max(n, e, M) = ceil(n / 65536) +
+ *   floor((2*pad4(n) + 4e) / (M - 35)).  Derivation: a piece that is not the last of its block could not take four more entries,
+ *   which cost at most 24 bytes, so it is larger than M - 24; of its bytes at most 8 (header) + 4 (its own first escape) are not
+ *   bytes of the input's sections, so it holds at least M - 35 of the record's 2*pad4(n) + 4e section bytes; and every block adds
+ *   one last piece.  mi355_cwire_split_bytes_max(n, e, M) = record bytes + 12 * pieces_max (a piece adds a header and at most one
+ *   escape word, and pads at most the record's own pad).  Both return 0 for a max_bytes outside [64, 65536].  Sum them over the
+ *   records of a call.
+ *   Malformed content under consistent headers: the family's guarantees -- nothing is read outside the input span, nothing is
+ *   written outside the outputs; piece sizes follow the codes and the wrapped running index (an escape ranked at or past e adds
+ *   nothing); the contents of that record's pieces are otherwise unspecified.
+ *   Refused with MI355_ERR_INVALID before anything is launched or written: whatever mi355_cwire_check_batch refuses; max_bytes
+ *   below 64, above 65536 or not a multiple of 4; with nrecords > 0 a null output pointer; d_cwire_out or d_piece_first not 4-byte
+ *   aligned; d_piece_pos not 8-byte aligned; the input span overlapping an output region.  nrecords == 0 writes piece_first[0] =
+ *   0 and piece_pos[0] = 0 and nothing else.
+ * Asynchronous on the core's stream, behind the last expansion of this core as every consumer of a packed stream is; with a
+ * caller's stream everything runs on it in call order.  Nothing is allocated inside the call (two words per block of 65536
+ * entries are made with the core and counted by mi355_workspace_bytes) and the core's state is neither read nor written.
+ * The chunk table of the GPU clients through its running sums, then a count pass over the blocks of all records (a workgroup
+ * walks its block four entries per lane, scans escape rank and running index, and finds each cut), one scan (piece_first, the
+ * pieces and bytes before each block in 64 bits, piece_pos[0]) and an emit pass that walks the blocks again and writes headers,
+ * codes, escapes, differences and zero pads with non-temporal stores, whole dwords copied.  No workgroup waits on another and
+ * no walk is longer than one block.
+ * Measured (profiles/multi_split.json: tools/bench_multi.py --legs split; 1080p, T = 1, median of five rounds, spread of the
+ * rounds 0.1 - 3.7 %, against mi355_cwire_coalesce_cwire_batch with T = 1 on the same records in the same run; the pieces equal
+ * the host form's at every point), us per input record at S = 4 / 16 / 64: webcam-like input (137 k entries per record, 201
+ * pieces at M = 1400, 32 at M = 8972) coalesce 15.99 / 8.20 / 6.30, split at 1400 51.99 / 13.22 / 3.44, at 8972 50.18 / 12.77 /
+ * 3.50; local input (a block moving over a still background, 4.8 k entries, 9 and 2 pieces) coalesce 16.64 / 5.41 / 2.41, split
+ * at 1400 10.20 / 2.71 / 0.73, at 8972 10.00 / 2.64 / 0.73.  The expectation -- no slower than that coalesce call by more than
+ * the rounds' spread -- is met on the local input at every S (0.30 - 0.61 of it) and for 64 webcam-like cameras (0.55) and MISSED
+ * for 4 and 16 webcam-like cameras (3.2 and 1.6 times its time): such a record is three blocks, four cameras are twelve
+ * workgroups that each walk sixteen rounds twice, and the call is bound by the latency of a round, not by bytes.  An earlier
+ * attempt at this call was not merged; this one fixes the piece rule so that blocks are independent.  The input is named
+ * d_cwire_in, as the mosaic call's is.  DESIGN.md section 4, "Splitting records into datagrams". */
+#define MI355_CWIRE_SPLIT_BLOCK 65536u
+int mi355_cwire_split_host(size_t frame_bytes, const void *cwire, size_t cwire_bytes, const uint32_t *h_counts,
+                           const uint32_t *h_escapes, int nrecords, size_t max_bytes, uint32_t *piece_first,
+                           uint64_t *piece_pos, size_t piece_capacity, void *out, size_t capacity_bytes);
+int mi355_cwire_split_cwire_batch(mi355_core *core, const void *d_cwire_in, const uint32_t *h_counts, const uint32_t *h_escapes,
+                                  int nrecords, size_t max_bytes, void *d_piece_first, void *d_piece_pos,
+                                  size_t piece_capacity, void *d_cwire_out, size_t capacity_bytes);
+size_t mi355_cwire_split_pieces_max(uint32_t n, uint32_t e, size_t max_bytes);
+size_t mi355_cwire_split_bytes_max(uint32_t n, uint32_t e, size_t max_bytes);
 
 /* A tick held to a budget: the sender's rate control.  The nstreams compact records mi355_diff_multi_cwire_batch just wrote
  * (back to back where h_counts[s] / h_escapes[s] put them; the headers come from the host and are not trusted in the buffer, as

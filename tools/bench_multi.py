@@ -70,6 +70,14 @@ the records of one tick (T = 1), in microseconds per stream, ONE JSON line for a
 The expectations to test: `crop_quarter` no slower than `coalesce` by more than the rounds' spread
 (`quarter_no_slower_than_coalesce`), and `crop_full` within the spread plus the one table launch (`full_minus_coalesce_us_per_call`).
 
+The split leg (--legs split, a run of its own: `--legs split --streams 4,16,64 > profiles/multi_split.json`) measures the call that
+cuts records into datagram-sized pieces on the records of one tick (T = 1), in microseconds per input record, ONE JSON line for all
+S, on the webcam-like and the local input:
+  coalesce       mi355_cwire_coalesce_cwire_batch with T = 1 on the same records (it gives them back): the family's nearest call;
+  split_1400     mi355_cwire_split_cwire_batch at max_bytes = 1400 (a UDP datagram inside an Ethernet frame);
+  split_8972     the same at max_bytes = 8972 (a jumbo frame).
+The expectation to test: either no slower than `coalesce` by more than the rounds' spread (`split_M_no_slower_than_coalesce`).
+
 The mosaic leg (--legs mosaic, a run of its own: `--legs mosaic --streams 4,16 > profiles/multi_mosaic.json`) measures the call that
 places S cameras side by side on one canvas (a C x C grid of whole frames, C = ceil(sqrt(S)): 2x2 into 3840x2160 and 4x4 into
 7680x4320 at 1080p), in microseconds per input record, ONE JSON line: T = 1 and T = 16, on the webcam-like and the local input:
@@ -1148,6 +1156,112 @@ def run_crop(W, H, S, rounds, kind):
     return out
 
 
+def run_split(W, H, S, rounds, kind, limits=(1400, 8972)):
+    """The split leg for one S and one input, T = 1 -> its dictionary.  coalesce: mi355_cwire_coalesce_cwire_batch on the records of
+    one tick (with T = 1 it gives the input back): the nearest call of the family that reads every record once and writes it once.
+    split_M: mi355_cwire_split_cwire_batch on the same records at max_bytes = M.  All on one core's own stream, alternating within
+    every round.  Before anything is timed the pieces are compared with mi355_cwire_split_host."""
+    import numpy as np
+    from cudavideostream_amd import CUDACore, cwire_bytes_max, cwire_split_bytes_max, cwire_split_host, cwire_split_pieces_max
+    dev = torch.device("cuda", 0)
+    n, T = 3 * W * H, 1
+    passes = 2 * max(1, 1024 // S)                     # ~2 k records per timed window
+    if kind == "webcam":                                # run_burst's input: one stream cut into S pieces
+        _, web = synth.webcam_stream(S + 1, W, H, device=dev)
+        web = web.reshape(S + 1, n)
+        states0, fwd = web[0:S].clone(), web[1:].reshape(S, T, n)
+    else:
+        states0, fwd = local_streams(S, T, W, H, dev)
+    per_call = min(S, max(1, ((1 << 32) - 1) // n))                  # streams per call: max_batch * N < 2^32
+    chunks = [(s0, min(per_call, S - s0)) for s0 in range(0, S, per_call)]
+    recs = []                                           # per chunk: (records, counts, escapes, bytes)
+    srv_states = states0.clone()
+    with CUDACore(W, H, max_batch=per_call) as server:
+        for s0, ns in chunks:
+            cwcap = cwire_bytes_max(n, ns)
+            d_off = torch.zeros(ns + 1, dtype=torch.int32, device=dev)
+            d_pos = torch.zeros(ns + 1, dtype=torch.int64, device=dev)
+            d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()
+            server.diff_multi_stream_cwire_batch(fwd[s0], srv_states[s0], ns, T, d_off, d_pos, d_cw, cwcap)
+            server.synchronize()
+            pos = d_pos.cpu().numpy().astype(np.int64)
+            counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
+            pad = (counts.astype(np.int64) + 3) & ~3
+            escapes = ((np.diff(pos) - 8 - 2 * pad) // 4).astype(np.uint32)
+            recs.append((d_cw[:int(pos[ns])].clone(), counts, escapes, int(pos[ns])))
+            del d_cw
+    ocap = cwire_bytes_max(n, per_call)
+    d_ooff = torch.zeros(per_call + 1, dtype=torch.int32, device=dev)
+    d_opos = torch.zeros(per_call + 1, dtype=torch.int64, device=dev)
+    d_out = torch.empty(ocap, dtype=torch.uint8, device=dev)
+    low = min(limits)
+    pcap = max(sum(cwire_split_pieces_max(c, e, low) for c, e in zip(r[1], r[2])) for r in recs)
+    bcap = max(sum(cwire_split_bytes_max(c, e, low) for c, e in zip(r[1], r[2])) for r in recs)
+    d_first = torch.zeros(per_call + 1, dtype=torch.int32, device=dev)
+    d_ppos = torch.zeros(pcap + 1, dtype=torch.int64, device=dev)
+    d_pieces = torch.empty(bcap, dtype=torch.uint8, device=dev)
+    relay = CUDACore(W, H, max_batch=per_call)
+    torch.cuda.synchronize()
+
+    def leg_coalesce():
+        for _ in range(passes):
+            for (s0, ns), r in zip(chunks, recs):
+                relay.cwire_coalesce_cwire_batch(r[0], r[1], r[2], ns, T, d_ooff, d_opos, d_out, ocap)
+        relay.synchronize()
+
+    def leg_split(M):
+        def leg():
+            for _ in range(passes):
+                for (s0, ns), r in zip(chunks, recs):
+                    relay.cwire_split_cwire_batch(r[0], r[1], r[2], ns, M, d_first, d_ppos, pcap, d_pieces, bcap)
+            relay.synchronize()
+        return leg
+
+    # the pieces are the host form's, at every limit
+    in_entries = sum(int(r[1].sum()) for r in recs)
+    in_bytes = sum(r[3] for r in recs)
+    out = {"input": kind, "streams": S, "frames": T, "passes": passes, "calls_per_tick": len(chunks),
+           "input_entries_per_stream": round(in_entries / S, 1), "input_bytes_per_stream": round(in_bytes / S, 1)}
+    for M in limits:
+        pieces = nbytes = 0
+        for (s0, ns), r in zip(chunks, recs):
+            relay.cwire_split_cwire_batch(r[0], r[1], r[2], ns, M, d_first, d_ppos, pcap, d_pieces, bcap)
+            relay.synchronize()
+            wf, wp, wo = cwire_split_host(r[0].cpu().numpy(), r[1], r[2], n, M, piece_capacity=pcap, capacity_bytes=bcap)
+            total = int(wf[-1])
+            assert np.array_equal(d_first[:ns + 1].cpu().numpy().view(np.uint32), wf)
+            assert np.array_equal(d_ppos[:total + 1].cpu().numpy().view(np.uint64), wp[:total + 1])
+            assert np.array_equal(d_pieces[:int(wp[total])].cpu().numpy(), wo[:int(wp[total])])
+            pieces += total
+            nbytes += int(wp[total])
+        out[f"pieces_per_stream_{M}"] = round(pieces / S, 1)
+        out[f"piece_bytes_per_stream_{M}"] = round(nbytes / S, 1)
+    table = {"coalesce": leg_coalesce}
+    table.update({f"split_{M}": leg_split(M) for M in limits})
+    times = {}
+    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
+        for name, leg in table.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            leg()
+            dt = time.perf_counter() - t0
+            if r:
+                times.setdefault(name, []).append(dt * 1e6 / (passes * S))
+    med, spread = {}, {}
+    for name in table:
+        st = stats(times[name])
+        st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
+        out[name + "_us_per_record"] = st
+        med[name], spread[name] = st["median"], st["max"] - st["min"]
+    for M in limits:
+        out[f"split_{M}_over_coalesce"] = round(med[f"split_{M}"] / med["coalesce"], 3)
+        # the expectation: no slower than the coalescer by more than the rounds' spread (of either leg)
+        out[f"split_{M}_no_slower_than_coalesce"] = bool(med[f"split_{M}"] <= med["coalesce"] + max(spread[f"split_{M}"], spread["coalesce"]))
+    relay.close()
+    return out
+
+
 def run_mosaic(W, H, S, T, rounds, kind):
     """The mosaic leg for one (S, T) and one input -> its dictionary.  mosaic: mi355_cwire_mosaic_cwire_batch on the burst's
     records, whole frames in a C x R grid.  state_route: mi355_apply_multi_stream_cwire_batch onto states the relay holds,
@@ -1328,7 +1442,7 @@ def main():
     ap.add_argument("--steps", type=int, default=8, help="K: webcam frames a stream walks through")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--legs", default="multi,cores_loop,pairs",
-                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or crop alone; or mosaic alone; or budget alone; or activity alone; or check alone; or refresh alone; or wall alone")
+                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or crop alone; or split alone; or mosaic alone; or budget alone; or activity alone; or check alone; or refresh alone; or wall alone")
     ap.add_argument("--frames", default="4,16,64", help="burst, burst_client and coalesce legs: T, frames per stream and call")
     a = ap.parse_args()
     have = load_library()
@@ -1377,6 +1491,18 @@ def main():
                 print(f"crop S={S} {kind}: done", file=sys.stderr, flush=True)
                 torch.cuda.empty_cache()
         print(json.dumps({"bench": "multi_crop", "size": f"{W}x{H}", "rounds": a.rounds, "crop": per}), flush=True)
+        return
+    if a.legs == "split":
+        per = []
+        for S in (int(v) for v in a.streams.split(",")):
+            for kind in ("webcam", "local"):
+                per.append(run_split(W, H, S, a.rounds, kind))
+                print(f"split S={S} {kind}: done", file=sys.stderr, flush=True)
+                torch.cuda.empty_cache()
+        ok = all(p[k] for p in per for k in p if k.endswith("_no_slower_than_coalesce"))
+        print(json.dumps({"bench": "multi_split", "size": f"{W}x{H}", "rounds": a.rounds, "split": per,
+                          "verdict": "no slower than coalesce at every point" if ok else "slower than coalesce at some point"}),
+              flush=True)
         return
     if a.legs == "mosaic":
         per = []

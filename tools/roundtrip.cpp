@@ -11,7 +11,7 @@
 // (ActivityCheck, RecordCheck, WallCheck), that is that mode.
 //
 //   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B]
-//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check] | --resync K [--burst B] | --crop X,Y,W,H [--burst K] | --mosaic CxR [--burst K]] [--wall K]]
+//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check] | --resync K [--burst B] | --crop X,Y,W,H [--burst K] | --mosaic CxR [--burst K] | [--burst K --coalesce] --datagram BYTES] [--wall K]]
 //   exit status 0 = all checks passed
 #include <algorithm>
 #include <cstdint>
@@ -864,6 +864,138 @@ static int run_multi_burst_coalesce(int w, int h, int T, int S, int K) {
     return 0;
 }
 
+// --compact --multi S [--burst K --coalesce] --datagram BYTES: a relay in front of a datagram socket (UDP, RTP, QUIC datagrams,
+// multicast).  It holds no frame: it uploads every camera's records as they came off its socket -- one tick, or with --burst K
+// --coalesce a burst that it first coalesces into one record per camera -- and cuts them into pieces of at most BYTES bytes with
+// ONE mi355_cwire_split_cwire_batch.  Every piece is one datagram (one write, one read).  The receiver needs nothing new: pieces
+// are records.  It stages each camera's pieces in a shuffled order (the tool's seeded generator), padded with n = 0 records to a
+// common count, and applies them with mi355_apply_multi_stream_cwire_batch, kDatagramRound pieces of every camera per call.
+// After every tick each camera's state at the receiver must equal the frame of a host client (mi355_cwire_apply_host) that applied
+// the original records, and the sender's state.  The line also says how many pieces and bytes a tick made.
+static const int kDatagramRound = 64;
+
+static int run_multi_datagram(int w, int h, int T, int S, int K, long max_bytes) {
+    const bool coalesce = K > 0;
+    if (!coalesce) K = 1;
+    Session ss(w, h);
+    const size_t n = ss.n, M = (size_t)max_bytes;
+    Cameras cams(S, w, h);
+    Sender tx;
+    Receiver relay, rcv;
+    if (tx.open(ss, S, K) || relay.open(ss, S, S * K, S * K, false) || rcv.open(ss, S, S * kDatagramRound, S)) return 1;
+    // what any S records of the frame can need: at most n entries, at most n escapes each
+    const size_t pcap = (size_t)S * mi355_cwire_split_pieces_max((uint32_t)n, (uint32_t)n, M);
+    const size_t bcap = (size_t)S * mi355_cwire_split_bytes_max((uint32_t)n, (uint32_t)n, M);
+    const size_t stage_cap = bcap + 8 * (size_t)S * kDatagramRound;
+    void *d_roff = ss.dev(relay.core, sizeof(uint32_t) * (S + 1)), *d_rpos = ss.dev(relay.core, sizeof(uint64_t) * (S + 1));
+    void *d_fwd = ss.dev(relay.core, rcv.cap);
+    void *d_first = ss.dev(relay.core, sizeof(uint32_t) * (S + 1)), *d_ppos = ss.dev(relay.core, sizeof(uint64_t) * (pcap + 1));
+    void *d_pieces = ss.dev(relay.core, bcap), *d_stage = ss.dev(rcv.core, stage_cap);
+    if (!ss.ok()) return 1;
+    std::vector<uint8_t> host_frames((size_t)S * n), pieces(bcap), arrived(bcap), stage(stage_cap);
+    std::vector<uint32_t> roff(S + 1), first(S + 1), cnt(S), esc(S), pc((size_t)S * kDatagramRound), pe((size_t)S * kDatagramRound);
+    std::vector<uint64_t> rpos(S + 1), ppos(pcap + 1);
+    std::vector<std::vector<uint32_t>> order(S);
+    if (cams.start(ss, tx, rcv, host_frames.data())) return 1;
+    size_t received = 0, datagrams = 0, datagram_bytes = 0, largest = 0;
+    int max_err = 0, calls = 0, steps = 0;
+    for (int t0 = 0; t0 < T; t0 += K, steps++) {
+        const int nb = T - t0 < K ? T - t0 : K;
+        cams.fill(tx.frames.data(), t0, nb);
+        // ---- server: one tick -> S records, or nb ticks -> S * nb records, in one call
+        if (tx.step(nb, coalesce)) return 1;
+        // ---- the sockets into the relay; a host client beside it applies every original record
+        if (slices_to_node(ss, tx, relay, nb, host_frames.data(), nullptr)) return 1;
+        received += tx.cb;
+        // ---- relay: (the burst -> one record per camera, then) the S records -> pieces, in one call; no frame exists here
+        const void *d_rec = relay.d_rx;
+        if (coalesce) {
+            OK(mi355_cwire_coalesce_cwire_batch(relay.core, relay.d_rx, relay.counts.data(), relay.escapes.data(), S, nb, d_roff, d_rpos,
+                                                d_fwd, rcv.cap));
+            OK(mi355_download(relay.core, roff.data(), d_roff, sizeof(uint32_t) * (S + 1)));
+            OK(mi355_download(relay.core, rpos.data(), d_rpos, sizeof(uint64_t) * (S + 1)));
+            if (rpos[S] > rcv.cap) { fprintf(stderr, "coalesced stream larger than its bound\n"); return 1; }
+            for (int s = 0; s < S; s++) {
+                cnt[s] = roff[s + 1] - roff[s];
+                esc[s] = (uint32_t)((rpos[s + 1] - rpos[s] - mi355_cwire_frame_bytes(cnt[s], 0)) / 4);
+            }
+            d_rec = d_fwd;
+        } else {
+            for (int s = 0; s < S; s++) {
+                cnt[s] = relay.counts[s];
+                esc[s] = relay.escapes[s];
+            }
+        }
+        OK(mi355_cwire_split_cwire_batch(relay.core, d_rec, cnt.data(), esc.data(), S, M, d_first, d_ppos, pcap, d_pieces, bcap));
+        calls++;
+        OK(mi355_download(relay.core, first.data(), d_first, sizeof(uint32_t) * (S + 1)));
+        const size_t np = first[S];
+        if (np > pcap) { fprintf(stderr, "more pieces than their bound\n"); return 1; }
+        OK(mi355_download(relay.core, ppos.data(), d_ppos, sizeof(uint64_t) * (np + 1)));
+        if (ppos[np] > bcap) { fprintf(stderr, "pieces larger than their bound\n"); return 1; }
+        OK(mi355_download(relay.core, pieces.data(), d_pieces, (size_t)ppos[np]));
+        // ---- the datagram socket: a piece is one write and one read
+        for (size_t p = 0; p < np; p++) {
+            const size_t len = (size_t)(ppos[p + 1] - ppos[p]);
+            if (len > M) { fprintf(stderr, "tick %d: piece %zu has %zu bytes > %zu\n", t0, p, len, M); return 1; }
+            if (!ss.send(pieces.data() + ppos[p], arrived.data() + ppos[p], len)) return 1;
+            largest = std::max(largest, len);
+        }
+        datagrams += np;
+        datagram_bytes += (size_t)ppos[np];
+        // ---- receiver: every camera's pieces in an order of their own, kDatagramRound of each per call, empty records behind them
+        size_t most = 0;
+        for (int s = 0; s < S; s++) {
+            order[s].clear();
+            for (uint32_t p = first[s]; p < first[s + 1]; p++) order[s].push_back(p);
+            for (size_t i = order[s].size(); i > 1; i--) std::swap(order[s][i - 1], order[s][rnd() % i]);
+            most = std::max(most, order[s].size());
+        }
+        for (size_t r0 = 0; r0 < most; r0 += kDatagramRound) {
+            const int nr = (int)std::min(most - r0, (size_t)kDatagramRound);
+            size_t q = 0;
+            for (int s = 0; s < S; s++)
+                for (int j = 0; j < nr; j++) {
+                    const size_t b = (size_t)s * nr + j;
+                    if (r0 + j < order[s].size()) {
+                        const uint32_t p = order[s][r0 + j];
+                        const size_t len = (size_t)(ppos[p + 1] - ppos[p]);
+                        memcpy(stage.data() + q, arrived.data() + ppos[p], len);
+                        memcpy(&pc[b], stage.data() + q, 4);
+                        memcpy(&pe[b], stage.data() + q + 4, 4);
+                        if (mi355_cwire_frame_bytes(pc[b], pe[b]) != len) { fprintf(stderr, "stream framing broken\n"); return 1; }
+                        q += len;
+                    } else {
+                        memset(stage.data() + q, 0, 8);
+                        pc[b] = pe[b] = 0;
+                        q += 8;
+                    }
+                }
+            OK(mi355_upload(rcv.core, d_stage, stage.data(), q));
+            OK(mi355_apply_multi_stream_cwire_batch(rcv.core, d_stage, pc.data(), pe.data(), S, nr, rcv.d_states, n, nullptr, 0));
+        }
+        if (rcv.get_states()) return 1;
+        // ---- checks
+        for (int s = 0; s < S; s++)
+            if (memcmp(&host_frames[(size_t)s * n], &rcv.states[(size_t)s * n], n) != 0) {
+                fprintf(stderr, "tick %d: camera %d: receiver state != host client that applied the %d original records\n", t0, s, nb);
+                return 1;
+            }
+        if (states_equal(tx, rcv, t0)) return 1;
+        for (int s = 0; s < S; s++)
+            max_err = std::max(max_err, max_abs_error(&rcv.states[(size_t)s * n], &tx.frames[((size_t)s * nb + nb - 1) * n], n));
+    }
+    if (!datagrams) { fprintf(stderr, "--datagram: no piece was made\n"); return 1; }
+    if (within_threshold(max_err, ss) || ss.close()) return 1;
+    printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"burst\": %d, \"coalesce\": %s, \"datagram\": %zu, "
+           "\"relay_calls\": %d, \"width\": %d, \"height\": %d, \"ticks\": %d, \"changed_bytes\": %zu, \"relay_received_bytes\": %zu, "
+           "\"pieces\": %zu, \"piece_bytes\": %zu, \"pieces_per_tick\": %.2f, \"piece_bytes_per_tick\": %.1f, \"largest_piece\": %zu, "
+           "\"raw_bytes\": %zu, \"max_abs_error\": %d}\n",
+           S, coalesce ? K : 0, coalesce ? "true" : "false", M, calls, w, h, T, tx.changed, received, datagrams, datagram_bytes,
+           (double)datagrams / steps, (double)datagram_bytes / steps, largest, (size_t)T * S * n, max_err);
+    return 0;
+}
+
 // --compact --multi S --crop X,Y,W,H [--burst K]: a relay for viewers that zoomed into their cameras.  It holds no frame: it
 // uploads every camera's records as they came off its socket (one tick, or a burst of K), cuts them to the rectangle with ONE
 // mi355_cwire_crop_cwire_batch -- of a burst, the crop of the coalesced burst -- and forwards those S records, indexed in the
@@ -1473,7 +1605,7 @@ static int usage(const char *text) {
 }
 
 int main(int argc, char **argv) {
-    long w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0, activity = -1, resync = -1, wall = 0, budget = -1;
+    long w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0, activity = -1, resync = -1, wall = 0, budget = -1, datagram = -1;
     bool compact = false, direct = false, gpu_client = false, burst_client = false, coalesce = false, per_frame = false, check = false;
     const struct { const char *name; bool *on; } flags[] = {
         {"--compact", &compact}, {"--direct", &direct}, {"--gpu-client", &gpu_client}, {"--burst-client", &burst_client},
@@ -1482,7 +1614,7 @@ int main(int argc, char **argv) {
     const struct { const char *name; long *value, least, below; } valued[] = {   // a value below `least` is taken as `below`
         {"--width", &w, any, 0}, {"--height", &h, any, 0}, {"--frames", &T, any, 0}, {"--batch", &B, any, 0}, {"--multi", &multi, any, 0},
         {"--burst", &burst, any, 0}, {"--activity", &activity, 0, 0}, {"--resync", &resync, 0, 0}, {"--wall", &wall, 1, -1},
-        {"--budget", &budget, 0, 0}};
+        {"--budget", &budget, 0, 0}, {"--datagram", &datagram, 0, 0}};
     int32_t crop[4] = {0, 0, 0, 0};
     bool cropped = false, crop_ok = true;
     int grid[2] = {0, 0};
@@ -1537,6 +1669,13 @@ int main(int argc, char **argv) {
             3.0 * w * h * grid[0] * grid[1] >= 2147483648.0)
             return usage("--mosaic CxR needs C, R >= 1, S <= C*R <= 4096 cells and a canvas below 2^31 bytes");
     }
+    if (datagram >= 0) {
+        if (!compact || !multi || cropped || mosaic || budget >= 0 || per_frame || burst_client || activity || check || resync >= 0 || wall ||
+            (burst && !coalesce))
+            return usage("--datagram BYTES needs --compact --multi S, alone or behind --burst K --coalesce");
+        if (datagram < 64 || datagram > (long)MI355_CWIRE_SPLIT_BLOCK || datagram % 4)
+            return usage("--datagram BYTES needs a multiple of 4 in [64, 65536]");
+    }
     if (per_frame) {
         if (!compact || direct || gpu_client || multi) return usage("--per-frame needs --compact alone");
         return run_per_frame(w, h, T);
@@ -1546,6 +1685,7 @@ int main(int argc, char **argv) {
     if (resync >= 0) return run_multi_resync(w, h, T, multi, resync, burst, wall);
     if (cropped) return run_multi_crop(w, h, T, multi, burst, crop);
     if (mosaic) return run_multi_mosaic(w, h, T, multi, burst, grid[0], grid[1]);
+    if (datagram >= 0) return run_multi_datagram(w, h, T, multi, coalesce ? burst : 0, datagram);
     if (coalesce) return run_multi_burst_coalesce(w, h, T, multi, burst);
     if (budget >= 0) return run_multi_budget(w, h, T, multi, budget);
     if (burst && !burst_client) return run_multi_burst(w, h, T, multi, burst);
