@@ -27,6 +27,22 @@ def _ptr(x):
     return x.data_ptr()
 
 
+def _headers(counts, escapes, n):
+    """The headers (n, e) of n records as a client read them: two contiguous uint32 arrays of at least n elements.  The caller
+    keeps them referenced until the C call has returned."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+    assert counts.size >= n and escapes.size >= n
+    return counts, escapes
+
+
+def _table(x, per, n, dtype):
+    """A host table of `per` members for each of n streams (rectangles, placements, budgets), contiguous."""
+    x = np.ascontiguousarray(x, dtype=dtype)
+    assert x.size >= per * n
+    return x
+
+
 class PinnedArray:
     """numpy view over hipHostMalloc'ed memory (CUDACore::alloc_arrays, kernels.cu:531-536)."""
 
@@ -368,9 +384,7 @@ class CUDACore:
         escapes) put them; only the tiles of a state that its record touches are read and written."""
         self._hold(d_cwire, d_states)
         stride = self.total if stride is None else stride
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
-        assert counts.size >= nstreams and escapes.size >= nstreams
+        counts, escapes = _headers(counts, escapes, nstreams)
         _l.check(self._lib.mi355_apply_multi_cwire_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
                                                          int(nstreams), _ptr(d_states), int(stride)))
 
@@ -406,9 +420,7 @@ class CUDACore:
         self._hold(d_cwire, d_states, d_frames_out)
         stride = self.total if stride is None else stride
         out_stride = self.total if out_stride is None else out_stride
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
-        assert counts.size >= nstreams * nframes and escapes.size >= nstreams * nframes
+        counts, escapes = _headers(counts, escapes, nstreams * nframes)
         _l.check(self._lib.mi355_apply_multi_stream_cwire_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
                                                                 int(nstreams), int(nframes), _ptr(d_states), int(stride),
                                                                 _ptr(d_frames_out), int(out_stride)))
@@ -419,9 +431,7 @@ class CUDACore:
         of (d_offsets, d_xs, d_diff): the sums (mod 256) of the stream's differences per byte index that are not 0, ascending.
         Applying segment s equals applying the stream's records in order."""
         self._hold(d_cwire, d_offsets, d_xs, d_diff)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
-        assert counts.size >= nstreams * nframes and escapes.size >= nstreams * nframes
+        counts, escapes = _headers(counts, escapes, nstreams * nframes)
         _l.check(self._lib.mi355_cwire_coalesce_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
                                                       int(nstreams), int(nframes), _ptr(d_offsets), _ptr(d_xs), _ptr(d_diff),
                                                       int(capacity)))
@@ -431,9 +441,7 @@ class CUDACore:
         """cwire_coalesce_batch into compact records: stream s's ONE record at d_frame_pos[s] (uint64[nstreams + 1]), the
         canonical encoding of its segment."""
         self._hold(d_cwire, d_offsets, d_frame_pos, d_cwire_out)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
-        assert counts.size >= nstreams * nframes and escapes.size >= nstreams * nframes
+        counts, escapes = _headers(counts, escapes, nstreams * nframes)
         _l.check(self._lib.mi355_cwire_coalesce_cwire_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
                                                             int(nstreams), int(nframes), _ptr(d_offsets), _ptr(d_frame_pos),
                                                             _ptr(d_cwire_out), int(capacity_bytes)))
@@ -444,10 +452,8 @@ class CUDACore:
         of the rectangle's own w x h frame (flags = lib.CROP_KEEP_INDEX: with the full frame's index).  Applying segment s to
         the crop of a state equals the crop of applying the stream's records to the state."""
         self._hold(d_cwire, d_offsets, d_xs, d_diff)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
-        rects = np.ascontiguousarray(rects, dtype=np.int32)
-        assert counts.size >= nstreams * nframes and escapes.size >= nstreams * nframes and rects.size >= 4 * nstreams
+        counts, escapes = _headers(counts, escapes, nstreams * nframes)
+        rects = _table(rects, 4, nstreams, np.int32)
         _l.check(self._lib.mi355_cwire_crop_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data, int(nstreams),
                                                   int(nframes), rects.ctypes.data, int(flags), _ptr(d_offsets), _ptr(d_xs),
                                                   _ptr(d_diff), int(capacity)))
@@ -457,10 +463,8 @@ class CUDACore:
         """cwire_crop_batch into compact records: stream s's ONE record at d_frame_pos[s] (uint64[nstreams + 1]), the
         canonical encoding of its segment."""
         self._hold(d_cwire, d_offsets, d_frame_pos, d_cwire_out)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
-        rects = np.ascontiguousarray(rects, dtype=np.int32)
-        assert counts.size >= nstreams * nframes and escapes.size >= nstreams * nframes and rects.size >= 4 * nstreams
+        counts, escapes = _headers(counts, escapes, nstreams * nframes)
+        rects = _table(rects, 4, nstreams, np.int32)
         _l.check(self._lib.mi355_cwire_crop_cwire_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
                                                         int(nstreams), int(nframes), rects.ctypes.data, int(flags),
                                                         _ptr(d_offsets), _ptr(d_frame_pos), _ptr(d_cwire_out),
@@ -473,10 +477,8 @@ class CUDACore:
         h, dx, dy) in pixels puts that rectangle of camera s at (dx, dy); overlapping destinations add.  d_offsets: uint32[2].
         Applying the segment to a canvas state equals placing what the streams' records make of the cameras' states."""
         self._hold(d_cwire, d_offsets, d_xs, d_diff)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
-        place = np.ascontiguousarray(place, dtype=np.int32)
-        assert counts.size >= nstreams * nframes and escapes.size >= nstreams * nframes and place.size >= 6 * nstreams
+        counts, escapes = _headers(counts, escapes, nstreams * nframes)
+        place = _table(place, 6, nstreams, np.int32)
         _l.check(self._lib.mi355_cwire_mosaic_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data, int(nstreams),
                                                     int(nframes), place.ctypes.data, int(canvas_w), int(canvas_h), _ptr(d_offsets),
                                                     _ptr(d_xs), _ptr(d_diff), int(capacity)))
@@ -486,10 +488,8 @@ class CUDACore:
         """cwire_mosaic_batch into ONE compact record at d_cwire_out, the canonical encoding of the segment; d_frame_pos
         (uint64[2]) = {0, record bytes}."""
         self._hold(d_cwire, d_offsets, d_frame_pos, d_cwire_out)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
-        place = np.ascontiguousarray(place, dtype=np.int32)
-        assert counts.size >= nstreams * nframes and escapes.size >= nstreams * nframes and place.size >= 6 * nstreams
+        counts, escapes = _headers(counts, escapes, nstreams * nframes)
+        place = _table(place, 6, nstreams, np.int32)
         _l.check(self._lib.mi355_cwire_mosaic_cwire_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
                                                           int(nstreams), int(nframes), place.ctypes.data, int(canvas_w),
                                                           int(canvas_h), _ptr(d_offsets), _ptr(d_frame_pos), _ptr(d_cwire_out),
@@ -504,10 +504,8 @@ class CUDACore:
         previous value at every dropped entry: records and states are those of a tick diffed at T_s."""
         self._hold(d_cwire, d_states, d_thresholds, d_offsets, d_frame_pos, d_cwire_out)
         stride = self.total if stride is None else stride
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
-        budgets = np.ascontiguousarray(budgets, dtype=np.uint32)
-        assert counts.size >= nstreams and escapes.size >= nstreams and budgets.size >= nstreams
+        counts, escapes = _headers(counts, escapes, nstreams)
+        budgets = _table(budgets, 1, nstreams, np.uint32)
         _l.check(self._lib.mi355_cwire_budget_cwire_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
                                                           _ptr(d_states), int(stride), int(nstreams), budgets.ctypes.data,
                                                           _ptr(d_thresholds), _ptr(d_offsets), _ptr(d_frame_pos),
@@ -529,9 +527,7 @@ class CUDACore:
                              min_count=1, accumulate=False):
         """activity_batch straight from compact records (headers counts / escapes, s * nframes + t order)."""
         self._hold(d_cwire, d_cells, d_summary)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
-        assert counts.size >= nstreams * nframes and escapes.size >= nstreams * nframes
+        counts, escapes = _headers(counts, escapes, nstreams * nframes)
         _l.check(self._lib.mi355_cwire_activity_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
                                                       int(nstreams), int(nframes), int(cell_w), int(cell_h), int(min_count),
                                                       int(bool(accumulate)), _ptr(d_cells), _ptr(d_summary)))
@@ -542,9 +538,7 @@ class CUDACore:
         {lib.CWIRE_BAD_* flags (0: well-formed and canonical), 255 codes, first entry at or past the frame's end (n: none),
         1 + the last decoded index, saturated}.  No state is read or written; cwire_check_host is the same on the host."""
         self._hold(d_cwire, d_verdicts)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
-        assert counts.size >= nrecords and escapes.size >= nrecords
+        counts, escapes = _headers(counts, escapes, nrecords)
         _l.check(self._lib.mi355_cwire_check_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
                                                    int(nrecords), _ptr(d_verdicts)))
 
@@ -556,9 +550,7 @@ class CUDACore:
         record r's pieces are d_piece_first[r] .. d_piece_first[r + 1] (uint32[nrecords + 1]).  cwire_split_host is the same on
         the host and the definition; cwire_split_pieces_max / cwire_split_bytes_max give sufficient capacities."""
         self._hold(d_cwire, d_piece_first, d_piece_pos, d_cwire_out)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
-        assert counts.size >= nrecords and escapes.size >= nrecords
+        counts, escapes = _headers(counts, escapes, nrecords)
         _l.check(self._lib.mi355_cwire_split_cwire_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
                                                          int(nrecords), int(max_bytes), _ptr(d_piece_first), _ptr(d_piece_pos),
                                                          int(piece_capacity), _ptr(d_cwire_out), int(capacity_bytes)))
@@ -600,8 +592,7 @@ class CUDACore:
         self._hold(d_states, d_tile_mask, d_wall)
         stride = self.total if stride is None else stride
         wall_pitch = 3 * int(wall_w) if wall_pitch is None else wall_pitch
-        place = np.ascontiguousarray(place, dtype=np.int32)
-        assert place.size >= 3 * nstreams
+        place = _table(place, 3, nstreams, np.int32)
         _l.check(self._lib.mi355_wall_compose_batch(self._h, _ptr(d_states), int(stride), int(nstreams), place.ctypes.data,
                                                     _ptr(d_tile_mask), _ptr(d_wall), int(wall_w), int(wall_h), int(wall_pitch)))
 
@@ -610,9 +601,7 @@ class CUDACore:
         an entry in, as the tile mask of refresh_cwire_batch: uint32[nstreams][ceil(tiles / 32)], overwritten or, with
         accumulate, ORed onto."""
         self._hold(d_cwire, d_tile_mask)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
-        assert counts.size >= nstreams * nframes and escapes.size >= nstreams * nframes
+        counts, escapes = _headers(counts, escapes, nstreams * nframes)
         _l.check(self._lib.mi355_cwire_touched_tiles_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
                                                            int(nstreams), int(nframes), int(bool(accumulate)), _ptr(d_tile_mask)))
 
@@ -657,9 +646,7 @@ class CUDACore:
     def cwire_decode_batch(self, d_cwire, counts, escapes, nframes, d_offsets, d_xs, d_diff, capacity):
         """Compact records -> packed stream; counts / escapes: the frames' headers (n, e) as the client read them."""
         self._hold(d_cwire, d_offsets, d_xs, d_diff)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
-        assert counts.size >= nframes and escapes.size >= nframes
+        counts, escapes = _headers(counts, escapes, nframes)
         _l.check(self._lib.mi355_cwire_decode_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
                                                     int(nframes), _ptr(d_offsets), _ptr(d_xs), _ptr(d_diff), int(capacity)))
 
@@ -668,9 +655,7 @@ class CUDACore:
         frames' headers (n, e) as the client read them.  d_frames_out: frame t is also written at t * stride."""
         self._hold(d_cwire, d_frames_out)
         stride = self.total if stride is None else stride
-        counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
-        assert counts.size >= nframes and escapes.size >= nframes
+        counts, escapes = _headers(counts, escapes, nframes)
         _l.check(self._lib.mi355_apply_cwire_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
                                                    int(nframes), _ptr(d_frames_out), int(stride)))
 

@@ -370,22 +370,35 @@ struct CwireOut {
     uint64_t capacity;   // bytes
 };
 
-// d_wire != nullptr: the expander writes the sender's byte stream (capacity in bytes) instead of d_xs/d_diff.
-// cw != nullptr: the log is expanded into compact records (launch_expand_cwire) instead.
-// feedback (pair mode): d_prev are the caller's states, one per batch index, and take the fed-back state of their frame
-// (mi355_diff_multi_*); the operands do not overlap (the entry points refuse that).
-// seg > 0 (stream mode, feedback): nframes / seg streams of seg frames each, batch index s * seg + t; d_prev are the caller's
-// states, one per STREAM (mi355_diff_multi_stream_*).  A tile of a state is read and written by the launches of one stream only,
-// exactly as with feedback pairs (the cut depends on the frame size alone), so the two forms share the fb_states bookkeeping
-// and may alternate on the same states.
-// consecutive (stream mode, no feedback): d_prev is ONE frame, the predecessor of frame 0; frame t is compared with frame t - 1
-// (mi355_diff_consecutive_batch).  The core's state takes no part.  d_prev may be the core's state or a caller's states: like a
-// pair batch's operand it is read tile by tile by the launch that packs the tile, on the stream that wrote that tile.
-// pipelined: a public batch entry point on the core's OWN stream -- the index and the expansion run on the side
-// stream beside the next batch's pack kernel (which needs only the state, carried on the core's stream, and a free
-// set of logs); completion is what mi355_synchronize / any other entry point waits for (use_device joins).  With a
-// caller's stream (mi355_set_stream) everything stays on that stream, in order: a caller who enqueues its own
-// consumers there must find the batch complete.
+// What a batch asks of run_batch beyond its operands; the defaults are mi355_exec's: one stream against the core's state, the
+// arrays out, everything on the core's stream.
+struct BatchMode {
+    // d_cur[i] against d_prev[i] (mi355_diff_pairs_batch); otherwise stream mode: frame 0 against the core's state, which takes
+    // the last frame, and frame t against frame t - 1
+    bool pair = false;
+    // (pair mode) d_prev are the caller's states, one per batch index, and take the fed-back state of their frame
+    // (mi355_diff_multi_*); the operands do not overlap (the entry points refuse that).
+    bool feedback = false;
+    // > 0 (stream mode, feedback): nframes / seg streams of seg frames each, batch index s * seg + t; d_prev are the caller's
+    // states, one per STREAM (mi355_diff_multi_stream_*).  A tile of a state is read and written by the launches of one stream
+    // only, exactly as with feedback pairs (the cut depends on the frame size alone), so the two forms share the fb_states
+    // bookkeeping and may alternate on the same states.
+    int seg = 0;
+    // (stream mode, no feedback) d_prev is ONE frame, the predecessor of frame 0; frame t is compared with frame t - 1
+    // (mi355_diff_consecutive_batch).  The core's state takes no part.  d_prev may be the core's state or a caller's states: like
+    // a pair batch's operand it is read tile by tile by the launch that packs the tile, on the stream that wrote that tile.
+    bool consecutive = false;
+    // != nullptr: the expander writes the sender's byte stream (capacity in bytes) instead of d_xs / d_diff
+    void *d_wire = nullptr;
+    // != nullptr: the log is expanded into compact records (launch_expand_cwire) instead
+    const CwireOut *cw = nullptr;
+    // a public batch entry point on the core's OWN stream -- the index and the expansion run on the side stream beside the next
+    // batch's pack kernel (which needs only the state, carried on the core's stream, and a free set of logs); completion is what
+    // mi355_synchronize / any other entry point waits for (use_device joins).  With a caller's stream (mi355_set_stream)
+    // everything stays on that stream, in order: a caller who enqueues its own consumers there must find the batch complete.
+    bool pipelined = false;
+};
+
 CwireDirectArgs cwire_args(mi355_core *c, const CwireOut *cw, const uint32_t *d_offsets, uint32_t ntiles) {
     CwireDirectArgs x{};
     x.x.offsets = d_offsets;
@@ -398,19 +411,17 @@ CwireDirectArgs cwire_args(mi355_core *c, const CwireOut *cw, const uint32_t *d_
     return x;
 }
 
-int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, size_t stride,
-              int nframes, void *d_offsets, void *d_xs, void *d_diff, size_t capacity,
-              void *d_wire = nullptr, bool pipelined = false, const CwireOut *cw = nullptr, bool feedback = false,
-              int seg = 0, bool consecutive = false) {
+int run_batch(mi355_core *c, const BatchMode &m, const void *d_cur, const void *d_prev, size_t stride,
+              int nframes, void *d_offsets, void *d_xs, void *d_diff, size_t capacity) {
     if (!c) return fail(MI355_ERR_INVALID, "null core");
     if (nframes < 0 || nframes > c->cfg.max_batch)
         return fail(MI355_ERR_INVALID, "nframes outside [0, max_batch]");
     if (!d_offsets) return fail(MI355_ERR_INVALID, "null d_offsets");
-    if (nframes > 0 && c->n > 0 && (!d_cur || ((pair || consecutive) && !d_prev)))
+    if (nframes > 0 && c->n > 0 && (!d_cur || ((m.pair || m.consecutive) && !d_prev)))
         return fail(MI355_ERR_INVALID, "null frame pointer");
     if (nframes > 0 && stride < c->n) return fail(MI355_ERR_INVALID, "stride_bytes < frame bytes");
-    if (capacity > 0 && !d_wire && !cw && (!d_xs || !d_diff)) return fail(MI355_ERR_INVALID, "null output pointer");
-    pipelined = pipelined && c->stream == c->own_stream && c->pipeline_ok && nframes > 0 && c->n > 0;
+    if (capacity > 0 && !m.d_wire && !m.cw && (!d_xs || !d_diff)) return fail(MI355_ERR_INVALID, "null output pointer");
+    bool pipelined = m.pipelined && c->stream == c->own_stream && c->pipeline_ok && nframes > 0 && c->n > 0;
     const bool own = pipelined;   // an own-stream batch (its total is recorded for the next decisions)
     if (c->filter_since_batch) pipelined = false;   // a filter / batch chain: one kernel after the other (use_device_filter)
     c->filter_since_batch = false;
@@ -418,8 +429,8 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
         // the parts of the last batch: a tick on the states of the tick before may queue up behind them unseen (every tile
         // stays on its stream); any other tick must not write what a part elsewhere still reads, and no other batch may
         // read what a tick's part elsewhere still writes
-        const bool same_states = feedback && c->fb_states == d_prev && c->fb_stride == stride;
-        if (int rc = use_device(c, false, !same_states && (feedback || c->fb_states))) return rc;
+        const bool same_states = m.feedback && c->fb_states == d_prev && c->fb_stride == stride;
+        if (int rc = use_device(c, false, !same_states && (m.feedback || c->fb_states))) return rc;
         if (int rc = setup_pipeline(c)) return rc;
         pipelined = c->pipeline_ok;
     }
@@ -434,11 +445,11 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
     c->fb_states = nullptr;   // (whatever was pending has been waited for above, or is these very states)
     if (nframes == 0 || c->n == 0) {
         HIP_TRY(hipMemsetAsync(d_offsets, 0, sizeof(uint32_t) * ((size_t)nframes + 1), c->stream));
-        if (d_wire) {   // empty frames still have their headers {n = 0}
+        if (m.d_wire) {   // empty frames still have their headers {n = 0}
             const size_t head = 4 * (size_t)nframes < capacity ? 4 * (size_t)nframes : capacity & ~(size_t)3;
-            if (head) HIP_TRY(hipMemsetAsync(d_wire, 0, head, c->stream));
+            if (head) HIP_TRY(hipMemsetAsync(m.d_wire, 0, head, c->stream));
         }
-        if (cw) HIP_TRY(launch_expand_cwire(cwire_args(c, cw, (const uint32_t *)d_offsets, 0u), nframes, c->stream));
+        if (m.cw) HIP_TRY(launch_expand_cwire(cwire_args(c, m.cw, (const uint32_t *)d_offsets, 0u), nframes, c->stream));
         return MI355_OK;
     }
     hipEvent_t *tev = nullptr;
@@ -456,10 +467,10 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
     if (tev) HIP_TRY(hipEventRecord(tev[0], c->stream));
     PackArgs a{};
     a.cur = (const uint8_t *)d_cur;
-    a.prev = seg ? nullptr : (const uint8_t *)d_prev;
+    a.prev = m.seg ? nullptr : (const uint8_t *)d_prev;
     a.state = c->state;
-    a.seg = seg;
-    if (seg) a.states = (uint8_t *)const_cast<void *>(d_prev);
+    a.seg = m.seg;
+    if (m.seg) a.states = (uint8_t *)const_cast<void *>(d_prev);
     a.stride = stride;
     a.n = c->n;
     a.nframes = nframes;
@@ -482,7 +493,7 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
     // read hits in the caches); the pairs of a round-robin shard do not, and are read with non-temporal loads like the
     // frames of a stream (diff_pack.hip, Group::load_desc).
     bool pair_once = false;
-    if (pair) {
+    if (m.pair) {
         const int64_t d = (int64_t)((intptr_t)d_prev - (intptr_t)d_cur), st = (int64_t)stride, T = nframes;
         bool shared = false;
         const int64_t k0 = d / st;
@@ -507,17 +518,17 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
         PackArgs a0 = a, a1 = a;
         a0.tile_end = cut;
         a1.tile_begin = cut;
-        HIP_TRY(launch_diff_pack(a0, pair, aligned, pair_once, blocks0, c->stream, feedback, consecutive));
+        HIP_TRY(launch_diff_pack(a0, m.pair, aligned, pair_once, blocks0, c->stream, m.feedback, m.consecutive));
         HIP_TRY(hipStreamWaitEvent(c->main2, c->fork[c->flip], 0));
         if (ls.in_use) HIP_TRY(hipStreamWaitEvent(c->main2, ls.expanded, 0));
-        HIP_TRY(launch_diff_pack(a1, pair, aligned, pair_once, blocks1, c->main2, feedback, consecutive));
+        HIP_TRY(launch_diff_pack(a1, m.pair, aligned, pair_once, blocks1, c->main2, m.feedback, m.consecutive));
         HIP_TRY(hipEventRecord(c->packed2[c->flip], c->main2));
         HIP_TRY(hipStreamWaitEvent(tail, c->packed2[c->flip], 0));
         if (tev) HIP_TRY(hipEventRecord(tev[5], c->main2));   // the pack "kernel" of a split batch ends when BOTH parts have
         c->parts_pending = c->flip;
-        if (feedback) { c->fb_states = d_prev; c->fb_stride = stride; }
+        if (m.feedback) { c->fb_states = d_prev; c->fb_stride = stride; }
     } else {
-        HIP_TRY(launch_diff_pack(a, pair, aligned, pair_once, pipelined ? k1_blocks : 0u, c->stream, feedback, consecutive));
+        HIP_TRY(launch_diff_pack(a, m.pair, aligned, pair_once, pipelined ? k1_blocks : 0u, c->stream, m.feedback, m.consecutive));
     }
     if (tev) {
         HIP_TRY(hipEventRecord(tev[1], c->stream));
@@ -555,10 +566,10 @@ int run_batch(mi355_core *c, bool pair, const void *d_cur, const void *d_prev, s
     g.rec_bytes = a.rec_bytes;
     g.out_xs = (int32_t *)d_xs;
     g.out_diff = (uint8_t *)d_diff;
-    g.wire = (uint8_t *)d_wire;
+    g.wire = (uint8_t *)m.d_wire;
     g.capacity = capacity;
-    if (cw) {   // the same log into compact records (the kernels read only its fields and the offsets)
-        CwireDirectArgs x = cwire_args(c, cw, g.offsets, c->ntiles);
+    if (m.cw) {   // the same log into compact records (the kernels read only its fields and the offsets)
+        CwireDirectArgs x = cwire_args(c, m.cw, g.offsets, c->ntiles);
         x.x = g;
         HIP_TRY(launch_expand_cwire(x, nframes, tail));
     } else {
@@ -854,19 +865,25 @@ int mi355_set_glyphs(mi355_core *c, const uint8_t *chars_px, int nglyphs, int gl
 
 int mi355_diff_stream_batch(mi355_core *c, const void *d_frames, size_t stride_bytes, int nframes,
                             void *d_offsets, void *d_xs, void *d_diff, size_t capacity) {
-    return run_batch(c, false, d_frames, nullptr, stride_bytes, nframes, d_offsets, d_xs, d_diff, capacity, nullptr, true);
+    BatchMode m;
+    m.pipelined = true;
+    return run_batch(c, m, d_frames, nullptr, stride_bytes, nframes, d_offsets, d_xs, d_diff, capacity);
 }
 
 int mi355_diff_pairs_batch(mi355_core *c, const void *d_cur, const void *d_prev, size_t stride_bytes,
                            int nframes, void *d_offsets, void *d_xs, void *d_diff, size_t capacity) {
-    return run_batch(c, true, d_cur, d_prev, stride_bytes, nframes, d_offsets, d_xs, d_diff, capacity, nullptr, true);
+    BatchMode m;
+    m.pair = m.pipelined = true;
+    return run_batch(c, m, d_cur, d_prev, stride_bytes, nframes, d_offsets, d_xs, d_diff, capacity);
 }
 
 int mi355_diff_stream_wire_batch(mi355_core *c, const void *d_frames, size_t stride_bytes, int nframes,
                                  void *d_offsets, void *d_wire, size_t capacity_bytes) {
     if (!d_wire) return fail(MI355_ERR_INVALID, "null d_wire");
-    return run_batch(c, false, d_frames, nullptr, stride_bytes, nframes, d_offsets, nullptr, nullptr,
-                     capacity_bytes, d_wire, true);
+    BatchMode m;
+    m.d_wire = d_wire;
+    m.pipelined = true;
+    return run_batch(c, m, d_frames, nullptr, stride_bytes, nframes, d_offsets, nullptr, nullptr, capacity_bytes);
 }
 
 int mi355_diff_stream_cwire_batch(mi355_core *c, const void *d_frames, size_t stride_bytes, int nframes,
@@ -878,7 +895,10 @@ int mi355_diff_stream_cwire_batch(mi355_core *c, const void *d_frames, size_t st
     if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_frame_pos & 7u))
         return fail(MI355_ERR_INVALID, "d_cwire and d_offsets must be 4-byte aligned, d_frame_pos 8-byte aligned");
     const CwireOut cw{(uint64_t *)d_frame_pos, (uint8_t *)d_cwire, (uint64_t)capacity_bytes};
-    return run_batch(c, false, d_frames, nullptr, stride_bytes, nframes, d_offsets, nullptr, nullptr, 0, nullptr, true, &cw);
+    BatchMode m;
+    m.cw = &cw;
+    m.pipelined = true;
+    return run_batch(c, m, d_frames, nullptr, stride_bytes, nframes, d_offsets, nullptr, nullptr, 0);
 }
 
 // ---- the caller's regions of device memory, for the overlap tests of the entry points below ---------------------------------
@@ -950,23 +970,27 @@ static int check_multi_stream(mi355_core *c, const void *d_frames, const void *d
 
 int mi355_diff_consecutive_batch(mi355_core *c, const void *d_first_prev, const void *d_frames, size_t frame_step_bytes, int nframes,
                                  void *d_offsets, void *d_xs, void *d_diff, size_t capacity) {
-    return run_batch(c, false, d_frames, d_first_prev, frame_step_bytes, nframes, d_offsets, d_xs, d_diff, capacity, nullptr, true,
-                     nullptr, false, 0, true);
+    BatchMode m;
+    m.consecutive = m.pipelined = true;
+    return run_batch(c, m, d_frames, d_first_prev, frame_step_bytes, nframes, d_offsets, d_xs, d_diff, capacity);
 }
 
 int mi355_diff_multi_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
                            void *d_offsets, void *d_xs, void *d_diff, size_t capacity) {
     if (int rc = check_multi_stream(c, d_frames, d_states, stride_bytes, nstreams, 1)) return rc;
-    return run_batch(c, true, d_frames, d_states, stride_bytes, nstreams, d_offsets, d_xs, d_diff, capacity, nullptr, true,
-                     nullptr, true);
+    BatchMode m;
+    m.pair = m.feedback = m.pipelined = true;
+    return run_batch(c, m, d_frames, d_states, stride_bytes, nstreams, d_offsets, d_xs, d_diff, capacity);
 }
 
 int mi355_diff_multi_wire_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
                                 void *d_offsets, void *d_wire, size_t capacity_bytes) {
     if (int rc = check_multi_stream(c, d_frames, d_states, stride_bytes, nstreams, 1)) return rc;
     if (!d_wire) return fail(MI355_ERR_INVALID, "null d_wire");
-    return run_batch(c, true, d_frames, d_states, stride_bytes, nstreams, d_offsets, nullptr, nullptr, capacity_bytes,
-                     d_wire, true, nullptr, true);
+    BatchMode m;
+    m.pair = m.feedback = m.pipelined = true;
+    m.d_wire = d_wire;
+    return run_batch(c, m, d_frames, d_states, stride_bytes, nstreams, d_offsets, nullptr, nullptr, capacity_bytes);
 }
 
 int mi355_diff_multi_cwire_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
@@ -977,23 +1001,30 @@ int mi355_diff_multi_cwire_batch(mi355_core *c, const void *d_frames, void *d_st
     if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_frame_pos & 7u))
         return fail(MI355_ERR_INVALID, "d_cwire and d_offsets must be 4-byte aligned, d_frame_pos 8-byte aligned");
     const CwireOut cw{(uint64_t *)d_frame_pos, (uint8_t *)d_cwire, (uint64_t)capacity_bytes};
-    return run_batch(c, true, d_frames, d_states, stride_bytes, nstreams, d_offsets, nullptr, nullptr, 0, nullptr, true, &cw,
-                     true);
+    BatchMode m;
+    m.pair = m.feedback = m.pipelined = true;
+    m.cw = &cw;
+    return run_batch(c, m, d_frames, d_states, stride_bytes, nstreams, d_offsets, nullptr, nullptr, 0);
 }
 
 int mi355_diff_multi_stream_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
                                   int nframes, void *d_offsets, void *d_xs, void *d_diff, size_t capacity) {
     if (int rc = check_multi_stream(c, d_frames, d_states, stride_bytes, nstreams, nframes)) return rc;
-    return run_batch(c, false, d_frames, d_states, stride_bytes, nstreams * nframes, d_offsets, d_xs, d_diff, capacity, nullptr, true,
-                     nullptr, true, nframes);
+    BatchMode m;
+    m.feedback = m.pipelined = true;
+    m.seg = nframes;
+    return run_batch(c, m, d_frames, d_states, stride_bytes, nstreams * nframes, d_offsets, d_xs, d_diff, capacity);
 }
 
 int mi355_diff_multi_stream_wire_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
                                        int nframes, void *d_offsets, void *d_wire, size_t capacity_bytes) {
     if (int rc = check_multi_stream(c, d_frames, d_states, stride_bytes, nstreams, nframes)) return rc;
     if (!d_wire) return fail(MI355_ERR_INVALID, "null d_wire");
-    return run_batch(c, false, d_frames, d_states, stride_bytes, nstreams * nframes, d_offsets, nullptr, nullptr, capacity_bytes,
-                     d_wire, true, nullptr, true, nframes);
+    BatchMode m;
+    m.feedback = m.pipelined = true;
+    m.seg = nframes;
+    m.d_wire = d_wire;
+    return run_batch(c, m, d_frames, d_states, stride_bytes, nstreams * nframes, d_offsets, nullptr, nullptr, capacity_bytes);
 }
 
 int mi355_diff_multi_stream_cwire_batch(mi355_core *c, const void *d_frames, void *d_states, size_t stride_bytes, int nstreams,
@@ -1004,8 +1035,11 @@ int mi355_diff_multi_stream_cwire_batch(mi355_core *c, const void *d_frames, voi
     if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_frame_pos & 7u))
         return fail(MI355_ERR_INVALID, "d_cwire and d_offsets must be 4-byte aligned, d_frame_pos 8-byte aligned");
     const CwireOut cw{(uint64_t *)d_frame_pos, (uint8_t *)d_cwire, (uint64_t)capacity_bytes};
-    return run_batch(c, false, d_frames, d_states, stride_bytes, nstreams * nframes, d_offsets, nullptr, nullptr, 0, nullptr, true,
-                     &cw, true, nframes);
+    BatchMode m;
+    m.feedback = m.pipelined = true;
+    m.seg = nframes;
+    m.cw = &cw;
+    return run_batch(c, m, d_frames, d_states, stride_bytes, nstreams * nframes, d_offsets, nullptr, nullptr, 0);
 }
 
 size_t mi355_wire_bytes(int nframes, uint64_t entries) { return 4 * (size_t)nframes + 5 * (size_t)entries; }
@@ -1157,6 +1191,16 @@ static int write_empty_heads(mi355_core *c, void *d_offsets, void *d_frame_pos) 
     return MI355_OK;
 }
 
+// *B = nstreams * nframes, the records or segments of a burst: refused below 0 and above max_batch
+static int burst_count(const mi355_core *c, int nstreams, int nframes, int *B) {
+    *B = 0;
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nstreams < 0 || nframes < 0) return fail(MI355_ERR_INVALID, "nstreams or nframes < 0");
+    if ((int64_t)nstreams * nframes > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams * nframes above max_batch");
+    *B = nstreams * nframes;
+    return MI355_OK;
+}
+
 int mi355_cwire_encode_batch(mi355_core *c, const void *d_offsets, const void *d_xs, const void *d_diff,
                              size_t entries_capacity, int nframes, void *d_frame_pos, void *d_cwire, size_t capacity_bytes) {
     if (!c) return fail(MI355_ERR_INVALID, "null core");
@@ -1235,10 +1279,8 @@ int mi355_apply_cwire_batch(mi355_core *c, const void *d_cwire, const uint32_t *
 static int check_apply_multi_stream(mi355_core *c, bool inputs, int nstreams, int nframes, const void *d_states, size_t stride,
                                     const void *d_out, size_t out_stride, bool *run) {
     *run = false;
-    if (!c) return fail(MI355_ERR_INVALID, "null core");
-    if (nstreams < 0 || nframes < 0) return fail(MI355_ERR_INVALID, "nstreams or nframes < 0");
-    const int64_t B = (int64_t)nstreams * nframes;
-    if (B > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams * nframes above max_batch");
+    int B;
+    if (int rc = burst_count(c, nstreams, nframes, &B)) return rc;
     if (B == 0) return MI355_OK;
     if (!inputs) return fail(MI355_ERR_INVALID, "null stream pointer");
     if (!d_states) return fail(MI355_ERR_INVALID, "null d_states");
@@ -1403,74 +1445,86 @@ int mi355_apply_multi_stream_cwire_batch(mi355_core *c, const void *d_cwire, con
     return MI355_OK;
 }
 
+// ---- the calls that take a burst of compact records and write ONE segment or ONE compact record per stream ---------------------
+// Their outputs, as the kernels take them, with what the calls refuse about them: offsets and either the arrays (xs, diff,
+// capacity in entries) or, compact, the records (frame_pos, cwire, capacity in bytes); the pointers of the other form are null.
+struct Produced : CwcOut {
+    bool compact;
+    static Produced arrays(void *d_offsets, void *d_xs, void *d_diff, size_t capacity) {
+        return Produced{{(uint32_t *)d_offsets, nullptr, nullptr, (int32_t *)d_xs, (uint8_t *)d_diff, capacity}, false};
+    }
+    static Produced records(void *d_offsets, void *d_frame_pos, void *d_cwire_out, size_t capacity_bytes) {
+        return Produced{{(uint32_t *)d_offsets, (uint64_t *)d_frame_pos, (uint8_t *)d_cwire_out, nullptr, nullptr, capacity_bytes}, true};
+    }
+    // (d_cwire: the call's input, which the text names among the outputs)
+    int check_aligned(const void *d_cwire) const {
+        if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)offsets & 3u) || ((uintptr_t)cwire & 3u) || ((uintptr_t)xs & 3u))
+            return fail(MI355_ERR_INVALID, "d_cwire, d_cwire_out, d_offsets and d_xs must be 4-byte aligned");
+        if ((uintptr_t)frame_pos & 7u) return fail(MI355_ERR_INVALID, "d_frame_pos must be 8-byte aligned");
+        return MI355_OK;
+    }
+    int check_given() const {
+        if (!offsets || (compact ? !frame_pos || !cwire : !xs || !diff)) return fail(MI355_ERR_INVALID, "null output pointer");
+        return MI355_OK;
+    }
+    // Refuses an output that overlaps the input, output by output; nsegments: the segments / records written (nstreams, or the
+    // mosaic's one)
+    int check_apart(const Region &in, int nsegments) const {
+        if (compact)
+            return check_regions({in}, {offsets_region(offsets, nsegments), frame_pos_region(frame_pos, nsegments),
+                                        Region{cwire, capacity, "d_cwire_out"}});
+        return check_regions({in}, {offsets_region(offsets, nsegments), Region{xs, 4 * capacity, "d_xs"}, Region{diff, capacity, "d_diff"}});
+    }
+};
+
+// The last rungs of coalesce, crop and mosaic alike: the record table (its header refusals), the overlap refusals, the device
+static int producer_table(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int B, const Produced &o,
+                          int nsegments, CwaTable *tab) {
+    if (int rc = cwa_table(c, h_counts, h_escapes, B, tab)) return rc;
+    if (int rc = o.check_apart(input_region(d_cwire, tab->bytes), nsegments)) return rc;
+    return use_device(c);
+}
+
 // ---- mi355_cwire_coalesce_(cwire_)batch: nframes records of each of nstreams streams -> ONE segment / record per stream -------
 // Both forms: everything is refused here, before anything is launched; the core's state is not touched.
 static int coalesce(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams,
-                    int nframes, bool cwire, void *d_offsets, void *d_frame_pos, void *d_cwire_out, void *d_xs, void *d_diff,
-                    size_t capacity) {
-    if (!c) return fail(MI355_ERR_INVALID, "null core");
-    if (nstreams < 0 || nframes < 0) return fail(MI355_ERR_INVALID, "nstreams or nframes < 0");
-    const int64_t B64 = (int64_t)nstreams * nframes;
-    if (B64 > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams * nframes above max_batch");
-    const int B = (int)B64;
-    if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_cwire_out & 3u) || ((uintptr_t)d_xs & 3u))
-        return fail(MI355_ERR_INVALID, "d_cwire, d_cwire_out, d_offsets and d_xs must be 4-byte aligned");
-    if ((uintptr_t)d_frame_pos & 7u) return fail(MI355_ERR_INVALID, "d_frame_pos must be 8-byte aligned");
-    if (B == 0) return write_empty_heads(c, d_offsets, d_frame_pos);
+                    int nframes, const Produced &o) {
+    int B;
+    if (int rc = burst_count(c, nstreams, nframes, &B)) return rc;
+    if (int rc = o.check_aligned(d_cwire)) return rc;
+    if (B == 0) return write_empty_heads(c, o.offsets, o.frame_pos);
     if (!d_cwire || !h_counts || !h_escapes) return fail(MI355_ERR_INVALID, "null stream pointer");
-    if (!d_offsets || (cwire ? !d_frame_pos || !d_cwire_out : !d_xs || !d_diff)) return fail(MI355_ERR_INVALID, "null output pointer");
+    if (int rc = o.check_given()) return rc;
     CwaTable tab;
-    if (int rc = cwa_table(c, h_counts, h_escapes, B, &tab)) return rc;
-    if (int rc = check_regions({input_region(d_cwire, tab.bytes)},   // (the outputs of the other form: nowhere)
-                               {offsets_region(d_offsets, nstreams), cwire ? frame_pos_region(d_frame_pos, nstreams) : Region{},
-                                cwire ? Region{d_cwire_out, capacity, "d_cwire_out"} : Region{},
-                                cwire ? Region{} : Region{d_xs, 4 * (uint64_t)capacity, "d_xs"},
-                                cwire ? Region{} : Region{d_diff, capacity, "d_diff"}}))
-        return rc;
-    if (int rc = use_device(c)) return rc;
-    const CwaArgs a = cwa_args(c, d_cwire);
-    CwcOut o{};
-    o.offsets = (uint32_t *)d_offsets;
-    o.frame_pos = (uint64_t *)d_frame_pos;
-    o.cwire = (uint8_t *)d_cwire_out;
-    o.xs = (int32_t *)d_xs;
-    o.diff = (uint8_t *)d_diff;
-    o.capacity = capacity;
-    HIP_TRY(launch_cwire_coalesce(a, tab.fr.data(), nstreams, nframes, o, cwire, c->stream));
+    if (int rc = producer_table(c, d_cwire, h_counts, h_escapes, B, o, nstreams, &tab)) return rc;
+    HIP_TRY(launch_cwire_coalesce(cwa_args(c, d_cwire), tab.fr.data(), nstreams, nframes, o, o.compact, c->stream));
     return MI355_OK;
 }
 
 int mi355_cwire_coalesce_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
                                int nstreams, int nframes, void *d_offsets, void *d_xs, void *d_diff, size_t capacity) {
-    return coalesce(c, d_cwire, h_counts, h_escapes, nstreams, nframes, false, d_offsets, nullptr, nullptr, d_xs, d_diff, capacity);
+    return coalesce(c, d_cwire, h_counts, h_escapes, nstreams, nframes, Produced::arrays(d_offsets, d_xs, d_diff, capacity));
 }
 
 int mi355_cwire_coalesce_cwire_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
                                      int nstreams, int nframes, void *d_offsets, void *d_frame_pos, void *d_cwire_out,
                                      size_t capacity_bytes) {
-    return coalesce(c, d_cwire, h_counts, h_escapes, nstreams, nframes, true, d_offsets, d_frame_pos, d_cwire_out, nullptr, nullptr,
-                    capacity_bytes);
+    return coalesce(c, d_cwire, h_counts, h_escapes, nstreams, nframes, Produced::records(d_offsets, d_frame_pos, d_cwire_out, capacity_bytes));
 }
 
 // ---- mi355_cwire_crop_(cwire_)batch: coalesce(...) with every stream's sums cut to its rectangle -----------------------------
 // Both forms: everything is refused here, before anything is launched; the core's state is not touched.  The per-stream words
 // are the budget call's (c->cwb_hist, max_batch rows): both calls are ordered on the core's stream.
 static int crop(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams, int nframes,
-                const int32_t *h_rects, unsigned flags, bool cwire, void *d_offsets, void *d_frame_pos, void *d_cwire_out, void *d_xs,
-                void *d_diff, size_t capacity) {
-    if (!c) return fail(MI355_ERR_INVALID, "null core");
-    if (nstreams < 0 || nframes < 0) return fail(MI355_ERR_INVALID, "nstreams or nframes < 0");
-    const int64_t B64 = (int64_t)nstreams * nframes;
-    if (B64 > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams * nframes above max_batch");
-    const int B = (int)B64;
+                const int32_t *h_rects, unsigned flags, const Produced &o) {
+    int B;
+    if (int rc = burst_count(c, nstreams, nframes, &B)) return rc;
     if (flags & ~MI355_CROP_KEEP_INDEX) return fail(MI355_ERR_INVALID, "unknown flag bit (MI355_CROP_KEEP_INDEX is the only one)");
-    if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_cwire_out & 3u) || ((uintptr_t)d_xs & 3u))
-        return fail(MI355_ERR_INVALID, "d_cwire, d_cwire_out, d_offsets and d_xs must be 4-byte aligned");
-    if ((uintptr_t)d_frame_pos & 7u) return fail(MI355_ERR_INVALID, "d_frame_pos must be 8-byte aligned");
-    if (B == 0) return write_empty_heads(c, d_offsets, d_frame_pos);
+    if (int rc = o.check_aligned(d_cwire)) return rc;
+    if (B == 0) return write_empty_heads(c, o.offsets, o.frame_pos);
     if (!d_cwire || !h_counts || !h_escapes) return fail(MI355_ERR_INVALID, "null stream pointer");
     if (!h_rects) return fail(MI355_ERR_INVALID, "null h_rects");
-    if (!d_offsets || (cwire ? !d_frame_pos || !d_cwire_out : !d_xs || !d_diff)) return fail(MI355_ERR_INVALID, "null output pointer");
+    if (int rc = o.check_given()) return rc;
     for (int s = 0; s < nstreams; s++) {
         const int32_t *r = h_rects + 4 * (size_t)s;
         if (r[0] < 0 || r[1] < 0 || r[2] < 0 || r[3] < 0) return fail(MI355_ERR_INVALID, "rectangle with a negative member");
@@ -1478,39 +1532,23 @@ static int crop(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, co
             return fail(MI355_ERR_INVALID, "rectangle outside the frame");
     }
     CwaTable tab;
-    if (int rc = cwa_table(c, h_counts, h_escapes, B, &tab)) return rc;
-    if (int rc = check_regions({input_region(d_cwire, tab.bytes)},   // (the outputs of the other form: nowhere)
-                               {offsets_region(d_offsets, nstreams), cwire ? frame_pos_region(d_frame_pos, nstreams) : Region{},
-                                cwire ? Region{d_cwire_out, capacity, "d_cwire_out"} : Region{},
-                                cwire ? Region{} : Region{d_xs, 4 * (uint64_t)capacity, "d_xs"},
-                                cwire ? Region{} : Region{d_diff, capacity, "d_diff"}}))
-        return rc;
-    if (int rc = use_device(c)) return rc;
-    const CwaArgs a = cwa_args(c, d_cwire);
-    CwcOut o{};
-    o.offsets = (uint32_t *)d_offsets;
-    o.frame_pos = (uint64_t *)d_frame_pos;
-    o.cwire = (uint8_t *)d_cwire_out;
-    o.xs = (int32_t *)d_xs;
-    o.diff = (uint8_t *)d_diff;
-    o.capacity = capacity;
-    HIP_TRY(launch_cwire_crop(a, tab.fr.data(), nstreams, nframes, h_rects, (uint32_t)c->cfg.width, (flags & MI355_CROP_KEEP_INDEX) != 0,
-                              c->cwb_hist, o, cwire, c->stream));
+    if (int rc = producer_table(c, d_cwire, h_counts, h_escapes, B, o, nstreams, &tab)) return rc;
+    HIP_TRY(launch_cwire_crop(cwa_args(c, d_cwire), tab.fr.data(), nstreams, nframes, h_rects, (uint32_t)c->cfg.width,
+                              (flags & MI355_CROP_KEEP_INDEX) != 0, c->cwb_hist, o, o.compact, c->stream));
     return MI355_OK;
 }
 
 int mi355_cwire_crop_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams,
                            int nframes, const int32_t *h_rects, unsigned flags, void *d_offsets, void *d_xs, void *d_diff,
                            size_t capacity) {
-    return crop(c, d_cwire, h_counts, h_escapes, nstreams, nframes, h_rects, flags, false, d_offsets, nullptr, nullptr, d_xs, d_diff,
-                capacity);
+    return crop(c, d_cwire, h_counts, h_escapes, nstreams, nframes, h_rects, flags, Produced::arrays(d_offsets, d_xs, d_diff, capacity));
 }
 
 int mi355_cwire_crop_cwire_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams,
                                  int nframes, const int32_t *h_rects, unsigned flags, void *d_offsets, void *d_frame_pos,
                                  void *d_cwire_out, size_t capacity_bytes) {
-    return crop(c, d_cwire, h_counts, h_escapes, nstreams, nframes, h_rects, flags, true, d_offsets, d_frame_pos, d_cwire_out, nullptr,
-                nullptr, capacity_bytes);
+    return crop(c, d_cwire, h_counts, h_escapes, nstreams, nframes, h_rects, flags,
+                Produced::records(d_offsets, d_frame_pos, d_cwire_out, capacity_bytes));
 }
 
 // ---- mi355_cwire_mosaic_(cwire_)batch: the streams' coalesced records placed on a canvas, ONE segment / record out --------------
@@ -1518,25 +1556,19 @@ int mi355_cwire_crop_cwire_batch(mi355_core *c, const void *d_cwire, const uint3
 // are the budget call's, as for the crop; the facts of the canvas' tiles take the chunk scratch, which holds max_batch *
 // cwa_chunks(N) words and is not grown here.
 static int mosaic(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams, int nframes,
-                  const int32_t *h_place, int canvas_w, int canvas_h, bool cwire, void *d_offsets, void *d_frame_pos, void *d_cwire_out,
-                  void *d_xs, void *d_diff, size_t capacity) {
-    if (!c) return fail(MI355_ERR_INVALID, "null core");
-    if (nstreams < 0 || nframes < 0) return fail(MI355_ERR_INVALID, "nstreams or nframes < 0");
-    const int64_t B64 = (int64_t)nstreams * nframes;
-    if (B64 > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams * nframes above max_batch");
-    const int B = (int)B64;
+                  const int32_t *h_place, int canvas_w, int canvas_h, const Produced &o) {
+    int B;
+    if (int rc = burst_count(c, nstreams, nframes, &B)) return rc;
     if (canvas_w < 1 || canvas_h < 1) return fail(MI355_ERR_INVALID, "canvas_w or canvas_h < 1");
     const uint64_t nc = 3ull * (uint64_t)canvas_w * (uint64_t)canvas_h;
     if (nc >= (1ull << 31)) return fail(MI355_ERR_INVALID, "canvas of 2^31 bytes or more");
     if ((uint64_t)mi355_state_tiles((size_t)nc) > (uint64_t)c->cfg.max_batch * mi355_state_tiles(c->n))
         return fail(MI355_ERR_INVALID, "canvas of more 4096-byte tiles than max_batch frames hold: create the core with a larger max_batch");
-    if (((uintptr_t)d_cwire & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_cwire_out & 3u) || ((uintptr_t)d_xs & 3u))
-        return fail(MI355_ERR_INVALID, "d_cwire, d_cwire_out, d_offsets and d_xs must be 4-byte aligned");
-    if ((uintptr_t)d_frame_pos & 7u) return fail(MI355_ERR_INVALID, "d_frame_pos must be 8-byte aligned");
-    if (B == 0) return write_empty_heads(c, d_offsets, d_frame_pos);
+    if (int rc = o.check_aligned(d_cwire)) return rc;
+    if (B == 0) return write_empty_heads(c, o.offsets, o.frame_pos);
     if (!d_cwire || !h_counts || !h_escapes) return fail(MI355_ERR_INVALID, "null stream pointer");
     if (!h_place) return fail(MI355_ERR_INVALID, "null h_place");
-    if (!d_offsets || (cwire ? !d_frame_pos || !d_cwire_out : !d_xs || !d_diff)) return fail(MI355_ERR_INVALID, "null output pointer");
+    if (int rc = o.check_given()) return rc;
     for (int s = 0; s < nstreams; s++) {
         const int32_t *p = h_place + 6 * (size_t)s;
         for (int k = 0; k < 6; k++)
@@ -1547,39 +1579,24 @@ static int mosaic(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, 
             return fail(MI355_ERR_INVALID, "destination rectangle outside the canvas");
     }
     CwaTable tab;
-    if (int rc = cwa_table(c, h_counts, h_escapes, B, &tab)) return rc;
-    if (int rc = check_regions({input_region(d_cwire, tab.bytes)},   // (the outputs of the other form: nowhere)
-                               {offsets_region(d_offsets, 1), cwire ? frame_pos_region(d_frame_pos, 1) : Region{},
-                                cwire ? Region{d_cwire_out, capacity, "d_cwire_out"} : Region{},
-                                cwire ? Region{} : Region{d_xs, 4 * (uint64_t)capacity, "d_xs"},
-                                cwire ? Region{} : Region{d_diff, capacity, "d_diff"}}))
-        return rc;
-    if (int rc = use_device(c)) return rc;
-    const CwaArgs a = cwa_args(c, d_cwire);
-    CwcOut o{};
-    o.offsets = (uint32_t *)d_offsets;
-    o.frame_pos = (uint64_t *)d_frame_pos;
-    o.cwire = (uint8_t *)d_cwire_out;
-    o.xs = (int32_t *)d_xs;
-    o.diff = (uint8_t *)d_diff;
-    o.capacity = capacity;
-    HIP_TRY(launch_cwire_mosaic(a, tab.fr.data(), nstreams, nframes, h_place, (uint32_t)c->cfg.width, (uint32_t)canvas_w, (uint32_t)nc,
-                                c->cwb_hist, o, cwire, c->stream));
+    if (int rc = producer_table(c, d_cwire, h_counts, h_escapes, B, o, 1, &tab)) return rc;
+    HIP_TRY(launch_cwire_mosaic(cwa_args(c, d_cwire), tab.fr.data(), nstreams, nframes, h_place, (uint32_t)c->cfg.width, (uint32_t)canvas_w,
+                                (uint32_t)nc, c->cwb_hist, o, o.compact, c->stream));
     return MI355_OK;
 }
 
 int mi355_cwire_mosaic_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams,
                              int nframes, const int32_t *h_place, int canvas_w, int canvas_h, void *d_offsets, void *d_xs, void *d_diff,
                              size_t capacity) {
-    return mosaic(c, d_cwire, h_counts, h_escapes, nstreams, nframes, h_place, canvas_w, canvas_h, false, d_offsets, nullptr, nullptr,
-                  d_xs, d_diff, capacity);
+    return mosaic(c, d_cwire, h_counts, h_escapes, nstreams, nframes, h_place, canvas_w, canvas_h,
+                  Produced::arrays(d_offsets, d_xs, d_diff, capacity));
 }
 
 int mi355_cwire_mosaic_cwire_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams,
                                    int nframes, const int32_t *h_place, int canvas_w, int canvas_h, void *d_offsets, void *d_frame_pos,
                                    void *d_cwire_out, size_t capacity_bytes) {
-    return mosaic(c, d_cwire, h_counts, h_escapes, nstreams, nframes, h_place, canvas_w, canvas_h, true, d_offsets, d_frame_pos,
-                  d_cwire_out, nullptr, nullptr, capacity_bytes);
+    return mosaic(c, d_cwire, h_counts, h_escapes, nstreams, nframes, h_place, canvas_w, canvas_h,
+                  Produced::records(d_offsets, d_frame_pos, d_cwire_out, capacity_bytes));
 }
 
 // ---- mi355_cwire_budget_cwire_batch: the records of one tick held to an entry budget each ------------------------------------
@@ -1619,13 +1636,8 @@ int mi355_cwire_budget_cwire_batch(mi355_core *c, const void *d_cwire, const uin
     CwaArgs a = cwa_args(c, d_cwire);
     a.state = (uint8_t *)d_states;
     a.stride = stride_bytes;
-    CwcOut o{};
-    o.offsets = (uint32_t *)d_offsets;
-    o.frame_pos = (uint64_t *)d_frame_pos;
-    o.cwire = (uint8_t *)d_cwire_out;
-    o.capacity = capacity_bytes;
-    HIP_TRY(launch_cwire_budget(a, tab.fr.data(), nstreams, h_budget, (uint32_t)c->cfg.threshold, c->cwb_hist, (uint32_t *)d_thresholds, o,
-                                c->stream));
+    HIP_TRY(launch_cwire_budget(a, tab.fr.data(), nstreams, h_budget, (uint32_t)c->cfg.threshold, c->cwb_hist, (uint32_t *)d_thresholds,
+                                Produced::records(d_offsets, d_frame_pos, d_cwire_out, capacity_bytes), c->stream));
     return MI355_OK;
 }
 
@@ -1642,15 +1654,12 @@ size_t mi355_activity_cells(int width, int height, int cell_w, int cell_h, int *
 // two device inputs, in_ok: none of its inputs is null.
 static int check_activity(mi355_core *c, const void *in0, const void *in1, bool in_ok, int nstreams, int nframes, int cell_w, int cell_h,
                           uint32_t min_count, const void *d_cells, const void *d_summary, int *B, ActGeom *g) {
-    *B = 0;
-    if (!c) return fail(MI355_ERR_INVALID, "null core");
-    if (nstreams < 0 || nframes < 0) return fail(MI355_ERR_INVALID, "nstreams or nframes < 0");
-    if ((int64_t)nstreams * nframes > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams * nframes above max_batch");
+    if (int rc = burst_count(c, nstreams, nframes, B)) return rc;
     if (cell_w < 1 || cell_h < 1) return fail(MI355_ERR_INVALID, "cell_w or cell_h < 1");
     if (min_count < 1) return fail(MI355_ERR_INVALID, "min_count < 1");
     if (((uintptr_t)in0 | (uintptr_t)in1 | (uintptr_t)d_cells | (uintptr_t)d_summary) & 3u)
         return fail(MI355_ERR_INVALID, "the device pointers must be 4-byte aligned");
-    if (nstreams * nframes == 0) return MI355_OK;
+    if (*B == 0) return MI355_OK;
     if (!in_ok) return fail(MI355_ERR_INVALID, "null stream pointer");
     if (!d_cells || !d_summary) return fail(MI355_ERR_INVALID, "null output pointer");
     int gw = 0;
@@ -1661,7 +1670,6 @@ static int check_activity(mi355_core *c, const void *in0, const void *in1, bool 
     g->cells = (uint32_t)mi355_activity_cells(c->cfg.width, c->cfg.height, cell_w, cell_h, &gw, nullptr);
     g->grid_w = (uint32_t)gw;
     g->min_count = min_count;
-    *B = nstreams * nframes;
     return MI355_OK;
 }
 
@@ -2035,12 +2043,8 @@ int mi355_refresh_cwire_batch(mi355_core *c, const void *d_states, size_t stride
     CwaArgs a = cwa_args(c, nullptr);   // (chunk: one fact word per (stream, tile), nstreams <= max_batch)
     a.state = (uint8_t *)d_states;      // (only read)
     a.stride = stride_bytes;
-    CwcOut o{};
-    o.offsets = (uint32_t *)d_offsets;
-    o.frame_pos = (uint64_t *)d_frame_pos;
-    o.cwire = (uint8_t *)d_cwire_out;
-    o.capacity = capacity_bytes;
-    HIP_TRY(launch_refresh(a, nstreams, (const uint32_t *)d_peer_digests, (uint32_t *)d_tile_mask, o, c->stream));
+    HIP_TRY(launch_refresh(a, nstreams, (const uint32_t *)d_peer_digests, (uint32_t *)d_tile_mask,
+                           Produced::records(d_offsets, d_frame_pos, d_cwire_out, capacity_bytes), c->stream));
     return MI355_OK;
 }
 
@@ -2100,11 +2104,9 @@ int mi355_wall_compose_batch(mi355_core *c, const void *d_states, size_t stride_
 
 int mi355_cwire_touched_tiles_batch(mi355_core *c, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams,
                                     int nframes, int accumulate, void *d_tile_mask) {
-    if (!c) return fail(MI355_ERR_INVALID, "null core");
-    if (nstreams < 0 || nframes < 0) return fail(MI355_ERR_INVALID, "nstreams or nframes < 0");
-    if ((int64_t)nstreams * nframes > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams * nframes above max_batch");
+    int B;
+    if (int rc = burst_count(c, nstreams, nframes, &B)) return rc;
     if (((uintptr_t)d_cwire | (uintptr_t)d_tile_mask) & 3u) return fail(MI355_ERR_INVALID, "the device pointers must be 4-byte aligned");
-    const int B = nstreams * nframes;
     if (B == 0) return MI355_OK;
     if (!d_cwire || !h_counts || !h_escapes) return fail(MI355_ERR_INVALID, "null stream pointer");
     if (!d_tile_mask) return fail(MI355_ERR_INVALID, "null output pointer");
@@ -2324,7 +2326,7 @@ static int warm_exec(mi355_core *c) {
     if (c->cfg.noise_filter && c->have_k9)   // (its output is not used: a filtered frame would differ from the state)
         HIP_TRY(launch_conv3x3(c->in, c->aux, c->cfg.width, c->cfg.height, c->k9, c->k9_sym, FrameBatch{N, 1}, s));
     if (int rc = prepare_frame(c, c->in, c->vis, nullptr, s)) return rc;
-    if (int rc = run_batch(c, false, c->in, nullptr, N, 1, c->offsets, c->one_xs, c->one_diff, N)) return rc;
+    if (int rc = run_batch(c, BatchMode{}, c->in, nullptr, N, 1, c->offsets, c->one_xs, c->one_diff, N)) return rc;
     if (vis == MI355_VIS_RED || vis == MI355_VIS_RED_OVERLAP)
         HIP_TRY(launch_red_overlap(c->vis, c->one_xs, c->offsets + 1, 0, N, s));
     HIP_TRY(launch_export(c->offsets, c->one_xs, c->one_diff, (int32_t *)c->h_count, (uint8_t *)c->h_count, c->h_count, s));
@@ -2353,7 +2355,7 @@ static int exec_frame(mi355_core *c, const uint8_t *frame_data, uint8_t *show_re
         HIP_TRY(hipMemcpyAsync(show_ready, c->vis, N, hipMemcpyDeviceToHost, s));
 
     // kernels.cu:505  kernel2
-    return run_batch(c, false, c->in, nullptr, N, 1, c->offsets, c->one_xs, c->one_diff, N);
+    return run_batch(c, BatchMode{}, c->in, nullptr, N, 1, c->offsets, c->one_xs, c->one_diff, N);
 }
 
 int mi355_exec(mi355_core *c, uint8_t *frame_data, uint8_t *show_ready, const char *text,
@@ -2471,7 +2473,7 @@ static int pipe_frame(mi355_core *c, const uint8_t *frame_data, uint8_t *show_re
         frame = c->in;
     }
     if (int rc = prepare_frame(c, frame, sl.d_vis, text, s)) return rc;
-    if (int rc = run_batch(c, false, frame, nullptr, N, 1, c->offsets, c->one_xs, c->one_diff, N)) return rc;
+    if (int rc = run_batch(c, BatchMode{}, frame, nullptr, N, 1, c->offsets, c->one_xs, c->one_diff, N)) return rc;
     if (vis == MI355_VIS_RED || vis == MI355_VIS_RED_OVERLAP)
         HIP_TRY(launch_red_overlap(sl.d_vis, c->one_xs, c->offsets + 1, 0, N, s));
     sl.has_vis = vis != MI355_VIS_NONE;
@@ -2735,6 +2737,8 @@ int mi355_alloc_outputs(mi355_core *c, size_t capacity, void **d_xs, void **d_di
                 const double s_pack = c->ms_pack, s_scan = c->ms_scan, s_exp = c->ms_expand, s_tot = c->ms_total;
                 const int s_l = c->launches;
                 double best_rate = 0;
+                BatchMode pairs;
+                pairs.pair = true;
                 while (ndraw < kMaxDraws && rc == MI355_OK) {
                     if (hipMalloc((void **)&cand[ndraw], df_bytes) != hipSuccess) { (void)hipGetLastError(); break; }
                     uint8_t *df = cand[ndraw++];
@@ -2742,11 +2746,11 @@ int mi355_alloc_outputs(mi355_core *c, size_t capacity, void **d_xs, void **d_di
                     // its clocks), one batch on the others
                     c->timing = false;
                     for (int rep = 0; rep < (ndraw == 1 ? 48 : 1) && rc == MI355_OK; rep++)
-                        rc = run_batch(c, true, frames, frames + (size_t)T * N, N, T, off, xs, df, capacity);
+                        rc = run_batch(c, pairs, frames, frames + (size_t)T * N, N, T, off, xs, df, capacity);
                     c->timing = true;
                     c->ms_expand = 0; c->launches = 0;
                     for (int rep = 0; rep < 3 && rc == MI355_OK; rep++)
-                        rc = run_batch(c, true, frames, frames + (size_t)T * N, N, T, off, xs, df, capacity);
+                        rc = run_batch(c, pairs, frames, frames + (size_t)T * N, N, T, off, xs, df, capacity);
                     if (rc == MI355_OK) rc = harvest_timing(c);
                     if (rc != MI355_OK) break;
                     uint32_t total = 0;

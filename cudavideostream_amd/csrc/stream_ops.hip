@@ -2614,21 +2614,31 @@ hipError_t launch_cwire_apply_multi_stream(const CwaArgs &a, const CwaFrame *rec
     return hipGetLastError();
 }
 
-template <bool CWIRE>
-static void launch_cwc(const CwaArgs &a, const CwcOut &o, int nstreams, int nframes, hipStream_t s) {
-    const dim3 tiles(a.ntiles * (uint32_t)nstreams);
-    if (a.ntiles) hipLaunchKernelGGL(k_cwc_sum, tiles, dim3(64), 0, s, a, nframes);
-    hipLaunchKernelGGL(k_cwc_scan<CWIRE>, dim3(nstreams), dim3(256), 0, s, a, o);
-    hipLaunchKernelGGL(k_cwc_place<CWIRE>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, nstreams);
-    if (a.ntiles) hipLaunchKernelGGL(k_cwc_emit<CWIRE>, tiles, dim3(64), 0, s, a, o, nframes);
+// The tail of every call that writes one segment / record per stream, once the facts of its tiles are made: the coalescer's scan
+// over the facts of `a`, the places of the nsegments segments, then the call's own emit kernel, which emit(form) launches; form is
+// std::integral_constant<bool, CWIRE>, the one place where the runtime cwire becomes the kernels' template argument.
+template <class Emit>
+static void launch_cwc_tail(const CwaArgs &a, const CwcOut &o, int nsegments, bool cwire, hipStream_t s, Emit emit) {
+    const auto tail = [&](auto form) {
+        hipLaunchKernelGGL(k_cwc_scan<decltype(form)::value>, dim3(nsegments), dim3(256), 0, s, a, o);
+        hipLaunchKernelGGL(k_cwc_place<decltype(form)::value>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, nsegments);
+        emit(form);
+    };
+    if (cwire) tail(std::true_type{});
+    else tail(std::false_type{});
 }
 
 hipError_t launch_cwire_coalesce(const CwaArgs &a, const CwaFrame *records, int nstreams, int nframes, const CwcOut &o, bool cwire,
                                  hipStream_t s) {
     if (nstreams <= 0 || nframes <= 0) return hipSuccess;
-    if (a.ntiles) launch_cwa_directory(a, records, nstreams * nframes, s);
-    if (cwire) launch_cwc<true>(a, o, nstreams, nframes, s);
-    else launch_cwc<false>(a, o, nstreams, nframes, s);
+    const dim3 tiles(a.ntiles * (uint32_t)nstreams);
+    if (a.ntiles) {
+        launch_cwa_directory(a, records, nstreams * nframes, s);
+        hipLaunchKernelGGL(k_cwc_sum, tiles, dim3(64), 0, s, a, nframes);
+    }
+    launch_cwc_tail(a, o, nstreams, cwire, s, [&](auto form) {
+        if (a.ntiles) hipLaunchKernelGGL(k_cwc_emit<decltype(form)::value>, tiles, dim3(64), 0, s, a, o, nframes);
+    });
     return hipGetLastError();
 }
 
@@ -2650,9 +2660,9 @@ hipError_t launch_cwire_budget(const CwaArgs &a, const CwaFrame *records, int ns
     }
     hipLaunchKernelGGL(k_cwb_thr, dim3(nstreams), dim3(256), 0, s, hist, thr0, thresholds);
     if (a.ntiles) hipLaunchKernelGGL(k_cwb_facts, tiles, dim3(64), 0, s, a, (const uint32_t *)hist, thr0);
-    hipLaunchKernelGGL(k_cwc_scan<true>, dim3(nstreams), dim3(256), 0, s, a, o);
-    hipLaunchKernelGGL(k_cwc_place<true>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, nstreams);
-    if (a.ntiles) hipLaunchKernelGGL(k_cwb_emit, tiles, dim3(64), 0, s, a, o, (const uint32_t *)hist, thr0);
+    launch_cwc_tail(a, o, nstreams, true, s, [&](auto) {
+        if (a.ntiles) hipLaunchKernelGGL(k_cwb_emit, tiles, dim3(64), 0, s, a, o, (const uint32_t *)hist, thr0);
+    });
     return hipGetLastError();
 }
 
@@ -2674,15 +2684,9 @@ hipError_t launch_cwire_crop(const CwaArgs &a, const CwaFrame *records, int nstr
         }
     }
     const dim3 tiles(a.ntiles * (uint32_t)nstreams);
-    if (cwire) {
-        hipLaunchKernelGGL(k_cwc_scan<true>, dim3(nstreams), dim3(256), 0, s, a, o);
-        hipLaunchKernelGGL(k_cwc_place<true>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, nstreams);
-        if (a.ntiles) hipLaunchKernelGGL(k_crop_emit<true>, tiles, dim3(64), 0, s, a, o, nframes, (const uint32_t *)words, row);
-    } else {
-        hipLaunchKernelGGL(k_cwc_scan<false>, dim3(nstreams), dim3(256), 0, s, a, o);
-        hipLaunchKernelGGL(k_cwc_place<false>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, nstreams);
-        if (a.ntiles) hipLaunchKernelGGL(k_crop_emit<false>, tiles, dim3(64), 0, s, a, o, nframes, (const uint32_t *)words, row);
-    }
+    launch_cwc_tail(a, o, nstreams, cwire, s, [&](auto form) {
+        if (a.ntiles) hipLaunchKernelGGL(k_crop_emit<decltype(form)::value>, tiles, dim3(64), 0, s, a, o, nframes, (const uint32_t *)words, row);
+    });
     return hipGetLastError();
 }
 
@@ -2707,15 +2711,10 @@ hipError_t launch_cwire_mosaic(const CwaArgs &a, const CwaFrame *records, int ns
     ac.ntiles = cwa_tiles(canvas_bytes);
     const dim3 canvas_tiles(ac.ntiles);   // (the canvas' size alone: no count of frames, streams or records sizes this grid)
     hipLaunchKernelGGL(k_mosaic_facts, canvas_tiles, dim3(64), 0, s, a, ns, nframes, (const uint32_t *)words, rs, rc, canvas_bytes);
-    if (cwire) {
-        hipLaunchKernelGGL(k_cwc_scan<true>, dim3(1), dim3(256), 0, s, ac, o);
-        hipLaunchKernelGGL(k_cwc_place<true>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, 1);
-        hipLaunchKernelGGL(k_mosaic_emit<true>, canvas_tiles, dim3(64), 0, s, a, o, ns, nframes, (const uint32_t *)words, rs, rc, canvas_bytes);
-    } else {
-        hipLaunchKernelGGL(k_cwc_scan<false>, dim3(1), dim3(256), 0, s, ac, o);
-        hipLaunchKernelGGL(k_cwc_place<false>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, 1);
-        hipLaunchKernelGGL(k_mosaic_emit<false>, canvas_tiles, dim3(64), 0, s, a, o, ns, nframes, (const uint32_t *)words, rs, rc, canvas_bytes);
-    }
+    launch_cwc_tail(ac, o, 1, cwire, s, [&](auto form) {   // (the facts and the emit see the streams' a)
+        hipLaunchKernelGGL(k_mosaic_emit<decltype(form)::value>, canvas_tiles, dim3(64), 0, s, a, o, ns, nframes, (const uint32_t *)words, rs, rc,
+                           canvas_bytes);
+    });
     return hipGetLastError();
 }
 
@@ -2735,9 +2734,9 @@ hipError_t launch_refresh(const CwaArgs &a, int nstreams, const uint32_t *peer, 
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(k_rf_facts, tiles, dim3(64), 0, s, a, peer, mask, mask_words);
     }
-    hipLaunchKernelGGL(k_cwc_scan<true>, dim3(nstreams), dim3(256), 0, s, a, o);
-    hipLaunchKernelGGL(k_cwc_place<true>, dim3(1), dim3(kCwcPlaceThreads), 0, s, o, nstreams);
-    if (a.ntiles) hipLaunchKernelGGL(k_rf_emit, tiles, dim3(64), 0, s, a, o);
+    launch_cwc_tail(a, o, nstreams, true, s, [&](auto) {
+        if (a.ntiles) hipLaunchKernelGGL(k_rf_emit, tiles, dim3(64), 0, s, a, o);
+    });
     return hipGetLastError();
 }
 
