@@ -142,6 +142,12 @@ public:
                             void *d_wall, int wall_w, int wall_h, size_t wall_pitch);
     void touched_tiles_multi(const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes, int nstreams, int nframes,
                              bool accumulate, void *d_tile_mask);
+    // thumb_cwire_multi: ONE compact record per stream of the thumbnail at scale k (1 .. 16) of each state against the held
+    // thumbnail at d_thumbs + s*thumb_stride (3 * ceil(w / k) * ceil(h / k) bytes), which moves where an entry is written; the
+    // mask as above, over the full-size states; outputs as for the refresh call.  Blocking; nstreams <= MI355_MAX_BATCH.
+    void thumb_cwire_multi(const void *d_states, size_t stride, int nstreams, int k, int threshold, const void *d_tile_mask,
+                           void *d_thumbs, size_t thumb_stride, void *d_offsets, void *d_frame_pos, void *d_cwire_out,
+                           size_t capacity_bytes);
 };
 
 static_assert(sizeof(CUDACore) == 160, "must match the reference's object size (LP64)");

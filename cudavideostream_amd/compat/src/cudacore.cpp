@@ -218,6 +218,14 @@ void CUDACore::touched_tiles_multi(const void *d_cwire, const uint32_t *h_counts
     MI355_CHECK(mi355_synchronize(core_));
 }
 
+void CUDACore::thumb_cwire_multi(const void *d_states, size_t stride, int nstreams, int k, int threshold, const void *d_tile_mask,
+                                 void *d_thumbs, size_t thumb_stride, void *d_offsets, void *d_frame_pos, void *d_cwire_out,
+                                 size_t capacity_bytes) {
+    MI355_CHECK(mi355_thumb_cwire_batch(core_, d_states, stride, nstreams, k, threshold, d_tile_mask, d_thumbs, thumb_stride, d_offsets,
+                                        d_frame_pos, d_cwire_out, capacity_bytes));
+    MI355_CHECK(mi355_synchronize(core_));
+}
+
 size_t CUDACore::chunkt_size() { return 32; }  // sizeof(long4), kernels.cu:27,527-529
 
 void CUDACore::alloc_arrays(uint8_t **h_frame, uint8_t **n_frame, uint8_t **o_frame, int **h_xs, int r,

@@ -605,6 +605,23 @@ class CUDACore:
         _l.check(self._lib.mi355_cwire_touched_tiles_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
                                                            int(nstreams), int(nframes), int(bool(accumulate)), _ptr(d_tile_mask)))
 
+    # ... and the low-resolution viewer behind it: records of the thumbnails, made where the tick's mask says something changed
+    def thumb_cwire_batch(self, d_states, nstreams, k, threshold, d_thumbs, d_offsets, d_frame_pos, d_cwire_out, capacity_bytes,
+                          d_tile_mask=None, stride=None, thumb_stride=None):
+        """ONE compact record per stream of the tw x th thumbnail (scale k in 1 .. 16; wall_thumb_size) of the state at
+        d_states + s*stride against the held thumbnail at d_thumbs + s*thumb_stride (3*tw*th bytes, any alignment): an entry
+        where |new - held| > threshold, and the held byte becomes the new one there.  d_tile_mask (cwire_touched_tiles_batch's
+        or refresh_cwire_batch's, over the full-size state) limits the work to where a selected tile lands; None: everywhere.
+        Offsets, frame positions and capacity as for refresh_cwire_batch; a stream whose record does not fit keeps its held
+        thumbnail.  thumb_cwire_host is the same on the host and the definition."""
+        self._hold(d_states, d_tile_mask, d_thumbs, d_offsets, d_frame_pos, d_cwire_out)
+        stride = self.total if stride is None else stride
+        if thumb_stride is None:
+            thumb_stride = 3 * wall_thumb_size(self.width, self.height, k)[0]
+        _l.check(self._lib.mi355_thumb_cwire_batch(self._h, _ptr(d_states), int(stride), int(nstreams), int(k), int(threshold),
+                                                   _ptr(d_tile_mask), _ptr(d_thumbs), int(thumb_stride), _ptr(d_offsets),
+                                                   _ptr(d_frame_pos), _ptr(d_cwire_out), int(capacity_bytes)))
+
     def wire_bytes(self, nframes, entries):
         return self._lib.mi355_wire_bytes(nframes, entries)
 
@@ -789,6 +806,28 @@ def wall_thumb_size(width, height, k):
     tw, th = C.c_int(0), C.c_int(0)
     pixels = _l.load().mi355_wall_thumb_size(int(width), int(height), int(k), C.byref(tw), C.byref(th))
     return pixels, tw.value, th.value
+
+
+def thumb_cwire_host(state, width, height, k, threshold, thumb, tile_mask=None, capacity_bytes=None):
+    """thumb_cwire_batch for one stream computed on the host (no GPU, no core) and its definition: (record bytes, n, e) of the
+    thumbnail at scale k of the uint8 `state` (3*width*height bytes) against the held thumbnail `thumb` (uint8 numpy array of
+    3*tw*th bytes, updated in place), processing exactly the pixels that tile_mask (uint32 words over the state's tiles; None:
+    every tile) requires.  The record is b"" and thumb stays as it is when it does not fit capacity_bytes (default: always
+    enough); n and e are exact either way."""
+    L = _l.load()
+    state = np.ascontiguousarray(np.frombuffer(state, np.uint8) if isinstance(state, (bytes, bytearray)) else state, dtype=np.uint8)
+    assert isinstance(thumb, np.ndarray) and thumb.dtype == np.uint8 and thumb.flags.c_contiguous
+    assert state.size == 3 * int(width) * int(height) and thumb.size == 3 * wall_thumb_size(width, height, k)[0]
+    mask = None if tile_mask is None else np.ascontiguousarray(tile_mask, dtype=np.uint32)
+    if capacity_bytes is None:
+        capacity_bytes = L.mi355_cwire_bytes_max(thumb.size, 1)
+    out = np.zeros(max(int(capacity_bytes), 1), np.uint8)
+    n, e, nbytes = C.c_uint32(0), C.c_uint32(0), C.c_size_t(0)
+    _l.check(L.mi355_thumb_cwire_host(state.ctypes.data, int(width), int(height), int(k), int(threshold),
+                                      None if mask is None else mask.ctypes.data, thumb.ctypes.data, out.ctypes.data,
+                                      int(capacity_bytes), C.byref(n), C.byref(e), C.byref(nbytes)))
+    fits = nbytes.value <= int(capacity_bytes)
+    return (out[:nbytes.value].tobytes() if fits else b""), n.value, e.value
 
 
 def cwire_apply_host(state, buf, nframes):

@@ -2119,6 +2119,128 @@ int mi355_cwire_touched_tiles_batch(mi355_core *c, const void *d_cwire, const ui
     return MI355_OK;
 }
 
+// ---- records of the thumbnails: a low-resolution viewer served from full-size states (stream_ops.hip, k_thumb_facts) ----------
+// The host form is the definition: exactly the required pixels, two passes over them (the sizes, then the record), the box
+// average recomputed in the second.
+extern "C++" {
+namespace {
+struct ThumbHost {
+    const uint8_t *state;
+    const uint32_t *mask;
+    int64_t w, h, k, tw, th;
+    bool required(int64_t u, int64_t v) const {
+        if (!mask) return true;
+        const int64_t x0 = u * k, x1 = std::min(w, x0 + k);
+        for (int64_t y = v * k; y < std::min(h, (v + 1) * k); y++)
+            for (int64_t t = 3 * (y * w + x0) / kCwaTile; t <= (3 * (y * w + x1) - 1) / kCwaTile; t++) {
+                uint32_t word;
+                memcpy(&word, (const uint8_t *)mask + 4 * (t >> 5), 4);   // (no alignment asked of the mask)
+                if ((word >> (t & 31)) & 1u) return true;
+            }
+        return false;
+    }
+    void pixel(int64_t u, int64_t v, uint8_t bgr[3]) const {
+        const int64_t x0 = u * k, x1 = std::min(w, x0 + k), y0 = v * k, y1 = std::min(h, y0 + k), a = (x1 - x0) * (y1 - y0);
+        int64_t sum[3] = {0, 0, 0};
+        for (int64_t y = y0; y < y1; y++)
+            for (int64_t x = x0; x < x1; x++)
+                for (int c = 0; c < 3; c++) sum[c] += state[3 * (y * w + x) + c];
+        for (int c = 0; c < 3; c++) bgr[c] = (uint8_t)((sum[c] + a / 2) / a);
+    }
+    // op(j, new byte, held byte) for every byte of a required pixel whose difference is above the threshold, j ascending
+    template <class Op>
+    void walk(const uint8_t *thumb, int threshold, Op op) const {
+        for (int64_t v = 0; v < th; v++)
+            for (int64_t u = 0; u < tw; u++) {
+                if (!required(u, v)) continue;
+                uint8_t bgr[3];
+                pixel(u, v, bgr);
+                for (int c = 0; c < 3; c++) {
+                    const int64_t j = 3 * (v * tw + u) + c;
+                    if (std::abs((int)bgr[c] - (int)thumb[j]) > threshold) op((uint32_t)j, bgr[c], thumb[j]);
+                }
+            }
+    }
+};
+}  // namespace
+}  // extern "C++"
+
+int mi355_thumb_cwire_host(const uint8_t *state, int width, int height, int k, int threshold, const uint32_t *tile_mask, uint8_t *thumb,
+                           void *out, size_t capacity_bytes, uint32_t *n, uint32_t *e, size_t *bytes) {
+    if (width < 1 || height < 1) return fail(MI355_ERR_INVALID, "width or height < 1");
+    if (3 * (int64_t)width * height >= (int64_t)1 << 31) return fail(MI355_ERR_INVALID, "3 * width * height >= 2^31");
+    if (k < 1 || k > 16) return fail(MI355_ERR_INVALID, "k outside 1 .. 16");
+    if (threshold < 0 || threshold > 255) return fail(MI355_ERR_INVALID, "threshold outside 0 .. 255");
+    if (!state || !thumb || !n || !e || !bytes) return fail(MI355_ERR_INVALID, "null argument");
+    if (!out && capacity_bytes) return fail(MI355_ERR_INVALID, "null out with capacity_bytes > 0");
+    ThumbHost t{state, tile_mask, width, height, k, (width + k - 1) / k, (height + k - 1) / k};
+    uint32_t cn = 0, ce = 0, end = 0;
+    t.walk(thumb, threshold, [&](uint32_t j, uint8_t, uint8_t) {
+        ce += j - end >= 255u;
+        end = j + 1u;
+        cn++;
+    });
+    const size_t need = (size_t)cwire_record_bytes(cn, ce);
+    *n = cn;
+    *e = ce;
+    *bytes = need;
+    if (need > capacity_bytes) return MI355_OK;   // exact sizes, nothing written: the caller repeats with more room
+    const uint32_t head[2] = {cn, ce};
+    memcpy(out, head, 8);   // (no alignment asked of out)
+    const CwireSections<uint8_t> sec((uint8_t *)out, 0, cn, ce);
+    for (uint32_t i = cn; i < (uint32_t)cwire_pad4(cn); i++) sec.code[i] = sec.diff[i] = 0;
+    uint32_t i = 0, r = 0;
+    end = 0;
+    t.walk(thumb, threshold, [&](uint32_t j, uint8_t nw, uint8_t held) {
+        const uint32_t g = j - end;
+        sec.code[i] = (uint8_t)(g < 255u ? g : 255u);
+        if (g >= 255u) {
+            memcpy(sec.esc + 4 * (size_t)r++, &g, 4);
+        }
+        sec.diff[i++] = (uint8_t)(nw - held);
+        thumb[j] = nw;   // (behind the walk's read of this byte; no later byte depends on it)
+        end = j + 1u;
+    });
+    return MI355_OK;
+}
+
+int mi355_thumb_cwire_batch(mi355_core *c, const void *d_states, size_t state_spacing_bytes, int nstreams, int k, int threshold,
+                            const void *d_tile_mask, void *d_thumbs, size_t thumb_spacing_bytes, void *d_offsets, void *d_frame_pos,
+                            void *d_cwire_out, size_t capacity_bytes) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nstreams < 0 || nstreams > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams outside [0, max_batch]");
+    if (k < 1 || k > 16) return fail(MI355_ERR_INVALID, "k outside 1 .. 16");
+    if (threshold < 0 || threshold > 255) return fail(MI355_ERR_INVALID, "threshold outside 0 .. 255");
+    if (((uintptr_t)d_tile_mask & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_cwire_out & 3u))
+        return fail(MI355_ERR_INVALID, "d_tile_mask, d_offsets and d_cwire_out must be 4-byte aligned");
+    if ((uintptr_t)d_frame_pos & 7u) return fail(MI355_ERR_INVALID, "d_frame_pos must be 8-byte aligned");
+    if (nstreams == 0) return write_empty_heads(c, d_offsets, d_frame_pos);
+    if (!d_states || !d_thumbs) return fail(MI355_ERR_INVALID, "null d_states or d_thumbs");
+    if (!d_offsets || !d_frame_pos || !d_cwire_out) return fail(MI355_ERR_INVALID, "null output pointer");
+    int tw, th;
+    const uint64_t thumb_bytes = 3 * (uint64_t)mi355_wall_thumb_size(c->cfg.width, c->cfg.height, k, &tw, &th);
+    if (state_spacing_bytes < c->n) return fail(MI355_ERR_INVALID, "state_spacing_bytes < frame bytes");
+    if (thumb_spacing_bytes < thumb_bytes) return fail(MI355_ERR_INVALID, "thumb_spacing_bytes < thumbnail bytes");
+    const Region st = resync_states(c, d_states, state_spacing_bytes, nstreams);
+    const Region mk = d_tile_mask ? nowhere(tile_mask_region(c, d_tile_mask, nstreams)) : Region{nullptr, 0, "d_tile_mask"};
+    if (overlap(mk, st)) return overlap_fail(mk, st);
+    if (int rc = check_regions({st, mk},
+                               {nowhere(Region{d_thumbs, thumb_bytes ? (uint64_t)(nstreams - 1) * thumb_spacing_bytes + thumb_bytes : 0,
+                                               "the thumbnails"}),
+                                offsets_region(d_offsets, nstreams), frame_pos_region(d_frame_pos, nstreams),
+                                nowhere(Region{d_cwire_out, capacity_bytes, "d_cwire_out"})},
+                               true))
+        return rc;
+    if (int rc = use_device(c)) return rc;
+    CwaArgs a = cwa_args(c, nullptr);   // (chunk: one fact word per (stream, thumbnail tile), no more than the states' tiles)
+    a.state = (uint8_t *)d_states;      // (only read)
+    a.stride = state_spacing_bytes;
+    HIP_TRY(launch_thumb_cwire(a, nstreams, (uint32_t)c->cfg.width, (uint32_t)c->cfg.height, (uint32_t)k, (uint32_t)threshold,
+                               (const uint32_t *)d_tile_mask, (uint8_t *)d_thumbs, thumb_spacing_bytes,
+                               Produced::records(d_offsets, d_frame_pos, d_cwire_out, capacity_bytes), c->stream));
+    return MI355_OK;
+}
+
 int mi355_int_diff(mi355_core *c, const void *d_cur, const void *d_prev, void *d_out, size_t n) {
     if (!c || (n && (!d_cur || !d_prev || !d_out))) return fail(MI355_ERR_INVALID, "null argument");
     if (int rc = use_device_filter(c)) return rc;

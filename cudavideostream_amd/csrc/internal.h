@@ -299,6 +299,21 @@ hipError_t launch_wall_compose(const uint8_t *states, size_t stride, uint32_t wi
 // |= the tiles that a record of stream s has an entry in; a.state / a.out / a.stride unused
 hipError_t launch_cwire_touched(const CwaArgs &a, const CwaFrame *records, int nstreams, int nframes, bool accumulate, uint32_t *mask,
                                 hipStream_t s);
+// mi355_thumb_cwire_batch: ONE record per stream of the thumbnail at scale k of the width x height state at a.state + s*a.stride
+// (only read) against the held thumbnail at thumbs + s*thumb_stride, which moves where an entry is written.  mask: the states'
+// tile mask or nullptr (every tile).  a.n / a.ntiles: the states'; the kernels get a copy with the thumbnail's, and a.chunk holds
+// one fact word per (stream, thumbnail tile) -- never more than the states' tiles.  o as for the coalescer, compact form.
+struct ThumbArgs {
+    uint8_t *thumbs;
+    size_t thumb_stride;
+    const uint32_t *mask;
+    uint32_t mask_words;
+    uint32_t width, height, k, tw, th, threshold;
+    ActDiv row;       // bytes of a thumbnail row, 3 * tw
+    ActDiv area[4];   // pixels of a block: [2 * (the last row) + (the last column)]
+};
+hipError_t launch_thumb_cwire(const CwaArgs &a, int nstreams, uint32_t width, uint32_t height, uint32_t k, uint32_t threshold,
+                              const uint32_t *mask, uint8_t *thumbs, size_t thumb_stride, const CwcOut &o, hipStream_t s);
 // mi355_cwire_split_cwire_batch: every record cut into pieces of at most max_bytes bytes (include/mi355diff.h, "the piece rule").
 // A block is kCwsBlock entries of one record, kCwsBlock / kCwaChunk chunks of the chunk table; a record of no entries has one
 // empty block, as it has one empty chunk.  blk / base: one word each per block of the call (scratch of the core, cws_blocks(N) per

@@ -2242,6 +2242,71 @@ __device__ __forceinline__ bool wall_band_selected(const uint32_t *mask, uint32_
     return any;
 }
 
+// The band sum, shared by k_wall_compose and the thumbnail records' kernels.  G column groups per thread, `step` bytes apart: bytes
+// [c0 + g * step, + 16) of every row of the band added vertically, sixteen 16-bit sums in byte order per group, w0[g] those of bytes
+// 0 .. 7 and w1[g] of bytes 8 .. 15; the bytes at or past b.cb count as zero.  One 16-byte load per row and group where the row's
+// address allows it, bytes otherwise and at the ragged end.  The rows go R at a time: the R * G loads of a step are issued before
+// the first of them is added (the wall: one group, row by row, its 256 threads and resident workgroups cover the latency; a
+// thumbnail tile's single wave walks its chunks one after the other and needs the loads in flight itself).
+template <int G, int R>
+__device__ __forceinline__ void wall_band_sum16(const WallBand &b, uint32_t c0, uint32_t step, cwa_u32x4 (&w0)[G], cwa_u32x4 (&w1)[G]) {
+    uint32_t ev[G][4], od[G][4], mine[G];   // ev[g][d]: bytes 0 and 2 of dword d, od[g][d]: bytes 1 and 3; mine: the group's bytes
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+        const uint32_t cg = c0 + (uint32_t)g * step;
+        mine[g] = cg < b.cb ? (b.cb - cg < 16u ? b.cb - cg : 16u) : 0u;
+#pragma unroll
+        for (uint32_t d = 0; d < 4u; d++) ev[g][d] = od[g][d] = 0u;
+    }
+    if (mine[0]) {   // (the groups ascend: none behind an empty one)
+        for (uint32_t r0 = 0; r0 < b.kh; r0 += R) {
+            cwa_u32x4 q[R][G];
+#pragma unroll
+            for (int j = 0; j < R; j++) {
+                const uint8_t *row = b.src + (size_t)(r0 + j) * b.pitch;
+                const bool live = R == 1 || r0 + j < b.kh, quads = !((uintptr_t)row & 15u);
+#pragma unroll
+                for (int g = 0; g < G; g++) {
+                    const uint32_t cg = c0 + (uint32_t)g * step;
+                    q[j][g] = cwa_u32x4{0u, 0u, 0u, 0u};
+                    if (live && mine[g] == 16u && quads) {
+                        q[j][g] = *(const cwa_u32x4 *)(row + cg);
+                    } else if (live && mine[g]) {
+#pragma unroll
+                        for (uint32_t i = 0; i < 16u; i++)
+                            if (i < mine[g]) q[j][g][i / 4u] |= (uint32_t)row[cg + i] << (8u * (i % 4u));
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < R; j++)
+#pragma unroll
+                for (int g = 0; g < G; g++)
+#pragma unroll
+                    for (uint32_t d = 0; d < 4u; d++) {
+                        ev[g][d] += q[j][g][d] & 0x00FF00FFu;
+                        od[g][d] += (q[j][g][d] >> 8) & 0x00FF00FFu;
+                    }
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < G; g++)
+#pragma unroll
+        for (uint32_t d = 0; d < 2u; d++) {
+            w0[g][2u * d] = (ev[g][d] & 0xFFFFu) | (od[g][d] << 16);
+            w0[g][2u * d + 1u] = (ev[g][d] >> 16) | (od[g][d] & 0xFFFF0000u);
+            w1[g][2u * d] = (ev[g][d + 2u] & 0xFFFFu) | (od[g][d + 2u] << 16);
+            w1[g][2u * d + 1u] = (ev[g][d + 2u] >> 16) | (od[g][d + 2u] & 0xFFFF0000u);
+        }
+}
+
+// Channel c of pixel u of the chunk whose column sums lie in s_sum: the sum of its kw entries at a 3-entry pitch
+__device__ __forceinline__ uint32_t wall_box_sum(const uint16_t *s_sum, uint32_t u, uint32_t c, uint32_t k, uint32_t kw) {
+    uint32_t sum = 0;
+    for (uint32_t i = 0; i < kw; i++) sum += s_sum[3u * (u * k + i) + c];
+    return sum;
+}
+
 __global__ __launch_bounds__(256) void k_wall_compose(const uint8_t *states, size_t stride, uint32_t width, uint32_t height,
                                                       const uint32_t *mask, uint32_t mask_words, uint8_t *wall, size_t wall_pitch,
                                                       const WallPlaceArgs h) {
@@ -2264,38 +2329,10 @@ __global__ __launch_bounds__(256) void k_wall_compose(const uint8_t *states, siz
     b.src = states + (size_t)st * stride + off;
     if (mask && !wall_band_selected(mask + (size_t)st * mask_words, off, b)) return;   // (the same for every thread)
 
-    // vertical sums of the thread's 16 bytes: ev[d] holds bytes 0 and 2 of dword d, od[d] bytes 1 and 3
-    uint32_t ev[4] = {0u, 0u, 0u, 0u}, od[4] = {0u, 0u, 0u, 0u};
-    const uint32_t c0 = 16u * tid;
-    if (c0 < b.cb) {
-        const uint32_t mine = b.cb - c0 < 16u ? b.cb - c0 : 16u;
-        for (uint32_t r = 0; r < b.kh; r++) {
-            const uint8_t *row = b.src + (size_t)r * b.pitch;
-            cwa_u32x4 q = {0u, 0u, 0u, 0u};
-            if (mine == 16u && !((uintptr_t)row & 15u)) {
-                q = *(const cwa_u32x4 *)(row + c0);
-            } else {
-#pragma unroll
-                for (uint32_t i = 0; i < 16u; i++)
-                    if (i < mine) q[i / 4u] |= (uint32_t)row[c0 + i] << (8u * (i % 4u));
-            }
-#pragma unroll
-            for (uint32_t d = 0; d < 4u; d++) {
-                ev[d] += q[d] & 0x00FF00FFu;
-                od[d] += (q[d] >> 8) & 0x00FF00FFu;
-            }
-        }
-    }
-    cwa_u32x4 w0, w1;   // sums of bytes 0 .. 7 and 8 .. 15, in byte order
-#pragma unroll
-    for (uint32_t d = 0; d < 2u; d++) {
-        w0[2u * d] = (ev[d] & 0xFFFFu) | (od[d] << 16);
-        w0[2u * d + 1u] = (ev[d] >> 16) | (od[d] & 0xFFFF0000u);
-        w1[2u * d] = (ev[d + 2u] & 0xFFFFu) | (od[d + 2u] << 16);
-        w1[2u * d + 1u] = (ev[d + 2u] >> 16) | (od[d + 2u] & 0xFFFF0000u);
-    }
-    s_sum32[2u * tid] = w0;
-    s_sum32[2u * tid + 1u] = w1;
+    cwa_u32x4 w0[1], w1[1];
+    wall_band_sum16<1, 1>(b, 16u * tid, 0u, w0, w1);
+    s_sum32[2u * tid] = w0[0];
+    s_sum32[2u * tid + 1u] = w1[0];
     __syncthreads();
 
     const uint16_t *s_sum = (const uint16_t *)s_sum32;
@@ -2304,8 +2341,7 @@ __global__ __launch_bounds__(256) void k_wall_compose(const uint8_t *states, siz
         const uint32_t u = o / 3u, c = o - 3u * u;
         const uint32_t left = width - (u0 + u) * k, kw = left < k ? left : k;
         const uint32_t a = kw * b.kh;
-        uint32_t sum = 0;
-        for (uint32_t i = 0; i < kw; i++) sum += s_sum[3u * (u * k + i) + c];
+        const uint32_t sum = wall_box_sum(s_sum, u, c, k, kw);
         out[o] = (uint8_t)(a == 1u ? sum : (sum + a / 2u) / a);
     }
 }
@@ -2331,6 +2367,119 @@ __global__ __launch_bounds__(64) void k_cw_touched(const CwaArgs a, int nframes,
         row[w] = (accumulate ? row[w] : 0u) | (uint32_t)set;
         if (w + 1u < mask_words) row[w + 1u] = (accumulate ? row[w + 1u] : 0u) | (uint32_t)(set >> 32);
     }
+}
+
+// ---- mi355_thumb_cwire_batch: records of the thumbnails, from the states as a tick left them (include/mi355diff.h) -------------
+// The tile grid runs over the THUMBNAIL (N' = 3 * tw * th bytes, cwa_tiles(N') tiles per stream): what is written -- the record
+// and the held thumbnail -- is the thumbnail's, so a tile of it is the unit that owns its held bytes, its fact word and its place
+// in the record, exactly as a tile of the state is in the refresh call.
+//   k_thumb_facts (grid: thumbnail tiles x streams, one wave) : the tile is a run of (row, byte range) pieces, each cut along
+//       the wall's chunks of its row (wall_chunk_pixels: a chunk's band is at most kWallBytes source bytes per row and keeps its
+//       row's 16-byte alignment).  A chunk whose band meets no selected tile (wall_band_selected) is skipped before a state byte
+//       moves; of a selected one the column sums go to LDS (wall_band_sum16: four 16-byte columns per lane, four rows at a
+//       time, sixteen loads in flight) and the chunk's output bytes INSIDE the piece are made as k_wall_compose makes them
+//       (wall_box_sum, then the rounding divide by act_div).
+//       The held bytes of the tile lie in LDS (cwa_tile_load); where |new - held| > threshold the difference byte goes to the
+//       tile of differences and `new` replaces the held byte in LDS, everywhere else the difference is zero.  cwc_tile_facts of
+//       that tile; a tile with no selected chunk stores the all-zero fact.
+//   k_cwc_scan<true>, k_cwc_place<true>                       : the coalescer's, on cwa_tiles(N') tiles per stream
+//   k_thumb_emit  (grid: the same)                            : returns on a zero fact or a record that does not fit; builds the
+//       same tile from the same bytes, stores the LDS copy of the held tile where a difference was set (whole dwords inside the
+//       tile where the address allows, bytes otherwise) and writes the entries (cwc_emit_tile).  The only pass that writes the
+//       held thumbnail and the last that reads it; a workgroup touches no thumbnail byte outside its own tile.
+// LDS reads of the horizontal sum are 16-bit at a 3-entry pitch, k entries apart between neighbouring pixels, as in the wall.
+__device__ __forceinline__ bool thumb_tile(uint8_t *s, uint8_t *s_held, cwa_u32x4 *s_sum32, const CwaArgs &a, const ThumbArgs &h,
+                                           uint32_t st, uint32_t lo, uint32_t len, int lane) {
+    const uint32_t k = h.k, rb = h.row.d, hi = lo + len;
+    const uint32_t cp = wall_chunk_pixels(h.tw, k);
+    const uint8_t *state = a.state + (size_t)st * a.stride;
+    const uint32_t *mask = h.mask ? h.mask + (size_t)st * h.mask_words : nullptr;
+    const uint16_t *s_sum = (const uint16_t *)s_sum32;
+    for (uint32_t i = lane; i < kCwaTile / 16; i += 64) ((cwa_u32x4 *)s)[i] = cwa_u32x4{0u, 0u, 0u, 0u};
+    cwa_tile_load(s_held, h.thumbs + (size_t)st * h.thumb_stride + lo, len, lane);
+    __syncthreads();
+    bool any = false;   // (the same for every lane, as is every branch around a barrier below)
+    const uint32_t v1 = act_div(hi - 1u, h.row);
+    for (uint32_t v = act_div(lo, h.row); v <= v1; v++) {
+        const uint32_t r0 = v * rb;                                                      // the row's first thumbnail byte
+        const uint32_t j0 = lo > r0 ? lo : r0, j1 = hi < r0 + rb ? hi : r0 + rb;         // the piece
+        WallBand b;
+        b.pitch = 3u * h.width;
+        b.kh = h.height - v * k < k ? h.height - v * k : k;
+        for (uint32_t cu0 = (j0 - r0) / 3u / cp * cp; 3u * cu0 < j1 - r0; cu0 += cp) {   // the row's chunks that the piece meets
+            const uint32_t cw = h.tw - cu0 < cp ? h.tw - cu0 : cp;
+            const uint32_t x1 = (cu0 + cw) * k < h.width ? (cu0 + cw) * k : h.width;
+            b.cb = 3u * (x1 - cu0 * k);
+            const uint32_t off = v * k * b.pitch + 3u * cu0 * k;
+            b.src = state + off;
+            if (mask && !wall_band_selected(mask, off, b)) continue;
+            if (any) __syncthreads();   // the sums of the chunk before are read
+            any = true;
+            constexpr int kGroups = kWallBytes / 1024u;   // a lane's column groups, 1024 bytes apart: a wave's load is one piece
+            cwa_u32x4 w0[kGroups], w1[kGroups];
+            wall_band_sum16<kGroups, 4>(b, 16u * lane, 1024u, w0, w1);
+#pragma unroll
+            for (int g = 0; g < kGroups; g++) {
+                const uint32_t q = 64u * g + lane;
+                if (16u * q >= b.cb) continue;
+                s_sum32[2u * q] = w0[g];
+                s_sum32[2u * q + 1u] = w1[g];
+            }
+            __syncthreads();
+            const uint32_t c0 = r0 + 3u * cu0, c1 = c0 + 3u * cw;   // the chunk's thumbnail bytes, cut to the piece
+            const uint32_t o0 = j0 > c0 ? j0 : c0, o1 = j1 < c1 ? j1 : c1;
+            for (uint32_t j = o0 + lane; j < o1; j += 64) {
+                const uint32_t col = j - r0, u = col / 3u, c = col - 3u * u;
+                const uint32_t left = h.width - u * k, kw = left < k ? left : k;
+                const ActDiv area = h.area[(v + 1u == h.th ? 2u : 0u) + (u + 1u == h.tw ? 1u : 0u)];
+                const uint32_t nw = act_div(wall_box_sum(s_sum, u - cu0, c, k, kw) + area.d / 2u, area);
+                const uint32_t old = s_held[j - lo];
+                const uint32_t mag = nw > old ? nw - old : old - nw;
+                if (mag > h.threshold) {
+                    s[j - lo] = (uint8_t)(nw - old);
+                    s_held[j - lo] = (uint8_t)nw;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    return any;
+}
+
+__global__ __launch_bounds__(64) void k_thumb_facts(const CwaArgs a, const ThumbArgs h) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16], s_h[kCwaTile / 16], s_sum32[kWallBytes / 8];
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    uint4 f = make_uint4(0u, 0u, 0u, 0u);
+    if (thumb_tile((uint8_t *)s_q, (uint8_t *)s_h, s_sum32, a, h, st, lo, len, lane)) f = cwc_tile_facts((const uint8_t *)s_q, lo, lane);
+    if (lane == 0) a.chunk[(size_t)st * a.ntiles + tile] = f;
+}
+
+__global__ __launch_bounds__(64) void k_thumb_emit(const CwaArgs a, const ThumbArgs h, const CwcOut o) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16], s_h[kCwaTile / 16], s_sum32[kWallBytes / 8];
+    __shared__ uint32_t s_code32[kCwaTile / 4 + 2], s_diff32[kCwaTile / 4 + 2];
+    const uint8_t *s = (const uint8_t *)s_q, *s_held = (const uint8_t *)s_h;
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
+    const uint4 fact = a.chunk[(size_t)st * a.ntiles + tile];   // {nonzero bytes, entries before, escapes before, end before}
+    if (fact.x == 0) return;   // no selected chunk, or no difference above the threshold
+    const uint32_t seg = o.offsets[st], n = o.offsets[st + 1] - seg;
+    const uint64_t fp0 = o.frame_pos[st], fp1 = o.frame_pos[st + 1];
+    if (fp1 > o.capacity) return;   // the record does not fit: skipped whole, and the stream's held thumbnail stays as it is
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    thumb_tile((uint8_t *)s_q, (uint8_t *)s_h, s_sum32, a, h, st, lo, len, lane);
+    // the held thumbnail at the emitted bytes: a dword that holds one is stored whole (its other bytes are the held ones, read
+    // by this workgroup alone), [0, len) only
+    uint8_t *dst = h.thumbs + (size_t)st * h.thumb_stride + lo;
+    const uint32_t q = ((uintptr_t)dst & 3u) ? 0u : len / 4u;
+    for (uint32_t i = lane; i < q; i += 64)
+        if (((const uint32_t *)s)[i]) ((uint32_t *)dst)[i] = ((const uint32_t *)s_held)[i];
+    for (uint32_t i = 4u * q + lane; i < len; i += 64)
+        if (s[i]) dst[i] = s_held[i];
+    cwc_emit_tile<true>(s, (uint8_t *)s_code32, (uint8_t *)s_diff32, fact, o, seg, n, fp0, cwire_record_escapes(fp1 - fp0, n), lo, lane);
 }
 
 // ---- mi355_cwire_split_cwire_batch: every record cut into pieces of at most max_bytes bytes (include/mi355diff.h) -----------------
@@ -2779,6 +2928,36 @@ hipError_t launch_cwire_touched(const CwaArgs &a, const CwaFrame *records, int n
     launch_cwa_directory(a, records, nstreams * nframes, s);
     hipLaunchKernelGGL(k_cw_touched, dim3((a.ntiles + 63u) / 64u * (uint32_t)nstreams), dim3(64), 0, s, a, nframes, accumulate ? 1 : 0, mask,
                        cwa_mask_words(a.n));
+    return hipGetLastError();
+}
+
+hipError_t launch_thumb_cwire(const CwaArgs &a, int nstreams, uint32_t width, uint32_t height, uint32_t k, uint32_t threshold,
+                              const uint32_t *mask, uint8_t *thumbs, size_t thumb_stride, const CwcOut &o, hipStream_t s) {
+    if (nstreams <= 0) return hipSuccess;
+    ThumbArgs h{};
+    h.thumbs = thumbs;
+    h.thumb_stride = thumb_stride;
+    h.mask = mask;
+    h.mask_words = cwa_mask_words(a.n);
+    h.width = width;
+    h.height = height;
+    h.k = k;
+    h.tw = (width + k - 1u) / k;
+    h.th = (height + k - 1u) / k;
+    h.threshold = threshold;
+    CwaArgs at = a;   // the facts, the scan and the emit see the thumbnail's bytes and tiles; a.state / a.stride stay the states'
+    at.n = 3u * h.tw * h.th;
+    at.ntiles = cwa_tiles(at.n);
+    if (at.ntiles) {   // (frames of no bytes have thumbnails of none: empty records)
+        h.row = act_divisor(3u * h.tw);
+        const uint32_t kw[2] = {k, width - (h.tw - 1u) * k}, kh[2] = {k, height - (h.th - 1u) * k};
+        for (int i = 0; i < 4; i++) h.area[i] = act_divisor(kh[i >> 1] * kw[i & 1]);
+    }
+    const dim3 thumb_tiles(at.ntiles * (uint32_t)nstreams);   // (a wave per thumbnail tile and stream: one launch, no rounds)
+    if (at.ntiles) hipLaunchKernelGGL(k_thumb_facts, thumb_tiles, dim3(64), 0, s, at, h);
+    launch_cwc_tail(at, o, nstreams, true, s, [&](auto) {
+        if (at.ntiles) hipLaunchKernelGGL(k_thumb_emit, thumb_tiles, dim3(64), 0, s, at, h, o);
+    });
     return hipGetLastError();
 }
 

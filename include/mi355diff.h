@@ -98,7 +98,8 @@ typedef struct mi355_config {
  *      + mi355_cwire_mosaic_batch, mi355_cwire_mosaic_cwire_batch (additions only);
  *      + mi355_diff_consecutive_batch (additions only);
  *      + mi355_cwire_split_host, mi355_cwire_split_cwire_batch, mi355_cwire_split_pieces_max, mi355_cwire_split_bytes_max,
- *      MI355_CWIRE_SPLIT_BLOCK (additions only) */
+ *      MI355_CWIRE_SPLIT_BLOCK (additions only);
+ *      + mi355_thumb_cwire_host, mi355_thumb_cwire_batch (additions only) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -1162,6 +1163,96 @@ int mi355_wall_compose_batch(mi355_core *core, const void *d_states, size_t stri
                              void *d_wall, int wall_w, int wall_h, size_t wall_pitch);
 int mi355_cwire_touched_tiles_batch(mi355_core *core, const void *d_cwire, const uint32_t *h_counts, const uint32_t *h_escapes,
                                     int nstreams, int nframes, int accumulate, void *d_tile_mask /* uint32[nstreams][mask_words] */);
+
+/* ---- Thumbnail records: a low-resolution viewer served from full-size states ------------------------------------------------------
+ * The node that the wall is not: a REMOTE receiver that wants a camera at 1/k size.  Box averaging with rounding does not commute
+ * with state[x] += diff (mod 256), so records cannot be downscaled without state the way they are cropped or placed; this call
+ * keeps that state where mi355_diff_multi_* keeps its states -- in the caller's memory -- and does work only where the tick's tile
+ * mask says something changed.  Its output is one ordinary compact record per stream of a tw x th frame: mi355_cwire_apply_host,
+ * mi355_apply_multi_cwire_batch, mi355_cwire_mosaic_* (sixteen thumbnails as ONE canvas record), mi355_cwire_split_*,
+ * mi355_cwire_check_* and the coalescer take it unchanged.  All integers, every comparison exact.
+ *   Geometry and value are the wall's: tw = ceil(width / k), th = ceil(height / k), N' = 3*tw*th, k in 1 .. 16
+ *   (mi355_wall_thumb_size), value = floor((sum of the block's channel-c bytes + floor(a / 2)) / a).  thumbnail(A) is the N'-byte
+ *   BGR24 thumbnail of an N-byte state A.
+ *   state_spacing_bytes and thumb_spacing_bytes are the bytes from one stream's state, or held thumbnail, to the next stream's:
+ *   what the other calls name stride_bytes, with its rules ("Strides and pitches" above: any value >= the window's bytes, the
+ *   products in 64 bits), and any alignment.
+ *   Inputs of stream s: the state at d_states + s*state_spacing_bytes (only read); the HELD THUMBNAIL at d_thumbs +
+ *   s*thumb_spacing_bytes, N' bytes, any alignment, read and written -- the frame this stream's low-resolution viewer has
+ *   reconstructed; d_tile_mask, NULL for every tile or uint32[nstreams][mask_words] over the FULL-SIZE state's 4096-byte tiles,
+ *   the object mi355_cwire_touched_tiles_batch and mi355_refresh_cwire_batch write (bits at or past tiles are ignored);
+ *   threshold in 0 .. 255.
+ *   A thumbnail pixel is REQUIRED by the wall's rule: its block contains a source pixel p whose bytes [3p, 3p + 3) meet a
+ *   selected tile (a pixel that straddles a tile edge belongs to both tiles).  The call processes every required pixel and MAY
+ *   process any other byte of the same stream's thumbnail (whole chunks, as the masked compose).  For every processed byte j:
+ *   new = thumbnail(state_s)[j], old = thumbs_s[j], df = new - old as integers; if |df| > threshold the entry (j, (uint8)df)
+ *   belongs to record s and thumbs_s[j] = new; otherwise nothing happens at j and the difference stays pending, as in the diff's
+ *   negative feedback.  threshold == 0 makes the held thumbnail an exact mirror (the relay's setting).
+ *   Outputs are those of mi355_refresh_cwire_batch: d_offsets uint32[nstreams + 1], d_frame_pos uint64[nstreams + 1] (always
+ *   exact), record s at d_cwire_out + d_frame_pos[s], the canonical encoding of its entries in ascending j (headers written, pad
+ *   bytes zero, byte for byte what mi355_cwire_encode_batch writes).  A record with d_frame_pos[s + 1] > capacity_bytes is skipped
+ *   whole AND ITS STREAM'S HELD THUMBNAIL IS NOT WRITTEN AT ALL: the viewer did not get the record, so the caller's model of the
+ *   viewer does not move; the caller repeats the call with more room and the same mask.  Records behind a skipped one that fit
+ *   are written.  mi355_cwire_bytes_max(N', nstreams) always suffices.
+ *   Laws:
+ *   1. Always: applying output record s to a copy of the held thumbnail as it was before the call gives the held thumbnail as it
+ *      is after the call -- any input, any mask, whichever extra bytes were processed.
+ *   2. Always: after the call every byte of a required pixel has thumbs[j] == thumbnail(state)[j], or |thumbnail(state)[j] - old|
+ *      <= threshold and thumbs[j] == old; any other byte is untouched or satisfies the same.
+ *   3. Under the invariant "outside the required pixels |thumbnail(state) - thumbs| <= threshold everywhere" (it holds when this
+ *      call has maintained the thumbnails with one threshold and the masks covered every change of the states) the output is
+ *      unique: byte for byte the host form's, and byte for byte what mi355_diff_multi_cwire_batch of a core of geometry tw x th
+ *      with that threshold writes from the frames thumbnail(state_s) and the states thumbs_s; held thumbnails and frame
+ *      positions match too.
+ *   4. The chain property, next to the wall's: if thumbs == thumbnail(states) before a tick and threshold == 0, then the tick
+ *      (mi355_diff_multi_cwire_batch on a sender, mi355_apply_multi_stream_cwire_batch on a relay),
+ *      mi355_cwire_touched_tiles_batch of the same records and this call, with no wait between the three, leave
+ *      thumbs == thumbnail(states); a viewer that applies the records holds the same bytes.
+ *   5. Key record: a NULL mask with a zeroed held thumbnail and threshold == 0 yields (j, thumbnail[j]) for every nonzero byte,
+ *      the refresh record of the thumbnail: a late joiner's first record and the repair after a lost one (the viewer clears its
+ *      state, the caller zeroes thumbs_s, one call with a NULL mask follows).
+ *   6. k == 1: the thumbnail is the state; with a zeroed held thumbnail, a NULL mask and threshold == 0 the records equal those of
+ *      mi355_refresh_cwire_batch(d_peer_digests = NULL) byte for byte.
+ *   Refused with MI355_ERR_INVALID before anything is launched or written: a null core; nstreams outside [0, max_batch]; k outside
+ *   1 .. 16; threshold outside 0 .. 255; with nstreams > 0 a null pointer other than d_tile_mask, state_spacing_bytes < N,
+ *   thumb_spacing_bytes < N'; d_tile_mask, d_offsets or d_cwire_out not 4-byte aligned; d_frame_pos not 8-byte aligned; any two of
+ *   these regions overlapping: the states' region, the thumbnails' region [d_thumbs, + (nstreams - 1)*thumb_spacing_bytes + N'),
+ *   the mask, the offsets, the frame positions, [d_cwire_out, + capacity_bytes).  nstreams == 0 writes offsets[0] = 0 and
+ *   frame_pos[0] = 0 and nothing else.  Bytes of the thumbnails' region outside each stream's N' bytes are never written, the
+ *   stride gap included; the states and the core's own state are never written; nothing is allocated.  Asynchronous on the core's
+ *   stream, in call order behind a tick, an apply, a clear or a touched-tiles call on the same core, with no synchronisation.
+ *   One k and one threshold per call: a ladder (full, 1/2, 1/4) is one call per rung, each rung with its own held thumbnails.
+ * mi355_thumb_cwire_host is the definition: plain C++, no core, no HIP call, no alignment demands.  It processes EXACTLY the
+ * required pixels of one state; *n, *e and *bytes (the record's entries, escapes and size) are always exact; the record and the
+ * thumbnail are written only if the record fits capacity_bytes.  Refused, with outputs untouched: a null state, thumb, n, e or
+ * bytes; a null out when capacity_bytes > 0; width or height < 1; 3*width*height >= 2^31; k or threshold out of range.
+ *   Kernels: k_thumb_facts and k_thumb_emit around the coalescer's scan and place, the shape of the refresh call.  The grid runs
+ *   over the tiles of the THUMBNAIL (4096 consecutive thumbnail bytes: several short rows, or part of a long one), one wave per
+ *   tile and stream.  A tile's rows are cut along the wall's chunks; a chunk whose source band meets no selected tile is skipped
+ *   before a state byte moves, a selected one is box-averaged with the wall's band sum (16-byte loads where the row's address
+ *   allows, 16-bit vertical sums, the horizontal sum through LDS at a 3-entry pitch, the rounding divide by multiply-and-correct).
+ *   The emit pass rebuilds the same tile from the same bytes; it is the only pass that writes the held thumbnail (at the emitted
+ *   bytes) and the last that reads it, and no workgroup touches another tile's thumbnail bytes.
+ * Measured: profiles/multi_thumb.json (tools/bench_multi.py --legs thumb --streams 4,16,64; microseconds per stream, 1080p,
+ * k = 2, 4, 8, threshold 0, median of five rounds, spreads up to 10 % at S = 4 and below 5 % above, one run on one board; every
+ * pass finds the held thumbnails one tick behind).  The route a caller had before -- touched tiles, the masked
+ * mi355_wall_compose_batch into a scratch wall, a synchronise, mi355_diff_multi_cwire_batch on a threshold-0 core of the
+ * thumbnail's geometry -- wrote the same records at all 18 points.  Both expectations were MISSED.  Touched tiles plus this call
+ * take 30.7 / 34.8 / 59.0 us per stream at S = 4 (k = 2 / 4 / 8, webcam-like tick), 21.2 / 10.4 / 15.7 at S = 16 and
+ * 19.8 / 8.53 / 5.71 at S = 64 against 41.5 / 41.7 / 35.7, 17.1 / 15.1 / 13.0 and 11.0 / 8.50 / 7.75 for the route; on the moving
+ * block 29.7 / 36.4 / 60.7, 9.88 / 10.2 / 15.8 and 6.63 / 4.33 / 4.37 against 41.2 / 41.3 / 40.9, 15.5 / 14.4 / 13.9 and
+ * 8.37 / 7.01 / 6.42: no slower than the route at 12 of 18 points (0.62 to 1.00 times), slower at k = 8 for S = 4 and 16 (1.14
+ * to 1.65 times: 24 tiles per stream, the call lasts as long as one tile's single wave) and on the webcam-like tick at k = 2 for
+ * S = 16 and 64 (1.24 and 1.80: a record as long as the thumbnail, bounded by the byte-serial emit).  The call alone with the
+ * moving block's mask (367 of 1519 tiles) against no mask: cheaper at k = 2 for every S (0.95, 0.68, 0.61 times) and at k = 4 for
+ * S = 64 (0.76), not cheaper at k = 4 for S = 4 and 16 and at k = 8 (1.01 to 1.15 times).  DESIGN.md says what bounds both.
+ * DESIGN.md section 4, "Records of the thumbnails". */
+int mi355_thumb_cwire_host(const uint8_t *state, int width, int height, int k, int threshold,
+                           const uint32_t *tile_mask /* or NULL: every tile */, uint8_t *thumb /* N' bytes, in and out */,
+                           void *out, size_t capacity_bytes, uint32_t *n, uint32_t *e, size_t *bytes);
+int mi355_thumb_cwire_batch(mi355_core *core, const void *d_states, size_t state_spacing_bytes, int nstreams, int k, int threshold,
+                            const void *d_tile_mask /* or NULL: every tile */, void *d_thumbs, size_t thumb_spacing_bytes,
+                            void *d_offsets, void *d_frame_pos, void *d_cwire_out, size_t capacity_bytes);
 
 /* Integer difference of tests/algorithms_benchmarks.cu:24-30 (kernel1): d[i] = cur[i] - prev[i] on
  * int32 arrays of n elements, no threshold, no pack. */

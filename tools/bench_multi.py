@@ -130,6 +130,20 @@ of ceil(sqrt(S)) columns:
 The expectations to test: `masked_local` cheaper than `full` at every k and S by more than the rounds' spread, and `full_k8` no
 slower than `digest` by more than the spread (`verdict`).  The other figures are reported, not judged.
 
+The thumb leg (--legs thumb, a run of its own: `--legs thumb --streams 4,16,64 > profiles/multi_thumb.json`) measures the call that
+serves a low-resolution viewer, mi355_thumb_cwire_batch at threshold 0, in microseconds per stream, ONE JSON line for all S, at the
+scales k = 2, 4 and 8, on ONE tick of the webcam-like and of the local (moving block) input.  Every pass alternates between the
+states before and after that tick, so the held thumbnails are always one tick behind:
+  touched_plus_call_*  mi355_cwire_touched_tiles_batch of the tick's records plus the call with that mask;
+  call_*               the call alone, the mask given;
+  call_nullmask_*      the call without a mask;
+  route_*              what a caller had before: touched tiles, the masked mi355_wall_compose_batch into a scratch wall, a
+                       synchronize (another core), mi355_diff_multi_cwire_batch on a threshold-0 core of the thumbnail's geometry.
+                       Its records, frame positions and states are asserted equal to the call's at every point before anything
+                       is timed.
+The expectations to test: `touched_plus_call` no slower than `route` at any point by more than the rounds' spread, and `call_local`
+cheaper than `call_nullmask_local` (`verdict`).
+
 Input of the other legs: ONE webcam stream of S + K + 1 frames; stream s shows frame s + j at step j, so every tick of every stream is the
 step between two consecutive webcam frames, and a tick's S frames are one contiguous region.  j walks 1 .. K and back."""
 import argparse
@@ -949,6 +963,158 @@ def run_wall(W, H, S, rounds, scales=(2, 4, 8)):
     return out
 
 
+def run_thumb(W, H, S, rounds, scales=(2, 4, 8)):
+    """The thumb leg for one S -> its dictionary.  Every leg alternates between the states before and after ONE tick (A, B, A, ..)
+    with the tick's tile mask, so every pass finds the held thumbnails one tick behind and does a tick's work; the route's
+    thumbnail-core states follow in the same way.  All legs alternate within every round."""
+    import numpy as np
+    from cudavideostream_amd import CUDACore, cwire_bytes_max, state_tiles, wall_thumb_size
+    dev = torch.device("cuda", 0)
+    n = 3 * W * H
+    mask_words = (state_tiles(n) + 31) // 32
+    passes = 2 * max(1, min(8, 64 // S))
+    cwcap = cwire_bytes_max(n, S)
+    d_off = torch.zeros(S + 1, dtype=torch.int32, device=dev)
+    d_pos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
+    d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
+    d_mask = torch.zeros(S * mask_words, dtype=torch.int32, device=dev)
+    core = CUDACore(W, H, max_batch=S)
+    ticks = {}
+    for kind in ("webcam", "local"):
+        if kind == "webcam":
+            _, web = synth.webcam_stream(S + 1, W, H, device=dev)
+            web = web.reshape(S + 1, n)
+            before, frames = web[:S].clone(), web[1:].clone()
+        else:
+            before, fwd = local_streams(S, 1, W, H, dev)
+            frames = fwd[:, 0].contiguous()
+        after = before.clone()
+        torch.cuda.synchronize()
+        core.diff_multi_cwire_batch(frames, after, S, d_off, d_pos, d_cw, cwcap)
+        core.synchronize()
+        pos = d_pos.cpu().numpy().astype(np.int64)
+        counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
+        escapes = ((np.diff(pos) - 8 - 2 * ((counts.astype(np.int64) + 3) & ~3)) // 4).astype(np.uint32)
+        d_kind_mask = torch.zeros_like(d_mask)
+        core.cwire_touched_tiles_batch(d_cw, counts, escapes, S, 1, d_kind_mask)
+        core.synchronize()
+        touched = int(sum(bin(int(v) & 0xFFFFFFFF).count("1") for v in d_kind_mask.cpu().numpy()))
+        ticks[kind] = ((before, after), d_cw[:int(pos[S])].clone(), counts, escapes, d_kind_mask, touched)
+        del frames
+    geo = {}
+    for k in scales:
+        _, tw, th = wall_thumb_size(W, H, k)
+        nt = 3 * tw * th
+        cap = cwire_bytes_max(nt, S)
+        geo[k] = dict(tw=tw, th=th, nt=nt, cap=cap, small=CUDACore(tw, th, threshold=0, max_batch=S),
+                      place=np.array([(0, s * th, k) for s in range(S)], np.int32),
+                      wall=torch.zeros(S * nt, dtype=torch.uint8, device=dev),
+                      out=[(torch.zeros(S + 1, dtype=torch.int32, device=dev), torch.zeros(S + 1, dtype=torch.int64, device=dev),
+                            torch.empty(cap, dtype=torch.uint8, device=dev)) for _ in range(2)])
+
+    def thumbs_of(states, k):
+        """The thumbnails of the states, by the call itself from zeroed held thumbnails (a key record)."""
+        g = geo[k]
+        d = torch.zeros(S * g["nt"], dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        core.thumb_cwire_batch(states, S, k, 0, d, *g["out"][0], g["cap"])
+        core.synchronize()
+        return d
+
+    def call(k, states, held, mask, out):
+        core.thumb_cwire_batch(states, S, k, 0, held, *out, geo[k]["cap"], d_tile_mask=mask)
+
+    def route(k, states, held, mask, out):
+        g = geo[k]
+        core.wall_compose_batch(states, S, g["place"], g["wall"], g["tw"], S * g["th"], d_tile_mask=mask)
+        core.synchronize()                                  # (another core, another stream)
+        g["small"].diff_multi_cwire_batch(g["wall"], held, S, *out, g["cap"])
+
+    table, checked = {}, 0
+    for kind in ("webcam", "local"):
+        (A, B), recs, counts, escapes, kmask, _ = ticks[kind]
+        for k in scales:
+            g = geo[k]
+            held = {name: thumbs_of(A, k) for name in ("touched", "masked", "null", "route")}
+            g["wall"].copy_(held["route"])                  # the scratch wall begins as the full composition, as a caller's would
+            # ---- the records of the tick A -> B: the call's equal the route's, byte for byte (and both leave the thumbnails of B)
+            torch.cuda.synchronize()
+            call(k, B, held["masked"], kmask, g["out"][0])
+            route(k, B, held["route"], kmask, g["out"][1])
+            core.synchronize()
+            g["small"].synchronize()
+            (o0, p0, c0), (o1, p1, c1) = g["out"]
+            end = int(p0[S].item())
+            assert torch.equal(o0, o1) and torch.equal(p0, p1) and torch.equal(c0[:end], c1[:end]), (kind, k)
+            assert torch.equal(held["masked"], held["route"]) and end > 8 * S, (kind, k)
+            checked += 1
+            for name in ("touched", "null"):                # every leg begins at B, like the two above
+                call(k, B, held[name], None, g["out"][0])
+            core.synchronize()
+
+            def legs(kind=kind, k=k, held=held, recs=recs, counts=counts, escapes=escapes, kmask=kmask, pair=(A, B)):
+                out = geo[k]["out"][0]
+
+                def touched_plus_call():
+                    for i in range(passes):
+                        core.cwire_touched_tiles_batch(recs, counts, escapes, S, 1, d_mask)
+                        call(k, pair[i % 2], held["touched"], d_mask, out)
+                    core.synchronize()
+
+                def call_masked():
+                    for i in range(passes):
+                        call(k, pair[i % 2], held["masked"], kmask, out)
+                    core.synchronize()
+
+                def call_null():
+                    for i in range(passes):
+                        call(k, pair[i % 2], held["null"], None, out)
+                    core.synchronize()
+
+                def the_route():
+                    for i in range(passes):
+                        core.cwire_touched_tiles_batch(recs, counts, escapes, S, 1, d_mask)
+                        route(k, pair[i % 2], held["route"], d_mask, geo[k]["out"][1])
+                        geo[k]["small"].synchronize()
+                return {f"touched_plus_call_{kind}_k{k}": touched_plus_call, f"call_{kind}_k{k}": call_masked,
+                        f"call_nullmask_{kind}_k{k}": call_null, f"route_{kind}_k{k}": the_route}
+            table.update(legs())
+    times = {}
+    for r in range(rounds + 1):                            # round 0 warms every leg up and is dropped
+        for name, leg in table.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            leg()
+            dt = time.perf_counter() - t0
+            if r:
+                times.setdefault(name, []).append(dt * 1e6 / (passes * S))
+    out = {"streams": S, "passes": passes, "tiles": state_tiles(n), "state_bytes": n, "records_equal_to_the_route": checked,
+           "touched_tiles_per_stream": {kind: round(ticks[kind][5] / S, 1) for kind in ticks}}
+    for name in table:
+        st = stats(times[name])
+        st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
+        out[name + "_us_per_stream"] = st
+    med = {k: statistics.median(v) for k, v in times.items()}
+
+    def spread(*names):
+        return max(max(times[k]) - min(times[k]) for k in names)
+
+    points = [(kind, k) for kind in ticks for k in scales]
+    out["touched_plus_call_over_route"] = {f"{kind}_k{k}": round(med[f"touched_plus_call_{kind}_k{k}"] / med[f"route_{kind}_k{k}"], 3)
+                                           for kind, k in points}
+    out["touched_plus_call_no_slower_than_route"] = bool(all(
+        med[f"touched_plus_call_{kind}_k{k}"] <= med[f"route_{kind}_k{k}"] + spread(f"touched_plus_call_{kind}_k{k}", f"route_{kind}_k{k}")
+        for kind, k in points))
+    out["call_local_over_nullmask"] = {f"k{k}": round(med[f"call_local_k{k}"] / med[f"call_nullmask_local_k{k}"], 3) for k in scales}
+    out["call_local_cheaper_than_nullmask"] = bool(all(
+        med[f"call_local_k{k}"] + spread(f"call_local_k{k}", f"call_nullmask_local_k{k}") < med[f"call_nullmask_local_k{k}"]
+        for k in scales))
+    for g in geo.values():
+        g["small"].close()
+    core.close()
+    return out
+
+
 def run_coalesce(W, H, S, T, rounds, kind):
     """The coalesce leg for one (S, T) and one input -> its dictionary.  coalesce: mi355_cwire_coalesce_cwire_batch on the
     burst's records, nothing else.  state_route: what a relay did before -- mi355_apply_multi_stream_cwire_batch onto states it
@@ -1442,7 +1608,7 @@ def main():
     ap.add_argument("--steps", type=int, default=8, help="K: webcam frames a stream walks through")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--legs", default="multi,cores_loop,pairs",
-                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or crop alone; or split alone; or mosaic alone; or budget alone; or activity alone; or check alone; or refresh alone; or wall alone")
+                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or crop alone; or split alone; or mosaic alone; or budget alone; or activity alone; or check alone; or refresh alone; or wall alone; or thumb alone")
     ap.add_argument("--frames", default="4,16,64", help="burst, burst_client and coalesce legs: T, frames per stream and call")
     a = ap.parse_args()
     have = load_library()
@@ -1569,6 +1735,19 @@ def main():
                                       if ok_mask else "masked update on the moving block not cheaper than the full compose at some k or S")
                           + "; " + ("full compose at k = 8 no slower than digest at every S" if ok_full
                                     else "full compose at k = 8 slower than digest at some S")}), flush=True)
+        return
+    if a.legs == "thumb":
+        per = []
+        for S in (int(v) for v in a.streams.split(",")):
+            per.append(run_thumb(W, H, S, a.rounds))
+            print(f"thumb S={S}: done", file=sys.stderr, flush=True)
+            torch.cuda.empty_cache()
+        ok_route, ok_mask = all(p["touched_plus_call_no_slower_than_route"] for p in per), all(p["call_local_cheaper_than_nullmask"] for p in per)
+        print(json.dumps({"bench": "multi_thumb", "size": f"{W}x{H}", "rounds": a.rounds, "thumb": per,
+                          "verdict": ("touched tiles plus the call no slower than the wall-and-diff route at every point"
+                                      if ok_route else "touched tiles plus the call slower than the wall-and-diff route at some point")
+                          + "; " + ("the call with the moving block's mask cheaper than without a mask at every k and S" if ok_mask
+                                    else "the call with the moving block's mask not cheaper than without a mask at some k or S")}), flush=True)
         return
     for S in (int(v) for v in a.streams.split(",")):
         run(W, H, S, a.steps, a.rounds, set(a.legs.split(",")), have)

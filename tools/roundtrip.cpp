@@ -8,10 +8,10 @@
 // second core.  The program checks that the client's frame equals the server's reconstructed state
 // after every batch and that every rebuilt byte is within the threshold of the frame that was sent.
 // Every other mode is described at the head of the run_* function, or of the check a mode hands its records to
-// (ActivityCheck, RecordCheck, WallCheck), that is that mode.
+// (ActivityCheck, RecordCheck, WallCheck, ThumbViewer), that is that mode.
 //
 //   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B]
-//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check] | --resync K [--burst B] | --crop X,Y,W,H [--burst K] | --mosaic CxR [--burst K] | [--burst K --coalesce] --datagram BYTES] [--wall K]]
+//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check] | --resync K [--burst B] | --crop X,Y,W,H [--burst K] | --mosaic CxR [--burst K] | [--burst K --coalesce] --datagram BYTES | --thumb K [--burst T] [--thumb-drop TICK]] [--wall K]]
 //   exit status 0 = all checks passed
 #include <algorithm>
 #include <cstdint>
@@ -109,11 +109,12 @@ struct Session {
         return p;
     }
     // "send" bytes and "receive" them: written in pieces that fit the pipe buffer, read back in between
-    bool send(const void *src, void *dst, size_t bytes) {
+    bool send(const void *src, void *dst, size_t bytes) { return through(fds, src, dst, bytes); }
+    static bool through(const int pipe_fds[2], const void *src, void *dst, size_t bytes) {   // (any pipe: a mode may open more)
         for (size_t at = 0; at < bytes;) {
             const size_t piece = bytes - at < 32768 ? bytes - at : 32768;
-            if (write(fds[1], (const uint8_t *)src + at, piece) != (ssize_t)piece) return false;
-            if (!read_all(fds[0], (uint8_t *)dst + at, piece)) return false;
+            if (write(pipe_fds[1], (const uint8_t *)src + at, piece) != (ssize_t)piece) return false;
+            if (!read_all(pipe_fds[0], (uint8_t *)dst + at, piece)) return false;
             at += piece;
         }
         return true;
@@ -485,6 +486,17 @@ struct RecordCheck {
     }
 };
 
+// pixel (u, v) of the thumbnail at scale k of the w x h BGR24 frame st: the rounded mean of its block, in plain C++
+static void box_average(const uint8_t *st, int w, int h, int k, int u, int v, uint8_t *bgr) {
+    const int x0 = u * k, x1 = std::min(w, x0 + k), y0 = v * k, y1 = std::min(h, y0 + k);
+    const uint32_t a = (uint32_t)((x1 - x0) * (y1 - y0));
+    uint32_t sum[3] = {0, 0, 0};
+    for (int y = y0; y < y1; y++)
+        for (int x = x0; x < x1; x++)
+            for (int c = 0; c < 3; c++) sum[c] += st[3 * ((size_t)y * w + x) + c];
+    for (int c = 0; c < 3; c++) bgr[c] = (uint8_t)((sum[c] + a / 2) / a);
+}
+
 // --compact --multi S --wall K [--burst B --burst-client | --resync R [--burst B]]: the receiver is a wall that shows its cameras.  It
 // keeps ONE wall frame of ceil(sqrt(S)) columns of thumbnails at scale K, composed fully once (mi355_wall_compose_batch without
 // a mask).  After every tick's apply -- with --burst B --burst-client after every burst's -- it asks which tiles the records it just
@@ -551,16 +563,8 @@ struct WallCheck {
         for (int s = 0; s < S; s++) {
             const uint8_t *st = states + (size_t)s * 3 * w * h;
             for (int v = 0; v < th; v++)
-                for (int u = 0; u < tw; u++) {
-                    const int x0 = u * k, x1 = std::min(w, x0 + k), y0 = v * k, y1 = std::min(h, y0 + k);
-                    const uint32_t a = (uint32_t)((x1 - x0) * (y1 - y0));
-                    uint32_t sum[3] = {0, 0, 0};
-                    for (int y = y0; y < y1; y++)
-                        for (int x = x0; x < x1; x++)
-                            for (int c = 0; c < 3; c++) sum[c] += st[3 * ((size_t)y * w + x) + c];
-                    uint8_t *o = &want[(size_t)(place[3 * s + 1] + v) * pitch + 3 * (size_t)(place[3 * s] + u)];
-                    for (int c = 0; c < 3; c++) o[c] = (uint8_t)((sum[c] + a / 2) / a);
-                }
+                for (int u = 0; u < tw; u++)
+                    box_average(st, w, h, k, u, v, &want[(size_t)(place[3 * s + 1] + v) * pitch + 3 * (size_t)(place[3 * s] + u)]);
         }
         if (got != want) { fprintf(stderr, "tick %d: the wall != the box average of the receiver's states\n", t); return 1; }
         compared++;
@@ -796,6 +800,163 @@ static int run_multi_burst(int w, int h, int T, int S, int K) {
            "\"ticks\": %d, \"changed_bytes\": %zu, \"wire_bytes\": %zu, \"reference_wire_bytes\": %zu, \"raw_bytes\": %zu, "
            "\"max_abs_error\": %d}\n",
            S, K, calls, w, h, T, tx.changed, sent_bytes, mi355_wire_bytes(T * S, tx.changed), (size_t)T * S * n, max_err);
+    return 0;
+}
+
+// --compact --multi S --thumb K [--burst T] [--thumb-drop TICK]: the sender also serves a low-resolution viewer.  It holds, next
+// to its S states, the S thumbnails at scale K that the viewer has reconstructed.  Behind every tick -- with --burst T behind every
+// burst -- it asks which tiles its own records landed in (mi355_cwire_touched_tiles_batch) and makes ONE record per camera of the
+// thumbnail's frame there (mi355_thumb_cwire_batch, threshold 0), the calls with no wait in between; camera s's thumbnail record
+// goes through a second pipe of its own.  The viewer is host-only: S frames of tw x th pixels, mi355_cwire_apply_host.  It joins
+// late: before the first tick the sender's held thumbnails and the viewer's frames are zero and one call without a mask makes
+// the key records.  After every tick or burst the viewer must equal a plain C++ box average of the sender's downloaded states.
+// The full-size receiver runs beside it as in --burst (tick by tick with T = 1).
+// --thumb-drop TICK: the viewer discards camera TICK % S's thumbnail record of the step that holds that tick; its picture must
+// then be wrong; the repair is the key-record procedure (the viewer clears that frame, the sender zeroes that held thumbnail, one
+// call without a mask) and the pictures must be equal from then on.
+struct ThumbViewer {
+    mi355_core *core = nullptr;   // the sender's
+    int w = 0, h = 0, k = 0, S = 0, tw = 0, th = 0, calls = 0, compared = 0;
+    size_t nt = 0, cap = 0, sent = 0;
+    void *d_thumbs = nullptr, *d_mask = nullptr, *d_off = nullptr, *d_pos = nullptr, *d_cw = nullptr;
+    std::vector<int> fds;           // a pipe per camera
+    std::vector<uint8_t> bytes, rx, frames, want;
+    std::vector<uint32_t> counts, escapes;
+    std::vector<uint64_t> pos;
+
+    int open(Session &ss, const Sender &tx, int k_, int most) {   // most: the records of the sender's largest step
+        if (!mi355_wall_thumb_size(ss.w, ss.h, k_, &tw, &th)) { fprintf(stderr, "--thumb K needs 1 <= K <= 16\n"); return 2; }
+        core = tx.core; w = ss.w; h = ss.h; k = k_; S = tx.S;
+        nt = (size_t)3 * tw * th;
+        cap = mi355_cwire_bytes_max(nt, S);
+        d_thumbs = ss.dev(core, (size_t)S * nt);
+        d_mask = ss.dev(core, 4 * (size_t)S * ((mi355_state_tiles(ss.n) + 31) / 32));
+        d_off = ss.dev(core, sizeof(uint32_t) * (S + 1));
+        d_pos = ss.dev(core, sizeof(uint64_t) * (S + 1));
+        d_cw = ss.dev(core, cap);
+        if (!ss.ok()) return 1;
+        fds.resize((size_t)2 * S);
+        for (int s = 0; s < S; s++)
+            if (pipe(&fds[(size_t)2 * s]) != 0) { fprintf(stderr, "pipe failed\n"); return 1; }
+        bytes.resize(cap); rx.resize(cap); frames.assign((size_t)S * nt, 0); want.resize((size_t)S * nt);
+        counts.resize(most); escapes.resize(most); pos.resize(S + 1);
+        OK(mi355_upload(core, d_thumbs, frames.data(), frames.size()));   // nobody has seen anything yet
+        return 0;
+    }
+    // the thumbnail records of the states as they are: where the nb records per camera of the sender's last step landed, or
+    // (nb == 0) everywhere; every camera's record through its pipe and onto the viewer's frame, but camera `drop`'s, which is lost.
+    // *lost: the entries of the lost record
+    int serve(const Sender &tx, int nb, int drop, uint32_t *lost) {
+        const void *mask = nullptr;
+        if (nb) {
+            if (walk_records(tx.bytes.data(), 0, tx.cb, S * nb, counts.data(), escapes.data(), nullptr)) return 1;
+            OK(mi355_cwire_touched_tiles_batch(core, tx.d_cw, counts.data(), escapes.data(), S, nb, 0, d_mask));
+            mask = d_mask;
+        }
+        OK(mi355_thumb_cwire_batch(core, tx.d_states, tx.n, S, k, 0, mask, d_thumbs, nt, d_off, d_pos, d_cw, cap));
+        calls++;
+        OK(mi355_download(core, pos.data(), d_pos, sizeof(uint64_t) * (S + 1)));
+        if (pos[S] > cap) { fprintf(stderr, "thumbnail records larger than their bound\n"); return 1; }
+        OK(mi355_download(core, bytes.data(), d_cw, (size_t)pos[S]));
+        for (int s = 0; s < S; s++) {
+            const size_t a = (size_t)pos[s], len = (size_t)pos[s + 1] - a;
+            if (!Session::through(&fds[(size_t)2 * s], bytes.data() + a, rx.data() + a, len)) return 1;
+            sent += len;
+            if (s == drop) {
+                memcpy(lost, rx.data() + a, 4);
+                continue;
+            }
+            size_t used = 0;
+            OK(mi355_cwire_apply_host(&frames[(size_t)s * nt], nt, rx.data() + a, len, 1, &used));
+            if (used != len) { fprintf(stderr, "thumbnail stream framing broken\n"); return 1; }
+        }
+        return 0;
+    }
+    // the key-record procedure for camera s
+    int rejoin(const Sender &tx, int s) {
+        std::fill(frames.begin() + (size_t)s * nt, frames.begin() + (size_t)(s + 1) * nt, 0);
+        OK(mi355_upload(core, (uint8_t *)d_thumbs + (size_t)s * nt, &frames[(size_t)s * nt], nt));
+        return serve(tx, 0, -1, nullptr);
+    }
+    // the box average of the sender's states (S frames back to back) -> want; true: the viewer's camera s shows it
+    void average(const uint8_t *states) {
+        for (int s = 0; s < S; s++)
+            for (int v = 0; v < th; v++)
+                for (int u = 0; u < tw; u++)
+                    box_average(states + (size_t)s * 3 * w * h, w, h, k, u, v, &want[(size_t)s * nt + 3 * ((size_t)v * tw + u)]);
+    }
+    bool shows(int s) const { return memcmp(&frames[(size_t)s * nt], &want[(size_t)s * nt], nt) == 0; }
+    int compare(const uint8_t *states, int t) {
+        average(states);
+        for (int s = 0; s < S; s++)
+            if (!shows(s)) { fprintf(stderr, "tick %d: camera %d: the viewer != the box average of the sender's state\n", t, s); return 1; }
+        compared++;
+        return 0;
+    }
+};
+
+static int run_multi_thumb(int w, int h, int T, int S, int K, int k, int drop_tick) {
+    const bool burst = K > 0;
+    if (!burst) K = 1;
+    Session ss(w, h);
+    const size_t n = ss.n;
+    Cameras cams(S, w, h);
+    Sender tx;
+    Receiver rcv;
+    ThumbViewer view;
+    if (tx.open(ss, S, K) || rcv.open(ss, S, S, S)) return 1;
+    if (int rc = view.open(ss, tx, k, S * K)) return rc;
+    std::vector<uint8_t> host_frames((size_t)S * n), sock(tx.cap);   // a host client per camera; the bytes as the sockets gave them
+    std::vector<uint32_t> b_counts(S * K), b_escapes(S * K);
+    std::vector<size_t> b_at(S * K + 1);
+    if (cams.start(ss, tx, rcv, host_frames.data())) return 1;
+    // ---- the viewer joins: key records of the thumbnails of the base frames
+    if (view.serve(tx, 0, -1, nullptr) || tx.get_states() || view.compare(tx.states.data(), -1)) return 1;
+    size_t sent_bytes = 0;
+    int max_err = 0, repaired = 0;
+    for (int t0 = 0; t0 < T; t0 += K) {
+        const int nb = T - t0 < K ? T - t0 : K;
+        cams.fill(tx.frames.data(), t0, nb);
+        if (tx.step(nb, burst)) return 1;
+        // ---- the low-resolution viewer: touched tiles of the step's records, the thumbnails' records, a pipe per camera
+        const bool dropping = drop_tick >= t0 && drop_tick < t0 + nb;
+        const int drop = dropping ? drop_tick % S : -1;
+        uint32_t lost = 0;
+        if (view.serve(tx, nb, drop, &lost) || tx.get_states()) return 1;
+        if (dropping) {
+            if (!lost) { fprintf(stderr, "--thumb-drop: the record to drop holds no entry\n"); return 1; }
+            view.average(tx.states.data());
+            if (view.shows(drop)) { fprintf(stderr, "--thumb-drop: the picture is right without its record\n"); return 1; }
+            if (view.rejoin(tx, drop)) return 1;
+            repaired++;
+        }
+        if (view.compare(tx.states.data(), t0 + nb - 1)) return 1;
+        // ---- the full-size receiver beside it: every socket's records, staged and applied tick by tick
+        for (int s = 0; s < S; s++) {
+            const size_t a = (size_t)tx.pos[(size_t)s * nb], b = (size_t)tx.pos[(size_t)(s + 1) * nb];
+            if (!ss.send(tx.bytes.data() + a, sock.data() + a, b - a)) return 1;
+        }
+        sent_bytes += tx.cb;
+        if (walk_records(sock.data(), 0, tx.cb, S * nb, b_counts.data(), b_escapes.data(), b_at.data())) return 1;
+        for (int j = 0; j < nb; j++) {
+            const size_t q = rcv.stage(sock.data(), b_at.data(), nb, j, -1);
+            for (int s = 0; s < S; s++)
+                if (host_apply(&host_frames[(size_t)s * n], n, rcv.rx.data(), rcv.at.data(), s)) return 1;
+            OK(mi355_upload(rcv.core, rcv.d_rx, rcv.rx.data(), q));
+            if (rcv.apply_tick() || rcv.get_states()) return 1;
+            if (same(host_frames.data(), rcv.states.data(), rcv.states.size(), "receiver states != host client frames", t0 + j)) return 1;
+            for (int s = 0; s < S; s++)
+                max_err = std::max(max_err, max_abs_error(&rcv.states[(size_t)s * n], &tx.frames[((size_t)s * nb + j) * n], n));
+        }
+        if (states_equal(tx, rcv, t0)) return 1;
+    }
+    if (drop_tick >= 0 && !repaired) { fprintf(stderr, "--thumb-drop TICK needs 0 <= TICK < --frames\n"); return 2; }
+    if (within_threshold(max_err, ss) || ss.close()) return 1;
+    for (int fd : view.fds) close(fd);
+    printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"burst\": %d, \"width\": %d, \"height\": %d, \"ticks\": %d, "
+           "\"changed_bytes\": %zu, \"wire_bytes\": %zu, \"max_abs_error\": %d, \"thumb\": {\"scale\": %d, \"size\": [%d, %d], "
+           "\"calls\": %d, \"wire_bytes\": %zu, \"viewers_equal\": %d, \"repaired\": %d}}\n",
+           S, burst ? K : 0, w, h, T, tx.changed, sent_bytes, max_err, k, view.tw, view.th, view.calls, view.sent, view.compared, repaired);
     return 0;
 }
 
@@ -1605,7 +1766,7 @@ static int usage(const char *text) {
 }
 
 int main(int argc, char **argv) {
-    long w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0, activity = -1, resync = -1, wall = 0, budget = -1, datagram = -1;
+    long w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0, activity = -1, resync = -1, wall = 0, budget = -1, datagram = -1, thumb = 0, thumb_drop = -1;
     bool compact = false, direct = false, gpu_client = false, burst_client = false, coalesce = false, per_frame = false, check = false;
     const struct { const char *name; bool *on; } flags[] = {
         {"--compact", &compact}, {"--direct", &direct}, {"--gpu-client", &gpu_client}, {"--burst-client", &burst_client},
@@ -1614,7 +1775,7 @@ int main(int argc, char **argv) {
     const struct { const char *name; long *value, least, below; } valued[] = {   // a value below `least` is taken as `below`
         {"--width", &w, any, 0}, {"--height", &h, any, 0}, {"--frames", &T, any, 0}, {"--batch", &B, any, 0}, {"--multi", &multi, any, 0},
         {"--burst", &burst, any, 0}, {"--activity", &activity, 0, 0}, {"--resync", &resync, 0, 0}, {"--wall", &wall, 1, -1},
-        {"--budget", &budget, 0, 0}, {"--datagram", &datagram, 0, 0}};
+        {"--budget", &budget, 0, 0}, {"--datagram", &datagram, 0, 0}, {"--thumb", &thumb, 1, -1}, {"--thumb-drop", &thumb_drop, 0, -2}};
     int32_t crop[4] = {0, 0, 0, 0};
     bool cropped = false, crop_ok = true;
     int grid[2] = {0, 0};
@@ -1676,12 +1837,19 @@ int main(int argc, char **argv) {
         if (datagram < 64 || datagram > (long)MI355_CWIRE_SPLIT_BLOCK || datagram % 4)
             return usage("--datagram BYTES needs a multiple of 4 in [64, 65536]");
     }
+    if (thumb || thumb_drop != -1) {
+        if (thumb < 1 || thumb > 16 || !compact || !multi || cropped || mosaic || datagram >= 0 || budget >= 0 || coalesce || per_frame ||
+            burst_client || activity || check || resync >= 0 || wall)
+            return usage("--thumb K needs 1 <= K <= 16 and --compact --multi S, alone or with --burst T");
+        if (thumb_drop < -1 || thumb_drop >= T) return usage("--thumb-drop TICK needs --thumb K and 0 <= TICK < --frames");
+    }
     if (per_frame) {
         if (!compact || direct || gpu_client || multi) return usage("--per-frame needs --compact alone");
         return run_per_frame(w, h, T);
     }
     if (!multi) return run_single(w, h, T, B, compact, direct, gpu_client);
     if (!compact || direct || gpu_client || multi < 0) return usage("--multi S needs --compact alone and S >= 1");
+    if (thumb) return run_multi_thumb(w, h, T, multi, burst, thumb, thumb_drop);
     if (resync >= 0) return run_multi_resync(w, h, T, multi, resync, burst, wall);
     if (cropped) return run_multi_crop(w, h, T, multi, burst, crop);
     if (mosaic) return run_multi_mosaic(w, h, T, multi, burst, grid[0], grid[1]);
