@@ -555,6 +555,37 @@ class CUDACore:
                                                          int(nrecords), int(max_bytes), _ptr(d_piece_first), _ptr(d_piece_pos),
                                                          int(piece_capacity), _ptr(d_cwire_out), int(capacity_bytes)))
 
+    # ... with parity datagrams behind the pieces, so that a receiver rebuilds what the link lost
+    def cwire_fec_batch(self, d_pieces, pieces_bytes, d_piece_first, d_piece_pos, piece_capacity, nrecords, group, nparity, pitch,
+                        d_fec_first, d_fec_len, group_capacity, d_out, capacity_bytes):
+        """nparity (1: P, 2: P and Q) parity blocks per group of `group` (1 .. 255) pieces of what cwire_split_cwire_batch wrote,
+        on the same stream behind it: block q of group g at d_out + (g*nparity + q)*pitch, d_fec_len[g] (uint32[group_capacity])
+        bytes long; record r's groups are d_fec_first[r] .. d_fec_first[r + 1] (uint32[nrecords + 1]).  cwire_fec_host is the same
+        on the host and the definition; cwire_fec_groups_max gives a sufficient group_capacity."""
+        self._hold(d_pieces, d_piece_first, d_piece_pos, d_fec_first, d_fec_len, d_out)
+        _l.check(self._lib.mi355_cwire_fec_batch(self._h, _ptr(d_pieces), int(pieces_bytes), _ptr(d_piece_first), _ptr(d_piece_pos),
+                                                 int(piece_capacity), int(nrecords), int(group), int(nparity), int(pitch),
+                                                 _ptr(d_fec_first), _ptr(d_fec_len), int(group_capacity), _ptr(d_out),
+                                                 int(capacity_bytes)))
+
+    def cwire_fec_repair_batch(self, d_rx, rx_bytes, njobs, job_first, slot_off, slot_len, parity_off, fec_len, d_out, pitch,
+                               d_verdict):
+        """The lost pieces of njobs groups rebuilt from what arrived in d_rx: job j has the slots job_first[j] .. job_first[j + 1]
+        of slot_off (byte offsets into d_rx, lib.FEC_ABSENT: lost) / slot_len, its parity blocks at parity_off[j] = (P, Q)
+        (lib.FEC_ABSENT: not there) and fec_len[j]; rebuilt block k to d_out + (2j + k)*pitch, its verdict (lib.FEC_BAD_*) to
+        d_verdict, uint32[njobs][2].  cwire_fec_repair_host is the same for one group on the host and the definition."""
+        self._hold(d_rx, d_out, d_verdict)
+        job_first = np.ascontiguousarray(job_first, dtype=np.uint32)
+        slot_off = np.ascontiguousarray(slot_off, dtype=np.uint64)
+        slot_len = np.ascontiguousarray(slot_len, dtype=np.uint32)
+        parity_off = np.ascontiguousarray(parity_off, dtype=np.uint64)
+        fec_len = np.ascontiguousarray(fec_len, dtype=np.uint32)
+        assert job_first.size >= njobs + 1 and parity_off.size >= 2 * njobs and fec_len.size >= njobs
+        assert slot_off.size >= int(job_first[njobs]) <= slot_len.size
+        _l.check(self._lib.mi355_cwire_fec_repair_batch(self._h, _ptr(d_rx), int(rx_bytes), int(njobs), job_first.ctypes.data,
+                                                        slot_off.ctypes.data, slot_len.ctypes.data, parity_off.ctypes.data,
+                                                        fec_len.ctypes.data, _ptr(d_out), int(pitch), _ptr(d_verdict)))
+
     # ... and when a record was refused or lost after all: the receiver's digests, the sender's refresh, the receiver's clear
     def state_digest_batch(self, d_states, nstreams, d_digests, stride=None):
         """Two words per tile of 4096 bytes of each of nstreams states (stream s at d_states + s*stride, any alignment) into
@@ -892,6 +923,55 @@ def cwire_split_host(buf, counts, escapes, frame_bytes, max_bytes, piece_capacit
                                       counts.size, int(max_bytes), piece_first.ctypes.data, piece_pos.ctypes.data,
                                       int(piece_capacity), out.ctypes.data, int(capacity_bytes)))
     return piece_first, piece_pos, out[:int(capacity_bytes)]
+
+
+def cwire_fec_groups_max(piece_capacity, nrecords, group):
+    """A sufficient group count for piece_capacity pieces in nrecords records at `group` pieces per group (0 for a group outside
+    1 .. 255)."""
+    return _l.load().mi355_cwire_fec_groups_max(int(piece_capacity), int(nrecords), int(group))
+
+
+def cwire_fec_host(pieces, pieces_bytes, piece_first, piece_pos, piece_capacity, group, nparity, pitch, group_capacity=None,
+                   capacity_bytes=None, fill=0):
+    """cwire_fec_batch computed on the host (no GPU, no core) and its definition: (fec_first uint32[nrecords + 1], fec_len
+    uint32[group_capacity], out uint8[capacity_bytes]) for the pieces of cwire_split_host / _cwire_batch.  The capacities default
+    to what always suffices; what the call does not write keeps `fill` (fec_len: fill in every byte)."""
+    L = _l.load()
+    pieces = np.ascontiguousarray(pieces, dtype=np.uint8)
+    piece_first = np.ascontiguousarray(piece_first, dtype=np.uint32)
+    piece_pos = np.ascontiguousarray(piece_pos, dtype=np.uint64)
+    nrecords = piece_first.size - 1
+    assert pieces.size >= pieces_bytes and piece_pos.size >= piece_capacity + 1
+    if group_capacity is None:
+        group_capacity = L.mi355_cwire_fec_groups_max(int(piece_capacity), nrecords, int(group))
+    if capacity_bytes is None:
+        capacity_bytes = int(group_capacity) * int(nparity) * int(pitch)
+    fec_first = np.zeros(nrecords + 1, np.uint32)
+    fec_len = np.full(max(int(group_capacity), 1), fill * 0x01010101, np.uint32)
+    out = np.full(max(int(capacity_bytes), 1), fill, np.uint8)
+    _l.check(L.mi355_cwire_fec_host(pieces.ctypes.data, int(pieces_bytes), piece_first.ctypes.data, piece_pos.ctypes.data,
+                                    int(piece_capacity), nrecords, int(group), int(nparity), int(pitch), fec_first.ctypes.data,
+                                    fec_len.ctypes.data, int(group_capacity), out.ctypes.data, int(capacity_bytes)))
+    return fec_first, fec_len[:int(group_capacity)], out[:int(capacity_bytes)]
+
+
+def cwire_fec_repair_host(slots, p, q, fec_len):
+    """One group repaired on the host (no GPU, no core), the definition of cwire_fec_repair_batch: slots is the group's members
+    in slot order, uint8 arrays or None for a lost one; p, q its parity blocks or None.  Returns (rebuilt blocks, one uint8 array
+    of fec_len bytes per lost slot, and their verdicts, lib.FEC_BAD_* flags)."""
+    L = _l.load()
+    keep = [None if s is None else np.ascontiguousarray(s, dtype=np.uint8) for s in slots]
+    p = None if p is None else np.ascontiguousarray(p, dtype=np.uint8)
+    q = None if q is None else np.ascontiguousarray(q, dtype=np.uint8)
+    assert all(x is None or x.size >= fec_len for x in (p, q))
+    ptrs = (C.c_void_p * max(len(keep), 1))(*[None if s is None else s.ctypes.data for s in keep])
+    lens = np.array([0 if s is None else s.size for s in keep] + [0], np.uint32)
+    lost = sum(s is None for s in keep)
+    outs = [np.zeros(int(fec_len), np.uint8) for _ in range(2)]
+    verdict = np.zeros(2, np.uint32)
+    _l.check(L.mi355_cwire_fec_repair_host(len(keep), C.addressof(ptrs), lens.ctypes.data, _ptr(p), _ptr(q), int(fec_len),
+                                           outs[0].ctypes.data, outs[1].ctypes.data, verdict.ctypes.data))
+    return outs[:lost], verdict[:lost]
 
 
 def state_tiles(frame_bytes):

@@ -1973,6 +1973,257 @@ int mi355_cwire_split_cwire_batch(mi355_core *c, const void *d_cwire, const uint
     return MI355_OK;
 }
 
+// ---- mi355_cwire_fec_*: parity blocks over groups of pieces, and their repair (include/mi355diff.h, "Parity pieces") ----------
+size_t mi355_cwire_fec_groups_max(size_t piece_capacity, int nrecords, int group) {
+    if (group < 1 || group > 255 || nrecords < 0) return 0;
+    return piece_capacity / (size_t)group + (size_t)nrecords;
+}
+
+static int fec_check_shape(int group, int nparity, size_t pitch) {
+    if (group < 1 || group > 255) return fail(MI355_ERR_INVALID, "group outside [1, 255]");
+    if (nparity < 1 || nparity > 2) return fail(MI355_ERR_INVALID, "nparity must be 1 or 2");
+    if (pitch < 64 || pitch > 65536 || (pitch & 3u)) return fail(MI355_ERR_INVALID, "pitch must be a multiple of 4 in [64, 65536]");
+    return MI355_OK;
+}
+
+// inputs and outputs of the two forms alike
+static int fec_check_regions(const void *pieces, size_t pieces_bytes, const void *piece_first, const void *piece_pos, size_t piece_capacity,
+                             int nrecords, int nparity, const void *fec_first, const void *fec_len, size_t group_capacity, const void *out,
+                             size_t capacity_bytes) {
+    (void)nparity;
+    return check_regions({Region{pieces, pieces_bytes, "the pieces"}, Region{piece_first, 4 * ((uint64_t)nrecords + 1), "piece_first"},
+                          Region{piece_pos, 8 * ((uint64_t)piece_capacity + 1), "piece_pos"}},
+                         {Region{fec_first, 4 * ((uint64_t)nrecords + 1), "fec_first"}, nowhere(Region{fec_len, 4 * (uint64_t)group_capacity, "fec_len"}),
+                          nowhere(Region{out, capacity_bytes, "the parity blocks"})},
+                         true);
+}
+
+// The definition.  The group and member arithmetic is cwire_common.h's, shared with the kernel.
+int mi355_cwire_fec_host(const void *pieces, size_t pieces_bytes, const uint32_t *piece_first, const uint64_t *piece_pos,
+                         size_t piece_capacity, int nrecords, int group, int nparity, size_t pitch, uint32_t *fec_first, uint32_t *fec_len,
+                         size_t group_capacity, void *out, size_t capacity_bytes) {
+    if (nrecords < 0) return fail(MI355_ERR_INVALID, "nrecords < 0");
+    if (int rc = fec_check_shape(group, nparity, pitch)) return rc;
+    if (nrecords == 0) {
+        if (fec_first) fec_first[0] = 0;
+        return MI355_OK;
+    }
+    if (!pieces || !piece_first || !piece_pos || !fec_first || !fec_len || !out) return fail(MI355_ERR_INVALID, "null argument");
+    if (int rc = fec_check_regions(pieces, pieces_bytes, piece_first, piece_pos, piece_capacity, nrecords, nparity, fec_first, fec_len,
+                                   group_capacity, out, capacity_bytes))
+        return rc;
+    const uint32_t G = (uint32_t)group, K = (uint32_t)nparity;
+    uint32_t groups = 0;
+    for (int r = 0; r < nrecords; r++) {
+        const uint32_t c = piece_first[r + 1] - piece_first[r];
+        fec_first[r] = groups;
+        groups += c / G + (c % G ? 1u : 0u);
+    }
+    fec_first[nrecords] = groups;
+    const uint8_t *src = (const uint8_t *)pieces;
+    std::vector<uint32_t> P, Q;
+    for (uint32_t g = 0; g < groups && g < group_capacity; g++) {
+        const FecGroup fg = fec_group(fec_first, piece_first, nrecords, G, g);
+        uint32_t L = 0;
+        bool bad = fg.m == 0;
+        for (uint32_t i = 0; i < fg.m; i++) {
+            const uint32_t len = fec_member_len(piece_pos, piece_capacity, pieces_bytes, (uint32_t)pitch, fg.p0 + i);
+            bad |= len == 0;
+            L = len > L ? len : L;
+        }
+        if (bad) L = 0;
+        fec_len[g] = L;
+        const uint64_t slot = (uint64_t)g * K * pitch;
+        if (L == 0 || slot + (uint64_t)K * pitch > capacity_bytes) continue;
+        P.assign(L / 4, 0u);
+        Q.assign(L / 4, 0u);
+        for (uint32_t i = fg.m; i > 0; i--) {   // Horner, from the last slot down
+            const uint64_t at = piece_pos[fg.p0 + i - 1];
+            const uint32_t len = (uint32_t)(piece_pos[fg.p0 + i] - at);
+            for (uint32_t w = 0; w < L / 4; w++) {
+                uint32_t v = 0;
+                if (4 * w < len) memcpy(&v, src + at + 4 * (size_t)w, 4);
+                P[w] ^= v;
+                Q[w] = fec_xtime(Q[w]) ^ v;
+            }
+        }
+        memcpy((uint8_t *)out + slot, P.data(), L);
+        if (K == 2) memcpy((uint8_t *)out + slot + pitch, Q.data(), L);
+    }
+    return MI355_OK;
+}
+
+int mi355_cwire_fec_batch(mi355_core *c, const void *d_pieces, size_t pieces_bytes, const void *d_piece_first, const void *d_piece_pos,
+                          size_t piece_capacity, int nrecords, int group, int nparity, size_t pitch, void *d_fec_first, void *d_fec_len,
+                          size_t group_capacity, void *d_out, size_t capacity_bytes) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nrecords < 0 || nrecords > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nrecords outside [0, max_batch]");
+    if (int rc = fec_check_shape(group, nparity, pitch)) return rc;
+    if (((uintptr_t)d_pieces | (uintptr_t)d_piece_first | (uintptr_t)d_fec_first | (uintptr_t)d_fec_len | (uintptr_t)d_out) & 3u)
+        return fail(MI355_ERR_INVALID, "d_pieces, d_piece_first, d_fec_first, d_fec_len and d_out must be 4-byte aligned");
+    if ((uintptr_t)d_piece_pos & 7u) return fail(MI355_ERR_INVALID, "d_piece_pos must be 8-byte aligned");
+    if (nrecords == 0) return write_empty_heads(c, d_fec_first, nullptr);
+    if (!d_pieces || !d_piece_first || !d_piece_pos || !d_fec_first || !d_fec_len || !d_out) return fail(MI355_ERR_INVALID, "null argument");
+    if (int rc = fec_check_regions(d_pieces, pieces_bytes, d_piece_first, d_piece_pos, piece_capacity, nrecords, nparity, d_fec_first,
+                                   d_fec_len, group_capacity, d_out, capacity_bytes))
+        return rc;
+    if (int rc = use_device(c)) return rc;
+    const FecArgs a{(const uint32_t *)d_pieces, (uint64_t)pieces_bytes, (const uint32_t *)d_piece_first, (const uint64_t *)d_piece_pos,
+                    (uint64_t)piece_capacity, nrecords, (uint32_t)group, (uint32_t)nparity, (uint32_t)pitch, (uint32_t *)d_fec_first,
+                    (uint32_t *)d_fec_len, (uint64_t)group_capacity, (uint32_t *)d_out, (uint64_t)capacity_bytes};
+    HIP_TRY(launch_cwire_fec(a, c->cu_count * 8u, c->stream));   // eight waves per SIMD
+    return MI355_OK;
+}
+
+namespace {
+// GF(2^8) modulo 0x11D on one byte, through the packed forms of cwire_common.h
+uint32_t gf_pow2(uint32_t i) {
+    uint32_t v = 1;
+    while (i--) v = fec_xtime(v) & 255u;
+    return v;
+}
+uint32_t gf_inv(uint32_t c) {
+    for (uint32_t x = 1; x < 256; x++)
+        if ((fec_mul(x, c) & 255u) == 1u) return x;
+    return 0;
+}
+
+// What one job asks for, refused or turned into the kernel's mode and constants (FecRepairJob).  present(i, from): slot i survives.
+struct FecPlan {
+    uint32_t mode, c1, c2, a, b, lost;
+};
+typedef bool (*FecPresent)(int i, const void *from);
+int fec_plan(int members, FecPresent present_fn, const void *from, const uint32_t *slot_len, bool have_p, bool have_q, uint32_t fec_len, FecPlan *pl) {
+    if (members < 1 || members > 255) return fail(MI355_ERR_INVALID, "members outside [1, 255]");
+    if (fec_len == 0 || (fec_len & 3u)) return fail(MI355_ERR_INVALID, "fec_len must be a positive multiple of 4");
+    if (!slot_len) return fail(MI355_ERR_INVALID, "null argument");
+    uint32_t lost[2] = {0, 0}, u = 0;
+    for (int i = 0; i < members; i++) {
+        if (!present_fn(i, from)) {
+            if (u < 2) lost[u] = (uint32_t)i;
+            u++;
+        } else if (slot_len[i] == 0 || (slot_len[i] & 3u) || slot_len[i] > fec_len)
+            return fail(MI355_ERR_INVALID, "a surviving length must be a positive multiple of 4 and at most fec_len");
+    }
+    if (u > (have_p ? 1u : 0u) + (have_q ? 1u : 0u)) return fail(MI355_ERR_INVALID, "more slots lost than parity blocks present");
+    pl->lost = u;
+    pl->a = lost[0];
+    pl->b = lost[1];
+    pl->c1 = pl->c2 = 0;
+    if (u == 0) pl->mode = 0;
+    else if (u == 1 && have_p) pl->mode = 1;
+    else if (u == 1) {
+        pl->mode = 2;
+        pl->c2 = gf_inv(gf_pow2(lost[0]));
+    } else {
+        pl->mode = 3;
+        pl->c1 = gf_pow2(lost[0]);
+        pl->c2 = gf_inv(gf_pow2(lost[0]) ^ gf_pow2(lost[1]));
+    }
+    return MI355_OK;
+}
+}  // namespace
+
+// The definition of the repair: the formulas of the header, word by word.
+int mi355_cwire_fec_repair_host(int members, const void *const *slot, const uint32_t *slot_len, const void *p, const void *q,
+                                uint32_t fec_len, void *out0, void *out1, uint32_t verdict[2]) {
+    if (!slot) return fail(MI355_ERR_INVALID, "null argument");
+    FecPlan pl;
+    if (int rc = fec_plan(members, [](int i, const void *from) { return ((const void *const *)from)[i] != nullptr; }, slot, slot_len, p != nullptr, q != nullptr, fec_len, &pl)) return rc;
+    if (pl.lost >= 1 && (!out0 || !verdict)) return fail(MI355_ERR_INVALID, "null output");
+    if (pl.lost == 2 && !out1) return fail(MI355_ERR_INVALID, "null output");
+    if (verdict) verdict[0] = verdict[1] = 0;
+    if (pl.lost == 0) return MI355_OK;
+    const uint32_t nw = fec_len / 4;
+    std::vector<uint32_t> d[2];
+    d[0].assign(nw, 0u);
+    d[1].assign(nw, 0u);
+    for (uint32_t w = 0; w < nw; w++) {
+        uint32_t P = 0, Q = 0, qs = 0;
+        if (p) memcpy(&P, (const uint8_t *)p + 4 * (size_t)w, 4);
+        if (q) memcpy(&Q, (const uint8_t *)q + 4 * (size_t)w, 4);
+        for (int i = members; i > 0; i--) {
+            uint32_t v = 0;
+            if (slot[i - 1] && 4 * w < slot_len[i - 1]) memcpy(&v, (const uint8_t *)slot[i - 1] + 4 * (size_t)w, 4);
+            P ^= v;
+            qs = fec_xtime(qs) ^ v;
+        }
+        Q ^= qs;   // P, Q: Pxy and Qxy of the header
+        if (pl.mode == 1) d[0][w] = P;
+        else if (pl.mode == 2) d[0][w] = fec_mul(Q, pl.c2);
+        else {
+            d[1][w] = fec_mul(Q ^ fec_mul(P, pl.c1), pl.c2);
+            d[0][w] = P ^ d[1][w];
+        }
+    }
+    for (uint32_t k = 0; k < pl.lost; k++) {
+        memcpy(k ? out1 : out0, d[k].data(), fec_len);
+        uint64_t tail = fec_len;
+        verdict[k] = nw >= 2 ? fec_header_verdict(d[k][0], d[k][1], fec_len, &tail) : (uint32_t)MI355_FEC_BAD_HEADER;
+        for (uint32_t w = (uint32_t)(tail / 4); w < nw; w++)
+            if (d[k][w]) verdict[k] |= MI355_FEC_BAD_TAIL;
+    }
+    return MI355_OK;
+}
+
+int mi355_cwire_fec_repair_batch(mi355_core *c, const void *d_rx, size_t rx_bytes, int njobs, const uint32_t *h_job_first,
+                                 const uint64_t *h_slot_off, const uint32_t *h_slot_len, const uint64_t *h_parity_off,
+                                 const uint32_t *h_fec_len, void *d_out, size_t pitch, void *d_verdict) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (njobs < 0 || njobs > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "njobs outside [0, max_batch]");
+    if (njobs == 0) return MI355_OK;
+    if (!d_rx || !h_job_first || !h_slot_off || !h_slot_len || !h_parity_off || !h_fec_len || !d_out || !d_verdict)
+        return fail(MI355_ERR_INVALID, "null argument");
+    if (((uintptr_t)d_rx | (uintptr_t)d_out | (uintptr_t)d_verdict | pitch) & 3u)
+        return fail(MI355_ERR_INVALID, "d_rx, d_out, d_verdict and pitch must be multiples of 4");
+    if (int rc = check_regions({Region{d_rx, rx_bytes, "d_rx"}},
+                               {Region{d_out, 2 * (uint64_t)njobs * pitch, "d_out"}, Region{d_verdict, 8 * (uint64_t)njobs, "d_verdict"}}, true))
+        return rc;
+    auto block_ok = [&](uint64_t off, uint64_t len) { return !(off & 3u) && off <= rx_bytes && len <= rx_bytes - off; };
+    std::vector<FecPlan> plan((size_t)njobs);
+    for (int j = 0; j < njobs; j++) {   // everything is refused before anything is launched
+        if (h_job_first[j + 1] < h_job_first[j]) return fail(MI355_ERR_INVALID, "h_job_first must not decrease");
+        const uint32_t s0 = h_job_first[j];
+        const int64_t members = (int64_t)h_job_first[j + 1] - s0;
+        const uint64_t po = h_parity_off[2 * (size_t)j], qo = h_parity_off[2 * (size_t)j + 1];
+        if (int rc = fec_plan(members > 255 ? 256 : (int)members, [](int i, const void *from) { return ((const uint64_t *)from)[i] != MI355_FEC_ABSENT; },
+                              h_slot_off + s0, h_slot_len + s0,
+                              po != MI355_FEC_ABSENT, qo != MI355_FEC_ABSENT, h_fec_len[j], &plan[(size_t)j]))
+            return rc;
+        if (h_fec_len[j] > pitch) return fail(MI355_ERR_INVALID, "h_fec_len above pitch");
+        for (int i = 0; i < (int)members; i++)
+            if (h_slot_off[s0 + i] != MI355_FEC_ABSENT && !block_ok(h_slot_off[s0 + i], h_slot_len[s0 + i]))
+                return fail(MI355_ERR_INVALID, "a slot misaligned or past rx_bytes");
+        if ((po != MI355_FEC_ABSENT && !block_ok(po, h_fec_len[j])) || (qo != MI355_FEC_ABSENT && !block_ok(qo, h_fec_len[j])))
+            return fail(MI355_ERR_INVALID, "a parity block misaligned or past rx_bytes");
+    }
+    if (int rc = use_device(c)) return rc;
+    FecRepairArgs h{};
+    int nj = 0;
+    uint32_t ns = 0;
+    auto flush = [&]() -> hipError_t {
+        const hipError_t e = launch_cwire_fec_repair((const uint8_t *)d_rx, h, nj, (uint8_t *)d_out, pitch, (uint32_t *)d_verdict, c->stream);
+        nj = 0;
+        ns = 0;
+        return e;
+    };
+    for (int j = 0; j < njobs; j++) {
+        const uint32_t s0 = h_job_first[j], members = h_job_first[j + 1] - s0;
+        if (nj == kFecRepairJobs || ns + members > (uint32_t)kFecRepairSlots) HIP_TRY(flush());
+        const FecPlan &pl = plan[(size_t)j];
+        h.job[nj] = FecRepairJob{h_parity_off[2 * (size_t)j], h_parity_off[2 * (size_t)j + 1], ns, members, h_fec_len[j], pl.mode, pl.c1, pl.c2,
+                                 (uint32_t)j};
+        for (uint32_t i = 0; i < members; i++) {
+            h.off[ns + i] = h_slot_off[s0 + i];
+            h.len[ns + i] = h_slot_len[s0 + i];
+        }
+        ns += members;
+        nj++;
+    }
+    HIP_TRY(flush());
+    return MI355_OK;
+}
+
 // ---- resynchronising a receiver: tile digests, refresh records, tile clears (stream_ops.hip, k_state_digest, k_rf_*) ----------
 size_t mi355_state_tiles(size_t frame_bytes) { return frame_bytes / kCwaTile + (frame_bytes % kCwaTile ? 1 : 0); }
 

@@ -174,5 +174,62 @@ __device__ __forceinline__ void cwire_scan_frame_pos(int nframes, uint64_t *fram
     if (tid == 0) frame_pos[nframes] = carry;
 }
 
+// ---- parity for the datagram path (include/mi355diff.h, "Parity pieces"): GF(2^8) modulo 0x11D on packed dwords ----------
+// Every byte of v times 2
+__host__ __device__ inline uint32_t fec_xtime(uint32_t v) { return ((v & 0x7f7f7f7fu) << 1) ^ (((v >> 7) & 0x01010101u) * 0x1du); }
+// Every byte of v times the constant c: eight shift-and-XOR steps under a uniform constant
+__host__ __device__ inline uint32_t fec_mul(uint32_t v, uint32_t c) {
+    uint32_t r = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        r ^= (c >> k) & 1u ? v : 0u;
+        v = fec_xtime(v);
+    }
+    return r;
+}
+
+// The record of global group g: the r with fec_first[r] <= g < fec_first[r + 1] (g below fec_first[nrecords])
+__host__ __device__ inline int fec_group_record(const uint32_t *fec_first, int nrecords, uint32_t g) {
+    int lo = 0, hi = nrecords;   // fec_first[lo] <= g < fec_first[hi]
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        if (fec_first[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// Group g: its first piece p0 and its members m.  Returns its length L_g, 0 for a void group -- a member absent or malformed
+// (include/mi355diff.h, "Void groups").  Members lane, lane + step, ... are tested: a host caller passes (0, 1), a wave (lane, 64)
+// and combines the lanes' answers (any 0: void; else the largest).  Reads piece_first[r], [r + 1], and piece_pos[p], [p + 1]
+// only for p < piece_capacity.
+struct FecGroup {
+    uint64_t p0;
+    uint32_t m;
+};
+__host__ __device__ inline FecGroup fec_group(const uint32_t *fec_first, const uint32_t *piece_first, int nrecords, uint32_t group, uint32_t g) {
+    const int r = fec_group_record(fec_first, nrecords, g);
+    const uint32_t c = piece_first[r + 1] - piece_first[r];
+    const uint64_t at = (uint64_t)(g - fec_first[r]) * group;
+    FecGroup fg;
+    fg.p0 = (uint64_t)piece_first[r] + at;
+    fg.m = at < c ? (c - at < group ? (uint32_t)(c - at) : group) : 0u;
+    return fg;
+}
+// One member: its length, 0 when absent or malformed
+__host__ __device__ inline uint32_t fec_member_len(const uint64_t *piece_pos, uint64_t piece_capacity, uint64_t pieces_bytes, uint32_t pitch,
+                                                   uint64_t p) {
+    if (p >= piece_capacity) return 0;
+    const uint64_t a = piece_pos[p], b = piece_pos[p + 1];
+    if (b > pieces_bytes || b <= a || ((a | b) & 3u) || b - a > pitch) return 0;
+    return (uint32_t)(b - a);
+}
+// The verdict of a rebuilt block's header {n, e} (bit 0: MI355_FEC_BAD_HEADER); *tail: the first byte that has to be zero
+__host__ __device__ inline uint32_t fec_header_verdict(uint32_t n, uint32_t e, uint32_t fec_len, uint64_t *tail) {
+    const uint64_t bytes = cwire_record_bytes(n, e);
+    *tail = bytes < fec_len ? bytes : fec_len;
+    return n == 0 || e > n || bytes > fec_len ? 1u : 0u;
+}
+
 }  // namespace mi355
 #endif

@@ -335,6 +335,40 @@ uint32_t cws_blocks(uint32_t n);   // blocks of a record of n entries (1 for n =
 // a.ftab and a.chunk are the scratch it shares with the other calls; a.dir / a.state / a.out / a.stride / a.ntiles unused
 hipError_t launch_cwire_split(const CwaArgs &a, const CwaFrame *records, int nrecords, uint32_t max_bytes, uint4 *blk, ulonglong2 *base,
                               const CwsOut &o, hipStream_t s);
+// mi355_cwire_fec_batch: parity blocks over groups of the pieces the split call wrote (include/mi355diff.h, "Parity pieces").
+// Everything the kernels read lies on the device; waves: how many waves the parity kernel's grid holds (sized from the device).
+struct FecArgs {
+    const uint32_t *pieces;       // pieces_bytes bytes
+    uint64_t pieces_bytes;
+    const uint32_t *piece_first;  // [nrecords + 1]
+    const uint64_t *piece_pos;    // [piece_capacity + 1]
+    uint64_t piece_capacity;
+    int nrecords;
+    uint32_t group, nparity, pitch;
+    uint32_t *fec_first;          // [nrecords + 1]
+    uint32_t *fec_len;            // [group_capacity]
+    uint64_t group_capacity;
+    uint32_t *out;
+    uint64_t capacity;            // bytes of out
+};
+hipError_t launch_cwire_fec(const FecArgs &a, uint32_t workgroups, hipStream_t s);
+// mi355_cwire_fec_repair_batch: the jobs' descriptors travel as kernel arguments, at most kFecRepairJobs jobs and kFecRepairSlots
+// slots per launch (a job of 255 members fits one launch).  mode: 0 nothing lost; 1 out0 = Pxy; 2 out0 = c2 * Qxy (P absent);
+// 3 two lost: out1 = c2 * (Qxy ^ c1 * Pxy), out0 = Pxy ^ out1.  Offsets are bytes into rx, kFecAbsent: not there.
+constexpr int kFecRepairJobs = 8, kFecRepairSlots = 256;
+constexpr uint64_t kFecAbsent = ~0ull;
+struct FecRepairJob {
+    uint64_t p_off, q_off;
+    uint32_t slot0, members, fec_len, mode, c1, c2, index;   // slot0: its first slot of the launch; index: the job of the call
+};
+struct FecRepairArgs {
+    FecRepairJob job[kFecRepairJobs];
+    uint64_t off[kFecRepairSlots];
+    uint32_t len[kFecRepairSlots];
+};
+// One launch: njobs jobs of h; block k of job j to out + (2j + k)*pitch, verdict[2j + k]
+hipError_t launch_cwire_fec_repair(const uint8_t *rx, const FecRepairArgs &h, int njobs, uint8_t *out, size_t pitch, uint32_t *verdict,
+                                   hipStream_t s);
 
 // filters.hip -- every per-frame kernel takes a FrameBatch: frame f lives at base + f*stride
 struct FrameBatch {

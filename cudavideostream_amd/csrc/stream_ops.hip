@@ -2674,6 +2674,151 @@ __global__ __launch_bounds__(256) void k_cws_scan(const uint4 *blk, ulonglong2 *
     }
 }
 
+// ---- mi355_cwire_fec_batch, mi355_cwire_fec_repair_batch: parity over groups of pieces (include/mi355diff.h, "Parity pieces") -----
+//   k_fec_first  (one workgroup) : fec_first = the exclusive scan of ceil(pieces / group) per record.
+//   k_fec_make   (a grid sized from the device, 256 threads) : the waves stride over items (group, chunk of kFecChunk dwords of its
+//       parity block).  An item is wave-uniform: the group's record by binary search in fec_first, the void rule on the members'
+//       positions a lane per member, then per dword of the chunk the members from the last slot down, four loads in flight: one
+//       XOR into P, xtime and one XOR into Q.  No tables, no LDS, no atomics; the item of chunk 0 writes fec_len.
+//   k_fec_repair (a workgroup per job) : the same walk over the survivors, the constant multiplies, the header and tail tests.
+constexpr uint32_t kFecChunk = 64;
+
+__global__ __launch_bounds__(256) void k_fec_first(const FecArgs a) {
+    __shared__ uint32_t s_w[2][4];
+    uint32_t groups = 0;
+    int buf = 0;
+    for (int r0 = 0; r0 < a.nrecords; r0 += 256, buf ^= 1) {
+        const int r = r0 + (int)threadIdx.x;
+        uint32_t v = 0;
+        if (r < a.nrecords) {
+            const uint32_t c = a.piece_first[r + 1] - a.piece_first[r];
+            v = c / a.group + (c % a.group ? 1u : 0u);
+        }
+        const uint32_t before = block_exclusive_scan<4>(v, s_w[buf], groups);
+        if (r < a.nrecords) a.fec_first[r] = before;
+    }
+    if (threadIdx.x == 0) a.fec_first[a.nrecords] = groups;
+}
+
+// shift: items of a group, a power of two not below the chunks of a pitch (an item past them has nothing to do)
+__global__ __launch_bounds__(256) void k_fec_make(const FecArgs a, uint32_t shift) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint64_t nwaves = (uint64_t)gridDim.x * 4u;
+    const uint32_t total = a.fec_first[a.nrecords];
+    const uint64_t ngroups = total < a.group_capacity ? total : a.group_capacity;
+    const uint32_t cpp = (a.pitch / 4u + kFecChunk - 1u) / kFecChunk;
+    const uint64_t nitems = ngroups << shift;
+    for (uint64_t item = (uint64_t)blockIdx.x * 4u + wave; item < nitems; item += nwaves) {
+        const uint32_t chunk = (uint32_t)item & ((1u << shift) - 1u);
+        if (chunk >= cpp) continue;
+        const uint32_t g = (uint32_t)(item >> shift);
+        const FecGroup fg = fec_group(a.fec_first, a.piece_first, a.nrecords, a.group, g);
+        // the void rule, before a piece byte moves: a lane per member
+        uint32_t L = 0;
+        bool bad = fg.m == 0;
+        for (uint32_t i = lane; i < fg.m; i += 64u) {
+            const uint32_t len = fec_member_len(a.piece_pos, a.piece_capacity, a.pieces_bytes, a.pitch, fg.p0 + i);
+            bad |= len == 0;
+            L = len > L ? len : L;
+        }
+#pragma unroll
+        for (int k = 32; k >= 1; k >>= 1) {
+            const uint32_t o = (uint32_t)__shfl_xor((int)L, k, 64);
+            L = o > L ? o : L;
+        }
+        if (__ballot(bad)) L = 0;
+        if (chunk == 0 && lane == 0) a.fec_len[g] = L;
+        if ((uint64_t)chunk * kFecChunk * 4u >= L) continue;   // (a void group included)
+        const uint64_t slot = (uint64_t)g * a.nparity * a.pitch;
+        if (slot + (uint64_t)a.nparity * a.pitch > a.capacity) continue;   // no room: skipped whole
+        const uint32_t w = chunk * kFecChunk + lane;
+        uint32_t P = 0, Q = 0;
+        for (uint32_t i = fg.m; i > 0;) {
+            const uint32_t nb = i < 4u ? i : 4u;
+            uint32_t v[4];
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) {
+                v[k] = 0;
+                if (k < nb) {
+                    const uint64_t p = fg.p0 + (i - 1u - k);
+                    const uint64_t at = a.piece_pos[p];
+                    const uint32_t len = (uint32_t)(a.piece_pos[p + 1] - at);
+                    if (4u * w < len) v[k] = a.pieces[at / 4u + w];
+                }
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++)
+                if (k < nb) {
+                    P ^= v[k];
+                    Q = fec_xtime(Q) ^ v[k];
+                }
+            i -= nb;
+        }
+        if (4u * w < L) {
+            a.out[slot / 4u + w] = P;
+            if (a.nparity == 2u) a.out[(slot + a.pitch) / 4u + w] = Q;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_fec_repair(const uint8_t *rx, const FecRepairArgs h, uint8_t *out, size_t pitch, uint32_t *verdict) {
+    const FecRepairJob jb = h.job[blockIdx.x];
+    const uint32_t nw = jb.fec_len / 4u;
+    // the rebuilt dwords w of the lost slots (d1: the second of two)
+    auto word = [&](uint32_t w, uint32_t &d0, uint32_t &d1) {
+        uint32_t P = jb.p_off != kFecAbsent ? ((const uint32_t *)(rx + jb.p_off))[w] : 0u;
+        uint32_t Q = jb.q_off != kFecAbsent ? ((const uint32_t *)(rx + jb.q_off))[w] : 0u;
+        uint32_t qs = 0;
+        for (uint32_t i = jb.members; i > 0; i--) {
+            const uint64_t off = h.off[jb.slot0 + i - 1u];
+            uint32_t v = 0;
+            if (off != kFecAbsent && 4u * w < h.len[jb.slot0 + i - 1u]) v = ((const uint32_t *)(rx + off))[w];
+            P ^= v;
+            qs = fec_xtime(qs) ^ v;
+        }
+        Q ^= qs;
+        d1 = 0;
+        if (jb.mode == 1u) d0 = P;
+        else if (jb.mode == 2u) d0 = fec_mul(Q, jb.c2);
+        else {
+            d1 = fec_mul(Q ^ fec_mul(P, jb.c1), jb.c2);
+            d0 = P ^ d1;
+        }
+    };
+    uint32_t vd[2] = {0u, 0u};
+    if (jb.mode != 0u) {
+        const int nblocks = jb.mode == 3u ? 2 : 1;
+        uint32_t n[2] = {0u, 0u}, e[2] = {0u, 0u};
+        uint64_t tail[2] = {0, 0};
+        if (nw >= 2u) {   // every thread makes the headers for itself
+            word(0, n[0], n[1]);
+            word(1, e[0], e[1]);
+            for (int k = 0; k < nblocks; k++) vd[k] = fec_header_verdict(n[k], e[k], jb.fec_len, &tail[k]);
+        } else {
+            vd[0] = vd[1] = 1u;
+            tail[0] = tail[1] = jb.fec_len;
+        }
+        bool nz[2] = {false, false};
+        uint32_t *o0 = (uint32_t *)(out + (size_t)(2u * jb.index) * pitch), *o1 = (uint32_t *)(out + (size_t)(2u * jb.index + 1u) * pitch);
+        for (uint32_t w = threadIdx.x; w < nw; w += 256u) {
+            uint32_t d[2];
+            word(w, d[0], d[1]);
+            o0[w] = d[0];
+            if (nblocks == 2) o1[w] = d[1];
+            for (int k = 0; k < nblocks; k++)   // (headers and tails are whole dwords)
+                nz[k] |= 4ull * w >= tail[k] && d[k] != 0u;
+        }
+        for (int k = 0; k < 2; k++)
+            if (__syncthreads_or(nz[k])) vd[k] |= 2u;
+        if (nblocks == 1) vd[1] = 0u;
+    }
+    if (threadIdx.x == 0) {
+        verdict[2u * jb.index] = vd[0];
+        verdict[2u * jb.index + 1u] = vd[1];
+    }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 uint32_t cwa_chunks(uint32_t n) { return n ? (n + kCwaChunk - 1) / kCwaChunk : 1u; }
 uint32_t cwa_tiles(uint32_t nbytes) { return (nbytes + kCwaTile - 1) / kCwaTile; }
@@ -2728,6 +2873,25 @@ hipError_t launch_cwire_split(const CwaArgs &a, const CwaFrame *records, int nre
     hipLaunchKernelGGL(k_cws_count, dim3(nblocks), dim3(kCwsThreads), 0, s, a, blk, max_bytes);
     hipLaunchKernelGGL(k_cws_scan, dim3(1), dim3(256), 0, s, blk, base, nblocks, nrecords, o);
     hipLaunchKernelGGL(k_cws_emit, dim3(nblocks), dim3(kCwsThreads), 0, s, a, blk, base, max_bytes, o);
+    return hipGetLastError();
+}
+
+// mi355_cwire_fec_batch: the group scan, then the parity grid.  The host knows neither pieces nor groups: the grid comes from
+// the device's size and strides over what the scan found.
+hipError_t launch_cwire_fec(const FecArgs &a, uint32_t workgroups, hipStream_t s) {
+    if (a.nrecords <= 0) return hipSuccess;
+    const uint32_t cpp = (a.pitch / 4u + kFecChunk - 1u) / kFecChunk;
+    uint32_t shift = 0;
+    while ((1u << shift) < cpp) shift++;
+    hipLaunchKernelGGL(k_fec_first, dim3(1), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_fec_make, dim3(workgroups), dim3(256), 0, s, a, shift);
+    return hipGetLastError();
+}
+
+hipError_t launch_cwire_fec_repair(const uint8_t *rx, const FecRepairArgs &h, int njobs, uint8_t *out, size_t pitch, uint32_t *verdict,
+                                   hipStream_t s) {
+    if (njobs <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_fec_repair, dim3((uint32_t)njobs), dim3(256), 0, s, rx, h, out, pitch, verdict);
     return hipGetLastError();
 }
 

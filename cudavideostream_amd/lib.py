@@ -27,6 +27,8 @@ PREPARE_BATCHES, PREPARE_GRAY_CHAIN, PREPARE_RED_CLEAR, PREPARE_CONV_KXK, PREPAR
 PREPARE_EXEC_CWIRE = 32   # (not part of PREPARE_ALL)
 CROP_KEEP_INDEX = 1   # MI355_CROP_*
 CWIRE_SPLIT_BLOCK = 65536   # MI355_CWIRE_SPLIT_BLOCK
+FEC_BAD_HEADER, FEC_BAD_TAIL = 1, 2   # MI355_FEC_BAD_*
+FEC_ABSENT = 0xFFFFFFFFFFFFFFFF   # MI355_FEC_ABSENT
 CWIRE_BAD_CODES, CWIRE_BAD_RANGE, CWIRE_BAD_PAD, CWIRE_BAD_ESCAPE, CWIRE_BAD_HEADER = 1, 2, 4, 8, 16   # MI355_CWIRE_BAD_*
 
 
@@ -139,6 +141,15 @@ SYMBOLS = {
                                                 C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "mi355_cwire_split_pieces_max": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_size_t]),
     "mi355_cwire_split_bytes_max": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_size_t]),
+    "mi355_cwire_fec_groups_max": (C.c_size_t, [C.c_size_t, C.c_int, C.c_int]),
+    "mi355_cwire_fec_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t,
+                                       C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "mi355_cwire_fec_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                        C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "mi355_cwire_fec_repair_host": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+    "mi355_cwire_fec_repair_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "mi355_state_tiles": (C.c_size_t, [C.c_size_t]),
     "mi355_state_digest_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "mi355_state_digest_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),

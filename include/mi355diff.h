@@ -99,7 +99,8 @@ typedef struct mi355_config {
  *      + mi355_diff_consecutive_batch (additions only);
  *      + mi355_cwire_split_host, mi355_cwire_split_cwire_batch, mi355_cwire_split_pieces_max, mi355_cwire_split_bytes_max,
  *      MI355_CWIRE_SPLIT_BLOCK (additions only);
- *      + mi355_thumb_cwire_host, mi355_thumb_cwire_batch (additions only) */
+ *      + mi355_thumb_cwire_host, mi355_thumb_cwire_batch (additions only);
+ *      + mi355_cwire_fec_* (additions only) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -734,6 +735,105 @@ int mi355_cwire_split_cwire_batch(mi355_core *core, const void *d_cwire_in, cons
                                   size_t piece_capacity, void *d_cwire_out, size_t capacity_bytes);
 size_t mi355_cwire_split_pieces_max(uint32_t n, uint32_t e, size_t max_bytes);
 size_t mi355_cwire_split_bytes_max(uint32_t n, uint32_t e, size_t max_bytes);
+
+/* Parity pieces for the datagram path: K parity datagrams per group of G pieces, so that any K losses inside a group are rebuilt
+ * by the receiver itself -- no digests up, no refresh records down, and a one-way or multicast link needs no back channel.  What
+ * is lost beyond K of a group stays the resync calls' business.
+ *   Input: what mi355_cwire_split_cwire_batch wrote -- the piece buffer of pieces_bytes bytes, piece_first (uint32[nrecords + 1])
+ *   and piece_pos (uint64[piece_capacity + 1]); piece p is the bytes [piece_pos[p], piece_pos[p + 1]).
+ *   Groups: record r has c_r = piece_first[r + 1] - piece_first[r] pieces and ceil(c_r / G) groups; group j of record r has the
+ *   members at slots i = 0 .. m - 1, m = min(G, c_r - j*G), the member at slot i being piece piece_first[r] + j*G + i.  G (group) is
+ *   in 1 .. 255, K (nparity) is 1 or 2; groups never span records.  fec_first, uint32[nrecords + 1], is the exclusive scan of the
+ *   groups per record and always exact; global group g = fec_first[r] + j.
+ *   Parity: L_g is the largest member length of the group.  Every member is read as little-endian dwords, zero-extended to L_g.
+ *   P[w] is the XOR of the members' words w.  Q[w] is the XOR over the slots i of 2^i * D_i[w], byte by byte in GF(2^8) modulo
+ *   x^8 + x^4 + x^3 + x^2 + 1 (0x11D) -- equally Horner's rule from the last slot down, Q = xtime(Q) ^ D_i, with xtime(v) =
+ *   ((v & 0x7f7f7f7f) << 1) ^ (((v >> 7) & 0x01010101) * 0x1d) on a packed dword.  The powers 2^0 .. 2^254 are distinct, hence
+ *   G <= 255.
+ *   Outputs, at a fixed pitch (the prototypes' spacing_bytes): fec_len, uint32[group_capacity]: entries g < min(total groups, group_capacity) are written and
+ *   exact, later entries are untouched.  Parity block q of group g (0: P, 1: Q) is the L_g bytes at out + (g*K + q)*pitch; bytes
+ *   [L_g, pitch) of a slot are never written.  pitch is a multiple of 4 in [64, 65536], normally the split call's max_bytes.  A
+ *   group with g >= group_capacity or (g + 1)*K*pitch > capacity_bytes is skipped whole and groups behind it that fit are written.
+ *   mi355_cwire_fec_groups_max(piece_capacity, nrecords, group) = floor(piece_capacity / group) + nrecords is never below the
+ *   groups of piece_capacity pieces in nrecords records (0 for a group outside 1 .. 255).
+ *   Void groups: a group is void when a member is absent (p >= piece_capacity, or piece_pos[p + 1] > pieces_bytes) or malformed
+ *   (piece_pos[p + 1] < piece_pos[p]; position or length not a multiple of 4; length 0; length > pitch).  It has fec_len[g] = 0
+ *   and none of its parity bytes is written.  This is the memory-safety rule: nothing is read outside the three input extents as
+ *   stated, nothing is written outside the outputs.  Tables that the split call wrote are always consistent; for any other table
+ *   only that guarantee holds.
+ *   Laws: a group of one member has P == Q == that member; fec_first depends on piece_first alone; parity of the pieces of
+ *   canonical records, then any loss of at most K of a group's m + K datagrams, then repair gives back the lost pieces byte for
+ *   byte; every rebuilt piece is canonical (mi355_cwire_check_host word 0 == 0); applying survivors and rebuilt pieces in any
+ *   order gives the state the record gives.
+ *   mi355_cwire_fec_host is the definition: plain C++, no core, no HIP call.  mi355_cwire_fec_batch is bit-identical to it in
+ *   fec_first, fec_len (as far as written) and every written parity byte; asynchronous on the core's stream, in call order behind
+ *   the split call with no synchronisation in between; nothing is allocated and the core's state is untouched.
+ *   Refused with MI355_ERR_INVALID before anything is launched or written: a null core; nrecords outside [0, max_batch]; group,
+ *   nparity or pitch out of range; with nrecords > 0 a null pointer; the 4-byte tables, d_pieces or d_out not 4-byte aligned;
+ *   d_piece_pos not 8-byte aligned; any output region overlapping an input region or another output.  nrecords == 0 writes
+ *   fec_first[0] = 0 and nothing else.
+ * Repair of one group, mi355_cwire_fec_repair_host (the definition): slot[i] is the surviving member at slot i (slot_len[i]
+ * bytes) or NULL for a lost one; p and q are the group's parity blocks or NULL; fec_len is the group's L_g.  u is the number of
+ * NULL slots, a < b the lost slots.  u == 0 writes nothing; u >= 1 writes fec_len bytes per lost slot, out0 for a, out1 for b.
+ * With Pxy = P ^ (XOR of the survivors) and Qxy = Q ^ (XOR of 2^i * survivor i): one lost and P present, D_a = Pxy; one lost and
+ * only Q present, D_a = inv(2^a) * Qxy; two lost, D_b = inv(2^a ^ 2^b) * (Qxy ^ 2^a * Pxy) and D_a = Pxy ^ D_b.
+ *   verdict[k] of rebuilt block k: bit 0 (MI355_FEC_BAD_HEADER): its header {n, e} has n == 0, e > n or
+ *   mi355_cwire_frame_bytes(n, e) > fec_len (a block shorter than a header has it set, too); bit 1 (MI355_FEC_BAD_TAIL): a nonzero
+ *   byte at or past mi355_cwire_frame_bytes(n, e).  Zero for what the sender made, and zero for a block that is not rebuilt.  A
+ *   clean verdict is no replacement for mi355_cwire_check_* before applying.
+ *   Refused, with the outputs untouched: members outside 1 .. 255; fec_len 0 or not a multiple of 4; a surviving length 0, not a
+ *   multiple of 4 or > fec_len; u > (p != NULL) + (q != NULL); a needed output NULL (verdict is needed when u >= 1).
+ *   Everything is wordwise, so the form also works on a common prefix of all blocks: from the first 8 bytes of each datagram
+ *   (fec_len = 8, every length 8) a receiver gets a lost piece's {n, e} without touching the payload; the verdict of a prefix
+ *   says nothing.
+ * Repair of many groups on a core, mi355_cwire_fec_repair_batch: job j has the slots h_job_first[j] .. h_job_first[j + 1] of
+ * h_slot_off (byte offsets into d_rx, MI355_FEC_ABSENT: lost) and h_slot_len, the parity blocks at h_parity_off[2j] (P) and
+ * [2j + 1] (Q) (MI355_FEC_ABSENT: not there) and h_fec_len[j].  Rebuilt block k of job j is the h_fec_len[j] bytes at d_out +
+ * (2j + k)*pitch, a job with one loss writes block 0 only; d_verdict, uint32[njobs][2], is written for every job, the words of
+ * blocks not rebuilt 0.  Byte for byte the host form's output.  All descriptors are host arrays and may be reused when the call
+ * returns: they travel as kernel arguments, 8 jobs and 256 slots per launch at the most, as h_place of the wall does (losses are
+ * rare: a launch per job or two is fine).  Asynchronous on the core's stream; nothing is allocated and nothing synchronises; the
+ * GF constants of a job are computed on the host.
+ *   Refused with MI355_ERR_INVALID before anything is launched or written: whatever the host form refuses, per job; an offset not
+ *   4-byte aligned or a block reaching past rx_bytes; h_fec_len[j] > pitch; njobs outside [0, max_batch]; d_rx, d_out, d_verdict
+ *   or pitch not a multiple of 4; d_out or d_verdict overlapping d_rx or each other; with njobs > 0 a null pointer.  A job with
+ *   nothing lost is legal and writes only its two verdict words.
+ * The parity call: one workgroup scans the groups per record, then a grid sized from the device (the host does not know the
+ * piece count and does not wait for it) whose waves stride over (group, 256 bytes of its parity block): the group's record by
+ * binary search in fec_first, the void rule on the members' positions before a piece byte moves, then per dword the members
+ * from the last slot down, one coalesced dword load bounded by the member's length, one XOR into P, xtime and one XOR into Q.
+ * No tables, no LDS, no atomics, no workgroup waits on another; pieces are 4-byte aligned only, so every load is one dword.
+ * The repair call: a workgroup per job does the same walk over the survivors, then the constant multiplies (eight shift-and-XOR
+ * steps on packed dwords under a wave-uniform constant), the header and tail tests and one verdict store per block.
+ * Measured (profiles/multi_fec.json: tools/bench_multi.py --legs fec; 1080p, T = 1, M = 1400, G = 8, median of five rounds, against
+ * mi355_cwire_split_cwire_batch on the same records in the same run; the parity equals the host form's at every point and the
+ * rebuilt pieces the pieces), us per input record at S = 4 / 16 / 64: webcam-like input (137 k entries per record, 201 pieces, 26
+ * groups, 71 kB of parity at K = 2) split 52.29 / 13.22 / 3.46, parity at K = 1 2.49 / 0.59 / 0.24, at K = 2 2.62 / 0.53 / 0.24; local
+ * input (a block moving over a still background, 4.8 k entries, 9 pieces, 2 groups) split 10.36 / 2.59 / 0.72, parity at K = 1 2.45 /
+ * 0.55 / 0.20, at K = 2 2.46 / 0.55 / 0.15.  The spread of the rounds is 0.1 - 10 % for the split call and 4 - 47 % for the parity
+ * call (126 % at one K = 1 point): at a few microseconds a call it is the host's enqueue rate that is timed.  The expectation -- the
+ * parity call at K = 2 no slower than the split call that feeds it, at any S, by more than the rounds' spread -- is met at every
+ * point (0.04 - 0.07 of the split call on webcam-like input, 0.21 - 0.24 on the local input): it reads once what split wrote and
+ * writes a quarter of it, in two launches where split takes nine.  The repair call, one job per stream, reported and not judged:
+ * 2.6 / 1.0 / 1.1 us per job for one lost piece and 2.7 / 1.1 / 1.1 for two, on either input.  Not profiled per kernel.  DESIGN.md
+ * section 4, "Parity for the datagram path". */
+#define MI355_FEC_BAD_HEADER 1u
+#define MI355_FEC_BAD_TAIL 2u
+#define MI355_FEC_ABSENT UINT64_MAX
+size_t mi355_cwire_fec_groups_max(size_t piece_capacity, int nrecords, int group);
+int mi355_cwire_fec_host(const void *pieces, size_t pieces_bytes, const uint32_t *piece_first, const uint64_t *piece_pos,
+                         size_t piece_capacity, int nrecords, int group, int nparity, size_t spacing_bytes, uint32_t *fec_first,
+                         uint32_t *fec_len, size_t group_capacity, void *out, size_t capacity_bytes);
+int mi355_cwire_fec_batch(mi355_core *core, const void *d_pieces, size_t pieces_bytes, const void *d_piece_first,
+                          const void *d_piece_pos, size_t piece_capacity, int nrecords, int group, int nparity, size_t spacing_bytes,
+                          void *d_fec_first, void *d_fec_len, size_t group_capacity, void *d_out, size_t capacity_bytes);
+int mi355_cwire_fec_repair_host(int members, const void *const *slot /* [members], NULL: lost */, const uint32_t *slot_len,
+                                const void *p /* or NULL */, const void *q /* or NULL */, uint32_t fec_len, void *out0, void *out1,
+                                uint32_t verdict[2]);
+int mi355_cwire_fec_repair_batch(mi355_core *core, const void *d_rx, size_t rx_bytes, int njobs,
+                                 const uint32_t *h_job_first /* [njobs + 1] */, const uint64_t *h_slot_off, const uint32_t *h_slot_len,
+                                 const uint64_t *h_parity_off /* [njobs][2] */, const uint32_t *h_fec_len /* [njobs] */, void *d_out,
+                                 size_t spacing_bytes, void *d_verdict /* uint32[njobs][2] */);
 
 /* A tick held to a budget: the sender's rate control.  The nstreams compact records mi355_diff_multi_cwire_batch just wrote
  * (back to back where h_counts[s] / h_escapes[s] put them; the headers come from the host and are not trusted in the buffer, as

@@ -78,6 +78,13 @@ S, on the webcam-like and the local input:
   split_8972     the same at max_bytes = 8972 (a jumbo frame).
 The expectation to test: either no slower than `coalesce` by more than the rounds' spread (`split_M_no_slower_than_coalesce`).
 
+The fec leg (--legs fec, a run of its own: `--legs fec --streams 4,16,64 > profiles/multi_fec.json`) measures the parity call behind
+the split call on the split leg's inputs (max_bytes = 1400, groups of 8), us per input record, and the repair call, us per job:
+  split          mi355_cwire_split_cwire_batch at max_bytes = 1400 on the records of one tick;
+  fec_k1, fec_k2 mi355_cwire_fec_batch with one and two parity blocks per group on the pieces it left;
+  repair_one, repair_two  mi355_cwire_fec_repair_batch, one job per stream, one and two lost pieces (reported, not judged).
+The expectation to test: fec_k2 no slower than `split` by more than the rounds' spread (`fec_k2_no_slower_than_split`).
+
 The mosaic leg (--legs mosaic, a run of its own: `--legs mosaic --streams 4,16 > profiles/multi_mosaic.json`) measures the call that
 places S cameras side by side on one canvas (a C x C grid of whole frames, C = ceil(sqrt(S)): 2x2 into 3840x2160 and 4x4 into
 7680x4320 at 1080p), in microseconds per input record, ONE JSON line: T = 1 and T = 16, on the webcam-like and the local input:
@@ -1428,6 +1435,149 @@ def run_split(W, H, S, rounds, kind, limits=(1400, 8972)):
     return out
 
 
+def run_fec(W, H, S, rounds, kind, M=1400, G=8):
+    """The fec leg for one S and one input, T = 1 -> its dictionary.  split: mi355_cwire_split_cwire_batch at max_bytes = M on the
+    records of one tick; fec_k1 / fec_k2: mi355_cwire_fec_batch with K = 1 / 2 parity blocks per group of G on the pieces that call
+    left; repair_one / repair_two: mi355_cwire_fec_repair_batch with one job per stream, the first piece (the first two) of its
+    first group lost.  All on one core's own stream, alternating within every round.  Before anything is timed the parity is
+    compared with mi355_cwire_fec_host and the rebuilt pieces with the pieces."""
+    import numpy as np
+    from cudavideostream_amd import (CUDACore, cwire_bytes_max, cwire_fec_groups_max, cwire_fec_host, cwire_split_bytes_max, cwire_split_host,
+                                     cwire_split_pieces_max, lib)
+    dev = torch.device("cuda", 0)
+    n, T = 3 * W * H, 1
+    passes = 2 * max(1, 1024 // S)                     # ~2 k records per timed window
+    if kind == "webcam":                                # run_split's input
+        _, web = synth.webcam_stream(S + 1, W, H, device=dev)
+        web = web.reshape(S + 1, n)
+        states0, fwd = web[0:S].clone(), web[1:].reshape(S, T, n)
+    else:
+        states0, fwd = local_streams(S, T, W, H, dev)
+    assert S * n < (1 << 32), "one call per tick: max_batch * N < 2^32"
+    cwcap = cwire_bytes_max(n, S)
+    with CUDACore(W, H, max_batch=S) as server:
+        d_off = torch.zeros(S + 1, dtype=torch.int32, device=dev)
+        d_pos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
+        d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        server.diff_multi_stream_cwire_batch(fwd, states0.clone(), S, T, d_off, d_pos, d_cw, cwcap)
+        server.synchronize()
+        pos = d_pos.cpu().numpy().astype(np.int64)
+        counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
+        escapes = ((np.diff(pos) - 8 - 2 * ((counts.astype(np.int64) + 3) & ~3)) // 4).astype(np.uint32)
+        recs = d_cw[:int(pos[S])].clone()
+        del d_cw
+    pcap = sum(cwire_split_pieces_max(c, e, M) for c, e in zip(counts, escapes))
+    bcap = sum(cwire_split_bytes_max(c, e, M) for c, e in zip(counts, escapes))
+    gcap = cwire_fec_groups_max(pcap, S, G)
+    d_first = torch.zeros(S + 1, dtype=torch.int32, device=dev)
+    d_ppos = torch.zeros(pcap + 1, dtype=torch.int64, device=dev)
+    d_all = torch.zeros(bcap + 2 * gcap * M, dtype=torch.uint8, device=dev)   # the pieces, then the parity blocks: the repair's d_rx
+    d_pieces, d_par = d_all[:bcap], d_all[bcap:]
+    d_ffirst = torch.zeros(S + 1, dtype=torch.int32, device=dev)
+    d_flen = torch.zeros(gcap, dtype=torch.int32, device=dev)
+    d_rep = torch.zeros(2 * S * M, dtype=torch.uint8, device=dev)
+    d_vd = torch.zeros(2 * S, dtype=torch.int32, device=dev)
+    relay = CUDACore(W, H, max_batch=S)
+    torch.cuda.synchronize()
+
+    def split():
+        relay.cwire_split_cwire_batch(recs, counts, escapes, S, M, d_first, d_ppos, pcap, d_pieces, bcap)
+
+    def fec(K):
+        relay.cwire_fec_batch(d_pieces, bcap, d_first, d_ppos, pcap, S, G, K, M, d_ffirst, d_flen, gcap, d_par, gcap * K * M)
+
+    # the pieces and the parity are the host forms', at both K
+    wf, wp, wo = cwire_split_host(recs.cpu().numpy(), counts, escapes, n, M, piece_capacity=pcap, capacity_bytes=bcap)
+    total = int(wf[-1])
+    out = {"input": kind, "streams": S, "frames": T, "passes": passes, "max_bytes": M, "group": G,
+           "input_entries_per_stream": round(int(counts.sum()) / S, 1), "input_bytes_per_stream": round(int(pos[S]) / S, 1),
+           "pieces_per_stream": round(total / S, 1), "piece_bytes_per_stream": round(int(wp[total]) / S, 1)}
+    for K in (1, 2):
+        split()
+        fec(K)                                          # behind the split call, no synchronisation in between
+        relay.synchronize()
+        hf, hl, ho = cwire_fec_host(wo, bcap, wf, wp, pcap, G, K, M, group_capacity=gcap, capacity_bytes=gcap * K * M)
+        ng = int(hf[-1])
+        assert np.array_equal(d_pieces[:int(wp[total])].cpu().numpy(), wo[:int(wp[total])])
+        assert np.array_equal(d_ffirst.cpu().numpy().view(np.uint32), hf) and np.array_equal(d_flen[:ng].cpu().numpy().view(np.uint32), hl[:ng])
+        got = d_par[:ng * K * M].cpu().numpy().reshape(ng * K, M)
+        want = ho[:ng * K * M].reshape(ng * K, M)
+        for g in range(ng):
+            L = int(hl[g])
+            assert L > 0 and np.array_equal(got[g * K:(g + 1) * K, :L], want[g * K:(g + 1) * K, :L]), (K, g)
+        out[f"groups_per_stream_k{K}"] = round(ng / S, 1)
+        out[f"parity_bytes_per_stream_k{K}"] = round(K * int(hl[:ng].astype(np.int64).sum()) / S, 1)
+    # (K = 2 is what d_par holds now)  one repair job per stream with a piece: its first group, the first piece or two lost
+    A = lib.FEC_ABSENT
+    jobs = {}
+    for lose in (1, 2):
+        job_first, slot_off, slot_len, par_off, fec_len, lost = [0], [], [], [], [], []
+        for s in range(S):
+            c = int(wf[s + 1]) - int(wf[s])
+            if c == 0:
+                continue
+            m, p0, g = min(G, c), int(wf[s]), int(hf[s])
+            gone = list(range(min(lose, m)))
+            for i in range(m):
+                slot_off.append(A if i in gone else int(wp[p0 + i]))
+                slot_len.append(int(wp[p0 + i + 1]) - int(wp[p0 + i]))
+            par_off.append([bcap + 2 * g * M, bcap + (2 * g + 1) * M if len(gone) == 2 else A])
+            fec_len.append(int(hl[g]))
+            job_first.append(len(slot_off))
+            lost.append([p0 + i for i in gone])
+        jobs[lose] = (len(fec_len), np.array(job_first, np.uint32), np.array(slot_off, np.uint64), np.array(slot_len, np.uint32),
+                      np.array(par_off, np.uint64), np.array(fec_len, np.uint32), lost)
+
+    def repair(lose):
+        nj, jf, so, sl, po, fl, _ = jobs[lose]
+        relay.cwire_fec_repair_batch(d_all, d_all.numel(), nj, jf, so, sl, po, fl, d_rep, M, d_vd)
+
+    for lose in (1, 2):
+        repair(lose)
+        relay.synchronize()
+        rep, vd = d_rep.cpu().numpy().reshape(2 * S, M), d_vd.cpu().numpy()
+        for j, ps in enumerate(jobs[lose][6]):
+            for k, p in enumerate(ps):
+                a, b = int(wp[p]), int(wp[p + 1])
+                assert vd[2 * j + k] == 0 and np.array_equal(rep[2 * j + k, :b - a], wo[a:b]), (lose, j, k)
+        out[f"repair_jobs_{lose}"] = jobs[lose][0]
+
+    def timed(call):
+        def leg():
+            for _ in range(passes):
+                call()
+            relay.synchronize()
+        return leg
+
+    table = {"split": timed(split), "fec_k1": timed(lambda: fec(1)), "fec_k2": timed(lambda: fec(2)),
+             "repair_one": timed(lambda: repair(1)), "repair_two": timed(lambda: repair(2))}
+    split()
+    relay.synchronize()
+    times = {}
+    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
+        for name, leg in table.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            leg()
+            dt = time.perf_counter() - t0
+            if r:
+                per = jobs[1][0] if name.startswith("repair") else S
+                times.setdefault(name, []).append(dt * 1e6 / (passes * max(per, 1)))
+    med, spread = {}, {}
+    for name in table:
+        st = stats(times[name])
+        st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
+        out[name + ("_us_per_job" if name.startswith("repair") else "_us_per_record")] = st
+        med[name], spread[name] = st["median"], st["max"] - st["min"]
+    for K in (1, 2):
+        out[f"fec_k{K}_over_split"] = round(med[f"fec_k{K}"] / med["split"], 3)
+    # the expectation: at K = 2 no slower than the split call that feeds it by more than the rounds' spread (of either leg)
+    out["fec_k2_no_slower_than_split"] = bool(med["fec_k2"] <= med["split"] + max(spread["fec_k2"], spread["split"]))
+    relay.close()
+    return out
+
+
 def run_mosaic(W, H, S, T, rounds, kind):
     """The mosaic leg for one (S, T) and one input -> its dictionary.  mosaic: mi355_cwire_mosaic_cwire_batch on the burst's
     records, whole frames in a C x R grid.  state_route: mi355_apply_multi_stream_cwire_batch onto states the relay holds,
@@ -1608,7 +1758,7 @@ def main():
     ap.add_argument("--steps", type=int, default=8, help="K: webcam frames a stream walks through")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--legs", default="multi,cores_loop,pairs",
-                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or crop alone; or split alone; or mosaic alone; or budget alone; or activity alone; or check alone; or refresh alone; or wall alone; or thumb alone")
+                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or crop alone; or split alone; or fec alone; or mosaic alone; or budget alone; or activity alone; or check alone; or refresh alone; or wall alone; or thumb alone")
     ap.add_argument("--frames", default="4,16,64", help="burst, burst_client and coalesce legs: T, frames per stream and call")
     a = ap.parse_args()
     have = load_library()
@@ -1668,6 +1818,18 @@ def main():
         ok = all(p[k] for p in per for k in p if k.endswith("_no_slower_than_coalesce"))
         print(json.dumps({"bench": "multi_split", "size": f"{W}x{H}", "rounds": a.rounds, "split": per,
                           "verdict": "no slower than coalesce at every point" if ok else "slower than coalesce at some point"}),
+              flush=True)
+        return
+    if a.legs == "fec":
+        per = []
+        for S in (int(v) for v in a.streams.split(",")):
+            for kind in ("webcam", "local"):
+                per.append(run_fec(W, H, S, a.rounds, kind))
+                print(f"fec S={S} {kind}: done", file=sys.stderr, flush=True)
+                torch.cuda.empty_cache()
+        ok = all(p["fec_k2_no_slower_than_split"] for p in per)
+        print(json.dumps({"bench": "multi_fec", "size": f"{W}x{H}", "rounds": a.rounds, "fec": per,
+                          "verdict": "parity at K = 2 no slower than split at every point" if ok else "parity at K = 2 slower than split at some point"}),
               flush=True)
         return
     if a.legs == "mosaic":

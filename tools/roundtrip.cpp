@@ -11,7 +11,7 @@
 // (ActivityCheck, RecordCheck, WallCheck, ThumbViewer), that is that mode.
 //
 //   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B]
-//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check] | --resync K [--burst B] | --crop X,Y,W,H [--burst K] | --mosaic CxR [--burst K] | [--burst K --coalesce] --datagram BYTES | --thumb K [--burst T] [--thumb-drop TICK]] [--wall K]]
+//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check] | --resync K [--burst B] | --crop X,Y,W,H [--burst K] | --mosaic CxR [--burst K] | [--burst K --coalesce] --datagram BYTES [--fec G[,K]] | --thumb K [--burst T] [--thumb-drop TICK]] [--wall K]]
 //   exit status 0 = all checks passed
 #include <algorithm>
 #include <cstdint>
@@ -1033,9 +1033,18 @@ static int run_multi_burst_coalesce(int w, int h, int T, int S, int K) {
 // common count, and applies them with mi355_apply_multi_stream_cwire_batch, kDatagramRound pieces of every camera per call.
 // After every tick each camera's state at the receiver must equal the frame of a host client (mi355_cwire_apply_host) that applied
 // the original records, and the sender's state.  The line also says how many pieces and bytes a tick made.
+// --fec G[,K] (G = 1 .. 255 pieces per group, K = 1 or 2 parity datagrams per group, default 1): the link loses datagrams and the
+// receiver rebuilds them.  The relay calls mi355_cwire_fec_batch behind the split call with no wait in between; every parity block
+// is one more datagram.  The side information of a datagram -- stream, group, slot, members, fec_len, parity or not -- is this
+// tool's own framing, outside the payload.  The seeded generator loses 0 .. K of every group's m + K datagrams, class by class in
+// turn: nothing; one piece; a piece and P; a piece and Q; two pieces; parity only -- and the run fails unless it met every class
+// that K allows.  The receiver takes the lost pieces' headers from the 8-byte prefixes (mi355_cwire_fec_repair_host), rebuilds what
+// is missing with ONE mi355_cwire_fec_repair_batch per tick, requires clean verdicts, checks the rebuilt pieces with
+// mi355_cwire_check_batch and then applies survivors and rebuilt pieces in a shuffled order as without --fec.  Losing more than K
+// of a group is the resync mode's business, not this one's.
 static const int kDatagramRound = 64;
 
-static int run_multi_datagram(int w, int h, int T, int S, int K, long max_bytes) {
+static int run_multi_datagram(int w, int h, int T, int S, int K, long max_bytes, int G, int Kp) {
     const bool coalesce = K > 0;
     if (!coalesce) K = 1;
     Session ss(w, h);
@@ -1057,6 +1066,24 @@ static int run_multi_datagram(int w, int h, int T, int S, int K, long max_bytes)
     std::vector<uint32_t> roff(S + 1), first(S + 1), cnt(S), esc(S), pc((size_t)S * kDatagramRound), pe((size_t)S * kDatagramRound);
     std::vector<uint64_t> rpos(S + 1), ppos(pcap + 1);
     std::vector<std::vector<uint32_t>> order(S);
+    // --fec: the relay's parity outputs; the receiver's copy of what arrived (pieces, then parity blocks), its rebuilt blocks
+    const size_t gcap = G ? mi355_cwire_fec_groups_max(pcap, S, G) : 0, par_cap = gcap * (size_t)Kp * M;
+    const int jobs_cap = S * kDatagramRound;   // (the receiver's max_batch)
+    void *d_ffirst = nullptr, *d_flen = nullptr, *d_par = nullptr, *d_frx = nullptr, *d_rep = nullptr, *d_vd = nullptr, *d_chk = nullptr;
+    if (G) {
+        d_ffirst = ss.dev(relay.core, sizeof(uint32_t) * (S + 1));
+        d_flen = ss.dev(relay.core, sizeof(uint32_t) * gcap);
+        d_par = ss.dev(relay.core, par_cap);
+        d_frx = ss.dev(rcv.core, bcap + par_cap);
+        d_rep = ss.dev(rcv.core, 2 * (size_t)jobs_cap * M);
+        d_vd = ss.dev(rcv.core, sizeof(uint32_t) * 6 * (size_t)jobs_cap);   // (the repair's verdicts, then the check's)
+        d_chk = ss.dev(rcv.core, (size_t)jobs_cap * M);
+        if (!ss.ok()) return 1;
+    }
+    std::vector<uint8_t> par(par_cap), par_arrived(par_cap), rebuilt(G ? 2 * (size_t)jobs_cap * M : 0), chk(G ? (size_t)jobs_cap * M : 0);
+    std::vector<uint32_t> ffirst(S + 1), flen(gcap), job_first, slot_len, job_len, vd(4 * (size_t)jobs_cap), job_piece;
+    std::vector<uint64_t> slot_off, par_off;
+    size_t parity_datagrams = 0, parity_bytes = 0, pieces_lost = 0, pieces_rebuilt = 0, met[5] = {0, 0, 0, 0, 0}, turn = 0;
     if (cams.start(ss, tx, rcv, host_frames.data())) return 1;
     size_t received = 0, datagrams = 0, datagram_bytes = 0, largest = 0;
     int max_err = 0, calls = 0, steps = 0;
@@ -1088,6 +1115,8 @@ static int run_multi_datagram(int w, int h, int T, int S, int K, long max_bytes)
             }
         }
         OK(mi355_cwire_split_cwire_batch(relay.core, d_rec, cnt.data(), esc.data(), S, M, d_first, d_ppos, pcap, d_pieces, bcap));
+        if (G)   // the parity blocks of what the split call is still writing: same stream, no wait
+            OK(mi355_cwire_fec_batch(relay.core, d_pieces, bcap, d_first, d_ppos, pcap, S, G, Kp, M, d_ffirst, d_flen, gcap, d_par, par_cap));
         calls++;
         OK(mi355_download(relay.core, first.data(), d_first, sizeof(uint32_t) * (S + 1)));
         const size_t np = first[S];
@@ -1104,6 +1133,116 @@ static int run_multi_datagram(int w, int h, int T, int S, int K, long max_bytes)
         }
         datagrams += np;
         datagram_bytes += (size_t)ppos[np];
+        if (G) {
+            // ---- the parity datagrams, and what the link loses of every group
+            OK(mi355_download(relay.core, ffirst.data(), d_ffirst, sizeof(uint32_t) * (S + 1)));
+            const size_t ng = ffirst[S];
+            if (ng > gcap) { fprintf(stderr, "more groups than their bound\n"); return 1; }
+            if (ng) OK(mi355_download(relay.core, flen.data(), d_flen, sizeof(uint32_t) * ng));
+            if (ng) OK(mi355_download(relay.core, par.data(), d_par, ng * (size_t)Kp * M));
+            job_first.assign(1, 0u);
+            slot_off.clear(); slot_len.clear(); par_off.clear(); job_len.clear(); job_piece.clear();
+            for (int s = 0; s < S; s++)
+                for (uint32_t g = ffirst[s]; g < ffirst[s + 1]; g++) {
+                    const uint32_t p0 = first[s] + (g - ffirst[s]) * (uint32_t)G, m = std::min((uint32_t)G, first[s + 1] - p0), L = flen[g];
+                    if (L == 0 || L > M) { fprintf(stderr, "tick %d: group %u of camera %d has fec_len %u\n", t0, g, s, L); return 1; }
+                    for (int q = 0; q < Kp; q++) {
+                        const size_t at = ((size_t)g * Kp + q) * M;
+                        if (!ss.send(par.data() + at, par_arrived.data() + at, L)) return 1;
+                    }
+                    parity_datagrams += Kp;
+                    parity_bytes += (size_t)Kp * L;
+                    // the classes in turn: 0 nothing, 1 one piece, 2 a piece and P, 3 a piece and Q, 4 two pieces, 5 parity only
+                    const int cls = Kp == 2 ? (int)(turn % 6) : (int)(turn % 3 == 2 ? 5 : turn % 3);
+                    turn++;
+                    int lost[2] = {-1, -1};
+                    bool have_p = true, have_q = Kp == 2;
+                    if (cls >= 1 && cls <= 4) lost[0] = (int)(rnd() % m);
+                    if (cls == 4 && m >= 2) {
+                        lost[1] = (int)((lost[0] + 1 + rnd() % (m - 1)) % m);
+                        if (lost[1] < lost[0]) std::swap(lost[0], lost[1]);
+                    }
+                    if (cls == 2) have_p = false;
+                    if (cls == 3) have_q = false;
+                    if (cls == 5) { if (Kp == 2 && (rnd() & 1)) have_q = false; else have_p = false; }
+                    if (cls >= 1) met[cls == 4 && m < 2 ? 0 : cls - 1]++;
+                    if (!have_p) memset(par_arrived.data() + (size_t)g * Kp * M, 0xEE, L);
+                    if (Kp == 2 && !have_q) memset(par_arrived.data() + ((size_t)g * Kp + 1) * M, 0xEE, L);
+                    if (lost[0] < 0) continue;
+                    // ---- receiver: the lost pieces' headers from the 8-byte prefixes; then one job of the tick's repair call
+                    const void *pre[255];
+                    uint32_t pre_len[255], hdr[2][2] = {{0, 0}, {0, 0}}, pre_vd[2];
+                    for (uint32_t i = 0; i < m; i++) {
+                        const bool gone = (int)i == lost[0] || (int)i == lost[1];
+                        const size_t at = (size_t)ppos[p0 + i], len = (size_t)(ppos[p0 + i + 1] - ppos[p0 + i]);
+                        if (gone) memset(arrived.data() + at, 0xEE, len);
+                        pre[i] = gone ? nullptr : arrived.data() + at;
+                        pre_len[i] = 8;
+                        slot_off.push_back(gone ? MI355_FEC_ABSENT : (uint64_t)at);
+                        slot_len.push_back((uint32_t)len);
+                        if (gone) job_piece.push_back(p0 + i);
+                    }
+                    if (lost[1] < 0) job_piece.push_back(UINT32_MAX);
+                    const uint8_t *pp = par_arrived.data() + (size_t)g * Kp * M, *pq = pp + M;
+                    OK(mi355_cwire_fec_repair_host((int)m, pre, pre_len, have_p ? pp : nullptr, have_q ? pq : nullptr, 8, hdr[0], hdr[1], pre_vd));
+                    for (int k = 0; k < 2 && lost[k] >= 0; k++)
+                        if (mi355_cwire_frame_bytes(hdr[k][0], hdr[k][1]) != (size_t)(ppos[p0 + lost[k] + 1] - ppos[p0 + lost[k]])) {
+                            fprintf(stderr, "tick %d: the prefix repair gave a wrong header for piece %u\n", t0, p0 + lost[k]);
+                            return 1;
+                        }
+                    par_off.push_back(have_p ? (uint64_t)(bcap + (size_t)g * Kp * M) : MI355_FEC_ABSENT);
+                    par_off.push_back(have_q ? (uint64_t)(bcap + ((size_t)g * Kp + 1) * M) : MI355_FEC_ABSENT);
+                    job_len.push_back(L);
+                    job_first.push_back((uint32_t)slot_off.size());
+                    pieces_lost += lost[1] >= 0 ? 2 : 1;
+                }
+            const int njobs = (int)job_len.size();
+            if (njobs > jobs_cap) { fprintf(stderr, "tick %d: %d groups to repair, the receiver's core takes %d\n", t0, njobs, jobs_cap); return 1; }
+            if (njobs) {
+                OK(mi355_upload(rcv.core, d_frx, arrived.data(), (size_t)ppos[np]));
+                OK(mi355_upload(rcv.core, (uint8_t *)d_frx + bcap, par_arrived.data(), ng * (size_t)Kp * M));
+                OK(mi355_cwire_fec_repair_batch(rcv.core, d_frx, bcap + par_cap, njobs, job_first.data(), slot_off.data(), slot_len.data(),
+                                                par_off.data(), job_len.data(), d_rep, M, d_vd));
+                OK(mi355_download(rcv.core, rebuilt.data(), d_rep, 2 * (size_t)njobs * M));
+                OK(mi355_download(rcv.core, vd.data(), d_vd, sizeof(uint32_t) * 2 * njobs));
+                // the rebuilt pieces back to back, checked before they are applied: clean verdicts are no replacement for that
+                for (size_t b0 = 0; b0 < 2 * (size_t)njobs; b0 += jobs_cap) {
+                    const size_t b1 = std::min(b0 + (size_t)jobs_cap, 2 * (size_t)njobs);
+                    size_t q = 0;
+                    int nc = 0;
+                    for (size_t b = b0; b < b1; b++) {
+                        const uint32_t p = job_piece[b];
+                        if (p == UINT32_MAX) continue;
+                        if (vd[b]) { fprintf(stderr, "tick %d: rebuilt piece %u has verdict %u\n", t0, p, vd[b]); return 1; }
+                        const size_t len = (size_t)(ppos[p + 1] - ppos[p]);
+                        memcpy(chk.data() + q, rebuilt.data() + b * M, len);
+                        memcpy(&pc[nc], chk.data() + q, 4);
+                        memcpy(&pe[nc], chk.data() + q + 4, 4);
+                        if (mi355_cwire_frame_bytes(pc[nc], pe[nc]) != len) { fprintf(stderr, "tick %d: rebuilt piece %u: framing broken\n", t0, p); return 1; }
+                        q += len;
+                        nc++;
+                    }
+                    if (!nc) continue;
+                    OK(mi355_upload(rcv.core, d_chk, chk.data(), q));
+                    OK(mi355_cwire_check_batch(rcv.core, d_chk, pc.data(), pe.data(), nc, (uint8_t *)d_vd + sizeof(uint32_t) * 2 * njobs));
+                    std::vector<uint32_t> cv(4 * (size_t)nc);
+                    OK(mi355_download(rcv.core, cv.data(), (uint8_t *)d_vd + sizeof(uint32_t) * 2 * njobs, sizeof(uint32_t) * 4 * nc));
+                    for (int i = 0; i < nc; i++)
+                        if (cv[4 * (size_t)i]) { fprintf(stderr, "tick %d: a rebuilt piece is refused by the check (flags %u)\n", t0, cv[4 * (size_t)i]); return 1; }
+                }
+                for (size_t b = 0; b < 2 * (size_t)njobs; b++) {
+                    const uint32_t p = job_piece[b];
+                    if (p == UINT32_MAX) continue;
+                    const size_t len = (size_t)(ppos[p + 1] - ppos[p]);
+                    if (memcmp(rebuilt.data() + b * M, pieces.data() + ppos[p], len) != 0) {
+                        fprintf(stderr, "tick %d: rebuilt piece %u differs from the piece that was sent\n", t0, p);
+                        return 1;
+                    }
+                    memcpy(arrived.data() + ppos[p], rebuilt.data() + b * M, len);
+                    pieces_rebuilt++;
+                }
+            }
+        }
         // ---- receiver: every camera's pieces in an order of their own, kDatagramRound of each per call, empty records behind them
         size_t most = 0;
         for (int s = 0; s < S; s++) {
@@ -1147,7 +1286,22 @@ static int run_multi_datagram(int w, int h, int T, int S, int K, long max_bytes)
             max_err = std::max(max_err, max_abs_error(&rcv.states[(size_t)s * n], &tx.frames[((size_t)s * nb + nb - 1) * n], n));
     }
     if (!datagrams) { fprintf(stderr, "--datagram: no piece was made\n"); return 1; }
+    if (G) {
+        static const char *const names[5] = {"one piece", "a piece and P", "a piece and Q", "two pieces", "parity only"};
+        for (int c = 0; c < 5; c++)
+            if (!met[c] && (Kp == 2 || c == 0 || c == 4)) { fprintf(stderr, "--fec: no group lost %s\n", names[c]); return 1; }
+        if (pieces_rebuilt != pieces_lost) { fprintf(stderr, "--fec: %zu pieces lost, %zu rebuilt\n", pieces_lost, pieces_rebuilt); return 1; }
+    }
     if (within_threshold(max_err, ss) || ss.close()) return 1;
+    if (G) {
+        printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"burst\": %d, \"coalesce\": %s, \"datagram\": %zu, "
+               "\"fec\": [%d, %d], \"relay_calls\": %d, \"width\": %d, \"height\": %d, \"ticks\": %d, \"changed_bytes\": %zu, "
+               "\"relay_received_bytes\": %zu, \"pieces\": %zu, \"piece_bytes\": %zu, \"parity_datagrams\": %zu, \"parity_bytes\": %zu, "
+               "\"pieces_lost\": %zu, \"pieces_rebuilt\": %zu, \"largest_piece\": %zu, \"raw_bytes\": %zu, \"max_abs_error\": %d}\n",
+               S, coalesce ? K : 0, coalesce ? "true" : "false", M, G, Kp, calls, w, h, T, tx.changed, received, datagrams, datagram_bytes,
+               parity_datagrams, parity_bytes, pieces_lost, pieces_rebuilt, largest, (size_t)T * S * n, max_err);
+        return 0;
+    }
     printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"burst\": %d, \"coalesce\": %s, \"datagram\": %zu, "
            "\"relay_calls\": %d, \"width\": %d, \"height\": %d, \"ticks\": %d, \"changed_bytes\": %zu, \"relay_received_bytes\": %zu, "
            "\"pieces\": %zu, \"piece_bytes\": %zu, \"pieces_per_tick\": %.2f, \"piece_bytes_per_tick\": %.1f, \"largest_piece\": %zu, "
@@ -1780,7 +1934,17 @@ int main(int argc, char **argv) {
     bool cropped = false, crop_ok = true;
     int grid[2] = {0, 0};
     bool mosaic = false, mosaic_ok = true;
+    int fec[2] = {0, 0};
+    bool fec_on = false, fec_ok = true;
     for (int i = 1; i < argc; i++) {   // (an option the tool does not know is ignored)
+        if (!strcmp(argv[i], "--fec") && i + 1 < argc) {
+            char tail = 0;
+            fec_on = true;
+            fec[1] = 1;
+            const int got = sscanf(argv[++i], "%d,%d%c", &fec[0], &fec[1], &tail);
+            fec_ok = got == 1 || got == 2;
+            continue;
+        }
         if (!strcmp(argv[i], "--crop") && i + 1 < argc) {
             char tail = 0;
             cropped = true;
@@ -1837,6 +2001,8 @@ int main(int argc, char **argv) {
         if (datagram < 64 || datagram > (long)MI355_CWIRE_SPLIT_BLOCK || datagram % 4)
             return usage("--datagram BYTES needs a multiple of 4 in [64, 65536]");
     }
+    if (fec_on && (datagram < 0 || !fec_ok || fec[0] < 1 || fec[0] > 255 || fec[1] < 1 || fec[1] > 2))
+        return usage("--fec G[,K] needs --datagram BYTES, G in 1 .. 255 and K = 1 or 2");
     if (thumb || thumb_drop != -1) {
         if (thumb < 1 || thumb > 16 || !compact || !multi || cropped || mosaic || datagram >= 0 || budget >= 0 || coalesce || per_frame ||
             burst_client || activity || check || resync >= 0 || wall)
@@ -1853,7 +2019,7 @@ int main(int argc, char **argv) {
     if (resync >= 0) return run_multi_resync(w, h, T, multi, resync, burst, wall);
     if (cropped) return run_multi_crop(w, h, T, multi, burst, crop);
     if (mosaic) return run_multi_mosaic(w, h, T, multi, burst, grid[0], grid[1]);
-    if (datagram >= 0) return run_multi_datagram(w, h, T, multi, coalesce ? burst : 0, datagram);
+    if (datagram >= 0) return run_multi_datagram(w, h, T, multi, coalesce ? burst : 0, datagram, fec[0], fec[1]);
     if (coalesce) return run_multi_burst_coalesce(w, h, T, multi, burst);
     if (budget >= 0) return run_multi_budget(w, h, T, multi, budget);
     if (burst && !burst_client) return run_multi_burst(w, h, T, multi, burst);
