@@ -155,6 +155,7 @@ Input of the other legs: ONE webcam stream of S + K + 1 frames; stream s shows f
 step between two consecutive webcam frames, and a tick's S frames are one contiguous region.  j walks 1 .. K and back."""
 import argparse
 import ctypes
+import itertools
 import json
 import os
 import statistics
@@ -168,6 +169,7 @@ sys.path.insert(0, ROOT)
 from cudavideostream_amd import lib, synth  # noqa: E402
 
 MULTI = ("mi355_diff_multi_batch", "mi355_diff_multi_wire_batch", "mi355_diff_multi_cwire_batch")
+KINDS = ("webcam", "local")
 
 
 def load_library():
@@ -193,10 +195,151 @@ def walk(K, ticks):
     return out
 
 
+# ---- the inputs and the sender's records: what every leg is fed
+def local_streams(S, T, W, H, dev):
+    """The local input: a static background with a block that moves 3 pixels per frame, as tools/roundtrip's make_frame
+    draws it, without the noise -> (states0 [S][n], frames [S][T][n])."""
+    n = 3 * W * H
+    i = torch.arange(n, device=dev, dtype=torch.int64)
+    bw, bh, y0 = W // 4 + 1, H // 4 + 1, H // 3
+    colour = torch.tensor([200, 210, 220], dtype=torch.uint8, device=dev)
+    frames = torch.empty(S, T + 1, n, dtype=torch.uint8, device=dev)
+    for s in range(S):
+        base = (40 + (i * 7 + s * 31) % 150).to(torch.uint8)
+        for t in range(T + 1):
+            f = frames[s, t]
+            f.copy_(base)
+            x0 = ((t + 5 * s) * 3) % (W - bw + 1)
+            f.view(H, W, 3)[y0:y0 + bh, x0:x0 + bw] = colour
+    return frames[:, 0].contiguous(), frames[:, 1:].contiguous()
+
+
+def burst_input(kind, S, T, W, H, dev):
+    """The burst-shaped input -> (states0 [S][n], frames [S][T][n]).  `webcam`: ONE webcam stream of S * T + 1 frames cut into S
+    pieces, stream s starts from frame s * T as its state and takes the T frames behind it (a view of the stream); `local`:
+    local_streams.  With T = 1 it is one tick of S streams."""
+    if kind != "webcam":
+        return local_streams(S, T, W, H, dev)
+    n, B = 3 * W * H, S * T
+    _, web = synth.webcam_stream(B + 1, W, H, device=dev)
+    web = web.reshape(B + 1, n)
+    return web[0:B:T].clone(), web[1:].reshape(S, T, n)
+
+
+def burst_chunks(S, T, n):
+    """A core takes max_batch * N < 2^32 bytes per call: the whole streams one call holds, and the fewest calls that cover S
+    streams of T frames as (first stream, streams)."""
+    per_call = min(S, max(1, ((1 << 32) - 1) // n // T))
+    return per_call, [(s0, min(per_call, S - s0)) for s0 in range(0, S, per_call)]
+
+
+def sender_records(W, H, fwd, states):
+    """The records of the burst fwd [S][T][n] from states [S][n], as a sender's mi355_diff_multi_stream_cwire_batch makes them on
+    a throw-away server core, one call per chunk of burst_chunks -> per chunk (records, counts, escapes, positions): the record
+    bytes cut to their end, the two header words of every record and the chunk's uint64[streams * T + 1] record positions.
+    `states` is advanced to the server's states after the burst."""
+    import numpy as np
+    from cudavideostream_amd import CUDACore, cwire_bytes_max
+    S, T, n = fwd.shape
+    per_call, chunks = burst_chunks(S, T, n)
+    recs = []
+    with CUDACore(W, H, max_batch=per_call * T) as server:
+        for s0, ns in chunks:
+            nb = ns * T
+            cwcap = cwire_bytes_max(n, nb)
+            d_off = torch.zeros(nb + 1, dtype=torch.int32, device=fwd.device)
+            d_pos = torch.zeros(nb + 1, dtype=torch.int64, device=fwd.device)
+            d_cw = torch.empty(cwcap, dtype=torch.uint8, device=fwd.device)
+            torch.cuda.synchronize()
+            server.diff_multi_stream_cwire_batch(fwd[s0], states[s0], ns, T, d_off, d_pos, d_cw, cwcap)
+            server.synchronize()
+            pos = d_pos.cpu().numpy().astype(np.int64)
+            counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
+            pad = (counts.astype(np.int64) + 3) & ~3     # a record: 8 header bytes, 2 * pad4(count) and 4 per escape
+            escapes = ((np.diff(pos) - 8 - 2 * pad) // 4).astype(np.uint32)
+            recs.append((d_cw[:int(pos[nb])].clone(), counts, escapes, pos))
+            del d_cw
+    torch.cuda.synchronize()
+    return recs
+
+
+def one_call(recs):
+    """The records of a leg that runs in one call."""
+    assert len(recs) == 1, "the leg runs in one call: max_batch * N < 2^32"
+    return recs[0]
+
+
+def mask_bits(d_mask):
+    """Tiles selected in a tile mask of 32-bit words."""
+    return int(sum(bin(int(v) & 0xFFFFFFFF).count("1") for v in d_mask.cpu().numpy()))
+
+
+# ---- the method: how every leg is timed, reported and judged
+def time_legs(table, rounds, per, before=None, after=None):
+    """Times the legs of `table` (name -> closure that ends in its cores' own synchronize()) -> name -> microseconds per unit of
+    every round but the first, which warms every leg up and is dropped.  The legs alternate within every round, in the table's
+    order.  `before(name)`, a leg's restore of its states or work copies, runs outside the timed window, which is
+    time.perf_counter() around leg() alone, behind a device-wide synchronize; `after(name)` runs behind it.  `per` is the units
+    of one window, a number or a function of the name."""
+    times = {name: [] for name in table}
+    for r in range(rounds + 1):
+        for name, leg in table.items():
+            if before:
+                before(name)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            leg()
+            dt = time.perf_counter() - t0
+            if r:
+                times[name].append(dt * 1e6 / (per(name) if callable(per) else per))
+            if after:
+                after(name)
+    return times
+
+
+def restorer(states, states0, cores, host0, cores_leg):
+    """before(name) of the legs that advance caller-held states, and, in the leg `cores_leg`, the states of one core each."""
+    def before(name):
+        states.copy_(states0)
+        if name == cores_leg:
+            for s, c in enumerate(cores):
+                c.set_state(host0[s])
+    return before
+
+
 def stats(us):
     return {"median": round(statistics.median(us), 3), "min": round(min(us), 3), "max": round(max(us), 3)}
 
 
+def report(out, times, unit, spread=False, as_printed=False):
+    """out[name + unit] = the statistics of the leg's rounds, with the relative spread where the leg prints it -> name ->
+    (median, max - min), the figures a leg is judged by: of the rounds themselves, or, where the leg judges by what it prints,
+    of the rounded statistics."""
+    fig = {}
+    for name, us in times.items():
+        st = stats(us)
+        if spread:
+            st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
+        out[name + unit] = st
+        fig[name] = (st["median"], st["max"] - st["min"]) if as_printed else (statistics.median(us), max(us) - min(us))
+    return fig
+
+
+def ratio(fig, a, b, digits=3):
+    return round(fig[a][0] / fig[b][0], digits)
+
+
+def versus(fig, a, b):
+    """(a over b, a no slower than b by more than the rounds' spread: the larger of the two legs' max - min)."""
+    return ratio(fig, a, b), bool(fig[a][0] <= fig[b][0] + max(fig[a][1], fig[b][1]))
+
+
+def cheaper(fig, a, b):
+    """a cheaper than b by more than the rounds' spread."""
+    return bool(fig[a][0] + max(fig[a][1], fig[b][1]) < fig[b][0])
+
+
+# ---- the legs
 def run(W, H, S, K, rounds, legs, have_multi):
     from cudavideostream_amd import CUDACore, cwire_bytes_max
     dev = torch.device("cuda", 0)
@@ -215,7 +358,6 @@ def run(W, H, S, K, rounds, legs, have_multi):
     d_pos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
     d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
     result = {"size": f"{W}x{H}", "streams": S, "ticks": ticks, "rounds": rounds, "has_multi": have_multi}
-    times = {}
     core = CUDACore(W, H, max_batch=S)
     core.prepare(lib.PREPARE_BATCHES)
     cores, outs = [], []
@@ -228,15 +370,7 @@ def run(W, H, S, K, rounds, legs, have_multi):
             outs.append((torch.zeros(2, dtype=torch.int32, device=dev), torch.empty(one, dtype=torch.int32, device=dev),
                          torch.empty(one, dtype=torch.uint8, device=dev)))
     torch.cuda.synchronize()
-
-    host0 = states0.cpu().numpy() if cores else None
-
-    def reset(name):
-        states.copy_(states0)
-        if name == "cores_loop":
-            for s, c in enumerate(cores):
-                c.set_state(host0[s])
-        torch.cuda.synchronize()
+    reset = restorer(states, states0, cores, states0.cpu().numpy() if cores else None, "cores_loop")
 
     def leg_multi():
         for j in steps:
@@ -262,28 +396,22 @@ def run(W, H, S, K, rounds, legs, have_multi):
             c.synchronize()
 
     table = {"multi": leg_multi, "multi_cwire": leg_multi_cwire, "pairs": leg_pairs, "cores_loop": leg_cores}
-    active = [k for k in table if ("multi" if k.startswith("multi") else k) in legs and (have_multi or not k.startswith("multi"))]
-    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
-        for name in active:
-            reset(name)
-            t0 = time.perf_counter()
-            table[name]()
-            dt = time.perf_counter() - t0
-            if r:
-                times.setdefault(name, []).append(dt * 1e6 / (ticks * S))
-    if "multi" in active:
+    table = {k: leg for k, leg in table.items()
+             if ("multi" if k.startswith("multi") else k) in legs and (have_multi or not k.startswith("multi"))}
+    times = time_legs(table, rounds, ticks * S, before=reset)
+    if "multi" in table:
         reset("multi")
+        torch.cuda.synchronize()
         core.diff_multi_batch(frames[1:1 + S], states, S, d_off, d_xs, d_df, cap)
         core.synchronize()
         total = int(d_off.cpu()[-1])
         assert 0 < total <= cap
         result["changed_bytes_per_frame"] = round(total / S, 1)
-    for name in active:
-        result[name + "_us_per_frame"] = stats(times[name])
+    fig = report(result, times, "_us_per_frame")
     if "multi" in times and "cores_loop" in times:
-        result["cores_loop_over_multi"] = round(statistics.median(times["cores_loop"]) / statistics.median(times["multi"]), 2)
+        result["cores_loop_over_multi"] = ratio(fig, "cores_loop", "multi", 2)
     if "multi" in times and "pairs" in times:
-        result["multi_over_pairs"] = round(statistics.median(times["multi"]) / statistics.median(times["pairs"]), 3)
+        result["multi_over_pairs"] = ratio(fig, "multi", "pairs")
     if "write_probe" in legs:                          # the board's streaming-write rate (wide stores), for the write-back's bound
         result["hbm_write_gbps"] = round(core.probe_hbm_write(1024, narrow=False), 1)
     print(json.dumps(result), flush=True)
@@ -292,10 +420,10 @@ def run(W, H, S, K, rounds, legs, have_multi):
     core.close()
 
 
-def run_client(W, H, S, K, rounds):
+def run_client(W, H, rounds, S, K):
     """The client leg for one S -> its dictionary."""
     import numpy as np
-    from cudavideostream_amd import CUDACore, cwire_bytes_max
+    from cudavideostream_amd import CUDACore
     dev = torch.device("cuda", 0)
     n = 3 * W * H
     ticks = max(16, min(512, 4096 // S))
@@ -303,28 +431,17 @@ def run_client(W, H, S, K, rounds):
     frames = frames.reshape(S + K + 1, n)
     states0 = frames[:S].clone()
     states = states0.clone()
-    cwcap = cwire_bytes_max(n, S)
-    d_off = torch.zeros(S + 1, dtype=torch.int32, device=dev)
-    d_pos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
-    d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
     recs = []                                          # per recorded tick: (records, counts, escapes, positions)
-    with CUDACore(W, H, max_batch=S) as server:
-        for j in range(1, K + 1):
-            server.diff_multi_cwire_batch(frames[j:j + S], states, S, d_off, d_pos, d_cw, cwcap)
-            server.synchronize()
-            pos = d_pos.cpu().numpy().astype(np.int64)
-            counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
-            pad = (counts.astype(np.int64) + 3) & ~3
-            escapes = ((np.diff(pos) - 8 - 2 * pad) // 4).astype(np.uint32)
-            recs.append((d_cw[:int(pos[S])].clone(), counts, escapes, pos))
+    for j in range(1, K + 1):
+        recs.append(one_call(sender_records(W, H, frames[j:j + S].unsqueeze(1), states)))
     cap = max(int(r[1].sum()) for r in recs) + 16
+    d_off = torch.zeros(S + 1, dtype=torch.int32, device=dev)
     d_xs = torch.empty(cap, dtype=torch.int32, device=dev)
     d_df = torch.empty(cap, dtype=torch.uint8, device=dev)
     client = CUDACore(W, H, max_batch=S)
     cores = [CUDACore(W, H, max_batch=1) for _ in range(S)]
     own = [[r[0][int(r[3][s]):int(r[3][s + 1])] for s in range(S)] for r in recs]   # camera s's record of tick k
     hdr = [[(r[1][s:s + 1], r[2][s:s + 1]) for s in range(S)] for r in recs]
-    host0 = states0.cpu().numpy()
     # touched tiles, from the decoded indices
     touched = []
     for r in recs:
@@ -358,35 +475,21 @@ def run_client(W, H, S, K, rounds):
         client.synchronize()
 
     table = {"multi_client": leg_multi_client, "cores_client": leg_cores_client, "decode_arrays": leg_decode_arrays}
-    times = {}
-    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
-        for name, leg in table.items():
-            states.copy_(states0)
-            if name == "cores_client":
-                for s, c in enumerate(cores):
-                    c.set_state(host0[s])
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            leg()
-            dt = time.perf_counter() - t0
-            if r:
-                times.setdefault(name, []).append(dt * 1e6 / (ticks * S))
+    times = time_legs(table, rounds, ticks * S, before=restorer(states, states0, cores, states0.cpu().numpy(), "cores_client"))
     out = {"streams": S, "ticks": ticks, "changed_bytes_per_stream": round(sum(int(r[1].sum()) for r in recs) / (K * S), 1),
            "record_bytes_per_stream": round(sum(int(r[3][S]) for r in recs) / (K * S), 1),
            "touched_tiles_per_stream": round(sum(touched) / (K * S), 1), "tiles_per_state": (n + 4095) // 4096,
            "state_bytes_moved_per_stream": round(sum(touched) * 2 * 4096 / (K * S), 1), "state_bytes_2N": 2 * n}
-    for name in table:
-        out[name + "_us_per_stream"] = stats(times[name])
-    med = {k: statistics.median(v) for k, v in times.items()}
-    out["cores_client_over_multi_client"] = round(med["cores_client"] / med["multi_client"], 2)
-    out["decode_arrays_over_multi_client"] = round(med["decode_arrays"] / med["multi_client"], 2)
+    fig = report(out, times, "_us_per_stream")
+    out["cores_client_over_multi_client"] = ratio(fig, "cores_client", "multi_client", 2)
+    out["decode_arrays_over_multi_client"] = ratio(fig, "decode_arrays", "multi_client", 2)
     for c in cores:
         c.close()
     client.close()
     return out
 
 
-def run_burst(W, H, S, T, rounds):
+def run_burst(W, H, rounds, S, T):
     """The burst leg for one (S, T) -> its dictionary."""
     from cudavideostream_amd import CUDACore, cwire_bytes_max
     dev = torch.device("cuda", 0)
@@ -403,8 +506,7 @@ def run_burst(W, H, S, T, rounds):
     d_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
     d_pos = torch.zeros(B + 1, dtype=torch.int64, device=dev)
     d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
-    per_call = min(S, max(1, ((1 << 32) - 1) // n // T))             # whole streams per call: max_batch * N < 2^32
-    chunks = [(s0, min(per_call, S - s0)) for s0 in range(0, S, per_call)]
+    per_call, chunks = burst_chunks(S, T, n)
     burst = CUDACore(W, H, max_batch=per_call * T)
     ticks = CUDACore(W, H, max_batch=S)
     cores = [CUDACore(W, H, max_batch=T) for _ in range(S)]
@@ -413,7 +515,6 @@ def run_burst(W, H, S, T, rounds):
              torch.empty(one, dtype=torch.uint8, device=dev)) for _ in range(S)]
     for c in [burst, ticks] + cores:
         c.prepare(lib.PREPARE_BATCHES)
-    host0 = states0.cpu().numpy()
     torch.cuda.synchronize()
 
     def leg_burst():
@@ -438,19 +539,7 @@ def run_burst(W, H, S, T, rounds):
             c.synchronize()
 
     table = {"burst_cwire": leg_burst, "multi_ticks": leg_ticks, "cores_stream": leg_cores}
-    times = {}
-    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
-        for name, leg in table.items():
-            states.copy_(states0)
-            if name == "cores_stream":
-                for s, c in enumerate(cores):
-                    c.set_state(host0[s])
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            leg()
-            dt = time.perf_counter() - t0
-            if r:
-                times.setdefault(name, []).append(dt * 1e6 / (passes * B))
+    times = time_legs(table, rounds, passes * B, before=restorer(states, states0, cores, states0.cpu().numpy(), "cores_stream"))
     states.copy_(states0)
     torch.cuda.synchronize()
     total = nbytes = 0
@@ -462,69 +551,26 @@ def run_burst(W, H, S, T, rounds):
     assert 0 < total and all(int(o[1].cpu()[-1]) <= one for o in outs)
     out = {"streams": S, "frames": T, "passes": passes, "calls_per_burst": len(chunks), "changed_bytes_per_frame": round(total / B, 1),
            "record_bytes_per_frame": round(nbytes / B, 1)}
-    for name in table:
-        out[name + "_us_per_frame"] = stats(times[name])
-    med = {k: statistics.median(v) for k, v in times.items()}
-    out["multi_ticks_over_burst"] = round(med["multi_ticks"] / med["burst_cwire"], 3)
-    out["cores_stream_over_burst"] = round(med["cores_stream"] / med["burst_cwire"], 3)
+    fig = report(out, times, "_us_per_frame")
+    out["multi_ticks_over_burst"] = ratio(fig, "multi_ticks", "burst_cwire")
+    out["cores_stream_over_burst"] = ratio(fig, "cores_stream", "burst_cwire")
     for c in [burst, ticks] + cores:
         c.close()
     return out
 
 
-def local_streams(S, T, W, H, dev):
-    """The local input: a static background with a block that moves 3 pixels per frame, as tools/roundtrip's make_frame
-    draws it, without the noise -> (states0 [S][n], frames [S][T][n])."""
-    n = 3 * W * H
-    i = torch.arange(n, device=dev, dtype=torch.int64)
-    bw, bh, y0 = W // 4 + 1, H // 4 + 1, H // 3
-    colour = torch.tensor([200, 210, 220], dtype=torch.uint8, device=dev)
-    frames = torch.empty(S, T + 1, n, dtype=torch.uint8, device=dev)
-    for s in range(S):
-        base = (40 + (i * 7 + s * 31) % 150).to(torch.uint8)
-        for t in range(T + 1):
-            f = frames[s, t]
-            f.copy_(base)
-            x0 = ((t + 5 * s) * 3) % (W - bw + 1)
-            f.view(H, W, 3)[y0:y0 + bh, x0:x0 + bw] = colour
-    return frames[:, 0].contiguous(), frames[:, 1:].contiguous()
-
-
-def run_burst_client(W, H, S, T, rounds, kind):
+def run_burst_client(W, H, rounds, S, T, kind):
     """The burst-client leg for one (S, T) and one input -> its dictionary."""
     import numpy as np
-    from cudavideostream_amd import CUDACore, cwire_bytes_max
+    from cudavideostream_amd import CUDACore
     dev = torch.device("cuda", 0)
     n, B = 3 * W * H, S * T
     ntiles = (n + 4095) // 4096
     passes = 2 * max(1, 1024 // B)                     # ~2 k records per timed window
-    if kind == "webcam":                                # run_burst's input: one stream cut into S pieces
-        _, web = synth.webcam_stream(B + 1, W, H, device=dev)
-        web = web.reshape(B + 1, n)
-        states0, fwd = web[0:B:T].clone(), web[1:].reshape(S, T, n)
-    else:
-        states0, fwd = local_streams(S, T, W, H, dev)
-    per_call = min(S, max(1, ((1 << 32) - 1) // n // T))             # whole streams per call: max_batch * N < 2^32
-    chunks = [(s0, min(per_call, S - s0)) for s0 in range(0, S, per_call)]
-    # ---- the records, as a sender's mi355_diff_multi_stream_cwire_batch makes them: per chunk (records, counts, escapes, positions)
-    recs = []
+    states0, fwd = burst_input(kind, S, T, W, H, dev)
+    per_call, chunks = burst_chunks(S, T, n)
     srv_states = states0.clone()
-    with CUDACore(W, H, max_batch=per_call * T) as server:
-        for s0, ns in chunks:
-            nb = ns * T
-            cwcap = cwire_bytes_max(n, nb)
-            d_off = torch.zeros(nb + 1, dtype=torch.int32, device=dev)
-            d_pos = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
-            d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
-            torch.cuda.synchronize()
-            server.diff_multi_stream_cwire_batch(fwd[s0], srv_states[s0], ns, T, d_off, d_pos, d_cw, cwcap)
-            server.synchronize()
-            pos = d_pos.cpu().numpy().astype(np.int64)
-            counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
-            pad = (counts.astype(np.int64) + 3) & ~3
-            escapes = ((np.diff(pos) - 8 - 2 * pad) // 4).astype(np.uint32)
-            recs.append((d_cw[:int(pos[nb])].clone(), counts, escapes, pos))
-            del d_cw
+    recs = sender_records(W, H, fwd, srv_states)       # per chunk (records, counts, escapes, positions)
     # re-staged tick-major for baseline (3): tick t = record (s, t) of every s back to back
     flat = [(recs[c][0], recs[c][3], j * T, recs[c][1], recs[c][2]) for c, (s0, ns) in enumerate(chunks) for j in range(ns)]
     staged = []
@@ -539,7 +585,6 @@ def run_burst_client(W, H, S, T, rounds, kind):
     client = CUDACore(W, H, max_batch=per_call * T)
     ticks = CUDACore(W, H, max_batch=S)
     cores = [CUDACore(W, H, max_batch=T) for _ in range(S)]
-    host0 = states0.cpu().numpy()
     # touched tiles, from the decoded indices: per record, and per stream and call (what the new call loads and stores)
     entries = sum(int(r[1].sum()) for r in recs)
     tiles_rec = tiles_call = 0
@@ -579,19 +624,7 @@ def run_burst_client(W, H, S, T, rounds, kind):
 
     table = {"burst_apply": lambda: leg_burst(None), "burst_apply_frames": lambda: leg_burst(d_out), "multi_ticks": leg_ticks,
              "cores_client": leg_cores}
-    times = {}
-    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
-        for name, leg in table.items():
-            states.copy_(states0)
-            if name == "cores_client":
-                for s, c in enumerate(cores):
-                    c.set_state(host0[s])
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            leg()
-            dt = time.perf_counter() - t0
-            if r:
-                times.setdefault(name, []).append(dt * 1e6 / (passes * B))
+    times = time_legs(table, rounds, passes * B, before=restorer(states, states0, cores, states0.cpu().numpy(), "cores_client"))
     # one burst from the base states is what the sender's states became, by every way
     states.copy_(states0)
     torch.cuda.synchronize()
@@ -603,45 +636,24 @@ def run_burst_client(W, H, S, T, rounds, kind):
            "changed_bytes_per_record": round(entries / B, 1), "record_bytes_per_record": round(sum(int(r[3][-1]) for r in recs) / B, 1),
            "tiles_per_state": ntiles, "touched_tiles_per_record": round(tiles_rec / B, 1),
            "touched_tiles_per_stream_and_call": round(tiles_call / S, 1)}
-    for name in table:
-        out[name + "_us_per_record"] = stats(times[name])
-    med = {k: statistics.median(v) for k, v in times.items()}
-    out["multi_ticks_over_burst_apply"] = round(med["multi_ticks"] / med["burst_apply"], 3)
-    out["cores_client_over_burst_apply"] = round(med["cores_client"] / med["burst_apply"], 3)
+    fig = report(out, times, "_us_per_record")
+    out["multi_ticks_over_burst_apply"] = ratio(fig, "multi_ticks", "burst_apply")
+    out["cores_client_over_burst_apply"] = ratio(fig, "cores_client", "burst_apply")
     for c in [client, ticks] + cores:
         c.close()
     return out
 
 
-def run_activity(W, H, S, T, rounds, kind, cell=16):
+def run_activity(W, H, rounds, S, T, kind, cell=16):
     """The activity leg for one (S, T) and one input -> its dictionary."""
     import numpy as np
-    from cudavideostream_amd import CUDACore, activity_cells, cwire_bytes_max
+    from cudavideostream_amd import CUDACore, activity_cells
     dev = torch.device("cuda", 0)
-    n, B = 3 * W * H, S * T
+    B = S * T
     passes = 2 * max(1, 1024 // B)                     # ~2 k records per timed window
-    if kind == "webcam":                                # run_burst's input: one stream cut into S pieces
-        _, web = synth.webcam_stream(B + 1, W, H, device=dev)
-        web = web.reshape(B + 1, n)
-        states0, fwd = web[0:B:T].clone(), web[1:].reshape(S, T, n)
-    else:
-        states0, fwd = local_streams(S, T, W, H, dev)
-    # ---- the records, as a sender's mi355_diff_multi_stream_cwire_batch makes them
-    cwcap = cwire_bytes_max(n, B)
-    d_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-    d_pos = torch.zeros(B + 1, dtype=torch.int64, device=dev)
-    d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
-    srv_states = states0.clone()
-    with CUDACore(W, H, max_batch=B) as server:
-        torch.cuda.synchronize()
-        server.diff_multi_stream_cwire_batch(fwd, srv_states, S, T, d_off, d_pos, d_cw, cwcap)
-        server.synchronize()
-    pos = d_pos.cpu().numpy().astype(np.int64)
-    off = d_off.cpu().numpy().view(np.uint32).astype(np.int64)
-    counts = np.diff(off).astype(np.uint32)
-    escapes = ((np.diff(pos) - 8 - 2 * ((counts.astype(np.int64) + 3) & ~3)) // 4).astype(np.uint32)
-    recs = d_cw[:int(pos[B])].clone()
-    del d_cw, fwd
+    states0, fwd = burst_input(kind, S, T, W, H, dev)
+    recs, counts, escapes, _ = one_call(sender_records(W, H, fwd, states0.clone()))
+    del fwd
     ncells = activity_cells(W, H, cell, cell)[0]
     d_cells = torch.empty(S * ncells, dtype=torch.int32, device=dev)
     d_sum = torch.empty(S * 8, dtype=torch.int32, device=dev)
@@ -659,16 +671,7 @@ def run_activity(W, H, S, T, rounds, kind, cell=16):
             core.apply_multi_stream_cwire_batch(recs, counts, escapes, S, T, states)
         core.synchronize()
 
-    table = {"activity": leg_activity, "burst_apply": leg_apply}
-    times = {}
-    for r in range(rounds + 1):                        # round 0 warms both legs up and is dropped
-        for name, leg in table.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            leg()
-            dt = time.perf_counter() - t0
-            if r:
-                times.setdefault(name, []).append(dt * 1e6 / (passes * B))
+    times = time_legs({"activity": leg_activity, "burst_apply": leg_apply}, rounds, passes * B)
     # every counted entry is in the grids, and every stream's count is its records'
     summ = d_sum.cpu().numpy().view(np.uint32).reshape(S, 8)
     per_stream = counts.astype(np.int64).reshape(S, T).sum(axis=1)
@@ -676,45 +679,22 @@ def run_activity(W, H, S, T, rounds, kind, cell=16):
     assert (d_cells.cpu().numpy().view(np.uint32).astype(np.int64).reshape(S, ncells).sum(axis=1) == per_stream).all()
     out = {"input": kind, "streams": S, "frames": T, "passes": passes, "cell": cell, "cells_per_stream": ncells,
            "changed_bytes_per_record": round(int(counts.sum()) / B, 1), "active_cells_per_stream": round(float(summ[:, 5].mean()), 1)}
-    for name in table:
-        out[name + "_us_per_record"] = stats(times[name])
-    med = {k: statistics.median(v) for k, v in times.items()}
-    spread = max(max(v) - min(v) for v in times.values())
-    out["activity_over_burst_apply"] = round(med["activity"] / med["burst_apply"], 3)
-    out["no_slower_than_burst_apply"] = bool(med["activity"] <= med["burst_apply"] + spread)
+    fig = report(out, times, "_us_per_record")
+    out["activity_over_burst_apply"], out["no_slower_than_burst_apply"] = versus(fig, "activity", "burst_apply")
     core.close()
     return out
 
 
-def run_check(W, H, S, T, rounds, kind):
+def run_check(W, H, rounds, S, T, kind):
     """The check leg for one (S, T) and one input -> its dictionary."""
     import numpy as np
-    from cudavideostream_amd import CUDACore, cwire_bytes_max, cwire_check_host
+    from cudavideostream_amd import CUDACore, cwire_check_host
     dev = torch.device("cuda", 0)
     n, B = 3 * W * H, S * T
     passes = 2 * max(1, 1024 // B)                     # ~2 k records per timed window
-    if kind == "webcam":                                # run_burst's input: one stream cut into S pieces
-        _, web = synth.webcam_stream(B + 1, W, H, device=dev)
-        web = web.reshape(B + 1, n)
-        states0, fwd = web[0:B:T].clone(), web[1:].reshape(S, T, n)
-    else:
-        states0, fwd = local_streams(S, T, W, H, dev)
-    # ---- the records, as a sender's mi355_diff_multi_stream_cwire_batch makes them
-    cwcap = cwire_bytes_max(n, B)
-    d_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-    d_pos = torch.zeros(B + 1, dtype=torch.int64, device=dev)
-    d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
-    srv_states = states0.clone()
-    with CUDACore(W, H, max_batch=B) as server:
-        torch.cuda.synchronize()
-        server.diff_multi_stream_cwire_batch(fwd, srv_states, S, T, d_off, d_pos, d_cw, cwcap)
-        server.synchronize()
-    pos = d_pos.cpu().numpy().astype(np.int64)
-    off = d_off.cpu().numpy().view(np.uint32).astype(np.int64)
-    counts = np.diff(off).astype(np.uint32)
-    escapes = ((np.diff(pos) - 8 - 2 * ((counts.astype(np.int64) + 3) & ~3)) // 4).astype(np.uint32)
-    recs = d_cw[:int(pos[B])].clone()
-    del d_cw, fwd
+    states0, fwd = burst_input(kind, S, T, W, H, dev)
+    recs, counts, escapes, pos = one_call(sender_records(W, H, fwd, states0.clone()))
+    del fwd
     d_verdicts = torch.empty(B * 4, dtype=torch.int32, device=dev)
     states = states0.clone()
     core = CUDACore(W, H, max_batch=B)
@@ -730,45 +710,30 @@ def run_check(W, H, S, T, rounds, kind):
             core.apply_multi_stream_cwire_batch(recs, counts, escapes, S, T, states)
         core.synchronize()
 
-    table = {"check": leg_check, "burst_apply": leg_apply}
-    times = {}
-    for r in range(rounds + 1):                        # round 0 warms both legs up and is dropped
-        for name, leg in table.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            leg()
-            dt = time.perf_counter() - t0
-            if r:
-                times.setdefault(name, []).append(dt * 1e6 / (passes * B))
+    times = time_legs({"check": leg_check, "burst_apply": leg_apply}, rounds, passes * B)
     # a sender's records are clean, and the device's verdicts are the host's
     got = d_verdicts.cpu().numpy().view(np.uint32).reshape(B, 4)
     assert not got[:, 0].any() and (got[:, 1] == escapes).all() and (got[:, 2] == counts).all()
     assert np.array_equal(got, cwire_check_host(recs.cpu().numpy(), counts, escapes, n))
     out = {"input": kind, "streams": S, "frames": T, "passes": passes, "changed_bytes_per_record": round(int(counts.sum()) / B, 1),
            "record_bytes_per_record": round(int(pos[B]) / B, 1)}
-    for name in table:
-        out[name + "_us_per_record"] = stats(times[name])
-    med = {k: statistics.median(v) for k, v in times.items()}
-    spread = max(max(v) - min(v) for v in times.values())
-    out["check_over_burst_apply"] = round(med["check"] / med["burst_apply"], 3)
-    out["no_slower_than_burst_apply"] = bool(med["check"] <= med["burst_apply"] + spread)
+    fig = report(out, times, "_us_per_record")
+    out["check_over_burst_apply"], out["no_slower_than_burst_apply"] = versus(fig, "check", "burst_apply")
     core.close()
     return out
 
 
-def run_refresh(W, H, S, rounds):
+def run_refresh(W, H, rounds, S):
     """The refresh leg for one S -> its dictionary.  All legs on one core's own stream, alternating within every round; the diff
     leg has its own copy of the states per pass, restored outside the window (it is the only leg that writes states it reads)."""
-    import numpy as np
     from cudavideostream_amd import CUDACore, cwire_bytes_max, state_tiles
     dev = torch.device("cuda", 0)
     n = 3 * W * H
     tiles = state_tiles(n)
     mask_words = (tiles + 31) // 32
     passes = max(2, min(16, 128 // S))
-    _, web = synth.webcam_stream(S + 1, W, H, device=dev)
-    web = web.reshape(S + 1, n)
-    sender, frames = web[:S].clone(), web[1:].clone()   # stream s: webcam frame s, and the tick s -> s + 1 for the diff leg
+    sender, fwd = burst_input("webcam", S, 1, W, H, dev)   # stream s: webcam frame s, and the tick s -> s + 1 for the diff leg
+    frames = fwd[:, 0].clone()
     cwcap = cwire_bytes_max(n, S)
     d_off = torch.zeros(S + 1, dtype=torch.int32, device=dev)
     d_pos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
@@ -789,7 +754,7 @@ def run_refresh(W, H, S, rounds):
         core.refresh_cwire_batch(sender, S, peers[name], d_mask, d_off, d_pos, d_cw, cwcap)
         core.synchronize()
         masks[name] = d_mask.clone()
-        selected[name] = int(sum(bin(int(v) & 0xFFFFFFFF).count("1") for v in d_mask.cpu().numpy()))
+        selected[name] = mask_bits(d_mask)
         assert selected[name] == S * int(hit.numel()), "the refresh did not select exactly the changed tiles"
         del recv
     work = torch.empty(passes, S, n, dtype=torch.uint8, device=dev)
@@ -827,78 +792,58 @@ def run_refresh(W, H, S, rounds):
             core.diff_multi_cwire_batch(frames, work[p], S, d_off, d_pos, d_cw, cwcap)
         core.synchronize()
 
+    def before(name):
+        if name == "diff":
+            work.copy_(sender.unsqueeze(0).expand(passes, S, n))
+
+    def after(name):
+        if name.startswith("refresh"):
+            rec_bytes[name] = int(d_pos[S].item())
+
     table = {"digest": leg_digest, "digest_skewed": leg_digest_skewed, "refresh_1pct": leg_refresh(peers["1pct"]), "refresh_10pct": leg_refresh(peers["10pct"]),
              "refresh_all": leg_refresh(None), "clear_10pct": leg_clear, "diff": leg_diff}
-    times = {}
-    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
-        for name, leg in table.items():
-            if name == "diff":
-                work.copy_(sender.unsqueeze(0).expand(passes, S, n))
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            leg()
-            dt = time.perf_counter() - t0
-            if r:
-                times.setdefault(name, []).append(dt * 1e6 / (passes * S))
-            if name.startswith("refresh"):
-                rec_bytes[name] = int(d_pos[S].item())
+    times = time_legs(table, rounds, passes * S, before=before, after=after)
     out = {"streams": S, "passes": passes, "tiles": tiles, "state_bytes": n}
-    for name in table:
-        st = stats(times[name])
-        st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
-        out[name + "_us_per_stream"] = st
+    fig = report(out, times, "_us_per_stream", spread=True)
     for name in ("1pct", "10pct"):
         out["refresh_" + name + "_tiles_per_stream"] = selected[name] // S
     for name, b in rec_bytes.items():
         out[name + "_bytes_per_stream"] = round(b / S, 1)
-    med = {k: statistics.median(v) for k, v in times.items()}
-    spread = max(max(times[k]) - min(times[k]) for k in ("digest", "diff"))
-    out["digest_over_diff"] = round(med["digest"] / med["diff"], 3)
-    out["digest_no_slower_than_diff"] = bool(med["digest"] <= med["diff"] + spread)
+    out["digest_over_diff"], out["digest_no_slower_than_diff"] = versus(fig, "digest", "diff")
     core.close()
     return out
 
 
-def run_wall(W, H, S, rounds, scales=(2, 4, 8)):
+def one_tick(W, H, S, core, d_mask, dev):
+    """One tick of every input for the wall and thumb legs -> kind -> (states before, states after, records, counts, escapes,
+    the tick's tile mask from mi355_cwire_touched_tiles_batch on `core`, tiles in it)."""
+    ticks = {}
+    for kind in KINDS:
+        before, fwd = burst_input(kind, S, 1, W, H, dev)
+        after = before.clone()
+        recs, counts, escapes, _ = one_call(sender_records(W, H, fwd, after))
+        d_kind_mask = torch.zeros_like(d_mask)
+        core.cwire_touched_tiles_batch(recs, counts, escapes, S, 1, d_kind_mask)
+        core.synchronize()
+        ticks[kind] = (before, after, recs, counts, escapes, d_kind_mask, mask_bits(d_kind_mask))
+    return ticks
+
+
+def run_wall(W, H, rounds, S, scales=(2, 4, 8)):
     """The wall leg for one S -> its dictionary.  All legs on one core's own stream, alternating within every round."""
     import numpy as np
-    from cudavideostream_amd import CUDACore, cwire_bytes_max, state_tiles, wall_thumb_size
+    from cudavideostream_amd import CUDACore, state_tiles, wall_thumb_size
     dev = torch.device("cuda", 0)
     n = 3 * W * H
     tiles = state_tiles(n)
     mask_words = (tiles + 31) // 32
     passes = max(2, min(16, 128 // S))
     cols = int(np.ceil(np.sqrt(S)))
-    cwcap = cwire_bytes_max(n, S)
-    d_off = torch.zeros(S + 1, dtype=torch.int32, device=dev)
-    d_pos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
-    d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
     d_mask = torch.zeros(S * mask_words, dtype=torch.int32, device=dev)
     d_dig = torch.zeros(S * tiles * 2, dtype=torch.int32, device=dev)
     core = CUDACore(W, H, max_batch=S)
-    # ---- one tick of every input: the states after it and its records
-    ticks = {}
-    for kind in ("webcam", "local"):
-        if kind == "webcam":
-            _, web = synth.webcam_stream(S + 1, W, H, device=dev)
-            web = web.reshape(S + 1, n)
-            before, frames = web[:S].clone(), web[1:].clone()
-        else:
-            before, fwd = local_streams(S, 1, W, H, dev)
-            frames = fwd[:, 0].contiguous()
-        states = before.clone()
-        torch.cuda.synchronize()
-        core.diff_multi_cwire_batch(frames, states, S, d_off, d_pos, d_cw, cwcap)
-        core.synchronize()
-        pos = d_pos.cpu().numpy().astype(np.int64)
-        counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
-        escapes = ((np.diff(pos) - 8 - 2 * ((counts.astype(np.int64) + 3) & ~3)) // 4).astype(np.uint32)
-        core.cwire_touched_tiles_batch(d_cw, counts, escapes, S, 1, d_mask)
-        core.synchronize()
-        touched = int(sum(bin(int(v) & 0xFFFFFFFF).count("1") for v in d_mask.cpu().numpy()))
-        ticks[kind] = (states, d_cw[:int(pos[S])].clone(), counts, escapes, touched)
-        del before, frames
-    aligned = ticks["webcam"][0]
+    ticks = one_tick(W, H, S, core, d_mask, dev)        # the legs show the states after the tick
+    aligned = ticks["webcam"][1]
     assert aligned.data_ptr() % 16 == 0
     skew_buf = torch.empty(S * n + 16, dtype=torch.uint8, device=dev)
     skewed = skew_buf[1:1 + S * n]                       # 1080p: N is a multiple of 16, so every stream is one byte off
@@ -927,7 +872,7 @@ def run_wall(W, H, S, rounds, scales=(2, 4, 8)):
 
     def leg_masked(k, kind):
         place, d_wall, wall_w, wall_h = walls[k]
-        states, recs, counts, escapes, _ = ticks[kind]
+        _, states, recs, counts, escapes, _, _ = ticks[kind]
 
         def leg():
             for _ in range(passes):
@@ -941,36 +886,18 @@ def run_wall(W, H, S, rounds, scales=(2, 4, 8)):
         table[f"full_k{k}"] = leg_full(k, aligned)
         table[f"masked_webcam_k{k}"] = leg_masked(k, "webcam")
         table[f"masked_local_k{k}"] = leg_masked(k, "local")
-    times = {}
-    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
-        for name, leg in table.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            leg()
-            dt = time.perf_counter() - t0
-            if r:
-                times.setdefault(name, []).append(dt * 1e6 / (passes * S))
+    times = time_legs(table, rounds, passes * S)
     out = {"streams": S, "passes": passes, "tiles": tiles, "state_bytes": n, "columns": cols,
-           "touched_tiles_per_stream": {kind: round(ticks[kind][4] / S, 1) for kind in ticks}}
-    for name in table:
-        st = stats(times[name])
-        st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
-        out[name + "_us_per_stream"] = st
-    med = {k: statistics.median(v) for k, v in times.items()}
-
-    def spread(*names):
-        return max(max(times[k]) - min(times[k]) for k in names)
-
-    out["masked_local_over_full"] = {f"k{k}": round(med[f"masked_local_k{k}"] / med[f"full_k{k}"], 3) for k in scales}
-    out["masked_local_cheaper_than_full"] = bool(all(
-        med[f"masked_local_k{k}"] + spread(f"masked_local_k{k}", f"full_k{k}") < med[f"full_k{k}"] for k in scales))
-    out["full_k8_over_digest"] = round(med["full_k8"] / med["digest"], 3)
-    out["full_k8_no_slower_than_digest"] = bool(med["full_k8"] <= med["digest"] + spread("full_k8", "digest"))
+           "touched_tiles_per_stream": {kind: round(ticks[kind][6] / S, 1) for kind in ticks}}
+    fig = report(out, times, "_us_per_stream", spread=True)
+    out["masked_local_over_full"] = {f"k{k}": ratio(fig, f"masked_local_k{k}", f"full_k{k}") for k in scales}
+    out["masked_local_cheaper_than_full"] = all(cheaper(fig, f"masked_local_k{k}", f"full_k{k}") for k in scales)
+    out["full_k8_over_digest"], out["full_k8_no_slower_than_digest"] = versus(fig, "full_k8", "digest")
     core.close()
     return out
 
 
-def run_thumb(W, H, S, rounds, scales=(2, 4, 8)):
+def run_thumb(W, H, rounds, S, scales=(2, 4, 8)):
     """The thumb leg for one S -> its dictionary.  Every leg alternates between the states before and after ONE tick (A, B, A, ..)
     with the tick's tile mask, so every pass finds the held thumbnails one tick behind and does a tick's work; the route's
     thumbnail-core states follow in the same way.  All legs alternate within every round."""
@@ -980,34 +907,9 @@ def run_thumb(W, H, S, rounds, scales=(2, 4, 8)):
     n = 3 * W * H
     mask_words = (state_tiles(n) + 31) // 32
     passes = 2 * max(1, min(8, 64 // S))
-    cwcap = cwire_bytes_max(n, S)
-    d_off = torch.zeros(S + 1, dtype=torch.int32, device=dev)
-    d_pos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
-    d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
     d_mask = torch.zeros(S * mask_words, dtype=torch.int32, device=dev)
     core = CUDACore(W, H, max_batch=S)
-    ticks = {}
-    for kind in ("webcam", "local"):
-        if kind == "webcam":
-            _, web = synth.webcam_stream(S + 1, W, H, device=dev)
-            web = web.reshape(S + 1, n)
-            before, frames = web[:S].clone(), web[1:].clone()
-        else:
-            before, fwd = local_streams(S, 1, W, H, dev)
-            frames = fwd[:, 0].contiguous()
-        after = before.clone()
-        torch.cuda.synchronize()
-        core.diff_multi_cwire_batch(frames, after, S, d_off, d_pos, d_cw, cwcap)
-        core.synchronize()
-        pos = d_pos.cpu().numpy().astype(np.int64)
-        counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
-        escapes = ((np.diff(pos) - 8 - 2 * ((counts.astype(np.int64) + 3) & ~3)) // 4).astype(np.uint32)
-        d_kind_mask = torch.zeros_like(d_mask)
-        core.cwire_touched_tiles_batch(d_cw, counts, escapes, S, 1, d_kind_mask)
-        core.synchronize()
-        touched = int(sum(bin(int(v) & 0xFFFFFFFF).count("1") for v in d_kind_mask.cpu().numpy()))
-        ticks[kind] = ((before, after), d_cw[:int(pos[S])].clone(), counts, escapes, d_kind_mask, touched)
-        del frames
+    ticks = one_tick(W, H, S, core, d_mask, dev)
     geo = {}
     for k in scales:
         _, tw, th = wall_thumb_size(W, H, k)
@@ -1038,8 +940,8 @@ def run_thumb(W, H, S, rounds, scales=(2, 4, 8)):
         g["small"].diff_multi_cwire_batch(g["wall"], held, S, *out, g["cap"])
 
     table, checked = {}, 0
-    for kind in ("webcam", "local"):
-        (A, B), recs, counts, escapes, kmask, _ = ticks[kind]
+    for kind in KINDS:
+        A, B, recs, counts, escapes, kmask, _ = ticks[kind]
         for k in scales:
             g = geo[k]
             held = {name: thumbs_of(A, k) for name in ("touched", "masked", "null", "route")}
@@ -1086,78 +988,36 @@ def run_thumb(W, H, S, rounds, scales=(2, 4, 8)):
                 return {f"touched_plus_call_{kind}_k{k}": touched_plus_call, f"call_{kind}_k{k}": call_masked,
                         f"call_nullmask_{kind}_k{k}": call_null, f"route_{kind}_k{k}": the_route}
             table.update(legs())
-    times = {}
-    for r in range(rounds + 1):                            # round 0 warms every leg up and is dropped
-        for name, leg in table.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            leg()
-            dt = time.perf_counter() - t0
-            if r:
-                times.setdefault(name, []).append(dt * 1e6 / (passes * S))
+    times = time_legs(table, rounds, passes * S)
     out = {"streams": S, "passes": passes, "tiles": state_tiles(n), "state_bytes": n, "records_equal_to_the_route": checked,
-           "touched_tiles_per_stream": {kind: round(ticks[kind][5] / S, 1) for kind in ticks}}
-    for name in table:
-        st = stats(times[name])
-        st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
-        out[name + "_us_per_stream"] = st
-    med = {k: statistics.median(v) for k, v in times.items()}
-
-    def spread(*names):
-        return max(max(times[k]) - min(times[k]) for k in names)
-
+           "touched_tiles_per_stream": {kind: round(ticks[kind][6] / S, 1) for kind in ticks}}
+    fig = report(out, times, "_us_per_stream", spread=True)
     points = [(kind, k) for kind in ticks for k in scales]
-    out["touched_plus_call_over_route"] = {f"{kind}_k{k}": round(med[f"touched_plus_call_{kind}_k{k}"] / med[f"route_{kind}_k{k}"], 3)
+    out["touched_plus_call_over_route"] = {f"{kind}_k{k}": ratio(fig, f"touched_plus_call_{kind}_k{k}", f"route_{kind}_k{k}")
                                            for kind, k in points}
-    out["touched_plus_call_no_slower_than_route"] = bool(all(
-        med[f"touched_plus_call_{kind}_k{k}"] <= med[f"route_{kind}_k{k}"] + spread(f"touched_plus_call_{kind}_k{k}", f"route_{kind}_k{k}")
-        for kind, k in points))
-    out["call_local_over_nullmask"] = {f"k{k}": round(med[f"call_local_k{k}"] / med[f"call_nullmask_local_k{k}"], 3) for k in scales}
-    out["call_local_cheaper_than_nullmask"] = bool(all(
-        med[f"call_local_k{k}"] + spread(f"call_local_k{k}", f"call_nullmask_local_k{k}") < med[f"call_nullmask_local_k{k}"]
-        for k in scales))
+    out["touched_plus_call_no_slower_than_route"] = all(versus(fig, f"touched_plus_call_{kind}_k{k}", f"route_{kind}_k{k}")[1]
+                                                        for kind, k in points)
+    out["call_local_over_nullmask"] = {f"k{k}": ratio(fig, f"call_local_k{k}", f"call_nullmask_local_k{k}") for k in scales}
+    out["call_local_cheaper_than_nullmask"] = all(cheaper(fig, f"call_local_k{k}", f"call_nullmask_local_k{k}") for k in scales)
     for g in geo.values():
         g["small"].close()
     core.close()
     return out
 
 
-def run_coalesce(W, H, S, T, rounds, kind):
+def run_coalesce(W, H, rounds, S, T, kind):
     """The coalesce leg for one (S, T) and one input -> its dictionary.  coalesce: mi355_cwire_coalesce_cwire_batch on the
     burst's records, nothing else.  state_route: what a relay did before -- mi355_apply_multi_stream_cwire_batch onto states it
     holds, then mi355_diff_multi_cwire_batch of a threshold-0 core between the new states and the saved ones (which the call
     advances), both on one core, no synchronisation in between."""
-    import numpy as np
     from cudavideostream_amd import CUDACore, cwire_bytes_max
     dev = torch.device("cuda", 0)
     n, B = 3 * W * H, S * T
     passes = 2 * max(1, 1024 // B)                     # ~2 k records per timed window
-    if kind == "webcam":                                # run_burst's input: one stream cut into S pieces
-        _, web = synth.webcam_stream(B + 1, W, H, device=dev)
-        web = web.reshape(B + 1, n)
-        states0, fwd = web[0:B:T].clone(), web[1:].reshape(S, T, n)
-    else:
-        states0, fwd = local_streams(S, T, W, H, dev)
-    per_call = min(S, max(1, ((1 << 32) - 1) // n // T))             # whole streams per call: max_batch * N < 2^32
-    chunks = [(s0, min(per_call, S - s0)) for s0 in range(0, S, per_call)]
-    recs = []                                           # per chunk: (records, counts, escapes, bytes)
+    states0, fwd = burst_input(kind, S, T, W, H, dev)
+    per_call, chunks = burst_chunks(S, T, n)
     srv_states = states0.clone()
-    with CUDACore(W, H, max_batch=per_call * T) as server:
-        for s0, ns in chunks:
-            nb = ns * T
-            cwcap = cwire_bytes_max(n, nb)
-            d_off = torch.zeros(nb + 1, dtype=torch.int32, device=dev)
-            d_pos = torch.zeros(nb + 1, dtype=torch.int64, device=dev)
-            d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
-            torch.cuda.synchronize()
-            server.diff_multi_stream_cwire_batch(fwd[s0], srv_states[s0], ns, T, d_off, d_pos, d_cw, cwcap)
-            server.synchronize()
-            pos = d_pos.cpu().numpy().astype(np.int64)
-            counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
-            pad = (counts.astype(np.int64) + 3) & ~3
-            escapes = ((np.diff(pos) - 8 - 2 * pad) // 4).astype(np.uint32)
-            recs.append((d_cw[:int(pos[nb])].clone(), counts, escapes, int(pos[nb])))
-            del d_cw
+    recs = sender_records(W, H, fwd, srv_states)       # per chunk (records, counts, escapes, positions)
     ocap = cwire_bytes_max(n, per_call)
     d_ooff = torch.zeros(per_call + 1, dtype=torch.int32, device=dev)
     d_opos = torch.zeros(per_call + 1, dtype=torch.int64, device=dev)
@@ -1181,21 +1041,13 @@ def run_coalesce(W, H, S, T, rounds, kind):
                 route.diff_multi_cwire_batch(states[s0], saved[s0], ns, d_roff, d_rpos, d_rout, ocap)
         route.synchronize()
 
-    table = {"coalesce": leg_coalesce, "state_route": leg_route}
-    times = {}
-    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
-        for name, leg in table.items():
-            states.copy_(states0)
-            saved.copy_(states0)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            leg()
-            dt = time.perf_counter() - t0
-            if r:
-                times.setdefault(name, []).append(dt * 1e6 / (passes * B))
+    def before(name=None):
+        states.copy_(states0)
+        saved.copy_(states0)
+
+    times = time_legs({"coalesce": leg_coalesce, "state_route": leg_route}, rounds, passes * B, before=before)
     # one burst from the base states: both ways make the same records, and they lead to the sender's states
-    states.copy_(states0)
-    saved.copy_(states0)
+    before()
     out_bytes = out_entries = 0
     torch.cuda.synchronize()
     for (s0, ns), r in zip(chunks, recs):
@@ -1209,23 +1061,19 @@ def run_coalesce(W, H, S, T, rounds, kind):
         out_bytes += nbytes
         out_entries += int(d_ooff[ns].item())
     assert torch.equal(states, srv_states) and torch.equal(saved, srv_states)
-    in_bytes = sum(r[3] for r in recs)
+    in_bytes = sum(int(r[3][-1]) for r in recs)
     out = {"input": kind, "streams": S, "frames": T, "passes": passes, "calls_per_burst": len(chunks),
            "input_entries_per_stream": round(sum(int(r[1].sum()) for r in recs) / S, 1), "output_entries_per_stream": round(out_entries / S, 1),
            "input_bytes_per_stream": round(in_bytes / S, 1), "output_bytes_per_stream": round(out_bytes / S, 1),
            "output_over_input_bytes": round(out_bytes / in_bytes, 4)}
-    for name in table:
-        st = stats(times[name])
-        st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
-        out[name + "_us_per_input_record"] = st
-    med = {k: statistics.median(v) for k, v in times.items()}
-    out["state_route_over_coalesce"] = round(med["state_route"] / med["coalesce"], 3)
+    fig = report(out, times, "_us_per_input_record", spread=True)
+    out["state_route_over_coalesce"] = ratio(fig, "state_route", "coalesce")
     relay.close()
     route.close()
     return out
 
 
-def run_crop(W, H, S, rounds, kind):
+def run_crop(W, H, rounds, S, kind):
     """The crop leg for one S and one input, T = 1 -> its dictionary.  coalesce: mi355_cwire_coalesce_cwire_batch on the records of
     one tick, the nearest route without the crop call.  crop_quarter / crop_full: mi355_cwire_crop_cwire_batch on the same records
     with the rectangle (W/4, H/4, W/2, H/2) for every stream, and with the full frame.  All on one core's own stream, alternating
@@ -1235,31 +1083,9 @@ def run_crop(W, H, S, rounds, kind):
     dev = torch.device("cuda", 0)
     n, T = 3 * W * H, 1
     passes = 2 * max(1, 1024 // S)                     # ~2 k records per timed window
-    if kind == "webcam":                                # run_burst's input: one stream cut into S pieces
-        _, web = synth.webcam_stream(S + 1, W, H, device=dev)
-        web = web.reshape(S + 1, n)
-        states0, fwd = web[0:S].clone(), web[1:].reshape(S, T, n)
-    else:
-        states0, fwd = local_streams(S, T, W, H, dev)
-    per_call = min(S, max(1, ((1 << 32) - 1) // n))                  # streams per call: max_batch * N < 2^32
-    chunks = [(s0, min(per_call, S - s0)) for s0 in range(0, S, per_call)]
-    recs = []                                           # per chunk: (records, counts, escapes, bytes)
-    srv_states = states0.clone()
-    with CUDACore(W, H, max_batch=per_call) as server:
-        for s0, ns in chunks:
-            cwcap = cwire_bytes_max(n, ns)
-            d_off = torch.zeros(ns + 1, dtype=torch.int32, device=dev)
-            d_pos = torch.zeros(ns + 1, dtype=torch.int64, device=dev)
-            d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
-            torch.cuda.synchronize()
-            server.diff_multi_stream_cwire_batch(fwd[s0], srv_states[s0], ns, T, d_off, d_pos, d_cw, cwcap)
-            server.synchronize()
-            pos = d_pos.cpu().numpy().astype(np.int64)
-            counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
-            pad = (counts.astype(np.int64) + 3) & ~3
-            escapes = ((np.diff(pos) - 8 - 2 * pad) // 4).astype(np.uint32)
-            recs.append((d_cw[:int(pos[ns])].clone(), counts, escapes, int(pos[ns])))
-            del d_cw
+    states0, fwd = burst_input(kind, S, T, W, H, dev)
+    per_call, chunks = burst_chunks(S, T, n)
+    recs = sender_records(W, H, fwd, states0.clone())   # per chunk (records, counts, escapes, positions)
     ocap = cwire_bytes_max(n, per_call)
     d_ooff = torch.zeros(per_call + 1, dtype=torch.int32, device=dev)
     d_opos = torch.zeros(per_call + 1, dtype=torch.int64, device=dev)
@@ -1284,16 +1110,7 @@ def run_crop(W, H, S, rounds, kind):
             relay.synchronize()
         return leg
 
-    table = {"coalesce": leg_coalesce, "crop_quarter": leg_crop(quarter), "crop_full": leg_crop(full)}
-    times = {}
-    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
-        for name, leg in table.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            leg()
-            dt = time.perf_counter() - t0
-            if r:
-                times.setdefault(name, []).append(dt * 1e6 / (passes * S))
+    times = time_legs({"coalesce": leg_coalesce, "crop_quarter": leg_crop(quarter), "crop_full": leg_crop(full)}, rounds, passes * S)
     # the full-frame crop of one record per stream is the coalescer's output (and the input); the quarter holds fewer entries
     in_entries = quarter_entries = quarter_bytes = 0
     for (s0, ns), r in zip(chunks, recs):
@@ -1301,7 +1118,7 @@ def run_crop(W, H, S, rounds, kind):
         relay.cwire_crop_cwire_batch(r[0], r[1], r[2], ns, T, full, d_ooff, d_opos, d_out, ocap)
         relay.synchronize()
         nbytes = int(d_cpos[ns].item())
-        assert nbytes == r[3] and torch.equal(d_opos[:ns + 1], d_cpos[:ns + 1]) and torch.equal(d_out[:nbytes], d_cout[:nbytes])
+        assert nbytes == int(r[3][-1]) and torch.equal(d_opos[:ns + 1], d_cpos[:ns + 1]) and torch.equal(d_out[:nbytes], d_cout[:nbytes])
         assert torch.equal(d_out[:nbytes], r[0])
         in_entries += int(d_coff[ns].item())
         relay.cwire_crop_cwire_batch(r[0], r[1], r[2], ns, T, quarter, d_ooff, d_opos, d_out, ocap)
@@ -1309,27 +1126,22 @@ def run_crop(W, H, S, rounds, kind):
         quarter_entries += int(d_ooff[ns].item())
         quarter_bytes += int(d_opos[ns].item())
     assert quarter_entries <= in_entries
-    in_bytes = sum(r[3] for r in recs)
+    in_bytes = sum(int(r[3][-1]) for r in recs)
     out = {"input": kind, "streams": S, "frames": T, "passes": passes, "calls_per_tick": len(chunks),
            "rectangle": [int(v) for v in quarter[0]],
            "input_entries_per_stream": round(in_entries / S, 1), "quarter_entries_per_stream": round(quarter_entries / S, 1),
            "input_bytes_per_stream": round(in_bytes / S, 1), "quarter_bytes_per_stream": round(quarter_bytes / S, 1)}
-    med, spread = {}, {}
-    for name in table:
-        st = stats(times[name])
-        st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
-        out[name + "_us_per_stream"] = st
-        med[name], spread[name] = st["median"], st["max"] - st["min"]
-    out["crop_quarter_over_coalesce"] = round(med["crop_quarter"] / med["coalesce"], 3)
-    out["crop_full_over_coalesce"] = round(med["crop_full"] / med["coalesce"], 3)
+    fig = report(out, times, "_us_per_stream", spread=True, as_printed=True)
     # the expectation: the quarter no slower than the coalescer by more than the rounds' spread (of either leg)
-    out["quarter_no_slower_than_coalesce"] = bool(med["crop_quarter"] <= med["coalesce"] + max(spread["crop_quarter"], spread["coalesce"]))
-    out["full_minus_coalesce_us_per_call"] = round((med["crop_full"] - med["coalesce"]) * S / len(chunks), 3)
+    out["crop_quarter_over_coalesce"], quarter_ok = versus(fig, "crop_quarter", "coalesce")
+    out["crop_full_over_coalesce"] = ratio(fig, "crop_full", "coalesce")
+    out["quarter_no_slower_than_coalesce"] = quarter_ok
+    out["full_minus_coalesce_us_per_call"] = round((fig["crop_full"][0] - fig["coalesce"][0]) * S / len(chunks), 3)
     relay.close()
     return out
 
 
-def run_split(W, H, S, rounds, kind, limits=(1400, 8972)):
+def run_split(W, H, rounds, S, kind, limits=(1400, 8972)):
     """The split leg for one S and one input, T = 1 -> its dictionary.  coalesce: mi355_cwire_coalesce_cwire_batch on the records of
     one tick (with T = 1 it gives the input back): the nearest call of the family that reads every record once and writes it once.
     split_M: mi355_cwire_split_cwire_batch on the same records at max_bytes = M.  All on one core's own stream, alternating within
@@ -1339,31 +1151,9 @@ def run_split(W, H, S, rounds, kind, limits=(1400, 8972)):
     dev = torch.device("cuda", 0)
     n, T = 3 * W * H, 1
     passes = 2 * max(1, 1024 // S)                     # ~2 k records per timed window
-    if kind == "webcam":                                # run_burst's input: one stream cut into S pieces
-        _, web = synth.webcam_stream(S + 1, W, H, device=dev)
-        web = web.reshape(S + 1, n)
-        states0, fwd = web[0:S].clone(), web[1:].reshape(S, T, n)
-    else:
-        states0, fwd = local_streams(S, T, W, H, dev)
-    per_call = min(S, max(1, ((1 << 32) - 1) // n))                  # streams per call: max_batch * N < 2^32
-    chunks = [(s0, min(per_call, S - s0)) for s0 in range(0, S, per_call)]
-    recs = []                                           # per chunk: (records, counts, escapes, bytes)
-    srv_states = states0.clone()
-    with CUDACore(W, H, max_batch=per_call) as server:
-        for s0, ns in chunks:
-            cwcap = cwire_bytes_max(n, ns)
-            d_off = torch.zeros(ns + 1, dtype=torch.int32, device=dev)
-            d_pos = torch.zeros(ns + 1, dtype=torch.int64, device=dev)
-            d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
-            torch.cuda.synchronize()
-            server.diff_multi_stream_cwire_batch(fwd[s0], srv_states[s0], ns, T, d_off, d_pos, d_cw, cwcap)
-            server.synchronize()
-            pos = d_pos.cpu().numpy().astype(np.int64)
-            counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
-            pad = (counts.astype(np.int64) + 3) & ~3
-            escapes = ((np.diff(pos) - 8 - 2 * pad) // 4).astype(np.uint32)
-            recs.append((d_cw[:int(pos[ns])].clone(), counts, escapes, int(pos[ns])))
-            del d_cw
+    states0, fwd = burst_input(kind, S, T, W, H, dev)
+    per_call, chunks = burst_chunks(S, T, n)
+    recs = sender_records(W, H, fwd, states0.clone())   # per chunk (records, counts, escapes, positions)
     ocap = cwire_bytes_max(n, per_call)
     d_ooff = torch.zeros(per_call + 1, dtype=torch.int32, device=dev)
     d_opos = torch.zeros(per_call + 1, dtype=torch.int64, device=dev)
@@ -1393,7 +1183,7 @@ def run_split(W, H, S, rounds, kind, limits=(1400, 8972)):
 
     # the pieces are the host form's, at every limit
     in_entries = sum(int(r[1].sum()) for r in recs)
-    in_bytes = sum(r[3] for r in recs)
+    in_bytes = sum(int(r[3][-1]) for r in recs)
     out = {"input": kind, "streams": S, "frames": T, "passes": passes, "calls_per_tick": len(chunks),
            "input_entries_per_stream": round(in_entries / S, 1), "input_bytes_per_stream": round(in_bytes / S, 1)}
     for M in limits:
@@ -1412,61 +1202,29 @@ def run_split(W, H, S, rounds, kind, limits=(1400, 8972)):
         out[f"piece_bytes_per_stream_{M}"] = round(nbytes / S, 1)
     table = {"coalesce": leg_coalesce}
     table.update({f"split_{M}": leg_split(M) for M in limits})
-    times = {}
-    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
-        for name, leg in table.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            leg()
-            dt = time.perf_counter() - t0
-            if r:
-                times.setdefault(name, []).append(dt * 1e6 / (passes * S))
-    med, spread = {}, {}
-    for name in table:
-        st = stats(times[name])
-        st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
-        out[name + "_us_per_record"] = st
-        med[name], spread[name] = st["median"], st["max"] - st["min"]
+    times = time_legs(table, rounds, passes * S)
+    fig = report(out, times, "_us_per_record", spread=True, as_printed=True)
     for M in limits:
-        out[f"split_{M}_over_coalesce"] = round(med[f"split_{M}"] / med["coalesce"], 3)
         # the expectation: no slower than the coalescer by more than the rounds' spread (of either leg)
-        out[f"split_{M}_no_slower_than_coalesce"] = bool(med[f"split_{M}"] <= med["coalesce"] + max(spread[f"split_{M}"], spread["coalesce"]))
+        out[f"split_{M}_over_coalesce"], out[f"split_{M}_no_slower_than_coalesce"] = versus(fig, f"split_{M}", "coalesce")
     relay.close()
     return out
 
 
-def run_fec(W, H, S, rounds, kind, M=1400, G=8):
+def run_fec(W, H, rounds, S, kind, M=1400, G=8):
     """The fec leg for one S and one input, T = 1 -> its dictionary.  split: mi355_cwire_split_cwire_batch at max_bytes = M on the
     records of one tick; fec_k1 / fec_k2: mi355_cwire_fec_batch with K = 1 / 2 parity blocks per group of G on the pieces that call
     left; repair_one / repair_two: mi355_cwire_fec_repair_batch with one job per stream, the first piece (the first two) of its
     first group lost.  All on one core's own stream, alternating within every round.  Before anything is timed the parity is
     compared with mi355_cwire_fec_host and the rebuilt pieces with the pieces."""
     import numpy as np
-    from cudavideostream_amd import (CUDACore, cwire_bytes_max, cwire_fec_groups_max, cwire_fec_host, cwire_split_bytes_max, cwire_split_host,
+    from cudavideostream_amd import (CUDACore, cwire_fec_groups_max, cwire_fec_host, cwire_split_bytes_max, cwire_split_host,
                                      cwire_split_pieces_max, lib)
     dev = torch.device("cuda", 0)
     n, T = 3 * W * H, 1
     passes = 2 * max(1, 1024 // S)                     # ~2 k records per timed window
-    if kind == "webcam":                                # run_split's input
-        _, web = synth.webcam_stream(S + 1, W, H, device=dev)
-        web = web.reshape(S + 1, n)
-        states0, fwd = web[0:S].clone(), web[1:].reshape(S, T, n)
-    else:
-        states0, fwd = local_streams(S, T, W, H, dev)
-    assert S * n < (1 << 32), "one call per tick: max_batch * N < 2^32"
-    cwcap = cwire_bytes_max(n, S)
-    with CUDACore(W, H, max_batch=S) as server:
-        d_off = torch.zeros(S + 1, dtype=torch.int32, device=dev)
-        d_pos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
-        d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
-        torch.cuda.synchronize()
-        server.diff_multi_stream_cwire_batch(fwd, states0.clone(), S, T, d_off, d_pos, d_cw, cwcap)
-        server.synchronize()
-        pos = d_pos.cpu().numpy().astype(np.int64)
-        counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
-        escapes = ((np.diff(pos) - 8 - 2 * ((counts.astype(np.int64) + 3) & ~3)) // 4).astype(np.uint32)
-        recs = d_cw[:int(pos[S])].clone()
-        del d_cw
+    states0, fwd = burst_input(kind, S, T, W, H, dev)   # run_split's input
+    recs, counts, escapes, pos = one_call(sender_records(W, H, fwd, states0.clone()))
     pcap = sum(cwire_split_pieces_max(c, e, M) for c, e in zip(counts, escapes))
     bcap = sum(cwire_split_bytes_max(c, e, M) for c, e in zip(counts, escapes))
     gcap = cwire_fec_groups_max(pcap, S, G)
@@ -1554,31 +1312,17 @@ def run_fec(W, H, S, rounds, kind, M=1400, G=8):
              "repair_one": timed(lambda: repair(1)), "repair_two": timed(lambda: repair(2))}
     split()
     relay.synchronize()
-    times = {}
-    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
-        for name, leg in table.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            leg()
-            dt = time.perf_counter() - t0
-            if r:
-                per = jobs[1][0] if name.startswith("repair") else S
-                times.setdefault(name, []).append(dt * 1e6 / (passes * max(per, 1)))
-    med, spread = {}, {}
-    for name in table:
-        st = stats(times[name])
-        st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
-        out[name + ("_us_per_job" if name.startswith("repair") else "_us_per_record")] = st
-        med[name], spread[name] = st["median"], st["max"] - st["min"]
-    for K in (1, 2):
-        out[f"fec_k{K}_over_split"] = round(med[f"fec_k{K}"] / med["split"], 3)
+    times = time_legs(table, rounds, lambda name: passes * max(jobs[1][0] if name.startswith("repair") else S, 1))
+    fig = report(out, {k: v for k, v in times.items() if not k.startswith("repair")}, "_us_per_record", spread=True, as_printed=True)
+    report(out, {k: v for k, v in times.items() if k.startswith("repair")}, "_us_per_job", spread=True)
+    out["fec_k1_over_split"] = ratio(fig, "fec_k1", "split")
     # the expectation: at K = 2 no slower than the split call that feeds it by more than the rounds' spread (of either leg)
-    out["fec_k2_no_slower_than_split"] = bool(med["fec_k2"] <= med["split"] + max(spread["fec_k2"], spread["split"]))
+    out["fec_k2_over_split"], out["fec_k2_no_slower_than_split"] = versus(fig, "fec_k2", "split")
     relay.close()
     return out
 
 
-def run_mosaic(W, H, S, T, rounds, kind):
+def run_mosaic(W, H, rounds, S, T, kind):
     """The mosaic leg for one (S, T) and one input -> its dictionary.  mosaic: mi355_cwire_mosaic_cwire_batch on the burst's
     records, whole frames in a C x R grid.  state_route: mi355_apply_multi_stream_cwire_batch onto states the relay holds,
     mi355_wall_compose_batch at k = 1 into a canvas, a synchronize, mi355_diff_stream_cwire_batch(nframes = 1) on a threshold-0
@@ -1594,27 +1338,10 @@ def run_mosaic(W, H, S, T, rounds, kind):
     nc = 3 * cw * ch
     assert B * n < (1 << 32) and nc < (1 << 31), "the leg runs in one call: max_batch * N < 2^32 and a canvas below 2^31 bytes"
     passes = 2 * max(1, 256 // B)
-    if kind == "webcam":                                # run_burst's input: one stream cut into S pieces
-        _, web = synth.webcam_stream(B + 1, W, H, device=dev)
-        web = web.reshape(B + 1, n)
-        states0, fwd = web[0:B:T].clone(), web[1:].reshape(S, T, n)
-    else:
-        states0, fwd = local_streams(S, T, W, H, dev)
-    cwcap = cwire_bytes_max(n, B)
-    d_off = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-    d_pos = torch.zeros(B + 1, dtype=torch.int64, device=dev)
-    d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
-    srv_states = states0.clone()
-    with CUDACore(W, H, max_batch=B) as server:
-        torch.cuda.synchronize()
-        server.diff_multi_stream_cwire_batch(fwd, srv_states, S, T, d_off, d_pos, d_cw, cwcap)
-        server.synchronize()
-    pos = d_pos.cpu().numpy().astype(np.int64)
-    counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
-    pad = (counts.astype(np.int64) + 3) & ~3
-    escapes = ((np.diff(pos) - 8 - 2 * pad) // 4).astype(np.uint32)
-    recs, in_bytes = d_cw[:int(pos[B])].clone(), int(pos[B])
-    del d_cw, fwd, srv_states
+    states0, fwd = burst_input(kind, S, T, W, H, dev)
+    recs, counts, escapes, pos = one_call(sender_records(W, H, fwd, states0.clone()))
+    in_bytes = int(pos[B])
+    del fwd
     ocap = cwire_bytes_max(nc, 1)
     d_ooff = torch.zeros(2, dtype=torch.int32, device=dev)
     d_opos = torch.zeros(2, dtype=torch.int64, device=dev)
@@ -1657,33 +1384,18 @@ def run_mosaic(W, H, S, T, rounds, kind):
             route_pass()
         canvas.synchronize()
 
-    table = {"mosaic": leg_mosaic, "state_route": leg_route}
-    times = {}
-    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
-        for name, leg in table.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            leg()
-            dt = time.perf_counter() - t0
-            if r:
-                times.setdefault(name, []).append(dt * 1e6 / (passes * B))
+    times = time_legs({"mosaic": leg_mosaic, "state_route": leg_route}, rounds, passes * B)
     out = {"input": kind, "streams": S, "frames": T, "passes": passes, "grid": [C, R], "canvas": [cw, ch],
            "input_entries_per_record": round(float(counts.sum()) / B, 1), "input_bytes_per_record": round(in_bytes / B, 1),
            "canvas_entries": out_entries, "canvas_record_bytes": out_bytes, "route_record_equals_mosaic": equal}
-    med, spread = {}, {}
-    for name in table:
-        st = stats(times[name])
-        st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
-        out[name + "_us_per_record"] = st
-        med[name], spread[name] = st["median"], st["max"] - st["min"]
-    out["mosaic_over_route"] = round(med["mosaic"] / med["state_route"], 3)
-    out["mosaic_no_slower_than_route"] = bool(med["mosaic"] <= med["state_route"] + max(spread["mosaic"], spread["state_route"]))
+    fig = report(out, times, "_us_per_record", spread=True, as_printed=True)
+    out["mosaic_over_route"], out["mosaic_no_slower_than_route"] = versus(fig, "mosaic", "state_route")
     for c in (relay, route, canvas):
         c.close()
     return out
 
 
-def run_budget(W, H, S, rounds):
+def run_budget(W, H, rounds, S):
     """The budget leg for one S -> its dictionary.  budget: mi355_cwire_budget_cwire_batch on the records of one tick with every
     stream's budget at half of its count, on the states as the tick left them.  second_diff: mi355_diff_multi_cwire_batch over the
     same S frames from the states before the tick -- the cheapest re-diff a caller has without the call (and one that still lacks
@@ -1694,30 +1406,24 @@ def run_budget(W, H, S, rounds):
     dev = torch.device("cuda", 0)
     n = 3 * W * H
     passes = max(2, min(16, 128 // S))
-    _, web = synth.webcam_stream(S + 1, W, H, device=dev)
-    web = web.reshape(S + 1, n)
-    pre, frames = web[:S].clone(), web[1:].clone()      # stream s: webcam frame s -> s + 1
-    cwcap = cwire_bytes_max(n, S)
-    d_off = torch.zeros(S + 1, dtype=torch.int32, device=dev)
-    d_pos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
-    d_cw = torch.empty(cwcap, dtype=torch.uint8, device=dev)
-    d_thr = torch.zeros(S, dtype=torch.int32, device=dev)
-    d_ooff, d_opos, d_out = torch.zeros_like(d_off), torch.zeros_like(d_pos), torch.empty_like(d_cw)
-    d_roff, d_rpos, d_rcw = torch.zeros_like(d_off), torch.zeros_like(d_pos), torch.empty_like(d_cw)
+    pre, fwd = burst_input("webcam", S, 1, W, H, dev)   # stream s: webcam frame s -> s + 1
+    frames = fwd[:, 0].clone()
     post = pre.clone()
+    recs, counts, escapes, pos = one_call(sender_records(W, H, fwd, post))
+    cwcap = cwire_bytes_max(n, S)
+    d_thr = torch.zeros(S, dtype=torch.int32, device=dev)
+    d_ooff = torch.zeros(S + 1, dtype=torch.int32, device=dev)
+    d_opos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
+    d_out = torch.empty(cwcap, dtype=torch.uint8, device=dev)
+    d_roff, d_rpos, d_rcw = torch.zeros_like(d_ooff), torch.zeros_like(d_opos), torch.empty_like(d_out)
     core = CUDACore(W, H, max_batch=S)
-    torch.cuda.synchronize()
-    core.diff_multi_cwire_batch(frames, post, S, d_off, d_pos, d_cw, cwcap)
-    core.synchronize()
-    pos = d_pos.cpu().numpy().astype(np.int64)
-    counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
-    escapes = ((np.diff(pos) - 8 - 2 * ((counts.astype(np.int64) + 3) & ~3)) // 4).astype(np.uint32)
     budgets = (counts // 2).astype(np.uint32)
     work = torch.empty(passes, S, n, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
 
     def leg_budget():
         for p in range(passes):
-            core.cwire_budget_cwire_batch(d_cw, counts, escapes, work[p], S, budgets, d_thr, d_ooff, d_opos, d_out, cwcap)
+            core.cwire_budget_cwire_batch(recs, counts, escapes, work[p], S, budgets, d_thr, d_ooff, d_opos, d_out, cwcap)
         core.synchronize()
 
     def leg_diff():
@@ -1725,30 +1431,71 @@ def run_budget(W, H, S, rounds):
             core.diff_multi_cwire_batch(frames, work[p], S, d_roff, d_rpos, d_rcw, cwcap)
         core.synchronize()
 
-    table = {"budget": (leg_budget, post), "second_diff": (leg_diff, pre)}
-    times = {}
-    for r in range(rounds + 1):                        # round 0 warms every leg up and is dropped
-        for name, (leg, start) in table.items():
-            work.copy_(start.unsqueeze(0).expand(passes, S, n))
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            leg()
-            dt = time.perf_counter() - t0
-            if r:
-                times.setdefault(name, []).append(dt * 1e6 / (passes * S))
+    start = {"budget": post, "second_diff": pre}
+    times = time_legs({"budget": leg_budget, "second_diff": leg_diff}, rounds, passes * S,
+                      before=lambda name: work.copy_(start[name].unsqueeze(0).expand(passes, S, n)))
     kept = np.diff(d_ooff.cpu().numpy().view(np.uint32).astype(np.int64))
     thr = d_thr.cpu().numpy().view(np.uint32)
-    assert (kept <= budgets).all() and (thr >= 20).all() and torch.equal(d_rpos, d_pos)
+    assert (kept <= budgets).all() and (thr >= 20).all() and np.array_equal(d_rpos.cpu().numpy(), pos)
     out = {"streams": S, "passes": passes, "entries_per_stream": round(float(counts.mean()), 1),
            "kept_entries_per_stream": round(float(kept.mean()), 1), "record_bytes_per_stream": round(int(pos[S]) / S, 1),
            "kept_bytes_per_stream": round(int(d_opos[S].item()) / S, 1), "threshold_min": int(thr.min()), "threshold_max": int(thr.max())}
-    for name in table:
-        st = stats(times[name])
-        st["spread"] = round((st["max"] - st["min"]) / st["median"], 4)
-        out[name + "_us_per_stream"] = st
-    out["second_diff_over_budget"] = round(statistics.median(times["second_diff"]) / statistics.median(times["budget"]), 3)
+    fig = report(out, times, "_us_per_stream", spread=True)
+    out["second_diff_over_budget"] = ratio(fig, "second_diff", "budget")
     core.close()
     return out
+
+
+# ---- the command line: one entry per --legs value that runs alone
+def ints(text):
+    return [int(v) for v in text.split(",")]
+
+
+def grid(**axes):
+    """Every combination of the axes' values, the first axis outermost -> the runners' keyword arguments."""
+    return [dict(zip(axes, p)) for p in itertools.product(*axes.values())]
+
+
+def activity_points(a):
+    """S of --streams with T = 1, and S = 16 with T = 16, on both inputs."""
+    return [dict(S=S, T=T, kind=kind) for S, T in [(S, 1) for S in ints(a.streams)] + [(16, 16)] for kind in KINDS]
+
+
+# run: the leg's runner, called with (W, H, rounds, **point); points: the points it runs at, from the arguments; bench: the name in
+# its JSON line, whose list of the points' dictionaries stands under the leg's own name; input, steps: further fields of that line;
+# quiet: no progress line on stderr; verdict: per part (the suffix of the points' booleans, the text if all hold, the text if not)
+LEGS = {
+    "client": dict(run=run_client, points=lambda a: grid(S=ints(a.streams), K=[a.steps]), bench="multi_client", input=True, steps=True,
+                   quiet=True),
+    "burst": dict(run=run_burst, points=lambda a: grid(S=ints(a.streams), T=ints(a.frames)), bench="multi_stream", input=True, quiet=True),
+    "burst_client": dict(run=run_burst_client, points=lambda a: grid(S=ints(a.streams), T=ints(a.frames), kind=KINDS),
+                         bench="multi_stream_client", quiet=True),
+    "coalesce": dict(run=run_coalesce, points=lambda a: grid(S=ints(a.streams), T=ints(a.frames), kind=KINDS), bench="multi_coalesce"),
+    "crop": dict(run=run_crop, points=lambda a: grid(S=ints(a.streams), kind=KINDS), bench="multi_crop"),
+    "split": dict(run=run_split, points=lambda a: grid(S=ints(a.streams), kind=KINDS), bench="multi_split",
+                  verdict=[("_no_slower_than_coalesce", "no slower than coalesce at every point", "slower than coalesce at some point")]),
+    "fec": dict(run=run_fec, points=lambda a: grid(S=ints(a.streams), kind=KINDS), bench="multi_fec",
+                verdict=[("fec_k2_no_slower_than_split", "parity at K = 2 no slower than split at every point",
+                          "parity at K = 2 slower than split at some point")]),
+    "mosaic": dict(run=run_mosaic, points=lambda a: grid(S=ints(a.streams), T=(1, 16), kind=KINDS), bench="multi_mosaic"),
+    "budget": dict(run=run_budget, points=lambda a: grid(S=ints(a.streams)), bench="multi_budget", input=True),
+    "activity": dict(run=run_activity, points=activity_points, bench="multi_activity",
+                     verdict=[("no_slower_than_burst_apply", "no slower than burst_apply at every point", "slower than burst_apply at some point")]),
+    "check": dict(run=run_check, points=activity_points, bench="multi_check",
+                  verdict=[("no_slower_than_burst_apply", "no slower than burst_apply at every point", "slower than burst_apply at some point")]),
+    "refresh": dict(run=run_refresh, points=lambda a: grid(S=ints(a.streams)), bench="multi_refresh",
+                    verdict=[("digest_no_slower_than_diff", "digest no slower than diff at every S", "digest slower than diff at some S")]),
+    "wall": dict(run=run_wall, points=lambda a: grid(S=ints(a.streams)), bench="multi_wall",
+                 verdict=[("masked_local_cheaper_than_full", "masked update on the moving block cheaper than the full compose at every k and S",
+                           "masked update on the moving block not cheaper than the full compose at some k or S"),
+                          ("full_k8_no_slower_than_digest", "full compose at k = 8 no slower than digest at every S",
+                           "full compose at k = 8 slower than digest at some S")]),
+    "thumb": dict(run=run_thumb, points=lambda a: grid(S=ints(a.streams)), bench="multi_thumb",
+                  verdict=[("touched_plus_call_no_slower_than_route", "touched tiles plus the call no slower than the wall-and-diff route at every point",
+                            "touched tiles plus the call slower than the wall-and-diff route at some point"),
+                           ("call_local_cheaper_than_nullmask", "the call with the moving block's mask cheaper than without a mask at every k and S",
+                            "the call with the moving block's mask not cheaper than without a mask at some k or S")]),
+}
 
 
 def main():
@@ -1758,162 +1505,35 @@ def main():
     ap.add_argument("--steps", type=int, default=8, help="K: webcam frames a stream walks through")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--legs", default="multi,cores_loop,pairs",
-                    help="of multi, cores_loop, pairs, write_probe; or client alone; or burst alone; or burst_client alone; or coalesce alone; or crop alone; or split alone; or fec alone; or mosaic alone; or budget alone; or activity alone; or check alone; or refresh alone; or wall alone; or thumb alone")
+                    help="of multi, cores_loop, pairs, write_probe" + "".join(f"; or {name} alone" for name in LEGS))
     ap.add_argument("--frames", default="4,16,64", help="burst, burst_client and coalesce legs: T, frames per stream and call")
     a = ap.parse_args()
     have = load_library()
     W, H = (int(v) for v in a.size.split("x"))
-    if a.legs == "client":
-        per = []
-        for S in (int(v) for v in a.streams.split(",")):
-            per.append(run_client(W, H, S, a.steps, a.rounds))
+    if a.legs not in LEGS:
+        for S in ints(a.streams):
+            run(W, H, S, a.steps, a.rounds, set(a.legs.split(",")), have)
             torch.cuda.empty_cache()
-        print(json.dumps({"bench": "multi_client", "size": f"{W}x{H}", "input": "synth.webcam_stream", "rounds": a.rounds,
-                          "steps": a.steps, "client": per}), flush=True)
         return
-    if a.legs == "burst":
-        per = []
-        for S in (int(v) for v in a.streams.split(",")):
-            for T in (int(v) for v in a.frames.split(",")):
-                per.append(run_burst(W, H, S, T, a.rounds))
-                torch.cuda.empty_cache()
-        print(json.dumps({"bench": "multi_stream", "size": f"{W}x{H}", "input": "synth.webcam_stream", "rounds": a.rounds,
-                          "burst": per}), flush=True)
-        return
-    if a.legs == "burst_client":
-        per = []
-        for S in (int(v) for v in a.streams.split(",")):
-            for T in (int(v) for v in a.frames.split(",")):
-                for kind in ("webcam", "local"):
-                    per.append(run_burst_client(W, H, S, T, a.rounds, kind))
-                    torch.cuda.empty_cache()
-        print(json.dumps({"bench": "multi_stream_client", "size": f"{W}x{H}", "rounds": a.rounds, "burst_client": per}), flush=True)
-        return
-    if a.legs == "coalesce":
-        per = []
-        for S in (int(v) for v in a.streams.split(",")):
-            for T in (int(v) for v in a.frames.split(",")):
-                for kind in ("webcam", "local"):
-                    per.append(run_coalesce(W, H, S, T, a.rounds, kind))
-                    print(f"coalesce S={S} T={T} {kind}: done", file=sys.stderr, flush=True)
-                    torch.cuda.empty_cache()
-        print(json.dumps({"bench": "multi_coalesce", "size": f"{W}x{H}", "rounds": a.rounds, "coalesce": per}), flush=True)
-        return
-    if a.legs == "crop":
-        per = []
-        for S in (int(v) for v in a.streams.split(",")):
-            for kind in ("webcam", "local"):
-                per.append(run_crop(W, H, S, a.rounds, kind))
-                print(f"crop S={S} {kind}: done", file=sys.stderr, flush=True)
-                torch.cuda.empty_cache()
-        print(json.dumps({"bench": "multi_crop", "size": f"{W}x{H}", "rounds": a.rounds, "crop": per}), flush=True)
-        return
-    if a.legs == "split":
-        per = []
-        for S in (int(v) for v in a.streams.split(",")):
-            for kind in ("webcam", "local"):
-                per.append(run_split(W, H, S, a.rounds, kind))
-                print(f"split S={S} {kind}: done", file=sys.stderr, flush=True)
-                torch.cuda.empty_cache()
-        ok = all(p[k] for p in per for k in p if k.endswith("_no_slower_than_coalesce"))
-        print(json.dumps({"bench": "multi_split", "size": f"{W}x{H}", "rounds": a.rounds, "split": per,
-                          "verdict": "no slower than coalesce at every point" if ok else "slower than coalesce at some point"}),
-              flush=True)
-        return
-    if a.legs == "fec":
-        per = []
-        for S in (int(v) for v in a.streams.split(",")):
-            for kind in ("webcam", "local"):
-                per.append(run_fec(W, H, S, a.rounds, kind))
-                print(f"fec S={S} {kind}: done", file=sys.stderr, flush=True)
-                torch.cuda.empty_cache()
-        ok = all(p["fec_k2_no_slower_than_split"] for p in per)
-        print(json.dumps({"bench": "multi_fec", "size": f"{W}x{H}", "rounds": a.rounds, "fec": per,
-                          "verdict": "parity at K = 2 no slower than split at every point" if ok else "parity at K = 2 slower than split at some point"}),
-              flush=True)
-        return
-    if a.legs == "mosaic":
-        per = []
-        for S in (int(v) for v in a.streams.split(",")):
-            for T in (1, 16):
-                for kind in ("webcam", "local"):
-                    per.append(run_mosaic(W, H, S, T, a.rounds, kind))
-                    print(f"mosaic S={S} T={T} {kind}: done", file=sys.stderr, flush=True)
-                    torch.cuda.empty_cache()
-        print(json.dumps({"bench": "multi_mosaic", "size": f"{W}x{H}", "rounds": a.rounds, "mosaic": per}), flush=True)
-        return
-    if a.legs == "budget":
-        per = []
-        for S in (int(v) for v in a.streams.split(",")):
-            per.append(run_budget(W, H, S, a.rounds))
-            print(f"budget S={S}: done", file=sys.stderr, flush=True)
-            torch.cuda.empty_cache()
-        print(json.dumps({"bench": "multi_budget", "size": f"{W}x{H}", "input": "synth.webcam_stream", "rounds": a.rounds,
-                          "budget": per}), flush=True)
-        return
-    if a.legs == "activity":
-        points = [(S, 1) for S in (int(v) for v in a.streams.split(","))] + [(16, 16)]
-        per = []
-        for S, T in points:
-            for kind in ("webcam", "local"):
-                per.append(run_activity(W, H, S, T, a.rounds, kind))
-                print(f"activity S={S} T={T} {kind}: done", file=sys.stderr, flush=True)
-                torch.cuda.empty_cache()
-        print(json.dumps({"bench": "multi_activity", "size": f"{W}x{H}", "rounds": a.rounds, "activity": per,
-                          "verdict": "no slower than burst_apply at every point" if all(p["no_slower_than_burst_apply"] for p in per)
-                          else "slower than burst_apply at some point"}), flush=True)
-        return
-    if a.legs == "check":
-        points = [(S, 1) for S in (int(v) for v in a.streams.split(","))] + [(16, 16)]
-        per = []
-        for S, T in points:
-            for kind in ("webcam", "local"):
-                per.append(run_check(W, H, S, T, a.rounds, kind))
-                print(f"check S={S} T={T} {kind}: done", file=sys.stderr, flush=True)
-                torch.cuda.empty_cache()
-        print(json.dumps({"bench": "multi_check", "size": f"{W}x{H}", "rounds": a.rounds, "check": per,
-                          "verdict": "no slower than burst_apply at every point" if all(p["no_slower_than_burst_apply"] for p in per)
-                          else "slower than burst_apply at some point"}), flush=True)
-        return
-    if a.legs == "refresh":
-        per = []
-        for S in (int(v) for v in a.streams.split(",")):
-            per.append(run_refresh(W, H, S, a.rounds))
-            print(f"refresh S={S}: done", file=sys.stderr, flush=True)
-            torch.cuda.empty_cache()
-        print(json.dumps({"bench": "multi_refresh", "size": f"{W}x{H}", "rounds": a.rounds, "refresh": per,
-                          "verdict": "digest no slower than diff at every S" if all(p["digest_no_slower_than_diff"] for p in per)
-                          else "digest slower than diff at some S"}), flush=True)
-        return
-    if a.legs == "wall":
-        per = []
-        for S in (int(v) for v in a.streams.split(",")):
-            per.append(run_wall(W, H, S, a.rounds))
-            print(f"wall S={S}: done", file=sys.stderr, flush=True)
-            torch.cuda.empty_cache()
-        ok_mask, ok_full = all(p["masked_local_cheaper_than_full"] for p in per), all(p["full_k8_no_slower_than_digest"] for p in per)
-        print(json.dumps({"bench": "multi_wall", "size": f"{W}x{H}", "rounds": a.rounds, "wall": per,
-                          "verdict": ("masked update on the moving block cheaper than the full compose at every k and S"
-                                      if ok_mask else "masked update on the moving block not cheaper than the full compose at some k or S")
-                          + "; " + ("full compose at k = 8 no slower than digest at every S" if ok_full
-                                    else "full compose at k = 8 slower than digest at some S")}), flush=True)
-        return
-    if a.legs == "thumb":
-        per = []
-        for S in (int(v) for v in a.streams.split(",")):
-            per.append(run_thumb(W, H, S, a.rounds))
-            print(f"thumb S={S}: done", file=sys.stderr, flush=True)
-            torch.cuda.empty_cache()
-        ok_route, ok_mask = all(p["touched_plus_call_no_slower_than_route"] for p in per), all(p["call_local_cheaper_than_nullmask"] for p in per)
-        print(json.dumps({"bench": "multi_thumb", "size": f"{W}x{H}", "rounds": a.rounds, "thumb": per,
-                          "verdict": ("touched tiles plus the call no slower than the wall-and-diff route at every point"
-                                      if ok_route else "touched tiles plus the call slower than the wall-and-diff route at some point")
-                          + "; " + ("the call with the moving block's mask cheaper than without a mask at every k and S" if ok_mask
-                                    else "the call with the moving block's mask not cheaper than without a mask at some k or S")}), flush=True)
-        return
-    for S in (int(v) for v in a.streams.split(",")):
-        run(W, H, S, a.steps, a.rounds, set(a.legs.split(",")), have)
+    leg = LEGS[a.legs]
+    per = []
+    for point in leg["points"](a):
+        per.append(leg["run"](W, H, a.rounds, **point))
+        if not leg.get("quiet"):
+            where = " ".join(str(v) if k == "kind" else f"{k}={v}" for k, v in point.items())
+            print(f"{a.legs} {where}: done", file=sys.stderr, flush=True)
         torch.cuda.empty_cache()
+    line = {"bench": leg["bench"], "size": f"{W}x{H}"}
+    if leg.get("input"):
+        line["input"] = "synth.webcam_stream"
+    line["rounds"] = a.rounds
+    if leg.get("steps"):
+        line["steps"] = a.steps
+    line[a.legs] = per
+    if "verdict" in leg:
+        line["verdict"] = "; ".join(ok if all(v for p in per for k, v in p.items() if k.endswith(flag)) else bad
+                                    for flag, ok, bad in leg["verdict"])
+    print(json.dumps(line), flush=True)
 
 
 if __name__ == "__main__":
