@@ -555,6 +555,28 @@ class CUDACore:
                                                          int(nrecords), int(max_bytes), _ptr(d_piece_first), _ptr(d_piece_pos),
                                                          int(piece_capacity), _ptr(d_cwire_out), int(capacity_bytes)))
 
+    # ... and either end of a stream socket: records run-coded where that makes them smaller, and back
+    def cwire_runs_encode_batch(self, d_cwire, counts, escapes, nrecords, policy, d_forms, d_pos, d_out, capacity_bytes):
+        """Every compact record (headers counts / escapes, back to back) for the link: in the run form where `policy`
+        (lib.RUNS_WHERE_SMALLER, lib.RUNS_ALWAYS) says so, copied otherwise.  d_forms, uint32[nrecords][4] = {form
+        (lib.RUNS_FORM_*), n, e, r} per record: what the receiver hands to cwire_runs_decode_batch; record b at d_out + d_pos[b]
+        (uint64[nrecords + 1], always exact), written only if it fits.  cwire_runs_encode_host is the same on the host and the
+        definition; cwire_runs_bytes_max gives a sufficient capacity."""
+        self._hold(d_cwire, d_forms, d_pos, d_out)
+        counts, escapes = _headers(counts, escapes, nrecords)
+        _l.check(self._lib.mi355_cwire_runs_encode_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
+                                                         int(nrecords), int(policy), _ptr(d_forms), _ptr(d_pos), _ptr(d_out),
+                                                         int(capacity_bytes)))
+
+    def cwire_runs_decode_batch(self, d_in, forms, nrecords, d_frame_pos, d_cwire_out, capacity_bytes):
+        """What cwire_runs_encode_batch wrote, back into compact records: `forms` is the sender's table (host, uint32[nrecords][4]),
+        record b goes to d_cwire_out + d_frame_pos[b] (uint64[nrecords + 1], always exact), written only if it fits.
+        cwire_runs_decode_host is the same on the host and the definition."""
+        self._hold(d_in, d_frame_pos, d_cwire_out)
+        forms = _table(forms, 4, nrecords, np.uint32)
+        _l.check(self._lib.mi355_cwire_runs_decode_batch(self._h, _ptr(d_in), forms.ctypes.data, int(nrecords), _ptr(d_frame_pos),
+                                                         _ptr(d_cwire_out), int(capacity_bytes)))
+
     # ... with parity datagrams behind the pieces, so that a receiver rebuilds what the link lost
     def cwire_fec_batch(self, d_pieces, pieces_bytes, d_piece_first, d_piece_pos, piece_capacity, nrecords, group, nparity, pitch,
                         d_fec_first, d_fec_len, group_capacity, d_out, capacity_bytes):
@@ -923,6 +945,58 @@ def cwire_split_host(buf, counts, escapes, frame_bytes, max_bytes, piece_capacit
                                       counts.size, int(max_bytes), piece_first.ctypes.data, piece_pos.ctypes.data,
                                       int(piece_capacity), out.ctypes.data, int(capacity_bytes)))
     return piece_first, piece_pos, out[:int(capacity_bytes)]
+
+
+def cwire_runs_frame_bytes(n, e, r):
+    """Bytes of a record of n entries, e escapes and r runs in the run form."""
+    return _l.load().mi355_cwire_runs_frame_bytes(int(n), int(e), int(r))
+
+
+def cwire_runs_bytes_max(frame_bytes, nrecords, policy):
+    """A sufficient output size for cwire_runs_encode_* of nrecords records of frames of frame_bytes bytes under `policy` (0 for
+    an unknown policy)."""
+    return _l.load().mi355_cwire_runs_bytes_max(int(frame_bytes), int(nrecords), int(policy))
+
+
+def _as_bytes(buf):
+    return np.ascontiguousarray(np.frombuffer(buf, np.uint8) if isinstance(buf, (bytes, bytearray)) else buf, dtype=np.uint8)
+
+
+def cwire_runs_encode_host(buf, counts, escapes, frame_bytes, policy, capacity_bytes=None):
+    """cwire_runs_encode_batch computed on the host (no GPU, no core) and its definition: (forms uint32[nrecords, 4], pos
+    uint64[nrecords + 1], out uint8[capacity_bytes]) for the records of `buf` that the headers counts / escapes describe.  The
+    capacity defaults to cwire_runs_bytes_max."""
+    L = _l.load()
+    buf = _as_bytes(buf)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+    assert counts.size == escapes.size
+    if capacity_bytes is None:
+        capacity_bytes = L.mi355_cwire_runs_bytes_max(int(frame_bytes), counts.size, int(policy))
+    forms = np.zeros((counts.size, 4), np.uint32)
+    pos = np.zeros(counts.size + 1, np.uint64)
+    out = np.zeros(max(int(capacity_bytes), 1), np.uint8)
+    _l.check(L.mi355_cwire_runs_encode_host(int(frame_bytes), buf.ctypes.data, buf.size, counts.ctypes.data, escapes.ctypes.data,
+                                            counts.size, int(policy), forms.ctypes.data, pos.ctypes.data, out.ctypes.data,
+                                            int(capacity_bytes)))
+    return forms, pos, out[:int(capacity_bytes)]
+
+
+def cwire_runs_decode_host(buf, forms, frame_bytes, capacity_bytes=None, out=None):
+    """cwire_runs_decode_batch computed on the host and its definition: (frame_pos uint64[nrecords + 1], cwire uint8[capacity_bytes])
+    from the link bytes `buf` and the sender's table `forms`.  The capacity defaults to the records' size.  `out`: an array to
+    decode into (what a refused call had written before it stopped stays there)."""
+    L = _l.load()
+    buf = _as_bytes(buf)
+    forms = np.ascontiguousarray(forms, dtype=np.uint32).reshape(-1, 4)
+    if capacity_bytes is None:
+        capacity_bytes = sum(L.mi355_cwire_frame_bytes(int(f[1]), int(f[2])) for f in forms) if out is None else out.size
+    frame_pos = np.zeros(forms.shape[0] + 1, np.uint64)
+    if out is None:
+        out = np.zeros(max(int(capacity_bytes), 1), np.uint8)
+    _l.check(L.mi355_cwire_runs_decode_host(int(frame_bytes), buf.ctypes.data, buf.size, forms.ctypes.data, forms.shape[0],
+                                            frame_pos.ctypes.data, out.ctypes.data, int(capacity_bytes)))
+    return frame_pos, out[:int(capacity_bytes)]
 
 
 def cwire_fec_groups_max(piece_capacity, nrecords, group):

@@ -17,6 +17,7 @@
 //   cw_items  T*ceil(W/16)*16 + T*4  mi355_diff_stream_cwire_batch: one word per item of the expansion, escapes per frame
 //   cwa_*     T*24 + 2*T*ceil(N/4096)*16  mi355_apply_cwire_batch: frame table, chunk facts, tile directory
 //   cws_*     2*T*max(1, ceil(N/65536))*16  mi355_cwire_split_cwire_batch: per block of 65536 entries its pieces and bytes, their bases
+//   cwr_*     T*40 + T*max(1, ceil(N/1024))*8  mi355_cwire_runs_decode_batch: record table, one word per workgroup of 1024 runs
 //   hist T*256*4, thr T*4 (per frame of a filter batch), k9 9*4, heat LUT 766*3, glyph atlas
 #include <cmath>
 #include <cstdio>
@@ -95,6 +96,8 @@ struct mi355_core {
     uint4 *cwa_dir = nullptr;       // [T][cwa_tiles(N)] directory words
     uint4 *cws_blk = nullptr;       // mi355_cwire_split_cwire_batch (stream_ops.hip): [T * cws_blocks(N)] block words
     ulonglong2 *cws_base = nullptr; // ... and the pieces and bytes before each block
+    CwrRecord *cwr_rtab = nullptr;  // mi355_cwire_runs_decode_batch (stream_ops.hip): [T] records of a call,
+    uint2 *cwr_chunk = nullptr;     // [T * cwr_chunks_max(N)] one word per workgroup
     uint32_t *cwb_hist = nullptr;   // mi355_cwire_budget_cwire_batch: [T][kCwbWords] bins of |cur - prev|, budget and threshold per stream
     uint8_t *gray1 = nullptr;      // fused gray+binarize chain: one gray byte per pixel of a batch, made on first use
     size_t gray1_stride = 0;
@@ -664,6 +667,8 @@ int mi355_create(const mi355_config *cfg, mi355_core **out) {
     if (!rc) rc = dev_alloc(c, &c->cwb_hist, T * kCwbWords);
     if (!rc) rc = dev_alloc(c, &c->cws_blk, T * cws_blocks(c->n));
     if (!rc) rc = dev_alloc(c, &c->cws_base, T * cws_blocks(c->n));
+    if (!rc) rc = dev_alloc(c, &c->cwr_rtab, T);
+    if (!rc) rc = dev_alloc(c, &c->cwr_chunk, T * cwr_chunks_max(c->n));
     if (!rc) rc = dev_alloc(c, &c->one_xs, N + 4);
     if (!rc) rc = dev_alloc(c, &c->one_diff, N + 16);
     if (!rc) rc = dev_alloc(c, &c->hist, 256 * T);
@@ -710,7 +715,7 @@ void mi355_destroy(mi355_core *c) {
     }
     void *ptrs[] = {c->state, c->in, c->aux, c->vis, c->rec, c->codes, c->meta, c->groff, c->totals, c->offsets, c->one_xs, c->one_diff, c->hist, c->thr, c->k9,
                     c->lut, c->glyphs, c->kxk, c->gray1, c->red_bounds, c->cw_cnt, c->cw_items, c->cw_esc,
-                    c->cwa_ftab, c->cwa_chunk, c->cwa_dir, c->cwb_hist, c->cws_blk, c->cws_base, c->cw_rec, c->cw_rec_pos};
+                    c->cwa_ftab, c->cwa_chunk, c->cwa_dir, c->cwb_hist, c->cws_blk, c->cws_base, c->cwr_rtab, c->cwr_chunk, c->cw_rec, c->cw_rec_pos};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->h_count) (void)hipHostFree(c->h_count);
     if (c->h_rec) (void)hipHostFree(c->h_rec);
@@ -1970,6 +1975,217 @@ int mi355_cwire_split_cwire_batch(mi355_core *c, const void *d_cwire, const uint
     const CwsOut o{(uint32_t *)d_piece_first, (uint64_t *)d_piece_pos, (uint64_t)piece_capacity, (uint8_t *)d_cwire_out,
                    (uint64_t)capacity_bytes};
     HIP_TRY(launch_cwire_split(a, tab.fr.data(), nrecords, (uint32_t)max_bytes, c->cws_blk, c->cws_base, o, c->stream));
+    return MI355_OK;
+}
+
+// ---- mi355_cwire_runs_*: run-coded records for the link (include/mi355diff.h, "Run-coded records") ---------------------------------
+size_t mi355_cwire_runs_frame_bytes(uint32_t n, uint32_t e, uint32_t r) { return (size_t)cwire_runs_bytes(n, e, r); }
+
+size_t mi355_cwire_runs_bytes_max(size_t frame_bytes, int nrecords, int policy) {
+    if (nrecords <= 0) return 0;
+    if (policy == MI355_RUNS_WHERE_SMALLER) return mi355_cwire_bytes_max(frame_bytes, nrecords);
+    if (policy == MI355_RUNS_ALWAYS) return (size_t)nrecords * (size_t)(12 + 3 * cwire_pad4(frame_bytes));
+    return 0;
+}
+
+static int runs_check_policy(int policy) {
+    if (policy != MI355_RUNS_WHERE_SMALLER && policy != MI355_RUNS_ALWAYS) return fail(MI355_ERR_INVALID, "unknown policy");
+    return MI355_OK;
+}
+
+// The definition of the encoder: a walk over the codes, run by run.
+int mi355_cwire_runs_encode_host(size_t frame_bytes, const void *cwire, size_t cwire_bytes, const uint32_t *h_counts,
+                                 const uint32_t *h_escapes, int nrecords, int policy, uint32_t *forms, uint64_t *pos, void *out,
+                                 size_t capacity_bytes) {
+    if (nrecords < 0) return fail(MI355_ERR_INVALID, "nrecords < 0");
+    if (frame_bytes >= 0xFFFFFFFFull) return fail(MI355_ERR_INVALID, "frame_bytes must be below 2^32 - 1");
+    if (int rc = runs_check_policy(policy)) return rc;
+    if (nrecords == 0) {
+        if (pos) pos[0] = 0;
+        return MI355_OK;
+    }
+    if (!cwire || !h_counts || !h_escapes) return fail(MI355_ERR_INVALID, "null stream pointer");
+    if (!forms || !pos || !out) return fail(MI355_ERR_INVALID, "null output pointer");
+    uint64_t span = 0;
+    for (int b = 0; b < nrecords; b++) {
+        if (h_escapes[b] > h_counts[b]) return fail(MI355_ERR_INVALID, "frame header: more escapes than entries");
+        if (h_counts[b] > frame_bytes) return fail(MI355_ERR_INVALID, "frame header: more entries than frame bytes");
+        span += cwire_record_bytes(h_counts[b], h_escapes[b]);
+        if (span > cwire_bytes) return fail(MI355_ERR_INVALID, "the records end past cwire_bytes");
+    }
+    if (int rc = check_regions({input_region(cwire, span)},
+                               {Region{forms, 16 * (uint64_t)nrecords, "forms"}, Region{pos, 8 * ((uint64_t)nrecords + 1), "pos"},
+                                Region{out, capacity_bytes, "out"}}))
+        return rc;
+    const uint8_t *p = (const uint8_t *)cwire;
+    uint8_t *dst = (uint8_t *)out;
+    std::vector<uint8_t> gap, len;
+    uint64_t in_pos = 0, at = 0;
+    for (int b = 0; b < nrecords; b++) {
+        const uint32_t n = h_counts[b], e = h_escapes[b];
+        const CwireSections<const uint8_t> sec(p, in_pos, n, e);
+        gap.clear();
+        len.clear();
+        for (uint32_t k = 0; k < n; k++) {
+            if (cwire_run_start(k, sec.code[k])) {
+                gap.push_back(sec.code[k]);
+                len.push_back(0);
+            } else {
+                len.back()++;
+            }
+        }
+        const uint32_t r = (uint32_t)gap.size();
+        const uint32_t form = policy == MI355_RUNS_ALWAYS || cwire_runs_smaller(n, r) ? MI355_RUNS_FORM_RUNS : MI355_RUNS_FORM_COMPACT;
+        const uint64_t bytes = cwire_link_bytes(form, n, e, r);
+        const uint32_t row[4] = {form, n, e, r};
+        memcpy(forms + 4 * (size_t)b, row, sizeof row);
+        pos[b] = at;
+        if (at + bytes <= capacity_bytes) {   // (a record that does not fit is skipped whole)
+            uint8_t *q = dst + at;
+            if (form == MI355_RUNS_FORM_COMPACT) {
+                memcpy(q, p + in_pos, bytes);
+                memcpy(q, row + 1, 8);
+            } else {
+                memset(q, 0, bytes);
+                memcpy(q, row + 1, 12);
+                uint8_t *og = q + 12, *ol = og + cwire_pad4(r), *oe = ol + cwire_pad4(r), *od = oe + 4 * (size_t)e;
+                if (r) {
+                    memcpy(og, gap.data(), r);
+                    memcpy(ol, len.data(), r);
+                }
+                memcpy(oe, sec.esc, 4 * (size_t)e);
+                memcpy(od, sec.diff, n);
+            }
+        }
+        at += bytes;
+        in_pos += cwire_record_bytes(n, e);
+    }
+    pos[nrecords] = at;
+    return MI355_OK;
+}
+
+int mi355_cwire_runs_encode_batch(mi355_core *c, const void *d_cwire_in, const uint32_t *h_counts, const uint32_t *h_escapes, int nrecords,
+                                  int policy, void *d_forms, void *d_pos, void *d_out, size_t capacity_bytes) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nrecords < 0 || nrecords > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nrecords outside [0, max_batch]");
+    if (int rc = runs_check_policy(policy)) return rc;
+    if (((uintptr_t)d_cwire_in | (uintptr_t)d_out | (uintptr_t)d_forms) & 3u)
+        return fail(MI355_ERR_INVALID, "d_cwire_in, d_out and d_forms must be 4-byte aligned");
+    if ((uintptr_t)d_pos & 7u) return fail(MI355_ERR_INVALID, "d_pos must be 8-byte aligned");
+    if (nrecords == 0) return write_empty_heads(c, nullptr, d_pos);
+    if (!d_cwire_in || !h_counts || !h_escapes) return fail(MI355_ERR_INVALID, "null stream pointer");
+    if (!d_forms || !d_pos || !d_out) return fail(MI355_ERR_INVALID, "null output pointer");
+    CwaTable tab;
+    if (int rc = cwa_table(c, h_counts, h_escapes, nrecords, &tab)) return rc;
+    if (int rc = check_regions({input_region(d_cwire_in, tab.bytes)},
+                               {Region{d_forms, 16 * (uint64_t)nrecords, "d_forms"}, Region{d_pos, 8 * ((uint64_t)nrecords + 1), "d_pos"},
+                                Region{d_out, capacity_bytes, "d_out"}}))
+        return rc;
+    if (int rc = use_device(c)) return rc;
+    const CwaArgs a = cwa_args(c, d_cwire_in);
+    const CwrOut o{(uint32_t *)d_forms, (uint64_t *)d_pos, (uint8_t *)d_out, (uint64_t)capacity_bytes};
+    HIP_TRY(launch_cwire_runs_encode(a, tab.fr.data(), nrecords, policy, o, c->stream));
+    return MI355_OK;
+}
+
+// What both decoders refuse in a row of the forms table
+static int runs_check_row(const uint32_t *row, uint64_t frame_bytes) {
+    if (row[0] != MI355_RUNS_FORM_COMPACT && row[0] != MI355_RUNS_FORM_RUNS) return fail(MI355_ERR_INVALID, "forms: a form other than 0 or 1");
+    if (row[1] > frame_bytes) return fail(MI355_ERR_INVALID, "forms: more entries than frame bytes");
+    if (row[2] > row[1]) return fail(MI355_ERR_INVALID, "forms: more escapes than entries");
+    if (row[3] > row[1]) return fail(MI355_ERR_INVALID, "forms: more runs than entries");
+    return MI355_OK;
+}
+
+// The definition of the decoder.  Records before a refused one stay written, with their frame_pos.
+int mi355_cwire_runs_decode_host(size_t frame_bytes, const void *in, size_t in_bytes, const uint32_t *h_forms, int nrecords,
+                                 uint64_t *frame_pos, void *cwire_out, size_t capacity_bytes) {
+    if (nrecords < 0) return fail(MI355_ERR_INVALID, "nrecords < 0");
+    if (frame_bytes >= 0xFFFFFFFFull) return fail(MI355_ERR_INVALID, "frame_bytes must be below 2^32 - 1");
+    if (nrecords == 0) {
+        if (frame_pos) frame_pos[0] = 0;
+        return MI355_OK;
+    }
+    if (!in || !h_forms) return fail(MI355_ERR_INVALID, "null stream pointer");
+    if (!frame_pos || !cwire_out) return fail(MI355_ERR_INVALID, "null output pointer");
+    if (int rc = check_regions({input_region(in, in_bytes), Region{h_forms, 16 * (uint64_t)nrecords, "h_forms"}},
+                               {Region{frame_pos, 8 * ((uint64_t)nrecords + 1), "frame_pos"}, Region{cwire_out, capacity_bytes, "cwire_out"}}))
+        return rc;
+    const uint8_t *p = (const uint8_t *)in;
+    uint8_t *dst = (uint8_t *)cwire_out;
+    uint64_t in_pos = 0, at = 0;
+    frame_pos[0] = 0;
+    for (int b = 0; b < nrecords; b++) {
+        const uint32_t *row = h_forms + 4 * (size_t)b;
+        if (int rc = runs_check_row(row, frame_bytes)) return rc;
+        const uint32_t form = row[0], n = row[1], e = row[2], r = row[3];
+        const uint64_t in_rec = cwire_link_bytes(form, n, e, r), bytes = cwire_record_bytes(n, e);
+        if (in_pos + in_rec > in_bytes) return fail(MI355_ERR_INVALID, "the records end past in_bytes (truncated input)");
+        const uint8_t *q = p + in_pos;
+        const uint8_t *ig = q + 12, *il = ig + cwire_pad4(r), *ie = il + cwire_pad4(r), *id = ie + 4 * (size_t)e;
+        if (form == MI355_RUNS_FORM_RUNS) {
+            uint64_t k = 0, n255 = 0;
+            for (uint32_t i = 0; i < r; i++) {
+                const uint32_t L = il[i] + 1u;
+                if ((k & 255u) + L > 256u) return fail(MI355_ERR_INVALID, "a run crosses a multiple of 256 entries");
+                k += L;
+                n255 += ig[i] == 255;
+            }
+            if (k != n) return fail(MI355_ERR_INVALID, "the run lengths do not sum to n");
+            if (n255 != e) return fail(MI355_ERR_INVALID, "the 255 gaps are not e");
+        }
+        if (at + bytes <= capacity_bytes) {   // (a record that does not fit is skipped whole)
+            uint8_t *o = dst + at;
+            if (form == MI355_RUNS_FORM_COMPACT) {
+                memcpy(o, q, bytes);
+                memcpy(o, row + 1, 8);
+            } else {
+                memset(o, 0, bytes);
+                memcpy(o, row + 1, 8);
+                const CwireSections<uint8_t> sec(dst, at, n, e);
+                uint64_t k = 0;
+                for (uint32_t i = 0; i < r; i++) {
+                    sec.code[k] = ig[i];
+                    k += il[i] + 1u;
+                }
+                memcpy(sec.esc, ie, 4 * (size_t)e);
+                memcpy(sec.diff, id, n);
+            }
+        }
+        at += bytes;
+        in_pos += in_rec;
+        frame_pos[b + 1] = at;
+    }
+    return MI355_OK;
+}
+
+int mi355_cwire_runs_decode_batch(mi355_core *c, const void *d_in, const uint32_t *h_forms, int nrecords, void *d_frame_pos,
+                                  void *d_cwire_out, size_t capacity_bytes) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nrecords < 0 || nrecords > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nrecords outside [0, max_batch]");
+    if (((uintptr_t)d_in | (uintptr_t)d_cwire_out) & 3u) return fail(MI355_ERR_INVALID, "d_in and d_cwire_out must be 4-byte aligned");
+    if ((uintptr_t)d_frame_pos & 7u) return fail(MI355_ERR_INVALID, "d_frame_pos must be 8-byte aligned");
+    if (nrecords == 0) return write_empty_heads(c, nullptr, d_frame_pos);
+    if (!d_in || !h_forms) return fail(MI355_ERR_INVALID, "null stream pointer");
+    if (!d_frame_pos || !d_cwire_out) return fail(MI355_ERR_INVALID, "null output pointer");
+    std::vector<CwrRecord> recs((size_t)nrecords);
+    uint64_t in_pos = 0, at = 0;
+    uint32_t cbase = 0;
+    for (int b = 0; b < nrecords; b++) {
+        const uint32_t *row = h_forms + 4 * (size_t)b;
+        if (int rc = runs_check_row(row, c->n)) return rc;
+        recs[b] = CwrRecord{in_pos, at, row[0], row[1], row[2], row[3], cbase, cwr_chunks(row[0], row[1], row[3])};
+        cbase += recs[b].nc;
+        in_pos += cwire_link_bytes(row[0], row[1], row[2], row[3]);
+        at += cwire_record_bytes(row[1], row[2]);
+    }
+    if (int rc = check_regions({input_region(d_in, in_pos)},
+                               {frame_pos_region(d_frame_pos, nrecords), Region{d_cwire_out, capacity_bytes, "d_cwire_out"}}))
+        return rc;
+    if (int rc = use_device(c)) return rc;
+    const CwrDecode d{(const uint8_t *)d_in, c->cwr_rtab, c->cwr_chunk, (uint64_t *)d_frame_pos, (uint8_t *)d_cwire_out,
+                      (uint64_t)capacity_bytes};
+    HIP_TRY(launch_cwire_runs_decode(d, recs.data(), nrecords, at, c->stream));
     return MI355_OK;
 }
 

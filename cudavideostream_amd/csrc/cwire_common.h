@@ -21,6 +21,23 @@ __host__ __device__ inline uint32_t cwire_record_escapes(uint64_t bytes, uint32_
     return (uint32_t)((bytes - 8 - 2 * cwire_pad4(n)) / 4);
 }
 
+// The run form of a record for the link (include/mi355diff.h, "Run-coded records"):
+//   u32 n | u32 e | u32 r | u8 gap[pad4(r)] | u8 len[pad4(r)] | u32 esc[e] | u8 diff[pad4(n)]
+// Entry k starts a run when k % 256 == 0 or code[k] != 0; gap = the start's code, len = the run's entries - 1.
+__host__ __device__ inline uint64_t cwire_runs_bytes(uint64_t n, uint64_t e, uint64_t r) { return 12 + 2 * cwire_pad4(r) + 4 * e + cwire_pad4(n); }
+__host__ __device__ inline bool cwire_run_start(uint32_t k, uint32_t code) { return (k & 255u) == 0 || code != 0; }
+// the run form is strictly smaller than the compact record
+__host__ __device__ inline bool cwire_runs_smaller(uint64_t n, uint64_t r) { return 4 + 2 * cwire_pad4(r) < cwire_pad4(n); }
+// the bytes of record {n, e, r} on the link in either form (form != 0: the run form)
+__host__ __device__ inline uint64_t cwire_link_bytes(uint32_t form, uint64_t n, uint64_t e, uint64_t r) {
+    return form ? cwire_runs_bytes(n, e, r) : cwire_record_bytes(n, e);
+}
+// the dwords [lo, hi) of a section of `total` dwords that part j of nparts copies
+__host__ __device__ inline void cwire_share(uint32_t total, uint32_t j, uint32_t nparts, uint32_t &lo, uint32_t &hi) {
+    lo = (uint32_t)((uint64_t)total * j / nparts);
+    hi = (uint32_t)((uint64_t)total * (j + 1) / nparts);
+}
+
 // Where the sections of the record {n, e} at base + pos are.  Byte = uint8_t or const uint8_t.
 template <class Byte>
 struct CwireSections {

@@ -335,6 +335,41 @@ uint32_t cws_blocks(uint32_t n);   // blocks of a record of n entries (1 for n =
 // a.ftab and a.chunk are the scratch it shares with the other calls; a.dir / a.state / a.out / a.stride / a.ntiles unused
 hipError_t launch_cwire_split(const CwaArgs &a, const CwaFrame *records, int nrecords, uint32_t max_bytes, uint4 *blk, ulonglong2 *base,
                               const CwsOut &o, hipStream_t s);
+// mi355_cwire_runs_encode_batch: every record into the run form or copied, as the policy says (include/mi355diff.h, "Run-coded
+// records").  a.ftab and a.chunk are the scratch it shares with the other calls (chunk = {runs, first run rank, 0, record});
+// forms / pos / out: the caller's.  a.dir / a.state / a.out / a.stride / a.ntiles unused.
+struct CwrOut {
+    uint32_t *forms;     // [nrecords][4] {form, n, e, r}
+    uint64_t *pos;       // [nrecords + 1]
+    uint8_t *out;
+    uint64_t capacity;   // bytes of out
+};
+hipError_t launch_cwire_runs_encode(const CwaArgs &a, const CwaFrame *records, int nrecords, int policy, const CwrOut &o, hipStream_t s);
+// mi355_cwire_runs_decode_batch: the records' places and headers are the host's (h_forms) and travel as kernel arguments,
+// kCwrTableRecords per launch.  A record in the run form is kCwrRuns runs per workgroup, one in the compact form kCwaChunk entries.
+constexpr uint32_t kCwrRuns = 1024;
+constexpr int kCwrTableRecords = 64;
+struct CwrRecord {
+    uint64_t in_pos, out_pos;   // byte positions on the link and in the compact stream
+    uint32_t form, n, e, r;
+    uint32_t cbase, nc;         // its workgroups: [cbase, cbase + nc) of the call, nc = cwr_chunks(form, n, r)
+};
+struct CwrTableArgs {
+    int32_t first, last;        // the launch's first record; last != 0: the launch holds the call's last record
+    uint64_t total;             // frame_pos[nrecords]
+    CwrRecord rec[kCwrTableRecords];
+};
+struct CwrDecode {
+    const uint8_t *in;
+    CwrRecord *rtab;       // [T] scratch of the core
+    uint2 *chunk;          // [T * cwr_chunks_max(N)] scratch: {record, entries of the record before the workgroup's runs}
+    uint64_t *frame_pos;   // [nrecords + 1], the caller's
+    uint8_t *out;
+    uint64_t capacity;     // bytes of out
+};
+uint32_t cwr_chunks(uint32_t form, uint32_t n, uint32_t r);   // workgroups of a record (never 0)
+uint32_t cwr_chunks_max(uint32_t nbytes);                     // ... of any record of a frame of nbytes bytes
+hipError_t launch_cwire_runs_decode(const CwrDecode &d, const CwrRecord *records, int nrecords, uint64_t total, hipStream_t s);
 // mi355_cwire_fec_batch: parity blocks over groups of the pieces the split call wrote (include/mi355diff.h, "Parity pieces").
 // Everything the kernels read lies on the device; waves: how many waves the parity kernel's grid holds (sized from the device).
 struct FecArgs {

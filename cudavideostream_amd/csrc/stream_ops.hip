@@ -2819,6 +2819,300 @@ __global__ __launch_bounds__(256) void k_fec_repair(const uint8_t *rx, const Fec
     }
 }
 
+// ---- mi355_cwire_runs_encode_batch, mi355_cwire_runs_decode_batch: run-coded records for the link (include/mi355diff.h) -----------
+// Encode, over the chunk table of the directory (k_cwa_table; a chunk is kCwaChunk codes of one record, and a multiple of 256
+// entries, so every chunk boundary is a cut and a chunk's runs depend on the chunk alone):
+//   k_cwr_count (grid: chunks)   : the chunk's run starts (k % 256 == 0 or a non-zero code), four entries per lane from one code
+//                                  dword, ballot and popcount -> chunk.x
+//   k_cwr_scan  (grid: records)  : exclusive scan over the record's chunks -> chunk.y, the first run rank; r, the size decision
+//                                  and the form row
+//   k_cwr_place (one workgroup)  : pos = the exclusive scan of the records' link bytes, in 64 bits
+//   k_cwr_emit  (grid: chunks)   : the starts' codes and places compacted in LDS by rank, then gap[] and len[] (the distance to the
+//                                  next start of the chunk) stored: whole dwords inside the chunk's runs, single bytes at its
+//                                  ragged ends, the pads by the record's last chunk; esc and diff copied as dwords, each chunk its
+//                                  share.  A record kept compact is copied, dword for dword.
+// Decode, over workgroups of kCwrRuns runs (run form) or kCwaChunk entries (compact form, a copy):
+//   k_cwr_table (grid: records)  : the host's places and headers -> rtab, frame_pos, workgroup -> record
+//   k_cwr_sums  (grid: workgroups): sum of len + 1 over its runs -> chunk.y
+//   k_cwr_dscan (grid: records)  : exclusive scan over the record's workgroups -> chunk.y, the entry its first run starts at
+//   k_cwr_expand(grid: workgroups): scans its runs, then builds the code bytes of the entries they cover 4096 at a time in LDS --
+//                                  zeros, the gaps at the run starts -- and stores them: whole dwords inside, single bytes at
+//                                  the ragged ends; everything clamped to n, the record's last workgroup writes the pad.
+// No workgroup waits on another and no two write the same byte; dwords that two workgroups share are written as bytes.
+// Reads stay inside the spans the headers give, writes inside [pos[b], pos[b + 1]) of a record that fits.
+__global__ __launch_bounds__(256) void k_cwr_count(const CwaArgs a) {
+    __shared__ uint32_t s_cnt[4];
+    const uint32_t c = blockIdx.x;
+    const CwaFrame f = a.ftab[a.chunk[c].w];
+    const uint32_t k0 = (c - f.cbase) * kCwaChunk;
+    const uint32_t k1 = f.n - k0 < kCwaChunk ? f.n : k0 + kCwaChunk;
+    const uint32_t *code = cwa_sections(a, f).code32();
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int i = 0; i < (int)(kCwaChunk / 1024); i++) {
+        const uint32_t d = k0 / 4 + threadIdx.x + 256 * i;
+        const uint32_t w = 4 * d < k1 ? code[d] : 0u;
+        bool fl[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) fl[j] = 4 * d + j < k1 && cwire_run_start(4 * d + j, (w >> (8 * j)) & 255u);
+        uint32_t wtot;
+        (void)cwire_rank4(fl, wtot);
+        cnt += wtot;   // (the wave's, in every lane)
+    }
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) a.chunk[c].x = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+__global__ __launch_bounds__(256) void k_cwr_scan(const CwaArgs a, int policy, uint32_t *forms) {
+    __shared__ uint32_t s_wave[2][4];
+    const CwaFrame f = a.ftab[blockIdx.x];
+    uint32_t carry = 0;
+    int buf = 0;
+    for (uint32_t i0 = 0; i0 < f.nc; i0 += 256, buf ^= 1) {
+        const uint32_t i = i0 + threadIdx.x;
+        uint4 *ch = a.chunk + f.cbase + i;
+        const uint32_t before = block_exclusive_scan<4>(i < f.nc ? ch->x : 0u, s_wave[buf], carry);
+        if (i < f.nc) ch->y = before;
+    }
+    if (threadIdx.x == 0) {
+        uint32_t *row = forms + 4 * (size_t)blockIdx.x;
+        row[0] = policy == 1 || cwire_runs_smaller(f.n, carry) ? 1u : 0u;
+        row[1] = f.n;
+        row[2] = f.e;
+        row[3] = carry;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_cwr_place(const uint32_t *forms, int nrecords, uint64_t *pos) {
+    __shared__ uint64_t s_wave[2][4];
+    uint64_t carry = 0;
+    int buf = 0;
+    for (int b0 = 0; b0 < nrecords; b0 += 256, buf ^= 1) {
+        const int b = b0 + (int)threadIdx.x;
+        const uint32_t *row = forms + 4 * (size_t)b;
+        const uint64_t bytes = b < nrecords ? cwire_link_bytes(row[0], row[1], row[2], row[3]) : 0;
+        const uint64_t before = block_exclusive_scan<4>(bytes, s_wave[buf], carry);
+        if (b < nrecords) pos[b] = before;
+    }
+    if (threadIdx.x == 0) pos[nrecords] = carry;
+}
+
+// dwords [lo, hi) of src to dst, by the workgroup's 256 threads
+__device__ __forceinline__ void cwr_copy(const uint32_t *src, uint32_t *dst, uint32_t lo, uint32_t hi) {
+    for (uint32_t i = lo + threadIdx.x; i < hi; i += 256) __builtin_nontemporal_store(src[i], dst + i);
+}
+// ... of a diff section of n bytes: the pad bytes of its last dword leave as zeros
+__device__ __forceinline__ void cwr_copy_diff(const uint32_t *src, uint32_t *dst, uint32_t lo, uint32_t hi, uint32_t n) {
+    const uint32_t last = (n & 3u) ? 0xFFFFFFFFu >> (32u - 8u * (n & 3u)) : 0xFFFFFFFFu;
+    for (uint32_t i = lo + threadIdx.x; i < hi; i += 256) __builtin_nontemporal_store(i + 1 == cwire_dwords(n) ? src[i] & last : src[i], dst + i);
+}
+
+// Bytes [lo, hi) of the byte array at dst (4-aligned) from the LDS bytes src[i - base], base a multiple of 4 relative to dst and
+// base <= lo: the dwords that lie inside [lo, hi) whole, the bytes of the others one by one.  Dwords [q0, q1) are looked at.
+__device__ __forceinline__ void cwr_store_bytes(uint8_t *dst, const uint8_t *src, uint64_t base, uint64_t lo, uint64_t hi, uint64_t q0, uint64_t q1) {
+    for (uint64_t q = q0 + threadIdx.x; q < q1; q += 256) {
+        const uint64_t g = 4 * q;
+        if (g >= lo && g + 4 <= hi) {
+            __builtin_nontemporal_store(*(const uint32_t *)(src + (g - base)), (uint32_t *)(dst + g));
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (g + j >= lo && g + j < hi) dst[g + j] = src[g + j - base];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_cwr_emit(const CwaArgs a, const CwrOut o) {
+    __shared__ uint32_t s_wave[2][4];
+    __shared__ uint16_t s_at[kCwaChunk + 4];
+    __shared__ __attribute__((aligned(4))) uint8_t s_gap[kCwaChunk + 4], s_len[kCwaChunk + 4];
+    const uint32_t c = blockIdx.x, tid = threadIdx.x;
+    const uint4 ch = a.chunk[c];
+    const uint32_t b = ch.w;
+    const CwaFrame f = a.ftab[b];
+    const uint32_t j = c - f.cbase;
+    const uint32_t form = o.forms[4 * (size_t)b], r = o.forms[4 * (size_t)b + 3];
+    const uint64_t pos = o.pos[b];
+    if (o.pos[b + 1] > o.capacity) return;   // a record that does not fit is skipped whole
+    const CwireSections<const uint8_t> sec = cwa_sections(a, f);
+    const uint32_t k0 = j * kCwaChunk;
+    const uint32_t k1 = f.n - k0 < kCwaChunk ? f.n : k0 + kCwaChunk;
+    const uint32_t d0 = k0 / 4, nd = k0 < k1 ? cwire_dwords(k1 - k0) : 0u;   // the chunk's code and diff dwords: d0 + [0, nd)
+    uint32_t e0, e1;
+    cwire_share(f.e, j, f.nc, e0, e1);
+    uint32_t *out = (uint32_t *)(o.out + pos);
+    if (j == 0 && tid == 0) {
+        __builtin_nontemporal_store(f.n, out);
+        __builtin_nontemporal_store(f.e, out + 1);
+        if (form) __builtin_nontemporal_store(r, out + 2);
+    }
+    if (!form) {   // the compact record, dword for dword
+        const CwireSections<uint8_t> dst(o.out, pos, f.n, f.e);
+        cwr_copy(sec.code32(), dst.code32(), d0, d0 + nd);
+        cwr_copy(sec.esc32(), dst.esc32(), e0, e1);
+        cwr_copy(sec.diff32(), dst.diff32(), d0, d0 + nd);
+        return;
+    }
+    uint8_t *og = o.out + pos + 12, *ol = og + cwire_pad4(r);
+    uint32_t *oe = (uint32_t *)(ol + cwire_pad4(r)), *od = oe + f.e;
+    cwr_copy(sec.esc32(), oe, e0, e1);
+    cwr_copy_diff(sec.diff32(), od, d0, d0 + nd, f.n);
+    // Runs [lo, hi) of the record are the chunk's.  Its starts by rank: where (s_at) and their codes (s_gap); the LDS bytes of run
+    // lo + i lie at sh + i, 4-aligned with gap[] and len[] of the record.
+    const uint64_t lo = ch.y < r ? ch.y : r, base = lo & ~3ull;
+    const uint32_t sh = (uint32_t)(lo - base);
+    const uint32_t *code = sec.code32();
+    uint32_t carry = 0;
+#pragma unroll
+    for (int i = 0; i < (int)(kCwaChunk / 1024); i++) {
+        const uint32_t dl = tid + 256 * i;
+        const uint32_t w = dl < nd ? code[d0 + dl] : 0u;
+        bool fl[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) fl[q] = k0 + 4 * dl + q < k1 && cwire_run_start(4 * dl + q, (w >> (8 * q)) & 255u);
+        uint32_t wtot;
+        const uint32_t before = cwire_rank4(fl, wtot);
+        uint32_t rank = block_waves_before<4>(wtot, 0, s_wave[i & 1], carry) + before;
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            if (fl[q]) {
+                s_at[rank] = (uint16_t)(4 * dl + q);   // (rank < kCwaChunk: a start per entry at the most)
+                s_gap[sh + rank] = (uint8_t)(w >> (8 * q));
+                rank++;
+            }
+    }
+    const uint32_t x = carry < ch.x ? carry : ch.x;   // (they differ only when the input changed between the launches)
+    if (tid == 0) s_at[carry] = (uint16_t)(k1 - k0);
+    __syncthreads();
+    for (uint32_t i = tid; i < x; i += 256) s_len[sh + i] = (uint8_t)(s_at[i + 1] - s_at[i] - 1u);
+    __syncthreads();
+    const uint64_t hi = r - lo < x ? r : lo + x;
+    cwr_store_bytes(og, s_gap, base, lo, hi, base / 4, (hi + 3) / 4);
+    cwr_store_bytes(ol, s_len, base, lo, hi, base / 4, (hi + 3) / 4);
+    if (j + 1 == f.nc && tid == 0)
+        for (uint64_t k = r; k < cwire_pad4(r); k++) og[k] = ol[k] = 0;
+}
+
+__global__ __launch_bounds__(256) void k_cwr_table(const CwrDecode d, const CwrTableArgs h) {
+    const CwrRecord rec = h.rec[blockIdx.x];
+    const uint32_t b = (uint32_t)h.first + blockIdx.x;
+    if (threadIdx.x == 0) {
+        d.rtab[b] = rec;
+        d.frame_pos[b] = rec.out_pos;
+        if (h.last && blockIdx.x + 1 == gridDim.x) d.frame_pos[b + 1] = h.total;
+    }
+    for (uint32_t j = threadIdx.x; j < rec.nc; j += 256) d.chunk[rec.cbase + j] = make_uint2(b, 0u);
+}
+
+// the sections of a record in the run form on the link
+struct CwrSections {
+    const uint8_t *gap, *len;
+    const uint32_t *esc, *diff;
+    __device__ CwrSections(const uint8_t *in, const CwrRecord &rec)
+        : gap(in + rec.in_pos + 12), len(gap + cwire_pad4(rec.r)), esc((const uint32_t *)(len + cwire_pad4(rec.r))), diff(esc + rec.e) {}
+};
+
+__global__ __launch_bounds__(256) void k_cwr_sums(const CwrDecode d) {
+    __shared__ uint32_t s_sum[4];
+    const uint32_t c = blockIdx.x;
+    const CwrRecord rec = d.rtab[d.chunk[c].x];
+    if (!rec.form) return;
+    const uint32_t q = (c - rec.cbase) * (kCwrRuns / 4) + threadIdx.x;   // the thread's dword of len[]: runs 4q .. 4q + 3
+    uint32_t sum = 0;
+    if (4 * (uint64_t)q < rec.r) {
+        const uint32_t w = ((const uint32_t *)CwrSections(d.in, rec).len)[q];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            if (4 * (uint64_t)q + j < rec.r) sum += ((w >> (8 * j)) & 255u) + 1u;
+    }
+    sum = cwa_wave_sum(sum);
+    if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) d.chunk[c].y = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+}
+
+__global__ __launch_bounds__(256) void k_cwr_dscan(const CwrDecode d) {
+    __shared__ uint32_t s_wave[2][4];
+    const CwrRecord rec = d.rtab[blockIdx.x];
+    if (!rec.form) return;
+    uint32_t carry = 0;
+    int buf = 0;
+    for (uint32_t i0 = 0; i0 < rec.nc; i0 += 256, buf ^= 1) {
+        const uint32_t i = i0 + threadIdx.x;
+        uint2 *ch = d.chunk + rec.cbase + i;
+        const uint32_t before = block_exclusive_scan<4>(i < rec.nc ? ch->y : 0u, s_wave[buf], carry);
+        if (i < rec.nc) ch->y = before;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_cwr_expand(const CwrDecode d) {
+    __shared__ uint32_t s_wave[4];
+    __shared__ uint32_t s_tile[kCwaChunk / 4];
+    const uint32_t c = blockIdx.x, tid = threadIdx.x;
+    const uint2 ch = d.chunk[c];
+    const CwrRecord rec = d.rtab[ch.x];
+    const uint32_t j = c - rec.cbase, n = rec.n;
+    if (rec.out_pos + cwire_record_bytes(n, rec.e) > d.capacity) return;   // a record that does not fit is skipped whole
+    const CwireSections<uint8_t> dst(d.out, rec.out_pos, n, rec.e);
+    if (j == 0 && tid == 0) {
+        uint32_t *head = (uint32_t *)(d.out + rec.out_pos);
+        __builtin_nontemporal_store(n, head);
+        __builtin_nontemporal_store(rec.e, head + 1);
+    }
+    uint32_t lo, hi;
+    if (!rec.form) {   // the compact record, dword for dword
+        const CwireSections<const uint8_t> src(d.in, rec.in_pos, n, rec.e);
+        cwire_share(cwire_dwords(n), j, rec.nc, lo, hi);
+        cwr_copy(src.code32(), dst.code32(), lo, hi);
+        cwr_copy(src.diff32(), dst.diff32(), lo, hi);
+        cwire_share(rec.e, j, rec.nc, lo, hi);
+        cwr_copy(src.esc32(), dst.esc32(), lo, hi);
+        return;
+    }
+    const CwrSections src(d.in, rec);
+    cwire_share(cwire_dwords(n), j, rec.nc, lo, hi);
+    cwr_copy_diff(src.diff, dst.diff32(), lo, hi, n);
+    cwire_share(rec.e, j, rec.nc, lo, hi);
+    cwr_copy(src.esc, dst.esc32(), lo, hi);
+    // the thread's four runs: their gaps and the entries they start at
+    const uint32_t q = j * (kCwrRuns / 4) + tid;
+    uint32_t gw = 0, at[5];
+    bool live[4] = {false, false, false, false};
+    at[0] = 0;
+    if (4 * (uint64_t)q < rec.r) {
+        gw = ((const uint32_t *)src.gap)[q];
+        const uint32_t lw = ((const uint32_t *)src.len)[q];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            live[i] = 4 * (uint64_t)q + i < rec.r;
+            at[i + 1] = at[i] + (live[i] ? ((lw >> (8 * i)) & 255u) + 1u : 0u);
+        }
+    } else {
+        at[1] = at[2] = at[3] = at[4] = 0;
+    }
+    uint32_t carry = 0;
+    const uint32_t first = ch.y + block_exclusive_scan<4>(at[4], s_wave, carry);
+    // The entries [E0, E1) are the workgroup's, clamped to n; the record's last workgroup goes on to pad4(n).  (Lengths that sum
+    // past n, or past 2^32, only shorten or empty what is written.)
+    const uint64_t E0 = ch.y < n ? ch.y : n, sumto = (uint64_t)ch.y + carry;
+    const uint64_t E1 = j + 1 == rec.nc ? cwire_pad4(n) : (sumto < n ? sumto : n);
+    for (uint64_t tile = E0 & ~3ull; tile < E1; tile += kCwaChunk) {
+        __syncthreads();   // (the round before has stored its tile)
+#pragma unroll
+        for (int i = 0; i < (int)(kCwaChunk / 1024); i++) s_tile[tid + 256 * i] = 0u;
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const uint64_t x = (uint64_t)first + at[i];
+            if (live[i] && x >= tile && x - tile < kCwaChunk && x >= E0 && x < n) ((uint8_t *)s_tile)[x - tile] = (uint8_t)(gw >> (8 * i));
+        }
+        __syncthreads();
+        const uint64_t end = E1 - tile < kCwaChunk ? E1 : tile + kCwaChunk;
+        cwr_store_bytes(dst.code, (const uint8_t *)s_tile, tile, E0 > tile ? E0 : tile, end, tile / 4, (end + 3) / 4);
+    }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 uint32_t cwa_chunks(uint32_t n) { return n ? (n + kCwaChunk - 1) / kCwaChunk : 1u; }
 uint32_t cwa_tiles(uint32_t nbytes) { return (nbytes + kCwaTile - 1) / kCwaTile; }
@@ -2873,6 +3167,46 @@ hipError_t launch_cwire_split(const CwaArgs &a, const CwaFrame *records, int nre
     hipLaunchKernelGGL(k_cws_count, dim3(nblocks), dim3(kCwsThreads), 0, s, a, blk, max_bytes);
     hipLaunchKernelGGL(k_cws_scan, dim3(1), dim3(256), 0, s, blk, base, nblocks, nrecords, o);
     hipLaunchKernelGGL(k_cws_emit, dim3(nblocks), dim3(kCwsThreads), 0, s, a, blk, base, max_bytes, o);
+    return hipGetLastError();
+}
+
+// mi355_cwire_runs_encode_batch: the chunk table, then count, scan, place and emit
+hipError_t launch_cwire_runs_encode(const CwaArgs &a, const CwaFrame *records, int nrecords, int policy, const CwrOut &o, hipStream_t s) {
+    if (nrecords <= 0) return hipSuccess;
+    const uint32_t nchunks = launch_cwa_table(a, records, nrecords, s);
+    // (a workgroup per record, any count up to max_batch in one grid; the table's 128 headers a launch are crossed by the 130-record
+    // call of tests/test_cwire_runs_gpu.py)
+    const dim3 per_record((uint32_t)nrecords);
+    hipLaunchKernelGGL(k_cwr_count, dim3(nchunks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_cwr_scan, per_record, dim3(256), 0, s, a, policy, o.forms);
+    hipLaunchKernelGGL(k_cwr_place, dim3(1), dim3(256), 0, s, (const uint32_t *)o.forms, nrecords, o.pos);
+    hipLaunchKernelGGL(k_cwr_emit, dim3(nchunks), dim3(256), 0, s, a, o);
+    return hipGetLastError();
+}
+
+uint32_t cwr_chunks(uint32_t form, uint32_t n, uint32_t r) {
+    if (!form) return cwa_chunks(n);
+    return r ? (r + kCwrRuns - 1) / kCwrRuns : 1u;
+}
+uint32_t cwr_chunks_max(uint32_t nbytes) { return nbytes ? (nbytes + kCwrRuns - 1) / kCwrRuns : 1u; }
+
+// mi355_cwire_runs_decode_batch: the record table, then sums, scan and expand
+hipError_t launch_cwire_runs_decode(const CwrDecode &d, const CwrRecord *records, int nrecords, uint64_t total, hipStream_t s) {
+    if (nrecords <= 0) return hipSuccess;
+    CwrTableArgs h{};
+    h.total = total;
+    for (int i0 = 0; i0 < nrecords; i0 += kCwrTableRecords) {
+        const int nr = nrecords - i0 < kCwrTableRecords ? nrecords - i0 : kCwrTableRecords;
+        h.first = i0;
+        h.last = i0 + nr == nrecords;
+        for (int i = 0; i < nr; i++) h.rec[i] = records[i0 + i];
+        hipLaunchKernelGGL(k_cwr_table, dim3(nr), dim3(256), 0, s, d, h);
+    }
+    const uint32_t nchunks = records[nrecords - 1].cbase + records[nrecords - 1].nc;
+    hipLaunchKernelGGL(k_cwr_sums, dim3(nchunks), dim3(256), 0, s, d);
+    const dim3 per_record((uint32_t)nrecords);   // (as in the encoder; the table's 64 records a launch are crossed by the same test)
+    hipLaunchKernelGGL(k_cwr_dscan, per_record, dim3(256), 0, s, d);
+    hipLaunchKernelGGL(k_cwr_expand, dim3(nchunks), dim3(256), 0, s, d);
     return hipGetLastError();
 }
 

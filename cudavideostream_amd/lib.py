@@ -29,6 +29,8 @@ CROP_KEEP_INDEX = 1   # MI355_CROP_*
 CWIRE_SPLIT_BLOCK = 65536   # MI355_CWIRE_SPLIT_BLOCK
 FEC_BAD_HEADER, FEC_BAD_TAIL = 1, 2   # MI355_FEC_BAD_*
 FEC_ABSENT = 0xFFFFFFFFFFFFFFFF   # MI355_FEC_ABSENT
+RUNS_WHERE_SMALLER, RUNS_ALWAYS = 0, 1    # MI355_RUNS_* (policies)
+RUNS_FORM_COMPACT, RUNS_FORM_RUNS = 0, 1  # MI355_RUNS_FORM_*
 CWIRE_BAD_CODES, CWIRE_BAD_RANGE, CWIRE_BAD_PAD, CWIRE_BAD_ESCAPE, CWIRE_BAD_HEADER = 1, 2, 4, 8, 16   # MI355_CWIRE_BAD_*
 
 
@@ -150,6 +152,15 @@ SYMBOLS = {
                                               C.c_void_p, C.c_void_p]),
     "mi355_cwire_fec_repair_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "mi355_cwire_runs_frame_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "mi355_cwire_runs_bytes_max": (C.c_size_t, [C.c_size_t, C.c_int, C.c_int]),
+    "mi355_cwire_runs_encode_host": (C.c_int, [C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mi355_cwire_runs_encode_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mi355_cwire_runs_decode_host": (C.c_int, [C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_size_t]),
+    "mi355_cwire_runs_decode_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]),
     "mi355_state_tiles": (C.c_size_t, [C.c_size_t]),
     "mi355_state_digest_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "mi355_state_digest_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),

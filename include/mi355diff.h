@@ -100,7 +100,9 @@ typedef struct mi355_config {
  *      + mi355_cwire_split_host, mi355_cwire_split_cwire_batch, mi355_cwire_split_pieces_max, mi355_cwire_split_bytes_max,
  *      MI355_CWIRE_SPLIT_BLOCK (additions only);
  *      + mi355_thumb_cwire_host, mi355_thumb_cwire_batch (additions only);
- *      + mi355_cwire_fec_* (additions only) */
+ *      + mi355_cwire_fec_* (additions only);
+ *      + mi355_cwire_runs_frame_bytes, mi355_cwire_runs_bytes_max, mi355_cwire_runs_encode_host, mi355_cwire_runs_encode_batch,
+ *      mi355_cwire_runs_decode_host, mi355_cwire_runs_decode_batch, MI355_RUNS_* (additions only) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -834,6 +836,97 @@ int mi355_cwire_fec_repair_batch(mi355_core *core, const void *d_rx, size_t rx_b
                                  const uint32_t *h_job_first /* [njobs + 1] */, const uint64_t *h_slot_off, const uint32_t *h_slot_len,
                                  const uint64_t *h_parity_off /* [njobs][2] */, const uint32_t *h_fec_len /* [njobs] */, void *d_out,
                                  size_t spacing_bytes, void *d_verdict /* uint32[njobs][2] */);
+
+/* Run-coded records for the link: a transcoder at the link's edge, the sender's last call before a stream socket and the
+ * receiver's first call behind it.  A compact record spends a code byte on every entry, also where the entry's index is the one
+ * before plus one (code 0); key frames (mi355_refresh_cwire_batch without digests), moving objects, threshold 0, a camera's first
+ * thumbnail record and mosaic canvases are almost only such codes.  The run form keeps one code per RUN of consecutive indices and
+ * halves those records; scattered noise it would enlarge, so the encoder packs a record only where the policy says so and tells
+ * the receiver in a table.  Everything between the two calls keeps working on compact records; decode(encode(x)) is x byte for
+ * byte.
+ *   The run form of a compact record {n, e, code[n], esc[e], diff[n]}: entry k STARTS A RUN when k % 256 == 0 or code[k] != 0; a
+ *   run is a start and the entries behind it up to the next start.  Runs never cross a multiple of 256 entries, a run holds 1 ..
+ *   256 entries (its length fits a byte, no second escape list), every 255 code is a start (the escape section carries over word
+ *   for word), and the runs of entries [4096c, 4096c + 4096) depend on those entries alone.  The cut costs at most 2 bytes per 256
+ *   entries.  4-byte aligned, little-endian:
+ *     u32 n | u32 e | u32 r
+ *     u8  gap[r]            code[k] of each run's first entry, in order (255: escaped, as in the compact record)
+ *     u8  0[pad4(r) - r]
+ *     u8  len[r]            entries of the run - 1
+ *     u8  0[pad4(r) - r]
+ *     u32 esc[e]            the compact record's escape section
+ *     u8  diff[n]           the compact record's diff section
+ *     u8  0[pad4(n) - n]
+ *   mi355_cwire_runs_frame_bytes(n, e, r) = 12 + 2*pad4(r) + 4*e + pad4(n): smaller than the compact record exactly when
+ *   4 + 2*pad4(r) < pad4(n).  xs = {3, 4, 5, 300, 301, 1000}: codes {3, 0, 0, 255, 0, 255}, esc {294, 698}; runs gap {3, 255, 255},
+ *   len {2, 1, 0}, r = 3; 36 bytes against 32, so not packed.  Canonical: one byte string per compact record -- runs are maximal
+ *   under the rule, pad bytes zero; n == 0 has r == 0 and 12 bytes.
+ *   Capacity: r <= n, and an escape spans at least 256 indices that hold one entry, so n + 255*e <= N and a record in the run form
+ *   never needs more than 12 + 3*pad4(n) + 4*e <= 12 + 3*pad4(N) bytes; under MI355_RUNS_WHERE_SMALLER a record leaves in the
+ *   smaller of its forms, never above the compact record's 8 + 2*pad4(N).  mi355_cwire_runs_bytes_max(frame_bytes, nrecords, policy)
+ *   = nrecords * (12 + 3*pad4(N)) under MI355_RUNS_ALWAYS, mi355_cwire_bytes_max(N, nrecords) under MI355_RUNS_WHERE_SMALLER, 0 for
+ *   an unknown policy.
+ *   Encoder.  Input: compact records back to back where h_counts[b] / h_escapes[b] put them, as in mi355_cwire_check_batch.
+ *   forms, uint32[nrecords][4]: forms[b] = {form, n, e, r}, form MI355_RUNS_FORM_COMPACT (the output bytes of record b are the
+ *   compact record) or MI355_RUNS_FORM_RUNS (they are the run form); r is the run count in either case.  The table is what the
+ *   sender puts on the socket ahead of the bytes and what the receiver hands to the decoder -- as every call of the family takes
+ *   h_counts / h_escapes from the host.  The header words inside the buffers are written by the encoder; the decoder skips them
+ *   and never follows them.  Policy: MI355_RUNS_WHERE_SMALLER uses the run form exactly when it is strictly smaller,
+ *   MI355_RUNS_ALWAYS always (tests, measurements).  pos, uint64[nrecords + 1]: the exclusive scan of the output sizes, always
+ *   exact; record b is written whole at out + pos[b] iff pos[b + 1] <= capacity_bytes, one that does not fit is skipped whole and
+ *   later ones that fit are still written.  A record kept compact is copied as it is (its pad bytes too); in the run form the
+ *   pad bytes are zero.
+ *   Decoder.  Input: the encoder's bytes and h_forms.  Output: the compact records back to back, frame_pos (uint64[nrecords + 1],
+ *   always exact -- it follows from h_forms alone) and the capacity rule above.  Decoding what the encoder wrote returns the
+ *   encoder's input bytes and frame positions, under either policy.
+ *   The host forms are the definition: plain C++, no core, no HIP call, no alignment requirement.  The GPU forms are bit-identical
+ *   to them in every output.
+ *   mi355_cwire_runs_decode_host refuses with MI355_ERR_INVALID (the reason in mi355_last_error): a truncated input; a form other
+ *   than 0 or 1; n > frame_bytes, e > n or r > n; a run that crosses a multiple of 256 entries; run lengths that do not sum to n;
+ *   a count of 255 gaps other than e.  Records before the refused one stay written, with their frame_pos.
+ *   mi355_cwire_runs_decode_batch under malformed content with consistent headers promises what the family promises: nothing is
+ *   read outside the span the headers give, nothing is written outside [frame_pos[b], frame_pos[b + 1]) and the position table,
+ *   entries past n are dropped; the contents of that one record are otherwise unspecified.
+ *   Refused with MI355_ERR_INVALID before anything is launched or written (batch forms): a null core; nrecords outside
+ *   [0, max_batch]; with nrecords > 0 a null pointer; h_escapes[b] > h_counts[b], h_counts[b] > N (decoder: a row of h_forms the
+ *   host decoder refuses by itself); an unknown policy; buffers, forms or input not 4-byte aligned, positions not 8-byte aligned;
+ *   the input span overlapping an output.  nrecords == 0 writes pos[0] = 0 (frame_pos[0] = 0) and nothing else.
+ * Asynchronous on the core's stream, behind the last expansion of this core; with a caller's stream everything runs on it in call
+ * order.  Nothing is allocated inside a call (the decoder's record table and one word per 1024 runs are made with the core and
+ * counted by mi355_workspace_bytes; the encoder uses the chunk table of the GPU clients) and the core's state is not touched.
+ * Encoder: the chunk table, a count pass (a workgroup per 4096 codes, four entries per lane from one code dword, run starts by
+ * ballot and popcount), a scan per record (first run rank per chunk, r, the size decision, the form row), one workgroup for pos in
+ * 64 bits, and an emit pass per chunk: the starts' codes and places compacted in LDS, len as the distance to the chunk's next
+ * start, gap[] and len[] stored as whole dwords inside the chunk's runs and single bytes at its ragged ends (no dword has two
+ * writers, the pads have one), esc and diff copied as whole dwords, non-temporal stores.  Decoder: the sum of len + 1 per
+ * workgroup of 1024 runs, a scan per record, then each workgroup builds the code bytes its runs cover 4096 at a time in LDS and
+ * stores them under the same single-writer rule, clamped to n.  No workgroup waits on another.
+ * Measured (profiles/multi_runs.json: tools/bench_multi.py --legs runs; 1080p, T = 1, MI355_RUNS_WHERE_SMALLER, median of five
+ * rounds, spread of the rounds 0.1 - 7.3 %, against mi355_cwire_coalesce_cwire_batch with T = 1 on the same records in the same
+ * run; both outputs equal the host forms' at every point), us per record at S = 4 / 16 / 64: key frames (mi355_refresh_cwire_batch
+ * of every tile; 6.22 M entries, 24.6 k runs, 12.44 MB in, 6.27 MB out: 0.504) coalesce 48.32 / 37.26 / 36.41, encode
+ * 11.79 / 8.43 / 9.81, decode 25.80 / 8.58 / 6.12; local input (a block moving over a still background, 4.8 k entries, 630 runs,
+ * 11.7 kB in, 8.2 kB out: 0.70) coalesce 16.64 / 5.37 / 2.39, encode 4.55 / 1.12 / 0.34, decode 3.62 / 0.94 / 0.26;
+ * webcam-like input (137 k entries, 122 k runs: kept compact, a dword copy) coalesce 16.18 / 8.14 / 6.23, encode 4.59 / 1.13 / 0.36,
+ * decode 3.62 / 0.95 / 0.26.  The expectation -- each call no slower than that coalesce call by more than the rounds' spread -- is
+ * met at every point (encode 0.06 - 0.28 of it, decode 0.04 - 0.53): both read the record about twice and write less than the
+ * coalescer does.  Not profiled per kernel.  DESIGN.md section 4, "Run-coded records for the
+ * link". */
+#define MI355_RUNS_WHERE_SMALLER 0
+#define MI355_RUNS_ALWAYS 1
+#define MI355_RUNS_FORM_COMPACT 0u
+#define MI355_RUNS_FORM_RUNS 1u
+size_t mi355_cwire_runs_frame_bytes(uint32_t n, uint32_t e, uint32_t r);
+size_t mi355_cwire_runs_bytes_max(size_t frame_bytes, int nrecords, int policy);
+int mi355_cwire_runs_encode_host(size_t frame_bytes, const void *cwire, size_t cwire_bytes, const uint32_t *h_counts,
+                                 const uint32_t *h_escapes, int nrecords, int policy, uint32_t *forms /* [nrecords][4] */,
+                                 uint64_t *pos /* [nrecords + 1] */, void *out, size_t capacity_bytes);
+int mi355_cwire_runs_encode_batch(mi355_core *core, const void *d_cwire_in, const uint32_t *h_counts, const uint32_t *h_escapes,
+                                  int nrecords, int policy, void *d_forms, void *d_pos, void *d_out, size_t capacity_bytes);
+int mi355_cwire_runs_decode_host(size_t frame_bytes, const void *in, size_t in_bytes, const uint32_t *h_forms, int nrecords,
+                                 uint64_t *frame_pos /* [nrecords + 1] */, void *cwire_out, size_t capacity_bytes);
+int mi355_cwire_runs_decode_batch(mi355_core *core, const void *d_in, const uint32_t *h_forms, int nrecords, void *d_frame_pos,
+                                  void *d_cwire_out, size_t capacity_bytes);
 
 /* A tick held to a budget: the sender's rate control.  The nstreams compact records mi355_diff_multi_cwire_batch just wrote
  * (back to back where h_counts[s] / h_escapes[s] put them; the headers come from the host and are not trusted in the buffer, as

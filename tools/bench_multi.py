@@ -85,6 +85,16 @@ the split call on the split leg's inputs (max_bytes = 1400, groups of 8), us per
   repair_one, repair_two  mi355_cwire_fec_repair_batch, one job per stream, one and two lost pieces (reported, not judged).
 The expectation to test: fec_k2 no slower than `split` by more than the rounds' spread (`fec_k2_no_slower_than_split`).
 
+The runs leg (--legs runs, a run of its own: `--legs runs --streams 4,16,64 > profiles/multi_runs.json`) measures the link-edge
+transcoder on the records of one tick (T = 1), us per record, on the webcam-like input, the local input and `keyframe`
+(mi355_refresh_cwire_batch of every tile of the webcam-like states: what a late joiner is sent):
+  coalesce       mi355_cwire_coalesce_cwire_batch with T = 1 on the same records: the split leg's comparator;
+  encode         mi355_cwire_runs_encode_batch under MI355_RUNS_WHERE_SMALLER;
+  decode         mi355_cwire_runs_decode_batch on what it wrote.
+It also reports bytes in, bytes out and records packed per input; both outputs are compared with the host forms before anything is
+timed.  The expectation to test: each no slower than `coalesce` by more than the rounds' spread
+(`encode_no_slower_than_coalesce`, `decode_no_slower_than_coalesce`).
+
 The mosaic leg (--legs mosaic, a run of its own: `--legs mosaic --streams 4,16 > profiles/multi_mosaic.json`) measures the call that
 places S cameras side by side on one canvas (a C x C grid of whole frames, C = ceil(sqrt(S)): 2x2 into 3840x2160 and 4x4 into
 7680x4320 at 1080p), in microseconds per input record, ONE JSON line: T = 1 and T = 16, on the webcam-like and the local input:
@@ -1211,6 +1221,98 @@ def run_split(W, H, rounds, S, kind, limits=(1400, 8972)):
     return out
 
 
+def key_frame_records(W, H, states):
+    """The key frames of states [S][n], as a sender's mi355_refresh_cwire_batch without digests makes them (every tile) -> one
+    chunk (records, counts, escapes, positions) as sender_records gives them."""
+    import numpy as np
+    from cudavideostream_amd import CUDACore, cwire_bytes_max
+    S, n = states.shape
+    cap = cwire_bytes_max(n, S)
+    d_off = torch.zeros(S + 1, dtype=torch.int32, device=states.device)
+    d_pos = torch.zeros(S + 1, dtype=torch.int64, device=states.device)
+    d_cw = torch.empty(cap, dtype=torch.uint8, device=states.device)
+    with CUDACore(W, H, max_batch=S) as server:
+        d_mask = torch.zeros(S * ((n + 4095) // 4096 + 31) // 32 + S, dtype=torch.int32, device=states.device)
+        torch.cuda.synchronize()
+        server.refresh_cwire_batch(states, S, None, d_mask, d_off, d_pos, d_cw, cap)
+        server.synchronize()
+    pos = d_pos.cpu().numpy().astype(np.int64)
+    counts = np.diff(d_off.cpu().numpy().view(np.uint32).astype(np.int64)).astype(np.uint32)
+    escapes = ((np.diff(pos) - 8 - 2 * ((counts.astype(np.int64) + 3) & ~3)) // 4).astype(np.uint32)
+    return [(d_cw[:int(pos[S])].clone(), counts, escapes, pos)]
+
+
+def run_runs(W, H, rounds, S, kind):
+    """The runs leg for one S and one input, T = 1 -> its dictionary.  coalesce: mi355_cwire_coalesce_cwire_batch on the records of
+    one tick (with T = 1 it gives the input back), the comparator of the split leg.  encode: mi355_cwire_runs_encode_batch under
+    MI355_RUNS_WHERE_SMALLER on the same records; decode: mi355_cwire_runs_decode_batch on what it wrote.  Inputs: the webcam-like
+    tick, the local tick, and `keyframe`, mi355_refresh_cwire_batch of every tile of the webcam-like states.  All on one core's own
+    stream, alternating within every round.  Before anything is timed both outputs are compared with the host forms."""
+    import numpy as np
+    from cudavideostream_amd import CUDACore, cwire_bytes_max, cwire_runs_bytes_max, cwire_runs_decode_host, cwire_runs_encode_host
+    dev = torch.device("cuda", 0)
+    n, T = 3 * W * H, 1
+    passes = 2 * max(1, 1024 // S)                     # ~2 k records per timed window
+    states0, fwd = burst_input("webcam" if kind == "keyframe" else kind, S, T, W, H, dev)
+    per_call, chunks = burst_chunks(S, T, n)
+    assert len(chunks) == 1, "the leg runs in one call: max_batch * N < 2^32"
+    recs = key_frame_records(W, H, states0) if kind == "keyframe" else sender_records(W, H, fwd, states0.clone())
+    d_cw, counts, escapes, pos = one_call(recs)
+    ocap = cwire_bytes_max(n, S)
+    d_ooff = torch.zeros(S + 1, dtype=torch.int32, device=dev)
+    d_opos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
+    d_out = torch.empty(ocap, dtype=torch.uint8, device=dev)
+    lcap = cwire_runs_bytes_max(n, S, lib.RUNS_WHERE_SMALLER)
+    d_forms = torch.zeros(4 * S, dtype=torch.int32, device=dev)
+    d_lpos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
+    d_link = torch.empty(lcap, dtype=torch.uint8, device=dev)
+    d_fpos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
+    d_back = torch.empty(ocap, dtype=torch.uint8, device=dev)
+    relay = CUDACore(W, H, max_batch=S)
+    torch.cuda.synchronize()
+    # both outputs are the host forms', and the decode is the input
+    relay.cwire_runs_encode_batch(d_cw, counts, escapes, S, lib.RUNS_WHERE_SMALLER, d_forms, d_lpos, d_link, lcap)
+    relay.synchronize()
+    host = d_cw.cpu().numpy()
+    wf, wp, wo = cwire_runs_encode_host(host, counts, escapes, n, lib.RUNS_WHERE_SMALLER, capacity_bytes=lcap)
+    forms = d_forms.cpu().numpy().view(np.uint32).reshape(S, 4).copy()
+    link_bytes = int(wp[-1])
+    assert np.array_equal(forms, wf) and np.array_equal(d_lpos.cpu().numpy().view(np.uint64), wp)
+    assert np.array_equal(d_link[:link_bytes].cpu().numpy(), wo[:link_bytes])
+    relay.cwire_runs_decode_batch(d_link, forms, S, d_fpos, d_back, ocap)
+    relay.synchronize()
+    fp, back = cwire_runs_decode_host(wo[:link_bytes], wf, n)
+    assert np.array_equal(d_fpos.cpu().numpy().view(np.uint64), fp) and int(fp[-1]) == host.size
+    assert np.array_equal(d_back[:host.size].cpu().numpy(), host) and np.array_equal(back, host)
+
+    def leg_coalesce():
+        for _ in range(passes):
+            relay.cwire_coalesce_cwire_batch(d_cw, counts, escapes, S, T, d_ooff, d_opos, d_out, ocap)
+        relay.synchronize()
+
+    def leg_encode():
+        for _ in range(passes):
+            relay.cwire_runs_encode_batch(d_cw, counts, escapes, S, lib.RUNS_WHERE_SMALLER, d_forms, d_lpos, d_link, lcap)
+        relay.synchronize()
+
+    def leg_decode():
+        for _ in range(passes):
+            relay.cwire_runs_decode_batch(d_link, forms, S, d_fpos, d_back, ocap)
+        relay.synchronize()
+
+    out = {"input": kind, "streams": S, "frames": T, "passes": passes,
+           "input_entries_per_stream": round(int(counts.sum()) / S, 1), "runs_per_stream": round(int(wf[:, 3].sum()) / S, 1),
+           "bytes_in_per_stream": round(host.size / S, 1), "bytes_out_per_stream": round(link_bytes / S, 1),
+           "bytes_out_over_in": round(link_bytes / host.size, 4), "records_packed": int(wf[:, 0].sum()), "records": S}
+    times = time_legs({"coalesce": leg_coalesce, "encode": leg_encode, "decode": leg_decode}, rounds, passes * S)
+    fig = report(out, times, "_us_per_record", spread=True, as_printed=True)
+    # the expectation: neither call slower than the coalescer by more than the rounds' spread (of either leg)
+    for name in ("encode", "decode"):
+        out[f"{name}_over_coalesce"], out[f"{name}_no_slower_than_coalesce"] = versus(fig, name, "coalesce")
+    relay.close()
+    return out
+
+
 def run_fec(W, H, rounds, S, kind, M=1400, G=8):
     """The fec leg for one S and one input, T = 1 -> its dictionary.  split: mi355_cwire_split_cwire_batch at max_bytes = M on the
     records of one tick; fec_k1 / fec_k2: mi355_cwire_fec_batch with K = 1 / 2 parity blocks per group of G on the pieces that call
@@ -1477,6 +1579,9 @@ LEGS = {
     "fec": dict(run=run_fec, points=lambda a: grid(S=ints(a.streams), kind=KINDS), bench="multi_fec",
                 verdict=[("fec_k2_no_slower_than_split", "parity at K = 2 no slower than split at every point",
                           "parity at K = 2 slower than split at some point")]),
+    "runs": dict(run=run_runs, points=lambda a: grid(S=ints(a.streams), kind=KINDS + ("keyframe",)), bench="multi_runs",
+                 verdict=[("encode_no_slower_than_coalesce", "encode no slower than coalesce at every point", "encode slower than coalesce at some point"),
+                          ("decode_no_slower_than_coalesce", "decode no slower than coalesce at every point", "decode slower than coalesce at some point")]),
     "mosaic": dict(run=run_mosaic, points=lambda a: grid(S=ints(a.streams), T=(1, 16), kind=KINDS), bench="multi_mosaic"),
     "budget": dict(run=run_budget, points=lambda a: grid(S=ints(a.streams)), bench="multi_budget", input=True),
     "activity": dict(run=run_activity, points=activity_points, bench="multi_activity",

@@ -11,7 +11,7 @@
 // (ActivityCheck, RecordCheck, WallCheck, ThumbViewer), that is that mode.
 //
 //   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B]
-//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check] | --resync K [--burst B] | --crop X,Y,W,H [--burst K] | --mosaic CxR [--burst K] | [--burst K --coalesce] --datagram BYTES [--fec G[,K]] | --thumb K [--burst T] [--thumb-drop TICK]] [--wall K]]
+//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check] | --resync K [--burst B] | --crop X,Y,W,H [--burst K] | --mosaic CxR [--burst K] | [--burst K --coalesce] --datagram BYTES [--fec G[,K]] | --thumb K [--burst T] [--thumb-drop TICK]] [--wall K] [--runs]]
 //   exit status 0 = all checks passed
 #include <algorithm>
 #include <cstdint>
@@ -68,6 +68,27 @@ static mi355_config make_config(int w, int h, int max_batch) {
     return cfg;
 }
 
+// --compact --multi S ... --runs: the link's edge.  Behind whatever relay steps were asked for, the node that writes records to a
+// stream socket run-codes them first (mi355_cwire_runs_encode_batch, MI355_RUNS_WHERE_SMALLER) and writes the forms table and
+// then the bytes; the node that reads them decodes them (mi355_cwire_runs_decode_batch) and goes on as it did before, on the
+// compact records it would have read without the flag -- which the tool checks byte for byte.  The two calls run on cores of
+// their own, of the size of the frames whose records cross (a canvas for --mosaic).  Session::send_records is that socket.
+static bool g_runs = false;
+struct Session;
+struct RunsLink {
+    mi355_core *enc, *dec;
+    int w, h, most;
+    size_t cap;
+    void *e_in, *e_forms, *e_pos, *e_out, *d_in, *d_pos, *d_out;
+    std::vector<uint32_t> counts, escapes, forms, forms_rx;
+    std::vector<uint64_t> pos;
+    std::vector<uint8_t> link, link_rx;
+    size_t compact_bytes, link_bytes, table_bytes, records, packed;
+    RunsLink() : enc(nullptr), dec(nullptr), w(0), h(0), most(0), cap(0), compact_bytes(0), link_bytes(0), table_bytes(0), records(0), packed(0) {}
+    int ensure(Session &ss, int nrec);
+    int send(Session &ss, const uint8_t *src, uint8_t *dst, size_t bytes, int nrec);
+};
+
 // What one run holds: its cores, its pipe and every allocation it handed out.  A failure is printed where it happens and
 // remembered: everything after it hands out nullptr, so a mode asks ok() once behind its set-up.  close() is for the success
 // path; after an error the function returns and the process ends.
@@ -79,6 +100,7 @@ struct Session {
     struct Dev { mi355_core *core; void *p; };
     std::vector<Dev> devs;
     std::vector<void *> pins;
+    RunsLink runs;   // --runs: what crosses the stream socket
 
     Session(int w_, int h_) : w(w_), h(h_), threshold(make_config(w_, h_, 1).threshold), n((size_t)3 * w_ * h_) {
         if (pipe(fds) != 0) failed = true;
@@ -89,8 +111,9 @@ struct Session {
         failed = true;
         return nullptr;
     }
-    mi355_core *core(int max_batch) {
-        const mi355_config cfg = make_config(w, h, max_batch);
+    mi355_core *core(int max_batch) { return core_of(w, h, max_batch); }
+    mi355_core *core_of(int cw, int ch, int max_batch) {   // (a core of another frame size: the link of a canvas)
+        const mi355_config cfg = make_config(cw, ch, max_batch);
         mi355_core *c = nullptr;
         if (failed || mi355_create(&cfg, &c) != MI355_OK) return (mi355_core *)fail("mi355_create");
         cores.push_back(c);
@@ -110,6 +133,11 @@ struct Session {
     }
     // "send" bytes and "receive" them: written in pieces that fit the pipe buffer, read back in between
     bool send(const void *src, void *dst, size_t bytes) { return through(fds, src, dst, bytes); }
+    // nrec compact records to the stream socket and off it again; with --runs they cross it run-coded where that is smaller
+    bool send_records(const uint8_t *src, uint8_t *dst, size_t bytes, int nrec) {
+        if (!g_runs || nrec == 0) return send(src, dst, bytes);
+        return runs.send(*this, src, dst, bytes, nrec) == 0;
+    }
     static bool through(const int pipe_fds[2], const void *src, void *dst, size_t bytes) {   // (any pipe: a mode may open more)
         for (size_t at = 0; at < bytes;) {
             const size_t piece = bytes - at < 32768 ? bytes - at : 32768;
@@ -123,6 +151,9 @@ struct Session {
         for (size_t i = 0; i < devs.size(); i++) OK(mi355_dev_free(devs[i].core, devs[i].p));
         for (size_t i = 0; i < pins.size(); i++) OK(mi355_host_free(pins[i]));
         for (size_t i = 0; i < cores.size(); i++) mi355_destroy(cores[i]);
+        if (g_runs)
+            printf("{\"runs\": true, \"records\": %zu, \"records_packed\": %zu, \"compact_bytes\": %zu, \"link_bytes\": %zu, "
+                   "\"forms_table_bytes\": %zu}\n", runs.records, runs.packed, runs.compact_bytes, runs.link_bytes, runs.table_bytes);
         return 0;
     }
 };
@@ -164,6 +195,46 @@ static int walk_records(const uint8_t *rx, size_t p, size_t end, int nrec, uint3
     if (r == nrec && p == end) return 0;
     fprintf(stderr, "stream framing broken\n");
     return 1;
+}
+
+int RunsLink::ensure(Session &ss, int nrec) {
+    if (w == 0) { w = ss.w; h = ss.h; }
+    if (nrec <= most) return 0;
+    most = nrec;   // (a mode that sends more records later gets a larger pair of cores; the old ones go with the session)
+    const size_t n = (size_t)3 * w * h;
+    cap = mi355_cwire_runs_bytes_max(n, most, MI355_RUNS_WHERE_SMALLER);
+    enc = ss.core_of(w, h, most);
+    dec = ss.core_of(w, h, most);
+    e_in = ss.dev(enc, cap); e_forms = ss.dev(enc, 16 * (size_t)most); e_pos = ss.dev(enc, 8 * ((size_t)most + 1)); e_out = ss.dev(enc, cap);
+    d_in = ss.dev(dec, cap); d_pos = ss.dev(dec, 8 * ((size_t)most + 1)); d_out = ss.dev(dec, cap);
+    counts.resize(most); escapes.resize(most); forms.resize(4 * (size_t)most); forms_rx.resize(4 * (size_t)most); pos.resize((size_t)most + 1);
+    link.resize(cap); link_rx.resize(cap);
+    return ss.ok() ? 0 : 1;
+}
+
+int RunsLink::send(Session &ss, const uint8_t *src, uint8_t *dst, size_t bytes, int nrec) {
+    if (ensure(ss, nrec)) return 1;
+    // ---- the sender's last call: its records (their headers are its own) -> the forms table and the link bytes
+    if (bytes > cap || walk_records(src, 0, bytes, nrec, counts.data(), escapes.data(), nullptr)) return 1;
+    OK(mi355_upload(enc, e_in, src, bytes));
+    OK(mi355_cwire_runs_encode_batch(enc, e_in, counts.data(), escapes.data(), nrec, MI355_RUNS_WHERE_SMALLER, e_forms, e_pos, e_out, cap));
+    OK(mi355_download(enc, forms.data(), e_forms, 16 * (size_t)nrec));
+    OK(mi355_download(enc, pos.data(), e_pos, 8 * ((size_t)nrec + 1)));
+    const size_t lb = (size_t)pos[nrec];
+    if (lb > bytes) { fprintf(stderr, "--runs: the link bytes exceed the compact bytes\n"); return 1; }
+    OK(mi355_download(enc, link.data(), e_out, lb));
+    // ---- the socket: the table, then the bytes
+    if (!ss.send(forms.data(), forms_rx.data(), 16 * (size_t)nrec) || !ss.send(link.data(), link_rx.data(), lb)) return 1;
+    // ---- the receiver's first call: compact records again, where it would have read them
+    OK(mi355_upload(dec, d_in, link_rx.data(), lb));
+    OK(mi355_cwire_runs_decode_batch(dec, d_in, forms_rx.data(), nrec, d_pos, d_out, cap));
+    OK(mi355_download(dec, pos.data(), d_pos, 8 * ((size_t)nrec + 1)));
+    if (pos[nrec] != bytes) { fprintf(stderr, "--runs: the decoded records are %llu bytes, the sender's %zu\n", (unsigned long long)pos[nrec], bytes); return 1; }
+    OK(mi355_download(dec, dst, d_out, bytes));
+    if (memcmp(dst, src, bytes) != 0) { fprintf(stderr, "--runs: the decoded records differ from the sender's\n"); return 1; }
+    for (int b = 0; b < nrec; b++) packed += forms[4 * (size_t)b] == MI355_RUNS_FORM_RUNS;
+    records += nrec; compact_bytes += bytes; link_bytes += lb; table_bytes += 16 * (size_t)nrec;
+    return 0;
 }
 
 // a host client beside a receiver: record r of a walk (rx, at) onto its frame; it must use the bytes the header said it has
@@ -311,11 +382,13 @@ struct Cameras {
 // [pos[s * nb], pos[(s + 1) * nb]), are one write; the node reads their headers behind those of camera s - 1 and uploads the
 // slice where it lies, stream-major, nothing re-staged.  A host client of camera s beside it applies the records one by one
 // (host_shown, if given: the frame it shows after each).
-static int slices_to_node(Session &ss, const Sender &tx, Receiver &node, int nb, uint8_t *host_frames, uint8_t *host_shown) {
+static int slices_to_node(Session &ss, const Sender &tx, Receiver &node, int nb, uint8_t *host_frames, uint8_t *host_shown,
+                          bool last_hop = false /* the node is the receiver: with --runs this socket is the link */) {
     const size_t n = tx.n;
     for (int s = 0; s < tx.S; s++) {
         const size_t a = (size_t)tx.pos[(size_t)s * nb], b = (size_t)tx.pos[(size_t)(s + 1) * nb];
-        if (!ss.send(tx.bytes.data() + a, node.rx.data() + a, b - a)) return 1;
+        if (!(last_hop ? ss.send_records(tx.bytes.data() + a, node.rx.data() + a, b - a, nb) : ss.send(tx.bytes.data() + a, node.rx.data() + a, b - a)))
+            return 1;
         if (node.walk(a, b, s * nb, nb)) return 1;
         for (int r = s * nb; r < (s + 1) * nb; r++) {
             if (host_apply(host_frames + (size_t)s * n, n, node.rx.data(), node.at.data(), r)) return 1;
@@ -626,9 +699,9 @@ static int run_multi(int w, int h, int T, int S, int K, int activity, bool check
         // ---- the sockets, the headers as read from the stream, the upload; the host clients beside it.  A tick: one pipe here,
         // the receiver stages the cameras' records back to back.  A burst: a slice per camera.
         if (burst) {
-            if (slices_to_node(ss, tx, rcv, nb, host_frames.data(), host_shown.data())) return 1;
+            if (slices_to_node(ss, tx, rcv, nb, host_frames.data(), host_shown.data(), true)) return 1;
         } else {
-            if (!ss.send(tx.bytes.data(), rcv.rx.data(), tx.cb) || rcv.walk(0, tx.cb, 0, S)) return 1;
+            if (!ss.send_records(tx.bytes.data(), rcv.rx.data(), tx.cb, S) || rcv.walk(0, tx.cb, 0, S)) return 1;
             for (int s = 0; s < S; s++)
                 if (host_apply(&host_frames[(size_t)s * n], n, rcv.rx.data(), rcv.at.data(), s)) return 1;
             host_shown = host_frames;
@@ -776,7 +849,7 @@ static int run_multi_burst(int w, int h, int T, int S, int K) {
         // ---- the sockets: camera s's slice [pos[s * nb], pos[(s + 1) * nb]) is one write
         for (int s = 0; s < S; s++) {
             const size_t a = (size_t)tx.pos[(size_t)s * nb], b = (size_t)tx.pos[(size_t)(s + 1) * nb];
-            if (!ss.send(tx.bytes.data() + a, burst.data() + a, b - a)) return 1;
+            if (!ss.send_records(tx.bytes.data() + a, burst.data() + a, b - a, nb)) return 1;
         }
         sent_bytes += tx.cb;
         // ---- receiver: the records of every socket, found from their headers
@@ -1001,7 +1074,7 @@ static int run_multi_burst_coalesce(int w, int h, int T, int S, int K) {
         OK(mi355_download(relay.core, fwd.data(), d_fwd, fb));
         kept += roff[S];
         // ---- the sockets out of the relay, one record per camera; the receiver finds them from their headers
-        if (!ss.send(fwd.data(), rcv.rx.data(), fb)) return 1;
+        if (!ss.send_records(fwd.data(), rcv.rx.data(), fb, S)) return 1;
         forwarded += fb;
         if (rcv.walk(0, fb, 0, S)) return 1;
         // ---- receiver: one call per burst
@@ -1407,6 +1480,8 @@ static int run_multi_mosaic(int w, int h, int T, int S, int K, int C, int R) {
     Session ss(w, h);
     const size_t n = ss.n, nc = n * C * R;
     const int cw = C * w, ch = R * h;
+    ss.runs.w = cw;   // (--runs: the records that cross the link are the canvas')
+    ss.runs.h = ch;
     Cameras cams(S, w, h);
     Sender tx;
     Receiver relay;
@@ -1450,7 +1525,7 @@ static int run_multi_mosaic(int w, int h, int T, int S, int K, int C, int R) {
         OK(mi355_download(relay.core, fwd.data(), d_fwd, fb));
         kept += roff[1];
         // ---- the ONE socket out of the relay; the viewer reads the header and applies the record to its canvas
-        if (!ss.send(fwd.data(), rx.data(), fb)) return 1;
+        if (!ss.send_records(fwd.data(), rx.data(), fb, 1)) return 1;
         forwarded += fb;
         uint32_t cnt, esc;
         size_t at[2];
@@ -1674,7 +1749,7 @@ static int run_multi_resync(int w, int h, int T, int S, int R, int K, int wall_k
         cams.fill(tx.frames.data(), t0, nb);
         // ---- server: nb ticks of S cameras; the sockets; the records of every socket, found from their headers
         if (tx.step(nb, K != 1)) return 1;
-        if (!ss.send(tx.bytes.data(), burst.data(), tx.cb)) return 1;
+        if (!ss.send_records(tx.bytes.data(), burst.data(), tx.cb, S * nb)) return 1;
         sent_bytes += tx.cb;
         if (walk_records(burst.data(), 0, tx.cb, S * nb, b_counts.data(), b_escapes.data(), b_at.data())) return 1;
         // ---- client: tick k = record (s, k) of every s back to back, one upload, one call
@@ -1722,7 +1797,7 @@ static int run_multi_resync(int w, int h, int T, int S, int R, int K, int wall_k
         if (refresh_bytes > rcv.cap) { fprintf(stderr, "refresh stream larger than its bound\n"); return 1; }
         OK(mi355_download(tx.core, tx.bytes.data(), d_rcw, refresh_bytes));
         if (!ss.send(mask.data(), mask_rx.data(), mask_bytes)) return 1;
-        if (!ss.send(tx.bytes.data(), rcv.rx.data(), refresh_bytes)) return 1;
+        if (!ss.send_records(tx.bytes.data(), rcv.rx.data(), refresh_bytes, S)) return 1;
         // ---- client: clear, then apply like any other records; a host client does the same beside it
         if (rcv.walk(0, refresh_bytes, 0, S)) return 1;
         host_client = rcv.states;
@@ -1924,7 +1999,7 @@ int main(int argc, char **argv) {
     bool compact = false, direct = false, gpu_client = false, burst_client = false, coalesce = false, per_frame = false, check = false;
     const struct { const char *name; bool *on; } flags[] = {
         {"--compact", &compact}, {"--direct", &direct}, {"--gpu-client", &gpu_client}, {"--burst-client", &burst_client},
-        {"--coalesce", &coalesce}, {"--per-frame", &per_frame}, {"--check", &check}};
+        {"--coalesce", &coalesce}, {"--per-frame", &per_frame}, {"--check", &check}, {"--runs", &g_runs}};
     const long any = INT32_MIN;   // (no least value)
     const struct { const char *name; long *value, least, below; } valued[] = {   // a value below `least` is taken as `below`
         {"--width", &w, any, 0}, {"--height", &h, any, 0}, {"--frames", &T, any, 0}, {"--batch", &B, any, 0}, {"--multi", &multi, any, 0},
@@ -2009,6 +2084,8 @@ int main(int argc, char **argv) {
             return usage("--thumb K needs 1 <= K <= 16 and --compact --multi S, alone or with --burst T");
         if (thumb_drop < -1 || thumb_drop >= T) return usage("--thumb-drop TICK needs --thumb K and 0 <= TICK < --frames");
     }
+    if (g_runs && (!compact || !multi || datagram >= 0 || cropped || budget >= 0 || thumb || per_frame))
+        return usage("--runs needs --compact --multi S, alone or with --burst K [--burst-client | --coalesce], --mosaic CxR or --resync K; not with --datagram");
     if (per_frame) {
         if (!compact || direct || gpu_client || multi) return usage("--per-frame needs --compact alone");
         return run_per_frame(w, h, T);
