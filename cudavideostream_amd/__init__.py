@@ -8,6 +8,7 @@ path of MatteoBattilana/CUDAVideoStream behind the reference's own CUDACore call
 """
 from .core import CHARS_STR, LR_THRESHOLDS, CUDACore, PinnedArray  # noqa: F401
 from .core import activity_cells, cwire_apply_host, cwire_budget_entries, cwire_bytes_max, cwire_frame_bytes  # noqa: F401
+from .core import cwire_despeckle_host  # noqa: F401
 from .core import cwire_check_host, state_digest_host, state_tiles, thumb_cwire_host, wall_thumb_size  # noqa: F401
 from .core import cwire_split_bytes_max, cwire_split_host, cwire_split_pieces_max  # noqa: F401
 from .core import cwire_fec_groups_max, cwire_fec_host, cwire_fec_repair_host  # noqa: F401

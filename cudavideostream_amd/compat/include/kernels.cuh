@@ -110,6 +110,14 @@ public:
     void budget_multi(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, void *d_states, size_t stride,
                       int nstreams, const uint32_t *budgets, void *d_thresholds, void *d_offsets, void *d_frame_pos,
                       void *d_cwire_out, size_t capacity_bytes);
+    // The second lever, keyed on the neighbourhood (include/mi355diff.h, mi355_cwire_despeckle_cwire_batch): an entry of record s
+    // stays when at least need[s] (0 .. 8; 0: the record passes through) of the 8 pixels around its pixel changed too.  The kept
+    // entries go to d_cwire_out + d_frame_pos[s], the entries dropped per camera to d_dropped (uint32[nstreams]), and d_states +
+    // s*stride is taken back to the previous value where an entry was dropped.  Run it before budget_multi when both are wanted.
+    // All but counts / escapes / need in DEVICE memory.  Blocking.
+    void despeckle_multi(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, void *d_states, size_t stride,
+                         int nstreams, const uint32_t *need, void *d_dropped, void *d_offsets, void *d_frame_pos,
+                         void *d_cwire_out, size_t capacity_bytes);
     // Where the cameras move (include/mi355diff.h, mi355_cwire_activity_batch): from the nframes records of camera s, laid out
     // and described as for apply_multi_stream, a grid of changed bytes per cell of cell_w x cell_h pixels at d_cells
     // (uint32[nstreams][mi355_activity_cells(...)]) and eight words at d_summary (uint32[nstreams][8]): entries, box x0, y0, x1,

@@ -169,6 +169,14 @@ void CUDACore::mosaic_multi_stream(const void *d_cwire, const uint32_t *counts, 
     MI355_CHECK(mi355_synchronize(core_));
 }
 
+void CUDACore::despeckle_multi(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, void *d_states, size_t stride,
+                               int nstreams, const uint32_t *need, void *d_dropped, void *d_offsets, void *d_frame_pos,
+                               void *d_cwire_out, size_t capacity_bytes) {
+    MI355_CHECK(mi355_cwire_despeckle_cwire_batch(core_, d_cwire, counts, escapes, d_states, stride, nstreams, need, d_dropped, d_offsets,
+                                                  d_frame_pos, d_cwire_out, capacity_bytes));
+    MI355_CHECK(mi355_synchronize(core_));
+}
+
 void CUDACore::budget_multi(const void *d_cwire, const uint32_t *counts, const uint32_t *escapes, void *d_states, size_t stride,
                             int nstreams, const uint32_t *budgets, void *d_thresholds, void *d_offsets, void *d_frame_pos,
                             void *d_cwire_out, size_t capacity_bytes) {

@@ -511,6 +511,22 @@ class CUDACore:
                                                           _ptr(d_thresholds), _ptr(d_offsets), _ptr(d_frame_pos),
                                                           _ptr(d_cwire_out), int(capacity_bytes)))
 
+    # ... and its second lever: the records of one tick without their isolated changes
+    def cwire_despeckle_cwire_batch(self, d_cwire, counts, escapes, d_states, nstreams, need, d_dropped, d_offsets, d_frame_pos,
+                                    d_cwire_out, capacity_bytes, stride=None):
+        """The records diff_multi_cwire_batch just made (headers counts / escapes), despeckled: an entry of stream s stays when
+        at least need[s] (0 .. 8; 0: the stream passes through) of the 8 pixels around its pixel changed too.  The kept entries
+        go to d_cwire_out + d_frame_pos[s], the entries dropped per stream to d_dropped (uint32[nstreams]), and d_states[s] takes
+        the previous value at every dropped entry: records and states are those of a tick on frames without the speckle."""
+        self._hold(d_cwire, d_states, d_dropped, d_offsets, d_frame_pos, d_cwire_out)
+        stride = self.total if stride is None else stride
+        counts, escapes = _headers(counts, escapes, nstreams)
+        need = _table(need, 1, nstreams, np.uint32)
+        _l.check(self._lib.mi355_cwire_despeckle_cwire_batch(self._h, _ptr(d_cwire), counts.ctypes.data, escapes.ctypes.data,
+                                                             _ptr(d_states), int(stride), int(nstreams), need.ctypes.data,
+                                                             _ptr(d_dropped), _ptr(d_offsets), _ptr(d_frame_pos),
+                                                             _ptr(d_cwire_out), int(capacity_bytes)))
+
     # ... and what any of these nodes can ask about a camera: is it moving, and where
     def activity_batch(self, d_offsets, d_xs, nstreams, nframes, cell_w, cell_h, d_cells, d_summary, min_count=1,
                        accumulate=False):
@@ -912,6 +928,34 @@ def cwire_check_host(buf, counts, escapes, frame_bytes):
     _l.check(L.mi355_cwire_check_host(int(frame_bytes), buf.ctypes.data, buf.size, counts.ctypes.data, escapes.ctypes.data,
                                       counts.size, verdicts.ctypes.data))
     return verdicts
+
+
+def cwire_despeckle_host(width, height, buf, counts, escapes, states, need, stride=None, capacity_bytes=None):
+    """cwire_despeckle_cwire_batch computed on the host (no GPU, no core) and its definition: (dropped uint32[nstreams], offsets
+    uint32[nstreams + 1], frame_pos uint64[nstreams + 1], out uint8[capacity_bytes]) for the records of `buf` that the headers
+    counts / escapes describe.  `states` (uint8, nstreams states `stride` bytes apart) is reverted in place at the dropped
+    entries.  The capacity defaults to cwire_bytes_max, which always suffices."""
+    L = _l.load()
+    buf = _as_bytes(buf)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    escapes = np.ascontiguousarray(escapes, dtype=np.uint32)
+    need = np.ascontiguousarray(need, dtype=np.uint32)
+    nstreams = counts.size
+    assert escapes.size == nstreams and need.size == nstreams
+    assert isinstance(states, np.ndarray) and states.dtype == np.uint8 and states.flags.c_contiguous
+    n = 3 * int(width) * int(height)
+    stride = n if stride is None else int(stride)
+    assert nstreams == 0 or stride < n or states.size >= (nstreams - 1) * stride + n
+    if capacity_bytes is None:
+        capacity_bytes = L.mi355_cwire_bytes_max(n, nstreams)
+    dropped = np.zeros(nstreams, np.uint32)
+    offsets = np.zeros(nstreams + 1, np.uint32)
+    frame_pos = np.zeros(nstreams + 1, np.uint64)
+    out = np.zeros(max(int(capacity_bytes), 1), np.uint8)
+    _l.check(L.mi355_cwire_despeckle_host(int(width), int(height), buf.ctypes.data, buf.size, counts.ctypes.data, escapes.ctypes.data,
+                                          states.ctypes.data, stride, nstreams, need.ctypes.data, dropped.ctypes.data,
+                                          offsets.ctypes.data, frame_pos.ctypes.data, out.ctypes.data, int(capacity_bytes)))
+    return dropped, offsets, frame_pos, out[:int(capacity_bytes)]
 
 
 def cwire_split_pieces_max(n, e, max_bytes):

@@ -99,6 +99,8 @@ struct mi355_core {
     CwrRecord *cwr_rtab = nullptr;  // mi355_cwire_runs_decode_batch (stream_ops.hip): [T] records of a call,
     uint2 *cwr_chunk = nullptr;     // [T * cwr_chunks_max(N)] one word per workgroup
     uint32_t *cwb_hist = nullptr;   // mi355_cwire_budget_cwire_batch: [T][kCwbWords] bins of |cur - prev|, budget and threshold per stream
+    // mi355_cwire_despeckle_cwire_batch (made on first use, need_despeckle): [2][T][dsp_words(N)] pixel bitmaps, changed then keep
+    uint32_t *dsp_bits = nullptr;
     uint8_t *gray1 = nullptr;      // fused gray+binarize chain: one gray byte per pixel of a batch, made on first use
     size_t gray1_stride = 0;
     float *k9 = nullptr;
@@ -715,7 +717,7 @@ void mi355_destroy(mi355_core *c) {
     }
     void *ptrs[] = {c->state, c->in, c->aux, c->vis, c->rec, c->codes, c->meta, c->groff, c->totals, c->offsets, c->one_xs, c->one_diff, c->hist, c->thr, c->k9,
                     c->lut, c->glyphs, c->kxk, c->gray1, c->red_bounds, c->cw_cnt, c->cw_items, c->cw_esc,
-                    c->cwa_ftab, c->cwa_chunk, c->cwa_dir, c->cwb_hist, c->cws_blk, c->cws_base, c->cwr_rtab, c->cwr_chunk, c->cw_rec, c->cw_rec_pos};
+                    c->cwa_ftab, c->cwa_chunk, c->cwa_dir, c->cwb_hist, c->cws_blk, c->cws_base, c->cwr_rtab, c->cwr_chunk, c->cw_rec, c->cw_rec_pos, c->dsp_bits};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (c->h_count) (void)hipHostFree(c->h_count);
     if (c->h_rec) (void)hipHostFree(c->h_rec);
@@ -726,10 +728,11 @@ void mi355_destroy(mi355_core *c) {
 
 static int warm_exec(mi355_core *c);   // below, beside mi355_exec
 static int need_exec_cwire(mi355_core *c);   // below, beside mi355_exec_cwire
+static int need_despeckle(mi355_core *c);    // below, beside mi355_cwire_despeckle_cwire_batch
 
 int mi355_prepare(mi355_core *c, unsigned what) {
     if (!c) return fail(MI355_ERR_INVALID, "null core");
-    if (what & ~(MI355_PREPARE_ALL | MI355_PREPARE_EXEC_CWIRE)) return fail(MI355_ERR_INVALID, "mi355_prepare: unknown bit in `what`");
+    if (what & ~(MI355_PREPARE_ALL | MI355_PREPARE_EXEC_CWIRE | MI355_PREPARE_DESPECKLE)) return fail(MI355_ERR_INVALID, "mi355_prepare: unknown bit in `what`");
     if (int rc = use_device(c)) return rc;
     if ((what & MI355_PREPARE_BATCHES) && c->n > 0) {
         if (int rc = setup_pipeline(c)) return rc;   // (a core that cannot have its second set stays sequential: not an error)
@@ -744,6 +747,8 @@ int mi355_prepare(mi355_core *c, unsigned what) {
         if (int rc = warm_exec(c)) return rc;
     if (what & MI355_PREPARE_EXEC_CWIRE)
         if (int rc = need_exec_cwire(c)) return rc;
+    if (what & MI355_PREPARE_DESPECKLE)
+        if (int rc = need_despeckle(c)) return rc;
     HIP_TRY(hipDeviceSynchronize());   // the memsets of the new buffers
     return MI355_OK;
 }
@@ -1643,6 +1648,167 @@ int mi355_cwire_budget_cwire_batch(mi355_core *c, const void *d_cwire, const uin
     a.stride = stride_bytes;
     HIP_TRY(launch_cwire_budget(a, tab.fr.data(), nstreams, h_budget, (uint32_t)c->cfg.threshold, c->cwb_hist, (uint32_t *)d_thresholds,
                                 Produced::records(d_offsets, d_frame_pos, d_cwire_out, capacity_bytes), c->stream));
+    return MI355_OK;
+}
+
+// ---- mi355_cwire_despeckle_host / _cwire_batch: the records of one tick without their isolated changes ------------------------
+// The definition.  Everything is validated and decoded before anything is written.
+int mi355_cwire_despeckle_host(int width, int height, const void *cwire, size_t cwire_bytes, const uint32_t *h_counts,
+                               const uint32_t *h_escapes, uint8_t *states, size_t spacing_bytes, int nstreams, const uint32_t *h_need,
+                               uint32_t *dropped, uint32_t *offsets, uint64_t *frame_pos, void *cwire_out, size_t capacity_bytes) {
+    if (nstreams < 0) return fail(MI355_ERR_INVALID, "nstreams < 0");
+    if (width < 1 || height < 1) return fail(MI355_ERR_INVALID, "width or height < 1");
+    const uint64_t P = (uint64_t)width * (uint64_t)height, N = 3 * P;
+    if (N >= (1ull << 31)) return fail(MI355_ERR_INVALID, "frame of 2^31 bytes or more");
+    if (spacing_bytes < N) return fail(MI355_ERR_INVALID, "spacing_bytes (the stride of the states) < frame bytes");
+    if (nstreams > 0 && (!cwire || !h_counts || !h_escapes || !states || !h_need)) return fail(MI355_ERR_INVALID, "null input pointer");
+    if (nstreams > 0 && (!dropped || !offsets || !frame_pos || !cwire_out)) return fail(MI355_ERR_INVALID, "null output pointer");
+    const uint8_t *p = (const uint8_t *)cwire;
+    std::vector<std::vector<uint32_t>> xs((size_t)nstreams);
+    std::vector<std::vector<uint8_t>> ds((size_t)nstreams);
+    char msg[160];
+    uint64_t at = 0;
+    for (int s = 0; s < nstreams; s++) {
+        const uint32_t n = h_counts[s], e = h_escapes[s];
+        if (h_need[s] > 8) {
+            snprintf(msg, sizeof msg, "stream %d: need %u > 8", s, h_need[s]);
+            return fail(MI355_ERR_INVALID, msg);
+        }
+        if (n > N) {
+            snprintf(msg, sizeof msg, "compact stream: record %d: %u entries > frame bytes", s, n);
+            return fail(MI355_ERR_INVALID, msg);
+        }
+        if (e > n) {
+            snprintf(msg, sizeof msg, "compact stream: record %d: %u escapes > %u entries", s, e, n);
+            return fail(MI355_ERR_INVALID, msg);
+        }
+        const uint64_t rec = cwire_record_bytes(n, e);
+        if (at > cwire_bytes || cwire_bytes - at < rec) {
+            snprintf(msg, sizeof msg, "compact stream: record %d: truncated record", s);
+            return fail(MI355_ERR_INVALID, msg);
+        }
+        const CwireSections<const uint8_t> sec(p, at, n, e);
+        uint32_t n255 = 0;
+        for (uint32_t k = 0; k < n; k++) n255 += sec.code[k] == 255;
+        if (n255 != e) {
+            snprintf(msg, sizeof msg, "compact stream: record %d: %u escape codes, header says %u", s, n255, e);
+            return fail(MI355_ERR_INVALID, msg);
+        }
+        uint64_t x = 0;   // running index + 1 (64-bit: escape values cannot wrap it)
+        for (uint32_t k = 0, r = 0; k < n; k++) {
+            uint32_t g = sec.code[k];
+            if (g == 255) memcpy(&g, sec.esc + 4 * (size_t)r++, 4);
+            x += (uint64_t)g + 1;
+            if (x > N) {
+                snprintf(msg, sizeof msg, "compact stream: record %d: entry %u decodes to an index >= frame bytes", s, k);
+                return fail(MI355_ERR_INVALID, msg);
+            }
+            if (sec.diff[k]) {   // (a zero difference is no entry)
+                xs[s].push_back((uint32_t)(x - 1));
+                ds[s].push_back(sec.diff[k]);
+            }
+        }
+        at += rec;
+    }
+    // which entries stay: the changed pixels around the entry's pixel, counted on a map with a border of one pixel
+    const size_t bw = (size_t)width + 2;
+    std::vector<uint8_t> changed;
+    uint8_t *out = (uint8_t *)cwire_out;
+    uint32_t first = 0;
+    uint64_t pos = 0;
+    for (int s = 0; s < nstreams; s++) {
+        const uint32_t need = h_need[s];
+        std::vector<uint32_t> &x = xs[s];
+        std::vector<uint8_t> &d = ds[s];
+        size_t kept = x.size();
+        if (need) {
+            changed.assign(bw * ((size_t)height + 2), 0);
+            const auto cell = [&](uint32_t xi) { return ((size_t)(xi / 3) / width + 1) * bw + (xi / 3) % width + 1; };
+            for (uint32_t xi : x) changed[cell(xi)] = 1;
+            uint8_t *state = states + (size_t)s * spacing_bytes;
+            kept = 0;
+            for (size_t k = 0; k < x.size(); k++) {
+                const uint8_t *m = &changed[cell(x[k])], *up = m - bw, *down = m + bw;
+                const uint32_t c = up[-1] + up[0] + up[1] + m[-1] + m[1] + down[-1] + down[0] + down[1];
+                if (c >= need) {
+                    x[kept] = x[k];
+                    d[kept++] = d[k];
+                } else {
+                    state[x[k]] = (uint8_t)(state[x[k]] - d[k]);   // the value before the tick
+                }
+            }
+        }
+        dropped[s] = (uint32_t)(x.size() - kept);
+        uint32_t e = 0, end = 0;
+        for (size_t k = 0; k < kept; k++) {
+            e += x[k] - end >= 255u;
+            end = x[k] + 1u;
+        }
+        const uint32_t n = (uint32_t)kept;
+        const uint64_t rec = cwire_record_bytes(n, e);
+        offsets[s] = first;
+        frame_pos[s] = pos;
+        if (pos + rec <= capacity_bytes) {   // (a record that does not fit is skipped whole)
+            memset(out + pos, 0, rec);
+            memcpy(out + pos, &n, 4);
+            memcpy(out + pos + 4, &e, 4);
+            const CwireSections<uint8_t> sec(out, pos, n, e);
+            end = 0;
+            for (uint32_t k = 0, r = 0; k < n; k++) {
+                const uint32_t g = x[k] - end;
+                sec.code[k] = (uint8_t)(g < 255u ? g : 255u);
+                if (g >= 255u) memcpy(sec.esc + 4 * (size_t)r++, &g, 4);
+                sec.diff[k] = d[k];
+                end = x[k] + 1u;
+            }
+        }
+        first += n;
+        pos += rec;
+    }
+    if (offsets) offsets[nstreams] = first;
+    if (frame_pos) frame_pos[nstreams] = pos;
+    return MI355_OK;
+}
+
+// The pixel bitmaps (changed, keep; max_batch streams each) of the despeckle call: made when first needed, or by
+// mi355_prepare(MI355_PREPARE_DESPECKLE) -- 133 MB at 1080p with max_batch 256, so not every core carries them.
+static int need_despeckle(mi355_core *c) {
+    if (c->dsp_bits || c->n == 0) return MI355_OK;
+    const size_t words = 2 * (size_t)c->cfg.max_batch * dsp_words(c->n);
+    if (int rc = dev_alloc(c, &c->dsp_bits, words)) return rc;
+    HIP_TRY(hipMemsetAsync(c->dsp_bits, 0, words * sizeof(uint32_t), c->stream));
+    return MI355_OK;
+}
+
+int mi355_cwire_despeckle_cwire_batch(mi355_core *c, const void *d_cwire_in, const uint32_t *h_counts, const uint32_t *h_escapes,
+                                      void *d_states, size_t spacing_bytes, int nstreams, const uint32_t *h_need, void *d_dropped,
+                                      void *d_offsets, void *d_frame_pos, void *d_cwire_out, size_t capacity_bytes) {
+    if (!c) return fail(MI355_ERR_INVALID, "null core");
+    if (nstreams < 0 || nstreams > c->cfg.max_batch) return fail(MI355_ERR_INVALID, "nstreams outside [0, max_batch]");
+    if (((uintptr_t)d_cwire_in & 3u) || ((uintptr_t)d_cwire_out & 3u) || ((uintptr_t)d_offsets & 3u) || ((uintptr_t)d_dropped & 3u))
+        return fail(MI355_ERR_INVALID, "d_cwire_in, d_cwire_out, d_offsets and d_dropped must be 4-byte aligned");
+    if ((uintptr_t)d_frame_pos & 7u) return fail(MI355_ERR_INVALID, "d_frame_pos must be 8-byte aligned");
+    if (nstreams == 0) return write_empty_heads(c, d_offsets, d_frame_pos);
+    if (!d_cwire_in || !h_counts || !h_escapes || !d_states || !h_need) return fail(MI355_ERR_INVALID, "null input pointer");
+    if (!d_dropped || !d_offsets || !d_frame_pos || !d_cwire_out) return fail(MI355_ERR_INVALID, "null output pointer");
+    if (spacing_bytes < c->n) return fail(MI355_ERR_INVALID, "spacing_bytes (the stride of the states) < frame bytes");
+    for (int s = 0; s < nstreams; s++)
+        if (h_need[s] > 8) return fail(MI355_ERR_INVALID, "h_need above 8");
+    CwaTable tab;
+    if (int rc = cwa_table(c, h_counts, h_escapes, nstreams, &tab)) return rc;
+    const Region in = input_region(d_cwire_in, tab.bytes), st = states_region(c, d_states, spacing_bytes, nstreams);
+    if (overlap(st, in)) return overlap_fail(st, in);
+    if (int rc = check_regions({in, st}, {offsets_region(d_offsets, nstreams), Region{d_dropped, (uint64_t)nstreams * sizeof(uint32_t), "d_dropped"},
+                                          frame_pos_region(d_frame_pos, nstreams), Region{d_cwire_out, capacity_bytes, "d_cwire_out"}}))
+        return rc;
+    if (int rc = use_device(c)) return rc;
+    if (int rc = need_despeckle(c)) return rc;
+    CwaArgs a = cwa_args(c, d_cwire_in);
+    a.state = (uint8_t *)d_states;
+    a.stride = spacing_bytes;
+    uint32_t *changed = c->dsp_bits, *keep = changed + (size_t)c->cfg.max_batch * dsp_words(c->n);
+    HIP_TRY(launch_cwire_despeckle(a, tab.fr.data(), nstreams, h_need, (uint32_t)c->cfg.width, c->cwb_hist, changed, keep, (uint32_t *)d_dropped,
+                                   Produced::records(d_offsets, d_frame_pos, d_cwire_out, capacity_bytes), c->stream));
     return MI355_OK;
 }
 

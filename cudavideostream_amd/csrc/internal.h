@@ -224,6 +224,19 @@ struct CwbInitArgs {
 };
 hipError_t launch_cwire_budget(const CwaArgs &a, const CwaFrame *records, int nstreams, const uint32_t *budget, uint32_t thr0,
                                uint32_t *hist, uint32_t *thresholds, const CwcOut &o, hipStream_t s);
+// mi355_cwire_despeckle_cwire_batch: record s without the entries of the pixels that have fewer than need[s] (host array, 0 .. 8; 0:
+// not filtered) changed pixels among the 8 around them, a.state + s*a.stride reverted at the dropped entries.  words: the budget
+// call's per-stream rows, of which a stream's first is written (need); changed / keep: dsp_words(a.n) words per stream each (scratch
+// of the core, one bit per pixel); dropped (uint32 per stream) and o: the caller's.  a.out unused, a.chunk doubles as the facts.
+constexpr int kDspInitStreams = 128;   // needs per k_dsp_init launch (kernel arguments)
+struct DspInitArgs {
+    int32_t first;
+    uint32_t need[kDspInitStreams];
+};
+uint32_t dsp_words(uint32_t nbytes);   // 32-bit words of a stream's pixel bitmap
+hipError_t launch_cwire_despeckle(const CwaArgs &a, const CwaFrame *records, int nstreams, const uint32_t *need, uint32_t width,
+                                  uint32_t *words, uint32_t *changed, uint32_t *keep, uint32_t *dropped, const CwcOut &o,
+                                  hipStream_t s);
 // mi355_(cwire_)activity_batch: per stream, a grid of counts of the entries of its nframes records (batch index s*nframes + t)
 // per cell of cell_w x cell_h pixels, and 8 summary words (include/mi355diff.h).  Divisors travel with floor(2^32 / d).
 struct ActDiv {

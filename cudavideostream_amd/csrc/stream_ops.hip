@@ -15,6 +15,8 @@
 //                           alone (mi355_cwire_coalesce_batch / _cwire_batch);
 //   k_cwb_*               : one record per stream thinned to an entry budget, the caller's states reverted where entries are
 //                           dropped (mi355_cwire_budget_cwire_batch);
+//   k_dsp_*               : one record per stream without the entries of isolated pixels (fewer than `need` changed pixels among
+//                           the 8 around them), the caller's states reverted there (mi355_cwire_despeckle_cwire_batch);
 //   k_crop_*              : a stream's coalesced records cut to a rectangle and re-indexed to the rectangle's frame
 //                           (mi355_cwire_crop_batch / _cwire_batch);
 //   k_mosaic_*            : the coalesced records of many streams placed side by side into ONE record of a canvas frame
@@ -1621,6 +1623,236 @@ __global__ __launch_bounds__(256) void k_act_summary(const uint32_t *cells, uint
     }
 }
 
+// ---- mi355_cwire_despeckle_cwire_batch: record s of a tick without its isolated changes, the caller's state s reverted there ----
+// A pixel is changed when record s holds an entry (nonzero difference, index < N) in one of its three bytes; an entry stays when at
+// least need[s] of the 8 pixels around its pixel (inside the frame) changed too.  The budget call with the histogram replaced by
+// two bitmaps of one bit per pixel (changed, keep: g.words words per stream each, scratch of the core made on first use).  The
+// per-stream word (need) lies in the budget call's rows, as the crop's words do.  Behind the directory of the nstreams records:
+//   k_dsp_init  (grid: streams x blocks)          : need -> the stream's row, dropped[s] = 0, the changed bitmap of the streams
+//                                                   that are filtered (need != 0) zeroed: nothing of an earlier call is seen
+//   k_dsp_mark  (grid: tiles x streams, one wave) : filtered streams only; a tile no entry lands in returns on its directory
+//                                                   word.  The tile of differences in LDS (cwc_sum_tile, one record), its changed
+//                                                   pixels as bits of at most 44 words in LDS, then ONE global atomic OR per
+//                                                   nonzero word: a pixel or a word at a tile's end is shared with the next tile
+//   k_dsp_keep  (grid: words x streams)           : a lane per 32 pixels, the bitmap alone: keep = changed & (neighbours >= need),
+//                                                   the eight neighbour bitmaps by bit shifts of the changed bitmap (distance 1 and
+//                                                   width -1, 0, +1; left / right masked in the first / last column), added bit-
+//                                                   parallel into four planes and compared with need.  Every word of the keep
+//                                                   bitmap of a filtered stream is written.  N/24 bytes read and written per
+//                                                   filtered stream: the only cost of the call that follows N and not the entries
+//   k_dsp_facts (grid: tiles x streams, one wave) : k_cwc_sum on the tile with the entries of the pixels not kept zeroed; the
+//                                                   dropped entries counted, ONE atomic per tile that drops any
+//   k_cwc_scan, k_cwc_place                       : the coalescer's, unchanged
+//   k_dsp_emit  (grid: tiles x streams, one wave) : the filtered tile again, from the same bytes; state[x] -= d at the dropped
+//                                                   entries, one byte load and one byte store by the lane that owns the byte (the
+//                                                   state is touched nowhere else, not even read), also where the record is skipped
+//                                                   for lack of room; then k_cwc_emit's tile
+// A stream with need == 0 is not filtered: its state and the bitmaps are not touched.  Malformed content: both tile passes filter
+// the same tile by the same keep words, so the facts and the record agree; an index >= N and a bad escape contribute nothing.
+constexpr uint32_t kDspTileWords = 48;   // bitmap words a tile's pixels span: at most 1367 pixels from bit <= 31 on, 44 words
+
+__global__ __launch_bounds__(256) void k_dsp_init(uint32_t *words, uint32_t *dropped, uint32_t *changed, uint32_t nwords,
+                                                  const DspInitArgs h) {
+    const uint32_t st = (uint32_t)h.first + blockIdx.x, need = h.need[blockIdx.x];
+    if (blockIdx.y == 0 && threadIdx.x == 0) {
+        words[(size_t)st * kCwbWords] = need;
+        dropped[st] = 0u;
+    }
+    if (!need) return;
+    uint32_t *bm = changed + (size_t)st * nwords;
+    for (uint32_t i = blockIdx.y * 256u + threadIdx.x; i < nwords; i += gridDim.y * 256u) bm[i] = 0u;
+}
+
+__global__ __launch_bounds__(64) void k_dsp_mark(const CwaArgs a, const uint32_t *words, uint32_t *changed, uint32_t nwords) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
+    __shared__ uint32_t s_bits[kDspTileWords];
+    uint8_t *s = (uint8_t *)s_q;
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
+    if (!words[(size_t)st * kCwbWords]) return;
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    if (!cwc_sum_tile(s, a, 1, st, tile, lo, lo + len, lane)) return;
+    if ((uint32_t)lane < kDspTileWords) s_bits[lane] = 0u;
+    __syncthreads();
+    const uint32_t wb = lo / 96u;   // the word of the tile's first pixel
+    const uint32_t *w = (const uint32_t *)s + 16 * lane;
+    uint32_t at = 0, acc = 0;       // the lane's pixels lie in at most two words: one LDS atomic each
+    for (int i = 0; i < 16; i++) {
+        const uint32_t v = w[i];
+        if (!v) continue;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (!((v >> (8 * j)) & 255u)) continue;
+            const uint32_t p = (lo + 64u * lane + 4u * i + j) / 3u, wi = p / 32u - wb;
+            if (wi != at) {
+                if (acc) atomicOr(s_bits + at, acc);
+                at = wi;
+                acc = 0;
+            }
+            acc |= 1u << (p & 31u);
+        }
+    }
+    if (acc) atomicOr(s_bits + at, acc);
+    __syncthreads();
+    if ((uint32_t)lane < kDspTileWords && wb + lane < nwords) {
+        const uint32_t v = s_bits[lane];
+        if (v) atomicOr(changed + (size_t)st * nwords + wb + lane, v);
+    }
+}
+
+// Bits [32*i + k, 32*i + k + 32) of the bitmap b of nwords words, as one word; bits outside the bitmap are 0
+__device__ __forceinline__ uint32_t dsp_bits_at(const uint32_t *b, uint32_t nwords, uint32_t i, int64_t k) {
+    const int64_t q = 32 * (int64_t)i + k;
+    const int64_t j = q >> 5;   // floor, also below 0
+    const uint32_t r = (uint32_t)(q & 31);
+    const uint32_t lo = j >= 0 && j < (int64_t)nwords ? b[j] : 0u;
+    if (!r) return lo;
+    const uint32_t hi = j + 1 >= 0 && j + 1 < (int64_t)nwords ? b[j + 1] : 0u;
+    return (lo >> r) | (hi << (32u - r));
+}
+
+// x + y + z of three planes of one-bit numbers: the sum's low plane, carry: its high plane
+__device__ __forceinline__ uint32_t dsp_add3(uint32_t x, uint32_t y, uint32_t z, uint32_t &carry) {
+    const uint32_t t = x ^ y;
+    carry = (x & y) | (z & t);
+    return t ^ z;
+}
+
+__global__ __launch_bounds__(256) void k_dsp_keep(const uint32_t *words, const uint32_t *changed, uint32_t *keep, uint32_t nwords,
+                                                  const ActDiv width) {
+    const uint32_t st = blockIdx.y, need = words[(size_t)st * kCwbWords];
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (!need || i >= nwords) return;
+    const uint32_t *b = changed + (size_t)st * nwords;
+    uint32_t *out = keep + (size_t)st * nwords;
+    const uint32_t c = b[i];
+    if (!c) {
+        out[i] = 0u;
+        return;
+    }
+    // the word's pixels in the first column (no left neighbours) and in the last (no right ones)
+    const uint32_t W = width.d, px0 = 32u * i - act_div(32u * i, width) * W;
+    uint32_t first = 0, last = 0;
+    for (uint32_t k = px0 ? W - px0 : 0u; k < 32u; k += W) first |= 1u << k;
+    for (uint32_t k = W - 1u - px0; k < 32u; k += W) last |= 1u << k;
+    const int64_t row = (int64_t)W;
+    const uint32_t n0 = dsp_bits_at(b, nwords, i, -row - 1) & ~first, n1 = dsp_bits_at(b, nwords, i, -row),
+                   n2 = dsp_bits_at(b, nwords, i, -row + 1) & ~last, n3 = dsp_bits_at(b, nwords, i, -1) & ~first,
+                   n4 = dsp_bits_at(b, nwords, i, 1) & ~last, n5 = dsp_bits_at(b, nwords, i, row - 1) & ~first,
+                   n6 = dsp_bits_at(b, nwords, i, row), n7 = dsp_bits_at(b, nwords, i, row + 1) & ~last;
+    // carry-save: the count of the eight, 0 .. 8, as the planes p3 p2 p1 p0
+    uint32_t c0, c1, c2, c3, d0, d1;
+    const uint32_t s0 = dsp_add3(n0, n1, n2, c0), s1 = dsp_add3(n3, n4, n5, c1), s2 = dsp_add3(n6, n7, 0u, c2);
+    const uint32_t p0 = dsp_add3(s0, s1, s2, c3);
+    const uint32_t t = dsp_add3(c0, c1, c2, d0);
+    const uint32_t p1 = dsp_add3(t, c3, 0u, d1);
+    const uint32_t p2 = d0 ^ d1, p3 = d0 & d1;
+    // count >= need, from the top plane down
+    const uint32_t plane[4] = {p0, p1, p2, p3};
+    uint32_t gt = 0, eq = ~0u;
+#pragma unroll
+    for (int k = 3; k >= 0; k--) {
+        const uint32_t nk = (need >> k) & 1u ? ~0u : 0u;
+        gt |= eq & plane[k] & ~nk;
+        eq &= ~(plane[k] ^ nk);
+    }
+    out[i] = c & (gt | eq);
+}
+
+// The keep words of the tile's pixels -> s_keep (kDspTileWords words; word 0 holds the pixel of byte lo)
+__device__ __forceinline__ void dsp_keep_load(uint32_t *s_keep, const uint32_t *keep, uint32_t nwords, uint32_t st, uint32_t lo, int lane) {
+    const uint32_t wb = lo / 96u;
+    if ((uint32_t)lane < kDspTileWords) s_keep[lane] = wb + lane < nwords ? keep[(size_t)st * nwords + wb + lane] : 0u;
+}
+
+// The lane's 64 bytes of the tile of differences s: the entries of the pixels not kept are zeroed and, REVERT, state[x] -= d is
+// stored to g (the tile's place in the state).  Returns the entries zeroed.
+template <bool REVERT>
+__device__ __forceinline__ uint32_t dsp_lane_bytes(uint8_t *s, const uint32_t *s_keep, uint32_t lo, uint8_t *g, int lane) {
+    uint32_t *w = (uint32_t *)s + 16 * lane;
+    const uint32_t wb = lo / 96u;
+    uint32_t gone = 0;
+    for (int i = 0; i < 16; i++) {
+        const uint32_t v = w[i];
+        if (!v) continue;
+        uint32_t keep = v;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const uint32_t d = (v >> (8 * j)) & 255u;
+            if (!d) continue;
+            const uint32_t at = 64u * lane + 4u * i + j, p = (lo + at) / 3u;
+            if ((s_keep[p / 32u - wb] >> (p & 31u)) & 1u) continue;
+            keep &= ~(255u << (8 * j));
+            gone++;
+            if (REVERT) g[at] = (uint8_t)(g[at] - d);
+        }
+        w[i] = keep;
+    }
+    return gone;
+}
+
+// The tile of stream st in LDS, filtered where `filter` says so; false: no entry of the record lands in the tile (s untouched).
+// gone: the entries the wave dropped.
+template <bool REVERT>
+__device__ __forceinline__ bool dsp_tile(uint8_t *s, uint32_t *s_keep, const CwaArgs &a, const uint32_t *keep, uint32_t nwords, bool filter,
+                                         uint32_t st, uint32_t tile, uint32_t lo, uint32_t len, int lane, uint32_t &gone) {
+    gone = 0;
+    if (!cwc_sum_tile(s, a, 1, st, tile, lo, lo + len, lane)) return false;
+    if (filter) {
+        dsp_keep_load(s_keep, keep, nwords, st, lo, lane);
+        __syncthreads();
+        gone = cwa_wave_sum(dsp_lane_bytes<REVERT>(s, s_keep, lo, a.state + (size_t)st * a.stride + lo, lane));
+        __syncthreads();
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(64) void k_dsp_facts(const CwaArgs a, const uint32_t *words, const uint32_t *keep, uint32_t nwords,
+                                                  uint32_t *dropped) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
+    __shared__ uint32_t s_keep[kDspTileWords];
+    uint8_t *s = (uint8_t *)s_q;
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
+    const bool filter = words[(size_t)st * kCwbWords] != 0u;
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    uint4 *fact = a.chunk + (size_t)st * a.ntiles + tile;
+    uint32_t gone;
+    if (!dsp_tile<false>(s, s_keep, a, keep, nwords, filter, st, tile, lo, len, lane, gone)) {
+        if (lane == 0) *fact = make_uint4(0u, 0u, 0u, 0u);
+        return;
+    }
+    const uint4 f = cwc_tile_facts(s, lo, lane);
+    if (lane == 0) {
+        *fact = f;
+        if (gone) atomicAdd(dropped + st, gone);
+    }
+}
+
+__global__ __launch_bounds__(64) void k_dsp_emit(const CwaArgs a, const CwcOut o, const uint32_t *words, const uint32_t *keep,
+                                                 uint32_t nwords) {
+    __shared__ cwa_u32x4 s_q[kCwaTile / 16];
+    __shared__ uint32_t s_keep[kDspTileWords];
+    __shared__ uint32_t s_code32[kCwaTile / 4 + 2], s_diff32[kCwaTile / 4 + 2];
+    uint8_t *s = (uint8_t *)s_q;
+    const int lane = threadIdx.x;
+    const uint32_t st = blockIdx.x / a.ntiles, tile = blockIdx.x % a.ntiles;
+    const bool filter = words[(size_t)st * kCwbWords] != 0u;
+    const uint4 fact = a.chunk[(size_t)st * a.ntiles + tile];   // {kept bytes, entries before, escapes before, end before}
+    const uint32_t seg = o.offsets[st], n = o.offsets[st + 1] - seg;
+    const uint64_t fp0 = o.frame_pos[st], fp1 = o.frame_pos[st + 1];
+    const bool write = fact.x != 0 && fp1 <= o.capacity;   // (a record that does not fit is skipped whole, by every workgroup alike)
+    if (!write && !filter) return;
+    const uint32_t lo = tile * kCwaTile;
+    const uint32_t len = a.n - lo < kCwaTile ? a.n - lo : kCwaTile;
+    uint32_t gone;
+    if (!dsp_tile<true>(s, s_keep, a, keep, nwords, filter, st, tile, lo, len, lane, gone)) return;
+    if (!write) return;
+    cwc_emit_tile<true>(s, (uint8_t *)s_code32, (uint8_t *)s_diff32, fact, o, seg, n, fp0, cwire_record_escapes(fp1 - fp0, n), lo, lane);
+}
+
 // ---- mi355_cwire_crop_(cwire_)batch: the coalesced records of stream s cut to its rectangle, re-indexed to the rectangle's frame -----
 // The coalescer with a filter on the tile, as the budget call is: behind the directory of the nstreams*nframes records
 //   k_crop_facts (grid: tiles x streams, one wave) : the rectangles {x0, y0, w, h} of its streams are kernel arguments (kCropStreams
@@ -3117,6 +3349,7 @@ __global__ __launch_bounds__(256) void k_cwr_expand(const CwrDecode d) {
 uint32_t cwa_chunks(uint32_t n) { return n ? (n + kCwaChunk - 1) / kCwaChunk : 1u; }
 uint32_t cwa_tiles(uint32_t nbytes) { return (nbytes + kCwaTile - 1) / kCwaTile; }
 uint32_t cwa_mask_words(uint32_t nbytes) { return (cwa_tiles(nbytes) + 31u) / 32u; }
+uint32_t dsp_words(uint32_t nbytes) { return (nbytes / 3u + 31u) / 32u; }
 
 // the n >= 1 records to the core's table (k_cwa_table, kCwaTableFrames per launch) -> their chunks (>= n: a record of no entries
 // has one empty chunk)
@@ -3309,6 +3542,39 @@ hipError_t launch_cwire_budget(const CwaArgs &a, const CwaFrame *records, int ns
     if (a.ntiles) hipLaunchKernelGGL(k_cwb_facts, tiles, dim3(64), 0, s, a, (const uint32_t *)hist, thr0);
     launch_cwc_tail(a, o, nstreams, true, s, [&](auto) {
         if (a.ntiles) hipLaunchKernelGGL(k_cwb_emit, tiles, dim3(64), 0, s, a, o, (const uint32_t *)hist, thr0);
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_cwire_despeckle(const CwaArgs &a, const CwaFrame *records, int nstreams, const uint32_t *need, uint32_t width,
+                                  uint32_t *words, uint32_t *changed, uint32_t *keep, uint32_t *dropped, const CwcOut &o,
+                                  hipStream_t s) {
+    if (nstreams <= 0) return hipSuccess;
+    const uint32_t nwords = dsp_words(a.n);
+    const uint32_t blocks = nwords / 4096u + 1u < 64u ? nwords / 4096u + 1u : 64u;   // 16 words or more a thread
+    DspInitArgs h{};
+    bool filter = false;
+    for (int s0 = 0; s0 < nstreams; s0 += kDspInitStreams) {
+        h.first = s0;
+        const int part = nstreams - s0 < kDspInitStreams ? nstreams - s0 : kDspInitStreams;
+        for (int j = 0; j < part; j++) {
+            h.need[j] = need[s0 + j];
+            filter = filter || need[s0 + j] != 0u;
+        }
+        hipLaunchKernelGGL(k_dsp_init, dim3(part, blocks), dim3(256), 0, s, words, dropped, changed, nwords, h);
+    }
+    const dim3 per_tile(a.ntiles * (uint32_t)nstreams), per_word((nwords + 255u) / 256u, (uint32_t)nstreams);
+    if (a.ntiles) {
+        launch_cwa_directory(a, records, nstreams, s);
+        if (filter) {
+            hipLaunchKernelGGL(k_dsp_mark, per_tile, dim3(64), 0, s, a, (const uint32_t *)words, changed, nwords);
+            hipLaunchKernelGGL(k_dsp_keep, per_word, dim3(256), 0, s, (const uint32_t *)words,
+                               (const uint32_t *)changed, keep, nwords, act_divisor(width));
+        }
+        hipLaunchKernelGGL(k_dsp_facts, per_tile, dim3(64), 0, s, a, (const uint32_t *)words, (const uint32_t *)keep, nwords, dropped);
+    }
+    launch_cwc_tail(a, o, nstreams, true, s, [&](auto) {
+        if (a.ntiles) hipLaunchKernelGGL(k_dsp_emit, per_tile, dim3(64), 0, s, a, o, (const uint32_t *)words, (const uint32_t *)keep, nwords);
     });
     return hipGetLastError();
 }

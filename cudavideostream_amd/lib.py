@@ -25,6 +25,7 @@ OPT_PIPELINE, OPT_MEDIAN_ROWS, OPT_SCAN_EPOCH_LEFT = 1, 6, 7   # MI355_OPT_* (id
 FLAG_OWN_QUEUES = 1   # MI355_FLAG_*
 PREPARE_BATCHES, PREPARE_GRAY_CHAIN, PREPARE_RED_CLEAR, PREPARE_CONV_KXK, PREPARE_EXEC, PREPARE_ALL = 1, 2, 4, 8, 16, 31   # MI355_PREPARE_*
 PREPARE_EXEC_CWIRE = 32   # (not part of PREPARE_ALL)
+PREPARE_DESPECKLE = 64    # (not part of PREPARE_ALL)
 CROP_KEEP_INDEX = 1   # MI355_CROP_*
 CWIRE_SPLIT_BLOCK = 65536   # MI355_CWIRE_SPLIT_BLOCK
 FEC_BAD_HEADER, FEC_BAD_TAIL = 1, 2   # MI355_FEC_BAD_*
@@ -114,6 +115,10 @@ SYMBOLS = {
     "mi355_cwire_budget_cwire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "mi355_cwire_budget_entries": (C.c_size_t, [C.c_size_t, C.c_size_t]),
+    "mi355_cwire_despeckle_host": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                             C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "mi355_cwire_despeckle_cwire_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "mi355_activity_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int,
                                        C.c_void_p, C.c_void_p]),
     "mi355_cwire_activity_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

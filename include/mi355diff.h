@@ -102,7 +102,8 @@ typedef struct mi355_config {
  *      + mi355_thumb_cwire_host, mi355_thumb_cwire_batch (additions only);
  *      + mi355_cwire_fec_* (additions only);
  *      + mi355_cwire_runs_frame_bytes, mi355_cwire_runs_bytes_max, mi355_cwire_runs_encode_host, mi355_cwire_runs_encode_batch,
- *      mi355_cwire_runs_decode_host, mi355_cwire_runs_decode_batch, MI355_RUNS_* (additions only) */
+ *      mi355_cwire_runs_decode_host, mi355_cwire_runs_decode_batch, MI355_RUNS_* (additions only);
+ *      + mi355_cwire_despeckle_host, mi355_cwire_despeckle_cwire_batch, MI355_PREPARE_DESPECKLE (additions only) */
 #define MI355_ABI_VERSION 10
 int mi355_abi_version(void);
 
@@ -134,6 +135,9 @@ size_t mi355_workspace_bytes(const mi355_core *core);
  *                              mi355_exec_cwire / mi355_pipe_submit_cwire, and one pass of their encode and export kernels on
  *                              an empty frame.  Not part of MI355_PREPARE_ALL: only a caller of the compact per-frame form
  *                              wants it, and asks for it by name.
+ *   MI355_PREPARE_DESPECKLE    the pixel bitmaps of mi355_cwire_despeckle_cwire_batch: 2 * max_batch * 4 * ceil(width*height / 32)
+ *                              bytes (133 MB at 1080p with max_batch 256).  Not part of MI355_PREPARE_ALL for that size: only
+ *                              a caller of that call wants them, and asks by name (or lets its first call make them).
  * mi355_create already makes the one a per-frame server needs (MI355_VIS_BINARIZE's gray bytes).  Blocking; idempotent;
  * mi355_workspace_bytes grows by what was made.  After mi355_prepare(core, MI355_PREPARE_ALL) no entry point of the core
  * allocates (mi355_pipe_open and mi355_set_glyphs, which say so, excepted -- and the first mi355_exec_cwire /
@@ -145,6 +149,7 @@ size_t mi355_workspace_bytes(const mi355_core *core);
 #define MI355_PREPARE_EXEC 16u
 #define MI355_PREPARE_ALL 31u
 #define MI355_PREPARE_EXEC_CWIRE 32u
+#define MI355_PREPARE_DESPECKLE 64u
 int mi355_prepare(mi355_core *core, unsigned what);
 
 /* Streams.  A core starts on a stream of its own, created hipStreamNonBlocking: it is NOT ordered against the
@@ -988,6 +993,77 @@ int mi355_cwire_budget_cwire_batch(mi355_core *core, const void *d_cwire, const 
  * the largest n <= frame_bytes with 8 + 2*pad4(n) + 4*min(n, frame_bytes/256) <= record_bytes (an escape spans at least 256
  * bytes of the frame), 0 when record_bytes < 8.  A sender turns its per-socket byte budget into h_budget[s] with it. */
 size_t mi355_cwire_budget_entries(size_t frame_bytes, size_t record_bytes);
+
+/* A tick without its speckle: the sender's second lever, keyed on the neighbourhood instead of the magnitude.  The nstreams compact
+ * records mi355_diff_multi_cwire_batch just wrote (placed by h_counts[s] / h_escapes[s]; the headers come from the host, as in
+ * mi355_cwire_budget_cwire_batch) and the caller's states as that tick left them -> records without the entries of isolated
+ * pixels (state s at states + s*spacing_bytes, the stride of the states as in the budget call).  What is not sent is not lost: the
+ * state goes back to the previous value there, so the change stays pending.  A
+ * sender that wants both runs this call first and the budget call on what is left.
+ *   Semantics, for stream s, frame width x height, P = width*height, N = 3P:
+ *   Changed pixel: pixel p is changed if record s holds an entry with index x < N, a nonzero diff byte and x / 3 == p (a zero
+ *   diff byte is no entry, as in the coalescer; records of this library hold none).
+ *   Neighbour count: c(p) = the changed pixels among (px + dx, py + dy), dx, dy in {-1, 0, 1} and not both 0, inside the frame,
+ *   with px = p % width and py = p / width.  Pixels outside the frame count 0; the other channels of p itself do not count.
+ *   Keep or drop: need = h_need[s], 0 .. 8.  0: the stream passes through byte for byte, its state is neither read nor written.
+ *   Otherwise an entry (x, d) is kept iff c(x / 3) >= need: all entries of a pixel share its fate.
+ *   Revert: for a dropped entry state[s][x] = (uint8)(state[s][x] - d), the value before the tick (the budget call's revert).
+ *   Outputs: record s at d_cwire_out + d_frame_pos[s] is the canonical encoding (ascending indices, pad bytes zero, header
+ *   written) of the kept entries; d_offsets, uint32[nstreams + 1], is the exclusive scan of the kept counts; d_frame_pos,
+ *   uint64[nstreams + 1], is always exact; d_dropped, uint32[nstreams], receives the entries dropped per stream.  Capacity rule
+ *   of the family: a record with d_frame_pos[s + 1] > capacity_bytes is skipped whole and later ones that fit are still written;
+ *   the states are reverted completely regardless; mi355_cwire_bytes_max(N, nstreams) always suffices.
+ *   Guarantees: (1) Equals a diff on blanked frames: with frames' = the tick's frames with every byte of every dropped pixel
+ *   replaced by the state byte before the tick, the records, offsets, frame positions and states are byte for byte what
+ *   mi355_diff_multi_cwire_batch leaves from frames' and the states before the tick: sender and receiver stay equal.  (2) A stream
+ *   with nothing to drop comes back byte for byte and its state is not written.  (3) Bytes of the states' region outside the N
+ *   bytes of each state are never written; state stores are single bytes.  (4) Malformed content under consistent headers gets
+ *   the budget call's promise: nothing is read outside the input span and the states, nothing is written outside the outputs
+ *   and the N bytes of each state, an index >= N and an escape ranked at or past e contribute nothing; only that stream's own
+ *   result is otherwise unspecified.  (5) No stale scratch: consecutive calls on one core are independent, whatever the earlier
+ *   call's nstreams, h_need or records were.
+ * mi355_cwire_despeckle_host is the definition: plain C++ on host memory, no core, no HIP call, no alignment requirement.  It
+ * validates every record as mi355_cwire_apply_host does and refuses with MI355_ERR_INVALID and a reason, before anything is
+ * written: a truncated record, n > N, e > n, a count of 255 codes that is not e, an index >= N; h_need[s] > 8; a null pointer
+ * with nstreams > 0; nstreams < 0; width < 1; height < 1; spacing_bytes < N.
+ * The batch form refuses with MI355_ERR_INVALID before anything is launched or written: a null core; nstreams outside
+ * [0, max_batch]; with nstreams > 0 a null pointer among the arguments; h_escapes[s] > h_counts[s]; h_counts[s] > N;
+ * h_need[s] > 8; spacing_bytes < N; d_cwire_in, d_cwire_out, d_offsets or d_dropped not 4-byte aligned; d_frame_pos not 8-byte
+ * aligned; the input span overlapping an output region or the states' region; an output region (offsets, dropped, frame_pos,
+ * [d_cwire_out, + capacity_bytes)) overlapping the states' region.  nstreams == 0 writes offsets[0] = 0 and frame_pos[0] = 0
+ * and nothing else.  Asynchronous on the core's stream, behind the last expansion of this core, so it may follow
+ * mi355_diff_multi_cwire_batch on one core without a synchronisation of the device work; a later tick on the same states sees
+ * every byte this call wrote.
+ * Scratch: two bitmaps of one bit per pixel and stream (changed, keep), 2 * max_batch * 4 * ceil(P / 32) bytes, made by the
+ * first call that needs them or by mi355_prepare(core, MI355_PREPARE_DESPECKLE) and counted by mi355_workspace_bytes from then
+ * on; after the prepare nothing is allocated inside the call.
+ * The directory kernels of mi355_apply_cwire_batch on the nstreams records, then, one wave per 4096-byte tile x stream and a
+ * tile no entry lands in returning on its directory word: the changed bitmap of the filtered streams zeroed; (1) the tile of
+ * differences rebuilt in LDS, its changed pixels OR-ed into the bitmap, one atomic per nonzero word; (2) a lane per 32 pixels
+ * on the bitmap alone: the eight neighbour bitmaps by bit shifts (distance 1 and width - 1, width, width + 1, the first and last
+ * column masked), added bit-parallel and compared with need -> the keep bitmap.  This pass reads and writes N/24 bytes per
+ * filtered stream and is the only cost of the call that follows N and not the entries; (3) the tile again with the entries of
+ * the pixels not kept zeroed -> the coalescer's facts, its scan and its placement, the dropped entries counted; (4) the same
+ * filtered tile from the same bytes, the dropped entries' state bytes reverted by single-byte loads and stores (the state is
+ * touched nowhere else; a tile of a record that is skipped for lack of room still reverts), the kept entries written as the
+ * coalescer writes them.
+ * Out of scope: the burst forms (frame t + 1 depends on how frame t was filtered); the per-frame host path; an arrays or
+ * plain-wire output; another neighbourhood than the 8 surrounding pixels; despeckle and budget in one call.
+ * Measured (profiles/multi_despeckle.json: tools/bench_multi.py --legs despeckle; microseconds per stream of this call at need = 3
+ * against mi355_cwire_budget_cwire_batch on the same records with budgets at half the counts; 1080p, S = 4, 16, 64, median of
+ * five rounds, spread 0.4 to 2.2 %, same run, same board): webcam-like input 52.9 / 38.5 / 28.5 against the budget call's 45.6 /
+ * 25.0 / 20.5, with 547 235 entries in and 56 455 out at S = 4 (bytes 1 105 716 -> 135 348), equal to the host form's; local input
+ * (nothing to drop) 22.2 / 7.7 / 4.0 against 23.7 / 9.0 / 5.1.  The expectation -- no slower than the budget call at any S by
+ * more than the rounds' spread plus the N/24 bitmap pass -- is MISSED on the webcam-like input (1.16x to 1.54x, where nine of ten
+ * entries are dropped and each costs a byte load and store to the state) and met on the local input.  DESIGN.md section 4,
+ * "Dropping isolated changes". */
+int mi355_cwire_despeckle_host(int width, int height, const void *cwire, size_t cwire_bytes, const uint32_t *h_counts,
+                               const uint32_t *h_escapes, uint8_t *states, size_t spacing_bytes, int nstreams,
+                               const uint32_t *h_need, uint32_t *dropped, uint32_t *offsets, uint64_t *frame_pos,
+                               void *cwire_out, size_t capacity_bytes);
+int mi355_cwire_despeckle_cwire_batch(mi355_core *core, const void *d_cwire_in, const uint32_t *h_counts, const uint32_t *h_escapes,
+                                      void *d_states, size_t spacing_bytes, int nstreams, const uint32_t *h_need, void *d_dropped,
+                                      void *d_offsets, void *d_frame_pos, void *d_cwire_out, size_t capacity_bytes);
 
 /* Where a camera moves: per stream, a grid of counts of its records' entries and a bounding box, made on the GPU from the records
  * a node already holds -- a recorder that keeps footage only while something moves, a wall that frames the active cameras, a

@@ -62,6 +62,16 @@ sender's rate control, in microseconds per stream, ONE JSON line for all S:
                re-diff a caller has without the call -- and it still lacks the threshold choice.
 Every pass of a timed window works on its own copy of the S states (restored outside the window).
 
+The despeckle leg (--legs despeckle, a run of its own: `--legs despeckle --streams 4,16,64 > profiles/multi_despeckle.json`)
+measures the sender's second lever on the records of one tick, in microseconds per stream, ONE JSON line for all S, on the
+webcam-like and the local input:
+  despeckle    mi355_cwire_despeckle_cwire_batch at need = 3 for every stream;
+  budget       mi355_cwire_budget_cwire_batch on the same records, every stream's budget at half of its count: the nearest
+               sibling (the same directory, three tile passes, a state tile read).
+The line carries entries and bytes in and out of both calls; on the webcam-like input the despeckle call's are compared with
+mi355_cwire_despeckle_host's.  The expectation to test: `despeckle` no slower than `budget` by more than the rounds' spread
+(judged strictly; `bitmap_pass_bytes_per_stream`, N/24, is the one cost the call has that follows N).
+
 The crop leg (--legs crop, a run of its own: `--legs crop --streams 4,16,64 > profiles/multi_crop.json`) measures the crop call on
 the records of one tick (T = 1), in microseconds per stream, ONE JSON line for all S, on the webcam-like and the local input:
   coalesce       mi355_cwire_coalesce_cwire_batch on the same records: the nearest route a relay has without the crop call;
@@ -1548,6 +1558,71 @@ def run_budget(W, H, rounds, S):
     return out
 
 
+def run_despeckle(W, H, rounds, S, kind):
+    """The despeckle leg for one S and one input -> its dictionary.  despeckle: mi355_cwire_despeckle_cwire_batch at need = 3 on
+    the records of one tick, on the states as the tick left them.  budget: mi355_cwire_budget_cwire_batch on the same records with
+    every stream's budget at half of its count -- the nearest sibling: the same directory, three tile passes, a state tile read.
+    Both on one core's own stream, alternating within every round; every pass of a timed window has its own copy of the states,
+    restored outside the window.  On the webcam-like input the entries and bytes out are compared with the host form's."""
+    import numpy as np
+    from cudavideostream_amd import CUDACore, cwire_bytes_max, cwire_despeckle_host, lib as _lib
+    dev = torch.device("cuda", 0)
+    n = 3 * W * H
+    passes = max(2, min(16, 128 // S))
+    pre, fwd = burst_input(kind, S, 1, W, H, dev)
+    post = pre.clone()
+    recs, counts, escapes, pos = one_call(sender_records(W, H, fwd, post))
+    del fwd
+    cwcap = cwire_bytes_max(n, S)
+    d_drop = torch.zeros(S, dtype=torch.int32, device=dev)
+    d_ooff = torch.zeros(S + 1, dtype=torch.int32, device=dev)
+    d_opos = torch.zeros(S + 1, dtype=torch.int64, device=dev)
+    d_out = torch.empty(cwcap, dtype=torch.uint8, device=dev)
+    d_thr, d_boff, d_bpos, d_bout = torch.zeros_like(d_drop), torch.zeros_like(d_ooff), torch.zeros_like(d_opos), torch.empty_like(d_out)
+    core = CUDACore(W, H, max_batch=S)
+    core.prepare(_lib.PREPARE_DESPECKLE)
+    need = np.full(S, 3, np.uint32)
+    budgets = (counts // 2).astype(np.uint32)
+    work = torch.empty(passes, S, n, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+
+    def leg_despeckle():
+        for p in range(passes):
+            core.cwire_despeckle_cwire_batch(recs, counts, escapes, work[p], S, need, d_drop, d_ooff, d_opos, d_out, cwcap)
+        core.synchronize()
+
+    def leg_budget():
+        for p in range(passes):
+            core.cwire_budget_cwire_batch(recs, counts, escapes, work[p], S, budgets, d_thr, d_boff, d_bpos, d_bout, cwcap)
+        core.synchronize()
+
+    times = time_legs({"despeckle": leg_despeckle, "budget": leg_budget}, rounds, passes * S,
+                      before=lambda name: work.copy_(post.unsqueeze(0).expand(passes, S, n)))
+    work[0].copy_(post)                    # once more outside the windows: the states the figures below are read from
+    torch.cuda.synchronize()
+    core.cwire_despeckle_cwire_batch(recs, counts, escapes, work[0], S, need, d_drop, d_ooff, d_opos, d_out, cwcap)
+    core.synchronize()
+    kept = np.diff(d_ooff.cpu().numpy().view(np.uint32).astype(np.int64))
+    dropped = d_drop.cpu().numpy().view(np.uint32).astype(np.int64)
+    out_bytes = int(d_opos[S].item())
+    assert np.array_equal(kept + dropped, counts.astype(np.int64))
+    out = {"input": kind, "streams": S, "passes": passes, "need": 3, "entries_in": int(counts.sum()), "entries_out": int(kept.sum()),
+           "bytes_in": int(pos[S]), "bytes_out": out_bytes, "budget_entries_out": int(np.diff(d_boff.cpu().numpy().view(np.uint32).astype(np.int64)).sum()),
+           "budget_bytes_out": int(d_bpos[S].item()), "bitmap_pass_bytes_per_stream": n // 24}
+    if kind == "webcam":   # the host form on the same records: entries, bytes and the records themselves
+        states = post.cpu().numpy()
+        h_drop, h_off, h_pos, h_out = cwire_despeckle_host(W, H, recs.cpu().numpy()[:int(pos[S])], counts, escapes, states, need)
+        out["equals_host_form"] = bool(np.array_equal(np.diff(h_off.astype(np.int64)), kept) and int(h_pos[S]) == out_bytes and
+                                       np.array_equal(h_out[:out_bytes], d_out[:out_bytes].cpu().numpy()) and
+                                       np.array_equal(states, work[0].cpu().numpy()))
+        assert out["equals_host_form"], "the call's records differ from mi355_cwire_despeckle_host's"
+    fig = report(out, times, "_us_per_stream", spread=True)
+    # the expectation, judged without the allowance for the N/24 bitmap pass (bitmap_pass_bytes_per_stream says how large it is)
+    out["despeckle_over_budget"], out["despeckle_no_slower_than_budget"] = versus(fig, "despeckle", "budget")
+    core.close()
+    return out
+
+
 # ---- the command line: one entry per --legs value that runs alone
 def ints(text):
     return [int(v) for v in text.split(",")]
@@ -1584,6 +1659,9 @@ LEGS = {
                           ("decode_no_slower_than_coalesce", "decode no slower than coalesce at every point", "decode slower than coalesce at some point")]),
     "mosaic": dict(run=run_mosaic, points=lambda a: grid(S=ints(a.streams), T=(1, 16), kind=KINDS), bench="multi_mosaic"),
     "budget": dict(run=run_budget, points=lambda a: grid(S=ints(a.streams)), bench="multi_budget", input=True),
+    "despeckle": dict(run=run_despeckle, points=lambda a: grid(S=ints(a.streams), kind=KINDS), bench="multi_despeckle",
+                      verdict=[("despeckle_no_slower_than_budget", "despeckle no slower than budget at every point",
+                                "despeckle slower than budget at some point")]),
     "activity": dict(run=run_activity, points=activity_points, bench="multi_activity",
                      verdict=[("no_slower_than_burst_apply", "no slower than burst_apply at every point", "slower than burst_apply at some point")]),
     "check": dict(run=run_check, points=activity_points, bench="multi_check",

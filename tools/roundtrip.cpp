@@ -11,7 +11,7 @@
 // (ActivityCheck, RecordCheck, WallCheck, ThumbViewer), that is that mode.
 //
 //   tools/roundtrip [--width W] [--height H] [--frames T] [--batch B]
-//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check] | --resync K [--burst B] | --crop X,Y,W,H [--burst K] | --mosaic CxR [--burst K] | [--burst K --coalesce] --datagram BYTES [--fec G[,K]] | --thumb K [--burst T] [--thumb-drop TICK]] [--wall K] [--runs]]
+//                   [--compact [--direct] [--gpu-client] [--per-frame] [--multi S [--budget BYTES | --despeckle NEED | --burst K [--burst-client | --coalesce]] [--activity CELL] [--check] | --resync K [--burst B] | --crop X,Y,W,H [--burst K] | --mosaic CxR [--burst K] | [--burst K --coalesce] --datagram BYTES [--fec G[,K]] | --thumb K [--burst T] [--thumb-drop TICK]] [--wall K] [--runs]]
 //   exit status 0 = all checks passed
 #include <algorithm>
 #include <cstdint>
@@ -820,6 +820,108 @@ static int run_multi_budget(int w, int h, int T, int S, long bytes) {
            "\"largest_threshold\": %d, \"records_within_budget\": true, \"states_equal_every_tick\": true, "
            "\"max_abs_error_when_still\": %d, \"wire_bytes\": %zu}\n",
            S, bytes, most, w, h, T, still + 1, thinned, largest, max_thr, max_err, sent_bytes);
+    return 0;
+}
+
+// the byte indices of the entries with a nonzero difference of the well-formed record {n, e} at rec
+static void record_indices(const uint8_t *rec, uint32_t n, uint32_t e, std::vector<uint32_t> *xs) {
+    const size_t pad = ((size_t)n + 3) & ~(size_t)3;
+    const uint8_t *code = rec + 8, *esc = code + pad, *diff = esc + 4 * (size_t)e;
+    uint64_t x = 0;
+    xs->clear();
+    for (uint32_t k = 0, r = 0; k < n; k++) {
+        uint32_t g = code[k];
+        if (g == 255) memcpy(&g, esc + 4 * (size_t)r++, 4);
+        x += (uint64_t)g + 1;
+        if (diff[k]) xs->push_back((uint32_t)(x - 1));
+    }
+}
+
+// --compact --multi S --despeckle NEED: the sender drops every camera's isolated changes before it sends a tick
+// (mi355_cwire_despeckle_cwire_batch, need = NEED for every camera), which takes its states back where it drops an entry; a host
+// client per camera applies what arrives.  Checked every tick: each client's frame equals the sender's state; records, counts and
+// states equal mi355_cwire_despeckle_host on a host copy of the tick; every sent entry's pixel has at least NEED changed pixels
+// among the 8 around it, by a plain count over the tick's own record.  After the moving input the last frames are repeated: what
+// was dropped is found again and dropped again, nothing is sent and the states stand still.
+static int run_multi_despeckle(int w, int h, int T, int S, long need_arg) {
+    Session ss(w, h);
+    const size_t n = ss.n;
+    Cameras cams(S, w, h);
+    Sender tx;
+    Receiver rcv;
+    if (tx.open(ss, S, 1) || rcv.open(ss, S, S, S)) return 1;
+    void *d_drop = ss.dev(tx.core, sizeof(uint32_t) * S), *d_ooff = ss.dev(tx.core, sizeof(uint32_t) * (S + 1));
+    void *d_opos = ss.dev(tx.core, sizeof(uint64_t) * (S + 1)), *d_out = ss.dev(tx.core, tx.cap);
+    if (!ss.ok()) return 1;
+    OK(mi355_prepare(tx.core, MI355_PREPARE_DESPECKLE));
+    if (cams.start(ss, tx, rcv, rcv.states.data())) return 1;
+    std::vector<uint32_t> counts(S), escapes(S), need(S, (uint32_t)need_arg), dropped(S), h_dropped(S), h_off(S + 1), xs_in, xs_out;
+    std::vector<uint64_t> pos(S + 1), h_pos(S + 1);
+    std::vector<uint8_t> out(tx.cap), h_out(tx.cap), h_states, changed((size_t)w * h), before;
+    size_t entries_in = 0, entries_out = 0, bytes_in = 0, bytes_out = 0, still_entries_out = 0;
+    const int still_ticks = 2;
+    for (int t = 0; t < T + still_ticks; t++) {
+        if (t < T) cams.fill(tx.frames.data(), t, 1);
+        // ---- server: one tick -> S records and their headers, then the records without their isolated changes
+        if (tx.step(1, false)) return 1;
+        for (int s = 0; s < S; s++) {
+            memcpy(&counts[s], &tx.bytes[tx.pos[s]], 4);
+            memcpy(&escapes[s], &tx.bytes[tx.pos[s] + 4], 4);
+            entries_in += counts[s];
+        }
+        bytes_in += tx.cb;
+        if (tx.get_states()) return 1;
+        h_states = tx.states;   // (the host form's copy: the states as the diff left them)
+        OK(mi355_cwire_despeckle_cwire_batch(tx.core, tx.d_cw, counts.data(), escapes.data(), tx.d_states, n, S, need.data(), d_drop, d_ooff,
+                                             d_opos, d_out, tx.cap));
+        OK(mi355_download(tx.core, pos.data(), d_opos, sizeof(uint64_t) * (S + 1)));
+        OK(mi355_download(tx.core, dropped.data(), d_drop, sizeof(uint32_t) * S));
+        if (pos[S] > tx.cap) { fprintf(stderr, "despeckled stream larger than its bound\n"); return 1; }
+        const size_t cb = (size_t)pos[S];
+        OK(mi355_download(tx.core, out.data(), d_out, cb));
+        // ---- check 1: the host form on a host copy gives the same records, counts and states
+        OK(mi355_cwire_despeckle_host(w, h, tx.bytes.data(), tx.cb, counts.data(), escapes.data(), h_states.data(), n, S, need.data(),
+                                      h_dropped.data(), h_off.data(), h_pos.data(), h_out.data(), tx.cap));
+        if (h_pos != pos || h_dropped != dropped || memcmp(h_out.data(), out.data(), cb) != 0) {
+            fprintf(stderr, "tick %d: the records differ from mi355_cwire_despeckle_host's\n", t);
+            return 1;
+        }
+        if (tx.get_states()) return 1;
+        if (same(tx.states.data(), h_states.data(), h_states.size(), "sender states != mi355_cwire_despeckle_host's", t)) return 1;
+        // ---- the pipe, the headers as read from the stream, a host client per camera
+        if (!ss.send(out.data(), rcv.rx.data(), cb) || rcv.walk(0, cb, 0, S)) return 1;
+        for (int s = 0; s < S; s++) {
+            if (host_apply(&rcv.states[(size_t)s * n], n, rcv.rx.data(), rcv.at.data(), s)) return 1;
+            // ---- check 2: every sent entry has at least NEED changed pixels around its pixel, by a plain count
+            record_indices(&tx.bytes[tx.pos[s]], counts[s], escapes[s], &xs_in);
+            record_indices(rcv.rx.data() + rcv.at[s], rcv.counts[s], rcv.escapes[s], &xs_out);
+            std::fill(changed.begin(), changed.end(), 0);
+            for (uint32_t x : xs_in) changed[x / 3] = 1;
+            for (uint32_t x : xs_out) {
+                const int p = (int)(x / 3), px = p % w, py = p / w;
+                long c = 0;
+                for (int dy = -1; dy <= 1; dy++)
+                    for (int dx = -1; dx <= 1; dx++)
+                        if ((dx || dy) && px + dx >= 0 && px + dx < w && py + dy >= 0 && py + dy < h) c += changed[(size_t)(py + dy) * w + px + dx];
+                if (c < need_arg) { fprintf(stderr, "tick %d: camera %d: byte %u was sent with %ld changed neighbours\n", t, s, x, c); return 1; }
+            }
+            if (xs_in.size() != xs_out.size() + dropped[s]) { fprintf(stderr, "tick %d: camera %d: kept + dropped != entries\n", t, s); return 1; }
+            (t < T ? entries_out : still_entries_out) += xs_out.size();
+        }
+        if (t < T) bytes_out += cb;
+        // ---- check 3: each client's frame equals the sender's state after every tick
+        if (same(tx.states.data(), rcv.states.data(), tx.states.size(), "receiver states != sender states", t)) return 1;
+        // ---- check 4, once the input stands still: so do the states
+        if (t >= T && same(tx.states.data(), before.data(), before.size(), "the states moved while the input stood still", t)) return 1;
+        before = tx.states;
+    }
+    if (still_entries_out) { fprintf(stderr, "%zu entries were sent while the input stood still\n", still_entries_out); return 1; }
+    if (ss.close()) return 1;
+    printf("{\"roundtrip\": \"ok\", \"format\": \"compact\", \"multi\": %d, \"despeckle\": %ld, \"width\": %d, \"height\": %d, \"ticks\": %d, "
+           "\"still_ticks\": %d, \"entries_in\": %zu, \"entries_out\": %zu, \"bytes_in\": %zu, \"bytes_out\": %zu, "
+           "\"equals_host_form\": true, \"sent_entries_have_neighbours\": true, \"states_equal_every_tick\": true, "
+           "\"states_stand_still\": true}\n",
+           S, need_arg, w, h, T, still_ticks, entries_in, entries_out, bytes_in, bytes_out);
     return 0;
 }
 
@@ -1995,7 +2097,7 @@ static int usage(const char *text) {
 }
 
 int main(int argc, char **argv) {
-    long w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0, activity = -1, resync = -1, wall = 0, budget = -1, datagram = -1, thumb = 0, thumb_drop = -1;
+    long w = 320, h = 180, T = 24, B = 8, multi = 0, burst = 0, activity = -1, resync = -1, wall = 0, budget = -1, datagram = -1, thumb = 0, thumb_drop = -1, despeckle = -1;
     bool compact = false, direct = false, gpu_client = false, burst_client = false, coalesce = false, per_frame = false, check = false;
     const struct { const char *name; bool *on; } flags[] = {
         {"--compact", &compact}, {"--direct", &direct}, {"--gpu-client", &gpu_client}, {"--burst-client", &burst_client},
@@ -2004,7 +2106,8 @@ int main(int argc, char **argv) {
     const struct { const char *name; long *value, least, below; } valued[] = {   // a value below `least` is taken as `below`
         {"--width", &w, any, 0}, {"--height", &h, any, 0}, {"--frames", &T, any, 0}, {"--batch", &B, any, 0}, {"--multi", &multi, any, 0},
         {"--burst", &burst, any, 0}, {"--activity", &activity, 0, 0}, {"--resync", &resync, 0, 0}, {"--wall", &wall, 1, -1},
-        {"--budget", &budget, 0, 0}, {"--datagram", &datagram, 0, 0}, {"--thumb", &thumb, 1, -1}, {"--thumb-drop", &thumb_drop, 0, -2}};
+        {"--budget", &budget, 0, 0}, {"--datagram", &datagram, 0, 0}, {"--thumb", &thumb, 1, -1}, {"--thumb-drop", &thumb_drop, 0, -2},
+        {"--despeckle", &despeckle, 0, -2}};
     int32_t crop[4] = {0, 0, 0, 0};
     bool cropped = false, crop_ok = true;
     int grid[2] = {0, 0};
@@ -2086,6 +2189,10 @@ int main(int argc, char **argv) {
     }
     if (g_runs && (!compact || !multi || datagram >= 0 || cropped || budget >= 0 || thumb || per_frame))
         return usage("--runs needs --compact --multi S, alone or with --burst K [--burst-client | --coalesce], --mosaic CxR or --resync K; not with --datagram");
+    if (despeckle != -1 && (despeckle < 0 || despeckle > 8 || !compact || !multi || burst || direct || gpu_client || per_frame || budget >= 0 ||
+                            coalesce || burst_client || activity || check || resync >= 0 || wall || cropped || mosaic || datagram >= 0 || thumb ||
+                            g_runs))
+        return usage("--despeckle NEED needs 0 <= NEED <= 8 and --compact --multi S alone");
     if (per_frame) {
         if (!compact || direct || gpu_client || multi) return usage("--per-frame needs --compact alone");
         return run_per_frame(w, h, T);
@@ -2099,6 +2206,7 @@ int main(int argc, char **argv) {
     if (datagram >= 0) return run_multi_datagram(w, h, T, multi, coalesce ? burst : 0, datagram, fec[0], fec[1]);
     if (coalesce) return run_multi_burst_coalesce(w, h, T, multi, burst);
     if (budget >= 0) return run_multi_budget(w, h, T, multi, budget);
+    if (despeckle >= 0) return run_multi_despeckle(w, h, T, multi, despeckle);
     if (burst && !burst_client) return run_multi_burst(w, h, T, multi, burst);
     return run_multi(w, h, T, multi, burst, activity, check, wall);   // (burst == 0: tick by tick)
 }
