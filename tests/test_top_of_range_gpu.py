@@ -27,6 +27,15 @@ this table):
       k_apply_multi_wire                                                                                           test_wall_gpu, test_batch_seams_gpu
     k_apply_multi_strided, k_apply_multi_show          grid.y = min(nstreams, 65535)  65536 streams (a loop in y)  test_counts_apply_multi_stream
     k_merge_index, k_merge_parts                       grid.x = nframes (/ 256)       none                         test_batch_seams_gpu
+    k_cwr_scan, k_cwr_dscan                            grid.x = records; 256 chunks   257 chunks (n > 2^20) /      test_runs_despeckle_seams_gpu.test_records_past_the_chunk_and_workgroup_rounds,
+                                                       or workgroups / round          r > 262 144 runs             test_every_byte_runs_encode (513 chunks), test_runs_despeckle_seams_gpu.test_link_positions_past_4_gib
+    k_cwr_place                                        256 records / round            257 records                  test_runs_despeckle_seams_gpu.test_records_past_the_place_rounds (257, 513), test_every_byte_runs_encode
+    k_cwr_table                                        64 records by value            65 records                   test_cwire_runs_gpu (130), test_runs_despeckle_seams_gpu.test_records_past_the_place_rounds
+    k_cws_table                                        128 records by value           129 records                  test_split_seams_gpu (145 records)
+    k_dsp_init                                         128 streams by value;          129 streams;                 test_runs_despeckle_seams_gpu.test_streams_past_the_init_launches (129, 257),
+                                                       grid.y = nwords / 4096 + 1     nwords 4096                  test_runs_despeckle_seams_gpu.test_a_sparse_call_between_two_dense_ones (2 and 3 blocks)
+    k_dsp_mark, k_dsp_keep, k_dsp_facts, k_dsp_emit    grid = tiles or words x        none: one grid               test_runs_despeckle_seams_gpu.test_streams_past_the_init_launches,
+                                                       nstreams                                                    test_cwire_despeckle_gpu
 The three expansion kernels take the whole batch as ONE grid y dimension, 65536 and 65537 included: the runtime accepts such a
 grid (its limit is 2^32 work-items per dimension, and y counts single work-groups here), which test_counts_* pin.
 Frames come from a pool of 251 pictures (251 divides neither 65535 nor 65536), frames from index 65535 on from a second pool:
@@ -43,7 +52,8 @@ Part 3, totals and positions.  The same shape at T = 1100 with every byte of eve
 bit 31 set), xs past 8 GiB, plain-wire positions past 2^32, compact-record positions past 2^32 from record 1023 on.  The
 reference is a plain statement (every_byte_reference; the host file checks it against pyoracle and cwire_spec at T = 4);
 expected buffers are built on the device and compared there in slices of at most 1 GiB (gpu_util.BigGuarded,
-gpu_util.assert_same_on_device).
+gpu_util.assert_same_on_device).  The consumers of compact records (CONSUMERS) each read that 4.6 GB record buffer; the run-code
+pair also writes and reads it as a link of 2.3 GB in the run form, made from runs_spec.to_runs of the zero-difference template.
 
 Every output lies in a guarded buffer that starts as a non-zero pattern, inputs are asserted unchanged, and every expected
 value comes from oracle/pyoracle.py, tests/cwire_spec.py and po.wire_pack."""
@@ -55,6 +65,7 @@ import torch
 
 import crop_spec as crop
 import cwire_spec as spec
+import runs_spec as rs
 from cudavideostream_amd import lib, state_tiles
 from oracle import pyoracle as po
 from gpu_util import DEV, BigGuarded, CUDACore, Guarded, Region, assert_same_on_device, to_dev
@@ -819,10 +830,14 @@ CONSUMERS = {
     "mi355_cwire_crop_cwire_batch": "test_every_byte_crop",
     "mi355_cwire_activity_batch": "test_every_byte_activity",
     "mi355_cwire_touched_tiles_batch": "test_every_byte_touched_tiles",
+    "mi355_cwire_runs_encode_batch": "test_every_byte_runs_encode",
 }
 CONSUMERS_EXCLUDED = {
     "mi355_apply_multi_cwire_batch": "one record per stream (4.2 MB each: positions stay far below 2^32 for any accepted count); the directory kernels of mi355_apply_multi_stream_cwire_batch",
     "mi355_cwire_budget_cwire_batch": "one record per stream, as above; the directory kernels of mi355_cwire_coalesce_cwire_batch",
+    "mi355_cwire_despeckle_cwire_batch": "one record per stream, as above: positions stay far below 2^32; the budget call's directory and tail",
+    "mi355_cwire_split_cwire_batch": "NOT run past 2^32 yet: it reads its records through the chunk table (cwa_sections) that mi355_cwire_check_batch "
+                                     "and mi355_cwire_runs_encode_batch run on this buffer, but its own 64-bit piece positions stay below 2^32 in every test",
 }
 
 
@@ -1046,4 +1061,91 @@ def test_every_byte_touched_tiles(dense_records):
         core.cwire_touched_tiles_batch(r.ptr, r.counts, r.escapes, S, K, mask.ptr)
         core.synchronize()
     assert_equal(mask.get().view(np.uint32), want.reshape(-1), "the tile mask")
+    r.check()
+
+
+@functools.lru_cache(maxsize=None)
+def runs_template():
+    """(the run form of templates()' compact record as bytes, r) from runs_spec.to_runs: everything but the differences of any
+    record of Part 3 on the link -- header, gap[], len[] -- with the differences, all 0 here, in the last N bytes."""
+    run, r = rs.to_runs(templates()[1])
+    run = np.frombuffer(run, np.uint8)
+    q = spec.pad4(r)
+    gap, ln = run[12:12 + r], run[12 + q:12 + q + r]
+    assert run.size == rs.runs_frame_bytes(N, 0, r) == 12 + 2 * q + N and rs.smaller(N, r), "the run form is the smaller one"
+    assert not gap.any() and (ln[:-1] == 255).all() and int(ln[-1]) == (N - 1) % 256 == 31, "runs of 256 entries and one of 32"
+    assert (r, run.size) == (8204, 2116420) and -(-N // 4096) == 513, "513 chunks: three rounds of k_cwr_scan"
+    assert not run[run.size - N:].any() and 1100 * run.size < 1 << 32
+    run.setflags(write=False)
+    return run, r
+
+
+def link_rows(big, T, RUN):
+    return big.t[:T * RUN].view(T, RUN)
+
+
+def assert_link_on_device(rows, r, head, what):
+    """rows [T][RUN] against the template's head and the differences of the dense records, in slices."""
+    RUN = rows.shape[1]
+    for a, b in slices(r.T, RUN):
+        assert_rows_on_device(rows[a:b, :RUN - N], head, f"{what}: header, gap and len", a)
+        assert_rows_on_device(rows[a:b, RUN - N:], r.rows[a:b, REC - N:], f"{what}: diff", a, RUN - N)
+
+
+def test_every_byte_runs_encode(dense_records):
+    """mi355_cwire_runs_encode_batch, RUNS_WHERE_SMALLER: input positions pass 2^32 at record 1023, every record is 513 chunks;
+    every form row is {1, N, 0, 8204}, pos[b] = 2 116 420 b, a record is the template's header, gap[] and len[] and then the
+    compact record's differences; compared on the device."""
+    r = dense_records
+    T = r.T
+    run_t, nr = runs_template()
+    RUN = run_t.size
+    require(log_bytes(T, 1) + BigGuarded.bytes_needed(T * RUN + 64) + (3 << 30))
+    forms, pos, out = Guarded(4 * T, I32), Guarded(T + 1, I64), BigGuarded(T * RUN + 64)
+    try:
+        with consumer_core() as core:
+            torch.cuda.synchronize()
+            core.cwire_runs_encode_batch(r.ptr, r.counts, r.escapes, T, lib.RUNS_WHERE_SMALLER, forms.ptr, pos.ptr, out.ptr, T * RUN + 64)
+            core.synchronize()
+        assert_equal(forms.get().view(np.uint32), np.tile(np.array([1, N, 0, nr], np.uint32), T), "forms")
+        assert_equal(pos.get().view(np.uint64), RUN * np.arange(T + 1, dtype=np.uint64), "pos")
+        out.check(written=T * RUN)
+        assert_link_on_device(link_rows(out, T, RUN), r, to_dev(run_t[:RUN - N]), "the link")
+    finally:
+        out.free()
+    r.check()
+
+
+def test_every_byte_runs_decode(dense_records):
+    """mi355_cwire_runs_decode_batch twice: the link of the 1100 records in the run form (built here from the template and the
+    records' differences; output positions pass 2^32) and the dense buffer itself under an all-compact table (input and output
+    positions both pass 2^32 on the copy path).  Both give the dense records, compared on the device."""
+    r = dense_records
+    T = r.T
+    run_t, nr = runs_template()
+    RUN = run_t.size
+    require(log_bytes(T, 1) + BigGuarded.bytes_needed(T * RUN) + BigGuarded.bytes_needed(T * REC) + (3 << 30))
+    link, out = BigGuarded(T * RUN), BigGuarded(T * REC)
+    try:
+        rows, head = link_rows(link, T, RUN), to_dev(run_t[:RUN - N])
+        for a, b in slices(T, RUN):
+            rows[a:b, :RUN - N] = head
+            rows[a:b, RUN - N:] = r.rows[a:b, REC - N:]
+        back = out.t.view(T, REC)
+        with consumer_core() as core:
+            for form, src in ((1, link), (0, r.g)):
+                table = np.tile(np.array([form, N, 0, nr], np.uint32), (T, 1))
+                fpos = Guarded(T + 1, I64)
+                out.buf.fill_(out.fill)
+                torch.cuda.synchronize()
+                core.cwire_runs_decode_batch(src.ptr, table, T, fpos.ptr, out.ptr, T * REC)
+                core.synchronize()
+                assert_equal(fpos.get().view(np.uint64), REC * np.arange(T + 1, dtype=np.uint64), f"form {form}: frame_pos")
+                out.check()
+                for a, b in slices(T, REC):
+                    assert_rows_on_device(back[a:b], r.rows[a:b], f"form {form}: the records", a)
+        link.check()
+        assert_link_on_device(rows, r, head, "the link is only read")
+    finally:
+        link.free(), out.free()
     r.check()

@@ -164,6 +164,20 @@ def test_the_plain_statement_equals_the_oracle_at_four_frames():
     top.every_byte_seams(top.T_LOW)
 
 
+def test_the_run_form_template_is_the_spec():
+    """runs_template asserts its figures from runs_spec.to_runs; a record of Part 3 with real differences is the template's head
+    and then those differences, and decodes to the compact record -- what test_every_byte_runs_* compare with on the device."""
+    import runs_spec as rs
+    run_t, r = top.runs_template()
+    rec_t = top.templates()[1]
+    diff = top.every_byte_frame(1) - top.every_byte_frame(0)
+    rec = np.concatenate([rec_t[:top.REC - top.N], diff])
+    run, r2 = rs.to_runs(rec)
+    assert r2 == r and run == np.concatenate([run_t[:run_t.size - top.N], diff]).tobytes() and rs.from_runs(run) == rec.tobytes()
+    forms, pos, link = rs.encode(np.concatenate([rec, rec_t]), 2, rs.WHERE_SMALLER)
+    assert forms.tolist() == [[1, top.N, 0, r]] * 2 and pos.tolist() == [0, run_t.size, 2 * run_t.size]
+
+
 def test_bands_differ_by_more_than_the_threshold():
     x = np.arange(top.N, dtype=np.int64)
     f = [top.band(t, x) for t in (0, 1, 2, 549, 1098, 1099)]
@@ -257,13 +271,17 @@ def test_the_consumer_table_is_complete():
     text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mi355diff.h")).read()
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     readers = [m.group(1) for m in re.finditer(r"\b(mi355_\w+)\s*\(([^;{}]*?)\)\s*;", text)
-               if re.search(r"const\s+void\s*\*\s*d_cwire\b", m.group(2)) or re.search(r"const\s+uint8_t\s*\*\s*d_cwire\b", m.group(2))]
+               if re.search(r"const\s+void\s*\*\s*d_cwire(_in)?\b", m.group(2)) or re.search(r"const\s+uint8_t\s*\*\s*d_cwire(_in)?\b", m.group(2))]
     listed = set(top.CONSUMERS) | set(top.CONSUMERS_EXCLUDED)
-    assert len(readers) >= 8, readers
+    assert len(readers) >= 13 and {"mi355_cwire_runs_encode_batch", "mi355_cwire_despeckle_cwire_batch"} <= set(readers), readers
     for name in top.CONSUMERS:
         assert callable(getattr(top, top.CONSUMERS[name])), name
     covered_elsewhere = {"mi355_cwire_coalesce_batch": "the arrays form of the coalescer: mi355_cwire_coalesce_cwire_batch's kernels with another sink",
-                         "mi355_cwire_crop_batch": "the arrays form of the crop: mi355_cwire_crop_cwire_batch's kernels with another sink"}
+                         "mi355_cwire_crop_batch": "the arrays form of the crop: mi355_cwire_crop_cwire_batch's kernels with another sink",
+                         "mi355_cwire_mosaic_cwire_batch": "test_top_of_range_mosaic_gpu.test_every_byte_mosaic, on the same buffer",
+                         "mi355_cwire_mosaic_batch": "the arrays form of the mosaic: mi355_cwire_mosaic_cwire_batch's kernels with another sink"}
+    import test_top_of_range_mosaic_gpu
+    assert callable(test_top_of_range_mosaic_gpu.test_every_byte_mosaic)
     for name in readers:
         assert name in listed or name in covered_elsewhere, f"{name} reads compact records and is neither run on the large buffer nor excluded"
 
@@ -279,13 +297,13 @@ def test_the_launcher_table_is_complete():
     doc = top.__doc__
     table = doc[doc.index("kernel (launcher)"):doc.index("The three expansion kernels")]
     named = set(re.findall(r"\bk_\w+\*?", table))
-    sized = re.compile(r"\b(nframes|nstreams|nrecords|ns|nf|cnt|tiles|grid|g)\b")
+    sized = re.compile(r"\b(nframes|nstreams|nrecords|ns|nf|cnt|tiles|grid|g|per_record|per_tile|per_word|part|nr)\b")
     seen = set()
     for path in sorted(glob.glob(os.path.join(root, "cudavideostream_amd", "csrc", "*.hip"))):
         text = open(path).read()
         for m in re.finditer(r"hipLaunchKernelGGL\(\s*\(?\s*(k_\w+)(.*?), 0, s\b", text, flags=re.S):
             kernel, grid = m.group(1), m.group(2).split("dim3(256)")[0].split("dim3(64)")[0]
-            if not sized.search(grid) and kernel not in ("k_cwire_place", "k_cwc_place", "k_cwire_scan"):
+            if not sized.search(grid) and kernel not in ("k_cwire_place", "k_cwc_place", "k_cwr_place", "k_cwire_scan"):
                 continue
             seen.add(kernel)
             if os.path.basename(path) == "filters.hip":
@@ -293,8 +311,14 @@ def test_the_launcher_table_is_complete():
             assert kernel in named or any(k.endswith("*") and kernel.startswith(k[:-1]) for k in named), \
                 f"{kernel} ({os.path.basename(path)}) is launched on a grid sized by a count and the table does not name it"
     assert {"k_expand", "k_expand_cwire", "k_cwire_items", "k_scan_groups", "k_diff_pack", "k_apply_multi_strided"} <= seen
+    assert {"k_cwr_scan", "k_cwr_dscan", "k_cwr_place", "k_cwr_table", "k_cws_table", "k_dsp_init", "k_dsp_mark", "k_dsp_keep",
+            "k_dsp_facts", "k_dsp_emit"} <= seen, "the launches of the run-code, split and despeckle calls are read"
     assert "filters.hip" in table and "for_frame_grids" in open(os.path.join(root, "cudavideostream_amd", "csrc", "filters.hip")).read()
     for name in set(re.findall(r"\btest_counts_\w+", table)):
         assert callable(getattr(top, name)), name
     for name in set(re.findall(r"\b(test_\w+_gpu)\b", table)):
         assert os.path.exists(os.path.join(root, "tests", name + ".py")), name
+    for module, name in set(re.findall(r"\b(test_\w+_gpu)\.(test_\w+)", table)):
+        assert callable(getattr(__import__(module), name)), (module, name)
+    for name in set(re.findall(r"(?<![.\w])test_every_byte_\w+", table)):
+        assert callable(getattr(top, name)), name
