@@ -66,7 +66,8 @@ import torch
 import crop_spec as crop
 import cwire_spec as spec
 import runs_spec as rs
-from cudavideostream_amd import lib, state_tiles
+import split_spec
+from cudavideostream_amd import cwire_split_bytes_max, cwire_split_host, cwire_split_pieces_max, lib, state_tiles
 from oracle import pyoracle as po
 from gpu_util import DEV, BigGuarded, CUDACore, Guarded, Region, assert_same_on_device, to_dev
 from test_activity_gpu import oracle as activity_oracle
@@ -831,13 +832,12 @@ CONSUMERS = {
     "mi355_cwire_activity_batch": "test_every_byte_activity",
     "mi355_cwire_touched_tiles_batch": "test_every_byte_touched_tiles",
     "mi355_cwire_runs_encode_batch": "test_every_byte_runs_encode",
+    "mi355_cwire_split_cwire_batch": "test_every_byte_split",
 }
 CONSUMERS_EXCLUDED = {
     "mi355_apply_multi_cwire_batch": "one record per stream (4.2 MB each: positions stay far below 2^32 for any accepted count); the directory kernels of mi355_apply_multi_stream_cwire_batch",
     "mi355_cwire_budget_cwire_batch": "one record per stream, as above; the directory kernels of mi355_cwire_coalesce_cwire_batch",
     "mi355_cwire_despeckle_cwire_batch": "one record per stream, as above: positions stay far below 2^32; the budget call's directory and tail",
-    "mi355_cwire_split_cwire_batch": "NOT run past 2^32 yet: it reads its records through the chunk table (cwa_sections) that mi355_cwire_check_batch "
-                                     "and mi355_cwire_runs_encode_batch run on this buffer, but its own 64-bit piece positions stay below 2^32 in every test",
 }
 
 
@@ -1148,4 +1148,68 @@ def test_every_byte_runs_decode(dense_records):
         assert_link_on_device(rows, r, head, "the link is only read")
     finally:
         link.free(), out.free()
+    r.check()
+
+
+SPLIT_M = 65536
+
+
+@functools.lru_cache(maxsize=None)
+def split_template():
+    """One record of Part 3 (the entries arange(N), all differences 0) split at SPLIT_M by mi355_cwire_split_host, and held to
+    split_spec's rule -> (pos int64[pieces + 1], [(a, b)] the entries of each piece, the pieces' bytes).  Every record of the
+    buffer has these entries, so this is the layout of every record's pieces; only the differences, the last b - a bytes of a
+    piece, change."""
+    rec = templates()[1]
+    counts, escapes = dense_headers(1)
+    first, pos, out = cwire_split_host(rec, counts, escapes, N, SPLIT_M)
+    P = int(first[1])
+    pos = pos[:P + 1].astype(np.int64)
+    cuts = split_spec.cuts(np.arange(N, dtype=np.int64), SPLIT_M)
+    assert len(cuts) == P and int(pos[0]) == 0
+    for p, (a, b) in enumerate(cuts):
+        assert (b - a) % 4 == 0 and int(pos[p + 1] - pos[p]) == split_spec.piece_bytes(np.arange(a, b), 0, b - a) <= SPLIT_M, p
+        assert bytes(out[int(pos[p]):int(pos[p + 1])]) == spec.encode_frame(np.arange(a, b), np.zeros(b - a, np.uint8)), p
+    assert any(a % split_spec.BLOCK == 0 and a for a, _ in cuts) and sum(b - a for a, b in cuts) == N
+    assert P <= cwire_split_pieces_max(N, 0, SPLIT_M) and int(pos[P]) <= cwire_split_bytes_max(N, 0, SPLIT_M)
+    out = out[:int(pos[P])].copy()
+    out.setflags(write=False)
+    return pos, cuts, out
+
+
+def test_every_byte_split(dense_records):
+    """mi355_cwire_split_cwire_batch at max_bytes 65536: input positions pass 2^32 at record 1023, and the call's own 64-bit piece
+    positions pass 2^32 between two pieces of record 1022.  piece_first is (pieces per record) * arange, piece_pos the template's
+    scan plus (bytes out per record) * the record's index, a piece is the template's header, codes and escape and then the matching
+    slice of its record's differences; compared on the device."""
+    r = dense_records
+    T = r.T
+    tpos, cuts, tout = split_template()
+    P, OUT = len(cuts), int(tpos[-1])
+    piece_cap, cap = T * cwire_split_pieces_max(N, 0, SPLIT_M), T * cwire_split_bytes_max(N, 0, SPLIT_M)
+    want_pos = (OUT * np.arange(T, dtype=np.int64)[:, None] + tpos[None, :P]).reshape(-1)
+    want_pos = np.append(want_pos, T * OUT).astype(np.uint64)
+    cross = int(np.searchsorted(want_pos, 1 << 32))
+    assert 0 < cross % P and want_pos[cross - 1] < 1 << 32 <= want_pos[cross], "piece_pos passes 2^32 inside a record's pieces"
+    assert T * P <= piece_cap and T * OUT <= cap and (T - 1) * REC >= 1 << 32
+    require(log_bytes(T, 1) + BigGuarded.bytes_needed(cap) + (3 << 30))
+    first, pos, out = Guarded(T + 1, I32), Guarded(piece_cap + 1, I64), BigGuarded(cap)
+    try:
+        with consumer_core() as core:
+            torch.cuda.synchronize()
+            core.cwire_split_cwire_batch(r.ptr, r.counts, r.escapes, T, SPLIT_M, first.ptr, pos.ptr, piece_cap, out.ptr, cap)
+            core.synchronize()
+        assert_equal(first.get().view(np.uint32), (P * np.arange(T + 1)).astype(np.uint32), "piece_first")
+        assert_equal(pos.get(written=T * P + 1)[:T * P + 1].view(np.uint64), want_pos, "piece_pos")
+        out.check(written=T * OUT)
+        rows = out.t[:T * OUT].view(T, OUT)
+        for p, (a, b) in enumerate(cuts):
+            at, end = int(tpos[p]), int(tpos[p + 1])
+            head = to_dev(tout[at:end - (b - a)])
+            for lo, hi in slices(T, OUT):
+                assert_rows_on_device(rows[lo:hi, at:end - (b - a)], head, f"piece {p} of every record: header, codes, escape", lo, at)
+                assert_rows_on_device(rows[lo:hi, end - (b - a):end], r.rows[lo:hi, REC - N + a:REC - N + b],
+                                      f"piece {p} of every record: diff", lo, end - (b - a))
+    finally:
+        out.free()
     r.check()

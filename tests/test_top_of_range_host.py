@@ -178,6 +178,24 @@ def test_the_run_form_template_is_the_spec():
     assert forms.tolist() == [[1, top.N, 0, r]] * 2 and pos.tolist() == [0, run_t.size, 2 * run_t.size]
 
 
+def test_the_split_template_is_the_spec():
+    """split_template asserts its layout from split_spec's rule; a record of Part 3 with real differences splits into the
+    template's heads, each followed by the matching slice of those differences -- what test_every_byte_split compares with on
+    the device -- and the piece positions of the 1100 records pass 2^32 inside record 1022."""
+    from cudavideostream_amd import cwire_split_host
+    tpos, cuts, tout = top.split_template()
+    diff = top.every_byte_frame(1) - top.every_byte_frame(0)
+    rec = np.concatenate([top.templates()[1][:top.REC - top.N], diff])
+    first, pos, out = cwire_split_host(rec, *top.dense_headers(1), top.N, top.SPLIT_M)
+    assert int(first[1]) == len(cuts) and np.array_equal(pos[:len(cuts) + 1].astype(np.int64), tpos)
+    for p, (a, b) in enumerate(cuts):
+        at, end = int(tpos[p]), int(tpos[p + 1])
+        assert np.array_equal(out[at:end - (b - a)], tout[at:end - (b - a)]) and np.array_equal(out[end - (b - a):end], diff[a:b]), p
+    OUT = int(tpos[-1])
+    r, inside = divmod(1 << 32, OUT)
+    assert r == 1022 < top.T_LOW and 0 < int(np.searchsorted(tpos, inside)) < len(cuts)
+
+
 def test_bands_differ_by_more_than_the_threshold():
     x = np.arange(top.N, dtype=np.int64)
     f = [top.band(t, x) for t in (0, 1, 2, 549, 1098, 1099)]
